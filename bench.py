@@ -6,6 +6,8 @@ spatial metric + arc-cosine kernel build + Cholesky(K~) + Cholesky(V) + solves +
 analytic gradients.
 
     python bench.py --gpus 1 --steps 10 --warmup 2                     # headline (BASELINE configs[2])
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full              # + roofline, in-flight leg, CPU baseline
+    python bench.py --steps 10 --dump-outputs bench_outputs            # + the last timed step's results as .npy
     python bench.py --config n4096                                      # configs[1]: N=4096, d=128
     python bench.py --config cells64                                    # configs[3]: 64 cells x N=4096, sharded
     python bench.py --config thetagrid                                  # configs[4]: 512 theta x N=8192, fp32
@@ -17,6 +19,12 @@ scaling); cells64 / thetagrid: the 64 cells / 512 theta points are sharded cycli
 (strong scaling: one step = one pass over all units).  The shared stimulus matrix X is generated on
 rank 0 and broadcast once outside the timed region (thetagrid also broadcasts r, m, V:
 multi.broadcast_state); there is no collective on the data path.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line (metric, value, unit, dtype, ms_per_step, ...).
+Everything else -- the live roofline of the dominant launch and its profiled evaluations, the leg with independent
+cells in flight, the CPU baseline, the fp64 accuracy sweep of the reduced-precision theta grid -- runs only with
+--full.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64); the inputs are
+seeded, so two builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -123,6 +131,32 @@ def clamp_groups(args, n_local):
         args.sets = max(1, min(args.sets, -(-max(1, n_local) // args.group)))
 
 
+def step_arrays(res, table=None):
+    """What a caller of the timed path receives from one step, as float64 arrays by name: the result table of a
+    sharded configuration (one row per unit: loss, then the gradient in syn.THETA_KEYS order), otherwise the result
+    dict of the evaluation (scalars as 0-d arrays, `grad` as a vector in syn.THETA_KEYS order)."""
+    if table is not None:
+        return {"results": table.detach().cpu().numpy().astype(np.float64)}
+    out = {}
+    for k, v in res.items():
+        if k == "grad":
+            out[k] = np.array([float(v[key]) for key in syn.THETA_KEYS], dtype=np.float64)
+        elif isinstance(v, torch.Tensor):
+            out[k] = v.detach().cpu().numpy().astype(np.float64)
+        elif isinstance(v, (bool, int, float)):
+            out[k] = np.asarray(float(v), dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"outputs of one step are {total} bytes, over the 64 MiB budget of --dump-outputs"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {path}: {', '.join(sorted(arrays))} ({total} bytes)")
+
+
 def build_V(X, grid, th0, dev):
     """V = K~(theta0)/2 (SPD by construction).  Setup only, outside the timed
     region; uses the library's own kernel-build entry point."""
@@ -221,6 +255,22 @@ def projected_report(args, eng, step, res, N, d, ntilde, n_kept, ms_per_step, un
     """JSON line of --config trunc / sparse: the B-projected closure (utils.py:2047-2099) at the reference's default
     EIGVAL_TOL.  Executed flops and per-family times from HIP events around every GEMM / Gram launch of one more
     evaluation; roofline of the largest 128-tile launch (K_b = K B or the lift W = (.) B^T, 2 N n_t n flops each)."""
+    out = {
+        "metric": ("GP fits/sec, B-projected (truncated-rank) M-step closure at the reference's default EIGVAL_TOL, "
+                   f"N={N} d={d}, {n_kept} of {ntilde} eigen-directions kept") if ntilde == N else
+                  (f"GP fits/sec, sparse M-step closure n_t={N} n_tilde={ntilde} d={d} at the reference's default EIGVAL_TOL, "
+                   f"{n_kept} eigen-directions kept"),
+        "value": round(units_per_s, 4), "unit": "fits/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"{args.config}: n_t={N} n_tilde={ntilde} d={d} f64, one evaluation of the B-projected closure "
+                               f"(utils.py:2047-2099) with 6 gradients, basis B[{ntilde} x {n_kept}] fixed (as during an M-step)",
+                   "N": N, "d": d, "n_tilde": ntilde, "n_kept": n_kept, "units_per_step": world,
+                   "parallelism": f"independent units over {world} GPU(s), one process per GPU, no data-path collective"},
+        "loss": res["loss"],
+    }
+    if not args.full:
+        return out
     eng.set_profile(1)
     step()
     prof = eng.get_profile()
@@ -261,20 +311,7 @@ def projected_report(args, eng, step, res, N, d, ntilde, n_kept, ms_per_step, un
         # written and read once (n~^2 doubles each), the N x nb panels a few times -- against the time at 8 TB/s
         "hbm_floor_ms": round((8.0 * ntilde * ntilde * 8 + 10.0 * N * nb * 8) / 8e12 * 1e3, 3),
     }
-    out = {
-        "metric": ("GP fits/sec, B-projected (truncated-rank) M-step closure at the reference's default EIGVAL_TOL, "
-                   f"N={N} d={d}, {n_kept} of {ntilde} eigen-directions kept") if ntilde == N else
-                  (f"GP fits/sec, sparse M-step closure n_t={N} n_tilde={ntilde} d={d} at the reference's default EIGVAL_TOL, "
-                   f"{n_kept} eigen-directions kept"),
-        "value": round(units_per_s, 4), "unit": "fits/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"{args.config}: n_t={N} n_tilde={ntilde} d={d} f64, one evaluation of the B-projected closure "
-                               f"(utils.py:2047-2099) with 6 gradients, basis B[{ntilde} x {n_kept}] fixed (as during an M-step)",
-                   "N": N, "d": d, "n_tilde": ntilde, "n_kept": n_kept, "units_per_step": world,
-                   "parallelism": f"independent units over {world} GPU(s), one process per GPU, no data-path collective"},
-        "loss": res["loss"], "roofline": roofline,
-    }
+    out["roofline"] = roofline
     if world == 1 and not args.no_cpu_baseline:
         from oracle import gp_oracle as orc
         cores = host_cores()
@@ -330,7 +367,15 @@ def main():
                     help="f64 = the reference's precision; mixed = fp64 factorisations and loss, fp32 gradient products "
                          "(the theta-grid configuration's default: the all-fp32 instance misses the 1e-5 bar on part of "
                          "the lattice); f32 = every matrix in fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the live roofline (profiled "
+                         "evaluations), the leg with independent cells in flight, the CPU baseline, the fp64 accuracy "
+                         "sweep of a reduced-precision theta grid")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.depth_given = args.depth is not None
     if args.depth is None:
         args.depth = 3   # measured optimum for both configs this round (cells64: 148 / 183 / 168 / 166 / 168 cells/s at 2..6)
@@ -482,7 +527,7 @@ def main():
         rd, md, Vd = multi.broadcast_state(r0, m0, V0, N, dev, dtype=tdt)
         Vd = Vd.contiguous()
         Xd = X.to(tdt)
-        if tdt != torch.float64 and not args.no_accuracy_check:
+        if args.full and tdt != torch.float64 and not args.no_accuracy_check:
             # the all-fp32 instance is checked against fp64 evaluations of the same points after the timed region
             r64, m64, V64 = multi.broadcast_state(r0, m0, V0, N, dev, dtype=torch.float64)
             V64 = V64.contiguous()
@@ -579,8 +624,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert math.isfinite(res["loss"]), "benchmark evaluation produced a non-finite loss"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_arrays(res, table[0] if args.config == "cells64" else
+                                                    last_table[0] if args.config == "thetagrid" else None))
     accuracy = None
-    if args.config == "thetagrid" and dtype_name != "f64" and not args.no_accuracy_check:
+    if args.full and args.config == "thetagrid" and dtype_name != "f64" and not args.no_accuracy_check:
         # every lattice point of the timed sweep against its fp64 evaluation (north star: 1e-5 relative on the log
         # marginal likelihood); all ranks hold the gathered tables
         ref = reference_sweep()
@@ -604,134 +652,135 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         log(f"timed region done: {ms_per_step:.2f} ms/step (host enqueue {eng.last_enqueue_ms():.2f} ms per unit)")
         units_per_s = units_per_step * args.steps / elapsed
-        F = fits_flops(N, d)
-        # ---- roofline of the dominant kernel, measured live on one more unit of this rank:
-        #      HIP events around every launch of the GEMM family on the launching stream
-        if args.config == "cells64":
-            c0 = multi.partition(args.cells, world, rank)[0]
-            rc, mc, Vc, thc = inputs[c0]
-            probe = lambda: eng.fit_eval(thc, lower, upper, grid, X, rc, mc, Vc, logA, lam0, want_grad=want_grad, want_vectors=False)
-        elif args.config == "thetagrid":
-            probe = lambda: eng.fit_eval(points[0], lower, upper, grid, Xd, rd, md, Vd, logA, lam0, want_grad=want_grad, want_vectors=False,
-                                         grad_precision=gprec)
-        else:
-            probe = step
-        # (five profiled evaluations, their per-launch times averaged: one sample of the largest launch moves by +-4 %
-        # with the clock state the chip happens to be in; counts and flops are the same every time)
-        eng.set_profile(1)
-        profs = []
-        for _ in range(PROFILED_EVALUATIONS):
-            probe()
-            profs.append(eng.get_profile())
-        prof = {k: (sum(p_[k] for p_ in profs) / len(profs) if isinstance(profs[0][k], float) else profs[0][k]) for k in profs[0]}
-        phases = None
-        if want_grad:
-            eng.set_profile(2)
-            probe()
-            phases = eng.get_phases()
-        executed_job = None
-        if args.config == "thetagrid":
-            # the timed lattice points reuse their context's V factor: their executed flops come from a probe that does too
+        if args.full:
+            F = fits_flops(N, d)
+            # ---- roofline of the dominant kernel, measured live on one more unit of this rank:
+            #      HIP events around every launch of the GEMM family on the launching stream
+            if args.config == "cells64":
+                c0 = multi.partition(args.cells, world, rank)[0]
+                rc, mc, Vc, thc = inputs[c0]
+                probe = lambda: eng.fit_eval(thc, lower, upper, grid, X, rc, mc, Vc, logA, lam0, want_grad=want_grad, want_vectors=False)
+            elif args.config == "thetagrid":
+                probe = lambda: eng.fit_eval(points[0], lower, upper, grid, Xd, rd, md, Vd, logA, lam0, want_grad=want_grad, want_vectors=False,
+                                             grad_precision=gprec)
+            else:
+                probe = step
+            # (five profiled evaluations, their per-launch times averaged: one sample of the largest launch moves by +-4 %
+            # with the clock state the chip happens to be in; counts and flops are the same every time)
             eng.set_profile(1)
-            eng.fit_eval(points[0], lower, upper, grid, Xd, rd, md, Vd, logA, lam0, want_grad=want_grad, want_vectors=False,
-                         grad_precision=gprec, reuse_V=True)
-            pr = eng.get_profile()
-            executed_job = pr["gemm_flops"] + pr["small_gemm_flops"] + pr["gram_flops"]
-        eng.set_profile(0)
-        unit_ms = phases["end"] if phases else ms_per_step
-        gemm_tflops = prof["gemm_flops"] / (prof["gemm_ms"] * 1e-3) / 1e12 if prof["gemm_ms"] > 0 else 0.0
-        # dominant kernel = the single largest launch: T = L^-1 L_V (both operands lower triangular, lower
-        # output; algorithmic flops N^3/3): one launch per fit of
-        # gemm_epi_kernel<R, false, true, 2> (the 128-tile body on the XCD-aware schedule, gemm_sched.hip, with the
-        # tile-norm epilogue that leaves ||T||_F^2 behind; gemm_xcd_kernel<R, false, true> when GPFIT_FUSED_EPI
-        # switches that epilogue off), so its
-        # rocprofv3 kernel_stats row is this launch's average.
-        npad = -(-N // 128) * 128
-        nt = npad // 128
-        dom_flops = float(npad) ** 3 / 3.0
-        rname = "double" if dtype_name == "f64" else "float"   # the dominant launch (T) runs in fp32 in the mixed mode
-        if dtype_name == "mixed":
-            peak = FP32_MFMA_PEAK_TFLOPS
-        # Which kernel T really is depends on its tile count (gemm.hip: launch_gemm): the XCD-aware data-parallel
-        # schedule from 1536 tiles (with the tile-norm epilogue unless GPFIT_FUSED_EPI switches it off), the stream-K
-        # schedule from 384, a small-tile launch below -- where no 128-tile launch exists and nothing is reported.
-        t_tiles = nt * (nt + 1) // 2
-        fused_norm = int(os.environ.get("GPFIT_FUSED_EPI", "7")) & 2
-        if t_tiles >= 1536:
-            dom_name = f"gemm_epi_kernel<{rname}, false, true, 2>" if fused_norm else f"gemm_xcd_kernel<{rname}, false, true>"
-            dom_how = "XCD-aware macro-tile schedule"
-        elif t_tiles >= 384:
-            dom_name = f"gemm_streamk_kernel<{rname}, false, true, {2 if fused_norm else 0}>"
-            dom_how = "stream-K schedule" + (" with the tile-norm epilogue" if fused_norm else "") + "; the live figure includes its fix-up kernel"
-        else:
-            dom_name, dom_how = None, None
-        measured = prof["largest_gemm_ms"] > 0 and dom_name is not None
-        dom_tflops = dom_flops / prof["largest_gemm_ms"] / 1e9 if measured else None
-        executed = prof["gemm_flops"] + prof["small_gemm_flops"] + prof["gram_flops"]
-        # the committed PMC passes (traffic, matrix-pipe utilisation, shader clock) describe the headline run only
-        pmc_applies = measured and dtype_name == "f64" and args.config == "headline" and (N, d) == (8192, 256)
-        util = profiled_mfma_util(dom_name) if pmc_applies else None
-        traffic = profiled_traffic(dom_name, blocks=None) if pmc_applies else None
-        notes = []
-        if not measured:
-            notes.append(f"T = L^-1 L_V has {t_tiles} 128-tiles at N={N}: no 128-tile launch of its own to time (small-tile instances), "
-                         "achieved / frac are null; see gemm_family and unit_executed_frac")
-        if measured and not pmc_applies:
-            notes.append("traffic / mfma_util / clock are PMC passes of the headline run (N=8192 d=256 f64) and are not copied to other runs")
-        if dtype_name == "mixed":
-            notes.append("mixed precision: T and the other gradient products run on the fp32 MFMA (peak 157.3), the factorisations on the "
-                         "fp64 MFMA (peak 78.6); unit_executed_frac is quoted against the fp32 peak and therefore understates the fp64 half")
-        roofline = {
-            "bound": "mfma",
-            "kernel": None if dom_name is None else dom_name + " (T = L^-1 L_V, N^3/3 flops, 1 launch/fit, %s; %s)"
-                      % (dom_how, "v_mfma_f64_16x16x4_f64" if dtype_name == "f64" else "v_mfma_f32_16x16x4_f32"),
-            "note": " | ".join(notes) or None,
-            "achieved": None if dom_tflops is None else round(dom_tflops, 2), "peak": peak, "unit": "TFLOP/s",
-            "frac": None if dom_tflops is None else round(dom_tflops / peak, 4),
-            # HBM-side bytes per launch (fetch with the gfx950 correction + write) from the committed PMC passes; the
-            # algorithmic operand bytes of the launch are 3 N^2 / 2 x 8 B (two triangular inputs, one triangular output)
-            "traffic": None if traffic is None else round((traffic["fetch_corrected"] + traffic["write"]) * 1e9),
-            "traffic_detail": traffic,
-            "algorithmic_bytes_per_launch": 1.5 * float(npad) ** 2 * (8 if dtype_name == "f64" else 4),
-            "mfma_util": util,
-            "launches_per_fit": 1 if measured else 0, "avg_launch_ms": round(prof["largest_gemm_ms"], 4) if measured else None,
-            "avg_over_profiled_evaluations": PROFILED_EVALUATIONS,
-            "algorithmic_flops_per_launch": dom_flops,
-            # `peak` is the nominal-clock figure (2.4 GHz).  The PMC pass shows the shader clock this launch
-            # really ran at (the fp64 GEMMs sit near 2.07 GHz in steady state, profiles/r02_clock_probe.txt);
-            # frac_at_measured_clock prices the same launch against the matrix peak at that clock.
-            "clock": None if not (util and util.get("shader_clock_ghz")) else {
-                "shader_clock_ghz": util["shader_clock_ghz"], "nominal_ghz": NOMINAL_GHZ,
-                "peak_at_measured_clock": round(peak * util["shader_clock_ghz"] / NOMINAL_GHZ, 2),
-                "frac_at_measured_clock": round(dom_tflops / (peak * util["shader_clock_ghz"] / NOMINAL_GHZ), 4),
-                "source": util["source"]},
-            "gemm_family": {"what": "all 128-tile GEMM/SYRK/TRSM/TRTRI launches (gemm_mfma_kernel<..,128> + gemm_streamk_kernel), executed flops",
-                            "launches_per_fit": prof["gemm_launches"], "tflops": round(gemm_tflops, 2),
-                            "frac": round(gemm_tflops / peak, 4),
-                            "avg_launch_ms": round(prof["gemm_ms"] / max(1, prof["gemm_launches"]), 4)},
-            # whole unit: flops the implementation EXECUTES (2.77 N^3 formulation, tile granularity) over the
-            # unit's wall time -- the honest utilisation of the matrix peak by the unit of work
-            "flops_executed_per_fit": executed,
-            "unit_ms": round(unit_ms, 3),
-            "unit_executed_tflops": round(executed / (unit_ms * 1e-3) / 1e12, 2),
-            "unit_executed_frac": round(executed / (unit_ms * 1e-3) / 1e12 / peak, 4),
-            # configurations of many units: the unit_* fields above describe ONE unit evaluated on its own (the profiled
-            # probe); the timed job runs them in groups, and its utilisation is the same executed flops per unit times the
-            # measured units per second (all GPUs)
-            "job_executed_tflops": None if units_per_step <= 1 else round((executed_job or executed) * units_per_s / 1e12 / world, 2),
-            "job_executed_frac": None if units_per_step <= 1 else round((executed_job or executed) * units_per_s / 1e12 / world / peak, 4),
-            "job_flops_executed_per_unit": None if units_per_step <= 1 else (executed_job or executed),
-            "phases_ms": phases,
-            "gemm_ms_per_fit": round(prof["gemm_ms"], 3), "leaf_ms_per_fit": round(prof["leaf_ms"], 3),
-            "leaf_launches_per_fit": prof["leaf_launches"],
-            "small_tile_gemm": {"launches_per_fit": prof["small_gemm_launches"], "ms_per_fit": round(prof["small_gemm_ms"], 3),
-                                "tflops": round(prof["small_gemm_flops"] / max(prof["small_gemm_ms"], 1e-9) / 1e9, 2)},
-            "gram_ms_per_fit": round(prof["gram_ms"], 3),
-            # SURVEY 8(d)'s algorithmic flop count F_fit = (14/3)N^3 + ... against the flops this formulation executes:
-            # a saving of the FORMULATION (a speed-up factor), never a rate or a fraction of peak
-            "unit_algorithmic_flops": F,
-            "formulation_speedup_algorithmic_over_executed_flops": round(F / executed, 3) if executed > 0 else None,
-        }
+            profs = []
+            for _ in range(PROFILED_EVALUATIONS):
+                probe()
+                profs.append(eng.get_profile())
+            prof = {k: (sum(p_[k] for p_ in profs) / len(profs) if isinstance(profs[0][k], float) else profs[0][k]) for k in profs[0]}
+            phases = None
+            if want_grad:
+                eng.set_profile(2)
+                probe()
+                phases = eng.get_phases()
+            executed_job = None
+            if args.config == "thetagrid":
+                # the timed lattice points reuse their context's V factor: their executed flops come from a probe that does too
+                eng.set_profile(1)
+                eng.fit_eval(points[0], lower, upper, grid, Xd, rd, md, Vd, logA, lam0, want_grad=want_grad, want_vectors=False,
+                             grad_precision=gprec, reuse_V=True)
+                pr = eng.get_profile()
+                executed_job = pr["gemm_flops"] + pr["small_gemm_flops"] + pr["gram_flops"]
+            eng.set_profile(0)
+            unit_ms = phases["end"] if phases else ms_per_step
+            gemm_tflops = prof["gemm_flops"] / (prof["gemm_ms"] * 1e-3) / 1e12 if prof["gemm_ms"] > 0 else 0.0
+            # dominant kernel = the single largest launch: T = L^-1 L_V (both operands lower triangular, lower
+            # output; algorithmic flops N^3/3): one launch per fit of
+            # gemm_epi_kernel<R, false, true, 2> (the 128-tile body on the XCD-aware schedule, gemm_sched.hip, with the
+            # tile-norm epilogue that leaves ||T||_F^2 behind; gemm_xcd_kernel<R, false, true> when GPFIT_FUSED_EPI
+            # switches that epilogue off), so its
+            # rocprofv3 kernel_stats row is this launch's average.
+            npad = -(-N // 128) * 128
+            nt = npad // 128
+            dom_flops = float(npad) ** 3 / 3.0
+            rname = "double" if dtype_name == "f64" else "float"   # the dominant launch (T) runs in fp32 in the mixed mode
+            if dtype_name == "mixed":
+                peak = FP32_MFMA_PEAK_TFLOPS
+            # Which kernel T really is depends on its tile count (gemm.hip: launch_gemm): the XCD-aware data-parallel
+            # schedule from 1536 tiles (with the tile-norm epilogue unless GPFIT_FUSED_EPI switches it off), the stream-K
+            # schedule from 384, a small-tile launch below -- where no 128-tile launch exists and nothing is reported.
+            t_tiles = nt * (nt + 1) // 2
+            fused_norm = int(os.environ.get("GPFIT_FUSED_EPI", "7")) & 2
+            if t_tiles >= 1536:
+                dom_name = f"gemm_epi_kernel<{rname}, false, true, 2>" if fused_norm else f"gemm_xcd_kernel<{rname}, false, true>"
+                dom_how = "XCD-aware macro-tile schedule"
+            elif t_tiles >= 384:
+                dom_name = f"gemm_streamk_kernel<{rname}, false, true, {2 if fused_norm else 0}>"
+                dom_how = "stream-K schedule" + (" with the tile-norm epilogue" if fused_norm else "") + "; the live figure includes its fix-up kernel"
+            else:
+                dom_name, dom_how = None, None
+            measured = prof["largest_gemm_ms"] > 0 and dom_name is not None
+            dom_tflops = dom_flops / prof["largest_gemm_ms"] / 1e9 if measured else None
+            executed = prof["gemm_flops"] + prof["small_gemm_flops"] + prof["gram_flops"]
+            # the committed PMC passes (traffic, matrix-pipe utilisation, shader clock) describe the headline run only
+            pmc_applies = measured and dtype_name == "f64" and args.config == "headline" and (N, d) == (8192, 256)
+            util = profiled_mfma_util(dom_name) if pmc_applies else None
+            traffic = profiled_traffic(dom_name, blocks=None) if pmc_applies else None
+            notes = []
+            if not measured:
+                notes.append(f"T = L^-1 L_V has {t_tiles} 128-tiles at N={N}: no 128-tile launch of its own to time (small-tile instances), "
+                             "achieved / frac are null; see gemm_family and unit_executed_frac")
+            if measured and not pmc_applies:
+                notes.append("traffic / mfma_util / clock are PMC passes of the headline run (N=8192 d=256 f64) and are not copied to other runs")
+            if dtype_name == "mixed":
+                notes.append("mixed precision: T and the other gradient products run on the fp32 MFMA (peak 157.3), the factorisations on the "
+                             "fp64 MFMA (peak 78.6); unit_executed_frac is quoted against the fp32 peak and therefore understates the fp64 half")
+            roofline = {
+                "bound": "mfma",
+                "kernel": None if dom_name is None else dom_name + " (T = L^-1 L_V, N^3/3 flops, 1 launch/fit, %s; %s)"
+                          % (dom_how, "v_mfma_f64_16x16x4_f64" if dtype_name == "f64" else "v_mfma_f32_16x16x4_f32"),
+                "note": " | ".join(notes) or None,
+                "achieved": None if dom_tflops is None else round(dom_tflops, 2), "peak": peak, "unit": "TFLOP/s",
+                "frac": None if dom_tflops is None else round(dom_tflops / peak, 4),
+                # HBM-side bytes per launch (fetch with the gfx950 correction + write) from the committed PMC passes; the
+                # algorithmic operand bytes of the launch are 3 N^2 / 2 x 8 B (two triangular inputs, one triangular output)
+                "traffic": None if traffic is None else round((traffic["fetch_corrected"] + traffic["write"]) * 1e9),
+                "traffic_detail": traffic,
+                "algorithmic_bytes_per_launch": 1.5 * float(npad) ** 2 * (8 if dtype_name == "f64" else 4),
+                "mfma_util": util,
+                "launches_per_fit": 1 if measured else 0, "avg_launch_ms": round(prof["largest_gemm_ms"], 4) if measured else None,
+                "avg_over_profiled_evaluations": PROFILED_EVALUATIONS,
+                "algorithmic_flops_per_launch": dom_flops,
+                # `peak` is the nominal-clock figure (2.4 GHz).  The PMC pass shows the shader clock this launch
+                # really ran at (the fp64 GEMMs sit near 2.07 GHz in steady state, profiles/r02_clock_probe.txt);
+                # frac_at_measured_clock prices the same launch against the matrix peak at that clock.
+                "clock": None if not (util and util.get("shader_clock_ghz")) else {
+                    "shader_clock_ghz": util["shader_clock_ghz"], "nominal_ghz": NOMINAL_GHZ,
+                    "peak_at_measured_clock": round(peak * util["shader_clock_ghz"] / NOMINAL_GHZ, 2),
+                    "frac_at_measured_clock": round(dom_tflops / (peak * util["shader_clock_ghz"] / NOMINAL_GHZ), 4),
+                    "source": util["source"]},
+                "gemm_family": {"what": "all 128-tile GEMM/SYRK/TRSM/TRTRI launches (gemm_mfma_kernel<..,128> + gemm_streamk_kernel), executed flops",
+                                "launches_per_fit": prof["gemm_launches"], "tflops": round(gemm_tflops, 2),
+                                "frac": round(gemm_tflops / peak, 4),
+                                "avg_launch_ms": round(prof["gemm_ms"] / max(1, prof["gemm_launches"]), 4)},
+                # whole unit: flops the implementation EXECUTES (2.77 N^3 formulation, tile granularity) over the
+                # unit's wall time -- the honest utilisation of the matrix peak by the unit of work
+                "flops_executed_per_fit": executed,
+                "unit_ms": round(unit_ms, 3),
+                "unit_executed_tflops": round(executed / (unit_ms * 1e-3) / 1e12, 2),
+                "unit_executed_frac": round(executed / (unit_ms * 1e-3) / 1e12 / peak, 4),
+                # configurations of many units: the unit_* fields above describe ONE unit evaluated on its own (the profiled
+                # probe); the timed job runs them in groups, and its utilisation is the same executed flops per unit times the
+                # measured units per second (all GPUs)
+                "job_executed_tflops": None if units_per_step <= 1 else round((executed_job or executed) * units_per_s / 1e12 / world, 2),
+                "job_executed_frac": None if units_per_step <= 1 else round((executed_job or executed) * units_per_s / 1e12 / world / peak, 4),
+                "job_flops_executed_per_unit": None if units_per_step <= 1 else (executed_job or executed),
+                "phases_ms": phases,
+                "gemm_ms_per_fit": round(prof["gemm_ms"], 3), "leaf_ms_per_fit": round(prof["leaf_ms"], 3),
+                "leaf_launches_per_fit": prof["leaf_launches"],
+                "small_tile_gemm": {"launches_per_fit": prof["small_gemm_launches"], "ms_per_fit": round(prof["small_gemm_ms"], 3),
+                                    "tflops": round(prof["small_gemm_flops"] / max(prof["small_gemm_ms"], 1e-9) / 1e9, 2)},
+                "gram_ms_per_fit": round(prof["gram_ms"], 3),
+                # SURVEY 8(d)'s algorithmic flop count F_fit = (14/3)N^3 + ... against the flops this formulation executes:
+                # a saving of the FORMULATION (a speed-up factor), never a rate or a fraction of peak
+                "unit_algorithmic_flops": F,
+                "formulation_speedup_algorithmic_over_executed_flops": round(F / executed, 3) if executed > 0 else None,
+            }
         metric = {"headline": f"GP fits/sec (kernel+chol+solve+grad loglik) at N={N} d={d}",
                   "n4096": f"GP fits/sec (kernel+chol+solve+grad loglik) at N={N} d={d}",
                   "cells64": "cells/sec, 64 independent cells x N=4096 d=128 sharded over the GPUs",
@@ -762,17 +811,18 @@ def main():
                                          "clamped to the local share)"
                                          if args.config in ("cells64", "thetagrid") and args.group > 0 else "")},
             "loss": res["loss"],
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = roofline
         if accuracy is not None:
             out["accuracy_vs_fp64"] = accuracy
-        if world == 1 and args.config == "headline" and not args.no_in_flight:
+        if args.full and world == 1 and args.config == "headline" and not args.no_in_flight:
             # Beside `value` (evaluations of ONE cell, each waiting for the previous one, as an L-BFGS closure does):
             # what the same GPU delivers when the evaluations are independent (several cells of this size, as in
             # configs[3]) and three are kept in flight on three contexts.  Informational, never `value`.
             out["independent_units_in_flight"] = in_flight_rate(eng, N, d, X, grid, dev, tdt, lower, upper, logA, lam0,
                                                                 want_grad, gprec, local_rank)
-        if world == 1 and not args.no_cpu_baseline and dtype_name == "f64" and args.config == "headline":
+        if args.full and world == 1 and not args.no_cpu_baseline and dtype_name == "f64" and args.config == "headline":
             cores, small, full = cpu_baseline(N, d, min(args.cpu_sample_n, N), args.cpu_quick)
             scale = (N / small["n"]) ** 3
             if full is not None:

@@ -24,7 +24,7 @@ with open(os.path.join(out_dir, f"{tag}_kernel_stats.csv"), "w") as f:
         w.writerow([r["Name"], r["Calls"], f"{float(r['TotalDurationNs'])/1e6:.3f}", f"{float(r['AverageNs'])/1e3:.2f}",
                     f"{float(r['MinNs'])/1e3:.2f}", f"{float(r['MaxNs'])/1e3:.2f}", r["Percentage"]])
 
-summary = {"source": "rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline"}
+summary = {"source": "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline"}
 gemm = [r for r in stats if "gemm_mfma_kernel" in r["Name"] or "gemm_streamk_kernel" in r["Name"]]
 tot = sum(float(r["TotalDurationNs"]) for r in gemm)
 calls = sum(int(r["Calls"]) for r in gemm)
