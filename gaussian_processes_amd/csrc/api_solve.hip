@@ -5,6 +5,8 @@
 #include "gpfit_mi355x.h"
 
 #include <cmath>
+#include <string>
+#include <vector>
 
 using namespace gpfit;
 
@@ -85,7 +87,57 @@ __global__ __launch_bounds__(256) void append_write_kernel(double* __restrict__ 
     Li[(int64_t)n * ldi + n] = 1.0 / lam;
   }
 }
+
+// the pass of one evaluation on host arrays (gpfit_fparam_lbfgs_host), sums in index order
+struct FparamHostPass {
+  const double* lam_m;
+  const double* lam_var;
+  int64_t n;
+  double sr, srm;
+  double A, se, sg;
+  void pass(double logA) {
+    A = std::exp(logA);
+    se = 0.0;
+    sg = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+      const double e = std::exp(A * lam_m[i] + 0.5 * A * A * lam_var[i]);
+      se += e;
+      sg += (lam_m[i] + A * lam_var[i]) * e;
+    }
+  }
+  double lambda0_closed() const { return std::log(sr) - std::log(se); }
+  FparamValues values(double lambda0_used) const {
+    const double el0 = std::exp(lambda0_used);
+    const double sf = se * el0;
+    return FparamValues{A * srm + lambda0_used * sr - sf, A * (srm - sg * el0), sf};
+  }
+};
 }  // namespace
+
+// history of the device optimiser: 4 * history_size doubles of dynamic LDS next to the 17 of the block sums
+static const int kFparamLbfgsMaxHistory = (64 * 1024 - 256) / 32;
+
+static int fparam_lbfgs_config(const char* name, int max_iter, int history_size, double lr, double tol_grad,
+                               double tol_change, Lbfgs1dConfig* cfg) {
+  // max_iter = 0: the first evaluation only (torch's step() evaluates before its loop); a history pair is only
+  // stored from the second iteration on
+  if (max_iter < 0 || history_size < 0 || (max_iter > 1 && history_size < 1) || !(lr >= 0.0)) {
+    set_error(std::string(name) + ": bad argument (max_iter >= 0, history_size >= 1 when max_iter > 1, lr >= 0)");
+    return -3;
+  }
+  if (history_size > kFparamLbfgsMaxHistory) {
+    set_error(std::string(name) + ": history_size " + std::to_string(history_size) + " does not fit the " +
+              std::to_string(kFparamLbfgsMaxHistory) + " pairs of the workgroup's LDS");
+    return -3;
+  }
+  cfg->lr = lr;
+  cfg->tolerance_grad = tol_grad;
+  cfg->tolerance_change = tol_change;
+  cfg->max_iter = max_iter;
+  cfg->max_eval = max_iter * 5 / 4;  // torch's default max_eval
+  cfg->history_size = history_size;
+  return 0;
+}
 
 extern "C" {
 
@@ -279,6 +331,61 @@ int gpfit_fparam_eval(gpfit_ctx* c, void* stream, const double* lam_m, const dou
                        c->scal_host + 32, s));
   GP_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < 7; ++i) out_host[i] = c->scal_host[32 + i];
+  return 0;
+}
+
+int gpfit_fparam_lbfgs(gpfit_ctx* c, void* stream, const double* lam_m, const double* lam_var, const double* r,
+                       int64_t N, double logA0, int lambda0_mode, double lambda0_fixed, int max_iter,
+                       int history_size, double lr, double tol_grad, double tol_change, double* f_out,
+                       double* out_host) {
+  if (!c || !lam_m || !lam_var || !r || !out_host || N <= 0 || N > INT32_MAX) {
+    set_error("gpfit_fparam_lbfgs: bad argument");
+    return -3;
+  }
+  Lbfgs1dConfig cfg;
+  GP_TRY(fparam_lbfgs_config("gpfit_fparam_lbfgs", max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+  GP_CTX_ENTER(c, "gpfit_fparam_lbfgs");
+  hipStream_t s = (hipStream_t)stream;
+  // one launch, one wait: the nine results go straight to pinned, device-mapped scalars no other entry point uses
+  GP_TRY(launch_fparam_lbfgs(lam_m, lam_var, r, (int)N, logA0, lambda0_mode ? 1 : 0, lambda0_fixed, cfg, f_out,
+                             c->scal_host + 52, s));
+  GP_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < 9; ++i) out_host[i] = c->scal_host[52 + i];
+  return 0;
+}
+
+int gpfit_fparam_lbfgs_host(const double* lam_m, const double* lam_var, const double* r, int64_t N, double logA0,
+                            int lambda0_mode, double lambda0_fixed, int max_iter, int history_size, double lr,
+                            double tol_grad, double tol_change, double* f_out, double* out_host) {
+  if (!lam_m || !lam_var || !r || !out_host || N <= 0) {
+    set_error("gpfit_fparam_lbfgs_host: bad argument");
+    return -3;
+  }
+  Lbfgs1dConfig cfg;
+  GP_TRY(fparam_lbfgs_config("gpfit_fparam_lbfgs_host", max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+  FparamClosure<FparamHostPass> obj{};
+  obj.ev = FparamHostPass{lam_m, lam_var, N, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = 0; i < N; ++i) {
+    obj.ev.sr += r[i];
+    obj.ev.srm += r[i] * lam_m[i];
+  }
+  obj.fixed = lambda0_mode ? 1 : 0;
+  obj.lambda0_fixed = lambda0_fixed;
+  std::vector<double> hist(4 * (size_t)history_size + 1);
+  double* h = hist.data();
+  const Lbfgs1dResult res = lbfgs1d_step<Lbfgs1dHostSlots>(
+      obj, logA0, cfg, Lbfgs1dStorage{h, h + history_size, h + 2 * history_size, h + 3 * history_size});
+  double lambda0 = std::nan("");
+  if (res.status == 0) {
+    obj.ev.pass(res.x);
+    lambda0 = obj.ev.lambda0_closed();
+    if (f_out)
+      for (int64_t i = 0; i < N; ++i)
+        f_out[i] = std::exp(obj.ev.A * lam_m[i] + 0.5 * obj.ev.A * obj.ev.A * lam_var[i] + lambda0);
+  }
+  const double o[9] = {res.x, lambda0, res.first_loss, res.last_loss, (double)res.n_evals, (double)res.n_iter,
+                       (double)res.status, res.status ? obj.fail_x : 0.0, res.status ? obj.fail_lambda0 : 0.0};
+  for (int i = 0; i < 9; ++i) out_host[i] = o[i];
   return 0;
 }
 

@@ -1045,38 +1045,75 @@ int launch_unpack_tri(const double* src, int64_t lds, int n, double* dst, int64_
 //   f_i = e_i exp(lambda0)                                   (utils.py:1138)
 //   loglik = A r.lam_m + lambda0 sum r - sum f               (utils.py:1243)
 //   dloglik/dlogA = A (r.lam_m - sum (lam_m + A lam_var) f)  (utils.py:1253)
+// The pass is shared by fparam_kernel (one evaluation) and fparam_lbfgs_kernel (the whole optimiser): at equal A
+// both give the same bits.
+
+// the totals that depend on A: sum e and sum (lam_m + A lam_var) e (valid in every thread)
+__device__ __forceinline__ void fparam_sums_A(const double* __restrict__ lam_m, const double* __restrict__ lam_var,
+                                              int n, double A, double* sh, double& se, double& sg) {
+  double e_sum = 0.0, g_sum = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const double e = exp(A * lam_m[i] + 0.5 * A * A * lam_var[i]);
+    e_sum += e;
+    g_sum += (lam_m[i] + A * lam_var[i]) * e;
+  }
+  se = block_sum(e_sum, sh);
+  sg = block_sum(g_sum, sh);
+}
+
+// the totals that do not: sum r and r.lam_m (valid in every thread)
+__device__ __forceinline__ void fparam_sums_r(const double* __restrict__ lam_m, const double* __restrict__ r, int n,
+                                              double* sh, double& sr, double& srm) {
+  double r_sum = 0.0, rm_sum = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    r_sum += r[i];
+    rm_sum += r[i] * lam_m[i];
+  }
+  sr = block_sum(r_sum, sh);
+  srm = block_sum(rm_sum, sh);
+}
+
+// the rate f_i at (A, lambda0)
+__device__ __forceinline__ void fparam_rate(const double* __restrict__ lam_m, const double* __restrict__ lam_var, int n,
+                                            double A, double lambda0, double* __restrict__ f) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) f[i] = exp(A * lam_m[i] + 0.5 * A * A * lam_var[i] + lambda0);
+}
+
+// the scalars of one evaluation from the four totals
+struct FparamScalars {
+  double lambda0, loglik, dloglik, sum_f, lambda0_closed;
+};
+__device__ __forceinline__ FparamScalars fparam_scalars(double A, double se, double sg, double sr, double srm,
+                                                        int closed_form, double lambda0_in) {
+  FparamScalars v;
+  v.lambda0 = closed_form ? (log(sr) - log(se)) : lambda0_in;
+  const double el0 = exp(v.lambda0);
+  v.sum_f = se * el0;
+  v.loglik = A * srm + v.lambda0 * sr - v.sum_f;
+  v.dloglik = A * (srm - sg * el0);
+  v.lambda0_closed = log(sr) - log(se);  // closed-form lambda0 for this logA, whatever was used above
+  return v;
+}
+
 // out[0] lambda0 used, out[1] loglik, out[2] dloglik/dlogA, out[3] sum f, out[4] sum r, out[5] r.lam_m,
 // out[6] closed-form lambda0
 __global__ void fparam_kernel(const double* __restrict__ lam_m, const double* __restrict__ lam_var,
                               const double* __restrict__ r, int n, double A, int closed_form, double lambda0_in,
                               double* __restrict__ f, double* __restrict__ out) {
   __shared__ double sh[17];
-  double se = 0.0, sr = 0.0, srm = 0.0, sg = 0.0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const double e = exp(A * lam_m[i] + 0.5 * A * A * lam_var[i]);
-    se += e;
-    sr += r[i];
-    srm += r[i] * lam_m[i];
-    sg += (lam_m[i] + A * lam_var[i]) * e;
-  }
-  se = block_sum(se, sh);
-  sr = block_sum(sr, sh);
-  srm = block_sum(srm, sh);
-  sg = block_sum(sg, sh);
-  const double lambda0 = closed_form ? (log(sr) - log(se)) : lambda0_in;
-  const double el0 = exp(lambda0);
-  if (f)
-    for (int i = threadIdx.x; i < n; i += blockDim.x)
-      f[i] = exp(A * lam_m[i] + 0.5 * A * A * lam_var[i] + lambda0);
+  double se, sg, sr, srm;
+  fparam_sums_A(lam_m, lam_var, n, A, sh, se, sg);
+  fparam_sums_r(lam_m, r, n, sh, sr, srm);
+  const FparamScalars v = fparam_scalars(A, se, sg, sr, srm, closed_form, lambda0_in);
+  if (f) fparam_rate(lam_m, lam_var, n, A, v.lambda0, f);
   if (threadIdx.x == 0) {
-    const double sf = se * el0;
-    out[0] = lambda0;
-    out[1] = A * srm + lambda0 * sr - sf;
-    out[2] = A * (srm - sg * el0);
-    out[3] = sf;
+    out[0] = v.lambda0;
+    out[1] = v.loglik;
+    out[2] = v.dloglik;
+    out[3] = v.sum_f;
     out[4] = sr;
     out[5] = srm;
-    out[6] = log(sr) - log(se);  // closed-form lambda0 for this logA, whatever was used above
+    out[6] = v.lambda0_closed;
   }
 }
 
@@ -1084,6 +1121,96 @@ int launch_fparam(const double* lam_m, const double* lam_var, const double* r, i
                   double lambda0_in, double* f, double* out, hipStream_t s) {
   hipLaunchKernelGGL(fparam_kernel, dim3(1), dim3(1024), 0, s, lam_m, lam_var, r, n, A, closed_form, lambda0_in, f,
                      out);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// The pass of the optimiser's closure at A = exp(logA).  The totals of the last pass are kept: the final rate is
+// usually asked at the A that was evaluated last.
+struct FparamDevicePass {
+  const double* lam_m;
+  const double* lam_var;
+  int n;
+  double* sh;
+  double sr, srm;
+  double A, se, sg;
+  __device__ void pass(double logA) {
+    const double A_new = exp(logA);
+    if (!(A_new == A)) {
+      fparam_sums_A(lam_m, lam_var, n, A_new, sh, se, sg);
+      A = A_new;
+    }
+  }
+  __device__ double lambda0_closed() const { return log(sr) - log(se); }
+  __device__ FparamValues values(double lambda0_used) const {
+    const FparamScalars v = fparam_scalars(A, se, sg, sr, srm, 0, lambda0_used);
+    return FparamValues{v.loglik, v.dloglik, v.sum_f};
+  }
+};
+
+// history slots in LDS: thread 0 writes, a barrier publishes (every thread computes the same values)
+struct Lbfgs1dLdsSlots {
+  __device__ static void put(double* p, int i, double v) {
+    if (threadIdx.x == 0) p[i] = v;
+  }
+  __device__ static void publish() { __syncthreads(); }
+};
+
+// The whole rate-parameter optimiser of an E-step (utils.py:1892-1934) in one workgroup: every thread runs the scalar
+// L-BFGS of lbfgs1d.h on the block totals, so the control flow is uniform.  Dynamic LDS: 4 * history_size doubles.
+// The optimiser's state does not fit the 128 VGPRs a 1024-thread workgroup leaves each lane: the resource report
+// shows 112 bytes per lane of register spills (the history itself is in LDS); the kernel averages 22 us per E-step.
+// out[0] final logA, [1] closed-form lambda0 there, [2] first loss, [3] last loss, [4] closure calls, [5] iterations,
+// [6] status (0 or the failing call), [7] logA and [8] lambda0 left by a failing call.  f: the rate at out[0..1].
+__global__ __launch_bounds__(1024) void fparam_lbfgs_kernel(const double* __restrict__ lam_m,
+                                                            const double* __restrict__ lam_var,
+                                                            const double* __restrict__ r, int n, double logA0,
+                                                            int lambda0_mode, double lambda0_fixed, Lbfgs1dConfig cfg,
+                                                            double* __restrict__ f, double* __restrict__ out) {
+  __shared__ double sh[17];
+  extern __shared__ double hist[];
+  const int hs = cfg.history_size;
+  FparamClosure<FparamDevicePass> obj;
+  obj.ev.lam_m = lam_m;
+  obj.ev.lam_var = lam_var;
+  obj.ev.n = n;
+  obj.ev.sh = sh;
+  obj.ev.A = __builtin_nan("");
+  obj.ev.se = obj.ev.sg = 0.0;
+  fparam_sums_r(lam_m, r, n, sh, obj.ev.sr, obj.ev.srm);
+  obj.fixed = lambda0_mode;
+  obj.lambda0_fixed = lambda0_fixed;
+  obj.lambda0 = 0.0;
+  obj.calls = 0;
+  obj.fail_x = obj.fail_lambda0 = 0.0;
+  const Lbfgs1dResult res =
+      lbfgs1d_step<Lbfgs1dLdsSlots>(obj, logA0, cfg, Lbfgs1dStorage{hist, hist + hs, hist + 2 * hs, hist + 3 * hs});
+  double lambda0 = __builtin_nan("");
+  if (res.status == 0) {
+    // lambda0_and_rate() (utils.py:1934): the closed form at the final logA and the rate there
+    obj.ev.pass(res.x);
+    lambda0 = obj.ev.lambda0_closed();
+    if (f) fparam_rate(lam_m, lam_var, n, obj.ev.A, lambda0, f);
+  }
+  if (threadIdx.x == 0) {
+    out[0] = res.x;
+    out[1] = lambda0;
+    out[2] = res.first_loss;
+    out[3] = res.last_loss;
+    out[4] = res.n_evals;
+    out[5] = res.n_iter;
+    out[6] = res.status;
+    out[7] = res.status ? obj.fail_x : 0.0;
+    out[8] = res.status ? obj.fail_lambda0 : 0.0;
+  }
+}
+
+int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double* r, int n, double logA0,
+                        int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f, double* out,
+                        hipStream_t s) {
+  const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
+  hipLaunchKernelGGL(fparam_lbfgs_kernel, dim3(1), dim3(1024), lds, s, lam_m, lam_var, r, n, logA0, lambda0_mode,
+                     lambda0_fixed, cfg, f, out);
   GP_HIP(hipGetLastError());
   return 0;
 }

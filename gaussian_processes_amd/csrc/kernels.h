@@ -1,6 +1,7 @@
 // Launchers of the non-GEMM kernels (elementwise / reductions / leaf).  Internal header.
 #pragma once
 #include "common.h"
+#include "lbfgs1d.h"
 
 namespace gpfit {
 
@@ -190,5 +191,9 @@ int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_
 int launch_unpack_tri(const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
 int launch_fparam(const double* lam_m, const double* lam_var, const double* r, int n, double A, int closed_form,
                   double lambda0_in, double* f, double* out, hipStream_t s);
+// The rate-parameter L-BFGS of an E-step in one launch (one workgroup): out[9] as documented at the kernel.
+int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double* r, int n, double logA0,
+                        int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f, double* out,
+                        hipStream_t s);
 
 }  // namespace gpfit

@@ -450,6 +450,34 @@ def _fparam_eval(lambda_m, lambda_var, r, logA, closed_form, lambda0=0.0, want_f
     return f, list(out)
 
 
+def _fparam_lbfgs(lambda_m, lambda_var, r, f_params, n_steps, i_estep):
+    """The rate-parameter optimiser of an E-step (utils.py:1892-1934) as one device call (gpfit_fparam_lbfgs):
+    lambda0 at its closed form for the starting logA, ``LBFGS([logA], lr=0.1, max_iter=n_steps, tolerance_change=1e-9,
+    tolerance_grad=1e-7, history_size=n_steps, line_search_fn='strong_wolfe').step(closure_f_params)`` and
+    ``lambda0_and_rate()``.  Updates ``f_params['logA']`` in place and sets ``f_params['lambda0']``; returns the rate
+    at the final (logA, lambda0) and that lambda0.  A non-finite sum f in closure call k raises the closure's
+    ValueError and leaves logA at that call's point and lambda0 at its closed form there, as the closure does."""
+    lib = _lib.load()
+    lm, lv, rr = _cu(lambda_m), _cu(lambda_var), _cu(r)
+    n = lm.shape[0]
+    eng = get_engine(n, 1)
+    f = torch.empty(n, dtype=TORCH_DTYPE, device=lm.device)
+    out = (ctypes.c_double * 9)()
+    fixed = 'loglambda0' in f_params
+    _lib.check(lib.gpfit_fparam_lbfgs(eng._ctx, _stream(), lm.data_ptr(), lv.data_ptr(), rr.data_ptr(), n,
+                                      _scalar(f_params['logA']), 1 if fixed else 0,
+                                      _scalar(_lambda0_of(f_params)) if fixed else 0.0, int(n_steps), int(n_steps),
+                                      0.1, 1.e-7, 1.e-9, f.data_ptr(), out), "gpfit_fparam_lbfgs")
+    status = int(out[6])
+    with torch.no_grad():
+        f_params['logA'].fill_(out[7] if status else out[0])      # the same tensor, as LBFGS's p.add_ leaves it
+    f_params['lambda0'] = torch.tensor(out[8] if status else out[1], dtype=TORCH_DTYPE)
+    if status:
+        raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been called {status} times in '
+                         f'estep {i_estep} iteration.')                                                      # :1923
+    return f, out[1]
+
+
 def mean_f_given_lambda_moments(f_params, lambda_m, lambda_var):
     """<f> = exp(A <lambda> + A^2/2 Var(lambda) + lambda0)   (utils.py:1126-1141)."""
     f, _ = _fparam_eval(lambda_m, lambda_var, None, f_params['logA'], False, _scalar(_lambda0_of(f_params)))
@@ -1478,27 +1506,10 @@ def varGP(x, r, **kwargs):
                         lambda_m, lambda_var = moments_now()                                    # :1884
                     # (the reference evaluates the rate here, :1885; nothing reads it before the closure below overwrites it)
                     tf = time.time()
-                    f_params['lambda0'] = lambda0_given_logA(f_params['logA'], r, lambda_m, lambda_var)      # :1892
-                    opt_f = torch.optim.LBFGS([f_params['logA']], lr=0.1, max_iter=nFparamstep, tolerance_change=1.e-9,
-                                              tolerance_grad=1.e-7, history_size=nFparamstep,
-                                              line_search_fn='strong_wolfe')                                # :1897
-                    calls = [0]
-
-                    def closure_f_params():
-                        calls[0] += 1
-                        # one fused pass: loglik, d/dlogA with the current lambda0, and the new closed-form lambda0 (the
-                        # rate vector itself is not written: nothing reads it before lambda0_and_rate() below; the
-                        # gradient is assigned, so there is nothing to zero first)
-                        _, out = _fparam_eval(lambda_m, lambda_var, r, f_params['logA'], False,
-                                              _scalar(_lambda0_of(f_params)), want_f=False)
-                        f_params['logA'].grad = torch.tensor(-out[2], dtype=TORCH_DTYPE)                     # :1913
-                        f_params['lambda0'] = torch.tensor(out[6], dtype=TORCH_DTYPE)                        # :1916
-                        if not math.isfinite(out[3]):
-                            raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been called '
-                                             f'{calls[0]} times in estep {i_estep} iteration.')              # :1923
-                        return torch.tensor(-out[1], dtype=TORCH_DTYPE)                                      # :1930
-                    opt_f.step(closure_f_params)                                                            # :1932
-                    f_params['lambda0'] = lambda0_and_rate()                                                # :1934
+                    # :1892-1934 (lambda0_given_logA, the LBFGS over logA with its closure, lambda0_and_rate) in one
+                    # device call; the rate it leaves is the one rate_now() is asked for next
+                    f_fp, lambda0_fp = _fparam_lbfgs(lambda_m, lambda_var, r, f_params, nFparamstep, i_estep)
+                    rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), lambda0_fp, f_fp)
                     times['fparams'] += time.time() - tf
             else:
                 print('No E-step')

@@ -268,6 +268,28 @@ int gpfit_fparam_eval(gpfit_ctx* ctx, void* stream, const double* lam_m, const d
                       const double* r, int64_t N, double logA, int closed_form_lambda0, double lambda0_in,
                       double* f_out, double* out_host);
 
+/* The whole rate-parameter optimiser of an E-step (varGP utils.py:1892-1934: lambda0_given_logA, then
+ * LBFGS([logA], lr, max_iter, tolerance_grad, tolerance_change, history_size, line_search_fn='strong_wolfe')
+ * .step(closure_f_params), then lambda0_and_rate) as one launch of one workgroup and one synchronisation.  The
+ * optimiser is a port of torch 2.10's LBFGS.step for one scalar (max_eval = max_iter*5/4); the closure's k-th call
+ * evaluates the pass of gpfit_fparam_eval at (logA_k, lambda0_{k-1}) and then sets lambda0_k to the closed form at
+ * logA_k, lambda0_0 being the closed form at logA0.  lambda0_mode = 1: every call uses lambda0_fixed instead
+ * (f_params carrying loglambda0: exp(loglambda0)).  A non-finite sum f stops the optimiser.
+ * out_host[9]: final logA, closed-form lambda0 there (NaN after a failure), first loss, last loss (at the final
+ * logA), closure calls, iterations, status (0, or the 1-based number of the call whose sum f was not finite),
+ * logA and lambda0 that call left behind (0 when status is 0).  f_out (device [N], may be NULL): the rate at the
+ * final (logA, lambda0), written when status is 0.  history_size up to 2040. */
+int gpfit_fparam_lbfgs(gpfit_ctx* ctx, void* stream, const double* lam_m, const double* lam_var,
+                       const double* r, int64_t N, double logA0, int lambda0_mode, double lambda0_fixed,
+                       int max_iter, int history_size, double lr, double tol_grad, double tol_change,
+                       double* f_out, double* out_host);
+/* The same optimiser and closure on host arrays (lam_m, lam_var, r, f_out), sums in index order: the CPU
+ * instance that checks the port against torch.optim.LBFGS without a GPU.  Same arguments and results. */
+int gpfit_fparam_lbfgs_host(const double* lam_m, const double* lam_var, const double* r, int64_t N,
+                            double logA0, int lambda0_mode, double lambda0_fixed, int max_iter,
+                            int history_size, double lr, double tol_grad, double tol_change, double* f_out,
+                            double* out_host);
+
 /* Active-learning utility of nstar candidate stimuli, U = H(r|x,D) - <H(r|f,x)>
  * (nd_utility with nd_p_r_given_xD, nd_lambda_r_mean, nd_mean_noise_entropy, utils.py:413-525;
  * call site one_cell_active_training.ipynb: u2d = nd_utility(logf_var, logf_mean, arange(100))).
