@@ -27,6 +27,16 @@ static int gemm_full(hipStream_t s, int ak, int bk, int M, int N, int K, double 
   return launch_gemm(g, s);
 }
 
+// the context's K~ work matrices as a batch of one chain for potrf_lockstep, on the caller's stream only (no
+// look-ahead side stream)
+static CholBatchT<double> one_chain(gpfit_ctx* c, int64_t ld) {
+  CholBatchT<double> b;
+  b.nb = 1;
+  b.A[0] = c->Kbuf; b.L[0] = c->Lbuf; b.Li[0] = c->Libuf; b.Tmp[0] = c->Tmp; b.info[0] = c->info;
+  b.ld = ld; b.sk_ws = c->sk_ws[0];
+  return b;
+}
+
 namespace {
 // y_i = sum_{j <= i} M[i][j] x_j for a lower-triangular row-major M (one wave per row)
 __global__ __launch_bounds__(256) void append_trmv_kernel(const double* __restrict__ M, int64_t ld, int n,
@@ -190,8 +200,8 @@ int gpfit_potrf(gpfit_ctx* c, void* stream, const double* A, int64_t lda, int64_
   const int64_t ld = np;
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
   GP_TRY(launch_pack_lower(A, lda, (int)n, c->Kbuf, ld, np, s));
-  CholBufs b{c->Kbuf, c->Lbuf, c->Libuf, c->Tmp, ld, c->info, 0, c->sk_ws[0]};
-  GP_TRY(potrf_rec(b, 0, np, Linv != nullptr, s));
+  const CholBatchT<double> b = one_chain(c, ld);
+  GP_TRY(potrf_lockstep(b, 0, np, Linv != nullptr ? 1u : 0u, s));
   GP_TRY(launch_logdet(c->Lbuf, ld, (int)n, c->scal + 3, s));
   if (L) GP_TRY(launch_unpack_tri(c->Lbuf, ld, (int)n, L, ldl, s));
   if (Linv) GP_TRY(launch_unpack_tri(c->Libuf, ld, (int)n, Linv, ldi, s));
@@ -228,21 +238,21 @@ int gpfit_estep(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_
   GP_TRY(launch_estep_prep(f, r, m, n, np, A, sv, rhs, s));
   // M = I + S K S (lower), SK = S K (dense), Kl = K (lower)
   GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, c->Wbuf, ld, s));
-  CholBufs b{c->Kbuf, c->Lbuf, c->Libuf, c->Tmp, ld, c->info, 0, c->sk_ws[0]};
+  const CholBatchT<double> b = one_chain(c, ld);
   // T = L_M^-1 (S K)          lower x dense                         N^3
   if (np >= 2 * TILE) {
     // block-wise, so that the off-diagonal block of L_M^-1 is never formed (N^3/4 less):
     //   T1 = [L^-1]11 B1 ,  T2 = [L^-1]22 (B2 - L21 T1)        with B = S K
     const int kt = np / TILE;
     const int n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;
-    GP_TRY(potrf_rec(b, 0, np, 2, s));
+    GP_TRY(potrf_lockstep(b, 0, np, 0u, s, 1u));   // [L^-1]11 and [L^-1]22 only
     GP_TRY(gemm_full(s, 0, 1, n1, np, n1, 1.0, c->Libuf, ld, c->Zbuf, ld, 0.0, c->Abuf, ld, 0, 1, 0, 1, c->sk_ws[0]));
     GP_TRY(gemm_full(s, 0, 1, n2, np, n1, -1.0, c->Lbuf + (int64_t)n1 * ld, ld, c->Abuf, ld, 1.0,
                      c->Zbuf + (int64_t)n1 * ld, ld, 0, 0, 0, 0, c->sk_ws[0]));
     GP_TRY(gemm_full(s, 0, 1, n2, np, n2, 1.0, c->Libuf + (int64_t)n1 * ld + n1, ld, c->Zbuf + (int64_t)n1 * ld, ld, 0.0,
                      c->Abuf + (int64_t)n1 * ld, ld, 0, 1, 0, 1, c->sk_ws[0]));
   } else {
-    GP_TRY(potrf_rec(b, 0, np, 1, s));
+    GP_TRY(potrf_lockstep(b, 0, np, 1u, s));
     GP_TRY(gemm_full(s, 0, 1, np, np, np, 1.0, c->Libuf, ld, c->Zbuf, ld, 0.0, c->Abuf, ld, 0, 1, 0, 1, c->sk_ws[0]));
   }
   // V = K - T^T T             lower tiles only                      N^3
@@ -282,7 +292,7 @@ int gpfit_estep_projected(gpfit_ctx* c, void* stream, const double* a, int64_t l
   const double A = std::exp(logA);
   double *sv = c->yv, *u = c->bv, *t2 = c->tvec, *z1 = c->mpad, *z = c->rpad, *mo = c->hvec;
   double *Y = c->Tbuf, *Lp = c->Wbuf, *P = c->Abuf, *V = c->Zbuf, *part = c->TmpV, *aLp = c->LiVbuf, *Zm = c->Cos;
-  c->lv_valid = false; c->lv32_valid = false;   // the work matrices of the V chain are reused
+  c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
   GP_TRY(launch_estep_proj_rows(a, lda, k, m, f, r, n, nrows, A, sv, u, s));
   GP_TRY(launch_estep_proj_scale(aL, ldal, k, n, nrows, sv, u, Y, want_moments ? aLp : nullptr, ld, npc, part, s));
@@ -290,8 +300,7 @@ int gpfit_estep_projected(gpfit_ctx* c, void* stream, const double* a, int64_t l
   // W = I + Y^T Y  (= I + L^T G L, G = A^2 a^T diag(f) a), lower tiles, identity on the padding
   GP_TRY(gemm_full(s, 1, 1, npc, npc, nrows, 1.0, Y, ld, Y, ld, 0.0, c->Kbuf, ld, 1, 0, 0, 0, c->sk_ws[0]));
   GP_TRY(launch_add_diag(c->Kbuf, ld, npc, 1.0, s));
-  CholBufs b{c->Kbuf, c->Lbuf, c->Libuf, c->Tmp, ld, c->info, 0, c->sk_ws[0]};
-  GP_TRY(potrf_rec(b, 0, npc, 1, s));
+  GP_TRY(potrf_lockstep(one_chain(c, ld), 0, npc, 1u, s));
   // m_new = L W^-1 (a L)^T u
   GP_TRY(launch_trmv_lower(c->Libuf, ld, npc, t2, z1, s));
   GP_TRY(launch_trmv_lower_t(c->Libuf, ld, npc, z1, z, c->trmv_part, s));

@@ -1,6 +1,6 @@
 // Cholesky leaf, register-resident variant: factor one 128 x 128 diagonal block and invert the
 // factor with the matrix held in the accumulator registers of four tile waves and only the current
-// 16-column panel in LDS (48 KiB instead of the 133 KiB of chol_leaf.hip); a fifth wave runs the pivot
+// 16-column panel in LDS (48 KiB instead of the 133 KiB of the round-1 LDS-resident leaf); a fifth wave runs the pivot
 // chains one panel ahead.
 //
 // Why: the leaf sits on the critical path of both factorisation chains 2N/128 times per fit (64 launches of
@@ -35,7 +35,7 @@
 // specialised per wave with its operands requested ahead, 3 / 11 / 11 / 11 tiles, the first chain under the tile
 // waves' prologue, B2 without the pivot wave); per panel now 1.6 k cycles before the chain, 4.4 k chain, 1.5 k
 // write-back on the pivot wave against 2.3 k solve + 5.4 k update pass on the tile waves.
-// info: LAPACK-style, as chol_leaf.hip (first non-positive pivot, offending pivot replaced by 1).
+// info: LAPACK-style (first non-positive pivot, offending pivot replaced by 1).
 #include "gemm_core.h"
 #include "kernels.h"
 
@@ -622,19 +622,7 @@ int launch_chol_leaf_batch(const LeafBatchT<R>& bt, hipStream_t s) {
   return 0;
 }
 
-template <typename R>
-int launch_chol_leaf_reg(const R* A, int64_t lda, R* L, int64_t ldl, R* Linv, int64_t ldi, int* info, int info_base,
-                         hipStream_t s) {
-  LeafBatchT<R> bt{};
-  bt.n = 1; bt.A[0] = A; bt.L[0] = L; bt.Li[0] = Linv; bt.info[0] = info;
-  bt.lda = lda; bt.ldl = ldl; bt.ldi = ldi; bt.info_base = info_base;
-  return launch_chol_leaf_batch(bt, s);
-}
-
 template int launch_chol_leaf_batch<double>(const LeafBatchT<double>&, hipStream_t);
 template int launch_chol_leaf_batch<float>(const LeafBatchT<float>&, hipStream_t);
-template int launch_chol_leaf_reg<double>(const double*, int64_t, double*, int64_t, double*, int64_t, int*, int,
-                                          hipStream_t);
-template int launch_chol_leaf_reg<float>(const float*, int64_t, float*, int64_t, float*, int64_t, int*, int, hipStream_t);
 
 }  // namespace gpfit

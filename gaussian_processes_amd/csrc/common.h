@@ -59,7 +59,7 @@ struct GemmArgsT {
   int split_k;               // >1: partial products written to C + z*sC (beta ignored)
   int tile;                  // 0 = choose (128 / 64 / 32), else forced block tile
   int reverse;               // tile walk: bit 0 backwards, bit 1 column-major (dense output)
-  int workspace;             // stream-K partial-tile workspace to use (0 main stream, 1 aux stream)
+  int workspace;             // stream-K partial-tile workspace to use (0 main stream, 1 side stream)
   void* sk_ws;               // caller-owned stream-K workspace (>= SK_WS_BYTES); nullptr: process-wide one
   int tile_limit;            // >0: launch only the first tile_limit tiles of the walk (stream-K head)
   int half_occ;              // 1: pad the launch with unused dynamic LDS so that only ONE workgroup of it fits on

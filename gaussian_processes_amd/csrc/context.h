@@ -22,12 +22,12 @@ struct gpfit_ctx {
          *q2 = nullptr, *dq1 = nullptr, *dq2 = nullptr, *hvec = nullptr;
   double *upart = nullptr, *vpart = nullptr, *sumA_part = nullptr, *frob_part = nullptr, *trmv_part = nullptr;
   double* rect_part = nullptr;  // (np/64)^2 per-tile sums of the rectangular adjoint
-  void* sk_ws[4] = {nullptr, nullptr, nullptr, nullptr};  // stream-K partial-tile workspaces (main / aux / two side streams)
-  // look-ahead: the first product of every inverse merge (tmp = L21 Li11) runs on a side stream of
-  // its chain while the second half of the block is being factored (fit.hip:potrf_rec)
-  hipStream_t side[2] = {nullptr, nullptr};
-  std::vector<hipEvent_t> side_ev[2];
-  int side_ev_next[2] = {0, 0};
+  void* sk_ws[2] = {nullptr, nullptr};  // stream-K partial-tile workspaces (main stream / side stream)
+  // look-ahead: the first product of every inverse merge (tmp = L21 Li11) runs on the side stream
+  // while the second half of the block is being factored (fit.hip:potrf_lockstep)
+  hipStream_t side = nullptr;
+  std::vector<hipEvent_t> side_ev;
+  int side_ev_next = 0;
   double* scal = nullptr;       // device scalars [64]
   double* scal_host = nullptr;  // pinned [64]
   int* pix = nullptr;           // device [dfull_cap]
@@ -44,7 +44,7 @@ struct gpfit_ctx {
   std::vector<hipEvent_t> ev_pool;
   double prof_out[16] = {0};
   // profile == 2: phase timing only (eight events per fit, none inside the factorisations): 0 start,
-  // 1 kernel build + moments done (fork), 2 K~ chain done, 3 V chain done (aux stream), 4 T and its
+  // 1 kernel build + moments done (fork), 2 K~'s solves done, 3 V factored, 4 T and its
   // norm done, 5 Q = I - T T^T done, 6 two-sided product done, 7 end
   hipEvent_t phase_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool phase_valid = false;
@@ -98,38 +98,9 @@ struct ProfScope {
 };
 template <typename R> double gemm_flops(const GemmArgsT<R>& g);
 
-template <typename R>
-struct CholBufsT {
-  R* A;    // input, lower triangle; destroyed
-  R* L;    // output factor
-  R* Li;   // output inverse blocks (full inverse when need_inv at the top)
-  R* Tmp;  // scratch, same shape
-  int64_t ld;
-  int* info;
-  int ws = 0;   // stream-K workspace id (1 for the factorisation running on the aux stream)
-  void* sk_ws = nullptr;  // that workspace (owned by the context)
-  // optional look-ahead resources of this chain (nullptr / 0: everything on the one stream)
-  gpfit_ctx* ctx = nullptr;
-  int chain = 0;           // index into ctx->side / side_ev
-  int side_min = 0;        // blocks of at least this size put their merge product on the side stream
-  int half_occ = 0;        // bit 0: this chain's own 128-tile launches run one workgroup per CU; bit 1: its side-stream products do
-  // optional: record mark_ev on the chain's stream once the leading mark_n x mark_n block is factored
-  // (the other chain can be started there, so that its latency-bound leaf stretches meet this chain's
-  // large products instead of this chain's leaf stretches)
-  hipEvent_t mark_ev = nullptr;
-  int mark_n = 0;
-};
-using CholBufs = CholBufsT<double>;
-// Recursive blocked Cholesky of the n x n diagonal block at offset r0 (n a multiple of 128),
-// built entirely from the MFMA GEMM and the 128 x 128 leaf.  need_inv = 1: the full inverse of
-// the factor is assembled on the way (L^-1 costs n^3/3 more; 0: only n^3/12 for the sub-block
-// inverses the solves need); 2: the inverses of the two diagonal half blocks but not the
-// off-diagonal block [L^-1]21 (for callers that apply L^-1 block-wise, n^3/8 less).
-template <typename R>
-int potrf_rec(const CholBufsT<R>& B, int r0, int n, int need_inv, hipStream_t s);
-
-// Several chains of the same size factored in lock step (fit.hip:potrf_lockstep): chain b factors A[b] (lower
-// triangle, destroyed) into L[b] with the inverse blocks in Li[b], scratch Tmp[b], LAPACK info in info[b].
+// Recursive blocked Cholesky of one or several matrices of the same size, factored in lock step
+// (fit.hip:potrf_lockstep): chain b factors A[b] (lower triangle, destroyed) into L[b] with the inverse blocks in
+// Li[b], scratch Tmp[b], LAPACK info in info[b].
 template <typename R>
 struct CholBatchT {
   int nb = 0;
@@ -141,13 +112,14 @@ struct CholBatchT {
   int64_t ld = 0;
   int ws = 0;
   void* sk_ws = nullptr;     // stream-K workspace of the launches issued chain by chain (one stream: shared)
-  gpfit_ctx* ctx = nullptr;  // look-ahead resources (side stream `chain` of this context), or nullptr
-  int chain = 0;
-  int side_min = 0;
+  gpfit_ctx* ctx = nullptr;  // look-ahead resources (this context's side stream), or nullptr: one stream
+  int side_min = 0;          // blocks of at least this size put their merge product on the side stream
 };
-// need: bit b = chain b needs the full inverse of its block (need_inv of potrf_rec); the diagonal sub-block
-// inverses every chain's solves need are always formed.
+// The n x n diagonal block at offset r0 (n a multiple of 128).  need: bit b = chain b needs the full inverse of
+// its block (L^-1 costs n^3/3 more); the diagonal sub-block inverses every chain's solves need are always formed
+// (n^3/12).  halves: bit b = chain b needs the inverses of the two diagonal half blocks but not the off-diagonal
+// block [L^-1]21 (for callers that apply L^-1 block-wise, n^3/8 less than need); read at this node only.
 template <typename R>
-int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStream_t s);
+int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStream_t s, uint32_t halves = 0);
 
 }  // namespace gpfit

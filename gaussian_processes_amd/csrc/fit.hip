@@ -113,7 +113,7 @@ double gemm_flops(const GemmArgsT<R>& g) {
 template <typename R>
 static GemmArgsT<R> gemm_args(int a_kmajor, int b_kmajor, int M, int N, int K, double alpha, const R* A, int64_t lda,
                               const R* B, int64_t ldb, double beta, R* C, int64_t ldc, int out_lower, int a_tri,
-                              int b_tri, int reverse = 0, int ws = 0, void* sk_ws = nullptr, int half_occ = 0) {
+                              int b_tri, int reverse = 0, int ws = 0, void* sk_ws = nullptr) {
   GemmArgsT<R> g{};
   g.A = A; g.B = B; g.C = C;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -122,7 +122,6 @@ static GemmArgsT<R> gemm_args(int a_kmajor, int b_kmajor, int M, int N, int K, d
   g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor;
   g.out_lower = out_lower; g.a_tri = a_tri; g.b_tri = b_tri;
   g.batch = 1; g.split_k = 1; g.reverse = reverse; g.workspace = ws; g.sk_ws = sk_ws ? sk_ws : g_main_sk_ws;
-  g.half_occ = half_occ;
   return g;
 }
 
@@ -136,21 +135,21 @@ static int gemm_log_eval() {
 }
 
 template <typename R>
-static int run_gemm(hipStream_t s, const GemmArgsT<R>& g, bool plain = false) {
+static int run_gemm(hipStream_t s, const GemmArgsT<R>& g) {
   if (gemm_log_eval() >= 0 && g_eval_count == gemm_log_eval())
     fprintf(stderr, "[gpfit gemm] M %d N %d K %d atri %d btri %d lower %d nb %d tile %d ak %d bk %d epi %d flops %.6e\n", g.M, g.N, g.K,
             g.a_tri, g.b_tri, g.out_lower, g.nptr > 0 ? g.nptr : 1, gemm_pick_tile(g), g.a_kmajor, g.b_kmajor, g.epi, gemm_flops(g));
   // profile kind 0: the 128-tile kernel family (the dominant kernel), 3: the small-tile instances
   ProfScope ps(s, g_prof ? gemm_flops(g) : 0.0, (g_prof && gemm_pick_tile(g) != TILE) ? 3 : 0);
-  return (plain || g.half_occ) ? launch_gemm_plain(g, s) : launch_gemm(g, s);  // plain: data-parallel, never stream-K
+  return launch_gemm(g, s);
 }
 
 template <typename R>
 static int gemm(hipStream_t s, int a_kmajor, int b_kmajor, int M, int N, int K, double alpha, const R* A,
                 int64_t lda, const R* B, int64_t ldb, double beta, R* C, int64_t ldc, int out_lower, int a_tri,
-                int b_tri, int reverse = 0, int ws = 0, void* sk_ws = nullptr, bool plain = false, int half_occ = 0) {
+                int b_tri, int reverse = 0, int ws = 0, void* sk_ws = nullptr) {
   return run_gemm(s, gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, out_lower, a_tri, b_tri,
-                                  reverse, ws, sk_ws, half_occ), plain);
+                                  reverse, ws, sk_ws));
 }
 
 #define GP_TRY(expr)            \
@@ -195,91 +194,18 @@ static int fused_epilogues() {
 }
 
 
-// ------------------------------------------------------------------ recursive Cholesky (+ inverse)
-template <typename R>
-int potrf_rec(const CholBufsT<R>& B, int r0, int n, int need_inv, hipStream_t s) {
-  const int64_t ld = B.ld;
-  auto at = [&](R* base, int r, int c) { return base + (int64_t)r * ld + c; };
-  if (n == TILE) {
-    ProfScope ps(s, 0.0, 1);
-    static const bool lds_leaf = getenv("GPFIT_LEAF_LDS") != nullptr;  // tuning knob: the LDS-resident leaf
-    if (lds_leaf) return launch_chol_leaf(at(B.A, r0, r0), ld, at(B.L, r0, r0), ld, at(B.Li, r0, r0), ld, B.info, r0, s);
-    return launch_chol_leaf_reg(at(B.A, r0, r0), ld, at(B.L, r0, r0), ld, at(B.Li, r0, r0), ld, B.info, r0, s);
-  }
-  const int k = n / TILE;
-  const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;
-  const int r1 = r0 + n1;
-  GP_TRY(potrf_rec<R>(B, r0, n1, 1, s));
-  if (B.mark_ev && r0 == 0 && n1 == B.mark_n) GP_HIP(hipEventRecord(B.mark_ev, s));
-  // L21 = A21 * L11^-T       (trsm as a GEMM against the explicit inverse; op(B) = Li11^T is upper)
-  GP_TRY(gemm<R>(s, 0, 0, n2, n1, n1, 1.0, at(B.A, r1, r0), ld, at(B.Li, r0, r0), ld, 0.0, at(B.L, r1, r0), ld, 0, 0, 2, walks()[0], B.ws, B.sk_ws, false, B.half_occ & 1));
-  // Look-ahead: tmp = L21 * Li11, the first product of the inverse merge, needs nothing from the second
-  // half, so it runs on the chain's side stream while that half is being factored (its leaves are
-  // latency-bound and leave the chip to it).  Possible because the leaf shares a CU with GEMM workgroups.
-  hipEvent_t joined = nullptr;
-  if (need_inv == 1 && B.ctx && B.side_min > 0 && n >= B.side_min && B.ctx->side[B.chain]) {
-    gpfit_ctx* c = B.ctx;
-    auto next_event = [&]() {
-      auto& pool = c->side_ev[B.chain];
-      int& nx = c->side_ev_next[B.chain];
-      if (nx == (int)pool.size()) {
-        hipEvent_t e = nullptr;
-        (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        pool.push_back(e);
-      }
-      return pool[nx++];
-    };
-    hipStream_t side = c->side[B.chain];
-    hipEvent_t fork = next_event();
-    joined = next_event();
-    GP_HIP(hipEventRecord(fork, s));
-    GP_HIP(hipStreamWaitEvent(side, fork, 0));
-    GP_TRY(gemm<R>(side, 0, 1, n2, n1, n1, 1.0, at(B.L, r1, r0), ld, at(B.Li, r0, r0), ld, 0.0, at(B.Tmp, r1, r0), ld, 0, 0, 1, walks()[1], 2 + B.chain, c->sk_ws[2 + B.chain], false, (B.half_occ >> 1) & 1));
-    GP_HIP(hipEventRecord(joined, side));
-  }
-  // A22 -= L21 L21^T          (syrk, lower tiles only); on the latency-bound levels tmp = L21 * Li11 shares its launch
-  // (potrf_lockstep below does the same: the two routes stay launch-for-launch the same products)
-  bool merged = false;
-  if (need_inv == 1 && !joined && !(B.half_occ & 1)) {
-    static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;
-    auto one = [&](GemmArgsT<R> g) { g.nptr = 1; g.batch = 1; g.Ap[0] = g.A; g.Bp[0] = g.B; g.Cp[0] = g.C; return g; };
-    const GemmArgsT<R> g2 = one(gemm_args<R>(0, 0, n2, n2, n1, -1.0, at(B.L, r1, r0), ld, at(B.L, r1, r0), ld, 1.0, at(B.A, r1, r1), ld,
-                                             1, 0, 0, 0, B.ws, B.sk_ws));
-    const GemmArgsT<R> g3 = one(gemm_args<R>(0, 1, n2, n1, n1, 1.0, at(B.L, r1, r0), ld, at(B.Li, r0, r0), ld, 0.0, at(B.Tmp, r1, r0), ld,
-                                             0, 0, 1, walks()[1], B.ws, B.sk_ws));
-    if (!no_batch && gemm_pair_ok(g2, g3)) {
-      ProfScope ps(s, g_prof ? gemm_flops(g2) + gemm_flops(g3) : 0.0, 3);
-      GP_TRY(launch_gemm_pair(g2, g3, s));
-      merged = true;
-    }
-  }
-  if (!merged)
-    GP_TRY(gemm<R>(s, 0, 0, n2, n2, n1, -1.0, at(B.L, r1, r0), ld, at(B.L, r1, r0), ld, 1.0, at(B.A, r1, r1), ld, 1, 0, 0, 0, B.ws, B.sk_ws, false, B.half_occ & 1));
-  GP_TRY(potrf_rec<R>(B, r1, n2, need_inv ? 1 : 0, s));
-  if (need_inv == 1) {
-    // Li21 = -Li22 * (L21 * Li11)
-    if (joined) GP_HIP(hipStreamWaitEvent(s, joined, 0));
-    else if (!merged) GP_TRY(gemm<R>(s, 0, 1, n2, n1, n1, 1.0, at(B.L, r1, r0), ld, at(B.Li, r0, r0), ld, 0.0, at(B.Tmp, r1, r0), ld, 0, 0, 1, walks()[1], B.ws, B.sk_ws, false, B.half_occ & 1));
-    GP_TRY(gemm<R>(s, 0, 1, n2, n1, n2, -1.0, at(B.Li, r1, r1), ld, at(B.Tmp, r1, r0), ld, 0.0, at(B.Li, r1, r0), ld, 0, 1, 0, walks()[2], B.ws, B.sk_ws, false, B.half_occ & 1));
-  }
-  return 0;
-}
-
-template int potrf_rec<double>(const CholBufsT<double>&, int, int, int, hipStream_t);
-template int potrf_rec<float>(const CholBufsT<float>&, int, int, int, hipStream_t);
-
-// ------------------------------------------------------------------ lock-step recursion over several chains
-// The same recursion for nb matrices of the same size at once (CholBatchT, context.h): the K~ and V chains of one
-// unit, or the chains of several independent units.  Every level whose launches cannot fill the chip -- the
-// leaves and the products of the small blocks, i.e. the latency-bound bottom of the recursion -- is ONE launch
-// for all chains (a pointer batch, GemmArgsT::nptr / LeafBatchT): the number of kernel boundaries on the critical
-// path no longer grows with the number of chains and every small launch has nb times the workgroups.  Products
-// that are 128-tile launches for a single chain are issued chain by chain through the ordinary launcher, with
-// its stream-K / XCD-aware schedules.  Results are bit-identical to potrf_rec: a chain's launches are the same
-// products in the same order; the batched ones are data-parallel launches exactly where potrf_rec's are (stream-K
-// only ever applies to 128-tile launches of a single problem, which take the same path here), and every
-// data-parallel instance sums k in ascending order per element whatever block tile the launcher picks.
-// need[b]: chain b needs the inverse of its block at this node (as need_inv of potrf_rec).
+// ------------------------------------------------------------------ recursive Cholesky (+ inverse), in lock step
+// Recursive blocked Cholesky built entirely from the MFMA GEMM and the 128 x 128 leaf, for nb matrices of the same
+// size at once (CholBatchT, context.h): one matrix (gpfit_potrf, the E-steps, a unit whose V factor is reused), the
+// K~ and V chains of one unit, or the chains of several independent units.  Every level whose launches cannot fill
+// the chip -- the leaves and the products of the small blocks, i.e. the latency-bound bottom of the recursion -- is
+// ONE launch for all chains (a pointer batch, GemmArgsT::nptr / LeafBatchT): the number of kernel boundaries on the
+// critical path does not grow with the number of chains and every small launch has nb times the workgroups.
+// Products that are 128-tile launches for a single chain are issued chain by chain through the ordinary launcher,
+// with its stream-K / XCD-aware schedules.  A chain therefore gets the same bits whatever else is in the batch: its
+// launches are the same products in the same order, stream-K only ever applies to 128-tile launches of a single
+// problem, and every data-parallel instance sums k in ascending order per element whatever block tile the launcher
+// picks.
 // cnt problems of one shape, problem i on (Ap[i], Bp[i], Cp[i]): one pointer-batched launch, unless the product
 // is a 128-tile launch already for a single problem -- then problem by problem through the ordinary launcher.
 template <typename R>
@@ -378,7 +304,7 @@ static GemmArgsT<R> batch_args(const CholBatchT<R>& B, uint32_t mask, int a_kmaj
 }
 
 template <typename R>
-int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStream_t s) {
+int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStream_t s, uint32_t halves) {
   const int64_t ld = B.ld;
   const uint32_t all = (B.nb >= 32) ? 0xffffffffu : ((1u << B.nb) - 1u);
   auto off = [&](int r, int c) { return (int64_t)r * ld + c; };
@@ -398,44 +324,35 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
   const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;
   const int r1 = r0 + n1;
   GP_TRY(potrf_lockstep<R>(B, r0, n1, all, s));
-  // L21 = A21 * L11^-T
+  // L21 = A21 * L11^-T       (trsm as a GEMM against the explicit inverse; op(B) = Li11^T is upper)
   GP_TRY(bgemm<R>(B, s, all, 0, 0, n2, n1, n1, 1.0, B.A, off(r1, r0), B.Li, off(r0, r0), 0.0, B.L, off(r1, r0), 0, 0, 2,
                   walks()[0], B.ws, B.sk_ws));
-  // look-ahead of the inverse merge's first product on the side stream (as potrf_rec)
+  // Look-ahead: tmp = L21 * Li11, the first product of the inverse merge, needs nothing from the second half, so it
+  // runs on the context's side stream while that half is being factored (its leaves are latency-bound and leave the
+  // chip to it).  Possible because the leaf shares a CU with GEMM workgroups.
   hipEvent_t joined = nullptr;
-#ifdef GPFIT_DEV
-  // timing experiment (wrong results by design): what the unit would cost if the first product of every inverse
-  // merge of a block of at least this size were hidden completely
-  static const int dev_skip_tmp = getenv("GPFIT_DEV_SKIP_TMP") ? atoi(getenv("GPFIT_DEV_SKIP_TMP")) : 0;
-  const bool skip_tmp = dev_skip_tmp > 0 && n >= dev_skip_tmp;
-#else
-  const bool skip_tmp = false;
-#endif
-  if (need && !skip_tmp && B.ctx && B.side_min > 0 && n >= B.side_min && B.ctx->side[B.chain]) {
+  if (need && B.ctx && B.side_min > 0 && n >= B.side_min && B.ctx->side) {
     gpfit_ctx* c = B.ctx;
     auto next_event = [&]() {
-      auto& pool = c->side_ev[B.chain];
-      int& nx = c->side_ev_next[B.chain];
-      if (nx == (int)pool.size()) {
+      if (c->side_ev_next == (int)c->side_ev.size()) {
         hipEvent_t e = nullptr;
         (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        pool.push_back(e);
+        c->side_ev.push_back(e);
       }
-      return pool[nx++];
+      return c->side_ev[c->side_ev_next++];
     };
-    hipStream_t side = c->side[B.chain];
     hipEvent_t fork = next_event();
     joined = next_event();
     GP_HIP(hipEventRecord(fork, s));
-    GP_HIP(hipStreamWaitEvent(side, fork, 0));
-    GP_TRY(bgemm<R>(B, side, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp, off(r1, r0), 0, 0, 1,
-                    walks()[1], 2 + B.chain, c->sk_ws[2 + B.chain]));
-    GP_HIP(hipEventRecord(joined, side));
+    GP_HIP(hipStreamWaitEvent(c->side, fork, 0));
+    GP_TRY(bgemm<R>(B, c->side, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp, off(r1, r0), 0, 0,
+                    1, walks()[1], 1, c->sk_ws[1]));
+    GP_HIP(hipEventRecord(joined, c->side));
   }
-  // A22 -= L21 L21^T.  On the latency-bound levels the first product of the inverse merge, L21 L11^-1 (it needs
-  // L21 and L11^-1 only), rides in the same launch: one launch boundary less per node of the recursion.
+  // A22 -= L21 L21^T (syrk, lower tiles only).  On the latency-bound levels the first product of the inverse merge,
+  // L21 L11^-1 (it needs L21 and L11^-1 only), rides in the same launch: one launch boundary less per node.
   bool merged = false;
-  if (need && !joined && !skip_tmp) {
+  if (need && !joined) {
     static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;
     const GemmArgsT<R> g2 = batch_args<R>(B, all, 0, 0, n2, n2, n1, -1.0, B.L, off(r1, r0), B.L, off(r1, r0), 1.0, B.A, off(r1, r1),
                                           1, 0, 0, 0);
@@ -453,10 +370,11 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
   if (!merged)
     GP_TRY(bgemm<R>(B, s, all, 0, 0, n2, n2, n1, -1.0, B.L, off(r1, r0), B.L, off(r1, r0), 1.0, B.A, off(r1, r1), 1, 0, 0, 0,
                     B.ws, B.sk_ws));
-  GP_TRY(potrf_lockstep<R>(B, r1, n2, need, s));
+  GP_TRY(potrf_lockstep<R>(B, r1, n2, need | halves, s));
   if (need) {
+    // Li21 = -Li22 * (L21 * Li11)
     if (joined) GP_HIP(hipStreamWaitEvent(s, joined, 0));
-    else if (!merged && !skip_tmp)
+    else if (!merged)
       GP_TRY(bgemm<R>(B, s, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp, off(r1, r0), 0, 0,
                       1, walks()[1], B.ws, B.sk_ws));
     GP_TRY(bgemm<R>(B, s, need, 0, 1, n2, n1, n2, -1.0, B.Li, off(r1, r1), B.Tmp, off(r1, r0), 0.0, B.Li, off(r1, r0), 0, 1, 0,
@@ -465,8 +383,8 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
   return 0;
 }
 
-template int potrf_lockstep<double>(const CholBatchT<double>&, int, int, uint32_t, hipStream_t);
-template int potrf_lockstep<float>(const CholBatchT<float>&, int, int, uint32_t, hipStream_t);
+template int potrf_lockstep<double>(const CholBatchT<double>&, int, int, uint32_t, hipStream_t, uint32_t);
+template int potrf_lockstep<float>(const CholBatchT<float>&, int, int, uint32_t, hipStream_t, uint32_t);
 
 // ------------------------------------------------------------------ two-sided triangular product
 // Wout (lower) = 1/2 Li^T Q Li on the n x n diagonal block at r0, Q symmetric (stored in full),
@@ -478,11 +396,7 @@ template int potrf_lockstep<float>(const CholBatchT<float>&, int, int, uint32_t,
 template <typename R>
 struct TwoSidedBufs {
   const R* Q; const R* Li; R* W; R* Z; R* H; int64_t ld; int min_split;
-  // optional: a side stream with two events; the top split then runs its two half-size diagonal products there,
-  // beside the three large off-diagonal products on the main stream (they depend on nothing of their level)
-  hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  void* side_sk_ws = nullptr;   // stream-K workspace of the launches issued on `side`
-  void* sk_ws = nullptr;        // stream-K workspace of this block's own launches (nullptr: the main stream's)
+  void* sk_ws = nullptr;        // stream-K workspace of this block's launches (nullptr: the main stream's)
 };
 // cnt diagonal blocks of size n (block i of problem b[i] at offset r0[i]) in lock step: the two half-size
 // two-sided products a split leaves behind (W11's A^T Q11 A and W22) depend on nothing else of their level, so
@@ -507,7 +421,7 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
     return 0;
   }
   const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;
-  auto diagonal_blocks = [&](hipStream_t st) -> int {
+  auto diagonal_blocks = [&]() -> int {
     // 1/2 A^T Q11 A (into W11) and W22 = 1/2 C^T Q22 C, all of them in lock step when the halves are equal
     TwoSidedBufs<R> bb[GEMM_MAXB];
     int rr[GEMM_MAXB];
@@ -515,22 +429,13 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
       for (int i = 0; i < cnt; ++i) {
         bb[2 * i] = b[i]; rr[2 * i] = r0[i];
         bb[2 * i + 1] = b[i]; rr[2 * i + 1] = r0[i] + n1;
-        bb[2 * i].side = bb[2 * i + 1].side = nullptr;
-        if (st != s) bb[2 * i].sk_ws = bb[2 * i + 1].sk_ws = b[i].side_sk_ws;
       }
-      return two_sided_list<R>(2 * cnt, bb, rr, n1, st);
+      return two_sided_list<R>(2 * cnt, bb, rr, n1, s);
     }
-    for (int i = 0; i < cnt; ++i) { bb[i] = b[i]; bb[i].side = nullptr; rr[i] = r0[i] + n1; if (st != s) bb[i].sk_ws = b[i].side_sk_ws; }
-    GP_TRY(two_sided_list<R>(cnt, bb, r0, n1, st));
-    return two_sided_list<R>(cnt, bb, rr, n2, st);
+    for (int i = 0; i < cnt; ++i) rr[i] = r0[i] + n1;
+    GP_TRY(two_sided_list<R>(cnt, b, r0, n1, s));
+    return two_sided_list<R>(cnt, b, rr, n2, s);
   };
-  const bool forked = cnt == 1 && b[0].side != nullptr;
-  if (forked) {
-    GP_HIP(hipEventRecord(b[0].ev_fork, s));
-    GP_HIP(hipStreamWaitEvent(b[0].side, b[0].ev_fork, 0));
-    GP_TRY(diagonal_blocks(b[0].side));
-    GP_HIP(hipEventRecord(b[0].ev_join, b[0].side));
-  }
   // Z21 = 1/2 Q22 B
   for (int i = 0; i < cnt; ++i) {
     const int r1 = r0[i] + n1;
@@ -577,8 +482,7 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
     Ap[i] = at(b[i].Li, r1, r1); Bp[i] = at(b[i].Z, r1, r0[i]); Cp[i] = at(b[i].W, r1, r0[i]);
   }
   GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, 0, b[0].sk_ws));
-  if (forked) GP_HIP(hipStreamWaitEvent(s, b[0].ev_join, 0));
-  else GP_TRY(diagonal_blocks(s));
+  GP_TRY(diagonal_blocks());
   // W11 += 1/2 (B^T H + H^T B)   (lower tiles)
   for (int i = 0; i < cnt; ++i) {
     const int r1 = r0[i] + n1;
@@ -591,10 +495,6 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
   }
   GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, b[0].sk_ws));
   return 0;
-}
-template <typename R>
-static int two_sided(const TwoSidedBufs<R>& b, int r0, int n, hipStream_t s) {
-  return two_sided_list<R>(1, &b, &r0, n, s);
 }
 
 // ------------------------------------------------------------------ host pieces of localker
@@ -643,15 +543,14 @@ static int check_limits(const double* theta, const double* lower, const double* 
   return 0;
 }
 
-// Side streams of the two chains (look-ahead products, the diagonal blocks of the two-sided product): off the
-// critical path, lowest priority.  Created when a synchronous evaluation first wants them -- contexts that only
-// ever serve grouped / asynchronous evaluations never do, and every stream a process creates is one more
-// claimant of the few hardware queues.
-static int ensure_side_streams(gpfit_ctx* c) {
-  if (c->side[0]) return 0;
+// Side stream of the factorisation's look-ahead products: off the critical path, lowest priority.  Created when a
+// synchronous evaluation first wants it -- contexts that only ever serve grouped / asynchronous evaluations never
+// do, and every stream a process creates is one more claimant of the few hardware queues.
+static int ensure_side_stream(gpfit_ctx* c) {
+  if (c->side) return 0;
   int least = 0, greatest = 0;
   GP_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-  for (int i = 0; i < 2; ++i) GP_HIP(hipStreamCreateWithPriority(&c->side[i], hipStreamNonBlocking, least));
+  GP_HIP(hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, least));
   return 0;
 }
 
@@ -681,7 +580,7 @@ struct PostJoin {
 // concurrency from batched launches, not from streams.
 template <typename R, typename PhaseFn>
 static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, const Theta* th, int n, int np, const int* d,
-                          const int* dp, int n_rows, int n_cols, int want_grad, hipStream_t s, PhaseFn&& phase, bool side_ok) {
+                          const int* dp, int n_rows, int n_cols, int want_grad, hipStream_t s, PhaseFn&& phase) {
   const int64_t ld = np;
   const R* Ap[GEMM_MAXB];
   const R* Bp[GEMM_MAXB];
@@ -730,23 +629,6 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
       tb[i].sk_ws = cs[0]->sk_ws[0];
       r0[i] = 0;
     }
-    // tuning knob: the half-size diagonal products of the top split on the chain-0 side stream (a single unit
-    // evaluated synchronously only, as the look-ahead of the factorisation)
-    static const int ts_side = getenv("GPFIT_TS_SIDE") ? atoi(getenv("GPFIT_TS_SIDE")) : 0;
-    gpfit_ctx* c = cs[0];
-    if (cnt == 1 && ts_side && side_ok && c->side[0]) {
-      auto next_event = [&]() {
-        auto& pool = c->side_ev[0];
-        int& nx = c->side_ev_next[0];
-        if (nx == (int)pool.size()) {
-          hipEvent_t e = nullptr;
-          (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-          pool.push_back(e);
-        }
-        return pool[nx++];
-      };
-      tb[0].side = c->side[0]; tb[0].ev_fork = next_event(); tb[0].ev_join = next_event(); tb[0].side_sk_ws = c->sk_ws[2];
-    }
     GP_TRY(two_sided_list<R>(cnt, tb, r0, np, s));
   }
   phase(6, s);
@@ -788,8 +670,8 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
 }
 template <typename R, typename PhaseFn>
 static int post_join(gpfit_ctx* c, const PostJoin<R>& a, const Theta& th, int n, int np, int d, int dp, int n_rows,
-                     int n_cols, int want_grad, hipStream_t s, PhaseFn&& phase, bool side_ok) {
-  return post_join_list<R>(1, &c, &a, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, s, phase, side_ok);
+                     int n_cols, int want_grad, hipStream_t s, PhaseFn&& phase) {
+  return post_join_list<R>(1, &c, &a, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, s, phase);
 }
 
 // The fused unit of work, templated on the scalar type of the device data: fp64 is the
@@ -817,8 +699,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
     for (int i = 0; i < 6; ++i) out_host[3 + i] = inf;
     return -2;
   }
-  hipStream_t s = (hipStream_t)stream, sa = c->aux;
-  if (getenv("GPFIT_SINGLE_STREAM")) sa = s;
+  hipStream_t s = (hipStream_t)stream;
   const int n = (int)N, np = (int)round_up(N, TILE);
   const int dfull = n_rows * n_cols;
   if (np > c->np_cap || dfull > c->dfull_cap) {
@@ -854,7 +735,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   GP_HIP(hipMemsetAsync(RP(c->mpad), 0, (size_t)np * sizeof(R), s));
   GP_HIP(hipMemcpyAsync(RP(c->mpad), m, (size_t)n * sizeof(R), hipMemcpyDeviceToDevice, s));
 
-  // ---- aux stream: Cholesky of V (only log|V| and L_V are needed; no full inverse).
+  // ---- V: only log|V| and L_V are needed (no full inverse).
   // Opt-in reuse (flag bit 1 of want_grad): the caller promises V is the matrix of the previous
   // call on this context (V is constant during an M-step, utils.py:2016-2114), so L_V and
   // log|V| are kept.  bench.py never sets it: the unit of work includes this factorisation.
@@ -862,51 +743,23 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   const bool async_call = (want_grad & 4) != 0;
   const bool mixed_grad = (want_grad & 8) != 0 && sizeof(R) == 8 && (want_grad & 1);
   want_grad &= 1;
-  // The V chain starts together with potrf(K~), not at the top of the call: the two recursions have
-  // the same shape, so started together their leaf phases and their large GEMMs coincide -- a large
-  // GEMM of one chain otherwise keeps every CU occupied and the other chain's leaf (133 KiB of LDS)
-  // waits for its tail (32.5 -> 31.8 ms/fit).  GPFIT_FORK_EARLY restores the old order (tuning knob).
-  static const bool fork_late = getenv("GPFIT_FORK_EARLY") == nullptr;
-  if (!fork_late) {
-    GP_HIP(hipEventRecord(c->ev_fork, s));
-    GP_HIP(hipStreamWaitEvent(sa, c->ev_fork, 0));
-  }
   // tuning knob: smallest block whose inverse-merge product goes to the side stream (0 = never)
   // (only for synchronous calls: with several units in flight on several contexts the chip is busy
-  // anyway and four more streams per context oversubscribe the hardware queues -- 64 cells x N = 4096,
+  // anyway and more streams per context oversubscribe the hardware queues -- 64 cells x N = 4096,
   // four in flight: 161 -> 118 cells/s with side streams)
   static const int side_min_env = getenv("GPFIT_SIDE_MIN") ? atoi(getenv("GPFIT_SIDE_MIN")) : 1024;
   const int side_min = async_call ? 0 : side_min_env;
-  if (!async_call) GP_TRY(ensure_side_streams(c));
-  // tuning knob (bit mask): 1 = the V chain's own 128-tile launches at one workgroup per CU, 2 = the
-  // side-stream products of both chains
-  static const int half_occ = getenv("GPFIT_HALF_OCC") ? atoi(getenv("GPFIT_HALF_OCC")) : 0;
-  c->side_ev_next[0] = c->side_ev_next[1] = 0;
-  auto enqueue_v_chain = [&]() -> int {
+  if (!async_call) GP_TRY(ensure_side_stream(c));
+  c->side_ev_next = 0;
+  // V is packed on the aux stream, beside the kernel build; both matrices then go through ONE recursion
+  // (potrf_lockstep) whose latency-bound levels are shared launches.
   if (!reuse_V) {
-      c->lv_valid = false; c->lv32_valid = false;
-      GP_TRY(launch_pack_lower(V, ldv, n, RP(c->Vbuf), ld, np, sa));
-      CholBufsT<R> bv{RP(c->Vbuf), RP(c->LVbuf), RP(c->LiVbuf), RP(c->TmpV), ld, c->info + 1, 1, c->sk_ws[1], c, 1, side_min, half_occ & 3};
-      GP_TRY(potrf_rec<R>(bv, 0, np, false, sa));
-      GP_TRY(launch_logdet(RP(c->LVbuf), ld, n, c->scal + 40, sa));
-    }
-    phase(3, sa);
-    GP_HIP(hipEventRecord(c->ev_join, sa));
-    return 0;
-  };
-  // Lock-step mode (default; GPFIT_LOCKSTEP=0 restores the two free-running chains): the V chain is not a
-  // stream of its own -- both matrices go through ONE recursion (potrf_lockstep) whose latency-bound levels are
-  // shared launches.  Only V's packing runs on the aux stream, beside the kernel build.
-  static const int lockstep_env = getenv("GPFIT_LOCKSTEP") ? atoi(getenv("GPFIT_LOCKSTEP")) : 1;
-  const bool lockstep = lockstep_env != 0 && !reuse_V;
-  if (lockstep) {
     c->lv_valid = false; c->lv32_valid = false;
     GP_HIP(hipEventRecord(c->ev_fork, s));
-    GP_HIP(hipStreamWaitEvent(sa, c->ev_fork, 0));
-    GP_TRY(launch_pack_lower(V, ldv, n, RP(c->Vbuf), ld, np, sa));
-    GP_HIP(hipEventRecord(c->ev_join, sa));
+    GP_HIP(hipStreamWaitEvent(c->aux, c->ev_fork, 0));
+    GP_TRY(launch_pack_lower(V, ldv, n, RP(c->Vbuf), ld, np, c->aux));
+    GP_HIP(hipEventRecord(c->ev_join, c->aux));
   }
-  if (!fork_late && !lockstep) GP_TRY(enqueue_v_chain());
 
   // ---- main stream: metric, kernel matrix, moments, Cholesky of K~ with its inverse
   GP_TRY(launch_localker<R>(th, c->pix, d, dp, n_rows, n_cols, RP(c->Cmat), dp, nullptr, s));
@@ -924,32 +777,17 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   GP_TRY(launch_moments(RP(c->Kvec), RP(c->q), RP(c->Cos), ld, V, ldv, m, r, n, A, lambda0, RP(c->lam_m), RP(c->lam_var), RP(c->fvec),
                         RP(c->wl), c->scal, c->sumA_part, c->info + 2, s));
   phase(1, s);
-  // tuning knob: start the V chain only when the K~ chain has factored its leading block of this size
-  static const int v_after = getenv("GPFIT_V_AFTER") ? atoi(getenv("GPFIT_V_AFTER")) : 0;
-  const bool v_marked = fork_late && !async_call && v_after >= TILE && v_after < np;
-  if (lockstep) {
-    GP_HIP(hipStreamWaitEvent(s, c->ev_join, 0));   // V is packed
+  {
+    // K~ (with its inverse) and V in lock step; K~ alone when V's factor is reused
     CholBatchT<R> cb;
-    cb.nb = 2;
+    cb.nb = reuse_V ? 1 : 2;
     cb.A[0] = RP(c->Kbuf); cb.L[0] = RP(c->Lbuf); cb.Li[0] = RP(c->Libuf); cb.Tmp[0] = RP(c->Tmp); cb.info[0] = c->info + 0;
     cb.A[1] = RP(c->Vbuf); cb.L[1] = RP(c->LVbuf); cb.Li[1] = RP(c->LiVbuf); cb.Tmp[1] = RP(c->TmpV); cb.info[1] = c->info + 1;
-    cb.ld = ld; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = c; cb.chain = 0; cb.side_min = side_min;
+    cb.ld = ld; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = c; cb.side_min = side_min;
+    if (!reuse_V) GP_HIP(hipStreamWaitEvent(s, c->ev_join, 0));   // V is packed
     GP_TRY(potrf_lockstep<R>(cb, 0, np, 1u, s));
-    GP_TRY(launch_logdet(RP(c->LVbuf), ld, n, c->scal + 40, s));
+    if (!reuse_V) GP_TRY(launch_logdet(RP(c->LVbuf), ld, n, c->scal + 40, s));
     phase(3, s);
-  } else if (fork_late && !v_marked) {
-    GP_HIP(hipEventRecord(c->ev_fork, s));
-    GP_HIP(hipStreamWaitEvent(sa, c->ev_fork, 0));
-    GP_TRY(enqueue_v_chain());
-  }
-  if (!lockstep) {
-    CholBufsT<R> bk{RP(c->Kbuf), RP(c->Lbuf), RP(c->Libuf), RP(c->Tmp), ld, c->info + 0, 0, c->sk_ws[0], c, 0, side_min, half_occ & 2};
-    if (v_marked) { bk.mark_ev = c->ev_fork; bk.mark_n = v_after; }
-    GP_TRY(potrf_rec<R>(bk, 0, np, true, s));
-    if (v_marked) {
-      GP_HIP(hipStreamWaitEvent(sa, c->ev_fork, 0));
-      GP_TRY(enqueue_v_chain());
-    }
   }
   GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + 3, s));
   GP_TRY(launch_trmv_lower(RP(c->Libuf), ld, np, RP(c->mpad), RP(c->yv), s));       // y = L^-1 m
@@ -957,8 +795,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   GP_TRY(launch_trmv_lower_t(RP(c->Libuf), ld, np, RP(c->yv), RP(c->bv), c->trmv_part, s));  // b = K~^-1 m
 
   phase(2, s);
-  // ---- join: everything that needs both factors
-  if (!lockstep) GP_HIP(hipStreamWaitEvent(s, c->ev_join, 0));
+  // ---- everything that needs both factors
   {
     PostJoin<R> pj{RP(c->Libuf), RP(c->LVbuf), RP(c->Cos), RP(c->bv), RP(c->q), RP(c->wl), RP(c->Xm), RP(c->Cmat),
                    RP(c->Tbuf), RP(c->Wbuf), RP(c->Zbuf), RP(c->Tmp), RP(c->Abuf), RP(c->Ybuf), RP(c->tvec),
@@ -983,9 +820,9 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
       PostJoin<float> pf{F(c->Kbuf), F(c->Vbuf), F(c->TmpV), F(c->q2), F(c->dq1), F(c->dq2), F(c->Xt2), F(c->dCpad),
                          F(c->Tbuf), F(c->Wbuf), F(c->Zbuf), F(c->Tmp), F(c->Abuf), F(c->Ybuf), F(c->tvec),
                          F(c->Mpart), F(c->Mmat)};
-      GP_TRY(post_join<float>(c, pf, th, n, np, d, dp, n_rows, n_cols, want_grad, s, phase, !async_call));
+      GP_TRY(post_join<float>(c, pf, th, n, np, d, dp, n_rows, n_cols, want_grad, s, phase));
     } else {
-      GP_TRY(post_join<R>(c, pj, th, n, np, d, dp, n_rows, n_cols, want_grad, s, phase, !async_call));
+      GP_TRY(post_join<R>(c, pj, th, n, np, d, dp, n_rows, n_cols, want_grad, s, phase));
     }
   }
 
@@ -1085,7 +922,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
     q.reuse_V = want_reuse && c->lv_valid && c->lv_n == n && c->lv_bytes == (int)sizeof(R);
     c->cur_n = n; c->cur_np = np; c->cur_d = d; c->cur_dp = dp;
     c->phase_valid = false;
-    c->side_ev_next[0] = c->side_ev_next[1] = 0;
+    c->side_ev_next = 0;
   }
   if (na == 0) return 0;
   gpfit_ctx* c0 = un[0].c;
@@ -1188,8 +1025,8 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
                                F(c->Mpart), F(c->Mmat)};
     }
   }
-  if (mixed_grad) GP_TRY(post_join_list<float>(na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase, false));
-  else GP_TRY(post_join_list<R>(na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase, false));
+  if (mixed_grad) GP_TRY(post_join_list<float>(na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase));
+  else GP_TRY(post_join_list<R>(na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase));
   {
     GroupCollectT gc{};
     gc.n_units = na;
@@ -1350,7 +1187,7 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   const double s0sq = th.sigma0 * th.sigma0, A = std::exp(logA);
   const int64_t ld = np, lb = nb;
   c->lv_valid = false; c->lv32_valid = false;
-  c->side_ev_next[0] = c->side_ev_next[1] = 0;
+  c->side_ev_next = 0;
   g_main_sk_ws = c->sk_ws[0];
   ++g_eval_count;
   prof_begin(c);
@@ -1534,7 +1371,7 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   const double s0sq = th.sigma0 * th.sigma0, A = std::exp(logA);
   const int64_t l2 = np2, lb = nb;
   c->lv_valid = false; c->lv32_valid = false;
-  c->side_ev_next[0] = c->side_ev_next[1] = 0;
+  c->side_ev_next = 0;
   g_main_sk_ws = c->sk_ws[0];
   ++g_eval_count;
   prof_begin(c);
@@ -1853,7 +1690,7 @@ int gpfit_ctx_create(int device, int64_t n_max, int64_t d_max, int64_t d_full_ma
   A(&c->rect_part, t64 * t64);
   A(&c->frob_part, 33 * (np / TILE) * (np / TILE + 1) / 2); A(&c->trmv_part, (np / TRMV_ROWS + 1) * np);
   A(&c->scal, 64);
-  for (int i = 0; i < 4 && !rc; ++i) {
+  for (int i = 0; i < 2 && !rc; ++i) {
     double* w = nullptr;
     rc = dev_alloc(c, &w, SK_WS_BYTES / sizeof(double));
     c->sk_ws[i] = w;
@@ -1871,15 +1708,13 @@ int gpfit_ctx_create(int device, int64_t n_max, int64_t d_max, int64_t d_full_ma
   GP_HIP(hipHostMalloc((void**)&c->pix_host, (size_t)c->dfull_cap * sizeof(int), HOST_FLAGS));
   GP_HIP(hipHostMalloc((void**)&c->info_host, 4 * sizeof(int), HOST_FLAGS));
   {
-    // the V chain is the shorter of the two factorisations: give its stream the lowest priority so
-    // that, whenever both have workgroups ready, the critical K~ chain is dispatched first
+    // the aux stream only packs V while the kernel matrix is being built, off the critical path: lowest priority,
+    // so that whenever both streams have work ready the main stream's kernel build is dispatched first
     int least = 0, greatest = 0;
     GP_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const char* e = getenv("GPFIT_AUX_PRIO");  // tuning knob: 0 = default priority
-    if (e && atoi(e) == 0) GP_HIP(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-    else GP_HIP(hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, least));
+    GP_HIP(hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, least));
   }
-  // (the side streams of the two chains are created on first use: ensure_side_streams)
+  // (the side stream of the look-ahead is created on first use: ensure_side_stream)
   GP_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   GP_HIP(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   // the strict-upper tiles of every triangular work matrix are never written and must read as 0
@@ -1903,10 +1738,8 @@ void gpfit_ctx_destroy(gpfit_ctx* c) {
   if (c->pix_host) (void)hipHostFree(c->pix_host);
   if (c->info_host) (void)hipHostFree(c->info_host);
   if (c->aux) (void)hipStreamDestroy(c->aux);
-  for (int i = 0; i < 2; ++i) {
-    if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
-    for (hipEvent_t e : c->side_ev[i]) (void)hipEventDestroy(e);
-  }
+  if (c->side) (void)hipStreamDestroy(c->side);
+  for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   for (hipEvent_t e : c->phase_ev)

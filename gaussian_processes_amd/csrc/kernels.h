@@ -11,17 +11,6 @@ struct Theta {
   double eb, er;                                      // exp(-2log2beta), exp(-log2rho2)
 };
 
-// ---- chol_leaf.hip
-template <typename R>
-int launch_chol_leaf(const R* A, int64_t lda, R* L, int64_t ldl, R* Linv, int64_t ldi, int* info, int info_base,
-                     hipStream_t s);
-
-// ---- chol_leaf_reg.hip: same contract, matrix in registers, 21 KiB of LDS (co-resident with GEMM workgroups)
-template <typename R>
-int launch_chol_leaf_reg(const R* A, int64_t lda, R* L, int64_t ldl, R* Linv, int64_t ldi, int* info, int info_base,
-                         hipStream_t s);
-// n independent 128 x 128 blocks in one launch (one workgroup each): block b factors A[b] into L[b], Li[b] and
-// reports into info[b]; common leading dimensions and info_base
 // Per-unit housekeeping of a group of evaluations, one launch for the whole group instead of four small copies /
 // fills per unit at the start and two device-to-host copies per unit at the end (each of those is a blit kernel with
 // a host round trip behind it: 1.8 ms per group of 16 at the end alone, profiles/r03_group_idle.txt).
@@ -48,6 +37,10 @@ template <typename R>
 int launch_group_prepare(const GroupPrepT<R>& g, hipStream_t s);
 int launch_group_collect(const GroupCollectT& g, hipStream_t s);
 
+// ---- chol_leaf_reg.hip: the 128 x 128 leaf of the recursive Cholesky, matrix in registers (co-resident with GEMM
+// workgroups).  n independent blocks in one launch (one workgroup each): block b factors A[b] (lower triangle) into
+// L[b] and its inverse Li[b] and reports the first non-positive pivot (LAPACK info, + info_base) into info[b];
+// common leading dimensions and info_base
 template <typename R>
 struct LeafBatchT {
   const R* A[GEMM_MAXB];

@@ -1,4 +1,4 @@
-"""Accuracy of the recursive Cholesky with explicit block inverses (fit.hip:potrf_rec) against the
+"""Accuracy of the recursive Cholesky with explicit block inverses (fit.hip:potrf_lockstep) against the
 condition number of the matrix: factor residual, inverse residual and log-determinant error for
 M = Q diag(lambda) Q^T with log-spaced eigenvalues, beside LAPACK's potrf (numpy) on the same matrices."""
 import os, sys

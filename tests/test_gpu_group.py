@@ -1,9 +1,9 @@
 """Grouped evaluation of independent units (gpfit_fit_eval_batch, through the C ABI) and the lock-step
 factorisation behind it.  Run with `-m gpu` on an MI355X.
 
-The claim under test is exactness, not a tolerance: a unit evaluated in a group, a unit evaluated alone, and a unit
-evaluated with every launch on its own (the two free-running factorisation chains of rounds 1-2, no pointer
-batches) produce the same bits, because every chain runs the same products in the same order and all
+The claim under test is exactness, not a tolerance: a unit evaluated in a group, a unit evaluated alone, a unit
+evaluated with every launch on its own (no pointer batches), and a matrix factored as the only chain of the
+recursion produce the same bits, because every chain runs the same products in the same order and all
 data-parallel GEMM instances sum k in ascending order per element.  The oracle comparison of the single path
 (tests/test_gpu_parity.py) therefore carries over to the groups."""
 import os
@@ -204,7 +204,7 @@ _CHILD = r"""
 import sys, torch
 sys.path.insert(0, %r)
 import numpy as np
-from gaussian_processes_amd import synthetic as syn
+from gaussian_processes_amd import synthetic as syn, utils
 from gaussian_processes_amd.engine import GPFitEngine
 from oracle import gp_oracle as orc
 N, d = 1408, 64
@@ -218,21 +218,31 @@ eng = GPFitEngine(N, d)
 o = eng.fit_eval(syn.theta_eval(2), lower, upper, grid, X.to(dev), torch.from_numpy(r_np).to(dev), torch.from_numpy(m_np).to(dev),
                  V.to(dev), syn.F_PARAMS["logA"], syn.F_PARAMS["lambda0"], want_vectors=False)
 print("HEX", float(o["loss"]).hex(), " ".join(float(v).hex() for v in o["grad"].values()), float(o["logdet_V"]).hex(), float(o["tr_KinvV"]).hex())
+# K~ factored alone (V's factor reused), and V factored alone (gpfit_potrf: one chain, no side stream)
+o2 = eng.fit_eval(syn.theta_eval(2), lower, upper, grid, X.to(dev), torch.from_numpy(r_np).to(dev), torch.from_numpy(m_np).to(dev),
+                  V.to(dev), syn.F_PARAMS["logA"], syn.F_PARAMS["lambda0"], want_vectors=False, reuse_V=True)
+for tag, x in (("FIRST", o), ("REUSE", o2)):
+    print(tag, float(x["loss"]).hex(), " ".join(float(v).hex() for v in x["grad"].values()), float(x["tr_KinvV"]).hex())
+print("LOGDET", float(o["logdet_V"]).hex(), float(utils.cholesky(V.to(dev))[2]).hex())
 """
 
 
-def test_lockstep_and_free_running_schedules_give_the_same_bits():
+def test_schedules_and_chains_factored_alone_give_the_same_bits():
     """The single unit under the schedules of the factorisations -- lock step with shared and paired launches
     (default), without the paired launches (GPFIT_NO_PAIR: the update of a node and the first product of its inverse
-    merge as two launches), with every product launched on its own (GPFIT_NO_BATCH), the two free-running chains of
-    rounds 1-2 (GPFIT_LOCKSTEP=0, with and without its own paired launches) -- one process each (the switches are read
-    once per process)."""
+    merge as two launches), with every product launched on its own (GPFIT_NO_BATCH) -- one process each (the switches
+    are read once per process).  In each, a chain factored on its own gives the bits it gets in lock step: K~ alone
+    (a second evaluation that reuses V's factor) reproduces loss, gradient and tr(K~^-1 V), and V alone
+    (utils.cholesky, the gpfit_potrf route) reproduces log|V|."""
     outs = []
-    for extra in ({}, {"GPFIT_NO_PAIR": "1"}, {"GPFIT_NO_BATCH": "1"}, {"GPFIT_LOCKSTEP": "0"}, {"GPFIT_LOCKSTEP": "0", "GPFIT_NO_PAIR": "1"}):
+    for extra in ({}, {"GPFIT_NO_PAIR": "1"}, {"GPFIT_NO_BATCH": "1"}):
         env = dict(os.environ, **extra)
         p = subprocess.run([sys.executable, "-c", _CHILD % ROOT], env=env, capture_output=True, text=True, timeout=300)
         assert p.returncode == 0, p.stderr[-2000:]
-        outs.append([l for l in p.stdout.splitlines() if l.startswith("HEX")][0])
+        lines = {l.split()[0]: l.split()[1:] for l in p.stdout.splitlines() if l.split() and l.split()[0] in ("HEX", "FIRST", "REUSE", "LOGDET")}
+        assert lines["REUSE"] == lines["FIRST"], (extra, lines)
+        assert lines["LOGDET"][0] == lines["LOGDET"][1], (extra, lines)
+        outs.append(lines["HEX"])
     assert all(o == outs[0] for o in outs), outs
 
 

@@ -1,5 +1,5 @@
 """Numerical stability of the recursive Cholesky whose triangular solves are GEMMs against explicit
-block inverses (fit.hip:potrf_rec) -- the VERDICT r01 robustness item: 'only conditionally stable ...
+block inverses (fit.hip:potrf_lockstep) -- the VERDICT r01 robustness item: 'only conditionally stable ...
 unexamined near the reference's keep-all margin'.  The reference keeps all eigen-directions while
 cond(K~) < 1e4 (EIGVAL_TOL = 1e-4, utils.py:1683) and its fixtures' full-rank family runs at tol 1e-14,
 so the range examined is cond = 1e2 .. 1e14.
