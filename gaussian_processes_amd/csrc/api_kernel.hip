@@ -9,12 +9,6 @@
 
 using namespace gpfit;
 
-#define GP_TRY(expr)            \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc != 0) return _rc;   \
-  } while (0)
-
 static int gemm_kk(hipStream_t s, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb,
                    double* C, int64_t ldc) {
   GemmArgs g{};

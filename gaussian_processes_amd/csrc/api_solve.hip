@@ -10,12 +10,6 @@
 
 using namespace gpfit;
 
-#define GP_TRY(expr)            \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc != 0) return _rc;   \
-  } while (0)
-
 static int gemm_full(hipStream_t s, int ak, int bk, int M, int N, int K, double alpha, const double* A, int64_t lda,
                      const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int lower, int at, int bt,
                      int walk, void* sk_ws) {

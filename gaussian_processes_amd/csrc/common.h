@@ -26,6 +26,13 @@ void set_error(const std::string& msg);
     }                                                                                    \
   } while (0)
 
+// the same for the library's own int-returning functions: hand a non-zero code up
+#define GP_TRY(expr)            \
+  do {                          \
+    int _rc = (expr);           \
+    if (_rc != 0) return _rc;   \
+  } while (0)
+
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // ---- MFMA GEMM (fp64, and fp32 for the theta-grid configuration) ----------------------

@@ -1,7 +1,12 @@
 // Host-side orchestration of the GP fit path on one MI355X: workspace context, the recursive
 // blocked Cholesky built from MFMA GEMMs, and the fused unit of work (one evaluation of the
 // reference's M-step closure, utils.py:2017-2112) in the original-basis Cholesky formulation
-// (DESIGN.md section 3).
+// (DESIGN.md section 3).  The five fused entry points -- gpfit_fit_eval, gpfit_fit_eval_batch,
+// gpfit_grad_pullback, gpfit_fit_eval_projected, gpfit_fit_eval_sparse -- are each a short sequence of
+// the shared stages defined once below ("shared stages of the fused closures": admission, kernel build,
+// the vectors behind the factor, the mixed-precision hand-over, the pull-back to the metric, the
+// n_kept x n_kept algebra of the truncated-rank closures, the host assembly of the 16 outputs); what
+// differs between the entry points is which stages they call and what they launch in between.
 #include "context.h"
 #include "gpfit_mi355x.h"
 
@@ -151,12 +156,6 @@ static int gemm(hipStream_t s, int a_kmajor, int b_kmajor, int M, int N, int K, 
   return run_gemm(s, gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, out_lower, a_tri, b_tri,
                                   reverse, ws, sk_ws));
 }
-
-#define GP_TRY(expr)            \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc != 0) return _rc;   \
-  } while (0)
 
 // C = alpha op(A) op(B) with the k range cut into `splits` slabs: the shapes of the truncated-rank closures whose
 // output has few tiles but a long k (K_b = K~ B: 8192 x 512 x 8192; B^T X: 512 x 512 x 8192) fill the chip with
@@ -563,6 +562,225 @@ static int dev_alloc(gpfit_ctx* c, T** p, size_t count) {
   return 0;
 }
 
+// ------------------------------------------------------------------ shared stages of the fused closures
+// The five fused entry points are short sequences of the stages below (file-local functions on the context, the
+// stream and plain pointers: nothing here allocates or dispatches indirectly -- the host enqueue time of a unit is
+// part of its measured time at N <= 2048).  Which entry point uses which:
+//   stage                                   fit_eval  _batch  grad_pullback  _projected  _sparse
+//   admit                                      x        x          x             x          x
+//   build_kernel                               x        x          x             x      (its parts)
+//   solve_mean, post_join_args,
+//   demote_for_mixed, set_pending              x        x
+//   adjoint_pass, xty                          x        x          x             x          x
+//   pullback_to_metric                                             x             x          x
+//   projected_factor, projected_kl_products                                      x          x
+//   assemble_out                          (fit_eval_finish)                      x          x
+// A stage is a fixed launch sequence; where two entry points order their launches differently the cut is between
+// stages, never inside one.
+template <typename R>
+static R* ws_as(double* b) { return reinterpret_cast<R*>(b); }  // the workspace is allocated for fp64
+
+// utils.py:2020-2028: out-of-box theta -> infinite loss and infinite gradients
+static void fill_out_of_box(double* out) {
+  const double inf = std::numeric_limits<double>::infinity();
+  out[0] = inf;
+  out[1] = out[2] = std::numeric_limits<double>::quiet_NaN();
+  for (int i = 0; i < 6; ++i) out[3 + i] = inf;
+}
+
+// Admission of one evaluation to context c: the limits (lower / upper may be absent), the capacity for np padded
+// stimuli, the masked pixel list (c->pix_host) with its count d and padded count dp, and the hyperparameters.
+// Returns 0, -2 (theta outside the limits: `out` holds the infinite loss / gradients) or -3; the error strings carry
+// the entry point's `name` and speak of `whose` capacity ("the context" / "a context's").
+struct Admitted { int d, dp; Theta th; };
+static int admit(gpfit_ctx* c, const char* name, const char* whose, const double* theta, const double* lower,
+                 const double* upper, int n_rows, int n_cols, int np, double* out, Admitted* a) {
+  if (lower && upper && check_limits(theta, lower, upper) != 0) {
+    fill_out_of_box(out);
+    return -2;
+  }
+  if (np > c->np_cap || n_rows * n_cols > c->dfull_cap) {
+    set_error(std::string(name) + ": problem larger than " + whose + " capacity");
+    return -3;
+  }
+  a->d = compute_mask(theta, n_rows, n_cols, nullptr, c->pix_host);
+  a->dp = (int)round_up(a->d, 32);
+  if (a->d <= 0 || a->dp > c->dp_cap) {
+    set_error(std::string(name) + ": masked pixel count is zero or exceeds " + whose + " capacity");
+    return -3;
+  }
+  a->th = make_theta(theta);
+  return 0;
+}
+
+// ---- kernel build: the metric C, then per set of stimuli the masked copies and vectors, then the Gram matrix
+template <typename R>
+static int build_metric(gpfit_ctx* c, hipStream_t s, const Theta& th, int d, int dp, int n_rows, int n_cols) {
+  return launch_localker<R>(th, c->pix, d, dp, n_rows, n_cols, ws_as<R>(c->Cmat), dp, nullptr, s);
+}
+// one set of n stimuli: masked and k-major in Xt [dp][np], row-major in Xm [np][dp], C Xt, and Kvec / q
+template <typename R>
+static int kernel_side(gpfit_ctx* c, hipStream_t s, const R* X, int64_t ldx, int n, int np, int d, int dp, double s0sq,
+                       R* Xt, R* XCt, R* Xm, R* Kvec, R* q) {
+  const int64_t ld = np;
+  GP_TRY(launch_gather(X, ldx, n, c->pix, d, dp, np, Xt, ld, Xm, dp, s));
+  GP_TRY(gemm<R>(s, 1, 1, dp, np, dp, 1.0, ws_as<R>(c->Cmat), dp, Xt, ld, 0.0, XCt, ld, 0, 0, 0));
+  return launch_qvec(Xt, XCt, ld, dp, n, np, s0sq, Kvec, q, s);
+}
+// K~ = acosker(x, x) with its cosine matrix: lower tiles, identity on the padding.  mirror: the tiles also store
+// their transposes (for callers that multiply with K~ from the left).  The launch sits in a profiling scope for every
+// caller: only gpfit_fit_eval, _projected and _sparse ever open a profile (prof_begin), and those three had it.
+template <typename R>
+static int gram_square(hipStream_t s, const R* XCt, const R* Xt, const R* q, R* Kout, R* Cos, int n, int np, int dp,
+                       double s0sq, int mirror) {
+  GramArgsT<R> g{};
+  g.XCt = XCt; g.Xt = Xt; g.q1 = q; g.q2 = q; g.Kout = Kout; g.Cos = Cos;
+  g.ld1 = np; g.ld2 = np; g.ldk = np; g.np1 = np; g.np2 = np; g.nv1 = n; g.nv2 = n; g.Kd = dp;
+  g.s0sq = s0sq; g.lower = 1; g.pad_identity = 1;
+  g.mirror = mirror;
+  ProfScope ps(s, (double)np * (np + TILE) * dp, 2);
+  return launch_gram(g, s);
+}
+// the kernel objects of one set of stimuli in the context's own buffers: Cmat, Xt, XCt, Xm, Kvec, q, Kbuf, Cos
+template <typename R>
+static int build_kernel(gpfit_ctx* c, hipStream_t s, const Theta& th, int d, int dp, int n_rows, int n_cols, const R* X,
+                        int64_t ldx, int n, int np, int mirror) {
+  const double s0sq = th.sigma0 * th.sigma0;
+  GP_TRY(build_metric<R>(c, s, th, d, dp, n_rows, n_cols));
+  GP_TRY(kernel_side<R>(c, s, X, ldx, n, np, d, dp, s0sq, ws_as<R>(c->Xt), ws_as<R>(c->XCt), ws_as<R>(c->Xm),
+                        ws_as<R>(c->Kvec), ws_as<R>(c->q)));
+  return gram_square<R>(s, ws_as<R>(c->XCt), ws_as<R>(c->Xt), ws_as<R>(c->q), ws_as<R>(c->Kbuf), ws_as<R>(c->Cos), n, np,
+                        dp, s0sq, mirror);
+}
+
+// ---- the vectors behind K~'s factor: y = L^-1 m, m^T K~^-1 m, b = K~^-1 m
+template <typename R>
+static int solve_mean(gpfit_ctx* c, int np, hipStream_t s) {
+  const int64_t ld = np;
+  GP_TRY(launch_trmv_lower(ws_as<R>(c->Libuf), ld, np, ws_as<R>(c->mpad), ws_as<R>(c->yv), s));
+  GP_TRY(launch_dot(ws_as<R>(c->yv), ws_as<R>(c->yv), np, c->scal + 6, s));
+  return launch_trmv_lower_t(ws_as<R>(c->Libuf), ld, np, ws_as<R>(c->yv), ws_as<R>(c->bv), c->trmv_part, s);
+}
+
+// ---- pull-back of an n x n adjoint to the d x d metric
+// Adjoint pass over the lower tiles of W: A_w into A (both triangles), t into tvec, the sums into scal[7..9].
+template <typename R>
+static int adjoint_pass(gpfit_ctx* c, hipStream_t s, const R* W, const R* Cos, const R* bv, const R* q, const R* wl, int n,
+                        int np, R* A, R* tvec) {
+  GP_TRY(launch_adjoint(W, Cos, (int64_t)np, bv, q, n, np, A, c->upart, c->vpart, c->sumA_part, s));
+  const int t64 = np / 64;
+  return launch_adjoint_reduce(c->upart, c->vpart, c->sumA_part, t64, t64 * (t64 + 1) / 2, q, wl, n, np, tvec, c->rpad,
+                               c->scal + 7, s);
+}
+// out [dp][dp] = Xa^T Yb over np rows: split-k into the slabs of Mpart, added in slab order.  prof: the product is
+// counted by a profile (gpfit_set_profile(c, 1)) -- so far only for the full-rank unit (post_join_list); the
+// truncated-rank closures' profiles never counted theirs, and their launch counts stay as they were.
+template <typename R>
+static int xty(gpfit_ctx* c, hipStream_t s, const R* Xa, const R* Yb, int np, int dp, R* out, bool prof) {
+  GemmArgsT<R> g{};
+  g.A = Xa; g.B = Yb; g.C = ws_as<R>(c->Mpart);
+  g.lda = dp; g.ldb = dp; g.ldc = dp;
+  g.M = dp; g.N = dp; g.K = np;
+  g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
+  g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
+  if (prof) {
+    ProfScope ps(s, g_prof ? gemm_flops(g) : 0.0, (g_prof && gemm_pick_tile(g) != TILE) ? 3 : 0);
+    GP_TRY(launch_gemm(g, s));
+  } else {
+    GP_TRY(launch_gemm(g, s));
+  }
+  return launch_reduce_slices(ws_as<R>(c->Mpart), (int64_t)dp * dp, c->split_k_M, out, (int64_t)dp * dp, s);
+}
+// Mmat = Xm^T (A_w + diag t) Xm for the adjoint W of acosker(x, x) on n stimuli (q, Cos, Xm theirs; A: np x np
+// scratch), with the b b^T and dKvec terms the caller left in bv / wl.  The contraction with dC_p
+// (launch_metric_contract) is the caller's: the sparse closure adds two more d x d matrices first.
+static int pullback_to_metric(gpfit_ctx* c, hipStream_t s, const double* W, const double* Cos, const double* q, int n,
+                              int np, int dp, double* A, const double* Xm) {
+  GP_TRY(adjoint_pass<double>(c, s, W, Cos, c->bv, q, c->wl, n, np, A, c->tvec));
+  GP_TRY(gemm<double>(s, 1, 1, np, dp, np, 1.0, A, np, Xm, dp, 0.0, c->Ybuf, dp, 0, 0, 0));
+  GP_TRY(launch_rowscale_add(c->Ybuf, dp, Xm, dp, c->tvec, np, dp, s));
+  return xty<double>(c, s, Xm, c->Ybuf, np, dp, c->Mmat, false);
+}
+
+// ---- the n_kept x n_kept algebra of the truncated-rank closures (nb = n_kept padded; leading dimension nb), in the
+// scratch matrices S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV.
+// K~_b (packed into S1) = L L^T with L^-1 (utils.py:2067) and V_b (packed into Va) = L_V L_V^T (log|V_b|, :1326) in
+// lock step, the V_b chain in the caller's four work matrices; then K~_b^-1 = L^-T L^-1 in S1 and V_b in S2, both
+// stored in full with the identity on the padding.
+static int projected_factor(gpfit_ctx* c, hipStream_t s, const double* V_b, int64_t ldvb, int nk, int nb, double* Va,
+                            double* Vl, double* Vli, double* Vt) {
+  double *S1 = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;
+  const int64_t lb = nb;
+  CholBatchT<double> cb;
+  cb.nb = 2;
+  cb.A[0] = S1; cb.L[0] = S2; cb.Li[0] = S3; cb.Tmp[0] = S4; cb.info[0] = c->info + 0;
+  cb.A[1] = Va; cb.L[1] = Vl; cb.Li[1] = Vli; cb.Tmp[1] = Vt; cb.info[1] = c->info + 1;
+  cb.ld = lb; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
+  GP_TRY(potrf_lockstep<double>(cb, 0, nb, 1u, s));
+  GP_TRY(launch_logdet(Vl, lb, nk, c->scal + 40, s));
+  GP_TRY(launch_logdet(S2, lb, nk, c->scal + 3, s));
+  GP_TRY(gemm<double>(s, 1, 1, nb, nb, nb, 1.0, S3, lb, S3, lb, 0.0, S1, lb, 1, 2, 1));
+  GP_TRY(launch_symmetrize(S1, lb, nb, s));
+  GP_TRY(launch_pack_lower(V_b, ldvb, nk, S2, lb, nb, s));
+  return launch_symmetrize(S2, lb, nb, s);
+}
+// K~_b^-1 V_b in S3, its trace tr(K~_b^-1 V_b) in scal[5], P1 = K~_b^-1 V_b K~_b^-1 in S4.  (The two closures form
+// a V_b on different sides of this stage, and b = K~_b^-1 m_b behind it.)
+static int projected_kl_products(gpfit_ctx* c, hipStream_t s, int nk, int nb) {
+  double *Ki = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;
+  const int64_t lb = nb;
+  GP_TRY(gemm<double>(s, 0, 1, nb, nb, nb, 1.0, Ki, lb, S2, lb, 0.0, S3, lb, 0, 0, 0));
+  GP_TRY(launch_proj_trace(S3, lb, nk, c->scal + 5, s));
+  return gemm<double>(s, 0, 1, nb, nb, nb, 1.0, S3, lb, Ki, lb, 0.0, S4, lb, 0, 0, 0);
+}
+
+// ---- host assembly of an evaluation's 16 output scalars from the device scalars (c->scal_host, c->info_host)
+// the part of the sigma_0 row every closure has, derived from utils.py:996-1004 / 1036
+static double sigma0_row_metric(const double* sc, double sigma0) { return sigma0 * (2.0 * sc[9] + 2.0 * sc[7]); }
+// d(loss)/d(theta) = dKL - dL (utils.py:2097-2099): the metric rows come from the contraction, the sigma_0 row in
+// closed form from the caller
+static void grad_rows(const double* sc, double sigma0_row, double* g6) {
+  g6[0] = sigma0_row;
+  g6[1] = sc[13];  // eps_0x
+  g6[2] = sc[14];  // eps_0y
+  g6[3] = sc[11];  // -2log2beta
+  g6[4] = sc[12];  // -log2rho2
+  g6[5] = sc[10];  // Amp
+}
+// pad: what the identity padding of both factors contributes to scal[5] = ||L^-1 L_V||_F^2 (np - n for the full-rank
+// unit, whose trace is that norm; 0 for the truncated-rank closures, whose trace kernel stops at n_kept).
+// err_K / err_V: the messages of the two Cholesky failures, whose LAPACK info is the return value.
+static int assemble_out(gpfit_ctx* c, double A, double lambda0, double sigma0_row, int pad, int d, int want_grad,
+                        const char* err_K, const char* err_V, double* out_host) {
+  const double* sc = c->scal_host;
+  const double loglik = A * sc[0] + lambda0 * sc[1] - sc[2];                   // utils.py:1243
+  const double trKinvV = sc[5] - (double)pad;
+  const double logdetV = sc[40];
+  const double KL = -0.5 * logdetV + 0.5 * sc[3] + 0.5 * sc[6] + 0.5 * trKinvV;  // utils.py:1326
+  out_host[0] = -(loglik - KL);                                                // utils.py:2087-2089
+  out_host[1] = loglik;
+  out_host[2] = KL;
+  if (want_grad) grad_rows(sc, sigma0_row, out_host + 3);
+  else
+    for (int i = 0; i < 6; ++i) out_host[3 + i] = 0.0;
+  out_host[9] = sc[3];
+  out_host[10] = logdetV;
+  out_host[11] = trKinvV;
+  out_host[12] = sc[6];
+  out_host[13] = (double)d;
+  out_host[14] = (double)c->info_host[0];
+  out_host[15] = (double)c->info_host[1];
+  if (c->info_host[0] != 0) {
+    set_error(err_K);
+    return c->info_host[0];
+  }
+  if (c->info_host[1] != 0) {
+    set_error(err_V);
+    return c->info_host[1];
+  }
+  return 0;
+}
+
 // Everything after the join of the two factorisation chains: T = L^-1 L_V and its norm, and (with
 // gradients) Q = I - T T^T, the two-sided product W, the adjoint pass and the pull-back to the metric.
 // Templated separately from the first half of the unit so that the mixed-precision mode (fp64
@@ -572,6 +790,35 @@ struct PostJoin {
   const R *Li, *LV, *Cos, *bv, *q, *wl, *Xm, *Cmat;           // inputs
   R *T, *W, *Z, *H, *A, *Y, *tvec, *Mpart, *Mmat;             // work matrices (np^2), Y [np][dp], Mpart / Mmat
 };
+template <typename R>
+static PostJoin<R> post_join_args(gpfit_ctx* c) {
+  auto RP = ws_as<R>;
+  return PostJoin<R>{RP(c->Libuf), RP(c->LVbuf), RP(c->Cos), RP(c->bv), RP(c->q), RP(c->wl), RP(c->Xm), RP(c->Cmat),
+                     RP(c->Tbuf), RP(c->Wbuf), RP(c->Zbuf), RP(c->Tmp), RP(c->Abuf), RP(c->Ybuf), RP(c->tvec),
+                     RP(c->Mpart), RP(c->Mmat)};
+}
+// Mixed precision: fp64 factorisations, log-determinants and likelihood; fp32 for the N^3-heavy products T, Q, W and
+// the pull-back (T's norm, the trace term of the KL, is therefore fp32-derived: 2e-9 on the loss at N = 8192).  This
+// is the hand-over: single-precision copies of the factors and of the O(N^2) / O(N) operands of the adjoint pass.
+// Li -> Kbuf (its input was destroyed by the factorisation), L_V -> Vbuf (likewise; kept while the V factor is
+// reused), cos(delta) -> TmpV, vectors and the d x d metric into spare buffers.
+static int demote_for_mixed(gpfit_ctx* c, bool reuse_V, int np, int dp, hipStream_t s, PostJoin<float>* pf) {
+  auto F = ws_as<float>;
+  const int64_t nn = (int64_t)np * np;
+  GP_TRY((launch_reduce_slices<double, float>(c->Libuf, nn, 1, F(c->Kbuf), nn, s)));
+  if (!(reuse_V && c->lv32_valid)) GP_TRY((launch_reduce_slices<double, float>(c->LVbuf, nn, 1, F(c->Vbuf), nn, s)));
+  c->lv32_valid = true;
+  GP_TRY((launch_reduce_slices<double, float>(c->Cos, nn, 1, F(c->TmpV), nn, s)));
+  GP_TRY((launch_reduce_slices<double, float>(c->bv, np, 1, F(c->q2), np, s)));
+  GP_TRY((launch_reduce_slices<double, float>(c->q, np, 1, F(c->dq1), np, s)));
+  GP_TRY((launch_reduce_slices<double, float>(c->wl, np, 1, F(c->dq2), np, s)));
+  GP_TRY((launch_reduce_slices<double, float>(c->Xm, (int64_t)np * dp, 1, F(c->Xt2), (int64_t)np * dp, s)));
+  GP_TRY((launch_reduce_slices<double, float>(c->Cmat, (int64_t)dp * dp, 1, F(c->dCpad), (int64_t)dp * dp, s)));
+  *pf = PostJoin<float>{F(c->Kbuf), F(c->Vbuf), F(c->TmpV), F(c->q2), F(c->dq1), F(c->dq2), F(c->Xt2), F(c->dCpad),
+                        F(c->Tbuf), F(c->Wbuf), F(c->Zbuf), F(c->Tmp), F(c->Abuf), F(c->Ybuf), F(c->tvec),
+                        F(c->Mpart), F(c->Mmat)};
+  return 0;
+}
 // cnt units at once (the units of a group, gpfit_fit_eval_batch; cnt = 1: the single unit): every product goes
 // through gemm_list / two_sided_list -- one pointer-batched launch where a single unit's product cannot fill the
 // chip, unit by unit through the ordinary launcher (balanced schedules, fused epilogues) where it can -- and the
@@ -632,13 +879,8 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
     GP_TRY(two_sided_list<R>(cnt, tb, r0, np, s));
   }
   phase(6, s);
-  const int t64 = np / 64;
-  for (int i = 0; i < cnt; ++i) {
-    gpfit_ctx* c = cs[i];
-    GP_TRY(launch_adjoint(a[i].T, a[i].Cos, ld, a[i].bv, a[i].q, n, np, a[i].A, c->upart, c->vpart, c->sumA_part, s));
-    GP_TRY(launch_adjoint_reduce(c->upart, c->vpart, c->sumA_part, t64, t64 * (t64 + 1) / 2, a[i].q, a[i].wl, n, np,
-                                 a[i].tvec, c->rpad, c->scal + 7, s));
-  }
+  for (int i = 0; i < cnt; ++i)
+    GP_TRY(adjoint_pass<R>(cs[i], s, a[i].T, a[i].Cos, a[i].bv, a[i].q, a[i].wl, n, np, a[i].A, a[i].tvec));
   // pull the contraction with dK~ back to the d x d metric: M = X^T (Aw + diag t) X   (units with the same
   // masked pixel count share the launch)
   {
@@ -652,26 +894,20 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
   for (int i = 0; i < cnt; ++i) {
     gpfit_ctx* c = cs[i];
     GP_TRY(launch_rowscale_add(a[i].Y, dp[i], a[i].Xm, dp[i], a[i].tvec, np, dp[i], s));
-    GemmArgsT<R> g{};
-    g.A = a[i].Xm; g.B = a[i].Y; g.C = a[i].Mpart;
-    g.lda = dp[i]; g.ldb = dp[i]; g.ldc = dp[i];
-    g.M = dp[i]; g.N = dp[i]; g.K = np;
-    g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
-    g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp[i] * dp[i];
-    {
-      ProfScope ps(s, g_prof ? gemm_flops(g) : 0.0, (g_prof && gemm_pick_tile(g) != TILE) ? 3 : 0);
-      GP_TRY(launch_gemm(g, s));
-    }
-    GP_TRY(launch_reduce_slices(a[i].Mpart, (int64_t)dp[i] * dp[i], c->split_k_M, a[i].Mmat, (int64_t)dp[i] * dp[i], s));
+    GP_TRY(xty<R>(c, s, a[i].Xm, a[i].Y, np, dp[i], a[i].Mmat, true));
     GP_TRY(launch_metric_contract(th[i], c->pix, d[i], n_rows, n_cols, a[i].Cmat, dp[i], a[i].Mmat, dp[i], c->scal + 10, c->upart,
                                   c->info + 3, s));
   }
   return 0;
 }
-template <typename R, typename PhaseFn>
-static int post_join(gpfit_ctx* c, const PostJoin<R>& a, const Theta& th, int n, int np, int d, int dp, int n_rows,
-                     int n_cols, int want_grad, hipStream_t s, PhaseFn&& phase) {
-  return post_join_list<R>(1, &c, &a, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, s, phase);
+
+// what gpfit_fit_eval_finish needs to collect the evaluation just enqueued on c.  use_done: it waits for the
+// group's completion event (c->pend.done) instead of the stream.
+static void set_pending(gpfit_ctx* c, hipStream_t s, double A, double lambda0, double sigma0, int n, int np, int d,
+                        int want_grad, int elem_bytes, bool use_done) {
+  c->pend.active = true; c->pend.stream = s; c->pend.A = A; c->pend.lambda0 = lambda0; c->pend.sigma0 = sigma0;
+  c->pend.n = n; c->pend.np = np; c->pend.d = d; c->pend.want_grad = want_grad; c->pend.elem_bytes = elem_bytes;
+  c->pend.use_done = use_done;
 }
 
 // The fused unit of work, templated on the scalar type of the device data: fp64 is the
@@ -685,35 +921,18 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
                          int n_rows, int n_cols, const R* X, int64_t ldx, int64_t N, const R* r, const R* m,
                          const R* V, int64_t ldv, double logA, double lambda0, int want_grad, double* out_host,
                          R* lam_m_out, R* lam_var_out, R* f_out) {
-  auto RP = [](double* b) { return reinterpret_cast<R*>(b); };  // workspace is allocated for fp64
+  auto RP = ws_as<R>;
   if (!c || !theta || !X || !r || !m || !V || !out_host || N <= 0) {
     set_error("gpfit_fit_eval: bad argument");
     return -3;
   }
   GP_CTX_ENTER(c, "gpfit_fit_eval");
-  const double inf = std::numeric_limits<double>::infinity();
-  if (lower && upper && check_limits(theta, lower, upper) != 0) {
-    // utils.py:2020-2028: out-of-box theta -> infinite loss and infinite gradients
-    out_host[0] = inf;
-    out_host[1] = out_host[2] = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < 6; ++i) out_host[3 + i] = inf;
-    return -2;
-  }
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)N, np = (int)round_up(N, TILE);
-  const int dfull = n_rows * n_cols;
-  if (np > c->np_cap || dfull > c->dfull_cap) {
-    set_error("gpfit_fit_eval: problem larger than the context capacity");
-    return -3;
-  }
-  const int d = compute_mask(theta, n_rows, n_cols, nullptr, c->pix_host);
-  const int dp = (int)round_up(d, 32);
-  if (d <= 0 || dp > c->dp_cap) {
-    set_error("gpfit_fit_eval: masked pixel count is zero or exceeds the context capacity");
-    return -3;
-  }
-  const Theta th = make_theta(theta);
-  const double s0sq = th.sigma0 * th.sigma0;
+  Admitted ad;
+  GP_TRY(admit(c, "gpfit_fit_eval", "the context", theta, lower, upper, n_rows, n_cols, np, out_host, &ad));
+  const int d = ad.d, dp = ad.dp;
+  const Theta th = ad.th;
   const double A = std::exp(logA);
   const int64_t ld = np;
   c->cur_n = n; c->cur_np = np; c->cur_d = d; c->cur_dp = dp;
@@ -762,18 +981,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   }
 
   // ---- main stream: metric, kernel matrix, moments, Cholesky of K~ with its inverse
-  GP_TRY(launch_localker<R>(th, c->pix, d, dp, n_rows, n_cols, RP(c->Cmat), dp, nullptr, s));
-  GP_TRY(launch_gather(X, ldx, n, c->pix, d, dp, np, RP(c->Xt), ld, RP(c->Xm), dp, s));
-  GP_TRY(gemm<R>(s, 1, 1, dp, np, dp, 1.0, RP(c->Cmat), dp, RP(c->Xt), ld, 0.0, RP(c->XCt), ld, 0, 0, 0));
-  GP_TRY(launch_qvec(RP(c->Xt), RP(c->XCt), ld, dp, n, np, s0sq, RP(c->Kvec), RP(c->q), s));
-  {
-    GramArgsT<R> g{};
-    g.XCt = RP(c->XCt); g.Xt = RP(c->Xt); g.q1 = RP(c->q); g.q2 = RP(c->q); g.Kout = RP(c->Kbuf); g.Cos = RP(c->Cos);
-    g.ld1 = ld; g.ld2 = ld; g.ldk = ld; g.np1 = np; g.np2 = np; g.nv1 = n; g.nv2 = n; g.Kd = dp;
-    g.s0sq = s0sq; g.lower = 1; g.pad_identity = 1;
-    ProfScope ps(s, (double)np * (np + TILE) * dp, 2);
-    GP_TRY(launch_gram(g, s));
-  }
+  GP_TRY(build_kernel<R>(c, s, th, d, dp, n_rows, n_cols, X, ldx, n, np, 0));
   GP_TRY(launch_moments(RP(c->Kvec), RP(c->q), RP(c->Cos), ld, V, ldv, m, r, n, A, lambda0, RP(c->lam_m), RP(c->lam_var), RP(c->fvec),
                         RP(c->wl), c->scal, c->sumA_part, c->info + 2, s));
   phase(1, s);
@@ -790,40 +998,17 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
     phase(3, s);
   }
   GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + 3, s));
-  GP_TRY(launch_trmv_lower(RP(c->Libuf), ld, np, RP(c->mpad), RP(c->yv), s));       // y = L^-1 m
-  GP_TRY(launch_dot(RP(c->yv), RP(c->yv), np, c->scal + 6, s));                  // m^T K~^-1 m
-  GP_TRY(launch_trmv_lower_t(RP(c->Libuf), ld, np, RP(c->yv), RP(c->bv), c->trmv_part, s));  // b = K~^-1 m
+  GP_TRY(solve_mean<R>(c, np, s));
 
   phase(2, s);
   // ---- everything that needs both factors
-  {
-    PostJoin<R> pj{RP(c->Libuf), RP(c->LVbuf), RP(c->Cos), RP(c->bv), RP(c->q), RP(c->wl), RP(c->Xm), RP(c->Cmat),
-                   RP(c->Tbuf), RP(c->Wbuf), RP(c->Zbuf), RP(c->Tmp), RP(c->Abuf), RP(c->Ybuf), RP(c->tvec),
-                   RP(c->Mpart), RP(c->Mmat)};
-    if (mixed_grad) {
-      // fp64 factorisations, log-determinants and likelihood; fp32 for the N^3-heavy products T, Q, W and the
-      // pull-back (T's norm, the trace term of the KL, is therefore fp32-derived: 2e-9 on the loss at N = 8192):
-      // single-precision copies of the factors and of the O(N^2) / O(N) operands of the adjoint pass.
-      // Li -> Kbuf (its input was destroyed by the factorisation), L_V -> Vbuf (likewise; kept while the
-      // V factor is reused), cos(delta) -> TmpV, vectors and the d x d metric into spare buffers.
-      auto F = [](double* b) { return reinterpret_cast<float*>(b); };
-      const int64_t nn = (int64_t)np * np;
-      GP_TRY((launch_reduce_slices<double, float>(c->Libuf, nn, 1, F(c->Kbuf), nn, s)));
-      if (!(reuse_V && c->lv32_valid)) GP_TRY((launch_reduce_slices<double, float>(c->LVbuf, nn, 1, F(c->Vbuf), nn, s)));
-      c->lv32_valid = true;
-      GP_TRY((launch_reduce_slices<double, float>(c->Cos, nn, 1, F(c->TmpV), nn, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->bv, np, 1, F(c->q2), np, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->q, np, 1, F(c->dq1), np, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->wl, np, 1, F(c->dq2), np, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->Xm, (int64_t)np * dp, 1, F(c->Xt2), (int64_t)np * dp, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->Cmat, (int64_t)dp * dp, 1, F(c->dCpad), (int64_t)dp * dp, s)));
-      PostJoin<float> pf{F(c->Kbuf), F(c->Vbuf), F(c->TmpV), F(c->q2), F(c->dq1), F(c->dq2), F(c->Xt2), F(c->dCpad),
-                         F(c->Tbuf), F(c->Wbuf), F(c->Zbuf), F(c->Tmp), F(c->Abuf), F(c->Ybuf), F(c->tvec),
-                         F(c->Mpart), F(c->Mmat)};
-      GP_TRY(post_join<float>(c, pf, th, n, np, d, dp, n_rows, n_cols, want_grad, s, phase));
-    } else {
-      GP_TRY(post_join<R>(c, pj, th, n, np, d, dp, n_rows, n_cols, want_grad, s, phase));
-    }
+  if (mixed_grad) {
+    PostJoin<float> pf;
+    GP_TRY(demote_for_mixed(c, reuse_V, np, dp, s, &pf));
+    GP_TRY(post_join_list<float>(1, &c, &pf, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, s, phase));
+  } else {
+    const PostJoin<R> pj = post_join_args<R>(c);
+    GP_TRY(post_join_list<R>(1, &c, &pj, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, s, phase));
   }
 
   if (lam_m_out) GP_HIP(hipMemcpyAsync(lam_m_out, RP(c->lam_m), (size_t)n * sizeof(R), hipMemcpyDeviceToDevice, s));
@@ -834,9 +1019,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   phase(7, s);
   c->phase_valid = (c->profile == 2 && want_grad && !reuse_V);
   c->last_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-  c->pend.active = true; c->pend.stream = s; c->pend.A = A; c->pend.lambda0 = lambda0; c->pend.sigma0 = th.sigma0;
-  c->pend.n = n; c->pend.np = np; c->pend.d = d; c->pend.want_grad = want_grad; c->pend.elem_bytes = (int)sizeof(R);
-  c->pend.use_done = false;
+  set_pending(c, s, A, lambda0, th.sigma0, n, np, d, want_grad, (int)sizeof(R), false);
   if (async_call) return 0;
   return fit_eval_finish(c, out_host);
 }
@@ -856,7 +1039,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
                                const double* upper, int n_rows, int n_cols, const R* const* X, int64_t ldx, int64_t N,
                                const R* const* r, const R* const* m, const R* const* V, int64_t ldv, const double* logA,
                                const double* lambda0, int want_grad, double* out_host, int* rc_out) {
-  auto RP = [](double* b) { return reinterpret_cast<R*>(b); };
+  auto RP = ws_as<R>;
   if (!cs || nu <= 0 || 2 * nu > GEMM_MAXB || !theta6 || !X || !r || !m || !V || !logA || !lambda0 || !out_host || !rc_out ||
       N <= 0) {
     set_error("gpfit_fit_eval_batch: bad argument (1 .. 16 units per call)");
@@ -884,9 +1067,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   DeviceGuard device_guard(cs[0]->device);
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)N, np = (int)round_up(N, TILE);
-  const int dfull = n_rows * n_cols;
   const int64_t ld = np;
-  const double inf = std::numeric_limits<double>::infinity();
   const bool mixed_grad = (want_grad & 8) != 0 && sizeof(R) == 8 && (want_grad & 1);
   const bool want_reuse = (want_grad & 2) != 0;
   want_grad &= 1;
@@ -897,30 +1078,16 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   int na = 0;
   for (int u = 0; u < nu; ++u) {
     gpfit_ctx* c = cs[u];
-    const double* theta = theta6 + 6 * u;
-    double* out = out_host + 16 * u;
-    rc_out[u] = 0;
-    if (lower && upper && check_limits(theta, lower, upper) != 0) {   // utils.py:2020-2028
-      out[0] = inf;
-      out[1] = out[2] = std::numeric_limits<double>::quiet_NaN();
-      for (int i = 0; i < 6; ++i) out[3 + i] = inf;
-      rc_out[u] = -2;
-      continue;
-    }
-    if (np > c->np_cap || dfull > c->dfull_cap) {
-      set_error("gpfit_fit_eval_batch: problem larger than a context's capacity");
-      return -3;
-    }
-    const int d = compute_mask(theta, n_rows, n_cols, nullptr, c->pix_host);
-    const int dp = (int)round_up(d, 32);
-    if (d <= 0 || dp > c->dp_cap) {
-      set_error("gpfit_fit_eval_batch: masked pixel count is zero or exceeds a context's capacity");
-      return -3;
-    }
+    Admitted ad;
+    const int rc = admit(c, "gpfit_fit_eval_batch", "a context's", theta6 + 6 * u, lower, upper, n_rows, n_cols, np,
+                         out_host + 16 * u, &ad);
+    rc_out[u] = rc == -2 ? -2 : 0;
+    if (rc == -2) continue;
+    if (rc != 0) return rc;
     Unit& q = un[na++];
-    q.c = c; q.u = u; q.d = d; q.dp = dp; q.th = make_theta(theta); q.A = std::exp(logA[u]);
+    q.c = c; q.u = u; q.d = ad.d; q.dp = ad.dp; q.th = ad.th; q.A = std::exp(logA[u]);
     q.reuse_V = want_reuse && c->lv_valid && c->lv_n == n && c->lv_bytes == (int)sizeof(R);
-    c->cur_n = n; c->cur_np = np; c->cur_d = d; c->cur_dp = dp;
+    c->cur_n = n; c->cur_np = np; c->cur_d = q.d; c->cur_dp = q.dp;
     c->phase_valid = false;
     c->side_ev_next = 0;
   }
@@ -949,20 +1116,8 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   for (int i = 0; i < na; ++i) {
     Unit& q = un[i];
     gpfit_ctx* c = q.c;
-    const int d = q.d, dp = q.dp;
-    const double s0sq = q.th.sigma0 * q.th.sigma0;
     g_main_sk_ws = c0->sk_ws[0];
-    GP_TRY(launch_localker<R>(q.th, c->pix, d, dp, n_rows, n_cols, RP(c->Cmat), dp, nullptr, s));
-    GP_TRY(launch_gather(X[q.u], ldx, n, c->pix, d, dp, np, RP(c->Xt), ld, RP(c->Xm), dp, s));
-    GP_TRY(gemm<R>(s, 1, 1, dp, np, dp, 1.0, RP(c->Cmat), dp, RP(c->Xt), ld, 0.0, RP(c->XCt), ld, 0, 0, 0));
-    GP_TRY(launch_qvec(RP(c->Xt), RP(c->XCt), ld, dp, n, np, s0sq, RP(c->Kvec), RP(c->q), s));
-    {
-      GramArgsT<R> g{};
-      g.XCt = RP(c->XCt); g.Xt = RP(c->Xt); g.q1 = RP(c->q); g.q2 = RP(c->q); g.Kout = RP(c->Kbuf); g.Cos = RP(c->Cos);
-      g.ld1 = ld; g.ld2 = ld; g.ldk = ld; g.np1 = np; g.np2 = np; g.nv1 = n; g.nv2 = n; g.Kd = dp;
-      g.s0sq = s0sq; g.lower = 1; g.pad_identity = 1;
-      GP_TRY(launch_gram(g, s));
-    }
+    GP_TRY(build_kernel<R>(c, s, q.th, q.d, q.dp, n_rows, n_cols, X[q.u], ldx, n, np, 0));
     GP_TRY(launch_moments(RP(c->Kvec), RP(c->q), RP(c->Cos), ld, V[q.u], ldv, m[q.u], r[q.u], n, q.A, lambda0[q.u], RP(c->lam_m),
                           RP(c->lam_var), RP(c->fvec), RP(c->wl), c->scal, c->sumA_part, c->info + 2, s));
     if (!q.reuse_V) {
@@ -998,32 +1153,12 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   for (int i = 0; i < na; ++i) {
     Unit& q = un[i];
     gpfit_ctx* c = q.c;
-    const int dp = q.dp;
-    cl[i] = c; thl[i] = q.th; dl[i] = q.d; dpl[i] = dp;
+    cl[i] = c; thl[i] = q.th; dl[i] = q.d; dpl[i] = q.dp;
     if (!q.reuse_V) GP_TRY(launch_logdet_pair(RP(c->Lbuf), c->scal + 3, RP(c->LVbuf), c->scal + 40, ld, n, s));
     else GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + 3, s));
-    GP_TRY(launch_trmv_lower(RP(c->Libuf), ld, np, RP(c->mpad), RP(c->yv), s));
-    GP_TRY(launch_dot(RP(c->yv), RP(c->yv), np, c->scal + 6, s));
-    GP_TRY(launch_trmv_lower_t(RP(c->Libuf), ld, np, RP(c->yv), RP(c->bv), c->trmv_part, s));
-    pjl[i] = PostJoin<R>{RP(c->Libuf), RP(c->LVbuf), RP(c->Cos), RP(c->bv), RP(c->q), RP(c->wl), RP(c->Xm), RP(c->Cmat),
-                         RP(c->Tbuf), RP(c->Wbuf), RP(c->Zbuf), RP(c->Tmp), RP(c->Abuf), RP(c->Ybuf), RP(c->tvec),
-                         RP(c->Mpart), RP(c->Mmat)};
-    if (mixed_grad) {
-      auto F = [](double* b) { return reinterpret_cast<float*>(b); };
-      const int64_t nn = (int64_t)np * np;
-      GP_TRY((launch_reduce_slices<double, float>(c->Libuf, nn, 1, F(c->Kbuf), nn, s)));
-      if (!(q.reuse_V && c->lv32_valid)) GP_TRY((launch_reduce_slices<double, float>(c->LVbuf, nn, 1, F(c->Vbuf), nn, s)));
-      c->lv32_valid = true;
-      GP_TRY((launch_reduce_slices<double, float>(c->Cos, nn, 1, F(c->TmpV), nn, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->bv, np, 1, F(c->q2), np, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->q, np, 1, F(c->dq1), np, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->wl, np, 1, F(c->dq2), np, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->Xm, (int64_t)np * dp, 1, F(c->Xt2), (int64_t)np * dp, s)));
-      GP_TRY((launch_reduce_slices<double, float>(c->Cmat, (int64_t)dp * dp, 1, F(c->dCpad), (int64_t)dp * dp, s)));
-      pfl[i] = PostJoin<float>{F(c->Kbuf), F(c->Vbuf), F(c->TmpV), F(c->q2), F(c->dq1), F(c->dq2), F(c->Xt2), F(c->dCpad),
-                               F(c->Tbuf), F(c->Wbuf), F(c->Zbuf), F(c->Tmp), F(c->Abuf), F(c->Ybuf), F(c->tvec),
-                               F(c->Mpart), F(c->Mmat)};
-    }
+    GP_TRY(solve_mean<R>(c, np, s));
+    if (mixed_grad) GP_TRY(demote_for_mixed(c, q.reuse_V, np, q.dp, s, &pfl[i]));
+    else pjl[i] = post_join_args<R>(c);
   }
   if (mixed_grad) GP_TRY(post_join_list<float>(na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase));
   else GP_TRY(post_join_list<R>(na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase));
@@ -1047,9 +1182,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
       if (!c->pend.done) GP_HIP(hipEventCreateWithFlags(&c->pend.done, hipEventDisableTiming));
       GP_HIP(hipEventRecord(c->pend.done, s));
     }
-    c->pend.use_done = true;
-    c->pend.active = true; c->pend.stream = s; c->pend.A = q.A; c->pend.lambda0 = lambda0[q.u]; c->pend.sigma0 = q.th.sigma0;
-    c->pend.n = n; c->pend.np = np; c->pend.d = q.d; c->pend.want_grad = want_grad; c->pend.elem_bytes = (int)sizeof(R);
+    set_pending(c, s, q.A, lambda0[q.u], q.th.sigma0, n, np, q.d, want_grad, (int)sizeof(R), true);
   }
   c0->last_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
   if (batch_times) {
@@ -1075,7 +1208,6 @@ static int grad_pullback_impl(gpfit_ctx* c, void* stream, const double* theta, i
                               int64_t ldx, int64_t N, const double* W, int64_t ldw, const double* gvec,
                               double* out6) {
   using R = double;
-  auto RP = [](double* b) { return b; };
   if (!c || !theta || !X || !W || !gvec || !out6 || N <= 0) {
     set_error("gpfit_grad_pullback: bad argument");
     return -3;
@@ -1083,65 +1215,24 @@ static int grad_pullback_impl(gpfit_ctx* c, void* stream, const double* theta, i
   GP_CTX_ENTER(c, "gpfit_grad_pullback");
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)N, np = (int)round_up(N, TILE);
-  const int dfull = n_rows * n_cols;
-  if (np > c->np_cap || dfull > c->dfull_cap) {
-    set_error("gpfit_grad_pullback: problem larger than the context capacity");
-    return -3;
-  }
-  const int d = compute_mask(theta, n_rows, n_cols, nullptr, c->pix_host);
-  const int dp = (int)round_up(d, 32);
-  if (d <= 0 || dp > c->dp_cap) {
-    set_error("gpfit_grad_pullback: masked pixel count is zero or exceeds the context capacity");
-    return -3;
-  }
-  const Theta th = make_theta(theta);
-  const double s0sq = th.sigma0 * th.sigma0;
-  const int64_t ld = np;
+  Admitted ad;   // (no limits here: theta is wherever the caller's closure was evaluated)
+  GP_TRY(admit(c, "gpfit_grad_pullback", "the context", theta, nullptr, nullptr, n_rows, n_cols, np, nullptr, &ad));
+  const int d = ad.d, dp = ad.dp;
+  const Theta th = ad.th;
   c->lv_valid = false; c->lv32_valid = false;  // the workspace matrices are reused
   g_main_sk_ws = c->sk_ws[0];
   GP_HIP(hipMemcpyAsync(c->pix, c->pix_host, (size_t)d * sizeof(int), hipMemcpyHostToDevice, s));
-  GP_TRY(launch_localker<R>(th, c->pix, d, dp, n_rows, n_cols, RP(c->Cmat), dp, nullptr, s));
-  GP_TRY(launch_gather(X, ldx, n, c->pix, d, dp, np, RP(c->Xt), ld, RP(c->Xm), dp, s));
-  GP_TRY(gemm<R>(s, 1, 1, dp, np, dp, 1.0, RP(c->Cmat), dp, RP(c->Xt), ld, 0.0, RP(c->XCt), ld, 0, 0, 0));
-  GP_TRY(launch_qvec(RP(c->Xt), RP(c->XCt), ld, dp, n, np, s0sq, RP(c->Kvec), RP(c->q), s));
-  {
-    GramArgsT<R> g{};
-    g.XCt = RP(c->XCt); g.Xt = RP(c->Xt); g.q1 = RP(c->q); g.q2 = RP(c->q); g.Kout = RP(c->Kbuf); g.Cos = RP(c->Cos);
-    g.ld1 = ld; g.ld2 = ld; g.ldk = ld; g.np1 = np; g.np2 = np; g.nv1 = n; g.nv2 = n; g.Kd = dp;
-    g.s0sq = s0sq; g.lower = 1; g.pad_identity = 1;
-    GP_TRY(launch_gram(g, s));
-  }
-  GP_TRY(launch_pack_lower(W, ldw, n, RP(c->Wbuf), ld, np, s));
-  GP_HIP(hipMemsetAsync(RP(c->bv), 0, (size_t)np * sizeof(R), s));             // no -1/2 b b^T term here
-  GP_HIP(hipMemsetAsync(RP(c->wl), 0, (size_t)np * sizeof(R), s));
-  GP_TRY(launch_scale_copy<R>(RP(c->wl), gvec, n, -1.0, s));                    // t_i = u_i / q_i + gvec_i
-  GP_TRY(launch_adjoint(RP(c->Wbuf), RP(c->Cos), ld, RP(c->bv), RP(c->q), n, np, RP(c->Abuf), c->upart, c->vpart,
-                        c->sumA_part, s));
-  const int t64 = np / 64;
-  GP_TRY(launch_adjoint_reduce(c->upart, c->vpart, c->sumA_part, t64, t64 * (t64 + 1) / 2, RP(c->q), RP(c->wl), n, np,
-                               RP(c->tvec), c->rpad, c->scal + 7, s));
-  GP_TRY(gemm<R>(s, 1, 1, np, dp, np, 1.0, RP(c->Abuf), ld, RP(c->Xm), dp, 0.0, RP(c->Ybuf), dp, 0, 0, 0));
-  GP_TRY(launch_rowscale_add(RP(c->Ybuf), dp, RP(c->Xm), dp, RP(c->tvec), np, dp, s));
-  {
-    GemmArgsT<R> g{};
-    g.A = RP(c->Xm); g.B = RP(c->Ybuf); g.C = RP(c->Mpart);
-    g.lda = dp; g.ldb = dp; g.ldc = dp;
-    g.M = dp; g.N = dp; g.K = np;
-    g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
-    g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
-    GP_TRY(launch_gemm(g, s));
-    GP_TRY(launch_reduce_slices(RP(c->Mpart), (int64_t)dp * dp, c->split_k_M, RP(c->Mmat), (int64_t)dp * dp, s));
-  }
-  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, RP(c->Cmat), dp, RP(c->Mmat), dp, c->scal + 10, c->upart, c->info + 3, s));
+  GP_TRY(build_kernel<R>(c, s, th, d, dp, n_rows, n_cols, X, ldx, n, np, 0));
+  GP_TRY(launch_pack_lower(W, ldw, n, c->Wbuf, (int64_t)np, np, s));
+  GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)np * sizeof(R), s));             // no -1/2 b b^T term here
+  GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)np * sizeof(R), s));
+  GP_TRY(launch_scale_copy<R>(c->wl, gvec, n, -1.0, s));                    // t_i = u_i / q_i + gvec_i
+  GP_TRY(pullback_to_metric(c, s, c->Wbuf, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm));
+  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   const double* sc = c->scal_host;
-  out6[0] = th.sigma0 * (2.0 * sc[9] + 2.0 * sc[7]) - 2.0 * th.sigma0 * sc[8];  // sigma_0
-  out6[1] = sc[13];  // eps_0x
-  out6[2] = sc[14];  // eps_0y
-  out6[3] = sc[11];  // -2log2beta
-  out6[4] = sc[12];  // -log2rho2
-  out6[5] = sc[10];  // Amp
+  grad_rows(sc, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[8], out6);
   return 0;
 }
 
@@ -1163,28 +1254,13 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
     return -3;
   }
   GP_CTX_ENTER(c, "gpfit_fit_eval_projected");
-  const double inf = std::numeric_limits<double>::infinity();
-  if (lower && upper && check_limits(theta, lower, upper) != 0) {
-    out_host[0] = inf;
-    out_host[1] = out_host[2] = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < 6; ++i) out_host[3 + i] = inf;
-    return -2;
-  }
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)N, np = (int)round_up(N, TILE), nk = (int)n_kept, nb = (int)round_up(n_kept, TILE);
-  const int dfull = n_rows * n_cols;
-  if (np > c->np_cap || dfull > c->dfull_cap) {
-    set_error("gpfit_fit_eval_projected: problem larger than the context capacity");
-    return -3;
-  }
-  const int d = compute_mask(theta, n_rows, n_cols, nullptr, c->pix_host);
-  const int dp = (int)round_up(d, 32);
-  if (d <= 0 || dp > c->dp_cap) {
-    set_error("gpfit_fit_eval_projected: masked pixel count is zero or exceeds the context capacity");
-    return -3;
-  }
-  const Theta th = make_theta(theta);
-  const double s0sq = th.sigma0 * th.sigma0, A = std::exp(logA);
+  Admitted ad;
+  GP_TRY(admit(c, "gpfit_fit_eval_projected", "the context", theta, lower, upper, n_rows, n_cols, np, out_host, &ad));
+  const int d = ad.d, dp = ad.dp;
+  const Theta th = ad.th;
+  const double A = std::exp(logA);
   const int64_t ld = np, lb = nb;
   c->lv_valid = false; c->lv32_valid = false;
   c->side_ev_next = 0;
@@ -1197,22 +1273,9 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   double *mbp = c->mpad, *bvec = c->yv, *gm = c->dq1, *gv = c->dq2;
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
   GP_HIP(hipMemcpyAsync(c->pix, c->pix_host, (size_t)d * sizeof(int), hipMemcpyHostToDevice, s));
-  // (log|V_b| of :1326: V_b is factored together with K~_b below -- one lock-step recursion on this stream, in
-  // four work matrices nothing else needs before the adjoints: Abuf, Wbuf, Zbuf, Tmp)
-  // ---- kernel build (as the full-rank unit): C, X masked, K~ (lower tiles -> mirrored), cos, Kvec, q
-  GP_TRY(launch_localker<R>(th, c->pix, d, dp, n_rows, n_cols, c->Cmat, dp, nullptr, s));
-  GP_TRY(launch_gather(X, ldx, n, c->pix, d, dp, np, c->Xt, ld, c->Xm, dp, s));
-  GP_TRY(gemm<R>(s, 1, 1, dp, np, dp, 1.0, c->Cmat, dp, c->Xt, ld, 0.0, c->XCt, ld, 0, 0, 0));
-  GP_TRY(launch_qvec(c->Xt, c->XCt, ld, dp, n, np, s0sq, c->Kvec, c->q, s));
-  {
-    GramArgsT<R> g{};
-    g.XCt = c->XCt; g.Xt = c->Xt; g.q1 = c->q; g.q2 = c->q; g.Kout = Kt; g.Cos = c->Cos;
-    g.ld1 = ld; g.ld2 = ld; g.ldk = ld; g.np1 = np; g.np2 = np; g.nv1 = n; g.nv2 = n; g.Kd = dp;
-    g.s0sq = s0sq; g.lower = 1; g.pad_identity = 1;
-    g.mirror = 1;   // K~ is multiplied from the left below: stored in full by the tiles themselves
-    ProfScope ps(s, (double)np * (np + TILE) * dp, 2);
-    GP_TRY(launch_gram(g, s));
-  }
+  // ---- kernel build (as the full-rank unit): C, X masked, cos, Kvec, q, and K~ stored in full by the tiles
+  // themselves (mirror): it is multiplied from the left below
+  GP_TRY(build_kernel<R>(c, s, th, d, dp, n_rows, n_cols, X, ldx, n, np, 1));
   // ---- projection (utils.py:2047-2049): K_b = K~ B, K~_b = sym(B^T K_b)
   GP_TRY(launch_pad_copy(B, ldb, n, nk, Bp, lb, np, nb, s));
   GP_HIP(hipMemsetAsync(mbp, 0, (size_t)np * sizeof(double), s));
@@ -1221,29 +1284,14 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   GP_TRY(gemm_splitk<R>(s, 1, 1, nb, nb, np, 1.0, Bp, lb, Kb, lb, S4, lb, splitk_for(nb, nb, np), c->Wbuf, (int64_t)c->np_cap * c->np_cap));
   GP_TRY(launch_symmetrize_avg(S4, lb, nk, s));                                             // :2048
   GP_TRY(launch_pack_lower(S4, lb, nk, S1, lb, nb, s));
+  // (log|V_b| of :1326: V_b is factored together with K~_b -- one lock-step recursion on this stream, in four work
+  // matrices nothing else needs before the adjoints: Abuf, Wbuf, Zbuf, Tmp)
   GP_TRY(launch_pack_lower(V_b, ldvb, nk, c->Abuf, lb, nb, s));
-  {
-    // K~_b = L L^T with L^-1 (:2067) and V_b = L_V L_V^T (log|V_b|, :1326) in lock step
-    CholBatchT<R> cb;
-    cb.nb = 2;
-    cb.A[0] = S1; cb.L[0] = S2; cb.Li[0] = S3; cb.Tmp[0] = S4; cb.info[0] = c->info + 0;
-    cb.A[1] = c->Abuf; cb.L[1] = c->Wbuf; cb.Li[1] = c->Zbuf; cb.Tmp[1] = c->Tmp; cb.info[1] = c->info + 1;
-    cb.ld = lb; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
-    GP_TRY(potrf_lockstep<R>(cb, 0, nb, 1u, s));
-  }
-  GP_TRY(launch_logdet(c->Wbuf, lb, nk, c->scal + 40, s));
-  GP_TRY(launch_logdet(S2, lb, nk, c->scal + 3, s));
-  // K~_b^-1 = L^-T L^-1 (lower tiles, mirrored)
-  GP_TRY(gemm<R>(s, 1, 1, nb, nb, nb, 1.0, S3, lb, S3, lb, 0.0, S1, lb, 1, 2, 1));
-  GP_TRY(launch_symmetrize(S1, lb, nb, s));
+  GP_TRY(projected_factor(c, s, V_b, ldvb, nk, nb, c->Abuf, c->Wbuf, c->Zbuf, c->Tmp));
   double* Ki = S1;
-  // V_b padded (identity on the padding), a V = B V_b, K~_b^-1 V_b and its trace, K~_b^-1 V_b K~_b^-1
-  GP_TRY(launch_pack_lower(V_b, ldvb, nk, S2, lb, nb, s));
-  GP_TRY(launch_symmetrize(S2, lb, nb, s));
+  // a V = B V_b, then K~_b^-1 V_b with its trace and K~_b^-1 V_b K~_b^-1 (P1, in S4)
   GP_TRY(gemm<R>(s, 0, 1, np, nb, nb, 1.0, Bp, lb, S2, lb, 0.0, aV, lb, 0, 0, 0));
-  GP_TRY(gemm<R>(s, 0, 1, nb, nb, nb, 1.0, Ki, lb, S2, lb, 0.0, S3, lb, 0, 0, 0));
-  GP_TRY(launch_proj_trace(S3, lb, nk, c->scal + 5, s));                                     // tr(K~_b^-1 V_b)
-  GP_TRY(gemm<R>(s, 0, 1, nb, nb, nb, 1.0, S3, lb, Ki, lb, 0.0, S4, lb, 0, 0, 0));            // P1
+  GP_TRY(projected_kl_products(c, s, nk, nb));
   GP_TRY(launch_symv_lower(Ki, lb, nb, mbp, bvec, s));                                        // b = K~_b^-1 m_b
   GP_TRY(launch_dot(mbp, bvec, nb, c->scal + 6, s));
   // ---- moments, rate, likelihood pieces (:1090, 1101, 1138, 1243) and the per-point adjoints
@@ -1276,54 +1324,15 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)np * sizeof(R), s));
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)np * sizeof(R), s));
   GP_TRY(launch_scale_copy<R>(c->wl, gv, n, 1.0, s));
-  GP_TRY(launch_adjoint(W, c->Cos, ld, c->bv, c->q, n, np, c->Abuf, c->upart, c->vpart, c->sumA_part, s));
-  const int t64 = np / 64;
-  GP_TRY(launch_adjoint_reduce(c->upart, c->vpart, c->sumA_part, t64, t64 * (t64 + 1) / 2, c->q, c->wl, n, np, c->tvec,
-                               c->rpad, c->scal + 7, s));
-  GP_TRY(gemm<R>(s, 1, 1, np, dp, np, 1.0, c->Abuf, ld, c->Xm, dp, 0.0, c->Ybuf, dp, 0, 0, 0));
-  GP_TRY(launch_rowscale_add(c->Ybuf, dp, c->Xm, dp, c->tvec, np, dp, s));
-  {
-    GemmArgsT<R> g{};
-    g.A = c->Xm; g.B = c->Ybuf; g.C = c->Mpart;
-    g.lda = dp; g.ldb = dp; g.ldc = dp;
-    g.M = dp; g.N = dp; g.K = np;
-    g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
-    g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
-    GP_TRY(launch_gemm(g, s));
-    GP_TRY(launch_reduce_slices(c->Mpart, (int64_t)dp * dp, c->split_k_M, c->Mmat, (int64_t)dp * dp, s));
-  }
+  GP_TRY(pullback_to_metric(c, s, W, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm));
   GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   const double* sc = c->scal_host;
-  const double loglik = A * sc[0] + lambda0 * sc[1] - sc[2];                                 // :1243
-  const double KL = -0.5 * sc[40] + 0.5 * sc[3] + 0.5 * sc[6] + 0.5 * sc[5];                  // :1326
-  out_host[0] = -(loglik - KL);
-  out_host[1] = loglik;
-  out_host[2] = KL;
-  out_host[3] = th.sigma0 * (2.0 * sc[9] + 2.0 * sc[7]) - 2.0 * th.sigma0 * sc[8];
-  out_host[4] = sc[13];
-  out_host[5] = sc[14];
-  out_host[6] = sc[11];
-  out_host[7] = sc[12];
-  out_host[8] = sc[10];
-  out_host[9] = sc[3];
-  out_host[10] = sc[40];
-  out_host[11] = sc[5];
-  out_host[12] = sc[6];
-  out_host[13] = (double)d;
-  out_host[14] = (double)c->info_host[0];
-  out_host[15] = (double)c->info_host[1];
-  if (c->info_host[0] != 0) {
-    set_error("gpfit_fit_eval_projected: Cholesky of the projected K_tilde failed (non-positive pivot)");
-    return c->info_host[0];
-  }
-  if (c->info_host[1] != 0) {
-    set_error("gpfit_fit_eval_projected: Cholesky of V_b failed (non-positive pivot)");
-    return c->info_host[1];
-  }
-  return 0;
+  return assemble_out(c, A, lambda0, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[8], 0, d, 1,
+                      "gpfit_fit_eval_projected: Cholesky of the projected K_tilde failed (non-positive pivot)",
+                      "gpfit_fit_eval_projected: Cholesky of V_b failed (non-positive pivot)", out_host);
 }
 
 // Sparse M-step closure (n_tilde < n_t: K[n_t][n_tilde] != K~, a = K_b K~_b^-1 with non-zero da_p;
@@ -1346,28 +1355,14 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
     return -3;
   }
   GP_CTX_ENTER(c, "gpfit_fit_eval_sparse");
-  const double inf = std::numeric_limits<double>::infinity();
-  if (lower && upper && check_limits(theta, lower, upper) != 0) {
-    out_host[0] = inf;
-    out_host[1] = out_host[2] = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < 6; ++i) out_host[3 + i] = inf;
-    return -2;
-  }
   hipStream_t s = (hipStream_t)stream;
   const int n1 = (int)N, n2 = (int)Ntilde, nk = (int)n_kept;
   const int np1 = (int)round_up(N, TILE), np2 = (int)round_up(Ntilde, TILE), nb = (int)round_up(n_kept, TILE);
-  const int dfull = n_rows * n_cols;
-  if (np1 > c->np_cap || np2 > c->np_cap || dfull > c->dfull_cap) {
-    set_error("gpfit_fit_eval_sparse: problem larger than the context capacity");
-    return -3;
-  }
-  const int d = compute_mask(theta, n_rows, n_cols, nullptr, c->pix_host);
-  const int dp = (int)round_up(d, 32);
-  if (d <= 0 || dp > c->dp_cap) {
-    set_error("gpfit_fit_eval_sparse: masked pixel count is zero or exceeds the context capacity");
-    return -3;
-  }
-  const Theta th = make_theta(theta);
+  Admitted ad;
+  GP_TRY(admit(c, "gpfit_fit_eval_sparse", "the context", theta, lower, upper, n_rows, n_cols, std::max(np1, np2),
+               out_host, &ad));
+  const int d = ad.d, dp = ad.dp;
+  const Theta th = ad.th;
   const double s0sq = th.sigma0 * th.sigma0, A = std::exp(logA);
   const int64_t l2 = np2, lb = nb;
   c->lv_valid = false; c->lv32_valid = false;
@@ -1383,23 +1378,12 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   double *mbp = c->mpad, *bvec = c->yv, *gm = c->dq1, *gv = c->dq2, *gvec = c->hvec;
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
   GP_HIP(hipMemcpyAsync(c->pix, c->pix_host, (size_t)d * sizeof(int), hipMemcpyHostToDevice, s));
-  // ---- kernel objects: C; training side (x: Xt, XCt, q, Kvec), inducing side (xtilde: Xt2, XCt2, q2)
-  GP_TRY(launch_localker<R>(th, c->pix, d, dp, n_rows, n_cols, c->Cmat, dp, nullptr, s));
-  GP_TRY(launch_gather(X, ldx, n1, c->pix, d, dp, np1, c->Xt, (int64_t)np1, X1m, dp, s));
-  GP_TRY(gemm<R>(s, 1, 1, dp, np1, dp, 1.0, c->Cmat, dp, c->Xt, np1, 0.0, c->XCt, np1, 0, 0, 0));
-  GP_TRY(launch_qvec(c->Xt, c->XCt, np1, dp, n1, np1, s0sq, c->Kvec, c->q, s));
-  GP_TRY(launch_gather(Xtilde, ldxt, n2, c->pix, d, dp, np2, c->Xt2, l2, X2m, dp, s));
-  GP_TRY(gemm<R>(s, 1, 1, dp, np2, dp, 1.0, c->Cmat, dp, c->Xt2, l2, 0.0, c->XCt2, l2, 0, 0, 0));
-  GP_TRY(launch_qvec(c->Xt2, c->XCt2, l2, dp, n2, np2, s0sq, c->hvec, c->q2, s));
-  {
-    GramArgsT<R> g{};  // K~ = acosker(xtilde, xtilde): lower tiles, mirrored below
-    g.XCt = c->XCt2; g.Xt = c->Xt2; g.q1 = c->q2; g.q2 = c->q2; g.Kout = Kt; g.Cos = CosT;
-    g.ld1 = l2; g.ld2 = l2; g.ldk = l2; g.np1 = np2; g.np2 = np2; g.nv1 = n2; g.nv2 = n2; g.Kd = dp;
-    g.s0sq = s0sq; g.lower = 1; g.pad_identity = 1;
-    g.mirror = 1;
-    ProfScope ps(s, (double)np2 * (np2 + TILE) * dp, 2);
-    GP_TRY(launch_gram(g, s));
-  }
+  // ---- kernel objects: C; training side (x: Xt, XCt, q, Kvec), inducing side (xtilde: Xt2, XCt2, q2);
+  // K~ = acosker(xtilde, xtilde), lower tiles mirrored by the tiles themselves
+  GP_TRY(build_metric<R>(c, s, th, d, dp, n_rows, n_cols));
+  GP_TRY(kernel_side<R>(c, s, X, ldx, n1, np1, d, dp, s0sq, c->Xt, c->XCt, X1m, c->Kvec, c->q));
+  GP_TRY(kernel_side<R>(c, s, Xtilde, ldxt, n2, np2, d, dp, s0sq, c->Xt2, c->XCt2, X2m, c->hvec, c->q2));
+  GP_TRY(gram_square<R>(s, c->XCt2, c->Xt2, c->q2, Kt, CosT, n2, np2, dp, s0sq, 1));
   {
     GramArgsT<R> g{};  // K = acosker(x, xtilde): rectangular, with its cosine matrix
     g.XCt = c->XCt; g.Xt = c->Xt2; g.q1 = c->q; g.q2 = c->q2; g.Kout = Kr; g.Cos = CosR;
@@ -1420,33 +1404,19 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   GP_TRY(launch_symmetrize_avg(S4, lb, nk, s));
   GP_TRY(launch_pack_lower(S4, lb, nk, S1, lb, nb, s));
   {
-    // K~_b = L L^T with L^-1 and V_b = L_V L_V^T (log|V_b|, :1326) in lock step.  The V_b chain takes four work
-    // matrices that are dead between the projections above and the adjoints below, each of the context's full
-    // np_cap^2 size (nb <= np2 <= np_cap: an nb x nb chain fits whatever n_kept is): Wbuf (free until P2), Kbuf
-    // and Lbuf (K~ and K are consumed by the projections; rewritten as G_a and G_a K~_b^-1 further down) and Abuf
-    // (a V_b is formed behind the chain).  The cosine matrices in Cos / Libuf stay untouched.
+    // The V_b chain of the lock-step factorisation takes four work matrices that are dead between the projections
+    // above and the adjoints below, each of the context's full np_cap^2 size (nb <= np2 <= np_cap: an nb x nb chain
+    // fits whatever n_kept is): Wbuf (free until P2), Kbuf and Lbuf (K~ and K are consumed by the projections;
+    // rewritten as G_a and G_a K~_b^-1 further down) and Abuf (a V_b is formed behind the chain).  The cosine
+    // matrices in Cos / Libuf stay untouched.
     double *Va = c->Wbuf, *Vl = c->Kbuf, *Vli = c->Lbuf, *Vt = c->Abuf;
-    const int64_t slot = (int64_t)nb * nb;
     GP_TRY(launch_pack_lower(V_b, ldvb, nk, Va, lb, nb, s));
-    CholBatchT<R> cb;
-    cb.nb = 2;
-    cb.A[0] = S1; cb.L[0] = S2; cb.Li[0] = S3; cb.Tmp[0] = S4; cb.info[0] = c->info + 0;
-    cb.A[1] = Va; cb.L[1] = Vl; cb.Li[1] = Vli; cb.Tmp[1] = Vt; cb.info[1] = c->info + 1;
-    cb.ld = lb; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
     for (double* p : {Vl, Vli, Vt})   // tiles above the diagonal read as zero
-      GP_HIP(hipMemsetAsync(p, 0, (size_t)slot * sizeof(double), s));
-    GP_TRY(potrf_lockstep<R>(cb, 0, nb, 1u, s));
-    GP_TRY(launch_logdet(Vl, lb, nk, c->scal + 40, s));
+      GP_HIP(hipMemsetAsync(p, 0, (size_t)nb * nb * sizeof(double), s));
+    GP_TRY(projected_factor(c, s, V_b, ldvb, nk, nb, Va, Vl, Vli, Vt));
   }
-  GP_TRY(launch_logdet(S2, lb, nk, c->scal + 3, s));
-  GP_TRY(gemm<R>(s, 1, 1, nb, nb, nb, 1.0, S3, lb, S3, lb, 0.0, S1, lb, 1, 2, 1));
-  GP_TRY(launch_symmetrize(S1, lb, nb, s));
   double* Ki = S1;
-  GP_TRY(launch_pack_lower(V_b, ldvb, nk, S2, lb, nb, s));
-  GP_TRY(launch_symmetrize(S2, lb, nb, s));
-  GP_TRY(gemm<R>(s, 0, 1, nb, nb, nb, 1.0, Ki, lb, S2, lb, 0.0, S3, lb, 0, 0, 0));            // K~_b^-1 V_b
-  GP_TRY(launch_proj_trace(S3, lb, nk, c->scal + 5, s));
-  GP_TRY(gemm<R>(s, 0, 1, nb, nb, nb, 1.0, S3, lb, Ki, lb, 0.0, S4, lb, 0, 0, 0));            // P1
+  GP_TRY(projected_kl_products(c, s, nk, nb));
   GP_TRY(gemm<R>(s, 0, 1, np1, nb, nb, 1.0, Kb, lb, Ki, lb, 0.0, am, lb, 0, 0, 0));           // a
   GP_TRY(gemm<R>(s, 0, 1, np1, nb, nb, 1.0, am, lb, S2, lb, 0.0, aV, lb, 0, 0, 0));           // a V_b
   GP_TRY(launch_symv_lower(Ki, lb, nb, mbp, bvec, s));
@@ -1468,24 +1438,11 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   GP_TRY(launch_symmetrize_avg(c->Wbuf, l2, np2, s));
   GP_TRY(gemm<R>(s, 0, 0, np1, np2, nb, 1.0, GaKi, lb, Bp, lb, 0.0, aV, l2, 0, 0, 0));        // W_K  (a V_b is dead)
   double* WK = aV;
-  // ---- square pull-back on the inducing stimuli (no b b^T term, no dKvec term)
+  // ---- square pull-back on the inducing stimuli (no b b^T term, no dKvec term; A_w into K_b, which is dead).
+  // (bv / wl are cleared over np_cap elements here, over np in the other two closures: each as it always was)
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)c->np_cap * sizeof(R), s));
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)c->np_cap * sizeof(R), s));
-  GP_TRY(launch_adjoint(c->Wbuf, CosT, l2, c->bv, c->q2, n2, np2, Kb, c->upart, c->vpart, c->sumA_part, s));  // K_b is dead
-  const int t64 = np2 / 64;
-  GP_TRY(launch_adjoint_reduce(c->upart, c->vpart, c->sumA_part, t64, t64 * (t64 + 1) / 2, c->q2, c->wl, n2, np2, c->tvec,
-                               c->rpad, c->scal + 7, s));
-  GP_TRY(gemm<R>(s, 1, 1, np2, dp, np2, 1.0, Kb, l2, X2m, dp, 0.0, c->Ybuf, dp, 0, 0, 0));
-  GP_TRY(launch_rowscale_add(c->Ybuf, dp, X2m, dp, c->tvec, np2, dp, s));
-  auto xty = [&](const double* Xa, const double* Yb, int np, double* out) -> int {
-    GemmArgsT<R> g{};
-    g.A = Xa; g.B = Yb; g.C = c->Mpart; g.lda = dp; g.ldb = dp; g.ldc = dp;
-    g.M = dp; g.N = dp; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
-    g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
-    GP_TRY(launch_gemm(g, s));
-    return launch_reduce_slices(c->Mpart, (int64_t)dp * dp, c->split_k_M, out, (int64_t)dp * dp, s);
-  };
-  GP_TRY(xty(X2m, c->Ybuf, np2, c->Mmat));
+  GP_TRY(pullback_to_metric(c, s, c->Wbuf, CosT, c->q2, n2, np2, dp, Kb, X2m));
   // ---- rectangular pull-back (x, xtilde) with gvec = -g_v on the training side (dKvec term)
   GP_TRY(launch_scale_copy<R>(gvec, gv, n1, -1.0, s));
   double* t1 = c->tvec;
@@ -1496,9 +1453,9 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   GP_TRY(launch_rowscale_add(c->Ybuf, dp, X1m, dp, t1, np1, dp, s));
   GP_HIP(hipMemsetAsync(Zm, 0, (size_t)np2 * dp * sizeof(double), s));
   GP_TRY(launch_rowscale_add(Zm, dp, X2m, dp, t2, np2, dp, s));
-  GP_TRY(xty(X1m, c->Ybuf, np1, c->dCpad));
+  GP_TRY(xty<R>(c, s, X1m, c->Ybuf, np1, dp, c->dCpad, false));
   GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
-  GP_TRY(xty(X2m, Zm, np2, c->dCpad));
+  GP_TRY(xty<R>(c, s, X2m, Zm, np2, dp, c->dCpad, false));
   GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
   GP_TRY(launch_symmetrize_avg(c->Mmat, dp, dp, s));
   GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
@@ -1506,35 +1463,12 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   const double* sc = c->scal_host;
-  const double loglik = A * sc[0] + lambda0 * sc[1] - sc[2];
-  const double KL = -0.5 * sc[40] + 0.5 * sc[3] + 0.5 * sc[6] + 0.5 * sc[5];
   const double sum_gvec = 0.5 * A * A * sc[2];                                               // -sum g_v
-  out_host[0] = -(loglik - KL);
-  out_host[1] = loglik;
-  out_host[2] = KL;
-  out_host[3] = th.sigma0 * (2.0 * sc[9] + 2.0 * sc[7]) + th.sigma0 * (2.0 * sc[20] + sc[21] + sc[22]) +
-                2.0 * th.sigma0 * sum_gvec;
-  out_host[4] = sc[13];
-  out_host[5] = sc[14];
-  out_host[6] = sc[11];
-  out_host[7] = sc[12];
-  out_host[8] = sc[10];
-  out_host[9] = sc[3];
-  out_host[10] = sc[40];
-  out_host[11] = sc[5];
-  out_host[12] = sc[6];
-  out_host[13] = (double)d;
-  out_host[14] = (double)c->info_host[0];
-  out_host[15] = (double)c->info_host[1];
-  if (c->info_host[0] != 0) {
-    set_error("gpfit_fit_eval_sparse: Cholesky of the projected K_tilde failed (non-positive pivot)");
-    return c->info_host[0];
-  }
-  if (c->info_host[1] != 0) {
-    set_error("gpfit_fit_eval_sparse: Cholesky of V_b failed (non-positive pivot)");
-    return c->info_host[1];
-  }
-  return 0;
+  return assemble_out(c, A, lambda0,
+                      sigma0_row_metric(sc, th.sigma0) + th.sigma0 * (2.0 * sc[20] + sc[21] + sc[22]) +
+                          2.0 * th.sigma0 * sum_gvec,
+                      0, d, 1, "gpfit_fit_eval_sparse: Cholesky of the projected K_tilde failed (non-positive pivot)",
+                      "gpfit_fit_eval_sparse: Cholesky of V_b failed (non-positive pivot)", out_host);
 }
 
 // Wait for the evaluation enqueued on this context and assemble its 16 host scalars.
@@ -1547,47 +1481,13 @@ int fit_eval_finish(gpfit_ctx* c, double* out_host) {
   DeviceGuard device_guard(c->device);
   if (c->pend.use_done && c->pend.done) GP_HIP(hipEventSynchronize(c->pend.done));
   else GP_HIP(hipStreamSynchronize(c->pend.stream));
-  const int n = c->pend.n, np = c->pend.np, want_grad = c->pend.want_grad;
-  const double A = c->pend.A, lambda0 = c->pend.lambda0, sigma0 = c->pend.sigma0;
-
   const double* sc = c->scal_host;
-  const double loglik = A * sc[0] + lambda0 * sc[1] - sc[2];                   // utils.py:1243
-  // the identity padding of both factors contributes exactly (np - n) to ||L^-1 L_V||_F^2
-  const double trKinvV = sc[5] - (double)(np - n);
-  const double logdetV = sc[40];
-  const double KL = -0.5 * logdetV + 0.5 * sc[3] + 0.5 * sc[6] + 0.5 * trKinvV;  // utils.py:1326
-  out_host[0] = -(loglik - KL);                                                // utils.py:2087-2089
-  out_host[1] = loglik;
-  out_host[2] = KL;
-  if (want_grad) {
-    // d(loss)/d(theta) = dKL - dL (utils.py:2097-2099); metric rows come from the contraction,
-    // the sigma_0 row from the closed form derived from utils.py:996-1004 / 1036.
-    out_host[3] = sigma0 * (2.0 * sc[9] + 2.0 * sc[7]) - 2.0 * sigma0 * sc[8];
-    out_host[4] = sc[13];  // eps_0x
-    out_host[5] = sc[14];  // eps_0y
-    out_host[6] = sc[11];  // -2log2beta
-    out_host[7] = sc[12];  // -log2rho2
-    out_host[8] = sc[10];  // Amp
-  } else {
-    for (int i = 0; i < 6; ++i) out_host[3 + i] = 0.0;
-  }
-  out_host[9] = sc[3];
-  out_host[10] = logdetV;
-  out_host[11] = trKinvV;
-  out_host[12] = sc[6];
-  out_host[13] = (double)c->pend.d;
-  out_host[14] = (double)c->info_host[0];
-  out_host[15] = (double)c->info_host[1];
-  if (c->info_host[0] != 0) {
-    set_error("Cholesky of K_tilde failed: non-positive pivot");
-    return c->info_host[0];
-  }
-  if (c->info_host[1] != 0) {
-    set_error("Cholesky of V failed: non-positive pivot");
-    return c->info_host[1];
-  }
+  const double sigma0 = c->pend.sigma0;
+  GP_TRY(assemble_out(c, c->pend.A, c->pend.lambda0, sigma0_row_metric(sc, sigma0) - 2.0 * sigma0 * sc[8],
+                      c->pend.np - c->pend.n, c->pend.d, c->pend.want_grad, "Cholesky of K_tilde failed: non-positive pivot",
+                      "Cholesky of V failed: non-positive pivot", out_host));
   c->lv_valid = true;
-  c->lv_n = n;
+  c->lv_n = c->pend.n;
   c->lv_bytes = c->pend.elem_bytes;
   return 0;
 }
