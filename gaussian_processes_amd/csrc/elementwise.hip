@@ -384,6 +384,116 @@ int launch_trmv_lower_t(const R* L, int64_t ldl, int np, const R* x, R* z, doubl
   return launch_reduce_slices(partial, np, chunks, z, np, s);
 }
 
+// ---- block forms beside the two triangular products: the dense off-diagonal block of a factor applied to a vector
+// (solve_mean in fit.hip substitutes with L21 instead of multiplying by [L^-1]21).  Same summation patterns as the
+// trmv kernels: a wave per row, or 64 columns x one chunk of TRMV_ROWS rows with the chunks added in order.
+// out_i = y_i - sum_j M[i][j] x_j   (M rows x cols, row-major)
+template <typename R>
+__global__ void gemv_sub_kernel(const R* __restrict__ M, int64_t ldm, int rows, int cols, const R* __restrict__ x,
+                                const R* __restrict__ y, R* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (i >= rows) return;
+  const R* row = M + (int64_t)i * ldm;
+  double v = 0.0;
+#pragma unroll 8
+  for (int j = lane; j < cols; j += 64) v += (double)row[j] * (double)x[j];
+  v = wave_sum(v);
+  if (lane == 0) out[i] = (R)((double)y[i] - v);
+}
+
+template <typename R>
+int launch_gemv_sub(const R* M, int64_t ldm, int rows, int cols, const R* x, const R* y, R* out, hipStream_t s) {
+  if (rows <= 0) return 0;
+  hipLaunchKernelGGL(gemv_sub_kernel<R>, dim3((rows + 3) / 4), dim3(256), 0, s, M, ldm, rows, cols, x, y, out);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// partial[chunk][j] = sum over the chunk's rows of M[i][j] x_i   (cols a multiple of 64)
+template <typename R>
+__global__ void gemv_t_kernel(const R* __restrict__ M, int64_t ldm, int rows, int cols, const R* __restrict__ x,
+                              double* __restrict__ partial) {
+  __shared__ double sh[4][64];
+  const int c = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + c;
+  const int i0 = blockIdx.y * TRMV_ROWS, i1 = min(rows, i0 + TRMV_ROWS);
+  double v = 0.0;
+#pragma unroll 8
+  for (int i = i0 + rl; i < i1; i += 4) v += (double)M[(int64_t)i * ldm + j] * (double)x[i];
+  sh[rl][c] = v;
+  __syncthreads();
+  if (rl == 0) partial[(int64_t)blockIdx.y * cols + j] = sh[0][c] + sh[1][c] + sh[2][c] + sh[3][c];
+}
+
+// out_j = y_j - sum_z partial[z][j]
+template <typename R>
+__global__ void sub_slices_kernel(const double* __restrict__ partial, int cols, int nslice, const R* __restrict__ y,
+                                  R* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cols) return;
+  double v = 0.0;
+  for (int z = 0; z < nslice; ++z) v += partial[(int64_t)z * cols + j];
+  out[j] = (R)((double)y[j] - v);
+}
+
+// out = y - M^T x   (partial: ceil(rows / TRMV_ROWS) * cols doubles)
+template <typename R>
+int launch_gemv_t_sub(const R* M, int64_t ldm, int rows, int cols, const R* x, const R* y, R* out, double* partial,
+                      hipStream_t s) {
+  if (rows <= 0 || cols <= 0) return 0;
+  if (cols % 64) {
+    set_error("launch_gemv_t_sub: the column count must be a multiple of 64");
+    return -3;
+  }
+  const int chunks = (rows + TRMV_ROWS - 1) / TRMV_ROWS;
+  hipLaunchKernelGGL(gemv_t_kernel<R>, dim3(cols / 64, chunks), dim3(256), 0, s, M, ldm, rows, cols, x, partial);
+  hipLaunchKernelGGL(sub_slices_kernel<R>, dim3((cols + 255) / 256), dim3(256), 0, s, partial, cols, chunks, y, out);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// partial[t] = sum of squares of 128-tile t of a block of tm x tn tiles (row-major tile order); lower: the tiles
+// on / below the block diagonal only, in the order of the GEMM's tile-norm epilogue (ti (ti + 1) / 2 + tj)
+template <typename R>
+__global__ void frob_block_kernel(const R* __restrict__ T, int64_t ldt, int tn, double* __restrict__ partial) {
+  __shared__ double sh[17];
+  const int ti = blockIdx.x / tn, tj = blockIdx.x % tn;
+  const R* base = T + (int64_t)ti * TILE * ldt + tj * TILE;
+  double v = 0.0;
+#pragma unroll 8
+  for (int e = threadIdx.x; e < TILE * TILE; e += 256) {
+    const double x = (double)base[(int64_t)(e >> 7) * ldt + (e & 127)];
+    v += x * x;
+  }
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = v;
+}
+
+template <typename R>
+int launch_frob_tiles(const R* T, int64_t ldt, int rows, int cols, int lower, double* partial, hipStream_t s) {
+  const int tm = rows / TILE, tn = cols / TILE;
+  if (tm <= 0 || tn <= 0) return 0;
+  if (lower) hipLaunchKernelGGL(frob_tile_kernel<R>, dim3(tm * (tm + 1) / 2), dim3(256), 0, s, T, ldt, partial);
+  else hipLaunchKernelGGL(frob_block_kernel<R>, dim3(tm * tn), dim3(256), 0, s, T, ldt, tn, partial);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// dst (fp32) <- src (fp64) over a rows x cols block
+__global__ void demote_block_kernel(const double* __restrict__ src, int64_t lds, float* __restrict__ dst, int64_t ldd,
+                                    int cols) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < cols) dst[(int64_t)blockIdx.y * ldd + c] = (float)src[(int64_t)blockIdx.y * lds + c];
+}
+
+int launch_demote_block(const double* src, int64_t lds, float* dst, int64_t ldd, int rows, int cols, hipStream_t s) {
+  if (rows <= 0 || cols <= 0) return 0;
+  hipLaunchKernelGGL(demote_block_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, src, lds, dst, ldd, cols);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 template <typename R>
 __global__ void dot_kernel(const R* __restrict__ x, const R* __restrict__ y, int n, double* __restrict__ out) {
   __shared__ double sh[17];
@@ -1228,6 +1338,9 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
   template int launch_frob_lower<R>(const R*, int64_t, int, double*, double*, hipStream_t);                         \
   template int launch_trmv_lower<R>(const R*, int64_t, int, const R*, R*, hipStream_t);                             \
   template int launch_trmv_lower_t<R>(const R*, int64_t, int, const R*, R*, double*, hipStream_t);                  \
+  template int launch_gemv_sub<R>(const R*, int64_t, int, int, const R*, const R*, R*, hipStream_t);                \
+  template int launch_gemv_t_sub<R>(const R*, int64_t, int, int, const R*, const R*, R*, double*, hipStream_t);     \
+  template int launch_frob_tiles<R>(const R*, int64_t, int, int, int, double*, hipStream_t);                        \
   template int launch_group_prepare<R>(const GroupPrepT<R>&, hipStream_t);                                          \
   template int launch_dot<R>(const R*, const R*, int, double*, hipStream_t);                                        \
   template int launch_moments<R>(const R*, const R*, const R*, int64_t, const R*, int64_t, const R*, const R*, int, \

@@ -397,6 +397,38 @@ struct TwoSidedBufs {
   const R* Q; const R* Li; R* W; R* Z; R* H; int64_t ld; int min_split;
   void* sk_ws = nullptr;        // stream-K workspace of this block's launches (nullptr: the main stream's)
 };
+// H = alpha A B + Z ;  Z = H + Z  for cnt problems (A row-major M x K, B k-major K x N with structure b_tri, H and Z
+// M x N): one launch with the dual-update epilogue; where the launch cannot carry it, a copy, the product with
+// beta = 1 and an axpby pass -- the same arithmetic.
+template <typename R>
+static int dual_update_list(hipStream_t s, int cnt, const R* const* Ap, const R* const* Bp, R* const* Hp, R* const* Zp, int M,
+                            int N, int K, double alpha, int64_t ld, int b_tri, int walk, void* sk_ws) {
+  // would the fused launch be possible?  (asked first: the unfused route must copy Z into H beforehand)
+  bool fused = false;
+  if (fused_epilogues() & 4) {
+    GemmArgsT<R> g = gemm_args<R>(0, 1, M, N, K, alpha, Ap[0], ld, Bp[0], ld, 0.0, Hp[0], ld, 0, 0, b_tri, walk, 0, sk_ws);
+    g.epi = 4; g.aux = Zp[0];
+    static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;
+    if (cnt > 1 && gemm_pick_tile(g) != TILE && !no_batch) { g.nptr = cnt; g.batch = cnt; }
+    fused = gemm_epilogue_ok(g);
+  }
+  if (fused) {
+    bool done = false;
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 0.0, ld, 0, 0, b_tri, walk, 0, sk_ws, 4, Zp, nullptr, &done));
+    if (!done) {
+      set_error("two_sided: the dual-update epilogue was announced but not carried");
+      return -100;
+    }
+    return 0;
+  }
+  for (int i = 0; i < cnt; ++i)
+    GP_HIP(hipMemcpy2DAsync(Hp[i], (size_t)ld * sizeof(R), Zp[i], (size_t)ld * sizeof(R), (size_t)N * sizeof(R), (size_t)M,
+                            hipMemcpyDeviceToDevice, s));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 1.0, ld, 0, 0, b_tri, walk, 0, sk_ws));
+  for (int i = 0; i < cnt; ++i) GP_TRY(launch_axpby_block<R>(Zp[i], ld, Hp[i], ld, M, N, 1.0, 1.0, s));
+  return 0;
+}
+
 // cnt diagonal blocks of size n (block i of problem b[i] at offset r0[i]) in lock step: the two half-size
 // two-sided products a split leaves behind (W11's A^T Q11 A and W22) depend on nothing else of their level, so
 // they -- and the sub-blocks of several units -- share their launches (gemm_list above): two 2048-sized problems
@@ -441,38 +473,15 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
     Ap[i] = at(b[i].Q, r1, r1); Bp[i] = at(b[i].Li, r1, r0[i]); Cp[i] = at(b[i].Z, r1, r0[i]);
   }
   GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 0, 0, 0, 0, b[0].sk_ws));
-  // H = Q21 A + Z21 ;  Z21 = H + 1/2 Q22 B  (one launch with the dual-update epilogue: H = acc + Z21, Z21 += H;
-  // where the launch cannot carry it, a copy, the product with beta = 1 and an axpby pass -- the same arithmetic)
+  // H = Q21 A + Z21 ;  Z21 = H + 1/2 Q22 B
   {
+    R* Hp[GEMM_MAXB];
     R* Zp[GEMM_MAXB];
     for (int i = 0; i < cnt; ++i) {
       const int r1 = r0[i] + n1;
-      Ap[i] = at(b[i].Q, r1, r0[i]); Bp[i] = at(b[i].Li, r0[i], r0[i]); Cp[i] = at(b[i].H, r1, r0[i]); Zp[i] = at(b[i].Z, r1, r0[i]);
+      Ap[i] = at(b[i].Q, r1, r0[i]); Bp[i] = at(b[i].Li, r0[i], r0[i]); Hp[i] = at(b[i].H, r1, r0[i]); Zp[i] = at(b[i].Z, r1, r0[i]);
     }
-    // would the fused launch be possible?  (asked first: the unfused route must copy Z21 into H beforehand)
-    bool fused = false;
-    if (fused_epilogues() & 4) {
-      GemmArgsT<R> g = gemm_args<R>(0, 1, n2, n1, n1, 1.0, Ap[0], ld, Bp[0], ld, 0.0, Cp[0], ld, 0, 0, 1, walks()[6], 0, b[0].sk_ws);
-      g.epi = 4; g.aux = Zp[0];
-      static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;
-      if (cnt > 1 && gemm_pick_tile(g) != TILE && !no_batch) { g.nptr = cnt; g.batch = cnt; }
-      fused = gemm_epilogue_ok(g);
-    }
-    if (fused) {
-      bool done = false;
-      GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[6], 0, b[0].sk_ws, 4, Zp, nullptr,
-                          &done));
-      if (!done) {
-        set_error("two_sided: the dual-update epilogue was announced but not carried");
-        return -100;
-      }
-    } else {
-      for (int i = 0; i < cnt; ++i)
-        GP_HIP(hipMemcpy2DAsync(Cp[i], (size_t)ld * sizeof(R), Zp[i], (size_t)ld * sizeof(R), (size_t)n1 * sizeof(R), (size_t)n2,
-                                hipMemcpyDeviceToDevice, s));
-      GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, 1.0, ld, ld, 1.0, ld, 0, 0, 1, walks()[6], 0, b[0].sk_ws));
-      for (int i = 0; i < cnt; ++i) GP_TRY(launch_axpby_block<R>(Zp[i], ld, Cp[i], ld, n2, n1, 1.0, 1.0, s));
-    }
+    GP_TRY(dual_update_list<R>(s, cnt, Ap, Bp, Hp, Zp, n2, n1, n1, 1.0, ld, 1, walks()[6], b[0].sk_ws));
   }
   // W21 = 1/2 C^T Z21
   static const int w21_walk = getenv("GPFIT_W21_WALK") ? atoi(getenv("GPFIT_W21_WALK")) : 0;
@@ -494,6 +503,69 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
   }
   GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, b[0].sk_ws));
   return 0;
+}
+
+// Smallest padded size whose closure works on the top node's blocks (A = L11^-1, C = L22^-1 and L21) instead of the
+// full inverse factor: the recursion then skips the merge [L^-1]21 = -C (L21 A), 2 n1^2 n2 flops on the critical
+// path, and T, W and the mean's solves substitute with L21 at the same flop count -- but in 3 (T), 11 instead of 2-7
+// (W) and 8 instead of 3 (vectors) launches of half the size.  Measured, full form | block form, ms per fit (fp64,
+// single unit, MI355X): N = 512 0.47 | 0.55, 1024 0.78 | 0.86, 2048 1.88 | 2.01, 2560 2.75 | 2.76, 3072 3.61 | 3.65,
+// 4096 6.05-6.09 | 5.99-6.02, 8192 29.64-29.66 | 27.76-27.90; groups of 16 x N = 4096 261 | 250 ms, mixed-precision
+// groups of 16 x N = 8192 (per 512 points) 7.75 | 6.82 s.  Below 2048 the launches cost far more than the merge
+// (latency-bound sizes: 12 us per extra dependent launch); a single unit's break-even lies between 3072 and 4096.
+// The threshold sits at 2048, the size from which tests/test_gpu_top_inverse.py checks that the merge's flops are
+// gone: between 2048 and 3072 the block form gives 0.13 ... 0.03 ms (7 ... 1 %) back to the full form (W's eleven
+// launches of half-size blocks on 64-tiles against two; DESIGN.md section 7, open item 0).
+// The all-fp32 instance: N = 4096 3.74-3.76 | 3.77-3.79, 8192 16.28-16.32 | 15.43-15.46.  Its merge runs at twice the
+// rate against the same launch costs, which puts its break-even 2^(1/3) above fp64's: 5120.
+// elem_bytes: of the chains being factored (a mixed-precision unit factors in fp64).
+constexpr int TOP_BLOCKS_MIN = 2048, TOP_BLOCKS_MIN_F32 = 5120;
+static bool top_in_blocks(int np, size_t elem_bytes) { return np >= (elem_bytes == 4 ? TOP_BLOCKS_MIN_F32 : TOP_BLOCKS_MIN); }
+
+// The top level of W = 1/2 L^-T Q L^-1 for cnt units, written with the factor's own off-diagonal block L21 (Lf[i]: the
+// matrix whose 21 block holds it) and the inverses A = L11^-1, C = L22^-1 of the diagonal halves: the closure never
+// forms [L^-1]21 = -C L21 A (potrf_lockstep's `halves`).  With R = C^T Q21:
+//   W22 = 1/2 C^T Q22 C                    two_sided_list on the block, then completed in both triangles
+//   Z21 = 1/2 R ;  H = Z21 - W22 L21 ;  J = Z21 + H = R - W22 L21          (dual update)
+//   W21 = H A                                                  ( = 1/2 (R - 2 W22 L21) A )
+//   M   = Q11 - L21^T J - J^T L21         in place over Q11, lower tiles, then completed
+//   W11 = 1/2 A^T M A                      two_sided_list on the block
+// The same flops as the split with the explicit [L^-1]21 (two_sided_list); W11 needs W22, so the two diagonal blocks
+// of this level do not share launches.  No step reads a block an earlier step of the stage has overwritten.
+template <typename R>
+static int two_sided_top(int cnt, const TwoSidedBufs<R>* b, const R* const* Lf, int n, hipStream_t s) {
+  if (cnt <= 0) return 0;
+  const int64_t ld = b[0].ld;
+  auto at = [&](const R* base, int r, int c) { return const_cast<R*>(base) + (int64_t)r * ld + c; };
+  int rr[GEMM_MAXB];
+  const int k = n / TILE;
+  const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;   // (top_in_blocks: both halves exist)
+  const R* Ap[GEMM_MAXB];
+  const R* Bp[GEMM_MAXB];
+  R* Cp[GEMM_MAXB];
+  R* Zp[GEMM_MAXB];
+  void* sk = b[0].sk_ws;
+  for (int i = 0; i < cnt; ++i) rr[i] = n1;
+  GP_TRY(two_sided_list<R>(cnt, b, rr, n2, s));
+  for (int i = 0; i < cnt; ++i) GP_TRY(launch_symmetrize(at(b[i].W, n1, n1), ld, n2, s));
+  // Z21 = 1/2 C^T Q21
+  static const int w21_walk = getenv("GPFIT_W21_WALK") ? atoi(getenv("GPFIT_W21_WALK")) : 0;
+  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Li, n1, n1); Bp[i] = at(b[i].Q, n1, 0); Cp[i] = at(b[i].Z, n1, 0); }
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, 0, sk));
+  // H = -W22 L21 + Z21 ;  Z21 = J = H + Z21
+  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].W, n1, n1); Bp[i] = at(Lf[i], n1, 0); Cp[i] = at(b[i].H, n1, 0); Zp[i] = at(b[i].Z, n1, 0); }
+  GP_TRY(dual_update_list<R>(s, cnt, Ap, Bp, Cp, Zp, n2, n1, n2, -1.0, ld, 0, 0, sk));
+  // W21 = H A
+  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].H, n1, 0); Bp[i] = at(b[i].Li, 0, 0); Cp[i] = at(b[i].W, n1, 0); }
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[6], 0, sk));
+  // M = Q11 - L21^T J - J^T L21   (lower tiles, then both triangles: the block products below read M in full)
+  for (int i = 0; i < cnt; ++i) { Ap[i] = at(Lf[i], n1, 0); Bp[i] = at(b[i].Z, n1, 0); Cp[i] = at(b[i].Q, 0, 0); }
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, sk));
+  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Z, n1, 0); Bp[i] = at(Lf[i], n1, 0); }
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, sk));
+  for (int i = 0; i < cnt; ++i) GP_TRY(launch_symmetrize(Cp[i], ld, n1, s));
+  for (int i = 0; i < cnt; ++i) rr[i] = 0;
+  return two_sided_list<R>(cnt, b, rr, n1, s);
 }
 
 // ------------------------------------------------------------------ host pieces of localker
@@ -653,13 +725,29 @@ static int build_kernel(gpfit_ctx* c, hipStream_t s, const Theta& th, int d, int
                         dp, s0sq, mirror);
 }
 
-// ---- the vectors behind K~'s factor: y = L^-1 m, m^T K~^-1 m, b = K~^-1 m
+// ---- the vectors behind K~'s factor: y = L^-1 m, m^T K~^-1 m = y . y, b = K~^-1 m = L^-T y.  Sizes in block form
+// (top_in_blocks) substitute with A = L11^-1, C = L22^-1 (the diagonal halves of Libuf) and L21 (in Lbuf); Libuf's 21
+// block is stale there and never read:
+//   y1 = A m1 ,  y2 = C (m2 - L21 y1) ,  b2 = C^T y2 ,  b1 = A^T (y1 - L21^T b2)
+// (the same bytes as the whole lower triangle of L^-1; bv doubles as the scratch of the two right-hand sides)
 template <typename R>
-static int solve_mean(gpfit_ctx* c, int np, hipStream_t s) {
+static int solve_mean(gpfit_ctx* c, int np, bool blocks, hipStream_t s) {
   const int64_t ld = np;
-  GP_TRY(launch_trmv_lower(ws_as<R>(c->Libuf), ld, np, ws_as<R>(c->mpad), ws_as<R>(c->yv), s));
-  GP_TRY(launch_dot(ws_as<R>(c->yv), ws_as<R>(c->yv), np, c->scal + 6, s));
-  return launch_trmv_lower_t(ws_as<R>(c->Libuf), ld, np, ws_as<R>(c->yv), ws_as<R>(c->bv), c->trmv_part, s);
+  R *m = ws_as<R>(c->mpad), *y = ws_as<R>(c->yv), *b = ws_as<R>(c->bv);
+  if (!blocks) {
+    GP_TRY(launch_trmv_lower(ws_as<R>(c->Libuf), ld, np, m, y, s));
+    GP_TRY(launch_dot(y, y, np, c->scal + 6, s));
+    return launch_trmv_lower_t(ws_as<R>(c->Libuf), ld, np, y, b, c->trmv_part, s);
+  }
+  const int kt = np / TILE, n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;   // potrf_lockstep's split of the top node
+  const R *A = ws_as<R>(c->Libuf), *C = A + (int64_t)n1 * ld + n1, *L21 = ws_as<R>(c->Lbuf) + (int64_t)n1 * ld;
+  GP_TRY(launch_trmv_lower(A, ld, n1, m, y, s));
+  GP_TRY(launch_gemv_sub(L21, ld, n2, n1, y, m + n1, b + n1, s));
+  GP_TRY(launch_trmv_lower(C, ld, n2, b + n1, y + n1, s));
+  GP_TRY(launch_dot(y, y, np, c->scal + 6, s));
+  GP_TRY(launch_trmv_lower_t(C, ld, n2, y + n1, b + n1, c->trmv_part, s));
+  GP_TRY(launch_gemv_t_sub(L21, ld, n2, n1, b + n1, y, b, c->trmv_part, s));
+  return launch_trmv_lower_t(A, ld, n1, b, b, c->trmv_part, s);
 }
 
 // ---- pull-back of an n x n adjoint to the d x d metric
@@ -783,29 +871,37 @@ static int assemble_out(gpfit_ctx* c, double A, double lambda0, double sigma0_ro
 
 // Everything after the join of the two factorisation chains: T = L^-1 L_V and its norm, and (with
 // gradients) Q = I - T T^T, the two-sided product W, the adjoint pass and the pull-back to the metric.
+// Sizes in block form (top_in_blocks): K~'s inverse factor arrives as the inverses of its two diagonal halves (Li:
+// A = L11^-1, C = L22^-1; Li's 21 block is stale) and the factor's own 21 block (L: the matrix whose 21 block holds
+// L21) -- [L^-1]21 is never formed.  Smaller sizes: Li is the full inverse factor, L is not read.
 // Templated separately from the first half of the unit so that the mixed-precision mode (fp64
 // factorisations, fp32 gradient products) can run it on single-precision copies.
 template <typename R>
 struct PostJoin {
-  const R *Li, *LV, *Cos, *bv, *q, *wl, *Xm, *Cmat;           // inputs
+  const R *Li, *L, *LV, *Cos, *bv, *q, *wl, *Xm, *Cmat;       // inputs
   R *T, *W, *Z, *H, *A, *Y, *tvec, *Mpart, *Mmat;             // work matrices (np^2), Y [np][dp], Mpart / Mmat
 };
 template <typename R>
 static PostJoin<R> post_join_args(gpfit_ctx* c) {
   auto RP = ws_as<R>;
-  return PostJoin<R>{RP(c->Libuf), RP(c->LVbuf), RP(c->Cos), RP(c->bv), RP(c->q), RP(c->wl), RP(c->Xm), RP(c->Cmat),
+  return PostJoin<R>{RP(c->Libuf), RP(c->Lbuf), RP(c->LVbuf), RP(c->Cos), RP(c->bv), RP(c->q), RP(c->wl), RP(c->Xm), RP(c->Cmat),
                      RP(c->Tbuf), RP(c->Wbuf), RP(c->Zbuf), RP(c->Tmp), RP(c->Abuf), RP(c->Ybuf), RP(c->tvec),
                      RP(c->Mpart), RP(c->Mmat)};
 }
 // Mixed precision: fp64 factorisations, log-determinants and likelihood; fp32 for the N^3-heavy products T, Q, W and
 // the pull-back (T's norm, the trace term of the KL, is therefore fp32-derived: 2e-9 on the loss at N = 8192).  This
 // is the hand-over: single-precision copies of the factors and of the O(N^2) / O(N) operands of the adjoint pass.
-// Li -> Kbuf (its input was destroyed by the factorisation), L_V -> Vbuf (likewise; kept while the V factor is
+// Li -> Kbuf (its input was destroyed by the factorisation), in block form with L21 in the image's 21 block (where
+// the full inverse has [L^-1]21), L_V -> Vbuf (likewise; kept while the V factor is
 // reused), cos(delta) -> TmpV, vectors and the d x d metric into spare buffers.
-static int demote_for_mixed(gpfit_ctx* c, bool reuse_V, int np, int dp, hipStream_t s, PostJoin<float>* pf) {
+static int demote_for_mixed(gpfit_ctx* c, bool reuse_V, int np, int dp, bool blocks, hipStream_t s, PostJoin<float>* pf) {
   auto F = ws_as<float>;
   const int64_t nn = (int64_t)np * np;
   GP_TRY((launch_reduce_slices<double, float>(c->Libuf, nn, 1, F(c->Kbuf), nn, s)));
+  if (blocks) {
+    const int kt = np / TILE, n1 = ((kt + 1) / 2) * TILE;
+    GP_TRY(launch_demote_block(c->Lbuf + (int64_t)n1 * np, np, F(c->Kbuf) + (int64_t)n1 * np, np, np - n1, n1, s));
+  }
   if (!(reuse_V && c->lv32_valid)) GP_TRY((launch_reduce_slices<double, float>(c->LVbuf, nn, 1, F(c->Vbuf), nn, s)));
   c->lv32_valid = true;
   GP_TRY((launch_reduce_slices<double, float>(c->Cos, nn, 1, F(c->TmpV), nn, s)));
@@ -814,11 +910,99 @@ static int demote_for_mixed(gpfit_ctx* c, bool reuse_V, int np, int dp, hipStrea
   GP_TRY((launch_reduce_slices<double, float>(c->wl, np, 1, F(c->dq2), np, s)));
   GP_TRY((launch_reduce_slices<double, float>(c->Xm, (int64_t)np * dp, 1, F(c->Xt2), (int64_t)np * dp, s)));
   GP_TRY((launch_reduce_slices<double, float>(c->Cmat, (int64_t)dp * dp, 1, F(c->dCpad), (int64_t)dp * dp, s)));
-  *pf = PostJoin<float>{F(c->Kbuf), F(c->Vbuf), F(c->TmpV), F(c->q2), F(c->dq1), F(c->dq2), F(c->Xt2), F(c->dCpad),
+  *pf = PostJoin<float>{F(c->Kbuf), F(c->Kbuf), F(c->Vbuf), F(c->TmpV), F(c->q2), F(c->dq1), F(c->dq2), F(c->Xt2), F(c->dCpad),
                         F(c->Tbuf), F(c->Wbuf), F(c->Zbuf), F(c->Tmp), F(c->Abuf), F(c->Ybuf), F(c->tvec),
                         F(c->Mpart), F(c->Mmat)};
   return 0;
 }
+
+// T = L^-1 L_V of cnt units in block form (top_in_blocks), with ||T||_F^2 into scal[5]:
+//   T11 = A LV11 ,  T22 = C LV22                 lower x lower -> lower (one list when the halves are equal)
+//   S = LV21 - L21 T11 ,  T21 = C S              dense x lower, lower x dense; S in Z's 21 block (idle until W):
+//                                                L_V stays intact (its factor may be reused)
+// The tiles leave their sums of squares behind (no separate pass over T) where a launch can carry the epilogue;
+// whether it is asked to depends on the single unit's launch only, so a group sums the norm in the unit's order.
+template <typename R>
+static int t_in_blocks(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int np, hipStream_t s) {
+  const int64_t ld = np;
+  const R* Ap[GEMM_MAXB];
+  const R* Bp[GEMM_MAXB];
+  R* Cp[GEMM_MAXB];
+  R* Tp[GEMM_MAXB];
+  double* Sp[GEMM_MAXB];
+  const int kt = np / TILE, n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;   // potrf_lockstep's split of the top node
+  int ent = 0;   // entries of frob_part written so far (the same for every unit)
+  // blocks whose launch cannot carry the norm get a pass of their own -- unless no launch of the unit carries it
+  // (all on small tiles): then ONE pass over T's lower tiles, which are exactly the tiles of the three blocks
+  auto asks = [&](int M, int Nn, int K, int lower, int a_tri, int b_tri, int walk) {
+    GemmArgsT<R> g1 = gemm_args<R>(0, 1, M, Nn, K, 1.0, a[0].Li, ld, a[0].LV, ld, 0.0, a[0].T, ld, lower, a_tri, b_tri, walk, 0, cs[0]->sk_ws[0]);
+    g1.epi = 2; g1.sumsq = cs[0]->frob_part;
+    return ((fused_epilogues() & 2) && gemm_pick_tile(g1) == TILE) ? gemm_sumsq_entries(g1) : 0;
+  };
+  const bool any_fused = asks(n1, n1, n1, 1, 1, 1, walks()[3]) > 0 || asks(n2, n2, n2, 1, 1, 1, walks()[3]) > 0 ||
+                         asks(n2, n1, n2, 0, 1, 0, walks()[2]) > 0;
+  // one list of lower x lower blocks: cb blocks (at rb[], all of size nblk) per unit
+  auto diag_blocks = [&](int cb, const int* rb, int nblk) -> int {
+    const int tb = nblk / TILE;
+    int e = asks(nblk, nblk, nblk, 1, 1, 1, walks()[3]);
+    const bool ask = e > 0;
+    if (!ask) e = tb * (tb + 1) / 2;
+    int m = 0;
+    for (int i = 0; i < cnt; ++i)
+      for (int j = 0; j < cb; ++j, ++m) {
+        const int64_t o = (int64_t)rb[j] * ld + rb[j];
+        Ap[m] = a[i].Li + o; Bp[m] = a[i].LV + o; Tp[m] = a[i].T + o; Sp[m] = cs[i]->frob_part + ent + j * e;
+      }
+    bool normed = false;
+    GP_TRY(gemm_list<R>(s, m, Ap, Bp, Tp, 0, 1, nblk, nblk, nblk, 1.0, ld, ld, 0.0, ld, 1, 1, 1, walks()[3], 0, cs[0]->sk_ws[0],
+                        ask ? 2 : 0, nullptr, Sp, &normed));
+    if (normed != ask) {
+      set_error("post_join: the tile-norm epilogue of a diagonal block of T was announced but not carried");
+      return -100;
+    }
+    if (!normed && any_fused)
+      for (int q = 0; q < m; ++q) GP_TRY(launch_frob_tiles<R>(Tp[q], ld, nblk, nblk, 1, Sp[q], s));
+    ent += cb * e;
+    return 0;
+  };
+  const int r_both[2] = {0, n1};
+  if (n2 == n1 && 2 * cnt <= GEMM_MAXB) GP_TRY(diag_blocks(2, r_both, n1));
+  else {
+    GP_TRY(diag_blocks(1, r_both, n1));
+    GP_TRY(diag_blocks(1, r_both + 1, n2));
+  }
+  {
+    const int64_t o21 = (int64_t)n1 * ld;
+    for (int i = 0; i < cnt; ++i) {
+      GP_HIP(hipMemcpy2DAsync(a[i].Z + o21, (size_t)ld * sizeof(R), a[i].LV + o21, (size_t)ld * sizeof(R), (size_t)n1 * sizeof(R),
+                              (size_t)n2, hipMemcpyDeviceToDevice, s));
+      Ap[i] = a[i].L + o21; Bp[i] = a[i].T; Cp[i] = a[i].Z + o21;
+    }
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, -1.0, ld, ld, 1.0, ld, 0, 0, 1, walks()[1], 0, cs[0]->sk_ws[0]));
+    int e = asks(n2, n1, n2, 0, 1, 0, walks()[2]);
+    const bool ask = e > 0;
+    if (!ask) e = (n2 / TILE) * (n1 / TILE);
+    for (int i = 0; i < cnt; ++i) {
+      Ap[i] = a[i].Li + o21 + n1; Bp[i] = a[i].Z + o21; Tp[i] = a[i].T + o21; Sp[i] = cs[i]->frob_part + ent;
+    }
+    bool normed = false;
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Tp, 0, 1, n2, n1, n2, 1.0, ld, ld, 0.0, ld, 0, 1, 0, walks()[2], 0, cs[0]->sk_ws[0],
+                        ask ? 2 : 0, nullptr, Sp, &normed));
+    if (normed != ask) {
+      set_error("post_join: the tile-norm epilogue of T21 was announced but not carried");
+      return -100;
+    }
+    if (!normed && any_fused)
+      for (int i = 0; i < cnt; ++i) GP_TRY(launch_frob_tiles<R>(Tp[i], ld, n2, n1, 0, Sp[i], s));
+    ent += e;
+  }
+  for (int i = 0; i < cnt; ++i) {
+    if (any_fused) GP_TRY(launch_frob_finish(cs[i]->frob_part, ent, cs[i]->scal + 5, s));
+    else GP_TRY(launch_frob_lower(a[i].T, ld, np, cs[i]->scal + 5, cs[i]->frob_part, s));
+  }
+  return 0;
+}
+
 // cnt units at once (the units of a group, gpfit_fit_eval_batch; cnt = 1: the single unit): every product goes
 // through gemm_list / two_sided_list -- one pointer-batched launch where a single unit's product cannot fill the
 // chip, unit by unit through the ordinary launcher (balanced schedules, fused epilogues) where it can -- and the
@@ -827,7 +1011,7 @@ static int demote_for_mixed(gpfit_ctx* c, bool reuse_V, int np, int dp, hipStrea
 // concurrency from batched launches, not from streams.
 template <typename R, typename PhaseFn>
 static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, const Theta* th, int n, int np, const int* d,
-                          const int* dp, int n_rows, int n_cols, int want_grad, hipStream_t s, PhaseFn&& phase) {
+                          const int* dp, int n_rows, int n_cols, int want_grad, bool blocks, hipStream_t s, PhaseFn&& phase) {
   const int64_t ld = np;
   const R* Ap[GEMM_MAXB];
   const R* Bp[GEMM_MAXB];
@@ -835,7 +1019,7 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
   double* Sp[GEMM_MAXB];
   if (cnt <= 0 || cnt > GEMM_MAXB) return cnt == 0 ? 0 : -3;
   // T = L^-1 L_V (lower x lower -> lower);  tr(K~^-1 V) = ||T||_F^2
-  {
+  if (!blocks) {
     for (int i = 0; i < cnt; ++i) { Ap[i] = a[i].Li; Bp[i] = a[i].LV; Cp[i] = a[i].T; Sp[i] = cs[i]->frob_part; }
     bool normed = false;
     int norm_entries = 0;
@@ -846,12 +1030,15 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
       if (normed) GP_TRY(launch_frob_finish(cs[i]->frob_part, norm_entries, cs[i]->scal + 5, s));
       else GP_TRY(launch_frob_lower(a[i].T, ld, np, cs[i]->scal + 5, cs[i]->frob_part, s));
     }
+  } else {
+    GP_TRY(t_in_blocks<R>(cnt, cs, a, np, s));
   }
   phase(4, s);
   if (!want_grad) return 0;
   // W = 1/2 (K~^-1 - K~^-1 V K~^-1) = 1/2 Li^T (I - T T^T) Li        (T = L^-1 L_V)
   //   Q = I - T T^T   lower x upper, lower tiles only          N^3/3
-  //   W = 1/2 Li^T Q Li  two-sided product (two_sided_list)    13/12 N^3 with one split
+  //   W = 1/2 Li^T Q Li  two-sided product (two_sided_top /    13/12 N^3 with one split
+  //                      two_sided_list)
   //                      (direct: R = Q Li, W = 1/2 Li^T R     4/3 N^3)
   {
     // T T^T: every tile of a tile column has the same k range [0, col + 128).  XCD-aware macro-tile schedule for
@@ -870,13 +1057,18 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
   {
     static const int ts_min = getenv("GPFIT_TS_MIN") ? atoi(getenv("GPFIT_TS_MIN")) : 4096;
     TwoSidedBufs<R> tb[GEMM_MAXB];
-    int r0[GEMM_MAXB];
+    const R* Lf[GEMM_MAXB];
     for (int i = 0; i < cnt; ++i) {
       tb[i] = TwoSidedBufs<R>{a[i].W, a[i].Li, a[i].T, a[i].Z, a[i].H, ld, ts_min > 0 ? ts_min : (1 << 30)};
       tb[i].sk_ws = cs[0]->sk_ws[0];
-      r0[i] = 0;
+      Lf[i] = a[i].L;
     }
-    GP_TRY(two_sided_list<R>(cnt, tb, r0, np, s));
+    if (blocks) GP_TRY(two_sided_top<R>(cnt, tb, Lf, np, s));
+    else {
+      int r0[GEMM_MAXB];
+      for (int i = 0; i < cnt; ++i) r0[i] = 0;
+      GP_TRY(two_sided_list<R>(cnt, tb, r0, np, s));
+    }
   }
   phase(6, s);
   for (int i = 0; i < cnt; ++i)
@@ -935,6 +1127,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   const Theta th = ad.th;
   const double A = std::exp(logA);
   const int64_t ld = np;
+  const bool blocks = top_in_blocks(np, sizeof(R));   // the closure works on the top node's blocks, no [L^-1]21
   c->cur_n = n; c->cur_np = np; c->cur_d = d; c->cur_dp = dp;
 
   ++g_eval_count;
@@ -993,22 +1186,25 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
     cb.A[1] = RP(c->Vbuf); cb.L[1] = RP(c->LVbuf); cb.Li[1] = RP(c->LiVbuf); cb.Tmp[1] = RP(c->TmpV); cb.info[1] = c->info + 1;
     cb.ld = ld; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = c; cb.side_min = side_min;
     if (!reuse_V) GP_HIP(hipStreamWaitEvent(s, c->ev_join, 0));   // V is packed
-    GP_TRY(potrf_lockstep<R>(cb, 0, np, 1u, s));
+    // (K~'s chain in block form: the inverses of the two diagonal halves only -- everything behind substitutes with
+    // L21, and the top-level look-ahead on the side stream disappears with the merge)
+    if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, s, 1u));
+    else GP_TRY(potrf_lockstep<R>(cb, 0, np, 1u, s));
     if (!reuse_V) GP_TRY(launch_logdet(RP(c->LVbuf), ld, n, c->scal + 40, s));
     phase(3, s);
   }
   GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + 3, s));
-  GP_TRY(solve_mean<R>(c, np, s));
+  GP_TRY(solve_mean<R>(c, np, blocks, s));
 
   phase(2, s);
   // ---- everything that needs both factors
   if (mixed_grad) {
     PostJoin<float> pf;
-    GP_TRY(demote_for_mixed(c, reuse_V, np, dp, s, &pf));
-    GP_TRY(post_join_list<float>(1, &c, &pf, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, s, phase));
+    GP_TRY(demote_for_mixed(c, reuse_V, np, dp, blocks, s, &pf));
+    GP_TRY(post_join_list<float>(1, &c, &pf, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, blocks, s, phase));
   } else {
     const PostJoin<R> pj = post_join_args<R>(c);
-    GP_TRY(post_join_list<R>(1, &c, &pj, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, s, phase));
+    GP_TRY(post_join_list<R>(1, &c, &pj, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, blocks, s, phase));
   }
 
   if (lam_m_out) GP_HIP(hipMemcpyAsync(lam_m_out, RP(c->lam_m), (size_t)n * sizeof(R), hipMemcpyDeviceToDevice, s));
@@ -1070,6 +1266,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   const int64_t ld = np;
   const bool mixed_grad = (want_grad & 8) != 0 && sizeof(R) == 8 && (want_grad & 1);
   const bool want_reuse = (want_grad & 2) != 0;
+  const bool blocks = top_in_blocks(np, sizeof(R));   // as in fit_eval_impl
   want_grad &= 1;
   const auto t_host0 = std::chrono::steady_clock::now();
 
@@ -1129,18 +1326,19 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   // ---- phase 2: all factorisations in lock step
   {
     CholBatchT<R> cb;
-    uint32_t need = 0;
+    uint32_t kchains = 0;   // the K~ chains: their inverse factors -- in block form the two diagonal halves only
     for (int i = 0; i < na; ++i) {
       gpfit_ctx* c = un[i].c;
       int b = cb.nb++;
       cb.A[b] = RP(c->Kbuf); cb.L[b] = RP(c->Lbuf); cb.Li[b] = RP(c->Libuf); cb.Tmp[b] = RP(c->Tmp); cb.info[b] = c->info + 0;
-      need |= 1u << b;
+      kchains |= 1u << b;
       if (un[i].reuse_V) continue;
       b = cb.nb++;
       cb.A[b] = RP(c->Vbuf); cb.L[b] = RP(c->LVbuf); cb.Li[b] = RP(c->LiVbuf); cb.Tmp[b] = RP(c->TmpV); cb.info[b] = c->info + 1;
     }
     cb.ld = ld; cb.ws = 0; cb.sk_ws = c0->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
-    GP_TRY(potrf_lockstep<R>(cb, 0, np, need, s));
+    if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, s, kchains));
+    else GP_TRY(potrf_lockstep<R>(cb, 0, np, kchains, s));
   }
   if (batch_times) (void)hipEventRecord(tev[2], s);
   // ---- phase 3: everything that needs the factors
@@ -1156,12 +1354,12 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
     cl[i] = c; thl[i] = q.th; dl[i] = q.d; dpl[i] = q.dp;
     if (!q.reuse_V) GP_TRY(launch_logdet_pair(RP(c->Lbuf), c->scal + 3, RP(c->LVbuf), c->scal + 40, ld, n, s));
     else GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + 3, s));
-    GP_TRY(solve_mean<R>(c, np, s));
-    if (mixed_grad) GP_TRY(demote_for_mixed(c, q.reuse_V, np, q.dp, s, &pfl[i]));
+    GP_TRY(solve_mean<R>(c, np, blocks, s));
+    if (mixed_grad) GP_TRY(demote_for_mixed(c, q.reuse_V, np, q.dp, blocks, s, &pfl[i]));
     else pjl[i] = post_join_args<R>(c);
   }
-  if (mixed_grad) GP_TRY(post_join_list<float>(na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase));
-  else GP_TRY(post_join_list<R>(na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, s, no_phase));
+  if (mixed_grad) GP_TRY(post_join_list<float>(na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, s, no_phase));
+  else GP_TRY(post_join_list<R>(na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, s, no_phase));
   {
     GroupCollectT gc{};
     gc.n_units = na;

@@ -137,7 +137,8 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgsT<R>& p, int tiles_
       __syncthreads();  // every wave is done with the operand stages
       if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
       __syncthreads();
-      if (threadIdx.x == 0) sumsq[(int64_t)ti * (ti + 1) / 2 + tj] = (red[0] + red[1]) + (red[2] + red[3]);
+      if (threadIdx.x == 0)
+        sumsq[p.out_lower ? (int64_t)ti * (ti + 1) / 2 + tj : (int64_t)ti * tiles_n + tj] = (red[0] + red[1]) + (red[2] + red[3]);
     }
     return;
   }
@@ -164,9 +165,9 @@ __global__ __launch_bounds__(GEMM_THREADS, (T == 128 || NS > 2 ? 2 : 4)) void ge
 }
 
 // The same 128-tile body under its own name for launches that follow an XCD-aware schedule table
-// (gemm_sched.hip): in the fit these are exactly T = L^-1 L_V (<R, false, true>) and Q = I - T T^T
-// (<R, false, false>), one launch each per evaluation, so a profiler's per-kernel row for this name
-// IS that launch.
+// (gemm_sched.hip): in the fit these are Q = I - T T^T (<R, false, false>) and, where a block of T = L^-1 L_V is
+// large enough for a table (<R, false, true>: N = 16384 up, or a unit below the block-form threshold), that block;
+// one launch each per evaluation, so a profiler's per-kernel row for this name IS that launch.
 #ifdef GPFIT_CLOCK_STAMPS
 // Diagnostic build only (scripts/scratch/dev_gemm_clock.sh): shader cycles (s_memtime) and 100 MHz ticks
 // (s_memrealtime) each workgroup of the last scheduled launch spent, [B_KMAJOR][block][2]; read back with
@@ -264,8 +265,9 @@ static void launch_T(const GemmArgsT<R>& p, hipStream_t s) {
     } else hipLaunchKernelGGL((gemm_mfma_kernel<R, AK, BK, ED, T, 2>), grid, block, 0, s, p, tn, tiles); \
   } while (0)
   if (p.epi) {
-    // fused epilogues exist for the layouts the fit uses: T = L^-1 L_V with tile norms, Q = -T T^T mirrored,
-    // H = Q21 A + Z21 with the dual update (gemm_epilogue_ok has checked the combination)
+    // fused epilogues exist for the layouts the fit uses: the blocks of T = L^-1 L_V with tile norms (lower or full
+    // output), Q = -T T^T mirrored, H = Q21 A + Z21 / H = -W22 L21 + Z21 with the dual update (gemm_epilogue_ok has
+    // checked the combination)
     if constexpr (T == TILE) {
       const int key = p.epi * 4 + (p.a_kmajor ? 2 : 0) + (p.b_kmajor ? 1 : 0);
       if (key == 2 * 4 + 1) hipLaunchKernelGGL((gemm_epi_kernel<R, false, true, 2>), grid, block, 0, s, p, tn, tiles);
@@ -303,7 +305,7 @@ bool gemm_epilogue_ok(const GemmArgsT<R>& a) {
   const int T = gemm_pick_tile(a);
   if ((a.M % T) || (a.N % T)) return false;                                    // full tiles only
   if ((a.epi & 1) && (!a.out_lower || a.M != a.N)) return false;
-  if ((a.epi & 2) && (T != TILE || !a.out_lower)) return false;
+  if ((a.epi & 2) && T != TILE) return false;
   if ((a.epi & 4) && a.nptr <= 0 && a.aux == nullptr) return false;
   // instances that exist (launch_T): 128-tile, row-major A, and per mode the operand layout the fit uses
   if (T != TILE || a.a_kmajor || a.half_occ) return false;
@@ -319,7 +321,7 @@ bool gemm_epilogue_ok(const GemmArgsT<R>& a) {
 template <typename R>
 int gemm_sumsq_entries(const GemmArgsT<R>& a) {
   if (!(a.epi & 2) || !gemm_epilogue_ok(a)) return 0;
-  const int t = a.M / TILE, nt = t * (t + 1) / 2;
+  const int t = a.M / TILE, nt = a.out_lower ? t * (t + 1) / 2 : t * (a.N / TILE);
   if (a.nptr > 0 || a.half_occ || a.tile_limit != 0 || a.batch > 1) return nt;
   if ((a.reverse & 8) && gemm_xcd_applies(a)) return nt;
   return gemm_streamk_applies(a) ? 33 * nt : nt;

@@ -85,6 +85,19 @@ int launch_frob_lower(const R* T, int64_t ldt, int np, double* out, double* part
 template <typename R> int launch_trmv_lower(const R* L, int64_t ldl, int np, const R* x, R* y, hipStream_t s);
 template <typename R>
 int launch_trmv_lower_t(const R* L, int64_t ldl, int np, const R* x, R* z, double* partial, hipStream_t s);
+// the dense off-diagonal block of a factor applied to a vector (M rows x cols, row-major): out = y - M x, and
+// out = y - M^T x (cols a multiple of 64; partial: ceil(rows / TRMV_ROWS) * cols doubles).  Deterministic, no atomics.
+template <typename R>
+int launch_gemv_sub(const R* M, int64_t ldm, int rows, int cols, const R* x, const R* y, R* out, hipStream_t s);
+template <typename R>
+int launch_gemv_t_sub(const R* M, int64_t ldm, int rows, int cols, const R* x, const R* y, R* out, double* partial,
+                      hipStream_t s);
+// partial[t] = sum of squares of 128-tile t of a rows x cols block (multiples of 128): all tiles in row-major order,
+// or (lower, square) the tiles on / below the diagonal in the order of the GEMM's tile-norm epilogue
+template <typename R>
+int launch_frob_tiles(const R* T, int64_t ldt, int rows, int cols, int lower, double* partial, hipStream_t s);
+// dst (fp32) <- src (fp64) over a rows x cols block
+int launch_demote_block(const double* src, int64_t lds, float* dst, int64_t ldd, int rows, int cols, hipStream_t s);
 // out[0] = x . y
 template <typename R> int launch_dot(const R* x, const R* y, int n, double* out, hipStream_t s);
 
