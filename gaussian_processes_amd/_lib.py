@@ -12,6 +12,23 @@ from .build import lib_path
 vp, i32, i64, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
 pd = ctypes.POINTER(ctypes.c_double)
 
+
+
+class DevGemmArgs(ctypes.Structure):
+    """gpfit_dev_gemm_args (test hooks of include/gpfit_mi355x.h)."""
+    _fields_ = ([(n, vp) for n in ("A", "B", "C")] + [(n, i64) for n in ("lda", "ldb", "ldc", "sA", "sB", "sC")] +
+                [("alpha", f64), ("beta", f64)] +
+                [(n, vp) for n in ("sk_ws", "aux", "sumsq", "Ap", "Bp", "Cp", "auxp", "sumsqp")] +
+                [(n, ctypes.c_int32) for n in ("M", "N", "K", "a_kmajor", "b_kmajor", "out_lower", "a_tri", "b_tri", "batch",
+                                               "split_k", "tile", "walk", "epi", "nptr")])
+
+
+class DevGemmRoute(ctypes.Structure):
+    """gpfit_dev_gemm_route_t."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("rc", "tile", "sk_first", "xcd", "stages", "half_occ", "edge", "epi",
+                                              "sumsq_entries", "blocks", "pair", "reserved")]
+
+
 _SIGS = {
     "gpfit_version": (i32, []),
     "gpfit_last_error": (ctypes.c_char_p, []),
@@ -53,6 +70,10 @@ _SIGS = {
     "gpfit_nd_utility": (i32, [vp, vp, vp, i64, vp, i32, vp]),
     "gpfit_probe_mfma_f64": (i32, [vp, vp, i32, i32]),
     "gpfit_probe_stream_copy": (i32, [vp, vp, vp, i64]),
+    # test hooks
+    "gpfit_dev_gemm_route": (i32, [i32, ctypes.POINTER(DevGemmArgs), ctypes.POINTER(DevGemmArgs), ctypes.POINTER(DevGemmRoute)]),
+    "gpfit_dev_gemm_plan": (i64, [i32, ctypes.POINTER(DevGemmArgs), i32, ctypes.POINTER(ctypes.c_int32), i64]),
+    "gpfit_dev_gemm": (i32, [vp, i32, ctypes.POINTER(DevGemmArgs), ctypes.POINTER(DevGemmArgs)]),
 }
 
 _lib = None

@@ -1,0 +1,155 @@
+// C-ABI test hooks of the GEMM launcher: which route a launch takes, the plans of the balanced schedules, and an
+// entry point that reaches every field of GemmArgsT (both element types, pointer batches, strided batches,
+// split-K, fused epilogues, the pair launch).  No arithmetic happens here: the hooks fill the launcher's own
+// argument struct and ask the launcher's own predicates (gemm.hip, gemm_streamk.hip, gemm_sched.hip).
+#include "gemm_core.h"
+#include "gpfit_mi355x.h"
+
+#include <cstring>
+
+namespace gpfit {
+namespace {
+
+template <typename R>
+int fill(const gpfit_dev_gemm_args& d, GemmArgsT<R>& g) {
+  g = GemmArgsT<R>{};
+  g.A = (const R*)d.A; g.B = (const R*)d.B; g.C = (R*)d.C;
+  g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc;
+  g.M = d.M; g.N = d.N; g.K = d.K;
+  g.alpha = d.alpha; g.beta = d.beta;
+  g.a_kmajor = d.a_kmajor; g.b_kmajor = d.b_kmajor;
+  g.out_lower = d.out_lower; g.a_tri = d.a_tri; g.b_tri = d.b_tri;
+  g.batch = d.batch > 0 ? d.batch : 1;
+  g.sA = d.sA; g.sB = d.sB; g.sC = d.sC;
+  g.split_k = d.split_k > 0 ? d.split_k : 1;
+  g.tile = d.tile;
+  g.reverse = d.walk & 15;
+  g.half_occ = (d.walk >> 4) & 1;
+  g.sk_ws = d.sk_ws;
+  g.epi = d.epi;
+  g.aux = (R*)d.aux;
+  g.sumsq = d.sumsq;
+  g.nptr = d.nptr;
+  if (d.nptr < 0 || d.nptr > GEMM_MAXB) return d.nptr < 0 ? -3 : 0;  // too many: the launcher's own error, no copy
+  for (int b = 0; b < d.nptr; ++b) {
+    if (!d.Ap || !d.Bp || !d.Cp) return -3;
+    g.Ap[b] = (const R*)d.Ap[b];
+    g.Bp[b] = (const R*)d.Bp[b];
+    g.Cp[b] = (R*)d.Cp[b];
+    g.auxp[b] = d.auxp ? (R*)d.auxp[b] : nullptr;
+    g.sumsqp[b] = d.sumsqp ? d.sumsqp[b] : nullptr;
+  }
+  return 0;
+}
+
+template <typename R>
+int route(const gpfit_dev_gemm_args& d, const gpfit_dev_gemm_args* d2, gpfit_dev_gemm_route_t& o) {
+  std::memset(&o, 0, sizeof(o));
+  o.sk_first = -1;
+  GemmArgsT<R> a, b;
+  if (fill(d, a) != 0 || (d2 && fill(*d2, b) != 0)) return -3;
+  if (d2) {
+    const GemmShape h = gemm_pair_shape(a, b);
+    o.pair = h.tile != 0;
+    o.rc = o.pair ? 0 : -3;
+    o.tile = h.tile; o.stages = h.stages; o.blocks = h.tiles;
+    return 0;
+  }
+  if (a.M <= 0 || a.N <= 0) return 0;
+  o.tile = gemm_pick_tile(a);
+  // the refusals of launch_gemm: an epilogue the launch cannot carry, and launch_gemm_plain's argument errors (every
+  // schedule's launch ends there: the XCD table's as a whole, the head of a stream-K tail)
+  if ((a.epi && !gemm_epilogue_ok(a)) || gemm_plain_args_error(a)) { o.rc = -3; return 0; }
+  o.epi = a.epi;
+  o.sumsq_entries = gemm_sumsq_entries(a);
+  int sched = gemm_schedule(a);
+  if (sched == 2) {
+    const int first = streamk_first_tile(a);
+    SkHostPlan plan;
+    if (streamk_plan_host(a, first, plan) != 0) sched = 0;   // the planner declines: data-parallel
+    else { o.sk_first = first; o.blocks = plan.blocks; }
+  }
+  o.xcd = sched == 1;
+  if (sched == 2) { o.tile = TILE; o.stages = 2; return 0; }
+  GemmArgsT<R> p = a;
+  std::vector<int> table;
+  if (sched == 1) {
+    if (xcd_plan_host(a, table) != 0) return -3;
+    p.tile = TILE;
+    p.sched = table.data();   // never dereferenced here: the shape only asks whether there is one
+    p.sched_blocks = (int)table.size();
+  }
+  const GemmShape h = gemm_plain_shape(p);
+  o.tile = h.tile; o.stages = h.stages; o.edge = h.edge; o.half_occ = h.half;
+  o.blocks = (int)std::min<long>((long)h.gx * h.gy * h.gz, 0x7fffffffL);
+  return 0;
+}
+
+template <typename R>
+int64_t plan(const gpfit_dev_gemm_args& d, int kind, int32_t* out, int64_t cap) {
+  GemmArgsT<R> a;
+  if (fill(d, a) != 0 || a.M <= 0 || a.N <= 0) return -3;
+  if (a.epi && !gemm_epilogue_ok(a)) return -3;
+  const int sched = gemm_schedule(a);
+  if (kind == 1) {
+    if (sched != 1) return -1;
+    std::vector<int> table;
+    if (xcd_plan_host(a, table) != 0) return -1;
+    const int64_t need = 1 + (int64_t)table.size();
+    if (need > cap || !out) return need;
+    out[0] = (int32_t)table.size();
+    std::memcpy(out + 1, table.data(), table.size() * sizeof(int));
+    return need;
+  }
+  if (kind != 2) return -3;
+  if (sched != 2) return -1;
+  const int first = streamk_first_tile(a);
+  SkHostPlan p;
+  if (streamk_plan_host(a, first, p) != 0) return -1;
+  const int64_t nt = (int64_t)p.tiles.size(), nfix = (int64_t)p.fix_tile.size(), nslot = (int64_t)p.fix_slot.size();
+  const int64_t need = 8 + 5 * nt + nfix + (nfix + 1) + nslot;
+  if (need > cap || !out) return need;
+  out[0] = first; out[1] = (int32_t)nt; out[2] = p.total; out[3] = p.blocks; out[4] = p.per_block;
+  out[5] = (int32_t)nfix; out[6] = (int32_t)nslot;
+  out[7] = (int32_t)(SK_WS_BYTES / ((size_t)TILE * TILE * sizeof(double)));
+  int32_t* w = out + 8;
+  for (const SkTile& t : p.tiles) { *w++ = t.row0; *w++ = t.col0; *w++ = t.kbeg; *w++ = t.ksteps; *w++ = t.prefix; }
+  std::memcpy(w, p.fix_tile.data(), nfix * sizeof(int)); w += nfix;
+  std::memcpy(w, p.fix_ptr.data(), (nfix + 1) * sizeof(int)); w += nfix + 1;
+  std::memcpy(w, p.fix_slot.data(), nslot * sizeof(int));
+  return need;
+}
+
+template <typename R>
+int run(hipStream_t s, const gpfit_dev_gemm_args& d, const gpfit_dev_gemm_args* d2) {
+  GemmArgsT<R> a, b;
+  if (fill(d, a) != 0 || (d2 && fill(*d2, b) != 0)) {
+    set_error("gpfit_dev_gemm: a pointer batch needs its pointer arrays");
+    return -3;
+  }
+  return d2 ? launch_gemm_pair(a, b, s) : launch_gemm(a, s);
+}
+
+}  // namespace
+}  // namespace gpfit
+
+extern "C" {
+
+int gpfit_dev_gemm_route(int is_f32, const gpfit_dev_gemm_args* args, const gpfit_dev_gemm_args* pair_args,
+                         gpfit_dev_gemm_route_t* out) {
+  if (!args || !out) return -3;
+  return is_f32 ? gpfit::route<float>(*args, pair_args, *out) : gpfit::route<double>(*args, pair_args, *out);
+}
+
+int64_t gpfit_dev_gemm_plan(int is_f32, const gpfit_dev_gemm_args* args, int kind, int32_t* out, int64_t cap) {
+  if (!args) return -3;
+  return is_f32 ? gpfit::plan<float>(*args, kind, out, cap) : gpfit::plan<double>(*args, kind, out, cap);
+}
+
+int gpfit_dev_gemm(void* stream, int is_f32, const gpfit_dev_gemm_args* args, const gpfit_dev_gemm_args* pair_args) {
+  if (!args) return -3;
+  return is_f32 ? gpfit::run<float>((hipStream_t)stream, *args, pair_args)
+                : gpfit::run<double>((hipStream_t)stream, *args, pair_args);
+}
+
+}  // extern "C"

@@ -65,7 +65,8 @@ struct GemmArgsT {
   int64_t sA, sB, sC;        // batch strides (elements)
   int split_k;               // >1: partial products written to C + z*sC (beta ignored)
   int tile;                  // 0 = choose (128 / 64 / 32), else forced block tile
-  int reverse;               // tile walk: bit 0 backwards, bit 1 column-major (dense output)
+  int reverse;               // tile walk (gemm_walk_tile, gemm_core.h): bit 0 backwards, bit 1 column-major, bit 2 k
+                             // downwards, bit 3 ask for the XCD-aware table
   int workspace;             // stream-K partial-tile workspace to use (0 main stream, 1 side stream)
   void* sk_ws;               // caller-owned stream-K workspace (>= SK_WS_BYTES); nullptr: process-wide one
   int tile_limit;            // >0: launch only the first tile_limit tiles of the walk (stream-K head)
@@ -131,6 +132,20 @@ template <typename R> bool gemm_streamk_carries(const GemmArgsT<R>& a);   // gem
 // tile + one per fix-up band); the squared Frobenius norm is the sum over all of them either way
 template <typename R> int gemm_sumsq_entries(const GemmArgsT<R>& a);
 template <typename R> bool gemm_xcd_applies(const GemmArgsT<R>& a);       // gemm_sched.hip
+// What the launcher decides before it launches, for the test hooks (api_dev.hip) as much as for itself:
+// the schedule launch_gemm gives a launch (0 data-parallel, 1 XCD-aware table, 2 stream-K) and the grid / instance
+// of a data-parallel launch (launch_gemm_plain, launch_gemm_pair).
+struct GemmShape {
+  int tile, tiles, tiles_n;  // block tile, tiles of one problem, tiles per tile row
+  int gx, gy, gz;            // grid
+  int edge;                  // predicated (ragged) instance
+  int stages;                // LDS stages of the main loop: 2, or the deep pipeline's 4 (64-tiles) / 8 (32-tiles)
+  int half;                  // half-occupancy launch
+};
+template <typename R> int gemm_schedule(const GemmArgsT<R>& a);
+template <typename R> const char* gemm_plain_args_error(const GemmArgsT<R>& a);   // nullptr: fine; else launch_gemm_plain's -3
+template <typename R> GemmShape gemm_plain_shape(const GemmArgsT<R>& a);
+template <typename R> GemmShape gemm_pair_shape(const GemmArgsT<R>& a, const GemmArgsT<R>& b);
 
 // Arc-cosine Gram matrix from the k-major, zero-padded operands XCt[Kd][ld1], Xt[Kd][ld2]:
 //   G = XCt^T Xt + s0^2 ; c = clip(G/(q1 q2 + 1e-7)) ; K = q1 q2 J(c)

@@ -23,32 +23,15 @@ __device__ __forceinline__ bool gemm_tile_compute(const GemmArgsT<R>& p, int til
 
   // heaviest tiles first: with triangular operands the k range depends on the tile position,
   // so the launcher asks for the walk that starts with the long ones (shorter tail):
-  // bit 0 = walk backwards, bit 1 = column-major (dense output only).
-  const int bid = (p.reverse & 1) ? (ntiles - 1 - (int)blockIdx.x) : (int)blockIdx.x;
+  // bit 0 = walk backwards, bit 1 = column-major (gemm_walk_tile, gemm_core.h).
   if (p.sched != nullptr) {
     // XCD-aware schedule: the table says which tile this block id computes (-1: padding entry)
     const int e = p.sched[blockIdx.x];
     if (e < 0) return false;
     ti = e >> 16;
     tj = e & 0xffff;
-  } else if (p.out_lower && (p.reverse & 2) && T == TILE) {
-    // column-major walk of the lower triangle: the tiles of a tile column share op(B)'s panel and,
-    // where the k range depends on the column only, stay at the same k (lock step in L2)
-    const int nt = tiles_n;
-    int j = (int)((2.0 * nt + 1.0 - sqrt((2.0 * nt + 1.0) * (2.0 * nt + 1.0) - 8.0 * (double)bid)) * 0.5);
-    while (j > 0 && (long)j * nt - (long)j * (j - 1) / 2 > bid) --j;
-    while ((long)(j + 1) * nt - (long)(j + 1) * j / 2 <= bid) ++j;
-    tj = j;
-    ti = j + (bid - (j * nt - j * (j - 1) / 2));
-  } else if (p.out_lower) {
-    lower_tile(bid, TILE / T, ti, tj);
-  } else if (p.reverse & 2) {
-    const int tiles_m = ntiles / tiles_n;
-    tj = bid / tiles_m;
-    ti = bid % tiles_m;
   } else {
-    ti = bid / tiles_n;
-    tj = bid % tiles_n;
+    gemm_walk_tile((int)blockIdx.x, p.reverse, p.out_lower != 0, TILE / T, tiles_n, ntiles, ti, tj);
   }
   row0 = ti * T;
   col0 = tj * T;
@@ -243,19 +226,49 @@ static void allow_dynamic_lds(const void* fn) {
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, HALF_OCC_LDS);
 }
 
+// Grid and instance of a data-parallel launch on T-tiles (batch already normalised: launch_gemm_plain).
 template <typename R, int T>
-static void launch_T(const GemmArgsT<R>& p, hipStream_t s) {
-  const int tm = (p.M + T - 1) / T, tn = (p.N + T - 1) / T;
-  const int tiles = p.out_lower ? lower_tile_count((p.M + TILE - 1) / TILE, TILE / T) : tm * tn;
-  const bool edge = (p.M % T) || (p.N % T) || (p.out_lower && (p.M % TILE));
-  dim3 grid(p.sched ? p.sched_blocks : (p.tile_limit > 0 ? std::min(p.tile_limit, tiles) : tiles), p.batch,
-            p.split_k > 1 ? p.split_k : 1);
-  dim3 block(GEMM_THREADS);
+static GemmShape plain_shape_T(const GemmArgsT<R>& p) {
+  GemmShape h{};
+  h.tile = T;
+  h.tiles_n = (p.N + T - 1) / T;
+  const int tm = (p.M + T - 1) / T;
+  h.tiles = p.out_lower ? lower_tile_count((p.M + TILE - 1) / TILE, TILE / T) : tm * h.tiles_n;
+  h.edge = (p.M % T) || (p.N % T) || (p.out_lower && (p.M % TILE));
+  h.gx = p.sched ? p.sched_blocks : (p.tile_limit > 0 ? std::min(p.tile_limit, h.tiles) : h.tiles);
+  h.gy = p.batch;
+  h.gz = p.split_k > 1 ? p.split_k : 1;
   constexpr int DEEP = (T == 128) ? 2 : (T == 64 ? 4 : 8);
   static const int deep_max = getenv("GPFIT_DEEP_MAX") ? atoi(getenv("GPFIT_DEEP_MAX")) : 512;  // tuning knob
-  const bool deep = DEEP > 2 && !edge && (long)grid.x * grid.y * grid.z <= deep_max;
+  const bool deep = DEEP > 2 && !h.edge && (long)h.gx * h.gy * h.gz <= deep_max;
+  h.stages = deep ? DEEP : 2;
   // half-occupancy launches (T = 128 only): 64 KiB static + 17 KiB of unused dynamic LDS = 81 KiB > 160 / 2
-  const bool half = (T == TILE) && p.half_occ && !deep;
+  h.half = (T == TILE) && p.half_occ && !deep;
+  return h;
+}
+
+template <typename R>
+GemmShape gemm_plain_shape(const GemmArgsT<R>& a) {
+  GemmArgsT<R> p = a;
+  if (p.nptr > 0) p.batch = p.nptr;
+  if (p.batch <= 0) p.batch = 1;
+  switch (gemm_pick_tile(p)) {
+    case 128: return plain_shape_T<R, 128>(p);
+    case 64: return plain_shape_T<R, 64>(p);
+    default: return plain_shape_T<R, 32>(p);
+  }
+}
+template GemmShape gemm_plain_shape<double>(const GemmArgsT<double>&);
+template GemmShape gemm_plain_shape<float>(const GemmArgsT<float>&);
+
+template <typename R, int T>
+static void launch_T(const GemmArgsT<R>& p, hipStream_t s) {
+  const GemmShape h = plain_shape_T<R, T>(p);
+  const int tn = h.tiles_n, tiles = h.tiles;
+  const bool edge = h.edge, deep = h.stages > 2, half = h.half;
+  dim3 grid(h.gx, h.gy, h.gz);
+  dim3 block(GEMM_THREADS);
+  constexpr int DEEP = (T == 128) ? 2 : (T == 64 ? 4 : 8);
 #define GP_LAUNCH(AK, BK, ED)                                                                          \
   do {                                                                                                 \
     if (deep) hipLaunchKernelGGL((gemm_mfma_kernel<R, AK, BK, ED, T, (ED ? 2 : DEEP)>), grid, block, 0, s, p, tn, tiles); \
@@ -331,6 +344,22 @@ template int gemm_sumsq_entries<float>(const GemmArgsT<float>&);
 template bool gemm_epilogue_ok<double>(const GemmArgsT<double>&);
 template bool gemm_epilogue_ok<float>(const GemmArgsT<float>&);
 
+// The schedule launch_gemm gives a launch: 0 data-parallel, 1 XCD-aware table, 2 stream-K (whose planner may still
+// decline a launch with an empty tile, which then stays data-parallel).
+template <typename R>
+int gemm_schedule(const GemmArgsT<R>& a) {
+  if (a.nptr > 0) return 0;   // pointer batches are data-parallel launches
+  if (a.half_occ) return 0;
+  if (a.tile_limit == 0 && gemm_pick_tile(a) == TILE && a.batch <= 1) {
+    if ((a.reverse & 8) && gemm_xcd_applies(a)) return 1;
+    // the fused epilogues other than the one gemm_streamk_carries names live in the data-parallel kernels only
+    if (streamk_first_tile(a) >= 0 && !(a.epi && !gemm_streamk_carries(a))) return 2;
+  }
+  return 0;
+}
+template int gemm_schedule<double>(const GemmArgsT<double>&);
+template int gemm_schedule<float>(const GemmArgsT<float>&);
+
 template <typename R>
 int launch_gemm(const GemmArgsT<R>& a, hipStream_t s) {
   if (a.M <= 0 || a.N <= 0) return 0;
@@ -338,41 +367,41 @@ int launch_gemm(const GemmArgsT<R>& a, hipStream_t s) {
     set_error("launch_gemm: this launch cannot carry a fused epilogue (ask gemm_epilogue_ok first)");
     return -3;
   }
-  if (a.nptr > 0) return launch_gemm_plain(a, s);   // pointer batches are data-parallel launches
-  if (a.half_occ) return launch_gemm_plain(a, s);
-  if (a.tile_limit == 0 && gemm_pick_tile(a) == TILE && a.batch <= 1) {
-    if (a.reverse & 8) {
-      const int rc = launch_gemm_xcd(a, s);    // XCD-aware data-parallel schedule (gemm_sched.hip)
-      if (rc <= 0) return rc;
+  switch (gemm_schedule(a)) {
+    case 1: return launch_gemm_xcd(a, s);        // XCD-aware data-parallel schedule (gemm_sched.hip)
+    case 2: {
+      const int rc = launch_gemm_streamk(a, s);  // large launches: balanced schedules (gemm_streamk.hip)
+      if (rc <= 0) return rc;                    // 1: the planner declined
     }
-    const int rc = launch_gemm_streamk(a, s);  // large launches: balanced schedules (gemm_streamk.hip)
-    if (rc <= 0) return rc;
   }
   return launch_gemm_plain(a, s);
 }
 
+// The argument errors of a data-parallel launch: nullptr, or what is wrong (launch_gemm_plain returns -3 with it).
 template <typename R>
-int launch_gemm_plain(const GemmArgsT<R>& a, hipStream_t s) {
-  if (a.M <= 0 || a.N <= 0) return 0;
+const char* gemm_plain_args_error(const GemmArgsT<R>& a) {
   // odd M/N are fine for the stores; k-major operands are then read up to one 16-byte chunk past
   // M/N, which internal callers cover with zero padding (the public gpfit_dgemm insists on even).
   constexpr int EPC = 16 / (int)sizeof(R);
-  if (a.K % ktile_of<R>() != 0 || (a.lda % EPC) || (a.ldb % EPC)) {
-    set_error("launch_gemm: K must be a multiple of the K step and lda, ldb multiples of 16 bytes");
-    return -3;
-  }
-  if (a.out_lower && a.M != a.N) {
-    set_error("launch_gemm: out_lower needs a square output");
+  if (a.K % ktile_of<R>() != 0 || (a.lda % EPC) || (a.ldb % EPC))
+    return "launch_gemm: K must be a multiple of the K step and lda, ldb multiples of 16 bytes";
+  if (a.out_lower && a.M != a.N) return "launch_gemm: out_lower needs a square output";
+  if (a.nptr > 0 && (a.nptr > GEMM_MAXB || a.sched || a.split_k > 1))
+    return "launch_gemm: a pointer batch holds at most GEMM_MAXB plain problems";
+  return nullptr;
+}
+template const char* gemm_plain_args_error<double>(const GemmArgsT<double>&);
+template const char* gemm_plain_args_error<float>(const GemmArgsT<float>&);
+
+template <typename R>
+int launch_gemm_plain(const GemmArgsT<R>& a, hipStream_t s) {
+  if (a.M <= 0 || a.N <= 0) return 0;
+  if (const char* err = gemm_plain_args_error(a)) {
+    set_error(err);
     return -3;
   }
   GemmArgsT<R> p = a;
-  if (p.nptr > 0) {
-    if (p.nptr > GEMM_MAXB || p.sched || p.split_k > 1) {
-      set_error("launch_gemm: a pointer batch holds at most GEMM_MAXB plain problems");
-      return -3;
-    }
-    p.batch = p.nptr;
-  }
+  if (p.nptr > 0) p.batch = p.nptr;
   if (p.batch <= 0) p.batch = 1;
   switch (gemm_pick_tile(p)) {
     case 128: launch_T<R, 128>(p, s); break;
@@ -411,6 +440,30 @@ static int pair_member_tile(const GemmArgsT<R>& a) {
   return (T == 32 || T == 64) ? T : 0;
 }
 
+// stages as launch_T picks them: the deep pipeline when the launch has at most two workgroups per CU
+static bool pair_deep(long total_tiles) {
+  static const int deep_max = getenv("GPFIT_DEEP_MAX") ? atoi(getenv("GPFIT_DEEP_MAX")) : 512;
+  return total_tiles <= deep_max;
+}
+template <typename R>
+static long pair_total_tiles(const GemmArgsT<R>& p, int T) {
+  return (long)(p.out_lower ? lower_tile_count(p.M / TILE, TILE / T) : (p.M / T) * (p.N / T)) * p.nptr;
+}
+
+// tile and stages of the shared launch (tile 0: the two cannot share one)
+template <typename R>
+GemmShape gemm_pair_shape(const GemmArgsT<R>& a, const GemmArgsT<R>& b) {
+  GemmShape h{};
+  if (!gemm_pair_ok(a, b)) return h;
+  h.tile = pair_member_tile(a);
+  const long total = pair_total_tiles(a, h.tile) + pair_total_tiles(b, h.tile);
+  h.tiles = (int)total;
+  h.stages = pair_deep(total) ? (h.tile == 32 ? 8 : 4) : 2;
+  return h;
+}
+template GemmShape gemm_pair_shape<double>(const GemmArgsT<double>&, const GemmArgsT<double>&);
+template GemmShape gemm_pair_shape<float>(const GemmArgsT<float>&, const GemmArgsT<float>&);
+
 template <typename R>
 bool gemm_pair_ok(const GemmArgsT<R>& a, const GemmArgsT<R>& b) {
   static const bool off = getenv("GPFIT_NO_PAIR") != nullptr;   // tuning knob: the two launches on their own
@@ -442,14 +495,13 @@ int launch_gemm_pair(const GemmArgsT<R>& a, const GemmArgsT<R>& b, hipStream_t s
     q.tiles[w] = p.out_lower ? lower_tile_count(p.M / TILE, TILE / T) : tm * tn;
     gx = std::max(gx, q.tiles[w]);
     gy = std::max(gy, p.batch);
-    total += (long)q.tiles[w] * p.batch;
+    total += pair_total_tiles(p, T);
   }
   const dim3 grid(gx, gy, 2), block(GEMM_THREADS);
-  // stages as launch_T picks them: the deep pipeline when the launch has at most two workgroups per CU
-  static const int deep_max = getenv("GPFIT_DEEP_MAX") ? atoi(getenv("GPFIT_DEEP_MAX")) : 512;
-  if (T == 32 && total <= deep_max) hipLaunchKernelGGL((gemm_pair_kernel<R, 32, 8>), grid, block, 0, s, q);
+  const bool deep = pair_deep(total);
+  if (T == 32 && deep) hipLaunchKernelGGL((gemm_pair_kernel<R, 32, 8>), grid, block, 0, s, q);
   else if (T == 32) hipLaunchKernelGGL((gemm_pair_kernel<R, 32, 2>), grid, block, 0, s, q);
-  else if (total <= deep_max) hipLaunchKernelGGL((gemm_pair_kernel<R, 64, 4>), grid, block, 0, s, q);
+  else if (deep) hipLaunchKernelGGL((gemm_pair_kernel<R, 64, 4>), grid, block, 0, s, q);
   else hipLaunchKernelGGL((gemm_pair_kernel<R, 64, 2>), grid, block, 0, s, q);
   GP_HIP(hipGetLastError());
   return 0;

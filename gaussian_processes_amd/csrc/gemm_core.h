@@ -16,6 +16,7 @@
 #include "common.h"
 
 #include <cstdint>
+#include <vector>
 
 namespace gpfit {
 
@@ -404,5 +405,55 @@ __device__ __host__ inline void lower_tile(int t, int r, int& ti, int& tj) {
   tj = v % w;
 }
 __host__ __device__ inline int lower_tile_count(int nblocks, int r) { return r * r * (nblocks * (nblocks + 1) / 2); }
+
+// THE tile walk: block b of a launch of ntiles tiles (tiles_n per tile row; lower output: tiles_n per side and
+// r = 128 / T sub-tiles per block side) computes tile (ti, tj).  walk bit 0: backwards; bit 1: column-major, for
+// a dense output and for the lower triangle on 128-tiles (the small-tile instances keep the block-row order of
+// lower_tile).  The data-parallel kernels (gemm.hip) and the stream-K planner (gemm_streamk.hip), which cuts the
+// tail [first, ntiles) of the same walk along k, both enumerate through this function and nothing else does, so
+// head and tail partition the output whatever the bits say.
+__host__ __device__ __forceinline__ void gemm_walk_tile(int b, int walk, bool lower, int r, int tiles_n, int ntiles,
+                                                        int& ti, int& tj) {
+  const int bid = (walk & 1) ? (ntiles - 1 - b) : b;
+  if (lower && (walk & 2) && r == 1) {
+    // column-major walk of the lower triangle: the tiles of a tile column share op(B)'s panel and,
+    // where the k range depends on the column only, stay at the same k (lock step in L2)
+    const int nt = tiles_n;
+    int j = (int)((2.0 * nt + 1.0 - sqrt((2.0 * nt + 1.0) * (2.0 * nt + 1.0) - 8.0 * (double)bid)) * 0.5);
+    while (j > 0 && (long)j * nt - (long)j * (j - 1) / 2 > bid) --j;
+    while ((long)(j + 1) * nt - (long)(j + 1) * j / 2 <= bid) ++j;
+    tj = j;
+    ti = j + (bid - (j * nt - j * (j - 1) / 2));
+  } else if (lower) {
+    lower_tile(bid, r, ti, tj);
+  } else if (walk & 2) {
+    const int tiles_m = ntiles / tiles_n;
+    tj = bid / tiles_m;
+    ti = bid % tiles_m;
+  } else {
+    ti = bid / tiles_n;
+    tj = bid % tiles_n;
+  }
+}
+
+// ---- host-side plans of the balanced schedules (no GPU call; the launchers upload them, the test hooks of
+// api_dev.hip hand them out)
+struct SkTile {
+  int row0, col0, kbeg, ksteps;
+  int prefix;  // k-steps of all tiles before this one in walk order (< 2^31: 4096 tiles x 512 steps)
+};
+struct SkHostPlan {
+  std::vector<SkTile> tiles;   // the stream-K tiles (the walk's [first, all)) in walk order
+  int total = 0, blocks = 0, per_block = 0;
+  std::vector<int> fix_tile;   // split tile ids
+  std::vector<int> fix_ptr;    // CSR offsets into fix_slot
+  std::vector<int> fix_slot;   // workspace slots in accumulation order
+};
+// first: number of leading tiles that stay data-parallel (tails of uniform launches); -1: not a stream-K launch
+template <typename R> int streamk_first_tile(const GemmArgsT<R>& a);
+// 0 planned, 1 the planner declines (a tile with an empty k range): the launch stays data-parallel
+template <typename R> int streamk_plan_host(const GemmArgsT<R>& a, int first, SkHostPlan& plan);
+// the XCD-aware tile table (gemm_sched.hip): entry = ti << 16 | tj, -1 padding; its length is the grid size
+template <typename R> int xcd_plan_host(const GemmArgsT<R>& a, std::vector<int>& table);
 
 }  // namespace gpfit

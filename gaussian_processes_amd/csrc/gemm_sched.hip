@@ -39,7 +39,7 @@ struct Item {
 }  // namespace
 
 template <typename R>
-static int build(const GemmArgsT<R>& a, Plan& plan) {
+int xcd_plan_host(const GemmArgsT<R>& a, std::vector<int>& table) {
   constexpr int KT = 128 / (int)sizeof(R);
   const int tm = a.M / TILE, tn = a.N / TILE;
   auto ksteps = [&](int ti, int tj) {
@@ -100,9 +100,19 @@ static int build(const GemmArgsT<R>& a, Plan& plan) {
   }
   size_t len = 0;
   for (auto& q : queue) len = std::max(len, q.size());
-  std::vector<int> table(8 * len, -1);
+  table.assign(8 * len, -1);
   for (int x = 0; x < 8; ++x)
     for (size_t i = 0; i < queue[x].size(); ++i) table[8 * i + x] = queue[x][i];
+  return 0;
+}
+template int xcd_plan_host<double>(const GemmArgsT<double>&, std::vector<int>&);
+template int xcd_plan_host<float>(const GemmArgsT<float>&, std::vector<int>&);
+
+// plan it on the host, then upload
+template <typename R>
+static int build(const GemmArgsT<R>& a, Plan& plan) {
+  std::vector<int> table;
+  GP_TRY(xcd_plan_host(a, table));
   plan.blocks = (int)table.size();
   GP_HIP(hipMalloc((void**)&plan.table, table.size() * sizeof(int)));
   GP_HIP(hipMemcpy(plan.table, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice));

@@ -23,11 +23,6 @@
 
 namespace gpfit {
 
-struct SkTile {
-  int row0, col0, kbeg, ksteps;
-  int prefix;  // k-steps of all tiles before this one in walk order (< 2^31: 4096 tiles x 512 steps)
-};
-
 struct SkPlan {
   SkTile* tiles = nullptr;   // device
   int ntiles = 0;
@@ -210,21 +205,21 @@ static std::mutex g_plan_mutex;
 // streams issuing large GEMMs never share partial tiles.  Sized for fp64, used by fp32 as well.
 static std::map<std::pair<int, hipStream_t>, void*> g_workspace;
 
+// The plan on the host: the tiles [first, all) of the launch's walk (gemm_walk_tile, the enumeration the
+// data-parallel head of the launch uses as well) with their k ranges, the cut, and the fix-up lists.
 template <typename R>
-static int build_plan(const GemmArgsT<R>& a, int first, SkPlan& plan) {
+int streamk_plan_host(const GemmArgsT<R>& a, int first, SkHostPlan& plan) {
   constexpr int KT = 128 / (int)sizeof(R);
   const int tm = a.M / TILE, tn = a.N / TILE;
   const int all_tiles = a.out_lower ? tm * (tm + 1) / 2 : tm * tn;
   const int ntiles = all_tiles - first;
-  std::vector<SkTile> tiles;
+  std::vector<SkTile>& tiles = plan.tiles;
+  tiles.clear();
   tiles.reserve(ntiles);
   long long prefix = 0;
   for (int b = first; b < all_tiles; ++b) {
-    const int bid = (a.reverse & 1) ? (all_tiles - 1 - b) : b;
     int ti, tj;
-    if (a.out_lower) tri_tile(bid, ti, tj);
-    else if (a.reverse & 2) { tj = bid / tm; ti = bid % tm; }
-    else { ti = bid / tn; tj = bid % tn; }
+    gemm_walk_tile(b, a.reverse, a.out_lower != 0, 1, tn, all_tiles, ti, tj);
     int kb = 0, ke = a.K;
     if (a.a_tri == 1) ke = std::min(ke, ti * TILE + TILE);
     if (a.a_tri == 2) kb = std::max(kb, ti * TILE);
@@ -235,7 +230,6 @@ static int build_plan(const GemmArgsT<R>& a, int first, SkPlan& plan) {
     tiles.push_back(SkTile{ti * TILE, tj * TILE, kb, ks, (int)prefix});
     prefix += ks;
   }
-  plan.ntiles = ntiles;
   if (prefix >= (1LL << 31)) return 1;
   plan.total = (int)prefix;
   // at most 16 shares per tile: finer cuts only add partial-tile traffic and fix-up work
@@ -259,23 +253,40 @@ static int build_plan(const GemmArgsT<R>& a, int first, SkPlan& plan) {
       ++tt;
     }
   }
-  std::vector<int> fix_tile, fix_ptr{0}, fix_slot;
+  plan.fix_tile.clear();
+  plan.fix_slot.clear();
+  plan.fix_ptr.assign(1, 0);
   for (int i = 0; i < ntiles; ++i)
     if (!slots[i].empty()) {
-      fix_tile.push_back(i);
-      fix_slot.insert(fix_slot.end(), slots[i].begin(), slots[i].end());
-      fix_ptr.push_back((int)fix_slot.size());
+      plan.fix_tile.push_back(i);
+      plan.fix_slot.insert(plan.fix_slot.end(), slots[i].begin(), slots[i].end());
+      plan.fix_ptr.push_back((int)plan.fix_slot.size());
     }
-  plan.nfix = (int)fix_tile.size();
-  GP_HIP(hipMalloc((void**)&plan.tiles, tiles.size() * sizeof(SkTile)));
-  GP_HIP(hipMemcpy(plan.tiles, tiles.data(), tiles.size() * sizeof(SkTile), hipMemcpyHostToDevice));
+  return 0;
+}
+template int streamk_plan_host<double>(const GemmArgsT<double>&, int, SkHostPlan&);
+template int streamk_plan_host<float>(const GemmArgsT<float>&, int, SkHostPlan&);
+
+// plan it on the host, then upload
+template <typename R>
+static int build_plan(const GemmArgsT<R>& a, int first, SkPlan& plan) {
+  SkHostPlan h;
+  const int rc = streamk_plan_host(a, first, h);
+  if (rc != 0) return rc;
+  plan.ntiles = (int)h.tiles.size();
+  plan.total = h.total;
+  plan.blocks = h.blocks;
+  plan.per_block = h.per_block;
+  plan.nfix = (int)h.fix_tile.size();
+  GP_HIP(hipMalloc((void**)&plan.tiles, h.tiles.size() * sizeof(SkTile)));
+  GP_HIP(hipMemcpy(plan.tiles, h.tiles.data(), h.tiles.size() * sizeof(SkTile), hipMemcpyHostToDevice));
   if (plan.nfix) {
-    GP_HIP(hipMalloc((void**)&plan.fix_tile, fix_tile.size() * sizeof(int)));
-    GP_HIP(hipMalloc((void**)&plan.fix_ptr, fix_ptr.size() * sizeof(int)));
-    GP_HIP(hipMalloc((void**)&plan.fix_slot, fix_slot.size() * sizeof(int)));
-    GP_HIP(hipMemcpy(plan.fix_tile, fix_tile.data(), fix_tile.size() * sizeof(int), hipMemcpyHostToDevice));
-    GP_HIP(hipMemcpy(plan.fix_ptr, fix_ptr.data(), fix_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-    GP_HIP(hipMemcpy(plan.fix_slot, fix_slot.data(), fix_slot.size() * sizeof(int), hipMemcpyHostToDevice));
+    GP_HIP(hipMalloc((void**)&plan.fix_tile, h.fix_tile.size() * sizeof(int)));
+    GP_HIP(hipMalloc((void**)&plan.fix_ptr, h.fix_ptr.size() * sizeof(int)));
+    GP_HIP(hipMalloc((void**)&plan.fix_slot, h.fix_slot.size() * sizeof(int)));
+    GP_HIP(hipMemcpy(plan.fix_tile, h.fix_tile.data(), h.fix_tile.size() * sizeof(int), hipMemcpyHostToDevice));
+    GP_HIP(hipMemcpy(plan.fix_ptr, h.fix_ptr.data(), h.fix_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
+    GP_HIP(hipMemcpy(plan.fix_slot, h.fix_slot.data(), h.fix_slot.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   return 0;
 }
@@ -290,7 +301,7 @@ static int build_plan(const GemmArgsT<R>& a, int first, SkPlan& plan) {
 //    are cut along k over the whole chip.
 // first: number of leading tiles that stay data-parallel (tails of uniform launches); -1: not a stream-K launch
 template <typename R>
-static int streamk_first_tile(const GemmArgsT<R>& a) {
+int streamk_first_tile(const GemmArgsT<R>& a) {
   static const bool disabled = getenv("GPFIT_NO_STREAMK") != nullptr;
   if (disabled) return -1;
   if ((a.M % TILE) || (a.N % TILE) || a.split_k > 1 || a.batch > 1 || a.nptr > 0 || (a.tile && a.tile != TILE)) return -1;
@@ -317,6 +328,9 @@ static int streamk_first_tile(const GemmArgsT<R>& a) {
   }
   return first;
 }
+
+template int streamk_first_tile<double>(const GemmArgsT<double>&);
+template int streamk_first_tile<float>(const GemmArgsT<float>&);
 
 template <typename R>
 bool gemm_streamk_applies(const GemmArgsT<R>& a) { return streamk_first_tile(a) >= 0; }

@@ -46,7 +46,8 @@ int gpfit_dgemm(void* stream, int a_kmajor, int b_kmajor, int M, int N, int K, d
 /* Same with the tuning knobs exposed: walk (bit 0: tile grid backwards, bit 1: column-major -- also
  * for the lower triangle of an out_lower launch --, bit 2: every tile walks k downwards, bit 3: XCD-aware
  * macro-tile schedule for launches of >= 1536 tiles, bit 4: one workgroup per CU)
- * and tile (0 = automatic, or 128 / 64 / 32). */
+ * and tile (0 = automatic, or 128 / 64 / 32).  Where only the tail of a launch takes the stream-K schedule,
+ * head and tail follow the same walk, so every combination of the bits covers the output exactly once. */
 int gpfit_dgemm_ex(void* stream, int a_kmajor, int b_kmajor, int M, int N, int K, double alpha,
                    const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
                    int64_t ldc, int out_lower, int a_tri, int b_tri, int walk, int tile);
@@ -332,6 +333,67 @@ int gpfit_fit_eval_f32(gpfit_ctx* ctx, void* stream, const double* theta, const 
  * (flops = blocks*4 waves*iters*16*2048) and a 16-byte-per-lane stream copy. */
 int gpfit_probe_mfma_f64(void* stream, double* scratch, int blocks, int iters);
 int gpfit_probe_stream_copy(void* stream, const double* in, double* out, int64_t n_doubles);
+
+/* ---- test hooks ----------------------------------------------------------------------
+ * For the test-suite (tests/test_gemm_plans_cpu.py, tests/test_gpu_gemm_schedules.py), not for
+ * applications: the GEMM launcher with every field of its argument struct exposed, and host-only
+ * queries of what it would do with a launch.  They add no arithmetic of their own. */
+typedef struct gpfit_dev_gemm_args {
+  const void* A;            /* device operands of element type double (is_f32 = 0) or float (1) */
+  const void* B;
+  void* C;
+  int64_t lda, ldb, ldc;
+  int64_t sA, sB, sC;       /* strides (elements) of a strided batch; sC also separates the slabs of split_k */
+  double alpha, beta;
+  void* sk_ws;              /* caller-owned stream-K workspace, or NULL */
+  void* aux;                /* epi 4 */
+  double* sumsq;            /* epi 2 */
+  const void* const* Ap;    /* nptr > 0: HOST arrays of nptr device pointers each (auxp, sumsqp may be NULL) */
+  const void* const* Bp;
+  void* const* Cp;
+  void* const* auxp;
+  double* const* sumsqp;
+  int32_t M, N, K;
+  int32_t a_kmajor, b_kmajor, out_lower, a_tri, b_tri;
+  int32_t batch;            /* problems of a strided batch (0 or 1: one) */
+  int32_t split_k;          /* > 1: k slabs, slab z written to C + z sC, beta ignored */
+  int32_t tile;             /* 0 automatic, or 128 / 64 / 32 */
+  int32_t walk;             /* as gpfit_dgemm_ex */
+  int32_t epi;              /* fused epilogue: 0 none, 1 mirror, 2 tile norms, 4 dual update */
+  int32_t nptr;             /* > 0: pointer batch of nptr problems (at most 32) */
+} gpfit_dev_gemm_args;
+
+typedef struct gpfit_dev_gemm_route_t {
+  int32_t rc;               /* 0, or -3: the launch would refuse its arguments (an epilogue it cannot carry, K not a
+                             * multiple of the K step, lda / ldb not multiples of 16 bytes, lower with M != N, a pointer
+                             * batch of more than 32 or with split_k; a pair that cannot share a launch) */
+  int32_t tile;             /* block tile: 128 / 64 / 32 */
+  int32_t sk_first;         /* stream-K: -1 not taken, 0 every tile, > 0 tiles of the data-parallel head */
+  int32_t xcd;              /* 1: XCD-aware schedule table */
+  int32_t stages;           /* LDS stages of the main loop: 2, deep pipeline 4 (64-tiles) / 8 (32-tiles) */
+  int32_t half_occ;         /* 1: half-occupancy launch */
+  int32_t edge;             /* 1: predicated (ragged) instance */
+  int32_t epi;              /* fused epilogue the launch carries */
+  int32_t sumsq_entries;    /* entries of sumsq an epi-2 launch writes (per problem) */
+  int32_t blocks;           /* workgroups of the (main) launch; pair: tiles of both members */
+  int32_t pair;             /* pair query: 1 the two launches can share one */
+  int32_t reserved;
+} gpfit_dev_gemm_route_t;
+
+/* What the launcher would do with these arguments (pair_args != NULL: with the two as one pair launch).  Host only,
+ * no GPU call, pointers are not dereferenced.  0, or -3 for a malformed query. */
+int gpfit_dev_gemm_route(int is_f32, const gpfit_dev_gemm_args* args, const gpfit_dev_gemm_args* pair_args,
+                         gpfit_dev_gemm_route_t* out);
+/* The plan of a balanced schedule, as the launcher would upload it.  Host only.  kind 2, stream-K:
+ *   out[0..7] = first, ntiles, total k-steps, blocks, per_block, nfix, nslot, workspace slots available;
+ *   then ntiles records (row0, col0, kbeg, ksteps, prefix) in walk order, fix_tile[nfix] (indices into the
+ *   records), fix_ptr[nfix + 1], fix_slot[nslot].
+ * kind 1, XCD-aware table: out[0] = length, then the table (ti << 16 | tj, -1 padding).
+ * Returns the number of int32 the plan takes (nothing is written when that exceeds cap), -1 when the launch does
+ * not take that schedule, -3 on a bad argument. */
+int64_t gpfit_dev_gemm_plan(int is_f32, const gpfit_dev_gemm_args* args, int kind, int32_t* out, int64_t cap);
+/* launch_gemm on these arguments, or launch_gemm_pair when pair_args is given.  Return value as gpfit_dgemm. */
+int gpfit_dev_gemm(void* stream, int is_f32, const gpfit_dev_gemm_args* args, const gpfit_dev_gemm_args* pair_args);
 
 #ifdef __cplusplus
 }
