@@ -20,13 +20,13 @@ class DevGemmArgs(ctypes.Structure):
                 [("alpha", f64), ("beta", f64)] +
                 [(n, vp) for n in ("sk_ws", "aux", "sumsq", "Ap", "Bp", "Cp", "auxp", "sumsqp")] +
                 [(n, ctypes.c_int32) for n in ("M", "N", "K", "a_kmajor", "b_kmajor", "out_lower", "a_tri", "b_tri", "batch",
-                                               "split_k", "tile", "walk", "epi", "nptr")])
+                                               "split_k", "tile", "walk", "epi", "nptr", "k_slabs")])
 
 
 class DevGemmRoute(ctypes.Structure):
     """gpfit_dev_gemm_route_t."""
     _fields_ = [(n, ctypes.c_int32) for n in ("rc", "tile", "sk_first", "xcd", "stages", "half_occ", "edge", "epi",
-                                              "sumsq_entries", "blocks", "pair", "reserved")]
+                                              "sumsq_entries", "blocks", "pair", "slabs")]
 
 
 _SIGS = {
@@ -74,6 +74,8 @@ _SIGS = {
     "gpfit_dev_gemm_route": (i32, [i32, ctypes.POINTER(DevGemmArgs), ctypes.POINTER(DevGemmArgs), ctypes.POINTER(DevGemmRoute)]),
     "gpfit_dev_gemm_plan": (i64, [i32, ctypes.POINTER(DevGemmArgs), i32, ctypes.POINTER(ctypes.c_int32), i64]),
     "gpfit_dev_gemm": (i32, [vp, i32, ctypes.POINTER(DevGemmArgs), ctypes.POINTER(DevGemmArgs)]),
+    "gpfit_dev_ctx_copy": (i32, [vp, ctypes.c_char_p, i64, vp, i64, i32]),
+    "gpfit_dev_ctx_fill": (i32, [vp, ctypes.c_char_p, i32]),
 }
 
 _lib = None

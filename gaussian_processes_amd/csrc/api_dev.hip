@@ -3,6 +3,7 @@
 // split-K, fused epilogues, the pair launch).  No arithmetic happens here: the hooks fill the launcher's own
 // argument struct and ask the launcher's own predicates (gemm.hip, gemm_streamk.hip, gemm_sched.hip).
 #include "gemm_core.h"
+#include "context.h"
 #include "gpfit_mi355x.h"
 
 #include <cstring>
@@ -22,6 +23,7 @@ int fill(const gpfit_dev_gemm_args& d, GemmArgsT<R>& g) {
   g.batch = d.batch > 0 ? d.batch : 1;
   g.sA = d.sA; g.sB = d.sB; g.sC = d.sC;
   g.split_k = d.split_k > 0 ? d.split_k : 1;
+  g.k_slabs = d.k_slabs > 0 ? d.k_slabs : 0;
   g.tile = d.tile;
   g.reverse = d.walk & 15;
   g.half_occ = (d.walk >> 4) & 1;
@@ -82,6 +84,7 @@ int route(const gpfit_dev_gemm_args& d, const gpfit_dev_gemm_args* d2, gpfit_dev
   const GemmShape h = gemm_plain_shape(p);
   o.tile = h.tile; o.stages = h.stages; o.edge = h.edge; o.half_occ = h.half;
   o.blocks = (int)std::min<long>((long)h.gx * h.gy * h.gz, 0x7fffffffL);
+  if (a.k_slabs > 0) o.slabs = slab_plan(a.M, a.k_slabs).live;
   return 0;
 }
 
@@ -99,6 +102,24 @@ int64_t plan(const gpfit_dev_gemm_args& d, int kind, int32_t* out, int64_t cap) 
     if (need > cap || !out) return need;
     out[0] = (int32_t)table.size();
     std::memcpy(out + 1, table.data(), table.size() * sizeof(int));
+    return need;
+  }
+  if (kind == 3) {
+    // the slab plan of the triangular-operand route: the items in launch order with their k ranges
+    if (a.k_slabs <= 0) return -1;
+    if (gemm_plain_args_error(a)) return -3;
+    const SlabPlan sp = slab_plan(a.M, a.k_slabs);
+    const int64_t need = 4 + 4 * (int64_t)sp.items;
+    if (need > cap || !out) return need;
+    out[0] = sp.items; out[1] = sp.live; out[2] = sp.ks * SLAB_TILE; out[3] = SLAB_TILE;
+    for (int e = 0; e < sp.items; ++e) {
+      int ti, z;
+      slab_item(sp, e, ti, z);
+      int32_t* w = out + 4 + 4 * e;
+      w[0] = ti; w[1] = z;
+      w[2] = std::max(ti, z * sp.ks) * SLAB_TILE;
+      w[3] = std::min((z + 1) * sp.ks, sp.nt) * SLAB_TILE;
+    }
     return need;
   }
   if (kind != 2) return -3;
@@ -130,6 +151,20 @@ int run(hipStream_t s, const gpfit_dev_gemm_args& d, const gpfit_dev_gemm_args* 
   return d2 ? launch_gemm_pair(a, b, s) : launch_gemm(a, s);
 }
 
+// a work buffer of the context by name, with its size in bytes
+struct CtxBuf { void* p; int64_t bytes; };
+CtxBuf ctx_buffer(gpfit_ctx* c, const char* name) {
+  const int64_t np = c->np_cap, dp = c->dp_cap, nn = np * np * 8;
+  const struct { const char* n; double* p; int64_t bytes; } tab[] = {
+      {"Abuf", c->Abuf, nn}, {"Tbuf", c->Tbuf, nn}, {"Wbuf", c->Wbuf, nn}, {"Zbuf", c->Zbuf, nn}, {"Cos", c->Cos, nn},
+      {"TmpV", c->TmpV, nn}, {"Xm", c->Xm, np * dp * 8}, {"Xt2", c->Xt2, np * dp * 8}, {"Ybuf", c->Ybuf, np * dp * 8},
+      {"Mmat", c->Mmat, dp * dp * 8}, {"Cmat", c->Cmat, dp * dp * 8}, {"tvec", c->tvec, 2 * np * 8}, {"bv", c->bv, np * 8},
+      {"q", c->q, np * 8}, {"wl", c->wl, np * 8}, {"q2", c->q2, np * 8}, {"dq1", c->dq1, np * 8}, {"dq2", c->dq2, np * 8}};
+  for (const auto& t : tab)
+    if (std::strcmp(t.n, name) == 0) return {t.p, t.bytes};
+  return {nullptr, 0};
+}
+
 }  // namespace
 }  // namespace gpfit
 
@@ -150,6 +185,29 @@ int gpfit_dev_gemm(void* stream, int is_f32, const gpfit_dev_gemm_args* args, co
   if (!args) return -3;
   return is_f32 ? gpfit::run<float>((hipStream_t)stream, *args, pair_args)
                 : gpfit::run<double>((hipStream_t)stream, *args, pair_args);
+}
+
+int gpfit_dev_ctx_copy(gpfit_ctx* ctx, const char* name, int64_t offset, void* dev, int64_t bytes, int to_ctx) {
+  if (!ctx || !name || !dev || offset < 0 || bytes < 0 || ctx->pend.active) return -3;
+  gpfit::DeviceGuard guard(ctx->device);
+  const gpfit::CtxBuf b = gpfit::ctx_buffer(ctx, name);
+  if (!b.p || offset + bytes > b.bytes) return -3;
+  GP_HIP(hipDeviceSynchronize());
+  char* w = (char*)b.p + offset;
+  GP_HIP(hipMemcpy(to_ctx ? (void*)w : dev, to_ctx ? dev : (void*)w, (size_t)bytes, hipMemcpyDeviceToDevice));
+  GP_HIP(hipDeviceSynchronize());
+  return 0;
+}
+
+int gpfit_dev_ctx_fill(gpfit_ctx* ctx, const char* name, int byte) {
+  if (!ctx || !name || ctx->pend.active) return -3;
+  gpfit::DeviceGuard guard(ctx->device);
+  const gpfit::CtxBuf b = gpfit::ctx_buffer(ctx, name);
+  if (!b.p) return -3;
+  GP_HIP(hipDeviceSynchronize());
+  GP_HIP(hipMemset(b.p, byte, (size_t)b.bytes));
+  GP_HIP(hipDeviceSynchronize());
+  return 0;
 }
 
 }  // extern "C"

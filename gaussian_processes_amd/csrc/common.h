@@ -64,6 +64,12 @@ struct GemmArgsT {
   int batch;                 // number of independent problems (grid.y)
   int64_t sA, sB, sC;        // batch strides (elements)
   int split_k;               // >1: partial products written to C + z*sC (beta ignored)
+  int k_slabs;               // >0: the triangular-operand route (a_tri == 2, square op(A), M == K a multiple of 64):
+                             // 64-tiles, k cut into at most k_slabs fixed slabs of whole tiles (slab_plan below),
+                             // one workgroup per (tile, slab) whose k range is not empty, heavy items first; slab z of
+                             // a row panel goes to C + z*sC (beta ignored) and the panel's live slabs are
+                             // z >= panel / tiles-per-slab.  A function of (M, k_slabs) alone: the same cut for one
+                             // problem and for a pointer batch.
   int tile;                  // 0 = choose (128 / 64 / 32), else forced block tile
   int reverse;               // tile walk (gemm_walk_tile, gemm_core.h): bit 0 backwards, bit 1 column-major, bit 2 k
                              // downwards, bit 3 ask for the XCD-aware table
@@ -103,6 +109,48 @@ struct GemmArgsT {
   double* sumsqp[GEMM_MAXB]; // epi 2: problem b's tile-norm table
 };
 using GemmArgs = GemmArgsT<double>;
+
+// ---- the slab plan of the triangular-operand route (GemmArgsT::k_slabs)
+// op(A) is upper triangular on nt x nt tiles of SLAB_TILE: row panel ti needs the k tiles [ti, nt).  k is cut into
+// slabs of ks = ceil(nt / S) tiles (live slabs: ceil(nt / ks) <= S) and an item is a (panel, slab) pair whose
+// k range [max(ti, z ks), min((z + 1) ks, nt)) is not empty.  Items in launch order, heavy first: the full ones
+// (ti <= z ks, slab by slab), then those that start r = ti - z ks = 1, 2, .. tiles into their slab (ks - r tiles
+// each; the last slab's are clipped at nt).  Kernel and host hooks enumerate through slab_item and nothing else.
+constexpr int SLAB_TILE = 64;
+struct SlabPlan {
+  int nt, ks, live;   // tiles per side, tiles per slab, live slabs
+  int full, rb;       // number of full items; partial items with r < rb exist in every live slab, the rest in all but the last
+  int items;
+};
+__host__ __device__ inline SlabPlan slab_plan(int M, int slabs) {
+  SlabPlan p;
+  p.nt = (M + SLAB_TILE - 1) / SLAB_TILE;
+  p.ks = (p.nt + slabs - 1) / slabs;
+  p.live = (p.nt + p.ks - 1) / p.ks;
+  p.full = p.live + p.ks * (p.live * (p.live - 1) / 2);
+  p.rb = p.nt - (p.live - 1) * p.ks;
+  p.items = p.full + (p.rb - 1) * p.live + (p.ks - p.rb) * (p.live - 1);
+  return p;
+}
+__host__ __device__ inline void slab_item(const SlabPlan& p, int e, int& ti, int& z) {
+  if (e < p.full) {
+    for (z = 0; e >= z * p.ks + 1; ++z) e -= z * p.ks + 1;
+    ti = e;
+    return;
+  }
+  e -= p.full;
+  int r;
+  const int head = (p.rb - 1) * p.live;
+  if (e < head) {
+    r = 1 + e / p.live;
+    z = e % p.live;
+  } else {
+    e -= head;
+    r = p.rb + e / (p.live - 1);
+    z = e % (p.live - 1);
+  }
+  ti = z * p.ks + r;
+}
 
 // K step staged through LDS: 16 KiB per operand per stage at T = 128 for either type
 constexpr size_t SK_WS_BYTES = (size_t)2 * 512 * TILE * TILE * sizeof(double);  // 2 partial tiles per resident workgroup

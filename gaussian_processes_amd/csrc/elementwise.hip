@@ -376,6 +376,48 @@ int launch_reduce_slices(const RI* src, int64_t slice_stride, int nslice, RO* ds
   return 0;
 }
 
+// dst[i][c] = sum of the live slabs z >= i / slab_rows of src[z][i][c], in slab order: the k slabs of a product with
+// an upper triangular op(A) (GemmArgsT::k_slabs) -- the slabs below a row's own never were written
+template <typename R>
+__global__ void reduce_slabs_kernel(const R* __restrict__ src, int64_t stride, int nslab, int slab_rows,
+                                    R* __restrict__ dst, int cols, int64_t count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  double v = 0.0;
+  for (int z = min(nslab - 1, (int)(i / cols) / slab_rows); z < nslab; ++z) v += (double)src[(int64_t)z * stride + i];
+  dst[i] = (R)v;
+}
+template <typename R>
+int launch_reduce_slabs(const R* src, int64_t slab_stride, int nslab, int slab_rows, R* dst, int rows, int cols, hipStream_t s) {
+  const int64_t count = (int64_t)rows * cols;
+  hipLaunchKernelGGL(reduce_slabs_kernel<R>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, src, slab_stride,
+                     nslab, slab_rows, dst, cols, count);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// dst = G + G^T with G = sum_z src[z] (n x n, in slice order): exactly symmetric, one pass
+template <typename R>
+__global__ void reduce_slices_sym_kernel(const R* __restrict__ src, int64_t stride, int nslice, R* __restrict__ dst, int n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n * n) return;
+  const int r = (int)(i / n), c = (int)(i % n);
+  const int64_t it = (int64_t)c * n + r;
+  double v = 0.0, w = 0.0;
+  for (int z = 0; z < nslice; ++z) {
+    v += (double)src[(int64_t)z * stride + i];
+    w += (double)src[(int64_t)z * stride + it];
+  }
+  dst[i] = (R)(v + w);
+}
+template <typename R>
+int launch_reduce_slices_sym(const R* src, int64_t slice_stride, int nslice, R* dst, int n, hipStream_t s) {
+  hipLaunchKernelGGL(reduce_slices_sym_kernel<R>, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, s, src,
+                     slice_stride, nslice, dst, n);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 template <typename R>
 int launch_trmv_lower_t(const R* L, int64_t ldl, int np, const R* x, R* z, double* partial, hipStream_t s) {
   const int chunks = (np + TRMV_ROWS - 1) / TRMV_ROWS;
@@ -579,12 +621,14 @@ int launch_moments(const R* Kvec, const R* q, const R* Cos, int64_t ldc, const R
 }
 
 // ------------------------------------------------------------------ adjoint pass (64 x 64 tiles)
+// Aout receives Lambda = tril(A_w, -1) + 1/2 diag(A_w) (A_w = Lambda + Lambda^T): every lower tile once, the
+// diagonal tiles with half the diagonal and zeros above it (the product that consumes Lambda reads whole diagonal
+// tiles); the tiles above the diagonal are not touched.
 template <typename R>
 __global__ __launch_bounds__(256) void adjoint_kernel(const R* __restrict__ W, const R* __restrict__ Cos, int64_t ld,
                                                       const R* __restrict__ b, const R* __restrict__ q, int n,
                                                       int np, R* __restrict__ Aout, double* __restrict__ upart,
                                                       double* __restrict__ vpart, double* __restrict__ sumA_part) {
-  __shared__ R tA[64][65];
   __shared__ double colsum[4][64];
   __shared__ double sh[17];
   int ti, tj;
@@ -612,8 +656,7 @@ __global__ __launch_bounds__(256) void adjoint_kernel(const R* __restrict__ W, c
       aw = w * (PI32 - acos(c)) / PI32;
       bm = w * sqrt(1.0 - c * c) / PI32;
     }
-    tA[rr][tx] = (R)aw;
-    Aout[(int64_t)i * ld + j] = (R)aw;
+    Aout[(int64_t)i * ld + j] = (R)((diag && i <= j) ? (i == j ? 0.5 * aw : 0.0) : aw);
     asum += aw;
     // row sum over the 64 columns of this tile (one wave holds a whole row)
     const double rs = wave_sum(bm * qj);
@@ -622,14 +665,7 @@ __global__ __launch_bounds__(256) void adjoint_kernel(const R* __restrict__ W, c
   }
   colsum[ty][tx] = csum;
   __syncthreads();
-  if (!diag) {
-    if (ty == 0) vpart[(int64_t)ti * np + j] = colsum[0][tx] + colsum[1][tx] + colsum[2][tx] + colsum[3][tx];
-    // mirrored tile: Aout[j][i] = Aw[i][j]
-    for (int rr = ty; rr < 64; rr += 4) {
-      const int jj = tj * 64 + rr, ii = ti * 64 + tx;
-      Aout[(int64_t)jj * ld + ii] = tA[tx][rr];
-    }
-  }
+  if (!diag && ty == 0) vpart[(int64_t)ti * np + j] = colsum[0][tx] + colsum[1][tx] + colsum[2][tx] + colsum[3][tx];
   asum = block_sum(asum, sh);
   if (threadIdx.x == 0) sumA_part[blockIdx.x] = diag ? asum : 2.0 * asum;
 }
@@ -809,16 +845,16 @@ int launch_adjoint_reduce(const double* upart, const double* vpart, const double
 
 template <typename R>
 __global__ void rowscale_add_kernel(R* __restrict__ Y, int64_t ldy, const R* __restrict__ Xm, int64_t ldm,
-                                    const R* __restrict__ t, int dp) {
+                                    const R* __restrict__ t, int dp, R scale) {
   const int i = blockIdx.y;
-  const R ti = t[i];
+  const R ti = scale * t[i];
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < dp; k += gridDim.x * blockDim.x)
     Y[(int64_t)i * ldy + k] += ti * Xm[(int64_t)i * ldm + k];
 }
 
 template <typename R>
-int launch_rowscale_add(R* Y, int64_t ldy, const R* Xm, int64_t ldm, const R* t, int np, int dp, hipStream_t s) {
-  hipLaunchKernelGGL(rowscale_add_kernel<R>, dim3((dp + 255) / 256, np), dim3(256), 0, s, Y, ldy, Xm, ldm, t, dp);
+int launch_rowscale_add(R* Y, int64_t ldy, const R* Xm, int64_t ldm, const R* t, int np, int dp, hipStream_t s, double scale) {
+  hipLaunchKernelGGL(rowscale_add_kernel<R>, dim3((dp + 255) / 256, np), dim3(256), 0, s, Y, ldy, Xm, ldm, t, dp, (R)scale);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -1349,7 +1385,9 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
                                  double*, hipStream_t);                                                             \
   template int launch_adjoint_reduce<R>(const double*, const double*, const double*, int, int, const R*, const R*,  \
                                         int, int, R*, double*, double*, hipStream_t);                               \
-  template int launch_rowscale_add<R>(R*, int64_t, const R*, int64_t, const R*, int, int, hipStream_t);             \
+  template int launch_rowscale_add<R>(R*, int64_t, const R*, int64_t, const R*, int, int, hipStream_t, double);     \
+  template int launch_reduce_slabs<R>(const R*, int64_t, int, int, R*, int, int, hipStream_t);                      \
+  template int launch_reduce_slices_sym<R>(const R*, int64_t, int, R*, int, hipStream_t);                           \
   template int launch_reduce_slices<R, R>(const R*, int64_t, int, R*, int64_t, hipStream_t);                        \
   template int launch_metric_contract<R>(const Theta&, const int*, int, int, int, const R*, int64_t, const R*,      \
                                          int64_t, double*, double*, int*, hipStream_t);                             \

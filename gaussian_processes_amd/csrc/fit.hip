@@ -751,7 +751,9 @@ static int solve_mean(gpfit_ctx* c, int np, bool blocks, hipStream_t s) {
 }
 
 // ---- pull-back of an n x n adjoint to the d x d metric
-// Adjoint pass over the lower tiles of W: A_w into A (both triangles), t into tvec, the sums into scal[7..9].
+// Adjoint pass over the lower tiles of W: Lambda = tril(A_w, -1) + 1/2 diag(A_w) into the lower 64-tiles of A (zeros
+// above the diagonal inside the diagonal tiles; the tiles above it are neither written here nor read by
+// lambda_t_x_list), t into tvec, the sums into scal[7..9].
 template <typename R>
 static int adjoint_pass(gpfit_ctx* c, hipStream_t s, const R* W, const R* Cos, const R* bv, const R* q, const R* wl, int n,
                         int np, R* A, R* tvec) {
@@ -760,11 +762,12 @@ static int adjoint_pass(gpfit_ctx* c, hipStream_t s, const R* W, const R* Cos, c
   return launch_adjoint_reduce(c->upart, c->vpart, c->sumA_part, t64, t64 * (t64 + 1) / 2, q, wl, n, np, tvec, c->rpad,
                                c->scal + 7, s);
 }
-// out [dp][dp] = Xa^T Yb over np rows: split-k into the slabs of Mpart, added in slab order.  prof: the product is
+// out [dp][dp] = Xa^T Yb over np rows: split-k into the slabs of Mpart, added in slab order; sym: out = G + G^T with
+// G that sum (the same pass: no extra launch).  prof: the product is
 // counted by a profile (gpfit_set_profile(c, 1)) -- so far only for the full-rank unit (post_join_list); the
 // truncated-rank closures' profiles never counted theirs, and their launch counts stay as they were.
 template <typename R>
-static int xty(gpfit_ctx* c, hipStream_t s, const R* Xa, const R* Yb, int np, int dp, R* out, bool prof) {
+static int xty(gpfit_ctx* c, hipStream_t s, const R* Xa, const R* Yb, int np, int dp, R* out, bool prof, bool sym = false) {
   GemmArgsT<R> g{};
   g.A = Xa; g.B = Yb; g.C = ws_as<R>(c->Mpart);
   g.lda = dp; g.ldb = dp; g.ldc = dp;
@@ -777,17 +780,54 @@ static int xty(gpfit_ctx* c, hipStream_t s, const R* Xa, const R* Yb, int np, in
   } else {
     GP_TRY(launch_gemm(g, s));
   }
+  if (sym) return launch_reduce_slices_sym(ws_as<R>(c->Mpart), (int64_t)dp * dp, c->split_k_M, out, dp, s);
   return launch_reduce_slices(ws_as<R>(c->Mpart), (int64_t)dp * dp, c->split_k_M, out, (int64_t)dp * dp, s);
 }
-// Mmat = Xm^T (A_w + diag t) Xm for the adjoint W of acosker(x, x) on n stimuli (q, Cos, Xm theirs; A: np x np
-// scratch), with the b b^T and dKvec terms the caller left in bv / wl.  The contraction with dC_p
+// The pull-back in its Lambda form.  A_w = Lambda + Lambda^T, so
+//   M = Xm^T (A_w + diag t) Xm = G + G^T ,   G = Xm^T (Lambda^T Xm + 1/2 diag(t) Xm):
+// half the flops of A_w Xm, and the adjoint pass stores every tile once.
+// Slabs of the product Lambda^T Xm (GemmArgsT::k_slabs): a function of the shape alone -- a unit gets the same cut,
+// hence the same bits, alone and inside a group.  Four slabs from 32 tiles per side, two from 8, and never more
+// than fit the np x np scratch matrix (np x dp each).
+static int pullback_slabs(int np, int dp) {
+  const int nt = np / SLAB_TILE;
+  return std::max(1, std::min(nt >= 32 ? 4 : (nt >= 8 ? 2 : 1), np / dp));
+}
+// Y[i] = Lambda[i]^T Xm[i] for cnt units of one shape (np a multiple of 64): Lambda is read k-major as A_w was, so
+// op(A) is upper triangular (a_tri 2) and the launch walks each row panel's own k range only, cut into
+// (panel, slab) items of roughly equal length.  One launch -- a pointer batch for cnt > 1 -- then per unit the sum
+// of each row's live slabs, in slab order (no atomics).  scratch[i]: np x np elements, idle (Z behind W).
+template <typename R>
+static int lambda_t_x_list(hipStream_t s, int cnt, const R* const* Lam, const R* const* Xm, R* const* Y, R* const* scratch,
+                           int np, int dp) {
+  if (cnt <= 0 || cnt > GEMM_MAXB) return cnt == 0 ? 0 : -3;
+  const int slabs = pullback_slabs(np, dp);
+  const SlabPlan sp = slab_plan(np, slabs);
+  const bool direct = sp.live == 1;   // one slab: straight into Y
+  GemmArgsT<R> g = gemm_args<R>(1, 1, np, dp, np, 1.0, Lam[0], np, Xm[0], dp, 0.0, direct ? Y[0] : scratch[0], dp, 0, 2, 0);
+  g.k_slabs = slabs;
+  g.sC = (int64_t)np * dp;
+  if (cnt > 1) {
+    g.nptr = cnt;
+    g.batch = cnt;
+    for (int i = 0; i < cnt; ++i) { g.Ap[i] = Lam[i]; g.Bp[i] = Xm[i]; g.Cp[i] = direct ? Y[i] : scratch[i]; }
+  }
+  GP_TRY(run_gemm(s, g));
+  if (direct) return 0;
+  for (int i = 0; i < cnt; ++i)
+    GP_TRY(launch_reduce_slabs(scratch[i], (int64_t)np * dp, sp.live, sp.ks * SLAB_TILE, Y[i], np, dp, s));
+  return 0;
+}
+// Mmat = Xm^T (A_w + diag t) Xm for the adjoint W of acosker(x, x) on n stimuli (q, Cos, Xm theirs; A, scratch:
+// np x np work matrices), with the b b^T and dKvec terms the caller left in bv / wl.  The contraction with dC_p
 // (launch_metric_contract) is the caller's: the sparse closure adds two more d x d matrices first.
 static int pullback_to_metric(gpfit_ctx* c, hipStream_t s, const double* W, const double* Cos, const double* q, int n,
-                              int np, int dp, double* A, const double* Xm) {
+                              int np, int dp, double* A, const double* Xm, double* scratch) {
   GP_TRY(adjoint_pass<double>(c, s, W, Cos, c->bv, q, c->wl, n, np, A, c->tvec));
-  GP_TRY(gemm<double>(s, 1, 1, np, dp, np, 1.0, A, np, Xm, dp, 0.0, c->Ybuf, dp, 0, 0, 0));
-  GP_TRY(launch_rowscale_add(c->Ybuf, dp, Xm, dp, c->tvec, np, dp, s));
-  return xty<double>(c, s, Xm, c->Ybuf, np, dp, c->Mmat, false);
+  const double* Ac = A;
+  GP_TRY(lambda_t_x_list<double>(s, 1, &Ac, &Xm, &c->Ybuf, &scratch, np, dp));
+  GP_TRY(launch_rowscale_add(c->Ybuf, dp, Xm, dp, c->tvec, np, dp, s, 0.5));
+  return xty<double>(c, s, Xm, c->Ybuf, np, dp, c->Mmat, false, true);
 }
 
 // ---- the n_kept x n_kept algebra of the truncated-rank closures (nb = n_kept padded; leading dimension nb), in the
@@ -1016,6 +1056,7 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
   const R* Ap[GEMM_MAXB];
   const R* Bp[GEMM_MAXB];
   R* Cp[GEMM_MAXB];
+  R* Sp2[GEMM_MAXB];
   double* Sp[GEMM_MAXB];
   if (cnt <= 0 || cnt > GEMM_MAXB) return cnt == 0 ? 0 : -3;
   // T = L^-1 L_V (lower x lower -> lower);  tr(K~^-1 V) = ||T||_F^2
@@ -1073,20 +1114,20 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
   phase(6, s);
   for (int i = 0; i < cnt; ++i)
     GP_TRY(adjoint_pass<R>(cs[i], s, a[i].T, a[i].Cos, a[i].bv, a[i].q, a[i].wl, n, np, a[i].A, a[i].tvec));
-  // pull the contraction with dK~ back to the d x d metric: M = X^T (Aw + diag t) X   (units with the same
-  // masked pixel count share the launch)
+  // pull the contraction with dK~ back to the d x d metric: M = X^T (Aw + diag t) X = G + G^T (pullback_to_metric;
+  // units with the same masked pixel count share the launch, the others go one by one through the same route)
   {
     bool same_dp = true;
     for (int i = 1; i < cnt; ++i) same_dp = same_dp && dp[i] == dp[0];
-    for (int i = 0; i < cnt; ++i) { Ap[i] = a[i].A; Bp[i] = a[i].Xm; Cp[i] = a[i].Y; }
-    if (same_dp) GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, np, dp[0], np, 1.0, ld, dp[0], 0.0, dp[0], 0, 0, 0, 0, 0, cs[0]->sk_ws[0]));
+    for (int i = 0; i < cnt; ++i) { Ap[i] = a[i].A; Bp[i] = a[i].Xm; Cp[i] = a[i].Y; Sp2[i] = a[i].Z; }
+    if (same_dp) GP_TRY(lambda_t_x_list<R>(s, cnt, Ap, Bp, Cp, Sp2, np, dp[0]));
     else
-      for (int i = 0; i < cnt; ++i) GP_TRY(gemm<R>(s, 1, 1, np, dp[i], np, 1.0, a[i].A, ld, a[i].Xm, dp[i], 0.0, a[i].Y, dp[i], 0, 0, 0));
+      for (int i = 0; i < cnt; ++i) GP_TRY(lambda_t_x_list<R>(s, 1, Ap + i, Bp + i, Cp + i, Sp2 + i, np, dp[i]));
   }
   for (int i = 0; i < cnt; ++i) {
     gpfit_ctx* c = cs[i];
-    GP_TRY(launch_rowscale_add(a[i].Y, dp[i], a[i].Xm, dp[i], a[i].tvec, np, dp[i], s));
-    GP_TRY(xty<R>(c, s, a[i].Xm, a[i].Y, np, dp[i], a[i].Mmat, true));
+    GP_TRY(launch_rowscale_add(a[i].Y, dp[i], a[i].Xm, dp[i], a[i].tvec, np, dp[i], s, 0.5));
+    GP_TRY(xty<R>(c, s, a[i].Xm, a[i].Y, np, dp[i], a[i].Mmat, true, true));
     GP_TRY(launch_metric_contract(th[i], c->pix, d[i], n_rows, n_cols, a[i].Cmat, dp[i], a[i].Mmat, dp[i], c->scal + 10, c->upart,
                                   c->info + 3, s));
   }
@@ -1425,7 +1466,7 @@ static int grad_pullback_impl(gpfit_ctx* c, void* stream, const double* theta, i
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)np * sizeof(R), s));             // no -1/2 b b^T term here
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)np * sizeof(R), s));
   GP_TRY(launch_scale_copy<R>(c->wl, gvec, n, -1.0, s));                    // t_i = u_i / q_i + gvec_i
-  GP_TRY(pullback_to_metric(c, s, c->Wbuf, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm));
+  GP_TRY(pullback_to_metric(c, s, c->Wbuf, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));
   GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
@@ -1522,7 +1563,7 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)np * sizeof(R), s));
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)np * sizeof(R), s));
   GP_TRY(launch_scale_copy<R>(c->wl, gv, n, 1.0, s));
-  GP_TRY(pullback_to_metric(c, s, W, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm));
+  GP_TRY(pullback_to_metric(c, s, W, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
   GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1640,7 +1681,7 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   // (bv / wl are cleared over np_cap elements here, over np in the other two closures: each as it always was)
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)c->np_cap * sizeof(R), s));
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)c->np_cap * sizeof(R), s));
-  GP_TRY(pullback_to_metric(c, s, c->Wbuf, CosT, c->q2, n2, np2, dp, Kb, X2m));
+  GP_TRY(pullback_to_metric(c, s, c->Wbuf, CosT, c->q2, n2, np2, dp, Kb, X2m, am));   // a (Tmp) is dead
   // ---- rectangular pull-back (x, xtilde) with gvec = -g_v on the training side (dKvec term)
   GP_TRY(launch_scale_copy<R>(gvec, gv, n1, -1.0, s));
   double* t1 = c->tvec;
@@ -1816,7 +1857,7 @@ int gpfit_ctx_create(int device, int64_t n_max, int64_t d_max, int64_t d_full_ma
   GP_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   GP_HIP(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   // the strict-upper tiles of every triangular work matrix are never written and must read as 0
-  // wherever a dense GEMM touches them (Zbuf/Abuf are written in full; the others are only read
+  // wherever a dense GEMM touches them (Zbuf is written in full; the others are only read
   // through triangular k ranges) -- zero everything once so no kernel ever sees garbage.
   for (double* p : {c->Kbuf, c->Cos, c->Lbuf, c->Libuf, c->Vbuf, c->LVbuf, c->LiVbuf, c->Tbuf, c->Zbuf, c->Wbuf,
                     c->Abuf, c->Tmp, c->TmpV})

@@ -24,7 +24,15 @@ __device__ __forceinline__ bool gemm_tile_compute(const GemmArgsT<R>& p, int til
   // heaviest tiles first: with triangular operands the k range depends on the tile position,
   // so the launcher asks for the walk that starts with the long ones (shorter tail):
   // bit 0 = walk backwards, bit 1 = column-major (gemm_walk_tile, gemm_core.h).
-  if (p.sched != nullptr) {
+  int slab = 0, slab_tiles = 0;
+  const bool slabbed = (T == SLAB_TILE) && p.k_slabs > 0;   // gemm_pick_tile: the route runs on 64-tiles only
+  if (slabbed) {
+    // triangular-operand route: block = (item, tile column), the item's (panel, slab) from the slab plan
+    const SlabPlan sp = slab_plan(p.M, p.k_slabs);
+    slab_item(sp, (int)blockIdx.x / tiles_n, ti, slab);
+    tj = (int)blockIdx.x % tiles_n;
+    slab_tiles = sp.ks;
+  } else if (p.sched != nullptr) {
     // XCD-aware schedule: the table says which tile this block id computes (-1: padding entry)
     const int e = p.sched[blockIdx.x];
     if (e < 0) return false;
@@ -54,7 +62,11 @@ __device__ __forceinline__ bool gemm_tile_compute(const GemmArgsT<R>& p, int til
   if (p.b_tri == 1) kbeg = max(kbeg, col0);
   if (p.b_tri == 2) kend = min(kend, col0 + T);
   // tri bounds are multiples of T >= 32 = the largest K step, so they stay K-step aligned
-  if (p.split_k > 1) {
+  if (slabbed) {
+    kbeg = max(kbeg, slab * slab_tiles * T);
+    kend = min(kend, (slab + 1) * slab_tiles * T);
+    C += (int64_t)slab * p.sC;
+  } else if (p.split_k > 1) {
     const int steps = max(0, kend - kbeg) / KT;
     const int per = (steps + p.split_k - 1) / p.split_k;
     const int s0 = min(steps, z * per), s1 = min(steps, (z + 1) * per);
@@ -82,7 +94,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgsT<R>& p, int tiles_
   R* C;
   if (!gemm_tile_compute<R, A_KMAJOR, B_KMAJOR, EDGE, T, NS>(p, tiles_n, ntiles, smem, acc, ti, tj, row0, col0, C)) return;
 
-  const R alpha = (R)p.alpha, beta = (p.split_k > 1) ? (R)0 : (R)p.beta;
+  const R alpha = (R)p.alpha, beta = (p.split_k > 1 || (T == SLAB_TILE && p.k_slabs > 0)) ? (R)0 : (R)p.beta;
   const int64_t ldc = p.ldc;
   const int M = p.M, N = p.N;
   if constexpr (EPI != 0) {
@@ -193,6 +205,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_epi_kernel(GemmArgsT<R> 
 // the small panels near the leaves of the recursion are not serialised on a handful of CUs.
 template <typename R>
 int gemm_pick_tile(const GemmArgsT<R>& a) {
+  if (a.k_slabs > 0) return SLAB_TILE;   // the slab route's cut is in 64-tiles, whatever the size of the launch
   if (a.tile == 128 || a.tile == 64 || a.tile == 32) return a.tile;
   auto ntiles = [&](int T) {
     const long tm = (a.M + T - 1) / T, tn = (a.N + T - 1) / T;
@@ -236,6 +249,7 @@ static GemmShape plain_shape_T(const GemmArgsT<R>& p) {
   h.tiles = p.out_lower ? lower_tile_count((p.M + TILE - 1) / TILE, TILE / T) : tm * h.tiles_n;
   h.edge = (p.M % T) || (p.N % T) || (p.out_lower && (p.M % TILE));
   h.gx = p.sched ? p.sched_blocks : (p.tile_limit > 0 ? std::min(p.tile_limit, h.tiles) : h.tiles);
+  if (p.k_slabs > 0) h.gx = slab_plan(p.M, p.k_slabs).items * h.tiles_n;
   h.gy = p.batch;
   h.gz = p.split_k > 1 ? p.split_k : 1;
   constexpr int DEEP = (T == 128) ? 2 : (T == 64 ? 4 : 8);
@@ -314,7 +328,7 @@ static void launch_T(const GemmArgsT<R>& p, hipStream_t s) {
 
 template <typename R>
 bool gemm_epilogue_ok(const GemmArgsT<R>& a) {
-  if (a.split_k > 1 || (a.batch > 1 && a.nptr <= 0) || a.M <= 0 || a.N <= 0) return false;
+  if (a.split_k > 1 || a.k_slabs > 0 || (a.batch > 1 && a.nptr <= 0) || a.M <= 0 || a.N <= 0) return false;
   const int T = gemm_pick_tile(a);
   if ((a.M % T) || (a.N % T)) return false;                                    // full tiles only
   if ((a.epi & 1) && (!a.out_lower || a.M != a.N)) return false;
@@ -388,6 +402,10 @@ const char* gemm_plain_args_error(const GemmArgsT<R>& a) {
   if (a.out_lower && a.M != a.N) return "launch_gemm: out_lower needs a square output";
   if (a.nptr > 0 && (a.nptr > GEMM_MAXB || a.sched || a.split_k > 1))
     return "launch_gemm: a pointer batch holds at most GEMM_MAXB plain problems";
+  if (a.k_slabs > 0 &&
+      (a.a_tri != 2 || a.b_tri || a.out_lower || a.M != a.K || (a.M % SLAB_TILE) || a.split_k > 1 || a.sched || a.tile_limit ||
+       a.half_occ || (a.batch > 1 && a.nptr <= 0) || (a.tile != 0 && a.tile != SLAB_TILE)))
+    return "launch_gemm: k_slabs needs an upper triangular square op(A) on whole 64-tiles and a plain launch";
   return nullptr;
 }
 template const char* gemm_plain_args_error<double>(const GemmArgsT<double>&);
@@ -433,7 +451,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (NS > 2 ? 2 : 4)) void gemm_pair_kern
 template <typename R>
 static int pair_member_tile(const GemmArgsT<R>& a) {
   constexpr int EPC = 16 / (int)sizeof(R);
-  if (a.nptr <= 0 || a.nptr > GEMM_MAXB || a.epi || a.split_k > 1 || a.sched || a.half_occ || a.tile_limit || a.a_kmajor) return 0;
+  if (a.nptr <= 0 || a.nptr > GEMM_MAXB || a.epi || a.split_k > 1 || a.k_slabs > 0 || a.sched || a.half_occ || a.tile_limit || a.a_kmajor) return 0;
   if (a.M <= 0 || a.N <= 0 || (a.M % 64) || (a.N % 64) || (a.out_lower && ((a.M % TILE) || a.M != a.N))) return 0;
   if (a.K % ktile_of<R>() != 0 || (a.lda % EPC) || (a.ldb % EPC)) return 0;
   const int T = gemm_pick_tile(a);

@@ -112,7 +112,8 @@ int launch_moments(const R* Kvec, const R* q, const R* Cos, int64_t ldc, const R
 
 // Adjoint pass over the lower tiles of W (np x np):
 //   w = W_ij - 1/2 b_i b_j ; Aw = w (pi - acos c)/pi ; Bm = w sqrt(1-c^2)/pi
-//   Aw written to Aout symmetric (both triangles), zero on padding;
+//   Aout = Lambda = tril(Aw, -1) + 1/2 diag(Aw) on the lower 64-tiles (Aw = Lambda + Lambda^T; zeros above the
+//   diagonal inside the diagonal tiles, zero on padding); the tiles above the diagonal are not written;
 //   upart[tj][i] = sum_{j in tile tj} Bm_ij q_j  (+ mirrored contribution -> vpart[ti][j])
 //   sumA_part[tile] = sum of Aw over the tile (off-diagonal tiles counted twice)
 template <typename R>
@@ -124,12 +125,19 @@ template <typename R>
 int launch_adjoint_reduce(const double* upart, const double* vpart, const double* sumA_part, int ntile,
                           int ntile_tri, const R* q, const R* wl, int n, int np, R* tvec, double* uq,
                           double* scal_out, hipStream_t s);
-// Y[n][k] += t[n] * Xm[n][k]
+// Y[n][k] += scale * t[n] * Xm[n][k]
 template <typename R>
-int launch_rowscale_add(R* Y, int64_t ldy, const R* Xm, int64_t ldm, const R* t, int np, int dp, hipStream_t s);
+int launch_rowscale_add(R* Y, int64_t ldy, const R* Xm, int64_t ldm, const R* t, int np, int dp, hipStream_t s,
+                        double scale = 1.0);
 // dst = sum_z src[z] (split-K reduction), count elements each
 template <typename RI, typename RO>
 int launch_reduce_slices(const RI* src, int64_t slice_stride, int nslice, RO* dst, int64_t count, hipStream_t s);
+// dst [rows][cols] = sum over the live k slabs of a row, z >= row / slab_rows, of src[z] (GemmArgsT::k_slabs)
+template <typename R>
+int launch_reduce_slabs(const R* src, int64_t slab_stride, int nslab, int slab_rows, R* dst, int rows, int cols, hipStream_t s);
+// dst = G + G^T, G = sum_z src[z] (n x n)
+template <typename R>
+int launch_reduce_slices_sym(const R* src, int64_t slice_stride, int nslice, R* dst, int n, hipStream_t s);
 // grad5[p] = sum_kl dC_p[k][l] * M[k][l] for the five metric hyperparameters, dC recomputed from C
 template <typename R>
 int launch_metric_contract(const Theta& th, const int* pix, int d, int n_rows, int n_cols, const R* C, int64_t ldc,

@@ -361,6 +361,10 @@ typedef struct gpfit_dev_gemm_args {
   int32_t walk;             /* as gpfit_dgemm_ex */
   int32_t epi;              /* fused epilogue: 0 none, 1 mirror, 2 tile norms, 4 dual update */
   int32_t nptr;             /* > 0: pointer batch of nptr problems (at most 32) */
+  int32_t k_slabs;          /* > 0: the triangular-operand route (a_tri 2, M == K a multiple of 64): 64-tiles, k in
+                             * at most k_slabs fixed slabs, one workgroup per (tile, slab) with a non-empty k range;
+                             * slab z of a row panel written to C + z sC, beta ignored; the slabs below a panel's own
+                             * k range are not written */
 } gpfit_dev_gemm_args;
 
 typedef struct gpfit_dev_gemm_route_t {
@@ -377,7 +381,7 @@ typedef struct gpfit_dev_gemm_route_t {
   int32_t sumsq_entries;    /* entries of sumsq an epi-2 launch writes (per problem) */
   int32_t blocks;           /* workgroups of the (main) launch; pair: tiles of both members */
   int32_t pair;             /* pair query: 1 the two launches can share one */
-  int32_t reserved;
+  int32_t slabs;            /* k_slabs route: live slabs (0: not that route) */
 } gpfit_dev_gemm_route_t;
 
 /* What the launcher would do with these arguments (pair_args != NULL: with the two as one pair launch).  Host only,
@@ -389,11 +393,18 @@ int gpfit_dev_gemm_route(int is_f32, const gpfit_dev_gemm_args* args, const gpfi
  *   then ntiles records (row0, col0, kbeg, ksteps, prefix) in walk order, fix_tile[nfix] (indices into the
  *   records), fix_ptr[nfix + 1], fix_slot[nslot].
  * kind 1, XCD-aware table: out[0] = length, then the table (ti << 16 | tj, -1 padding).
+ * kind 3, slab plan of the k_slabs route: out[0..3] = items, live slabs, k per slab, tile; then per item in launch
+ *   order (row panel, slab, kbeg, kend); every tile column of a panel runs the same items.
  * Returns the number of int32 the plan takes (nothing is written when that exceeds cap), -1 when the launch does
  * not take that schedule, -3 on a bad argument. */
 int64_t gpfit_dev_gemm_plan(int is_f32, const gpfit_dev_gemm_args* args, int kind, int32_t* out, int64_t cap);
 /* launch_gemm on these arguments, or launch_gemm_pair when pair_args is given.  Return value as gpfit_dgemm. */
 int gpfit_dev_gemm(void* stream, int is_f32, const gpfit_dev_gemm_args* args, const gpfit_dev_gemm_args* pair_args);
+/* A context's work buffer by its name in the sources ("Abuf", "Tbuf", "Wbuf", "Zbuf", "Cos", "TmpV", "Xm", "Xt2", "Ybuf",
+ * "Mmat", "Cmat", "tvec", "bv", "q", "wl", "q2", "dq1", "dq2"): copy `bytes` bytes at byte `offset` to (to_ctx = 0) or
+ * from (1) the device pointer `dev`, or fill the whole buffer with one byte value.  Synchronous.  0, or -3. */
+int gpfit_dev_ctx_copy(gpfit_ctx* ctx, const char* name, int64_t offset, void* dev, int64_t bytes, int to_ctx);
+int gpfit_dev_ctx_fill(gpfit_ctx* ctx, const char* name, int byte);
 
 #ifdef __cplusplus
 }
