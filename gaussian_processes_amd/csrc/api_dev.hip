@@ -1,7 +1,7 @@
 // C-ABI test hooks of the GEMM launcher: which route a launch takes, the plans of the balanced schedules, and an
 // entry point that reaches every field of GemmArgsT (both element types, pointer batches, strided batches,
 // split-K, fused epilogues, the pair launch).  No arithmetic happens here: the hooks fill the launcher's own
-// argument struct and ask the launcher's own predicates (gemm.hip, gemm_streamk.hip, gemm_sched.hip).
+// argument struct and read the launcher's own decision (gemm_route, common.h) and its planners.
 #include "gemm_core.h"
 #include "context.h"
 #include "gpfit_mi355x.h"
@@ -44,47 +44,31 @@ int fill(const gpfit_dev_gemm_args& d, GemmArgsT<R>& g) {
   return 0;
 }
 
+// The route as the launcher computes it, field by field, and the verdict of the schedule's planner: the table's
+// length for an XCD route, the stream-K kernel's grid -- or the planner's decline, with which the launch stays
+// data-parallel exactly as launch_gemm then runs it.
 template <typename R>
 int route(const gpfit_dev_gemm_args& d, const gpfit_dev_gemm_args* d2, gpfit_dev_gemm_route_t& o) {
   std::memset(&o, 0, sizeof(o));
   o.sk_first = -1;
   GemmArgsT<R> a, b;
   if (fill(d, a) != 0 || (d2 && fill(*d2, b) != 0)) return -3;
-  if (d2) {
-    const GemmShape h = gemm_pair_shape(a, b);
-    o.pair = h.tile != 0;
-    o.rc = o.pair ? 0 : -3;
-    o.tile = h.tile; o.stages = h.stages; o.blocks = h.tiles;
-    return 0;
-  }
-  if (a.M <= 0 || a.N <= 0) return 0;
-  o.tile = gemm_pick_tile(a);
-  // the refusals of launch_gemm: an epilogue the launch cannot carry, and launch_gemm_plain's argument errors (every
-  // schedule's launch ends there: the XCD table's as a whole, the head of a stream-K tail)
-  if ((a.epi && !gemm_epilogue_ok(a)) || gemm_plain_args_error(a)) { o.rc = -3; return 0; }
-  o.epi = a.epi;
-  o.sumsq_entries = gemm_sumsq_entries(a);
-  int sched = gemm_schedule(a);
-  if (sched == 2) {
-    const int first = streamk_first_tile(a);
+  GemmRoute r = d2 ? gemm_pair_shape(a, b) : gemm_route(a);
+  long blocks = d2 ? r.tiles : -1;   // pair: tiles of both members; stream-K: its kernel's grid; else the route's grid
+  if (r.rc == 0 && r.sched == GEMM_STREAMK) {
     SkHostPlan plan;
-    if (streamk_plan_host(a, first, plan) != 0) sched = 0;   // the planner declines: data-parallel
-    else { o.sk_first = first; o.blocks = plan.blocks; }
+    if (streamk_plan_host(a, r.sk_first, plan) != 0) r.stay_data_parallel();
+    else blocks = plan.blocks;
   }
-  o.xcd = sched == 1;
-  if (sched == 2) { o.tile = TILE; o.stages = 2; return 0; }
-  GemmArgsT<R> p = a;
-  std::vector<int> table;
-  if (sched == 1) {
+  if (r.rc == 0 && r.sched == GEMM_XCD) {
+    std::vector<int> table;
     if (xcd_plan_host(a, table) != 0) return -3;
-    p.tile = TILE;
-    p.sched = table.data();   // never dereferenced here: the shape only asks whether there is one
-    p.sched_blocks = (int)table.size();
+    r.gx = (int)table.size();   // as launch_gemm_xcd
   }
-  const GemmShape h = gemm_plain_shape(p);
-  o.tile = h.tile; o.stages = h.stages; o.edge = h.edge; o.half_occ = h.half;
-  o.blocks = (int)std::min<long>((long)h.gx * h.gy * h.gz, 0x7fffffffL);
-  if (a.k_slabs > 0) o.slabs = slab_plan(a.M, a.k_slabs).live;
+  o.rc = r.rc; o.tile = r.tile; o.sk_first = r.sk_first; o.xcd = r.sched == GEMM_XCD; o.stages = r.stages;
+  o.half_occ = r.half; o.edge = r.edge; o.epi = r.epi; o.sumsq_entries = r.sumsq_entries; o.slabs = r.slabs;
+  o.pair = d2 && r.rc == 0;
+  o.blocks = (int)std::min<long>(blocks >= 0 ? blocks : (long)r.gx * r.gy * r.gz, 0x7fffffffL);
   return 0;
 }
 
@@ -92,10 +76,10 @@ template <typename R>
 int64_t plan(const gpfit_dev_gemm_args& d, int kind, int32_t* out, int64_t cap) {
   GemmArgsT<R> a;
   if (fill(d, a) != 0 || a.M <= 0 || a.N <= 0) return -3;
-  if (a.epi && !gemm_epilogue_ok(a)) return -3;
-  const int sched = gemm_schedule(a);
+  const GemmRoute r = gemm_route(a);
+  if (r.rc != 0) return -3;
   if (kind == 1) {
-    if (sched != 1) return -1;
+    if (r.sched != GEMM_XCD) return -1;
     std::vector<int> table;
     if (xcd_plan_host(a, table) != 0) return -1;
     const int64_t need = 1 + (int64_t)table.size();
@@ -107,7 +91,6 @@ int64_t plan(const gpfit_dev_gemm_args& d, int kind, int32_t* out, int64_t cap) 
   if (kind == 3) {
     // the slab plan of the triangular-operand route: the items in launch order with their k ranges
     if (a.k_slabs <= 0) return -1;
-    if (gemm_plain_args_error(a)) return -3;
     const SlabPlan sp = slab_plan(a.M, a.k_slabs);
     const int64_t need = 4 + 4 * (int64_t)sp.items;
     if (need > cap || !out) return need;
@@ -117,14 +100,16 @@ int64_t plan(const gpfit_dev_gemm_args& d, int kind, int32_t* out, int64_t cap) 
       slab_item(sp, e, ti, z);
       int32_t* w = out + 4 + 4 * e;
       w[0] = ti; w[1] = z;
-      w[2] = std::max(ti, z * sp.ks) * SLAB_TILE;
-      w[3] = std::min((z + 1) * sp.ks, sp.nt) * SLAB_TILE;
+      // as the kernel: the tile's k range (the same for every tile column), clipped to the slab
+      const KRange kr = gemm_tile_k_range(a.a_tri, a.b_tri, a.K, ti * SLAB_TILE, 0, SLAB_TILE);
+      w[2] = std::max(kr.beg, z * sp.ks * SLAB_TILE);
+      w[3] = std::min(kr.end, (z + 1) * sp.ks * SLAB_TILE);
     }
     return need;
   }
   if (kind != 2) return -3;
-  if (sched != 2) return -1;
-  const int first = streamk_first_tile(a);
+  if (r.sched != GEMM_STREAMK) return -1;
+  const int first = r.sk_first;
   SkHostPlan p;
   if (streamk_plan_host(a, first, p) != 0) return -1;
   const int64_t nt = (int64_t)p.tiles.size(), nfix = (int64_t)p.fix_tile.size(), nslot = (int64_t)p.fix_slot.size();
@@ -148,7 +133,7 @@ int run(hipStream_t s, const gpfit_dev_gemm_args& d, const gpfit_dev_gemm_args* 
     set_error("gpfit_dev_gemm: a pointer batch needs its pointer arrays");
     return -3;
   }
-  return d2 ? launch_gemm_pair(a, b, s) : launch_gemm(a, s);
+  return d2 ? launch_gemm_pair(a, b, gemm_pair_shape(a, b), s) : launch_gemm(a, s);
 }
 
 // a work buffer of the context by name, with its size in bytes

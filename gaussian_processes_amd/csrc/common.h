@@ -73,23 +73,22 @@ struct GemmArgsT {
   int tile;                  // 0 = choose (128 / 64 / 32), else forced block tile
   int reverse;               // tile walk (gemm_walk_tile, gemm_core.h): bit 0 backwards, bit 1 column-major, bit 2 k
                              // downwards, bit 3 ask for the XCD-aware table
-  int workspace;             // stream-K partial-tile workspace to use (0 main stream, 1 side stream)
-  void* sk_ws;               // caller-owned stream-K workspace (>= SK_WS_BYTES); nullptr: process-wide one
-  int tile_limit;            // >0: launch only the first tile_limit tiles of the walk (stream-K head)
   int half_occ;              // 1: pad the launch with unused dynamic LDS so that only ONE workgroup of it fits on
                              // a CU: a long GEMM off the critical path then leaves half of every CU (79 KiB
                              // of LDS, 320 VGPRs) to the latency-bound kernels of the critical chain instead
                              // of holding every workgroup slot of the chip for its whole duration
-  const int* sched;          // device tile table of an XCD-aware schedule (gemm_sched.hip), or nullptr
-  int sched_blocks;          // its length = the grid size
+  void* sk_ws;               // caller-owned stream-K workspace (>= SK_WS_BYTES); nullptr: process-wide one
+  int reserved;              // unused, always 0: keeps the fields a kernel reads behind it at their offsets
+  const int* sched;          // device tile table of an XCD-aware schedule (gemm_sched.hip), or nullptr: set by
+                             // launch_gemm_xcd, callers leave it null (the table's length is the route's grid)
   // Fused epilogues of the data-parallel launches (gemm.hip; a launch that takes the stream-K schedule cannot
-  // honour them -- ask gemm_epilogue_ok() first).  Bit mask:
+  // honour them -- gemm_route().epi says what a launch carries).  Bit mask:
   //   1  mirror: square lower output, every stored element below the diagonal is also stored transposed
   //      (replaces a symmetrisation pass over the matrix)
   //   2  tile norms: sum of squares of the stored values of 128-tile (ti, tj) in sumsq[ti (ti + 1) / 2 + tj] (lower
   //      output) or sumsq[ti tiles_n + tj] (full output)
   //      (128-tile launches only; replaces a pass over the matrix; on the stream-K schedule split
-  //      tiles leave theirs per fix-up band behind the per-tile table: gemm_sumsq_entries)
+  //      tiles leave theirs per fix-up band behind the per-tile table: GemmRoute::sumsq_entries)
   //   4  dual update: with D = aux (same leading dimension as C), C = alpha op(A) op(B) + D and then
   //      aux = C + D (beta is ignored; replaces a copy and an axpby pass)
   int epi;
@@ -157,43 +156,52 @@ constexpr size_t SK_WS_BYTES = (size_t)2 * 512 * TILE * TILE * sizeof(double);  
 
 template <typename R> constexpr int ktile_of() { return 128 / (int)sizeof(R); }
 
-template <typename R> int launch_gemm(const GemmArgsT<R>& a, hipStream_t s);
-template <typename R> int gemm_pick_tile(const GemmArgsT<R>& a);   // block tile the launcher will use (128 / 64 / 32)
-// stream-K schedule for large 128-tile launches (gemm_streamk.hip): 0 issued, 1 not applicable
-template <typename R> int launch_gemm_streamk(const GemmArgsT<R>& a, hipStream_t s);
-template <typename R> int launch_gemm_plain(const GemmArgsT<R>& a, hipStream_t s);  // data-parallel launch, no stream-K
+// THE decision about a launch: everything launch_gemm settles before it launches.  gemm_route is the only place
+// where a launch's fate is decided; launch_gemm computes it once and executes it, the callers that must know
+// beforehand what a launch will do (fit.hip: will it carry the epilogue, how many norm entries does it leave) and the
+// test hooks (api_dev.hip) read the same struct.
+enum { GEMM_DATA_PARALLEL = 0, GEMM_XCD = 1, GEMM_STREAMK = 2 };
+struct GemmRoute {
+  int rc;                    // 0, or -3: the launch is refused (error says why; only tile is filled in then)
+  const char* error;
+  int sched;                 // GEMM_DATA_PARALLEL, GEMM_XCD (the table of gemm_sched.hip), or GEMM_STREAMK (gemm_streamk.hip)
+                             // -- if its planner accepts: it declines a launch that has a tile with an empty k range
+                             // (or too many k steps), which then runs as stay_data_parallel() says
+  int sk_first;              // stream-K: tiles of the data-parallel head (0: every tile is cut along k); else -1
+  int tile;                  // block tile 128 / 64 / 32; 0: an empty product, nothing is launched
+  int tiles, tiles_n;        // tiles of one problem, tiles per tile row
+  int stages;                // LDS stages of the main loop: 2, or the deep pipeline's 4 (64-tiles) / 8 (32-tiles)
+  int edge;                  // predicated (ragged) instance
+  int half;                  // half-occupancy launch
+  int gx, gy, gz;            // grid of the data-parallel launch: the whole launch, or the head of a stream-K tail (no
+                             // launch when sk_first == 0); XCD-aware table: gx is the table's length, known once
+                             // launch_gemm_xcd has the plan (0 until then).  Pair launch: blockIdx.z = the member
+  int epi;                   // fused epilogue the launch carries (= the one asked for: one it cannot carry is refused)
+  int sumsq_entries;         // epi 2: entries of sumsq the launch writes per problem: one per tile on the data-parallel
+                             // schedules, 33 per tile on stream-K (one per tile + one per fix-up band); the squared
+                             // Frobenius norm is the sum over all of them either way
+  int slabs;                 // k_slabs route: live slabs (0: not that route)
+  // The stream-K planner declined.  sumsq_entries stays at 33 per tile although the data-parallel launch then writes
+  // one per tile: as before this struct existed, a caller that sums the table must not send an epi-2 launch whose
+  // planner declines (lower output with both operands upper triangular); fit.hip's are lower x lower, never declined.
+  void stay_data_parallel() { sched = GEMM_DATA_PARALLEL; sk_first = -1; gx = tiles; }
+};
+template <typename R> GemmRoute gemm_route(const GemmArgsT<R>& a);
+template <typename R> int gemm_pick_tile(const GemmArgsT<R>& a);   // block tile of the route, for callers that have not filled the batch in yet
+template <typename R> int launch_gemm(const GemmArgsT<R>& a, const GemmRoute& r, hipStream_t s);   // r = gemm_route(a)
+template <typename R> int launch_gemm(const GemmArgsT<R>& a, hipStream_t s) { return launch_gemm(a, gemm_route(a), s); }
+// The executors of a route (launch_gemm calls them).  stream-K (gemm_streamk.hip): 0 issued, 1 the planner declined.
+template <typename R> int launch_gemm_streamk(const GemmArgsT<R>& a, const GemmRoute& r, hipStream_t s);
+template <typename R> int launch_gemm_xcd(const GemmArgsT<R>& a, GemmRoute r, hipStream_t s);          // gemm_sched.hip
+template <typename R> int launch_gemm_plain(const GemmArgsT<R>& a, const GemmRoute& r, hipStream_t s);   // the route's grid and instance
 // Two independent pointer-batched products as ONE launch (blockIdx.z picks the problem): small-tile products of the
 // latency-bound levels of the recursion that depend on the same predecessor but differ in structure (lower output or
-// not, operand layout, alpha / beta), so they cannot share a pointer batch.  gemm_pair_ok: both are plain pointer
-// batches on full 32-tiles with a row-major op(A); the launch then runs exactly the tile bodies the two separate
-// launches would have run (same bits).
-template <typename R> bool gemm_pair_ok(const GemmArgsT<R>& a, const GemmArgsT<R>& b);
-template <typename R> int launch_gemm_pair(const GemmArgsT<R>& a, const GemmArgsT<R>& b, hipStream_t s);
-// XCD-aware data-parallel schedule (gemm_sched.hip): 0 issued, 1 not applicable.  Walk bit 3 asks for it.
-template <typename R> int launch_gemm_xcd(const GemmArgsT<R>& a, hipStream_t s);
-// would launch_gemm run these arguments on a data-parallel schedule (plain or XCD-aware), i.e. honour a.epi?
-template <typename R> bool gemm_epilogue_ok(const GemmArgsT<R>& a);
-template <typename R> bool gemm_streamk_applies(const GemmArgsT<R>& a);   // gemm_streamk.hip
-template <typename R> bool gemm_streamk_carries(const GemmArgsT<R>& a);   // gemm_streamk.hip: it would also honour a.epi
-// entries of a.sumsq an epi-2 launch of these arguments writes (0: the launch cannot carry the epilogue): nt =
-// tiles of the (lower or full) output on the data-parallel schedules (one per tile), 33 nt on the stream-K schedule (one per
-// tile + one per fix-up band); the squared Frobenius norm is the sum over all of them either way
-template <typename R> int gemm_sumsq_entries(const GemmArgsT<R>& a);
-template <typename R> bool gemm_xcd_applies(const GemmArgsT<R>& a);       // gemm_sched.hip
-// What the launcher decides before it launches, for the test hooks (api_dev.hip) as much as for itself:
-// the schedule launch_gemm gives a launch (0 data-parallel, 1 XCD-aware table, 2 stream-K) and the grid / instance
-// of a data-parallel launch (launch_gemm_plain, launch_gemm_pair).
-struct GemmShape {
-  int tile, tiles, tiles_n;  // block tile, tiles of one problem, tiles per tile row
-  int gx, gy, gz;            // grid
-  int edge;                  // predicated (ragged) instance
-  int stages;                // LDS stages of the main loop: 2, or the deep pipeline's 4 (64-tiles) / 8 (32-tiles)
-  int half;                  // half-occupancy launch
-};
-template <typename R> int gemm_schedule(const GemmArgsT<R>& a);
-template <typename R> const char* gemm_plain_args_error(const GemmArgsT<R>& a);   // nullptr: fine; else launch_gemm_plain's -3
-template <typename R> GemmShape gemm_plain_shape(const GemmArgsT<R>& a);
-template <typename R> GemmShape gemm_pair_shape(const GemmArgsT<R>& a, const GemmArgsT<R>& b);
+// not, operand layout, alpha / beta), so they cannot share a pointer batch.  They can share a launch (rc 0) when both
+// are plain pointer batches on full tiles of the same small size (32 or 64) with a row-major op(A); the launch then
+// runs exactly the tile bodies the two separate launches would have run (same bits).  The route of the shared launch:
+// rc, tile, stages, the grid, tiles = the tiles of both members.
+template <typename R> GemmRoute gemm_pair_shape(const GemmArgsT<R>& a, const GemmArgsT<R>& b);
+template <typename R> int launch_gemm_pair(const GemmArgsT<R>& a, const GemmArgsT<R>& b, const GemmRoute& h, hipStream_t s);   // h = gemm_pair_shape(a, b)
 
 // Arc-cosine Gram matrix from the k-major, zero-padded operands XCt[Kd][ld1], Xt[Kd][ld2]:
 //   G = XCt^T Xt + s0^2 ; c = clip(G/(q1 q2 + 1e-7)) ; K = q1 q2 J(c)

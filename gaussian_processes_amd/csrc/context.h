@@ -96,7 +96,7 @@ struct ProfScope {
   ProfScope(hipStream_t s, double flops, int kind);
   ~ProfScope();
 };
-template <typename R> double gemm_flops(const GemmArgsT<R>& g);
+template <typename R> double gemm_flops(const GemmArgsT<R>& g, int tile);
 
 // Recursive blocked Cholesky of one or several matrices of the same size, factored in lock step
 // (fit.hip:potrf_lockstep): chain b factors A[b] (lower triangle, destroyed) into L[b] with the inverse blocks in
@@ -110,7 +110,6 @@ struct CholBatchT {
   R* Tmp[GEMM_MAXB];
   int* info[GEMM_MAXB];
   int64_t ld = 0;
-  int ws = 0;
   void* sk_ws = nullptr;     // stream-K workspace of the launches issued chain by chain (one stream: shared)
   gpfit_ctx* ctx = nullptr;  // look-ahead resources (this context's side stream), or nullptr: one stream
   int side_min = 0;          // blocks of at least this size put their merge product on the side stream

@@ -8,6 +8,7 @@
 // n_kept x n_kept algebra of the truncated-rank closures, the host assembly of the 16 outputs); what
 // differs between the entry points is which stages they call and what they launch in between.
 #include "context.h"
+#include "gemm_core.h"
 #include "gpfit_mi355x.h"
 
 #include <algorithm>
@@ -95,21 +96,16 @@ ProfScope::~ProfScope() {
   }
 }
 
-// flops actually executed by one GEMM launch (whole 128-tiles over each tile's k range)
+// flops actually executed by one GEMM launch on T-tiles (the route's tile; whole tiles over each tile's k range)
 template <typename R>
-double gemm_flops(const GemmArgsT<R>& g) {
-  const int T = gemm_pick_tile(g);
+double gemm_flops(const GemmArgsT<R>& g, int T) {
   const int tm = (g.M + T - 1) / T, tn = (g.N + T - 1) / T, r = TILE / T;
   double steps = 0;
   for (int ti = 0; ti < tm; ++ti)
     for (int tj = 0; tj < tn; ++tj) {
       if (g.out_lower && tj / r > ti / r) continue;
-      int kb = 0, ke = g.K;
-      if (g.a_tri == 1) ke = std::min(ke, ti * T + T);
-      if (g.a_tri == 2) kb = std::max(kb, ti * T);
-      if (g.b_tri == 1) kb = std::max(kb, tj * T);
-      if (g.b_tri == 2) ke = std::min(ke, tj * T + T);
-      if (ke > kb) steps += (ke - kb);
+      const KRange kr = gemm_tile_k_range(g.a_tri, g.b_tri, g.K, ti * T, tj * T, T);
+      if (kr.end > kr.beg) steps += (kr.end - kr.beg);
     }
   return 2.0 * T * T * steps * (g.nptr > 0 ? g.nptr : (g.batch > 0 ? g.batch : 1));
 }
@@ -118,7 +114,7 @@ double gemm_flops(const GemmArgsT<R>& g) {
 template <typename R>
 static GemmArgsT<R> gemm_args(int a_kmajor, int b_kmajor, int M, int N, int K, double alpha, const R* A, int64_t lda,
                               const R* B, int64_t ldb, double beta, R* C, int64_t ldc, int out_lower, int a_tri,
-                              int b_tri, int reverse = 0, int ws = 0, void* sk_ws = nullptr) {
+                              int b_tri, int reverse = 0, void* sk_ws = nullptr) {
   GemmArgsT<R> g{};
   g.A = A; g.B = B; g.C = C;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -126,7 +122,7 @@ static GemmArgsT<R> gemm_args(int a_kmajor, int b_kmajor, int M, int N, int K, d
   g.alpha = alpha; g.beta = beta;
   g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor;
   g.out_lower = out_lower; g.a_tri = a_tri; g.b_tri = b_tri;
-  g.batch = 1; g.split_k = 1; g.reverse = reverse; g.workspace = ws; g.sk_ws = sk_ws ? sk_ws : g_main_sk_ws;
+  g.batch = 1; g.split_k = 1; g.reverse = reverse; g.sk_ws = sk_ws ? sk_ws : g_main_sk_ws;
   return g;
 }
 
@@ -139,22 +135,25 @@ static int gemm_log_eval() {
   return v;
 }
 
+// launch g on its route r = gemm_route(g)
 template <typename R>
-static int run_gemm(hipStream_t s, const GemmArgsT<R>& g) {
+static int run_gemm(hipStream_t s, const GemmArgsT<R>& g, const GemmRoute& r) {
   if (gemm_log_eval() >= 0 && g_eval_count == gemm_log_eval())
     fprintf(stderr, "[gpfit gemm] M %d N %d K %d atri %d btri %d lower %d nb %d tile %d ak %d bk %d epi %d flops %.6e\n", g.M, g.N, g.K,
-            g.a_tri, g.b_tri, g.out_lower, g.nptr > 0 ? g.nptr : 1, gemm_pick_tile(g), g.a_kmajor, g.b_kmajor, g.epi, gemm_flops(g));
+            g.a_tri, g.b_tri, g.out_lower, g.nptr > 0 ? g.nptr : 1, r.tile, g.a_kmajor, g.b_kmajor, g.epi, gemm_flops(g, r.tile));
   // profile kind 0: the 128-tile kernel family (the dominant kernel), 3: the small-tile instances
-  ProfScope ps(s, g_prof ? gemm_flops(g) : 0.0, (g_prof && gemm_pick_tile(g) != TILE) ? 3 : 0);
-  return launch_gemm(g, s);
+  ProfScope ps(s, g_prof ? gemm_flops(g, r.tile) : 0.0, (g_prof && r.tile != TILE) ? 3 : 0);
+  return launch_gemm(g, r, s);
 }
+template <typename R>
+static int run_gemm(hipStream_t s, const GemmArgsT<R>& g) { return run_gemm(s, g, gemm_route(g)); }
 
 template <typename R>
 static int gemm(hipStream_t s, int a_kmajor, int b_kmajor, int M, int N, int K, double alpha, const R* A,
                 int64_t lda, const R* B, int64_t ldb, double beta, R* C, int64_t ldc, int out_lower, int a_tri,
-                int b_tri, int reverse = 0, int ws = 0, void* sk_ws = nullptr) {
+                int b_tri, int reverse = 0, void* sk_ws = nullptr) {
   return run_gemm(s, gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, out_lower, a_tri, b_tri,
-                                  reverse, ws, sk_ws));
+                                  reverse, sk_ws));
 }
 
 // C = alpha op(A) op(B) with the k range cut into `splits` slabs: the shapes of the truncated-rank closures whose
@@ -210,7 +209,7 @@ static int fused_epilogues() {
 template <typename R>
 static int gemm_list(hipStream_t s, int cnt, const R* const* Ap, const R* const* Bp, R* const* Cp, int a_kmajor,
                      int b_kmajor, int M, int N, int K, double alpha, int64_t lda, int64_t ldb, double beta, int64_t ldc,
-                     int out_lower, int a_tri, int b_tri, int reverse = 0, int ws_id = 0, void* sk_ws = nullptr,
+                     int out_lower, int a_tri, int b_tri, int reverse = 0, void* sk_ws = nullptr,
                      int epi = 0, R* const* auxp = nullptr, double* const* sumsqp = nullptr, bool* epi_done = nullptr,
                      int* sumsq_entries = nullptr) {
   if (epi_done) *epi_done = false;
@@ -221,36 +220,28 @@ static int gemm_list(hipStream_t s, int cnt, const R* const* Ap, const R* const*
     return -3;
   }
   GemmArgsT<R> g = gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, Ap[0], lda, Bp[0], ldb, beta, Cp[0], ldc, out_lower,
-                                a_tri, b_tri, reverse, ws_id, sk_ws);
+                                a_tri, b_tri, reverse, sk_ws);
   static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;   // tuning knob: every product on its own
   // epi: fused epilogue wanted (common.h); *epi_done says whether the launches carried it -- all of them or none
-  // (the caller runs the separate passes otherwise)
-  // Large-tile products normally go unit by unit through the ordinary launcher (balanced schedules).  Lists that
-  // carry an epilogue (T and Q of a group) may share ONE data-parallel 128-tile launch instead once there are enough
-  // of them to fill the chip for many rounds (GPFIT_LIST_T128 = smallest such count, 0 = never): no stream-K fix-up,
-  // no partial tiles, and the epilogues (tile norms, mirrored store) ride along -- a single unit's stream-K launch
-  // cannot carry them.
-  static const int list_t128 = getenv("GPFIT_LIST_T128") ? atoi(getenv("GPFIT_LIST_T128")) : 0;
-  static const int list_t128_dim = getenv("GPFIT_LIST_T128_DIM") ? atoi(getenv("GPFIT_LIST_T128_DIM")) : 4096;
-  const bool share_t128 = epi != 0 && list_t128 > 0 && cnt >= list_t128 && M <= list_t128_dim && N <= list_t128_dim;
-  if (cnt == 1 || (gemm_pick_tile(g) == TILE && !share_t128) || no_batch) {
-    bool fused = epi != 0;
-    for (int i = 0; i < cnt && fused; ++i) {
-      g.A = Ap[i]; g.B = Bp[i]; g.C = Cp[i];
-      g.epi = epi; g.aux = auxp ? auxp[i] : nullptr; g.sumsq = sumsqp ? sumsqp[i] : nullptr;
-      fused = gemm_epilogue_ok(g);
-    }
-    for (int i = 0; i < cnt; ++i) {
+  // (the caller runs the separate passes otherwise); *sumsq_entries: what the route of one such launch says
+  if (cnt == 1 || gemm_pick_tile(g) == TILE || no_batch) {
+    auto problem = [&](int i, bool fused) {
       g.A = Ap[i]; g.B = Bp[i]; g.C = Cp[i];
       g.epi = fused ? epi : 0; g.aux = (fused && auxp) ? auxp[i] : nullptr; g.sumsq = (fused && sumsqp) ? sumsqp[i] : nullptr;
-      GP_TRY(run_gemm(s, g));
+    };
+    GemmRoute routes[GEMM_MAXB];
+    bool fused = epi != 0;
+    for (int i = 0; i < cnt && fused; ++i) {
+      problem(i, true);
+      routes[i] = gemm_route(g);
+      fused = routes[i].epi != 0;
+    }
+    for (int i = 0; i < cnt; ++i) {
+      problem(i, fused);
+      GP_TRY(fused ? run_gemm(s, g, routes[i]) : run_gemm(s, g));
     }
     if (epi_done) *epi_done = fused;
-    if (fused && sumsq_entries) {
-      g.A = Ap[0]; g.B = Bp[0]; g.C = Cp[0];
-      g.epi = epi; g.aux = auxp ? auxp[0] : nullptr; g.sumsq = sumsqp ? sumsqp[0] : nullptr;
-      *sumsq_entries = gemm_sumsq_entries(g);
-    }
+    if (fused && sumsq_entries) *sumsq_entries = routes[0].sumsq_entries;
     return 0;
   }
   g.nptr = cnt;
@@ -260,16 +251,20 @@ static int gemm_list(hipStream_t s, int cnt, const R* const* Ap, const R* const*
     g.auxp[i] = auxp ? auxp[i] : nullptr; g.sumsqp[i] = sumsqp ? sumsqp[i] : nullptr;
   }
   g.epi = epi;
-  if (epi && !gemm_epilogue_ok(g)) g.epi = 0;
+  GemmRoute r = gemm_route(g);
+  if (epi && r.epi == 0) {   // the batch cannot carry it: without
+    g.epi = 0;
+    r = gemm_route(g);
+  }
   if (epi_done) *epi_done = g.epi != 0;
-  if (g.epi && sumsq_entries) *sumsq_entries = gemm_sumsq_entries(g);
-  return run_gemm(s, g);
+  if (sumsq_entries) *sumsq_entries = r.sumsq_entries;
+  return run_gemm(s, g, r);
 }
 
 template <typename R>
 static int bgemm(const CholBatchT<R>& B, hipStream_t s, uint32_t mask, int a_kmajor, int b_kmajor, int M, int N, int K,
                  double alpha, R* const* Ab, int64_t offA, R* const* Bb, int64_t offB, double beta, R* const* Cb,
-                 int64_t offC, int out_lower, int a_tri, int b_tri, int reverse, int ws_id, void* sk_ws) {
+                 int64_t offC, int out_lower, int a_tri, int b_tri, int reverse, void* sk_ws) {
   const R* Ap[GEMM_MAXB];
   const R* Bp[GEMM_MAXB];
   R* Cp[GEMM_MAXB];
@@ -280,7 +275,7 @@ static int bgemm(const CholBatchT<R>& B, hipStream_t s, uint32_t mask, int a_kma
       ++cnt;
     }
   return gemm_list<R>(s, cnt, Ap, Bp, Cp, a_kmajor, b_kmajor, M, N, K, alpha, B.ld, B.ld, beta, B.ld, out_lower, a_tri,
-                      b_tri, reverse, ws_id, sk_ws);
+                      b_tri, reverse, sk_ws);
 }
 
 // the pointer batch of the chains in `mask` (as bgemm builds it), for launches that take two batches at once
@@ -289,7 +284,7 @@ static GemmArgsT<R> batch_args(const CholBatchT<R>& B, uint32_t mask, int a_kmaj
                                R* const* Ab, int64_t offA, R* const* Bb, int64_t offB, double beta, R* const* Cb, int64_t offC,
                                int out_lower, int a_tri, int b_tri, int reverse) {
   GemmArgsT<R> g = gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, (const R*)nullptr, B.ld, (const R*)nullptr, B.ld, beta,
-                                (R*)nullptr, B.ld, out_lower, a_tri, b_tri, reverse, B.ws, B.sk_ws);
+                                (R*)nullptr, B.ld, out_lower, a_tri, b_tri, reverse, B.sk_ws);
   int cnt = 0;
   for (int b = 0; b < B.nb; ++b)
     if (mask & (1u << b)) {
@@ -325,7 +320,7 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
   GP_TRY(potrf_lockstep<R>(B, r0, n1, all, s));
   // L21 = A21 * L11^-T       (trsm as a GEMM against the explicit inverse; op(B) = Li11^T is upper)
   GP_TRY(bgemm<R>(B, s, all, 0, 0, n2, n1, n1, 1.0, B.A, off(r1, r0), B.Li, off(r0, r0), 0.0, B.L, off(r1, r0), 0, 0, 2,
-                  walks()[0], B.ws, B.sk_ws));
+                  walks()[0], B.sk_ws));
   // Look-ahead: tmp = L21 * Li11, the first product of the inverse merge, needs nothing from the second half, so it
   // runs on the context's side stream while that half is being factored (its leaves are latency-bound and leave the
   // chip to it).  Possible because the leaf shares a CU with GEMM workgroups.
@@ -345,7 +340,7 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
     GP_HIP(hipEventRecord(fork, s));
     GP_HIP(hipStreamWaitEvent(c->side, fork, 0));
     GP_TRY(bgemm<R>(B, c->side, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp, off(r1, r0), 0, 0,
-                    1, walks()[1], 1, c->sk_ws[1]));
+                    1, walks()[1], c->sk_ws[1]));
     GP_HIP(hipEventRecord(joined, c->side));
   }
   // A22 -= L21 L21^T (syrk, lower tiles only).  On the latency-bound levels the first product of the inverse merge,
@@ -357,27 +352,28 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
                                           1, 0, 0, 0);
     const GemmArgsT<R> g3 = batch_args<R>(B, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp,
                                           off(r1, r0), 0, 0, 1, walks()[1]);
-    if (!no_batch && gemm_pair_ok(g2, g3)) {
+    const GemmRoute pr = no_batch ? GemmRoute{} : gemm_pair_shape(g2, g3);
+    if (!no_batch && pr.rc == 0) {
       if (gemm_log_eval() >= 0 && g_eval_count == gemm_log_eval())
         fprintf(stderr, "[gpfit gemm] pair: M %d N %d K %d lower 1 nb %d + M %d N %d K %d btri 1 nb %d tile %d flops %.6e\n", g2.M, g2.N,
-                g2.K, g2.nptr, g3.M, g3.N, g3.K, g3.nptr, gemm_pick_tile(g3), gemm_flops(g2) + gemm_flops(g3));
-      ProfScope ps(s, g_prof ? gemm_flops(g2) + gemm_flops(g3) : 0.0, 3);
-      GP_TRY(launch_gemm_pair(g2, g3, s));
+                g2.K, g2.nptr, g3.M, g3.N, g3.K, g3.nptr, pr.tile, gemm_flops(g2, pr.tile) + gemm_flops(g3, pr.tile));
+      ProfScope ps(s, g_prof ? gemm_flops(g2, pr.tile) + gemm_flops(g3, pr.tile) : 0.0, 3);
+      GP_TRY(launch_gemm_pair(g2, g3, pr, s));
       merged = true;
     }
   }
   if (!merged)
     GP_TRY(bgemm<R>(B, s, all, 0, 0, n2, n2, n1, -1.0, B.L, off(r1, r0), B.L, off(r1, r0), 1.0, B.A, off(r1, r1), 1, 0, 0, 0,
-                    B.ws, B.sk_ws));
+                    B.sk_ws));
   GP_TRY(potrf_lockstep<R>(B, r1, n2, need | halves, s));
   if (need) {
     // Li21 = -Li22 * (L21 * Li11)
     if (joined) GP_HIP(hipStreamWaitEvent(s, joined, 0));
     else if (!merged)
       GP_TRY(bgemm<R>(B, s, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp, off(r1, r0), 0, 0,
-                      1, walks()[1], B.ws, B.sk_ws));
+                      1, walks()[1], B.sk_ws));
     GP_TRY(bgemm<R>(B, s, need, 0, 1, n2, n1, n2, -1.0, B.Li, off(r1, r1), B.Tmp, off(r1, r0), 0.0, B.Li, off(r1, r0), 0, 1, 0,
-                    walks()[2], B.ws, B.sk_ws));
+                    walks()[2], B.sk_ws));
   }
   return 0;
 }
@@ -406,15 +402,15 @@ static int dual_update_list(hipStream_t s, int cnt, const R* const* Ap, const R*
   // would the fused launch be possible?  (asked first: the unfused route must copy Z into H beforehand)
   bool fused = false;
   if (fused_epilogues() & 4) {
-    GemmArgsT<R> g = gemm_args<R>(0, 1, M, N, K, alpha, Ap[0], ld, Bp[0], ld, 0.0, Hp[0], ld, 0, 0, b_tri, walk, 0, sk_ws);
+    GemmArgsT<R> g = gemm_args<R>(0, 1, M, N, K, alpha, Ap[0], ld, Bp[0], ld, 0.0, Hp[0], ld, 0, 0, b_tri, walk, sk_ws);
     g.epi = 4; g.aux = Zp[0];
     static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;
     if (cnt > 1 && gemm_pick_tile(g) != TILE && !no_batch) { g.nptr = cnt; g.batch = cnt; }
-    fused = gemm_epilogue_ok(g);
+    fused = gemm_route(g).epi != 0;
   }
   if (fused) {
     bool done = false;
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 0.0, ld, 0, 0, b_tri, walk, 0, sk_ws, 4, Zp, nullptr, &done));
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 0.0, ld, 0, 0, b_tri, walk, sk_ws, 4, Zp, nullptr, &done));
     if (!done) {
       set_error("two_sided: the dual-update epilogue was announced but not carried");
       return -100;
@@ -424,7 +420,7 @@ static int dual_update_list(hipStream_t s, int cnt, const R* const* Ap, const R*
   for (int i = 0; i < cnt; ++i)
     GP_HIP(hipMemcpy2DAsync(Hp[i], (size_t)ld * sizeof(R), Zp[i], (size_t)ld * sizeof(R), (size_t)N * sizeof(R), (size_t)M,
                             hipMemcpyDeviceToDevice, s));
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 1.0, ld, 0, 0, b_tri, walk, 0, sk_ws));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 1.0, ld, 0, 0, b_tri, walk, sk_ws));
   for (int i = 0; i < cnt; ++i) GP_TRY(launch_axpby_block<R>(Zp[i], ld, Hp[i], ld, M, N, 1.0, 1.0, s));
   return 0;
 }
@@ -446,9 +442,9 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
   if (n < b[0].min_split || k < 2) {
     static const int wbase_walk = getenv("GPFIT_WBASE_WALK") ? atoi(getenv("GPFIT_WBASE_WALK")) : 0;
     for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Q, r0[i], r0[i]); Bp[i] = at(b[i].Li, r0[i], r0[i]); Cp[i] = at(b[i].Z, r0[i], r0[i]); }
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n, n, n, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[5], 0, b[0].sk_ws));
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n, n, n, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[5], b[0].sk_ws));
     for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Li, r0[i], r0[i]); Bp[i] = at(b[i].Z, r0[i], r0[i]); Cp[i] = at(b[i].W, r0[i], r0[i]); }
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n, n, n, 0.5, ld, ld, 0.0, ld, 1, 2, 0, wbase_walk, 0, b[0].sk_ws));
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n, n, n, 0.5, ld, ld, 0.0, ld, 1, 2, 0, wbase_walk, b[0].sk_ws));
     return 0;
   }
   const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;
@@ -472,7 +468,7 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
     const int r1 = r0[i] + n1;
     Ap[i] = at(b[i].Q, r1, r1); Bp[i] = at(b[i].Li, r1, r0[i]); Cp[i] = at(b[i].Z, r1, r0[i]);
   }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 0, 0, 0, 0, b[0].sk_ws));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 0, 0, 0, b[0].sk_ws));
   // H = Q21 A + Z21 ;  Z21 = H + 1/2 Q22 B
   {
     R* Hp[GEMM_MAXB];
@@ -489,19 +485,19 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
     const int r1 = r0[i] + n1;
     Ap[i] = at(b[i].Li, r1, r1); Bp[i] = at(b[i].Z, r1, r0[i]); Cp[i] = at(b[i].W, r1, r0[i]);
   }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, 0, b[0].sk_ws));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, b[0].sk_ws));
   GP_TRY(diagonal_blocks());
   // W11 += 1/2 (B^T H + H^T B)   (lower tiles)
   for (int i = 0; i < cnt; ++i) {
     const int r1 = r0[i] + n1;
     Ap[i] = at(b[i].Li, r1, r0[i]); Bp[i] = at(b[i].H, r1, r0[i]); Cp[i] = at(b[i].W, r0[i], r0[i]);
   }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, b[0].sk_ws));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, b[0].sk_ws));
   for (int i = 0; i < cnt; ++i) {
     const int r1 = r0[i] + n1;
     Ap[i] = at(b[i].H, r1, r0[i]); Bp[i] = at(b[i].Li, r1, r0[i]);
   }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, b[0].sk_ws));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, b[0].sk_ws));
   return 0;
 }
 
@@ -551,18 +547,18 @@ static int two_sided_top(int cnt, const TwoSidedBufs<R>* b, const R* const* Lf, 
   // Z21 = 1/2 C^T Q21
   static const int w21_walk = getenv("GPFIT_W21_WALK") ? atoi(getenv("GPFIT_W21_WALK")) : 0;
   for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Li, n1, n1); Bp[i] = at(b[i].Q, n1, 0); Cp[i] = at(b[i].Z, n1, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, 0, sk));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, sk));
   // H = -W22 L21 + Z21 ;  Z21 = J = H + Z21
   for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].W, n1, n1); Bp[i] = at(Lf[i], n1, 0); Cp[i] = at(b[i].H, n1, 0); Zp[i] = at(b[i].Z, n1, 0); }
   GP_TRY(dual_update_list<R>(s, cnt, Ap, Bp, Cp, Zp, n2, n1, n2, -1.0, ld, 0, 0, sk));
   // W21 = H A
   for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].H, n1, 0); Bp[i] = at(b[i].Li, 0, 0); Cp[i] = at(b[i].W, n1, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[6], 0, sk));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[6], sk));
   // M = Q11 - L21^T J - J^T L21   (lower tiles, then both triangles: the block products below read M in full)
   for (int i = 0; i < cnt; ++i) { Ap[i] = at(Lf[i], n1, 0); Bp[i] = at(b[i].Z, n1, 0); Cp[i] = at(b[i].Q, 0, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, sk));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, sk));
   for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Z, n1, 0); Bp[i] = at(Lf[i], n1, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, 0, sk));
+  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, sk));
   for (int i = 0; i < cnt; ++i) GP_TRY(launch_symmetrize(Cp[i], ld, n1, s));
   for (int i = 0; i < cnt; ++i) rr[i] = 0;
   return two_sided_list<R>(cnt, b, rr, n1, s);
@@ -774,11 +770,12 @@ static int xty(gpfit_ctx* c, hipStream_t s, const R* Xa, const R* Yb, int np, in
   g.M = dp; g.N = dp; g.K = np;
   g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
   g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
+  const GemmRoute r = gemm_route(g);
   if (prof) {
-    ProfScope ps(s, g_prof ? gemm_flops(g) : 0.0, (g_prof && gemm_pick_tile(g) != TILE) ? 3 : 0);
-    GP_TRY(launch_gemm(g, s));
+    ProfScope ps(s, g_prof ? gemm_flops(g, r.tile) : 0.0, (g_prof && r.tile != TILE) ? 3 : 0);
+    GP_TRY(launch_gemm(g, r, s));
   } else {
-    GP_TRY(launch_gemm(g, s));
+    GP_TRY(launch_gemm(g, r, s));
   }
   if (sym) return launch_reduce_slices_sym(ws_as<R>(c->Mpart), (int64_t)dp * dp, c->split_k_M, out, dp, s);
   return launch_reduce_slices(ws_as<R>(c->Mpart), (int64_t)dp * dp, c->split_k_M, out, (int64_t)dp * dp, s);
@@ -843,7 +840,7 @@ static int projected_factor(gpfit_ctx* c, hipStream_t s, const double* V_b, int6
   cb.nb = 2;
   cb.A[0] = S1; cb.L[0] = S2; cb.Li[0] = S3; cb.Tmp[0] = S4; cb.info[0] = c->info + 0;
   cb.A[1] = Va; cb.L[1] = Vl; cb.Li[1] = Vli; cb.Tmp[1] = Vt; cb.info[1] = c->info + 1;
-  cb.ld = lb; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
+  cb.ld = lb; cb.sk_ws = c->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
   GP_TRY(potrf_lockstep<double>(cb, 0, nb, 1u, s));
   GP_TRY(launch_logdet(Vl, lb, nk, c->scal + 40, s));
   GP_TRY(launch_logdet(S2, lb, nk, c->scal + 3, s));
@@ -975,9 +972,9 @@ static int t_in_blocks(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int 
   // blocks whose launch cannot carry the norm get a pass of their own -- unless no launch of the unit carries it
   // (all on small tiles): then ONE pass over T's lower tiles, which are exactly the tiles of the three blocks
   auto asks = [&](int M, int Nn, int K, int lower, int a_tri, int b_tri, int walk) {
-    GemmArgsT<R> g1 = gemm_args<R>(0, 1, M, Nn, K, 1.0, a[0].Li, ld, a[0].LV, ld, 0.0, a[0].T, ld, lower, a_tri, b_tri, walk, 0, cs[0]->sk_ws[0]);
+    GemmArgsT<R> g1 = gemm_args<R>(0, 1, M, Nn, K, 1.0, a[0].Li, ld, a[0].LV, ld, 0.0, a[0].T, ld, lower, a_tri, b_tri, walk, cs[0]->sk_ws[0]);
     g1.epi = 2; g1.sumsq = cs[0]->frob_part;
-    return ((fused_epilogues() & 2) && gemm_pick_tile(g1) == TILE) ? gemm_sumsq_entries(g1) : 0;
+    return (fused_epilogues() & 2) ? gemm_route(g1).sumsq_entries : 0;
   };
   const bool any_fused = asks(n1, n1, n1, 1, 1, 1, walks()[3]) > 0 || asks(n2, n2, n2, 1, 1, 1, walks()[3]) > 0 ||
                          asks(n2, n1, n2, 0, 1, 0, walks()[2]) > 0;
@@ -994,7 +991,7 @@ static int t_in_blocks(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int 
         Ap[m] = a[i].Li + o; Bp[m] = a[i].LV + o; Tp[m] = a[i].T + o; Sp[m] = cs[i]->frob_part + ent + j * e;
       }
     bool normed = false;
-    GP_TRY(gemm_list<R>(s, m, Ap, Bp, Tp, 0, 1, nblk, nblk, nblk, 1.0, ld, ld, 0.0, ld, 1, 1, 1, walks()[3], 0, cs[0]->sk_ws[0],
+    GP_TRY(gemm_list<R>(s, m, Ap, Bp, Tp, 0, 1, nblk, nblk, nblk, 1.0, ld, ld, 0.0, ld, 1, 1, 1, walks()[3], cs[0]->sk_ws[0],
                         ask ? 2 : 0, nullptr, Sp, &normed));
     if (normed != ask) {
       set_error("post_join: the tile-norm epilogue of a diagonal block of T was announced but not carried");
@@ -1018,7 +1015,7 @@ static int t_in_blocks(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int 
                               (size_t)n2, hipMemcpyDeviceToDevice, s));
       Ap[i] = a[i].L + o21; Bp[i] = a[i].T; Cp[i] = a[i].Z + o21;
     }
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, -1.0, ld, ld, 1.0, ld, 0, 0, 1, walks()[1], 0, cs[0]->sk_ws[0]));
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, -1.0, ld, ld, 1.0, ld, 0, 0, 1, walks()[1], cs[0]->sk_ws[0]));
     int e = asks(n2, n1, n2, 0, 1, 0, walks()[2]);
     const bool ask = e > 0;
     if (!ask) e = (n2 / TILE) * (n1 / TILE);
@@ -1026,7 +1023,7 @@ static int t_in_blocks(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int 
       Ap[i] = a[i].Li + o21 + n1; Bp[i] = a[i].Z + o21; Tp[i] = a[i].T + o21; Sp[i] = cs[i]->frob_part + ent;
     }
     bool normed = false;
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Tp, 0, 1, n2, n1, n2, 1.0, ld, ld, 0.0, ld, 0, 1, 0, walks()[2], 0, cs[0]->sk_ws[0],
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Tp, 0, 1, n2, n1, n2, 1.0, ld, ld, 0.0, ld, 0, 1, 0, walks()[2], cs[0]->sk_ws[0],
                         ask ? 2 : 0, nullptr, Sp, &normed));
     if (normed != ask) {
       set_error("post_join: the tile-norm epilogue of T21 was announced but not carried");
@@ -1065,7 +1062,7 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
     bool normed = false;
     int norm_entries = 0;
     // the tiles leave their sums of squares behind (no separate pass over T) where the launch can carry the epilogue
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, np, np, np, 1.0, ld, ld, 0.0, ld, 1, 1, 1, walks()[3], 0, cs[0]->sk_ws[0],
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, np, np, np, 1.0, ld, ld, 0.0, ld, 1, 1, 1, walks()[3], cs[0]->sk_ws[0],
                         (fused_epilogues() & 2) ? 2 : 0, nullptr, Sp, &normed, &norm_entries));
     for (int i = 0; i < cnt; ++i) {
       if (normed) GP_TRY(launch_frob_finish(cs[i]->frob_part, norm_entries, cs[i]->scal + 5, s));
@@ -1087,7 +1084,7 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
     // stream-K 3.2)
     for (int i = 0; i < cnt; ++i) { Ap[i] = a[i].T; Bp[i] = a[i].T; Cp[i] = a[i].W; }
     bool mirrored = false;
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 0, np, np, np, -1.0, ld, ld, 0.0, ld, 1, 1, 2, walks()[4], 0, cs[0]->sk_ws[0],
+    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 0, np, np, np, -1.0, ld, ld, 0.0, ld, 1, 1, 2, walks()[4], cs[0]->sk_ws[0],
                         (fused_epilogues() & 1) ? 1 : 0, nullptr, nullptr, &mirrored));
     for (int i = 0; i < cnt; ++i) {
       GP_TRY(launch_add_diag(a[i].W, ld, np, 1.0, s));
@@ -1225,7 +1222,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
     cb.nb = reuse_V ? 1 : 2;
     cb.A[0] = RP(c->Kbuf); cb.L[0] = RP(c->Lbuf); cb.Li[0] = RP(c->Libuf); cb.Tmp[0] = RP(c->Tmp); cb.info[0] = c->info + 0;
     cb.A[1] = RP(c->Vbuf); cb.L[1] = RP(c->LVbuf); cb.Li[1] = RP(c->LiVbuf); cb.Tmp[1] = RP(c->TmpV); cb.info[1] = c->info + 1;
-    cb.ld = ld; cb.ws = 0; cb.sk_ws = c->sk_ws[0]; cb.ctx = c; cb.side_min = side_min;
+    cb.ld = ld; cb.sk_ws = c->sk_ws[0]; cb.ctx = c; cb.side_min = side_min;
     if (!reuse_V) GP_HIP(hipStreamWaitEvent(s, c->ev_join, 0));   // V is packed
     // (K~'s chain in block form: the inverses of the two diagonal halves only -- everything behind substitutes with
     // L21, and the top-level look-ahead on the side stream disappears with the merge)
@@ -1377,7 +1374,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
       b = cb.nb++;
       cb.A[b] = RP(c->Vbuf); cb.L[b] = RP(c->LVbuf); cb.Li[b] = RP(c->LiVbuf); cb.Tmp[b] = RP(c->TmpV); cb.info[b] = c->info + 1;
     }
-    cb.ld = ld; cb.ws = 0; cb.sk_ws = c0->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
+    cb.ld = ld; cb.sk_ws = c0->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
     if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, s, kchains));
     else GP_TRY(potrf_lockstep<R>(cb, 0, np, kchains, s));
   }

@@ -56,11 +56,8 @@ __device__ __forceinline__ bool gemm_tile_compute(const GemmArgsT<R>& p, int til
     C = p.C + (int64_t)b * p.sC;
   }
 
-  int kbeg = 0, kend = p.K;
-  if (p.a_tri == 1) kend = min(kend, row0 + T);
-  if (p.a_tri == 2) kbeg = max(kbeg, row0);
-  if (p.b_tri == 1) kbeg = max(kbeg, col0);
-  if (p.b_tri == 2) kend = min(kend, col0 + T);
+  const KRange kr = gemm_tile_k_range(p.a_tri, p.b_tri, p.K, row0, col0, T);
+  int kbeg = kr.beg, kend = kr.end;
   // tri bounds are multiples of T >= 32 = the largest K step, so they stay K-step aligned
   if (slabbed) {
     kbeg = max(kbeg, slab * slab_tiles * T);
@@ -239,48 +236,123 @@ static void allow_dynamic_lds(const void* fn) {
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, HALF_OCC_LDS);
 }
 
-// Grid and instance of a data-parallel launch on T-tiles (batch already normalised: launch_gemm_plain).
-template <typename R, int T>
-static GemmShape plain_shape_T(const GemmArgsT<R>& p) {
-  GemmShape h{};
-  h.tile = T;
-  h.tiles_n = (p.N + T - 1) / T;
-  const int tm = (p.M + T - 1) / T;
-  h.tiles = p.out_lower ? lower_tile_count((p.M + TILE - 1) / TILE, TILE / T) : tm * h.tiles_n;
-  h.edge = (p.M % T) || (p.N % T) || (p.out_lower && (p.M % TILE));
-  h.gx = p.sched ? p.sched_blocks : (p.tile_limit > 0 ? std::min(p.tile_limit, h.tiles) : h.tiles);
-  if (p.k_slabs > 0) h.gx = slab_plan(p.M, p.k_slabs).items * h.tiles_n;
-  h.gy = p.batch;
-  h.gz = p.split_k > 1 ? p.split_k : 1;
-  constexpr int DEEP = (T == 128) ? 2 : (T == 64 ? 4 : 8);
+// Stages of a launch of `blocks` workgroups on full T-tiles: the deep pipeline (4 at T = 64, 8 at T = 32) when the
+// launch has at most two workgroups per CU, i.e. when nothing else hides the load latency.
+static int gemm_stages(int T, bool edge, long blocks) {
   static const int deep_max = getenv("GPFIT_DEEP_MAX") ? atoi(getenv("GPFIT_DEEP_MAX")) : 512;  // tuning knob
-  const bool deep = DEEP > 2 && !h.edge && (long)h.gx * h.gy * h.gz <= deep_max;
-  h.stages = deep ? DEEP : 2;
-  // half-occupancy launches (T = 128 only): 64 KiB static + 17 KiB of unused dynamic LDS = 81 KiB > 160 / 2
-  h.half = (T == TILE) && p.half_occ && !deep;
-  return h;
+  return (T == TILE || edge || blocks > deep_max) ? 2 : (T == 64 ? 4 : 8);
 }
 
+// Stream-K (gemm_streamk.hip) for one problem of `ntiles` whole 128-tiles; two uses:
+//  * operands triangular on both sides (k range of a tile ~ distance from the diagonal): pure
+//    stream-K over all tiles (+8 % on L^-1 L_V, T T^T, L^-T R);
+//  * uniform k range whose tile count leaves a short last round (2080 = 4 x 512 + 32): the full
+//    rounds stay data-parallel -- workgroups that start together walk k in lock step and share
+//    operand panels in L2, which stream-K's staggered shares give up -- and only the tail tiles
+//    are cut along k over the whole chip.
+// Returns the number of leading tiles that stay data-parallel (tails of uniform launches); -1: not a stream-K launch.
 template <typename R>
-GemmShape gemm_plain_shape(const GemmArgsT<R>& a) {
-  GemmArgsT<R> p = a;
-  if (p.nptr > 0) p.batch = p.nptr;
-  if (p.batch <= 0) p.batch = 1;
-  switch (gemm_pick_tile(p)) {
-    case 128: return plain_shape_T<R, 128>(p);
-    case 64: return plain_shape_T<R, 64>(p);
-    default: return plain_shape_T<R, 32>(p);
-  }
+static int streamk_first_tile(const GemmArgsT<R>& a, long ntiles) {
+  static const bool disabled = getenv("GPFIT_NO_STREAMK") != nullptr;
+  if (disabled) return -1;
+  static const int sk_min = getenv("GPFIT_SK_MIN_TILES") ? atoi(getenv("GPFIT_SK_MIN_TILES")) : 384;
+  if (ntiles < sk_min || (long)a.K < 1024) return -1;  // small launches: latency-, not balance-bound
+  // classes of launches that take the stream-K schedule (tuning knob, bit mask): 1 operands
+  // triangular on both sides, 2 lower output with an upper-triangular op(A), 4 tails of uniform
+  // launches.  Class 2 is off by default: since the LDS-DMA main loop its data-parallel launch
+  // (heavy rows first) is the faster one (2.86 vs 3.04 ms at N = 8192).
+  static const int sk_classes = getenv("GPFIT_SK_CLASSES") ? atoi(getenv("GPFIT_SK_CLASSES")) : 5;
+  const bool cls1 = (a.a_tri != 0 && a.b_tri != 0), cls2 = (a.out_lower && a.a_tri == 2 && a.b_tri == 0);
+  if ((cls1 && !(sk_classes & 1)) || (cls2 && !(sk_classes & 2))) return -1;
+  if (cls1 || cls2) return 0;
+  if (!(sk_classes & 4)) return -1;
+  if (a.a_tri || a.b_tri) return -1;       // one-sided triangles: the heavy-first walk already balances
+  const int tail = (int)(ntiles % SK_SLOTS);
+  if (tail == 0 || tail >= 384 || ntiles < SK_SLOTS) return -1;
+  return (int)ntiles - tail;
 }
-template GemmShape gemm_plain_shape<double>(const GemmArgsT<double>&);
-template GemmShape gemm_plain_shape<float>(const GemmArgsT<float>&);
+
+// The route of a launch (common.h): refusals, schedule, epilogue, grid and instance -- decided here and nowhere else.
+template <typename R>
+GemmRoute gemm_route(const GemmArgsT<R>& a) {
+  GemmRoute r{};
+  r.sk_first = -1;
+  if (a.M <= 0 || a.N <= 0) return r;
+  const int T = r.tile = gemm_pick_tile(a);
+  auto refuse = [T](const char* why) {
+    GemmRoute e{};
+    e.rc = -3; e.error = why; e.tile = T; e.sk_first = -1;
+    return e;
+  };
+  const bool strided = a.batch > 1 && a.nptr <= 0;
+  r.tiles_n = (a.N + T - 1) / T;
+  r.tiles = a.out_lower ? lower_tile_count((a.M + TILE - 1) / TILE, TILE / T) : ((a.M + T - 1) / T) * r.tiles_n;
+  r.edge = (a.M % T) || (a.N % T) || (a.out_lower && (a.M % TILE));
+
+  // The schedule.  One problem on whole 128-tiles may take a balanced one: the XCD-aware table when the walk asks
+  // for it and there are several rounds of the 512 resident workgroups to balance (below that the stream-K /
+  // heavy-first walks win: N = 4096, 528 tiles, 7.27 vs 7.5 ms per fit), else stream-K where it pays.
+  if (T == TILE && !r.edge && a.nptr <= 0 && a.batch <= 1 && a.split_k <= 1 && !a.half_occ &&
+      (a.tile == 0 || a.tile == TILE)) {
+    static const long xcd_min = getenv("GPFIT_XCD_MIN_TILES") ? atol(getenv("GPFIT_XCD_MIN_TILES")) : 1536;
+    const long tm = a.M / TILE, tn = a.N / TILE, ntiles = a.out_lower ? tm * (tm + 1) / 2 : tm * tn;
+    if ((a.reverse & 8) && !(a.out_lower && a.M != a.N) && tm < 32768 && tn < 32768 && ntiles >= xcd_min) r.sched = GEMM_XCD;
+    else if ((r.sk_first = streamk_first_tile(a, ntiles)) >= 0) r.sched = GEMM_STREAMK;
+  }
+
+  // Fused epilogues: full tiles of one problem or a pointer batch, and the instances that exist (launch_T): 128-tile,
+  // row-major A, and per mode the operand layout the fit uses -- the blocks of T = L^-1 L_V with tile norms (lower or
+  // full output), Q = -T T^T mirrored, H = Q21 A + Z21 / H = -W22 L21 + Z21 with the dual update.
+  // On the stream-K schedule: the tile norms (2) of a square lower output whose tiles ALL take it (T = L^-1 L_V of a
+  // unit below the size where the XCD-aware tables take over).  The mirrored store (1) was built for this schedule
+  // too and taken out again: the transposed stores of an accumulator tile are 32-byte fragments, which cost Q's
+  // launch 50 us and its fix-up 16 at N = 4096 against 28 us for the separate symmetrisation pass (which transposes
+  // through LDS).
+  if (a.epi) {
+    bool ok = a.split_k <= 1 && a.k_slabs <= 0 && !strided && T == TILE && !(a.M % T) && !(a.N % T) && !a.a_kmajor && !a.half_occ;
+    if ((a.epi & 1) && (!a.out_lower || a.M != a.N)) ok = false;
+    if ((a.epi & 4) && a.nptr <= 0 && a.aux == nullptr) ok = false;
+    if (!((a.epi == 2 && a.b_kmajor) || (a.epi == 1 && !a.b_kmajor) || (a.epi == 4 && a.b_kmajor))) ok = false;
+    if (r.sched == GEMM_STREAMK && !(r.sk_first == 0 && a.out_lower && a.M == a.N && a.epi == 2 && a.sumsq != nullptr)) ok = false;
+    if (!ok) return refuse("launch_gemm: this launch cannot carry a fused epilogue (gemm_route says so beforehand)");
+  }
+  // odd M/N are fine for the stores; k-major operands are then read up to one 16-byte chunk past
+  // M/N, which internal callers cover with zero padding (the public gpfit_dgemm insists on even).
+  constexpr int EPC = 16 / (int)sizeof(R);
+  if (a.K % ktile_of<R>() != 0 || (a.lda % EPC) || (a.ldb % EPC))
+    return refuse("launch_gemm: K must be a multiple of the K step and lda, ldb multiples of 16 bytes");
+  if (a.out_lower && a.M != a.N) return refuse("launch_gemm: out_lower needs a square output");
+  if (a.nptr > 0 && (a.nptr > GEMM_MAXB || a.sched || a.split_k > 1))
+    return refuse("launch_gemm: a pointer batch holds at most GEMM_MAXB plain problems");
+  if (a.k_slabs > 0 &&
+      (a.a_tri != 2 || a.b_tri || a.out_lower || a.M != a.K || (a.M % SLAB_TILE) || a.split_k > 1 || a.sched ||
+       a.half_occ || strided || (a.tile != 0 && a.tile != SLAB_TILE)))
+    return refuse("launch_gemm: k_slabs needs an upper triangular square op(A) on whole 64-tiles and a plain launch");
+
+  r.epi = a.epi;
+  if (a.epi & 2) r.sumsq_entries = (r.sched == GEMM_STREAMK ? 33 : 1) * r.tiles;
+  // grid and instance of the data-parallel launch
+  r.gx = r.sched == GEMM_XCD ? 0 : (r.sched == GEMM_STREAMK ? r.sk_first : r.tiles);
+  if (a.k_slabs > 0) {
+    const SlabPlan sp = slab_plan(a.M, a.k_slabs);
+    r.gx = sp.items * r.tiles_n;
+    r.slabs = sp.live;
+  }
+  r.gy = a.nptr > 0 ? a.nptr : std::max(a.batch, 1);
+  r.gz = a.split_k > 1 ? a.split_k : 1;
+  r.stages = gemm_stages(T, r.edge, (long)r.gx * r.gy * r.gz);
+  // half-occupancy launches (T = 128 only): 64 KiB static + 17 KiB of unused dynamic LDS = 81 KiB > 160 / 2
+  r.half = T == TILE && a.half_occ;
+  return r;
+}
+template GemmRoute gemm_route<double>(const GemmArgsT<double>&);
+template GemmRoute gemm_route<float>(const GemmArgsT<float>&);
 
 template <typename R, int T>
-static void launch_T(const GemmArgsT<R>& p, hipStream_t s) {
-  const GemmShape h = plain_shape_T<R, T>(p);
-  const int tn = h.tiles_n, tiles = h.tiles;
-  const bool edge = h.edge, deep = h.stages > 2, half = h.half;
-  dim3 grid(h.gx, h.gy, h.gz);
+static void launch_T(const GemmArgsT<R>& p, const GemmRoute& r, hipStream_t s) {
+  const int tn = r.tiles_n, tiles = r.tiles;
+  const bool edge = r.edge, deep = r.stages > 2, half = r.half;
+  dim3 grid(r.gx, r.gy, r.gz);
   dim3 block(GEMM_THREADS);
   constexpr int DEEP = (T == 128) ? 2 : (T == 64 ? 4 : 8);
 #define GP_LAUNCH(AK, BK, ED)                                                                          \
@@ -291,12 +363,10 @@ static void launch_T(const GemmArgsT<R>& p, hipStream_t s) {
       hipLaunchKernelGGL((gemm_mfma_kernel<R, AK, BK, ED, T, 2>), grid, block, HALF_OCC_LDS, s, p, tn, tiles); \
     } else hipLaunchKernelGGL((gemm_mfma_kernel<R, AK, BK, ED, T, 2>), grid, block, 0, s, p, tn, tiles); \
   } while (0)
-  if (p.epi) {
-    // fused epilogues exist for the layouts the fit uses: the blocks of T = L^-1 L_V with tile norms (lower or full
-    // output), Q = -T T^T mirrored, H = Q21 A + Z21 / H = -W22 L21 + Z21 with the dual update (gemm_epilogue_ok has
-    // checked the combination)
+  if (r.epi) {
+    // the instances gemm_route admits
     if constexpr (T == TILE) {
-      const int key = p.epi * 4 + (p.a_kmajor ? 2 : 0) + (p.b_kmajor ? 1 : 0);
+      const int key = r.epi * 4 + (p.a_kmajor ? 2 : 0) + (p.b_kmajor ? 1 : 0);
       if (key == 2 * 4 + 1) hipLaunchKernelGGL((gemm_epi_kernel<R, false, true, 2>), grid, block, 0, s, p, tn, tiles);
       else if (key == 1 * 4 + 0) hipLaunchKernelGGL((gemm_epi_kernel<R, false, false, 1>), grid, block, 0, s, p, tn, tiles);
       else if (key == 4 * 4 + 1) hipLaunchKernelGGL((gemm_epi_kernel<R, false, true, 4>), grid, block, 0, s, p, tn, tiles);
@@ -327,104 +397,29 @@ static void launch_T(const GemmArgsT<R>& p, hipStream_t s) {
 }
 
 template <typename R>
-bool gemm_epilogue_ok(const GemmArgsT<R>& a) {
-  if (a.split_k > 1 || a.k_slabs > 0 || (a.batch > 1 && a.nptr <= 0) || a.M <= 0 || a.N <= 0) return false;
-  const int T = gemm_pick_tile(a);
-  if ((a.M % T) || (a.N % T)) return false;                                    // full tiles only
-  if ((a.epi & 1) && (!a.out_lower || a.M != a.N)) return false;
-  if ((a.epi & 2) && T != TILE) return false;
-  if ((a.epi & 4) && a.nptr <= 0 && a.aux == nullptr) return false;
-  // instances that exist (launch_T): 128-tile, row-major A, and per mode the operand layout the fit uses
-  if (T != TILE || a.a_kmajor || a.half_occ) return false;
-  if (!((a.epi == 2 && a.b_kmajor) || (a.epi == 1 && !a.b_kmajor) || (a.epi == 4 && a.b_kmajor))) return false;
-  if (a.nptr > 0) return true;   // pointer batches are always data-parallel
-  if (T == TILE && a.tile_limit == 0) {
-    if ((a.reverse & 8) && gemm_xcd_applies(a)) return true;
-    if (gemm_streamk_applies(a)) return gemm_streamk_carries(a);
+int launch_gemm(const GemmArgsT<R>& a, const GemmRoute& route, hipStream_t s) {
+  if (route.rc != 0) {
+    set_error(route.error);
+    return route.rc;
   }
-  return true;
+  if (route.tile == 0) return 0;
+  if (route.sched == GEMM_XCD) return launch_gemm_xcd(a, route, s);        // XCD-aware data-parallel schedule (gemm_sched.hip)
+  if (route.sched != GEMM_STREAMK) return launch_gemm_plain(a, route, s);
+  const int rc = launch_gemm_streamk(a, route, s);                        // large launches: balanced schedules (gemm_streamk.hip)
+  if (rc <= 0) return rc;
+  GemmRoute r = route;                                                    // 1: the planner declined
+  r.stay_data_parallel();
+  return launch_gemm_plain(a, r, s);
 }
 
 template <typename R>
-int gemm_sumsq_entries(const GemmArgsT<R>& a) {
-  if (!(a.epi & 2) || !gemm_epilogue_ok(a)) return 0;
-  const int t = a.M / TILE, nt = a.out_lower ? t * (t + 1) / 2 : t * (a.N / TILE);
-  if (a.nptr > 0 || a.half_occ || a.tile_limit != 0 || a.batch > 1) return nt;
-  if ((a.reverse & 8) && gemm_xcd_applies(a)) return nt;
-  return gemm_streamk_applies(a) ? 33 * nt : nt;
-}
-template int gemm_sumsq_entries<double>(const GemmArgsT<double>&);
-template int gemm_sumsq_entries<float>(const GemmArgsT<float>&);
-template bool gemm_epilogue_ok<double>(const GemmArgsT<double>&);
-template bool gemm_epilogue_ok<float>(const GemmArgsT<float>&);
-
-// The schedule launch_gemm gives a launch: 0 data-parallel, 1 XCD-aware table, 2 stream-K (whose planner may still
-// decline a launch with an empty tile, which then stays data-parallel).
-template <typename R>
-int gemm_schedule(const GemmArgsT<R>& a) {
-  if (a.nptr > 0) return 0;   // pointer batches are data-parallel launches
-  if (a.half_occ) return 0;
-  if (a.tile_limit == 0 && gemm_pick_tile(a) == TILE && a.batch <= 1) {
-    if ((a.reverse & 8) && gemm_xcd_applies(a)) return 1;
-    // the fused epilogues other than the one gemm_streamk_carries names live in the data-parallel kernels only
-    if (streamk_first_tile(a) >= 0 && !(a.epi && !gemm_streamk_carries(a))) return 2;
-  }
-  return 0;
-}
-template int gemm_schedule<double>(const GemmArgsT<double>&);
-template int gemm_schedule<float>(const GemmArgsT<float>&);
-
-template <typename R>
-int launch_gemm(const GemmArgsT<R>& a, hipStream_t s) {
-  if (a.M <= 0 || a.N <= 0) return 0;
-  if (a.epi && !gemm_epilogue_ok(a)) {
-    set_error("launch_gemm: this launch cannot carry a fused epilogue (ask gemm_epilogue_ok first)");
-    return -3;
-  }
-  switch (gemm_schedule(a)) {
-    case 1: return launch_gemm_xcd(a, s);        // XCD-aware data-parallel schedule (gemm_sched.hip)
-    case 2: {
-      const int rc = launch_gemm_streamk(a, s);  // large launches: balanced schedules (gemm_streamk.hip)
-      if (rc <= 0) return rc;                    // 1: the planner declined
-    }
-  }
-  return launch_gemm_plain(a, s);
-}
-
-// The argument errors of a data-parallel launch: nullptr, or what is wrong (launch_gemm_plain returns -3 with it).
-template <typename R>
-const char* gemm_plain_args_error(const GemmArgsT<R>& a) {
-  // odd M/N are fine for the stores; k-major operands are then read up to one 16-byte chunk past
-  // M/N, which internal callers cover with zero padding (the public gpfit_dgemm insists on even).
-  constexpr int EPC = 16 / (int)sizeof(R);
-  if (a.K % ktile_of<R>() != 0 || (a.lda % EPC) || (a.ldb % EPC))
-    return "launch_gemm: K must be a multiple of the K step and lda, ldb multiples of 16 bytes";
-  if (a.out_lower && a.M != a.N) return "launch_gemm: out_lower needs a square output";
-  if (a.nptr > 0 && (a.nptr > GEMM_MAXB || a.sched || a.split_k > 1))
-    return "launch_gemm: a pointer batch holds at most GEMM_MAXB plain problems";
-  if (a.k_slabs > 0 &&
-      (a.a_tri != 2 || a.b_tri || a.out_lower || a.M != a.K || (a.M % SLAB_TILE) || a.split_k > 1 || a.sched || a.tile_limit ||
-       a.half_occ || (a.batch > 1 && a.nptr <= 0) || (a.tile != 0 && a.tile != SLAB_TILE)))
-    return "launch_gemm: k_slabs needs an upper triangular square op(A) on whole 64-tiles and a plain launch";
-  return nullptr;
-}
-template const char* gemm_plain_args_error<double>(const GemmArgsT<double>&);
-template const char* gemm_plain_args_error<float>(const GemmArgsT<float>&);
-
-template <typename R>
-int launch_gemm_plain(const GemmArgsT<R>& a, hipStream_t s) {
-  if (a.M <= 0 || a.N <= 0) return 0;
-  if (const char* err = gemm_plain_args_error(a)) {
-    set_error(err);
-    return -3;
-  }
+int launch_gemm_plain(const GemmArgsT<R>& a, const GemmRoute& r, hipStream_t s) {
   GemmArgsT<R> p = a;
-  if (p.nptr > 0) p.batch = p.nptr;
-  if (p.batch <= 0) p.batch = 1;
-  switch (gemm_pick_tile(p)) {
-    case 128: launch_T<R, 128>(p, s); break;
-    case 64: launch_T<R, 64>(p, s); break;
-    default: launch_T<R, 32>(p, s); break;
+  p.batch = r.gy;
+  switch (r.tile) {
+    case 128: launch_T<R, 128>(p, r, s); break;
+    case 64: launch_T<R, 64>(p, r, s); break;
+    default: launch_T<R, 32>(p, r, s); break;
   }
   GP_HIP(hipGetLastError());
   return 0;
@@ -447,76 +442,56 @@ __global__ __launch_bounds__(GEMM_THREADS, (NS > 2 ? 2 : 4)) void gemm_pair_kern
   else gemm_tile_body<R, false, false, false, T, NS>(p, q.tiles_n[w], q.tiles[w], smem);
 }
 
-// the block tile both members would take on their own (32 or 64), 0: not a member of a pair
+// the route a member would take on its own, if that is a plain pointer batch on full 32- or 64-tiles (else tile 0)
 template <typename R>
-static int pair_member_tile(const GemmArgsT<R>& a) {
-  constexpr int EPC = 16 / (int)sizeof(R);
-  if (a.nptr <= 0 || a.nptr > GEMM_MAXB || a.epi || a.split_k > 1 || a.k_slabs > 0 || a.sched || a.half_occ || a.tile_limit || a.a_kmajor) return 0;
-  if (a.M <= 0 || a.N <= 0 || (a.M % 64) || (a.N % 64) || (a.out_lower && ((a.M % TILE) || a.M != a.N))) return 0;
-  if (a.K % ktile_of<R>() != 0 || (a.lda % EPC) || (a.ldb % EPC)) return 0;
-  const int T = gemm_pick_tile(a);
-  return (T == 32 || T == 64) ? T : 0;
+static GemmRoute pair_member_route(const GemmArgsT<R>& a) {
+  const GemmRoute none{};
+  if (a.nptr <= 0 || a.epi || a.k_slabs > 0 || a.half_occ || a.a_kmajor || (a.M % 64) || (a.N % 64)) return none;
+  const GemmRoute r = gemm_route(a);
+  return (r.rc == 0 && !r.edge && (r.tile == 32 || r.tile == 64)) ? r : none;
 }
 
-// stages as launch_T picks them: the deep pipeline when the launch has at most two workgroups per CU
-static bool pair_deep(long total_tiles) {
-  static const int deep_max = getenv("GPFIT_DEEP_MAX") ? atoi(getenv("GPFIT_DEEP_MAX")) : 512;
-  return total_tiles <= deep_max;
-}
 template <typename R>
-static long pair_total_tiles(const GemmArgsT<R>& p, int T) {
-  return (long)(p.out_lower ? lower_tile_count(p.M / TILE, TILE / T) : (p.M / T) * (p.N / T)) * p.nptr;
-}
-
-// tile and stages of the shared launch (tile 0: the two cannot share one)
-template <typename R>
-GemmShape gemm_pair_shape(const GemmArgsT<R>& a, const GemmArgsT<R>& b) {
-  GemmShape h{};
-  if (!gemm_pair_ok(a, b)) return h;
-  h.tile = pair_member_tile(a);
-  const long total = pair_total_tiles(a, h.tile) + pair_total_tiles(b, h.tile);
-  h.tiles = (int)total;
-  h.stages = pair_deep(total) ? (h.tile == 32 ? 8 : 4) : 2;
-  return h;
-}
-template GemmShape gemm_pair_shape<double>(const GemmArgsT<double>&, const GemmArgsT<double>&);
-template GemmShape gemm_pair_shape<float>(const GemmArgsT<float>&, const GemmArgsT<float>&);
-
-template <typename R>
-bool gemm_pair_ok(const GemmArgsT<R>& a, const GemmArgsT<R>& b) {
+GemmRoute gemm_pair_shape(const GemmArgsT<R>& a, const GemmArgsT<R>& b) {
   static const bool off = getenv("GPFIT_NO_PAIR") != nullptr;   // tuning knob: the two launches on their own
   static const bool no64 = getenv("GPFIT_NO_PAIR64") != nullptr;
-  if (off) return false;
-  const int ta = pair_member_tile(a), tb = pair_member_tile(b);
-  return ta != 0 && ta == tb && !(no64 && ta == 64);
+  GemmRoute h{};
+  h.sk_first = -1;
+  const GemmRoute ra = pair_member_route(a), rb = pair_member_route(b);
+  if (off || ra.tile == 0 || ra.tile != rb.tile || (no64 && ra.tile == 64)) {
+    h.rc = -3;
+    h.error = "launch_gemm_pair: the two problems cannot share a launch (gemm_pair_shape says so beforehand)";
+    return h;
+  }
+  h.tile = ra.tile;
+  h.tiles = ra.tiles * ra.gy + rb.tiles * rb.gy;
+  h.stages = gemm_stages(h.tile, false, h.tiles);
+  h.gx = std::max(ra.tiles, rb.tiles);
+  h.gy = std::max(ra.gy, rb.gy);
+  h.gz = 2;
+  return h;
 }
-template bool gemm_pair_ok<double>(const GemmArgsT<double>&, const GemmArgsT<double>&);
-template bool gemm_pair_ok<float>(const GemmArgsT<float>&, const GemmArgsT<float>&);
+template GemmRoute gemm_pair_shape<double>(const GemmArgsT<double>&, const GemmArgsT<double>&);
+template GemmRoute gemm_pair_shape<float>(const GemmArgsT<float>&, const GemmArgsT<float>&);
 
 template <typename R>
-int launch_gemm_pair(const GemmArgsT<R>& a, const GemmArgsT<R>& b, hipStream_t s) {
-  if (!gemm_pair_ok(a, b)) {
-    set_error("launch_gemm_pair: the two problems cannot share a launch (ask gemm_pair_ok first)");
-    return -3;
+int launch_gemm_pair(const GemmArgsT<R>& a, const GemmArgsT<R>& b, const GemmRoute& h, hipStream_t s) {
+  if (h.rc != 0) {
+    set_error(h.error);
+    return h.rc;
   }
   static_assert(sizeof(GemmPairT<R>) <= 4096, "kernel arguments are limited to 4 KiB");
-  const int T = pair_member_tile(a);
+  const int T = h.tile;
   GemmPairT<R> q;
-  int gx = 0, gy = 0;
-  long total = 0;
   for (int w = 0; w < 2; ++w) {
     q.g[w] = w == 0 ? a : b;
     GemmArgsT<R>& p = q.g[w];
     p.batch = p.nptr;
-    const int tm = p.M / T, tn = p.N / T;
-    q.tiles_n[w] = tn;
-    q.tiles[w] = p.out_lower ? lower_tile_count(p.M / TILE, TILE / T) : tm * tn;
-    gx = std::max(gx, q.tiles[w]);
-    gy = std::max(gy, p.batch);
-    total += pair_total_tiles(p, T);
+    q.tiles_n[w] = p.N / T;
+    q.tiles[w] = p.out_lower ? lower_tile_count(p.M / TILE, TILE / T) : (p.M / T) * (p.N / T);
   }
-  const dim3 grid(gx, gy, 2), block(GEMM_THREADS);
-  const bool deep = pair_deep(total);
+  const dim3 grid(h.gx, h.gy, h.gz), block(GEMM_THREADS);
+  const bool deep = h.stages > 2;
   if (T == 32 && deep) hipLaunchKernelGGL((gemm_pair_kernel<R, 32, 8>), grid, block, 0, s, q);
   else if (T == 32) hipLaunchKernelGGL((gemm_pair_kernel<R, 32, 2>), grid, block, 0, s, q);
   else if (deep) hipLaunchKernelGGL((gemm_pair_kernel<R, 64, 4>), grid, block, 0, s, q);
@@ -524,13 +499,13 @@ int launch_gemm_pair(const GemmArgsT<R>& a, const GemmArgsT<R>& b, hipStream_t s
   GP_HIP(hipGetLastError());
   return 0;
 }
-template int launch_gemm_pair<double>(const GemmArgsT<double>&, const GemmArgsT<double>&, hipStream_t);
-template int launch_gemm_pair<float>(const GemmArgsT<float>&, const GemmArgsT<float>&, hipStream_t);
+template int launch_gemm_pair<double>(const GemmArgsT<double>&, const GemmArgsT<double>&, const GemmRoute&, hipStream_t);
+template int launch_gemm_pair<float>(const GemmArgsT<float>&, const GemmArgsT<float>&, const GemmRoute&, hipStream_t);
 
-template int launch_gemm<double>(const GemmArgsT<double>&, hipStream_t);
-template int launch_gemm<float>(const GemmArgsT<float>&, hipStream_t);
-template int launch_gemm_plain<double>(const GemmArgsT<double>&, hipStream_t);
-template int launch_gemm_plain<float>(const GemmArgsT<float>&, hipStream_t);
+template int launch_gemm<double>(const GemmArgsT<double>&, const GemmRoute&, hipStream_t);
+template int launch_gemm<float>(const GemmArgsT<float>&, const GemmRoute&, hipStream_t);
+template int launch_gemm_plain<double>(const GemmArgsT<double>&, const GemmRoute&, hipStream_t);
+template int launch_gemm_plain<float>(const GemmArgsT<float>&, const GemmRoute&, hipStream_t);
 template int gemm_pick_tile<double>(const GemmArgsT<double>&);
 template int gemm_pick_tile<float>(const GemmArgsT<float>&);
 

@@ -436,8 +436,23 @@ __host__ __device__ __forceinline__ void gemm_walk_tile(int b, int walk, bool lo
   }
 }
 
+// THE k range of a tile: op(A) op(B) of the T x T tile at (row0, col0) sums k over [beg, end) -- all of [0, K) for
+// dense operands; a lower triangular op(A) (a_tri 1) has nothing right of the tile's last row, an upper triangular
+// one (2) nothing left of its first; op(B) likewise by the tile's columns (b_tri 1 lower: from the first column on,
+// 2 upper: up to the last).  end <= beg: the tile is zero.  Kernels, planners and the flop count all ask here.
+struct KRange { int beg, end; };
+__host__ __device__ __forceinline__ KRange gemm_tile_k_range(int a_tri, int b_tri, int K, int row0, int col0, int T) {
+  int kbeg = 0, kend = K;
+  if (a_tri == 1) kend = kend < row0 + T ? kend : row0 + T;
+  if (a_tri == 2) kbeg = kbeg > row0 ? kbeg : row0;
+  if (b_tri == 1) kbeg = kbeg > col0 ? kbeg : col0;
+  if (b_tri == 2) kend = kend < col0 + T ? kend : col0 + T;
+  return {kbeg, kend};
+}
+
 // ---- host-side plans of the balanced schedules (no GPU call; the launchers upload them, the test hooks of
 // api_dev.hip hand them out)
+constexpr int SK_SLOTS = 512;  // workgroups of the stream-K kernel resident at a time: 256 CUs x 2 (189 VGPRs, 64 KiB LDS each)
 struct SkTile {
   int row0, col0, kbeg, ksteps;
   int prefix;  // k-steps of all tiles before this one in walk order (< 2^31: 4096 tiles x 512 steps)
@@ -449,9 +464,7 @@ struct SkHostPlan {
   std::vector<int> fix_ptr;    // CSR offsets into fix_slot
   std::vector<int> fix_slot;   // workspace slots in accumulation order
 };
-// first: number of leading tiles that stay data-parallel (tails of uniform launches); -1: not a stream-K launch
-template <typename R> int streamk_first_tile(const GemmArgsT<R>& a);
-// 0 planned, 1 the planner declines (a tile with an empty k range): the launch stays data-parallel
+// first = GemmRoute::sk_first.  0 planned, 1 the planner declines (a tile with an empty k range): the launch stays data-parallel
 template <typename R> int streamk_plan_host(const GemmArgsT<R>& a, int first, SkHostPlan& plan);
 // the XCD-aware tile table (gemm_sched.hip): entry = ti << 16 | tj, -1 padding; its length is the grid size
 template <typename R> int xcd_plan_host(const GemmArgsT<R>& a, std::vector<int>& table);

@@ -43,11 +43,8 @@ int xcd_plan_host(const GemmArgsT<R>& a, std::vector<int>& table) {
   constexpr int KT = 128 / (int)sizeof(R);
   const int tm = a.M / TILE, tn = a.N / TILE;
   auto ksteps = [&](int ti, int tj) {
-    int kb = 0, ke = a.K;
-    if (a.a_tri == 1) ke = std::min(ke, ti * TILE + TILE);
-    if (a.a_tri == 2) kb = std::max(kb, ti * TILE);
-    if (a.b_tri == 1) kb = std::max(kb, tj * TILE);
-    if (a.b_tri == 2) ke = std::min(ke, tj * TILE + TILE);
+    const KRange kr = gemm_tile_k_range(a.a_tri, a.b_tri, a.K, ti * TILE, tj * TILE, TILE);
+    const int kb = kr.beg, ke = kr.end;
     return std::max(0, ke - kb) / KT;
   };
   // tuning knobs: macro-tile rows x columns, and the weight (as a fraction 1/cutdiv of a queue's
@@ -119,23 +116,9 @@ static int build(const GemmArgsT<R>& a, Plan& plan) {
   return 0;
 }
 
+// Executes an XCD route (gemm_route): the data-parallel launch of the route with the table's length as its grid.
 template <typename R>
-bool gemm_xcd_applies(const GemmArgsT<R>& a) {
-  if ((a.M % TILE) || (a.N % TILE) || a.split_k > 1 || a.batch > 1 || a.nptr > 0 || (a.tile && a.tile != TILE)) return false;
-  if (a.out_lower && a.M != a.N) return false;
-  const long tm = a.M / TILE, tn = a.N / TILE;
-  if (tm >= 32768 || tn >= 32768) return false;
-  // A data-parallel schedule needs several rounds of the 512 resident workgroups to balance; below
-  // that the stream-K / heavy-first walks win (N = 4096: 528 tiles, 7.27 vs 7.5 ms per fit).
-  static const long min_tiles = getenv("GPFIT_XCD_MIN_TILES") ? atol(getenv("GPFIT_XCD_MIN_TILES")) : 1536;
-  return (a.out_lower ? tm * (tm + 1) / 2 : tm * tn) >= min_tiles;
-}
-template bool gemm_xcd_applies<double>(const GemmArgsT<double>&);
-template bool gemm_xcd_applies<float>(const GemmArgsT<float>&);
-
-template <typename R>
-int launch_gemm_xcd(const GemmArgsT<R>& a, hipStream_t s) {
-  if (!gemm_xcd_applies(a)) return 1;
+int launch_gemm_xcd(const GemmArgsT<R>& a, GemmRoute r, hipStream_t s) {
   int device = 0;
   GP_HIP(hipGetDevice(&device));
   Plan plan;
@@ -152,14 +135,13 @@ int launch_gemm_xcd(const GemmArgsT<R>& a, hipStream_t s) {
     plan = it->second;
   }
   GemmArgsT<R> p = a;
-  p.tile = TILE;
   p.sched = plan.table;
-  p.sched_blocks = plan.blocks;
+  r.gx = plan.blocks;
   p.reverse &= 4;  // the table fixes the tile walk; only the k direction bit survives
-  return launch_gemm_plain(p, s);
+  return launch_gemm_plain(p, r, s);
 }
 
-template int launch_gemm_xcd<double>(const GemmArgsT<double>&, hipStream_t);
-template int launch_gemm_xcd<float>(const GemmArgsT<float>&, hipStream_t);
+template int launch_gemm_xcd<double>(const GemmArgsT<double>&, GemmRoute, hipStream_t);
+template int launch_gemm_xcd<float>(const GemmArgsT<float>&, GemmRoute, hipStream_t);
 
 }  // namespace gpfit

@@ -56,8 +56,6 @@ struct SkParams {
   int nt_all;
 };
 
-constexpr int SK_SLOTS = 512;  // resident workgroups: 256 CUs x 2 (189 VGPRs, 64 KiB LDS each)
-
 // one segment of a tile's k range (its own function so that the kernel's epilogue variants share ONE call site of the
 // main loop: the host pass of the compiler rejects a second instantiation context of the same main-loop specialisation)
 template <typename R, bool A_KMAJOR, bool B_KMAJOR>
@@ -220,11 +218,8 @@ int streamk_plan_host(const GemmArgsT<R>& a, int first, SkHostPlan& plan) {
   for (int b = first; b < all_tiles; ++b) {
     int ti, tj;
     gemm_walk_tile(b, a.reverse, a.out_lower != 0, 1, tn, all_tiles, ti, tj);
-    int kb = 0, ke = a.K;
-    if (a.a_tri == 1) ke = std::min(ke, ti * TILE + TILE);
-    if (a.a_tri == 2) kb = std::max(kb, ti * TILE);
-    if (a.b_tri == 1) kb = std::max(kb, tj * TILE);
-    if (a.b_tri == 2) ke = std::min(ke, tj * TILE + TILE);
+    const KRange kr = gemm_tile_k_range(a.a_tri, a.b_tri, a.K, ti * TILE, tj * TILE, TILE);
+    const int kb = kr.beg, ke = kr.end;
     const int ks = std::max(0, ke - kb) / KT;
     if (ks == 0) return 1;  // empty tiles would need a beta-only pass: leave those launches to gemm.hip
     tiles.push_back(SkTile{ti * TILE, tj * TILE, kb, ks, (int)prefix});
@@ -291,71 +286,12 @@ static int build_plan(const GemmArgsT<R>& a, int first, SkPlan& plan) {
   return 0;
 }
 
-// Returns 0 when the launch was issued here, 1 when the caller should use the plain
-// data-parallel launch, < 0 on error.  Two uses:
-//  * operands triangular on both sides (k range of a tile ~ distance from the diagonal): pure
-//    stream-K over all tiles (+8 % on L^-1 L_V, T T^T, L^-T R);
-//  * uniform k range whose tile count leaves a short last round (2080 = 4 x 512 + 32): the full
-//    rounds stay data-parallel -- workgroups that start together walk k in lock step and share
-//    operand panels in L2, which stream-K's staggered shares give up -- and only the tail tiles
-//    are cut along k over the whole chip.
-// first: number of leading tiles that stay data-parallel (tails of uniform launches); -1: not a stream-K launch
+// Executes a stream-K route (gemm_route: r.sk_first leading tiles stay data-parallel, the rest -- every tile when it is
+// 0 -- is cut along k).  Returns 0 when the launch was issued here, 1 when the planner declines and the caller should
+// use the plain data-parallel launch, < 0 on error.
 template <typename R>
-int streamk_first_tile(const GemmArgsT<R>& a) {
-  static const bool disabled = getenv("GPFIT_NO_STREAMK") != nullptr;
-  if (disabled) return -1;
-  if ((a.M % TILE) || (a.N % TILE) || a.split_k > 1 || a.batch > 1 || a.nptr > 0 || (a.tile && a.tile != TILE)) return -1;
-  const long tm = a.M / TILE, tn = a.N / TILE;
-  const int ntiles = (int)(a.out_lower ? tm * (tm + 1) / 2 : tm * tn);
-  static const int sk_min = getenv("GPFIT_SK_MIN_TILES") ? atoi(getenv("GPFIT_SK_MIN_TILES")) : 384;
-  static const int sk_all = getenv("GPFIT_SK_ALL") ? 1 : 0;  // experiment: stream-K for every eligible launch
-  if (ntiles < sk_min || (long)a.K < 1024) return -1;  // small launches: latency-, not balance-bound
-  int first = 0;
-  // classes of launches that take the stream-K schedule (tuning knob, bit mask): 1 operands
-  // triangular on both sides, 2 lower output with an upper-triangular op(A), 4 tails of uniform
-  // launches.  Class 2 is off by default: since the LDS-DMA main loop its data-parallel launch
-  // (heavy rows first) is the faster one (2.86 vs 3.04 ms at N = 8192).
-  static const int sk_classes = getenv("GPFIT_SK_CLASSES") ? atoi(getenv("GPFIT_SK_CLASSES")) : 5;
-  const bool cls1 = (a.a_tri != 0 && a.b_tri != 0), cls2 = (a.out_lower && a.a_tri == 2 && a.b_tri == 0);
-  if ((cls1 && !(sk_classes & 1)) || (cls2 && !(sk_classes & 2))) return -1;
-  const bool both_tri = cls1 || cls2;
-  if (!both_tri && !(sk_classes & 4)) return -1;
-  if (!both_tri && !(sk_all && ntiles < SK_SLOTS)) {
-    if (a.a_tri || a.b_tri) return -1;       // one-sided triangles: the heavy-first walk already balances
-    const int tail = ntiles % SK_SLOTS;
-    if (tail == 0 || tail >= 384 || ntiles < SK_SLOTS) return -1;
-    first = ntiles - tail;
-  }
-  return first;
-}
-
-template int streamk_first_tile<double>(const GemmArgsT<double>&);
-template int streamk_first_tile<float>(const GemmArgsT<float>&);
-
-template <typename R>
-bool gemm_streamk_applies(const GemmArgsT<R>& a) { return streamk_first_tile(a) >= 0; }
-template bool gemm_streamk_applies<double>(const GemmArgsT<double>&);
-template bool gemm_streamk_applies<float>(const GemmArgsT<float>&);
-
-// Fused epilogue on the stream-K schedule: the tile norms (2) of a square lower output whose tiles ALL take the
-// stream-K schedule (T = L^-1 L_V of a unit below the size where the XCD-aware tables take over).  The mirrored
-// store (1) was built for this schedule too and taken out again: the transposed stores of an accumulator tile are
-// 32-byte fragments, which cost Q's launch 50 us and its fix-up 16 at N = 4096 against 28 us for the separate
-// symmetrisation pass (which transposes through LDS).
-template <typename R>
-bool gemm_streamk_carries(const GemmArgsT<R>& a) {
-  if (streamk_first_tile(a) != 0) return false;
-  if (!a.out_lower || a.M != a.N || a.a_kmajor) return false;
-  return a.epi == 2 && a.b_kmajor && a.sumsq != nullptr;
-}
-template bool gemm_streamk_carries<double>(const GemmArgsT<double>&);
-template bool gemm_streamk_carries<float>(const GemmArgsT<float>&);
-
-template <typename R>
-int launch_gemm_streamk(const GemmArgsT<R>& a, hipStream_t s) {
-  const int first = streamk_first_tile(a);
-  if (first < 0) return 1;
-  if (a.epi && !gemm_streamk_carries(a)) return 1;   // the other fused epilogues live in the data-parallel kernels only
+int launch_gemm_streamk(const GemmArgsT<R>& a, const GemmRoute& r, hipStream_t s) {
+  const int first = r.sk_first;
   int device = 0;
   GP_HIP(hipGetDevice(&device));
   SkPlan plan;
@@ -377,13 +313,7 @@ int launch_gemm_streamk(const GemmArgsT<R>& a, hipStream_t s) {
       fallback_ws = w;
     }
   }
-  if (first > 0) {  // the full rounds, data-parallel
-    GemmArgsT<R> head = a;
-    head.tile = TILE;
-    head.tile_limit = first;
-    const int rc = launch_gemm_plain(head, s);
-    if (rc != 0) return rc;
-  }
+  if (first > 0) GP_TRY(launch_gemm_plain(a, r, s));  // the full rounds, data-parallel: the route's grid
   SkParams<R> p{};
   p.A = a.A; p.B = a.B; p.C = a.C; p.lda = a.lda; p.ldb = a.ldb; p.ldc = a.ldc; p.M = a.M; p.N = a.N;
   p.alpha = a.alpha; p.beta = a.beta; p.tiles = plan.tiles; p.ntiles = plan.ntiles; p.total = plan.total;
@@ -391,31 +321,27 @@ int launch_gemm_streamk(const GemmArgsT<R>& a, hipStream_t s) {
   p.sumsq = a.sumsq; p.nt_all = (a.M / TILE) * (a.M / TILE + 1) / 2;
   dim3 grid(plan.blocks), block(GEMM_THREADS);
   const int sel = (a.a_kmajor ? 2 : 0) | (a.b_kmajor ? 1 : 0);
-  if (a.epi == 0) switch (sel) {
+  if (r.epi == 0) switch (sel) {
     case 0: hipLaunchKernelGGL((gemm_streamk_kernel<R, false, false>), grid, block, 0, s, p); break;
     case 1: hipLaunchKernelGGL((gemm_streamk_kernel<R, false, true>), grid, block, 0, s, p); break;
     case 2: hipLaunchKernelGGL((gemm_streamk_kernel<R, true, false>), grid, block, 0, s, p); break;
     case 3: hipLaunchKernelGGL((gemm_streamk_kernel<R, true, true>), grid, block, 0, s, p); break;
   }
-  if (a.epi == 0) {
+  if (r.epi == 0) {
     if (plan.nfix)
       hipLaunchKernelGGL(streamk_fixup_kernel<R>, dim3(plan.nfix, 32), dim3(256), 0, s, p, plan.fix_tile, plan.fix_ptr,
                          plan.fix_slot);
-    GP_HIP(hipGetLastError());
-    return 0;
-  }
-  if (a.epi == 2) {
+  } else {  // the tile norms: the one epilogue the route lets this schedule carry
     hipLaunchKernelGGL((gemm_streamk_kernel<R, false, true, 2>), grid, block, 0, s, p);
     if (plan.nfix)
       hipLaunchKernelGGL((streamk_fixup_kernel<R, 2>), dim3(plan.nfix, 32), dim3(256), 0, s, p, plan.fix_tile, plan.fix_ptr,
                          plan.fix_slot);
-    GP_HIP(hipGetLastError());
-    return 0;
   }
-  return 1;
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
-template int launch_gemm_streamk<double>(const GemmArgsT<double>&, hipStream_t);
-template int launch_gemm_streamk<float>(const GemmArgsT<float>&, hipStream_t);
+template int launch_gemm_streamk<double>(const GemmArgsT<double>&, const GemmRoute&, hipStream_t);
+template int launch_gemm_streamk<float>(const GemmArgsT<float>&, const GemmRoute&, hipStream_t);
 
 }  // namespace gpfit

@@ -267,7 +267,7 @@ print("VAL", repr(float(o["tr_KinvV"])), repr(float(o["loss"])), " ".join(repr(f
 
 def test_tile_norms_on_the_stream_k_schedule_match_the_separate_pass():
     """tr(K~^-1 V) = ||T||_F^2 at a size where T = L^-1 L_V takes the stream-K schedule: the tile norms left behind
-    by the launch and its fix-up kernel (33 table entries per tile, gemm_sumsq_entries) against the separate pass over
+    by the launch and its fix-up kernel (33 table entries per tile, GemmRoute::sumsq_entries) against the separate pass over
     T (GPFIT_FUSED_EPI=0) -- two processes, the switch is read once.  Same T, two summation orders of N^2 / 2 squares."""
     vals = []
     for extra in ({}, {"GPFIT_FUSED_EPI": "0"}):
