@@ -2,21 +2,12 @@
 // functions: localker (C, dC), acosker (K and the six dK, square / rectangular / diagonal).
 // The fused fit path (fit.hip) never materialises dK; these exist so that the drop-in module
 // can serve notebooks that call utils.acosker / utils.localker directly.
-#include "context.h"
+#include "product.h"
 #include "gpfit_mi355x.h"
 
 #include <cmath>
 
 using namespace gpfit;
-
-static int gemm_kk(hipStream_t s, int M, int N, int K, const double* A, int64_t lda, const double* B, int64_t ldb,
-                   double* C, int64_t ldc) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K; g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
-  g.batch = 1; g.split_k = 1;
-  return launch_gemm(g, s);
-}
 
 extern "C" {
 
@@ -57,6 +48,7 @@ int gpfit_acosker(gpfit_ctx* c, void* stream, double sigma0, const double* x1, i
   }
   GP_CTX_ENTER(c, "gpfit_acosker");
   hipStream_t s = (hipStream_t)stream;
+  const Lane lane{s, nullptr};   // the process-wide stream-K workspace, as ever
   const int dp = (int)round_up(d, 32), np1 = (int)round_up(n1, TILE), np2 = (int)round_up(n2, TILE);
   if (dp > c->dp_cap || np1 > c->np_cap || np2 > c->np_cap) {
     set_error("gpfit_acosker: problem larger than the context capacity");
@@ -67,13 +59,13 @@ int gpfit_acosker(gpfit_ctx* c, void* stream, double sigma0, const double* x1, i
   const double s0sq = sigma0 * sigma0;
   GP_TRY(launch_pad_copy(C, ldC, (int)d, (int)d, c->Cmat, dp, dp, dp, s));
   GP_TRY(launch_gather<double>(x1, ld1, (int)n1, nullptr, (int)d, dp, np1, c->Xt, np1, nullptr, 0, s));
-  GP_TRY(gemm_kk(s, dp, np1, dp, c->Cmat, dp, c->Xt, np1, c->XCt, np1));
+  GP_TRY(product(lane, {dp, np1, dp}, 1.0, trans(mat(c->Cmat, dp)), plain(mat(c->Xt, np1)), into(mat(c->XCt, np1))));
   GP_TRY(launch_qvec(c->Xt, c->XCt, np1, dp, (int)n1, np1, s0sq, c->Kvec, c->q, s));
   const double* Xt2 = c->Xt;
   const double* q2 = c->q;
   if (!same) {
     GP_TRY(launch_gather<double>(x2, ld2, (int)n2, nullptr, (int)d, dp, np2, c->Xt2, np2, nullptr, 0, s));
-    GP_TRY(gemm_kk(s, dp, np2, dp, c->Cmat, dp, c->Xt2, np2, c->XCt2, np2));
+    GP_TRY(product(lane, {dp, np2, dp}, 1.0, trans(mat(c->Cmat, dp)), plain(mat(c->Xt2, np2)), into(mat(c->XCt2, np2))));
     GP_TRY(launch_qvec(c->Xt2, c->XCt2, np2, dp, (int)n2, np2, s0sq, c->hvec, c->q2, s));
     Xt2 = c->Xt2;
     q2 = c->q2;
@@ -98,16 +90,16 @@ int gpfit_acosker(gpfit_ctx* c, void* stream, double sigma0, const double* x1, i
       for (int p = 0; p < 5; ++p) {
         double* out = dK + (int64_t)kDcToTheta[p] * nn;
         GP_TRY(launch_pad_copy(dC + (int64_t)p * d * d, d, (int)d, (int)d, c->dCpad, dp, dp, dp, s));
-        GP_TRY(gemm_kk(s, dp, np1, dp, c->dCpad, dp, c->Xt, np1, c->XDt, np1));
+        GP_TRY(product(lane, {dp, np1, dp}, 1.0, trans(mat(c->dCpad, dp)), plain(mat(c->Xt, np1)), into(mat(c->XDt, np1))));
         GP_TRY(launch_dq(c->Xt, c->XDt, np1, dp, (int)n1, c->q, c->dq1, nullptr, s));
         const double* dq2 = c->dq1;
         if (!same) {
-          GP_TRY(gemm_kk(s, dp, np2, dp, c->dCpad, dp, c->Xt2, np2, c->XDt2, np2));
+          GP_TRY(product(lane, {dp, np2, dp}, 1.0, trans(mat(c->dCpad, dp)), plain(mat(c->Xt2, np2)), into(mat(c->XDt2, np2))));
           GP_TRY(launch_dq(c->Xt2, c->XDt2, np2, dp, (int)n2, q2, c->dq2, nullptr, s));
           dq2 = c->dq2;
         }
         // H = x1 dC_p x2^T straight into the caller's dK_p, then the element-wise chain in place
-        GP_TRY(gemm_kk(s, (int)n1, (int)n2, dp, c->XDt, np1, Xt2, np2, out, n2));
+        GP_TRY(product(lane, {(int)n1, (int)n2, dp}, 1.0, trans(mat(c->XDt, np1)), plain(mat(Xt2, np2)), into(mat(out, n2))));
         GP_TRY(launch_dk_metric(out, n2, c->Cos, np2, c->q, q2, c->dq1, dq2, (int)n1, (int)n2, s));
       }
     }
@@ -125,6 +117,7 @@ int gpfit_acosker_pullback(gpfit_ctx* c, void* stream, double sigma0, const doub
   }
   GP_CTX_ENTER(c, "gpfit_acosker_pullback");
   hipStream_t s = (hipStream_t)stream;
+  const Lane lane{s, nullptr};   // the process-wide stream-K workspace, as ever
   const int dp = (int)round_up(d, 32), np1 = (int)round_up(n1, TILE), np2 = (int)round_up(n2, TILE);
   if (dp > c->dp_cap || np1 > c->np_cap || np2 > c->np_cap) {
     set_error("gpfit_acosker_pullback: problem larger than the context capacity");
@@ -138,10 +131,10 @@ int gpfit_acosker_pullback(gpfit_ctx* c, void* stream, double sigma0, const doub
   // forward pieces: q1, q2, the cosine matrix
   GP_TRY(launch_pad_copy(C, ldC, (int)d, (int)d, c->Cmat, dp, dp, dp, s));
   GP_TRY(launch_gather<double>(x1, ld1, (int)n1, nullptr, (int)d, dp, np1, c->Xt, np1, X1m, dp, s));
-  GP_TRY(gemm_kk(s, dp, np1, dp, c->Cmat, dp, c->Xt, np1, c->XCt, np1));
+  GP_TRY(product(lane, {dp, np1, dp}, 1.0, trans(mat(c->Cmat, dp)), plain(mat(c->Xt, np1)), into(mat(c->XCt, np1))));
   GP_TRY(launch_qvec(c->Xt, c->XCt, np1, dp, (int)n1, np1, s0sq, c->Kvec, c->q, s));
   GP_TRY(launch_gather<double>(x2, ld2, (int)n2, nullptr, (int)d, dp, np2, c->Xt2, np2, X2m, dp, s));
-  GP_TRY(gemm_kk(s, dp, np2, dp, c->Cmat, dp, c->Xt2, np2, c->XCt2, np2));
+  GP_TRY(product(lane, {dp, np2, dp}, 1.0, trans(mat(c->Cmat, dp)), plain(mat(c->Xt2, np2)), into(mat(c->XCt2, np2))));
   GP_TRY(launch_qvec(c->Xt2, c->XCt2, np2, dp, (int)n2, np2, s0sq, c->hvec, c->q2, s));
   {
     GramArgs g{};
@@ -155,23 +148,16 @@ int gpfit_acosker_pullback(gpfit_ctx* c, void* stream, double sigma0, const doub
   double* t1 = c->tvec;
   double* t2 = c->tvec + c->np_cap;
   GP_TRY(launch_adjoint_rect(W, ldw, c->Cos, np2, c->q, c->q2, (int)n1, (int)n2, np1, np2, c->Abuf, np2, c->upart,
-                             c->vpart, c->rect_part, t1_extra, t1, t2, c->rpad, c->mpad, c->scal + 20, s));
+                             c->vpart, c->rect_part, t1_extra, t1, t2, c->rpad, c->mpad, c->scal + S_RECT, s));
   // M = x1^T (A_w x2 + t1 o x1) + x2^T (t2 o x2)
-  {
-    GemmArgs g{};
-    g.A = c->Abuf; g.B = X2m; g.C = c->Ybuf; g.lda = np2; g.ldb = dp; g.ldc = dp;
-    g.M = np1; g.N = dp; g.K = np2; g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 0; g.b_kmajor = 1; g.batch = 1; g.split_k = 1;
-    GP_TRY(launch_gemm(g, s));
-  }
+  GP_TRY(product(lane, {np1, dp, np2}, 1.0, plain(mat(c->Abuf, np2)), plain(mat(X2m, dp)), into(mat(c->Ybuf, dp))));
   GP_TRY(launch_rowscale_add(c->Ybuf, dp, X1m, dp, t1, np1, dp, s));
   GP_HIP(hipMemsetAsync(Zm, 0, (size_t)np2 * dp * sizeof(double), s));
   GP_TRY(launch_rowscale_add(Zm, dp, X2m, dp, t2, np2, dp, s));
   auto xty = [&](const double* Xa, const double* Yb, int np, double* out) -> int {
-    GemmArgs g{};
-    g.A = Xa; g.B = Yb; g.C = c->Mpart; g.lda = dp; g.ldb = dp; g.ldc = dp;
-    g.M = dp; g.N = dp; g.K = np; g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
-    g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
-    GP_TRY(launch_gemm(g, s));
+    GemmArgs g = product_args(lane, {dp, dp, np}, 1.0, trans(mat(Xa, dp)), plain(mat(Yb, dp)), into(mat(c->Mpart, dp)));
+    g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
+    GP_TRY(run_gemm(s, g));
     return launch_reduce_slices(c->Mpart, (int64_t)dp * dp, c->split_k_M, out, (int64_t)dp * dp, s);
   };
   GP_TRY(xty(X1m, c->Ybuf, np1, c->Mmat));
@@ -181,9 +167,9 @@ int gpfit_acosker_pullback(gpfit_ctx* c, void* stream, double sigma0, const doub
                           (size_t)d * sizeof(double), (size_t)d, hipMemcpyDeviceToDevice, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
-  out_host[0] = c->scal_host[20];
-  out_host[1] = c->scal_host[21];
-  out_host[2] = c->scal_host[22];
+  out_host[0] = c->scal_host[S_RECT];
+  out_host[1] = c->scal_host[S_RECT_U1];
+  out_host[2] = c->scal_host[S_RECT_U2];
   return 0;
 }
 
@@ -195,6 +181,7 @@ int gpfit_acosker_diag(gpfit_ctx* c, void* stream, double sigma0, const double* 
   }
   GP_CTX_ENTER(c, "gpfit_acosker_diag");
   hipStream_t s = (hipStream_t)stream;
+  const Lane lane{s, nullptr};   // the process-wide stream-K workspace, as ever
   const int dp = (int)round_up(d, 32), np1 = (int)round_up(n1, TILE);
   if (dp > c->dp_cap || np1 > c->np_cap) {
     set_error("gpfit_acosker_diag: problem larger than the context capacity");
@@ -203,7 +190,7 @@ int gpfit_acosker_diag(gpfit_ctx* c, void* stream, double sigma0, const double* 
   const double s0sq = sigma0 * sigma0;
   GP_TRY(launch_pad_copy(C, ldC, (int)d, (int)d, c->Cmat, dp, dp, dp, s));
   GP_TRY(launch_gather<double>(x1, ld1, (int)n1, nullptr, (int)d, dp, np1, c->Xt, np1, nullptr, 0, s));
-  GP_TRY(gemm_kk(s, dp, np1, dp, c->Cmat, dp, c->Xt, np1, c->XCt, np1));
+  GP_TRY(product(lane, {dp, np1, dp}, 1.0, trans(mat(c->Cmat, dp)), plain(mat(c->Xt, np1)), into(mat(c->XCt, np1))));
   GP_TRY(launch_qvec(c->Xt, c->XCt, np1, dp, (int)n1, np1, s0sq, c->Kvec, c->q, s));
   GP_HIP(hipMemcpyAsync(Kvec, c->Kvec, (size_t)n1 * sizeof(double), hipMemcpyDeviceToDevice, s));  // utils.py:1029
   if (dKvec) {
@@ -211,7 +198,7 @@ int gpfit_acosker_diag(gpfit_ctx* c, void* stream, double sigma0, const double* 
     if (dC) {
       for (int p = 0; p < 5; ++p) {
         GP_TRY(launch_pad_copy(dC + (int64_t)p * d * d, d, (int)d, (int)d, c->dCpad, dp, dp, dp, s));
-        GP_TRY(gemm_kk(s, dp, np1, dp, c->dCpad, dp, c->Xt, np1, c->XDt, np1));
+        GP_TRY(product(lane, {dp, np1, dp}, 1.0, trans(mat(c->dCpad, dp)), plain(mat(c->Xt, np1)), into(mat(c->XDt, np1))));
         GP_TRY(launch_dq(c->Xt, c->XDt, np1, dp, (int)n1, c->q, nullptr, dKvec + (int64_t)kDcToTheta[p] * n1, s));  // :1042
       }
     }

@@ -1,7 +1,7 @@
 // C-ABI entry points built on the recursive MFMA Cholesky: a standalone factorisation
 // (log_det, general solves of the drop-in module), the fused E-step Newton update and the
 // one-pass firing-rate-parameter evaluation.
-#include "context.h"
+#include "product.h"
 #include "gpfit_mi355x.h"
 
 #include <cmath>
@@ -10,24 +10,13 @@
 
 using namespace gpfit;
 
-static int gemm_full(hipStream_t s, int ak, int bk, int M, int N, int K, double alpha, const double* A, int64_t lda,
-                     const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int lower, int at, int bt,
-                     int walk, void* sk_ws) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.a_kmajor = ak; g.b_kmajor = bk;
-  g.out_lower = lower; g.a_tri = at; g.b_tri = bt; g.batch = 1; g.split_k = 1; g.reverse = walk;
-  g.sk_ws = sk_ws;
-  return launch_gemm(g, s);
-}
-
 // the context's K~ work matrices as a batch of one chain for potrf_lockstep, on the caller's stream only (no
 // look-ahead side stream)
 static CholBatchT<double> one_chain(gpfit_ctx* c, int64_t ld) {
   CholBatchT<double> b;
   b.nb = 1;
-  b.A[0] = c->Kbuf; b.L[0] = c->Lbuf; b.Li[0] = c->Libuf; b.Tmp[0] = c->Tmp; b.info[0] = c->info;
-  b.ld = ld; b.sk_ws = c->sk_ws[0];
+  b.A[0] = c->Kbuf; b.L[0] = c->Lbuf; b.Li[0] = c->Libuf; b.Tmp[0] = c->Tmp; b.info[0] = c->info + INFO_K;
+  b.ld = ld;
   return b;
 }
 
@@ -162,19 +151,19 @@ int gpfit_potrf_append(gpfit_ctx* c, void* stream, double* L, int64_t ldl, doubl
   double* w = c->bv;       // L^-T l
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
   hipLaunchKernelGGL(append_trmv_kernel, dim3((ni + 3) / 4), dim3(256), 0, s, Linv, ldi, ni, kcol, l);
-  hipLaunchKernelGGL(append_trmv_t_kernel, dim3((ni + 63) / 64), dim3(256), 0, s, Linv, ldi, ni, l, w, c->scal + 48);
+  hipLaunchKernelGGL(append_trmv_t_kernel, dim3((ni + 63) / 64), dim3(256), 0, s, Linv, ldi, ni, l, w, c->scal + S_APPEND);
   hipLaunchKernelGGL(append_write_kernel, dim3((ni + 256) / 256), dim3(256), 0, s, L, ldl, Linv, ldi, ni, l, w, kcol,
-                     c->scal + 48, c->info);
+                     c->scal + S_APPEND, c->info + INFO_K);
   GP_HIP(hipGetLastError());
-  GP_HIP(hipMemcpyAsync(c->scal_host + 48, c->scal + 48, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  GP_HIP(hipMemcpyAsync(c->scal_host + S_APPEND, c->scal + S_APPEND, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
-  if (info_host) *info_host = c->info_host[0];
-  if (c->info_host[0] != 0) {
+  if (info_host) *info_host = c->info_host[INFO_K];
+  if (c->info_host[INFO_K] != 0) {
     set_error("gpfit_potrf_append: the extended matrix is not positive definite");
-    return c->info_host[0];
+    return c->info_host[INFO_K];
   }
-  if (logdet_inout_host) *logdet_inout_host += 2.0 * std::log(c->scal_host[49]);
+  if (logdet_inout_host) *logdet_inout_host += 2.0 * std::log(c->scal_host[S_APPEND_LAMBDA]);
   return 0;
 }
 
@@ -195,18 +184,18 @@ int gpfit_potrf(gpfit_ctx* c, void* stream, const double* A, int64_t lda, int64_
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
   GP_TRY(launch_pack_lower(A, lda, (int)n, c->Kbuf, ld, np, s));
   const CholBatchT<double> b = one_chain(c, ld);
-  GP_TRY(potrf_lockstep(b, 0, np, Linv != nullptr ? 1u : 0u, s));
-  GP_TRY(launch_logdet(c->Lbuf, ld, (int)n, c->scal + 3, s));
+  GP_TRY(potrf_lockstep(b, 0, np, Linv != nullptr ? 1u : 0u, main_lane(c, s)));
+  GP_TRY(launch_logdet(c->Lbuf, ld, (int)n, c->scal + S_LOGDET_K, s));
   if (L) GP_TRY(launch_unpack_tri(c->Lbuf, ld, (int)n, L, ldl, s));
   if (Linv) GP_TRY(launch_unpack_tri(c->Libuf, ld, (int)n, Linv, ldi, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
-  if (logdet_host) *logdet_host = c->scal_host[3];
-  if (info_host) *info_host = c->info_host[0];
-  if (c->info_host[0] != 0) {
+  if (logdet_host) *logdet_host = c->scal_host[S_LOGDET_K];
+  if (info_host) *info_host = c->info_host[INFO_K];
+  if (c->info_host[INFO_K] != 0) {
     set_error("gpfit_potrf: matrix is not positive definite");
-    return c->info_host[0];
+    return c->info_host[INFO_K];
   }
   return 0;
 }
@@ -233,33 +222,33 @@ int gpfit_estep(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_
   // M = I + S K S (lower), SK = S K (dense), Kl = K (lower)
   GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, c->Wbuf, ld, s));
   const CholBatchT<double> b = one_chain(c, ld);
+  const Lane lane = main_lane(c, s);
+  auto at = [&](double* X, int r, int col) { return mat(X + (int64_t)r * ld + col, ld); };
   // T = L_M^-1 (S K)          lower x dense                         N^3
   if (np >= 2 * TILE) {
     // block-wise, so that the off-diagonal block of L_M^-1 is never formed (N^3/4 less):
     //   T1 = [L^-1]11 B1 ,  T2 = [L^-1]22 (B2 - L21 T1)        with B = S K
     const int kt = np / TILE;
     const int n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;
-    GP_TRY(potrf_lockstep(b, 0, np, 0u, s, 1u));   // [L^-1]11 and [L^-1]22 only
-    GP_TRY(gemm_full(s, 0, 1, n1, np, n1, 1.0, c->Libuf, ld, c->Zbuf, ld, 0.0, c->Abuf, ld, 0, 1, 0, 1, c->sk_ws[0]));
-    GP_TRY(gemm_full(s, 0, 1, n2, np, n1, -1.0, c->Lbuf + (int64_t)n1 * ld, ld, c->Abuf, ld, 1.0,
-                     c->Zbuf + (int64_t)n1 * ld, ld, 0, 0, 0, 0, c->sk_ws[0]));
-    GP_TRY(gemm_full(s, 0, 1, n2, np, n2, 1.0, c->Libuf + (int64_t)n1 * ld + n1, ld, c->Zbuf + (int64_t)n1 * ld, ld, 0.0,
-                     c->Abuf + (int64_t)n1 * ld, ld, 0, 1, 0, 1, c->sk_ws[0]));
+    GP_TRY(potrf_lockstep(b, 0, np, 0u, lane, 1u));   // [L^-1]11 and [L^-1]22 only
+    GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
+    GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(c->Lbuf, n1, 0)), plain(at(c->Abuf, 0, 0)), into(at(c->Zbuf, n1, 0), 1.0)));
+    GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(c->Libuf, n1, n1))), plain(at(c->Zbuf, n1, 0)), into(at(c->Abuf, n1, 0)), 1));
   } else {
-    GP_TRY(potrf_lockstep(b, 0, np, 1u, s));
-    GP_TRY(gemm_full(s, 0, 1, np, np, np, 1.0, c->Libuf, ld, c->Zbuf, ld, 0.0, c->Abuf, ld, 0, 1, 0, 1, c->sk_ws[0]));
+    GP_TRY(potrf_lockstep(b, 0, np, 1u, lane));
+    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
   }
   // V = K - T^T T             lower tiles only                      N^3
-  GP_TRY(gemm_full(s, 1, 1, np, np, np, -1.0, c->Abuf, ld, c->Abuf, ld, 1.0, c->Wbuf, ld, 1, 0, 0, 0, c->sk_ws[0]));
+  GP_TRY(product(lane, {np, np, np}, -1.0, trans(at(c->Abuf, 0, 0)), plain(at(c->Abuf, 0, 0)), into_lower(at(c->Wbuf, 0, 0), 1.0)));
   // m_new = V (A^2 f o m + A (r - f))                                utils.py:1431
   GP_TRY(launch_symv_lower(c->Wbuf, ld, n, rhs, c->tvec, s));
   GP_HIP(hipMemcpyAsync(m_new, c->tvec, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
   GP_TRY(launch_unpack_sym(c->Wbuf, ld, n, V_new, ldv, s));  // symmetric by construction (utils.py:1438)
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
-  if (c->info_host[0] != 0) {
+  if (c->info_host[INFO_K] != 0) {
     set_error("gpfit_estep: I + S K S is not positive definite (is K_tilde symmetric positive definite?)");
-    return c->info_host[0];
+    return c->info_host[INFO_K];
   }
   return 0;
 }
@@ -287,34 +276,36 @@ int gpfit_estep_projected(gpfit_ctx* c, void* stream, const double* a, int64_t l
   double *sv = c->yv, *u = c->bv, *t2 = c->tvec, *z1 = c->mpad, *z = c->rpad, *mo = c->hvec;
   double *Y = c->Tbuf, *Lp = c->Wbuf, *P = c->Abuf, *V = c->Zbuf, *part = c->TmpV, *aLp = c->LiVbuf, *Zm = c->Cos;
   c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
+  const Lane lane = main_lane(c, s);
+  auto M = [&](double* X) { return mat(X, ld); };
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
   GP_TRY(launch_estep_proj_rows(a, lda, k, m, f, r, n, nrows, A, sv, u, s));
   GP_TRY(launch_estep_proj_scale(aL, ldal, k, n, nrows, sv, u, Y, want_moments ? aLp : nullptr, ld, npc, part, s));
   GP_TRY((launch_reduce_slices<double, double>(part, npc, nrows / 32, t2, npc, s)));   // t2 = (a L)^T u
   // W = I + Y^T Y  (= I + L^T G L, G = A^2 a^T diag(f) a), lower tiles, identity on the padding
-  GP_TRY(gemm_full(s, 1, 1, npc, npc, nrows, 1.0, Y, ld, Y, ld, 0.0, c->Kbuf, ld, 1, 0, 0, 0, c->sk_ws[0]));
+  GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(M(Y)), plain(M(Y)), into_lower(M(c->Kbuf))));
   GP_TRY(launch_add_diag(c->Kbuf, ld, npc, 1.0, s));
-  GP_TRY(potrf_lockstep(one_chain(c, ld), 0, npc, 1u, s));
+  GP_TRY(potrf_lockstep(one_chain(c, ld), 0, npc, 1u, lane));
   // m_new = L W^-1 (a L)^T u
   GP_TRY(launch_trmv_lower(c->Libuf, ld, npc, t2, z1, s));
   GP_TRY(launch_trmv_lower_t(c->Libuf, ld, npc, z1, z, c->trmv_part, s));
   GP_TRY(launch_pack_lower(L, ldl, k, Lp, ld, npc, s));
   GP_TRY(launch_trmv_lower(Lp, ld, npc, z, mo, s));
   // V_new = P P^T, P = L L_W^-T  (= (K~^-1 + G)^-1 = solve(I + K~ G, K~), utils.py:1430)
-  GP_TRY(gemm_full(s, 0, 0, npc, npc, npc, 1.0, Lp, ld, c->Libuf, ld, 0.0, P, ld, 0, 1, 2, 0, c->sk_ws[0]));
-  GP_TRY(gemm_full(s, 0, 0, npc, npc, npc, 1.0, P, ld, P, ld, 0.0, V, ld, 1, 0, 0, 0, c->sk_ws[0]));
+  GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(M(Lp))), trans(tril(M(c->Libuf))), into(M(P))));
+  GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(M(P)), trans(M(P)), into_lower(M(V))));
   GP_HIP(hipMemcpyAsync(m_new, mo, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s));
   GP_TRY(launch_unpack_sym(V, ld, k, V_new, ldv, s));   // symmetric by construction (utils.py:1438)
   if (want_moments) {
     // the moments of lambda the caller evaluates next (utils.py:1090, 1101), from Z = aL L_W^-T: a V_new a^T = Z Z^T
-    GP_TRY(gemm_full(s, 0, 0, nrows, npc, npc, 1.0, aLp, ld, c->Libuf, ld, 0.0, Zm, ld, 0, 0, 2, 0, c->sk_ws[0]));
+    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(M(aLp)), trans(tril(M(c->Libuf))), into(M(Zm))));
     GP_TRY(launch_estep_proj_moments(Zm, ld, k, z1, kv0, n, lam_m_out, lam_var_out, s));
   }
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
-  if (c->info_host[0] != 0) {
+  if (c->info_host[INFO_K] != 0) {
     set_error("gpfit_estep_projected: I + L^T G L is not positive definite (NaN or negative firing rates?)");
-    return c->info_host[0];
+    return c->info_host[INFO_K];
   }
   return 0;
 }
@@ -331,9 +322,9 @@ int gpfit_fparam_eval(gpfit_ctx* c, void* stream, const double* lam_m, const dou
   // the seven results go straight to the context's pinned, device-mapped scalars (no copy command behind the kernel:
   // the L-BFGS of the rate parameters calls this ~6 times per E-step and waits for every answer)
   GP_TRY(launch_fparam(lam_m, lam_var, r, (int)N, std::exp(logA), closed_form_lambda0, lambda0_in, f_out,
-                       c->scal_host + 32, s));
+                       c->scal_host + S_FPARAM, s));
   GP_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < 7; ++i) out_host[i] = c->scal_host[32 + i];
+  for (int i = 0; i < 7; ++i) out_host[i] = c->scal_host[S_FPARAM + i];
   return 0;
 }
 
@@ -351,9 +342,9 @@ int gpfit_fparam_lbfgs(gpfit_ctx* c, void* stream, const double* lam_m, const do
   hipStream_t s = (hipStream_t)stream;
   // one launch, one wait: the nine results go straight to pinned, device-mapped scalars no other entry point uses
   GP_TRY(launch_fparam_lbfgs(lam_m, lam_var, r, (int)N, logA0, lambda0_mode ? 1 : 0, lambda0_fixed, cfg, f_out,
-                             c->scal_host + 52, s));
+                             c->scal_host + S_LBFGS, s));
   GP_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < 9; ++i) out_host[i] = c->scal_host[52 + i];
+  for (int i = 0; i < 9; ++i) out_host[i] = c->scal_host[S_LBFGS + i];
   return 0;
 }
 

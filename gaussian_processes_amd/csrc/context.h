@@ -58,13 +58,49 @@ struct gpfit_ctx {
 
   // cached state of the last upload / evaluation (used by estep / predict entry points)
   int cur_n = 0, cur_np = 0, cur_d = 0, cur_dp = 0;
-  bool lv_valid = false;  // LVbuf / scal[40] hold the factor and log-det of the last V
+  bool lv_valid = false;  // LVbuf / scal[S_LOGDET_V] hold the factor and log-det of the last V
   bool lv32_valid = false;  // Vbuf holds the single-precision copy of that factor (mixed-precision mode)
   int lv_n = 0;
   int lv_bytes = 0;       // element size the cached factor was computed in
 };
 
 namespace gpfit {
+
+// A stream-K workspace belongs to the stream its launches run on, so the two travel together: the caller's (main)
+// stream pairs with the context's sk_ws[0] -- in a group, the leader's -- and the side stream with sk_ws[1].
+struct Lane { hipStream_t s; void* sk_ws; };
+inline Lane main_lane(const gpfit_ctx* c, hipStream_t s) { return {s, c->sk_ws[0]}; }
+inline Lane side_lane(const gpfit_ctx* c) { return {c->side, c->sk_ws[1]}; }
+
+// ---- names of the numbered slots
+// gpfit_ctx::scal / scal_host (64 doubles), with who writes each
+enum ScalSlot {
+  S_RLAM = 0, S_SUMR = 1, S_SUMF = 2,   // likelihood sums r . lam_m, sum r, sum f (launch_moments / launch_proj_moments)
+  S_LOGDET_K = 3,                       // log|K~| (launch_logdet / launch_logdet_pair)
+  S_TRACE = 5,                          // ||T||_F^2 (launch_frob_finish / launch_frob_lower) or tr(K~_b^-1 V_b) (launch_proj_trace)
+  S_MKM = 6,                            // m^T K~^-1 m (launch_dot)
+  S_ADJ = 7, S_ADJ_WL = 8, S_ADJ_SUMA = 9,   // adjoint sums: sum u/q (S_ADJ), sum wl, sum A_w (launch_adjoint_reduce)
+  S_METRIC = 10,                        // 10-14: the contraction with dC_p (launch_metric_contract), in the order ...
+  S_D_AMP = 10, S_D_BETA = 11, S_D_RHO = 12, S_D_EPSX = 13, S_D_EPSY = 14,   // ... Amp, -2log2beta, -log2rho2, eps_0x, eps_0y
+  S_RECT = 20, S_RECT_U1 = 21, S_RECT_U2 = 22,   // rectangular adjoint: sum A_w (S_RECT), sum u1/q1, sum u2/q2 (launch_adjoint_rect)
+  S_FPARAM = 32,                        // 32-38, scal_host only: launch_fparam writes them directly (gpfit_fparam_eval)
+  S_LOGDET_V = 40,                      // log|V| (launch_logdet / launch_logdet_pair); kept while lv_valid
+  S_APPEND = 48, S_APPEND_LAMBDA = 49,  // gpfit_potrf_append: l . l, the new diagonal entry
+  S_LBFGS = 52,                         // 52-60, scal_host only: launch_fparam_lbfgs writes them directly
+};
+// gpfit_ctx::info / info_host (4 ints)
+enum InfoWord {
+  INFO_K = 0, INFO_V = 1,   // LAPACK info of the two Cholesky chains (chol_leaf_reg.hip; gpfit_potrf_append: word 0)
+  INFO_MOMENTS = 2,         // ticket of launch_moments' last-block reduction (0 between calls)
+  INFO_METRIC = 3,          // ticket of launch_metric_contract (0 between calls)
+};
+// the tile walks of the large launches, in the order GPFIT_WALKS lists them (fit.hip: walk())
+enum Walk { W_TRSM, W_TMP, W_MERGE, W_T, W_Q, W_RBASE, W_H, W_COUNT };
+// out_host[16] of the fused closures (assemble_out; include/gpfit_mi355x.h documents them; engine.py reads by index)
+enum OutSlot {
+  OUT_LOSS = 0, OUT_LOGLIK = 1, OUT_KL = 2, OUT_GRAD = 3 /* 3-8 */, OUT_LOGDET_K = 9, OUT_LOGDET_V = 10, OUT_TRACE = 11,
+  OUT_MKM = 12, OUT_D = 13, OUT_INFO_K = 14, OUT_INFO_V = 15, OUT_COUNT = 16,
+};
 
 // Every context entry point runs on the context's device whatever the caller's current device is,
 // and restores the caller's device on return.
@@ -110,7 +146,6 @@ struct CholBatchT {
   R* Tmp[GEMM_MAXB];
   int* info[GEMM_MAXB];
   int64_t ld = 0;
-  void* sk_ws = nullptr;     // stream-K workspace of the launches issued chain by chain (one stream: shared)
   gpfit_ctx* ctx = nullptr;  // look-ahead resources (this context's side stream), or nullptr: one stream
   int side_min = 0;          // blocks of at least this size put their merge product on the side stream
 };
@@ -119,6 +154,6 @@ struct CholBatchT {
 // (n^3/12).  halves: bit b = chain b needs the inverses of the two diagonal half blocks but not the off-diagonal
 // block [L^-1]21 (for callers that apply L^-1 block-wise, n^3/8 less than need); read at this node only.
 template <typename R>
-int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStream_t s, uint32_t halves = 0);
+int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, Lane lane, uint32_t halves = 0);
 
 }  // namespace gpfit

@@ -7,7 +7,7 @@
 // the vectors behind the factor, the mixed-precision hand-over, the pull-back to the metric, the
 // n_kept x n_kept algebra of the truncated-rank closures, the host assembly of the 16 outputs); what
 // differs between the entry points is which stages they call and what they launch in between.
-#include "context.h"
+#include "product.h"
 #include "gemm_core.h"
 #include "gpfit_mi355x.h"
 
@@ -22,22 +22,21 @@ namespace gpfit {
 
 // ------------------------------------------------------------------ per-launch profiling
 static thread_local gpfit_ctx* g_prof = nullptr;
-static thread_local void* g_main_sk_ws = nullptr;  // stream-K workspace of the context being evaluated
 
 // tile-walk choices of the large launches (tuning knob GPFIT_WALKS = trsm,tmp,merge,T,Q,Rbase,H)
-static const int* walks() {
-  static int w[7] = {3, 2, 1, 9, 9, 2, 2};  // bit 3 = XCD-aware macro-tile schedule where the launch is large enough
-                                          // (gemm_sched.hip), else the walk in the low bits
+static int walk(Walk which) {
+  static int w[W_COUNT] = {3, 2, 1, 9, 9, 2, 2};  // bit 3 = XCD-aware macro-tile schedule where the launch is large enough
+                                                // (gemm_sched.hip), else the walk in the low bits
   static bool init = false;
   if (!init) {
     init = true;
     if (const char* e = getenv("GPFIT_WALKS")) {
-      int v[7];
+      int v[W_COUNT];
       if (sscanf(e, "%d,%d,%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6]) == 7)
-        for (int i = 0; i < 7; ++i) w[i] = v[i];
+        for (int i = 0; i < W_COUNT; ++i) w[i] = v[i];
     }
   }
-  return w;
+  return w[which];
 }
 
 static hipEvent_t prof_event(gpfit_ctx* c) {
@@ -111,21 +110,6 @@ double gemm_flops(const GemmArgsT<R>& g, int T) {
 }
 
 // ------------------------------------------------------------------ GEMM convenience
-template <typename R>
-static GemmArgsT<R> gemm_args(int a_kmajor, int b_kmajor, int M, int N, int K, double alpha, const R* A, int64_t lda,
-                              const R* B, int64_t ldb, double beta, R* C, int64_t ldc, int out_lower, int a_tri,
-                              int b_tri, int reverse = 0, void* sk_ws = nullptr) {
-  GemmArgsT<R> g{};
-  g.A = A; g.B = B; g.C = C;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K;
-  g.alpha = alpha; g.beta = beta;
-  g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor;
-  g.out_lower = out_lower; g.a_tri = a_tri; g.b_tri = b_tri;
-  g.batch = 1; g.split_k = 1; g.reverse = reverse; g.sk_ws = sk_ws ? sk_ws : g_main_sk_ws;
-  return g;
-}
-
 // tuning aid: GPFIT_GEMM_LOG=k lists every GEMM launch of the k-th evaluation of the process on stderr (shape,
 // structure flags, problems in the batch, block tile, executed flops), in launch order -- to be paired with a
 // kernel trace of the same run (scripts/trace_gemm_rates.py)
@@ -134,46 +118,30 @@ static int gemm_log_eval() {
   static const int v = getenv("GPFIT_GEMM_LOG") ? atoi(getenv("GPFIT_GEMM_LOG")) : -1;
   return v;
 }
-
-// launch g on its route r = gemm_route(g)
+static bool gemm_logging() { return gemm_log_eval() >= 0 && g_eval_count == gemm_log_eval(); }
+// the fields of a log line behind its head: scalars, leading dimensions, walk, split-k, k slabs
 template <typename R>
-static int run_gemm(hipStream_t s, const GemmArgsT<R>& g, const GemmRoute& r) {
-  if (gemm_log_eval() >= 0 && g_eval_count == gemm_log_eval())
-    fprintf(stderr, "[gpfit gemm] M %d N %d K %d atri %d btri %d lower %d nb %d tile %d ak %d bk %d epi %d flops %.6e\n", g.M, g.N, g.K,
+static void gemm_log_tail(const char* tag, const GemmArgsT<R>& g, const char* end) {
+  fprintf(stderr, "%s alpha %g beta %g lda %lld ldb %lld ldc %lld walk %d split %d slabs %d%s", tag, g.alpha, g.beta, (long long)g.lda,
+          (long long)g.ldb, (long long)g.ldc, g.reverse, g.split_k, g.k_slabs, end);
+}
+
+// launch g on its route r = gemm_route(g).  Every product of fit.hip, api_solve.hip and api_kernel.hip is logged here; a
+// profile entry is made only while a fit_eval-family evaluation has a profile open (g_prof): never for the latter two
+template <typename R>
+int run_gemm(hipStream_t s, const GemmArgsT<R>& g, const GemmRoute& r) {
+  if (gemm_logging()) {
+    fprintf(stderr, "[gpfit gemm] M %d N %d K %d atri %d btri %d lower %d nb %d tile %d ak %d bk %d epi %d flops %.6e", g.M, g.N, g.K,
             g.a_tri, g.b_tri, g.out_lower, g.nptr > 0 ? g.nptr : 1, r.tile, g.a_kmajor, g.b_kmajor, g.epi, gemm_flops(g, r.tile));
+    gemm_log_tail("", g, "\n");
+  }
   // profile kind 0: the 128-tile kernel family (the dominant kernel), 3: the small-tile instances
   ProfScope ps(s, g_prof ? gemm_flops(g, r.tile) : 0.0, (g_prof && r.tile != TILE) ? 3 : 0);
   return launch_gemm(g, r, s);
 }
-template <typename R>
-static int run_gemm(hipStream_t s, const GemmArgsT<R>& g) { return run_gemm(s, g, gemm_route(g)); }
+template int run_gemm<double>(hipStream_t, const GemmArgsT<double>&, const GemmRoute&);
+template int run_gemm<float>(hipStream_t, const GemmArgsT<float>&, const GemmRoute&);
 
-template <typename R>
-static int gemm(hipStream_t s, int a_kmajor, int b_kmajor, int M, int N, int K, double alpha, const R* A,
-                int64_t lda, const R* B, int64_t ldb, double beta, R* C, int64_t ldc, int out_lower, int a_tri,
-                int b_tri, int reverse = 0, void* sk_ws = nullptr) {
-  return run_gemm(s, gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, out_lower, a_tri, b_tri,
-                                  reverse, sk_ws));
-}
-
-// C = alpha op(A) op(B) with the k range cut into `splits` slabs: the shapes of the truncated-rank closures whose
-// output has few tiles but a long k (K_b = K~ B: 8192 x 512 x 8192; B^T X: 512 x 512 x 8192) fill the chip with
-// 128-tiles only this way.  The slabs go to `partial` (splits x M x ldc elements) and are added in slab order by
-// one pass (deterministic; C must be the contiguous block [M][ldc]).  splits <= 1: the plain launch.
-template <typename R>
-static int gemm_splitk(hipStream_t s, int a_kmajor, int b_kmajor, int M, int N, int K, double alpha, const R* A, int64_t lda,
-                       const R* B, int64_t ldb, R* C, int64_t ldc, int splits, R* partial, int64_t partial_elems) {
-  static const bool off = getenv("GPFIT_NO_SPLITK") != nullptr;   // tuning knob
-  splits = (int)std::min<int64_t>(splits, partial_elems / std::max<int64_t>(1, (int64_t)M * ldc));   // what the scratch holds
-  if (splits <= 1 || off || partial == nullptr)
-    return gemm<R>(s, a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, 0.0, C, ldc, 0, 0, 0);
-  GemmArgsT<R> g = gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, 0.0, partial, ldc, 0, 0, 0);
-  g.split_k = splits;
-  g.sC = (int64_t)M * ldc;
-  g.tile = TILE;
-  GP_TRY(run_gemm(s, g));
-  return launch_reduce_slices(partial, (int64_t)M * ldc, splits, C, (int64_t)M * ldc, s);
-}
 // slabs so that a product with few output tiles still launches about one and a half rounds of 128-tile workgroups,
 // each with a k range of at least 256
 static int splitk_for(int M, int N, int K) {
@@ -183,6 +151,25 @@ static int splitk_for(int M, int N, int K) {
   sp = std::min<long>(sp, std::max(1, K / 256));
   return (int)std::max<long>(1, sp);
 }
+// C = alpha op(A) op(B) with the k range cut into splitk_for slabs: the shapes of the truncated-rank closures whose
+// output has few tiles but a long k (K_b = K~ B: 8192 x 512 x 8192; B^T X: 512 x 512 x 8192) fill the chip with
+// 128-tiles only this way.  The slabs go to `partial` (splits x M x ldc elements) and are added in slab order by
+// one pass (deterministic; C must be the contiguous block [M][ldc]).  One slab: the plain launch.
+template <typename R>
+static int gemm_splitk(Lane lane, Dims d, double alpha, const Operand<R>& a, const Operand<R>& b, R* C, int64_t ldc, R* partial,
+                       int64_t partial_elems) {
+  static const bool off = getenv("GPFIT_NO_SPLITK") != nullptr;   // tuning knob
+  const int64_t slab = (int64_t)d.M * ldc;
+  const int splits = (int)std::min<int64_t>(splitk_for(d.M, d.N, d.K),
+                                            partial_elems / std::max<int64_t>(1, slab));   // what the scratch holds
+  if (splits <= 1 || off || partial == nullptr) return product(lane, d, alpha, a, b, into(mat(C, ldc)));
+  GemmArgsT<R> g = product_args(lane, d, alpha, a, b, into(mat(partial, ldc)));
+  g.split_k = splits;
+  g.sC = slab;
+  g.tile = TILE;
+  GP_TRY(run_gemm(lane.s, g));
+  return launch_reduce_slices(partial, slab, splits, C, slab, lane.s);
+}
 
 // tuning knob (bit mask, default all): fused GEMM epilogues -- 1 Q's symmetrisation, 2 T's norm, 4 the H / Z21 update
 // of the two-sided product
@@ -191,43 +178,24 @@ static int fused_epilogues() {
   return v;
 }
 
-
-// ------------------------------------------------------------------ recursive Cholesky (+ inverse), in lock step
-// Recursive blocked Cholesky built entirely from the MFMA GEMM and the 128 x 128 leaf, for nb matrices of the same
-// size at once (CholBatchT, context.h): one matrix (gpfit_potrf, the E-steps, a unit whose V factor is reused), the
-// K~ and V chains of one unit, or the chains of several independent units.  Every level whose launches cannot fill
-// the chip -- the leaves and the products of the small blocks, i.e. the latency-bound bottom of the recursion -- is
-// ONE launch for all chains (a pointer batch, GemmArgsT::nptr / LeafBatchT): the number of kernel boundaries on the
-// critical path does not grow with the number of chains and every small launch has nb times the workgroups.
-// Products that are 128-tile launches for a single chain are issued chain by chain through the ordinary launcher,
-// with its stream-K / XCD-aware schedules.  A chain therefore gets the same bits whatever else is in the batch: its
-// launches are the same products in the same order, stream-K only ever applies to 128-tile launches of a single
-// problem, and every data-parallel instance sums k in ascending order per element whatever block tile the launcher
-// picks.
-// cnt problems of one shape, problem i on (Ap[i], Bp[i], Cp[i]): one pointer-batched launch, unless the product
-// is a 128-tile launch already for a single problem -- then problem by problem through the ordinary launcher.
+// One product for every problem of a list (product.h).  e: fused epilogue wanted; e->carried says whether the launches
+// carried it -- all of them or none (the caller runs the separate passes otherwise); e->sumsq_entries: what the route
+// of one such launch says.
 template <typename R>
-static int gemm_list(hipStream_t s, int cnt, const R* const* Ap, const R* const* Bp, R* const* Cp, int a_kmajor,
-                     int b_kmajor, int M, int N, int K, double alpha, int64_t lda, int64_t ldb, double beta, int64_t ldc,
-                     int out_lower, int a_tri, int b_tri, int reverse = 0, void* sk_ws = nullptr,
-                     int epi = 0, R* const* auxp = nullptr, double* const* sumsqp = nullptr, bool* epi_done = nullptr,
-                     int* sumsq_entries = nullptr) {
-  if (epi_done) *epi_done = false;
-  if (sumsq_entries) *sumsq_entries = 0;
+int product(Lane lane, Dims d, double alpha, const Operand<R>& a, const Operand<R>& b, const Output<R>& c, int walk, Epilogue<R>* e) {
+  const int cnt = c.m.cnt, epi = e ? e->which : 0;
+  if (e) { e->carried = false; e->sumsq_entries = 0; }
   if (cnt <= 0) return 0;
   if (cnt > GEMM_MAXB) {
-    set_error("gemm_list: more problems than a pointer batch holds");
+    set_error("product: more problems than a pointer batch holds");
     return -3;
   }
-  GemmArgsT<R> g = gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, Ap[0], lda, Bp[0], ldb, beta, Cp[0], ldc, out_lower,
-                                a_tri, b_tri, reverse, sk_ws);
+  GemmArgsT<R> g = product_args(lane, d, alpha, a, b, c, walk);
   static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;   // tuning knob: every product on its own
-  // epi: fused epilogue wanted (common.h); *epi_done says whether the launches carried it -- all of them or none
-  // (the caller runs the separate passes otherwise); *sumsq_entries: what the route of one such launch says
   if (cnt == 1 || gemm_pick_tile(g) == TILE || no_batch) {
     auto problem = [&](int i, bool fused) {
-      g.A = Ap[i]; g.B = Bp[i]; g.C = Cp[i];
-      g.epi = fused ? epi : 0; g.aux = (fused && auxp) ? auxp[i] : nullptr; g.sumsq = (fused && sumsqp) ? sumsqp[i] : nullptr;
+      g.A = a.m.p[i]; g.B = b.m.p[i]; g.C = c.m.p[i];
+      g.epi = fused ? epi : 0; g.aux = fused ? e->aux[i] : nullptr; g.sumsq = fused ? e->sumsq[i] : nullptr;
     };
     GemmRoute routes[GEMM_MAXB];
     bool fused = epi != 0;
@@ -238,70 +206,52 @@ static int gemm_list(hipStream_t s, int cnt, const R* const* Ap, const R* const*
     }
     for (int i = 0; i < cnt; ++i) {
       problem(i, fused);
-      GP_TRY(fused ? run_gemm(s, g, routes[i]) : run_gemm(s, g));
+      GP_TRY(fused ? run_gemm(lane.s, g, routes[i]) : run_gemm(lane.s, g));
     }
-    if (epi_done) *epi_done = fused;
-    if (fused && sumsq_entries) *sumsq_entries = routes[0].sumsq_entries;
+    if (e) e->carried = fused;
+    if (fused) e->sumsq_entries = routes[0].sumsq_entries;
     return 0;
   }
-  g.nptr = cnt;
-  g.batch = cnt;
-  for (int i = 0; i < cnt; ++i) {
-    g.Ap[i] = Ap[i]; g.Bp[i] = Bp[i]; g.Cp[i] = Cp[i];
-    g.auxp[i] = auxp ? auxp[i] : nullptr; g.sumsqp[i] = sumsqp ? sumsqp[i] : nullptr;
-  }
-  g.epi = epi;
+  g = batch_args(lane, d, alpha, a, b, c, walk, e);
   GemmRoute r = gemm_route(g);
   if (epi && r.epi == 0) {   // the batch cannot carry it: without
     g.epi = 0;
     r = gemm_route(g);
   }
-  if (epi_done) *epi_done = g.epi != 0;
-  if (sumsq_entries) *sumsq_entries = r.sumsq_entries;
-  return run_gemm(s, g, r);
+  if (e) { e->carried = g.epi != 0; e->sumsq_entries = r.sumsq_entries; }
+  return run_gemm(lane.s, g, r);
 }
+template int product<double>(Lane, Dims, double, const Operand<double>&, const Operand<double>&, const Output<double>&, int,
+                             Epilogue<double>*);
+template int product<float>(Lane, Dims, double, const Operand<float>&, const Operand<float>&, const Output<float>&, int,
+                            Epilogue<float>*);
 
+// ------------------------------------------------------------------ recursive Cholesky (+ inverse), in lock step
+// Recursive blocked Cholesky built entirely from the MFMA GEMM and the 128 x 128 leaf, for nb matrices of the same
+// size at once (CholBatchT, context.h): one matrix (gpfit_potrf, the E-steps, a unit whose V factor is reused), the
+// K~ and V chains of one unit, or the chains of several independent units.  Every level whose launches cannot fill
+// the chip -- the leaves and the products of the small blocks, i.e. the latency-bound bottom of the recursion -- is
+// ONE launch for all chains (a pointer batch, GemmArgsT::nptr / LeafBatchT): the number of kernel boundaries on the
+// critical path does not grow with the number of chains and every small launch has nb times the workgroups.
+// Products that are 128-tile launches for a single chain are issued chain by chain through the ordinary launcher,
+// with its stream-K / XCD-aware schedules (product above).  A chain therefore gets the same bits whatever else is in
+// the batch: its launches are the same products in the same order, stream-K only ever applies to 128-tile launches of
+// a single problem, and every data-parallel instance sums k in ascending order per element whatever block tile the
+// launcher picks.
 template <typename R>
-static int bgemm(const CholBatchT<R>& B, hipStream_t s, uint32_t mask, int a_kmajor, int b_kmajor, int M, int N, int K,
-                 double alpha, R* const* Ab, int64_t offA, R* const* Bb, int64_t offB, double beta, R* const* Cb,
-                 int64_t offC, int out_lower, int a_tri, int b_tri, int reverse, void* sk_ws) {
-  const R* Ap[GEMM_MAXB];
-  const R* Bp[GEMM_MAXB];
-  R* Cp[GEMM_MAXB];
-  int cnt = 0;
-  for (int b = 0; b < B.nb; ++b)
-    if (mask & (1u << b)) {
-      Ap[cnt] = Ab[b] + offA; Bp[cnt] = Bb[b] + offB; Cp[cnt] = Cb[b] + offC;
-      ++cnt;
-    }
-  return gemm_list<R>(s, cnt, Ap, Bp, Cp, a_kmajor, b_kmajor, M, N, K, alpha, B.ld, B.ld, beta, B.ld, out_lower, a_tri,
-                      b_tri, reverse, sk_ws);
-}
-
-// the pointer batch of the chains in `mask` (as bgemm builds it), for launches that take two batches at once
-template <typename R>
-static GemmArgsT<R> batch_args(const CholBatchT<R>& B, uint32_t mask, int a_kmajor, int b_kmajor, int M, int N, int K, double alpha,
-                               R* const* Ab, int64_t offA, R* const* Bb, int64_t offB, double beta, R* const* Cb, int64_t offC,
-                               int out_lower, int a_tri, int b_tri, int reverse) {
-  GemmArgsT<R> g = gemm_args<R>(a_kmajor, b_kmajor, M, N, K, alpha, (const R*)nullptr, B.ld, (const R*)nullptr, B.ld, beta,
-                                (R*)nullptr, B.ld, out_lower, a_tri, b_tri, reverse, B.sk_ws);
-  int cnt = 0;
-  for (int b = 0; b < B.nb; ++b)
-    if (mask & (1u << b)) {
-      g.Ap[cnt] = Ab[b] + offA; g.Bp[cnt] = Bb[b] + offB; g.Cp[cnt] = Cb[b] + offC;
-      ++cnt;
-    }
-  g.nptr = cnt;
-  g.batch = cnt;
-  if (cnt > 0) { g.A = g.Ap[0]; g.B = g.Bp[0]; g.C = g.Cp[0]; }
-  return g;
-}
-
-template <typename R>
-int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStream_t s, uint32_t halves) {
+int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, Lane lane, uint32_t halves) {
   const int64_t ld = B.ld;
+  const hipStream_t s = lane.s;
   const uint32_t all = (B.nb >= 32) ? 0xffffffffu : ((1u << B.nb) - 1u);
   auto off = [&](int r, int c) { return (int64_t)r * ld + c; };
+  // block (r, c) of matrix X of every chain in `mask`
+  auto blk = [&](uint32_t mask, R* const* X, int r, int c) {
+    Mat<R> m{};
+    m.ld = ld;
+    for (int b = 0; b < B.nb; ++b)
+      if (mask & (1u << b)) m.p[m.cnt++] = X[b] + off(r, c);
+    return m;
+  };
   if (n == TILE) {
     ProfScope ps(s, 0.0, 1);
     LeafBatchT<R> bt{};
@@ -317,13 +267,20 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
   const int k = n / TILE;
   const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;
   const int r1 = r0 + n1;
-  GP_TRY(potrf_lockstep<R>(B, r0, n1, all, s));
-  // L21 = A21 * L11^-T       (trsm as a GEMM against the explicit inverse; op(B) = Li11^T is upper)
-  GP_TRY(bgemm<R>(B, s, all, 0, 0, n2, n1, n1, 1.0, B.A, off(r1, r0), B.Li, off(r0, r0), 0.0, B.L, off(r1, r0), 0, 0, 2,
-                  walks()[0], B.sk_ws));
-  // Look-ahead: tmp = L21 * Li11, the first product of the inverse merge, needs nothing from the second half, so it
-  // runs on the context's side stream while that half is being factored (its leaves are latency-bound and leave the
-  // chip to it).  Possible because the leaf shares a CU with GEMM workgroups.
+  GP_TRY(potrf_lockstep<R>(B, r0, n1, all, lane));
+  // L21 = A21 L11^-T       (trsm as a GEMM against the explicit inverse)
+  GP_TRY(product(lane, {n2, n1, n1}, 1.0, plain(blk(all, B.A, r1, r0)), trans(tril(blk(all, B.Li, r0, r0))),
+                 into(blk(all, B.L, r1, r0)), walk(W_TRSM)));
+  // the two products that only need L21 and L11^-1:  A22 -= L21 L21^T (syrk, lower tiles only) for every chain, and
+  // tmp = L21 Li11, the first product of the inverse merge, for the chains in `need`
+  const Operand<R> L21 = plain(blk(all, B.L, r1, r0)), L21t = trans(blk(all, B.L, r1, r0));
+  const Output<R> A22 = into_lower(blk(all, B.A, r1, r1), 1.0);
+  const Operand<R> L21n = plain(blk(need, B.L, r1, r0)), Li11 = plain(tril(blk(need, B.Li, r0, r0)));
+  const Output<R> tmp = into(blk(need, B.Tmp, r1, r0));
+  const Dims syrk{n2, n2, n1}, merge1{n2, n1, n1};
+  // Look-ahead: tmp needs nothing from the second half, so it runs on the context's side stream while that half is
+  // being factored (its leaves are latency-bound and leave the chip to it).  Possible because the leaf shares a CU
+  // with GEMM workgroups.
   hipEvent_t joined = nullptr;
   if (need && B.ctx && B.side_min > 0 && n >= B.side_min && B.ctx->side) {
     gpfit_ctx* c = B.ctx;
@@ -339,47 +296,42 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, hipStre
     joined = next_event();
     GP_HIP(hipEventRecord(fork, s));
     GP_HIP(hipStreamWaitEvent(c->side, fork, 0));
-    GP_TRY(bgemm<R>(B, c->side, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp, off(r1, r0), 0, 0,
-                    1, walks()[1], c->sk_ws[1]));
+    GP_TRY(product(side_lane(c), merge1, 1.0, L21n, Li11, tmp, walk(W_TMP)));
     GP_HIP(hipEventRecord(joined, c->side));
   }
-  // A22 -= L21 L21^T (syrk, lower tiles only).  On the latency-bound levels the first product of the inverse merge,
-  // L21 L11^-1 (it needs L21 and L11^-1 only), rides in the same launch: one launch boundary less per node.
+  // On the latency-bound levels tmp rides in the syrk's launch: one launch boundary less per node.
   bool merged = false;
   if (need && !joined) {
     static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;
-    const GemmArgsT<R> g2 = batch_args<R>(B, all, 0, 0, n2, n2, n1, -1.0, B.L, off(r1, r0), B.L, off(r1, r0), 1.0, B.A, off(r1, r1),
-                                          1, 0, 0, 0);
-    const GemmArgsT<R> g3 = batch_args<R>(B, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp,
-                                          off(r1, r0), 0, 0, 1, walks()[1]);
+    const GemmArgsT<R> g2 = batch_args(lane, syrk, -1.0, L21, L21t, A22);
+    const GemmArgsT<R> g3 = batch_args(lane, merge1, 1.0, L21n, Li11, tmp, walk(W_TMP));
     const GemmRoute pr = no_batch ? GemmRoute{} : gemm_pair_shape(g2, g3);
     if (!no_batch && pr.rc == 0) {
-      if (gemm_log_eval() >= 0 && g_eval_count == gemm_log_eval())
-        fprintf(stderr, "[gpfit gemm] pair: M %d N %d K %d lower 1 nb %d + M %d N %d K %d btri 1 nb %d tile %d flops %.6e\n", g2.M, g2.N,
+      if (gemm_logging()) {
+        fprintf(stderr, "[gpfit gemm] pair: M %d N %d K %d lower 1 nb %d + M %d N %d K %d btri 1 nb %d tile %d flops %.6e", g2.M, g2.N,
                 g2.K, g2.nptr, g3.M, g3.N, g3.K, g3.nptr, pr.tile, gemm_flops(g2, pr.tile) + gemm_flops(g3, pr.tile));
+        gemm_log_tail(" a:", g2, "");
+        gemm_log_tail(" b:", g3, "\n");
+      }
       ProfScope ps(s, g_prof ? gemm_flops(g2, pr.tile) + gemm_flops(g3, pr.tile) : 0.0, 3);
       GP_TRY(launch_gemm_pair(g2, g3, pr, s));
       merged = true;
     }
   }
-  if (!merged)
-    GP_TRY(bgemm<R>(B, s, all, 0, 0, n2, n2, n1, -1.0, B.L, off(r1, r0), B.L, off(r1, r0), 1.0, B.A, off(r1, r1), 1, 0, 0, 0,
-                    B.sk_ws));
-  GP_TRY(potrf_lockstep<R>(B, r1, n2, need | halves, s));
+  if (!merged) GP_TRY(product(lane, syrk, -1.0, L21, L21t, A22));
+  GP_TRY(potrf_lockstep<R>(B, r1, n2, need | halves, lane));
   if (need) {
-    // Li21 = -Li22 * (L21 * Li11)
+    // Li21 = -Li22 (L21 Li11)
     if (joined) GP_HIP(hipStreamWaitEvent(s, joined, 0));
-    else if (!merged)
-      GP_TRY(bgemm<R>(B, s, need, 0, 1, n2, n1, n1, 1.0, B.L, off(r1, r0), B.Li, off(r0, r0), 0.0, B.Tmp, off(r1, r0), 0, 0,
-                      1, walks()[1], B.sk_ws));
-    GP_TRY(bgemm<R>(B, s, need, 0, 1, n2, n1, n2, -1.0, B.Li, off(r1, r1), B.Tmp, off(r1, r0), 0.0, B.Li, off(r1, r0), 0, 1, 0,
-                    walks()[2], B.sk_ws));
+    else if (!merged) GP_TRY(product(lane, merge1, 1.0, L21n, Li11, tmp, walk(W_TMP)));
+    GP_TRY(product(lane, {n2, n1, n2}, -1.0, plain(tril(blk(need, B.Li, r1, r1))), plain(blk(need, B.Tmp, r1, r0)),
+                   into(blk(need, B.Li, r1, r0)), walk(W_MERGE)));
   }
   return 0;
 }
 
-template int potrf_lockstep<double>(const CholBatchT<double>&, int, int, uint32_t, hipStream_t, uint32_t);
-template int potrf_lockstep<float>(const CholBatchT<float>&, int, int, uint32_t, hipStream_t, uint32_t);
+template int potrf_lockstep<double>(const CholBatchT<double>&, int, int, uint32_t, Lane, uint32_t);
+template int potrf_lockstep<float>(const CholBatchT<float>&, int, int, uint32_t, Lane, uint32_t);
 
 // ------------------------------------------------------------------ two-sided triangular product
 // Wout (lower) = 1/2 Li^T Q Li on the n x n diagonal block at r0, Q symmetric (stored in full),
@@ -388,64 +340,66 @@ template int potrf_lockstep<float>(const CholBatchT<float>&, int, int, uint32_t,
 //   W11 = A^T Q11 A + B^T H + H^T B,   W21 = C^T (H + 1/2 Q22 B),   W22 = C^T Q22 C,
 // costs 3/4 n^3 plus the two half-size products (LAPACK's sygst idea), i.e. 13/12 n^3 with
 // one level; blocks of n >= min_split (4096) are split again: 1.02 n^3 at n = 8192.  Z and H are n x n scratch matrices with the same leading dimension.
+// L: the matrix whose 21 block holds the factor's own L21 (two_sided_top only).
 template <typename R>
-struct TwoSidedBufs {
-  const R* Q; const R* Li; R* W; R* Z; R* H; int64_t ld; int min_split;
-  void* sk_ws = nullptr;        // stream-K workspace of this block's launches (nullptr: the main stream's)
-};
-// H = alpha A B + Z ;  Z = H + Z  for cnt problems (A row-major M x K, B k-major K x N with structure b_tri, H and Z
-// M x N): one launch with the dual-update epilogue; where the launch cannot carry it, a copy, the product with
-// beta = 1 and an axpby pass -- the same arithmetic.
+struct TwoSidedBufs { R* Q; const R* Li; R *W, *Z, *H; const R* L; int64_t ld; int min_split; };   // (Q: overwritten by two_sided_top)
+// block (r0[i] + dr, r0[i] + dc) of matrix X of every problem (r0 == nullptr: the blocks sit at the origin)
+template <typename R, typename P>
+static Mat<P> ts_blk(int cnt, const TwoSidedBufs<R>* b, const int* r0, P* TwoSidedBufs<R>::*X, int dr, int dc) {
+  return mats(cnt, b[0].ld, [&](int i) { const int o = r0 ? r0[i] : 0; return b[i].*X + (int64_t)(o + dr) * b[i].ld + o + dc; });
+}
+// H = alpha op(A) op(B) + Z ;  Z = H + Z  for every problem of the list (H and Z M x N): one launch with the dual-update
+// epilogue; where the launch cannot carry it, a copy, the product with beta = 1 and an axpby pass -- the same arithmetic.
 template <typename R>
-static int dual_update_list(hipStream_t s, int cnt, const R* const* Ap, const R* const* Bp, R* const* Hp, R* const* Zp, int M,
-                            int N, int K, double alpha, int64_t ld, int b_tri, int walk, void* sk_ws) {
+static int dual_update_list(Lane lane, Dims d, double alpha, const Operand<R>& a, const Operand<R>& b, const Mat<R>& H,
+                            const Mat<R>& Z, int wk) {
+  const int cnt = H.cnt;
+  const int64_t ld = H.ld;
+  Epilogue<R> e{4};
+  for (int i = 0; i < cnt; ++i) e.aux[i] = Z.p[i];
   // would the fused launch be possible?  (asked first: the unfused route must copy Z into H beforehand)
   bool fused = false;
   if (fused_epilogues() & 4) {
-    GemmArgsT<R> g = gemm_args<R>(0, 1, M, N, K, alpha, Ap[0], ld, Bp[0], ld, 0.0, Hp[0], ld, 0, 0, b_tri, walk, sk_ws);
-    g.epi = 4; g.aux = Zp[0];
+    GemmArgsT<R> g = product_args(lane, d, alpha, a, b, into(H), wk);
+    g.epi = 4; g.aux = Z.p[0];
     static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;
     if (cnt > 1 && gemm_pick_tile(g) != TILE && !no_batch) { g.nptr = cnt; g.batch = cnt; }
     fused = gemm_route(g).epi != 0;
   }
   if (fused) {
-    bool done = false;
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 0.0, ld, 0, 0, b_tri, walk, sk_ws, 4, Zp, nullptr, &done));
-    if (!done) {
+    GP_TRY(product(lane, d, alpha, a, b, into(H), wk, &e));
+    if (!e.carried) {
       set_error("two_sided: the dual-update epilogue was announced but not carried");
       return -100;
     }
     return 0;
   }
   for (int i = 0; i < cnt; ++i)
-    GP_HIP(hipMemcpy2DAsync(Hp[i], (size_t)ld * sizeof(R), Zp[i], (size_t)ld * sizeof(R), (size_t)N * sizeof(R), (size_t)M,
-                            hipMemcpyDeviceToDevice, s));
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Hp, 0, 1, M, N, K, alpha, ld, ld, 1.0, ld, 0, 0, b_tri, walk, sk_ws));
-  for (int i = 0; i < cnt; ++i) GP_TRY(launch_axpby_block<R>(Zp[i], ld, Hp[i], ld, M, N, 1.0, 1.0, s));
+    GP_HIP(hipMemcpy2DAsync(H.p[i], (size_t)ld * sizeof(R), Z.p[i], (size_t)ld * sizeof(R), (size_t)d.N * sizeof(R), (size_t)d.M,
+                            hipMemcpyDeviceToDevice, lane.s));
+  GP_TRY(product(lane, d, alpha, a, b, into(H, 1.0), wk));
+  for (int i = 0; i < cnt; ++i) GP_TRY(launch_axpby_block<R>(Z.p[i], ld, H.p[i], ld, d.M, d.N, 1.0, 1.0, lane.s));
   return 0;
 }
 
 // cnt diagonal blocks of size n (block i of problem b[i] at offset r0[i]) in lock step: the two half-size
 // two-sided products a split leaves behind (W11's A^T Q11 A and W22) depend on nothing else of their level, so
-// they -- and the sub-blocks of several units -- share their launches (gemm_list above): two 2048-sized problems
+// they -- and the sub-blocks of several units -- share their launches (product): two 2048-sized problems
 // are one 128-tile launch of 512 workgroups instead of two 64-tile launches.  Same products, same order per
 // block: bit-identical to the block-by-block recursion.
 template <typename R>
-static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int n, hipStream_t s) {
+static int two_sided_list(Lane lane, int cnt, const TwoSidedBufs<R>* b, const int* r0, int n) {
   if (cnt <= 0) return 0;
-  const int64_t ld = b[0].ld;
-  auto at = [&](const R* base, int r, int c) { return const_cast<R*>(base) + (int64_t)r * ld + c; };
-  const R* Ap[GEMM_MAXB];
-  const R* Bp[GEMM_MAXB];
-  R* Cp[GEMM_MAXB];
+  using TS = TwoSidedBufs<R>;
+  auto blk = [&](auto X, int dr, int dc) { return ts_blk(cnt, b, r0, X, dr, dc); };
   const int k = n / TILE;
   if (n < b[0].min_split || k < 2) {
     static const int wbase_walk = getenv("GPFIT_WBASE_WALK") ? atoi(getenv("GPFIT_WBASE_WALK")) : 0;
-    for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Q, r0[i], r0[i]); Bp[i] = at(b[i].Li, r0[i], r0[i]); Cp[i] = at(b[i].Z, r0[i], r0[i]); }
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n, n, n, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[5], b[0].sk_ws));
-    for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Li, r0[i], r0[i]); Bp[i] = at(b[i].Z, r0[i], r0[i]); Cp[i] = at(b[i].W, r0[i], r0[i]); }
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n, n, n, 0.5, ld, ld, 0.0, ld, 1, 2, 0, wbase_walk, b[0].sk_ws));
-    return 0;
+    // Z = Q Li (Q is symmetric: read k-major) ;  W = 1/2 Li^T Z (lower tiles)
+    GP_TRY(product(lane, {n, n, n}, 1.0, trans(blk(&TS::Q, 0, 0)), plain(tril(blk(&TS::Li, 0, 0))), into(blk(&TS::Z, 0, 0)),
+                   walk(W_RBASE)));
+    return product(lane, {n, n, n}, 0.5, trans(tril(blk(&TS::Li, 0, 0))), plain(blk(&TS::Z, 0, 0)),
+                   into_lower(blk(&TS::W, 0, 0)), wbase_walk);
   }
   const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;
   auto diagonal_blocks = [&]() -> int {
@@ -457,48 +411,25 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
         bb[2 * i] = b[i]; rr[2 * i] = r0[i];
         bb[2 * i + 1] = b[i]; rr[2 * i + 1] = r0[i] + n1;
       }
-      return two_sided_list<R>(2 * cnt, bb, rr, n1, s);
+      return two_sided_list<R>(lane, 2 * cnt, bb, rr, n1);
     }
     for (int i = 0; i < cnt; ++i) rr[i] = r0[i] + n1;
-    GP_TRY(two_sided_list<R>(cnt, b, r0, n1, s));
-    return two_sided_list<R>(cnt, b, rr, n2, s);
+    GP_TRY(two_sided_list<R>(lane, cnt, b, r0, n1));
+    return two_sided_list<R>(lane, cnt, b, rr, n2);
   };
   // Z21 = 1/2 Q22 B
-  for (int i = 0; i < cnt; ++i) {
-    const int r1 = r0[i] + n1;
-    Ap[i] = at(b[i].Q, r1, r1); Bp[i] = at(b[i].Li, r1, r0[i]); Cp[i] = at(b[i].Z, r1, r0[i]);
-  }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 0, 0, 0, b[0].sk_ws));
+  GP_TRY(product(lane, {n2, n1, n2}, 0.5, trans(blk(&TS::Q, n1, n1)), plain(blk(&TS::Li, n1, 0)), into(blk(&TS::Z, n1, 0))));
   // H = Q21 A + Z21 ;  Z21 = H + 1/2 Q22 B
-  {
-    R* Hp[GEMM_MAXB];
-    R* Zp[GEMM_MAXB];
-    for (int i = 0; i < cnt; ++i) {
-      const int r1 = r0[i] + n1;
-      Ap[i] = at(b[i].Q, r1, r0[i]); Bp[i] = at(b[i].Li, r0[i], r0[i]); Hp[i] = at(b[i].H, r1, r0[i]); Zp[i] = at(b[i].Z, r1, r0[i]);
-    }
-    GP_TRY(dual_update_list<R>(s, cnt, Ap, Bp, Hp, Zp, n2, n1, n1, 1.0, ld, 1, walks()[6], b[0].sk_ws));
-  }
+  GP_TRY(dual_update_list(lane, {n2, n1, n1}, 1.0, plain(blk(&TS::Q, n1, 0)), plain(tril(blk(&TS::Li, 0, 0))), blk(&TS::H, n1, 0),
+                          blk(&TS::Z, n1, 0), walk(W_H)));
   // W21 = 1/2 C^T Z21
   static const int w21_walk = getenv("GPFIT_W21_WALK") ? atoi(getenv("GPFIT_W21_WALK")) : 0;
-  for (int i = 0; i < cnt; ++i) {
-    const int r1 = r0[i] + n1;
-    Ap[i] = at(b[i].Li, r1, r1); Bp[i] = at(b[i].Z, r1, r0[i]); Cp[i] = at(b[i].W, r1, r0[i]);
-  }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, b[0].sk_ws));
+  GP_TRY(product(lane, {n2, n1, n2}, 0.5, trans(tril(blk(&TS::Li, n1, n1))), plain(blk(&TS::Z, n1, 0)),
+                 into(blk(&TS::W, n1, 0)), w21_walk));
   GP_TRY(diagonal_blocks());
   // W11 += 1/2 (B^T H + H^T B)   (lower tiles)
-  for (int i = 0; i < cnt; ++i) {
-    const int r1 = r0[i] + n1;
-    Ap[i] = at(b[i].Li, r1, r0[i]); Bp[i] = at(b[i].H, r1, r0[i]); Cp[i] = at(b[i].W, r0[i], r0[i]);
-  }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, b[0].sk_ws));
-  for (int i = 0; i < cnt; ++i) {
-    const int r1 = r0[i] + n1;
-    Ap[i] = at(b[i].H, r1, r0[i]); Bp[i] = at(b[i].Li, r1, r0[i]);
-  }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, 0.5, ld, ld, 1.0, ld, 1, 0, 0, 0, b[0].sk_ws));
-  return 0;
+  GP_TRY(product(lane, {n1, n1, n2}, 0.5, trans(blk(&TS::Li, n1, 0)), plain(blk(&TS::H, n1, 0)), into_lower(blk(&TS::W, 0, 0), 1.0)));
+  return product(lane, {n1, n1, n2}, 0.5, trans(blk(&TS::H, n1, 0)), plain(blk(&TS::Li, n1, 0)), into_lower(blk(&TS::W, 0, 0), 1.0));
 }
 
 // Smallest padded size whose closure works on the top node's blocks (A = L11^-1, C = L22^-1 and L21) instead of the
@@ -518,7 +449,7 @@ static int two_sided_list(int cnt, const TwoSidedBufs<R>* b, const int* r0, int 
 constexpr int TOP_BLOCKS_MIN = 2048, TOP_BLOCKS_MIN_F32 = 5120;
 static bool top_in_blocks(int np, size_t elem_bytes) { return np >= (elem_bytes == 4 ? TOP_BLOCKS_MIN_F32 : TOP_BLOCKS_MIN); }
 
-// The top level of W = 1/2 L^-T Q L^-1 for cnt units, written with the factor's own off-diagonal block L21 (Lf[i]: the
+// The top level of W = 1/2 L^-T Q L^-1 for cnt units, written with the factor's own off-diagonal block L21 (b[i].L: the
 // matrix whose 21 block holds it) and the inverses A = L11^-1, C = L22^-1 of the diagonal halves: the closure never
 // forms [L^-1]21 = -C L21 A (potrf_lockstep's `halves`).  With R = C^T Q21:
 //   W22 = 1/2 C^T Q22 C                    two_sided_list on the block, then completed in both triangles
@@ -529,39 +460,34 @@ static bool top_in_blocks(int np, size_t elem_bytes) { return np >= (elem_bytes 
 // The same flops as the split with the explicit [L^-1]21 (two_sided_list); W11 needs W22, so the two diagonal blocks
 // of this level do not share launches.  No step reads a block an earlier step of the stage has overwritten.
 template <typename R>
-static int two_sided_top(int cnt, const TwoSidedBufs<R>* b, const R* const* Lf, int n, hipStream_t s) {
+static int two_sided_top(Lane lane, int cnt, const TwoSidedBufs<R>* b, int n) {
   if (cnt <= 0) return 0;
+  using TS = TwoSidedBufs<R>;
+  const hipStream_t s = lane.s;
   const int64_t ld = b[0].ld;
-  auto at = [&](const R* base, int r, int c) { return const_cast<R*>(base) + (int64_t)r * ld + c; };
+  auto blk = [&](auto X, int r, int c) { return ts_blk(cnt, b, (const int*)nullptr, X, r, c); };
   int rr[GEMM_MAXB];
   const int k = n / TILE;
   const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;   // (top_in_blocks: both halves exist)
-  const R* Ap[GEMM_MAXB];
-  const R* Bp[GEMM_MAXB];
-  R* Cp[GEMM_MAXB];
-  R* Zp[GEMM_MAXB];
-  void* sk = b[0].sk_ws;
   for (int i = 0; i < cnt; ++i) rr[i] = n1;
-  GP_TRY(two_sided_list<R>(cnt, b, rr, n2, s));
-  for (int i = 0; i < cnt; ++i) GP_TRY(launch_symmetrize(at(b[i].W, n1, n1), ld, n2, s));
+  GP_TRY(two_sided_list<R>(lane, cnt, b, rr, n2));
+  for (int i = 0; i < cnt; ++i) GP_TRY(launch_symmetrize(b[i].W + (int64_t)n1 * ld + n1, ld, n2, s));
   // Z21 = 1/2 C^T Q21
   static const int w21_walk = getenv("GPFIT_W21_WALK") ? atoi(getenv("GPFIT_W21_WALK")) : 0;
-  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Li, n1, n1); Bp[i] = at(b[i].Q, n1, 0); Cp[i] = at(b[i].Z, n1, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n2, n1, n2, 0.5, ld, ld, 0.0, ld, 0, 2, 0, w21_walk, sk));
+  GP_TRY(product(lane, {n2, n1, n2}, 0.5, trans(tril(blk(&TS::Li, n1, n1))), plain(blk(&TS::Q, n1, 0)),
+                 into(blk(&TS::Z, n1, 0)), w21_walk));
   // H = -W22 L21 + Z21 ;  Z21 = J = H + Z21
-  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].W, n1, n1); Bp[i] = at(Lf[i], n1, 0); Cp[i] = at(b[i].H, n1, 0); Zp[i] = at(b[i].Z, n1, 0); }
-  GP_TRY(dual_update_list<R>(s, cnt, Ap, Bp, Cp, Zp, n2, n1, n2, -1.0, ld, 0, 0, sk));
+  GP_TRY(dual_update_list(lane, {n2, n1, n2}, -1.0, plain(blk(&TS::W, n1, n1)), plain(blk(&TS::L, n1, 0)), blk(&TS::H, n1, 0),
+                          blk(&TS::Z, n1, 0), 0));
   // W21 = H A
-  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].H, n1, 0); Bp[i] = at(b[i].Li, 0, 0); Cp[i] = at(b[i].W, n1, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, 1.0, ld, ld, 0.0, ld, 0, 0, 1, walks()[6], sk));
+  GP_TRY(product(lane, {n2, n1, n1}, 1.0, plain(blk(&TS::H, n1, 0)), plain(tril(blk(&TS::Li, 0, 0))), into(blk(&TS::W, n1, 0)),
+                 walk(W_H)));
   // M = Q11 - L21^T J - J^T L21   (lower tiles, then both triangles: the block products below read M in full)
-  for (int i = 0; i < cnt; ++i) { Ap[i] = at(Lf[i], n1, 0); Bp[i] = at(b[i].Z, n1, 0); Cp[i] = at(b[i].Q, 0, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, sk));
-  for (int i = 0; i < cnt; ++i) { Ap[i] = at(b[i].Z, n1, 0); Bp[i] = at(Lf[i], n1, 0); }
-  GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 1, 1, n1, n1, n2, -1.0, ld, ld, 1.0, ld, 1, 0, 0, 0, sk));
-  for (int i = 0; i < cnt; ++i) GP_TRY(launch_symmetrize(Cp[i], ld, n1, s));
+  GP_TRY(product(lane, {n1, n1, n2}, -1.0, trans(blk(&TS::L, n1, 0)), plain(blk(&TS::Z, n1, 0)), into_lower(blk(&TS::Q, 0, 0), 1.0)));
+  GP_TRY(product(lane, {n1, n1, n2}, -1.0, trans(blk(&TS::Z, n1, 0)), plain(blk(&TS::L, n1, 0)), into_lower(blk(&TS::Q, 0, 0), 1.0)));
+  for (int i = 0; i < cnt; ++i) GP_TRY(launch_symmetrize(b[i].Q, ld, n1, s));
   for (int i = 0; i < cnt; ++i) rr[i] = 0;
-  return two_sided_list<R>(cnt, b, rr, n1, s);
+  return two_sided_list<R>(lane, cnt, b, rr, n1);
 }
 
 // ------------------------------------------------------------------ host pieces of localker
@@ -651,9 +577,9 @@ static R* ws_as(double* b) { return reinterpret_cast<R*>(b); }  // the workspace
 // utils.py:2020-2028: out-of-box theta -> infinite loss and infinite gradients
 static void fill_out_of_box(double* out) {
   const double inf = std::numeric_limits<double>::infinity();
-  out[0] = inf;
-  out[1] = out[2] = std::numeric_limits<double>::quiet_NaN();
-  for (int i = 0; i < 6; ++i) out[3 + i] = inf;
+  out[OUT_LOSS] = inf;
+  out[OUT_LOGLIK] = out[OUT_KL] = std::numeric_limits<double>::quiet_NaN();
+  for (int i = 0; i < 6; ++i) out[OUT_GRAD + i] = inf;
 }
 
 // Admission of one evaluation to context c: the limits (lower / upper may be absent), the capacity for np padded
@@ -688,11 +614,13 @@ static int build_metric(gpfit_ctx* c, hipStream_t s, const Theta& th, int d, int
 }
 // one set of n stimuli: masked and k-major in Xt [dp][np], row-major in Xm [np][dp], C Xt, and Kvec / q
 template <typename R>
-static int kernel_side(gpfit_ctx* c, hipStream_t s, const R* X, int64_t ldx, int n, int np, int d, int dp, double s0sq,
+static int kernel_side(gpfit_ctx* c, Lane lane, const R* X, int64_t ldx, int n, int np, int d, int dp, double s0sq,
                        R* Xt, R* XCt, R* Xm, R* Kvec, R* q) {
   const int64_t ld = np;
+  const hipStream_t s = lane.s;
   GP_TRY(launch_gather(X, ldx, n, c->pix, d, dp, np, Xt, ld, Xm, dp, s));
-  GP_TRY(gemm<R>(s, 1, 1, dp, np, dp, 1.0, ws_as<R>(c->Cmat), dp, Xt, ld, 0.0, XCt, ld, 0, 0, 0));
+  // C X^T (C is symmetric: read k-major)
+  GP_TRY(product(lane, {dp, np, dp}, 1.0, trans(mat(ws_as<R>(c->Cmat), dp)), plain(mat(Xt, ld)), into(mat(XCt, ld))));
   return launch_qvec(Xt, XCt, ld, dp, n, np, s0sq, Kvec, q, s);
 }
 // K~ = acosker(x, x) with its cosine matrix: lower tiles, identity on the padding.  mirror: the tiles also store
@@ -711,11 +639,12 @@ static int gram_square(hipStream_t s, const R* XCt, const R* Xt, const R* q, R* 
 }
 // the kernel objects of one set of stimuli in the context's own buffers: Cmat, Xt, XCt, Xm, Kvec, q, Kbuf, Cos
 template <typename R>
-static int build_kernel(gpfit_ctx* c, hipStream_t s, const Theta& th, int d, int dp, int n_rows, int n_cols, const R* X,
+static int build_kernel(gpfit_ctx* c, Lane lane, const Theta& th, int d, int dp, int n_rows, int n_cols, const R* X,
                         int64_t ldx, int n, int np, int mirror) {
   const double s0sq = th.sigma0 * th.sigma0;
+  const hipStream_t s = lane.s;
   GP_TRY(build_metric<R>(c, s, th, d, dp, n_rows, n_cols));
-  GP_TRY(kernel_side<R>(c, s, X, ldx, n, np, d, dp, s0sq, ws_as<R>(c->Xt), ws_as<R>(c->XCt), ws_as<R>(c->Xm),
+  GP_TRY(kernel_side<R>(c, lane, X, ldx, n, np, d, dp, s0sq, ws_as<R>(c->Xt), ws_as<R>(c->XCt), ws_as<R>(c->Xm),
                         ws_as<R>(c->Kvec), ws_as<R>(c->q)));
   return gram_square<R>(s, ws_as<R>(c->XCt), ws_as<R>(c->Xt), ws_as<R>(c->q), ws_as<R>(c->Kbuf), ws_as<R>(c->Cos), n, np,
                         dp, s0sq, mirror);
@@ -732,7 +661,7 @@ static int solve_mean(gpfit_ctx* c, int np, bool blocks, hipStream_t s) {
   R *m = ws_as<R>(c->mpad), *y = ws_as<R>(c->yv), *b = ws_as<R>(c->bv);
   if (!blocks) {
     GP_TRY(launch_trmv_lower(ws_as<R>(c->Libuf), ld, np, m, y, s));
-    GP_TRY(launch_dot(y, y, np, c->scal + 6, s));
+    GP_TRY(launch_dot(y, y, np, c->scal + S_MKM, s));
     return launch_trmv_lower_t(ws_as<R>(c->Libuf), ld, np, y, b, c->trmv_part, s);
   }
   const int kt = np / TILE, n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;   // potrf_lockstep's split of the top node
@@ -740,7 +669,7 @@ static int solve_mean(gpfit_ctx* c, int np, bool blocks, hipStream_t s) {
   GP_TRY(launch_trmv_lower(A, ld, n1, m, y, s));
   GP_TRY(launch_gemv_sub(L21, ld, n2, n1, y, m + n1, b + n1, s));
   GP_TRY(launch_trmv_lower(C, ld, n2, b + n1, y + n1, s));
-  GP_TRY(launch_dot(y, y, np, c->scal + 6, s));
+  GP_TRY(launch_dot(y, y, np, c->scal + S_MKM, s));
   GP_TRY(launch_trmv_lower_t(C, ld, n2, y + n1, b + n1, c->trmv_part, s));
   GP_TRY(launch_gemv_t_sub(L21, ld, n2, n1, b + n1, y, b, c->trmv_part, s));
   return launch_trmv_lower_t(A, ld, n1, b, b, c->trmv_part, s);
@@ -749,14 +678,14 @@ static int solve_mean(gpfit_ctx* c, int np, bool blocks, hipStream_t s) {
 // ---- pull-back of an n x n adjoint to the d x d metric
 // Adjoint pass over the lower tiles of W: Lambda = tril(A_w, -1) + 1/2 diag(A_w) into the lower 64-tiles of A (zeros
 // above the diagonal inside the diagonal tiles; the tiles above it are neither written here nor read by
-// lambda_t_x_list), t into tvec, the sums into scal[7..9].
+// lambda_t_x_list), t into tvec, the sums into scal[S_ADJ..].
 template <typename R>
 static int adjoint_pass(gpfit_ctx* c, hipStream_t s, const R* W, const R* Cos, const R* bv, const R* q, const R* wl, int n,
                         int np, R* A, R* tvec) {
   GP_TRY(launch_adjoint(W, Cos, (int64_t)np, bv, q, n, np, A, c->upart, c->vpart, c->sumA_part, s));
   const int t64 = np / 64;
   return launch_adjoint_reduce(c->upart, c->vpart, c->sumA_part, t64, t64 * (t64 + 1) / 2, q, wl, n, np, tvec, c->rpad,
-                               c->scal + 7, s);
+                               c->scal + S_ADJ, s);
 }
 // out [dp][dp] = Xa^T Yb over np rows: split-k into the slabs of Mpart, added in slab order; sym: out = G + G^T with
 // G that sum (the same pass: no extra launch).  prof: the product is
@@ -764,12 +693,10 @@ static int adjoint_pass(gpfit_ctx* c, hipStream_t s, const R* W, const R* Cos, c
 // truncated-rank closures' profiles never counted theirs, and their launch counts stay as they were.
 template <typename R>
 static int xty(gpfit_ctx* c, hipStream_t s, const R* Xa, const R* Yb, int np, int dp, R* out, bool prof, bool sym = false) {
-  GemmArgsT<R> g{};
-  g.A = Xa; g.B = Yb; g.C = ws_as<R>(c->Mpart);
-  g.lda = dp; g.ldb = dp; g.ldc = dp;
-  g.M = dp; g.N = dp; g.K = np;
-  g.alpha = 1.0; g.beta = 0.0; g.a_kmajor = 1; g.b_kmajor = 1;
-  g.batch = 1; g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
+  // (no workspace, as ever: gemm_route keeps a split_k > 1 launch off the stream-K schedule, so none is ever read)
+  GemmArgsT<R> g = product_args(Lane{s, nullptr}, {dp, dp, np}, 1.0, trans(mat(Xa, dp)), plain(mat(Yb, dp)),
+                                into(mat(ws_as<R>(c->Mpart), dp)));
+  g.split_k = c->split_k_M; g.sC = (int64_t)dp * dp;
   const GemmRoute r = gemm_route(g);
   if (prof) {
     ProfScope ps(s, g_prof ? gemm_flops(g, r.tile) : 0.0, (g_prof && r.tile != TILE) ? 3 : 0);
@@ -793,36 +720,32 @@ static int pullback_slabs(int np, int dp) {
 // Y[i] = Lambda[i]^T Xm[i] for cnt units of one shape (np a multiple of 64): Lambda is read k-major as A_w was, so
 // op(A) is upper triangular (a_tri 2) and the launch walks each row panel's own k range only, cut into
 // (panel, slab) items of roughly equal length.  One launch -- a pointer batch for cnt > 1 -- then per unit the sum
-// of each row's live slabs, in slab order (no atomics).  scratch[i]: np x np elements, idle (Z behind W).
+// of each row's live slabs, in slab order (no atomics).  a = Lambda^T, b = Xm; scratch: np x np elements each, idle (Z behind W).
 template <typename R>
-static int lambda_t_x_list(hipStream_t s, int cnt, const R* const* Lam, const R* const* Xm, R* const* Y, R* const* scratch,
-                           int np, int dp) {
+static int lambda_t_x_list(Lane lane, const Operand<R>& a, const Operand<R>& b, const Mat<R>& Y, const Mat<R>& scratch, int np, int dp) {
+  const int cnt = Y.cnt;
   if (cnt <= 0 || cnt > GEMM_MAXB) return cnt == 0 ? 0 : -3;
   const int slabs = pullback_slabs(np, dp);
   const SlabPlan sp = slab_plan(np, slabs);
   const bool direct = sp.live == 1;   // one slab: straight into Y
-  GemmArgsT<R> g = gemm_args<R>(1, 1, np, dp, np, 1.0, Lam[0], np, Xm[0], dp, 0.0, direct ? Y[0] : scratch[0], dp, 0, 2, 0);
+  const Output<R> c = into(direct ? Y : scratch);
+  GemmArgsT<R> g = cnt > 1 ? batch_args(lane, {np, dp, np}, 1.0, a, b, c) : product_args(lane, {np, dp, np}, 1.0, a, b, c);
   g.k_slabs = slabs;
   g.sC = (int64_t)np * dp;
-  if (cnt > 1) {
-    g.nptr = cnt;
-    g.batch = cnt;
-    for (int i = 0; i < cnt; ++i) { g.Ap[i] = Lam[i]; g.Bp[i] = Xm[i]; g.Cp[i] = direct ? Y[i] : scratch[i]; }
-  }
-  GP_TRY(run_gemm(s, g));
+  GP_TRY(run_gemm(lane.s, g));
   if (direct) return 0;
   for (int i = 0; i < cnt; ++i)
-    GP_TRY(launch_reduce_slabs(scratch[i], (int64_t)np * dp, sp.live, sp.ks * SLAB_TILE, Y[i], np, dp, s));
+    GP_TRY(launch_reduce_slabs(scratch.p[i], (int64_t)np * dp, sp.live, sp.ks * SLAB_TILE, Y.p[i], np, dp, lane.s));
   return 0;
 }
 // Mmat = Xm^T (A_w + diag t) Xm for the adjoint W of acosker(x, x) on n stimuli (q, Cos, Xm theirs; A, scratch:
 // np x np work matrices), with the b b^T and dKvec terms the caller left in bv / wl.  The contraction with dC_p
 // (launch_metric_contract) is the caller's: the sparse closure adds two more d x d matrices first.
-static int pullback_to_metric(gpfit_ctx* c, hipStream_t s, const double* W, const double* Cos, const double* q, int n,
+static int pullback_to_metric(gpfit_ctx* c, Lane lane, const double* W, const double* Cos, const double* q, int n,
                               int np, int dp, double* A, const double* Xm, double* scratch) {
+  const hipStream_t s = lane.s;
   GP_TRY(adjoint_pass<double>(c, s, W, Cos, c->bv, q, c->wl, n, np, A, c->tvec));
-  const double* Ac = A;
-  GP_TRY(lambda_t_x_list<double>(s, 1, &Ac, &Xm, &c->Ybuf, &scratch, np, dp));
+  GP_TRY(lambda_t_x_list(lane, trans(tril(mat(A, np))), plain(mat(Xm, dp)), mat(c->Ybuf, dp), mat(scratch, dp), np, dp));
   GP_TRY(launch_rowscale_add(c->Ybuf, dp, Xm, dp, c->tvec, np, dp, s, 0.5));
   return xty<double>(c, s, Xm, c->Ybuf, np, dp, c->Mmat, false, true);
 }
@@ -832,76 +755,77 @@ static int pullback_to_metric(gpfit_ctx* c, hipStream_t s, const double* W, cons
 // K~_b (packed into S1) = L L^T with L^-1 (utils.py:2067) and V_b (packed into Va) = L_V L_V^T (log|V_b|, :1326) in
 // lock step, the V_b chain in the caller's four work matrices; then K~_b^-1 = L^-T L^-1 in S1 and V_b in S2, both
 // stored in full with the identity on the padding.
-static int projected_factor(gpfit_ctx* c, hipStream_t s, const double* V_b, int64_t ldvb, int nk, int nb, double* Va,
+static int projected_factor(gpfit_ctx* c, Lane lane, const double* V_b, int64_t ldvb, int nk, int nb, double* Va,
                             double* Vl, double* Vli, double* Vt) {
   double *S1 = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;
   const int64_t lb = nb;
+  const hipStream_t s = lane.s;
   CholBatchT<double> cb;
   cb.nb = 2;
-  cb.A[0] = S1; cb.L[0] = S2; cb.Li[0] = S3; cb.Tmp[0] = S4; cb.info[0] = c->info + 0;
-  cb.A[1] = Va; cb.L[1] = Vl; cb.Li[1] = Vli; cb.Tmp[1] = Vt; cb.info[1] = c->info + 1;
-  cb.ld = lb; cb.sk_ws = c->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
-  GP_TRY(potrf_lockstep<double>(cb, 0, nb, 1u, s));
-  GP_TRY(launch_logdet(Vl, lb, nk, c->scal + 40, s));
-  GP_TRY(launch_logdet(S2, lb, nk, c->scal + 3, s));
-  GP_TRY(gemm<double>(s, 1, 1, nb, nb, nb, 1.0, S3, lb, S3, lb, 0.0, S1, lb, 1, 2, 1));
+  cb.A[0] = S1; cb.L[0] = S2; cb.Li[0] = S3; cb.Tmp[0] = S4; cb.info[0] = c->info + INFO_K;
+  cb.A[1] = Va; cb.L[1] = Vl; cb.Li[1] = Vli; cb.Tmp[1] = Vt; cb.info[1] = c->info + INFO_V;
+  cb.ld = lb; cb.ctx = nullptr; cb.side_min = 0;
+  GP_TRY(potrf_lockstep<double>(cb, 0, nb, 1u, lane));
+  GP_TRY(launch_logdet(Vl, lb, nk, c->scal + S_LOGDET_V, s));
+  GP_TRY(launch_logdet(S2, lb, nk, c->scal + S_LOGDET_K, s));
+  GP_TRY(product(lane, {nb, nb, nb}, 1.0, trans(tril(mat(S3, lb))), plain(tril(mat(S3, lb))), into_lower(mat(S1, lb))));   // L^-T L^-1
   GP_TRY(launch_symmetrize(S1, lb, nb, s));
   GP_TRY(launch_pack_lower(V_b, ldvb, nk, S2, lb, nb, s));
   return launch_symmetrize(S2, lb, nb, s);
 }
-// K~_b^-1 V_b in S3, its trace tr(K~_b^-1 V_b) in scal[5], P1 = K~_b^-1 V_b K~_b^-1 in S4.  (The two closures form
+// K~_b^-1 V_b in S3, its trace tr(K~_b^-1 V_b) in scal[S_TRACE], P1 = K~_b^-1 V_b K~_b^-1 in S4.  (The two closures form
 // a V_b on different sides of this stage, and b = K~_b^-1 m_b behind it.)
-static int projected_kl_products(gpfit_ctx* c, hipStream_t s, int nk, int nb) {
+static int projected_kl_products(gpfit_ctx* c, Lane lane, int nk, int nb) {
   double *Ki = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;
   const int64_t lb = nb;
-  GP_TRY(gemm<double>(s, 0, 1, nb, nb, nb, 1.0, Ki, lb, S2, lb, 0.0, S3, lb, 0, 0, 0));
-  GP_TRY(launch_proj_trace(S3, lb, nk, c->scal + 5, s));
-  return gemm<double>(s, 0, 1, nb, nb, nb, 1.0, S3, lb, Ki, lb, 0.0, S4, lb, 0, 0, 0);
+  GP_TRY(product(lane, {nb, nb, nb}, 1.0, plain(mat(Ki, lb)), plain(mat(S2, lb)), into(mat(S3, lb))));
+  GP_TRY(launch_proj_trace(S3, lb, nk, c->scal + S_TRACE, lane.s));
+  return product(lane, {nb, nb, nb}, 1.0, plain(mat(S3, lb)), plain(mat(Ki, lb)), into(mat(S4, lb)));
 }
 
 // ---- host assembly of an evaluation's 16 output scalars from the device scalars (c->scal_host, c->info_host)
 // the part of the sigma_0 row every closure has, derived from utils.py:996-1004 / 1036
-static double sigma0_row_metric(const double* sc, double sigma0) { return sigma0 * (2.0 * sc[9] + 2.0 * sc[7]); }
+static double sigma0_row_metric(const double* sc, double sigma0) { return sigma0 * (2.0 * sc[S_ADJ_SUMA] + 2.0 * sc[S_ADJ]); }
 // d(loss)/d(theta) = dKL - dL (utils.py:2097-2099): the metric rows come from the contraction, the sigma_0 row in
 // closed form from the caller
 static void grad_rows(const double* sc, double sigma0_row, double* g6) {
   g6[0] = sigma0_row;
-  g6[1] = sc[13];  // eps_0x
-  g6[2] = sc[14];  // eps_0y
-  g6[3] = sc[11];  // -2log2beta
-  g6[4] = sc[12];  // -log2rho2
-  g6[5] = sc[10];  // Amp
+  g6[1] = sc[S_D_EPSX];
+  g6[2] = sc[S_D_EPSY];
+  g6[3] = sc[S_D_BETA];
+  g6[4] = sc[S_D_RHO];
+  g6[5] = sc[S_D_AMP];
 }
-// pad: what the identity padding of both factors contributes to scal[5] = ||L^-1 L_V||_F^2 (np - n for the full-rank
+// pad: what the identity padding of both factors contributes to scal[S_TRACE] = ||L^-1 L_V||_F^2 (np - n for the full-rank
 // unit, whose trace is that norm; 0 for the truncated-rank closures, whose trace kernel stops at n_kept).
 // err_K / err_V: the messages of the two Cholesky failures, whose LAPACK info is the return value.
 static int assemble_out(gpfit_ctx* c, double A, double lambda0, double sigma0_row, int pad, int d, int want_grad,
                         const char* err_K, const char* err_V, double* out_host) {
   const double* sc = c->scal_host;
-  const double loglik = A * sc[0] + lambda0 * sc[1] - sc[2];                   // utils.py:1243
-  const double trKinvV = sc[5] - (double)pad;
-  const double logdetV = sc[40];
-  const double KL = -0.5 * logdetV + 0.5 * sc[3] + 0.5 * sc[6] + 0.5 * trKinvV;  // utils.py:1326
-  out_host[0] = -(loglik - KL);                                                // utils.py:2087-2089
-  out_host[1] = loglik;
-  out_host[2] = KL;
-  if (want_grad) grad_rows(sc, sigma0_row, out_host + 3);
+  const double loglik = A * sc[S_RLAM] + lambda0 * sc[S_SUMR] - sc[S_SUMF];      // utils.py:1243
+  const double trKinvV = sc[S_TRACE] - (double)pad;
+  const double logdetV = sc[S_LOGDET_V];
+  const double KL = -0.5 * logdetV + 0.5 * sc[S_LOGDET_K] + 0.5 * sc[S_MKM] + 0.5 * trKinvV;  // utils.py:1326
+  out_host[OUT_LOSS] = -(loglik - KL);                                           // utils.py:2087-2089
+  out_host[OUT_LOGLIK] = loglik;
+  out_host[OUT_KL] = KL;
+  if (want_grad) grad_rows(sc, sigma0_row, out_host + OUT_GRAD);
   else
-    for (int i = 0; i < 6; ++i) out_host[3 + i] = 0.0;
-  out_host[9] = sc[3];
-  out_host[10] = logdetV;
-  out_host[11] = trKinvV;
-  out_host[12] = sc[6];
-  out_host[13] = (double)d;
-  out_host[14] = (double)c->info_host[0];
-  out_host[15] = (double)c->info_host[1];
-  if (c->info_host[0] != 0) {
+    for (int i = 0; i < 6; ++i) out_host[OUT_GRAD + i] = 0.0;
+  out_host[OUT_LOGDET_K] = sc[S_LOGDET_K];
+  out_host[OUT_LOGDET_V] = logdetV;
+  out_host[OUT_TRACE] = trKinvV;
+  out_host[OUT_MKM] = sc[S_MKM];
+  out_host[OUT_D] = (double)d;
+  out_host[OUT_INFO_K] = (double)c->info_host[INFO_K];
+  out_host[OUT_INFO_V] = (double)c->info_host[INFO_V];
+  if (c->info_host[INFO_K] != 0) {
     set_error(err_K);
-    return c->info_host[0];
+    return c->info_host[INFO_K];
   }
-  if (c->info_host[1] != 0) {
+  if (c->info_host[INFO_V] != 0) {
     set_error(err_V);
-    return c->info_host[1];
+    return c->info_host[INFO_V];
   }
   return 0;
 }
@@ -960,45 +884,50 @@ static int demote_for_mixed(gpfit_ctx* c, bool reuse_V, int np, int dp, bool blo
 // The tiles leave their sums of squares behind (no separate pass over T) where a launch can carry the epilogue;
 // whether it is asked to depends on the single unit's launch only, so a group sums the norm in the unit's order.
 template <typename R>
-static int t_in_blocks(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int np, hipStream_t s) {
+static int t_in_blocks(Lane lane, int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int np) {
+  using PJ = PostJoin<R>;
   const int64_t ld = np;
-  const R* Ap[GEMM_MAXB];
-  const R* Bp[GEMM_MAXB];
-  R* Cp[GEMM_MAXB];
-  R* Tp[GEMM_MAXB];
-  double* Sp[GEMM_MAXB];
+  const hipStream_t s = lane.s;
   const int kt = np / TILE, n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;   // potrf_lockstep's split of the top node
+  const int64_t o21 = (int64_t)n1 * ld;
   int ent = 0;   // entries of frob_part written so far (the same for every unit)
   // blocks whose launch cannot carry the norm get a pass of their own -- unless no launch of the unit carries it
   // (all on small tiles): then ONE pass over T's lower tiles, which are exactly the tiles of the three blocks
-  auto asks = [&](int M, int Nn, int K, int lower, int a_tri, int b_tri, int walk) {
-    GemmArgsT<R> g1 = gemm_args<R>(0, 1, M, Nn, K, 1.0, a[0].Li, ld, a[0].LV, ld, 0.0, a[0].T, ld, lower, a_tri, b_tri, walk, cs[0]->sk_ws[0]);
+  const auto Li0 = tril(mat(a[0].Li, ld)), LV0 = mat(a[0].LV, ld);   // the first unit's, for the probe
+  const Mat<R> T0 = mat(a[0].T, ld);
+  auto asks = [&](Dims d, const Operand<R>& LV, const Output<R>& out, int wk) {   // op(A) is a lower block of L^-1 in all three
+    GemmArgsT<R> g1 = product_args(lane, d, 1.0, plain(Li0), LV, out, wk);
     g1.epi = 2; g1.sumsq = cs[0]->frob_part;
     return (fused_epilogues() & 2) ? gemm_route(g1).sumsq_entries : 0;
   };
-  const bool any_fused = asks(n1, n1, n1, 1, 1, 1, walks()[3]) > 0 || asks(n2, n2, n2, 1, 1, 1, walks()[3]) > 0 ||
-                         asks(n2, n1, n2, 0, 1, 0, walks()[2]) > 0;
+  auto asks_diag = [&](int nblk) { return asks({nblk, nblk, nblk}, plain(tril(LV0)), into_lower(T0), walk(W_T)); };
+  auto asks_21 = [&]() { return asks({n2, n1, n2}, plain(LV0), into(T0), walk(W_MERGE)); };
+  const bool any_fused = asks_diag(n1) > 0 || asks_diag(n2) > 0 || asks_21() > 0;
+  // the product into T's blocks `out` with the tile norms asked for (e entries per problem, from sums[q] on) or passed
+  // over afterwards
+  auto normed_product = [&](Dims d, const Operand<R>& A, const Operand<R>& B, const Output<R>& out, int wk, bool ask, Epilogue<R>& e,
+                            const char* what) -> int {
+    e.which = ask ? 2 : 0;
+    GP_TRY(product(lane, d, 1.0, A, B, out, wk, &e));
+    if (e.carried != ask) {
+      set_error(std::string("post_join: the tile-norm epilogue of ") + what + " was announced but not carried");
+      return -100;
+    }
+    if (!e.carried && any_fused)
+      for (int q = 0; q < out.m.cnt; ++q) GP_TRY(launch_frob_tiles<R>(out.m.p[q], ld, d.M, d.N, out.lower ? 1 : 0, e.sumsq[q], s));
+    return 0;
+  };
   // one list of lower x lower blocks: cb blocks (at rb[], all of size nblk) per unit
   auto diag_blocks = [&](int cb, const int* rb, int nblk) -> int {
     const int tb = nblk / TILE;
-    int e = asks(nblk, nblk, nblk, 1, 1, 1, walks()[3]);
+    int e = asks_diag(nblk);
     const bool ask = e > 0;
     if (!ask) e = tb * (tb + 1) / 2;
-    int m = 0;
-    for (int i = 0; i < cnt; ++i)
-      for (int j = 0; j < cb; ++j, ++m) {
-        const int64_t o = (int64_t)rb[j] * ld + rb[j];
-        Ap[m] = a[i].Li + o; Bp[m] = a[i].LV + o; Tp[m] = a[i].T + o; Sp[m] = cs[i]->frob_part + ent + j * e;
-      }
-    bool normed = false;
-    GP_TRY(gemm_list<R>(s, m, Ap, Bp, Tp, 0, 1, nblk, nblk, nblk, 1.0, ld, ld, 0.0, ld, 1, 1, 1, walks()[3], cs[0]->sk_ws[0],
-                        ask ? 2 : 0, nullptr, Sp, &normed));
-    if (normed != ask) {
-      set_error("post_join: the tile-norm epilogue of a diagonal block of T was announced but not carried");
-      return -100;
-    }
-    if (!normed && any_fused)
-      for (int q = 0; q < m; ++q) GP_TRY(launch_frob_tiles<R>(Tp[q], ld, nblk, nblk, 1, Sp[q], s));
+    auto blk = [&](auto X) { return mats(cnt * cb, ld, [&](int q) { return a[q / cb].*X + (int64_t)rb[q % cb] * (ld + 1); }); };
+    Epilogue<R> ep{};
+    for (int q = 0; q < cnt * cb && q < GEMM_MAXB; ++q) ep.sumsq[q] = cs[q / cb]->frob_part + ent + (q % cb) * e;
+    GP_TRY(normed_product({nblk, nblk, nblk}, plain(tril(blk(&PJ::Li))), plain(tril(blk(&PJ::LV))), into_lower(blk(&PJ::T)),
+                          walk(W_T), ask, ep, "a diagonal block of T"));
     ent += cb * e;
     return 0;
   };
@@ -1009,67 +938,56 @@ static int t_in_blocks(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, int 
     GP_TRY(diag_blocks(1, r_both + 1, n2));
   }
   {
-    const int64_t o21 = (int64_t)n1 * ld;
-    for (int i = 0; i < cnt; ++i) {
+    auto blk = [&](auto X, int64_t o) { return mats(cnt, ld, [&](int i) { return a[i].*X + o; }); };
+    for (int i = 0; i < cnt; ++i)
       GP_HIP(hipMemcpy2DAsync(a[i].Z + o21, (size_t)ld * sizeof(R), a[i].LV + o21, (size_t)ld * sizeof(R), (size_t)n1 * sizeof(R),
                               (size_t)n2, hipMemcpyDeviceToDevice, s));
-      Ap[i] = a[i].L + o21; Bp[i] = a[i].T; Cp[i] = a[i].Z + o21;
-    }
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, n2, n1, n1, -1.0, ld, ld, 1.0, ld, 0, 0, 1, walks()[1], cs[0]->sk_ws[0]));
-    int e = asks(n2, n1, n2, 0, 1, 0, walks()[2]);
+    // S = LV21 - L21 T11 (in Z's 21 block) ;  T21 = C S
+    GP_TRY(product(lane, {n2, n1, n1}, -1.0, plain(blk(&PJ::L, o21)), plain(tril(blk(&PJ::T, 0))), into(blk(&PJ::Z, o21), 1.0),
+                   walk(W_TMP)));
+    int e = asks_21();
     const bool ask = e > 0;
     if (!ask) e = (n2 / TILE) * (n1 / TILE);
-    for (int i = 0; i < cnt; ++i) {
-      Ap[i] = a[i].Li + o21 + n1; Bp[i] = a[i].Z + o21; Tp[i] = a[i].T + o21; Sp[i] = cs[i]->frob_part + ent;
-    }
-    bool normed = false;
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Tp, 0, 1, n2, n1, n2, 1.0, ld, ld, 0.0, ld, 0, 1, 0, walks()[2], cs[0]->sk_ws[0],
-                        ask ? 2 : 0, nullptr, Sp, &normed));
-    if (normed != ask) {
-      set_error("post_join: the tile-norm epilogue of T21 was announced but not carried");
-      return -100;
-    }
-    if (!normed && any_fused)
-      for (int i = 0; i < cnt; ++i) GP_TRY(launch_frob_tiles<R>(Tp[i], ld, n2, n1, 0, Sp[i], s));
+    Epilogue<R> ep{};
+    for (int i = 0; i < cnt; ++i) ep.sumsq[i] = cs[i]->frob_part + ent;
+    GP_TRY(normed_product({n2, n1, n2}, plain(tril(blk(&PJ::Li, o21 + n1))), plain(blk(&PJ::Z, o21)), into(blk(&PJ::T, o21)),
+                          walk(W_MERGE), ask, ep, "T21"));
     ent += e;
   }
   for (int i = 0; i < cnt; ++i) {
-    if (any_fused) GP_TRY(launch_frob_finish(cs[i]->frob_part, ent, cs[i]->scal + 5, s));
-    else GP_TRY(launch_frob_lower(a[i].T, ld, np, cs[i]->scal + 5, cs[i]->frob_part, s));
+    if (any_fused) GP_TRY(launch_frob_finish(cs[i]->frob_part, ent, cs[i]->scal + S_TRACE, s));
+    else GP_TRY(launch_frob_lower(a[i].T, ld, np, cs[i]->scal + S_TRACE, cs[i]->frob_part, s));
   }
   return 0;
 }
 
 // cnt units at once (the units of a group, gpfit_fit_eval_batch; cnt = 1: the single unit): every product goes
-// through gemm_list / two_sided_list -- one pointer-batched launch where a single unit's product cannot fill the
+// through product / two_sided_list -- one pointer-batched launch where a single unit's product cannot fill the
 // chip, unit by unit through the ordinary launcher (balanced schedules, fused epilogues) where it can -- and the
 // element-wise passes run unit by unit, all on ONE stream: a stream that waits on an event is not free on this
 // runtime (every queue with a pending barrier packet slows the dispatch of the others), so a group gets its
-// concurrency from batched launches, not from streams.
+// concurrency from batched launches, not from streams.  lane: the caller's stream with the leader's workspace.
 template <typename R, typename PhaseFn>
-static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, const Theta* th, int n, int np, const int* d,
-                          const int* dp, int n_rows, int n_cols, int want_grad, bool blocks, hipStream_t s, PhaseFn&& phase) {
+static int post_join_list(Lane lane, int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, const Theta* th, int n, int np, const int* d,
+                          const int* dp, int n_rows, int n_cols, int want_grad, bool blocks, PhaseFn&& phase) {
+  using PJ = PostJoin<R>;
   const int64_t ld = np;
-  const R* Ap[GEMM_MAXB];
-  const R* Bp[GEMM_MAXB];
-  R* Cp[GEMM_MAXB];
-  R* Sp2[GEMM_MAXB];
-  double* Sp[GEMM_MAXB];
+  const hipStream_t s = lane.s;
   if (cnt <= 0 || cnt > GEMM_MAXB) return cnt == 0 ? 0 : -3;
+  auto all = [&](auto X, int64_t ldx) { return mats(cnt, ldx, [&](int i) { return a[i].*X; }); };   // matrix X of every unit
   // T = L^-1 L_V (lower x lower -> lower);  tr(K~^-1 V) = ||T||_F^2
   if (!blocks) {
-    for (int i = 0; i < cnt; ++i) { Ap[i] = a[i].Li; Bp[i] = a[i].LV; Cp[i] = a[i].T; Sp[i] = cs[i]->frob_part; }
-    bool normed = false;
-    int norm_entries = 0;
     // the tiles leave their sums of squares behind (no separate pass over T) where the launch can carry the epilogue
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 1, np, np, np, 1.0, ld, ld, 0.0, ld, 1, 1, 1, walks()[3], cs[0]->sk_ws[0],
-                        (fused_epilogues() & 2) ? 2 : 0, nullptr, Sp, &normed, &norm_entries));
+    Epilogue<R> e{(fused_epilogues() & 2) ? 2 : 0};
+    for (int i = 0; i < cnt; ++i) e.sumsq[i] = cs[i]->frob_part;
+    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(all(&PJ::Li, ld))), plain(tril(all(&PJ::LV, ld))), into_lower(all(&PJ::T, ld)),
+                   walk(W_T), &e));
     for (int i = 0; i < cnt; ++i) {
-      if (normed) GP_TRY(launch_frob_finish(cs[i]->frob_part, norm_entries, cs[i]->scal + 5, s));
-      else GP_TRY(launch_frob_lower(a[i].T, ld, np, cs[i]->scal + 5, cs[i]->frob_part, s));
+      if (e.carried) GP_TRY(launch_frob_finish(cs[i]->frob_part, e.sumsq_entries, cs[i]->scal + S_TRACE, s));
+      else GP_TRY(launch_frob_lower(a[i].T, ld, np, cs[i]->scal + S_TRACE, cs[i]->frob_part, s));
     }
   } else {
-    GP_TRY(t_in_blocks<R>(cnt, cs, a, np, s));
+    GP_TRY(t_in_blocks<R>(lane, cnt, cs, a, np));
   }
   phase(4, s);
   if (!want_grad) return 0;
@@ -1082,30 +1000,25 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
     // T T^T: every tile of a tile column has the same k range [0, col + 128).  XCD-aware macro-tile schedule for
     // a single large unit (2.97 ms at N = 8192 in the fit; the column-major heavy-first data-parallel walk 3.02,
     // stream-K 3.2)
-    for (int i = 0; i < cnt; ++i) { Ap[i] = a[i].T; Bp[i] = a[i].T; Cp[i] = a[i].W; }
-    bool mirrored = false;
-    GP_TRY(gemm_list<R>(s, cnt, Ap, Bp, Cp, 0, 0, np, np, np, -1.0, ld, ld, 0.0, ld, 1, 1, 2, walks()[4], cs[0]->sk_ws[0],
-                        (fused_epilogues() & 1) ? 1 : 0, nullptr, nullptr, &mirrored));
+    Epilogue<R> mirror{(fused_epilogues() & 1) ? 1 : 0};
+    GP_TRY(product(lane, {np, np, np}, -1.0, plain(tril(all(&PJ::T, ld))), trans(tril(all(&PJ::T, ld))), into_lower(all(&PJ::W, ld)),
+                   walk(W_Q), &mirror));
     for (int i = 0; i < cnt; ++i) {
       GP_TRY(launch_add_diag(a[i].W, ld, np, 1.0, s));
-      if (!mirrored) GP_TRY(launch_symmetrize(a[i].W, ld, np, s));   // otherwise the tiles stored their transposes
+      if (!mirror.carried) GP_TRY(launch_symmetrize(a[i].W, ld, np, s));   // otherwise the tiles stored their transposes
     }
   }
   phase(5, s);
   {
     static const int ts_min = getenv("GPFIT_TS_MIN") ? atoi(getenv("GPFIT_TS_MIN")) : 4096;
     TwoSidedBufs<R> tb[GEMM_MAXB];
-    const R* Lf[GEMM_MAXB];
-    for (int i = 0; i < cnt; ++i) {
-      tb[i] = TwoSidedBufs<R>{a[i].W, a[i].Li, a[i].T, a[i].Z, a[i].H, ld, ts_min > 0 ? ts_min : (1 << 30)};
-      tb[i].sk_ws = cs[0]->sk_ws[0];
-      Lf[i] = a[i].L;
-    }
-    if (blocks) GP_TRY(two_sided_top<R>(cnt, tb, Lf, np, s));
+    for (int i = 0; i < cnt; ++i)   // Q in W, W over T
+      tb[i] = TwoSidedBufs<R>{a[i].W, a[i].Li, a[i].T, a[i].Z, a[i].H, a[i].L, ld, ts_min > 0 ? ts_min : (1 << 30)};
+    if (blocks) GP_TRY(two_sided_top<R>(lane, cnt, tb, np));
     else {
       int r0[GEMM_MAXB];
       for (int i = 0; i < cnt; ++i) r0[i] = 0;
-      GP_TRY(two_sided_list<R>(cnt, tb, r0, np, s));
+      GP_TRY(two_sided_list<R>(lane, cnt, tb, r0, np));
     }
   }
   phase(6, s);
@@ -1116,17 +1029,20 @@ static int post_join_list(int cnt, gpfit_ctx* const* cs, const PostJoin<R>* a, c
   {
     bool same_dp = true;
     for (int i = 1; i < cnt; ++i) same_dp = same_dp && dp[i] == dp[0];
-    for (int i = 0; i < cnt; ++i) { Ap[i] = a[i].A; Bp[i] = a[i].Xm; Cp[i] = a[i].Y; Sp2[i] = a[i].Z; }
-    if (same_dp) GP_TRY(lambda_t_x_list<R>(s, cnt, Ap, Bp, Cp, Sp2, np, dp[0]));
+    if (same_dp)
+      GP_TRY(lambda_t_x_list(lane, trans(tril(all(&PJ::A, ld))), plain(all(&PJ::Xm, dp[0])), all(&PJ::Y, dp[0]), all(&PJ::Z, dp[0]), np,
+                             dp[0]));
     else
-      for (int i = 0; i < cnt; ++i) GP_TRY(lambda_t_x_list<R>(s, 1, Ap + i, Bp + i, Cp + i, Sp2 + i, np, dp[i]));
+      for (int i = 0; i < cnt; ++i)
+        GP_TRY(lambda_t_x_list(lane, trans(tril(mat(a[i].A, ld))), plain(mat(a[i].Xm, dp[i])), mat(a[i].Y, dp[i]), mat(a[i].Z, dp[i]), np,
+                               dp[i]));
   }
   for (int i = 0; i < cnt; ++i) {
     gpfit_ctx* c = cs[i];
     GP_TRY(launch_rowscale_add(a[i].Y, dp[i], a[i].Xm, dp[i], a[i].tvec, np, dp[i], s, 0.5));
     GP_TRY(xty<R>(c, s, a[i].Xm, a[i].Y, np, dp[i], a[i].Mmat, true, true));
-    GP_TRY(launch_metric_contract(th[i], c->pix, d[i], n_rows, n_cols, a[i].Cmat, dp[i], a[i].Mmat, dp[i], c->scal + 10, c->upart,
-                                  c->info + 3, s));
+    GP_TRY(launch_metric_contract(th[i], c->pix, d[i], n_rows, n_cols, a[i].Cmat, dp[i], a[i].Mmat, dp[i], c->scal + S_METRIC, c->upart,
+                                  c->info + INFO_METRIC, s));
   }
   return 0;
 }
@@ -1177,7 +1093,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   };
   c->phase_valid = false;
   phase(0, s);
-  g_main_sk_ws = c->sk_ws[0];
+  const Lane lane = main_lane(c, s);
   prof_begin(c);
   struct ProfGuard { gpfit_ctx* c; ~ProfGuard() { prof_end(c); } } prof_guard{c};
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
@@ -1212,26 +1128,26 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   }
 
   // ---- main stream: metric, kernel matrix, moments, Cholesky of K~ with its inverse
-  GP_TRY(build_kernel<R>(c, s, th, d, dp, n_rows, n_cols, X, ldx, n, np, 0));
+  GP_TRY(build_kernel<R>(c, lane, th, d, dp, n_rows, n_cols, X, ldx, n, np, 0));
   GP_TRY(launch_moments(RP(c->Kvec), RP(c->q), RP(c->Cos), ld, V, ldv, m, r, n, A, lambda0, RP(c->lam_m), RP(c->lam_var), RP(c->fvec),
-                        RP(c->wl), c->scal, c->sumA_part, c->info + 2, s));
+                        RP(c->wl), c->scal + S_RLAM, c->sumA_part, c->info + INFO_MOMENTS, s));
   phase(1, s);
   {
     // K~ (with its inverse) and V in lock step; K~ alone when V's factor is reused
     CholBatchT<R> cb;
     cb.nb = reuse_V ? 1 : 2;
-    cb.A[0] = RP(c->Kbuf); cb.L[0] = RP(c->Lbuf); cb.Li[0] = RP(c->Libuf); cb.Tmp[0] = RP(c->Tmp); cb.info[0] = c->info + 0;
-    cb.A[1] = RP(c->Vbuf); cb.L[1] = RP(c->LVbuf); cb.Li[1] = RP(c->LiVbuf); cb.Tmp[1] = RP(c->TmpV); cb.info[1] = c->info + 1;
-    cb.ld = ld; cb.sk_ws = c->sk_ws[0]; cb.ctx = c; cb.side_min = side_min;
+    cb.A[0] = RP(c->Kbuf); cb.L[0] = RP(c->Lbuf); cb.Li[0] = RP(c->Libuf); cb.Tmp[0] = RP(c->Tmp); cb.info[0] = c->info + INFO_K;
+    cb.A[1] = RP(c->Vbuf); cb.L[1] = RP(c->LVbuf); cb.Li[1] = RP(c->LiVbuf); cb.Tmp[1] = RP(c->TmpV); cb.info[1] = c->info + INFO_V;
+    cb.ld = ld; cb.ctx = c; cb.side_min = side_min;
     if (!reuse_V) GP_HIP(hipStreamWaitEvent(s, c->ev_join, 0));   // V is packed
     // (K~'s chain in block form: the inverses of the two diagonal halves only -- everything behind substitutes with
     // L21, and the top-level look-ahead on the side stream disappears with the merge)
-    if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, s, 1u));
-    else GP_TRY(potrf_lockstep<R>(cb, 0, np, 1u, s));
-    if (!reuse_V) GP_TRY(launch_logdet(RP(c->LVbuf), ld, n, c->scal + 40, s));
+    if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, lane, 1u));
+    else GP_TRY(potrf_lockstep<R>(cb, 0, np, 1u, lane));
+    if (!reuse_V) GP_TRY(launch_logdet(RP(c->LVbuf), ld, n, c->scal + S_LOGDET_V, s));
     phase(3, s);
   }
-  GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + 3, s));
+  GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + S_LOGDET_K, s));
   GP_TRY(solve_mean<R>(c, np, blocks, s));
 
   phase(2, s);
@@ -1239,10 +1155,10 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   if (mixed_grad) {
     PostJoin<float> pf;
     GP_TRY(demote_for_mixed(c, reuse_V, np, dp, blocks, s, &pf));
-    GP_TRY(post_join_list<float>(1, &c, &pf, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, blocks, s, phase));
+    GP_TRY(post_join_list<float>(lane, 1, &c, &pf, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, blocks, phase));
   } else {
     const PostJoin<R> pj = post_join_args<R>(c);
-    GP_TRY(post_join_list<R>(1, &c, &pj, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, blocks, s, phase));
+    GP_TRY(post_join_list<R>(lane, 1, &c, &pj, &th, n, np, &d, &dp, n_rows, n_cols, want_grad, blocks, phase));
   }
 
   if (lam_m_out) GP_HIP(hipMemcpyAsync(lam_m_out, RP(c->lam_m), (size_t)n * sizeof(R), hipMemcpyDeviceToDevice, s));
@@ -1266,7 +1182,7 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
 // (post_join_list).  Every unit's numbers are bit-identical to gpfit_fit_eval on its own.
 // want_grad bits as gpfit_fit_eval (1 gradients, 2 reuse this context's V factor, 8 mixed precision); bit 2
 // (asynchronous) is implied: the call returns after enqueuing and the units are collected one by one with
-// gpfit_fit_eval_finish.  rc_out[u]: 0 enqueued (collect it), -2 theta outside the limits (out_host[16 u ..]
+// gpfit_fit_eval_finish.  rc_out[u]: 0 enqueued (collect it), -2 theta outside the limits (out_host[OUT_COUNT u ..]
 // already holds the infinite loss / gradients, nothing to collect).
 template <typename R>
 static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const double* theta6, const double* lower,
@@ -1315,7 +1231,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
     gpfit_ctx* c = cs[u];
     Admitted ad;
     const int rc = admit(c, "gpfit_fit_eval_batch", "a context's", theta6 + 6 * u, lower, upper, n_rows, n_cols, np,
-                         out_host + 16 * u, &ad);
+                         out_host + OUT_COUNT * u, &ad);
     rc_out[u] = rc == -2 ? -2 : 0;
     if (rc == -2) continue;
     if (rc != 0) return rc;
@@ -1328,6 +1244,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   }
   if (na == 0) return 0;
   gpfit_ctx* c0 = un[0].c;
+  const Lane lane = main_lane(c0, s);   // every launch of the group on the caller's stream with the leader's workspace
   // tuning aid: GPFIT_BATCH_TIMES=1 prints the three phases of every group (synchronises: not for timed runs)
   static const bool batch_times = getenv("GPFIT_BATCH_TIMES") != nullptr;
   hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1351,10 +1268,9 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   for (int i = 0; i < na; ++i) {
     Unit& q = un[i];
     gpfit_ctx* c = q.c;
-    g_main_sk_ws = c0->sk_ws[0];
-    GP_TRY(build_kernel<R>(c, s, q.th, q.d, q.dp, n_rows, n_cols, X[q.u], ldx, n, np, 0));
+    GP_TRY(build_kernel<R>(c, lane, q.th, q.d, q.dp, n_rows, n_cols, X[q.u], ldx, n, np, 0));
     GP_TRY(launch_moments(RP(c->Kvec), RP(c->q), RP(c->Cos), ld, V[q.u], ldv, m[q.u], r[q.u], n, q.A, lambda0[q.u], RP(c->lam_m),
-                          RP(c->lam_var), RP(c->fvec), RP(c->wl), c->scal, c->sumA_part, c->info + 2, s));
+                          RP(c->lam_var), RP(c->fvec), RP(c->wl), c->scal + S_RLAM, c->sumA_part, c->info + INFO_MOMENTS, s));
     if (!q.reuse_V) {
       c->lv_valid = false; c->lv32_valid = false;
       GP_TRY(launch_pack_lower(V[q.u], ldv, n, RP(c->Vbuf), ld, np, s));
@@ -1368,15 +1284,15 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
     for (int i = 0; i < na; ++i) {
       gpfit_ctx* c = un[i].c;
       int b = cb.nb++;
-      cb.A[b] = RP(c->Kbuf); cb.L[b] = RP(c->Lbuf); cb.Li[b] = RP(c->Libuf); cb.Tmp[b] = RP(c->Tmp); cb.info[b] = c->info + 0;
+      cb.A[b] = RP(c->Kbuf); cb.L[b] = RP(c->Lbuf); cb.Li[b] = RP(c->Libuf); cb.Tmp[b] = RP(c->Tmp); cb.info[b] = c->info + INFO_K;
       kchains |= 1u << b;
       if (un[i].reuse_V) continue;
       b = cb.nb++;
-      cb.A[b] = RP(c->Vbuf); cb.L[b] = RP(c->LVbuf); cb.Li[b] = RP(c->LiVbuf); cb.Tmp[b] = RP(c->TmpV); cb.info[b] = c->info + 1;
+      cb.A[b] = RP(c->Vbuf); cb.L[b] = RP(c->LVbuf); cb.Li[b] = RP(c->LiVbuf); cb.Tmp[b] = RP(c->TmpV); cb.info[b] = c->info + INFO_V;
     }
-    cb.ld = ld; cb.sk_ws = c0->sk_ws[0]; cb.ctx = nullptr; cb.side_min = 0;
-    if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, s, kchains));
-    else GP_TRY(potrf_lockstep<R>(cb, 0, np, kchains, s));
+    cb.ld = ld; cb.ctx = nullptr; cb.side_min = 0;
+    if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, lane, kchains));
+    else GP_TRY(potrf_lockstep<R>(cb, 0, np, kchains, lane));
   }
   if (batch_times) (void)hipEventRecord(tev[2], s);
   // ---- phase 3: everything that needs the factors
@@ -1390,14 +1306,14 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
     Unit& q = un[i];
     gpfit_ctx* c = q.c;
     cl[i] = c; thl[i] = q.th; dl[i] = q.d; dpl[i] = q.dp;
-    if (!q.reuse_V) GP_TRY(launch_logdet_pair(RP(c->Lbuf), c->scal + 3, RP(c->LVbuf), c->scal + 40, ld, n, s));
-    else GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + 3, s));
+    if (!q.reuse_V) GP_TRY(launch_logdet_pair(RP(c->Lbuf), c->scal + S_LOGDET_K, RP(c->LVbuf), c->scal + S_LOGDET_V, ld, n, s));
+    else GP_TRY(launch_logdet(RP(c->Lbuf), ld, n, c->scal + S_LOGDET_K, s));
     GP_TRY(solve_mean<R>(c, np, blocks, s));
     if (mixed_grad) GP_TRY(demote_for_mixed(c, q.reuse_V, np, q.dp, blocks, s, &pfl[i]));
     else pjl[i] = post_join_args<R>(c);
   }
-  if (mixed_grad) GP_TRY(post_join_list<float>(na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, s, no_phase));
-  else GP_TRY(post_join_list<R>(na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, s, no_phase));
+  if (mixed_grad) GP_TRY(post_join_list<float>(lane, na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, no_phase));
+  else GP_TRY(post_join_list<R>(lane, na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, no_phase));
   {
     GroupCollectT gc{};
     gc.n_units = na;
@@ -1456,19 +1372,20 @@ static int grad_pullback_impl(gpfit_ctx* c, void* stream, const double* theta, i
   const int d = ad.d, dp = ad.dp;
   const Theta th = ad.th;
   c->lv_valid = false; c->lv32_valid = false;  // the workspace matrices are reused
-  g_main_sk_ws = c->sk_ws[0];
+  const Lane lane = main_lane(c, s);
   GP_HIP(hipMemcpyAsync(c->pix, c->pix_host, (size_t)d * sizeof(int), hipMemcpyHostToDevice, s));
-  GP_TRY(build_kernel<R>(c, s, th, d, dp, n_rows, n_cols, X, ldx, n, np, 0));
+  GP_TRY(build_kernel<R>(c, lane, th, d, dp, n_rows, n_cols, X, ldx, n, np, 0));
   GP_TRY(launch_pack_lower(W, ldw, n, c->Wbuf, (int64_t)np, np, s));
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)np * sizeof(R), s));             // no -1/2 b b^T term here
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)np * sizeof(R), s));
   GP_TRY(launch_scale_copy<R>(c->wl, gvec, n, -1.0, s));                    // t_i = u_i / q_i + gvec_i
-  GP_TRY(pullback_to_metric(c, s, c->Wbuf, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));
-  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
+  GP_TRY(pullback_to_metric(c, lane, c->Wbuf, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));
+  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
+                                c->info + INFO_METRIC, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   const double* sc = c->scal_host;
-  grad_rows(sc, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[8], out6);
+  grad_rows(sc, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[S_ADJ_WL], out6);
   return 0;
 }
 
@@ -1500,7 +1417,7 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   const int64_t ld = np, lb = nb;
   c->lv_valid = false; c->lv32_valid = false;
   c->side_ev_next = 0;
-  g_main_sk_ws = c->sk_ws[0];
+  const Lane lane = main_lane(c, s);
   ++g_eval_count;
   prof_begin(c);
   struct ProfGuard { gpfit_ctx* c; ~ProfGuard() { prof_end(c); } } prof_guard{c};
@@ -1511,35 +1428,36 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   GP_HIP(hipMemcpyAsync(c->pix, c->pix_host, (size_t)d * sizeof(int), hipMemcpyHostToDevice, s));
   // ---- kernel build (as the full-rank unit): C, X masked, cos, Kvec, q, and K~ stored in full by the tiles
   // themselves (mirror): it is multiplied from the left below
-  GP_TRY(build_kernel<R>(c, s, th, d, dp, n_rows, n_cols, X, ldx, n, np, 1));
+  GP_TRY(build_kernel<R>(c, lane, th, d, dp, n_rows, n_cols, X, ldx, n, np, 1));
   // ---- projection (utils.py:2047-2049): K_b = K~ B, K~_b = sym(B^T K_b)
   GP_TRY(launch_pad_copy(B, ldb, n, nk, Bp, lb, np, nb, s));
   GP_HIP(hipMemsetAsync(mbp, 0, (size_t)np * sizeof(double), s));
   GP_HIP(hipMemcpyAsync(mbp, m_b, (size_t)nk * sizeof(double), hipMemcpyDeviceToDevice, s));
-  GP_TRY(gemm_splitk<R>(s, 0, 1, np, nb, np, 1.0, Kt, ld, Bp, lb, Kb, lb, splitk_for(np, nb, np), c->Wbuf, (int64_t)c->np_cap * c->np_cap));
-  GP_TRY(gemm_splitk<R>(s, 1, 1, nb, nb, np, 1.0, Bp, lb, Kb, lb, S4, lb, splitk_for(nb, nb, np), c->Wbuf, (int64_t)c->np_cap * c->np_cap));
+  GP_TRY(gemm_splitk(lane, {np, nb, np}, 1.0, plain(mat(Kt, ld)), plain(mat(Bp, lb)), Kb, lb, c->Wbuf, (int64_t)c->np_cap * c->np_cap));
+  GP_TRY(gemm_splitk(lane, {nb, nb, np}, 1.0, trans(mat(Bp, lb)), plain(mat(Kb, lb)), S4, lb, c->Wbuf, (int64_t)c->np_cap * c->np_cap));
   GP_TRY(launch_symmetrize_avg(S4, lb, nk, s));                                             // :2048
   GP_TRY(launch_pack_lower(S4, lb, nk, S1, lb, nb, s));
   // (log|V_b| of :1326: V_b is factored together with K~_b -- one lock-step recursion on this stream, in four work
   // matrices nothing else needs before the adjoints: Abuf, Wbuf, Zbuf, Tmp)
   GP_TRY(launch_pack_lower(V_b, ldvb, nk, c->Abuf, lb, nb, s));
-  GP_TRY(projected_factor(c, s, V_b, ldvb, nk, nb, c->Abuf, c->Wbuf, c->Zbuf, c->Tmp));
+  GP_TRY(projected_factor(c, lane, V_b, ldvb, nk, nb, c->Abuf, c->Wbuf, c->Zbuf, c->Tmp));
   double* Ki = S1;
   // a V = B V_b, then K~_b^-1 V_b with its trace and K~_b^-1 V_b K~_b^-1 (P1, in S4)
-  GP_TRY(gemm<R>(s, 0, 1, np, nb, nb, 1.0, Bp, lb, S2, lb, 0.0, aV, lb, 0, 0, 0));
-  GP_TRY(projected_kl_products(c, s, nk, nb));
+  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S2, lb)), into(mat(aV, lb))));
+  GP_TRY(projected_kl_products(c, lane, nk, nb));
   GP_TRY(launch_symv_lower(Ki, lb, nb, mbp, bvec, s));                                        // b = K~_b^-1 m_b
-  GP_TRY(launch_dot(mbp, bvec, nb, c->scal + 6, s));
+  GP_TRY(launch_dot(mbp, bvec, nb, c->scal + S_MKM, s));
   // ---- moments, rate, likelihood pieces (:1090, 1101, 1138, 1243) and the per-point adjoints
   GP_TRY(launch_proj_moments(Bp, Kb, aV, lb, nb, mbp, c->Kvec, r, n, A, lambda0, c->lam_m, c->lam_var, c->fvec, gm, gv,
-                             c->upart, c->scal + 0, s));
+                             c->upart, c->scal + S_RLAM, s));
   // ---- adjoints (utils._closure_projected): G_a, G_Kb, G_K~b, W
   GP_TRY(launch_proj_ga(Kb, aV, lb, nb, n, np, gm, gv, mbp, Ga, s));
-  GP_TRY(gemm<R>(s, 0, 1, np, nb, nb, 1.0, Ga, lb, Ki, lb, 0.0, GaKi, lb, 0, 0, 0));
-  GP_TRY(gemm_splitk<R>(s, 1, 1, nb, nb, np, 1.0, Bp, lb, GaKi, lb, c->Abuf, lb, splitk_for(nb, nb, np), c->Wbuf, (int64_t)c->np_cap * c->np_cap));   // P2 = B^T G_a K~_b^-1
+  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Ga, lb)), plain(mat(Ki, lb)), into(mat(GaKi, lb))));
+  GP_TRY(gemm_splitk(lane, {nb, nb, np}, 1.0, trans(mat(Bp, lb)), plain(mat(GaKi, lb)), c->Abuf, lb, c->Wbuf,
+                     (int64_t)c->np_cap * c->np_cap));   // P2 = B^T G_a K~_b^-1
   GP_TRY(launch_proj_gktb(Ki, S4, c->Abuf, lb, nb, bvec, S3, s));                            // G_K~b
   GP_TRY(launch_proj_gkb(Bp, lb, nb, n, np, gv, GaKi, s));                                   // G_Kb (in place)
-  GP_TRY(gemm<R>(s, 0, 1, np, nb, nb, 1.0, Bp, lb, S3, lb, 1.0, GaKi, lb, 0, 0, 0));          // + B G_K~b
+  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S3, lb)), into(mat(GaKi, lb), 1.0)));          // + B G_K~b
   // W = sym((.) B^T).  With P = B G_K~b + G_Kb:  1/2 (P B^T + B P^T) = 1/2 [P | B] [B | P]^T -- ONE product with
   // k = 2 nb that writes the lower tiles only (what the adjoint pass reads): the same flops as the full P B^T, and
   // neither its upper half nor the averaging pass over N x N exist.  (Falls back to the two steps when 2 nb
@@ -1551,22 +1469,23 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
     GP_TRY(launch_pad_copy(Bp, lb, np, nb, Cat1 + nb, l2b, np, nb, s));
     GP_TRY(launch_pad_copy(Bp, lb, np, nb, Cat2, l2b, np, nb, s));
     GP_TRY(launch_pad_copy(GaKi, lb, np, nb, Cat2 + nb, l2b, np, nb, s));
-    GP_TRY(gemm<R>(s, 0, 0, np, np, 2 * nb, 0.5, Cat1, l2b, Cat2, l2b, 0.0, W, ld, 1, 0, 0));
+    GP_TRY(product(lane, {np, np, 2 * nb}, 0.5, plain(mat(Cat1, l2b)), trans(mat(Cat2, l2b)), into_lower(mat(W, ld))));
   } else {
-    GP_TRY(gemm<R>(s, 0, 0, np, np, nb, 1.0, GaKi, lb, Bp, lb, 0.0, W, ld, 0, 0, 0));
+    GP_TRY(product(lane, {np, np, nb}, 1.0, plain(mat(GaKi, lb)), trans(mat(Bp, lb)), into(mat(W, ld))));
     GP_TRY(launch_symmetrize_avg(W, ld, np, s));
   }
   // ---- pull-back of <W, dK~_p> + <gvec, dKvec_p> to the metric (as gpfit_grad_pullback; gvec = -g_v)
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)np * sizeof(R), s));
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)np * sizeof(R), s));
   GP_TRY(launch_scale_copy<R>(c->wl, gv, n, 1.0, s));
-  GP_TRY(pullback_to_metric(c, s, W, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
-  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
+  GP_TRY(pullback_to_metric(c, lane, W, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
+  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
+                                c->info + INFO_METRIC, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   const double* sc = c->scal_host;
-  return assemble_out(c, A, lambda0, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[8], 0, d, 1,
+  return assemble_out(c, A, lambda0, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[S_ADJ_WL], 0, d, 1,
                       "gpfit_fit_eval_projected: Cholesky of the projected K_tilde failed (non-positive pivot)",
                       "gpfit_fit_eval_projected: Cholesky of V_b failed (non-positive pivot)", out_host);
 }
@@ -1603,7 +1522,7 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   const int64_t l2 = np2, lb = nb;
   c->lv_valid = false; c->lv32_valid = false;
   c->side_ev_next = 0;
-  g_main_sk_ws = c->sk_ws[0];
+  const Lane lane = main_lane(c, s);
   ++g_eval_count;
   prof_begin(c);
   struct ProfGuard { gpfit_ctx* c; ~ProfGuard() { prof_end(c); } } prof_guard{c};
@@ -1617,8 +1536,8 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   // ---- kernel objects: C; training side (x: Xt, XCt, q, Kvec), inducing side (xtilde: Xt2, XCt2, q2);
   // K~ = acosker(xtilde, xtilde), lower tiles mirrored by the tiles themselves
   GP_TRY(build_metric<R>(c, s, th, d, dp, n_rows, n_cols));
-  GP_TRY(kernel_side<R>(c, s, X, ldx, n1, np1, d, dp, s0sq, c->Xt, c->XCt, X1m, c->Kvec, c->q));
-  GP_TRY(kernel_side<R>(c, s, Xtilde, ldxt, n2, np2, d, dp, s0sq, c->Xt2, c->XCt2, X2m, c->hvec, c->q2));
+  GP_TRY(kernel_side<R>(c, lane, X, ldx, n1, np1, d, dp, s0sq, c->Xt, c->XCt, X1m, c->Kvec, c->q));
+  GP_TRY(kernel_side<R>(c, lane, Xtilde, ldxt, n2, np2, d, dp, s0sq, c->Xt2, c->XCt2, X2m, c->hvec, c->q2));
   GP_TRY(gram_square<R>(s, c->XCt2, c->Xt2, c->q2, Kt, CosT, n2, np2, dp, s0sq, 1));
   {
     GramArgsT<R> g{};  // K = acosker(x, xtilde): rectangular, with its cosine matrix
@@ -1634,9 +1553,12 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   GP_HIP(hipMemsetAsync(mbp, 0, (size_t)c->np_cap * sizeof(double), s));
   GP_HIP(hipMemcpyAsync(mbp, m_b, (size_t)nk * sizeof(double), hipMemcpyDeviceToDevice, s));
   // (skinny products with a long k are cut into k slabs, gemm_splitk; Wbuf is free until the adjoints)
-  GP_TRY(gemm_splitk<R>(s, 0, 1, np1, nb, np2, 1.0, Kr, l2, Bp, lb, Kb, lb, splitk_for(np1, nb, np2), c->Wbuf, (int64_t)c->np_cap * c->np_cap));
-  GP_TRY(gemm_splitk<R>(s, 0, 1, np2, nb, np2, 1.0, Kt, l2, Bp, lb, am, lb, splitk_for(np2, nb, np2), c->Wbuf, (int64_t)c->np_cap * c->np_cap));   // K~ B (temporary)
-  GP_TRY(gemm_splitk<R>(s, 1, 1, nb, nb, np2, 1.0, Bp, lb, am, lb, S4, lb, splitk_for(nb, nb, np2), c->Wbuf, (int64_t)c->np_cap * c->np_cap));
+  GP_TRY(gemm_splitk(lane, {np1, nb, np2}, 1.0, plain(mat(Kr, l2)), plain(mat(Bp, lb)), Kb, lb, c->Wbuf,
+                     (int64_t)c->np_cap * c->np_cap));
+  GP_TRY(gemm_splitk(lane, {np2, nb, np2}, 1.0, plain(mat(Kt, l2)), plain(mat(Bp, lb)), am, lb, c->Wbuf,
+                     (int64_t)c->np_cap * c->np_cap));   // K~ B (temporary)
+  GP_TRY(gemm_splitk(lane, {nb, nb, np2}, 1.0, trans(mat(Bp, lb)), plain(mat(am, lb)), S4, lb, c->Wbuf,
+                     (int64_t)c->np_cap * c->np_cap));
   GP_TRY(launch_symmetrize_avg(S4, lb, nk, s));
   GP_TRY(launch_pack_lower(S4, lb, nk, S1, lb, nb, s));
   {
@@ -1649,43 +1571,45 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
     GP_TRY(launch_pack_lower(V_b, ldvb, nk, Va, lb, nb, s));
     for (double* p : {Vl, Vli, Vt})   // tiles above the diagonal read as zero
       GP_HIP(hipMemsetAsync(p, 0, (size_t)nb * nb * sizeof(double), s));
-    GP_TRY(projected_factor(c, s, V_b, ldvb, nk, nb, Va, Vl, Vli, Vt));
+    GP_TRY(projected_factor(c, lane, V_b, ldvb, nk, nb, Va, Vl, Vli, Vt));
   }
   double* Ki = S1;
-  GP_TRY(projected_kl_products(c, s, nk, nb));
-  GP_TRY(gemm<R>(s, 0, 1, np1, nb, nb, 1.0, Kb, lb, Ki, lb, 0.0, am, lb, 0, 0, 0));           // a
-  GP_TRY(gemm<R>(s, 0, 1, np1, nb, nb, 1.0, am, lb, S2, lb, 0.0, aV, lb, 0, 0, 0));           // a V_b
+  GP_TRY(projected_kl_products(c, lane, nk, nb));
+  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(mat(Kb, lb)), plain(mat(Ki, lb)), into(mat(am, lb))));           // a
+  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(mat(am, lb)), plain(mat(S2, lb)), into(mat(aV, lb))));           // a V_b
   GP_TRY(launch_symv_lower(Ki, lb, nb, mbp, bvec, s));
-  GP_TRY(launch_dot(mbp, bvec, nb, c->scal + 6, s));
+  GP_TRY(launch_dot(mbp, bvec, nb, c->scal + S_MKM, s));
   // ---- moments / likelihood pieces with a = K_b K~_b^-1, per-point adjoints
   GP_TRY(launch_proj_moments(am, Kb, aV, lb, nb, mbp, c->Kvec, r, n1, A, lambda0, c->lam_m, c->lam_var, c->fvec, gm, gv,
-                             c->upart, c->scal + 0, s));
+                             c->upart, c->scal + S_RLAM, s));
   double* Ga = Kt;       // [np1][nb]
   double* GaKi = Kr;     // [np1][nb]
   GP_TRY(launch_proj_ga(Kb, aV, lb, nb, n1, np1, gm, gv, mbp, Ga, s));
-  GP_TRY(gemm<R>(s, 0, 1, np1, nb, nb, 1.0, Ga, lb, Ki, lb, 0.0, GaKi, lb, 0, 0, 0));
-  GP_TRY(gemm_splitk<R>(s, 1, 1, nb, nb, np1, 1.0, am, lb, GaKi, lb, c->Wbuf, lb, splitk_for(nb, nb, np1), c->TmpV + (int64_t)nb * nb,
+  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(mat(Ga, lb)), plain(mat(Ki, lb)), into(mat(GaKi, lb))));
+  GP_TRY(gemm_splitk(lane, {nb, nb, np1}, 1.0, trans(mat(am, lb)), plain(mat(GaKi, lb)), c->Wbuf, lb, c->TmpV + (int64_t)nb * nb,
                         (int64_t)c->np_cap * c->np_cap - (int64_t)nb * nb));   // P2 = a^T G_a K~_b^-1 (slabs behind P1 in TmpV)
   GP_TRY(launch_proj_gktb(Ki, S4, c->Wbuf, lb, nb, bvec, S3, s));                            // G_K~b
   GP_TRY(launch_proj_gkb(am, lb, nb, n1, np1, gv, GaKi, s));                                 // G_Kb (in place)
   // ---- the two adjoints:  W~ = sym(B G_K~b B^T) [np2 x np2],  W_K = G_Kb B^T [np1 x np2]
-  GP_TRY(gemm<R>(s, 0, 1, np2, nb, nb, 1.0, Bp, lb, S3, lb, 0.0, Kt, lb, 0, 0, 0));           // B G_K~b  (G_a is dead)
-  GP_TRY(gemm<R>(s, 0, 0, np2, np2, nb, 1.0, Kt, lb, Bp, lb, 0.0, c->Wbuf, l2, 0, 0, 0));
+  GP_TRY(product(lane, {np2, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S3, lb)),
+                 into(mat(Kt, lb))));           // B G_K~b  (G_a is dead)
+  GP_TRY(product(lane, {np2, np2, nb}, 1.0, plain(mat(Kt, lb)), trans(mat(Bp, lb)), into(mat(c->Wbuf, l2))));
   GP_TRY(launch_symmetrize_avg(c->Wbuf, l2, np2, s));
-  GP_TRY(gemm<R>(s, 0, 0, np1, np2, nb, 1.0, GaKi, lb, Bp, lb, 0.0, aV, l2, 0, 0, 0));        // W_K  (a V_b is dead)
+  GP_TRY(product(lane, {np1, np2, nb}, 1.0, plain(mat(GaKi, lb)), trans(mat(Bp, lb)),
+                 into(mat(aV, l2))));        // W_K  (a V_b is dead)
   double* WK = aV;
   // ---- square pull-back on the inducing stimuli (no b b^T term, no dKvec term; A_w into K_b, which is dead).
   // (bv / wl are cleared over np_cap elements here, over np in the other two closures: each as it always was)
   GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)c->np_cap * sizeof(R), s));
   GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)c->np_cap * sizeof(R), s));
-  GP_TRY(pullback_to_metric(c, s, c->Wbuf, CosT, c->q2, n2, np2, dp, Kb, X2m, am));   // a (Tmp) is dead
+  GP_TRY(pullback_to_metric(c, lane, c->Wbuf, CosT, c->q2, n2, np2, dp, Kb, X2m, am));   // a (Tmp) is dead
   // ---- rectangular pull-back (x, xtilde) with gvec = -g_v on the training side (dKvec term)
   GP_TRY(launch_scale_copy<R>(gvec, gv, n1, -1.0, s));
   double* t1 = c->tvec;
   double* t2 = c->tvec + c->np_cap;
   GP_TRY(launch_adjoint_rect(WK, l2, CosR, l2, c->q, c->q2, n1, n2, np1, np2, Kt, l2, c->upart, c->vpart, c->rect_part,
-                             gvec, t1, t2, c->rpad, c->mpad, c->scal + 20, s));
-  GP_TRY(gemm<R>(s, 0, 1, np1, dp, np2, 1.0, Kt, l2, X2m, dp, 0.0, c->Ybuf, dp, 0, 0, 0));
+                             gvec, t1, t2, c->rpad, c->mpad, c->scal + S_RECT, s));
+  GP_TRY(product(lane, {np1, dp, np2}, 1.0, plain(mat(Kt, l2)), plain(mat(X2m, dp)), into(mat(c->Ybuf, dp))));
   GP_TRY(launch_rowscale_add(c->Ybuf, dp, X1m, dp, t1, np1, dp, s));
   GP_HIP(hipMemsetAsync(Zm, 0, (size_t)np2 * dp * sizeof(double), s));
   GP_TRY(launch_rowscale_add(Zm, dp, X2m, dp, t2, np2, dp, s));
@@ -1694,14 +1618,15 @@ static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta,
   GP_TRY(xty<R>(c, s, X2m, Zm, np2, dp, c->dCpad, false));
   GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
   GP_TRY(launch_symmetrize_avg(c->Mmat, dp, dp, s));
-  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + 10, c->upart, c->info + 3, s));
+  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
+                                c->info + INFO_METRIC, s));
   GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   const double* sc = c->scal_host;
-  const double sum_gvec = 0.5 * A * A * sc[2];                                               // -sum g_v
+  const double sum_gvec = 0.5 * A * A * sc[S_SUMF];                                               // -sum g_v
   return assemble_out(c, A, lambda0,
-                      sigma0_row_metric(sc, th.sigma0) + th.sigma0 * (2.0 * sc[20] + sc[21] + sc[22]) +
+                      sigma0_row_metric(sc, th.sigma0) + th.sigma0 * (2.0 * sc[S_RECT] + sc[S_RECT_U1] + sc[S_RECT_U2]) +
                           2.0 * th.sigma0 * sum_gvec,
                       0, d, 1, "gpfit_fit_eval_sparse: Cholesky of the projected K_tilde failed (non-positive pivot)",
                       "gpfit_fit_eval_sparse: Cholesky of V_b failed (non-positive pivot)", out_host);
@@ -1719,7 +1644,7 @@ int fit_eval_finish(gpfit_ctx* c, double* out_host) {
   else GP_HIP(hipStreamSynchronize(c->pend.stream));
   const double* sc = c->scal_host;
   const double sigma0 = c->pend.sigma0;
-  GP_TRY(assemble_out(c, c->pend.A, c->pend.lambda0, sigma0_row_metric(sc, sigma0) - 2.0 * sigma0 * sc[8],
+  GP_TRY(assemble_out(c, c->pend.A, c->pend.lambda0, sigma0_row_metric(sc, sigma0) - 2.0 * sigma0 * sc[S_ADJ_WL],
                       c->pend.np - c->pend.n, c->pend.d, c->pend.want_grad, "Cholesky of K_tilde failed: non-positive pivot",
                       "Cholesky of V failed: non-positive pivot", out_host));
   c->lv_valid = true;

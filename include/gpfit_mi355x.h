@@ -118,7 +118,8 @@ int gpfit_acosker_diag(gpfit_ctx* ctx, void* stream, double sigma0, const double
  * X[N][ldx] is the UN-masked stimulus matrix (device), r, m [N], V[N][ldv] symmetric (device).
  * out_host[16] (HOST): 0 loss = -(loglik - KL), 1 loglik, 2 KL, 3..8 d loss/d theta (dict order),
  *   9 log|K~|, 10 log|V|, 11 tr(K~^-1 V), 12 m^T K~^-1 m, 13 masked pixel count,
- *   14 info(K~), 15 info(V).
+ *   14 info(K~), 15 info(V).  (In the library: enum OutSlot of csrc/context.h -- OUT_LOSS, OUT_LOGLIK, OUT_KL,
+ *   OUT_GRAD, OUT_LOGDET_K, OUT_LOGDET_V, OUT_TRACE, OUT_MKM, OUT_D, OUT_INFO_K, OUT_INFO_V.)
  * want_grad: bit 0 = compute the gradients; bit 1 = V is unchanged since the previous call on
  * this context (constant during an M-step): reuse its Cholesky factor and log-det; bit 2 =
  * asynchronous: only enqueue on `stream` and return (out_host is not written); the caller collects

@@ -105,3 +105,72 @@ def test_group_with_an_unequal_top_split(dev):
         ref = np.array([grad[k] for k in KEYS])
         got = np.array([g["grad"][k] for k in KEYS])
         assert np.abs(ref - got).max() <= 1e-6 * np.abs(ref).max()
+
+
+SPLIT_SCRIPT = r"""
+import json, sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+from gaussian_processes_amd import synthetic as syn
+from gaussian_processes_amd.engine import GPFitEngine, fit_eval_group
+from oracle import gp_oracle as orc
+N, d, units = 640, 64, 3
+dev = torch.device("cuda:0")
+KEYS = syn.THETA_KEYS
+LOWER, UPPER = syn.limits()
+LOGA, LAM0 = syn.F_PARAMS["logA"], syn.F_PARAMS["lambda0"]
+T = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64))
+grid = syn.grid_for(d)
+X = T(syn.stimuli(N, d))
+inp = []
+for c in range(units):   # as cells() of the test module
+    r_np, m_np = syn.cell_inputs(N, c)
+    th0 = syn.theta0(c)
+    C0, mask0 = orc.spatial_metric(th0, LOWER, UPPER, grid)
+    V = 0.5 * orc.arccos_gram(th0, X[:, mask0], X[:, mask0], C0)
+    inp.append((T(r_np).to(dev), T(m_np).to(dev), V.to(dev), syn.theta_eval(c)))
+X = X.to(dev)
+engs = [GPFitEngine(N, d) for _ in range(units)]
+alone = [engs[0].fit_eval(th, LOWER, UPPER, grid, X, r, m, V, LOGA, LAM0, want_vectors=False) for r, m, V, th in inp]
+grouped = fit_eval_group(engs, [t[3] for t in inp], LOWER, UPPER, grid, X, [t[0] for t in inp], [t[1] for t in inp],
+                         [t[2] for t in inp], LOGA, LAM0)
+names = ("loss", "loglik", "KL", "logdet_K", "logdet_V", "tr_KinvV", "mKinvm")
+flat = lambda o: [float(o[k]).hex() for k in names] + [float(o["grad"][k]).hex() for k in KEYS]
+print("RESULT " + json.dumps({"alone": [flat(o) for o in alone], "grouped": [flat(o) for o in grouped]}))
+"""
+
+
+def test_recursive_two_sided_product_at_640(dev, tmp_path):
+    """The recursive two-sided product (two_sided_list's split), which the default GPFIT_TS_MIN = 4096 keeps out of
+    every other test's reach: with GPFIT_TS_MIN=256 (read once, hence a process of its own) N = 640 walks
+    640 -> 384 + 256 -> 256 + 128 -> 128 + 128, i.e. the unequal halves and the shared list of 2 cnt equal halves.  A
+    group of 3 against the same units one by one (same bits: loss, log-likelihood, KL, the four diagnostics, the six
+    gradients), the split's own products in the launch log, and every unit against the CPU oracle (tolerances of tests/test_gpu_parity.py: 1e-9 on the loss terms,
+    1e-6 of the largest component on the gradients)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "split.py"
+    script.write_text(SPLIT_SCRIPT)
+    env = dict(os.environ, GPFIT_TS_MIN="256", GPFIT_GEMM_LOG="1", PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    res = subprocess.run([sys.executable, str(script), root], env=env, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    # the split was really taken: its first product, Z21 = 1/2 Q22 B (256 x 384 x 256, Q read k-major, dense), is in the
+    # launch log of the first evaluation -- at the top level and, with N 128 K 256, one level down
+    import re
+    log = [ln for ln in res.stderr.splitlines() if "[gpfit gemm]" in ln]
+    for shape in ("M 256 N 384 K 256", "M 128 N 256 K 128"):
+        assert [ln for ln in log if re.search(shape + r" atri 0 btri 0 lower 0 nb 1 tile \d+ ak 1 bk 1 epi 0 .* alpha 0\.5 beta 0 ", ln)], shape
+    got = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("RESULT ")][0][7:])
+    assert got["alone"] == got["grouped"]
+    N, d, units = 640, 64, 3
+    grid, X, inp = cells(N, d, units, torch.device("cpu"))
+    for (r, m, V, th), row in zip(inp, got["alone"]):
+        loss, grad, p = orc.mstep_closure_cholesky(th, LOWER, UPPER, grid, X, r, m, V, LOGA, LAM0, want_parts=True)
+        vals = [float.fromhex(h) for h in row]
+        print(f"N=640 TS_MIN=256: loss {vals[0]!r} oracle {float(loss)!r}")
+        for gotv, ref in ((vals[0], loss), (vals[1], p["loglik"]), (vals[2], p["KL"])):
+            assert abs(gotv - float(ref)) <= 1e-9 * abs(float(ref))
+        ref = np.array([grad[k] for k in KEYS])
+        assert np.abs(ref - np.array(vals[7:])).max() <= 1e-6 * np.abs(ref).max()
