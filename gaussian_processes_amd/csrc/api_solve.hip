@@ -348,6 +348,77 @@ int gpfit_fparam_lbfgs(gpfit_ctx* c, void* stream, const double* lam_m, const do
   return 0;
 }
 
+static_assert(GPFIT_ESTEP_CHAIN_MAX_STEPS == CHAIN_MAX_STEPS, "the header states the cap of the chain block");
+
+int gpfit_estep_chain(gpfit_ctx* c, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
+                      const double* L, int64_t ldl, int64_t N, int64_t nb, const double* r, const double* kv0, double* m,
+                      double* f, double* V_out, int64_t ldv, double* lam_m, double* lam_var, double logA0,
+                      int lambda0_mode, double lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                      double tol_grad, double tol_change, double* rec_host) {
+  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS) {
+    set_error("gpfit_estep_chain: n_steps " + std::to_string(n_steps) + " is not within 1 .. " +
+              std::to_string(CHAIN_MAX_STEPS));
+    return -3;
+  }
+  if (!c || !a || !aL || !L || !r || !kv0 || !m || !f || !V_out || !lam_m || !lam_var || !rec_host || N <= 0 || N > INT32_MAX ||
+      nb <= 0 || lda < nb || ldal < nb || ldl < nb || ldv < nb) {
+    set_error("gpfit_estep_chain: bad argument");
+    return -3;
+  }
+  Lbfgs1dConfig cfg;
+  GP_TRY(fparam_lbfgs_config("gpfit_estep_chain", max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+  GP_CTX_ENTER(c, "gpfit_estep_chain");
+  hipStream_t s = (hipStream_t)stream;
+  const int n = (int)N, k = (int)nb;
+  const int nrows = (int)round_up(N, TILE), npc = (int)round_up(nb, TILE);
+  if (nrows > c->np_cap || npc > c->np_cap) {
+    set_error("gpfit_estep_chain: problem larger than the context capacity");
+    return -3;
+  }
+  const int64_t ld = npc;
+  // the work vectors and matrices of gpfit_estep_projected, product for product
+  double *sv = c->yv, *u = c->bv, *t2 = c->tvec, *z1 = c->mpad, *z = c->rpad, *mo = c->hvec;
+  double *Y = c->Tbuf, *Lp = c->Wbuf, *P = c->Abuf, *Vw = c->Zbuf, *part = c->TmpV, *aLp = c->LiVbuf, *Zm = c->Cos;
+  c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
+  const Lane lane = main_lane(c, s);
+  auto M = [&](double* X) { return mat(X, ld); };
+  ChainBlock* blk = c->chain;
+  const ChainGate gate{&blk->stop, c->info + INFO_K};
+  const size_t rec_bytes = (size_t)n_steps * CHAIN_REC * sizeof(double);
+  GP_HIP(hipMemsetAsync(&blk->rec[0][0], 0, rec_bytes, s));
+  GP_TRY(launch_chain_init(blk, logA0, lambda0_mode ? lambda0_fixed : 0.0, s));
+  // L does not change over the chain: packed once
+  GP_TRY(launch_pack_lower(L, ldl, k, Lp, ld, npc, s));
+  for (int step = 0; step < n_steps; ++step) {
+    double* rec = &blk->rec[step][0];
+    GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
+    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
+    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
+    GP_TRY(launch_estep_proj_rows_chain(a, lda, k, m, f, r, n, nrows, blk, rec, sv, u, s));
+    GP_TRY(launch_estep_proj_scale(aL, ldal, k, n, nrows, sv, u, Y, aLp, ld, npc, part, s));
+    GP_TRY((launch_reduce_slices<double, double>(part, npc, nrows / 32, t2, npc, s)));   // t2 = (a L)^T u
+    GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(M(Y)), plain(M(Y)), into_lower(M(c->Kbuf))));
+    GP_TRY(launch_add_diag(c->Kbuf, ld, npc, 1.0, s));
+    GP_TRY(potrf_lockstep(one_chain(c, ld), 0, npc, 1u, lane));
+    GP_TRY(launch_chain_info(blk, c->info + INFO_K, rec, s));
+    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
+    GP_TRY(launch_trmv_lower(c->Libuf, ld, npc, t2, z1, s));
+    GP_TRY(launch_trmv_lower_t(c->Libuf, ld, npc, z1, z, c->trmv_part, s));
+    GP_TRY(launch_trmv_lower(Lp, ld, npc, z, mo, s));
+    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(M(Lp))), trans(tril(M(c->Libuf))), into(M(P))));
+    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(M(P)), trans(M(P)), into_lower(M(Vw))));
+    GP_TRY(launch_chain_copy(gate, mo, k, m, s));
+    GP_TRY(launch_unpack_sym_chain(gate, Vw, ld, k, V_out, ldv, s));
+    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(M(aLp)), trans(tril(M(c->Libuf))), into(M(Zm))));
+    GP_TRY(launch_estep_proj_moments_chain(gate, Zm, ld, k, z1, kv0, n, lam_m, lam_var, s));
+    GP_TRY(launch_fparam_lbfgs_chain(gate, lam_m, lam_var, r, n, lambda0_mode ? 1 : 0, lambda0_fixed, cfg, f, blk, rec, s));
+  }
+  GP_HIP(hipMemcpyAsync(c->chain_host, &blk->rec[0][0], rec_bytes, hipMemcpyDeviceToHost, s));
+  GP_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[i] = c->chain_host[i];
+  return 0;
+}
+
 int gpfit_fparam_lbfgs_host(const double* lam_m, const double* lam_var, const double* r, int64_t N, double logA0,
                             int lambda0_mode, double lambda0_fixed, int max_iter, int history_size, double lr,
                             double tol_grad, double tol_change, double* f_out, double* out_host) {

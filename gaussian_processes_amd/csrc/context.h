@@ -34,6 +34,8 @@ struct gpfit_ctx {
   int* pix_host = nullptr;      // pinned
   int* info = nullptr;          // device [4]
   int* info_host = nullptr;     // pinned [4]
+  gpfit::ChainBlock* chain = nullptr;  // device: the state and step records of gpfit_estep_chain
+  double* chain_host = nullptr;        // pinned [CHAIN_MAX_STEPS][CHAIN_REC]: the records, one copy at the chain's end
   std::vector<void*> allocs;
   int split_k_M = 32;
 

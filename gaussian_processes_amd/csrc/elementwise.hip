@@ -1170,6 +1170,52 @@ int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_
   return 0;
 }
 
+// ---- the small kernels of a chained E-step (gpfit_estep_chain; kernels.h: ChainBlock, ChainGate)
+__global__ void chain_init_kernel(ChainBlock* __restrict__ blk, double logA0, double lambda0) {
+  blk->logA = logA0;
+  blk->lambda0 = lambda0;
+  blk->stop = 0;
+}
+int launch_chain_init(ChainBlock* blk, double logA0, double lambda0, hipStream_t s) {
+  hipLaunchKernelGGL(chain_init_kernel, dim3(1), dim3(1), 0, s, blk, logA0, lambda0);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ void chain_info_kernel(ChainBlock* __restrict__ blk, const int* __restrict__ info, double* __restrict__ rec) {
+  if (blk->stop != 0) return;   // a skipped step: its factorisation ran on workspace only, its record stays zero
+  const int v = *info;
+  rec[CR_INFO] = v;
+  if (v != 0) blk->stop = 1;
+}
+int launch_chain_info(ChainBlock* blk, const int* info, double* rec, hipStream_t s) {
+  hipLaunchKernelGGL(chain_info_kernel, dim3(1), dim3(1), 0, s, blk, info, rec);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ void chain_copy_kernel(ChainGate g, const double* __restrict__ src, int n, double* __restrict__ dst) {
+  if (!g.open()) return;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+int launch_chain_copy(ChainGate g, const double* src, int n, double* dst, hipStream_t s) {
+  hipLaunchKernelGGL(chain_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g, src, n, dst);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+// unpack_sym_kernel behind the gate
+__global__ void unpack_sym_chain_kernel(ChainGate g, const double* __restrict__ src, int64_t lds, int n,
+                                        double* __restrict__ dst, int64_t ldd) {
+  if (!g.open()) return;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+  if (i >= n || j >= n) return;
+  dst[(int64_t)i * ldd + j] = (j <= i) ? src[(int64_t)i * lds + j] : src[(int64_t)j * lds + i];
+}
+int launch_unpack_sym_chain(ChainGate g, const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s) {
+  hipLaunchKernelGGL(unpack_sym_chain_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, g, src, lds, n, dst, ldd);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 // dst[n][ldd] <- lower triangle of src, strict upper zeroed (triangular factor for the caller)
 __global__ void unpack_tri_kernel(const double* __restrict__ src, int64_t lds, int n, double* __restrict__ dst,
                                   int64_t ldd) {
@@ -1308,13 +1354,17 @@ struct Lbfgs1dLdsSlots {
 // shows 112 bytes per lane of register spills (the history itself is in LDS); the kernel averages 22 us per E-step.
 // out[0] final logA, [1] closed-form lambda0 there, [2] first loss, [3] last loss, [4] closure calls, [5] iterations,
 // [6] status (0 or the failing call), [7] logA and [8] lambda0 left by a failing call.  f: the rate at out[0..1].
-__global__ __launch_bounds__(1024) void fparam_lbfgs_kernel(const double* __restrict__ lam_m,
-                                                            const double* __restrict__ lam_var,
-                                                            const double* __restrict__ r, int n, double logA0,
-                                                            int lambda0_mode, double lambda0_fixed, Lbfgs1dConfig cfg,
-                                                            double* __restrict__ f, double* __restrict__ out) {
-  __shared__ double sh[17];
-  extern __shared__ double hist[];
+// (fparam_lbfgs_run is the optimiser itself, fparam_lbfgs_store its nine results: shared with the chain's kernel)
+struct FparamLbfgsRun {
+  Lbfgs1dResult res;
+  double lambda0, fail_x, fail_lambda0;
+};
+__device__ __forceinline__ FparamLbfgsRun fparam_lbfgs_run(const double* __restrict__ lam_m,
+                                                           const double* __restrict__ lam_var,
+                                                           const double* __restrict__ r, int n, double logA0,
+                                                           int lambda0_mode, double lambda0_fixed,
+                                                           const Lbfgs1dConfig& cfg, double* __restrict__ f, double* sh,
+                                                           double* hist) {
   const int hs = cfg.history_size;
   FparamClosure<FparamDevicePass> obj;
   obj.ev.lam_m = lam_m;
@@ -1329,25 +1379,64 @@ __global__ __launch_bounds__(1024) void fparam_lbfgs_kernel(const double* __rest
   obj.lambda0 = 0.0;
   obj.calls = 0;
   obj.fail_x = obj.fail_lambda0 = 0.0;
-  const Lbfgs1dResult res =
-      lbfgs1d_step<Lbfgs1dLdsSlots>(obj, logA0, cfg, Lbfgs1dStorage{hist, hist + hs, hist + 2 * hs, hist + 3 * hs});
-  double lambda0 = __builtin_nan("");
-  if (res.status == 0) {
+  FparamLbfgsRun o;
+  o.res = lbfgs1d_step<Lbfgs1dLdsSlots>(obj, logA0, cfg, Lbfgs1dStorage{hist, hist + hs, hist + 2 * hs, hist + 3 * hs});
+  o.lambda0 = __builtin_nan("");
+  if (o.res.status == 0) {
     // lambda0_and_rate() (utils.py:1934): the closed form at the final logA and the rate there
-    obj.ev.pass(res.x);
-    lambda0 = obj.ev.lambda0_closed();
-    if (f) fparam_rate(lam_m, lam_var, n, obj.ev.A, lambda0, f);
+    obj.ev.pass(o.res.x);
+    o.lambda0 = obj.ev.lambda0_closed();
+    if (f) fparam_rate(lam_m, lam_var, n, obj.ev.A, o.lambda0, f);
   }
+  o.fail_x = obj.fail_x;
+  o.fail_lambda0 = obj.fail_lambda0;
+  return o;
+}
+__device__ __forceinline__ void fparam_lbfgs_store(const FparamLbfgsRun& o, double* __restrict__ out) {
+  out[0] = o.res.x;
+  out[1] = o.lambda0;
+  out[2] = o.res.first_loss;
+  out[3] = o.res.last_loss;
+  out[4] = o.res.n_evals;
+  out[5] = o.res.n_iter;
+  out[6] = o.res.status;
+  out[7] = o.res.status ? o.fail_x : 0.0;
+  out[8] = o.res.status ? o.fail_lambda0 : 0.0;
+}
+__global__ __launch_bounds__(1024) void fparam_lbfgs_kernel(const double* __restrict__ lam_m,
+                                                            const double* __restrict__ lam_var,
+                                                            const double* __restrict__ r, int n, double logA0,
+                                                            int lambda0_mode, double lambda0_fixed, Lbfgs1dConfig cfg,
+                                                            double* __restrict__ f, double* __restrict__ out) {
+  __shared__ double sh[17];
+  extern __shared__ double hist[];
+  const FparamLbfgsRun o = fparam_lbfgs_run(lam_m, lam_var, r, n, logA0, lambda0_mode, lambda0_fixed, cfg, f, sh, hist);
+  if (threadIdx.x == 0) fparam_lbfgs_store(o, out);
+}
+// The optimiser of a chained step (gpfit_estep_chain): behind the gate, from the logA the block holds.  rec[0..8]: the
+// nine results, rec[CR_RAN] = 1.  Status 0 leaves (logA, lambda0) in the block for the next step (and the rate in f);
+// a failing closure call sets the stop word instead.
+__global__ __launch_bounds__(1024) void fparam_lbfgs_chain_kernel(ChainGate g, const double* __restrict__ lam_m,
+                                                                  const double* __restrict__ lam_var,
+                                                                  const double* __restrict__ r, int n, int lambda0_mode,
+                                                                  double lambda0_fixed, Lbfgs1dConfig cfg,
+                                                                  double* __restrict__ f, ChainBlock* blk,
+                                                                  double* __restrict__ rec) {
+  __shared__ double sh[17];
+  extern __shared__ double hist[];
+  if (!g.open()) return;   // the same two words in every thread: uniform
+  const double logA0 = blk->logA;
+  const FparamLbfgsRun o = fparam_lbfgs_run(lam_m, lam_var, r, n, logA0, lambda0_mode, lambda0_fixed, cfg, f, sh, hist);
+  __syncthreads();         // every thread has read the gate and the block before thread 0 writes them
   if (threadIdx.x == 0) {
-    out[0] = res.x;
-    out[1] = lambda0;
-    out[2] = res.first_loss;
-    out[3] = res.last_loss;
-    out[4] = res.n_evals;
-    out[5] = res.n_iter;
-    out[6] = res.status;
-    out[7] = res.status ? obj.fail_x : 0.0;
-    out[8] = res.status ? obj.fail_lambda0 : 0.0;
+    fparam_lbfgs_store(o, rec + CR_LBFGS);
+    rec[CR_RAN] = 1.0;
+    if (o.res.status == 0) {
+      blk->logA = o.res.x;
+      blk->lambda0 = o.lambda0;
+    } else {
+      blk->stop = 1;
+    }
   }
 }
 
@@ -1357,6 +1446,15 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
   const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
   hipLaunchKernelGGL(fparam_lbfgs_kernel, dim3(1), dim3(1024), lds, s, lam_m, lam_var, r, n, logA0, lambda0_mode,
                      lambda0_fixed, cfg, f, out);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_fparam_lbfgs_chain(ChainGate g, const double* lam_m, const double* lam_var, const double* r, int n,
+                              int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f,
+                              ChainBlock* blk, double* rec, hipStream_t s) {
+  const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
+  hipLaunchKernelGGL(fparam_lbfgs_chain_kernel, dim3(1), dim3(1024), lds, s, g, lam_m, lam_var, r, n, lambda0_mode,
+                     lambda0_fixed, cfg, f, blk, rec);
   GP_HIP(hipGetLastError());
   return 0;
 }

@@ -1758,6 +1758,7 @@ int gpfit_ctx_create(int device, int64_t n_max, int64_t d_max, int64_t d_full_ma
   }
   if (!rc) rc = dev_alloc(c, &c->pix, (size_t)c->dfull_cap);
   if (!rc) rc = dev_alloc(c, &c->info, 4);
+  if (!rc) rc = dev_alloc(c, &c->chain, 1);
   if (rc) {
     gpfit_ctx_destroy(c);
     return rc;
@@ -1768,6 +1769,7 @@ int gpfit_ctx_create(int device, int64_t n_max, int64_t d_max, int64_t d_full_ma
   GP_HIP(hipHostMalloc((void**)&c->scal_host, 64 * sizeof(double), HOST_FLAGS));
   GP_HIP(hipHostMalloc((void**)&c->pix_host, (size_t)c->dfull_cap * sizeof(int), HOST_FLAGS));
   GP_HIP(hipHostMalloc((void**)&c->info_host, 4 * sizeof(int), HOST_FLAGS));
+  GP_HIP(hipHostMalloc((void**)&c->chain_host, (size_t)CHAIN_MAX_STEPS * CHAIN_REC * sizeof(double), HOST_FLAGS));
   {
     // the aux stream only packs V while the kernel matrix is being built, off the critical path: lowest priority,
     // so that whenever both streams have work ready the main stream's kernel build is dispatched first
@@ -1798,6 +1800,7 @@ void gpfit_ctx_destroy(gpfit_ctx* c) {
   if (c->scal_host) (void)hipHostFree(c->scal_host);
   if (c->pix_host) (void)hipHostFree(c->pix_host);
   if (c->info_host) (void)hipHostFree(c->info_host);
+  if (c->chain_host) (void)hipHostFree(c->chain_host);
   if (c->aux) (void)hipStreamDestroy(c->aux);
   if (c->side) (void)hipStreamDestroy(c->side);
   for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);

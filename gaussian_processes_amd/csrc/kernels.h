@@ -210,4 +210,47 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
                         int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f, double* out,
                         hipStream_t s);
 
+// ---- chained E-steps (gpfit_estep_chain): nEstep x (Newton update, moments, rate-parameter L-BFGS) enqueued in one go.
+// What a step hands to the next stays on the device in a ChainBlock; no kernel waits on another, every launch that
+// makes a step visible to the caller tests the gate first.
+constexpr int CHAIN_MAX_STEPS = 1024;   // GPFIT_ESTEP_CHAIN_MAX_STEPS of the public header
+constexpr int CHAIN_REC = 12;           // doubles per step record
+enum ChainRecSlot {
+  CR_LBFGS = 0,   // 0-8: the nine results of the optimiser (launch_fparam_lbfgs)
+  CR_INFO = 9,    // LAPACK info of W = I + L^T G L
+  CR_RAN = 10,    // 1: the step ran and was committed; 0: skipped (or its factorisation failed)
+  CR_A = 11,      // the A = exp(logA) of the step's Newton update
+};
+struct ChainBlock {
+  double logA;            // what the optimiser of the last committed step left: the next step starts from it
+  double lambda0;         // the closed-form lambda0 that step left (its record's slot 1); informational, nothing reads it
+  int stop, pad;          // non-zero once a step has failed: nothing is committed from then on
+  double rec[CHAIN_MAX_STEPS][CHAIN_REC];
+};
+// Open while no earlier step has failed and this step's factorisation has not (block-uniform: two scalar loads).
+struct ChainGate {
+  const int* stop;
+  const int* info;
+  __device__ __forceinline__ bool open() const { return *stop == 0 && *info == 0; }
+};
+// block <- (logA0, lambda0, stop = 0); the records are zeroed by the caller
+int launch_chain_init(ChainBlock* blk, double logA0, double lambda0, hipStream_t s);
+// launch_estep_proj_rows with A = exp(blk->logA) formed on the device (the same row body: equal A, equal bits);
+// rec[CR_A] <- A unless the chain has stopped
+int launch_estep_proj_rows_chain(const double* a, int64_t lda, int nb, const double* mb, const double* f, const double* r,
+                                 int n, int nrows, const ChainBlock* blk, double* rec, double* sv, double* u,
+                                 hipStream_t s);
+// behind the factorisation (one thread): rec[CR_INFO] <- *info, and the stop word is set when it is non-zero
+int launch_chain_info(ChainBlock* blk, const int* info, double* rec, hipStream_t s);
+// the commits of a step, each behind the gate: dst <- src, launch_unpack_sym, launch_estep_proj_moments
+int launch_chain_copy(ChainGate g, const double* src, int n, double* dst, hipStream_t s);
+int launch_unpack_sym_chain(ChainGate g, const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
+int launch_estep_proj_moments_chain(ChainGate g, const double* Z, int64_t ld, int nb, const double* z1, const double* kv0,
+                                    int n, double* lam_m, double* lam_var, hipStream_t s);
+// launch_fparam_lbfgs behind the gate, started at blk->logA: rec[0..8] <- its results and rec[CR_RAN] <- 1; with status 0
+// it leaves (logA, lambda0) in the block and the rate in f, otherwise it sets the stop word
+int launch_fparam_lbfgs_chain(ChainGate g, const double* lam_m, const double* lam_var, const double* r, int n,
+                              int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f,
+                              ChainBlock* blk, double* rec, hipStream_t s);
+
 }  // namespace gpfit

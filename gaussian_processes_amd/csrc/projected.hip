@@ -152,10 +152,11 @@ int launch_proj_trace(const double* A, int64_t lda, int n, double* out, hipStrea
 // ---- fused E-step in the projected basis (gpfit_estep_projected, api_solve.hip)
 // One wave per training point i: lam = a_i . m_b, s_i = A sqrt(f_i), u_i = A^2 f_i lam + A (r_i - f_i)
 // (the right-hand side G m + g of utils.py:1431 before its projection a^T); zero on the padding rows.
-__global__ __launch_bounds__(256) void estep_proj_rows_kernel(const double* __restrict__ a, int64_t lda, int nb,
-                                                               const double* __restrict__ mb, const double* __restrict__ f,
-                                                               const double* __restrict__ r, int n, int nrows, double A,
-                                                               double* __restrict__ sv, double* __restrict__ u) {
+// (the body is shared by the by-value kernel and the chain's, which forms A on the device: equal A, equal bits)
+__device__ __forceinline__ void estep_proj_rows_body(const double* __restrict__ a, int64_t lda, int nb,
+                                                     const double* __restrict__ mb, const double* __restrict__ f,
+                                                     const double* __restrict__ r, int n, int nrows, double A,
+                                                     double* __restrict__ sv, double* __restrict__ u) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= nrows) return;
@@ -175,6 +176,24 @@ __global__ __launch_bounds__(256) void estep_proj_rows_kernel(const double* __re
       u[i] = 0.0;
     }
   }
+}
+__global__ __launch_bounds__(256) void estep_proj_rows_kernel(const double* __restrict__ a, int64_t lda, int nb,
+                                                               const double* __restrict__ mb, const double* __restrict__ f,
+                                                               const double* __restrict__ r, int n, int nrows, double A,
+                                                               double* __restrict__ sv, double* __restrict__ u) {
+  estep_proj_rows_body(a, lda, nb, mb, f, r, n, nrows, A, sv, u);
+}
+// A step of gpfit_estep_chain: A = exp(logA) of the chain block, recorded for the caller while the chain runs
+__global__ __launch_bounds__(256) void estep_proj_rows_chain_kernel(const double* __restrict__ a, int64_t lda, int nb,
+                                                                     const double* __restrict__ mb,
+                                                                     const double* __restrict__ f,
+                                                                     const double* __restrict__ r, int n, int nrows,
+                                                                     const ChainBlock* __restrict__ blk,
+                                                                     double* __restrict__ rec, double* __restrict__ sv,
+                                                                     double* __restrict__ u) {
+  const double A = exp(blk->logA);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && blk->stop == 0) rec[CR_A] = A;
+  estep_proj_rows_body(a, lda, nb, mb, f, r, n, nrows, A, sv, u);
 }
 
 // Y[i][j] = s_i aL[i][j], zero padded to [nrows][ld] (and, if asked for, the zero-padded copy aLp of aL itself);
@@ -205,6 +224,14 @@ int launch_estep_proj_rows(const double* a, int64_t lda, int nb, const double* m
   GP_HIP(hipGetLastError());
   return 0;
 }
+int launch_estep_proj_rows_chain(const double* a, int64_t lda, int nb, const double* mb, const double* f, const double* r,
+                                 int n, int nrows, const ChainBlock* blk, double* rec, double* sv, double* u,
+                                 hipStream_t s) {
+  hipLaunchKernelGGL(estep_proj_rows_chain_kernel, dim3((nrows + 3) / 4), dim3(256), 0, s, a, lda, nb, mb, f, r, n,
+                     nrows, blk, rec, sv, u);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
 int launch_estep_proj_scale(const double* aL, int64_t ldal, int nb, int n, int nrows, const double* sv, const double* u,
                             double* Y, double* aLp, int64_t ld, int npc, double* part, hipStream_t s) {
   hipLaunchKernelGGL(estep_proj_scale_kernel, dim3((npc + 255) / 256, nrows / 32), dim3(256), 0, s, aL, ldal, nb, n, sv,
@@ -215,10 +242,9 @@ int launch_estep_proj_scale(const double* aL, int64_t ldal, int nb, int n, int n
 
 // The moments of lambda behind the update, from Z = aL L_W^-T (one wave per training point):
 //   lam_m_i = a_i . m_new = Z_i . z1 (z1 = L_W^-1 aL^T u),  lam_var_i = kv0_i + a_i V_new a_i^T = kv0_i + |Z_i|^2
-__global__ __launch_bounds__(256) void estep_proj_moments_kernel(const double* __restrict__ Z, int64_t ld, int nb,
-                                                                  const double* __restrict__ z1,
-                                                                  const double* __restrict__ kv0, int n,
-                                                                  double* __restrict__ lam_m, double* __restrict__ lam_var) {
+__device__ __forceinline__ void estep_proj_moments_body(const double* __restrict__ Z, int64_t ld, int nb,
+                                                       const double* __restrict__ z1, const double* __restrict__ kv0,
+                                                       int n, double* __restrict__ lam_m, double* __restrict__ lam_var) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
@@ -238,9 +264,31 @@ __global__ __launch_bounds__(256) void estep_proj_moments_kernel(const double* _
     lam_var[i] = kv0[i] + s1;
   }
 }
+__global__ __launch_bounds__(256) void estep_proj_moments_kernel(const double* __restrict__ Z, int64_t ld, int nb,
+                                                                  const double* __restrict__ z1,
+                                                                  const double* __restrict__ kv0, int n,
+                                                                  double* __restrict__ lam_m, double* __restrict__ lam_var) {
+  estep_proj_moments_body(Z, ld, nb, z1, kv0, n, lam_m, lam_var);
+}
+// the same behind the gate of a chained step (gpfit_estep_chain)
+__global__ __launch_bounds__(256) void estep_proj_moments_chain_kernel(ChainGate g, const double* __restrict__ Z,
+                                                                        int64_t ld, int nb, const double* __restrict__ z1,
+                                                                        const double* __restrict__ kv0, int n,
+                                                                        double* __restrict__ lam_m,
+                                                                        double* __restrict__ lam_var) {
+  if (!g.open()) return;
+  estep_proj_moments_body(Z, ld, nb, z1, kv0, n, lam_m, lam_var);
+}
 int launch_estep_proj_moments(const double* Z, int64_t ld, int nb, const double* z1, const double* kv0, int n,
                               double* lam_m, double* lam_var, hipStream_t s) {
   hipLaunchKernelGGL(estep_proj_moments_kernel, dim3((n + 3) / 4), dim3(256), 0, s, Z, ld, nb, z1, kv0, n, lam_m, lam_var);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_estep_proj_moments_chain(ChainGate g, const double* Z, int64_t ld, int nb, const double* z1, const double* kv0,
+                                    int n, double* lam_m, double* lam_var, hipStream_t s) {
+  hipLaunchKernelGGL(estep_proj_moments_chain_kernel, dim3((n + 3) / 4), dim3(256), 0, s, g, Z, ld, nb, z1, kv0, n, lam_m,
+                     lam_var);
   GP_HIP(hipGetLastError());
   return 0;
 }

@@ -622,6 +622,61 @@ def _estep_projected(r, KKtilde_inv, aL, L, m, f_params, f_mean, kv0=None):
     return m_new, V_new
 
 
+CHAIN_MAX_STEPS = 1024   # GPFIT_ESTEP_CHAIN_MAX_STEPS of the C header
+
+
+def _estep_chain(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
+                 lambda_m=None, lambda_var=None):
+    """``n_steps`` E-steps between two kernel rebuilds (utils.py:1864-1934: ``_estep_projected`` with its moments, then
+    ``_fparam_lbfgs``) as ONE device call and one wait (``gpfit_estep_chain``): ``logA``, ``lambda0`` and the rate stay
+    on the device between the steps.  ``lambda0_fixed``: the optimiser's closure evaluates at this lambda0 (lambda0_mode
+    1 of ``gpfit_fparam_lbfgs``); the rate it leaves for the next step is still the one at the closed-form lambda0, as
+    that call leaves it, so this is not the host loop of a fit whose f_params carry loglambda0 (``varGP`` keeps the
+    loop there).  Returns
+    copies ``(m, V, lambda_m, lambda_var, f, records)`` of the state behind the last step that ran -- the arguments are
+    left alone -- and one 12-number record per step (include/gpfit_mi355x.h); ``V``, ``lambda_m``, ``lambda_var`` given
+    here are what comes back when no step commits.  ``_estep_chain_commit`` turns the records into f_params or into the
+    error of the first failing step."""
+    r, a, aL, L, kv0 = (_cu(t).contiguous() for t in (r, KKtilde_inv, aL, L, kv0))
+    N, nb = a.shape
+    dev = a.device
+    m = _cu(m).clone().contiguous()
+    f = _cu(f_mean).clone().contiguous()
+    V = torch.empty((nb, nb), dtype=TORCH_DTYPE, device=dev) if V is None else _cu(V).clone().contiguous()
+    lam_m = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_m is None else _cu(lambda_m).clone().contiguous()
+    lam_var = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_var is None else _cu(lambda_var).clone().contiguous()
+    eng = get_engine(max(N, nb), 1)
+    n_steps = int(n_steps)
+    rec = (ctypes.c_double * (12 * max(n_steps, 1)))()
+    fixed = lambda0_fixed is not None
+    _lib.check(_lib.load().gpfit_estep_chain(eng._ctx, _stream(), a.data_ptr(), a.stride(0), aL.data_ptr(), aL.stride(0),
+                                             L.data_ptr(), L.stride(0), N, nb, r.data_ptr(), kv0.data_ptr(), m.data_ptr(),
+                                             f.data_ptr(), V.data_ptr(), V.stride(0), lam_m.data_ptr(), lam_var.data_ptr(),
+                                             float(logA0), 1 if fixed else 0, float(lambda0_fixed) if fixed else 0.0,
+                                             n_steps, int(n_fparam_steps), int(n_fparam_steps), 0.1, 1.e-7, 1.e-9, rec),
+               "gpfit_estep_chain")
+    return m, V, lam_m, lam_var, f, [list(rec[12 * k:12 * k + 12]) for k in range(n_steps)]
+
+
+def _estep_chain_commit(records, f_params):
+    """Walk the records of ``_estep_chain`` as the host loop would have met them: ``f_params['logA']`` is filled in
+    place and ``f_params['lambda0']`` set after every step that ran; the first failing step raises what
+    ``_estep_projected`` / ``_fparam_lbfgs`` raise for it.  Returns the last record."""
+    for k, rec in enumerate(records):
+        if rec[9] != 0:
+            raise torch.linalg.LinAlgError(f"Estep: I + L^T G L is not positive definite (info={int(rec[9])})")
+        if rec[10] != 1:
+            raise _lib.GpfitError(f"gpfit_estep_chain: step {k} was skipped without a failing step before it")
+        status = int(rec[6])
+        with torch.no_grad():
+            f_params['logA'].fill_(rec[7] if status else rec[0])      # the same tensor, as LBFGS's p.add_ leaves it
+        f_params['lambda0'] = torch.tensor(rec[8] if status else rec[1], dtype=TORCH_DTYPE)
+        if status:
+            raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been called {status} times in '
+                             f'estep {k} iteration.')                                                        # :1923
+    return records[-1]
+
+
 # ------------------------------------------------------------------ inference
 def lambda_moments_star(xstar, xtilde, C, theta, K_tilde, K_tilde_inv, m, V, B, kernfun):
     """Predictive moments of lambda at test points (utils.py:1476-1500).  ``xstar`` may hold
@@ -951,6 +1006,10 @@ _DENSE_MIN_N = 256     # below this the reference's own eigh (a few ms)
 #   "eigenvectors" the reference's own choice (utils.py:1683-1694): the kept eigenvectors, K_tilde_b diagonal, at the
 #                  price of one k x k eigendecomposition (k = 1024) per basis: 16 ms more per EM iteration.
 EIGTOP_BASIS = _os_mod.environ.get("GPFIT_EIGTOP_BASIS", "subspace")
+# The nEstep updates of an EM iteration in the truncated / sparse regimes as one device call (_estep_chain) instead of
+# two calls and two waits per update (module global read at call time; GPFIT_ESTEP_CHAIN=0 turns it off).  A = exp(logA)
+# is then the device's exp, not the host's: a fit may differ from the loop's by rounding.
+ESTEP_CHAIN = _os_mod.environ.get("GPFIT_ESTEP_CHAIN", "1") != "0"
 # per host thread (the reference's active-learning notebook fits and scores on two threads): the route the last
 # call of _stabilised_basis took, and (N, EIGVAL_TOL) -> "full" | "truncated", which of the two rank checks to try
 # first -- a hint only, so one thread's history never changes what another thread's fit costs
@@ -1459,58 +1518,83 @@ def varGP(x, r, **kwargs):
 
             t0 = time.time()
             if nEstep > 0:
-                for i_estep in range(nEstep):
-                    if i_estep == 0 and nMstep > 0:
+                if (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params
+                        and not full_rank()):
+                    # the nEstep updates of this iteration as one device call (the loop below, enqueued in one go).
+                    # The host loop stays (silently: the "E-steps" time is then the loop's) for more updates than the
+                    # chain's cap, and for f_params carrying loglambda0: the optimiser leaves the rate at the
+                    # closed-form lambda0, which is what the next update reads in the chain, while the loop evaluates
+                    # it anew at the fixed lambda0 (rate_now, :1877)
+                    if nMstep > 0:
                         lambda_m, lambda_var = moments_now()                                  # :1871
                         f_params['lambda0'] = lambda0_and_rate()                              # :1874
                     f_mean = rate_now()                                                         # :1877
-                    fused_moments = False
-                    if full_rank():
-                        # fused Newton update in the original basis, then back to the eigenbasis
-                        m_orig = m_b if _is_identity(B) else matmul(B, m_b)
-                        m_new = torch.empty(nt, dtype=TORCH_DTYPE, device=dev)
-                        V_new = torch.empty((nt, nt), dtype=TORCH_DTYPE, device=dev)
-                        eng = get_engine(nt, 1)
-                        rc = _lib.load().gpfit_estep(eng._ctx, _stream(), K_tilde.data_ptr(), K_tilde.stride(0), nt,
-                                                     r.data_ptr(), m_orig.data_ptr(), f_mean.data_ptr(),
-                                                     _scalar(f_params['logA']), m_new.data_ptr(), V_new.data_ptr(),
-                                                     V_new.stride(0))
-                        if rc != 0:
-                            if not bool(torch.isfinite(f_mean).all()):
-                                # the reference's LU solve lets NaNs through and reports them one step
-                                # later, in the rate-parameter closure (utils.py:1923-1924)
-                                raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been '
-                                                 f'called 1 times in estep {i_estep} iteration. Try substituting '
-                                                 f'them with inf.')
-                            raise torch.linalg.LinAlgError(f"Estep: {_lib.last_error()} (rc={rc})")
-                        if _is_identity(B):
-                            m_b, V_b = m_new, V_new            # symmetric by construction (gpfit_estep)
+                    if estep_factor[0] is None or estep_factor[0][0] is not K_tilde_b:
+                        L_kb, _, _, info_kb = cholesky(K_tilde_b)
+                        if info_kb != 0:
+                            raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info_kb})")
+                        estep_factor[0] = (K_tilde_b, L_kb, matmul(KKtilde_inv_b, L_kb),
+                                           Kvec - torch.sum(K_b * KKtilde_inv_b, 1))
+                    m_b, V_b, lambda_m, lambda_var, f_fp, chain_rec = _estep_chain(
+                        r, KKtilde_inv_b, estep_factor[0][2], estep_factor[0][1], estep_factor[0][3], m_b, f_mean,
+                        _scalar(f_params['logA']), nEstep, nFparamstep, V=V_b, lambda_m=lambda_m,
+                        lambda_var=lambda_var)
+                    last_rec = _estep_chain_commit(chain_rec, f_params)     # raises for the first failing step
+                    rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), last_rec[1], f_fp)
+                    # (the rate-parameter share of the call is not separable: times['fparams'] stays as it is)
+                else:
+                    for i_estep in range(nEstep):
+                        if i_estep == 0 and nMstep > 0:
+                            lambda_m, lambda_var = moments_now()                                  # :1871
+                            f_params['lambda0'] = lambda0_and_rate()                              # :1874
+                        f_mean = rate_now()                                                         # :1877
+                        fused_moments = False
+                        if full_rank():
+                            # fused Newton update in the original basis, then back to the eigenbasis
+                            m_orig = m_b if _is_identity(B) else matmul(B, m_b)
+                            m_new = torch.empty(nt, dtype=TORCH_DTYPE, device=dev)
+                            V_new = torch.empty((nt, nt), dtype=TORCH_DTYPE, device=dev)
+                            eng = get_engine(nt, 1)
+                            rc = _lib.load().gpfit_estep(eng._ctx, _stream(), K_tilde.data_ptr(), K_tilde.stride(0), nt,
+                                                         r.data_ptr(), m_orig.data_ptr(), f_mean.data_ptr(),
+                                                         _scalar(f_params['logA']), m_new.data_ptr(), V_new.data_ptr(),
+                                                         V_new.stride(0))
+                            if rc != 0:
+                                if not bool(torch.isfinite(f_mean).all()):
+                                    # the reference's LU solve lets NaNs through and reports them one step
+                                    # later, in the rate-parameter closure (utils.py:1923-1924)
+                                    raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been '
+                                                     f'called 1 times in estep {i_estep} iteration. Try substituting '
+                                                     f'them with inf.')
+                                raise torch.linalg.LinAlgError(f"Estep: {_lib.last_error()} (rc={rc})")
+                            if _is_identity(B):
+                                m_b, V_b = m_new, V_new            # symmetric by construction (gpfit_estep)
+                            else:
+                                m_b = matmul(B, m_new, transA=True)
+                                V_b = matmul(B, matmul(V_new, B), transA=True)
+                                V_b = (V_b + V_b.T) / 2
                         else:
-                            m_b = matmul(B, m_new, transA=True)
-                            V_b = matmul(B, matmul(V_new, B), transA=True)
-                            V_b = (V_b + V_b.T) / 2
-                    else:
-                        # :1880, with the factor of K~_b shared by the E-steps of this iteration
-                        if estep_factor[0] is None or estep_factor[0][0] is not K_tilde_b:
-                            L_kb, _, _, info_kb = cholesky(K_tilde_b)
-                            if info_kb != 0:
-                                raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info_kb})")
-                            estep_factor[0] = (K_tilde_b, L_kb, matmul(KKtilde_inv_b, L_kb),
-                                               Kvec - torch.sum(K_b * KKtilde_inv_b, 1))
-                        # the update and the moments behind it (:1884) in one device call
-                        m_b, V_b, lambda_m, lambda_var = _estep_projected(r, KKtilde_inv_b, estep_factor[0][2],
-                                                                          estep_factor[0][1], m_b, f_params, f_mean,
-                                                                          kv0=estep_factor[0][3])
-                        fused_moments = True
-                    if not fused_moments:
-                        lambda_m, lambda_var = moments_now()                                    # :1884
-                    # (the reference evaluates the rate here, :1885; nothing reads it before the closure below overwrites it)
-                    tf = time.time()
-                    # :1892-1934 (lambda0_given_logA, the LBFGS over logA with its closure, lambda0_and_rate) in one
-                    # device call; the rate it leaves is the one rate_now() is asked for next
-                    f_fp, lambda0_fp = _fparam_lbfgs(lambda_m, lambda_var, r, f_params, nFparamstep, i_estep)
-                    rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), lambda0_fp, f_fp)
-                    times['fparams'] += time.time() - tf
+                            # :1880, with the factor of K~_b shared by the E-steps of this iteration
+                            if estep_factor[0] is None or estep_factor[0][0] is not K_tilde_b:
+                                L_kb, _, _, info_kb = cholesky(K_tilde_b)
+                                if info_kb != 0:
+                                    raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info_kb})")
+                                estep_factor[0] = (K_tilde_b, L_kb, matmul(KKtilde_inv_b, L_kb),
+                                                   Kvec - torch.sum(K_b * KKtilde_inv_b, 1))
+                            # the update and the moments behind it (:1884) in one device call
+                            m_b, V_b, lambda_m, lambda_var = _estep_projected(r, KKtilde_inv_b, estep_factor[0][2],
+                                                                              estep_factor[0][1], m_b, f_params, f_mean,
+                                                                              kv0=estep_factor[0][3])
+                            fused_moments = True
+                        if not fused_moments:
+                            lambda_m, lambda_var = moments_now()                                    # :1884
+                        # (the reference evaluates the rate here, :1885; nothing reads it before the closure below overwrites it)
+                        tf = time.time()
+                        # :1892-1934 (lambda0_given_logA, the LBFGS over logA with its closure, lambda0_and_rate) in one
+                        # device call; the rate it leaves is the one rate_now() is asked for next
+                        f_fp, lambda0_fp = _fparam_lbfgs(lambda_m, lambda_var, r, f_params, nFparamstep, i_estep)
+                        rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), lambda0_fp, f_fp)
+                        times['fparams'] += time.time() - tf
             else:
                 print('No E-step')
             times['estep'] += time.time() - t0

@@ -292,6 +292,33 @@ int gpfit_fparam_lbfgs_host(const double* lam_m, const double* lam_var, const do
                             int history_size, double lr, double tol_grad, double tol_change, double* f_out,
                             double* out_host);
 
+/* The E-steps between two kernel rebuilds as ONE call (varGP utils.py:1864-1934 in the truncated and sparse regimes):
+ * n_steps x (gpfit_estep_projected with its moments, then gpfit_fparam_lbfgs started at the logA in force), everything
+ * enqueued on `stream`, one synchronisation at the end.  logA, lambda0 and the rate stay on the device between steps.
+ * Fixed: a, aL, L, r, kv0 as in gpfit_estep_projected (kv0 is required here).  State, device, in/out: m [nb], f [N]
+ * (updated in place: each step's first kernel consumes both before anything of that step writes them).  Outputs, device:
+ * V[nb][ldv], lam_m [N], lam_var [N] of the last step that ran.  By value: logA0, lambda0_mode / lambda0_fixed and the
+ * optimiser's max_iter, history_size, lr, tol_grad, tol_change as in gpfit_fparam_lbfgs;
+ * 1 <= n_steps <= GPFIT_ESTEP_CHAIN_MAX_STEPS.
+ * rec_host[n_steps][12], one record per step: [0..8] out_host of gpfit_fparam_lbfgs, [9] LAPACK info of W = I + L^T G L,
+ * [10] 1 when the step ran and its results were committed, 0 when it was skipped or its factorisation failed,
+ * [11] the A = exp(logA) its Newton update used (exp of the device; gpfit_estep_projected takes the host's).  At equal
+ * A a step gives the bits of the two calls it stands for.
+ * With lambda0_mode = 1 a step is still exactly those two calls: the rate it leaves in f, which the next step's update
+ * reads, is the one gpfit_fparam_lbfgs writes, at the closed-form lambda0 of the final logA and not at lambda0_fixed.
+ * varGP with f_params carrying loglambda0 evaluates the rate at the fixed lambda0 before every update
+ * (utils.py:1877 -> :1136): such a caller keeps its host loop.
+ * A step whose W is not positive definite (info != 0) commits nothing; a step whose optimiser fails (status != 0) has
+ * committed m, V and the moments, and leaves f, logA and lambda0 alone.  After either, no later step changes m, V, f,
+ * lam_m, lam_var, logA or lambda0, and its record is all zero.
+ * Returns 0 when the chain ran, whatever the records say; < 0 on bad arguments or insufficient capacity. */
+#define GPFIT_ESTEP_CHAIN_MAX_STEPS 1024
+int gpfit_estep_chain(gpfit_ctx* ctx, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
+                      const double* L, int64_t ldl, int64_t N, int64_t nb, const double* r, const double* kv0,
+                      double* m, double* f, double* V, int64_t ldv, double* lam_m, double* lam_var, double logA0,
+                      int lambda0_mode, double lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                      double tol_grad, double tol_change, double* rec_host);
+
 /* Active-learning utility of nstar candidate stimuli, U = H(r|x,D) - <H(r|f,x)>
  * (nd_utility with nd_p_r_given_xD, nd_lambda_r_mean, nd_mean_noise_entropy, utils.py:413-525;
  * call site one_cell_active_training.ipynb: u2d = nd_utility(logf_var, logf_mean, arange(100))).
