@@ -4,6 +4,7 @@
 #include "product.h"
 #include "gpfit_mi355x.h"
 
+#include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -416,6 +417,106 @@ int gpfit_estep_chain(gpfit_ctx* c, void* stream, const double* a, int64_t lda, 
   GP_HIP(hipMemcpyAsync(c->chain_host, &blk->rec[0][0], rec_bytes, hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[i] = c->chain_host[i];
+  return 0;
+}
+
+static_assert(GPFIT_ESTEP_CHAIN_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+
+int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a, const int64_t* lda,
+                            const double* const* aL, const int64_t* ldal, const double* const* L, const int64_t* ldl,
+                            int64_t N, const int64_t* nb, const double* const* r, const double* const* kv0,
+                            double* const* m, double* const* f, double* const* V, const int64_t* ldv,
+                            double* const* lam_m, double* const* lam_var, const double* logA0, int lambda0_mode,
+                            const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                            double tol_grad, double tol_change, double* rec_host) {
+  const char* name = "gpfit_estep_chain_batch";
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(name) + ": " + why);
+    return -3;
+  };
+  if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS)
+    return refuse("n_steps " + std::to_string(n_steps) + " is not within 1 .. " + std::to_string(CHAIN_MAX_STEPS));
+  if (!ctxs || !a || !lda || !aL || !ldal || !L || !ldl || !nb || !r || !kv0 || !m || !f || !V || !ldv || !lam_m || !lam_var ||
+      !logA0 || (lambda0_mode && !lambda0_fixed) || !rec_host || N <= 0 || N > INT32_MAX)
+    return refuse("bad argument");
+  Lbfgs1dConfig cfg;
+  GP_TRY(fparam_lbfgs_config(name, max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+  const int nrows = (int)round_up(N, TILE);
+  for (int u = 0; u < n_units; ++u) {
+    const std::string unit = "unit " + std::to_string(u) + ": ";
+    if (!ctxs[u] || !a[u] || !aL[u] || !L[u] || !r[u] || !kv0[u] || !m[u] || !f[u] || !V[u] || !lam_m[u] || !lam_var[u])
+      return refuse(unit + "null context or operand");
+    if (nb[u] <= 0 || lda[u] < nb[u] || ldal[u] < nb[u] || ldl[u] < nb[u] || ldv[u] < nb[u])
+      return refuse(unit + "bad size or leading dimension");
+    if (ctxs[u]->device != ctxs[0]->device) return refuse("the contexts of one call must live on one device");
+    for (int v = 0; v < u; ++v)
+      if (ctxs[v] == ctxs[u]) return refuse("every unit needs a context of its own");
+    if (ctxs[u]->pend.active) return refuse("an asynchronous evaluation is pending on one of the contexts");
+    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+    if (round_up(nb[u], TILE) != round_up(nb[0], TILE))
+      return refuse(unit + "round_up(nb, 128) = " + std::to_string(round_up(nb[u], TILE)) + " differs from unit 0's " +
+                    std::to_string(round_up(nb[0], TILE)) + " (group the units by padded size)");
+    if (nrows > ctxs[u]->np_cap || round_up(nb[u], TILE) > ctxs[u]->np_cap)
+      return refuse(unit + "problem larger than the context capacity");
+  }
+  DeviceGuard device_guard(ctxs[0]->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int nu = n_units, npc = (int)round_up(nb[0], TILE);
+  const int64_t ld = npc;
+  ChainGroupT g{};
+  g.n_units = nu; g.n = (int)N; g.nrows = nrows; g.npc = npc; g.ld = ld;
+  CholBatchT<double> cb;
+  for (int u = 0; u < nu; ++u) {
+    gpfit_ctx* c = ctxs[u];
+    c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
+    g.nb.v[u] = (int)nb[u]; g.kmax = std::max(g.kmax, (int)nb[u]);
+    g.a.v[u] = a[u]; g.aL.v[u] = aL[u]; g.L.v[u] = L[u]; g.r.v[u] = r[u]; g.kv0.v[u] = kv0[u];
+    g.lda.v[u] = lda[u]; g.ldal.v[u] = ldal[u]; g.ldl.v[u] = ldl[u]; g.ldv.v[u] = ldv[u];
+    g.m.v[u] = m[u]; g.f.v[u] = f[u]; g.V.v[u] = V[u]; g.lam_m.v[u] = lam_m[u]; g.lam_var.v[u] = lam_var[u];
+    g.logA0.v[u] = logA0[u]; g.lambda0.v[u] = lambda0_mode ? lambda0_fixed[u] : 0.0;
+    g.blk.v[u] = c->chain; g.info.v[u] = c->info; g.rec_host.v[u] = c->chain_host;
+    // the work vectors and matrices of gpfit_estep_chain
+    g.sv.v[u] = c->yv; g.u.v[u] = c->bv; g.t2.v[u] = c->tvec; g.z1.v[u] = c->mpad; g.z.v[u] = c->rpad; g.mo.v[u] = c->hvec;
+    g.Y.v[u] = c->Tbuf; g.Lp.v[u] = c->Wbuf; g.Vw.v[u] = c->Zbuf; g.part.v[u] = c->TmpV; g.aLp.v[u] = c->LiVbuf;
+    g.Zm.v[u] = c->Cos; g.W.v[u] = c->Kbuf; g.Li.v[u] = c->Libuf; g.trmv_part.v[u] = c->trmv_part;
+    const int b = cb.nb++;
+    cb.A[b] = c->Kbuf; cb.L[b] = c->Lbuf; cb.Li[b] = c->Libuf; cb.Tmp[b] = c->Tmp; cb.info[b] = c->info + INFO_K;
+  }
+  cb.ld = ld;
+  const uint32_t all = (1u << nu) - 1u;
+  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
+  auto all_of = [&](double* gpfit_ctx::*X) { return mats(nu, ld, [&](int i) { return ctxs[i]->*X; }); };
+  const Mat<double> Y = all_of(&gpfit_ctx::Tbuf), W = all_of(&gpfit_ctx::Kbuf), Lp = all_of(&gpfit_ctx::Wbuf),
+                    Li = all_of(&gpfit_ctx::Libuf), P = all_of(&gpfit_ctx::Abuf), Vw = all_of(&gpfit_ctx::Zbuf),
+                    aLp = all_of(&gpfit_ctx::LiVbuf), Zm = all_of(&gpfit_ctx::Cos);
+  GP_TRY(launch_chain_init_group(g, n_steps, s));
+  // L does not change over the chain: packed once
+  GP_TRY(launch_pack_lower_group(nu, g.L, g.ldl, g.nb, g.Lp, ld, npc, s));
+  // gpfit_estep_chain, product for product
+  for (int step = 0; step < n_steps; ++step) {
+    GP_TRY(launch_estep_proj_rows_chain_group(g, step, s));
+    GP_TRY(launch_estep_proj_scale_group(g, s));
+    GP_TRY(launch_reduce_slices_group(nu, g.part, npc, nrows / 32, g.t2, npc, s));   // t2 = (a L)^T u
+    GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(Y), plain(Y), into_lower(W)));
+    GP_TRY(launch_add_diag_group(nu, g.W, ld, npc, 1.0, s));
+    GP_TRY(potrf_lockstep(cb, 0, npc, all, lane));
+    GP_TRY(launch_chain_info_group(g, step, s));
+    GP_TRY(launch_trmv_lower_group(nu, g.Li, ld, npc, g.t2, g.z1, s));
+    GP_TRY(launch_trmv_lower_t_group(nu, g.Li, ld, npc, g.z1, g.z, g.trmv_part, s));
+    GP_TRY(launch_trmv_lower_group(nu, g.Lp, ld, npc, g.z, g.mo, s));
+    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(Lp)), trans(tril(Li)), into(P)));
+    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(P), trans(P), into_lower(Vw)));
+    GP_TRY(launch_chain_copy_group(g, s));
+    GP_TRY(launch_unpack_sym_chain_group(g, s));
+    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(aLp), trans(tril(Li)), into(Zm)));
+    GP_TRY(launch_estep_proj_moments_chain_group(g, s));
+    GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
+  }
+  GP_TRY(launch_chain_collect_group(g, n_steps, s));
+  GP_HIP(hipStreamSynchronize(s));
+  for (int u = 0; u < nu; ++u)
+    for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[(size_t)u * n_steps * CHAIN_REC + i] = ctxs[u]->chain_host[i];
   return 0;
 }
 

@@ -192,11 +192,11 @@ int launch_group_collect(const GroupCollectT& g, hipStream_t s) {
 // (a tile is copied by eight blocks, sixteen rows each: with one block per tile a 640 x 640 matrix had 15 blocks on
 // the chip and the copy took 21-33 us; 64 us at N = 4096)
 template <typename R>
-__global__ __launch_bounds__(256) void pack_lower_kernel(const R* __restrict__ src, int64_t lds, int n, R* __restrict__ dst,
-                                                         int64_t ldd) {
+__device__ __forceinline__ void pack_lower_body(const R* __restrict__ src, int64_t lds, int n, R* __restrict__ dst, int64_t ldd,
+                                                int bz) {
   const int tj = blockIdx.x, ti = blockIdx.y;
   if (tj > ti) return;
-  const int r0 = ti * TILE + 16 * blockIdx.z, c0 = tj * TILE;
+  const int r0 = ti * TILE + 16 * bz, c0 = tj * TILE;
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
     const int e = threadIdx.x + 256 * it;
@@ -207,10 +207,28 @@ __global__ __launch_bounds__(256) void pack_lower_kernel(const R* __restrict__ s
     dst[(int64_t)i * ldd + j] = v;
   }
 }
+template <typename R>
+__global__ __launch_bounds__(256) void pack_lower_kernel(const R* __restrict__ src, int64_t lds, int n, R* __restrict__ dst,
+                                                         int64_t ldd) {
+  pack_lower_body(src, lds, n, dst, ldd, (int)blockIdx.z);
+}
+// the same for every unit of a group: blockIdx.z = unit * (TILE / 16) + the sixteen-row slice
+__global__ __launch_bounds__(256) void pack_lower_group_kernel(PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n,
+                                                               PerUnit<double*> dst, int64_t ldd) {
+  const int u = blockIdx.z / (TILE / 16);
+  pack_lower_body(src[u], lds[u], n[u], dst[u], ldd, (int)(blockIdx.z % (TILE / 16)));
+}
 
 template <typename R>
 int launch_pack_lower(const R* src, int64_t lds, int n, R* dst, int64_t ldd, int np, hipStream_t s) {
   hipLaunchKernelGGL(pack_lower_kernel<R>, dim3(np / TILE, np / TILE, TILE / 16), dim3(256), 0, s, src, lds, n, dst, ldd);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_pack_lower_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
+                            int64_t ldd, int np, hipStream_t s) {
+  hipLaunchKernelGGL(pack_lower_group_kernel, dim3(np / TILE, np / TILE, n_units * (TILE / 16)), dim3(256), 0, s, src, lds, n,
+                     dst, ldd);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -319,8 +337,8 @@ int launch_frob_finish(const double* partial, int nt, double* out, hipStream_t s
 }
 
 template <typename R>
-__global__ void trmv_lower_kernel(const R* __restrict__ L, int64_t ldl, int np, const R* __restrict__ x,
-                                  R* __restrict__ y) {
+__device__ __forceinline__ void trmv_lower_body(const R* __restrict__ L, int64_t ldl, int np, const R* __restrict__ x,
+                                                R* __restrict__ y) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (i >= np) return;
@@ -331,6 +349,15 @@ __global__ void trmv_lower_kernel(const R* __restrict__ L, int64_t ldl, int np, 
   v = wave_sum(v);
   if (lane == 0) y[i] = (R)v;
 }
+template <typename R>
+__global__ void trmv_lower_kernel(const R* __restrict__ L, int64_t ldl, int np, const R* __restrict__ x,
+                                  R* __restrict__ y) {
+  trmv_lower_body(L, ldl, np, x, y);
+}
+__global__ void trmv_lower_group_kernel(PerUnit<double*> L, int64_t ldl, int np, PerUnit<double*> x, PerUnit<double*> y) {
+  const int u = blockIdx.y;
+  trmv_lower_body<double>(L[u], ldl, np, x[u], y[u]);
+}
 
 template <typename R>
 int launch_trmv_lower(const R* L, int64_t ldl, int np, const R* x, R* y, hipStream_t s) {
@@ -338,12 +365,17 @@ int launch_trmv_lower(const R* L, int64_t ldl, int np, const R* x, R* y, hipStre
   GP_HIP(hipGetLastError());
   return 0;
 }
+int launch_trmv_lower_group(int n_units, PerUnit<double*> L, int64_t ldl, int np, PerUnit<double*> x, PerUnit<double*> y,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(trmv_lower_group_kernel, dim3((np + 3) / 4, n_units), dim3(256), 0, s, L, ldl, np, x, y);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
 
 // z_j = sum_{i >= j} L[i][j] x_i : block = 64 columns x one chunk of TRMV_ROWS rows
 template <typename R>
-__global__ void trmv_lower_t_kernel(const R* __restrict__ L, int64_t ldl, int np, const R* __restrict__ x,
-                                    double* __restrict__ partial) {
-  __shared__ double sh[4][64];
+__device__ __forceinline__ void trmv_lower_t_body(const R* __restrict__ L, int64_t ldl, int np, const R* __restrict__ x,
+                                                  double* __restrict__ partial, double (*sh)[64]) {
   const int c = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + c;
   const int i0 = blockIdx.y * TRMV_ROWS, i1 = min(np, i0 + TRMV_ROWS);
@@ -357,15 +389,42 @@ __global__ void trmv_lower_t_kernel(const R* __restrict__ L, int64_t ldl, int np
   __syncthreads();
   if (rl == 0) partial[(int64_t)blockIdx.y * np + j] = sh[0][c] + sh[1][c] + sh[2][c] + sh[3][c];
 }
+template <typename R>
+__global__ void trmv_lower_t_kernel(const R* __restrict__ L, int64_t ldl, int np, const R* __restrict__ x,
+                                    double* __restrict__ partial) {
+  __shared__ double sh[4][64];
+  trmv_lower_t_body(L, ldl, np, x, partial, sh);
+}
+__global__ void trmv_lower_t_group_kernel(PerUnit<double*> L, int64_t ldl, int np, PerUnit<double*> x, PerUnit<double*> partial) {
+  __shared__ double sh[4][64];
+  const int u = blockIdx.z;
+  trmv_lower_t_body<double>(L[u], ldl, np, x[u], partial[u], sh);
+}
 
 template <typename RI, typename RO>
-__global__ void reduce_slices_kernel(const RI* __restrict__ src, int64_t stride, int nslice, RO* __restrict__ dst,
-                                     int64_t count) {
+__device__ __forceinline__ void reduce_slices_body(const RI* __restrict__ src, int64_t stride, int nslice, RO* __restrict__ dst,
+                                                   int64_t count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   double v = 0.0;
   for (int z = 0; z < nslice; ++z) v += (double)src[(int64_t)z * stride + i];
   dst[i] = (RO)v;
+}
+template <typename RI, typename RO>
+__global__ void reduce_slices_kernel(const RI* __restrict__ src, int64_t stride, int nslice, RO* __restrict__ dst,
+                                     int64_t count) {
+  reduce_slices_body(src, stride, nslice, dst, count);
+}
+__global__ void reduce_slices_group_kernel(PerUnit<double*> src, int64_t stride, int nslice, PerUnit<double*> dst, int64_t count) {
+  const int u = blockIdx.y;
+  reduce_slices_body<double, double>(src[u], stride, nslice, dst[u], count);
+}
+int launch_reduce_slices_group(int n_units, PerUnit<double*> src, int64_t slice_stride, int nslice, PerUnit<double*> dst,
+                               int64_t count, hipStream_t s) {
+  hipLaunchKernelGGL(reduce_slices_group_kernel, dim3((unsigned)((count + 255) / 256), n_units), dim3(256), 0, s, src,
+                     slice_stride, nslice, dst, count);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 template <typename RI, typename RO>
@@ -424,6 +483,13 @@ int launch_trmv_lower_t(const R* L, int64_t ldl, int np, const R* x, R* z, doubl
   hipLaunchKernelGGL(trmv_lower_t_kernel<R>, dim3(np / 64, chunks), dim3(256), 0, s, L, ldl, np, x, partial);
   GP_HIP(hipGetLastError());
   return launch_reduce_slices(partial, np, chunks, z, np, s);
+}
+int launch_trmv_lower_t_group(int n_units, PerUnit<double*> L, int64_t ldl, int np, PerUnit<double*> x, PerUnit<double*> z,
+                              PerUnit<double*> partial, hipStream_t s) {
+  const int chunks = (np + TRMV_ROWS - 1) / TRMV_ROWS;
+  hipLaunchKernelGGL(trmv_lower_t_group_kernel, dim3(np / 64, chunks, n_units), dim3(256), 0, s, L, ldl, np, x, partial);
+  GP_HIP(hipGetLastError());
+  return launch_reduce_slices_group(n_units, partial, np, chunks, z, np, s);
 }
 
 // ---- block forms beside the two triangular products: the dense off-diagonal block of a factor applied to a vector
@@ -1038,6 +1104,15 @@ int launch_add_diag(R* A, int64_t lda, int n, double v, hipStream_t s) {
   GP_HIP(hipGetLastError());
   return 0;
 }
+__global__ void add_diag_group_kernel(PerUnit<double*> A, int64_t lda, int n, double v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) A[blockIdx.y][(int64_t)i * lda + i] += v;
+}
+int launch_add_diag_group(int n_units, PerUnit<double*> A, int64_t lda, int n, double v, hipStream_t s) {
+  hipLaunchKernelGGL(add_diag_group_kernel, dim3((n + 255) / 256, n_units), dim3(256), 0, s, A, lda, n, v);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
 
 // dst[i] = alpha * src[i]
 template <typename R>
@@ -1212,6 +1287,80 @@ __global__ void unpack_sym_chain_kernel(ChainGate g, const double* __restrict__ 
 }
 int launch_unpack_sym_chain(ChainGate g, const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s) {
   hipLaunchKernelGGL(unpack_sym_chain_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, g, src, lds, n, dst, ldd);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the same for a group of chains (gpfit_estep_chain_batch; kernels.h: ChainGroupT): unit u = the free grid
+// dimension, its own block and info word behind every gate
+__global__ __launch_bounds__(256) void chain_init_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<double> logA0,
+                                                               PerUnit<double> lambda0, int n_rec) {
+  const int u = blockIdx.x;
+  ChainBlock* b = blk[u];
+  double* rec = &b->rec[0][0];
+  for (int i = threadIdx.x; i < n_rec; i += 256) rec[i] = 0.0;
+  if (threadIdx.x == 0) {
+    b->logA = logA0[u];
+    b->lambda0 = lambda0[u];
+    b->stop = 0;
+  }
+}
+int launch_chain_init_group(const ChainGroupT& g, int n_steps, hipStream_t s) {
+  hipLaunchKernelGGL(chain_init_group_kernel, dim3(g.n_units), dim3(256), 0, s, g.blk, g.logA0, g.lambda0, n_steps * CHAIN_REC);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ void chain_info_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info, int step) {
+  ChainBlock* b = blk[blockIdx.x];
+  if (b->stop != 0) return;
+  const int v = info[blockIdx.x][0];
+  b->rec[step][CR_INFO] = v;
+  if (v != 0) b->stop = 1;
+}
+int launch_chain_info_group(const ChainGroupT& g, int step, hipStream_t s) {
+  hipLaunchKernelGGL(chain_info_group_kernel, dim3(g.n_units), dim3(1), 0, s, g.blk, g.info, step);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ void chain_copy_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info, PerUnit<double*> src, PerUnit<int> n,
+                                        PerUnit<double*> dst) {
+  const int u = blockIdx.y;
+  const ChainGate g{&blk[u]->stop, info[u]};
+  if (!g.open()) return;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n[u]) dst[u][i] = src[u][i];
+}
+int launch_chain_copy_group(const ChainGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(chain_copy_group_kernel, dim3((g.kmax + 255) / 256, g.n_units), dim3(256), 0, s, g.blk, g.info, g.mo, g.nb,
+                     g.m);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ void unpack_sym_chain_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info, PerUnit<double*> srcs, int64_t lds,
+                                              PerUnit<int> ns, PerUnit<double*> dsts, PerUnit<int64_t> ldds) {
+  const int u = blockIdx.z;
+  const ChainGate g{&blk[u]->stop, info[u]};
+  if (!g.open()) return;
+  const int n = ns[u];
+  const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+  if (i >= n || j >= n) return;
+  const double* __restrict__ src = srcs[u];
+  dsts[u][(int64_t)i * ldds[u] + j] = (j <= i) ? src[(int64_t)i * lds + j] : src[(int64_t)j * lds + i];
+}
+int launch_unpack_sym_chain_group(const ChainGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(unpack_sym_chain_group_kernel, dim3((g.kmax + 255) / 256, g.kmax, g.n_units), dim3(256), 0, s, g.blk, g.info,
+                     g.Vw, g.ld, g.nb, g.V, g.ldv);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ __launch_bounds__(256) void chain_collect_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<double*> rec_host, int n_rec) {
+  const double* rec = &blk[blockIdx.x]->rec[0][0];
+  double* out = rec_host[blockIdx.x];
+  for (int i = threadIdx.x; i < n_rec; i += 256) out[i] = rec[i];
+  __threadfence_system();
+}
+int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s) {
+  hipLaunchKernelGGL(chain_collect_group_kernel, dim3(g.n_units), dim3(256), 0, s, g.blk, g.rec_host, n_steps * CHAIN_REC);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -1416,14 +1565,11 @@ __global__ __launch_bounds__(1024) void fparam_lbfgs_kernel(const double* __rest
 // The optimiser of a chained step (gpfit_estep_chain): behind the gate, from the logA the block holds.  rec[0..8]: the
 // nine results, rec[CR_RAN] = 1.  Status 0 leaves (logA, lambda0) in the block for the next step (and the rate in f);
 // a failing closure call sets the stop word instead.
-__global__ __launch_bounds__(1024) void fparam_lbfgs_chain_kernel(ChainGate g, const double* __restrict__ lam_m,
-                                                                  const double* __restrict__ lam_var,
-                                                                  const double* __restrict__ r, int n, int lambda0_mode,
-                                                                  double lambda0_fixed, Lbfgs1dConfig cfg,
-                                                                  double* __restrict__ f, ChainBlock* blk,
-                                                                  double* __restrict__ rec) {
-  __shared__ double sh[17];
-  extern __shared__ double hist[];
+__device__ __forceinline__ void fparam_lbfgs_chain_body(ChainGate g, const double* __restrict__ lam_m,
+                                                        const double* __restrict__ lam_var, const double* __restrict__ r,
+                                                        int n, int lambda0_mode, double lambda0_fixed,
+                                                        const Lbfgs1dConfig& cfg, double* __restrict__ f, ChainBlock* blk,
+                                                        double* __restrict__ rec, double* sh, double* hist) {
   if (!g.open()) return;   // the same two words in every thread: uniform
   const double logA0 = blk->logA;
   const FparamLbfgsRun o = fparam_lbfgs_run(lam_m, lam_var, r, n, logA0, lambda0_mode, lambda0_fixed, cfg, f, sh, hist);
@@ -1438,6 +1584,29 @@ __global__ __launch_bounds__(1024) void fparam_lbfgs_chain_kernel(ChainGate g, c
       blk->stop = 1;
     }
   }
+}
+__global__ __launch_bounds__(1024) void fparam_lbfgs_chain_kernel(ChainGate g, const double* __restrict__ lam_m,
+                                                                  const double* __restrict__ lam_var,
+                                                                  const double* __restrict__ r, int n, int lambda0_mode,
+                                                                  double lambda0_fixed, Lbfgs1dConfig cfg,
+                                                                  double* __restrict__ f, ChainBlock* blk,
+                                                                  double* __restrict__ rec) {
+  __shared__ double sh[17];
+  extern __shared__ double hist[];
+  fparam_lbfgs_chain_body(g, lam_m, lam_var, r, n, lambda0_mode, lambda0_fixed, cfg, f, blk, rec, sh, hist);
+}
+// one workgroup per unit of a group (gpfit_estep_chain_batch): each behind its own gate, from its own block
+__global__ __launch_bounds__(1024) void fparam_lbfgs_chain_group_kernel(PerUnit<ChainBlock*> blks, PerUnit<int*> info,
+                                                                        PerUnit<double*> lam_m, PerUnit<double*> lam_var,
+                                                                        PerUnit<const double*> r, int n, int lambda0_mode,
+                                                                        PerUnit<double> lambda0_fixed, Lbfgs1dConfig cfg,
+                                                                        PerUnit<double*> f, int step) {
+  __shared__ double sh[17];
+  extern __shared__ double hist[];
+  const int u = blockIdx.x;
+  ChainBlock* blk = blks[u];
+  fparam_lbfgs_chain_body(ChainGate{&blk->stop, info[u]}, lam_m[u], lam_var[u], r[u], n, lambda0_mode, lambda0_fixed[u], cfg,
+                          f[u], blk, &blk->rec[step][0], sh, hist);
 }
 
 int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double* r, int n, double logA0,
@@ -1455,6 +1624,14 @@ int launch_fparam_lbfgs_chain(ChainGate g, const double* lam_m, const double* la
   const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
   hipLaunchKernelGGL(fparam_lbfgs_chain_kernel, dim3(1), dim3(1024), lds, s, g, lam_m, lam_var, r, n, lambda0_mode,
                      lambda0_fixed, cfg, f, blk, rec);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s) {
+  const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
+  hipLaunchKernelGGL(fparam_lbfgs_chain_group_kernel, dim3(g.n_units), dim3(1024), lds, s, g.blk, g.info, g.lam_m, g.lam_var,
+                     g.r, g.n, lambda0_mode, g.lambda0, cfg, g.f, step);
   GP_HIP(hipGetLastError());
   return 0;
 }

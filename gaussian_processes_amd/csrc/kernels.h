@@ -253,4 +253,53 @@ int launch_fparam_lbfgs_chain(ChainGate g, const double* lam_m, const double* la
                               int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f,
                               ChainBlock* blk, double* rec, hipStream_t s);
 
+// ---- the chains of several independent units in lock step (gpfit_estep_chain_batch): every small kernel of a step
+// is ONE launch for the group, with the unit on a grid dimension the single form leaves free and a per-unit table
+// passed by value (as GroupPrepT).  Each unit runs the body of its single form over the same block and thread indices:
+// the same sums in the same order, hence the same bits as gpfit_estep_chain on that unit alone.  Each unit has its own
+// ChainBlock and info word, so its gate is its own.
+constexpr int CHAIN_MAXU = GEMM_MAXB / 2;   // units per call: one factorisation chain each, half a pointer batch like GroupPrepT
+template <typename T>
+struct PerUnit {
+  T v[CHAIN_MAXU];
+  __host__ __device__ __forceinline__ T operator[](int u) const { return v[u]; }
+};
+// The group as the host describes it once per call; every launcher hands its kernel the tables that kernel reads.
+struct ChainGroupT {
+  int n_units, n, nrows, npc, kmax;   // shared: training points, their padding, the padded basis size; the largest nb
+  int64_t ld;                         // leading dimension of the work matrices (= npc)
+  PerUnit<int> nb;
+  PerUnit<const double*> a, aL, L, r, kv0;
+  PerUnit<int64_t> lda, ldal, ldl, ldv;
+  PerUnit<double*> m, f, V, lam_m, lam_var;
+  PerUnit<double> logA0, lambda0;
+  PerUnit<ChainBlock*> blk;
+  PerUnit<int*> info;                 // the context's four info words; word INFO_K (0) is the chain's
+  PerUnit<double*> rec_host;          // the context's pinned, device-visible chain_host
+  // the work vectors and matrices of gpfit_estep_chain, per context
+  PerUnit<double*> sv, u, t2, z1, z, mo, Y, Lp, Vw, part, aLp, Zm, W, Li, trmv_part;
+};
+// block <- (logA0, lambda0, stop = 0) and the first n_steps records zeroed
+int launch_chain_init_group(const ChainGroupT& g, int n_steps, hipStream_t s);
+// the four info words zeroed, then launch_estep_proj_rows_chain on the record of `step`
+int launch_estep_proj_rows_chain_group(const ChainGroupT& g, int step, hipStream_t s);
+int launch_estep_proj_scale_group(const ChainGroupT& g, hipStream_t s);
+int launch_chain_info_group(const ChainGroupT& g, int step, hipStream_t s);
+int launch_chain_copy_group(const ChainGroupT& g, hipStream_t s);           // m <- mo
+int launch_unpack_sym_chain_group(const ChainGroupT& g, hipStream_t s);     // V <- Vw
+int launch_estep_proj_moments_chain_group(const ChainGroupT& g, hipStream_t s);
+int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s);
+// the first n_steps records of every unit into its rec_host (one launch instead of a copy command per unit)
+int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s);
+// the unit-batched forms of the general kernels a step uses (common sizes and leading dimensions unless per unit)
+int launch_pack_lower_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
+                            int64_t ldd, int np, hipStream_t s);
+int launch_add_diag_group(int n_units, PerUnit<double*> A, int64_t lda, int n, double v, hipStream_t s);
+int launch_reduce_slices_group(int n_units, PerUnit<double*> src, int64_t slice_stride, int nslice, PerUnit<double*> dst,
+                               int64_t count, hipStream_t s);
+int launch_trmv_lower_group(int n_units, PerUnit<double*> L, int64_t ldl, int np, PerUnit<double*> x, PerUnit<double*> y,
+                            hipStream_t s);
+int launch_trmv_lower_t_group(int n_units, PerUnit<double*> L, int64_t ldl, int np, PerUnit<double*> x, PerUnit<double*> z,
+                              PerUnit<double*> partial, hipStream_t s);
+
 }  // namespace gpfit

@@ -196,12 +196,28 @@ __global__ __launch_bounds__(256) void estep_proj_rows_chain_kernel(const double
   estep_proj_rows_body(a, lda, nb, mb, f, r, n, nrows, A, sv, u);
 }
 
+// the same for every unit of a group (gpfit_estep_chain_batch): unit = blockIdx.y; the unit's four info words are zeroed
+// here, by the first kernel of the step
+__global__ __launch_bounds__(256) void estep_proj_rows_chain_group_kernel(PerUnit<const double*> a, PerUnit<int64_t> lda,
+                                                                           PerUnit<int> nb, PerUnit<double*> mb,
+                                                                           PerUnit<double*> f, PerUnit<const double*> r,
+                                                                           int n, int nrows, PerUnit<ChainBlock*> blks,
+                                                                           PerUnit<int*> info, int step, PerUnit<double*> sv,
+                                                                           PerUnit<double*> uv) {
+  const int u = blockIdx.y;
+  ChainBlock* blk = blks[u];
+  const double A = exp(blk->logA);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && blk->stop == 0) blk->rec[step][CR_A] = A;
+  if (blockIdx.x == 0 && threadIdx.x < 4) info[u][threadIdx.x] = 0;
+  estep_proj_rows_body(a[u], lda[u], nb[u], mb[u], f[u], r[u], n, nrows, A, sv[u], uv[u]);
+}
+
 // Y[i][j] = s_i aL[i][j], zero padded to [nrows][ld] (and, if asked for, the zero-padded copy aLp of aL itself);
 // part[slice][j] = sum over the 32 rows of the slice of aL[i][j] u_i (added up slice by slice afterwards: deterministic)
-__global__ __launch_bounds__(256) void estep_proj_scale_kernel(const double* __restrict__ aL, int64_t ldal, int nb, int n,
-                                                                const double* __restrict__ sv, const double* __restrict__ u,
-                                                                double* __restrict__ Y, double* __restrict__ aLp,
-                                                                int64_t ld, int npc, double* __restrict__ part) {
+__device__ __forceinline__ void estep_proj_scale_body(const double* __restrict__ aL, int64_t ldal, int nb, int n,
+                                                      const double* __restrict__ sv, const double* __restrict__ u,
+                                                      double* __restrict__ Y, double* __restrict__ aLp, int64_t ld, int npc,
+                                                      double* __restrict__ part) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= npc) return;
   const int i0 = blockIdx.y * 32;
@@ -215,6 +231,20 @@ __global__ __launch_bounds__(256) void estep_proj_scale_kernel(const double* __r
     acc += v * u[i];
   }
   part[(int64_t)blockIdx.y * npc + j] = acc;
+}
+__global__ __launch_bounds__(256) void estep_proj_scale_kernel(const double* __restrict__ aL, int64_t ldal, int nb, int n,
+                                                                const double* __restrict__ sv, const double* __restrict__ u,
+                                                                double* __restrict__ Y, double* __restrict__ aLp,
+                                                                int64_t ld, int npc, double* __restrict__ part) {
+  estep_proj_scale_body(aL, ldal, nb, n, sv, u, Y, aLp, ld, npc, part);
+}
+__global__ __launch_bounds__(256) void estep_proj_scale_group_kernel(PerUnit<const double*> aL, PerUnit<int64_t> ldal,
+                                                                      PerUnit<int> nb, int n, PerUnit<double*> sv,
+                                                                      PerUnit<double*> uv, PerUnit<double*> Y,
+                                                                      PerUnit<double*> aLp, int64_t ld, int npc,
+                                                                      PerUnit<double*> part) {
+  const int u = blockIdx.z;
+  estep_proj_scale_body(aL[u], ldal[u], nb[u], n, sv[u], uv[u], Y[u], aLp[u], ld, npc, part[u]);
 }
 
 int launch_estep_proj_rows(const double* a, int64_t lda, int nb, const double* mb, const double* f, const double* r,
@@ -289,6 +319,37 @@ int launch_estep_proj_moments_chain(ChainGate g, const double* Z, int64_t ld, in
                                     int n, double* lam_m, double* lam_var, hipStream_t s) {
   hipLaunchKernelGGL(estep_proj_moments_chain_kernel, dim3((n + 3) / 4), dim3(256), 0, s, g, Z, ld, nb, z1, kv0, n, lam_m,
                      lam_var);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+
+// ---- the group forms (gpfit_estep_chain_batch)
+int launch_estep_proj_rows_chain_group(const ChainGroupT& g, int step, hipStream_t s) {
+  hipLaunchKernelGGL(estep_proj_rows_chain_group_kernel, dim3((g.nrows + 3) / 4, g.n_units), dim3(256), 0, s, g.a, g.lda, g.nb,
+                     g.m, g.f, g.r, g.n, g.nrows, g.blk, g.info, step, g.sv, g.u);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_estep_proj_scale_group(const ChainGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(estep_proj_scale_group_kernel, dim3((g.npc + 255) / 256, g.nrows / 32, g.n_units), dim3(256), 0, s, g.aL,
+                     g.ldal, g.nb, g.n, g.sv, g.u, g.Y, g.aLp, g.ld, g.npc, g.part);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ __launch_bounds__(256) void estep_proj_moments_chain_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info,
+                                                                              PerUnit<double*> Z, int64_t ld, PerUnit<int> nb,
+                                                                              PerUnit<double*> z1, PerUnit<const double*> kv0,
+                                                                              int n, PerUnit<double*> lam_m,
+                                                                              PerUnit<double*> lam_var) {
+  const int u = blockIdx.y;
+  const ChainGate g{&blk[u]->stop, info[u]};
+  if (!g.open()) return;
+  estep_proj_moments_body(Z[u], ld, nb[u], z1[u], kv0[u], n, lam_m[u], lam_var[u]);
+}
+int launch_estep_proj_moments_chain_group(const ChainGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(estep_proj_moments_chain_group_kernel, dim3((g.n + 3) / 4, g.n_units), dim3(256), 0, s, g.blk, g.info, g.Zm,
+                     g.ld, g.nb, g.z1, g.kv0, g.n, g.lam_m, g.lam_var);
   GP_HIP(hipGetLastError());
   return 0;
 }

@@ -19,6 +19,7 @@ import copy
 import ctypes
 import math
 import threading
+import time
 import warnings
 
 import torch
@@ -637,25 +638,298 @@ def _estep_chain(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam
     left alone -- and one 12-number record per step (include/gpfit_mi355x.h); ``V``, ``lambda_m``, ``lambda_var`` given
     here are what comes back when no step commits.  ``_estep_chain_commit`` turns the records into f_params or into the
     error of the first failing step."""
+    q = _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m,
+                       lambda_var)
+    rendezvous = getattr(_CELLS, "rendezvous", None)
+    if rendezvous is not None:      # a fit of varGP_cells: the chains of the wave's cells go out as group calls
+        return rendezvous.call(q)
+    return _chain_run_single(q)
+
+
+MAX_CHAIN_UNITS = 16     # GPFIT_ESTEP_CHAIN_MAX_UNITS of the C header
+_CELLS = threading.local()   # .rendezvous: the _ChainRendezvous of the varGP_cells wave this thread fits in; .engines
+
+
+def _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
+                   lambda_m=None, lambda_var=None, engine=None):
+    """The arguments of ``_estep_chain`` as one request: fixed operands contiguous on the device, the state cloned (the
+    call updates its copies in place), and the workspace the call runs on -- this thread's unless one is given."""
     r, a, aL, L, kv0 = (_cu(t).contiguous() for t in (r, KKtilde_inv, aL, L, kv0))
     N, nb = a.shape
     dev = a.device
-    m = _cu(m).clone().contiguous()
-    f = _cu(f_mean).clone().contiguous()
-    V = torch.empty((nb, nb), dtype=TORCH_DTYPE, device=dev) if V is None else _cu(V).clone().contiguous()
-    lam_m = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_m is None else _cu(lambda_m).clone().contiguous()
-    lam_var = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_var is None else _cu(lambda_var).clone().contiguous()
-    eng = get_engine(max(N, nb), 1)
-    n_steps = int(n_steps)
-    rec = (ctypes.c_double * (12 * max(n_steps, 1)))()
-    fixed = lambda0_fixed is not None
-    _lib.check(_lib.load().gpfit_estep_chain(eng._ctx, _stream(), a.data_ptr(), a.stride(0), aL.data_ptr(), aL.stride(0),
-                                             L.data_ptr(), L.stride(0), N, nb, r.data_ptr(), kv0.data_ptr(), m.data_ptr(),
-                                             f.data_ptr(), V.data_ptr(), V.stride(0), lam_m.data_ptr(), lam_var.data_ptr(),
-                                             float(logA0), 1 if fixed else 0, float(lambda0_fixed) if fixed else 0.0,
-                                             n_steps, int(n_fparam_steps), int(n_fparam_steps), 0.1, 1.e-7, 1.e-9, rec),
+    q = {"r": r, "a": a, "aL": aL, "L": L, "kv0": kv0, "N": int(N), "nb": int(nb), "logA0": float(logA0),
+         "n_steps": int(n_steps), "nfp": int(n_fparam_steps),
+         "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
+    q["m"] = _cu(m).clone().contiguous()
+    q["f"] = _cu(f_mean).clone().contiguous()
+    q["V"] = torch.empty((nb, nb), dtype=TORCH_DTYPE, device=dev) if V is None else _cu(V).clone().contiguous()
+    q["lam_m"] = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_m is None else _cu(lambda_m).clone().contiguous()
+    q["lam_var"] = (torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_var is None
+                    else _cu(lambda_var).clone().contiguous())
+    q["engine"] = engine if engine is not None else get_engine(max(N, nb), 1)
+    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    return q
+
+
+def _chain_result(q, rec):
+    n = q["n_steps"]
+    return q["m"], q["V"], q["lam_m"], q["lam_var"], q["f"], [list(rec[12 * k:12 * k + 12]) for k in range(n)]
+
+
+def _chain_run_single(q):
+    """``gpfit_estep_chain`` on one request."""
+    rec = (ctypes.c_double * (12 * max(q["n_steps"], 1)))()
+    fixed = q["lambda0_fixed"] is not None
+    a, aL, L, V = q["a"], q["aL"], q["L"], q["V"]
+    _lib.check(_lib.load().gpfit_estep_chain(q["engine"]._ctx, q["stream"], a.data_ptr(), a.stride(0), aL.data_ptr(),
+                                             aL.stride(0), L.data_ptr(), L.stride(0), q["N"], q["nb"], q["r"].data_ptr(),
+                                             q["kv0"].data_ptr(), q["m"].data_ptr(), q["f"].data_ptr(), V.data_ptr(),
+                                             V.stride(0), q["lam_m"].data_ptr(), q["lam_var"].data_ptr(), q["logA0"],
+                                             1 if fixed else 0, q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"],
+                                             q["nfp"], 0.1, 1.e-7, 1.e-9, rec),
                "gpfit_estep_chain")
-    return m, V, lam_m, lam_var, f, [list(rec[12 * k:12 * k + 12]) for k in range(n_steps)]
+    return _chain_result(q, rec)
+
+
+def _chain_bucket_key(q):
+    """Requests with equal keys may share one ``gpfit_estep_chain_batch`` call: what that call shares between its units,
+    and the padded basis size (the recursion's split, hence the bits, depend on it)."""
+    return (q["a"].device.index, q["stream"].value, q["N"], -(-q["nb"] // 128) * 128, q["n_steps"], q["nfp"],
+            q["lambda0_fixed"] is not None)
+
+
+def _chain_batch_raw(ctxs, qs):
+    """``gpfit_estep_chain_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return code
+    and the records, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as None goes
+    in as a null pointer."""
+    nu = len(qs)
+
+    def ptrs(key):
+        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
+
+    def lds(key):
+        return (ctypes.c_int64 * nu)(*[q["nb"] if q[key] is None else q[key].stride(0) for q in qs])
+
+    q0 = qs[0]
+    fixed = q0["lambda0_fixed"] is not None
+    rec = (ctypes.c_double * (12 * max(q0["n_steps"], 1) * nu))()
+    rc = _lib.load().gpfit_estep_chain_batch(
+        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
+        ptrs("a"), lds("a"), ptrs("aL"), lds("aL"), ptrs("L"), lds("L"), q0["N"],
+        (ctypes.c_int64 * nu)(*[q["nb"] for q in qs]), ptrs("r"), ptrs("kv0"), ptrs("m"), ptrs("f"), ptrs("V"), lds("V"),
+        ptrs("lam_m"), ptrs("lam_var"), _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
+        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], 0.1, 1.e-7,
+        1.e-9, rec)
+    return rc, rec
+
+
+def _chain_run_group(qs):
+    """One ``gpfit_estep_chain_batch`` call on requests of one bucket (``_chain_bucket_key``), each on its own
+    workspace; per request what ``_chain_run_single`` returns, with the same bits."""
+    if len({_chain_bucket_key(q) for q in qs}) != 1:
+        raise ValueError("_chain_run_group: the requests of one call share N, the padded basis size, the number of steps "
+                         "and the optimiser's settings")
+    rc, rec = _chain_batch_raw([q["engine"]._ctx for q in qs], qs)
+    _lib.check(rc, "gpfit_estep_chain_batch")
+    per = 12 * qs[0]["n_steps"]
+    return [_chain_result(q, rec[u * per:(u + 1) * per]) for u, q in enumerate(qs)]
+
+
+def _group_engines(count, n):
+    """``count`` workspaces of this thread for problems up to ``n``: its own (``get_engine``) and ``count - 1`` more,
+    kept for the thread's later group calls."""
+    own = get_engine(n, 1)
+    extra = [e for e in getattr(_CELLS, "engines", []) if e.n_max >= n and e.device == own.device]
+    while len(extra) < count - 1:
+        extra.append(GPFitEngine(n, 1, 1, device=own.device))
+    _CELLS.engines = extra
+    return [own] + extra[:count - 1]
+
+
+def _estep_chain_group(units, n_steps, n_fparam_steps):
+    """``_estep_chain`` for several independent units (cells, restarts of one cell) as ONE device call
+    (``gpfit_estep_chain_batch``).  ``units``: one dict per unit with the arguments of ``_estep_chain`` by name (``r``,
+    ``KKtilde_inv``, ``aL``, ``L``, ``kv0``, ``m``, ``f_mean``, ``logA0`` and optionally ``lambda0_fixed``, ``V``,
+    ``lambda_m``, ``lambda_var``); 1 .. 16 units with the same number of training points and the same
+    ``round_up(nb, 128)``, all with or all without ``lambda0_fixed``.  Returns, per unit, what ``_estep_chain`` returns
+    for it, bit for bit: a unit that fails stops alone."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"_estep_chain_group: 1 .. {MAX_CHAIN_UNITS} units per call")
+    cap = max(max(u["KKtilde_inv"].shape) for u in units)
+    engines = _group_engines(len(units), cap)
+    return _chain_run_group([_chain_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, engine=e, **u)
+                             for u, e in zip(units, engines)])
+
+
+class _ChainRendezvous:
+    """Where the fits of one ``varGP_cells`` wave meet.  Each of ``parties`` host threads runs one fit; a fit that
+    reaches its E-steps hands its chain request to ``call`` and waits.  When every fit still alive has arrived, the
+    last one to arrive sorts the requests into buckets by ``key`` and issues ``group`` once per bucket (``single`` for a
+    bucket of one, ``group`` in slices of ``max_units`` for a larger one), then hands every fit its result.  A fit's
+    thread starts with ``enter``; a fit that ends, fails or will never ask (``leave``) is no longer waited for.  An
+    exception of a call is raised in every fit whose request was part of that call.  ``group_sizes``: the units of
+    every call issued, in order."""
+
+    def __init__(self, parties, single, group, key, max_units=MAX_CHAIN_UNITS):
+        self.cond = threading.Condition()
+        # between two chains only one fit runs at a time (enter / call / leave pass the turn on): the fits then never
+        # compete for the interpreter or wait behind each other's launches on the shared stream, and the phase times a
+        # fit reports are its own costs
+        self.turn = threading.Lock()
+        self.alive = int(parties)
+        self.single, self.group, self.key, self.max_units = single, group, key, int(max_units)
+        self.waiting = {}      # ticket -> request
+        self.results = {}      # ticket -> result or exception
+        self.group_sizes = []
+        self.call_seconds = []     # host wall time of every call issued (enqueue to results), as group_sizes
+        self.seconds_in_call = 0.0  # summed over the fits: time between handing a request in and getting its result
+
+    def enter(self):
+        """First statement of a fit's thread: wait for the turn."""
+        self.turn.acquire()
+
+    def leave(self):
+        self.turn.release()
+        with self.cond:
+            self.alive -= 1
+            if self.waiting and len(self.waiting) >= self.alive:
+                self._issue()
+
+    def call(self, request):
+        ticket = object()
+        t_in = time.perf_counter()
+        self.turn.release()
+        with self.cond:
+            self.waiting[ticket] = request
+            if len(self.waiting) >= self.alive:
+                self._issue()
+            while ticket not in self.results:
+                self.cond.wait()
+            res = self.results.pop(ticket)
+        self.turn.acquire()
+        with self.cond:
+            self.seconds_in_call += time.perf_counter() - t_in
+        if isinstance(res, BaseException):
+            raise res
+        return res
+
+    def _issue(self):
+        """Run every waiting request (the lock is held: every other live fit is waiting for exactly this)."""
+        buckets = {}
+        for ticket, q in self.waiting.items():
+            buckets.setdefault(self.key(q), []).append(ticket)
+        for tickets in buckets.values():
+            for i in range(0, len(tickets), self.max_units):
+                part = tickets[i:i + self.max_units]
+                self.group_sizes.append(len(part))
+                t_call = time.perf_counter()
+                try:
+                    if len(part) == 1:
+                        out = [self.single(self.waiting[part[0]])]
+                    else:
+                        out = self.group([self.waiting[t] for t in part])
+                        if len(out) != len(part):
+                            raise RuntimeError("the group call returned a result list of the wrong length")
+                except BaseException as err:      # handed to every participant, also a KeyboardInterrupt
+                    out = [err] * len(part)
+                self.call_seconds.append(time.perf_counter() - t_call)
+                for t, res in zip(part, out):
+                    self.results[t] = res
+        self.waiting.clear()
+        self.cond.notify_all()
+
+
+def _cells_withdraw():
+    """A fit of a ``varGP_cells`` wave that will never ask for a chain says so: the others stop waiting for it."""
+    rendezvous = getattr(_CELLS, "rendezvous", None)
+    if rendezvous is not None:
+        _CELLS.rendezvous = None
+        rendezvous.leave()
+
+
+_IDLE_ENGINES = []   # workspaces of finished varGP_cells fits (guarded by _POOL.lock), adopted by the fits of the next wave
+
+
+def release_cell_workspaces():
+    """Free the workspaces ``varGP_cells`` keeps between calls."""
+    with _POOL.lock:
+        _IDLE_ENGINES.clear()
+
+
+def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
+    """Fit several cells recorded on the same stimuli ``x`` (or several restarts of one cell): returns the list of
+    ``(fit_model, err_dict)`` that ``varGP(x, r_list[i], **kwargs_list[i])`` returns, fit by fit.
+
+    The fits run ``max_units`` (at most 16) at a time, one host thread each with its own workspace, all on the
+    caller's current stream.  ``varGP`` itself is unchanged; where a fit would issue the E-steps of an EM iteration as
+    one device call (``_estep_chain``: truncated and sparse regimes), it waits until every fit of its wave that is
+    still running has reached the same point, and the chains of all of them go out as ONE call per group of equal
+    ``(N, round_up(nb, 128), nEstep, nFparamstep, lambda0 mode)`` (``gpfit_estep_chain_batch``: the small kernels and
+    the bottom of the Cholesky recursions cost one launch for the group instead of one per cell).  Each cell's numbers
+    are those of ``varGP`` on its own, bit for bit.  Between two chains the fits of a wave take turns, one running at a
+    time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
+    Fits that never chain (f_params carrying ``loglambda0``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
+    being waited for; a fit in the full-rank regime is waited for until it ends.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is
+    the error of every fit in that call.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
+    invocation, in order (1: the single call).  The workspaces of the fits (one per concurrent fit, each of the size of
+    a ``varGP`` workspace) are kept for the next call; ``release_cell_workspaces()`` frees them."""
+    n_fits = len(r_list)
+    if len(kwargs_list) != n_fits:
+        raise ValueError("varGP_cells: one kwargs dict per response vector")
+    max_units = int(max_units)
+    if not 1 <= max_units <= MAX_CHAIN_UNITS:
+        raise ValueError(f"varGP_cells: max_units must be within 1 .. {MAX_CHAIN_UNITS}")
+    dev = _device()
+    stream = torch.cuda.current_stream(dev)
+    grad = torch.is_grad_enabled()
+    results, errors, sizes, call_seconds, in_call = [None] * n_fits, [None] * n_fits, [], [], 0.0
+
+    def fit(i, rendezvous):
+        key = (dev.index, threading.get_ident())
+        _CELLS.rendezvous = rendezvous
+        rendezvous.enter()
+        try:
+            torch.cuda.set_device(dev)
+            torch.set_grad_enabled(grad)      # per thread in torch: as in the caller's
+            with _POOL.lock:                  # a workspace an earlier fit has left behind, if there is one
+                idle = [e for e in _IDLE_ENGINES if e.device == dev.index]
+                if idle:
+                    _IDLE_ENGINES.remove(idle[-1])
+                    _POOL.eng[key] = idle[-1]
+            with torch.cuda.stream(stream):
+                results[i] = varGP(x, r_list[i], **kwargs_list[i])
+        except BaseException as err:          # what varGP itself raises (bad arguments): re-raised in the caller below
+            errors[i] = err
+        finally:
+            _cells_withdraw()
+            with _POOL.lock:                  # the thread ends here: its workspace serves the next wave or call
+                e = _POOL.eng.pop(key, None)
+                if e is not None and len(_IDLE_ENGINES) < MAX_CHAIN_UNITS:
+                    _IDLE_ENGINES.append(e)
+
+    for first in range(0, n_fits, max_units):
+        wave = range(first, min(n_fits, first + max_units))
+        rendezvous = _ChainRendezvous(len(wave), _chain_run_single, _chain_run_group, _chain_bucket_key, max_units)
+        threads = [threading.Thread(target=fit, args=(i, rendezvous), name=f"varGP_cells-{i}") for i in wave]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        sizes += rendezvous.group_sizes
+        call_seconds += rendezvous.call_seconds
+        in_call += rendezvous.seconds_in_call
+    varGP_cells.last_group_sizes = sizes
+    varGP_cells.last_call_seconds = call_seconds      # host wall time of each of those calls
+    varGP_cells.last_seconds_in_call = in_call        # summed over the fits: waiting for the wave plus the call
+    for err in errors:
+        if err is not None:
+            raise err
+    return results
+
+
+varGP_cells.last_group_sizes = []
+varGP_cells.last_call_seconds = []
+varGP_cells.last_seconds_in_call = 0.0
 
 
 def _estep_chain_commit(records, f_params):
@@ -1372,6 +1646,8 @@ def varGP(x, r, **kwargs):
 
     same_points = (ntilde == nt) and (x_given_as_xtilde or torch.equal(xtilde, x))
     eigvecs = None
+    if not ESTEP_CHAIN or 'loglambda0' in f_params or not 0 < nEstep <= CHAIN_MAX_STEPS or maxiter <= 1:
+        _cells_withdraw()     # under varGP_cells: this fit keeps the host loop, nobody waits for its chains
 
     def build_kernels(th):
         C_, mask_ = localker(theta=th, theta_lower_lims=theta_lower_lims, theta_higher_lims=theta_higher_lims,

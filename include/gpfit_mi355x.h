@@ -319,6 +319,27 @@ int gpfit_estep_chain(gpfit_ctx* ctx, void* stream, const double* a, int64_t lda
                       int lambda0_mode, double lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                       double tol_grad, double tol_change, double* rec_host);
 
+/* gpfit_estep_chain for 1 .. GPFIT_ESTEP_CHAIN_MAX_UNITS independent units (cells, restarts of one cell) as ONE call:
+ * unit u runs on its own context ctxs[u] (pairwise distinct, one device) with its own a[u], aL[u], L[u], r[u], kv0[u],
+ * m[u], f[u], V[u], lam_m[u], lam_var[u], leading dimensions lda[u], ldal[u], ldl[u], ldv[u], size nb[u] and start
+ * logA0[u] / lambda0_fixed[u] (read when lambda0_mode is 1); N, n_steps, lambda0_mode and the optimiser's settings are
+ * shared.  Everything is enqueued on `stream`, one synchronisation at the end.  The factorisations of the units run in
+ * lock step and every small kernel of a step is one launch for the group, so a step costs the launches of one unit.
+ * All units of a call must have the same round_up(nb[u], 128) (nb[u] itself may differ): the recursion's split depends
+ * on the padded size; otherwise -3 -- the caller groups its units by padded size.
+ * rec_host[n_units][n_steps][12]: the records of gpfit_estep_chain, unit by unit.  Every output and record of unit u has
+ * the bits of gpfit_estep_chain called for that unit alone; a unit that stops (W not positive definite, optimiser
+ * failure) stops alone, exactly as there, and changes nothing in the others.
+ * Returns 0 when the chains ran, whatever the records say; < 0 on bad arguments (nothing is enqueued then). */
+#define GPFIT_ESTEP_CHAIN_MAX_UNITS 16
+int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a,
+                            const int64_t* lda, const double* const* aL, const int64_t* ldal, const double* const* L,
+                            const int64_t* ldl, int64_t N, const int64_t* nb, const double* const* r,
+                            const double* const* kv0, double* const* m, double* const* f, double* const* V,
+                            const int64_t* ldv, double* const* lam_m, double* const* lam_var, const double* logA0,
+                            int lambda0_mode, const double* lambda0_fixed, int n_steps, int max_iter, int history_size,
+                            double lr, double tol_grad, double tol_change, double* rec_host);
+
 /* Active-learning utility of nstar candidate stimuli, U = H(r|x,D) - <H(r|f,x)>
  * (nd_utility with nd_p_r_given_xD, nd_lambda_r_mean, nd_mean_noise_entropy, utils.py:413-525;
  * call site one_cell_active_training.ipynb: u2d = nd_utility(logf_var, logf_mean, arange(100))).
