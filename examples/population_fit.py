@@ -1,6 +1,7 @@
 """Several cells recorded on the same stimuli, fitted together: ``utils.varGP_cells`` (the E-step chains of the cells of
-a wave go out as ONE device call per EM iteration) or, with ``--loop``, ``utils.varGP`` cell after cell.  Both give the
-same numbers per cell, bit for bit.
+a wave go out as ONE device call per EM iteration, and the sparse M-step closures of their L-BFGS as one call whenever
+the wave's fits meet) or, with ``--loop``, ``utils.varGP`` cell after cell.  Both give the same numbers per cell, bit for
+bit.
 
     python examples/population_fit.py --cells 4                      # four synthetic cells through varGP_cells
     python examples/population_fit.py --cells 4 --loop               # the same fits one after another
@@ -8,10 +9,11 @@ same numbers per cell, bit for bit.
         --nfstep 4 --repeat 3                                        # the lab's shape (scripts/lab_fit_times.py's settings)
 
 Per repetition it prints the wall time of all fits and, averaged over the cells, the phase times ``varGP`` reports;
-for ``varGP_cells`` also how many units each chain call carried and how long those calls took.  Under ``varGP_cells``
-a fit's own "E-steps" time includes waiting for the other fits of its wave, so the E-step time per cell is printed as
-(that time - the time between handing a chain in and getting it back), i.e. the per-cell preamble of the phase, plus
-the cell's share of the group calls."""
+for ``varGP_cells`` also how many units each chain call and each closure call carried and how long those calls took.
+Under ``varGP_cells`` a fit's own "E-steps" time includes waiting for the other fits of its wave, so the E-step time per
+cell is printed as (that time - the time between handing a chain in and getting it back), i.e. the per-cell preamble of
+the phase, plus the cell's share of the group calls; the M-step time per cell by the same accounting with the closure
+calls."""
 import argparse
 import contextlib
 import io
@@ -93,6 +95,13 @@ for rep in range(max(1, args.repeat)):
         line += (f" | chain calls by units carried {hist}, {sum(secs):.3f} s in all; in the rendezvous {in_call:.3f}s per cell"
                  f" -> E-step time per cell {estep:.3f}s (preamble {ph['E-steps'] - in_call:.3f} + share of the calls "
                  f"{sum(secs) / args.cells:.3f})")
+        csizes, csecs = gp.varGP_cells.last_closure_group_sizes, gp.varGP_cells.last_closure_call_seconds
+        in_closure = gp.varGP_cells.last_seconds_in_closure_call / args.cells
+        mstep = ph["M-steps"] - in_closure + sum(csecs) / args.cells
+        chist = {n: csizes.count(n) for n in sorted(set(csizes))}
+        line += (f" | closure calls by units carried {chist}, {sum(csecs):.3f} s in all; in the rendezvous {in_closure:.3f}s per "
+                 f"cell -> M-step time per cell {mstep:.3f}s (own part {ph['M-steps'] - in_closure:.3f} + share of the calls "
+                 f"{sum(csecs) / args.cells:.3f})")
     print(line + (f" | FAILED cells {failed}" if failed else ""), flush=True)
 lm = [float(fit["values_track"]["loss_track"]["logmarginal"][-1]) for fit, _ in fits]
 print("final logmarginal per cell:", " ".join(f"{v:.4f}" for v in lm))

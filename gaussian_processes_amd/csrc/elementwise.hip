@@ -3,6 +3,8 @@
 // work; they are written for coalesced access and deterministic (atomic-free) reductions.
 #include "kernels.h"
 
+#include <algorithm>
+
 namespace gpfit {
 
 // ------------------------------------------------------------------ helpers
@@ -188,6 +190,40 @@ int launch_group_collect(const GroupCollectT& g, hipStream_t s) {
   return 0;
 }
 
+// the same beginning for the sparse closures of a group (gpfit_fit_eval_sparse_batch): unit = blockIdx.y
+__global__ __launch_bounds__(256) void closure_prepare_kernel(ClosurePrepT g) {
+  const int u = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int nk = g.nk[u];
+  if (i < g.nb) g.mpad[u][i] = (i < nk) ? g.m_b[u][i] : 0.0;
+  if (i < g.cap[u]) { g.bv[u][i] = 0.0; g.wl[u][i] = 0.0; }
+  if (blockIdx.x == 0) {
+    const int d = g.d[u];
+    const int* src = g.pix_host[u];
+    int* dst = g.pix[u];
+    for (int k = threadIdx.x; k < d; k += 256) dst[k] = src[k];
+    if (threadIdx.x < 4) g.info[u][threadIdx.x] = 0;
+  }
+}
+int launch_closure_prepare(const ClosurePrepT& g, hipStream_t s) {
+  hipLaunchKernelGGL(closure_prepare_kernel, dim3((std::max(g.cap_max, g.nb) + 255) / 256, g.n_units), dim3(256), 0, s, g);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+// count zeros into each of three matrices per unit: blockIdx.y = which, blockIdx.z = unit
+__global__ __launch_bounds__(256) void zero3_group_kernel(PerUnit<double*> a, PerUnit<double*> b, PerUnit<double*> c, int64_t count) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const int u = blockIdx.z;
+  double* p = blockIdx.y == 0 ? a[u] : (blockIdx.y == 1 ? b[u] : c[u]);
+  p[i] = 0.0;
+}
+int launch_zero3_group(int n_units, PerUnit<double*> a, PerUnit<double*> b, PerUnit<double*> c, int64_t count, hipStream_t s) {
+  hipLaunchKernelGGL(zero3_group_kernel, dim3((unsigned)((count + 255) / 256), 3, n_units), dim3(256), 0, s, a, b, c, count);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------ pack / symmetrize
 // (a tile is copied by eight blocks, sixteen rows each: with one block per tile a 640 x 640 matrix had 15 blocks on
 // the chip and the copy took 21-33 us; 64 us at N = 4096)
@@ -234,8 +270,7 @@ int launch_pack_lower_group(int n_units, PerUnit<const double*> src, PerUnit<int
 }
 
 template <typename R>
-__global__ void symmetrize_kernel(R* __restrict__ A, int64_t lda, int n) {
-  __shared__ R tile[32][33];
+__device__ __forceinline__ void symmetrize_body(R* __restrict__ A, int64_t lda, int n, R (*tile)[33]) {
   const int tj = blockIdx.x, ti = blockIdx.y;
   if (tj > ti) return;
   const int tx = threadIdx.x, ty = threadIdx.y;
@@ -252,6 +287,15 @@ __global__ void symmetrize_kernel(R* __restrict__ A, int64_t lda, int n) {
     if (ii < n && jj < n && ii > jj) A[(int64_t)jj * lda + ii] = tile[tx][ty + 8 * r];
   }
 }
+template <typename R>
+__global__ void symmetrize_kernel(R* __restrict__ A, int64_t lda, int n) {
+  __shared__ R tile[32][33];
+  symmetrize_body(A, lda, n, tile);
+}
+__global__ void symmetrize_group_kernel(PerUnit<double*> A, int64_t lda, int n) {
+  __shared__ double tile[32][33];
+  symmetrize_body<double>(A[blockIdx.z], lda, n, tile);
+}
 
 template <typename R>
 int launch_symmetrize(R* A, int64_t lda, int n, hipStream_t s) {
@@ -260,17 +304,41 @@ int launch_symmetrize(R* A, int64_t lda, int n, hipStream_t s) {
   GP_HIP(hipGetLastError());
   return 0;
 }
+int launch_symmetrize_group(int n_units, PerUnit<double*> A, int64_t lda, int n, hipStream_t s) {
+  const int t = (n + 31) / 32;
+  hipLaunchKernelGGL(symmetrize_group_kernel, dim3(t, t, n_units), dim3(32, 8), 0, s, A, lda, n);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
 
 // ------------------------------------------------------------------ small reductions
 template <typename R>
-__global__ void logdet_kernel(const R* __restrict__ L0, double* __restrict__ out0, const R* __restrict__ L1,
-                              double* __restrict__ out1, int64_t ldl, int n) {
-  __shared__ double sh[17];
+__device__ __forceinline__ void logdet_body(const R* __restrict__ L0, double* __restrict__ out0, const R* __restrict__ L1,
+                                            double* __restrict__ out1, int64_t ldl, int n, double* sh) {
   const R* __restrict__ L = blockIdx.x == 0 ? L0 : L1;
   double v = 0.0;
   for (int i = threadIdx.x; i < n; i += blockDim.x) v += log((double)L[(int64_t)i * ldl + i]);
   v = block_sum(v, sh);
   if (threadIdx.x == 0) (blockIdx.x == 0 ? out0 : out1)[0] = 2.0 * v;  // utils.py:1278
+}
+template <typename R>
+__global__ void logdet_kernel(const R* __restrict__ L0, double* __restrict__ out0, const R* __restrict__ L1,
+                              double* __restrict__ out1, int64_t ldl, int n) {
+  __shared__ double sh[17];
+  logdet_body(L0, out0, L1, out1, ldl, n, sh);
+}
+// two factors of every unit of a group: unit = blockIdx.y
+__global__ void logdet_pair_group_kernel(PerUnit<const double*> L0, PerUnit<double*> out0, PerUnit<const double*> L1,
+                                         PerUnit<double*> out1, int64_t ldl, PerUnit<int> n) {
+  __shared__ double sh[17];
+  const int u = blockIdx.y;
+  logdet_body<double>(L0[u], out0[u], L1[u], out1[u], ldl, n[u], sh);
+}
+int launch_logdet_pair_group(int n_units, PerUnit<const double*> L0, PerUnit<double*> out0, PerUnit<const double*> L1,
+                             PerUnit<double*> out1, int64_t ldl, PerUnit<int> n, hipStream_t s) {
+  hipLaunchKernelGGL(logdet_pair_group_kernel, dim3(2, n_units), dim3(1024), 0, s, L0, out0, L1, out1, ldl, n);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 template <typename R>
@@ -603,12 +671,27 @@ int launch_demote_block(const double* src, int64_t lds, float* dst, int64_t ldd,
 }
 
 template <typename R>
-__global__ void dot_kernel(const R* __restrict__ x, const R* __restrict__ y, int n, double* __restrict__ out) {
-  __shared__ double sh[17];
+__device__ __forceinline__ void dot_body(const R* __restrict__ x, const R* __restrict__ y, int n, double* __restrict__ out,
+                                         double* sh) {
   double v = 0.0;
   for (int i = threadIdx.x; i < n; i += blockDim.x) v += (double)x[i] * (double)y[i];
   v = block_sum(v, sh);
   if (threadIdx.x == 0) out[0] = v;
+}
+template <typename R>
+__global__ void dot_kernel(const R* __restrict__ x, const R* __restrict__ y, int n, double* __restrict__ out) {
+  __shared__ double sh[17];
+  dot_body(x, y, n, out, sh);
+}
+__global__ void dot_group_kernel(PerUnit<double*> x, PerUnit<double*> y, int n, PerUnit<double*> out) {
+  __shared__ double sh[17];
+  const int u = blockIdx.y;
+  dot_body<double>(x[u], y[u], n, out[u], sh);
+}
+int launch_dot_group(int n_units, PerUnit<double*> x, PerUnit<double*> y, int n, PerUnit<double*> out, hipStream_t s) {
+  hipLaunchKernelGGL(dot_group_kernel, dim3(1, n_units), dim3(1024), 0, s, x, y, n, out);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 template <typename R>
@@ -995,11 +1078,27 @@ int launch_metric_contract(const Theta& th, const int* pix, int d, int n_rows, i
 
 // ------------------------------------------------------------------ generic API helpers
 // dst[dp][ldd] <- src[d][lds] zero padded
-__global__ void pad_copy_kernel(const double* __restrict__ src, int64_t lds, int rows, int cols,
-                                double* __restrict__ dst, int64_t ldd, int prow, int pcol) {
+__device__ __forceinline__ void pad_copy_body(const double* __restrict__ src, int64_t lds, int rows, int cols,
+                                              double* __restrict__ dst, int64_t ldd, int prow, int pcol) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
   if (j >= pcol || i >= prow) return;
   dst[(int64_t)i * ldd + j] = (i < rows && j < cols) ? src[(int64_t)i * lds + j] : 0.0;
+}
+__global__ void pad_copy_kernel(const double* __restrict__ src, int64_t lds, int rows, int cols,
+                                double* __restrict__ dst, int64_t ldd, int prow, int pcol) {
+  pad_copy_body(src, lds, rows, cols, dst, ldd, prow, pcol);
+}
+__global__ void pad_copy_group_kernel(PerUnit<const double*> src, PerUnit<int64_t> lds, int rows, PerUnit<int> cols,
+                                      PerUnit<double*> dst, int64_t ldd, int prow, int pcol) {
+  const int u = blockIdx.z;
+  pad_copy_body(src[u], lds[u], rows, cols[u], dst[u], ldd, prow, pcol);
+}
+int launch_pad_copy_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, int rows, PerUnit<int> cols,
+                          PerUnit<double*> dst, int64_t ldd, int prow, int pcol, hipStream_t s) {
+  hipLaunchKernelGGL(pad_copy_group_kernel, dim3((pcol + 255) / 256, prow, n_units), dim3(256), 0, s, src, lds, rows, cols,
+                     dst, ldd, prow, pcol);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_pad_copy(const double* src, int64_t lds, int rows, int cols, double* dst, int64_t ldd, int prow,
@@ -1011,13 +1110,27 @@ int launch_pad_copy(const double* src, int64_t lds, int rows, int cols, double* 
 }
 
 // K <- (K + K^T)/2 for a square n x n matrix (reference utils.py:1024-1025 when n1 == n2 but x1 != x2)
-__global__ void symmetrize_avg_kernel(double* __restrict__ A, int64_t lda, int n) {
+__device__ __forceinline__ void symmetrize_avg_body(double* __restrict__ A, int64_t lda, int n) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
   if (i >= n || j >= i) return;
   const double a = A[(int64_t)i * lda + j], b = A[(int64_t)j * lda + i];
   const double v = (a + b) / 2.0;
   A[(int64_t)i * lda + j] = v;
   A[(int64_t)j * lda + i] = v;
+}
+__global__ void symmetrize_avg_kernel(double* __restrict__ A, int64_t lda, int n) { symmetrize_avg_body(A, lda, n); }
+// (the grid covers the largest n of the group: a unit's blocks beyond its own n return at once, as the single form's do)
+__global__ void symmetrize_avg_group_kernel(PerUnit<double*> A, int64_t lda, PerUnit<int> n) {
+  const int u = blockIdx.z;
+  symmetrize_avg_body(A[u], lda, n[u]);
+}
+int launch_symmetrize_avg_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, hipStream_t s) {
+  int nmax = 0;
+  for (int u = 0; u < n_units; ++u) nmax = std::max(nmax, n.v[u]);
+  if (nmax <= 0) return 0;
+  hipLaunchKernelGGL(symmetrize_avg_group_kernel, dim3((nmax + 255) / 256, nmax, n_units), dim3(256), 0, s, A, lda, n);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_symmetrize_avg(double* A, int64_t lda, int n, hipStream_t s) {
@@ -1213,8 +1326,8 @@ int launch_estep_build(const double* K, int64_t ldk, int n, int np, const double
 
 // y = A x for a symmetric matrix stored in its lower triangle (row-major): one wave per row
 // gathers the row part (j <= i) and the column part (j > i) of row i.
-__global__ void symv_lower_kernel(const double* __restrict__ A, int64_t lda, int n, const double* __restrict__ x,
-                                  double* __restrict__ y) {
+__device__ __forceinline__ void symv_lower_body(const double* __restrict__ A, int64_t lda, int n,
+                                                const double* __restrict__ x, double* __restrict__ y) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (i >= n) return;
@@ -1223,6 +1336,20 @@ __global__ void symv_lower_kernel(const double* __restrict__ A, int64_t lda, int
   for (int j = i + 1 + lane; j < n; j += 64) v += A[(int64_t)j * lda + i] * x[j];
   v = wave_sum(v);
   if (lane == 0) y[i] = v;
+}
+__global__ void symv_lower_kernel(const double* __restrict__ A, int64_t lda, int n, const double* __restrict__ x,
+                                  double* __restrict__ y) {
+  symv_lower_body(A, lda, n, x, y);
+}
+__global__ void symv_lower_group_kernel(PerUnit<double*> A, int64_t lda, int n, PerUnit<double*> x, PerUnit<double*> y) {
+  const int u = blockIdx.y;
+  symv_lower_body(A[u], lda, n, x[u], y[u]);
+}
+int launch_symv_lower_group(int n_units, PerUnit<double*> A, int64_t lda, int n, PerUnit<double*> x, PerUnit<double*> y,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(symv_lower_group_kernel, dim3((n + 3) / 4, n_units), dim3(256), 0, s, A, lda, n, x, y);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_symv_lower(const double* A, int64_t lda, int n, const double* x, double* y, hipStream_t s) {

@@ -1,8 +1,9 @@
 // Host-side orchestration of the GP fit path on one MI355X: workspace context, the recursive
 // blocked Cholesky built from MFMA GEMMs, and the fused unit of work (one evaluation of the
 // reference's M-step closure, utils.py:2017-2112) in the original-basis Cholesky formulation
-// (DESIGN.md section 3).  The five fused entry points -- gpfit_fit_eval, gpfit_fit_eval_batch,
-// gpfit_grad_pullback, gpfit_fit_eval_projected, gpfit_fit_eval_sparse -- are each a short sequence of
+// (DESIGN.md section 3).  The fused entry points -- gpfit_fit_eval, gpfit_fit_eval_batch,
+// gpfit_grad_pullback, gpfit_fit_eval_projected, gpfit_fit_eval_sparse and its group form
+// gpfit_fit_eval_sparse_batch (one body) -- are each a short sequence of
 // the shared stages defined once below ("shared stages of the fused closures": admission, kernel build,
 // the vectors behind the factor, the mixed-precision hand-over, the pull-back to the metric, the
 // n_kept x n_kept algebra of the truncated-rank closures, the host assembly of the 16 outputs); what
@@ -169,6 +170,28 @@ static int gemm_splitk(Lane lane, Dims d, double alpha, const Operand<R>& a, con
   g.tile = TILE;
   GP_TRY(run_gemm(lane.s, g));
   return launch_reduce_slices(partial, slab, splits, C, slab, lane.s);
+}
+
+// The same for every problem of a list, each with its own slab scratch.  A product that takes slabs for one problem is
+// issued problem by problem -- the slab count depends on the problem's own scratch, and a 128-tile launch fills the
+// chip alone; where no problem takes slabs the list goes through product, which decides about batching as ever.
+template <typename R>
+static int gemm_splitk_list(Lane lane, Dims d, double alpha, const Operand<R>& a, const Operand<R>& b, const Mat<R>& C,
+                            R* const* partial, const int64_t* partial_elems) {
+  static const bool off = getenv("GPFIT_NO_SPLITK") != nullptr;
+  const int cnt = C.cnt;
+  const int64_t slab = (int64_t)d.M * C.ld;
+  bool any = false;
+  for (int i = 0; i < cnt && !off; ++i)
+    any = any || (partial[i] && std::min<int64_t>(splitk_for(d.M, d.N, d.K), partial_elems[i] / std::max<int64_t>(1, slab)) > 1);
+  if (!any) return product(lane, d, alpha, a, b, into(C));
+  for (int i = 0; i < cnt; ++i) {
+    Operand<R> ai = a, bi = b;
+    ai.m.cnt = bi.m.cnt = 1;
+    ai.m.p[0] = a.m.p[i]; bi.m.p[0] = b.m.p[i];
+    GP_TRY(gemm_splitk(lane, d, alpha, ai, bi, C.p[i], C.ld, partial[i], partial_elems[i]));
+  }
+  return 0;
 }
 
 // tuning knob (bit mask, default all): fused GEMM epilogues -- 1 Q's symmetrisation, 2 T's norm, 4 the H / Z21 update
@@ -557,10 +580,10 @@ static int dev_alloc(gpfit_ctx* c, T** p, size_t count) {
 }
 
 // ------------------------------------------------------------------ shared stages of the fused closures
-// The five fused entry points are short sequences of the stages below (file-local functions on the context, the
+// The fused entry points are short sequences of the stages below (file-local functions on the context, the
 // stream and plain pointers: nothing here allocates or dispatches indirectly -- the host enqueue time of a unit is
 // part of its measured time at N <= 2048).  Which entry point uses which:
-//   stage                                   fit_eval  _batch  grad_pullback  _projected  _sparse
+//   stage                                   fit_eval  _batch  grad_pullback  _projected  _sparse (single and _batch)
 //   admit                                      x        x          x             x          x
 //   build_kernel                               x        x          x             x      (its parts)
 //   solve_mean, post_join_args,
@@ -751,36 +774,62 @@ static int pullback_to_metric(gpfit_ctx* c, Lane lane, const double* W, const do
 }
 
 // ---- the n_kept x n_kept algebra of the truncated-rank closures (nb = n_kept padded; leading dimension nb), in the
-// scratch matrices S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV.
-// K~_b (packed into S1) = L L^T with L^-1 (utils.py:2067) and V_b (packed into Va) = L_V L_V^T (log|V_b|, :1326) in
-// lock step, the V_b chain in the caller's four work matrices; then K~_b^-1 = L^-T L^-1 in S1 and V_b in S2, both
-// stored in full with the identity on the padding.
-static int projected_factor(gpfit_ctx* c, Lane lane, const double* V_b, int64_t ldvb, int nk, int nb, double* Va,
-                            double* Vl, double* Vli, double* Vt) {
-  double *S1 = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;
+// scratch matrices S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV of each unit's context -- for a list of cnt units (the sparse
+// closures of a group; one unit: the single closures), every small kernel one launch for the list (kernels.h).
+template <typename T, typename F>
+static PerUnit<T> per_unit(int cnt, F&& at) {
+  PerUnit<T> t{};
+  for (int i = 0; i < cnt && i < CHAIN_MAXU; ++i) t.v[i] = at(i);
+  return t;
+}
+// the work matrices of a unit's V_b chain (the caller's: which of the context's are idle differs between the closures)
+struct ProjChain { double *Va, *Vl, *Vli, *Vt; };
+// K~_b (packed into S1) = L L^T with L^-1 (utils.py:2067) and V_b (packed into Va) = L_V L_V^T (log|V_b|, :1326): the
+// 2 cnt chains in lock step, the inverse for the K~_b chains only; then K~_b^-1 = L^-T L^-1 in S1 and V_b in S2, both
+// stored in full with the identity on the padding.  nk[i]: the unit's own n_kept; nb is shared (the recursion's split).
+static int projected_factor(Lane lane, int cnt, gpfit_ctx* const* cs, const double* const* V_b, const int64_t* ldvb, const int* nk,
+                            int nb, const ProjChain* vc) {
+  if (cnt <= 0 || cnt > CHAIN_MAXU) return cnt == 0 ? 0 : -3;
   const int64_t lb = nb;
   const hipStream_t s = lane.s;
+  auto of = [&](double* gpfit_ctx::*X) { return per_unit<double*>(cnt, [&](int i) { return cs[i]->*X; }); };
+  auto all = [&](double* gpfit_ctx::*X) { return mats(cnt, lb, [&](int i) { return cs[i]->*X; }); };
   CholBatchT<double> cb;
-  cb.nb = 2;
-  cb.A[0] = S1; cb.L[0] = S2; cb.Li[0] = S3; cb.Tmp[0] = S4; cb.info[0] = c->info + INFO_K;
-  cb.A[1] = Va; cb.L[1] = Vl; cb.Li[1] = Vli; cb.Tmp[1] = Vt; cb.info[1] = c->info + INFO_V;
+  uint32_t kchains = 0;
+  for (int i = 0; i < cnt; ++i) {
+    gpfit_ctx* c = cs[i];
+    int b = cb.nb++;
+    cb.A[b] = c->Vbuf; cb.L[b] = c->LVbuf; cb.Li[b] = c->LiVbuf; cb.Tmp[b] = c->TmpV; cb.info[b] = c->info + INFO_K;
+    kchains |= 1u << b;
+    b = cb.nb++;
+    cb.A[b] = vc[i].Va; cb.L[b] = vc[i].Vl; cb.Li[b] = vc[i].Vli; cb.Tmp[b] = vc[i].Vt; cb.info[b] = c->info + INFO_V;
+  }
   cb.ld = lb; cb.ctx = nullptr; cb.side_min = 0;
-  GP_TRY(potrf_lockstep<double>(cb, 0, nb, 1u, lane));
-  GP_TRY(launch_logdet(Vl, lb, nk, c->scal + S_LOGDET_V, s));
-  GP_TRY(launch_logdet(S2, lb, nk, c->scal + S_LOGDET_K, s));
-  GP_TRY(product(lane, {nb, nb, nb}, 1.0, trans(tril(mat(S3, lb))), plain(tril(mat(S3, lb))), into_lower(mat(S1, lb))));   // L^-T L^-1
-  GP_TRY(launch_symmetrize(S1, lb, nb, s));
-  GP_TRY(launch_pack_lower(V_b, ldvb, nk, S2, lb, nb, s));
-  return launch_symmetrize(S2, lb, nb, s);
+  GP_TRY(potrf_lockstep<double>(cb, 0, nb, kchains, lane));
+  const PerUnit<int> nks = per_unit<int>(cnt, [&](int i) { return nk[i]; });
+  GP_TRY(launch_logdet_pair_group(cnt, per_unit<const double*>(cnt, [&](int i) { return vc[i].Vl; }),
+                                  per_unit<double*>(cnt, [&](int i) { return cs[i]->scal + S_LOGDET_V; }),
+                                  per_unit<const double*>(cnt, [&](int i) { return cs[i]->LVbuf; }),
+                                  per_unit<double*>(cnt, [&](int i) { return cs[i]->scal + S_LOGDET_K; }), lb, nks, s));
+  GP_TRY(product(lane, {nb, nb, nb}, 1.0, trans(tril(all(&gpfit_ctx::LiVbuf))), plain(tril(all(&gpfit_ctx::LiVbuf))),
+                 into_lower(all(&gpfit_ctx::Vbuf))));   // L^-T L^-1
+  GP_TRY(launch_symmetrize_group(cnt, of(&gpfit_ctx::Vbuf), lb, nb, s));
+  GP_TRY(launch_pack_lower_group(cnt, per_unit<const double*>(cnt, [&](int i) { return V_b[i]; }),
+                                 per_unit<int64_t>(cnt, [&](int i) { return ldvb[i]; }), nks, of(&gpfit_ctx::LVbuf), lb, nb, s));
+  return launch_symmetrize_group(cnt, of(&gpfit_ctx::LVbuf), lb, nb, s);
 }
 // K~_b^-1 V_b in S3, its trace tr(K~_b^-1 V_b) in scal[S_TRACE], P1 = K~_b^-1 V_b K~_b^-1 in S4.  (The two closures form
 // a V_b on different sides of this stage, and b = K~_b^-1 m_b behind it.)
-static int projected_kl_products(gpfit_ctx* c, Lane lane, int nk, int nb) {
-  double *Ki = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;
+static int projected_kl_products(Lane lane, int cnt, gpfit_ctx* const* cs, const int* nk, int nb) {
+  if (cnt <= 0 || cnt > CHAIN_MAXU) return cnt == 0 ? 0 : -3;
   const int64_t lb = nb;
-  GP_TRY(product(lane, {nb, nb, nb}, 1.0, plain(mat(Ki, lb)), plain(mat(S2, lb)), into(mat(S3, lb))));
-  GP_TRY(launch_proj_trace(S3, lb, nk, c->scal + S_TRACE, lane.s));
-  return product(lane, {nb, nb, nb}, 1.0, plain(mat(S3, lb)), plain(mat(Ki, lb)), into(mat(S4, lb)));
+  auto all = [&](double* gpfit_ctx::*X) { return mats(cnt, lb, [&](int i) { return cs[i]->*X; }); };
+  const Mat<double> Ki = all(&gpfit_ctx::Vbuf), S2 = all(&gpfit_ctx::LVbuf), S3 = all(&gpfit_ctx::LiVbuf), S4 = all(&gpfit_ctx::TmpV);
+  GP_TRY(product(lane, {nb, nb, nb}, 1.0, plain(Ki), plain(S2), into(S3)));
+  GP_TRY(launch_proj_trace_group(cnt, per_unit<double*>(cnt, [&](int i) { return cs[i]->LiVbuf; }), lb,
+                                 per_unit<int>(cnt, [&](int i) { return nk[i]; }),
+                                 per_unit<double*>(cnt, [&](int i) { return cs[i]->scal + S_TRACE; }), lane.s));
+  return product(lane, {nb, nb, nb}, 1.0, plain(S3), plain(Ki), into(S4));
 }
 
 // ---- host assembly of an evaluation's 16 output scalars from the device scalars (c->scal_host, c->info_host)
@@ -1440,11 +1489,12 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   // (log|V_b| of :1326: V_b is factored together with K~_b -- one lock-step recursion on this stream, in four work
   // matrices nothing else needs before the adjoints: Abuf, Wbuf, Zbuf, Tmp)
   GP_TRY(launch_pack_lower(V_b, ldvb, nk, c->Abuf, lb, nb, s));
-  GP_TRY(projected_factor(c, lane, V_b, ldvb, nk, nb, c->Abuf, c->Wbuf, c->Zbuf, c->Tmp));
+  const ProjChain vchain{c->Abuf, c->Wbuf, c->Zbuf, c->Tmp};
+  GP_TRY(projected_factor(lane, 1, &c, &V_b, &ldvb, &nk, nb, &vchain));
   double* Ki = S1;
   // a V = B V_b, then K~_b^-1 V_b with its trace and K~_b^-1 V_b K~_b^-1 (P1, in S4)
   GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S2, lb)), into(mat(aV, lb))));
-  GP_TRY(projected_kl_products(c, lane, nk, nb));
+  GP_TRY(projected_kl_products(lane, 1, &c, &nk, nb));
   GP_TRY(launch_symv_lower(Ki, lb, nb, mbp, bvec, s));                                        // b = K~_b^-1 m_b
   GP_TRY(launch_dot(mbp, bvec, nb, c->scal + S_MKM, s));
   // ---- moments, rate, likelihood pieces (:1090, 1101, 1138, 1243) and the per-point adjoints
@@ -1498,138 +1548,251 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
 //   W_K = G_Kb B^T           against dK_p    (rectangular pull-back, with the dKvec term riding on it)
 // (algebra of utils._closure_sparse).  The two d x d matrices are added before the one contraction
 // with dC_p, which is linear in them.
-static int fit_eval_sparse_impl(gpfit_ctx* c, void* stream, const double* theta, const double* lower,
-                                const double* upper, int n_rows, int n_cols, const double* X, int64_t ldx, int64_t N,
-                                const double* Xtilde, int64_t ldxt, int64_t Ntilde, const double* r, const double* B,
-                                int64_t ldb, int64_t n_kept, const double* m_b, const double* V_b, int64_t ldvb,
-                                double logA, double lambda0, double* out_host) {
+// ONE body for gpfit_fit_eval_sparse (the group of one) and gpfit_fit_eval_sparse_batch: nu independent units, each on
+// its own context, all on the caller's stream with one synchronisation at the end.  Unit by unit, as in
+// fit_eval_batch_impl: the kernel builds and the pull-backs (the masked pixel count differs from unit to unit and these
+// launches fill the chip alone).  Everything between them goes out for the list: the factorisations of all units as one
+// lock-step recursion, every product through product on the list of units, every small kernel as its unit-batched
+// form.  A unit runs the same products in the same order with the same reduction order in every small kernel whatever
+// else is in the group, so its 16 outputs have the same bits alone and in any group.
+// Returns 0, or < 0 before anything is enqueued or any output written; rc_out[u]: 0, -2 (theta outside the unit's limits:
+// the infinite loss / gradients in its outputs, nothing enqueued for it) or the LAPACK info of a failed pivot.
+static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, int nu, void* stream, const double* theta6,
+                                      const double* lower6, const double* upper6, int n_rows, int n_cols,
+                                      const double* const* X, int64_t ldx, int64_t N, const double* const* Xtilde, int64_t ldxt,
+                                      int64_t Ntilde, const double* const* r, const double* const* B, const int64_t* ldb,
+                                      const int64_t* n_kept, const double* const* m_b, const double* const* V_b,
+                                      const int64_t* ldvb, const double* logA, const double* lambda0, double* out_host,
+                                      int* rc_out) {
   using R = double;
-  if (!c || !theta || !X || !Xtilde || !r || !B || !m_b || !V_b || !out_host || N <= 0 || Ntilde <= 0 || n_kept <= 0 ||
-      n_kept > Ntilde) {
-    set_error("gpfit_fit_eval_sparse: bad argument");
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(name) + ": " + why);
     return -3;
+  };
+  if (nu < 1 || nu > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+  if (!cs || !theta6 || !X || !Xtilde || !r || !B || !ldb || !n_kept || !m_b || !V_b || !ldvb || !logA || !lambda0 || !out_host ||
+      !rc_out || N <= 0 || Ntilde <= 0 || (lower6 == nullptr) != (upper6 == nullptr))
+    return refuse("bad argument");
+  const int n1 = (int)N, n2 = (int)Ntilde;
+  const int np1 = (int)round_up(N, TILE), np2 = (int)round_up(Ntilde, TILE), nb = (int)round_up(n_kept[0], TILE);
+  // ---- admission of every unit before anything is enqueued or written
+  struct Unit { gpfit_ctx* c; int u, d, dp, nk; Theta th; double A; };
+  Unit un[CHAIN_MAXU];
+  bool outside[CHAIN_MAXU];
+  int na = 0;
+  for (int u = 0; u < nu; ++u) {
+    const std::string unit = nu > 1 ? "unit " + std::to_string(u) + ": " : std::string();
+    if (!cs[u] || !X[u] || !Xtilde[u] || !r[u] || !B[u] || !m_b[u] || !V_b[u]) return refuse(unit + "null context or operand");
+    if (n_kept[u] <= 0 || n_kept[u] > Ntilde)
+      return refuse(unit + "bad argument: n_kept " + std::to_string(n_kept[u]) + " is not within 1 .. Ntilde = " + std::to_string(Ntilde));
+    if (ldb[u] < n_kept[u] || ldvb[u] < n_kept[u]) return refuse(unit + "bad leading dimension");
+    if (cs[u]->device != cs[0]->device) return refuse("the contexts of one call must live on one device");
+    for (int v = 0; v < u; ++v)
+      if (cs[v] == cs[u]) return refuse("every unit needs a context of its own");
+    if (cs[u]->pend.active)
+      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
+    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+    if (round_up(n_kept[u], TILE) != nb)
+      return refuse(unit + "round_up(n_kept, 128) = " + std::to_string(round_up(n_kept[u], TILE)) + " differs from unit 0's " +
+                    std::to_string(nb) + " (group the units by padded size)");
   }
-  GP_CTX_ENTER(c, "gpfit_fit_eval_sparse");
+  for (int u = 0; u < nu; ++u) {
+    double scratch_out[OUT_COUNT];
+    Admitted ad;
+    const int rc = admit(cs[u], name, nu > 1 ? "a context's" : "the context", theta6 + 6 * u, lower6 ? lower6 + 6 * u : nullptr,
+                         upper6 ? upper6 + 6 * u : nullptr, n_rows, n_cols, std::max(np1, np2), scratch_out, &ad);
+    outside[u] = rc == -2;
+    if (rc == -2) continue;
+    if (rc != 0) return rc;
+    Unit& q = un[na++];
+    q.c = cs[u]; q.u = u; q.d = ad.d; q.dp = ad.dp; q.nk = (int)n_kept[u]; q.th = ad.th; q.A = std::exp(logA[u]);
+  }
+  for (int u = 0; u < nu; ++u) {
+    rc_out[u] = outside[u] ? -2 : 0;
+    if (outside[u]) fill_out_of_box(out_host + OUT_COUNT * u);
+  }
+  if (na == 0) return 0;
+  DeviceGuard device_guard(cs[0]->device);
   hipStream_t s = (hipStream_t)stream;
-  const int n1 = (int)N, n2 = (int)Ntilde, nk = (int)n_kept;
-  const int np1 = (int)round_up(N, TILE), np2 = (int)round_up(Ntilde, TILE), nb = (int)round_up(n_kept, TILE);
-  Admitted ad;
-  GP_TRY(admit(c, "gpfit_fit_eval_sparse", "the context", theta, lower, upper, n_rows, n_cols, std::max(np1, np2),
-               out_host, &ad));
-  const int d = ad.d, dp = ad.dp;
-  const Theta th = ad.th;
-  const double s0sq = th.sigma0 * th.sigma0, A = std::exp(logA);
   const int64_t l2 = np2, lb = nb;
-  c->lv_valid = false; c->lv32_valid = false;
-  c->side_ev_next = 0;
-  const Lane lane = main_lane(c, s);
+  gpfit_ctx* cl[CHAIN_MAXU];
+  int nkl[CHAIN_MAXU];
+  for (int i = 0; i < na; ++i) {
+    gpfit_ctx* c = un[i].c;
+    cl[i] = c; nkl[i] = un[i].nk;
+    c->lv_valid = false; c->lv32_valid = false;
+    c->side_ev_next = 0;
+  }
+  gpfit_ctx* c0 = cl[0];
+  const Lane lane = main_lane(c0, s);   // every launch on the caller's stream with the leader's workspace
   ++g_eval_count;
-  prof_begin(c);
-  struct ProfGuard { gpfit_ctx* c; ~ProfGuard() { prof_end(c); } } prof_guard{c};
-  double *X1m = c->Xm, *X2m = c->XDt, *Zm = c->XDt2;
-  double *Kt = c->Kbuf, *CosT = c->Cos, *Kr = c->Lbuf, *CosR = c->Libuf, *Bp = c->Tbuf, *Kb = c->Zbuf, *am = c->Tmp,
-         *aV = c->Abuf;
-  double *S1 = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;
-  double *mbp = c->mpad, *bvec = c->yv, *gm = c->dq1, *gv = c->dq2, *gvec = c->hvec;
-  GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
-  GP_HIP(hipMemcpyAsync(c->pix, c->pix_host, (size_t)d * sizeof(int), hipMemcpyHostToDevice, s));
-  // ---- kernel objects: C; training side (x: Xt, XCt, q, Kvec), inducing side (xtilde: Xt2, XCt2, q2);
-  // K~ = acosker(xtilde, xtilde), lower tiles mirrored by the tiles themselves
-  GP_TRY(build_metric<R>(c, s, th, d, dp, n_rows, n_cols));
-  GP_TRY(kernel_side<R>(c, lane, X, ldx, n1, np1, d, dp, s0sq, c->Xt, c->XCt, X1m, c->Kvec, c->q));
-  GP_TRY(kernel_side<R>(c, lane, Xtilde, ldxt, n2, np2, d, dp, s0sq, c->Xt2, c->XCt2, X2m, c->hvec, c->q2));
-  GP_TRY(gram_square<R>(s, c->XCt2, c->Xt2, c->q2, Kt, CosT, n2, np2, dp, s0sq, 1));
+  prof_begin(c0);
+  struct ProfGuard { gpfit_ctx* c; ~ProfGuard() { prof_end(c); } } prof_guard{c0};
+  // The work matrices, per context (as ever): X1m = Xm, X2m = XDt, Zm = XDt2; Kt = Kbuf, CosT = Cos, Kr = Lbuf,
+  // CosR = Libuf, Bp = Tbuf, Kb = Zbuf, am = Tmp, aV = Abuf; S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV; mbp = mpad, bvec = yv,
+  // gm = dq1, gv = dq2, gvec = hvec.
+  auto of = [&](double* gpfit_ctx::*X_) { return per_unit<double*>(na, [&](int i) { return cl[i]->*X_; }); };
+  auto cof = [&](double* gpfit_ctx::*X_) { return per_unit<const double*>(na, [&](int i) { return cl[i]->*X_; }); };
+  auto scal_of = [&](int slot) { return per_unit<double*>(na, [&](int i) { return cl[i]->scal + slot; }); };
+  auto all = [&](double* gpfit_ctx::*X_, int64_t ld) { return mats(na, ld, [&](int i) { return cl[i]->*X_; }); };
+  const PerUnit<int> nks = per_unit<int>(na, [&](int i) { return nkl[i]; });
   {
+    // pixel lists, info words, the padded m_b and the cleared bv / wl of all units: one launch
+    ClosurePrepT gp{};
+    gp.n_units = na; gp.nb = nb;
+    for (int i = 0; i < na; ++i) {
+      gpfit_ctx* c = cl[i];
+      gp.pix_host.v[i] = c->pix_host; gp.pix.v[i] = c->pix; gp.info.v[i] = c->info; gp.d.v[i] = un[i].d; gp.nk.v[i] = nkl[i];
+      gp.cap.v[i] = c->np_cap; gp.cap_max = std::max(gp.cap_max, c->np_cap);
+      gp.m_b.v[i] = m_b[un[i].u]; gp.mpad.v[i] = c->mpad; gp.bv.v[i] = c->bv; gp.wl.v[i] = c->wl;
+    }
+    GP_TRY(launch_closure_prepare(gp, s));
+  }
+  // ---- unit by unit, the kernel objects: C; training side (x: Xt, XCt, q, Kvec), inducing side (xtilde: Xt2, XCt2, q2);
+  // K~ = acosker(xtilde, xtilde), lower tiles mirrored by the tiles themselves; K = acosker(x, xtilde)
+  for (int i = 0; i < na; ++i) {
+    gpfit_ctx* c = cl[i];
+    const Unit& q = un[i];
+    const double s0sq = q.th.sigma0 * q.th.sigma0;
+    GP_TRY(build_metric<R>(c, s, q.th, q.d, q.dp, n_rows, n_cols));
+    GP_TRY(kernel_side<R>(c, lane, X[q.u], ldx, n1, np1, q.d, q.dp, s0sq, c->Xt, c->XCt, c->Xm, c->Kvec, c->q));
+    GP_TRY(kernel_side<R>(c, lane, Xtilde[q.u], ldxt, n2, np2, q.d, q.dp, s0sq, c->Xt2, c->XCt2, c->XDt, c->hvec, c->q2));
+    GP_TRY(gram_square<R>(s, c->XCt2, c->Xt2, c->q2, c->Kbuf, c->Cos, n2, np2, q.dp, s0sq, 1));
     GramArgsT<R> g{};  // K = acosker(x, xtilde): rectangular, with its cosine matrix
-    g.XCt = c->XCt; g.Xt = c->Xt2; g.q1 = c->q; g.q2 = c->q2; g.Kout = Kr; g.Cos = CosR;
-    g.ld1 = np1; g.ld2 = l2; g.ldk = l2; g.np1 = np1; g.np2 = np2; g.nv1 = n1; g.nv2 = n2; g.Kd = dp;
+    g.XCt = c->XCt; g.Xt = c->Xt2; g.q1 = c->q; g.q2 = c->q2; g.Kout = c->Lbuf; g.Cos = c->Libuf;
+    g.ld1 = np1; g.ld2 = l2; g.ldk = l2; g.np1 = np1; g.np2 = np2; g.nv1 = n1; g.nv2 = n2; g.Kd = q.dp;
     g.s0sq = s0sq; g.lower = 0; g.pad_identity = 0;
     g.ldcos = l2;
-    ProfScope ps(s, 2.0 * np1 * np2 * dp, 2);
+    ProfScope ps(s, 2.0 * np1 * np2 * q.dp, 2);
     GP_TRY(launch_gram(g, s));
   }
   // ---- projection (:2047-2049, 2067-2068): K_b = K B, K~_b = sym(B^T K~ B), a = K_b K~_b^-1
-  GP_TRY(launch_pad_copy(B, ldb, n2, nk, Bp, lb, np2, nb, s));
-  GP_HIP(hipMemsetAsync(mbp, 0, (size_t)c->np_cap * sizeof(double), s));
-  GP_HIP(hipMemcpyAsync(mbp, m_b, (size_t)nk * sizeof(double), hipMemcpyDeviceToDevice, s));
-  // (skinny products with a long k are cut into k slabs, gemm_splitk; Wbuf is free until the adjoints)
-  GP_TRY(gemm_splitk(lane, {np1, nb, np2}, 1.0, plain(mat(Kr, l2)), plain(mat(Bp, lb)), Kb, lb, c->Wbuf,
-                     (int64_t)c->np_cap * c->np_cap));
-  GP_TRY(gemm_splitk(lane, {np2, nb, np2}, 1.0, plain(mat(Kt, l2)), plain(mat(Bp, lb)), am, lb, c->Wbuf,
-                     (int64_t)c->np_cap * c->np_cap));   // K~ B (temporary)
-  GP_TRY(gemm_splitk(lane, {nb, nb, np2}, 1.0, trans(mat(Bp, lb)), plain(mat(am, lb)), S4, lb, c->Wbuf,
-                     (int64_t)c->np_cap * c->np_cap));
-  GP_TRY(launch_symmetrize_avg(S4, lb, nk, s));
-  GP_TRY(launch_pack_lower(S4, lb, nk, S1, lb, nb, s));
+  const Mat<R> Kt = all(&gpfit_ctx::Kbuf, l2), Kr = all(&gpfit_ctx::Lbuf, l2), Bp = all(&gpfit_ctx::Tbuf, lb),
+               Kb = all(&gpfit_ctx::Zbuf, lb), am = all(&gpfit_ctx::Tmp, lb), aV = all(&gpfit_ctx::Abuf, lb);
+  const Mat<R> Ki = all(&gpfit_ctx::Vbuf, lb), S2 = all(&gpfit_ctx::LVbuf, lb), S3 = all(&gpfit_ctx::LiVbuf, lb),
+               S4 = all(&gpfit_ctx::TmpV, lb);
+  GP_TRY(launch_pad_copy_group(na, per_unit<const double*>(na, [&](int i) { return B[un[i].u]; }),
+                               per_unit<int64_t>(na, [&](int i) { return ldb[un[i].u]; }), n2, nks, of(&gpfit_ctx::Tbuf), lb, np2, nb, s));
+  {
+    // (skinny products with a long k are cut into k slabs, gemm_splitk; Wbuf is free until the adjoints)
+    R* part[CHAIN_MAXU];
+    int64_t part_elems[CHAIN_MAXU];
+    for (int i = 0; i < na; ++i) { part[i] = cl[i]->Wbuf; part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap; }
+    GP_TRY(gemm_splitk_list(lane, {np1, nb, np2}, 1.0, plain(Kr), plain(Bp), Kb, part, part_elems));
+    GP_TRY(gemm_splitk_list(lane, {np2, nb, np2}, 1.0, plain(Kt), plain(Bp), am, part, part_elems));   // K~ B (temporary)
+    GP_TRY(gemm_splitk_list(lane, {nb, nb, np2}, 1.0, trans(Bp), plain(am), S4, part, part_elems));
+  }
+  GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::TmpV), lb, nks, s));
+  const PerUnit<int64_t> lbs = per_unit<int64_t>(na, [&](int) { return lb; });
+  GP_TRY(launch_pack_lower_group(na, cof(&gpfit_ctx::TmpV), lbs, nks, of(&gpfit_ctx::Vbuf), lb, nb, s));
   {
     // The V_b chain of the lock-step factorisation takes four work matrices that are dead between the projections
     // above and the adjoints below, each of the context's full np_cap^2 size (nb <= np2 <= np_cap: an nb x nb chain
     // fits whatever n_kept is): Wbuf (free until P2), Kbuf and Lbuf (K~ and K are consumed by the projections;
     // rewritten as G_a and G_a K~_b^-1 further down) and Abuf (a V_b is formed behind the chain).  The cosine
     // matrices in Cos / Libuf stay untouched.
-    double *Va = c->Wbuf, *Vl = c->Kbuf, *Vli = c->Lbuf, *Vt = c->Abuf;
-    GP_TRY(launch_pack_lower(V_b, ldvb, nk, Va, lb, nb, s));
-    for (double* p : {Vl, Vli, Vt})   // tiles above the diagonal read as zero
-      GP_HIP(hipMemsetAsync(p, 0, (size_t)nb * nb * sizeof(double), s));
-    GP_TRY(projected_factor(c, lane, V_b, ldvb, nk, nb, Va, Vl, Vli, Vt));
+    ProjChain vc[CHAIN_MAXU];
+    const double* Vb[CHAIN_MAXU];
+    int64_t ldv[CHAIN_MAXU];
+    for (int i = 0; i < na; ++i) {
+      vc[i] = ProjChain{cl[i]->Wbuf, cl[i]->Kbuf, cl[i]->Lbuf, cl[i]->Abuf};
+      Vb[i] = V_b[un[i].u]; ldv[i] = ldvb[un[i].u];
+    }
+    GP_TRY(launch_pack_lower_group(na, per_unit<const double*>(na, [&](int i) { return Vb[i]; }),
+                                   per_unit<int64_t>(na, [&](int i) { return ldv[i]; }), nks, of(&gpfit_ctx::Wbuf), lb, nb, s));
+    // tiles above the diagonal read as zero
+    GP_TRY(launch_zero3_group(na, of(&gpfit_ctx::Kbuf), of(&gpfit_ctx::Lbuf), of(&gpfit_ctx::Abuf), (int64_t)nb * nb, s));
+    GP_TRY(projected_factor(lane, na, cl, Vb, ldv, nkl, nb, vc));
   }
-  double* Ki = S1;
-  GP_TRY(projected_kl_products(c, lane, nk, nb));
-  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(mat(Kb, lb)), plain(mat(Ki, lb)), into(mat(am, lb))));           // a
-  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(mat(am, lb)), plain(mat(S2, lb)), into(mat(aV, lb))));           // a V_b
-  GP_TRY(launch_symv_lower(Ki, lb, nb, mbp, bvec, s));
-  GP_TRY(launch_dot(mbp, bvec, nb, c->scal + S_MKM, s));
-  // ---- moments / likelihood pieces with a = K_b K~_b^-1, per-point adjoints
-  GP_TRY(launch_proj_moments(am, Kb, aV, lb, nb, mbp, c->Kvec, r, n1, A, lambda0, c->lam_m, c->lam_var, c->fvec, gm, gv,
-                             c->upart, c->scal + S_RLAM, s));
-  double* Ga = Kt;       // [np1][nb]
-  double* GaKi = Kr;     // [np1][nb]
-  GP_TRY(launch_proj_ga(Kb, aV, lb, nb, n1, np1, gm, gv, mbp, Ga, s));
-  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(mat(Ga, lb)), plain(mat(Ki, lb)), into(mat(GaKi, lb))));
-  GP_TRY(gemm_splitk(lane, {nb, nb, np1}, 1.0, trans(mat(am, lb)), plain(mat(GaKi, lb)), c->Wbuf, lb, c->TmpV + (int64_t)nb * nb,
-                        (int64_t)c->np_cap * c->np_cap - (int64_t)nb * nb));   // P2 = a^T G_a K~_b^-1 (slabs behind P1 in TmpV)
-  GP_TRY(launch_proj_gktb(Ki, S4, c->Wbuf, lb, nb, bvec, S3, s));                            // G_K~b
-  GP_TRY(launch_proj_gkb(am, lb, nb, n1, np1, gv, GaKi, s));                                 // G_Kb (in place)
+  GP_TRY(projected_kl_products(lane, na, cl, nkl, nb));
+  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(Kb), plain(Ki), into(am)));           // a
+  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(am), plain(S2), into(aV)));           // a V_b
+  GP_TRY(launch_symv_lower_group(na, of(&gpfit_ctx::Vbuf), lb, nb, of(&gpfit_ctx::mpad), of(&gpfit_ctx::yv), s));
+  GP_TRY(launch_dot_group(na, of(&gpfit_ctx::mpad), of(&gpfit_ctx::yv), nb, scal_of(S_MKM), s));
+  // ---- moments / likelihood pieces with a = K_b K~_b^-1, per-point adjoints; G_a = Kbuf, G_a K~_b^-1 = Lbuf [np1][nb]
+  ProjGroupT pg{};
+  pg.n_units = na; pg.n = n1; pg.np = np1; pg.nb = nb; pg.ld = lb;
+  pg.r = per_unit<const double*>(na, [&](int i) { return r[un[i].u]; });
+  pg.A = per_unit<double>(na, [&](int i) { return un[i].A; });
+  pg.lambda0 = per_unit<double>(na, [&](int i) { return lambda0[un[i].u]; });
+  pg.am = of(&gpfit_ctx::Tmp); pg.Kb = of(&gpfit_ctx::Zbuf); pg.aV = of(&gpfit_ctx::Abuf); pg.mb = of(&gpfit_ctx::mpad);
+  pg.Kvec = of(&gpfit_ctx::Kvec); pg.lam_m = of(&gpfit_ctx::lam_m); pg.lam_var = of(&gpfit_ctx::lam_var); pg.f = of(&gpfit_ctx::fvec);
+  pg.gm = of(&gpfit_ctx::dq1); pg.gv = of(&gpfit_ctx::dq2); pg.part = of(&gpfit_ctx::upart); pg.out3 = scal_of(S_RLAM);
+  pg.Ga = of(&gpfit_ctx::Kbuf); pg.GaKi = of(&gpfit_ctx::Lbuf);
+  pg.Ki = of(&gpfit_ctx::Vbuf); pg.P1 = of(&gpfit_ctx::TmpV); pg.P2 = of(&gpfit_ctx::Wbuf); pg.bvec = of(&gpfit_ctx::yv);
+  pg.G = of(&gpfit_ctx::LiVbuf);
+  const Mat<R> Ga = all(&gpfit_ctx::Kbuf, lb), GaKi = all(&gpfit_ctx::Lbuf, lb);
+  GP_TRY(launch_proj_moments_group(pg, s));
+  GP_TRY(launch_proj_ga_group(pg, s));
+  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(Ga), plain(Ki), into(GaKi)));
+  {
+    // P2 = a^T G_a K~_b^-1 (slabs behind P1 in TmpV)
+    R* part[CHAIN_MAXU];
+    int64_t part_elems[CHAIN_MAXU];
+    for (int i = 0; i < na; ++i) {
+      part[i] = cl[i]->TmpV + (int64_t)nb * nb;
+      part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap - (int64_t)nb * nb;
+    }
+    GP_TRY(gemm_splitk_list(lane, {nb, nb, np1}, 1.0, trans(am), plain(GaKi), all(&gpfit_ctx::Wbuf, lb), part, part_elems));
+  }
+  GP_TRY(launch_proj_gktb_group(pg, s));   // G_K~b
+  GP_TRY(launch_proj_gkb_group(pg, s));    // G_Kb (in place)
   // ---- the two adjoints:  W~ = sym(B G_K~b B^T) [np2 x np2],  W_K = G_Kb B^T [np1 x np2]
-  GP_TRY(product(lane, {np2, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S3, lb)),
-                 into(mat(Kt, lb))));           // B G_K~b  (G_a is dead)
-  GP_TRY(product(lane, {np2, np2, nb}, 1.0, plain(mat(Kt, lb)), trans(mat(Bp, lb)), into(mat(c->Wbuf, l2))));
-  GP_TRY(launch_symmetrize_avg(c->Wbuf, l2, np2, s));
-  GP_TRY(product(lane, {np1, np2, nb}, 1.0, plain(mat(GaKi, lb)), trans(mat(Bp, lb)),
-                 into(mat(aV, l2))));        // W_K  (a V_b is dead)
-  double* WK = aV;
-  // ---- square pull-back on the inducing stimuli (no b b^T term, no dKvec term; A_w into K_b, which is dead).
-  // (bv / wl are cleared over np_cap elements here, over np in the other two closures: each as it always was)
-  GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)c->np_cap * sizeof(R), s));
-  GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)c->np_cap * sizeof(R), s));
-  GP_TRY(pullback_to_metric(c, lane, c->Wbuf, CosT, c->q2, n2, np2, dp, Kb, X2m, am));   // a (Tmp) is dead
-  // ---- rectangular pull-back (x, xtilde) with gvec = -g_v on the training side (dKvec term)
-  GP_TRY(launch_scale_copy<R>(gvec, gv, n1, -1.0, s));
-  double* t1 = c->tvec;
-  double* t2 = c->tvec + c->np_cap;
-  GP_TRY(launch_adjoint_rect(WK, l2, CosR, l2, c->q, c->q2, n1, n2, np1, np2, Kt, l2, c->upart, c->vpart, c->rect_part,
-                             gvec, t1, t2, c->rpad, c->mpad, c->scal + S_RECT, s));
-  GP_TRY(product(lane, {np1, dp, np2}, 1.0, plain(mat(Kt, l2)), plain(mat(X2m, dp)), into(mat(c->Ybuf, dp))));
-  GP_TRY(launch_rowscale_add(c->Ybuf, dp, X1m, dp, t1, np1, dp, s));
-  GP_HIP(hipMemsetAsync(Zm, 0, (size_t)np2 * dp * sizeof(double), s));
-  GP_TRY(launch_rowscale_add(Zm, dp, X2m, dp, t2, np2, dp, s));
-  GP_TRY(xty<R>(c, s, X1m, c->Ybuf, np1, dp, c->dCpad, false));
-  GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
-  GP_TRY(xty<R>(c, s, X2m, Zm, np2, dp, c->dCpad, false));
-  GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
-  GP_TRY(launch_symmetrize_avg(c->Mmat, dp, dp, s));
-  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
-                                c->info + INFO_METRIC, s));
-  GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
-  GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  GP_TRY(product(lane, {np2, nb, nb}, 1.0, plain(Bp), plain(S3), into(all(&gpfit_ctx::Kbuf, lb))));   // B G_K~b  (G_a is dead)
+  GP_TRY(product(lane, {np2, np2, nb}, 1.0, plain(all(&gpfit_ctx::Kbuf, lb)), trans(Bp), into(all(&gpfit_ctx::Wbuf, l2))));
+  GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::Wbuf), l2, per_unit<int>(na, [&](int) { return np2; }), s));
+  GP_TRY(product(lane, {np1, np2, nb}, 1.0, plain(GaKi), trans(Bp), into(all(&gpfit_ctx::Abuf, l2))));   // W_K  (a V_b is dead)
+  // ---- unit by unit, the two pull-backs
+  for (int i = 0; i < na; ++i) {
+    gpfit_ctx* c = cl[i];
+    const Unit& q = un[i];
+    const int d = q.d, dp = q.dp;
+    double *X1m = c->Xm, *X2m = c->XDt, *Zm = c->XDt2, *KtU = c->Kbuf, *WK = c->Abuf, *gv = c->dq2, *gvec = c->hvec;
+    // square pull-back on the inducing stimuli (no b b^T term, no dKvec term: bv / wl were cleared at the start; A_w
+    // into K_b, which is dead; a (Tmp) is dead)
+    GP_TRY(pullback_to_metric(c, lane, c->Wbuf, c->Cos, c->q2, n2, np2, dp, c->Zbuf, X2m, c->Tmp));
+    // rectangular pull-back (x, xtilde) with gvec = -g_v on the training side (dKvec term)
+    GP_TRY(launch_scale_copy<R>(gvec, gv, n1, -1.0, s));
+    double* t1 = c->tvec;
+    double* t2 = c->tvec + c->np_cap;
+    GP_TRY(launch_adjoint_rect(WK, l2, c->Libuf, l2, c->q, c->q2, n1, n2, np1, np2, KtU, l2, c->upart, c->vpart, c->rect_part,
+                               gvec, t1, t2, c->rpad, c->mpad, c->scal + S_RECT, s));
+    GP_TRY(product(lane, {np1, dp, np2}, 1.0, plain(mat(KtU, l2)), plain(mat(X2m, dp)), into(mat(c->Ybuf, dp))));
+    GP_TRY(launch_rowscale_add(c->Ybuf, dp, X1m, dp, t1, np1, dp, s));
+    GP_HIP(hipMemsetAsync(Zm, 0, (size_t)np2 * dp * sizeof(double), s));
+    GP_TRY(launch_rowscale_add(Zm, dp, X2m, dp, t2, np2, dp, s));
+    GP_TRY(xty<R>(c, s, X1m, c->Ybuf, np1, dp, c->dCpad, false));
+    GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
+    GP_TRY(xty<R>(c, s, X2m, Zm, np2, dp, c->dCpad, false));
+    GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
+    GP_TRY(launch_symmetrize_avg(c->Mmat, dp, dp, s));
+    GP_TRY(launch_metric_contract(q.th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
+                                  c->info + INFO_METRIC, s));
+  }
+  {
+    // the 64 scalars and the info words of every unit straight into its pinned host buffers: one launch
+    GroupCollectT gc{};
+    gc.n_units = na;
+    for (int i = 0; i < na; ++i) {
+      gpfit_ctx* c = cl[i];
+      gc.scal[i] = c->scal; gc.info[i] = c->info; gc.scal_host[i] = c->scal_host; gc.info_host[i] = c->info_host;
+    }
+    GP_TRY(launch_group_collect(gc, s));
+  }
   GP_HIP(hipStreamSynchronize(s));
-  const double* sc = c->scal_host;
-  const double sum_gvec = 0.5 * A * A * sc[S_SUMF];                                               // -sum g_v
-  return assemble_out(c, A, lambda0,
-                      sigma0_row_metric(sc, th.sigma0) + th.sigma0 * (2.0 * sc[S_RECT] + sc[S_RECT_U1] + sc[S_RECT_U2]) +
-                          2.0 * th.sigma0 * sum_gvec,
-                      0, d, 1, "gpfit_fit_eval_sparse: Cholesky of the projected K_tilde failed (non-positive pivot)",
-                      "gpfit_fit_eval_sparse: Cholesky of V_b failed (non-positive pivot)", out_host);
+  const std::string err_K = std::string(name) + ": Cholesky of the projected K_tilde failed (non-positive pivot)";
+  const std::string err_V = std::string(name) + ": Cholesky of V_b failed (non-positive pivot)";
+  for (int i = 0; i < na; ++i) {
+    gpfit_ctx* c = cl[i];
+    const Unit& q = un[i];
+    const double* sc = c->scal_host;
+    const double sum_gvec = 0.5 * q.A * q.A * sc[S_SUMF];                                               // -sum g_v
+    rc_out[q.u] = assemble_out(c, q.A, lambda0[q.u],
+                               sigma0_row_metric(sc, q.th.sigma0) +
+                                   q.th.sigma0 * (2.0 * sc[S_RECT] + sc[S_RECT_U1] + sc[S_RECT_U2]) + 2.0 * q.th.sigma0 * sum_gvec,
+                               0, q.d, 1, err_K.c_str(), err_V.c_str(), out_host + OUT_COUNT * q.u);
+  }
+  return 0;
 }
 
 // Wait for the evaluation enqueued on this context and assemble its 16 host scalars.
@@ -1706,8 +1869,25 @@ int gpfit_fit_eval_sparse(gpfit_ctx* c, void* stream, const double* theta, const
                           int64_t ldxt, int64_t Ntilde, const double* r, const double* B, int64_t ldb, int64_t n_kept,
                           const double* m_b, const double* V_b, int64_t ldvb, double logA, double lambda0,
                           double* out_host) {
-  return fit_eval_sparse_impl(c, stream, theta, lower, upper, n_rows, n_cols, X, ldx, N, Xtilde, ldxt, Ntilde, r, B, ldb,
-                              n_kept, m_b, V_b, ldvb, logA, lambda0, out_host);
+  // the group of one (fit_eval_sparse_group_impl): a unit's numbers are the same alone and in any group
+  int rc = 0;
+  const int ret = fit_eval_sparse_group_impl("gpfit_fit_eval_sparse", &c, 1, stream, theta, lower, upper, n_rows, n_cols, &X, ldx, N,
+                                             &Xtilde, ldxt, Ntilde, &r, &B, &ldb, &n_kept, &m_b, &V_b, &ldvb, &logA, &lambda0,
+                                             out_host, &rc);
+  return ret != 0 ? ret : rc;
+}
+
+static_assert(GPFIT_FIT_EVAL_SPARSE_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+
+int gpfit_fit_eval_sparse_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* theta, const double* lower,
+                                const double* upper, int n_rows, int n_cols, const double* const* X, int64_t ldx, int64_t N,
+                                const double* const* Xtilde, int64_t ldxt, int64_t Ntilde, const double* const* r,
+                                const double* const* B, const int64_t* ldb, const int64_t* n_kept, const double* const* m_b,
+                                const double* const* V_b, const int64_t* ldvb, const double* logA, const double* lambda0,
+                                double* out_host, int* rc_out) {
+  return fit_eval_sparse_group_impl("gpfit_fit_eval_sparse_batch", ctxs, n_units, stream, theta, lower, upper, n_rows, n_cols, X,
+                                    ldx, N, Xtilde, ldxt, Ntilde, r, B, ldb, n_kept, m_b, V_b, ldvb, logA, lambda0, out_host,
+                                    rc_out);
 }
 
 int gpfit_grad_pullback(gpfit_ctx* c, void* stream, const double* theta, int n_rows, int n_cols, const double* X,

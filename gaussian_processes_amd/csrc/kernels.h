@@ -302,4 +302,46 @@ int launch_trmv_lower_group(int n_units, PerUnit<double*> L, int64_t ldl, int np
 int launch_trmv_lower_t_group(int n_units, PerUnit<double*> L, int64_t ldl, int np, PerUnit<double*> x, PerUnit<double*> z,
                               PerUnit<double*> partial, hipStream_t s);
 
+// ---- the sparse M-step closures of several independent units in one call (gpfit_fit_eval_sparse_batch; the single call
+// gpfit_fit_eval_sparse is the group of one): the same rule -- the unit on a free grid dimension, tables by value, the
+// single form's body over the same block and thread indices.
+// Begin: the masked pixel list from its pinned host copy, the info words zeroed, m_b zero-padded to nb, and the two
+// vectors the pull-backs expect cleared (bv, wl over the context's capacity).
+struct ClosurePrepT {
+  int n_units, nb, cap_max;
+  PerUnit<const int*> pix_host;
+  PerUnit<int*> pix, info;
+  PerUnit<int> d, nk, cap;
+  PerUnit<const double*> m_b;
+  PerUnit<double*> mpad, bv, wl;
+};
+int launch_closure_prepare(const ClosurePrepT& g, hipStream_t s);
+int launch_zero3_group(int n_units, PerUnit<double*> a, PerUnit<double*> b, PerUnit<double*> c, int64_t count, hipStream_t s);
+int launch_pad_copy_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, int rows, PerUnit<int> cols,
+                          PerUnit<double*> dst, int64_t ldd, int prow, int pcol, hipStream_t s);
+int launch_symmetrize_group(int n_units, PerUnit<double*> A, int64_t lda, int n, hipStream_t s);
+int launch_symmetrize_avg_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, hipStream_t s);
+// out0[u] = log|L0[u] L0[u]^T|, out1[u] likewise (launch_logdet_pair per unit, the unit's own n)
+int launch_logdet_pair_group(int n_units, PerUnit<const double*> L0, PerUnit<double*> out0, PerUnit<const double*> L1,
+                             PerUnit<double*> out1, int64_t ldl, PerUnit<int> n, hipStream_t s);
+int launch_symv_lower_group(int n_units, PerUnit<double*> A, int64_t lda, int n, PerUnit<double*> x, PerUnit<double*> y,
+                            hipStream_t s);
+int launch_dot_group(int n_units, PerUnit<double*> x, PerUnit<double*> y, int n, PerUnit<double*> out, hipStream_t s);
+int launch_proj_trace_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, PerUnit<double*> out, hipStream_t s);
+// the operands of the element-wise passes of the projected closures, per unit (n training points padded to np rows, the
+// padded basis size nb = the leading dimension ld): launch_proj_moments, _ga, _gkb, _gktb for the group
+struct ProjGroupT {
+  int n_units, n, np, nb;
+  int64_t ld;
+  PerUnit<const double*> r;
+  PerUnit<double> A, lambda0;
+  PerUnit<double*> am, Kb, aV, mb, Kvec, lam_m, lam_var, f, gm, gv, part, out3;   // moments (am: a = K_b K~_b^-1, or B)
+  PerUnit<double*> Ga, GaKi;                                                      // G_a ; G_a K~_b^-1 -> G_Kb in place
+  PerUnit<double*> Ki, P1, P2, bvec, G;                                           // G_K~b
+};
+int launch_proj_moments_group(const ProjGroupT& g, hipStream_t s);
+int launch_proj_ga_group(const ProjGroupT& g, hipStream_t s);
+int launch_proj_gkb_group(const ProjGroupT& g, hipStream_t s);
+int launch_proj_gktb_group(const ProjGroupT& g, hipStream_t s);
+
 }  // namespace gpfit

@@ -9,14 +9,15 @@ namespace gpfit {
 // One wave per training point i (utils.py:1090, 1101, 1138 with a = B):
 //   lam_m = B_i . m_b,  lam_var = Kvec_i - B_i . Kb_i + aV_i . B_i,  f = exp(A lam_m + A^2/2 lam_var + lambda0)
 //   g_m = A (r - f),  g_v = -A^2 f / 2;   block partial sums of r lam_m, r, f -> part[3][gridDim.x]
-__global__ __launch_bounds__(256) void proj_moments_kernel(const double* __restrict__ Bp, const double* __restrict__ Kb,
-                                                            const double* __restrict__ aV, int64_t ld, int nb,
-                                                            const double* __restrict__ mb, const double* __restrict__ Kvec,
-                                                            const double* __restrict__ r, int n, double A, double lambda0,
-                                                            double* __restrict__ lam_m, double* __restrict__ lam_var,
-                                                            double* __restrict__ f, double* __restrict__ gm,
-                                                            double* __restrict__ gv, double* __restrict__ part) {
-  __shared__ double red[3][4];
+// (the bodies below are shared by the single kernels and the unit-batched ones of gpfit_fit_eval_sparse_batch, which put
+// the unit on a grid dimension the single form leaves free: the same sums in the same order, hence the same bits)
+__device__ __forceinline__ void proj_moments_body(const double* __restrict__ Bp, const double* __restrict__ Kb,
+                                                  const double* __restrict__ aV, int64_t ld, int nb,
+                                                  const double* __restrict__ mb, const double* __restrict__ Kvec,
+                                                  const double* __restrict__ r, int n, double A, double lambda0,
+                                                  double* __restrict__ lam_m, double* __restrict__ lam_var,
+                                                  double* __restrict__ f, double* __restrict__ gm,
+                                                  double* __restrict__ gv, double* __restrict__ part, double (*red)[4]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + w;
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -54,10 +55,19 @@ __global__ __launch_bounds__(256) void proj_moments_kernel(const double* __restr
     part[(int64_t)q * gridDim.x + blockIdx.x] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
   }
 }
+__global__ __launch_bounds__(256) void proj_moments_kernel(const double* __restrict__ Bp, const double* __restrict__ Kb,
+                                                            const double* __restrict__ aV, int64_t ld, int nb,
+                                                            const double* __restrict__ mb, const double* __restrict__ Kvec,
+                                                            const double* __restrict__ r, int n, double A, double lambda0,
+                                                            double* __restrict__ lam_m, double* __restrict__ lam_var,
+                                                            double* __restrict__ f, double* __restrict__ gm,
+                                                            double* __restrict__ gv, double* __restrict__ part) {
+  __shared__ double red[3][4];
+  proj_moments_body(Bp, Kb, aV, ld, nb, mb, Kvec, r, n, A, lambda0, lam_m, lam_var, f, gm, gv, part, red);
+}
 
 // out[q] = sum of part[q][0..nblk) in index order (deterministic), q = 0..2
-__global__ __launch_bounds__(256) void proj_sum3_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out) {
-  __shared__ double red[256];
+__device__ __forceinline__ void proj_sum3_body(const double* __restrict__ part, int nblk, double* __restrict__ out, double* red) {
   for (int q = 0; q < 3; ++q) {
     double s = 0.0;
     for (int i = threadIdx.x; i < nblk; i += 256) s += part[(int64_t)q * nblk + i];
@@ -71,40 +81,58 @@ __global__ __launch_bounds__(256) void proj_sum3_kernel(const double* __restrict
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(256) void proj_sum3_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out) {
+  __shared__ double red[256];
+  proj_sum3_body(part, nblk, out, red);
+}
 
 // G_a = g_m m_b^T - diag(g_v) K_b + 2 diag(g_v) aV   (N x nb, rows >= n left zero)
-__global__ __launch_bounds__(256) void proj_ga_kernel(const double* __restrict__ Kb, const double* __restrict__ aV,
-                                                       int64_t ld, int nb, int n, const double* __restrict__ gm,
-                                                       const double* __restrict__ gv, const double* __restrict__ mb,
-                                                       double* __restrict__ Ga) {
+__device__ __forceinline__ void proj_ga_body(const double* __restrict__ Kb, const double* __restrict__ aV, int64_t ld, int nb,
+                                             int n, const double* __restrict__ gm, const double* __restrict__ gv,
+                                             const double* __restrict__ mb, double* __restrict__ Ga) {
   const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
   if (j >= nb) return;
   const int64_t o = (int64_t)i * ld + j;
   Ga[o] = (i < n) ? gm[i] * mb[j] - gv[i] * Kb[o] + 2.0 * gv[i] * aV[o] : 0.0;
 }
+__global__ __launch_bounds__(256) void proj_ga_kernel(const double* __restrict__ Kb, const double* __restrict__ aV,
+                                                       int64_t ld, int nb, int n, const double* __restrict__ gm,
+                                                       const double* __restrict__ gv, const double* __restrict__ mb,
+                                                       double* __restrict__ Ga) {
+  proj_ga_body(Kb, aV, ld, nb, n, gm, gv, mb, Ga);
+}
 
 // G_Kb = diag(g_v) B - G_a K~_b^-1, in place on the product (rows >= n left zero)
-__global__ __launch_bounds__(256) void proj_gkb_kernel(const double* __restrict__ Bp, int64_t ld, int nb, int n,
-                                                        const double* __restrict__ gv, double* __restrict__ GaKi) {
+__device__ __forceinline__ void proj_gkb_body(const double* __restrict__ Bp, int64_t ld, int nb, int n,
+                                              const double* __restrict__ gv, double* __restrict__ GaKi) {
   const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
   if (j >= nb) return;
   const int64_t o = (int64_t)i * ld + j;
   GaKi[o] = (i < n) ? gv[i] * Bp[o] - GaKi[o] : 0.0;
 }
+__global__ __launch_bounds__(256) void proj_gkb_kernel(const double* __restrict__ Bp, int64_t ld, int nb, int n,
+                                                        const double* __restrict__ gv, double* __restrict__ GaKi) {
+  proj_gkb_body(Bp, ld, nb, n, gv, GaKi);
+}
 
 // G_K~b = 1/2 K~_b^-1 - 1/2 b b^T - 1/2 (K~_b^-1 V_b K~_b^-1) + B^T G_a K~_b^-1     (nb x nb)
-__global__ __launch_bounds__(256) void proj_gktb_kernel(const double* __restrict__ Ki, const double* __restrict__ P1,
-                                                         const double* __restrict__ P2, int64_t ld, int nb,
-                                                         const double* __restrict__ b, double* __restrict__ G) {
+__device__ __forceinline__ void proj_gktb_body(const double* __restrict__ Ki, const double* __restrict__ P1,
+                                               const double* __restrict__ P2, int64_t ld, int nb,
+                                               const double* __restrict__ b, double* __restrict__ G) {
   const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
   if (j >= nb) return;
   const int64_t o = (int64_t)i * ld + j;
   G[o] = 0.5 * Ki[o] - 0.5 * b[i] * b[j] - 0.5 * P1[o] + P2[o];
 }
+__global__ __launch_bounds__(256) void proj_gktb_kernel(const double* __restrict__ Ki, const double* __restrict__ P1,
+                                                         const double* __restrict__ P2, int64_t ld, int nb,
+                                                         const double* __restrict__ b, double* __restrict__ G) {
+  proj_gktb_body(Ki, P1, P2, ld, nb, b, G);
+}
 
 // out[0] = sum_i A[i][i], i < n
-__global__ __launch_bounds__(256) void proj_trace_kernel(const double* __restrict__ A, int64_t lda, int n, double* __restrict__ out) {
-  __shared__ double red[256];
+__device__ __forceinline__ void proj_trace_body(const double* __restrict__ A, int64_t lda, int n, double* __restrict__ out,
+                                                double* red) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += A[(int64_t)i * lda + i];
   red[threadIdx.x] = s;
@@ -114,6 +142,80 @@ __global__ __launch_bounds__(256) void proj_trace_kernel(const double* __restric
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = red[0];
+}
+__global__ __launch_bounds__(256) void proj_trace_kernel(const double* __restrict__ A, int64_t lda, int n, double* __restrict__ out) {
+  __shared__ double red[256];
+  proj_trace_body(A, lda, n, out, red);
+}
+
+// ---- the unit-batched forms (gpfit_fit_eval_sparse_batch; kernels.h: ProjGroupT): unit = the free grid dimension
+__global__ __launch_bounds__(256) void proj_moments_group_kernel(PerUnit<double*> am, PerUnit<double*> Kb, PerUnit<double*> aV,
+                                                                  int64_t ld, int nb, PerUnit<double*> mb, PerUnit<double*> Kvec,
+                                                                  PerUnit<const double*> r, int n, PerUnit<double> A,
+                                                                  PerUnit<double> lambda0, PerUnit<double*> lam_m,
+                                                                  PerUnit<double*> lam_var, PerUnit<double*> f,
+                                                                  PerUnit<double*> gm, PerUnit<double*> gv, PerUnit<double*> part) {
+  __shared__ double red[3][4];
+  const int u = blockIdx.y;
+  proj_moments_body(am[u], Kb[u], aV[u], ld, nb, mb[u], Kvec[u], r[u], n, A[u], lambda0[u], lam_m[u], lam_var[u], f[u], gm[u],
+                    gv[u], part[u], red);
+}
+__global__ __launch_bounds__(256) void proj_sum3_group_kernel(PerUnit<double*> part, int nblk, PerUnit<double*> out) {
+  __shared__ double red[256];
+  const int u = blockIdx.y;
+  proj_sum3_body(part[u], nblk, out[u], red);
+}
+__global__ __launch_bounds__(256) void proj_ga_group_kernel(PerUnit<double*> Kb, PerUnit<double*> aV, int64_t ld, int nb, int n,
+                                                             PerUnit<double*> gm, PerUnit<double*> gv, PerUnit<double*> mb,
+                                                             PerUnit<double*> Ga) {
+  const int u = blockIdx.z;
+  proj_ga_body(Kb[u], aV[u], ld, nb, n, gm[u], gv[u], mb[u], Ga[u]);
+}
+__global__ __launch_bounds__(256) void proj_gkb_group_kernel(PerUnit<double*> am, int64_t ld, int nb, int n, PerUnit<double*> gv,
+                                                              PerUnit<double*> GaKi) {
+  const int u = blockIdx.z;
+  proj_gkb_body(am[u], ld, nb, n, gv[u], GaKi[u]);
+}
+__global__ __launch_bounds__(256) void proj_gktb_group_kernel(PerUnit<double*> Ki, PerUnit<double*> P1, PerUnit<double*> P2,
+                                                               int64_t ld, int nb, PerUnit<double*> b, PerUnit<double*> G) {
+  const int u = blockIdx.z;
+  proj_gktb_body(Ki[u], P1[u], P2[u], ld, nb, b[u], G[u]);
+}
+__global__ __launch_bounds__(256) void proj_trace_group_kernel(PerUnit<double*> A, int64_t lda, PerUnit<int> n, PerUnit<double*> out) {
+  __shared__ double red[256];
+  const int u = blockIdx.y;
+  proj_trace_body(A[u], lda, n[u], out[u], red);
+}
+int launch_proj_moments_group(const ProjGroupT& g, hipStream_t s) {
+  const int nblk = (g.n + 3) / 4;
+  hipLaunchKernelGGL(proj_moments_group_kernel, dim3(nblk, g.n_units), dim3(256), 0, s, g.am, g.Kb, g.aV, g.ld, g.nb, g.mb,
+                     g.Kvec, g.r, g.n, g.A, g.lambda0, g.lam_m, g.lam_var, g.f, g.gm, g.gv, g.part);
+  hipLaunchKernelGGL(proj_sum3_group_kernel, dim3(1, g.n_units), dim3(256), 0, s, g.part, nblk, g.out3);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_proj_ga_group(const ProjGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(proj_ga_group_kernel, dim3((g.nb + 255) / 256, g.np, g.n_units), dim3(256), 0, s, g.Kb, g.aV, g.ld, g.nb,
+                     g.n, g.gm, g.gv, g.mb, g.Ga);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_proj_gkb_group(const ProjGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(proj_gkb_group_kernel, dim3((g.nb + 255) / 256, g.np, g.n_units), dim3(256), 0, s, g.am, g.ld, g.nb, g.n,
+                     g.gv, g.GaKi);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_proj_gktb_group(const ProjGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(proj_gktb_group_kernel, dim3((g.nb + 255) / 256, g.nb, g.n_units), dim3(256), 0, s, g.Ki, g.P1, g.P2, g.ld,
+                     g.nb, g.bvec, g.G);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_proj_trace_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, PerUnit<double*> out, hipStream_t s) {
+  hipLaunchKernelGGL(proj_trace_group_kernel, dim3(1, n_units), dim3(256), 0, s, A, lda, n, out);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_proj_moments(const double* Bp, const double* Kb, const double* aV, int64_t ld, int nb, const double* mb,

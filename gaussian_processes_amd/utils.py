@@ -657,7 +657,7 @@ def _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fpar
     r, a, aL, L, kv0 = (_cu(t).contiguous() for t in (r, KKtilde_inv, aL, L, kv0))
     N, nb = a.shape
     dev = a.device
-    q = {"r": r, "a": a, "aL": aL, "L": L, "kv0": kv0, "N": int(N), "nb": int(nb), "logA0": float(logA0),
+    q = {"kind": "chain", "r": r, "a": a, "aL": aL, "L": L, "kv0": kv0, "N": int(N), "nb": int(nb), "logA0": float(logA0),
          "n_steps": int(n_steps), "nfp": int(n_fparam_steps),
          "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
     q["m"] = _cu(m).clone().contiguous()
@@ -735,14 +735,15 @@ def _chain_run_group(qs):
     return [_chain_result(q, rec[u * per:(u + 1) * per]) for u, q in enumerate(qs)]
 
 
-def _group_engines(count, n):
-    """``count`` workspaces of this thread for problems up to ``n``: its own (``get_engine``) and ``count - 1`` more,
-    kept for the thread's later group calls."""
-    own = get_engine(n, 1)
-    extra = [e for e in getattr(_CELLS, "engines", []) if e.n_max >= n and e.device == own.device]
+def _group_engines(count, n, d=1, d_full=1):
+    """``count`` workspaces of this thread for problems up to ``n`` stimuli (``d`` masked / ``d_full`` image pixels): its
+    own (``get_engine``) and ``count - 1`` more, kept for the thread's later group calls."""
+    own = get_engine(n, d, d_full)
+    kept = getattr(_CELLS, "engines", [])
+    extra = [e for e in kept if e.n_max >= n and e.d_max >= d and e.d_full_max >= d_full and e.device == own.device]
     while len(extra) < count - 1:
-        extra.append(GPFitEngine(n, 1, 1, device=own.device))
-    _CELLS.engines = extra
+        extra.append(GPFitEngine(n, d, d_full, device=own.device))
+    _CELLS.engines = extra + [e for e in kept if e not in extra]
     return [own] + extra[:count - 1]
 
 
@@ -768,7 +769,15 @@ class _ChainRendezvous:
     bucket of one, ``group`` in slices of ``max_units`` for a larger one), then hands every fit its result.  A fit's
     thread starts with ``enter``; a fit that ends, fails or will never ask (``leave``) is no longer waited for.  An
     exception of a call is raised in every fit whose request was part of that call.  ``group_sizes``: the units of
-    every call issued, in order."""
+    every call issued, in order.
+
+    A wave's fits hand in two kinds of request -- the E-step chains and the M-step closures of their L-BFGS, whose line
+    searches differ from cell to cell -- so at any moment some fits wait with a closure and others with a chain.  The
+    rendezvous does not tell them apart: ``single``, ``group`` and ``key`` dispatch on the request's ``kind`` field, and
+    ``key`` carries the kind, so two kinds never share a call.  Only the bookkeeping looks at it: calls of requests whose
+    ``kind`` is ``"closure"`` are counted in ``closure_group_sizes`` / ``closure_call_seconds`` /
+    ``seconds_in_closure_call``, all others (a request without a kind included) in ``group_sizes`` / ``call_seconds`` /
+    ``seconds_in_call``."""
 
     def __init__(self, parties, single, group, key, max_units=MAX_CHAIN_UNITS):
         self.cond = threading.Condition()
@@ -783,6 +792,11 @@ class _ChainRendezvous:
         self.group_sizes = []
         self.call_seconds = []     # host wall time of every call issued (enqueue to results), as group_sizes
         self.seconds_in_call = 0.0  # summed over the fits: time between handing a request in and getting its result
+        self.closure_group_sizes, self.closure_call_seconds, self.seconds_in_closure_call = [], [], 0.0
+
+    @staticmethod
+    def _is_closure(request):
+        return isinstance(request, dict) and request.get("kind") == "closure"
 
     def enter(self):
         """First statement of a fit's thread: wait for the turn."""
@@ -808,7 +822,10 @@ class _ChainRendezvous:
             res = self.results.pop(ticket)
         self.turn.acquire()
         with self.cond:
-            self.seconds_in_call += time.perf_counter() - t_in
+            if self._is_closure(request):
+                self.seconds_in_closure_call += time.perf_counter() - t_in
+            else:
+                self.seconds_in_call += time.perf_counter() - t_in
         if isinstance(res, BaseException):
             raise res
         return res
@@ -821,7 +838,8 @@ class _ChainRendezvous:
         for tickets in buckets.values():
             for i in range(0, len(tickets), self.max_units):
                 part = tickets[i:i + self.max_units]
-                self.group_sizes.append(len(part))
+                closure = self._is_closure(self.waiting[part[0]])
+                (self.closure_group_sizes if closure else self.group_sizes).append(len(part))
                 t_call = time.perf_counter()
                 try:
                     if len(part) == 1:
@@ -832,7 +850,7 @@ class _ChainRendezvous:
                             raise RuntimeError("the group call returned a result list of the wrong length")
                 except BaseException as err:      # handed to every participant, also a KeyboardInterrupt
                     out = [err] * len(part)
-                self.call_seconds.append(time.perf_counter() - t_call)
+                (self.closure_call_seconds if closure else self.call_seconds).append(time.perf_counter() - t_call)
                 for t, res in zip(part, out):
                     self.results[t] = res
         self.waiting.clear()
@@ -870,8 +888,13 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
     Fits that never chain (f_params carrying ``loglambda0``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
     being waited for; a fit in the full-rank regime is waited for until it ends.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is
-    the error of every fit in that call.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
-    invocation, in order (1: the single call).  The workspaces of the fits (one per concurrent fit, each of the size of
+    the error of every fit in that call.  The sparse M-step closures of the wave's fits (``_closure_sparse``) meet at the
+    same place: whenever every live fit waits -- some with a closure of their L-BFGS, some already with their next chain
+    -- the closures go out as ONE ``gpfit_fit_eval_sparse_batch`` call per group of equal ``_closure_bucket_key`` and the
+    chains as theirs.  A closure that returns the infinite loss on the host (theta outside the limits) asks nothing, and
+    a fit in the full-rank or truncated regime keeps its own closure calls.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
+    invocation, in order (1: the single call); ``last_closure_group_sizes``, ``last_closure_call_seconds`` and
+    ``last_seconds_in_closure_call``: the same for the closure calls.  The workspaces of the fits (one per concurrent fit, each of the size of
     a ``varGP`` workspace) are kept for the next call; ``release_cell_workspaces()`` frees them."""
     n_fits = len(r_list)
     if len(kwargs_list) != n_fits:
@@ -883,6 +906,7 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     stream = torch.cuda.current_stream(dev)
     grad = torch.is_grad_enabled()
     results, errors, sizes, call_seconds, in_call = [None] * n_fits, [None] * n_fits, [], [], 0.0
+    closure_sizes, closure_seconds, in_closure = [], [], 0.0
 
     def fit(i, rendezvous):
         key = (dev.index, threading.get_ident())
@@ -909,7 +933,7 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
 
     for first in range(0, n_fits, max_units):
         wave = range(first, min(n_fits, first + max_units))
-        rendezvous = _ChainRendezvous(len(wave), _chain_run_single, _chain_run_group, _chain_bucket_key, max_units)
+        rendezvous = _ChainRendezvous(len(wave), _request_run_single, _request_run_group, _request_bucket_key, max_units)
         threads = [threading.Thread(target=fit, args=(i, rendezvous), name=f"varGP_cells-{i}") for i in wave]
         for t in threads:
             t.start()
@@ -918,9 +942,15 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
         sizes += rendezvous.group_sizes
         call_seconds += rendezvous.call_seconds
         in_call += rendezvous.seconds_in_call
+        closure_sizes += rendezvous.closure_group_sizes
+        closure_seconds += rendezvous.closure_call_seconds
+        in_closure += rendezvous.seconds_in_closure_call
     varGP_cells.last_group_sizes = sizes
     varGP_cells.last_call_seconds = call_seconds      # host wall time of each of those calls
     varGP_cells.last_seconds_in_call = in_call        # summed over the fits: waiting for the wave plus the call
+    varGP_cells.last_closure_group_sizes = closure_sizes      # the same three for the M-step closure calls
+    varGP_cells.last_closure_call_seconds = closure_seconds
+    varGP_cells.last_seconds_in_closure_call = in_closure
     for err in errors:
         if err is not None:
             raise err
@@ -930,6 +960,9 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
 varGP_cells.last_group_sizes = []
 varGP_cells.last_call_seconds = []
 varGP_cells.last_seconds_in_call = 0.0
+varGP_cells.last_closure_group_sizes = []
+varGP_cells.last_closure_call_seconds = []
+varGP_cells.last_seconds_in_closure_call = 0.0
 
 
 def _estep_chain_commit(records, f_params):
@@ -1415,26 +1448,132 @@ def _closure_sparse(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params)
     """Sparse M-step closure (n_tilde < n_t; utils.py:2030-2099, 1114-1120): ONE call of the fused entry
     point ``gpfit_fit_eval_sparse``; the step-by-step formulation below (``_closure_sparse_steps``) is
     the path taken when a factorisation meets a non-positive pivot (reference's eigen-fallback of
-    ``log_det``, utils.py:1279-1304)."""
-    lib = _lib.load()
+    ``log_det``, utils.py:1279-1304).  In a fit of ``varGP_cells`` the device call is the wave's: the request goes
+    to the rendezvous and comes back as one unit of a ``gpfit_fit_eval_sparse_batch`` call, with the same bits."""
+    q = _closure_sparse_prepare(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params)
+    rendezvous = getattr(_CELLS, "rendezvous", None)
+    rc_, out = rendezvous.call(q) if rendezvous is not None else _closure_run_single(q)
+    return _closure_sparse_finish(q, rc_, out)
+
+
+def _closure_sparse_prepare(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params, engine=None):
+    """The arguments of ``_closure_sparse`` as one request: the operands on the device, the scalars as floats, and the
+    workspace and stream the call runs on -- this thread's unless an engine is given."""
     lower, upper = lims
     xc, xtc, rc, Bc, mc, Vc = _cu(x), _cu(xtilde), _cu(r), _cu(B), _cu(m_b), _cu(V_b)
     rows, cols = _grid(n_px_side)
-    eng = get_engine(max(xc.shape[0], xtc.shape[0]), xc.shape[1], rows * cols)
+    q = {"kind": "closure", "theta": [float(v) for v in theta_vec(theta)],
+         "lower": [_scalar(lower[k]) for k in THETA_KEYS], "upper": [_scalar(upper[k]) for k in THETA_KEYS],
+         "rows": rows, "cols": cols, "x": xc, "xt": xtc, "r": rc, "B": Bc, "m_b": mc, "V_b": Vc,
+         "N": int(xc.shape[0]), "Nt": int(xtc.shape[0]), "n_kept": int(Bc.shape[1]),
+         "logA": _scalar(f_params['logA']), "lambda0": _scalar(_lambda0_of(f_params)),
+         "args": (theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params)}
+    q["engine"] = engine if engine is not None else get_engine(max(q["N"], q["Nt"]), xc.shape[1], rows * cols)
+    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    return q
+
+
+def _closure_run_single(q):
+    """``gpfit_fit_eval_sparse`` on one request: ``(rc, out[16])``."""
     out = (ctypes.c_double * 16)()
-    rc_ = lib.gpfit_fit_eval_sparse(eng._ctx, _stream(), _lib.darr(theta_vec(theta)),
-                                    _lib.darr([_scalar(lower[k]) for k in THETA_KEYS]),
-                                    _lib.darr([_scalar(upper[k]) for k in THETA_KEYS]), rows, cols,
-                                    xc.data_ptr(), xc.stride(0), xc.shape[0], xtc.data_ptr(), xtc.stride(0), xtc.shape[0],
-                                    rc.data_ptr(), Bc.data_ptr(), Bc.stride(0), Bc.shape[1], mc.data_ptr(), Vc.data_ptr(),
-                                    Vc.stride(0), _scalar(f_params['logA']), _scalar(_lambda0_of(f_params)), out)
-    if rc_ == -2:
-        raise ValueError(_lib.last_error())
-    if rc_ < 0:
+    x, xt, B, V = q["x"], q["xt"], q["B"], q["V_b"]
+    rc_ = _lib.load().gpfit_fit_eval_sparse(q["engine"]._ctx, q["stream"], _lib.darr(q["theta"]), _lib.darr(q["lower"]),
+                                            _lib.darr(q["upper"]), q["rows"], q["cols"], x.data_ptr(), x.stride(0), q["N"],
+                                            xt.data_ptr(), xt.stride(0), q["Nt"], q["r"].data_ptr(), B.data_ptr(),
+                                            B.stride(0), q["n_kept"], q["m_b"].data_ptr(), V.data_ptr(), V.stride(0),
+                                            q["logA"], q["lambda0"], out)
+    if rc_ < 0 and rc_ != -2:
         _lib.check(rc_, "gpfit_fit_eval_sparse")
+    return rc_, list(out)
+
+
+def _closure_bucket_key(q):
+    """Requests with equal keys may share one ``gpfit_fit_eval_sparse_batch`` call: what that call shares between its
+    units, and the padded basis size (the recursion's split, hence the bits, depend on it)."""
+    return (q["x"].device.index, q["stream"].value, q["N"], q["Nt"], q["x"].stride(0), q["xt"].stride(0), q["rows"], q["cols"],
+            -(-q["n_kept"] // 128) * 128)
+
+
+def _closure_batch_raw(ctxs, qs, out=None, rcs=None):
+    """``gpfit_fit_eval_sparse_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return
+    code, the 16 outputs per unit and the per-unit codes, nothing checked here -- the shared arguments are those of
+    ``qs[0]``.  A tensor given as None goes in as a null pointer; ``out`` / ``rcs``: the caller's arrays instead of new ones."""
+    nu = len(qs)
+
+    def ptrs(key):
+        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
+
+    def flat(key):
+        return _lib.darr([v for q in qs for v in q[key]])
+
+    q0 = qs[0]
+    out = (ctypes.c_double * (16 * nu))() if out is None else out
+    rcs = (ctypes.c_int * nu)() if rcs is None else rcs
+    rc = _lib.load().gpfit_fit_eval_sparse_batch(
+        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
+        flat("theta"), flat("lower"), flat("upper"), q0["rows"], q0["cols"], ptrs("x"), q0["x"].stride(0), q0["N"], ptrs("xt"),
+        q0["xt"].stride(0), q0["Nt"], ptrs("r"), ptrs("B"),
+        (ctypes.c_int64 * nu)(*[q["n_kept"] if q["B"] is None else q["B"].stride(0) for q in qs]),
+        (ctypes.c_int64 * nu)(*[q["n_kept"] for q in qs]), ptrs("m_b"), ptrs("V_b"),
+        (ctypes.c_int64 * nu)(*[q["n_kept"] if q["V_b"] is None else q["V_b"].stride(0) for q in qs]),
+        _lib.darr([q["logA"] for q in qs]), _lib.darr([q["lambda0"] for q in qs]), out, rcs)
+    return rc, out, rcs
+
+
+def _closure_run_group(qs):
+    """One ``gpfit_fit_eval_sparse_batch`` call on requests of one bucket (``_closure_bucket_key``), each on its own
+    workspace; per request what ``_closure_run_single`` returns, with the same bits."""
+    if len({_closure_bucket_key(q) for q in qs}) != 1:
+        raise ValueError("_closure_run_group: the requests of one call share the stimuli's sizes and leading dimensions, "
+                         "the pixel grid and the padded basis size")
+    rc, out, rcs = _closure_batch_raw([q["engine"]._ctx for q in qs], qs)
+    _lib.check(rc, "gpfit_fit_eval_sparse_batch")
+    return [(int(rcs[u]), list(out[16 * u:16 * u + 16])) for u in range(len(qs))]
+
+
+def _closure_sparse_finish(q, rc_, out):
+    """What ``_closure_sparse`` returns or raises for the code and the outputs the device call gave its request; a
+    non-positive pivot (``rc_ > 0``) takes the step-by-step formulation, in the caller's own thread."""
+    if rc_ == -2:
+        _lib.load().gpfit_check_limits(_lib.darr(q["theta"]), _lib.darr(q["lower"]), _lib.darr(q["upper"]))   # its message
+        raise ValueError(_lib.last_error())
     if rc_ == 0:
         return out[0], {k: out[3 + i] for i, k in enumerate(THETA_KEYS)}
-    return _closure_sparse_steps(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params)
+    return _closure_sparse_steps(*q["args"])
+
+
+def _closure_sparse_group(units):
+    """``_closure_sparse`` for several independent units (cells, restarts of one cell) as ONE device call
+    (``gpfit_fit_eval_sparse_batch``).  ``units``: one dict per unit with the arguments of ``_closure_sparse`` by name;
+    1 .. 16 units of one ``_closure_bucket_key``.  Returns, per unit, what ``_closure_sparse`` returns for it, bit for
+    bit; a unit whose call would raise has the exception in its place, and a unit whose factorisation fails takes the
+    step-by-step formulation alone."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"_closure_sparse_group: 1 .. {MAX_CHAIN_UNITS} units per call")
+    rows, cols = _grid(units[0]["n_px_side"])
+    cap = max(max(u["x"].shape[0], u["xtilde"].shape[0]) for u in units)
+    engines = _group_engines(len(units), cap, units[0]["x"].shape[1], rows * cols)
+    qs = [_closure_sparse_prepare(engine=e, **u) for u, e in zip(units, engines)]
+    res = []
+    for q, (rc_, out) in zip(qs, _closure_run_group(qs) if len(qs) > 1 else [_closure_run_single(qs[0])]):
+        try:
+            res.append(_closure_sparse_finish(q, rc_, out))
+        except Exception as err:      # what _closure_sparse raises for this unit alone
+            res.append(err)
+    return res
+
+
+# what the rendezvous of varGP_cells is given: two kinds of request, each with its own calls and bucket key
+def _request_run_single(q):
+    return _closure_run_single(q) if q["kind"] == "closure" else _chain_run_single(q)
+
+
+def _request_run_group(qs):
+    return _closure_run_group(qs) if qs[0]["kind"] == "closure" else _chain_run_group(qs)
+
+
+def _request_bucket_key(q):
+    return (q["kind"],) + (_closure_bucket_key(q) if q["kind"] == "closure" else _chain_bucket_key(q))
 
 
 def _closure_sparse_steps(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params):
