@@ -53,6 +53,8 @@ _SIGS = {
     "gpfit_fparam_lbfgs": (i32, [vp, vp, vp, vp, vp, i64, f64, i32, f64, i32, i32, f64, f64, f64, vp, pd]),
     "gpfit_estep_chain": (i32, [vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, f64, i32, f64,
                                 i32, i32, i32, f64, f64, f64, pd]),
+    "gpfit_estep_chain_full": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, f64, i32, f64, i32, i32, i32, f64,
+                                     f64, f64, pd]),
     "gpfit_estep_chain_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, pd, i32, pd,
                                       i32, i32, i32, f64, f64, f64, pd]),
     "gpfit_fparam_lbfgs_host": (i32, [vp, vp, vp, i64, f64, i32, f64, i32, i32, f64, f64, f64, vp, pd]),

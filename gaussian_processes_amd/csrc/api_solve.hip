@@ -420,6 +420,76 @@ int gpfit_estep_chain(gpfit_ctx* c, void* stream, const double* a, int64_t lda, 
   return 0;
 }
 
+int gpfit_estep_chain_full(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_t N, const double* r,
+                           const double* kv0, double* m, double* f, double* V_out, int64_t ldv, double* lam_m,
+                           double* lam_var, double logA0, int lambda0_mode, double lambda0_fixed, int n_steps,
+                           int max_iter, int history_size, double lr, double tol_grad, double tol_change,
+                           double* rec_host) {
+  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS) {
+    set_error("gpfit_estep_chain_full: n_steps " + std::to_string(n_steps) + " is not within 1 .. " +
+              std::to_string(CHAIN_MAX_STEPS));
+    return -3;
+  }
+  if (!c || !K || !r || !kv0 || !m || !f || !V_out || !lam_m || !lam_var || !rec_host || N <= 0 || N > INT32_MAX ||
+      ldk < N || ldv < N) {
+    set_error("gpfit_estep_chain_full: bad argument");
+    return -3;
+  }
+  Lbfgs1dConfig cfg;
+  GP_TRY(fparam_lbfgs_config("gpfit_estep_chain_full", max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+  GP_CTX_ENTER(c, "gpfit_estep_chain_full");
+  hipStream_t s = (hipStream_t)stream;
+  const int n = (int)N, np = (int)round_up(N, TILE);
+  if (np > c->np_cap) {
+    set_error("gpfit_estep_chain_full: problem larger than the context capacity");
+    return -3;
+  }
+  const int64_t ld = np;
+  // the work vectors and matrices of gpfit_estep, product for product
+  double *sv = c->yv, *rhs = c->bv, *mo = c->tvec, *Vw = c->Wbuf;
+  const CholBatchT<double> b = one_chain(c, ld);
+  const Lane lane = main_lane(c, s);
+  auto at = [&](double* X, int r, int col) { return mat(X + (int64_t)r * ld + col, ld); };
+  ChainBlock* blk = c->chain;
+  const ChainGate gate{&blk->stop, c->info + INFO_K};
+  const size_t rec_bytes = (size_t)n_steps * CHAIN_REC * sizeof(double);
+  GP_HIP(hipMemsetAsync(&blk->rec[0][0], 0, rec_bytes, s));
+  GP_TRY(launch_chain_init(blk, logA0, lambda0_mode ? lambda0_fixed : 0.0, s));
+  for (int step = 0; step < n_steps; ++step) {
+    double* rec = &blk->rec[step][0];
+    GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
+    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
+    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
+    GP_TRY(launch_estep_prep_chain(f, r, m, n, np, blk, rec, sv, rhs, s));
+    // M = I + S K S (lower), SK = S K (dense), Kl = K (lower): Kl is overwritten by V, so it is rebuilt every step
+    GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, Vw, ld, s));
+    if (np >= 2 * TILE) {
+      const int kt = np / TILE;
+      const int n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;
+      GP_TRY(potrf_lockstep(b, 0, np, 0u, lane, 1u));   // [L^-1]11 and [L^-1]22 only
+      GP_TRY(launch_chain_info(blk, c->info + INFO_K, rec, s));
+      GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
+      GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(c->Lbuf, n1, 0)), plain(at(c->Abuf, 0, 0)), into(at(c->Zbuf, n1, 0), 1.0)));
+      GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(c->Libuf, n1, n1))), plain(at(c->Zbuf, n1, 0)), into(at(c->Abuf, n1, 0)), 1));
+    } else {
+      GP_TRY(potrf_lockstep(b, 0, np, 1u, lane));
+      GP_TRY(launch_chain_info(blk, c->info + INFO_K, rec, s));
+      GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
+    }
+    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
+    GP_TRY(product(lane, {np, np, np}, -1.0, trans(at(c->Abuf, 0, 0)), plain(at(c->Abuf, 0, 0)), into_lower(at(Vw, 0, 0), 1.0)));
+    GP_TRY(launch_symv_lower(Vw, ld, n, rhs, mo, s));
+    GP_TRY(launch_chain_copy(gate, mo, n, m, s));
+    GP_TRY(launch_unpack_sym_chain(gate, Vw, ld, n, V_out, ldv, s));
+    GP_TRY(launch_estep_full_moments_chain(gate, mo, Vw, ld, kv0, n, lam_m, lam_var, s));
+    GP_TRY(launch_fparam_lbfgs_chain(gate, lam_m, lam_var, r, n, lambda0_mode ? 1 : 0, lambda0_fixed, cfg, f, blk, rec, s));
+  }
+  GP_HIP(hipMemcpyAsync(c->chain_host, &blk->rec[0][0], rec_bytes, hipMemcpyDeviceToHost, s));
+  GP_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[i] = c->chain_host[i];
+  return 0;
+}
+
 static_assert(GPFIT_ESTEP_CHAIN_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
 
 int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a, const int64_t* lda,

@@ -1276,9 +1276,10 @@ int launch_fill(double* x, int64_t n, double v, hipStream_t s) {
 
 // ------------------------------------------------------------------ E-step helpers
 // s_i = A sqrt(f_i) ; rhs_i = A^2 f_i m_i + A (r_i - f_i)   (utils.py:1421-1422, 1431 with a = I)
-__global__ void estep_prep_kernel(const double* __restrict__ f, const double* __restrict__ r,
-                                  const double* __restrict__ m, int n, int np, double A, double* __restrict__ sv,
-                                  double* __restrict__ rhs) {
+// (the body is shared by the by-value kernel and the chain's, which forms A on the device: equal A, equal bits)
+__device__ __forceinline__ void estep_prep_body(const double* __restrict__ f, const double* __restrict__ r,
+                                                const double* __restrict__ m, int n, int np, double A,
+                                                double* __restrict__ sv, double* __restrict__ rhs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= np) return;
   if (i >= n) {
@@ -1289,10 +1290,30 @@ __global__ void estep_prep_kernel(const double* __restrict__ f, const double* __
   sv[i] = A * sqrt(f[i]);
   rhs[i] = A * A * f[i] * m[i] + A * (r[i] - f[i]);
 }
+__global__ void estep_prep_kernel(const double* __restrict__ f, const double* __restrict__ r,
+                                  const double* __restrict__ m, int n, int np, double A, double* __restrict__ sv,
+                                  double* __restrict__ rhs) {
+  estep_prep_body(f, r, m, n, np, A, sv, rhs);
+}
+// A step of gpfit_estep_chain_full: A = exp(logA) of the chain block, recorded for the caller while the chain runs
+__global__ void estep_prep_chain_kernel(const double* __restrict__ f, const double* __restrict__ r,
+                                        const double* __restrict__ m, int n, int np,
+                                        const ChainBlock* __restrict__ blk, double* __restrict__ rec,
+                                        double* __restrict__ sv, double* __restrict__ rhs) {
+  const double A = exp(blk->logA);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && blk->stop == 0) rec[CR_A] = A;
+  estep_prep_body(f, r, m, n, np, A, sv, rhs);
+}
 
 int launch_estep_prep(const double* f, const double* r, const double* m, int n, int np, double A, double* sv,
                       double* rhs, hipStream_t s) {
   hipLaunchKernelGGL(estep_prep_kernel, dim3((np + 255) / 256), dim3(256), 0, s, f, r, m, n, np, A, sv, rhs);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, const ChainBlock* blk,
+                            double* rec, double* sv, double* rhs, hipStream_t s) {
+  hipLaunchKernelGGL(estep_prep_chain_kernel, dim3((np + 255) / 256), dim3(256), 0, s, f, r, m, n, np, blk, rec, sv, rhs);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -1414,6 +1435,26 @@ __global__ void unpack_sym_chain_kernel(ChainGate g, const double* __restrict__ 
 }
 int launch_unpack_sym_chain(ChainGate g, const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s) {
   hipLaunchKernelGGL(unpack_sym_chain_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, g, src, lds, n, dst, ldd);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// the full-rank moments behind a committed update (gpfit_estep_chain_full; a = B = I): lam_m = m_new and
+// lam_var = (Kvec - diag K~) + diag V, the diagonal read from the lower-tile work matrix the update left
+__global__ void estep_full_moments_chain_kernel(ChainGate g, const double* __restrict__ m_new,
+                                                const double* __restrict__ Vw, int64_t ld,
+                                                const double* __restrict__ kv0, int n, double* __restrict__ lam_m,
+                                                double* __restrict__ lam_var) {
+  if (!g.open()) return;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  lam_m[i] = m_new[i];
+  lam_var[i] = kv0[i] + Vw[(int64_t)i * ld + i];
+}
+int launch_estep_full_moments_chain(ChainGate g, const double* m_new, const double* Vw, int64_t ld, const double* kv0,
+                                    int n, double* lam_m, double* lam_var, hipStream_t s) {
+  hipLaunchKernelGGL(estep_full_moments_chain_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g, m_new, Vw, ld, kv0, n,
+                     lam_m, lam_var);
   GP_HIP(hipGetLastError());
   return 0;
 }

@@ -247,6 +247,13 @@ int launch_chain_copy(ChainGate g, const double* src, int n, double* dst, hipStr
 int launch_unpack_sym_chain(ChainGate g, const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
 int launch_estep_proj_moments_chain(ChainGate g, const double* Z, int64_t ld, int nb, const double* z1, const double* kv0,
                                     int n, double* lam_m, double* lam_var, hipStream_t s);
+// the full-rank chain (gpfit_estep_chain_full): launch_estep_prep with A = exp(blk->logA) formed on the device (the same
+// body: equal A, equal bits), rec[CR_A] <- A unless the chain has stopped; and, behind the gate, the moments of the
+// original basis, lam_m <- m_new, lam_var <- kv0 + diag(Vw) (Vw: the lower-tile work matrix holding V)
+int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, const ChainBlock* blk,
+                            double* rec, double* sv, double* rhs, hipStream_t s);
+int launch_estep_full_moments_chain(ChainGate g, const double* m_new, const double* Vw, int64_t ld, const double* kv0,
+                                    int n, double* lam_m, double* lam_var, hipStream_t s);
 // launch_fparam_lbfgs behind the gate, started at blk->logA: rec[0..8] <- its results and rec[CR_RAN] <- 1; with status 0
 // it leaves (logA, lambda0) in the block and the rate in f, otherwise it sets the stop word
 int launch_fparam_lbfgs_chain(ChainGate g, const double* lam_m, const double* lam_var, const double* r, int n,

@@ -646,6 +646,37 @@ def _estep_chain(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam
     return _chain_run_single(q)
 
 
+def _estep_chain_full(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
+                      lambda_m=None, lambda_var=None):
+    """``_estep_chain`` in the full-rank regime (inducing set = training set, every eigenvalue kept, identity basis):
+    ``n_steps`` x (the update of ``gpfit_estep`` in the original basis, the moments ``lambda_m = m``, ``lambda_var =
+    kv0 + diag(V)`` with ``kv0 = Kvec - diag(K~)``, then ``_fparam_lbfgs``) as ONE device call and one wait
+    (``gpfit_estep_chain_full``).  Returns what ``_estep_chain`` returns: copies ``(m, V, lambda_m, lambda_var, f,
+    records)`` of the state behind the last step that committed, the arguments left alone; ``lambda0_fixed`` as there.
+    The call goes out on this thread's workspace, also under ``varGP_cells`` (no lock-step group form: a full-rank fit
+    keeps its turn until it ends).  ``_estep_chain_full_commit`` turns the records into f_params or into the error of
+    the first failing step."""
+    r, K, kv0 = (_cu(t).contiguous() for t in (r, K_tilde, kv0))
+    N = int(K.shape[0])
+    dev = K.device
+    m = _cu(m).clone().contiguous()
+    f = _cu(f_mean).clone().contiguous()
+    V = torch.empty((N, N), dtype=TORCH_DTYPE, device=dev) if V is None else _cu(V).clone().contiguous()
+    lam_m = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_m is None else _cu(lambda_m).clone().contiguous()
+    lam_var = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_var is None else _cu(lambda_var).clone().contiguous()
+    n_steps, nfp = int(n_steps), int(n_fparam_steps)
+    fixed = lambda0_fixed is not None
+    rec = (ctypes.c_double * (12 * max(n_steps, 1)))()
+    eng = get_engine(N, 1)
+    _lib.check(_lib.load().gpfit_estep_chain_full(eng._ctx, _stream(), K.data_ptr(), K.stride(0), N, r.data_ptr(),
+                                                  kv0.data_ptr(), m.data_ptr(), f.data_ptr(), V.data_ptr(), V.stride(0),
+                                                  lam_m.data_ptr(), lam_var.data_ptr(), float(logA0), 1 if fixed else 0,
+                                                  float(lambda0_fixed) if fixed else 0.0, n_steps, nfp, nfp, 0.1, 1.e-7,
+                                                  1.e-9, rec),
+               "gpfit_estep_chain_full")
+    return m, V, lam_m, lam_var, f, [list(rec[12 * k:12 * k + 12]) for k in range(n_steps)]
+
+
 MAX_CHAIN_UNITS = 16     # GPFIT_ESTEP_CHAIN_MAX_UNITS of the C header
 _CELLS = threading.local()   # .rendezvous: the _ChainRendezvous of the varGP_cells wave this thread fits in; .engines
 
@@ -887,7 +918,8 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     are those of ``varGP`` on its own, bit for bit.  Between two chains the fits of a wave take turns, one running at a
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
     Fits that never chain (f_params carrying ``loglambda0``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
-    being waited for; a fit in the full-rank regime is waited for until it ends.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is
+    being waited for; a fit in the full-rank regime issues its chains (``_estep_chain_full``) directly on its own
+    workspace and is waited for until it ends.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is
     the error of every fit in that call.  The sparse M-step closures of the wave's fits (``_closure_sparse``) meet at the
     same place: whenever every live fit waits -- some with a closure of their L-BFGS, some already with their next chain
     -- the closures go out as ONE ``gpfit_fit_eval_sparse_batch`` call per group of equal ``_closure_bucket_key`` and the
@@ -982,6 +1014,25 @@ def _estep_chain_commit(records, f_params):
             raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been called {status} times in '
                              f'estep {k} iteration.')                                                        # :1923
     return records[-1]
+
+
+def _estep_chain_full_commit(records, f_params, f_mean):
+    """``_estep_chain_commit`` for the records of ``_estep_chain_full``: the errors are those of the host loop around
+    ``gpfit_estep``.  A step whose I + S K S is not positive definite raises the loop's ValueError when the rate it read
+    is not finite (``f_mean``: the rate the chain returns -- a step that commits nothing leaves it as it read it), its
+    LinAlgError otherwise; every other step is handed to ``_estep_chain_commit``."""
+    for k, rec in enumerate(records):
+        if rec[9] != 0:
+            if k > 0:
+                _estep_chain_commit(records[:k], f_params)
+            if not bool(torch.isfinite(f_mean).all()):
+                # the reference's LU solve lets NaNs through and reports them one step later, in the rate-parameter
+                # closure (utils.py:1923-1924)
+                raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been called 1 times in '
+                                 f'estep {k} iteration. Try substituting them with inf.')
+            raise torch.linalg.LinAlgError("Estep: gpfit_estep: I + S K S is not positive definite (is K_tilde symmetric "
+                                           f"positive definite?) (rc={int(rec[9])})")
+    return _estep_chain_commit(records, f_params)
 
 
 # ------------------------------------------------------------------ inference
@@ -1313,8 +1364,8 @@ _DENSE_MIN_N = 256     # below this the reference's own eigh (a few ms)
 #   "eigenvectors" the reference's own choice (utils.py:1683-1694): the kept eigenvectors, K_tilde_b diagonal, at the
 #                  price of one k x k eigendecomposition (k = 1024) per basis: 16 ms more per EM iteration.
 EIGTOP_BASIS = _os_mod.environ.get("GPFIT_EIGTOP_BASIS", "subspace")
-# The nEstep updates of an EM iteration in the truncated / sparse regimes as one device call (_estep_chain) instead of
-# two calls and two waits per update (module global read at call time; GPFIT_ESTEP_CHAIN=0 turns it off).  A = exp(logA)
+# The nEstep updates of an EM iteration as one device call (_estep_chain in the truncated / sparse regimes,
+# _estep_chain_full in the full-rank regime with the identity basis) instead of two calls and two waits per update (module global read at call time; GPFIT_ESTEP_CHAIN=0 turns it off).  A = exp(logA)
 # is then the device's exp, not the host's: a fit may differ from the loop's by rounding.
 ESTEP_CHAIN = _os_mod.environ.get("GPFIT_ESTEP_CHAIN", "1") != "0"
 # per host thread (the reference's active-learning notebook fits and scores on two threads): the route the last
@@ -1733,9 +1784,13 @@ def varGP(x, r, **kwargs):
     State is kept, as in the reference, in the eigenbasis ``B`` of K~ (``m_b``, ``V_b``).  While
     every eigenvalue is kept and the inducing set is the training set (the regime of the
     north-star configurations) the M-step closure is ONE call of the fused HIP unit of work
-    (``gpfit_fit_eval``) and the E-step ONE call of ``gpfit_estep`` in the original basis;
-    otherwise the same steps run in the reference's projected formulation on the GPU
-    primitives.
+    (``gpfit_fit_eval``) and the ``nEstep`` E-steps of an EM iteration ONE call in the original basis
+    (``gpfit_estep_chain_full``: the update of ``gpfit_estep``, the moments and the rate-parameter optimiser,
+    ``nEstep`` times, with one wait); otherwise the same steps run in the reference's projected formulation on
+    the GPU primitives, the E-steps again as one call (``gpfit_estep_chain``).  The host loop around single
+    updates stays where a chain does not apply: ``f_params`` carrying ``loglambda0``, more than 1024 E-steps,
+    ``GPFIT_ESTEP_CHAIN=0``, and the full-rank regime with a square basis that is not the identity (the ``eigh``
+    route keeping every eigenvalue), which rotates by ``B`` around every update.
 
     Deviations from the reference's ``fit_model``, both additive or opt-out:
     * ``final_kernel['eigvecs']`` (utils.py:2241: the N x N eigenvector matrix of K~) is ``None`` when every
@@ -1957,6 +2012,21 @@ def varGP(x, r, **kwargs):
                     last_rec = _estep_chain_commit(chain_rec, f_params)     # raises for the first failing step
                     rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), last_rec[1], f_fp)
                     # (the rate-parameter share of the call is not separable: times['fparams'] stays as it is)
+                elif (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params
+                        and full_rank() and _is_identity(B)):
+                    # the full-rank regime in the original basis (a = B = I): the loop below around gpfit_estep as one
+                    # device call.  A square B that is not the identity (the eigh route keeping everything) keeps the
+                    # loop: it rotates by B around every update
+                    if nMstep > 0:
+                        lambda_m, lambda_var = moments_now()                                  # :1871
+                        f_params['lambda0'] = lambda0_and_rate()                              # :1874
+                    f_mean = rate_now()                                                         # :1877
+                    kv0 = Kvec - torch.diagonal(K_tilde_b)
+                    m_b, V_b, lambda_m, lambda_var, f_fp, chain_rec = _estep_chain_full(
+                        r, K_tilde, kv0, m_b, f_mean, _scalar(f_params['logA']), nEstep, nFparamstep, V=V_b,
+                        lambda_m=lambda_m, lambda_var=lambda_var)
+                    last_rec = _estep_chain_full_commit(chain_rec, f_params, f_fp)     # raises for the first failing step
+                    rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), last_rec[1], f_fp)
                 else:
                     for i_estep in range(nEstep):
                         if i_estep == 0 and nMstep > 0:

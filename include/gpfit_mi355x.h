@@ -345,6 +345,31 @@ int gpfit_estep_chain(gpfit_ctx* ctx, void* stream, const double* a, int64_t lda
                       int lambda0_mode, double lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                       double tol_grad, double tol_change, double* rec_host);
 
+/* The same chain in the full-rank regime (inducing set = training set, every eigenvalue kept, identity basis: varGP
+ * utils.py:1864-1934 with a = B = I): n_steps x (the update of gpfit_estep in the original basis, the moments
+ * lam_m = m_new, lam_var = kv0 + diag(V_new), then gpfit_fparam_lbfgs started at the logA in force), everything enqueued
+ * on `stream`, one synchronisation at the end.  logA, lambda0 and the rate stay on the device between steps.
+ * Fixed: K[N][ldk] symmetric (full) as in gpfit_estep, r [N], kv0 [N] = Kvec - diag(K~) (the caller's).  State, device,
+ * in/out: m [N], f [N] (updated in place: each step's first kernel consumes both before anything of that step writes
+ * them).  Outputs, device: V[N][ldv] (full, symmetric), lam_m [N], lam_var [N] of the last step that committed.  By
+ * value: logA0, lambda0_mode / lambda0_fixed and the optimiser's settings as in gpfit_fparam_lbfgs;
+ * 1 <= n_steps <= GPFIT_ESTEP_CHAIN_MAX_STEPS.
+ * rec_host[n_steps][12]: the records of gpfit_estep_chain, slot for slot; [9] is the LAPACK info of M = I + S K S,
+ * [11] the A = exp(logA) the device used (gpfit_estep takes the host's).  At equal A a step gives the bits of the calls
+ * it stands for: gpfit_estep, (Kvec - diag K~) + diag V, gpfit_fparam_lbfgs.
+ * lambda0_mode = 1 means what it means in gpfit_estep_chain, with the same caveat: a caller whose f_params carry
+ * loglambda0 keeps its host loop.
+ * A step whose M is not positive definite (info != 0) commits nothing; a step whose optimiser fails (status != 0) has
+ * committed m, V and the moments, and leaves f, logA and lambda0 alone.  After either, no later step changes m, V, f,
+ * lam_m, lam_var, logA or lambda0, and its record is all zero.
+ * Returns 0 when the chain ran, whatever the records say; -3, with nothing enqueued, on a bad argument, n_steps outside
+ * its range or round_up(N, 128) above the context's capacity. */
+int gpfit_estep_chain_full(gpfit_ctx* ctx, void* stream, const double* K, int64_t ldk, int64_t N, const double* r,
+                           const double* kv0, double* m, double* f, double* V, int64_t ldv, double* lam_m,
+                           double* lam_var, double logA0, int lambda0_mode, double lambda0_fixed, int n_steps,
+                           int max_iter, int history_size, double lr, double tol_grad, double tol_change,
+                           double* rec_host);
+
 /* gpfit_estep_chain for 1 .. GPFIT_ESTEP_CHAIN_MAX_UNITS independent units (cells, restarts of one cell) as ONE call:
  * unit u runs on its own context ctxs[u] (pairwise distinct, one device) with its own a[u], aL[u], L[u], r[u], kv0[u],
  * m[u], f[u], V[u], lam_m[u], lam_var[u], leading dimensions lda[u], ldal[u], ldl[u], ldv[u], size nb[u] and start
