@@ -21,6 +21,38 @@ static CholBatchT<double> one_chain(gpfit_ctx* c, int64_t ld) {
   return b;
 }
 
+// The full-rank Newton update of gpfit_estep and of every step of gpfit_estep_chain_full, on the context's work
+// matrices (M = I + S K S in Kbuf, S K in Zbuf, K's lower tiles in Wbuf; ld = np), in two halves: the chain records the
+// factorisation's info word between them.
+// From np = 2 TILE on T = L_M^-1 (S K) is formed block-wise, so that the off-diagonal block of L_M^-1 is never formed
+// (N^3/4 less):   T1 = [L^-1]11 B1 ,  T2 = [L^-1]22 (B2 - L21 T1)        with B = S K ; n1 rows in the top block
+static int full_update_split(int np) {
+  if (np < 2 * TILE) return 0;   // one leaf with its full inverse
+  const int kt = np / TILE;
+  const int n1 = ((kt + 1) / 2) * TILE;
+  return n1;
+}
+static int full_update_factor(gpfit_ctx* c, int np, Lane lane) {
+  const CholBatchT<double> b = one_chain(c, np);
+  if (full_update_split(np)) return potrf_lockstep(b, 0, np, 0u, lane, 1u);   // [L^-1]11 and [L^-1]22 only
+  return potrf_lockstep(b, 0, np, 1u, lane);
+}
+static int full_update_products(gpfit_ctx* c, int np, Lane lane) {
+  const int64_t ld = np;
+  auto at = [&](double* X, int r, int col) { return mat(X + (int64_t)r * ld + col, ld); };
+  // T = L_M^-1 (S K)          lower x dense                         N^3
+  if (const int n1 = full_update_split(np)) {
+    const int n2 = np - n1;
+    GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
+    GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(c->Lbuf, n1, 0)), plain(at(c->Abuf, 0, 0)), into(at(c->Zbuf, n1, 0), 1.0)));
+    GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(c->Libuf, n1, n1))), plain(at(c->Zbuf, n1, 0)), into(at(c->Abuf, n1, 0)), 1));
+  } else {
+    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
+  }
+  // V = K - T^T T             lower tiles only                      N^3
+  return product(lane, {np, np, np}, -1.0, trans(at(c->Abuf, 0, 0)), plain(at(c->Abuf, 0, 0)), into_lower(at(c->Wbuf, 0, 0), 1.0));
+}
+
 namespace {
 // y_i = sum_{j <= i} M[i][j] x_j for a lower-triangular row-major M (one wave per row)
 __global__ __launch_bounds__(256) void append_trmv_kernel(const double* __restrict__ M, int64_t ld, int n,
@@ -222,25 +254,9 @@ int gpfit_estep(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_
   GP_TRY(launch_estep_prep(f, r, m, n, np, A, sv, rhs, s));
   // M = I + S K S (lower), SK = S K (dense), Kl = K (lower)
   GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, c->Wbuf, ld, s));
-  const CholBatchT<double> b = one_chain(c, ld);
   const Lane lane = main_lane(c, s);
-  auto at = [&](double* X, int r, int col) { return mat(X + (int64_t)r * ld + col, ld); };
-  // T = L_M^-1 (S K)          lower x dense                         N^3
-  if (np >= 2 * TILE) {
-    // block-wise, so that the off-diagonal block of L_M^-1 is never formed (N^3/4 less):
-    //   T1 = [L^-1]11 B1 ,  T2 = [L^-1]22 (B2 - L21 T1)        with B = S K
-    const int kt = np / TILE;
-    const int n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;
-    GP_TRY(potrf_lockstep(b, 0, np, 0u, lane, 1u));   // [L^-1]11 and [L^-1]22 only
-    GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
-    GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(c->Lbuf, n1, 0)), plain(at(c->Abuf, 0, 0)), into(at(c->Zbuf, n1, 0), 1.0)));
-    GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(c->Libuf, n1, n1))), plain(at(c->Zbuf, n1, 0)), into(at(c->Abuf, n1, 0)), 1));
-  } else {
-    GP_TRY(potrf_lockstep(b, 0, np, 1u, lane));
-    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
-  }
-  // V = K - T^T T             lower tiles only                      N^3
-  GP_TRY(product(lane, {np, np, np}, -1.0, trans(at(c->Abuf, 0, 0)), plain(at(c->Abuf, 0, 0)), into_lower(at(c->Wbuf, 0, 0), 1.0)));
+  GP_TRY(full_update_factor(c, np, lane));
+  GP_TRY(full_update_products(c, np, lane));
   // m_new = V (A^2 f o m + A (r - f))                                utils.py:1431
   GP_TRY(launch_symv_lower(c->Wbuf, ld, n, rhs, c->tvec, s));
   GP_HIP(hipMemcpyAsync(m_new, c->tvec, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -350,76 +366,144 @@ int gpfit_fparam_lbfgs(gpfit_ctx* c, void* stream, const double* lam_m, const do
 }
 
 static_assert(GPFIT_ESTEP_CHAIN_MAX_STEPS == CHAIN_MAX_STEPS, "the header states the cap of the chain block");
+static_assert(GPFIT_ESTEP_CHAIN_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+
+// ONE body for gpfit_estep_chain (the group of one) and gpfit_estep_chain_batch: n_steps x (the update of
+// gpfit_estep_projected, product for product on the same work vectors and matrices, its moments, the rate-parameter
+// optimiser) for every unit on its own context, all on the caller's stream with one synchronisation at the end.  The
+// factorisations of all units are one lock-step recursion, every product goes through product on the list of units,
+// every small kernel is its unit-batched form: a unit runs the same products in the same order with the same reduction
+// order whatever else is in the group, so its outputs have the same bits alone and in any group.
+static int estep_chain_group_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a,
+                                  const int64_t* lda, const double* const* aL, const int64_t* ldal, const double* const* L,
+                                  const int64_t* ldl, int64_t N, const int64_t* nb, const double* const* r,
+                                  const double* const* kv0, double* const* m, double* const* f, double* const* V,
+                                  const int64_t* ldv, double* const* lam_m, double* const* lam_var, const double* logA0,
+                                  int lambda0_mode, const double* lambda0_fixed, int n_steps, int max_iter, int history_size,
+                                  double lr, double tol_grad, double tol_change, double* rec_host) {
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(name) + ": " + why);
+    return -3;
+  };
+  if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS)
+    return refuse("n_steps " + std::to_string(n_steps) + " is not within 1 .. " + std::to_string(CHAIN_MAX_STEPS));
+  if (!ctxs || !a || !lda || !aL || !ldal || !L || !ldl || !nb || !r || !kv0 || !m || !f || !V || !ldv || !lam_m || !lam_var ||
+      !logA0 || (lambda0_mode && !lambda0_fixed) || !rec_host || N <= 0 || N > INT32_MAX)
+    return refuse("bad argument");
+  Lbfgs1dConfig cfg;
+  GP_TRY(fparam_lbfgs_config(name, max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+  const int nrows = (int)round_up(N, TILE);
+  for (int u = 0; u < n_units; ++u) {
+    const std::string unit = n_units > 1 ? "unit " + std::to_string(u) + ": " : std::string();
+    if (!ctxs[u] || !a[u] || !aL[u] || !L[u] || !r[u] || !kv0[u] || !m[u] || !f[u] || !V[u] || !lam_m[u] || !lam_var[u])
+      return refuse(unit + "bad argument: null context or operand");
+    if (nb[u] <= 0 || lda[u] < nb[u] || ldal[u] < nb[u] || ldl[u] < nb[u] || ldv[u] < nb[u])
+      return refuse(unit + "bad argument: bad size or leading dimension");
+    if (ctxs[u]->device != ctxs[0]->device) return refuse("the contexts of one call must live on one device");
+    for (int v = 0; v < u; ++v)
+      if (ctxs[v] == ctxs[u]) return refuse("every unit needs a context of its own");
+    if (ctxs[u]->pend.active)
+      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
+    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+    if (round_up(nb[u], TILE) != round_up(nb[0], TILE))
+      return refuse(unit + "round_up(nb, 128) = " + std::to_string(round_up(nb[u], TILE)) + " differs from unit 0's " +
+                    std::to_string(round_up(nb[0], TILE)) + " (group the units by padded size)");
+    if (nrows > ctxs[u]->np_cap || round_up(nb[u], TILE) > ctxs[u]->np_cap)
+      return refuse(unit + "problem larger than the context capacity");
+  }
+  DeviceGuard device_guard(ctxs[0]->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int nu = n_units, npc = (int)round_up(nb[0], TILE);
+  const int64_t ld = npc;
+  ChainGroupT g{};
+  g.n_units = nu; g.n = (int)N; g.nrows = nrows; g.npc = npc; g.ld = ld;
+  CholBatchT<double> cb;
+  for (int u = 0; u < nu; ++u) {
+    gpfit_ctx* c = ctxs[u];
+    c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
+    g.nb.v[u] = (int)nb[u]; g.kmax = std::max(g.kmax, (int)nb[u]);
+    g.a.v[u] = a[u]; g.aL.v[u] = aL[u]; g.L.v[u] = L[u]; g.r.v[u] = r[u]; g.kv0.v[u] = kv0[u];
+    g.lda.v[u] = lda[u]; g.ldal.v[u] = ldal[u]; g.ldl.v[u] = ldl[u]; g.ldv.v[u] = ldv[u];
+    g.m.v[u] = m[u]; g.f.v[u] = f[u]; g.V.v[u] = V[u]; g.lam_m.v[u] = lam_m[u]; g.lam_var.v[u] = lam_var[u];
+    g.logA0.v[u] = logA0[u]; g.lambda0.v[u] = lambda0_mode ? lambda0_fixed[u] : 0.0;
+    g.blk.v[u] = c->chain; g.info.v[u] = c->info; g.rec_host.v[u] = c->chain_host;
+    // the work vectors and matrices of gpfit_estep_projected
+    g.sv.v[u] = c->yv; g.u.v[u] = c->bv; g.t2.v[u] = c->tvec; g.z1.v[u] = c->mpad; g.z.v[u] = c->rpad; g.mo.v[u] = c->hvec;
+    g.Y.v[u] = c->Tbuf; g.Lp.v[u] = c->Wbuf; g.Vw.v[u] = c->Zbuf; g.part.v[u] = c->TmpV; g.aLp.v[u] = c->LiVbuf;
+    g.Zm.v[u] = c->Cos; g.W.v[u] = c->Kbuf; g.Li.v[u] = c->Libuf; g.trmv_part.v[u] = c->trmv_part;
+    const int b = cb.nb++;
+    cb.A[b] = c->Kbuf; cb.L[b] = c->Lbuf; cb.Li[b] = c->Libuf; cb.Tmp[b] = c->Tmp; cb.info[b] = c->info + INFO_K;
+  }
+  cb.ld = ld;
+  const uint32_t all = (1u << nu) - 1u;
+  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
+  auto all_of = [&](double* gpfit_ctx::*X) { return mats(nu, ld, [&](int i) { return ctxs[i]->*X; }); };
+  const Mat<double> Y = all_of(&gpfit_ctx::Tbuf), W = all_of(&gpfit_ctx::Kbuf), Lp = all_of(&gpfit_ctx::Wbuf),
+                    Li = all_of(&gpfit_ctx::Libuf), P = all_of(&gpfit_ctx::Abuf), Vw = all_of(&gpfit_ctx::Zbuf),
+                    aLp = all_of(&gpfit_ctx::LiVbuf), Zm = all_of(&gpfit_ctx::Cos);
+  GP_TRY(launch_chain_init_group(g, n_steps, s));
+  // L does not change over the chain: packed once
+  GP_TRY(launch_pack_lower_group(nu, g.L, g.ldl, g.nb, g.Lp, ld, npc, s));
+  for (int step = 0; step < n_steps; ++step) {
+    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
+    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
+    GP_TRY(launch_estep_proj_rows_chain_group(g, step, s));
+    GP_TRY(launch_estep_proj_scale_group(g, s));
+    GP_TRY(launch_reduce_slices_group(nu, g.part, npc, nrows / 32, g.t2, npc, s));   // t2 = (a L)^T u
+    // W = I + Y^T Y  (= I + L^T G L, G = A^2 a^T diag(f) a), lower tiles, identity on the padding
+    GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(Y), plain(Y), into_lower(W)));
+    GP_TRY(launch_add_diag_group(nu, g.W, ld, npc, 1.0, s));
+    GP_TRY(potrf_lockstep(cb, 0, npc, all, lane));
+    GP_TRY(launch_chain_info_group(g, step, s));
+    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
+    // m_new = L W^-1 (a L)^T u
+    GP_TRY(launch_trmv_lower_group(nu, g.Li, ld, npc, g.t2, g.z1, s));
+    GP_TRY(launch_trmv_lower_t_group(nu, g.Li, ld, npc, g.z1, g.z, g.trmv_part, s));
+    GP_TRY(launch_trmv_lower_group(nu, g.Lp, ld, npc, g.z, g.mo, s));
+    // V_new = P P^T, P = L L_W^-T
+    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(Lp)), trans(tril(Li)), into(P)));
+    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(P), trans(P), into_lower(Vw)));
+    GP_TRY(launch_chain_copy_group(g, s));
+    GP_TRY(launch_unpack_sym_chain_group(g, s));
+    // the moments of lambda behind the update, from Z = aL L_W^-T
+    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(aLp), trans(tril(Li)), into(Zm)));
+    GP_TRY(launch_estep_proj_moments_chain_group(g, s));
+    GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
+  }
+  GP_TRY(launch_chain_collect_group(g, n_steps, s));
+  GP_HIP(hipStreamSynchronize(s));
+  for (int u = 0; u < nu; ++u)
+    for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[(size_t)u * n_steps * CHAIN_REC + i] = ctxs[u]->chain_host[i];
+  return 0;
+}
 
 int gpfit_estep_chain(gpfit_ctx* c, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
                       const double* L, int64_t ldl, int64_t N, int64_t nb, const double* r, const double* kv0, double* m,
                       double* f, double* V_out, int64_t ldv, double* lam_m, double* lam_var, double logA0,
                       int lambda0_mode, double lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                       double tol_grad, double tol_change, double* rec_host) {
-  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS) {
-    set_error("gpfit_estep_chain: n_steps " + std::to_string(n_steps) + " is not within 1 .. " +
-              std::to_string(CHAIN_MAX_STEPS));
-    return -3;
-  }
-  if (!c || !a || !aL || !L || !r || !kv0 || !m || !f || !V_out || !lam_m || !lam_var || !rec_host || N <= 0 || N > INT32_MAX ||
-      nb <= 0 || lda < nb || ldal < nb || ldl < nb || ldv < nb) {
-    set_error("gpfit_estep_chain: bad argument");
-    return -3;
-  }
-  Lbfgs1dConfig cfg;
-  GP_TRY(fparam_lbfgs_config("gpfit_estep_chain", max_iter, history_size, lr, tol_grad, tol_change, &cfg));
-  GP_CTX_ENTER(c, "gpfit_estep_chain");
-  hipStream_t s = (hipStream_t)stream;
-  const int n = (int)N, k = (int)nb;
-  const int nrows = (int)round_up(N, TILE), npc = (int)round_up(nb, TILE);
-  if (nrows > c->np_cap || npc > c->np_cap) {
-    set_error("gpfit_estep_chain: problem larger than the context capacity");
-    return -3;
-  }
-  const int64_t ld = npc;
-  // the work vectors and matrices of gpfit_estep_projected, product for product
-  double *sv = c->yv, *u = c->bv, *t2 = c->tvec, *z1 = c->mpad, *z = c->rpad, *mo = c->hvec;
-  double *Y = c->Tbuf, *Lp = c->Wbuf, *P = c->Abuf, *Vw = c->Zbuf, *part = c->TmpV, *aLp = c->LiVbuf, *Zm = c->Cos;
-  c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
-  const Lane lane = main_lane(c, s);
-  auto M = [&](double* X) { return mat(X, ld); };
-  ChainBlock* blk = c->chain;
-  const ChainGate gate{&blk->stop, c->info + INFO_K};
-  const size_t rec_bytes = (size_t)n_steps * CHAIN_REC * sizeof(double);
-  GP_HIP(hipMemsetAsync(&blk->rec[0][0], 0, rec_bytes, s));
-  GP_TRY(launch_chain_init(blk, logA0, lambda0_mode ? lambda0_fixed : 0.0, s));
-  // L does not change over the chain: packed once
-  GP_TRY(launch_pack_lower(L, ldl, k, Lp, ld, npc, s));
-  for (int step = 0; step < n_steps; ++step) {
-    double* rec = &blk->rec[step][0];
-    GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
-    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
-    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
-    GP_TRY(launch_estep_proj_rows_chain(a, lda, k, m, f, r, n, nrows, blk, rec, sv, u, s));
-    GP_TRY(launch_estep_proj_scale(aL, ldal, k, n, nrows, sv, u, Y, aLp, ld, npc, part, s));
-    GP_TRY((launch_reduce_slices<double, double>(part, npc, nrows / 32, t2, npc, s)));   // t2 = (a L)^T u
-    GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(M(Y)), plain(M(Y)), into_lower(M(c->Kbuf))));
-    GP_TRY(launch_add_diag(c->Kbuf, ld, npc, 1.0, s));
-    GP_TRY(potrf_lockstep(one_chain(c, ld), 0, npc, 1u, lane));
-    GP_TRY(launch_chain_info(blk, c->info + INFO_K, rec, s));
-    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
-    GP_TRY(launch_trmv_lower(c->Libuf, ld, npc, t2, z1, s));
-    GP_TRY(launch_trmv_lower_t(c->Libuf, ld, npc, z1, z, c->trmv_part, s));
-    GP_TRY(launch_trmv_lower(Lp, ld, npc, z, mo, s));
-    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(M(Lp))), trans(tril(M(c->Libuf))), into(M(P))));
-    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(M(P)), trans(M(P)), into_lower(M(Vw))));
-    GP_TRY(launch_chain_copy(gate, mo, k, m, s));
-    GP_TRY(launch_unpack_sym_chain(gate, Vw, ld, k, V_out, ldv, s));
-    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(M(aLp)), trans(tril(M(c->Libuf))), into(M(Zm))));
-    GP_TRY(launch_estep_proj_moments_chain(gate, Zm, ld, k, z1, kv0, n, lam_m, lam_var, s));
-    GP_TRY(launch_fparam_lbfgs_chain(gate, lam_m, lam_var, r, n, lambda0_mode ? 1 : 0, lambda0_fixed, cfg, f, blk, rec, s));
-  }
-  GP_HIP(hipMemcpyAsync(c->chain_host, &blk->rec[0][0], rec_bytes, hipMemcpyDeviceToHost, s));
-  GP_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[i] = c->chain_host[i];
-  return 0;
+  // the group of one (estep_chain_group_impl): a unit's numbers are the same alone and in any group
+  return estep_chain_group_impl("gpfit_estep_chain", &c, 1, stream, &a, &lda, &aL, &ldal, &L, &ldl, N, &nb, &r, &kv0, &m, &f,
+                                &V_out, &ldv, &lam_m, &lam_var, &logA0, lambda0_mode, &lambda0_fixed, n_steps, max_iter,
+                                history_size, lr, tol_grad, tol_change, rec_host);
 }
 
+int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a, const int64_t* lda,
+                            const double* const* aL, const int64_t* ldal, const double* const* L, const int64_t* ldl,
+                            int64_t N, const int64_t* nb, const double* const* r, const double* const* kv0,
+                            double* const* m, double* const* f, double* const* V, const int64_t* ldv,
+                            double* const* lam_m, double* const* lam_var, const double* logA0, int lambda0_mode,
+                            const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                            double tol_grad, double tol_change, double* rec_host) {
+  return estep_chain_group_impl("gpfit_estep_chain_batch", ctxs, n_units, stream, a, lda, aL, ldal, L, ldl, N, nb, r, kv0, m, f,
+                                V, ldv, lam_m, lam_var, logA0, lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr,
+                                tol_grad, tol_change, rec_host);
+}
+
+// The full-rank chain: the update of gpfit_estep (full_update_factor / full_update_products) in place of the projected
+// one, on the bookkeeping of the projected chain -- a ChainGroupT of one unit with nb = n, so that the init, the info
+// word, the gated commits of m and V, the optimiser and the collect are the launches of estep_chain_group_impl.
 int gpfit_estep_chain_full(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_t N, const double* r,
                            const double* kv0, double* m, double* f, double* V_out, int64_t ldv, double* lam_m,
                            double* lam_var, double logA0, int lambda0_mode, double lambda0_fixed, int n_steps,
@@ -445,148 +529,37 @@ int gpfit_estep_chain_full(gpfit_ctx* c, void* stream, const double* K, int64_t 
     return -3;
   }
   const int64_t ld = np;
-  // the work vectors and matrices of gpfit_estep, product for product
+  // the work vectors and matrices of gpfit_estep
   double *sv = c->yv, *rhs = c->bv, *mo = c->tvec, *Vw = c->Wbuf;
-  const CholBatchT<double> b = one_chain(c, ld);
   const Lane lane = main_lane(c, s);
-  auto at = [&](double* X, int r, int col) { return mat(X + (int64_t)r * ld + col, ld); };
-  ChainBlock* blk = c->chain;
-  const ChainGate gate{&blk->stop, c->info + INFO_K};
-  const size_t rec_bytes = (size_t)n_steps * CHAIN_REC * sizeof(double);
-  GP_HIP(hipMemsetAsync(&blk->rec[0][0], 0, rec_bytes, s));
-  GP_TRY(launch_chain_init(blk, logA0, lambda0_mode ? lambda0_fixed : 0.0, s));
+  ChainGroupT g{};
+  g.n_units = 1; g.n = n; g.ld = ld;
+  g.nb.v[0] = n; g.kmax = n;
+  g.r.v[0] = r; g.m.v[0] = m; g.f.v[0] = f; g.V.v[0] = V_out; g.ldv.v[0] = ldv; g.lam_m.v[0] = lam_m; g.lam_var.v[0] = lam_var;
+  g.logA0.v[0] = logA0; g.lambda0.v[0] = lambda0_mode ? lambda0_fixed : 0.0;
+  g.blk.v[0] = c->chain; g.info.v[0] = c->info; g.rec_host.v[0] = c->chain_host;
+  g.mo.v[0] = mo; g.Vw.v[0] = Vw;
+  const ChainGate gate{&c->chain->stop, c->info + INFO_K};
+  GP_TRY(launch_chain_init_group(g, n_steps, s));
   for (int step = 0; step < n_steps; ++step) {
-    double* rec = &blk->rec[step][0];
-    GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
     // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
     // step's writers (the gated copy into m, the optimiser's rate), all on one stream
-    GP_TRY(launch_estep_prep_chain(f, r, m, n, np, blk, rec, sv, rhs, s));
+    GP_TRY(launch_estep_prep_chain(f, r, m, n, np, c->chain, step, c->info, sv, rhs, s));
     // M = I + S K S (lower), SK = S K (dense), Kl = K (lower): Kl is overwritten by V, so it is rebuilt every step
     GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, Vw, ld, s));
-    if (np >= 2 * TILE) {
-      const int kt = np / TILE;
-      const int n1 = ((kt + 1) / 2) * TILE, n2 = np - n1;
-      GP_TRY(potrf_lockstep(b, 0, np, 0u, lane, 1u));   // [L^-1]11 and [L^-1]22 only
-      GP_TRY(launch_chain_info(blk, c->info + INFO_K, rec, s));
-      GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
-      GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(c->Lbuf, n1, 0)), plain(at(c->Abuf, 0, 0)), into(at(c->Zbuf, n1, 0), 1.0)));
-      GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(c->Libuf, n1, n1))), plain(at(c->Zbuf, n1, 0)), into(at(c->Abuf, n1, 0)), 1));
-    } else {
-      GP_TRY(potrf_lockstep(b, 0, np, 1u, lane));
-      GP_TRY(launch_chain_info(blk, c->info + INFO_K, rec, s));
-      GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
-    }
-    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
-    GP_TRY(product(lane, {np, np, np}, -1.0, trans(at(c->Abuf, 0, 0)), plain(at(c->Abuf, 0, 0)), into_lower(at(Vw, 0, 0), 1.0)));
-    GP_TRY(launch_symv_lower(Vw, ld, n, rhs, mo, s));
-    GP_TRY(launch_chain_copy(gate, mo, n, m, s));
-    GP_TRY(launch_unpack_sym_chain(gate, Vw, ld, n, V_out, ldv, s));
-    GP_TRY(launch_estep_full_moments_chain(gate, mo, Vw, ld, kv0, n, lam_m, lam_var, s));
-    GP_TRY(launch_fparam_lbfgs_chain(gate, lam_m, lam_var, r, n, lambda0_mode ? 1 : 0, lambda0_fixed, cfg, f, blk, rec, s));
-  }
-  GP_HIP(hipMemcpyAsync(c->chain_host, &blk->rec[0][0], rec_bytes, hipMemcpyDeviceToHost, s));
-  GP_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[i] = c->chain_host[i];
-  return 0;
-}
-
-static_assert(GPFIT_ESTEP_CHAIN_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
-
-int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a, const int64_t* lda,
-                            const double* const* aL, const int64_t* ldal, const double* const* L, const int64_t* ldl,
-                            int64_t N, const int64_t* nb, const double* const* r, const double* const* kv0,
-                            double* const* m, double* const* f, double* const* V, const int64_t* ldv,
-                            double* const* lam_m, double* const* lam_var, const double* logA0, int lambda0_mode,
-                            const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
-                            double tol_grad, double tol_change, double* rec_host) {
-  const char* name = "gpfit_estep_chain_batch";
-  auto refuse = [&](const std::string& why) {
-    set_error(std::string(name) + ": " + why);
-    return -3;
-  };
-  if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
-  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS)
-    return refuse("n_steps " + std::to_string(n_steps) + " is not within 1 .. " + std::to_string(CHAIN_MAX_STEPS));
-  if (!ctxs || !a || !lda || !aL || !ldal || !L || !ldl || !nb || !r || !kv0 || !m || !f || !V || !ldv || !lam_m || !lam_var ||
-      !logA0 || (lambda0_mode && !lambda0_fixed) || !rec_host || N <= 0 || N > INT32_MAX)
-    return refuse("bad argument");
-  Lbfgs1dConfig cfg;
-  GP_TRY(fparam_lbfgs_config(name, max_iter, history_size, lr, tol_grad, tol_change, &cfg));
-  const int nrows = (int)round_up(N, TILE);
-  for (int u = 0; u < n_units; ++u) {
-    const std::string unit = "unit " + std::to_string(u) + ": ";
-    if (!ctxs[u] || !a[u] || !aL[u] || !L[u] || !r[u] || !kv0[u] || !m[u] || !f[u] || !V[u] || !lam_m[u] || !lam_var[u])
-      return refuse(unit + "null context or operand");
-    if (nb[u] <= 0 || lda[u] < nb[u] || ldal[u] < nb[u] || ldl[u] < nb[u] || ldv[u] < nb[u])
-      return refuse(unit + "bad size or leading dimension");
-    if (ctxs[u]->device != ctxs[0]->device) return refuse("the contexts of one call must live on one device");
-    for (int v = 0; v < u; ++v)
-      if (ctxs[v] == ctxs[u]) return refuse("every unit needs a context of its own");
-    if (ctxs[u]->pend.active) return refuse("an asynchronous evaluation is pending on one of the contexts");
-    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
-    if (round_up(nb[u], TILE) != round_up(nb[0], TILE))
-      return refuse(unit + "round_up(nb, 128) = " + std::to_string(round_up(nb[u], TILE)) + " differs from unit 0's " +
-                    std::to_string(round_up(nb[0], TILE)) + " (group the units by padded size)");
-    if (nrows > ctxs[u]->np_cap || round_up(nb[u], TILE) > ctxs[u]->np_cap)
-      return refuse(unit + "problem larger than the context capacity");
-  }
-  DeviceGuard device_guard(ctxs[0]->device);
-  hipStream_t s = (hipStream_t)stream;
-  const int nu = n_units, npc = (int)round_up(nb[0], TILE);
-  const int64_t ld = npc;
-  ChainGroupT g{};
-  g.n_units = nu; g.n = (int)N; g.nrows = nrows; g.npc = npc; g.ld = ld;
-  CholBatchT<double> cb;
-  for (int u = 0; u < nu; ++u) {
-    gpfit_ctx* c = ctxs[u];
-    c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
-    g.nb.v[u] = (int)nb[u]; g.kmax = std::max(g.kmax, (int)nb[u]);
-    g.a.v[u] = a[u]; g.aL.v[u] = aL[u]; g.L.v[u] = L[u]; g.r.v[u] = r[u]; g.kv0.v[u] = kv0[u];
-    g.lda.v[u] = lda[u]; g.ldal.v[u] = ldal[u]; g.ldl.v[u] = ldl[u]; g.ldv.v[u] = ldv[u];
-    g.m.v[u] = m[u]; g.f.v[u] = f[u]; g.V.v[u] = V[u]; g.lam_m.v[u] = lam_m[u]; g.lam_var.v[u] = lam_var[u];
-    g.logA0.v[u] = logA0[u]; g.lambda0.v[u] = lambda0_mode ? lambda0_fixed[u] : 0.0;
-    g.blk.v[u] = c->chain; g.info.v[u] = c->info; g.rec_host.v[u] = c->chain_host;
-    // the work vectors and matrices of gpfit_estep_chain
-    g.sv.v[u] = c->yv; g.u.v[u] = c->bv; g.t2.v[u] = c->tvec; g.z1.v[u] = c->mpad; g.z.v[u] = c->rpad; g.mo.v[u] = c->hvec;
-    g.Y.v[u] = c->Tbuf; g.Lp.v[u] = c->Wbuf; g.Vw.v[u] = c->Zbuf; g.part.v[u] = c->TmpV; g.aLp.v[u] = c->LiVbuf;
-    g.Zm.v[u] = c->Cos; g.W.v[u] = c->Kbuf; g.Li.v[u] = c->Libuf; g.trmv_part.v[u] = c->trmv_part;
-    const int b = cb.nb++;
-    cb.A[b] = c->Kbuf; cb.L[b] = c->Lbuf; cb.Li[b] = c->Libuf; cb.Tmp[b] = c->Tmp; cb.info[b] = c->info + INFO_K;
-  }
-  cb.ld = ld;
-  const uint32_t all = (1u << nu) - 1u;
-  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
-  auto all_of = [&](double* gpfit_ctx::*X) { return mats(nu, ld, [&](int i) { return ctxs[i]->*X; }); };
-  const Mat<double> Y = all_of(&gpfit_ctx::Tbuf), W = all_of(&gpfit_ctx::Kbuf), Lp = all_of(&gpfit_ctx::Wbuf),
-                    Li = all_of(&gpfit_ctx::Libuf), P = all_of(&gpfit_ctx::Abuf), Vw = all_of(&gpfit_ctx::Zbuf),
-                    aLp = all_of(&gpfit_ctx::LiVbuf), Zm = all_of(&gpfit_ctx::Cos);
-  GP_TRY(launch_chain_init_group(g, n_steps, s));
-  // L does not change over the chain: packed once
-  GP_TRY(launch_pack_lower_group(nu, g.L, g.ldl, g.nb, g.Lp, ld, npc, s));
-  // gpfit_estep_chain, product for product
-  for (int step = 0; step < n_steps; ++step) {
-    GP_TRY(launch_estep_proj_rows_chain_group(g, step, s));
-    GP_TRY(launch_estep_proj_scale_group(g, s));
-    GP_TRY(launch_reduce_slices_group(nu, g.part, npc, nrows / 32, g.t2, npc, s));   // t2 = (a L)^T u
-    GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(Y), plain(Y), into_lower(W)));
-    GP_TRY(launch_add_diag_group(nu, g.W, ld, npc, 1.0, s));
-    GP_TRY(potrf_lockstep(cb, 0, npc, all, lane));
+    GP_TRY(full_update_factor(c, np, lane));
     GP_TRY(launch_chain_info_group(g, step, s));
-    GP_TRY(launch_trmv_lower_group(nu, g.Li, ld, npc, g.t2, g.z1, s));
-    GP_TRY(launch_trmv_lower_t_group(nu, g.Li, ld, npc, g.z1, g.z, g.trmv_part, s));
-    GP_TRY(launch_trmv_lower_group(nu, g.Lp, ld, npc, g.z, g.mo, s));
-    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(Lp)), trans(tril(Li)), into(P)));
-    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(P), trans(P), into_lower(Vw)));
+    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
+    GP_TRY(full_update_products(c, np, lane));
+    GP_TRY(launch_symv_lower(Vw, ld, n, rhs, mo, s));
     GP_TRY(launch_chain_copy_group(g, s));
     GP_TRY(launch_unpack_sym_chain_group(g, s));
-    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(aLp), trans(tril(Li)), into(Zm)));
-    GP_TRY(launch_estep_proj_moments_chain_group(g, s));
+    GP_TRY(launch_estep_full_moments_chain(gate, mo, Vw, ld, kv0, n, lam_m, lam_var, s));
     GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
   }
   GP_TRY(launch_chain_collect_group(g, n_steps, s));
   GP_HIP(hipStreamSynchronize(s));
-  for (int u = 0; u < nu; ++u)
-    for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[(size_t)u * n_steps * CHAIN_REC + i] = ctxs[u]->chain_host[i];
+  for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[i] = c->chain_host[i];
   return 0;
 }
 

@@ -1295,13 +1295,14 @@ __global__ void estep_prep_kernel(const double* __restrict__ f, const double* __
                                   double* __restrict__ rhs) {
   estep_prep_body(f, r, m, n, np, A, sv, rhs);
 }
-// A step of gpfit_estep_chain_full: A = exp(logA) of the chain block, recorded for the caller while the chain runs
+// A step of gpfit_estep_chain_full: A = exp(logA) of the chain block, recorded for the caller while the chain runs; the
+// context's four info words are zeroed here, by the first kernel of the step (as estep_proj_rows_chain_group_kernel does)
 __global__ void estep_prep_chain_kernel(const double* __restrict__ f, const double* __restrict__ r,
-                                        const double* __restrict__ m, int n, int np,
-                                        const ChainBlock* __restrict__ blk, double* __restrict__ rec,
-                                        double* __restrict__ sv, double* __restrict__ rhs) {
+                                        const double* __restrict__ m, int n, int np, ChainBlock* __restrict__ blk, int step,
+                                        int* __restrict__ info, double* __restrict__ sv, double* __restrict__ rhs) {
   const double A = exp(blk->logA);
-  if (blockIdx.x == 0 && threadIdx.x == 0 && blk->stop == 0) rec[CR_A] = A;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && blk->stop == 0) blk->rec[step][CR_A] = A;
+  if (blockIdx.x == 0 && threadIdx.x < 4) info[threadIdx.x] = 0;
   estep_prep_body(f, r, m, n, np, A, sv, rhs);
 }
 
@@ -1311,9 +1312,9 @@ int launch_estep_prep(const double* f, const double* r, const double* m, int n, 
   GP_HIP(hipGetLastError());
   return 0;
 }
-int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, const ChainBlock* blk,
-                            double* rec, double* sv, double* rhs, hipStream_t s) {
-  hipLaunchKernelGGL(estep_prep_chain_kernel, dim3((np + 255) / 256), dim3(256), 0, s, f, r, m, n, np, blk, rec, sv, rhs);
+int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, ChainBlock* blk, int step,
+                            int* info, double* sv, double* rhs, hipStream_t s) {
+  hipLaunchKernelGGL(estep_prep_chain_kernel, dim3((np + 255) / 256), dim3(256), 0, s, f, r, m, n, np, blk, step, info, sv, rhs);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -1393,52 +1394,7 @@ int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_
   return 0;
 }
 
-// ---- the small kernels of a chained E-step (gpfit_estep_chain; kernels.h: ChainBlock, ChainGate)
-__global__ void chain_init_kernel(ChainBlock* __restrict__ blk, double logA0, double lambda0) {
-  blk->logA = logA0;
-  blk->lambda0 = lambda0;
-  blk->stop = 0;
-}
-int launch_chain_init(ChainBlock* blk, double logA0, double lambda0, hipStream_t s) {
-  hipLaunchKernelGGL(chain_init_kernel, dim3(1), dim3(1), 0, s, blk, logA0, lambda0);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-__global__ void chain_info_kernel(ChainBlock* __restrict__ blk, const int* __restrict__ info, double* __restrict__ rec) {
-  if (blk->stop != 0) return;   // a skipped step: its factorisation ran on workspace only, its record stays zero
-  const int v = *info;
-  rec[CR_INFO] = v;
-  if (v != 0) blk->stop = 1;
-}
-int launch_chain_info(ChainBlock* blk, const int* info, double* rec, hipStream_t s) {
-  hipLaunchKernelGGL(chain_info_kernel, dim3(1), dim3(1), 0, s, blk, info, rec);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-__global__ void chain_copy_kernel(ChainGate g, const double* __restrict__ src, int n, double* __restrict__ dst) {
-  if (!g.open()) return;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[i];
-}
-int launch_chain_copy(ChainGate g, const double* src, int n, double* dst, hipStream_t s) {
-  hipLaunchKernelGGL(chain_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g, src, n, dst);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-// unpack_sym_kernel behind the gate
-__global__ void unpack_sym_chain_kernel(ChainGate g, const double* __restrict__ src, int64_t lds, int n,
-                                        double* __restrict__ dst, int64_t ldd) {
-  if (!g.open()) return;
-  const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-  if (i >= n || j >= n) return;
-  dst[(int64_t)i * ldd + j] = (j <= i) ? src[(int64_t)i * lds + j] : src[(int64_t)j * lds + i];
-}
-int launch_unpack_sym_chain(ChainGate g, const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s) {
-  hipLaunchKernelGGL(unpack_sym_chain_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, g, src, lds, n, dst, ldd);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-
+// ---- the small kernels of a chained E-step (kernels.h: ChainBlock, ChainGate, ChainGroupT)
 // the full-rank moments behind a committed update (gpfit_estep_chain_full; a = B = I): lam_m = m_new and
 // lam_var = (Kvec - diag K~) + diag V, the diagonal read from the lower-tile work matrix the update left
 __global__ void estep_full_moments_chain_kernel(ChainGate g, const double* __restrict__ m_new,
@@ -1459,8 +1415,8 @@ int launch_estep_full_moments_chain(ChainGate g, const double* m_new, const doub
   return 0;
 }
 
-// ---- the same for a group of chains (gpfit_estep_chain_batch; kernels.h: ChainGroupT): unit u = the free grid
-// dimension, its own block and info word behind every gate
+// the bookkeeping and the gated commits of a step for a group of chains (the single call is the group of one): unit u =
+// the free grid dimension, its own block and info word behind every gate
 __global__ __launch_bounds__(256) void chain_init_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<double> logA0,
                                                                PerUnit<double> lambda0, int n_rec) {
   const int u = blockIdx.x;
@@ -1480,7 +1436,7 @@ int launch_chain_init_group(const ChainGroupT& g, int n_steps, hipStream_t s) {
 }
 __global__ void chain_info_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info, int step) {
   ChainBlock* b = blk[blockIdx.x];
-  if (b->stop != 0) return;
+  if (b->stop != 0) return;   // a skipped step: its factorisation ran on workspace only, its record stays zero
   const int v = info[blockIdx.x][0];
   b->rec[step][CR_INFO] = v;
   if (v != 0) b->stop = 1;
@@ -1730,7 +1686,7 @@ __global__ __launch_bounds__(1024) void fparam_lbfgs_kernel(const double* __rest
   const FparamLbfgsRun o = fparam_lbfgs_run(lam_m, lam_var, r, n, logA0, lambda0_mode, lambda0_fixed, cfg, f, sh, hist);
   if (threadIdx.x == 0) fparam_lbfgs_store(o, out);
 }
-// The optimiser of a chained step (gpfit_estep_chain): behind the gate, from the logA the block holds.  rec[0..8]: the
+// The optimiser of a chained step: behind the gate, from the logA the block holds.  rec[0..8]: the
 // nine results, rec[CR_RAN] = 1.  Status 0 leaves (logA, lambda0) in the block for the next step (and the rate in f);
 // a failing closure call sets the stop word instead.
 __device__ __forceinline__ void fparam_lbfgs_chain_body(ChainGate g, const double* __restrict__ lam_m,
@@ -1753,17 +1709,7 @@ __device__ __forceinline__ void fparam_lbfgs_chain_body(ChainGate g, const doubl
     }
   }
 }
-__global__ __launch_bounds__(1024) void fparam_lbfgs_chain_kernel(ChainGate g, const double* __restrict__ lam_m,
-                                                                  const double* __restrict__ lam_var,
-                                                                  const double* __restrict__ r, int n, int lambda0_mode,
-                                                                  double lambda0_fixed, Lbfgs1dConfig cfg,
-                                                                  double* __restrict__ f, ChainBlock* blk,
-                                                                  double* __restrict__ rec) {
-  __shared__ double sh[17];
-  extern __shared__ double hist[];
-  fparam_lbfgs_chain_body(g, lam_m, lam_var, r, n, lambda0_mode, lambda0_fixed, cfg, f, blk, rec, sh, hist);
-}
-// one workgroup per unit of a group (gpfit_estep_chain_batch): each behind its own gate, from its own block
+// one workgroup per unit of a group: each behind its own gate, from its own block
 __global__ __launch_bounds__(1024) void fparam_lbfgs_chain_group_kernel(PerUnit<ChainBlock*> blks, PerUnit<int*> info,
                                                                         PerUnit<double*> lam_m, PerUnit<double*> lam_var,
                                                                         PerUnit<const double*> r, int n, int lambda0_mode,
@@ -1786,16 +1732,6 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
   GP_HIP(hipGetLastError());
   return 0;
 }
-int launch_fparam_lbfgs_chain(ChainGate g, const double* lam_m, const double* lam_var, const double* r, int n,
-                              int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f,
-                              ChainBlock* blk, double* rec, hipStream_t s) {
-  const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
-  hipLaunchKernelGGL(fparam_lbfgs_chain_kernel, dim3(1), dim3(1024), lds, s, g, lam_m, lam_var, r, n, lambda0_mode,
-                     lambda0_fixed, cfg, f, blk, rec);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-
 int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s) {
   const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
   hipLaunchKernelGGL(fparam_lbfgs_chain_group_kernel, dim3(g.n_units), dim3(1024), lds, s, g.blk, g.info, g.lam_m, g.lam_var,

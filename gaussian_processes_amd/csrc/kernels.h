@@ -210,9 +210,14 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
                         int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f, double* out,
                         hipStream_t s);
 
-// ---- chained E-steps (gpfit_estep_chain): nEstep x (Newton update, moments, rate-parameter L-BFGS) enqueued in one go.
-// What a step hands to the next stays on the device in a ChainBlock; no kernel waits on another, every launch that
-// makes a step visible to the caller tests the gate first.
+// ---- chained E-steps (gpfit_estep_chain, gpfit_estep_chain_batch, gpfit_estep_chain_full): nEstep x (Newton update,
+// moments, rate-parameter L-BFGS) enqueued in one go.  What a step hands to the next stays on the device in a ChainBlock;
+// no kernel waits on another, every launch that makes a step visible to the caller tests the gate first.
+// ONE family of kernels for one chain and for the chains of several independent units in lock step: the single call is
+// the group of one.  Every small kernel of a step is one launch for the group, with the unit on a free grid dimension and
+// a per-unit table passed by value (as GroupPrepT); a unit's sums run over the same block and thread indices in the same
+// order whatever else is in the group, hence the same bits alone and in any group.  Each unit has its own ChainBlock and
+// info word, so its gate is its own.
 constexpr int CHAIN_MAX_STEPS = 1024;   // GPFIT_ESTEP_CHAIN_MAX_STEPS of the public header
 constexpr int CHAIN_REC = 12;           // doubles per step record
 enum ChainRecSlot {
@@ -227,44 +232,13 @@ struct ChainBlock {
   int stop, pad;          // non-zero once a step has failed: nothing is committed from then on
   double rec[CHAIN_MAX_STEPS][CHAIN_REC];
 };
-// Open while no earlier step has failed and this step's factorisation has not (block-uniform: two scalar loads).
+// Open while no earlier step has failed and this step's factorisation has not (block-uniform: two scalar loads).  The
+// gated kernels build it from their unit's entries of the tables.
 struct ChainGate {
   const int* stop;
   const int* info;
   __device__ __forceinline__ bool open() const { return *stop == 0 && *info == 0; }
 };
-// block <- (logA0, lambda0, stop = 0); the records are zeroed by the caller
-int launch_chain_init(ChainBlock* blk, double logA0, double lambda0, hipStream_t s);
-// launch_estep_proj_rows with A = exp(blk->logA) formed on the device (the same row body: equal A, equal bits);
-// rec[CR_A] <- A unless the chain has stopped
-int launch_estep_proj_rows_chain(const double* a, int64_t lda, int nb, const double* mb, const double* f, const double* r,
-                                 int n, int nrows, const ChainBlock* blk, double* rec, double* sv, double* u,
-                                 hipStream_t s);
-// behind the factorisation (one thread): rec[CR_INFO] <- *info, and the stop word is set when it is non-zero
-int launch_chain_info(ChainBlock* blk, const int* info, double* rec, hipStream_t s);
-// the commits of a step, each behind the gate: dst <- src, launch_unpack_sym, launch_estep_proj_moments
-int launch_chain_copy(ChainGate g, const double* src, int n, double* dst, hipStream_t s);
-int launch_unpack_sym_chain(ChainGate g, const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
-int launch_estep_proj_moments_chain(ChainGate g, const double* Z, int64_t ld, int nb, const double* z1, const double* kv0,
-                                    int n, double* lam_m, double* lam_var, hipStream_t s);
-// the full-rank chain (gpfit_estep_chain_full): launch_estep_prep with A = exp(blk->logA) formed on the device (the same
-// body: equal A, equal bits), rec[CR_A] <- A unless the chain has stopped; and, behind the gate, the moments of the
-// original basis, lam_m <- m_new, lam_var <- kv0 + diag(Vw) (Vw: the lower-tile work matrix holding V)
-int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, const ChainBlock* blk,
-                            double* rec, double* sv, double* rhs, hipStream_t s);
-int launch_estep_full_moments_chain(ChainGate g, const double* m_new, const double* Vw, int64_t ld, const double* kv0,
-                                    int n, double* lam_m, double* lam_var, hipStream_t s);
-// launch_fparam_lbfgs behind the gate, started at blk->logA: rec[0..8] <- its results and rec[CR_RAN] <- 1; with status 0
-// it leaves (logA, lambda0) in the block and the rate in f, otherwise it sets the stop word
-int launch_fparam_lbfgs_chain(ChainGate g, const double* lam_m, const double* lam_var, const double* r, int n,
-                              int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f,
-                              ChainBlock* blk, double* rec, hipStream_t s);
-
-// ---- the chains of several independent units in lock step (gpfit_estep_chain_batch): every small kernel of a step
-// is ONE launch for the group, with the unit on a grid dimension the single form leaves free and a per-unit table
-// passed by value (as GroupPrepT).  Each unit runs the body of its single form over the same block and thread indices:
-// the same sums in the same order, hence the same bits as gpfit_estep_chain on that unit alone.  Each unit has its own
-// ChainBlock and info word, so its gate is its own.
 constexpr int CHAIN_MAXU = GEMM_MAXB / 2;   // units per call: one factorisation chain each, half a pointer batch like GroupPrepT
 template <typename T>
 struct PerUnit {
@@ -272,6 +246,7 @@ struct PerUnit {
   __host__ __device__ __forceinline__ T operator[](int u) const { return v[u]; }
 };
 // The group as the host describes it once per call; every launcher hands its kernel the tables that kernel reads.
+// (gpfit_estep_chain_full fills what the bookkeeping and the commits read, for one unit with nb = n.)
 struct ChainGroupT {
   int n_units, n, nrows, npc, kmax;   // shared: training points, their padding, the padded basis size; the largest nb
   int64_t ld;                         // leading dimension of the work matrices (= npc)
@@ -283,21 +258,35 @@ struct ChainGroupT {
   PerUnit<ChainBlock*> blk;
   PerUnit<int*> info;                 // the context's four info words; word INFO_K (0) is the chain's
   PerUnit<double*> rec_host;          // the context's pinned, device-visible chain_host
-  // the work vectors and matrices of gpfit_estep_chain, per context
+  // the work vectors and matrices of gpfit_estep_projected, per context
   PerUnit<double*> sv, u, t2, z1, z, mo, Y, Lp, Vw, part, aLp, Zm, W, Li, trmv_part;
 };
 // block <- (logA0, lambda0, stop = 0) and the first n_steps records zeroed
 int launch_chain_init_group(const ChainGroupT& g, int n_steps, hipStream_t s);
-// the four info words zeroed, then launch_estep_proj_rows_chain on the record of `step`
+// launch_estep_proj_rows with A = exp(blk->logA) formed on the device (the same row body: equal A, equal bits) on m, f;
+// rec[step][CR_A] <- A unless the chain has stopped; the four info words zeroed (the first kernel of a step)
 int launch_estep_proj_rows_chain_group(const ChainGroupT& g, int step, hipStream_t s);
 int launch_estep_proj_scale_group(const ChainGroupT& g, hipStream_t s);
+// behind the factorisation (one thread per unit): rec[step][CR_INFO] <- the info word, and the stop word is set when it
+// is non-zero
 int launch_chain_info_group(const ChainGroupT& g, int step, hipStream_t s);
-int launch_chain_copy_group(const ChainGroupT& g, hipStream_t s);           // m <- mo
-int launch_unpack_sym_chain_group(const ChainGroupT& g, hipStream_t s);     // V <- Vw
+// the commits of a step, each behind the gate: m <- mo, V <- Vw (launch_unpack_sym), launch_estep_proj_moments
+int launch_chain_copy_group(const ChainGroupT& g, hipStream_t s);
+int launch_unpack_sym_chain_group(const ChainGroupT& g, hipStream_t s);
 int launch_estep_proj_moments_chain_group(const ChainGroupT& g, hipStream_t s);
+// launch_fparam_lbfgs behind the gate, started at blk->logA: rec[step][0..8] <- its results and rec[step][CR_RAN] <- 1;
+// with status 0 it leaves (logA, lambda0) in the block and the rate in f, otherwise it sets the stop word
 int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s);
 // the first n_steps records of every unit into its rec_host (one launch instead of a copy command per unit)
 int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s);
+// the two kernels of the full-rank step only (gpfit_estep_chain_full, one unit): launch_estep_prep with A =
+// exp(blk->logA) formed on the device (the same body: equal A, equal bits), rec[step][CR_A] <- A unless the chain has
+// stopped, the four info words zeroed; and, behind the gate, the moments of the original basis, lam_m <- m_new,
+// lam_var <- kv0 + diag(Vw) (Vw: the lower-tile work matrix holding V)
+int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, ChainBlock* blk, int step,
+                            int* info, double* sv, double* rhs, hipStream_t s);
+int launch_estep_full_moments_chain(ChainGate g, const double* m_new, const double* Vw, int64_t ld, const double* kv0,
+                                    int n, double* lam_m, double* lam_var, hipStream_t s);
 // the unit-batched forms of the general kernels a step uses (common sizes and leading dimensions unless per unit)
 int launch_pack_lower_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
                             int64_t ldd, int np, hipStream_t s);

@@ -285,21 +285,9 @@ __global__ __launch_bounds__(256) void estep_proj_rows_kernel(const double* __re
                                                                double* __restrict__ sv, double* __restrict__ u) {
   estep_proj_rows_body(a, lda, nb, mb, f, r, n, nrows, A, sv, u);
 }
-// A step of gpfit_estep_chain: A = exp(logA) of the chain block, recorded for the caller while the chain runs
-__global__ __launch_bounds__(256) void estep_proj_rows_chain_kernel(const double* __restrict__ a, int64_t lda, int nb,
-                                                                     const double* __restrict__ mb,
-                                                                     const double* __restrict__ f,
-                                                                     const double* __restrict__ r, int n, int nrows,
-                                                                     const ChainBlock* __restrict__ blk,
-                                                                     double* __restrict__ rec, double* __restrict__ sv,
-                                                                     double* __restrict__ u) {
-  const double A = exp(blk->logA);
-  if (blockIdx.x == 0 && threadIdx.x == 0 && blk->stop == 0) rec[CR_A] = A;
-  estep_proj_rows_body(a, lda, nb, mb, f, r, n, nrows, A, sv, u);
-}
-
-// the same for every unit of a group (gpfit_estep_chain_batch): unit = blockIdx.y; the unit's four info words are zeroed
-// here, by the first kernel of the step
+// A step of the chained E-steps (the single call is the group of one), for every unit of the group: unit = blockIdx.y;
+// A = exp(logA) of the unit's chain block, recorded for the caller while the chain runs; the unit's four info words are
+// zeroed here, by the first kernel of the step
 __global__ __launch_bounds__(256) void estep_proj_rows_chain_group_kernel(PerUnit<const double*> a, PerUnit<int64_t> lda,
                                                                            PerUnit<int> nb, PerUnit<double*> mb,
                                                                            PerUnit<double*> f, PerUnit<const double*> r,
@@ -356,14 +344,6 @@ int launch_estep_proj_rows(const double* a, int64_t lda, int nb, const double* m
   GP_HIP(hipGetLastError());
   return 0;
 }
-int launch_estep_proj_rows_chain(const double* a, int64_t lda, int nb, const double* mb, const double* f, const double* r,
-                                 int n, int nrows, const ChainBlock* blk, double* rec, double* sv, double* u,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL(estep_proj_rows_chain_kernel, dim3((nrows + 3) / 4), dim3(256), 0, s, a, lda, nb, mb, f, r, n,
-                     nrows, blk, rec, sv, u);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
 int launch_estep_proj_scale(const double* aL, int64_t ldal, int nb, int n, int nrows, const double* sv, const double* u,
                             double* Y, double* aLp, int64_t ld, int npc, double* part, hipStream_t s) {
   hipLaunchKernelGGL(estep_proj_scale_kernel, dim3((npc + 255) / 256, nrows / 32), dim3(256), 0, s, aL, ldal, nb, n, sv,
@@ -402,31 +382,14 @@ __global__ __launch_bounds__(256) void estep_proj_moments_kernel(const double* _
                                                                   double* __restrict__ lam_m, double* __restrict__ lam_var) {
   estep_proj_moments_body(Z, ld, nb, z1, kv0, n, lam_m, lam_var);
 }
-// the same behind the gate of a chained step (gpfit_estep_chain)
-__global__ __launch_bounds__(256) void estep_proj_moments_chain_kernel(ChainGate g, const double* __restrict__ Z,
-                                                                        int64_t ld, int nb, const double* __restrict__ z1,
-                                                                        const double* __restrict__ kv0, int n,
-                                                                        double* __restrict__ lam_m,
-                                                                        double* __restrict__ lam_var) {
-  if (!g.open()) return;
-  estep_proj_moments_body(Z, ld, nb, z1, kv0, n, lam_m, lam_var);
-}
 int launch_estep_proj_moments(const double* Z, int64_t ld, int nb, const double* z1, const double* kv0, int n,
                               double* lam_m, double* lam_var, hipStream_t s) {
   hipLaunchKernelGGL(estep_proj_moments_kernel, dim3((n + 3) / 4), dim3(256), 0, s, Z, ld, nb, z1, kv0, n, lam_m, lam_var);
   GP_HIP(hipGetLastError());
   return 0;
 }
-int launch_estep_proj_moments_chain(ChainGate g, const double* Z, int64_t ld, int nb, const double* z1, const double* kv0,
-                                    int n, double* lam_m, double* lam_var, hipStream_t s) {
-  hipLaunchKernelGGL(estep_proj_moments_chain_kernel, dim3((n + 3) / 4), dim3(256), 0, s, g, Z, ld, nb, z1, kv0, n, lam_m,
-                     lam_var);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
 
-
-// ---- the group forms (gpfit_estep_chain_batch)
+// ---- the chained E-steps (gpfit_estep_chain, gpfit_estep_chain_batch)
 int launch_estep_proj_rows_chain_group(const ChainGroupT& g, int step, hipStream_t s) {
   hipLaunchKernelGGL(estep_proj_rows_chain_group_kernel, dim3((g.nrows + 3) / 4, g.n_units), dim3(256), 0, s, g.a, g.lda, g.nb,
                      g.m, g.f, g.r, g.n, g.nrows, g.blk, g.info, step, g.sv, g.u);
@@ -439,6 +402,7 @@ int launch_estep_proj_scale_group(const ChainGroupT& g, hipStream_t s) {
   GP_HIP(hipGetLastError());
   return 0;
 }
+// estep_proj_moments_body behind each unit's gate
 __global__ __launch_bounds__(256) void estep_proj_moments_chain_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info,
                                                                               PerUnit<double*> Z, int64_t ld, PerUnit<int> nb,
                                                                               PerUnit<double*> z1, PerUnit<const double*> kv0,

@@ -626,6 +626,19 @@ def _estep_projected(r, KKtilde_inv, aL, L, m, f_params, f_mean, kv0=None):
 CHAIN_MAX_STEPS = 1024   # GPFIT_ESTEP_CHAIN_MAX_STEPS of the C header
 
 
+def _chain_state(m, f_mean, V, lambda_m, lambda_var, N, nv, dev):
+    """The state a chain call updates in place, as copies of its own ``(m, f, V, lambda_m, lambda_var)``: the arguments
+    are left alone; ``V`` (nv x nv) and the moments (N) not given start uninitialised."""
+    def own(t, *shape):
+        return torch.empty(shape, dtype=TORCH_DTYPE, device=dev) if t is None else _cu(t).clone().contiguous()
+    return _cu(m).clone().contiguous(), _cu(f_mean).clone().contiguous(), own(V, nv, nv), own(lambda_m, N), own(lambda_var, N)
+
+
+def _chain_records(rec, n_steps):
+    """One 12-number record per step (include/gpfit_mi355x.h) from the flat array a chain call filled."""
+    return [list(rec[12 * k:12 * k + 12]) for k in range(n_steps)]
+
+
 def _estep_chain(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
                  lambda_m=None, lambda_var=None):
     """``n_steps`` E-steps between two kernel rebuilds (utils.py:1864-1934: ``_estep_projected`` with its moments, then
@@ -658,12 +671,7 @@ def _estep_chain_full(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps
     the first failing step."""
     r, K, kv0 = (_cu(t).contiguous() for t in (r, K_tilde, kv0))
     N = int(K.shape[0])
-    dev = K.device
-    m = _cu(m).clone().contiguous()
-    f = _cu(f_mean).clone().contiguous()
-    V = torch.empty((N, N), dtype=TORCH_DTYPE, device=dev) if V is None else _cu(V).clone().contiguous()
-    lam_m = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_m is None else _cu(lambda_m).clone().contiguous()
-    lam_var = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_var is None else _cu(lambda_var).clone().contiguous()
+    m, f, V, lam_m, lam_var = _chain_state(m, f_mean, V, lambda_m, lambda_var, N, N, K.device)
     n_steps, nfp = int(n_steps), int(n_fparam_steps)
     fixed = lambda0_fixed is not None
     rec = (ctypes.c_double * (12 * max(n_steps, 1)))()
@@ -674,7 +682,7 @@ def _estep_chain_full(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps
                                                   float(lambda0_fixed) if fixed else 0.0, n_steps, nfp, nfp, 0.1, 1.e-7,
                                                   1.e-9, rec),
                "gpfit_estep_chain_full")
-    return m, V, lam_m, lam_var, f, [list(rec[12 * k:12 * k + 12]) for k in range(n_steps)]
+    return m, V, lam_m, lam_var, f, _chain_records(rec, n_steps)
 
 
 MAX_CHAIN_UNITS = 16     # GPFIT_ESTEP_CHAIN_MAX_UNITS of the C header
@@ -691,20 +699,14 @@ def _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fpar
     q = {"kind": "chain", "r": r, "a": a, "aL": aL, "L": L, "kv0": kv0, "N": int(N), "nb": int(nb), "logA0": float(logA0),
          "n_steps": int(n_steps), "nfp": int(n_fparam_steps),
          "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
-    q["m"] = _cu(m).clone().contiguous()
-    q["f"] = _cu(f_mean).clone().contiguous()
-    q["V"] = torch.empty((nb, nb), dtype=TORCH_DTYPE, device=dev) if V is None else _cu(V).clone().contiguous()
-    q["lam_m"] = torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_m is None else _cu(lambda_m).clone().contiguous()
-    q["lam_var"] = (torch.empty(N, dtype=TORCH_DTYPE, device=dev) if lambda_var is None
-                    else _cu(lambda_var).clone().contiguous())
+    q["m"], q["f"], q["V"], q["lam_m"], q["lam_var"] = _chain_state(m, f_mean, V, lambda_m, lambda_var, N, nb, dev)
     q["engine"] = engine if engine is not None else get_engine(max(N, nb), 1)
     q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
     return q
 
 
 def _chain_result(q, rec):
-    n = q["n_steps"]
-    return q["m"], q["V"], q["lam_m"], q["lam_var"], q["f"], [list(rec[12 * k:12 * k + 12]) for k in range(n)]
+    return q["m"], q["V"], q["lam_m"], q["lam_var"], q["f"], _chain_records(rec, q["n_steps"])
 
 
 def _chain_run_single(q):

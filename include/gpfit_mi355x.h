@@ -337,6 +337,7 @@ int gpfit_fparam_lbfgs_host(const double* lam_m, const double* lam_var, const do
  * A step whose W is not positive definite (info != 0) commits nothing; a step whose optimiser fails (status != 0) has
  * committed m, V and the moments, and leaves f, logA and lambda0 alone.  After either, no later step changes m, V, f,
  * lam_m, lam_var, logA or lambda0, and its record is all zero.
+ * There is one implementation for this call and gpfit_estep_chain_batch: the single call is the group of one.
  * Returns 0 when the chain ran, whatever the records say; < 0 on bad arguments or insufficient capacity. */
 #define GPFIT_ESTEP_CHAIN_MAX_STEPS 1024
 int gpfit_estep_chain(gpfit_ctx* ctx, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
@@ -379,7 +380,7 @@ int gpfit_estep_chain_full(gpfit_ctx* ctx, void* stream, const double* K, int64_
  * All units of a call must have the same round_up(nb[u], 128) (nb[u] itself may differ): the recursion's split depends
  * on the padded size; otherwise -3 -- the caller groups its units by padded size.
  * rec_host[n_units][n_steps][12]: the records of gpfit_estep_chain, unit by unit.  Every output and record of unit u has
- * the bits of gpfit_estep_chain called for that unit alone; a unit that stops (W not positive definite, optimiser
+ * the bits it has when that unit is called alone (gpfit_estep_chain is this call with one unit); a unit that stops (W not positive definite, optimiser
  * failure) stops alone, exactly as there, and changes nothing in the others.
  * Returns 0 when the chains ran, whatever the records say; < 0 on bad arguments (nothing is enqueued then). */
 #define GPFIT_ESTEP_CHAIN_MAX_UNITS 16

@@ -1,8 +1,10 @@
 """gpfit_estep_chain_batch (the E-step chains of several independent units as one lock-step device call) on the GPU:
-every unit against gpfit_estep_chain on that unit alone, bit for bit; a failing unit stops alone; the refusals; and
-varGP_cells against the same fits run one after another."""
+every unit inside a group against the same unit alone (gpfit_estep_chain, the group of one of the same implementation),
+bit for bit; one step of a group against the un-chained calls it stands for; a failing unit stops alone; the refusals;
+and varGP_cells against the same fits run one after another."""
 import contextlib
 import copy
+import ctypes
 import functools
 import io
 import math
@@ -62,6 +64,7 @@ def unit(c, logA0, fixed=None, **over):
 
 
 def single(gp, u, n_steps, nfp=NFP):
+    """The unit alone: gpfit_estep_chain, the group of one."""
     return gp._estep_chain(n_steps=n_steps, n_fparam_steps=nfp, **u)
 
 
@@ -82,6 +85,7 @@ def assert_bit_equal(got, want, what):
 @pytest.mark.parametrize("n_steps", [1, 3])
 @pytest.mark.parametrize("nt,nbs", SHAPES)
 def test_every_unit_has_the_bits_of_its_single_chain(gp, nt, nbs, n_steps, fixed):
+    """A unit inside a group against the same unit alone."""
     units = [unit(case(nt, nb, 100 + i), math.log(0.5) + 0.1 * i, fixed) for i, nb in enumerate(nbs)]
     group = gp._estep_chain_group(units, n_steps, NFP)
     assert len(group) == len(units)
@@ -94,7 +98,37 @@ def test_every_unit_has_the_bits_of_its_single_chain(gp, nt, nbs, n_steps, fixed
     assert moved                                            # the optimisers moved: the steps really differ
 
 
+def test_one_step_of_a_group_against_the_existing_pair(gp):
+    """The group's own anchor in code the chain does not share: three units at N = 200 (nb = 70, 128, 101 under one padded
+    size), one step, against _estep_projected(kv0=) followed by gpfit_fparam_lbfgs unit by unit (tests/
+    test_gpu_estep_chain.py::test_one_step_against_the_existing_pair).  logA0 = 0 for all: exp is exactly 1 on the device
+    and on the host, so this is the exact branch and every output and the optimiser's nine results have the pair's bits."""
+    nt, nbs = SHAPES[0]
+    assert (nt, nbs) == (200, (70, 128, 101))
+    cs = [case(nt, nb, 600 + i) for i, nb in enumerate(nbs)]
+    group = gp._estep_chain_group([unit(c, 0.0) for c in cs], 1, NFP)
+    assert len(group) == 3
+    for i, (c, (m1, V1, lm1, lv1, f1, rec)) in enumerate(zip(cs, group)):
+        fp = {"logA": torch.tensor(0.0, dtype=torch.float64)}
+        m2, V2, lm2, lv2 = gp._estep_projected(c["r"], c["a"], c["aL"], c["L"], c["m"], fp, c["f"], kv0=c["kv0"])
+        n = lm2.shape[0]
+        f2 = torch.empty(n, dtype=torch.float64, device=lm2.device)
+        out = (ctypes.c_double * 9)()
+        _lib.check(_lib.load().gpfit_fparam_lbfgs(gp.get_engine(n, 1)._ctx, gp._stream(), lm2.data_ptr(), lv2.data_ptr(),
+                                                  c["r"].data_ptr(), n, 0.0, 0, 0.0, NFP, NFP, 0.1, 1e-7, 1e-9, f2.data_ptr(),
+                                                  out), "gpfit_fparam_lbfgs")
+        rec, out = rec[0], list(out)
+        assert rec[9] == 0 and rec[10] == 1 and rec[6] == 0 and out[6] == 0, (i, rec, out)
+        assert rec[11] == 1.0, (i, rec[11])
+        for name, x, y in (("m", m1, m2), ("V", V1, V2), ("lam_m", lm1, lm2), ("lam_var", lv1, lv2), ("f", f1, f2)):
+            assert torch.equal(x, y), (i, name)
+        assert same(rec[:9], out), (i, rec, out)
+        assert rec[0] != 0.0                                # the optimiser moved
+
+
 def test_sixteen_units_and_a_group_of_one(gp):
+    """Units inside a group of 16 against the same units alone, and the group of one through the batch entry point
+    against the single entry point."""
     nbs = [70 + (58 * i) // 15 for i in range(16)]          # 70 .. 128 under one padded size
     assert nbs[0] == 70 and nbs[-1] == 128
     units = [unit(case(200, nb, 200 + i), math.log(0.5) - 0.05 * i) for i, nb in enumerate(nbs)]
@@ -108,8 +142,8 @@ def test_sixteen_units_and_a_group_of_one(gp):
 
 def test_a_unit_whose_W_is_not_positive_definite_stops_alone(gp):
     """Unit 1 of three starts from a rate with one entry inf (test_non_finite_rate_stops_the_chain): its record carries
-    the info and nothing else, its arrays come back with the bits they went in with; units 0 and 2 are their single
-    chains."""
+    the info and nothing else, its arrays come back with the bits they went in with; every unit inside the group has the
+    bits of the same unit alone."""
     cs = [case(200, 128, 300 + i) for i in range(3)]
     rng = np.random.default_rng(3)
     f_bad = cs[1]["f"].clone()
@@ -125,7 +159,7 @@ def test_a_unit_whose_W_is_not_positive_definite_stops_alone(gp):
     assert rec[1] == [0.0] * 12 and rec[2] == [0.0] * 12, rec
     for x, y in ((m, cs[1]["m"]), (V, V0), (lm, lm0), (lv, lv0), (f, f_bad)):
         assert torch.equal(x, y)
-    assert_bit_equal(group[1], single(gp, units[1], 3), "the failing unit against its single chain")
+    assert_bit_equal(group[1], single(gp, units[1], 3), "the failing unit in the group against the same unit alone")
     for i in (0, 2):
         want = single(gp, units[i], 3)
         assert all(rec[9] == 0 and rec[10] == 1 and rec[6] == 0 for rec in want[5]), (i, want[5])
@@ -135,7 +169,7 @@ def test_a_unit_whose_W_is_not_positive_definite_stops_alone(gp):
 def test_a_unit_whose_optimiser_fails_stops_alone(gp):
     """kv0[3] = 1e6 in unit 1: the update of step 0 is committed, its moments carry lam_var[3] >= 1e6, so the first
     closure call of the optimiser meets sum f = inf (status 1); f stays and the two steps behind are skipped.  Units 0
-    and 2 run their three steps with the bits of their single chains."""
+    and 2 run their three steps; every unit inside the group has the bits of the same unit alone."""
     cs = [case(200, 128, 400 + i) for i in range(3)]
     kv_bad = cs[1]["kv0"].clone()
     kv_bad[3] = 1.0e6
@@ -145,7 +179,7 @@ def test_a_unit_whose_optimiser_fails_stops_alone(gp):
     assert rec[0][9] == 0 and rec[0][10] == 1 and int(rec[0][6]) == 1, rec[0]
     assert rec[1] == [0.0] * 12 and rec[2] == [0.0] * 12, rec
     assert torch.equal(f, cs[1]["f"]) and not torch.equal(m, cs[1]["m"]) and float(lv[3]) >= 1.0e6
-    assert_bit_equal(group[1], single(gp, units[1], 3), "the failing unit against its single chain")
+    assert_bit_equal(group[1], single(gp, units[1], 3), "the failing unit in the group against the same unit alone")
     for i in (0, 2):
         want = single(gp, units[i], 3)
         assert all(rec[9] == 0 and rec[10] == 1 and rec[6] == 0 for rec in want[5]), (i, want[5])
