@@ -77,9 +77,9 @@ inline Lane side_lane(const gpfit_ctx* c) { return {c->side, c->sk_ws[1]}; }
 // ---- names of the numbered slots
 // gpfit_ctx::scal / scal_host (64 doubles), with who writes each
 enum ScalSlot {
-  S_RLAM = 0, S_SUMR = 1, S_SUMF = 2,   // likelihood sums r . lam_m, sum r, sum f (launch_moments / launch_proj_moments)
+  S_RLAM = 0, S_SUMR = 1, S_SUMF = 2,   // likelihood sums r . lam_m, sum r, sum f (launch_moments / launch_proj_moments_group)
   S_LOGDET_K = 3,                       // log|K~| (launch_logdet / launch_logdet_pair)
-  S_TRACE = 5,                          // ||T||_F^2 (launch_frob_finish / launch_frob_lower) or tr(K~_b^-1 V_b) (launch_proj_trace)
+  S_TRACE = 5,                          // ||T||_F^2 (launch_frob_finish / launch_frob_lower) or tr(K~_b^-1 V_b) (launch_proj_trace_group)
   S_MKM = 6,                            // m^T K~^-1 m (launch_dot)
   S_ADJ = 7, S_ADJ_WL = 8, S_ADJ_SUMA = 9,   // adjoint sums: sum u/q (S_ADJ), sum wl, sum A_w (launch_adjoint_reduce)
   S_METRIC = 10,                        // 10-14: the contraction with dC_p (launch_metric_contract), in the order ...

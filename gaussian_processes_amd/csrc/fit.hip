@@ -152,44 +152,38 @@ static int splitk_for(int M, int N, int K) {
   sp = std::min<long>(sp, std::max(1, K / 256));
   return (int)std::max<long>(1, sp);
 }
-// C = alpha op(A) op(B) with the k range cut into splitk_for slabs: the shapes of the truncated-rank closures whose
-// output has few tiles but a long k (K_b = K~ B: 8192 x 512 x 8192; B^T X: 512 x 512 x 8192) fill the chip with
-// 128-tiles only this way.  The slabs go to `partial` (splits x M x ldc elements) and are added in slab order by
-// one pass (deterministic; C must be the contiguous block [M][ldc]).  One slab: the plain launch.
-template <typename R>
-static int gemm_splitk(Lane lane, Dims d, double alpha, const Operand<R>& a, const Operand<R>& b, R* C, int64_t ldc, R* partial,
-                       int64_t partial_elems) {
-  static const bool off = getenv("GPFIT_NO_SPLITK") != nullptr;   // tuning knob
-  const int64_t slab = (int64_t)d.M * ldc;
-  const int splits = (int)std::min<int64_t>(splitk_for(d.M, d.N, d.K),
-                                            partial_elems / std::max<int64_t>(1, slab));   // what the scratch holds
-  if (splits <= 1 || off || partial == nullptr) return product(lane, d, alpha, a, b, into(mat(C, ldc)));
-  GemmArgsT<R> g = product_args(lane, d, alpha, a, b, into(mat(partial, ldc)));
-  g.split_k = splits;
-  g.sC = slab;
-  g.tile = TILE;
-  GP_TRY(run_gemm(lane.s, g));
-  return launch_reduce_slices(partial, slab, splits, C, slab, lane.s);
-}
-
-// The same for every problem of a list, each with its own slab scratch.  A product that takes slabs for one problem is
-// issued problem by problem -- the slab count depends on the problem's own scratch, and a 128-tile launch fills the
+// C = alpha op(A) op(B) for every problem of a list, the k range of each cut into splitk_for slabs: the shapes of the
+// truncated-rank closures whose output has few tiles but a long k (K_b = K~ B: 8192 x 512 x 8192; B^T X: 512 x 512 x
+// 8192) fill the chip with 128-tiles only this way.  A problem's slabs go to its own scratch partial[i] (splits x M x ld
+// elements; as many slabs as it holds) and are added in slab order by one pass (deterministic; C must be the contiguous
+// block [M][ld]).  A product that takes slabs for one problem is issued problem by problem -- a 128-tile launch fills the
 // chip alone; where no problem takes slabs the list goes through product, which decides about batching as ever.
 template <typename R>
 static int gemm_splitk_list(Lane lane, Dims d, double alpha, const Operand<R>& a, const Operand<R>& b, const Mat<R>& C,
                             R* const* partial, const int64_t* partial_elems) {
-  static const bool off = getenv("GPFIT_NO_SPLITK") != nullptr;
-  const int cnt = C.cnt;
+  static const bool off = getenv("GPFIT_NO_SPLITK") != nullptr;   // tuning knob
   const int64_t slab = (int64_t)d.M * C.ld;
+  int splits[GEMM_MAXB];
   bool any = false;
-  for (int i = 0; i < cnt && !off; ++i)
-    any = any || (partial[i] && std::min<int64_t>(splitk_for(d.M, d.N, d.K), partial_elems[i] / std::max<int64_t>(1, slab)) > 1);
+  for (int i = 0; i < C.cnt; ++i) {
+    splits[i] = (off || !partial[i]) ? 1 : (int)std::min<int64_t>(splitk_for(d.M, d.N, d.K), partial_elems[i] / std::max<int64_t>(1, slab));
+    any = any || splits[i] > 1;
+  }
   if (!any) return product(lane, d, alpha, a, b, into(C));
-  for (int i = 0; i < cnt; ++i) {
+  for (int i = 0; i < C.cnt; ++i) {
     Operand<R> ai = a, bi = b;
     ai.m.cnt = bi.m.cnt = 1;
     ai.m.p[0] = a.m.p[i]; bi.m.p[0] = b.m.p[i];
-    GP_TRY(gemm_splitk(lane, d, alpha, ai, bi, C.p[i], C.ld, partial[i], partial_elems[i]));
+    if (splits[i] <= 1) {
+      GP_TRY(product(lane, d, alpha, ai, bi, into(mat(C.p[i], C.ld))));
+      continue;
+    }
+    GemmArgsT<R> g = product_args(lane, d, alpha, ai, bi, into(mat(partial[i], C.ld)));
+    g.split_k = splits[i];
+    g.sC = slab;
+    g.tile = TILE;
+    GP_TRY(run_gemm(lane.s, g));
+    GP_TRY(launch_reduce_slices(partial[i], slab, splits[i], C.p[i], slab, lane.s));
   }
   return 0;
 }
@@ -590,7 +584,7 @@ static int dev_alloc(gpfit_ctx* c, T** p, size_t count) {
 //   demote_for_mixed, set_pending              x        x
 //   adjoint_pass, xty                          x        x          x             x          x
 //   pullback_to_metric                                             x             x          x
-//   projected_factor, projected_kl_products                                      x          x
+//   projected_factor, _kl_products, _adjoints, closure_prepare / _collect        x          x
 //   assemble_out                          (fit_eval_finish)                      x          x
 // A stage is a fixed launch sequence; where two entry points order their launches differently the cut is between
 // stages, never inside one.
@@ -782,7 +776,12 @@ static PerUnit<T> per_unit(int cnt, F&& at) {
   for (int i = 0; i < cnt && i < CHAIN_MAXU; ++i) t.v[i] = at(i);
   return t;
 }
-// the work matrices of a unit's V_b chain (the caller's: which of the context's are idle differs between the closures)
+// the work matrices of a unit's V_b chain (the caller's: which of the context's are idle differs between the closures).
+// The recursion writes a chain's L, L^-1 and Tmp on and below the diagonal only and reads them as triangles (k ranges
+// that end with the diagonal tile, which the leaf writes whole) or as blocks below the diagonal: what the tiles above
+// hold is never summed, and the truncated closure hands over Wbuf, Zbuf and Tmp as the last evaluation left them.  The
+// sparse closure clears its three first (launch_zero3_group): its chain began in slots of the split-K scratch, which
+// were cleared, and the clear moved with the chain into Kbuf, Lbuf and Abuf.  Each keeps its own launch sequence.
 struct ProjChain { double *Va, *Vl, *Vli, *Vt; };
 // K~_b (packed into S1) = L L^T with L^-1 (utils.py:2067) and V_b (packed into Va) = L_V L_V^T (log|V_b|, :1326): the
 // 2 cnt chains in lock step, the inverse for the K~_b chains only; then K~_b^-1 = L^-T L^-1 in S1 and V_b in S2, both
@@ -830,6 +829,42 @@ static int projected_kl_products(Lane lane, int cnt, gpfit_ctx* const* cs, const
                                  per_unit<int>(cnt, [&](int i) { return nk[i]; }),
                                  per_unit<double*>(cnt, [&](int i) { return cs[i]->scal + S_TRACE; }), lane.s));
   return product(lane, {nb, nb, nb}, 1.0, plain(S3), plain(Ki), into(S4));
+}
+// What both closures run behind a V_b, for the units of pg (a = pg.am is B, or K_b K~_b^-1): b = K~_b^-1 m_b and m_b . b;
+// moments, rate, likelihood pieces (utils.py:1090, 1101, 1138, 1243) and the per-point adjoints g_m, g_v; G_a, G_a K~_b^-1,
+// P2 = a^T G_a K~_b^-1 in the k slabs of each unit's `part`, G_K~b, and G_Kb in place on G_a K~_b^-1 (utils._closure_adjoints).
+static int projected_adjoints(Lane lane, const ProjGroupT& pg, double* const* part, const int64_t* part_elems) {
+  auto all = [&](const PerUnit<double*>& X) { return mats(pg.n_units, pg.ld, [&](int i) { return X[i]; }); };
+  GP_TRY(launch_symv_lower_group(pg.n_units, pg.Ki, pg.ld, pg.nb, pg.mb, pg.bvec, lane.s));
+  GP_TRY(launch_dot_group(pg.n_units, pg.mb, pg.bvec, pg.nb, pg.mkm, lane.s));
+  GP_TRY(launch_proj_moments_group(pg, lane.s));
+  GP_TRY(launch_proj_ga_group(pg, lane.s));
+  GP_TRY(product(lane, {pg.np, pg.nb, pg.nb}, 1.0, plain(all(pg.Ga)), plain(all(pg.Ki)), into(all(pg.GaKi))));
+  GP_TRY(gemm_splitk_list(lane, {pg.nb, pg.nb, pg.np}, 1.0, trans(all(pg.am)), plain(all(pg.GaKi)), all(pg.P2), part, part_elems));
+  GP_TRY(launch_proj_gktb_group(pg, lane.s));   // G_K~b
+  return launch_proj_gkb_group(pg, lane.s);     // G_Kb
+}
+// The housekeeping of the closures of cnt units, one launch each (kernels.h).  Begin: pixel lists, info words, m_b padded
+// to nb, bv / wl cleared.  End: the 64 scalars and the info words of every unit straight into its pinned host buffers.
+static int closure_prepare(int cnt, gpfit_ctx* const* cs, const int* d, const int* nk, const double* const* m_b, int nb, hipStream_t s) {
+  ClosurePrepT gp{};
+  gp.n_units = cnt; gp.nb = nb;
+  for (int i = 0; i < cnt; ++i) {
+    gpfit_ctx* c = cs[i];
+    gp.pix_host.v[i] = c->pix_host; gp.pix.v[i] = c->pix; gp.info.v[i] = c->info; gp.d.v[i] = d[i]; gp.nk.v[i] = nk[i];
+    gp.cap.v[i] = c->np_cap; gp.cap_max = std::max(gp.cap_max, c->np_cap);
+    gp.m_b.v[i] = m_b[i]; gp.mpad.v[i] = c->mpad; gp.bv.v[i] = c->bv; gp.wl.v[i] = c->wl;
+  }
+  return launch_closure_prepare(gp, s);
+}
+static int closure_collect(int cnt, gpfit_ctx* const* cs, hipStream_t s) {
+  GroupCollectT gc{};
+  gc.n_units = cnt;
+  for (int i = 0; i < cnt; ++i) {
+    gpfit_ctx* c = cs[i];
+    gc.scal[i] = c->scal; gc.info[i] = c->info; gc.scal_host[i] = c->scal_host; gc.info_host[i] = c->info_host;
+  }
+  return launch_group_collect(gc, s);
 }
 
 // ---- host assembly of an evaluation's 16 output scalars from the device scalars (c->scal_host, c->info_host)
@@ -1445,7 +1480,8 @@ static int grad_pullback_impl(gpfit_ctx* c, void* stream, const double* theta, i
 // the device in one call (the algebra of utils._closure_projected).  Every
 // N x n matrix lives zero-padded to nb = ceil(n / 128) 128 columns in one of the context's N x N
 // work matrices; the n x n ones carry the identity on their padding (log-determinants and solves
-// are unaffected, the padding of G_K~b cancels to zero).
+// are unaffected, the padding of G_K~b cancels to zero).  The closure of ONE unit written through the list forms (every
+// small kernel its unit-batched launch, the products on lists of one), on this closure's own choice of work matrices.
 static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* theta, const double* lower,
                                    const double* upper, int n_rows, int n_cols, const double* X, int64_t ldx, int64_t N,
                                    const double* r, const double* B, int64_t ldb, int64_t n_kept, const double* m_b,
@@ -1473,40 +1509,39 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   double *Kt = c->Kbuf, *Bp = c->Lbuf, *Kb = c->Libuf, *aV = c->Tbuf, *Ga = c->Zbuf, *GaKi = c->Tmp, *W = c->Wbuf;
   double *S1 = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;   // n x n scratch (leading dimension nb)
   double *mbp = c->mpad, *bvec = c->yv, *gm = c->dq1, *gv = c->dq2;
-  GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
-  GP_HIP(hipMemcpyAsync(c->pix, c->pix_host, (size_t)d * sizeof(int), hipMemcpyHostToDevice, s));
+  auto one = [](auto v) { return per_unit<decltype(v)>(1, [&](int) { return v; }); };
+  const PerUnit<int> nks = one(nk);
+  GP_TRY(closure_prepare(1, &c, &d, &nk, &m_b, nb, s));
   // ---- kernel build (as the full-rank unit): C, X masked, cos, Kvec, q, and K~ stored in full by the tiles
   // themselves (mirror): it is multiplied from the left below
   GP_TRY(build_kernel<R>(c, lane, th, d, dp, n_rows, n_cols, X, ldx, n, np, 1));
   // ---- projection (utils.py:2047-2049): K_b = K~ B, K~_b = sym(B^T K_b)
-  GP_TRY(launch_pad_copy(B, ldb, n, nk, Bp, lb, np, nb, s));
-  GP_HIP(hipMemsetAsync(mbp, 0, (size_t)np * sizeof(double), s));
-  GP_HIP(hipMemcpyAsync(mbp, m_b, (size_t)nk * sizeof(double), hipMemcpyDeviceToDevice, s));
-  GP_TRY(gemm_splitk(lane, {np, nb, np}, 1.0, plain(mat(Kt, ld)), plain(mat(Bp, lb)), Kb, lb, c->Wbuf, (int64_t)c->np_cap * c->np_cap));
-  GP_TRY(gemm_splitk(lane, {nb, nb, np}, 1.0, trans(mat(Bp, lb)), plain(mat(Kb, lb)), S4, lb, c->Wbuf, (int64_t)c->np_cap * c->np_cap));
-  GP_TRY(launch_symmetrize_avg(S4, lb, nk, s));                                             // :2048
-  GP_TRY(launch_pack_lower(S4, lb, nk, S1, lb, nb, s));
+  GP_TRY(launch_pad_copy_group(1, one(B), one(ldb), n, nks, one(Bp), lb, np, nb, s));
+  // (skinny products with a long k are cut into k slabs, gemm_splitk_list; Wbuf is free until the adjoints)
+  double* const part = c->Wbuf;
+  const int64_t part_elems = (int64_t)c->np_cap * c->np_cap;
+  GP_TRY(gemm_splitk_list(lane, {np, nb, np}, 1.0, plain(mat(Kt, ld)), plain(mat(Bp, lb)), mat(Kb, lb), &part, &part_elems));
+  GP_TRY(gemm_splitk_list(lane, {nb, nb, np}, 1.0, trans(mat(Bp, lb)), plain(mat(Kb, lb)), mat(S4, lb), &part, &part_elems));
+  GP_TRY(launch_symmetrize_avg_group(1, one(S4), lb, nks, s));                                 // :2048
+  GP_TRY(launch_pack_lower_group(1, one((const double*)S4), one(lb), nks, one(S1), lb, nb, s));
   // (log|V_b| of :1326: V_b is factored together with K~_b -- one lock-step recursion on this stream, in four work
   // matrices nothing else needs before the adjoints: Abuf, Wbuf, Zbuf, Tmp)
-  GP_TRY(launch_pack_lower(V_b, ldvb, nk, c->Abuf, lb, nb, s));
+  GP_TRY(launch_pack_lower_group(1, one(V_b), one(ldvb), nks, one(c->Abuf), lb, nb, s));
   const ProjChain vchain{c->Abuf, c->Wbuf, c->Zbuf, c->Tmp};
   GP_TRY(projected_factor(lane, 1, &c, &V_b, &ldvb, &nk, nb, &vchain));
-  double* Ki = S1;
-  // a V = B V_b, then K~_b^-1 V_b with its trace and K~_b^-1 V_b K~_b^-1 (P1, in S4)
+  // K~_b^-1 is in S1 now.  a V = B V_b, then K~_b^-1 V_b with its trace and K~_b^-1 V_b K~_b^-1 (P1, in S4)
   GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S2, lb)), into(mat(aV, lb))));
   GP_TRY(projected_kl_products(lane, 1, &c, &nk, nb));
-  GP_TRY(launch_symv_lower(Ki, lb, nb, mbp, bvec, s));                                        // b = K~_b^-1 m_b
-  GP_TRY(launch_dot(mbp, bvec, nb, c->scal + S_MKM, s));
-  // ---- moments, rate, likelihood pieces (:1090, 1101, 1138, 1243) and the per-point adjoints
-  GP_TRY(launch_proj_moments(Bp, Kb, aV, lb, nb, mbp, c->Kvec, r, n, A, lambda0, c->lam_m, c->lam_var, c->fvec, gm, gv,
-                             c->upart, c->scal + S_RLAM, s));
-  // ---- adjoints (utils._closure_projected): G_a, G_Kb, G_K~b, W
-  GP_TRY(launch_proj_ga(Kb, aV, lb, nb, n, np, gm, gv, mbp, Ga, s));
-  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Ga, lb)), plain(mat(Ki, lb)), into(mat(GaKi, lb))));
-  GP_TRY(gemm_splitk(lane, {nb, nb, np}, 1.0, trans(mat(Bp, lb)), plain(mat(GaKi, lb)), c->Abuf, lb, c->Wbuf,
-                     (int64_t)c->np_cap * c->np_cap));   // P2 = B^T G_a K~_b^-1
-  GP_TRY(launch_proj_gktb(Ki, S4, c->Abuf, lb, nb, bvec, S3, s));                            // G_K~b
-  GP_TRY(launch_proj_gkb(Bp, lb, nb, n, np, gv, GaKi, s));                                   // G_Kb (in place)
+  // ---- moments / likelihood pieces with a = B and the adjoints G_a, G_Kb, G_K~b (P2 = B^T G_a K~_b^-1 in Abuf)
+  ProjGroupT pg{};
+  pg.n_units = 1; pg.n = n; pg.np = np; pg.nb = nb; pg.ld = lb;
+  pg.r = one(r); pg.A = one(A); pg.lambda0 = one(lambda0);
+  pg.am = one(Bp); pg.Kb = one(Kb); pg.aV = one(aV); pg.mb = one(mbp);
+  pg.Kvec = one(c->Kvec); pg.lam_m = one(c->lam_m); pg.lam_var = one(c->lam_var); pg.f = one(c->fvec);
+  pg.gm = one(gm); pg.gv = one(gv); pg.part = one(c->upart); pg.out3 = one(c->scal + S_RLAM);
+  pg.Ga = one(Ga); pg.GaKi = one(GaKi);
+  pg.Ki = one(S1); pg.P1 = one(S4); pg.P2 = one(c->Abuf); pg.bvec = one(bvec); pg.mkm = one(c->scal + S_MKM); pg.G = one(S3);
+  GP_TRY(projected_adjoints(lane, pg, &part, &part_elems));
   GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S3, lb)), into(mat(GaKi, lb), 1.0)));          // + B G_K~b
   // W = sym((.) B^T).  With P = B G_K~b + G_Kb:  1/2 (P B^T + B P^T) = 1/2 [P | B] [B | P]^T -- ONE product with
   // k = 2 nb that writes the lower tiles only (what the adjoint pass reads): the same flops as the full P B^T, and
@@ -1515,24 +1550,23 @@ static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* the
   if (2 * (int64_t)nb * np <= (int64_t)c->np_cap * c->np_cap) {
     double *Cat1 = Ga, *Cat2 = aV;   // G_a and a V_b are dead
     const int64_t l2b = 2 * lb;
-    GP_TRY(launch_pad_copy(GaKi, lb, np, nb, Cat1, l2b, np, nb, s));
-    GP_TRY(launch_pad_copy(Bp, lb, np, nb, Cat1 + nb, l2b, np, nb, s));
-    GP_TRY(launch_pad_copy(Bp, lb, np, nb, Cat2, l2b, np, nb, s));
-    GP_TRY(launch_pad_copy(GaKi, lb, np, nb, Cat2 + nb, l2b, np, nb, s));
+    const PerUnit<const double*> P = one((const double*)GaKi), Bc = one((const double*)Bp);
+    GP_TRY(launch_pad_copy_group(1, P, one(lb), np, one(nb), one(Cat1), l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(1, Bc, one(lb), np, one(nb), one(Cat1 + nb), l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(1, Bc, one(lb), np, one(nb), one(Cat2), l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(1, P, one(lb), np, one(nb), one(Cat2 + nb), l2b, np, nb, s));
     GP_TRY(product(lane, {np, np, 2 * nb}, 0.5, plain(mat(Cat1, l2b)), trans(mat(Cat2, l2b)), into_lower(mat(W, ld))));
   } else {
     GP_TRY(product(lane, {np, np, nb}, 1.0, plain(mat(GaKi, lb)), trans(mat(Bp, lb)), into(mat(W, ld))));
-    GP_TRY(launch_symmetrize_avg(W, ld, np, s));
+    GP_TRY(launch_symmetrize_avg_group(1, one(W), ld, one(np), s));
   }
-  // ---- pull-back of <W, dK~_p> + <gvec, dKvec_p> to the metric (as gpfit_grad_pullback; gvec = -g_v)
-  GP_HIP(hipMemsetAsync(c->bv, 0, (size_t)np * sizeof(R), s));
-  GP_HIP(hipMemsetAsync(c->wl, 0, (size_t)np * sizeof(R), s));
+  // ---- pull-back of <W, dK~_p> + <gvec, dKvec_p> to the metric (as gpfit_grad_pullback; gvec = -g_v; bv and wl were
+  // cleared at the start)
   GP_TRY(launch_scale_copy<R>(c->wl, gv, n, 1.0, s));
   GP_TRY(pullback_to_metric(c, lane, W, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
   GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
                                 c->info + INFO_METRIC, s));
-  GP_HIP(hipMemcpyAsync(c->scal_host, c->scal, 64 * sizeof(double), hipMemcpyDeviceToHost, s));
-  GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  GP_TRY(closure_collect(1, &c, s));
   GP_HIP(hipStreamSynchronize(s));
   const double* sc = c->scal_host;
   return assemble_out(c, A, lambda0, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[S_ADJ_WL], 0, d, 1,
@@ -1616,10 +1650,11 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
   hipStream_t s = (hipStream_t)stream;
   const int64_t l2 = np2, lb = nb;
   gpfit_ctx* cl[CHAIN_MAXU];
-  int nkl[CHAIN_MAXU];
+  int nkl[CHAIN_MAXU], dl[CHAIN_MAXU];
+  const double* mbl[CHAIN_MAXU];
   for (int i = 0; i < na; ++i) {
     gpfit_ctx* c = un[i].c;
-    cl[i] = c; nkl[i] = un[i].nk;
+    cl[i] = c; nkl[i] = un[i].nk; dl[i] = un[i].d; mbl[i] = m_b[un[i].u];
     c->lv_valid = false; c->lv32_valid = false;
     c->side_ev_next = 0;
   }
@@ -1636,18 +1671,7 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
   auto scal_of = [&](int slot) { return per_unit<double*>(na, [&](int i) { return cl[i]->scal + slot; }); };
   auto all = [&](double* gpfit_ctx::*X_, int64_t ld) { return mats(na, ld, [&](int i) { return cl[i]->*X_; }); };
   const PerUnit<int> nks = per_unit<int>(na, [&](int i) { return nkl[i]; });
-  {
-    // pixel lists, info words, the padded m_b and the cleared bv / wl of all units: one launch
-    ClosurePrepT gp{};
-    gp.n_units = na; gp.nb = nb;
-    for (int i = 0; i < na; ++i) {
-      gpfit_ctx* c = cl[i];
-      gp.pix_host.v[i] = c->pix_host; gp.pix.v[i] = c->pix; gp.info.v[i] = c->info; gp.d.v[i] = un[i].d; gp.nk.v[i] = nkl[i];
-      gp.cap.v[i] = c->np_cap; gp.cap_max = std::max(gp.cap_max, c->np_cap);
-      gp.m_b.v[i] = m_b[un[i].u]; gp.mpad.v[i] = c->mpad; gp.bv.v[i] = c->bv; gp.wl.v[i] = c->wl;
-    }
-    GP_TRY(launch_closure_prepare(gp, s));
-  }
+  GP_TRY(closure_prepare(na, cl, dl, nkl, mbl, nb, s));   // pixel lists, info words, the padded m_b, bv / wl cleared
   // ---- unit by unit, the kernel objects: C; training side (x: Xt, XCt, q, Kvec), inducing side (xtilde: Xt2, XCt2, q2);
   // K~ = acosker(xtilde, xtilde), lower tiles mirrored by the tiles themselves; K = acosker(x, xtilde)
   for (int i = 0; i < na; ++i) {
@@ -1673,15 +1697,13 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
                S4 = all(&gpfit_ctx::TmpV, lb);
   GP_TRY(launch_pad_copy_group(na, per_unit<const double*>(na, [&](int i) { return B[un[i].u]; }),
                                per_unit<int64_t>(na, [&](int i) { return ldb[un[i].u]; }), n2, nks, of(&gpfit_ctx::Tbuf), lb, np2, nb, s));
-  {
-    // (skinny products with a long k are cut into k slabs, gemm_splitk; Wbuf is free until the adjoints)
-    R* part[CHAIN_MAXU];
-    int64_t part_elems[CHAIN_MAXU];
-    for (int i = 0; i < na; ++i) { part[i] = cl[i]->Wbuf; part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap; }
-    GP_TRY(gemm_splitk_list(lane, {np1, nb, np2}, 1.0, plain(Kr), plain(Bp), Kb, part, part_elems));
-    GP_TRY(gemm_splitk_list(lane, {np2, nb, np2}, 1.0, plain(Kt), plain(Bp), am, part, part_elems));   // K~ B (temporary)
-    GP_TRY(gemm_splitk_list(lane, {nb, nb, np2}, 1.0, trans(Bp), plain(am), S4, part, part_elems));
-  }
+  // (skinny products with a long k are cut into k slabs, gemm_splitk_list; Wbuf is free until the adjoints)
+  R* part[CHAIN_MAXU];
+  int64_t part_elems[CHAIN_MAXU];
+  for (int i = 0; i < na; ++i) { part[i] = cl[i]->Wbuf; part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap; }
+  GP_TRY(gemm_splitk_list(lane, {np1, nb, np2}, 1.0, plain(Kr), plain(Bp), Kb, part, part_elems));
+  GP_TRY(gemm_splitk_list(lane, {np2, nb, np2}, 1.0, plain(Kt), plain(Bp), am, part, part_elems));   // K~ B (temporary)
+  GP_TRY(gemm_splitk_list(lane, {nb, nb, np2}, 1.0, trans(Bp), plain(am), S4, part, part_elems));
   GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::TmpV), lb, nks, s));
   const PerUnit<int64_t> lbs = per_unit<int64_t>(na, [&](int) { return lb; });
   GP_TRY(launch_pack_lower_group(na, cof(&gpfit_ctx::TmpV), lbs, nks, of(&gpfit_ctx::Vbuf), lb, nb, s));
@@ -1707,8 +1729,6 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
   GP_TRY(projected_kl_products(lane, na, cl, nkl, nb));
   GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(Kb), plain(Ki), into(am)));           // a
   GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(am), plain(S2), into(aV)));           // a V_b
-  GP_TRY(launch_symv_lower_group(na, of(&gpfit_ctx::Vbuf), lb, nb, of(&gpfit_ctx::mpad), of(&gpfit_ctx::yv), s));
-  GP_TRY(launch_dot_group(na, of(&gpfit_ctx::mpad), of(&gpfit_ctx::yv), nb, scal_of(S_MKM), s));
   // ---- moments / likelihood pieces with a = K_b K~_b^-1, per-point adjoints; G_a = Kbuf, G_a K~_b^-1 = Lbuf [np1][nb]
   ProjGroupT pg{};
   pg.n_units = na; pg.n = n1; pg.np = np1; pg.nb = nb; pg.ld = lb;
@@ -1720,28 +1740,17 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
   pg.gm = of(&gpfit_ctx::dq1); pg.gv = of(&gpfit_ctx::dq2); pg.part = of(&gpfit_ctx::upart); pg.out3 = scal_of(S_RLAM);
   pg.Ga = of(&gpfit_ctx::Kbuf); pg.GaKi = of(&gpfit_ctx::Lbuf);
   pg.Ki = of(&gpfit_ctx::Vbuf); pg.P1 = of(&gpfit_ctx::TmpV); pg.P2 = of(&gpfit_ctx::Wbuf); pg.bvec = of(&gpfit_ctx::yv);
-  pg.G = of(&gpfit_ctx::LiVbuf);
-  const Mat<R> Ga = all(&gpfit_ctx::Kbuf, lb), GaKi = all(&gpfit_ctx::Lbuf, lb);
-  GP_TRY(launch_proj_moments_group(pg, s));
-  GP_TRY(launch_proj_ga_group(pg, s));
-  GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(Ga), plain(Ki), into(GaKi)));
-  {
-    // P2 = a^T G_a K~_b^-1 (slabs behind P1 in TmpV)
-    R* part[CHAIN_MAXU];
-    int64_t part_elems[CHAIN_MAXU];
-    for (int i = 0; i < na; ++i) {
-      part[i] = cl[i]->TmpV + (int64_t)nb * nb;
-      part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap - (int64_t)nb * nb;
-    }
-    GP_TRY(gemm_splitk_list(lane, {nb, nb, np1}, 1.0, trans(am), plain(GaKi), all(&gpfit_ctx::Wbuf, lb), part, part_elems));
+  pg.mkm = scal_of(S_MKM); pg.G = of(&gpfit_ctx::LiVbuf);
+  for (int i = 0; i < na; ++i) {   // P2's slabs behind P1 in TmpV
+    part[i] = cl[i]->TmpV + (int64_t)nb * nb;
+    part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap - (int64_t)nb * nb;
   }
-  GP_TRY(launch_proj_gktb_group(pg, s));   // G_K~b
-  GP_TRY(launch_proj_gkb_group(pg, s));    // G_Kb (in place)
+  GP_TRY(projected_adjoints(lane, pg, part, part_elems));
   // ---- the two adjoints:  W~ = sym(B G_K~b B^T) [np2 x np2],  W_K = G_Kb B^T [np1 x np2]
   GP_TRY(product(lane, {np2, nb, nb}, 1.0, plain(Bp), plain(S3), into(all(&gpfit_ctx::Kbuf, lb))));   // B G_K~b  (G_a is dead)
   GP_TRY(product(lane, {np2, np2, nb}, 1.0, plain(all(&gpfit_ctx::Kbuf, lb)), trans(Bp), into(all(&gpfit_ctx::Wbuf, l2))));
   GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::Wbuf), l2, per_unit<int>(na, [&](int) { return np2; }), s));
-  GP_TRY(product(lane, {np1, np2, nb}, 1.0, plain(GaKi), trans(Bp), into(all(&gpfit_ctx::Abuf, l2))));   // W_K  (a V_b is dead)
+  GP_TRY(product(lane, {np1, np2, nb}, 1.0, plain(all(&gpfit_ctx::Lbuf, lb)), trans(Bp), into(all(&gpfit_ctx::Abuf, l2))));   // W_K  (a V_b is dead)
   // ---- unit by unit, the two pull-backs
   for (int i = 0; i < na; ++i) {
     gpfit_ctx* c = cl[i];
@@ -1769,16 +1778,7 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
     GP_TRY(launch_metric_contract(q.th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
                                   c->info + INFO_METRIC, s));
   }
-  {
-    // the 64 scalars and the info words of every unit straight into its pinned host buffers: one launch
-    GroupCollectT gc{};
-    gc.n_units = na;
-    for (int i = 0; i < na; ++i) {
-      gpfit_ctx* c = cl[i];
-      gc.scal[i] = c->scal; gc.info[i] = c->info; gc.scal_host[i] = c->scal_host; gc.info_host[i] = c->info_host;
-    }
-    GP_TRY(launch_group_collect(gc, s));
-  }
+  GP_TRY(closure_collect(na, cl, s));
   GP_HIP(hipStreamSynchronize(s));
   const std::string err_K = std::string(name) + ": Cholesky of the projected K_tilde failed (non-positive pivot)";
   const std::string err_V = std::string(name) + ": Cholesky of V_b failed (non-positive pivot)";

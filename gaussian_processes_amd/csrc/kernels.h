@@ -174,16 +174,7 @@ int launch_dk_metric(double* H, int64_t ldh, const double* Cos, int64_t ldc, con
                      const double* dq1, const double* dq2, int n1, int n2, hipStream_t s);
 int launch_fill(double* x, int64_t n, double v, hipStream_t s);
 
-// ---- projected.hip: element-wise pieces of the fused truncated-rank closure (gpfit_fit_eval_projected)
-int launch_proj_moments(const double* Bp, const double* Kb, const double* aV, int64_t ld, int nb, const double* mb,
-                        const double* Kvec, const double* r, int n, double A, double lambda0, double* lam_m,
-                        double* lam_var, double* f, double* gm, double* gv, double* part, double* out3, hipStream_t s);
-int launch_proj_ga(const double* Kb, const double* aV, int64_t ld, int nb, int n, int np, const double* gm,
-                   const double* gv, const double* mb, double* Ga, hipStream_t s);
-int launch_proj_gkb(const double* Bp, int64_t ld, int nb, int n, int np, const double* gv, double* GaKi, hipStream_t s);
-int launch_proj_gktb(const double* Ki, const double* P1, const double* P2, int64_t ld, int nb, const double* b, double* G,
-                     hipStream_t s);
-int launch_proj_trace(const double* A, int64_t lda, int n, double* out, hipStream_t s);
+// ---- projected.hip (the element-wise passes of the truncated-rank and sparse closures: ProjGroupT below)
 // fused E-step in the projected basis (gpfit_estep_projected): per-row scalars s = A sqrt(f), u = A^2 f (a m) + A (r - f)
 // over nrows >= n rows (zero on the padding); then Y = diag(s) aL zero-padded to [nrows][ld] (nrows a multiple of
 // 32) with the slice sums of aL^T u in part[nrows / 32][npc]
@@ -324,8 +315,14 @@ int launch_symv_lower_group(int n_units, PerUnit<double*> A, int64_t lda, int n,
                             hipStream_t s);
 int launch_dot_group(int n_units, PerUnit<double*> x, PerUnit<double*> y, int n, PerUnit<double*> out, hipStream_t s);
 int launch_proj_trace_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, PerUnit<double*> out, hipStream_t s);
-// the operands of the element-wise passes of the projected closures, per unit (n training points padded to np rows, the
-// padded basis size nb = the leading dimension ld): launch_proj_moments, _ga, _gkb, _gktb for the group
+// the operands of the element-wise passes of the projected closures (gpfit_fit_eval_projected: one unit, a = B;
+// gpfit_fit_eval_sparse / _batch: a = K_b K~_b^-1), per unit -- n training points padded to np rows, the padded basis
+// size nb = the leading dimension ld:
+//   moments  lam_m = a m_b, lam_var = Kvec - rowsum(a o K_b) + rowsum(aV o a), f, g_m = A (r - f), g_v = -A^2 f / 2;
+//            out3 = {r . lam_m, sum r, sum f} through part (3 ceil(n / 4) doubles), added in block order
+//   ga       G_a = g_m m_b^T - diag(g_v) K_b + 2 diag(g_v) aV                        (rows >= n zero)
+//   gktb     G = 1/2 K~_b^-1 - 1/2 b b^T - 1/2 P1 + P2        (P1 = K~_b^-1 V_b K~_b^-1, P2 = a^T G_a K~_b^-1)
+//   gkb      G_Kb = diag(g_v) a - G_a K~_b^-1, in place on GaKi                     (rows >= n zero)
 struct ProjGroupT {
   int n_units, n, np, nb;
   int64_t ld;
@@ -333,7 +330,7 @@ struct ProjGroupT {
   PerUnit<double> A, lambda0;
   PerUnit<double*> am, Kb, aV, mb, Kvec, lam_m, lam_var, f, gm, gv, part, out3;   // moments (am: a = K_b K~_b^-1, or B)
   PerUnit<double*> Ga, GaKi;                                                      // G_a ; G_a K~_b^-1 -> G_Kb in place
-  PerUnit<double*> Ki, P1, P2, bvec, G;                                           // G_K~b
+  PerUnit<double*> Ki, P1, P2, bvec, mkm, G;                                      // b = K~_b^-1 m_b, m_b . b ; G_K~b
 };
 int launch_proj_moments_group(const ProjGroupT& g, hipStream_t s);
 int launch_proj_ga_group(const ProjGroupT& g, hipStream_t s);

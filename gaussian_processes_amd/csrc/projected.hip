@@ -1,16 +1,16 @@
-// Element-wise pieces of the fused truncated-rank (B-projected) M-step closure
-// (gpfit_fit_eval_projected, fit.hip): moments / rate / likelihood over the N x n projected
-// matrices, the adjoint assembly, and the small n x n combinations.  fp64 only (the reference's
+// Element-wise pieces of the fused truncated-rank and sparse M-step closures (gpfit_fit_eval_projected,
+// gpfit_fit_eval_sparse and its _batch form; fit.hip: projected_adjoints): moments / rate / likelihood over the N x n
+// projected matrices, the adjoint assembly, and the small n x n combinations.  fp64 only (the reference's
 // precision; utils.py:31-33).
 #include "kernels.h"
 
 namespace gpfit {
 
-// One wave per training point i (utils.py:1090, 1101, 1138 with a = B):
-//   lam_m = B_i . m_b,  lam_var = Kvec_i - B_i . Kb_i + aV_i . B_i,  f = exp(A lam_m + A^2/2 lam_var + lambda0)
+// One wave per training point i (utils.py:1090, 1101, 1138; Bp: the matrix a of the moments, B or K_b K~_b^-1):
+//   lam_m = a_i . m_b,  lam_var = Kvec_i - a_i . Kb_i + aV_i . a_i,  f = exp(A lam_m + A^2/2 lam_var + lambda0)
 //   g_m = A (r - f),  g_v = -A^2 f / 2;   block partial sums of r lam_m, r, f -> part[3][gridDim.x]
-// (the bodies below are shared by the single kernels and the unit-batched ones of gpfit_fit_eval_sparse_batch, which put
-// the unit on a grid dimension the single form leaves free: the same sums in the same order, hence the same bits)
+// (each body below is written for one unit; its kernel puts the unit on a grid dimension the body leaves free, so a unit's
+// sums run in the same order whatever else is in the launch: the same bits alone and in any group)
 __device__ __forceinline__ void proj_moments_body(const double* __restrict__ Bp, const double* __restrict__ Kb,
                                                   const double* __restrict__ aV, int64_t ld, int nb,
                                                   const double* __restrict__ mb, const double* __restrict__ Kvec,
@@ -55,16 +55,6 @@ __device__ __forceinline__ void proj_moments_body(const double* __restrict__ Bp,
     part[(int64_t)q * gridDim.x + blockIdx.x] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
   }
 }
-__global__ __launch_bounds__(256) void proj_moments_kernel(const double* __restrict__ Bp, const double* __restrict__ Kb,
-                                                            const double* __restrict__ aV, int64_t ld, int nb,
-                                                            const double* __restrict__ mb, const double* __restrict__ Kvec,
-                                                            const double* __restrict__ r, int n, double A, double lambda0,
-                                                            double* __restrict__ lam_m, double* __restrict__ lam_var,
-                                                            double* __restrict__ f, double* __restrict__ gm,
-                                                            double* __restrict__ gv, double* __restrict__ part) {
-  __shared__ double red[3][4];
-  proj_moments_body(Bp, Kb, aV, ld, nb, mb, Kvec, r, n, A, lambda0, lam_m, lam_var, f, gm, gv, part, red);
-}
 
 // out[q] = sum of part[q][0..nblk) in index order (deterministic), q = 0..2
 __device__ __forceinline__ void proj_sum3_body(const double* __restrict__ part, int nblk, double* __restrict__ out, double* red) {
@@ -81,10 +71,6 @@ __device__ __forceinline__ void proj_sum3_body(const double* __restrict__ part, 
     __syncthreads();
   }
 }
-__global__ __launch_bounds__(256) void proj_sum3_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out) {
-  __shared__ double red[256];
-  proj_sum3_body(part, nblk, out, red);
-}
 
 // G_a = g_m m_b^T - diag(g_v) K_b + 2 diag(g_v) aV   (N x nb, rows >= n left zero)
 __device__ __forceinline__ void proj_ga_body(const double* __restrict__ Kb, const double* __restrict__ aV, int64_t ld, int nb,
@@ -95,12 +81,6 @@ __device__ __forceinline__ void proj_ga_body(const double* __restrict__ Kb, cons
   const int64_t o = (int64_t)i * ld + j;
   Ga[o] = (i < n) ? gm[i] * mb[j] - gv[i] * Kb[o] + 2.0 * gv[i] * aV[o] : 0.0;
 }
-__global__ __launch_bounds__(256) void proj_ga_kernel(const double* __restrict__ Kb, const double* __restrict__ aV,
-                                                       int64_t ld, int nb, int n, const double* __restrict__ gm,
-                                                       const double* __restrict__ gv, const double* __restrict__ mb,
-                                                       double* __restrict__ Ga) {
-  proj_ga_body(Kb, aV, ld, nb, n, gm, gv, mb, Ga);
-}
 
 // G_Kb = diag(g_v) B - G_a K~_b^-1, in place on the product (rows >= n left zero)
 __device__ __forceinline__ void proj_gkb_body(const double* __restrict__ Bp, int64_t ld, int nb, int n,
@@ -109,10 +89,6 @@ __device__ __forceinline__ void proj_gkb_body(const double* __restrict__ Bp, int
   if (j >= nb) return;
   const int64_t o = (int64_t)i * ld + j;
   GaKi[o] = (i < n) ? gv[i] * Bp[o] - GaKi[o] : 0.0;
-}
-__global__ __launch_bounds__(256) void proj_gkb_kernel(const double* __restrict__ Bp, int64_t ld, int nb, int n,
-                                                        const double* __restrict__ gv, double* __restrict__ GaKi) {
-  proj_gkb_body(Bp, ld, nb, n, gv, GaKi);
 }
 
 // G_K~b = 1/2 K~_b^-1 - 1/2 b b^T - 1/2 (K~_b^-1 V_b K~_b^-1) + B^T G_a K~_b^-1     (nb x nb)
@@ -123,11 +99,6 @@ __device__ __forceinline__ void proj_gktb_body(const double* __restrict__ Ki, co
   if (j >= nb) return;
   const int64_t o = (int64_t)i * ld + j;
   G[o] = 0.5 * Ki[o] - 0.5 * b[i] * b[j] - 0.5 * P1[o] + P2[o];
-}
-__global__ __launch_bounds__(256) void proj_gktb_kernel(const double* __restrict__ Ki, const double* __restrict__ P1,
-                                                         const double* __restrict__ P2, int64_t ld, int nb,
-                                                         const double* __restrict__ b, double* __restrict__ G) {
-  proj_gktb_body(Ki, P1, P2, ld, nb, b, G);
 }
 
 // out[0] = sum_i A[i][i], i < n
@@ -143,12 +114,8 @@ __device__ __forceinline__ void proj_trace_body(const double* __restrict__ A, in
   }
   if (threadIdx.x == 0) out[0] = red[0];
 }
-__global__ __launch_bounds__(256) void proj_trace_kernel(const double* __restrict__ A, int64_t lda, int n, double* __restrict__ out) {
-  __shared__ double red[256];
-  proj_trace_body(A, lda, n, out, red);
-}
 
-// ---- the unit-batched forms (gpfit_fit_eval_sparse_batch; kernels.h: ProjGroupT): unit = the free grid dimension
+// ---- the kernels (kernels.h: ProjGroupT; a single closure is the group of one): unit = the free grid dimension
 __global__ __launch_bounds__(256) void proj_moments_group_kernel(PerUnit<double*> am, PerUnit<double*> Kb, PerUnit<double*> aV,
                                                                   int64_t ld, int nb, PerUnit<double*> mb, PerUnit<double*> Kvec,
                                                                   PerUnit<const double*> r, int n, PerUnit<double> A,
@@ -214,39 +181,6 @@ int launch_proj_gktb_group(const ProjGroupT& g, hipStream_t s) {
 }
 int launch_proj_trace_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, PerUnit<double*> out, hipStream_t s) {
   hipLaunchKernelGGL(proj_trace_group_kernel, dim3(1, n_units), dim3(256), 0, s, A, lda, n, out);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_proj_moments(const double* Bp, const double* Kb, const double* aV, int64_t ld, int nb, const double* mb,
-                        const double* Kvec, const double* r, int n, double A, double lambda0, double* lam_m,
-                        double* lam_var, double* f, double* gm, double* gv, double* part, double* out3, hipStream_t s) {
-  const int nblk = (n + 3) / 4;
-  hipLaunchKernelGGL(proj_moments_kernel, dim3(nblk), dim3(256), 0, s, Bp, Kb, aV, ld, nb, mb, Kvec, r, n, A, lambda0,
-                     lam_m, lam_var, f, gm, gv, part);
-  hipLaunchKernelGGL(proj_sum3_kernel, dim3(1), dim3(256), 0, s, part, nblk, out3);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-int launch_proj_ga(const double* Kb, const double* aV, int64_t ld, int nb, int n, int np, const double* gm,
-                   const double* gv, const double* mb, double* Ga, hipStream_t s) {
-  hipLaunchKernelGGL(proj_ga_kernel, dim3((nb + 255) / 256, np), dim3(256), 0, s, Kb, aV, ld, nb, n, gm, gv, mb, Ga);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-int launch_proj_gkb(const double* Bp, int64_t ld, int nb, int n, int np, const double* gv, double* GaKi, hipStream_t s) {
-  hipLaunchKernelGGL(proj_gkb_kernel, dim3((nb + 255) / 256, np), dim3(256), 0, s, Bp, ld, nb, n, gv, GaKi);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-int launch_proj_gktb(const double* Ki, const double* P1, const double* P2, int64_t ld, int nb, const double* b, double* G,
-                     hipStream_t s) {
-  hipLaunchKernelGGL(proj_gktb_kernel, dim3((nb + 255) / 256, nb), dim3(256), 0, s, Ki, P1, P2, ld, nb, b, G);
-  GP_HIP(hipGetLastError());
-  return 0;
-}
-int launch_proj_trace(const double* A, int64_t lda, int n, double* out, hipStream_t s) {
-  hipLaunchKernelGGL(proj_trace_kernel, dim3(1), dim3(256), 0, s, A, lda, n, out);
   GP_HIP(hipGetLastError());
   return 0;
 }

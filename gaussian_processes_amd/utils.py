@@ -1437,6 +1437,34 @@ def _closure_projected(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params):
     return _closure_projected_steps(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params)
 
 
+def _closure_adjoints(K_b, K_tilde_b, Kvec, a, m_b, V_b, r, f_params):
+    """The algebra the two step-by-step closures share, from the projected kernel objects to the adjoints of the loss
+    (docstring of ``_closure_projected_steps``).  ``a``: the matrix of the moments -- B for the truncated-rank closure, None
+    for the sparse one's a = K_b K~_b^-1.  Returns the loss and what the callers lift to their W matrices:
+    (loss, g_v, G_Kb, G_Kb~)."""
+    A = math.exp(_scalar(f_params['logA']))
+    lambda0 = _scalar(_lambda0_of(f_params))
+    Ki = spd_inverse(K_tilde_b)                                                     # :2067
+    if a is None:
+        a = matmul(K_b, Ki)                                                         # :2068
+    aV = matmul(a, V_b)
+    lambda_m = matmul(a, m_b)                                                       # :1090
+    lambda_var = Kvec - torch.sum(a * K_b, 1) + torch.sum(aV * a, 1)                 # :1101
+    f_mean = torch.exp(A * lambda_m + 0.5 * A * A * lambda_var + lambda0)            # :1138
+    loglik = A * torch.dot(r, lambda_m) + lambda0 * torch.sum(r) - torch.sum(f_mean)  # :1243
+    b = matmul(Ki, m_b)
+    KiV = matmul(Ki, V_b)
+    KL = (-0.5 * log_det(V_b, 'V', ignore_warning=True) + 0.5 * log_det(K_tilde_b, 'K_tilde', ignore_warning=True)
+          + 0.5 * torch.dot(m_b, b) + 0.5 * torch.trace(KiV))                        # :1326
+    g_m = A * (r - f_mean)
+    g_v = -0.5 * A * A * f_mean
+    G_a = torch.outer(g_m, m_b) - g_v[:, None] * K_b + 2.0 * g_v[:, None] * aV
+    G_aKi = matmul(G_a, Ki)
+    G_Kb = g_v[:, None] * a - G_aKi
+    G_Ktb = 0.5 * Ki - 0.5 * torch.outer(b, b) - 0.5 * matmul(KiV, Ki) + matmul(a, G_aKi, transA=True)
+    return -(_scalar(loglik) - _scalar(KL)), g_v, G_Kb, G_Ktb
+
+
 def _closure_projected_steps(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params):
     """Truncated-rank M-step closure (utils.py:2030-2099 with n < n_tilde = n_t, inducing set =
     training set) in adjoint form: the same loss as the reference's B-projected formulation, but
@@ -1462,28 +1490,10 @@ def _closure_projected_steps(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params
     x_m = x[:, mask].contiguous()
     K_tilde = acosker(theta, x_m, x_m, C=C, dC=None, diag=False)
     Kvec = acosker(theta, x_m, x2=None, C=C, dC=None, diag=True)
-    A = math.exp(_scalar(f_params['logA']))
-    lambda0 = _scalar(_lambda0_of(f_params))
     K_b = matmul(K_tilde, B)                                                        # :2049
     K_tilde_b = matmul(B, K_b, transA=True)                                         # :2047
     K_tilde_b = (K_tilde_b + K_tilde_b.T) * 0.5                                     # :2048
-    Ki = spd_inverse(K_tilde_b)                                                     # :2067
-    a = B                                                                           # :2068 (n_tilde == n_t)
-    aV = matmul(a, V_b)
-    lambda_m = matmul(a, m_b)                                                       # :1090
-    lambda_var = Kvec - torch.sum(a * K_b, 1) + torch.sum(aV * a, 1)                 # :1101
-    f_mean = torch.exp(A * lambda_m + 0.5 * A * A * lambda_var + lambda0)            # :1138
-    loglik = A * torch.dot(r, lambda_m) + lambda0 * torch.sum(r) - torch.sum(f_mean)  # :1243
-    b = matmul(Ki, m_b)
-    KiV = matmul(Ki, V_b)
-    KL = (-0.5 * log_det(V_b, 'V', ignore_warning=True) + 0.5 * log_det(K_tilde_b, 'K_tilde', ignore_warning=True)
-          + 0.5 * torch.dot(m_b, b) + 0.5 * torch.trace(KiV))                        # :1326
-    g_m = A * (r - f_mean)
-    g_v = -0.5 * A * A * f_mean
-    G_a = torch.outer(g_m, m_b) - g_v[:, None] * K_b + 2.0 * g_v[:, None] * aV
-    G_aKi = matmul(G_a, Ki)
-    G_Kb = g_v[:, None] * a - G_aKi
-    G_Ktb = 0.5 * Ki - 0.5 * torch.outer(b, b) - 0.5 * matmul(KiV, Ki) + matmul(a, G_aKi, transA=True)
+    loss, g_v, G_Kb, G_Ktb = _closure_adjoints(K_b, K_tilde_b, Kvec, B, m_b, V_b, r, f_params)   # a = B (:2068, n_tilde == n_t)
     W = matmul(matmul(B, G_Ktb) + G_Kb, B, transB=True)
     W = ((W + W.T) * 0.5).contiguous()
     gvec = (-g_v).contiguous()
@@ -1494,7 +1504,7 @@ def _closure_projected_steps(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params
     _lib.check(lib.gpfit_grad_pullback(eng._ctx, _stream(), th, rows, cols, xc.data_ptr(), xc.stride(0), xc.shape[0],
                                        W.data_ptr(), W.stride(0), gvec.data_ptr(), out), "gpfit_grad_pullback")
     grad = {k: out[i] for i, k in enumerate(THETA_KEYS)}
-    return -(_scalar(loglik) - _scalar(KL)), grad
+    return loss, grad
 
 
 def _closure_sparse(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params):
@@ -1651,28 +1661,10 @@ def _closure_sparse_steps(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_p
     K_tilde = acosker(theta, xt_m, xt_m, C=C, dC=None, diag=False)
     Kvec = acosker(theta, x_m, x2=None, C=C, dC=None, diag=True)
     K = acosker(theta, x_m, xt_m, C=C, dC=None, diag=False)                          # :968-990
-    A = math.exp(_scalar(f_params['logA']))
-    lambda0 = _scalar(_lambda0_of(f_params))
     K_b = matmul(K, B)                                                              # :2049
     K_tilde_b = matmul(B, matmul(K_tilde, B), transA=True)                          # :2047
     K_tilde_b = (K_tilde_b + K_tilde_b.T) * 0.5                                     # :2048
-    Ki = spd_inverse(K_tilde_b)                                                     # :2067
-    a = matmul(K_b, Ki)                                                             # :2068
-    aV = matmul(a, V_b)
-    lambda_m = matmul(a, m_b)                                                       # :1090
-    lambda_var = Kvec - torch.sum(a * K_b, 1) + torch.sum(aV * a, 1)                 # :1101
-    f_mean = torch.exp(A * lambda_m + 0.5 * A * A * lambda_var + lambda0)            # :1138
-    loglik = A * torch.dot(r, lambda_m) + lambda0 * torch.sum(r) - torch.sum(f_mean)  # :1243
-    b = matmul(Ki, m_b)
-    KiV = matmul(Ki, V_b)
-    KL = (-0.5 * log_det(V_b, 'V', ignore_warning=True) + 0.5 * log_det(K_tilde_b, 'K_tilde', ignore_warning=True)
-          + 0.5 * torch.dot(m_b, b) + 0.5 * torch.trace(KiV))                        # :1326
-    g_m = A * (r - f_mean)
-    g_v = -0.5 * A * A * f_mean
-    G_a = torch.outer(g_m, m_b) - g_v[:, None] * K_b + 2.0 * g_v[:, None] * aV
-    G_aKi = matmul(G_a, Ki)
-    G_Kb = g_v[:, None] * a - G_aKi
-    G_Ktb = 0.5 * Ki - 0.5 * torch.outer(b, b) - 0.5 * matmul(KiV, Ki) + matmul(a, G_aKi, transA=True)
+    loss, g_v, G_Kb, G_Ktb = _closure_adjoints(K_b, K_tilde_b, Kvec, None, m_b, V_b, r, f_params)   # a = K_b K~_b^-1 (:2068)
     # square part: W~ against dK~_p
     Wt = matmul(matmul(B, G_Ktb), B, transB=True)
     Wt = ((Wt + Wt.T) * 0.5).contiguous()
@@ -1700,7 +1692,7 @@ def _closure_sparse_steps(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_p
     for k in DC_KEYS:
         grad[k] += _scalar(torch.sum(dC[k] * M))
     grad['sigma_0'] += s0 * (2.0 * out3[0] + out3[1] + out3[2]) + 2 * s0 * _scalar(gvec.sum())
-    return -(_scalar(loglik) - _scalar(KL)), grad
+    return loss, grad
 
 
 @torch.no_grad()
