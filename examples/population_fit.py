@@ -1,12 +1,13 @@
 """Several cells recorded on the same stimuli, fitted together: ``utils.varGP_cells`` (the E-step chains of the cells of
-a wave go out as ONE device call per EM iteration, and the sparse M-step closures of their L-BFGS as one call whenever
-the wave's fits meet) or, with ``--loop``, ``utils.varGP`` cell after cell.  Both give the same numbers per cell, bit for
-bit.
+a wave go out as ONE device call per EM iteration, and the M-step closures of their L-BFGS -- sparse, or truncated-rank
+when ``--ntilde`` equals ``--n`` and the tolerance drops eigenvalues -- as one call whenever the wave's fits meet) or, with
+``--loop``, ``utils.varGP`` cell after cell.  Both give the same numbers per cell, bit for bit.
 
     python examples/population_fit.py --cells 4                      # four synthetic cells through varGP_cells
     python examples/population_fit.py --cells 4 --loop               # the same fits one after another
     python examples/population_fit.py --n 3160 --ntilde 2100 --d 256 --cells 16 --maxiter 30 --nestep 10 --nmstep 10 \\
         --nfstep 4 --repeat 3                                        # the lab's shape (scripts/lab_fit_times.py's settings)
+    python examples/population_fit.py --n 1024 --ntilde 1024 --d 256 --cells 16   # inducing set = training set: truncated rank
 
 Per repetition it prints the wall time of all fits and, averaged over the cells, the phase times ``varGP`` reports;
 for ``varGP_cells`` also how many units each chain call and each closure call carried and how long those calls took.
@@ -103,5 +104,8 @@ for rep in range(max(1, args.repeat)):
                  f"cell -> M-step time per cell {mstep:.3f}s (own part {ph['M-steps'] - in_closure:.3f} + share of the calls "
                  f"{sum(csecs) / args.cells:.3f})")
     print(line + (f" | FAILED cells {failed}" if failed else ""), flush=True)
+kept = [int(fit["B"].shape[1]) for fit, _ in fits]
+regime = "sparse" if args.ntilde < args.n else ("truncated rank" if max(kept) < args.ntilde else "full rank")
+print(f"eigen-directions kept per cell: {min(kept)} .. {max(kept)} of {args.ntilde} ({regime})")
 lm = [float(fit["values_track"]["loss_track"]["logmarginal"][-1]) for fit, _ in fits]
 print("final logmarginal per cell:", " ".join(f"{v:.4f}" for v in lm))

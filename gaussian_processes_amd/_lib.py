@@ -70,6 +70,8 @@ _SIGS = {
     "gpfit_fit_eval_batch_f32": (i32, [vp, i32, vp, pd, pd, pd, i32, i32, vp, i64, i64, vp, vp, vp, i64, pd, pd, i32, pd,
                                        ctypes.POINTER(i32)]),
     "gpfit_fit_eval_projected": (i32, [vp, vp, pd, pd, pd, i32, i32, vp, i64, i64, vp, vp, i64, i64, vp, vp, i64, f64, f64, pd]),
+    "gpfit_fit_eval_projected_batch": (i32, [vp, i32, vp, pd, pd, pd, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, pd, pd,
+                                             pd, ctypes.POINTER(i32)]),
     "gpfit_fit_eval_sparse": (i32, [vp, vp, pd, pd, pd, i32, i32, vp, i64, i64, vp, i64, i64, vp, vp, i64, i64, vp, vp, i64,
                                     f64, f64, pd]),
     "gpfit_fit_eval_sparse_batch": (i32, [vp, i32, vp, pd, pd, pd, i32, i32, vp, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp,

@@ -2,8 +2,8 @@
 // blocked Cholesky built from MFMA GEMMs, and the fused unit of work (one evaluation of the
 // reference's M-step closure, utils.py:2017-2112) in the original-basis Cholesky formulation
 // (DESIGN.md section 3).  The fused entry points -- gpfit_fit_eval, gpfit_fit_eval_batch,
-// gpfit_grad_pullback, gpfit_fit_eval_projected, gpfit_fit_eval_sparse and its group form
-// gpfit_fit_eval_sparse_batch (one body) -- are each a short sequence of
+// gpfit_grad_pullback, gpfit_fit_eval_projected and gpfit_fit_eval_sparse with their group forms
+// gpfit_fit_eval_projected_batch / gpfit_fit_eval_sparse_batch (one body each) -- are each a short sequence of
 // the shared stages defined once below ("shared stages of the fused closures": admission, kernel build,
 // the vectors behind the factor, the mixed-precision hand-over, the pull-back to the metric, the
 // n_kept x n_kept algebra of the truncated-rank closures, the host assembly of the 16 outputs); what
@@ -577,7 +577,7 @@ static int dev_alloc(gpfit_ctx* c, T** p, size_t count) {
 // The fused entry points are short sequences of the stages below (file-local functions on the context, the
 // stream and plain pointers: nothing here allocates or dispatches indirectly -- the host enqueue time of a unit is
 // part of its measured time at N <= 2048).  Which entry point uses which:
-//   stage                                   fit_eval  _batch  grad_pullback  _projected  _sparse (single and _batch)
+//   stage                                   fit_eval  _batch  grad_pullback  _projected  _sparse (each single and _batch)
 //   admit                                      x        x          x             x          x
 //   build_kernel                               x        x          x             x      (its parts)
 //   solve_mean, post_join_args,
@@ -768,7 +768,7 @@ static int pullback_to_metric(gpfit_ctx* c, Lane lane, const double* W, const do
 }
 
 // ---- the n_kept x n_kept algebra of the truncated-rank closures (nb = n_kept padded; leading dimension nb), in the
-// scratch matrices S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV of each unit's context -- for a list of cnt units (the sparse
+// scratch matrices S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV of each unit's context -- for a list of cnt units (the
 // closures of a group; one unit: the single closures), every small kernel one launch for the list (kernels.h).
 template <typename T, typename F>
 static PerUnit<T> per_unit(int cnt, F&& at) {
@@ -1480,98 +1480,198 @@ static int grad_pullback_impl(gpfit_ctx* c, void* stream, const double* theta, i
 // the device in one call (the algebra of utils._closure_projected).  Every
 // N x n matrix lives zero-padded to nb = ceil(n / 128) 128 columns in one of the context's N x N
 // work matrices; the n x n ones carry the identity on their padding (log-determinants and solves
-// are unaffected, the padding of G_K~b cancels to zero).  The closure of ONE unit written through the list forms (every
-// small kernel its unit-batched launch, the products on lists of one), on this closure's own choice of work matrices.
-static int fit_eval_projected_impl(gpfit_ctx* c, void* stream, const double* theta, const double* lower,
-                                   const double* upper, int n_rows, int n_cols, const double* X, int64_t ldx, int64_t N,
-                                   const double* r, const double* B, int64_t ldb, int64_t n_kept, const double* m_b,
-                                   const double* V_b, int64_t ldvb, double logA, double lambda0, double* out_host) {
+// are unaffected, the padding of G_K~b cancels to zero).
+// ONE body for gpfit_fit_eval_projected (the group of one) and gpfit_fit_eval_projected_batch: nu independent units, each
+// on its own context and this closure's own choice of work matrices, all on the caller's stream with one synchronisation
+// at the end -- the structure of fit_eval_sparse_group_impl below.  Unit by unit: the kernel build (the masked pixel count
+// differs from unit to unit, and the Gram launch fills the chip alone) and the pull-back (the same, and its slabs go to the
+// unit's own Mpart).  For the list: everything between them -- the 2 nu factorisations as one lock-step recursion, the
+// products through product / gemm_splitk_list on the list of units, every small kernel as its unit-batched form.  A unit
+// runs the same products in the same order with the same slab counts and the same reduction order in every small kernel
+// whatever else is in the group, so its 16 outputs have the same bits alone and in any group.  Two things depend on a
+// context's capacity -- how many k slabs its scratch holds (gemm_splitk_list) and the route of the lift -- so the
+// contexts of one call have one capacity (refused otherwise): the route is decided once per call from shared values
+// and is the one each unit takes alone on its context.
+// Returns 0, or < 0 before anything is enqueued or any output written; rc_out[u]: 0, -2 (theta outside the unit's limits:
+// the infinite loss / gradients in its outputs, nothing enqueued for it) or the LAPACK info of a failed pivot.
+static int fit_eval_projected_group_impl(const char* name, gpfit_ctx* const* cs, int nu, void* stream, const double* theta6,
+                                         const double* lower6, const double* upper6, int n_rows, int n_cols,
+                                         const double* const* X, int64_t ldx, int64_t N, const double* const* r,
+                                         const double* const* B, const int64_t* ldb, const int64_t* n_kept,
+                                         const double* const* m_b, const double* const* V_b, const int64_t* ldvb,
+                                         const double* logA, const double* lambda0, double* out_host, int* rc_out) {
   using R = double;
-  if (!c || !theta || !X || !r || !B || !m_b || !V_b || !out_host || N <= 0 || n_kept <= 0 || n_kept > N) {
-    set_error("gpfit_fit_eval_projected: bad argument");
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(name) + ": " + why);
     return -3;
+  };
+  if (nu < 1 || nu > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+  if (!cs || !theta6 || !X || !r || !B || !ldb || !n_kept || !m_b || !V_b || !ldvb || !logA || !lambda0 || !out_host || !rc_out ||
+      N <= 0 || (lower6 == nullptr) != (upper6 == nullptr))
+    return refuse("bad argument");
+  const int n = (int)N, np = (int)round_up(N, TILE), nb = (int)round_up(n_kept[0], TILE);
+  // ---- admission of every unit before anything is enqueued or written
+  struct Unit { gpfit_ctx* c; int u, d, dp, nk; Theta th; double A; };
+  Unit un[CHAIN_MAXU];
+  bool outside[CHAIN_MAXU];
+  int na = 0;
+  for (int u = 0; u < nu; ++u) {
+    const std::string unit = nu > 1 ? "unit " + std::to_string(u) + ": " : std::string();
+    if (!cs[u] || !X[u] || !r[u] || !B[u] || !m_b[u] || !V_b[u]) return refuse(unit + "null context or operand");
+    if (n_kept[u] <= 0 || n_kept[u] > N)
+      return refuse(unit + "bad argument: n_kept " + std::to_string(n_kept[u]) + " is not within 1 .. N = " + std::to_string(N));
+    if (ldb[u] < n_kept[u] || ldvb[u] < n_kept[u]) return refuse(unit + "bad leading dimension");
+    if (cs[u]->device != cs[0]->device) return refuse("the contexts of one call must live on one device");
+    for (int v = 0; v < u; ++v)
+      if (cs[v] == cs[u]) return refuse("every unit needs a context of its own");
+    if (cs[u]->pend.active)
+      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
+    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+    if (round_up(n_kept[u], TILE) != nb)
+      return refuse(unit + "round_up(n_kept, 128) = " + std::to_string(round_up(n_kept[u], TILE)) + " differs from unit 0's " +
+                    std::to_string(nb) + " (group the units by padded size)");
+    // the slabs of the projections and the route of the lift depend on the capacity: one capacity, one route per call
+    if (cs[u]->np_cap != cs[0]->np_cap)
+      return refuse(unit + "the context's capacity of " + std::to_string(cs[u]->np_cap) + " stimuli differs from unit 0's " +
+                    std::to_string(cs[0]->np_cap) + " (group the units by the capacity of their contexts)");
   }
-  GP_CTX_ENTER(c, "gpfit_fit_eval_projected");
+  for (int u = 0; u < nu; ++u) {
+    double scratch_out[OUT_COUNT];
+    Admitted ad;
+    const int rc = admit(cs[u], name, nu > 1 ? "a context's" : "the context", theta6 + 6 * u, lower6 ? lower6 + 6 * u : nullptr,
+                         upper6 ? upper6 + 6 * u : nullptr, n_rows, n_cols, np, scratch_out, &ad);
+    outside[u] = rc == -2;
+    if (rc == -2) continue;
+    if (rc != 0) return rc;
+    Unit& q = un[na++];
+    q.c = cs[u]; q.u = u; q.d = ad.d; q.dp = ad.dp; q.nk = (int)n_kept[u]; q.th = ad.th; q.A = std::exp(logA[u]);
+  }
+  for (int u = 0; u < nu; ++u) {
+    rc_out[u] = outside[u] ? -2 : 0;
+    if (outside[u]) fill_out_of_box(out_host + OUT_COUNT * u);
+  }
+  if (na == 0) return 0;
+  DeviceGuard device_guard(cs[0]->device);
   hipStream_t s = (hipStream_t)stream;
-  const int n = (int)N, np = (int)round_up(N, TILE), nk = (int)n_kept, nb = (int)round_up(n_kept, TILE);
-  Admitted ad;
-  GP_TRY(admit(c, "gpfit_fit_eval_projected", "the context", theta, lower, upper, n_rows, n_cols, np, out_host, &ad));
-  const int d = ad.d, dp = ad.dp;
-  const Theta th = ad.th;
-  const double A = std::exp(logA);
   const int64_t ld = np, lb = nb;
-  c->lv_valid = false; c->lv32_valid = false;
-  c->side_ev_next = 0;
-  const Lane lane = main_lane(c, s);
+  gpfit_ctx* cl[CHAIN_MAXU];
+  int nkl[CHAIN_MAXU], dl[CHAIN_MAXU];
+  const double* mbl[CHAIN_MAXU];
+  for (int i = 0; i < na; ++i) {
+    gpfit_ctx* c = un[i].c;
+    cl[i] = c; nkl[i] = un[i].nk; dl[i] = un[i].d; mbl[i] = m_b[un[i].u];
+    c->lv_valid = false; c->lv32_valid = false;
+    c->side_ev_next = 0;
+  }
+  gpfit_ctx* c0 = cl[0];
+  const Lane lane = main_lane(c0, s);   // every launch on the caller's stream with the leader's workspace
   ++g_eval_count;
-  prof_begin(c);
-  struct ProfGuard { gpfit_ctx* c; ~ProfGuard() { prof_end(c); } } prof_guard{c};
-  double *Kt = c->Kbuf, *Bp = c->Lbuf, *Kb = c->Libuf, *aV = c->Tbuf, *Ga = c->Zbuf, *GaKi = c->Tmp, *W = c->Wbuf;
-  double *S1 = c->Vbuf, *S2 = c->LVbuf, *S3 = c->LiVbuf, *S4 = c->TmpV;   // n x n scratch (leading dimension nb)
-  double *mbp = c->mpad, *bvec = c->yv, *gm = c->dq1, *gv = c->dq2;
-  auto one = [](auto v) { return per_unit<decltype(v)>(1, [&](int) { return v; }); };
-  const PerUnit<int> nks = one(nk);
-  GP_TRY(closure_prepare(1, &c, &d, &nk, &m_b, nb, s));
-  // ---- kernel build (as the full-rank unit): C, X masked, cos, Kvec, q, and K~ stored in full by the tiles
-  // themselves (mirror): it is multiplied from the left below
-  GP_TRY(build_kernel<R>(c, lane, th, d, dp, n_rows, n_cols, X, ldx, n, np, 1));
+  prof_begin(c0);
+  struct ProfGuard { gpfit_ctx* c; ~ProfGuard() { prof_end(c); } } prof_guard{c0};
+  // The work matrices, per context (as ever): Kt = Kbuf, Bp = Lbuf, Kb = Libuf, aV = Tbuf, Ga = Zbuf, GaKi = Tmp, W = Wbuf;
+  // the V_b chain in Abuf, Wbuf, Zbuf, Tmp; P2 = Abuf; S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV (n x n, leading dimension nb);
+  // mbp = mpad, bvec = yv, gm = dq1, gv = dq2.
+  auto of = [&](double* gpfit_ctx::*X_) { return per_unit<double*>(na, [&](int i) { return cl[i]->*X_; }); };
+  auto cof = [&](double* gpfit_ctx::*X_) { return per_unit<const double*>(na, [&](int i) { return cl[i]->*X_; }); };
+  auto scal_of = [&](int slot) { return per_unit<double*>(na, [&](int i) { return cl[i]->scal + slot; }); };
+  auto all = [&](double* gpfit_ctx::*X_, int64_t ld_) { return mats(na, ld_, [&](int i) { return cl[i]->*X_; }); };
+  auto same = [&](auto v) { return per_unit<decltype(v)>(na, [&](int) { return v; }); };
+  const PerUnit<int> nks = per_unit<int>(na, [&](int i) { return nkl[i]; });
+  GP_TRY(closure_prepare(na, cl, dl, nkl, mbl, nb, s));   // pixel lists, info words, the padded m_b, bv / wl cleared
+  // ---- unit by unit, the kernel build (as the full-rank unit): C, X masked, cos, Kvec, q, and K~ stored in full by the
+  // tiles themselves (mirror): it is multiplied from the left below.  (The masked pixel count differs per unit.)
+  for (int i = 0; i < na; ++i)
+    GP_TRY(build_kernel<R>(cl[i], lane, un[i].th, un[i].d, un[i].dp, n_rows, n_cols, X[un[i].u], ldx, n, np, 1));
   // ---- projection (utils.py:2047-2049): K_b = K~ B, K~_b = sym(B^T K_b)
-  GP_TRY(launch_pad_copy_group(1, one(B), one(ldb), n, nks, one(Bp), lb, np, nb, s));
-  // (skinny products with a long k are cut into k slabs, gemm_splitk_list; Wbuf is free until the adjoints)
-  double* const part = c->Wbuf;
-  const int64_t part_elems = (int64_t)c->np_cap * c->np_cap;
-  GP_TRY(gemm_splitk_list(lane, {np, nb, np}, 1.0, plain(mat(Kt, ld)), plain(mat(Bp, lb)), mat(Kb, lb), &part, &part_elems));
-  GP_TRY(gemm_splitk_list(lane, {nb, nb, np}, 1.0, trans(mat(Bp, lb)), plain(mat(Kb, lb)), mat(S4, lb), &part, &part_elems));
-  GP_TRY(launch_symmetrize_avg_group(1, one(S4), lb, nks, s));                                 // :2048
-  GP_TRY(launch_pack_lower_group(1, one((const double*)S4), one(lb), nks, one(S1), lb, nb, s));
-  // (log|V_b| of :1326: V_b is factored together with K~_b -- one lock-step recursion on this stream, in four work
-  // matrices nothing else needs before the adjoints: Abuf, Wbuf, Zbuf, Tmp)
-  GP_TRY(launch_pack_lower_group(1, one(V_b), one(ldvb), nks, one(c->Abuf), lb, nb, s));
-  const ProjChain vchain{c->Abuf, c->Wbuf, c->Zbuf, c->Tmp};
-  GP_TRY(projected_factor(lane, 1, &c, &V_b, &ldvb, &nk, nb, &vchain));
+  const Mat<R> Kt = all(&gpfit_ctx::Kbuf, ld), Bp = all(&gpfit_ctx::Lbuf, lb), Kb = all(&gpfit_ctx::Libuf, lb),
+               aV = all(&gpfit_ctx::Tbuf, lb), GaKi = all(&gpfit_ctx::Tmp, lb);
+  const Mat<R> S2 = all(&gpfit_ctx::LVbuf, lb), S3 = all(&gpfit_ctx::LiVbuf, lb), S4 = all(&gpfit_ctx::TmpV, lb);
+  GP_TRY(launch_pad_copy_group(na, per_unit<const double*>(na, [&](int i) { return B[un[i].u]; }),
+                               per_unit<int64_t>(na, [&](int i) { return ldb[un[i].u]; }), n, nks, of(&gpfit_ctx::Lbuf), lb, np, nb, s));
+  // (skinny products with a long k are cut into k slabs, gemm_splitk_list, each unit's in its own scratch; Wbuf is free
+  // until the adjoints)
+  R* part[CHAIN_MAXU];
+  int64_t part_elems[CHAIN_MAXU];
+  for (int i = 0; i < na; ++i) { part[i] = cl[i]->Wbuf; part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap; }
+  GP_TRY(gemm_splitk_list(lane, {np, nb, np}, 1.0, plain(Kt), plain(Bp), Kb, part, part_elems));
+  GP_TRY(gemm_splitk_list(lane, {nb, nb, np}, 1.0, trans(Bp), plain(Kb), S4, part, part_elems));
+  GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::TmpV), lb, nks, s));                                 // :2048
+  GP_TRY(launch_pack_lower_group(na, cof(&gpfit_ctx::TmpV), same(lb), nks, of(&gpfit_ctx::Vbuf), lb, nb, s));
+  {
+    // (log|V_b| of :1326: V_b is factored together with K~_b -- the 2 na chains as one lock-step recursion on this stream,
+    // each unit's V_b chain in four work matrices of its context nothing else needs before the adjoints: Abuf, Wbuf, Zbuf,
+    // Tmp, handed over as the last evaluation left them -- the note at ProjChain)
+    ProjChain vc[CHAIN_MAXU];
+    const double* Vb[CHAIN_MAXU];
+    int64_t ldv[CHAIN_MAXU];
+    for (int i = 0; i < na; ++i) {
+      vc[i] = ProjChain{cl[i]->Abuf, cl[i]->Wbuf, cl[i]->Zbuf, cl[i]->Tmp};
+      Vb[i] = V_b[un[i].u]; ldv[i] = ldvb[un[i].u];
+    }
+    GP_TRY(launch_pack_lower_group(na, per_unit<const double*>(na, [&](int i) { return Vb[i]; }),
+                                   per_unit<int64_t>(na, [&](int i) { return ldv[i]; }), nks, of(&gpfit_ctx::Abuf), lb, nb, s));
+    GP_TRY(projected_factor(lane, na, cl, Vb, ldv, nkl, nb, vc));
+  }
   // K~_b^-1 is in S1 now.  a V = B V_b, then K~_b^-1 V_b with its trace and K~_b^-1 V_b K~_b^-1 (P1, in S4)
-  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S2, lb)), into(mat(aV, lb))));
-  GP_TRY(projected_kl_products(lane, 1, &c, &nk, nb));
+  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(Bp), plain(S2), into(aV)));
+  GP_TRY(projected_kl_products(lane, na, cl, nkl, nb));
   // ---- moments / likelihood pieces with a = B and the adjoints G_a, G_Kb, G_K~b (P2 = B^T G_a K~_b^-1 in Abuf)
   ProjGroupT pg{};
-  pg.n_units = 1; pg.n = n; pg.np = np; pg.nb = nb; pg.ld = lb;
-  pg.r = one(r); pg.A = one(A); pg.lambda0 = one(lambda0);
-  pg.am = one(Bp); pg.Kb = one(Kb); pg.aV = one(aV); pg.mb = one(mbp);
-  pg.Kvec = one(c->Kvec); pg.lam_m = one(c->lam_m); pg.lam_var = one(c->lam_var); pg.f = one(c->fvec);
-  pg.gm = one(gm); pg.gv = one(gv); pg.part = one(c->upart); pg.out3 = one(c->scal + S_RLAM);
-  pg.Ga = one(Ga); pg.GaKi = one(GaKi);
-  pg.Ki = one(S1); pg.P1 = one(S4); pg.P2 = one(c->Abuf); pg.bvec = one(bvec); pg.mkm = one(c->scal + S_MKM); pg.G = one(S3);
-  GP_TRY(projected_adjoints(lane, pg, &part, &part_elems));
-  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(mat(Bp, lb)), plain(mat(S3, lb)), into(mat(GaKi, lb), 1.0)));          // + B G_K~b
+  pg.n_units = na; pg.n = n; pg.np = np; pg.nb = nb; pg.ld = lb;
+  pg.r = per_unit<const double*>(na, [&](int i) { return r[un[i].u]; });
+  pg.A = per_unit<double>(na, [&](int i) { return un[i].A; });
+  pg.lambda0 = per_unit<double>(na, [&](int i) { return lambda0[un[i].u]; });
+  pg.am = of(&gpfit_ctx::Lbuf); pg.Kb = of(&gpfit_ctx::Libuf); pg.aV = of(&gpfit_ctx::Tbuf); pg.mb = of(&gpfit_ctx::mpad);
+  pg.Kvec = of(&gpfit_ctx::Kvec); pg.lam_m = of(&gpfit_ctx::lam_m); pg.lam_var = of(&gpfit_ctx::lam_var); pg.f = of(&gpfit_ctx::fvec);
+  pg.gm = of(&gpfit_ctx::dq1); pg.gv = of(&gpfit_ctx::dq2); pg.part = of(&gpfit_ctx::upart); pg.out3 = scal_of(S_RLAM);
+  pg.Ga = of(&gpfit_ctx::Zbuf); pg.GaKi = of(&gpfit_ctx::Tmp);
+  pg.Ki = of(&gpfit_ctx::Vbuf); pg.P1 = of(&gpfit_ctx::TmpV); pg.P2 = of(&gpfit_ctx::Abuf); pg.bvec = of(&gpfit_ctx::yv);
+  pg.mkm = scal_of(S_MKM); pg.G = of(&gpfit_ctx::LiVbuf);
+  GP_TRY(projected_adjoints(lane, pg, part, part_elems));
+  GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(Bp), plain(S3), into(GaKi, 1.0)));          // + B G_K~b
   // W = sym((.) B^T).  With P = B G_K~b + G_Kb:  1/2 (P B^T + B P^T) = 1/2 [P | B] [B | P]^T -- ONE product with
   // k = 2 nb that writes the lower tiles only (what the adjoint pass reads): the same flops as the full P B^T, and
   // neither its upper half nor the averaging pass over N x N exist.  (Falls back to the two steps when 2 nb
-  // columns do not fit the N x N scratch matrices, i.e. when hardly anything was truncated.)
-  if (2 * (int64_t)nb * np <= (int64_t)c->np_cap * c->np_cap) {
-    double *Cat1 = Ga, *Cat2 = aV;   // G_a and a V_b are dead
-    const int64_t l2b = 2 * lb;
-    const PerUnit<const double*> P = one((const double*)GaKi), Bc = one((const double*)Bp);
-    GP_TRY(launch_pad_copy_group(1, P, one(lb), np, one(nb), one(Cat1), l2b, np, nb, s));
-    GP_TRY(launch_pad_copy_group(1, Bc, one(lb), np, one(nb), one(Cat1 + nb), l2b, np, nb, s));
-    GP_TRY(launch_pad_copy_group(1, Bc, one(lb), np, one(nb), one(Cat2), l2b, np, nb, s));
-    GP_TRY(launch_pad_copy_group(1, P, one(lb), np, one(nb), one(Cat2 + nb), l2b, np, nb, s));
-    GP_TRY(product(lane, {np, np, 2 * nb}, 0.5, plain(mat(Cat1, l2b)), trans(mat(Cat2, l2b)), into_lower(mat(W, ld))));
+  // columns do not fit the N x N scratch matrices, i.e. when hardly anything was truncated.)  One route for the call:
+  // nb, np and the capacity are shared.
+  const Mat<R> W = all(&gpfit_ctx::Wbuf, ld);
+  if (2 * (int64_t)nb * np <= (int64_t)c0->np_cap * c0->np_cap) {
+    const int64_t l2b = 2 * lb;   // Cat1 = Zbuf, Cat2 = Tbuf: G_a and a V_b are dead
+    const PerUnit<const double*> P = cof(&gpfit_ctx::Tmp), Bc = cof(&gpfit_ctx::Lbuf);
+    const PerUnit<double*> Cat1 = of(&gpfit_ctx::Zbuf), Cat2 = of(&gpfit_ctx::Tbuf);
+    const PerUnit<double*> Cat1b = per_unit<double*>(na, [&](int i) { return cl[i]->Zbuf + nb; }),
+                           Cat2b = per_unit<double*>(na, [&](int i) { return cl[i]->Tbuf + nb; });
+    GP_TRY(launch_pad_copy_group(na, P, same(lb), np, same(nb), Cat1, l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(na, Bc, same(lb), np, same(nb), Cat1b, l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(na, Bc, same(lb), np, same(nb), Cat2, l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(na, P, same(lb), np, same(nb), Cat2b, l2b, np, nb, s));
+    GP_TRY(product(lane, {np, np, 2 * nb}, 0.5, plain(all(&gpfit_ctx::Zbuf, l2b)), trans(all(&gpfit_ctx::Tbuf, l2b)), into_lower(W)));
   } else {
-    GP_TRY(product(lane, {np, np, nb}, 1.0, plain(mat(GaKi, lb)), trans(mat(Bp, lb)), into(mat(W, ld))));
-    GP_TRY(launch_symmetrize_avg_group(1, one(W), ld, one(np), s));
+    GP_TRY(product(lane, {np, np, nb}, 1.0, plain(GaKi), trans(Bp), into(W)));
+    GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::Wbuf), ld, same(np), s));
   }
-  // ---- pull-back of <W, dK~_p> + <gvec, dKvec_p> to the metric (as gpfit_grad_pullback; gvec = -g_v; bv and wl were
-  // cleared at the start)
-  GP_TRY(launch_scale_copy<R>(c->wl, gv, n, 1.0, s));
-  GP_TRY(pullback_to_metric(c, lane, W, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
-  GP_TRY(launch_metric_contract(th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
-                                c->info + INFO_METRIC, s));
-  GP_TRY(closure_collect(1, &c, s));
+  // ---- unit by unit (the masked pixel count again), the pull-back of <W, dK~_p> + <gvec, dKvec_p> to the metric (as
+  // gpfit_grad_pullback; gvec = -g_v; bv and wl were cleared at the start)
+  for (int i = 0; i < na; ++i) {
+    gpfit_ctx* c = cl[i];
+    const Unit& q = un[i];
+    GP_TRY(launch_scale_copy<R>(c->wl, c->dq2, n, 1.0, s));
+    GP_TRY(pullback_to_metric(c, lane, c->Wbuf, c->Cos, c->q, n, np, q.dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
+    GP_TRY(launch_metric_contract(q.th, c->pix, q.d, n_rows, n_cols, c->Cmat, q.dp, c->Mmat, q.dp, c->scal + S_METRIC, c->upart,
+                                  c->info + INFO_METRIC, s));
+  }
+  GP_TRY(closure_collect(na, cl, s));
   GP_HIP(hipStreamSynchronize(s));
-  const double* sc = c->scal_host;
-  return assemble_out(c, A, lambda0, sigma0_row_metric(sc, th.sigma0) - 2.0 * th.sigma0 * sc[S_ADJ_WL], 0, d, 1,
-                      "gpfit_fit_eval_projected: Cholesky of the projected K_tilde failed (non-positive pivot)",
-                      "gpfit_fit_eval_projected: Cholesky of V_b failed (non-positive pivot)", out_host);
+  const std::string err_K = std::string(name) + ": Cholesky of the projected K_tilde failed (non-positive pivot)";
+  const std::string err_V = std::string(name) + ": Cholesky of V_b failed (non-positive pivot)";
+  for (int i = 0; i < na; ++i) {
+    gpfit_ctx* c = cl[i];
+    const Unit& q = un[i];
+    const double* sc = c->scal_host;
+    rc_out[q.u] = assemble_out(c, q.A, lambda0[q.u], sigma0_row_metric(sc, q.th.sigma0) - 2.0 * q.th.sigma0 * sc[S_ADJ_WL], 0,
+                               q.d, 1, err_K.c_str(), err_V.c_str(), out_host + OUT_COUNT * q.u);
+  }
+  return 0;
 }
 
 // Sparse M-step closure (n_tilde < n_t: K[n_t][n_tilde] != K~, a = K_b K~_b^-1 with non-zero da_p;
@@ -1860,8 +1960,22 @@ int gpfit_fit_eval_projected(gpfit_ctx* c, void* stream, const double* theta, co
                              int n_rows, int n_cols, const double* X, int64_t ldx, int64_t N, const double* r,
                              const double* B, int64_t ldb, int64_t n_kept, const double* m_b, const double* V_b,
                              int64_t ldvb, double logA, double lambda0, double* out_host) {
-  return fit_eval_projected_impl(c, stream, theta, lower, upper, n_rows, n_cols, X, ldx, N, r, B, ldb, n_kept, m_b, V_b,
-                                 ldvb, logA, lambda0, out_host);
+  // the group of one (fit_eval_projected_group_impl): a unit's numbers are the same alone and in any group
+  int rc = 0;
+  const int ret = fit_eval_projected_group_impl("gpfit_fit_eval_projected", &c, 1, stream, theta, lower, upper, n_rows, n_cols, &X,
+                                                ldx, N, &r, &B, &ldb, &n_kept, &m_b, &V_b, &ldvb, &logA, &lambda0, out_host, &rc);
+  return ret != 0 ? ret : rc;
+}
+
+static_assert(GPFIT_FIT_EVAL_PROJECTED_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+
+int gpfit_fit_eval_projected_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* theta, const double* lower,
+                                   const double* upper, int n_rows, int n_cols, const double* const* X, int64_t ldx, int64_t N,
+                                   const double* const* r, const double* const* B, const int64_t* ldb, const int64_t* n_kept,
+                                   const double* const* m_b, const double* const* V_b, const int64_t* ldvb, const double* logA,
+                                   const double* lambda0, double* out_host, int* rc_out) {
+  return fit_eval_projected_group_impl("gpfit_fit_eval_projected_batch", ctxs, n_units, stream, theta, lower, upper, n_rows,
+                                       n_cols, X, ldx, N, r, B, ldb, n_kept, m_b, V_b, ldvb, logA, lambda0, out_host, rc_out);
 }
 
 int gpfit_fit_eval_sparse(gpfit_ctx* c, void* stream, const double* theta, const double* lower, const double* upper,

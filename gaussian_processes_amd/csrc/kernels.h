@@ -315,7 +315,7 @@ int launch_symv_lower_group(int n_units, PerUnit<double*> A, int64_t lda, int n,
                             hipStream_t s);
 int launch_dot_group(int n_units, PerUnit<double*> x, PerUnit<double*> y, int n, PerUnit<double*> out, hipStream_t s);
 int launch_proj_trace_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, PerUnit<double*> out, hipStream_t s);
-// the operands of the element-wise passes of the projected closures (gpfit_fit_eval_projected: one unit, a = B;
+// the operands of the element-wise passes of the projected closures (gpfit_fit_eval_projected / _batch: a = B;
 // gpfit_fit_eval_sparse / _batch: a = K_b K~_b^-1), per unit -- n training points padded to np rows, the padded basis
 // size nb = the leading dimension ld:
 //   moments  lam_m = a m_b, lam_var = Kvec - rowsum(a o K_b) + rowsum(aV o a), f, g_m = A (r - f), g_v = -A^2 f / 2;

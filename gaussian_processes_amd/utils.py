@@ -926,7 +926,7 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     same place: whenever every live fit waits -- some with a closure of their L-BFGS, some already with their next chain
     -- the closures go out as ONE ``gpfit_fit_eval_sparse_batch`` call per group of equal ``_closure_bucket_key`` and the
     chains as theirs.  A closure that returns the infinite loss on the host (theta outside the limits) asks nothing, and
-    a fit in the full-rank or truncated regime keeps its own closure calls.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
+    the truncated-rank closures (``_closure_projected``: ``ntilde == ntrain`` with eigenvalues dropped) meet there in the same way, as ONE ``gpfit_fit_eval_projected_batch`` call per group of equal key (the regime is part of the key: the two never share a call; so is the capacity of the fit's workspace).  A fit in the full-rank regime keeps its own ``fit_eval`` calls.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
     invocation, in order (1: the single call); ``last_closure_group_sizes``, ``last_closure_call_seconds`` and
     ``last_seconds_in_closure_call``: the same for the closure calls.  The workspaces of the fits (one per concurrent fit, each of the size of
     a ``varGP`` workspace) are kept for the next call; ``release_cell_workspaces()`` frees them."""
@@ -1414,27 +1414,133 @@ def _closure_projected(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params):
     factorisations, moments / likelihood / KL, adjoints, lift and pull-back on the device).  When a
     factorisation meets a non-positive pivot the reference's ``log_det`` would take its
     eigen-fallback (utils.py:1279-1304): the step-by-step formulation below (``_closure_projected_steps``)
-    reproduces that and is used instead."""
-    lib = _lib.load()
+    reproduces that and is used instead.  In a fit of ``varGP_cells`` the device call is the wave's: the request goes
+    to the rendezvous and comes back as one unit of a ``gpfit_fit_eval_projected_batch`` call, with the same bits."""
+    q = _closure_projected_prepare(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params)
+    rendezvous = getattr(_CELLS, "rendezvous", None)
+    rc_, out = rendezvous.call(q) if rendezvous is not None else _closure_run_single(q)
+    return _closure_projected_finish(q, rc_, out)
+
+
+def _closure_projected_prepare(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params, engine=None):
+    """The arguments of ``_closure_projected`` as one request (``regime``: truncated -- a closure request without that field
+    is a sparse one): the operands on the device, the scalars as floats, and the workspace and stream the call runs on
+    -- this thread's unless an engine is given.  ``cap``: the padded number of stimuli the workspace was created for, on
+    which the k slabs of the projections and the route of the lift depend."""
     lower, upper = lims
     xc, rc, Bc, mc, Vc = _cu(x), _cu(r), _cu(B), _cu(m_b), _cu(V_b)
     rows, cols = _grid(n_px_side)
-    N, nk = Bc.shape
-    eng = get_engine(N, xc.shape[1], rows * cols)
+    q = {"kind": "closure", "regime": "truncated", "theta": [float(v) for v in theta_vec(theta)],
+         "lower": [_scalar(lower[k]) for k in THETA_KEYS], "upper": [_scalar(upper[k]) for k in THETA_KEYS],
+         "rows": rows, "cols": cols, "x": xc, "r": rc, "B": Bc, "m_b": mc, "V_b": Vc,
+         "N": int(Bc.shape[0]), "n_kept": int(Bc.shape[1]),
+         "logA": _scalar(f_params['logA']), "lambda0": _scalar(_lambda0_of(f_params)),
+         "args": (theta, lims, n_px_side, x, r, B, m_b, V_b, f_params)}
+    q["engine"] = engine if engine is not None else get_engine(q["N"], xc.shape[1], rows * cols)
+    q["cap"] = -(-q["engine"].n_max // 128) * 128
+    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    return q
+
+
+def _closure_projected_run_single(q):
+    """``gpfit_fit_eval_projected`` on one truncated request: ``(rc, out[16])``."""
     out = (ctypes.c_double * 16)()
-    rc_ = lib.gpfit_fit_eval_projected(eng._ctx, _stream(), _lib.darr(theta_vec(theta)),
-                                       _lib.darr([_scalar(lower[k]) for k in THETA_KEYS]),
-                                       _lib.darr([_scalar(upper[k]) for k in THETA_KEYS]), rows, cols,
-                                       xc.data_ptr(), xc.stride(0), N, rc.data_ptr(), Bc.data_ptr(), Bc.stride(0), nk,
-                                       mc.data_ptr(), Vc.data_ptr(), Vc.stride(0), _scalar(f_params['logA']),
-                                       _scalar(_lambda0_of(f_params)), out)
-    if rc_ == -2:
-        raise ValueError(_lib.last_error())
-    if rc_ < 0:
+    x, B, V = q["x"], q["B"], q["V_b"]
+    rc_ = _lib.load().gpfit_fit_eval_projected(q["engine"]._ctx, q["stream"], _lib.darr(q["theta"]), _lib.darr(q["lower"]),
+                                               _lib.darr(q["upper"]), q["rows"], q["cols"], x.data_ptr(), x.stride(0), q["N"],
+                                               q["r"].data_ptr(), B.data_ptr(), B.stride(0), q["n_kept"], q["m_b"].data_ptr(),
+                                               V.data_ptr(), V.stride(0), q["logA"], q["lambda0"], out)
+    if rc_ < 0 and rc_ != -2:
         _lib.check(rc_, "gpfit_fit_eval_projected")
+    return rc_, list(out)
+
+
+def _closure_projected_bucket_key(q):
+    """Truncated requests with equal keys may share one ``gpfit_fit_eval_projected_batch`` call: the regime (the two
+    regimes never share a call), what that call shares between its units, the padded basis size (the recursion's split,
+    hence the bits, depend on it) and the capacity of the workspace (the slab counts and the lift's route depend on it)."""
+    return ("truncated", q["x"].device.index, q["stream"].value, q["N"], q["x"].stride(0), q["rows"], q["cols"],
+            -(-q["n_kept"] // 128) * 128, q["cap"])
+
+
+def _closure_projected_batch_raw(ctxs, qs, out=None, rcs=None):
+    """``gpfit_fit_eval_projected_batch`` on the truncated requests ``qs`` with the contexts ``ctxs`` (one per request): the
+    return code, the 16 outputs per unit and the per-unit codes, nothing checked here -- the shared arguments are those
+    of ``qs[0]``.  A tensor given as None goes in as a null pointer; ``out`` / ``rcs``: the caller's arrays instead of new
+    ones."""
+    nu = len(qs)
+
+    def ptrs(key):
+        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
+
+    def flat(key):
+        return _lib.darr([v for q in qs for v in q[key]])
+
+    q0 = qs[0]
+    out = (ctypes.c_double * (16 * nu))() if out is None else out
+    rcs = (ctypes.c_int * nu)() if rcs is None else rcs
+    rc = _lib.load().gpfit_fit_eval_projected_batch(
+        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
+        flat("theta"), flat("lower"), flat("upper"), q0["rows"], q0["cols"], ptrs("x"), q0["x"].stride(0), q0["N"], ptrs("r"),
+        ptrs("B"), (ctypes.c_int64 * nu)(*[q["n_kept"] if q["B"] is None else q["B"].stride(0) for q in qs]),
+        (ctypes.c_int64 * nu)(*[q["n_kept"] for q in qs]), ptrs("m_b"), ptrs("V_b"),
+        (ctypes.c_int64 * nu)(*[q["n_kept"] if q["V_b"] is None else q["V_b"].stride(0) for q in qs]),
+        _lib.darr([q["logA"] for q in qs]), _lib.darr([q["lambda0"] for q in qs]), out, rcs)
+    return rc, out, rcs
+
+
+def _closure_projected_run_group(qs):
+    """One ``gpfit_fit_eval_projected_batch`` call on truncated requests of one bucket (``_closure_projected_bucket_key``),
+    each on its own workspace; per request what ``_closure_projected_run_single`` returns, with the same bits."""
+    if len({_closure_bucket_key(q) for q in qs}) != 1:
+        raise ValueError("_closure_run_group: the truncated requests of one call share the stimuli's size and leading "
+                         "dimension, the pixel grid, the padded basis size and the capacity of their workspaces")
+    rc, out, rcs = _closure_projected_batch_raw([q["engine"]._ctx for q in qs], qs)
+    _lib.check(rc, "gpfit_fit_eval_projected_batch")
+    return [(int(rcs[u]), list(out[16 * u:16 * u + 16])) for u in range(len(qs))]
+
+
+def _closure_projected_finish(q, rc_, out):
+    """What ``_closure_projected`` returns or raises for the code and the outputs the device call gave its request; a
+    non-positive pivot (``rc_ > 0``) takes the step-by-step formulation, in the caller's own thread."""
+    if rc_ == -2:
+        _lib.load().gpfit_check_limits(_lib.darr(q["theta"]), _lib.darr(q["lower"]), _lib.darr(q["upper"]))   # its message
+        raise ValueError(_lib.last_error())
     if rc_ == 0:
         return out[0], {k: out[3 + i] for i, k in enumerate(THETA_KEYS)}
-    return _closure_projected_steps(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params)
+    return _closure_projected_steps(*q["args"])
+
+
+def _closure_projected_group(units):
+    """``_closure_projected`` for several independent units (cells, restarts of one cell) as ONE device call
+    (``gpfit_fit_eval_projected_batch``).  ``units``: one dict per unit with the arguments of ``_closure_projected`` by
+    name; 1 .. 16 units of one bucket (``_closure_bucket_key``).  Returns, per unit, what ``_closure_projected`` returns
+    for it on a workspace created for its number of stimuli, bit for bit (a closure's slab counts and the route of its
+    lift, hence its last bits, depend on the capacity of the workspace: the units here run on workspaces of that one
+    capacity, whatever the size of the thread's own); a unit whose call would raise has the exception in its place, and
+    a unit whose factorisation fails takes the step-by-step formulation alone."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"_closure_projected_group: 1 .. {MAX_CHAIN_UNITS} units per call")
+    rows, cols = _grid(units[0]["n_px_side"])
+    n, d, d_full = max(u["x"].shape[0] for u in units), units[0]["x"].shape[1], rows * cols
+    # one capacity per call (the slab counts and the lift's route depend on it), that of a workspace created for these n
+    # stimuli: this thread's own if it has that capacity, kept ones that have it, and new ones kept for later group calls
+    kept = getattr(_CELLS, "engines", [])
+    engines = [e for e in [get_engine(n, d, d_full)] + kept
+               if -(-e.n_max // 128) == -(-n // 128) and e.d_max >= d and e.d_full_max >= d_full
+               and e.device == _device().index][:len(units)]
+    while len(engines) < len(units):
+        engines.append(GPFitEngine(n, d, d_full, device=_device().index))
+        kept = kept + [engines[-1]]
+    _CELLS.engines = kept
+    qs = [_closure_projected_prepare(engine=e, **u) for u, e in zip(units, engines)]
+    res = []
+    for q, (rc_, out) in zip(qs, _closure_run_group(qs) if len(qs) > 1 else [_closure_run_single(qs[0])]):
+        try:
+            res.append(_closure_projected_finish(q, rc_, out))
+        except Exception as err:      # what _closure_projected raises for this unit alone
+            res.append(err)
+    return res
 
 
 def _closure_adjoints(K_b, K_tilde_b, Kvec, a, m_b, V_b, r, f_params):
@@ -1537,7 +1643,9 @@ def _closure_sparse_prepare(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f
 
 
 def _closure_run_single(q):
-    """``gpfit_fit_eval_sparse`` on one request: ``(rc, out[16])``."""
+    """``gpfit_fit_eval_sparse`` on one request: ``(rc, out[16])`` (a truncated request: ``gpfit_fit_eval_projected``)."""
+    if q.get("regime") == "truncated":
+        return _closure_projected_run_single(q)
     out = (ctypes.c_double * 16)()
     x, xt, B, V = q["x"], q["xt"], q["B"], q["V_b"]
     rc_ = _lib.load().gpfit_fit_eval_sparse(q["engine"]._ctx, q["stream"], _lib.darr(q["theta"]), _lib.darr(q["lower"]),
@@ -1552,7 +1660,10 @@ def _closure_run_single(q):
 
 def _closure_bucket_key(q):
     """Requests with equal keys may share one ``gpfit_fit_eval_sparse_batch`` call: what that call shares between its
-    units, and the padded basis size (the recursion's split, hence the bits, depend on it)."""
+    units, and the padded basis size (the recursion's split, hence the bits, depend on it).  A truncated request
+    (``regime``) has the key of its own call, ``_closure_projected_bucket_key``, which begins with the regime."""
+    if q.get("regime") == "truncated":
+        return _closure_projected_bucket_key(q)
     return (q["x"].device.index, q["stream"].value, q["N"], q["Nt"], q["x"].stride(0), q["xt"].stride(0), q["rows"], q["cols"],
             -(-q["n_kept"] // 128) * 128)
 
@@ -1585,7 +1696,10 @@ def _closure_batch_raw(ctxs, qs, out=None, rcs=None):
 
 def _closure_run_group(qs):
     """One ``gpfit_fit_eval_sparse_batch`` call on requests of one bucket (``_closure_bucket_key``), each on its own
-    workspace; per request what ``_closure_run_single`` returns, with the same bits."""
+    workspace; per request what ``_closure_run_single`` returns, with the same bits.  (Truncated requests: their own call,
+    ``_closure_projected_run_group``.)"""
+    if all(q.get("regime") == "truncated" for q in qs):
+        return _closure_projected_run_group(qs)
     if len({_closure_bucket_key(q) for q in qs}) != 1:
         raise ValueError("_closure_run_group: the requests of one call share the stimuli's sizes and leading dimensions, "
                          "the pixel grid and the padded basis size")

@@ -201,6 +201,34 @@ int gpfit_fit_eval_projected(gpfit_ctx* ctx, void* stream, const double* theta, 
                              const double* r, const double* B, int64_t ldb, int64_t n_kept, const double* m_b,
                              const double* V_b, int64_t ldvb, double logA, double lambda0, double* out_host);
 
+/* gpfit_fit_eval_projected for 1 .. GPFIT_FIT_EVAL_PROJECTED_MAX_UNITS independent units -- cells recorded on the same
+ * stimuli, restarts of one cell -- as ONE call: unit u runs on its own context ctxs[u] (pairwise distinct, one device, one
+ * capacity) with its own theta[6u ..], lower[6u ..], upper[6u ..] (both NULL: no limits), X[u] (may be the same matrix for
+ * every unit), r[u], B[u], ldb[u], n_kept[u], m_b[u], V_b[u], ldvb[u], logA[u], lambda0[u]; n_rows, n_cols, ldx and N are
+ * shared.  Everything is enqueued on `stream`, one synchronisation at the end.  The kernel builds and the pull-backs run
+ * unit by unit (the masked pixel count differs from unit to unit); between them the 2 n_units factorisations run as one
+ * lock-step recursion, every product goes out for the list of units and every small kernel is one launch for the group,
+ * so that stretch costs the launches of one unit.  (Two chains per unit in a pointer batch of 32: hence 16 units.)
+ * All units of a call must have the same round_up(n_kept[u], 128) (n_kept[u] itself may differ): the recursion's split
+ * depends on the padded size.  All contexts of a call must have been created for the same number of stimuli
+ * (round_up(n_max, 128)): the k slabs of the projections and the route of the lift W depend on a context's capacity, and
+ * a unit takes in a group exactly what it takes alone on its context.  Otherwise -3 -- the caller groups its units by
+ * padded size and capacity.
+ * out_host[16 n_units]: the 16 slots of gpfit_fit_eval_projected, unit by unit, each with the bits of that call on the
+ * unit alone (on the same context) whatever else is in the group.  rc_out[n_units]: what the single call would have
+ * returned for the unit -- 0; -2 theta outside the unit's limits (its slots hold the infinite loss and gradients, nothing
+ * was enqueued for it); > 0 the LAPACK info of a failed pivot, which changes nothing in the other units.
+ * Returns 0, or < 0 for a bad argument, insufficient capacity or a HIP error: for the first two nothing has been
+ * enqueued and neither out_host nor rc_out has been written.  gpfit_fit_eval_projected itself is this call with one
+ * unit. */
+#define GPFIT_FIT_EVAL_PROJECTED_MAX_UNITS 16
+int gpfit_fit_eval_projected_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* theta,
+                                   const double* lower, const double* upper, int n_rows, int n_cols,
+                                   const double* const* X, int64_t ldx, int64_t N, const double* const* r,
+                                   const double* const* B, const int64_t* ldb, const int64_t* n_kept,
+                                   const double* const* m_b, const double* const* V_b, const int64_t* ldvb,
+                                   const double* logA, const double* lambda0, double* out_host, int* rc_out);
+
 /* Sparse M-step closure, fused: n_tilde < n_t inducing stimuli (the regime of the lab's own fits,
  * one_cell_fit.ipynb:89: n_t ~ 3160, n_tilde up to 2100): K[n_t][n_tilde] = acosker(x, xtilde) differs from
  * K~ = acosker(xtilde, xtilde), a = K_b K~_b^-1 (utils.py:1693, 2068) and da_p is non-zero (:1114).
