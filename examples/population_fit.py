@@ -1,20 +1,24 @@
 """Several cells recorded on the same stimuli, fitted together: ``utils.varGP_cells`` (the E-step chains of the cells of
 a wave go out as ONE device call per EM iteration, and the M-step closures of their L-BFGS -- sparse, or truncated-rank
-when ``--ntilde`` equals ``--n`` and the tolerance drops eigenvalues -- as one call whenever the wave's fits meet) or, with
-``--loop``, ``utils.varGP`` cell after cell.  Both give the same numbers per cell, bit for bit.
+when ``--ntilde`` equals ``--n`` and the tolerance drops eigenvalues, or full-rank when it keeps them all (``--eigval-tol``)
+-- as one call whenever the wave's fits meet) or, with ``--loop``, ``utils.varGP`` cell after cell.  Both give the same
+numbers per cell, bit for bit.
 
     python examples/population_fit.py --cells 4                      # four synthetic cells through varGP_cells
     python examples/population_fit.py --cells 4 --loop               # the same fits one after another
     python examples/population_fit.py --n 3160 --ntilde 2100 --d 256 --cells 16 --maxiter 30 --nestep 10 --nmstep 10 \\
         --nfstep 4 --repeat 3                                        # the lab's shape (scripts/lab_fit_times.py's settings)
     python examples/population_fit.py --n 1024 --ntilde 1024 --d 256 --cells 16   # inducing set = training set: truncated rank
+    python examples/population_fit.py --n 512 --ntilde 512 --d 64 --cells 16 --eigval-tol 1e-14   # every eigenvalue kept: full rank
 
 Per repetition it prints the wall time of all fits and, averaged over the cells, the phase times ``varGP`` reports;
 for ``varGP_cells`` also how many units each chain call and each closure call carried and how long those calls took.
 Under ``varGP_cells`` a fit's own "E-steps" time includes waiting for the other fits of its wave, so the E-step time per
 cell is printed as (that time - the time between handing a chain in and getting it back), i.e. the per-cell preamble of
 the phase, plus the cell's share of the group calls; the M-step time per cell by the same accounting with the closure
-calls."""
+calls.  The chain and closure calls of fits in the full-rank regime are counted apart (``last_full_group_sizes``,
+``last_full_closure_group_sizes``) and enter the same two figures; ``GPFIT_FULL_RANK_GROUPS=0`` makes such fits issue their
+own calls, one fit after the other."""
 import argparse
 import contextlib
 import io
@@ -38,11 +42,15 @@ ap.add_argument("--nfstep", type=int, default=4)
 ap.add_argument("--max-units", type=int, default=16, help="fits per wave of varGP_cells")
 ap.add_argument("--repeat", type=int, default=2, help="the first repetition carries the one-time costs of the process")
 ap.add_argument("--loop", action="store_true", help="varGP cell after cell instead of varGP_cells")
+ap.add_argument("--eigval-tol", type=float, default=None,
+                help="utils.EIGVAL_TOL: eigenvalues of K~ below it (relative) are dropped; 1e-14 keeps them all (full rank)")
 args = ap.parse_args()
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gaussian_processes_amd import synthetic as syn, utils as gp  # noqa: E402
 
+if args.eigval_tol is not None:
+    gp.EIGVAL_TOL = args.eigval_tol      # a module global read at call time
 n_px = int(round(args.d ** 0.5))
 assert n_px * n_px == args.d, "--d must be a square number of pixels"
 dev = torch.device("cuda")
@@ -89,19 +97,25 @@ for rep in range(max(1, args.repeat)):
     line = (f"rep {rep}: wall {wall:.3f} s = {wall / args.cells:.3f} s per cell | per cell: "
             + ", ".join(f"{k} {v:.3f}s" for k, v in ph.items()))
     if not args.loop:
-        sizes, secs = gp.varGP_cells.last_group_sizes, gp.varGP_cells.last_call_seconds
-        in_call = gp.varGP_cells.last_seconds_in_call / args.cells
+        v = gp.varGP_cells
+        fsizes = v.last_full_group_sizes
+        sizes, secs = v.last_group_sizes, v.last_call_seconds + v.last_full_call_seconds
+        in_call = (v.last_seconds_in_call + v.last_seconds_in_full_call) / args.cells
         estep = ph["E-steps"] - in_call + sum(secs) / args.cells
         hist = {n: sizes.count(n) for n in sorted(set(sizes))}
-        line += (f" | chain calls by units carried {hist}, {sum(secs):.3f} s in all; in the rendezvous {in_call:.3f}s per cell"
+        fhist = {n: fsizes.count(n) for n in sorted(set(fsizes))}
+        line += (f" | chain calls by units carried {hist}, full-rank chain calls {fhist}, {sum(secs):.3f} s in all; in the "
+                 f"rendezvous {in_call:.3f}s per cell"
                  f" -> E-step time per cell {estep:.3f}s (preamble {ph['E-steps'] - in_call:.3f} + share of the calls "
                  f"{sum(secs) / args.cells:.3f})")
-        csizes, csecs = gp.varGP_cells.last_closure_group_sizes, gp.varGP_cells.last_closure_call_seconds
-        in_closure = gp.varGP_cells.last_seconds_in_closure_call / args.cells
+        fcsizes = v.last_full_closure_group_sizes
+        csizes, csecs = v.last_closure_group_sizes, v.last_closure_call_seconds + v.last_full_closure_call_seconds
+        in_closure = (v.last_seconds_in_closure_call + v.last_seconds_in_full_closure_call) / args.cells
         mstep = ph["M-steps"] - in_closure + sum(csecs) / args.cells
         chist = {n: csizes.count(n) for n in sorted(set(csizes))}
-        line += (f" | closure calls by units carried {chist}, {sum(csecs):.3f} s in all; in the rendezvous {in_closure:.3f}s per "
-                 f"cell -> M-step time per cell {mstep:.3f}s (own part {ph['M-steps'] - in_closure:.3f} + share of the calls "
+        fchist = {n: fcsizes.count(n) for n in sorted(set(fcsizes))}
+        line += (f" | closure calls by units carried {chist}, full-rank closure calls {fchist}, {sum(csecs):.3f} s in all; in "
+                 f"the rendezvous {in_closure:.3f}s per cell -> M-step time per cell {mstep:.3f}s (own part {ph['M-steps'] - in_closure:.3f} + share of the calls "
                  f"{sum(csecs) / args.cells:.3f})")
     print(line + (f" | FAILED cells {failed}" if failed else ""), flush=True)
 kept = [int(fit["B"].shape[1]) for fit, _ in fits]

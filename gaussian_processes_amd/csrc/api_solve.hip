@@ -21,9 +21,10 @@ static CholBatchT<double> one_chain(gpfit_ctx* c, int64_t ld) {
   return b;
 }
 
-// The full-rank Newton update of gpfit_estep and of every step of gpfit_estep_chain_full, on the context's work
-// matrices (M = I + S K S in Kbuf, S K in Zbuf, K's lower tiles in Wbuf; ld = np), in two halves: the chain records the
-// factorisation's info word between them.
+// The full-rank Newton update of gpfit_estep and of every step of gpfit_estep_chain_full / _batch, on the work matrices
+// of every context of the list (M = I + S K S in Kbuf, S K in Zbuf, K's lower tiles in Wbuf; ld = np), in two halves:
+// the chain records the factorisation's info word between them.  One unit or several: one lock-step recursion and one
+// product per line for the list, so a unit has the same bits alone and in any group.
 // From np = 2 TILE on T = L_M^-1 (S K) is formed block-wise, so that the off-diagonal block of L_M^-1 is never formed
 // (N^3/4 less):   T1 = [L^-1]11 B1 ,  T2 = [L^-1]22 (B2 - L21 T1)        with B = S K ; n1 rows in the top block
 static int full_update_split(int np) {
@@ -32,25 +33,35 @@ static int full_update_split(int np) {
   const int n1 = ((kt + 1) / 2) * TILE;
   return n1;
 }
-static int full_update_factor(gpfit_ctx* c, int np, Lane lane) {
-  const CholBatchT<double> b = one_chain(c, np);
-  if (full_update_split(np)) return potrf_lockstep(b, 0, np, 0u, lane, 1u);   // [L^-1]11 and [L^-1]22 only
-  return potrf_lockstep(b, 0, np, 1u, lane);
+static int full_update_factor(gpfit_ctx* const* ctxs, int nu, int np, Lane lane) {
+  CholBatchT<double> b;
+  for (int u = 0; u < nu; ++u) {
+    gpfit_ctx* c = ctxs[u];
+    const int i = b.nb++;
+    b.A[i] = c->Kbuf; b.L[i] = c->Lbuf; b.Li[i] = c->Libuf; b.Tmp[i] = c->Tmp; b.info[i] = c->info + INFO_K;
+  }
+  b.ld = np;
+  const uint32_t all = (uint32_t)((1ull << nu) - 1ull);
+  if (full_update_split(np)) return potrf_lockstep(b, 0, np, 0u, lane, all);   // [L^-1]11 and [L^-1]22 only
+  return potrf_lockstep(b, 0, np, all, lane);
 }
-static int full_update_products(gpfit_ctx* c, int np, Lane lane) {
+static int full_update_products(gpfit_ctx* const* ctxs, int nu, int np, Lane lane) {
   const int64_t ld = np;
-  auto at = [&](double* X, int r, int col) { return mat(X + (int64_t)r * ld + col, ld); };
+  auto at = [&](double* gpfit_ctx::*X, int r, int col) {
+    return mats(nu, ld, [&](int i) { return ctxs[i]->*X + (int64_t)r * ld + col; });
+  };
+  const auto Li = &gpfit_ctx::Libuf, L = &gpfit_ctx::Lbuf, SK = &gpfit_ctx::Zbuf, T = &gpfit_ctx::Abuf, Kl = &gpfit_ctx::Wbuf;
   // T = L_M^-1 (S K)          lower x dense                         N^3
   if (const int n1 = full_update_split(np)) {
     const int n2 = np - n1;
-    GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
-    GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(c->Lbuf, n1, 0)), plain(at(c->Abuf, 0, 0)), into(at(c->Zbuf, n1, 0), 1.0)));
-    GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(c->Libuf, n1, n1))), plain(at(c->Zbuf, n1, 0)), into(at(c->Abuf, n1, 0)), 1));
+    GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(Li, 0, 0))), plain(at(SK, 0, 0)), into(at(T, 0, 0)), 1));
+    GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(L, n1, 0)), plain(at(T, 0, 0)), into(at(SK, n1, 0), 1.0)));
+    GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(Li, n1, n1))), plain(at(SK, n1, 0)), into(at(T, n1, 0)), 1));
   } else {
-    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(c->Libuf, 0, 0))), plain(at(c->Zbuf, 0, 0)), into(at(c->Abuf, 0, 0)), 1));
+    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(Li, 0, 0))), plain(at(SK, 0, 0)), into(at(T, 0, 0)), 1));
   }
   // V = K - T^T T             lower tiles only                      N^3
-  return product(lane, {np, np, np}, -1.0, trans(at(c->Abuf, 0, 0)), plain(at(c->Abuf, 0, 0)), into_lower(at(c->Wbuf, 0, 0), 1.0));
+  return product(lane, {np, np, np}, -1.0, trans(at(T, 0, 0)), plain(at(T, 0, 0)), into_lower(at(Kl, 0, 0), 1.0));
 }
 
 namespace {
@@ -255,8 +266,8 @@ int gpfit_estep(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_
   // M = I + S K S (lower), SK = S K (dense), Kl = K (lower)
   GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, c->Wbuf, ld, s));
   const Lane lane = main_lane(c, s);
-  GP_TRY(full_update_factor(c, np, lane));
-  GP_TRY(full_update_products(c, np, lane));
+  GP_TRY(full_update_factor(&c, 1, np, lane));
+  GP_TRY(full_update_products(&c, 1, np, lane));
   // m_new = V (A^2 f o m + A (r - f))                                utils.py:1431
   GP_TRY(launch_symv_lower(c->Wbuf, ld, n, rhs, c->tvec, s));
   GP_HIP(hipMemcpyAsync(m_new, c->tvec, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -501,66 +512,107 @@ int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, c
                                 tol_grad, tol_change, rec_host);
 }
 
-// The full-rank chain: the update of gpfit_estep (full_update_factor / full_update_products) in place of the projected
-// one, on the bookkeeping of the projected chain -- a ChainGroupT of one unit with nb = n, so that the init, the info
-// word, the gated commits of m and V, the optimiser and the collect are the launches of estep_chain_group_impl.
+static_assert(GPFIT_ESTEP_CHAIN_FULL_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+
+// ONE body for gpfit_estep_chain_full (the group of one) and gpfit_estep_chain_full_batch.  The full-rank chain: the
+// update of gpfit_estep (full_update_factor / full_update_products) in place of the projected one, on the bookkeeping of
+// the projected chain -- a ChainGroupT with nb = n, so that the init, the info word, the gated commits of m and V, the
+// optimiser and the collect are the launches of estep_chain_group_impl.  Every unit on its own context, all on the
+// caller's stream with one synchronisation at the end; one lock-step recursion, every product on the list of units,
+// every small kernel in its unit-batched form: the same bits alone and in any group.
+static int estep_chain_full_group_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* stream,
+                                       const double* const* K, const int64_t* ldk, int64_t N, const double* const* r,
+                                       const double* const* kv0, double* const* m, double* const* f, double* const* V,
+                                       const int64_t* ldv, double* const* lam_m, double* const* lam_var, const double* logA0,
+                                       int lambda0_mode, const double* lambda0_fixed, int n_steps, int max_iter,
+                                       int history_size, double lr, double tol_grad, double tol_change, double* rec_host) {
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(name) + ": " + why);
+    return -3;
+  };
+  if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS)
+    return refuse("n_steps " + std::to_string(n_steps) + " is not within 1 .. " + std::to_string(CHAIN_MAX_STEPS));
+  if (!ctxs || !K || !ldk || !r || !kv0 || !m || !f || !V || !ldv || !lam_m || !lam_var || !logA0 ||
+      (lambda0_mode && !lambda0_fixed) || !rec_host || N <= 0 || N > INT32_MAX)
+    return refuse("bad argument");
+  Lbfgs1dConfig cfg;
+  GP_TRY(fparam_lbfgs_config(name, max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+  const int n = (int)N, np = (int)round_up(N, TILE);
+  for (int u = 0; u < n_units; ++u) {
+    const std::string unit = n_units > 1 ? "unit " + std::to_string(u) + ": " : std::string();
+    if (!ctxs[u] || !K[u] || !r[u] || !kv0[u] || !m[u] || !f[u] || !V[u] || !lam_m[u] || !lam_var[u])
+      return refuse(unit + "bad argument: null context or operand");
+    if (ldk[u] < N || ldv[u] < N) return refuse(unit + "bad argument: bad size or leading dimension");
+    if (ctxs[u]->device != ctxs[0]->device) return refuse("the contexts of one call must live on one device");
+    for (int v = 0; v < u; ++v)
+      if (ctxs[v] == ctxs[u]) return refuse("every unit needs a context of its own");
+    if (ctxs[u]->pend.active)
+      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
+    if (np > ctxs[u]->np_cap) return refuse(unit + "problem larger than the context capacity");
+  }
+  DeviceGuard device_guard(ctxs[0]->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int nu = n_units;
+  const int64_t ld = np;
+  ChainGroupT g{};
+  g.n_units = nu; g.n = n; g.nrows = np; g.npc = np; g.ld = ld; g.kmax = n;
+  for (int u = 0; u < nu; ++u) {
+    gpfit_ctx* c = ctxs[u];
+    g.nb.v[u] = n;
+    g.K.v[u] = K[u]; g.ldk.v[u] = ldk[u]; g.r.v[u] = r[u]; g.kv0.v[u] = kv0[u]; g.ldv.v[u] = ldv[u];
+    g.m.v[u] = m[u]; g.f.v[u] = f[u]; g.V.v[u] = V[u]; g.lam_m.v[u] = lam_m[u]; g.lam_var.v[u] = lam_var[u];
+    g.logA0.v[u] = logA0[u]; g.lambda0.v[u] = lambda0_mode ? lambda0_fixed[u] : 0.0;
+    g.blk.v[u] = c->chain; g.info.v[u] = c->info; g.rec_host.v[u] = c->chain_host;
+    // the work vectors and matrices of gpfit_estep
+    g.sv.v[u] = c->yv; g.u.v[u] = c->bv; g.mo.v[u] = c->tvec;
+    g.W.v[u] = c->Kbuf; g.SK.v[u] = c->Zbuf; g.Vw.v[u] = c->Wbuf;
+  }
+  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
+  GP_TRY(launch_chain_init_group(g, n_steps, s));
+  for (int step = 0; step < n_steps; ++step) {
+    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
+    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
+    GP_TRY(launch_estep_prep_chain_group(g, step, s));
+    // M = I + S K S (lower), SK = S K (dense), Kl = K (lower): Kl is overwritten by V, so it is rebuilt every step
+    GP_TRY(launch_estep_build_group(g, s));
+    GP_TRY(full_update_factor(ctxs, nu, np, lane));
+    GP_TRY(launch_chain_info_group(g, step, s));
+    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
+    GP_TRY(full_update_products(ctxs, nu, np, lane));
+    GP_TRY(launch_symv_lower_group(nu, g.Vw, ld, n, g.u, g.mo, s));
+    GP_TRY(launch_chain_copy_group(g, s));
+    GP_TRY(launch_unpack_sym_chain_group(g, s));
+    GP_TRY(launch_estep_full_moments_chain_group(g, s));
+    GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
+  }
+  GP_TRY(launch_chain_collect_group(g, n_steps, s));
+  GP_HIP(hipStreamSynchronize(s));
+  for (int u = 0; u < nu; ++u)
+    for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[(size_t)u * n_steps * CHAIN_REC + i] = ctxs[u]->chain_host[i];
+  return 0;
+}
+
 int gpfit_estep_chain_full(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_t N, const double* r,
                            const double* kv0, double* m, double* f, double* V_out, int64_t ldv, double* lam_m,
                            double* lam_var, double logA0, int lambda0_mode, double lambda0_fixed, int n_steps,
                            int max_iter, int history_size, double lr, double tol_grad, double tol_change,
                            double* rec_host) {
-  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS) {
-    set_error("gpfit_estep_chain_full: n_steps " + std::to_string(n_steps) + " is not within 1 .. " +
-              std::to_string(CHAIN_MAX_STEPS));
-    return -3;
-  }
-  if (!c || !K || !r || !kv0 || !m || !f || !V_out || !lam_m || !lam_var || !rec_host || N <= 0 || N > INT32_MAX ||
-      ldk < N || ldv < N) {
-    set_error("gpfit_estep_chain_full: bad argument");
-    return -3;
-  }
-  Lbfgs1dConfig cfg;
-  GP_TRY(fparam_lbfgs_config("gpfit_estep_chain_full", max_iter, history_size, lr, tol_grad, tol_change, &cfg));
-  GP_CTX_ENTER(c, "gpfit_estep_chain_full");
-  hipStream_t s = (hipStream_t)stream;
-  const int n = (int)N, np = (int)round_up(N, TILE);
-  if (np > c->np_cap) {
-    set_error("gpfit_estep_chain_full: problem larger than the context capacity");
-    return -3;
-  }
-  const int64_t ld = np;
-  // the work vectors and matrices of gpfit_estep
-  double *sv = c->yv, *rhs = c->bv, *mo = c->tvec, *Vw = c->Wbuf;
-  const Lane lane = main_lane(c, s);
-  ChainGroupT g{};
-  g.n_units = 1; g.n = n; g.ld = ld;
-  g.nb.v[0] = n; g.kmax = n;
-  g.r.v[0] = r; g.m.v[0] = m; g.f.v[0] = f; g.V.v[0] = V_out; g.ldv.v[0] = ldv; g.lam_m.v[0] = lam_m; g.lam_var.v[0] = lam_var;
-  g.logA0.v[0] = logA0; g.lambda0.v[0] = lambda0_mode ? lambda0_fixed : 0.0;
-  g.blk.v[0] = c->chain; g.info.v[0] = c->info; g.rec_host.v[0] = c->chain_host;
-  g.mo.v[0] = mo; g.Vw.v[0] = Vw;
-  const ChainGate gate{&c->chain->stop, c->info + INFO_K};
-  GP_TRY(launch_chain_init_group(g, n_steps, s));
-  for (int step = 0; step < n_steps; ++step) {
-    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
-    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
-    GP_TRY(launch_estep_prep_chain(f, r, m, n, np, c->chain, step, c->info, sv, rhs, s));
-    // M = I + S K S (lower), SK = S K (dense), Kl = K (lower): Kl is overwritten by V, so it is rebuilt every step
-    GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, Vw, ld, s));
-    GP_TRY(full_update_factor(c, np, lane));
-    GP_TRY(launch_chain_info_group(g, step, s));
-    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
-    GP_TRY(full_update_products(c, np, lane));
-    GP_TRY(launch_symv_lower(Vw, ld, n, rhs, mo, s));
-    GP_TRY(launch_chain_copy_group(g, s));
-    GP_TRY(launch_unpack_sym_chain_group(g, s));
-    GP_TRY(launch_estep_full_moments_chain(gate, mo, Vw, ld, kv0, n, lam_m, lam_var, s));
-    GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
-  }
-  GP_TRY(launch_chain_collect_group(g, n_steps, s));
-  GP_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[i] = c->chain_host[i];
-  return 0;
+  // the group of one (estep_chain_full_group_impl): a unit's numbers are the same alone and in any group
+  return estep_chain_full_group_impl("gpfit_estep_chain_full", &c, 1, stream, &K, &ldk, N, &r, &kv0, &m, &f, &V_out, &ldv,
+                                     &lam_m, &lam_var, &logA0, lambda0_mode, &lambda0_fixed, n_steps, max_iter, history_size,
+                                     lr, tol_grad, tol_change, rec_host);
+}
+
+int gpfit_estep_chain_full_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* K,
+                                 const int64_t* ldk, int64_t N, const double* const* r, const double* const* kv0,
+                                 double* const* m, double* const* f, double* const* V, const int64_t* ldv,
+                                 double* const* lam_m, double* const* lam_var, const double* logA0, int lambda0_mode,
+                                 const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                                 double tol_grad, double tol_change, double* rec_host) {
+  return estep_chain_full_group_impl("gpfit_estep_chain_full_batch", ctxs, n_units, stream, K, ldk, N, r, kv0, m, f, V, ldv,
+                                     lam_m, lam_var, logA0, lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr,
+                                     tol_grad, tol_change, rec_host);
 }
 
 int gpfit_fparam_lbfgs_host(const double* lam_m, const double* lam_var, const double* r, int64_t N, double logA0,

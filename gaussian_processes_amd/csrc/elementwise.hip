@@ -1295,15 +1295,18 @@ __global__ void estep_prep_kernel(const double* __restrict__ f, const double* __
                                   double* __restrict__ rhs) {
   estep_prep_body(f, r, m, n, np, A, sv, rhs);
 }
-// A step of gpfit_estep_chain_full: A = exp(logA) of the chain block, recorded for the caller while the chain runs; the
-// context's four info words are zeroed here, by the first kernel of the step (as estep_proj_rows_chain_group_kernel does)
-__global__ void estep_prep_chain_kernel(const double* __restrict__ f, const double* __restrict__ r,
-                                        const double* __restrict__ m, int n, int np, ChainBlock* __restrict__ blk, int step,
-                                        int* __restrict__ info, double* __restrict__ sv, double* __restrict__ rhs) {
+// A step of gpfit_estep_chain_full / _batch (unit u = blockIdx.y): A = exp(logA) of the unit's chain block, recorded for
+// the caller while the chain runs; the context's four info words are zeroed here, by the first kernel of the step (as
+// estep_proj_rows_chain_group_kernel does)
+__global__ void estep_prep_chain_group_kernel(PerUnit<double*> f, PerUnit<const double*> r, PerUnit<double*> m, int n, int np,
+                                              PerUnit<ChainBlock*> blks, int step, PerUnit<int*> infos, PerUnit<double*> sv,
+                                              PerUnit<double*> rhs) {
+  const int u = blockIdx.y;
+  ChainBlock* __restrict__ blk = blks[u];
   const double A = exp(blk->logA);
   if (blockIdx.x == 0 && threadIdx.x == 0 && blk->stop == 0) blk->rec[step][CR_A] = A;
-  if (blockIdx.x == 0 && threadIdx.x < 4) info[threadIdx.x] = 0;
-  estep_prep_body(f, r, m, n, np, A, sv, rhs);
+  if (blockIdx.x == 0 && threadIdx.x < 4) infos[u][threadIdx.x] = 0;
+  estep_prep_body(f[u], r[u], m[u], n, np, A, sv[u], rhs[u]);
 }
 
 int launch_estep_prep(const double* f, const double* r, const double* m, int n, int np, double A, double* sv,
@@ -1312,18 +1315,20 @@ int launch_estep_prep(const double* f, const double* r, const double* m, int n, 
   GP_HIP(hipGetLastError());
   return 0;
 }
-int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, ChainBlock* blk, int step,
-                            int* info, double* sv, double* rhs, hipStream_t s) {
-  hipLaunchKernelGGL(estep_prep_chain_kernel, dim3((np + 255) / 256), dim3(256), 0, s, f, r, m, n, np, blk, step, info, sv, rhs);
+int launch_estep_prep_chain_group(const ChainGroupT& g, int step, hipStream_t s) {
+  hipLaunchKernelGGL(estep_prep_chain_group_kernel, dim3((g.npc + 255) / 256, g.n_units), dim3(256), 0, s, g.f, g.r, g.m, g.n,
+                     g.npc, g.blk, step, g.info, g.sv, g.u);
   GP_HIP(hipGetLastError());
   return 0;
 }
 
 // M = I + diag(s) K diag(s) (lower 128-tiles, identity padding), SK = diag(s) K (full, zero padded),
 // Kl = K (lower 128-tiles, zero padded) -- one pass over K
-__global__ void estep_build_kernel(const double* __restrict__ K, int64_t ldk, int n, const double* __restrict__ sv,
-                                   double* __restrict__ Mb, double* __restrict__ SK, double* __restrict__ Kl,
-                                   int64_t ld) {
+// (the body is shared by the single kernel and the unit-batched one: every element by the same expression, whatever
+// the grid)
+__device__ __forceinline__ void estep_build_body(const double* __restrict__ K, int64_t ldk, int n,
+                                                 const double* __restrict__ sv, double* __restrict__ Mb,
+                                                 double* __restrict__ SK, double* __restrict__ Kl, int64_t ld) {
   const int tj = blockIdx.x, ti = blockIdx.y;
   const int r0 = ti * TILE, c0 = tj * TILE;
   for (int e = threadIdx.x; e < TILE * TILE; e += blockDim.x) {
@@ -1338,10 +1343,27 @@ __global__ void estep_build_kernel(const double* __restrict__ K, int64_t ldk, in
     }
   }
 }
+__global__ void estep_build_kernel(const double* __restrict__ K, int64_t ldk, int n, const double* __restrict__ sv,
+                                   double* __restrict__ Mb, double* __restrict__ SK, double* __restrict__ Kl,
+                                   int64_t ld) {
+  estep_build_body(K, ldk, n, sv, Mb, SK, Kl, ld);
+}
+// the same pass for every unit of a group (unit u = blockIdx.z, its own K and ldk)
+__global__ void estep_build_group_kernel(PerUnit<const double*> K, PerUnit<int64_t> ldk, int n, PerUnit<double*> sv,
+                                         PerUnit<double*> Mb, PerUnit<double*> SK, PerUnit<double*> Kl, int64_t ld) {
+  const int u = blockIdx.z;
+  estep_build_body(K[u], ldk[u], n, sv[u], Mb[u], SK[u], Kl[u], ld);
+}
 
 int launch_estep_build(const double* K, int64_t ldk, int n, int np, const double* sv, double* Mb, double* SK,
                        double* Kl, int64_t ld, hipStream_t s) {
   hipLaunchKernelGGL(estep_build_kernel, dim3(np / TILE, np / TILE), dim3(256), 0, s, K, ldk, n, sv, Mb, SK, Kl, ld);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_estep_build_group(const ChainGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(estep_build_group_kernel, dim3(g.npc / TILE, g.npc / TILE, g.n_units), dim3(256), 0, s, g.K, g.ldk, g.n,
+                     g.sv, g.W, g.SK, g.Vw, g.ld);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -1395,22 +1417,23 @@ int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_
 }
 
 // ---- the small kernels of a chained E-step (kernels.h: ChainBlock, ChainGate, ChainGroupT)
-// the full-rank moments behind a committed update (gpfit_estep_chain_full; a = B = I): lam_m = m_new and
-// lam_var = (Kvec - diag K~) + diag V, the diagonal read from the lower-tile work matrix the update left
-__global__ void estep_full_moments_chain_kernel(ChainGate g, const double* __restrict__ m_new,
-                                                const double* __restrict__ Vw, int64_t ld,
-                                                const double* __restrict__ kv0, int n, double* __restrict__ lam_m,
-                                                double* __restrict__ lam_var) {
+// the full-rank moments behind a committed update (gpfit_estep_chain_full / _batch; a = B = I; unit u = blockIdx.y behind
+// its own gate): lam_m = m_new and lam_var = (Kvec - diag K~) + diag V, the diagonal read from the lower-tile work
+// matrix the update left
+__global__ void estep_full_moments_chain_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info, PerUnit<double*> m_new,
+                                                      PerUnit<double*> Vw, int64_t ld, PerUnit<const double*> kv0, int n,
+                                                      PerUnit<double*> lam_m, PerUnit<double*> lam_var) {
+  const int u = blockIdx.y;
+  const ChainGate g{&blk[u]->stop, info[u]};
   if (!g.open()) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  lam_m[i] = m_new[i];
-  lam_var[i] = kv0[i] + Vw[(int64_t)i * ld + i];
+  lam_m[u][i] = m_new[u][i];
+  lam_var[u][i] = kv0[u][i] + Vw[u][(int64_t)i * ld + i];
 }
-int launch_estep_full_moments_chain(ChainGate g, const double* m_new, const double* Vw, int64_t ld, const double* kv0,
-                                    int n, double* lam_m, double* lam_var, hipStream_t s) {
-  hipLaunchKernelGGL(estep_full_moments_chain_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g, m_new, Vw, ld, kv0, n,
-                     lam_m, lam_var);
+int launch_estep_full_moments_chain_group(const ChainGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(estep_full_moments_chain_group_kernel, dim3((g.n + 255) / 256, g.n_units), dim3(256), 0, s, g.blk, g.info,
+                     g.mo, g.Vw, g.ld, g.kv0, g.n, g.lam_m, g.lam_var);
   GP_HIP(hipGetLastError());
   return 0;
 }

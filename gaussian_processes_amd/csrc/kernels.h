@@ -201,8 +201,8 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
                         int lambda0_mode, double lambda0_fixed, const Lbfgs1dConfig& cfg, double* f, double* out,
                         hipStream_t s);
 
-// ---- chained E-steps (gpfit_estep_chain, gpfit_estep_chain_batch, gpfit_estep_chain_full): nEstep x (Newton update,
-// moments, rate-parameter L-BFGS) enqueued in one go.  What a step hands to the next stays on the device in a ChainBlock;
+// ---- chained E-steps (gpfit_estep_chain, gpfit_estep_chain_batch, gpfit_estep_chain_full, gpfit_estep_chain_full_batch):
+// nEstep x (Newton update, moments, rate-parameter L-BFGS) enqueued in one go.  What a step hands to the next stays on the device in a ChainBlock;
 // no kernel waits on another, every launch that makes a step visible to the caller tests the gate first.
 // ONE family of kernels for one chain and for the chains of several independent units in lock step: the single call is
 // the group of one.  Every small kernel of a step is one launch for the group, with the unit on a free grid dimension and
@@ -237,7 +237,8 @@ struct PerUnit {
   __host__ __device__ __forceinline__ T operator[](int u) const { return v[u]; }
 };
 // The group as the host describes it once per call; every launcher hands its kernel the tables that kernel reads.
-// (gpfit_estep_chain_full fills what the bookkeeping and the commits read, for one unit with nb = n.)
+// (The full-rank chain fills what the bookkeeping, the commits and its own three kernels read, with nb = n and
+// nrows = npc = round_up(n, 128).)
 struct ChainGroupT {
   int n_units, n, nrows, npc, kmax;   // shared: training points, their padding, the padded basis size; the largest nb
   int64_t ld;                         // leading dimension of the work matrices (= npc)
@@ -251,6 +252,10 @@ struct ChainGroupT {
   PerUnit<double*> rec_host;          // the context's pinned, device-visible chain_host
   // the work vectors and matrices of gpfit_estep_projected, per context
   PerUnit<double*> sv, u, t2, z1, z, mo, Y, Lp, Vw, part, aLp, Zm, W, Li, trmv_part;
+  // the full-rank chain only: K[n][ldk] of gpfit_estep and the work matrix of S K
+  PerUnit<const double*> K;
+  PerUnit<int64_t> ldk;
+  PerUnit<double*> SK;
 };
 // block <- (logA0, lambda0, stop = 0) and the first n_steps records zeroed
 int launch_chain_init_group(const ChainGroupT& g, int n_steps, hipStream_t s);
@@ -270,14 +275,15 @@ int launch_estep_proj_moments_chain_group(const ChainGroupT& g, hipStream_t s);
 int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s);
 // the first n_steps records of every unit into its rec_host (one launch instead of a copy command per unit)
 int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s);
-// the two kernels of the full-rank step only (gpfit_estep_chain_full, one unit): launch_estep_prep with A =
-// exp(blk->logA) formed on the device (the same body: equal A, equal bits), rec[step][CR_A] <- A unless the chain has
-// stopped, the four info words zeroed; and, behind the gate, the moments of the original basis, lam_m <- m_new,
-// lam_var <- kv0 + diag(Vw) (Vw: the lower-tile work matrix holding V)
-int launch_estep_prep_chain(const double* f, const double* r, const double* m, int n, int np, ChainBlock* blk, int step,
-                            int* info, double* sv, double* rhs, hipStream_t s);
-int launch_estep_full_moments_chain(ChainGate g, const double* m_new, const double* Vw, int64_t ld, const double* kv0,
-                                    int n, double* lam_m, double* lam_var, hipStream_t s);
+// the three kernels of the full-rank step only (gpfit_estep_chain_full, gpfit_estep_chain_full_batch), unit-batched like
+// the rest: launch_estep_prep with A = exp(blk->logA) formed on the device (the same body: equal A, equal bits) into
+// sv / u (the right-hand side), rec[step][CR_A] <- A unless the chain has stopped, the four info words zeroed;
+// launch_estep_build (the same body) from each unit's K / ldk into W (M), SK and Vw (K's lower tiles); and, behind the
+// gate, the moments of the original basis, lam_m <- mo, lam_var <- kv0 + diag(Vw) (Vw: the lower-tile work matrix
+// holding V)
+int launch_estep_prep_chain_group(const ChainGroupT& g, int step, hipStream_t s);
+int launch_estep_build_group(const ChainGroupT& g, hipStream_t s);
+int launch_estep_full_moments_chain_group(const ChainGroupT& g, hipStream_t s);
 // the unit-batched forms of the general kernels a step uses (common sizes and leading dimensions unless per unit)
 int launch_pack_lower_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
                             int64_t ldd, int np, hipStream_t s);

@@ -666,23 +666,15 @@ def _estep_chain_full(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps
     kv0 + diag(V)`` with ``kv0 = Kvec - diag(K~)``, then ``_fparam_lbfgs``) as ONE device call and one wait
     (``gpfit_estep_chain_full``).  Returns what ``_estep_chain`` returns: copies ``(m, V, lambda_m, lambda_var, f,
     records)`` of the state behind the last step that committed, the arguments left alone; ``lambda0_fixed`` as there.
-    The call goes out on this thread's workspace, also under ``varGP_cells`` (no lock-step group form: a full-rank fit
-    keeps its turn until it ends).  ``_estep_chain_full_commit`` turns the records into f_params or into the error of
-    the first failing step."""
-    r, K, kv0 = (_cu(t).contiguous() for t in (r, K_tilde, kv0))
-    N = int(K.shape[0])
-    m, f, V, lam_m, lam_var = _chain_state(m, f_mean, V, lambda_m, lambda_var, N, N, K.device)
-    n_steps, nfp = int(n_steps), int(n_fparam_steps)
-    fixed = lambda0_fixed is not None
-    rec = (ctypes.c_double * (12 * max(n_steps, 1)))()
-    eng = get_engine(N, 1)
-    _lib.check(_lib.load().gpfit_estep_chain_full(eng._ctx, _stream(), K.data_ptr(), K.stride(0), N, r.data_ptr(),
-                                                  kv0.data_ptr(), m.data_ptr(), f.data_ptr(), V.data_ptr(), V.stride(0),
-                                                  lam_m.data_ptr(), lam_var.data_ptr(), float(logA0), 1 if fixed else 0,
-                                                  float(lambda0_fixed) if fixed else 0.0, n_steps, nfp, nfp, 0.1, 1.e-7,
-                                                  1.e-9, rec),
-               "gpfit_estep_chain_full")
-    return m, V, lam_m, lam_var, f, _chain_records(rec, n_steps)
+    In a fit of ``varGP_cells`` the device call is the wave's (unless ``FULL_RANK_GROUPS`` is off): the request goes to
+    the rendezvous and comes back as one unit of a ``gpfit_estep_chain_full_batch`` call, with the same bits.
+    ``_estep_chain_full_commit`` turns the records into f_params or into the error of the first failing step."""
+    q = _chain_full_prepare(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m,
+                            lambda_var)
+    rendezvous = getattr(_CELLS, "rendezvous", None)
+    if rendezvous is not None and FULL_RANK_GROUPS:
+        return rendezvous.call(q)
+    return _chain_full_run_single(q)
 
 
 MAX_CHAIN_UNITS = 16     # GPFIT_ESTEP_CHAIN_MAX_UNITS of the C header
@@ -701,6 +693,19 @@ def _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fpar
          "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
     q["m"], q["f"], q["V"], q["lam_m"], q["lam_var"] = _chain_state(m, f_mean, V, lambda_m, lambda_var, N, nb, dev)
     q["engine"] = engine if engine is not None else get_engine(max(N, nb), 1)
+    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    return q
+
+
+def _chain_full_prepare(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
+                        lambda_m=None, lambda_var=None, engine=None):
+    """The arguments of ``_estep_chain_full`` as one request (kind ``"chain_full"``): as ``_chain_prepare``."""
+    r, K, kv0 = (_cu(t).contiguous() for t in (r, K_tilde, kv0))
+    N = int(K.shape[0])
+    q = {"kind": "chain_full", "r": r, "K": K, "kv0": kv0, "N": N, "logA0": float(logA0), "n_steps": int(n_steps),
+         "nfp": int(n_fparam_steps), "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
+    q["m"], q["f"], q["V"], q["lam_m"], q["lam_var"] = _chain_state(m, f_mean, V, lambda_m, lambda_var, N, N, K.device)
+    q["engine"] = engine if engine is not None else get_engine(N, 1)
     q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
     return q
 
@@ -768,6 +773,64 @@ def _chain_run_group(qs):
     return [_chain_result(q, rec[u * per:(u + 1) * per]) for u, q in enumerate(qs)]
 
 
+def _chain_full_run_single(q):
+    """``gpfit_estep_chain_full`` on one request."""
+    rec = (ctypes.c_double * (12 * max(q["n_steps"], 1)))()
+    fixed = q["lambda0_fixed"] is not None
+    K, V = q["K"], q["V"]
+    _lib.check(_lib.load().gpfit_estep_chain_full(q["engine"]._ctx, q["stream"], K.data_ptr(), K.stride(0), q["N"],
+                                                  q["r"].data_ptr(), q["kv0"].data_ptr(), q["m"].data_ptr(),
+                                                  q["f"].data_ptr(), V.data_ptr(), V.stride(0), q["lam_m"].data_ptr(),
+                                                  q["lam_var"].data_ptr(), q["logA0"], 1 if fixed else 0,
+                                                  q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"], q["nfp"],
+                                                  0.1, 1.e-7, 1.e-9, rec),
+               "gpfit_estep_chain_full")
+    return _chain_result(q, rec)
+
+
+def _chain_full_bucket_key(q):
+    """Requests with equal keys may share one ``gpfit_estep_chain_full_batch`` call: what that call shares between its
+    units."""
+    return (q["K"].device.index, q["stream"].value, q["N"], q["n_steps"], q["nfp"], q["lambda0_fixed"] is not None)
+
+
+def _chain_full_batch_raw(ctxs, qs, rec=None):
+    """``gpfit_estep_chain_full_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return
+    code and the records, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as None
+    goes in as a null pointer, a leading dimension given as ``q["ldk"]`` / ``q["ldv"]`` replaces the tensor's; ``rec``: the
+    caller's array instead of a new one."""
+    nu = len(qs)
+
+    def ptrs(key):
+        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
+
+    def lds(key, ld):
+        return (ctypes.c_int64 * nu)(*[q[ld] if ld in q else (q["N"] if q[key] is None else q[key].stride(0)) for q in qs])
+
+    q0 = qs[0]
+    fixed = q0["lambda0_fixed"] is not None
+    rec = (ctypes.c_double * (12 * max(q0["n_steps"], 1) * max(nu, 1)))() if rec is None else rec
+    rc = _lib.load().gpfit_estep_chain_full_batch(
+        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
+        ptrs("K"), lds("K", "ldk"), q0["N"], ptrs("r"), ptrs("kv0"), ptrs("m"), ptrs("f"), ptrs("V"), lds("V", "ldv"),
+        ptrs("lam_m"), ptrs("lam_var"), _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
+        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], 0.1, 1.e-7,
+        1.e-9, rec)
+    return rc, rec
+
+
+def _chain_full_run_group(qs):
+    """One ``gpfit_estep_chain_full_batch`` call on requests of one bucket (``_chain_full_bucket_key``), each on its own
+    workspace; per request what ``_chain_full_run_single`` returns, with the same bits."""
+    if len({_chain_full_bucket_key(q) for q in qs}) != 1:
+        raise ValueError("_chain_full_run_group: the requests of one call share N, the number of steps and the optimiser's "
+                         "settings")
+    rc, rec = _chain_full_batch_raw([q["engine"]._ctx for q in qs], qs)
+    _lib.check(rc, "gpfit_estep_chain_full_batch")
+    per = 12 * qs[0]["n_steps"]
+    return [_chain_result(q, rec[u * per:(u + 1) * per]) for u, q in enumerate(qs)]
+
+
 def _group_engines(count, n, d=1, d_full=1):
     """``count`` workspaces of this thread for problems up to ``n`` stimuli (``d`` masked / ``d_full`` image pixels): its
     own (``get_engine``) and ``count - 1`` more, kept for the thread's later group calls."""
@@ -795,6 +858,20 @@ def _estep_chain_group(units, n_steps, n_fparam_steps):
                              for u, e in zip(units, engines)])
 
 
+def _estep_chain_full_group(units, n_steps, n_fparam_steps):
+    """``_estep_chain_full`` for several independent units (cells, restarts of one cell) as ONE device call
+    (``gpfit_estep_chain_full_batch``).  ``units``: one dict per unit with the arguments of ``_estep_chain_full`` by name
+    (``r``, ``K_tilde``, ``kv0``, ``m``, ``f_mean``, ``logA0`` and optionally ``lambda0_fixed``, ``V``, ``lambda_m``,
+    ``lambda_var``); 1 .. 16 units with the same number of training points, all with or all without ``lambda0_fixed``.
+    Returns, per unit, what ``_estep_chain_full`` returns for it, bit for bit: a unit that fails stops alone."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"_estep_chain_full_group: 1 .. {MAX_CHAIN_UNITS} units per call")
+    cap = max(u["K_tilde"].shape[0] for u in units)
+    engines = _group_engines(len(units), cap)
+    return _chain_full_run_group([_chain_full_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, engine=e, **u)
+                                  for u, e in zip(units, engines)])
+
+
 class _ChainRendezvous:
     """Where the fits of one ``varGP_cells`` wave meet.  Each of ``parties`` host threads runs one fit; a fit that
     reaches its E-steps hands its chain request to ``call`` and waits.  When every fit still alive has arrived, the
@@ -810,7 +887,9 @@ class _ChainRendezvous:
     ``key`` carries the kind, so two kinds never share a call.  Only the bookkeeping looks at it: calls of requests whose
     ``kind`` is ``"closure"`` are counted in ``closure_group_sizes`` / ``closure_call_seconds`` /
     ``seconds_in_closure_call``, all others (a request without a kind included) in ``group_sizes`` / ``call_seconds`` /
-    ``seconds_in_call``."""
+    ``seconds_in_call``.  The full-rank regime has two classes of its own: kind ``"chain_full"`` is counted in
+    ``full_group_sizes`` / ``full_call_seconds`` / ``seconds_in_full_call``, and a closure whose ``regime`` is ``"full"``
+    in ``full_closure_group_sizes`` / ``full_closure_call_seconds`` / ``seconds_in_full_closure_call``."""
 
     def __init__(self, parties, single, group, key, max_units=MAX_CHAIN_UNITS):
         self.cond = threading.Condition()
@@ -826,10 +905,16 @@ class _ChainRendezvous:
         self.call_seconds = []     # host wall time of every call issued (enqueue to results), as group_sizes
         self.seconds_in_call = 0.0  # summed over the fits: time between handing a request in and getting its result
         self.closure_group_sizes, self.closure_call_seconds, self.seconds_in_closure_call = [], [], 0.0
+        self.full_group_sizes, self.full_call_seconds, self.seconds_in_full_call = [], [], 0.0
+        self.full_closure_group_sizes, self.full_closure_call_seconds, self.seconds_in_full_closure_call = [], [], 0.0
 
     @staticmethod
-    def _is_closure(request):
-        return isinstance(request, dict) and request.get("kind") == "closure"
+    def _book(request):
+        """The prefix of the three counters a request is counted in."""
+        kind = request.get("kind") if isinstance(request, dict) else None
+        if kind == "closure":
+            return "full_closure_" if request.get("regime") == "full" else "closure_"
+        return "full_" if kind == "chain_full" else ""
 
     def enter(self):
         """First statement of a fit's thread: wait for the turn."""
@@ -855,10 +940,8 @@ class _ChainRendezvous:
             res = self.results.pop(ticket)
         self.turn.acquire()
         with self.cond:
-            if self._is_closure(request):
-                self.seconds_in_closure_call += time.perf_counter() - t_in
-            else:
-                self.seconds_in_call += time.perf_counter() - t_in
+            name = "seconds_in_" + self._book(request) + "call"
+            setattr(self, name, getattr(self, name) + time.perf_counter() - t_in)
         if isinstance(res, BaseException):
             raise res
         return res
@@ -871,8 +954,8 @@ class _ChainRendezvous:
         for tickets in buckets.values():
             for i in range(0, len(tickets), self.max_units):
                 part = tickets[i:i + self.max_units]
-                closure = self._is_closure(self.waiting[part[0]])
-                (self.closure_group_sizes if closure else self.group_sizes).append(len(part))
+                book = self._book(self.waiting[part[0]])
+                getattr(self, book + "group_sizes").append(len(part))
                 t_call = time.perf_counter()
                 try:
                     if len(part) == 1:
@@ -883,7 +966,7 @@ class _ChainRendezvous:
                             raise RuntimeError("the group call returned a result list of the wrong length")
                 except BaseException as err:      # handed to every participant, also a KeyboardInterrupt
                     out = [err] * len(part)
-                (self.closure_call_seconds if closure else self.call_seconds).append(time.perf_counter() - t_call)
+                getattr(self, book + "call_seconds").append(time.perf_counter() - t_call)
                 for t, res in zip(part, out):
                     self.results[t] = res
         self.waiting.clear()
@@ -920,15 +1003,17 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     are those of ``varGP`` on its own, bit for bit.  Between two chains the fits of a wave take turns, one running at a
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
     Fits that never chain (f_params carrying ``loglambda0``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
-    being waited for; a fit in the full-rank regime issues its chains (``_estep_chain_full``) directly on its own
-    workspace and is waited for until it ends.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is
+    being waited for.  A fit in the full-rank regime (inducing set = training set, every eigenvalue kept, identity
+    basis) hands in its chains (``_estep_chain_full``) in the same way: they go out as ONE ``gpfit_estep_chain_full_batch``
+    call per group of equal ``(N, nEstep, nFparamstep, lambda0 mode)`` and never share a call with the projected chains.
+    A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is
     the error of every fit in that call.  The sparse M-step closures of the wave's fits (``_closure_sparse``) meet at the
     same place: whenever every live fit waits -- some with a closure of their L-BFGS, some already with their next chain
     -- the closures go out as ONE ``gpfit_fit_eval_sparse_batch`` call per group of equal ``_closure_bucket_key`` and the
     chains as theirs.  A closure that returns the infinite loss on the host (theta outside the limits) asks nothing, and
-    the truncated-rank closures (``_closure_projected``: ``ntilde == ntrain`` with eigenvalues dropped) meet there in the same way, as ONE ``gpfit_fit_eval_projected_batch`` call per group of equal key (the regime is part of the key: the two never share a call; so is the capacity of the fit's workspace).  A fit in the full-rank regime keeps its own ``fit_eval`` calls.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
+    the truncated-rank closures (``_closure_projected``: ``ntilde == ntrain`` with eigenvalues dropped) meet there in the same way, as ONE ``gpfit_fit_eval_projected_batch`` call per group of equal key (the regime is part of the key: the two never share a call; so is the capacity of the fit's workspace).  The full-rank closures meet there as well, as ONE ``gpfit_fit_eval_batch`` call on the fits' own workspaces per group of equal ``_closure_full_bucket_key`` -- the ``reuse_V`` flag is part of it, so the first closures of an M-step and later ones never share a call; a unit whose factorisation fails is that fit's error alone.  With ``FULL_RANK_GROUPS`` off (``GPFIT_FULL_RANK_GROUPS=0``) a full-rank fit issues its chains and closures directly on its own workspace and keeps its turn until it ends.  Out of the groups stay the basis rebuilds, the loss evaluation between chain and M-step and the fp32 instance.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
     invocation, in order (1: the single call); ``last_closure_group_sizes``, ``last_closure_call_seconds`` and
-    ``last_seconds_in_closure_call``: the same for the closure calls.  The workspaces of the fits (one per concurrent fit, each of the size of
+    ``last_seconds_in_closure_call``: the same for the closure calls; the calls of the full-rank regime are counted apart, in ``last_full_group_sizes`` / ``last_full_call_seconds`` / ``last_seconds_in_full_call`` (chains) and ``last_full_closure_group_sizes`` / ``last_full_closure_call_seconds`` / ``last_seconds_in_full_closure_call`` (closures).  The workspaces of the fits (one per concurrent fit, each of the size of
     a ``varGP`` workspace) are kept for the next call; ``release_cell_workspaces()`` frees them."""
     n_fits = len(r_list)
     if len(kwargs_list) != n_fits:
@@ -941,6 +1026,8 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     grad = torch.is_grad_enabled()
     results, errors, sizes, call_seconds, in_call = [None] * n_fits, [None] * n_fits, [], [], 0.0
     closure_sizes, closure_seconds, in_closure = [], [], 0.0
+    full = {"full_group_sizes": [], "full_call_seconds": [], "seconds_in_full_call": 0.0, "full_closure_group_sizes": [],
+            "full_closure_call_seconds": [], "seconds_in_full_closure_call": 0.0}
 
     def fit(i, rendezvous):
         key = (dev.index, threading.get_ident())
@@ -979,12 +1066,16 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
         closure_sizes += rendezvous.closure_group_sizes
         closure_seconds += rendezvous.closure_call_seconds
         in_closure += rendezvous.seconds_in_closure_call
+        for name in full:
+            full[name] += getattr(rendezvous, name)
     varGP_cells.last_group_sizes = sizes
     varGP_cells.last_call_seconds = call_seconds      # host wall time of each of those calls
     varGP_cells.last_seconds_in_call = in_call        # summed over the fits: waiting for the wave plus the call
     varGP_cells.last_closure_group_sizes = closure_sizes      # the same three for the M-step closure calls
     varGP_cells.last_closure_call_seconds = closure_seconds
     varGP_cells.last_seconds_in_closure_call = in_closure
+    for name, value in full.items():          # the same six for the chains and the closures of the full-rank regime
+        setattr(varGP_cells, "last_" + name, value)
     for err in errors:
         if err is not None:
             raise err
@@ -997,6 +1088,12 @@ varGP_cells.last_seconds_in_call = 0.0
 varGP_cells.last_closure_group_sizes = []
 varGP_cells.last_closure_call_seconds = []
 varGP_cells.last_seconds_in_closure_call = 0.0
+varGP_cells.last_full_group_sizes = []
+varGP_cells.last_full_call_seconds = []
+varGP_cells.last_seconds_in_full_call = 0.0
+varGP_cells.last_full_closure_group_sizes = []
+varGP_cells.last_full_closure_call_seconds = []
+varGP_cells.last_seconds_in_full_closure_call = 0.0
 
 
 def _estep_chain_commit(records, f_params):
@@ -1370,6 +1467,10 @@ EIGTOP_BASIS = _os_mod.environ.get("GPFIT_EIGTOP_BASIS", "subspace")
 # _estep_chain_full in the full-rank regime with the identity basis) instead of two calls and two waits per update (module global read at call time; GPFIT_ESTEP_CHAIN=0 turns it off).  A = exp(logA)
 # is then the device's exp, not the host's: a fit may differ from the loop's by rounding.
 ESTEP_CHAIN = _os_mod.environ.get("GPFIT_ESTEP_CHAIN", "1") != "0"
+# Under varGP_cells the chains (_estep_chain_full) and the M-step closures of fits in the full-rank regime meet at the
+# wave's rendezvous and go out as group calls (module global read at call time; GPFIT_FULL_RANK_GROUPS=0 turns it off: such
+# a fit then issues its own calls and keeps its turn until it ends).
+FULL_RANK_GROUPS = _os_mod.environ.get("GPFIT_FULL_RANK_GROUPS", "1") != "0"
 # per host thread (the reference's active-learning notebook fits and scores on two threads): the route the last
 # call of _stabilised_basis took, and (N, EIGVAL_TOL) -> "full" | "truncated", which of the two rank checks to try
 # first -- a hint only, so one thread's history never changes what another thread's fit costs
@@ -1646,6 +1747,8 @@ def _closure_run_single(q):
     """``gpfit_fit_eval_sparse`` on one request: ``(rc, out[16])`` (a truncated request: ``gpfit_fit_eval_projected``)."""
     if q.get("regime") == "truncated":
         return _closure_projected_run_single(q)
+    if q.get("regime") == "full":
+        return _closure_full_run_single(q)
     out = (ctypes.c_double * 16)()
     x, xt, B, V = q["x"], q["xt"], q["B"], q["V_b"]
     rc_ = _lib.load().gpfit_fit_eval_sparse(q["engine"]._ctx, q["stream"], _lib.darr(q["theta"]), _lib.darr(q["lower"]),
@@ -1664,6 +1767,8 @@ def _closure_bucket_key(q):
     (``regime``) has the key of its own call, ``_closure_projected_bucket_key``, which begins with the regime."""
     if q.get("regime") == "truncated":
         return _closure_projected_bucket_key(q)
+    if q.get("regime") == "full":
+        return _closure_full_bucket_key(q)
     return (q["x"].device.index, q["stream"].value, q["N"], q["Nt"], q["x"].stride(0), q["xt"].stride(0), q["rows"], q["cols"],
             -(-q["n_kept"] // 128) * 128)
 
@@ -1700,6 +1805,8 @@ def _closure_run_group(qs):
     ``_closure_projected_run_group``.)"""
     if all(q.get("regime") == "truncated" for q in qs):
         return _closure_projected_run_group(qs)
+    if all(q.get("regime") == "full" for q in qs):
+        return _closure_full_run_group(qs)
     if len({_closure_bucket_key(q) for q in qs}) != 1:
         raise ValueError("_closure_run_group: the requests of one call share the stimuli's sizes and leading dimensions, "
                          "the pixel grid and the padded basis size")
@@ -1740,17 +1847,94 @@ def _closure_sparse_group(units):
     return res
 
 
-# what the rendezvous of varGP_cells is given: two kinds of request, each with its own calls and bucket key
+def _closure_full(theta, lims, n_px_side, x, r, m, V, f_params, reuse_V):
+    """Full-rank M-step closure (``m``, ``V`` in the original basis): ONE ``fit_eval`` call on this thread's workspace,
+    which keeps V's factor between the closures of an M-step (``reuse_V``).  In a fit of ``varGP_cells`` the device call
+    is the wave's (unless ``FULL_RANK_GROUPS`` is off): the request goes to the rendezvous and comes back as one unit of
+    a ``gpfit_fit_eval_batch`` call on the fits' own workspaces, with the same bits.  Returns the result dict of
+    ``fit_eval`` or raises what it raises.  ``theta`` is within ``lims``: the caller has checked."""
+    lower, upper = lims
+    rows, cols = _grid(n_px_side)
+    xc = _cu(x)
+    q = {"kind": "closure", "regime": "full", "theta": [float(v) for v in theta_vec(theta)],
+         "lower": [_scalar(lower[k]) for k in THETA_KEYS], "upper": [_scalar(upper[k]) for k in THETA_KEYS],
+         "n_px_side": n_px_side, "rows": rows, "cols": cols, "x": xc, "r": _cu(r), "m": _cu(m), "V": _cu(V),
+         "N": int(xc.shape[0]), "logA": _scalar(f_params['logA']), "lambda0": _scalar(_lambda0_of(f_params)),
+         "reuse_V": bool(reuse_V)}
+    q["engine"] = get_engine(q["N"], xc.shape[1], rows * cols)
+    q["cap"] = -(-q["engine"].n_max // 128) * 128
+    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    rendezvous = getattr(_CELLS, "rendezvous", None)
+    if rendezvous is not None and FULL_RANK_GROUPS:
+        return rendezvous.call(q)
+    return _closure_full_run_single(q)
+
+
+def _closure_full_run_single(q):
+    """``fit_eval`` on one full-rank request, on the request's workspace: its result dict (or its exception)."""
+    return q["engine"].fit_eval(q["theta"], q["lower"], q["upper"], q["n_px_side"], q["x"], q["r"], q["m"], q["V"], q["logA"],
+                                q["lambda0"], want_grad=True, want_vectors=False, reuse_V=q["reuse_V"])
+
+
+def _closure_full_bucket_key(q):
+    """Full-rank requests with equal keys may share one ``gpfit_fit_eval_batch`` call: the regime (the regimes never share
+    a call), what that call shares between its units -- the ``reuse_V`` flag among it: the first closures of an M-step
+    and later ones never meet in one call -- and the capacity of the workspaces."""
+    return ("full", q["x"].device.index, q["stream"].value, q["N"], q["x"].stride(0), q["V"].stride(0), q["rows"], q["cols"],
+            q["cap"], q["reuse_V"])
+
+
+def _closure_full_run_group(qs):
+    """One ``gpfit_fit_eval_batch`` call on full-rank requests of one bucket (``_closure_full_bucket_key``), each on its
+    own workspace (the one that holds its V factor); per request what ``_closure_full_run_single`` returns, with the same
+    bits -- or, in its place, the exception ``fit_eval`` raises for that unit alone (a failed factorisation).  No limits
+    go in: every request's theta has been checked on the host."""
+    if len({_closure_full_bucket_key(q) for q in qs}) != 1:
+        raise ValueError("_closure_run_group: the full-rank requests of one call share the stimuli's size and leading "
+                         "dimension, the pixel grid, the capacity of their workspaces and the reuse_V flag")
+    nu, q0 = len(qs), qs[0]
+
+    def ptrs(key):
+        return (ctypes.c_void_p * nu)(*[q[key].data_ptr() for q in qs])
+
+    out = (ctypes.c_double * (16 * nu))()
+    rcs = (ctypes.c_int * nu)()
+    rc = _lib.load().gpfit_fit_eval_batch(
+        (ctypes.c_void_p * nu)(*[q["engine"]._ctx.value for q in qs]), nu, q0["stream"],
+        _lib.darr([v for q in qs for v in q["theta"]]), None, None, q0["rows"], q0["cols"], ptrs("x"), q0["x"].stride(0),
+        q0["N"], ptrs("r"), ptrs("m"), ptrs("V"), q0["V"].stride(0), _lib.darr([q["logA"] for q in qs]),
+        _lib.darr([q["lambda0"] for q in qs]), 1 | (2 if q0["reuse_V"] else 0), out, rcs)
+    _lib.check(rc, "gpfit_fit_eval_batch")
+    res = []
+    for u, q in enumerate(qs):      # every pending unit is collected, also behind a failed one
+        ticket = {"rc": int(rcs[u]), "out": (ctypes.c_double * 16)(*out[16 * u:16 * u + 16]), "pending": rcs[u] == 0,
+                  "lam_m": None, "lam_var": None, "f": None}
+        try:
+            res.append(q["engine"].fit_eval_finish(ticket))
+        except Exception as err:    # this unit's alone
+            res.append(err)
+    return res
+
+
+# what the rendezvous of varGP_cells is given: three kinds of request, each with its own calls and bucket key
+_REQUEST_KINDS = {
+    "chain": (lambda q: _chain_run_single(q), lambda qs: _chain_run_group(qs), lambda q: _chain_bucket_key(q)),
+    "chain_full": (lambda q: _chain_full_run_single(q), lambda qs: _chain_full_run_group(qs),
+                   lambda q: _chain_full_bucket_key(q)),
+    "closure": (lambda q: _closure_run_single(q), lambda qs: _closure_run_group(qs), lambda q: _closure_bucket_key(q)),
+}
+
+
 def _request_run_single(q):
-    return _closure_run_single(q) if q["kind"] == "closure" else _chain_run_single(q)
+    return _REQUEST_KINDS[q["kind"]][0](q)
 
 
 def _request_run_group(qs):
-    return _closure_run_group(qs) if qs[0]["kind"] == "closure" else _chain_run_group(qs)
+    return _REQUEST_KINDS[qs[0]["kind"]][1](qs)
 
 
 def _request_bucket_key(q):
-    return (q["kind"],) + (_closure_bucket_key(q) if q["kind"] == "closure" else _chain_bucket_key(q))
+    return (q["kind"],) + _REQUEST_KINDS[q["kind"]][2](q)
 
 
 def _closure_sparse_steps(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params):
@@ -2231,10 +2415,7 @@ def varGP(x, r, **kwargs):
                     if outside:
                         return torch.tensor(float('inf'))
                     if fast:
-                        e = get_engine(nt, nx, nx)
-                        res = e.fit_eval(theta, theta_lower_lims, theta_higher_lims, n_px_side, x, r, m_orig, V_orig,
-                                         _scalar(f_params['logA']), _scalar(_lambda0_of(f_params)), want_grad=True,
-                                         want_vectors=False, reuse_V=v_factored[0])
+                        res = _closure_full(theta, lims, n_px_side, x, r, m_orig, V_orig, f_params, v_factored[0])
                         v_factored[0] = True  # V is constant for the rest of this M-step
                         loss, grad = res['loss'], res['grad']
                     elif same_points and not no_fast:

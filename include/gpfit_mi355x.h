@@ -391,6 +391,7 @@ int gpfit_estep_chain(gpfit_ctx* ctx, void* stream, const double* a, int64_t lda
  * A step whose M is not positive definite (info != 0) commits nothing; a step whose optimiser fails (status != 0) has
  * committed m, V and the moments, and leaves f, logA and lambda0 alone.  After either, no later step changes m, V, f,
  * lam_m, lam_var, logA or lambda0, and its record is all zero.
+ * There is one implementation for this call and gpfit_estep_chain_full_batch: the single call is the group of one.
  * Returns 0 when the chain ran, whatever the records say; -3, with nothing enqueued, on a bad argument, n_steps outside
  * its range or round_up(N, 128) above the context's capacity. */
 int gpfit_estep_chain_full(gpfit_ctx* ctx, void* stream, const double* K, int64_t ldk, int64_t N, const double* r,
@@ -419,6 +420,27 @@ int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, c
                             const int64_t* ldv, double* const* lam_m, double* const* lam_var, const double* logA0,
                             int lambda0_mode, const double* lambda0_fixed, int n_steps, int max_iter, int history_size,
                             double lr, double tol_grad, double tol_change, double* rec_host);
+
+/* gpfit_estep_chain_full for 1 .. GPFIT_ESTEP_CHAIN_FULL_MAX_UNITS independent units (cells, restarts of one cell) as ONE
+ * call: unit u runs on its own context ctxs[u] (pairwise distinct, one device) with its own K[u], r[u], kv0[u], m[u],
+ * f[u], V[u], lam_m[u], lam_var[u], leading dimensions ldk[u], ldv[u] and start logA0[u] / lambda0_fixed[u] (read when
+ * lambda0_mode is 1); N, n_steps, lambda0_mode and the optimiser's settings are shared.  Everything is enqueued on
+ * `stream`, one synchronisation at the end.  The factorisations of the units run in lock step, every product of a step
+ * is one call on the list of units and every small kernel one launch for the group, so a step costs the launches of one
+ * unit.
+ * rec_host[n_units][n_steps][12]: the records of gpfit_estep_chain_full, unit by unit.  Every output and record of unit
+ * u has the bits it has when that unit is called alone (gpfit_estep_chain_full is this call with one unit); a unit that
+ * stops (M not positive definite, optimiser failure) stops alone, exactly as there, and changes nothing in the others.
+ * Returns 0 when the chains ran, whatever the records say; -3, with nothing enqueued and nothing written, for n_units or
+ * n_steps outside their ranges, a null pointer, ldk[u] < N or ldv[u] < N, contexts on different devices, the same
+ * context twice, a context with a pending asynchronous evaluation, or round_up(N, 128) above a context's capacity. */
+#define GPFIT_ESTEP_CHAIN_FULL_MAX_UNITS 16
+int gpfit_estep_chain_full_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* K,
+                                 const int64_t* ldk, int64_t N, const double* const* r, const double* const* kv0,
+                                 double* const* m, double* const* f, double* const* V, const int64_t* ldv,
+                                 double* const* lam_m, double* const* lam_var, const double* logA0, int lambda0_mode,
+                                 const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                                 double tol_grad, double tol_change, double* rec_host);
 
 /* Active-learning utility of nstar candidate stimuli, U = H(r|x,D) - <H(r|f,x)>
  * (nd_utility with nd_p_r_given_xD, nd_lambda_r_mean, nd_mean_noise_entropy, utils.py:413-525;
