@@ -15,6 +15,7 @@ reference's dead code (``utility`` / ``get_utility`` scalar variants, ``block_ma
 """
 from __future__ import annotations
 
+import collections
 import copy
 import ctypes
 import math
@@ -624,19 +625,36 @@ def _estep_projected(r, KKtilde_inv, aL, L, m, f_params, f_mean, kv0=None):
 
 
 CHAIN_MAX_STEPS = 1024   # GPFIT_ESTEP_CHAIN_MAX_STEPS of the C header
+MAX_CHAIN_UNITS = 16     # GPFIT_ESTEP_CHAIN_MAX_UNITS of the C header
+_FPARAM_LBFGS = (0.1, 1.e-7, 1.e-9)   # lr, tol_grad, tol_change of the rate-parameter optimiser inside a chain
+_CELLS = threading.local()   # .rendezvous: the _ChainRendezvous of the varGP_cells wave this thread fits in; .engines
 
 
-def _chain_state(m, f_mean, V, lambda_m, lambda_var, N, nv, dev):
-    """The state a chain call updates in place, as copies of its own ``(m, f, V, lambda_m, lambda_var)``: the arguments
-    are left alone; ``V`` (nv x nv) and the moments (N) not given start uninitialised."""
-    def own(t, *shape):
-        return torch.empty(shape, dtype=TORCH_DTYPE, device=dev) if t is None else _cu(t).clone().contiguous()
-    return _cu(m).clone().contiguous(), _cu(f_mean).clone().contiguous(), own(V, nv, nv), own(lambda_m, N), own(lambda_var, N)
+# ------------------------------------------------------------------ requests: what a device call of a fit is made of
+# A call that the fits of a varGP_cells wave can share is prepared as a request: a dict with its ``kind`` (and, for a
+# closure, its ``regime``), the operands on the device, the scalars, and the workspace (``engine``) and stream it runs
+# on.  _REQUEST_KINDS (below the closures) describes each kind; the four helpers here marshal a list of requests into
+# the per-unit tables of a batch entry point.
+def _ctx_table(ctxs):
+    """The contexts of a batch call, given as engines' ``_ctx`` values or as raw integers."""
+    return (ctypes.c_void_p * len(ctxs))(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs])
 
 
-def _chain_records(rec, n_steps):
-    """One 12-number record per step (include/gpfit_mi355x.h) from the flat array a chain call filled."""
-    return [list(rec[12 * k:12 * k + 12]) for k in range(n_steps)]
+def _ptr_table(qs, key):
+    """One device pointer per request; a tensor given as None goes in as a null pointer."""
+    return (ctypes.c_void_p * len(qs))(*[None if q[key] is None else q[key].data_ptr() for q in qs])
+
+
+def _ld_table(qs, key, default, override=None):
+    """One leading dimension per request: ``q[override]`` where a request has that field, else the tensor's, else
+    ``q[default]`` when the tensor is None."""
+    return (ctypes.c_int64 * len(qs))(*[q[override] if override in q else (q[default] if q[key] is None else q[key].stride(0))
+                                        for q in qs])
+
+
+def _flat(qs, key):
+    """The per-request lists of floats ``q[key]``, one behind the other."""
+    return _lib.darr([v for q in qs for v in q[key]])
 
 
 def _estep_chain(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
@@ -649,14 +667,11 @@ def _estep_chain(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam
     loop there).  Returns
     copies ``(m, V, lambda_m, lambda_var, f, records)`` of the state behind the last step that ran -- the arguments are
     left alone -- and one 12-number record per step (include/gpfit_mi355x.h); ``V``, ``lambda_m``, ``lambda_var`` given
-    here are what comes back when no step commits.  ``_estep_chain_commit`` turns the records into f_params or into the
-    error of the first failing step."""
-    q = _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m,
-                       lambda_var)
-    rendezvous = getattr(_CELLS, "rendezvous", None)
-    if rendezvous is not None:      # a fit of varGP_cells: the chains of the wave's cells go out as group calls
-        return rendezvous.call(q)
-    return _chain_run_single(q)
+    here are what comes back when no step commits.  In a fit of ``varGP_cells`` the device call is the wave's
+    (``_submit``).  ``_estep_chain_commit`` turns the records into f_params or into the error of the first failing
+    step."""
+    return _submit(_chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V,
+                                  lambda_m, lambda_var))
 
 
 def _estep_chain_full(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
@@ -669,54 +684,65 @@ def _estep_chain_full(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps
     In a fit of ``varGP_cells`` the device call is the wave's (unless ``FULL_RANK_GROUPS`` is off): the request goes to
     the rendezvous and comes back as one unit of a ``gpfit_estep_chain_full_batch`` call, with the same bits.
     ``_estep_chain_full_commit`` turns the records into f_params or into the error of the first failing step."""
-    q = _chain_full_prepare(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m,
-                            lambda_var)
-    rendezvous = getattr(_CELLS, "rendezvous", None)
-    if rendezvous is not None and FULL_RANK_GROUPS:
-        return rendezvous.call(q)
-    return _chain_full_run_single(q)
+    return _submit(_chain_full_prepare(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V,
+                                       lambda_m, lambda_var))
 
 
-MAX_CHAIN_UNITS = 16     # GPFIT_ESTEP_CHAIN_MAX_UNITS of the C header
-_CELLS = threading.local()   # .rendezvous: the _ChainRendezvous of the varGP_cells wave this thread fits in; .engines
+def _chain_request(kind, operands, N, nv, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m, lambda_var,
+                   engine):
+    """What the requests of the two chain kinds share: the fixed ``operands`` (name -> tensor, contiguous on the device),
+    the scalars, the state ``(m, f, V, lam_m, lam_var)`` as copies of its own -- the call updates them in place, the
+    arguments are left alone; ``V`` (nv x nv) and the moments (N) not given start uninitialised -- and the workspace and
+    stream the call runs on, this thread's unless an engine is given."""
+    dev = operands["r"].device
+
+    def own(t, *shape):
+        return torch.empty(shape, dtype=TORCH_DTYPE, device=dev) if t is None else _cu(t).clone().contiguous()
+    q = {"kind": kind, **operands, "N": int(N), "logA0": float(logA0), "n_steps": int(n_steps), "nfp": int(n_fparam_steps),
+         "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
+    q["m"], q["f"] = _cu(m).clone().contiguous(), _cu(f_mean).clone().contiguous()
+    q["V"], q["lam_m"], q["lam_var"] = own(V, nv, nv), own(lambda_m, N), own(lambda_var, N)
+    q["engine"] = engine if engine is not None else get_engine(max(N, nv), 1)
+    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    return q
 
 
 def _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
                    lambda_m=None, lambda_var=None, engine=None):
-    """The arguments of ``_estep_chain`` as one request: fixed operands contiguous on the device, the state cloned (the
-    call updates its copies in place), and the workspace the call runs on -- this thread's unless one is given."""
+    """The arguments of ``_estep_chain`` as one request (kind ``"chain"``, ``_chain_request``)."""
     r, a, aL, L, kv0 = (_cu(t).contiguous() for t in (r, KKtilde_inv, aL, L, kv0))
     N, nb = a.shape
-    dev = a.device
-    q = {"kind": "chain", "r": r, "a": a, "aL": aL, "L": L, "kv0": kv0, "N": int(N), "nb": int(nb), "logA0": float(logA0),
-         "n_steps": int(n_steps), "nfp": int(n_fparam_steps),
-         "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
-    q["m"], q["f"], q["V"], q["lam_m"], q["lam_var"] = _chain_state(m, f_mean, V, lambda_m, lambda_var, N, nb, dev)
-    q["engine"] = engine if engine is not None else get_engine(max(N, nb), 1)
-    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    q = _chain_request("chain", {"r": r, "a": a, "aL": aL, "L": L, "kv0": kv0}, N, nb, m, f_mean, logA0, n_steps,
+                       n_fparam_steps, lambda0_fixed, V, lambda_m, lambda_var, engine)
+    q["nb"] = int(nb)
     return q
 
 
 def _chain_full_prepare(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
                         lambda_m=None, lambda_var=None, engine=None):
-    """The arguments of ``_estep_chain_full`` as one request (kind ``"chain_full"``): as ``_chain_prepare``."""
+    """The arguments of ``_estep_chain_full`` as one request (kind ``"chain_full"``, ``_chain_request``)."""
     r, K, kv0 = (_cu(t).contiguous() for t in (r, K_tilde, kv0))
     N = int(K.shape[0])
-    q = {"kind": "chain_full", "r": r, "K": K, "kv0": kv0, "N": N, "logA0": float(logA0), "n_steps": int(n_steps),
-         "nfp": int(n_fparam_steps), "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
-    q["m"], q["f"], q["V"], q["lam_m"], q["lam_var"] = _chain_state(m, f_mean, V, lambda_m, lambda_var, N, N, K.device)
-    q["engine"] = engine if engine is not None else get_engine(N, 1)
-    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
-    return q
+    return _chain_request("chain_full", {"r": r, "K": K, "kv0": kv0}, N, N, m, f_mean, logA0, n_steps, n_fparam_steps,
+                          lambda0_fixed, V, lambda_m, lambda_var, engine)
 
 
-def _chain_result(q, rec):
-    return q["m"], q["V"], q["lam_m"], q["lam_var"], q["f"], _chain_records(rec, q["n_steps"])
+def _chain_rec_array(q, n_units=1):
+    """The array a chain call on ``n_units`` requests like ``q`` fills: one 12-number record (include/gpfit_mi355x.h) per
+    step and unit."""
+    return (ctypes.c_double * (12 * max(q["n_steps"], 1) * max(n_units, 1)))()
+
+
+def _chain_result(q, u, rec):
+    """What a chain call returns for its unit ``u``: the request's state, and the unit's records cut out of the flat
+    array (a single call is unit 0 of its own array)."""
+    first, n = 12 * q["n_steps"] * u, q["n_steps"]
+    return q["m"], q["V"], q["lam_m"], q["lam_var"], q["f"], [list(rec[first + 12 * k:first + 12 * k + 12]) for k in range(n)]
 
 
 def _chain_run_single(q):
     """``gpfit_estep_chain`` on one request."""
-    rec = (ctypes.c_double * (12 * max(q["n_steps"], 1)))()
+    rec = _chain_rec_array(q)
     fixed = q["lambda0_fixed"] is not None
     a, aL, L, V = q["a"], q["aL"], q["L"], q["V"]
     _lib.check(_lib.load().gpfit_estep_chain(q["engine"]._ctx, q["stream"], a.data_ptr(), a.stride(0), aL.data_ptr(),
@@ -724,9 +750,24 @@ def _chain_run_single(q):
                                              q["kv0"].data_ptr(), q["m"].data_ptr(), q["f"].data_ptr(), V.data_ptr(),
                                              V.stride(0), q["lam_m"].data_ptr(), q["lam_var"].data_ptr(), q["logA0"],
                                              1 if fixed else 0, q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"],
-                                             q["nfp"], 0.1, 1.e-7, 1.e-9, rec),
+                                             q["nfp"], *_FPARAM_LBFGS, rec),
                "gpfit_estep_chain")
-    return _chain_result(q, rec)
+    return _chain_result(q, 0, rec)
+
+
+def _chain_full_run_single(q):
+    """``gpfit_estep_chain_full`` on one request."""
+    rec = _chain_rec_array(q)
+    fixed = q["lambda0_fixed"] is not None
+    K, V = q["K"], q["V"]
+    _lib.check(_lib.load().gpfit_estep_chain_full(q["engine"]._ctx, q["stream"], K.data_ptr(), K.stride(0), q["N"],
+                                                  q["r"].data_ptr(), q["kv0"].data_ptr(), q["m"].data_ptr(),
+                                                  q["f"].data_ptr(), V.data_ptr(), V.stride(0), q["lam_m"].data_ptr(),
+                                                  q["lam_var"].data_ptr(), q["logA0"], 1 if fixed else 0,
+                                                  q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"], q["nfp"],
+                                                  *_FPARAM_LBFGS, rec),
+               "gpfit_estep_chain_full")
+    return _chain_result(q, 0, rec)
 
 
 def _chain_bucket_key(q):
@@ -736,62 +777,28 @@ def _chain_bucket_key(q):
             q["lambda0_fixed"] is not None)
 
 
-def _chain_batch_raw(ctxs, qs):
-    """``gpfit_estep_chain_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return code
-    and the records, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as None goes
-    in as a null pointer."""
-    nu = len(qs)
-
-    def ptrs(key):
-        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
-
-    def lds(key):
-        return (ctypes.c_int64 * nu)(*[q["nb"] if q[key] is None else q[key].stride(0) for q in qs])
-
-    q0 = qs[0]
-    fixed = q0["lambda0_fixed"] is not None
-    rec = (ctypes.c_double * (12 * max(q0["n_steps"], 1) * nu))()
-    rc = _lib.load().gpfit_estep_chain_batch(
-        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
-        ptrs("a"), lds("a"), ptrs("aL"), lds("aL"), ptrs("L"), lds("L"), q0["N"],
-        (ctypes.c_int64 * nu)(*[q["nb"] for q in qs]), ptrs("r"), ptrs("kv0"), ptrs("m"), ptrs("f"), ptrs("V"), lds("V"),
-        ptrs("lam_m"), ptrs("lam_var"), _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
-        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], 0.1, 1.e-7,
-        1.e-9, rec)
-    return rc, rec
-
-
-def _chain_run_group(qs):
-    """One ``gpfit_estep_chain_batch`` call on requests of one bucket (``_chain_bucket_key``), each on its own
-    workspace; per request what ``_chain_run_single`` returns, with the same bits."""
-    if len({_chain_bucket_key(q) for q in qs}) != 1:
-        raise ValueError("_chain_run_group: the requests of one call share N, the padded basis size, the number of steps "
-                         "and the optimiser's settings")
-    rc, rec = _chain_batch_raw([q["engine"]._ctx for q in qs], qs)
-    _lib.check(rc, "gpfit_estep_chain_batch")
-    per = 12 * qs[0]["n_steps"]
-    return [_chain_result(q, rec[u * per:(u + 1) * per]) for u, q in enumerate(qs)]
-
-
-def _chain_full_run_single(q):
-    """``gpfit_estep_chain_full`` on one request."""
-    rec = (ctypes.c_double * (12 * max(q["n_steps"], 1)))()
-    fixed = q["lambda0_fixed"] is not None
-    K, V = q["K"], q["V"]
-    _lib.check(_lib.load().gpfit_estep_chain_full(q["engine"]._ctx, q["stream"], K.data_ptr(), K.stride(0), q["N"],
-                                                  q["r"].data_ptr(), q["kv0"].data_ptr(), q["m"].data_ptr(),
-                                                  q["f"].data_ptr(), V.data_ptr(), V.stride(0), q["lam_m"].data_ptr(),
-                                                  q["lam_var"].data_ptr(), q["logA0"], 1 if fixed else 0,
-                                                  q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"], q["nfp"],
-                                                  0.1, 1.e-7, 1.e-9, rec),
-               "gpfit_estep_chain_full")
-    return _chain_result(q, rec)
-
-
 def _chain_full_bucket_key(q):
     """Requests with equal keys may share one ``gpfit_estep_chain_full_batch`` call: what that call shares between its
     units."""
     return (q["K"].device.index, q["stream"].value, q["N"], q["n_steps"], q["nfp"], q["lambda0_fixed"] is not None)
+
+
+def _chain_batch_raw(ctxs, qs, rec=None):
+    """``gpfit_estep_chain_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return code
+    and the records, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as None goes
+    in as a null pointer; ``rec``: the caller's array instead of a new one."""
+    q0 = qs[0]
+    fixed = q0["lambda0_fixed"] is not None
+    rec = _chain_rec_array(q0, len(qs)) if rec is None else rec
+    rc = _lib.load().gpfit_estep_chain_batch(
+        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "a"), _ld_table(qs, "a", "nb"), _ptr_table(qs, "aL"),
+        _ld_table(qs, "aL", "nb"), _ptr_table(qs, "L"), _ld_table(qs, "L", "nb"), q0["N"],
+        (ctypes.c_int64 * len(qs))(*[q["nb"] for q in qs]), _ptr_table(qs, "r"), _ptr_table(qs, "kv0"), _ptr_table(qs, "m"),
+        _ptr_table(qs, "f"), _ptr_table(qs, "V"), _ld_table(qs, "V", "nb"), _ptr_table(qs, "lam_m"), _ptr_table(qs, "lam_var"),
+        _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
+        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], *_FPARAM_LBFGS,
+        rec)
+    return rc, rec
 
 
 def _chain_full_batch_raw(ctxs, qs, rec=None):
@@ -799,48 +806,59 @@ def _chain_full_batch_raw(ctxs, qs, rec=None):
     code and the records, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as None
     goes in as a null pointer, a leading dimension given as ``q["ldk"]`` / ``q["ldv"]`` replaces the tensor's; ``rec``: the
     caller's array instead of a new one."""
-    nu = len(qs)
-
-    def ptrs(key):
-        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
-
-    def lds(key, ld):
-        return (ctypes.c_int64 * nu)(*[q[ld] if ld in q else (q["N"] if q[key] is None else q[key].stride(0)) for q in qs])
-
     q0 = qs[0]
     fixed = q0["lambda0_fixed"] is not None
-    rec = (ctypes.c_double * (12 * max(q0["n_steps"], 1) * max(nu, 1)))() if rec is None else rec
+    rec = _chain_rec_array(q0, len(qs)) if rec is None else rec
     rc = _lib.load().gpfit_estep_chain_full_batch(
-        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
-        ptrs("K"), lds("K", "ldk"), q0["N"], ptrs("r"), ptrs("kv0"), ptrs("m"), ptrs("f"), ptrs("V"), lds("V", "ldv"),
-        ptrs("lam_m"), ptrs("lam_var"), _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
-        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], 0.1, 1.e-7,
-        1.e-9, rec)
+        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "K"), _ld_table(qs, "K", "N", "ldk"), q0["N"],
+        _ptr_table(qs, "r"), _ptr_table(qs, "kv0"), _ptr_table(qs, "m"), _ptr_table(qs, "f"), _ptr_table(qs, "V"),
+        _ld_table(qs, "V", "N", "ldv"), _ptr_table(qs, "lam_m"), _ptr_table(qs, "lam_var"),
+        _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
+        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], *_FPARAM_LBFGS,
+        rec)
     return rc, rec
 
 
-def _chain_full_run_group(qs):
-    """One ``gpfit_estep_chain_full_batch`` call on requests of one bucket (``_chain_full_bucket_key``), each on its own
-    workspace; per request what ``_chain_full_run_single`` returns, with the same bits."""
-    if len({_chain_full_bucket_key(q) for q in qs}) != 1:
-        raise ValueError("_chain_full_run_group: the requests of one call share N, the number of steps and the optimiser's "
-                         "settings")
-    rc, rec = _chain_full_batch_raw([q["engine"]._ctx for q in qs], qs)
-    _lib.check(rc, "gpfit_estep_chain_full_batch")
-    per = 12 * qs[0]["n_steps"]
-    return [_chain_result(q, rec[u * per:(u + 1) * per]) for u, q in enumerate(qs)]
-
-
-def _group_engines(count, n, d=1, d_full=1):
+def _group_engines(count, n, d=1, d_full=1, exact=False):
     """``count`` workspaces of this thread for problems up to ``n`` stimuli (``d`` masked / ``d_full`` image pixels): its
-    own (``get_engine``) and ``count - 1`` more, kept for the thread's later group calls."""
+    own (``get_engine``), then kept ones that fit, then new ones, which are kept for the thread's later group calls.
+    ``exact``: every workspace of the call has the capacity of one created for exactly these ``n`` stimuli, whatever
+    the size of the thread's own (a closure's slab counts and the route of its lift, hence its last bits, depend on the
+    capacity)."""
     own = get_engine(n, d, d_full)
     kept = getattr(_CELLS, "engines", [])
-    extra = [e for e in kept if e.n_max >= n and e.d_max >= d and e.d_full_max >= d_full and e.device == own.device]
-    while len(extra) < count - 1:
-        extra.append(GPFitEngine(n, d, d_full, device=own.device))
-    _CELLS.engines = extra + [e for e in kept if e not in extra]
-    return [own] + extra[:count - 1]
+
+    def fits(e):
+        n_fits = -(-e.n_max // 128) == -(-n // 128) if exact else e.n_max >= n
+        return n_fits and e.d_max >= d and e.d_full_max >= d_full and e.device == own.device
+    mine = [own] if fits(own) else []      # without ``exact`` it always fits
+    fitting = [e for e in kept if fits(e)]
+    new = [GPFitEngine(n, d, d_full, device=own.device) for _ in range(count - len(mine) - len(fitting))]
+    # the order of the kept list decides which workspaces a later call of another size meets first: it stays what each
+    # rule has always left behind
+    _CELLS.engines = kept + new if exact else fitting + new + [e for e in kept if e not in fitting]
+    return (mine + fitting + new)[:count]
+
+
+def _units_group(name, units, size, prepare, steps=None, exact=False):
+    """What the four ``*_group(units)`` functions share: 1 .. 16 units, one workspace each (``size(units)``: ``n, d,
+    d_full`` of ``_group_engines``), one request each (``prepare(engine=..., **unit)``) and one device call.  Chains
+    (``steps`` None) go to the batch entry point whatever their number: what ``_request_run_group`` returns.  A closure
+    alone goes to the single entry point, and every closure is finished (``_closure_finish`` with ``steps``): a unit
+    whose call would raise has the exception in its place."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"{name}: 1 .. {MAX_CHAIN_UNITS} units per call")
+    engines = _group_engines(len(units), *size(units), exact=exact)
+    qs = [prepare(engine=e, **u) for u, e in zip(units, engines)]
+    if steps is None:
+        return _request_run_group(qs)
+    res = []
+    for q, (rc_, out) in zip(qs, _request_run_group(qs) if len(qs) > 1 else [_request_run_single(qs[0])]):
+        try:
+            res.append(_closure_finish(q, rc_, out, steps))
+        except Exception as err:      # what the closure raises for this unit alone
+            res.append(err)
+    return res
 
 
 def _estep_chain_group(units, n_steps, n_fparam_steps):
@@ -850,12 +868,8 @@ def _estep_chain_group(units, n_steps, n_fparam_steps):
     ``lambda_m``, ``lambda_var``); 1 .. 16 units with the same number of training points and the same
     ``round_up(nb, 128)``, all with or all without ``lambda0_fixed``.  Returns, per unit, what ``_estep_chain`` returns
     for it, bit for bit: a unit that fails stops alone."""
-    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
-        raise ValueError(f"_estep_chain_group: 1 .. {MAX_CHAIN_UNITS} units per call")
-    cap = max(max(u["KKtilde_inv"].shape) for u in units)
-    engines = _group_engines(len(units), cap)
-    return _chain_run_group([_chain_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, engine=e, **u)
-                             for u, e in zip(units, engines)])
+    return _units_group("_estep_chain_group", units, lambda us: (max(max(u["KKtilde_inv"].shape) for u in us),),
+                        lambda **u: _chain_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, **u))
 
 
 def _estep_chain_full_group(units, n_steps, n_fparam_steps):
@@ -864,12 +878,11 @@ def _estep_chain_full_group(units, n_steps, n_fparam_steps):
     (``r``, ``K_tilde``, ``kv0``, ``m``, ``f_mean``, ``logA0`` and optionally ``lambda0_fixed``, ``V``, ``lambda_m``,
     ``lambda_var``); 1 .. 16 units with the same number of training points, all with or all without ``lambda0_fixed``.
     Returns, per unit, what ``_estep_chain_full`` returns for it, bit for bit: a unit that fails stops alone."""
-    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
-        raise ValueError(f"_estep_chain_full_group: 1 .. {MAX_CHAIN_UNITS} units per call")
-    cap = max(u["K_tilde"].shape[0] for u in units)
-    engines = _group_engines(len(units), cap)
-    return _chain_full_run_group([_chain_full_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, engine=e, **u)
-                                  for u, e in zip(units, engines)])
+    return _units_group("_estep_chain_full_group", units, lambda us: (max(u["K_tilde"].shape[0] for u in us),),
+                        lambda **u: _chain_full_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, **u))
+
+
+_BOOKS = ("", "closure_", "full_", "full_closure_")   # the prefixes of the counters a call of the rendezvous is counted in
 
 
 class _ChainRendezvous:
@@ -881,15 +894,14 @@ class _ChainRendezvous:
     exception of a call is raised in every fit whose request was part of that call.  ``group_sizes``: the units of
     every call issued, in order.
 
-    A wave's fits hand in two kinds of request -- the E-step chains and the M-step closures of their L-BFGS, whose line
-    searches differ from cell to cell -- so at any moment some fits wait with a closure and others with a chain.  The
-    rendezvous does not tell them apart: ``single``, ``group`` and ``key`` dispatch on the request's ``kind`` field, and
-    ``key`` carries the kind, so two kinds never share a call.  Only the bookkeeping looks at it: calls of requests whose
-    ``kind`` is ``"closure"`` are counted in ``closure_group_sizes`` / ``closure_call_seconds`` /
-    ``seconds_in_closure_call``, all others (a request without a kind included) in ``group_sizes`` / ``call_seconds`` /
-    ``seconds_in_call``.  The full-rank regime has two classes of its own: kind ``"chain_full"`` is counted in
-    ``full_group_sizes`` / ``full_call_seconds`` / ``seconds_in_full_call``, and a closure whose ``regime`` is ``"full"``
-    in ``full_closure_group_sizes`` / ``full_closure_call_seconds`` / ``seconds_in_full_closure_call``."""
+    A wave's fits hand in several kinds of request -- the E-step chains and the M-step closures of their L-BFGS, whose
+    line searches differ from cell to cell -- so at any moment some fits wait with a closure and others with a chain.
+    The rendezvous does not tell them apart: ``single``, ``group`` and ``key`` dispatch on the request's kind
+    (``_REQUEST_KINDS``), and ``key`` carries the kind, so two kinds never share a call.  Only the bookkeeping looks at
+    it: per book of ``_BOOKS`` there are three counters, ``<book>group_sizes`` / ``<book>call_seconds`` /
+    ``seconds_in_<book>call``, and a call is counted in the book of its kind -- the projected chains in ``""`` (a request
+    without a kind included), the sparse and truncated closures in ``"closure_"``, and the full-rank regime in two
+    books of its own, its chains in ``"full_"`` and its closures in ``"full_closure_"``."""
 
     def __init__(self, parties, single, group, key, max_units=MAX_CHAIN_UNITS):
         self.cond = threading.Condition()
@@ -901,20 +913,18 @@ class _ChainRendezvous:
         self.single, self.group, self.key, self.max_units = single, group, key, int(max_units)
         self.waiting = {}      # ticket -> request
         self.results = {}      # ticket -> result or exception
-        self.group_sizes = []
-        self.call_seconds = []     # host wall time of every call issued (enqueue to results), as group_sizes
-        self.seconds_in_call = 0.0  # summed over the fits: time between handing a request in and getting its result
-        self.closure_group_sizes, self.closure_call_seconds, self.seconds_in_closure_call = [], [], 0.0
-        self.full_group_sizes, self.full_call_seconds, self.seconds_in_full_call = [], [], 0.0
-        self.full_closure_group_sizes, self.full_closure_call_seconds, self.seconds_in_full_closure_call = [], [], 0.0
+        for book in _BOOKS:
+            setattr(self, book + "group_sizes", [])        # the units of every call issued, in order
+            setattr(self, book + "call_seconds", [])       # host wall time of each of them (enqueue to results)
+            # summed over the fits: time between handing a request in and getting its result
+            setattr(self, "seconds_in_" + book + "call", 0.0)
 
     @staticmethod
     def _book(request):
         """The prefix of the three counters a request is counted in."""
-        kind = request.get("kind") if isinstance(request, dict) else None
-        if kind == "closure":
-            return "full_closure_" if request.get("regime") == "full" else "closure_"
-        return "full_" if kind == "chain_full" else ""
+        if not isinstance(request, dict) or request.get("kind") is None:
+            return ""
+        return _request_kind(request).book
 
     def enter(self):
         """First statement of a fit's thread: wait for the turn."""
@@ -990,31 +1000,58 @@ def release_cell_workspaces():
         _IDLE_ENGINES.clear()
 
 
+_CELLS_COUNTERS = tuple(name for book in _BOOKS for name in (book + "group_sizes", book + "call_seconds",
+                                                              "seconds_in_" + book + "call"))
+
+
 def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     """Fit several cells recorded on the same stimuli ``x`` (or several restarts of one cell): returns the list of
     ``(fit_model, err_dict)`` that ``varGP(x, r_list[i], **kwargs_list[i])`` returns, fit by fit.
 
-    The fits run ``max_units`` (at most 16) at a time, one host thread each with its own workspace, all on the
-    caller's current stream.  ``varGP`` itself is unchanged; where a fit would issue the E-steps of an EM iteration as
-    one device call (``_estep_chain``: truncated and sparse regimes), it waits until every fit of its wave that is
-    still running has reached the same point, and the chains of all of them go out as ONE call per group of equal
-    ``(N, round_up(nb, 128), nEstep, nFparamstep, lambda0 mode)`` (``gpfit_estep_chain_batch``: the small kernels and
-    the bottom of the Cholesky recursions cost one launch for the group instead of one per cell).  Each cell's numbers
-    are those of ``varGP`` on its own, bit for bit.  Between two chains the fits of a wave take turns, one running at a
+    The wave.  The fits run ``max_units`` (at most 16) at a time, one host thread each with its own workspace, all on
+    the caller's current stream.  ``varGP`` itself is unchanged; where a fit would issue a device call of one of the
+    kinds below, it waits until every fit of its wave that is still running waits as well -- some with a closure of
+    their L-BFGS, some already with their next chain -- and the waiting requests go out as ONE call per kind and group
+    of equal key (``_REQUEST_KINDS``, ``_request_bucket_key``); two kinds never share a call.  Each cell's numbers are
+    those of ``varGP`` on its own, bit for bit.  Between two calls the fits of a wave take turns, one running at a
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
     Fits that never chain (f_params carrying ``loglambda0``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
-    being waited for.  A fit in the full-rank regime (inducing set = training set, every eigenvalue kept, identity
-    basis) hands in its chains (``_estep_chain_full``) in the same way: they go out as ONE ``gpfit_estep_chain_full_batch``
-    call per group of equal ``(N, nEstep, nFparamstep, lambda0 mode)`` and never share a call with the projected chains.
-    A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is
-    the error of every fit in that call.  The sparse M-step closures of the wave's fits (``_closure_sparse``) meet at the
-    same place: whenever every live fit waits -- some with a closure of their L-BFGS, some already with their next chain
-    -- the closures go out as ONE ``gpfit_fit_eval_sparse_batch`` call per group of equal ``_closure_bucket_key`` and the
-    chains as theirs.  A closure that returns the infinite loss on the host (theta outside the limits) asks nothing, and
-    the truncated-rank closures (``_closure_projected``: ``ntilde == ntrain`` with eigenvalues dropped) meet there in the same way, as ONE ``gpfit_fit_eval_projected_batch`` call per group of equal key (the regime is part of the key: the two never share a call; so is the capacity of the fit's workspace).  The full-rank closures meet there as well, as ONE ``gpfit_fit_eval_batch`` call on the fits' own workspaces per group of equal ``_closure_full_bucket_key`` -- the ``reuse_V`` flag is part of it, so the first closures of an M-step and later ones never share a call; a unit whose factorisation fails is that fit's error alone.  With ``FULL_RANK_GROUPS`` off (``GPFIT_FULL_RANK_GROUPS=0``) a full-rank fit issues its chains and closures directly on its own workspace and keeps its turn until it ends.  Out of the groups stay the basis rebuilds, the loss evaluation between chain and M-step and the fp32 instance.  ``varGP_cells.last_group_sizes``: the units of every chain call of the last
-    invocation, in order (1: the single call); ``last_closure_group_sizes``, ``last_closure_call_seconds`` and
-    ``last_seconds_in_closure_call``: the same for the closure calls; the calls of the full-rank regime are counted apart, in ``last_full_group_sizes`` / ``last_full_call_seconds`` / ``last_seconds_in_full_call`` (chains) and ``last_full_closure_group_sizes`` / ``last_full_closure_call_seconds`` / ``last_seconds_in_full_closure_call`` (closures).  The workspaces of the fits (one per concurrent fit, each of the size of
-    a ``varGP`` workspace) are kept for the next call; ``release_cell_workspaces()`` frees them."""
+    being waited for.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is the
+    error of every fit in that call.  Out of the groups stay the basis rebuilds, the loss evaluation between chain and
+    M-step and the fp32 instance.
+
+    Projected chains (``_estep_chain``: the E-steps of an EM iteration as one device call, truncated and sparse
+    regimes): ONE ``gpfit_estep_chain_batch`` call per group of equal ``(N, round_up(nb, 128), nEstep, nFparamstep,
+    lambda0 mode)`` -- the small kernels and the bottom of the Cholesky recursions cost one launch for the group
+    instead of one per cell.
+
+    Full-rank chains (``_estep_chain_full``: inducing set = training set, every eigenvalue kept, identity basis): ONE
+    ``gpfit_estep_chain_full_batch`` call per group of equal ``(N, nEstep, nFparamstep, lambda0 mode)``; they never
+    share a call with the projected chains.
+
+    Sparse closures (``_closure_sparse``, the M-step closures of a fit with ``ntilde < ntrain``): ONE
+    ``gpfit_fit_eval_sparse_batch`` call per group of equal ``_closure_bucket_key``.  A closure that returns the
+    infinite loss on the host (theta outside the limits) asks nothing.
+
+    Truncated-rank closures (``_closure_projected``: ``ntilde == ntrain`` with eigenvalues dropped): ONE
+    ``gpfit_fit_eval_projected_batch`` call per group of equal key.  The regime is part of the key, so the two never
+    share a call; so is the capacity of the fit's workspace.
+
+    Full-rank closures (``_closure_full``): ONE ``gpfit_fit_eval_batch`` call on the fits' own workspaces per group of
+    equal ``_closure_full_bucket_key`` -- the ``reuse_V`` flag is part of it, so the first closures of an M-step and
+    later ones never share a call; a unit whose factorisation fails is that fit's error alone.  With
+    ``FULL_RANK_GROUPS`` off (``GPFIT_FULL_RANK_GROUPS=0``) a full-rank fit issues its chains and closures directly on
+    its own workspace and keeps its turn until it ends.
+
+    The counters.  ``varGP_cells.last_group_sizes``: the units of every projected chain call of the last invocation, in
+    order (1: the single call); ``last_call_seconds``: the host wall time of each of those calls;
+    ``last_seconds_in_call``: summed over the fits, the time between handing a request in and getting its result
+    (waiting for the wave plus the call).  ``last_closure_group_sizes``, ``last_closure_call_seconds`` and ``last_seconds_in_closure_call``: the same
+    for the sparse and truncated closure calls.  The calls of the full-rank regime are counted apart, in
+    ``last_full_group_sizes`` / ``last_full_call_seconds`` / ``last_seconds_in_full_call`` (chains) and
+    ``last_full_closure_group_sizes`` / ``last_full_closure_call_seconds`` / ``last_seconds_in_full_closure_call``
+    (closures).  The workspaces of the fits (one per concurrent fit, each of the size of a ``varGP`` workspace) are
+    kept for the next call; ``release_cell_workspaces()`` frees them."""
     n_fits = len(r_list)
     if len(kwargs_list) != n_fits:
         raise ValueError("varGP_cells: one kwargs dict per response vector")
@@ -1024,10 +1061,8 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     dev = _device()
     stream = torch.cuda.current_stream(dev)
     grad = torch.is_grad_enabled()
-    results, errors, sizes, call_seconds, in_call = [None] * n_fits, [None] * n_fits, [], [], 0.0
-    closure_sizes, closure_seconds, in_closure = [], [], 0.0
-    full = {"full_group_sizes": [], "full_call_seconds": [], "seconds_in_full_call": 0.0, "full_closure_group_sizes": [],
-            "full_closure_call_seconds": [], "seconds_in_full_closure_call": 0.0}
+    results, errors = [None] * n_fits, [None] * n_fits
+    counters = {name: 0.0 if name.startswith("seconds_in_") else [] for name in _CELLS_COUNTERS}
 
     def fit(i, rendezvous):
         key = (dev.index, threading.get_ident())
@@ -1060,21 +1095,9 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
             t.start()
         for t in threads:
             t.join()
-        sizes += rendezvous.group_sizes
-        call_seconds += rendezvous.call_seconds
-        in_call += rendezvous.seconds_in_call
-        closure_sizes += rendezvous.closure_group_sizes
-        closure_seconds += rendezvous.closure_call_seconds
-        in_closure += rendezvous.seconds_in_closure_call
-        for name in full:
-            full[name] += getattr(rendezvous, name)
-    varGP_cells.last_group_sizes = sizes
-    varGP_cells.last_call_seconds = call_seconds      # host wall time of each of those calls
-    varGP_cells.last_seconds_in_call = in_call        # summed over the fits: waiting for the wave plus the call
-    varGP_cells.last_closure_group_sizes = closure_sizes      # the same three for the M-step closure calls
-    varGP_cells.last_closure_call_seconds = closure_seconds
-    varGP_cells.last_seconds_in_closure_call = in_closure
-    for name, value in full.items():          # the same six for the chains and the closures of the full-rank regime
+        for name in counters:
+            counters[name] += getattr(rendezvous, name)
+    for name, value in counters.items():
         setattr(varGP_cells, "last_" + name, value)
     for err in errors:
         if err is not None:
@@ -1082,18 +1105,9 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     return results
 
 
-varGP_cells.last_group_sizes = []
-varGP_cells.last_call_seconds = []
-varGP_cells.last_seconds_in_call = 0.0
-varGP_cells.last_closure_group_sizes = []
-varGP_cells.last_closure_call_seconds = []
-varGP_cells.last_seconds_in_closure_call = 0.0
-varGP_cells.last_full_group_sizes = []
-varGP_cells.last_full_call_seconds = []
-varGP_cells.last_seconds_in_full_call = 0.0
-varGP_cells.last_full_closure_group_sizes = []
-varGP_cells.last_full_closure_call_seconds = []
-varGP_cells.last_seconds_in_full_closure_call = 0.0
+for _name in _CELLS_COUNTERS:
+    setattr(varGP_cells, "last_" + _name, 0.0 if _name.startswith("seconds_in_") else [])
+del _name
 
 
 def _estep_chain_commit(records, f_params):
@@ -1518,98 +1532,122 @@ def _closure_projected(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params):
     reproduces that and is used instead.  In a fit of ``varGP_cells`` the device call is the wave's: the request goes
     to the rendezvous and comes back as one unit of a ``gpfit_fit_eval_projected_batch`` call, with the same bits."""
     q = _closure_projected_prepare(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params)
-    rendezvous = getattr(_CELLS, "rendezvous", None)
-    rc_, out = rendezvous.call(q) if rendezvous is not None else _closure_run_single(q)
-    return _closure_projected_finish(q, rc_, out)
+    return _closure_finish(q, *_submit(q), _closure_projected_steps)
 
 
-def _closure_projected_prepare(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params, engine=None):
-    """The arguments of ``_closure_projected`` as one request (``regime``: truncated -- a closure request without that field
-    is a sparse one): the operands on the device, the scalars as floats, and the workspace and stream the call runs on
-    -- this thread's unless an engine is given.  ``cap``: the padded number of stimuli the workspace was created for, on
-    which the k slabs of the projections and the route of the lift depend."""
+def _closure_prepare(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params, xtilde=None, engine=None):
+    """The arguments of ``_closure_sparse`` (``xtilde`` given) or ``_closure_projected`` (no ``xtilde``) as one request: the
+    operands on the device, the scalars as floats, and the workspace and stream the call runs on -- this thread's
+    unless an engine is given.  A sparse request has ``xt`` / ``Nt`` and no ``regime`` field; a truncated one has ``regime``
+    and ``cap``, the padded number of stimuli the workspace was created for, on which the k slabs of the projections and
+    the route of the lift depend.  ``args``: what the kind's step-by-step function takes."""
     lower, upper = lims
-    xc, rc, Bc, mc, Vc = _cu(x), _cu(r), _cu(B), _cu(m_b), _cu(V_b)
+    sparse = xtilde is not None
+    xc, xtc, rc, Bc, mc, Vc = _cu(x), _cu(xtilde) if sparse else None, _cu(r), _cu(B), _cu(m_b), _cu(V_b)
     rows, cols = _grid(n_px_side)
-    q = {"kind": "closure", "regime": "truncated", "theta": [float(v) for v in theta_vec(theta)],
+    q = {"kind": "closure", "theta": [float(v) for v in theta_vec(theta)],
          "lower": [_scalar(lower[k]) for k in THETA_KEYS], "upper": [_scalar(upper[k]) for k in THETA_KEYS],
-         "rows": rows, "cols": cols, "x": xc, "r": rc, "B": Bc, "m_b": mc, "V_b": Vc,
-         "N": int(Bc.shape[0]), "n_kept": int(Bc.shape[1]),
-         "logA": _scalar(f_params['logA']), "lambda0": _scalar(_lambda0_of(f_params)),
-         "args": (theta, lims, n_px_side, x, r, B, m_b, V_b, f_params)}
-    q["engine"] = engine if engine is not None else get_engine(q["N"], xc.shape[1], rows * cols)
-    q["cap"] = -(-q["engine"].n_max // 128) * 128
+         "rows": rows, "cols": cols, "x": xc, "r": rc, "B": Bc, "m_b": mc, "V_b": Vc, "n_kept": int(Bc.shape[1]),
+         "logA": _scalar(f_params['logA']), "lambda0": _scalar(_lambda0_of(f_params))}
+    if sparse:
+        q.update(xt=xtc, N=int(xc.shape[0]), Nt=int(xtc.shape[0]),
+                 args=(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params))
+        n_max = max(q["N"], q["Nt"])
+    else:
+        q.update(regime="truncated", N=int(Bc.shape[0]), args=(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params))
+        n_max = q["N"]
+    q["engine"] = engine if engine is not None else get_engine(n_max, xc.shape[1], rows * cols)
+    if not sparse:
+        q["cap"] = -(-q["engine"].n_max // 128) * 128
     q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
     return q
 
 
-def _closure_projected_run_single(q):
-    """``gpfit_fit_eval_projected`` on one truncated request: ``(rc, out[16])``."""
+def _closure_run_single(q):
+    """``gpfit_fit_eval_sparse`` on one sparse request, ``gpfit_fit_eval_projected`` (the same argument list without
+    xtilde) on one truncated request: ``(rc, out[16])``."""
     out = (ctypes.c_double * 16)()
     x, B, V = q["x"], q["B"], q["V_b"]
-    rc_ = _lib.load().gpfit_fit_eval_projected(q["engine"]._ctx, q["stream"], _lib.darr(q["theta"]), _lib.darr(q["lower"]),
-                                               _lib.darr(q["upper"]), q["rows"], q["cols"], x.data_ptr(), x.stride(0), q["N"],
-                                               q["r"].data_ptr(), B.data_ptr(), B.stride(0), q["n_kept"], q["m_b"].data_ptr(),
-                                               V.data_ptr(), V.stride(0), q["logA"], q["lambda0"], out)
+    name = "gpfit_fit_eval_sparse" if "xt" in q else "gpfit_fit_eval_projected"
+    xt = (q["xt"].data_ptr(), q["xt"].stride(0), q["Nt"]) if "xt" in q else ()
+    rc_ = getattr(_lib.load(), name)(q["engine"]._ctx, q["stream"], _lib.darr(q["theta"]), _lib.darr(q["lower"]),
+                                     _lib.darr(q["upper"]), q["rows"], q["cols"], x.data_ptr(), x.stride(0), q["N"], *xt,
+                                     q["r"].data_ptr(), B.data_ptr(), B.stride(0), q["n_kept"], q["m_b"].data_ptr(),
+                                     V.data_ptr(), V.stride(0), q["logA"], q["lambda0"], out)
     if rc_ < 0 and rc_ != -2:
-        _lib.check(rc_, "gpfit_fit_eval_projected")
+        _lib.check(rc_, name)
     return rc_, list(out)
 
 
+def _closure_sparse_bucket_key(q):
+    """Sparse requests with equal keys may share one ``gpfit_fit_eval_sparse_batch`` call: what that call shares between
+    its units, and the padded basis size (the recursion's split, hence the bits, depend on it)."""
+    return (q["x"].device.index, q["stream"].value, q["N"], q["Nt"], q["x"].stride(0), q["xt"].stride(0), q["rows"], q["cols"],
+            -(-q["n_kept"] // 128) * 128)
+
+
 def _closure_projected_bucket_key(q):
-    """Truncated requests with equal keys may share one ``gpfit_fit_eval_projected_batch`` call: the regime (the two
+    """Truncated requests with equal keys may share one ``gpfit_fit_eval_projected_batch`` call: the regime (the
     regimes never share a call), what that call shares between its units, the padded basis size (the recursion's split,
     hence the bits, depend on it) and the capacity of the workspace (the slab counts and the lift's route depend on it)."""
     return ("truncated", q["x"].device.index, q["stream"].value, q["N"], q["x"].stride(0), q["rows"], q["cols"],
             -(-q["n_kept"] // 128) * 128, q["cap"])
 
 
-def _closure_projected_batch_raw(ctxs, qs, out=None, rcs=None):
-    """``gpfit_fit_eval_projected_batch`` on the truncated requests ``qs`` with the contexts ``ctxs`` (one per request): the
-    return code, the 16 outputs per unit and the per-unit codes, nothing checked here -- the shared arguments are those
-    of ``qs[0]``.  A tensor given as None goes in as a null pointer; ``out`` / ``rcs``: the caller's arrays instead of new
-    ones."""
-    nu = len(qs)
+def _closure_bucket_key(q):
+    """The bucket key of a closure request of any regime: ``_request_bucket_key`` without its leading kind."""
+    return _request_kind(q).key(q)
 
-    def ptrs(key):
-        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
 
-    def flat(key):
-        return _lib.darr([v for q in qs for v in q[key]])
-
-    q0 = qs[0]
+def _closure_batch_raw(ctxs, qs, out=None, rcs=None):
+    """``gpfit_fit_eval_sparse_batch`` on sparse requests ``qs``, ``gpfit_fit_eval_projected_batch`` (the same argument list
+    without xtilde) on truncated ones, with the contexts ``ctxs`` (one per request): the return code, the 16 outputs per
+    unit and the per-unit codes, nothing checked here -- the shared arguments, and the choice of the entry point, are
+    those of ``qs[0]``.  A tensor given as None goes in as a null pointer; ``out`` / ``rcs``: the caller's arrays instead of
+    new ones."""
+    nu, q0 = len(qs), qs[0]
     out = (ctypes.c_double * (16 * nu))() if out is None else out
     rcs = (ctypes.c_int * nu)() if rcs is None else rcs
-    rc = _lib.load().gpfit_fit_eval_projected_batch(
-        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
-        flat("theta"), flat("lower"), flat("upper"), q0["rows"], q0["cols"], ptrs("x"), q0["x"].stride(0), q0["N"], ptrs("r"),
-        ptrs("B"), (ctypes.c_int64 * nu)(*[q["n_kept"] if q["B"] is None else q["B"].stride(0) for q in qs]),
-        (ctypes.c_int64 * nu)(*[q["n_kept"] for q in qs]), ptrs("m_b"), ptrs("V_b"),
-        (ctypes.c_int64 * nu)(*[q["n_kept"] if q["V_b"] is None else q["V_b"].stride(0) for q in qs]),
-        _lib.darr([q["logA"] for q in qs]), _lib.darr([q["lambda0"] for q in qs]), out, rcs)
+    name = "gpfit_fit_eval_sparse_batch" if "xt" in q0 else "gpfit_fit_eval_projected_batch"
+    xt = (_ptr_table(qs, "xt"), q0["xt"].stride(0), q0["Nt"]) if "xt" in q0 else ()
+    rc = getattr(_lib.load(), name)(
+        _ctx_table(ctxs), nu, q0["stream"], _flat(qs, "theta"), _flat(qs, "lower"), _flat(qs, "upper"), q0["rows"], q0["cols"],
+        _ptr_table(qs, "x"), q0["x"].stride(0), q0["N"], *xt, _ptr_table(qs, "r"), _ptr_table(qs, "B"),
+        _ld_table(qs, "B", "n_kept"), (ctypes.c_int64 * nu)(*[q["n_kept"] for q in qs]), _ptr_table(qs, "m_b"),
+        _ptr_table(qs, "V_b"), _ld_table(qs, "V_b", "n_kept"), _lib.darr([q["logA"] for q in qs]),
+        _lib.darr([q["lambda0"] for q in qs]), out, rcs)
     return rc, out, rcs
 
 
-def _closure_projected_run_group(qs):
-    """One ``gpfit_fit_eval_projected_batch`` call on truncated requests of one bucket (``_closure_projected_bucket_key``),
-    each on its own workspace; per request what ``_closure_projected_run_single`` returns, with the same bits."""
-    if len({_closure_bucket_key(q) for q in qs}) != 1:
-        raise ValueError("_closure_run_group: the truncated requests of one call share the stimuli's size and leading "
-                         "dimension, the pixel grid, the padded basis size and the capacity of their workspaces")
-    rc, out, rcs = _closure_projected_batch_raw([q["engine"]._ctx for q in qs], qs)
-    _lib.check(rc, "gpfit_fit_eval_projected_batch")
-    return [(int(rcs[u]), list(out[16 * u:16 * u + 16])) for u in range(len(qs))]
+def _closure_unit(q, u, out, rcs):
+    """What ``_closure_run_single`` returns, for unit ``u`` of a batch call: ``(rc, out[16])``."""
+    return int(rcs[u]), list(out[16 * u:16 * u + 16])
 
 
-def _closure_projected_finish(q, rc_, out):
-    """What ``_closure_projected`` returns or raises for the code and the outputs the device call gave its request; a
-    non-positive pivot (``rc_ > 0``) takes the step-by-step formulation, in the caller's own thread."""
+def _closure_finish(q, rc_, out, steps):
+    """What ``_closure_sparse`` / ``_closure_projected`` returns or raises for the code and the outputs the device call gave
+    its request; a non-positive pivot (``rc_ > 0``) takes the kind's step-by-step formulation ``steps``, in the caller's
+    own thread."""
     if rc_ == -2:
         _lib.load().gpfit_check_limits(_lib.darr(q["theta"]), _lib.darr(q["lower"]), _lib.darr(q["upper"]))   # its message
         raise ValueError(_lib.last_error())
     if rc_ == 0:
         return out[0], {k: out[3 + i] for i, k in enumerate(THETA_KEYS)}
-    return _closure_projected_steps(*q["args"])
+    return steps(*q["args"])
+
+
+# The names under which each regime's entry function reaches the code the two regimes share: the tests call them, and
+# count a regime's device calls by wrapping its prepare.
+_closure_sparse_prepare = _closure_projected_prepare = _closure_prepare
+_closure_projected_run_single = _closure_run_single
+_closure_projected_batch_raw = _closure_batch_raw
+
+
+def _closure_size(units):
+    """``n, d, d_full`` of the workspaces a group of closure units needs (``_group_engines``)."""
+    rows, cols = _grid(units[0]["n_px_side"])
+    n = max(max(u["x"].shape[0], u["xtilde"].shape[0] if "xtilde" in u else 0) for u in units)
+    return n, units[0]["x"].shape[1], rows * cols
 
 
 def _closure_projected_group(units):
@@ -1620,28 +1658,8 @@ def _closure_projected_group(units):
     lift, hence its last bits, depend on the capacity of the workspace: the units here run on workspaces of that one
     capacity, whatever the size of the thread's own); a unit whose call would raise has the exception in its place, and
     a unit whose factorisation fails takes the step-by-step formulation alone."""
-    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
-        raise ValueError(f"_closure_projected_group: 1 .. {MAX_CHAIN_UNITS} units per call")
-    rows, cols = _grid(units[0]["n_px_side"])
-    n, d, d_full = max(u["x"].shape[0] for u in units), units[0]["x"].shape[1], rows * cols
-    # one capacity per call (the slab counts and the lift's route depend on it), that of a workspace created for these n
-    # stimuli: this thread's own if it has that capacity, kept ones that have it, and new ones kept for later group calls
-    kept = getattr(_CELLS, "engines", [])
-    engines = [e for e in [get_engine(n, d, d_full)] + kept
-               if -(-e.n_max // 128) == -(-n // 128) and e.d_max >= d and e.d_full_max >= d_full
-               and e.device == _device().index][:len(units)]
-    while len(engines) < len(units):
-        engines.append(GPFitEngine(n, d, d_full, device=_device().index))
-        kept = kept + [engines[-1]]
-    _CELLS.engines = kept
-    qs = [_closure_projected_prepare(engine=e, **u) for u, e in zip(units, engines)]
-    res = []
-    for q, (rc_, out) in zip(qs, _closure_run_group(qs) if len(qs) > 1 else [_closure_run_single(qs[0])]):
-        try:
-            res.append(_closure_projected_finish(q, rc_, out))
-        except Exception as err:      # what _closure_projected raises for this unit alone
-            res.append(err)
-    return res
+    return _units_group("_closure_projected_group", units, _closure_size, _closure_prepare, _closure_projected_steps,
+                        exact=True)
 
 
 def _closure_adjoints(K_b, K_tilde_b, Kvec, a, m_b, V_b, r, f_params):
@@ -1720,110 +1738,8 @@ def _closure_sparse(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params)
     the path taken when a factorisation meets a non-positive pivot (reference's eigen-fallback of
     ``log_det``, utils.py:1279-1304).  In a fit of ``varGP_cells`` the device call is the wave's: the request goes
     to the rendezvous and comes back as one unit of a ``gpfit_fit_eval_sparse_batch`` call, with the same bits."""
-    q = _closure_sparse_prepare(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params)
-    rendezvous = getattr(_CELLS, "rendezvous", None)
-    rc_, out = rendezvous.call(q) if rendezvous is not None else _closure_run_single(q)
-    return _closure_sparse_finish(q, rc_, out)
-
-
-def _closure_sparse_prepare(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params, engine=None):
-    """The arguments of ``_closure_sparse`` as one request: the operands on the device, the scalars as floats, and the
-    workspace and stream the call runs on -- this thread's unless an engine is given."""
-    lower, upper = lims
-    xc, xtc, rc, Bc, mc, Vc = _cu(x), _cu(xtilde), _cu(r), _cu(B), _cu(m_b), _cu(V_b)
-    rows, cols = _grid(n_px_side)
-    q = {"kind": "closure", "theta": [float(v) for v in theta_vec(theta)],
-         "lower": [_scalar(lower[k]) for k in THETA_KEYS], "upper": [_scalar(upper[k]) for k in THETA_KEYS],
-         "rows": rows, "cols": cols, "x": xc, "xt": xtc, "r": rc, "B": Bc, "m_b": mc, "V_b": Vc,
-         "N": int(xc.shape[0]), "Nt": int(xtc.shape[0]), "n_kept": int(Bc.shape[1]),
-         "logA": _scalar(f_params['logA']), "lambda0": _scalar(_lambda0_of(f_params)),
-         "args": (theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params)}
-    q["engine"] = engine if engine is not None else get_engine(max(q["N"], q["Nt"]), xc.shape[1], rows * cols)
-    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
-    return q
-
-
-def _closure_run_single(q):
-    """``gpfit_fit_eval_sparse`` on one request: ``(rc, out[16])`` (a truncated request: ``gpfit_fit_eval_projected``)."""
-    if q.get("regime") == "truncated":
-        return _closure_projected_run_single(q)
-    if q.get("regime") == "full":
-        return _closure_full_run_single(q)
-    out = (ctypes.c_double * 16)()
-    x, xt, B, V = q["x"], q["xt"], q["B"], q["V_b"]
-    rc_ = _lib.load().gpfit_fit_eval_sparse(q["engine"]._ctx, q["stream"], _lib.darr(q["theta"]), _lib.darr(q["lower"]),
-                                            _lib.darr(q["upper"]), q["rows"], q["cols"], x.data_ptr(), x.stride(0), q["N"],
-                                            xt.data_ptr(), xt.stride(0), q["Nt"], q["r"].data_ptr(), B.data_ptr(),
-                                            B.stride(0), q["n_kept"], q["m_b"].data_ptr(), V.data_ptr(), V.stride(0),
-                                            q["logA"], q["lambda0"], out)
-    if rc_ < 0 and rc_ != -2:
-        _lib.check(rc_, "gpfit_fit_eval_sparse")
-    return rc_, list(out)
-
-
-def _closure_bucket_key(q):
-    """Requests with equal keys may share one ``gpfit_fit_eval_sparse_batch`` call: what that call shares between its
-    units, and the padded basis size (the recursion's split, hence the bits, depend on it).  A truncated request
-    (``regime``) has the key of its own call, ``_closure_projected_bucket_key``, which begins with the regime."""
-    if q.get("regime") == "truncated":
-        return _closure_projected_bucket_key(q)
-    if q.get("regime") == "full":
-        return _closure_full_bucket_key(q)
-    return (q["x"].device.index, q["stream"].value, q["N"], q["Nt"], q["x"].stride(0), q["xt"].stride(0), q["rows"], q["cols"],
-            -(-q["n_kept"] // 128) * 128)
-
-
-def _closure_batch_raw(ctxs, qs, out=None, rcs=None):
-    """``gpfit_fit_eval_sparse_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return
-    code, the 16 outputs per unit and the per-unit codes, nothing checked here -- the shared arguments are those of
-    ``qs[0]``.  A tensor given as None goes in as a null pointer; ``out`` / ``rcs``: the caller's arrays instead of new ones."""
-    nu = len(qs)
-
-    def ptrs(key):
-        return (ctypes.c_void_p * nu)(*[None if q[key] is None else q[key].data_ptr() for q in qs])
-
-    def flat(key):
-        return _lib.darr([v for q in qs for v in q[key]])
-
-    q0 = qs[0]
-    out = (ctypes.c_double * (16 * nu))() if out is None else out
-    rcs = (ctypes.c_int * nu)() if rcs is None else rcs
-    rc = _lib.load().gpfit_fit_eval_sparse_batch(
-        (ctypes.c_void_p * nu)(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs]), nu, q0["stream"],
-        flat("theta"), flat("lower"), flat("upper"), q0["rows"], q0["cols"], ptrs("x"), q0["x"].stride(0), q0["N"], ptrs("xt"),
-        q0["xt"].stride(0), q0["Nt"], ptrs("r"), ptrs("B"),
-        (ctypes.c_int64 * nu)(*[q["n_kept"] if q["B"] is None else q["B"].stride(0) for q in qs]),
-        (ctypes.c_int64 * nu)(*[q["n_kept"] for q in qs]), ptrs("m_b"), ptrs("V_b"),
-        (ctypes.c_int64 * nu)(*[q["n_kept"] if q["V_b"] is None else q["V_b"].stride(0) for q in qs]),
-        _lib.darr([q["logA"] for q in qs]), _lib.darr([q["lambda0"] for q in qs]), out, rcs)
-    return rc, out, rcs
-
-
-def _closure_run_group(qs):
-    """One ``gpfit_fit_eval_sparse_batch`` call on requests of one bucket (``_closure_bucket_key``), each on its own
-    workspace; per request what ``_closure_run_single`` returns, with the same bits.  (Truncated requests: their own call,
-    ``_closure_projected_run_group``.)"""
-    if all(q.get("regime") == "truncated" for q in qs):
-        return _closure_projected_run_group(qs)
-    if all(q.get("regime") == "full" for q in qs):
-        return _closure_full_run_group(qs)
-    if len({_closure_bucket_key(q) for q in qs}) != 1:
-        raise ValueError("_closure_run_group: the requests of one call share the stimuli's sizes and leading dimensions, "
-                         "the pixel grid and the padded basis size")
-    rc, out, rcs = _closure_batch_raw([q["engine"]._ctx for q in qs], qs)
-    _lib.check(rc, "gpfit_fit_eval_sparse_batch")
-    return [(int(rcs[u]), list(out[16 * u:16 * u + 16])) for u in range(len(qs))]
-
-
-def _closure_sparse_finish(q, rc_, out):
-    """What ``_closure_sparse`` returns or raises for the code and the outputs the device call gave its request; a
-    non-positive pivot (``rc_ > 0``) takes the step-by-step formulation, in the caller's own thread."""
-    if rc_ == -2:
-        _lib.load().gpfit_check_limits(_lib.darr(q["theta"]), _lib.darr(q["lower"]), _lib.darr(q["upper"]))   # its message
-        raise ValueError(_lib.last_error())
-    if rc_ == 0:
-        return out[0], {k: out[3 + i] for i, k in enumerate(THETA_KEYS)}
-    return _closure_sparse_steps(*q["args"])
+    q = _closure_sparse_prepare(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params, xtilde=xtilde)
+    return _closure_finish(q, *_submit(q), _closure_sparse_steps)
 
 
 def _closure_sparse_group(units):
@@ -1832,19 +1748,7 @@ def _closure_sparse_group(units):
     1 .. 16 units of one ``_closure_bucket_key``.  Returns, per unit, what ``_closure_sparse`` returns for it, bit for
     bit; a unit whose call would raise has the exception in its place, and a unit whose factorisation fails takes the
     step-by-step formulation alone."""
-    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
-        raise ValueError(f"_closure_sparse_group: 1 .. {MAX_CHAIN_UNITS} units per call")
-    rows, cols = _grid(units[0]["n_px_side"])
-    cap = max(max(u["x"].shape[0], u["xtilde"].shape[0]) for u in units)
-    engines = _group_engines(len(units), cap, units[0]["x"].shape[1], rows * cols)
-    qs = [_closure_sparse_prepare(engine=e, **u) for u, e in zip(units, engines)]
-    res = []
-    for q, (rc_, out) in zip(qs, _closure_run_group(qs) if len(qs) > 1 else [_closure_run_single(qs[0])]):
-        try:
-            res.append(_closure_sparse_finish(q, rc_, out))
-        except Exception as err:      # what _closure_sparse raises for this unit alone
-            res.append(err)
-    return res
+    return _units_group("_closure_sparse_group", units, _closure_size, _closure_prepare, _closure_sparse_steps)
 
 
 def _closure_full(theta, lims, n_px_side, x, r, m, V, f_params, reuse_V):
@@ -1864,10 +1768,7 @@ def _closure_full(theta, lims, n_px_side, x, r, m, V, f_params, reuse_V):
     q["engine"] = get_engine(q["N"], xc.shape[1], rows * cols)
     q["cap"] = -(-q["engine"].n_max // 128) * 128
     q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
-    rendezvous = getattr(_CELLS, "rendezvous", None)
-    if rendezvous is not None and FULL_RANK_GROUPS:
-        return rendezvous.call(q)
-    return _closure_full_run_single(q)
+    return _submit(q)
 
 
 def _closure_full_run_single(q):
@@ -1884,57 +1785,96 @@ def _closure_full_bucket_key(q):
             q["cap"], q["reuse_V"])
 
 
-def _closure_full_run_group(qs):
-    """One ``gpfit_fit_eval_batch`` call on full-rank requests of one bucket (``_closure_full_bucket_key``), each on its
-    own workspace (the one that holds its V factor); per request what ``_closure_full_run_single`` returns, with the same
-    bits -- or, in its place, the exception ``fit_eval`` raises for that unit alone (a failed factorisation).  No limits
-    go in: every request's theta has been checked on the host."""
-    if len({_closure_full_bucket_key(q) for q in qs}) != 1:
-        raise ValueError("_closure_run_group: the full-rank requests of one call share the stimuli's size and leading "
-                         "dimension, the pixel grid, the capacity of their workspaces and the reuse_V flag")
+def _closure_full_batch_raw(ctxs, qs, out=None, rcs=None):
+    """``gpfit_fit_eval_batch`` on the full-rank requests ``qs`` with the contexts ``ctxs`` (their own workspaces', which
+    hold their V factors): the return code, the 16 outputs per unit and the per-unit codes, nothing checked here -- the
+    shared arguments are those of ``qs[0]``.  No limits go in: every request's theta has been checked on the host."""
     nu, q0 = len(qs), qs[0]
-
-    def ptrs(key):
-        return (ctypes.c_void_p * nu)(*[q[key].data_ptr() for q in qs])
-
-    out = (ctypes.c_double * (16 * nu))()
-    rcs = (ctypes.c_int * nu)()
+    out = (ctypes.c_double * (16 * nu))() if out is None else out
+    rcs = (ctypes.c_int * nu)() if rcs is None else rcs
     rc = _lib.load().gpfit_fit_eval_batch(
-        (ctypes.c_void_p * nu)(*[q["engine"]._ctx.value for q in qs]), nu, q0["stream"],
-        _lib.darr([v for q in qs for v in q["theta"]]), None, None, q0["rows"], q0["cols"], ptrs("x"), q0["x"].stride(0),
-        q0["N"], ptrs("r"), ptrs("m"), ptrs("V"), q0["V"].stride(0), _lib.darr([q["logA"] for q in qs]),
-        _lib.darr([q["lambda0"] for q in qs]), 1 | (2 if q0["reuse_V"] else 0), out, rcs)
-    _lib.check(rc, "gpfit_fit_eval_batch")
-    res = []
-    for u, q in enumerate(qs):      # every pending unit is collected, also behind a failed one
-        ticket = {"rc": int(rcs[u]), "out": (ctypes.c_double * 16)(*out[16 * u:16 * u + 16]), "pending": rcs[u] == 0,
-                  "lam_m": None, "lam_var": None, "f": None}
-        try:
-            res.append(q["engine"].fit_eval_finish(ticket))
-        except Exception as err:    # this unit's alone
-            res.append(err)
-    return res
+        _ctx_table(ctxs), nu, q0["stream"], _flat(qs, "theta"), None, None, q0["rows"], q0["cols"], _ptr_table(qs, "x"),
+        q0["x"].stride(0), q0["N"], _ptr_table(qs, "r"), _ptr_table(qs, "m"), _ptr_table(qs, "V"), q0["V"].stride(0),
+        _lib.darr([q["logA"] for q in qs]), _lib.darr([q["lambda0"] for q in qs]), 1 | (2 if q0["reuse_V"] else 0), out, rcs)
+    return rc, out, rcs
 
 
-# what the rendezvous of varGP_cells is given: three kinds of request, each with its own calls and bucket key
-_REQUEST_KINDS = {
-    "chain": (lambda q: _chain_run_single(q), lambda qs: _chain_run_group(qs), lambda q: _chain_bucket_key(q)),
-    "chain_full": (lambda q: _chain_full_run_single(q), lambda qs: _chain_full_run_group(qs),
-                   lambda q: _chain_full_bucket_key(q)),
-    "closure": (lambda q: _closure_run_single(q), lambda qs: _closure_run_group(qs), lambda q: _closure_bucket_key(q)),
-}
+def _closure_full_unit(q, u, out, rcs):
+    """What ``_closure_full_run_single`` returns, for unit ``u`` of a batch call, with the same bits -- or, in its place,
+    the exception ``fit_eval`` raises for that unit alone (a failed factorisation).  Every pending unit of the call is
+    collected (``fit_eval_finish``), also behind a failed one."""
+    ticket = {"rc": int(rcs[u]), "out": (ctypes.c_double * 16)(*out[16 * u:16 * u + 16]), "pending": rcs[u] == 0,
+              "lam_m": None, "lam_var": None, "f": None}
+    try:
+        return q["engine"].fit_eval_finish(ticket)
+    except Exception as err:    # this unit's alone
+        return err
+
+
+# What the rendezvous of varGP_cells is given: five kinds of request, one record each.  ``book``: the counters its calls
+# are counted in (_BOOKS); ``gated``: FULL_RANK_GROUPS off keeps it out of the rendezvous; ``run_single(q)``: the single
+# entry point; ``batch(ctxs, qs)``: the batch entry point ``entry``, unchecked -- its return code, then its output
+# arrays; ``unit(q, u, *arrays)``: the result of unit u cut out of them, what run_single returns for q alone;
+# ``key(q)``: requests of one kind with equal keys may share a call; ``share``: what that means, for the error.
+_RequestKind = collections.namedtuple("_RequestKind", "kind regime book gated run_single entry batch unit key share")
+_REQUEST_KINDS = {(k.kind, k.regime): k for k in (
+    _RequestKind(kind="chain", regime=None, book="", gated=False, run_single=_chain_run_single,
+                 entry="gpfit_estep_chain_batch", batch=_chain_batch_raw, unit=_chain_result, key=_chain_bucket_key,
+                 share="the requests of one call share N, the padded basis size, the number of steps and the optimiser's "
+                 "settings"),
+    _RequestKind(kind="chain_full", regime=None, book="full_", gated=True, run_single=_chain_full_run_single,
+                 entry="gpfit_estep_chain_full_batch", batch=_chain_full_batch_raw, unit=_chain_result,
+                 key=_chain_full_bucket_key,
+                 share="the requests of one call share N, the number of steps and the optimiser's settings"),
+    _RequestKind(kind="closure", regime=None, book="closure_", gated=False, run_single=_closure_run_single,
+                 entry="gpfit_fit_eval_sparse_batch", batch=_closure_batch_raw, unit=_closure_unit,
+                 key=_closure_sparse_bucket_key,
+                 share="the requests of one call share the stimuli's sizes and leading dimensions, the pixel grid and the "
+                 "padded basis size"),
+    _RequestKind(kind="closure", regime="truncated", book="closure_", gated=False, run_single=_closure_run_single,
+                 entry="gpfit_fit_eval_projected_batch", batch=_closure_batch_raw, unit=_closure_unit,
+                 key=_closure_projected_bucket_key,
+                 share="the truncated requests of one call share the stimuli's size and leading dimension, the pixel grid, "
+                 "the padded basis size and the capacity of their workspaces"),
+    _RequestKind(kind="closure", regime="full", book="full_closure_", gated=True, run_single=_closure_full_run_single,
+                 entry="gpfit_fit_eval_batch", batch=_closure_full_batch_raw, unit=_closure_full_unit,
+                 key=_closure_full_bucket_key,
+                 share="the full-rank requests of one call share the stimuli's size and leading dimension, the pixel grid, "
+                 "the capacity of their workspaces and the reuse_V flag"))}
+
+
+def _request_kind(q):
+    return _REQUEST_KINDS[q["kind"], q.get("regime")]
 
 
 def _request_run_single(q):
-    return _REQUEST_KINDS[q["kind"]][0](q)
-
-
-def _request_run_group(qs):
-    return _REQUEST_KINDS[qs[0]["kind"]][1](qs)
+    return _request_kind(q).run_single(q)
 
 
 def _request_bucket_key(q):
-    return (q["kind"],) + _REQUEST_KINDS[q["kind"]][2](q)
+    return (q["kind"],) + _request_kind(q).key(q)
+
+
+def _request_run_group(qs):
+    """One call of the batch entry point of the requests' kind on requests of one bucket (``_request_bucket_key``), each
+    on its own workspace; per request what the kind's ``run_single`` returns, with the same bits."""
+    kind = _request_kind(qs[0])
+    if len({_request_bucket_key(q) for q in qs}) != 1:
+        raise ValueError(f"{kind.entry}: {kind.share}")
+    rc, *arrays = kind.batch([q["engine"]._ctx for q in qs], qs)
+    _lib.check(rc, kind.entry)
+    return [kind.unit(q, u, *arrays) for u, q in enumerate(qs)]
+
+
+def _submit(q):
+    """The result of the request's device call: in a fit of ``varGP_cells`` the call is the wave's -- the request goes to
+    the rendezvous and comes back as one unit of a group call -- unless the kind is a full-rank one and
+    ``FULL_RANK_GROUPS`` is off; anywhere else it is the kind's single call."""
+    kind = _request_kind(q)
+    rendezvous = getattr(_CELLS, "rendezvous", None)
+    if rendezvous is not None and (FULL_RANK_GROUPS or not kind.gated):
+        return rendezvous.call(q)
+    return kind.run_single(q)
 
 
 def _closure_sparse_steps(theta, lims, n_px_side, x, xtilde, r, B, m_b, V_b, f_params):

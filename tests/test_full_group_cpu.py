@@ -242,27 +242,31 @@ def test_a_failing_group_is_raised_in_its_participants_only():
 
 def test_the_dispatchers_send_each_kind_to_its_own_call(monkeypatch):
     seen = []
-    for name in ("_chain_full_run_single", "_closure_full_run_single", "_chain_run_single"):
-        monkeypatch.setattr(gp, name, lambda q, name=name: seen.append((name, q["name"])) or name)
-    for name in ("_chain_full_run_group", "_closure_full_run_group", "_chain_run_group"):
-        monkeypatch.setattr(gp, name, lambda qs, name=name: seen.append((name, [q["name"] for q in qs])) or [name] * len(qs))
-    f0, f1 = dict(chain_full(), name="f0"), dict(chain_full(), name="f1")
-    c0, c1 = dict(closure_full(), name="c0"), dict(closure_full(), name="c1")
-    p0 = dict(chain(), name="p0")
-    assert gp._request_run_single(f0) == "_chain_full_run_single" and gp._request_run_single(c0) == "_closure_full_run_single"
-    assert gp._request_run_single(p0) == "_chain_run_single"
-    assert gp._request_run_group([f0, f1]) == ["_chain_full_run_group"] * 2
-    assert gp._request_run_group([c0, c1]) == ["_closure_full_run_group"] * 2
-    assert gp._request_run_group([p0, p0]) == ["_chain_run_group"] * 2
-    assert seen == [("_chain_full_run_single", "f0"), ("_closure_full_run_single", "c0"), ("_chain_run_single", "p0"),
-                    ("_chain_full_run_group", ["f0", "f1"]), ("_closure_full_run_group", ["c0", "c1"]),
-                    ("_chain_run_group", ["p0", "p0"])]
+    names = {("chain_full", None): "chain_full", ("closure", "full"): "closure_full", ("chain", None): "chain"}
+    for key, name in names.items():
+        monkeypatch.setitem(gp._REQUEST_KINDS, key, gp._REQUEST_KINDS[key]._replace(
+            run_single=lambda q, name=name: seen.append((name + " single", q["name"])) or name + " single",
+            batch=lambda ctxs, qs, name=name: seen.append((name + " group", [q["name"] for q in qs])) or (0, name + " group"),
+            unit=lambda q, u, out: out))
+    eng = type("Engine", (), {"_ctx": 0})()
+    f0, f1 = dict(chain_full(), name="f0", engine=eng), dict(chain_full(), name="f1", engine=eng)
+    c0, c1 = dict(closure_full(), name="c0", engine=eng), dict(closure_full(), name="c1", engine=eng)
+    p0 = dict(chain(), name="p0", engine=eng)
+    assert gp._request_run_single(f0) == "chain_full single" and gp._request_run_single(c0) == "closure_full single"
+    assert gp._request_run_single(p0) == "chain single"
+    assert gp._request_run_group([f0, f1]) == ["chain_full group"] * 2
+    assert gp._request_run_group([c0, c1]) == ["closure_full group"] * 2
+    assert gp._request_run_group([p0, p0]) == ["chain group"] * 2
+    assert seen == [("chain_full single", "f0"), ("closure_full single", "c0"), ("chain single", "p0"),
+                    ("chain_full group", ["f0", "f1"]), ("closure_full group", ["c0", "c1"]),
+                    ("chain group", ["p0", "p0"])]
     try:
-        gp._closure_run_group([c0, dict(sparse(), name="s0")])
+        gp._request_run_group([c0, dict(sparse(), name="s0", engine=eng)])
     except ValueError as err:
         assert "share" in str(err)
     else:
         raise AssertionError("a call with both regimes was not refused")
+    assert len(seen) == 6
 
 
 def test_the_switch_and_the_counters_exist():

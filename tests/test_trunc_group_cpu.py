@@ -31,6 +31,10 @@ class M:
         return self.ld
 
 
+class Engine:
+    _ctx = 0
+
+
 def trunc(N=200, n_kept=70, ldx=64, rows=8, cols=8, stream=None, dev=0, cap=256):
     return {"kind": "closure", "regime": "truncated", "x": M(ldx, dev), "stream": Stream(stream), "N": N, "n_kept": n_kept,
             "rows": rows, "cols": cols, "cap": cap}
@@ -129,17 +133,23 @@ def test_truncated_and_sparse_closures_waiting_together_go_out_as_separate_calls
 
 
 def test_the_dispatchers_send_a_request_to_its_regimes_call(monkeypatch):
-    """_closure_run_single / _closure_run_group look at the regime field; a mixed list is refused."""
+    """_request_run_single / _request_run_group take the truncated kind's record for a request with that regime field; a
+    mixed list is refused."""
     seen = []
-    monkeypatch.setattr(gp, "_closure_projected_run_single", lambda q: seen.append(("single", q["name"])) or (0, [0.0] * 16))
-    monkeypatch.setattr(gp, "_closure_projected_run_group", lambda qs: seen.append(("group", [q["name"] for q in qs])) or
-                        [(0, [0.0] * 16)] * len(qs))
-    t0, t1 = dict(trunc(), name="t0"), dict(trunc(n_kept=100), name="t1")
+    kind = gp._REQUEST_KINDS["closure", "truncated"]
+    monkeypatch.setitem(gp._REQUEST_KINDS, ("closure", "truncated"), kind._replace(
+        run_single=lambda q: seen.append(("single", q["name"])) or (0, [0.0] * 16),
+        batch=lambda ctxs, qs: seen.append(("group", [q["name"] for q in qs])) or (0, [0.0] * 16 * len(qs), [0] * len(qs))))
+    sparse_kind = gp._REQUEST_KINDS["closure", None]
+    monkeypatch.setitem(gp._REQUEST_KINDS, ("closure", None), sparse_kind._replace(
+        run_single=lambda q: seen.append(("sparse single", q["name"])), batch=lambda ctxs, qs: seen.append("sparse group")))
+    t0, t1 = dict(trunc(), name="t0", engine=Engine()), dict(trunc(n_kept=100), name="t1", engine=Engine())
     assert gp._request_run_single(t0)[0] == 0 and len(gp._request_run_group([t0, t1])) == 2
     assert seen == [("single", "t0"), ("group", ["t0", "t1"])]
     try:
-        gp._closure_run_group([t0, dict(sparse(), name="s0")])
+        gp._request_run_group([t0, dict(sparse(), name="s0", engine=Engine())])
     except ValueError as err:
         assert "share" in str(err)
     else:
         raise AssertionError("a call with both regimes was not refused")
+    assert seen == [("single", "t0"), ("group", ["t0", "t1"])]
