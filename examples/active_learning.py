@@ -2,13 +2,15 @@
 then repeatedly score every remaining image with the information-gain utility, add the best one to the training
 and inducing sets and refit from the previous posterior.
 
-    python examples/active_learning.py --pool 1200 --start 300 --iterations 5 [--notebook-step]
+    python examples/active_learning.py --pool 1200 --start 300 --iterations 5 [--per-round 8] [--notebook-step]
 
 The step between two fits is ``utils.extend_inducing_set``: K~ grown by its latest column and, while every
 eigenvalue is kept, the Cholesky factor of the previous fit extended by one row (gpfit_potrf_append) -- no
 eigendecomposition per added image.  ``--notebook-step`` prepares the refit the notebook's way instead (eigh of the
 grown matrix, :1889-1900) so that the two can be timed against each other; one iteration of the loop is checked
-against the real reference in the GPU suite (fixture g9)."""
+against the real reference in the GPU suite (fixture g9).  ``--per-round B`` runs the loop the way a rig shows stimuli,
+in batches: a round takes the B images of largest utility, grows the model by all of them in ONE
+``extend_inducing_set`` (the factor by a block of B rows, gpfit_potrf_append_block) and refits once."""
 import argparse
 import contextlib
 import copy
@@ -26,8 +28,11 @@ ap.add_argument("--pool", type=int, default=1200, help="images available")
 ap.add_argument("--start", type=int, default=300, help="images of the initial fit")
 ap.add_argument("--iterations", type=int, default=5)
 ap.add_argument("--px", type=int, default=8, help="pixels per side")
+ap.add_argument("--per-round", type=int, default=1, help="images added per round (one preparation and one refit per round)")
 ap.add_argument("--notebook-step", action="store_true", help="eigh of the grown K~ for every added image, as the notebook does")
 args = ap.parse_args()
+if args.per_round < 1:
+    ap.error("--per-round must be at least 1")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -79,14 +84,15 @@ for it in range(args.iterations):
         lam_m, lam_var = U.lambda_moments(xstar[:, mask], model["K_tilde_b"], K_star_b @ model["K_tilde_inv_b"], Kvec_star,
                                           K_star_b, C, model["m_b"], model["V_b"], th)
         u = U.nd_utility(A ** 2 * lam_var, A * lam_m + lambda0, r_counts)
-        best = remaining[int(u.argmax())]
+        take = min(args.per_round, remaining.shape[0])
+        best = remaining[torch.topk(u.reshape(-1), take).indices.cpu()] if take > 1 else remaining[int(u.argmax())][None]
         sync()
         t_score = time.time() - t0
         # add it and prepare the refit from the previous posterior
         t0 = time.time()
-        in_use = torch.cat((in_use, best[None]))
+        in_use = torch.cat((in_use, best))
         n = in_use.shape[0]
-        grown = U.extend_inducing_set(model, X[best], route="eigh" if args.notebook_step else None)
+        grown = U.extend_inducing_set(model, X[best[0]] if take == 1 else X[best], route="eigh" if args.notebook_step else None)
         nxt = {"fit_parameters": dict(model["fit_parameters"]), "hyperparams_tuple": model["hyperparams_tuple"],
                "f_params": model["f_params"], **grown}
         nxt["fit_parameters"].update({"ntilde": n, "in_use_idx": in_use, "xtilde_idx": in_use, "maxiter": 2})
@@ -97,6 +103,6 @@ for it in range(args.iterations):
         sync()
         t_fit = time.time() - t0
     assert not err["is_error"], err
-    print(f"iteration {it + 1}: scored {remaining.shape[0]} images in {t_score * 1e3:.1f} ms (max utility {float(u.max()):.4f}, image {int(best)}); "
-          f"refit prepared in {t_prep * 1e3:.1f} ms ({nxt['init_kernel']['basis_route']} route), "
+    print(f"iteration {it + 1}: scored {remaining.shape[0]} images in {t_score * 1e3:.1f} ms (max utility {float(u.max()):.4f}, image {int(best[0])}); "
+          f"{take} per round, refit prepared in {t_prep * 1e3:.1f} ms ({nxt['init_kernel']['basis_route']} route), "
           f"refit on {n} images in {t_fit:.2f} s, log marginal {float(model['values_track']['loss_track']['logmarginal'][-1]):.3f}")

@@ -46,6 +46,7 @@ _SIGS = {
                              vp, vp, vp]),
     "gpfit_potrf": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, i64, pd, ctypes.POINTER(i32)]),
     "gpfit_potrf_append": (i32, [vp, vp, vp, i64, vp, i64, i64, vp, pd, ctypes.POINTER(i32)]),
+    "gpfit_potrf_append_block": (i32, [vp, vp, vp, i64, vp, i64, i64, i64, vp, i64, pd, ctypes.POINTER(i32)]),
     "gpfit_estep": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, f64, vp, vp, i64]),
     "gpfit_estep_projected": (i32, [vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, f64, vp, vp, i64, vp, vp,
                                     vp]),

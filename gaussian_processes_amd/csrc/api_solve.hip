@@ -211,6 +211,83 @@ int gpfit_potrf_append(gpfit_ctx* c, void* stream, double* L, int64_t ldl, doubl
   return 0;
 }
 
+// The block step (k rows at once; skinny.hip has the two reductions over n), nine launches whatever n and k:
+//   Y = L^-1 K12           slabs + sum   (the sum also writes L21 = Y^T and zeroes columns n .. of the rows above)
+//   S = K22 - Y^T Y        slabs + sum   (into a 128-tile with a unit diagonal behind k)
+//   L22, L22^-1            the register-resident leaf on that tile (info_base = n: pivot j reports n + j + 1; the padding
+//                          pivots are 1 and never reported)
+//   W = L^-T Y             slabs + sum   (the triangular extent only)
+//   [L^-1]21 = -L22^-1 W^T one slab (the reduction is k <= 128 long), stored transposed and negated as it is formed
+//   the two k x k diagonal blocks and the log-det
+// Work matrices: Tmp (partials), TmpV (Y), Kbuf (W), Abuf / Lbuf / Libuf (the three tiles) -- none of them carries
+// anything between calls (Vbuf, LVbuf and the lv_valid state are not touched).
+int gpfit_potrf_append_block(gpfit_ctx* c, void* stream, double* L, int64_t ldl, double* Linv, int64_t ldi, int64_t n,
+                             int64_t k, const double* Kcols, int64_t ldk, double* logdet_inout_host, int* info_host) {
+  auto refuse = [&](const std::string& why) {
+    set_error("gpfit_potrf_append_block: " + why);
+    return -3;
+  };
+  if (!c || !L || !Linv || !Kcols) return refuse("bad argument: null context or operand");
+  if (n < 1) return refuse("bad argument: n < 1");
+  if (k < 1 || k > SKINNY_LD) return refuse("k = " + std::to_string(k) + " is not within 1 .. " + std::to_string(SKINNY_LD));
+  if (ldl < n + k || ldi < n + k || ldk < k)
+    return refuse("bad argument: the factors need room for rows and columns n .. n + k - 1 (ldl, ldi >= n + k; ldk >= k)");
+  GP_CTX_ENTER(c, "gpfit_potrf_append_block");
+  if (n + k > c->np_cap) return refuse("matrix larger than the context capacity");
+  hipStream_t s = (hipStream_t)stream;
+  const int ni = (int)n, ki = (int)k;
+  const int nslab = skinny_slabs(ni);
+  const int64_t cap = (int64_t)c->np_cap * c->np_cap, pz = (int64_t)ni * SKINNY_LD;
+  if (nslab * pz > cap || nslab * (int64_t)ki * SKINNY_LD > cap) return refuse("the partials do not fit the context's work matrix");
+  double *P = c->Tmp, *Y = c->TmpV, *W = c->Kbuf, *St = c->Abuf, *Lt = c->Lbuf, *Lit = c->Libuf;
+  GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
+  SkinnyArgs g{};
+  SkinnySumArgs r{};
+  g.alpha = 1.0; g.kc = ki;
+  r.P = P; r.kc = ki; r.L = L; r.ldl = ldl; r.Li = Linv; r.ldi = ldi; r.n = ni; r.Kc = Kcols; r.ldk = ldk;
+  // Y = L^-1 K12
+  g.A = Linv; g.sam = ldi; g.sar = 1; g.tri = 1; g.M = ni; g.K = ni;
+  g.B = Kcols; g.sbr = ldk; g.sbc = 1;
+  g.O = P; g.soz = pz; g.som = SKINNY_LD; g.soc = 1;
+  GP_TRY(launch_skinny_slabs(g, s));
+  r.pz = pz; r.M = ni; r.nslab = nslab; r.tri = 1; r.mode = SKINNY_SUM_ROWS; r.dst = Y;
+  GP_TRY(launch_skinny_sum(r, s));
+  // S = K22 - Y^T Y
+  g.A = Y; g.sam = 1; g.sar = SKINNY_LD; g.tri = 0; g.M = ki; g.K = ni;
+  g.B = Y; g.sbr = SKINNY_LD; g.sbc = 1;
+  g.soz = (int64_t)ki * SKINNY_LD;
+  GP_TRY(launch_skinny_slabs(g, s));
+  r.pz = g.soz; r.M = ki; r.tri = 0; r.mode = SKINNY_SUM_SCHUR; r.dst = St;
+  GP_TRY(launch_skinny_sum(r, s));
+  // L22 and its inverse
+  LeafBatchT<double> bt{};
+  bt.A[0] = St; bt.L[0] = Lt; bt.Li[0] = Lit; bt.info[0] = c->info + INFO_K;
+  bt.lda = bt.ldl = bt.ldi = SKINNY_LD; bt.info_base = ni; bt.n = 1;
+  GP_TRY(launch_chol_leaf_batch(bt, s));
+  // W = L^-T Y
+  g.A = Linv; g.sam = 1; g.sar = ldi; g.tri = 2; g.M = ni; g.K = ni;
+  g.soz = pz;
+  GP_TRY(launch_skinny_slabs(g, s));
+  r.pz = pz; r.M = ni; r.tri = 2; r.mode = SKINNY_SUM_PLAIN; r.dst = W;
+  GP_TRY(launch_skinny_sum(r, s));
+  // [L^-1]21 = -L22^-1 W^T: out(m = column j, c = row a) = -sum_b W[j][b] L22^-1[a][b]
+  g.A = W; g.sam = SKINNY_LD; g.sar = 1; g.tri = 0; g.M = ni; g.K = ki;
+  g.B = Lit; g.sbr = 1; g.sbc = SKINNY_LD;
+  g.O = Linv + n * ldi; g.soz = 0; g.som = 1; g.soc = ldi; g.alpha = -1.0;
+  GP_TRY(launch_skinny_slabs(g, s));
+  GP_TRY(launch_append_block_finish(Lt, Lit, L, ldl, Linv, ldi, ni, ki, c->scal + S_APPEND_LOGDET, s));
+  GP_HIP(hipMemcpyAsync(c->scal_host + S_APPEND_LOGDET, c->scal + S_APPEND_LOGDET, sizeof(double), hipMemcpyDeviceToHost, s));
+  GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  GP_HIP(hipStreamSynchronize(s));
+  if (info_host) *info_host = c->info_host[INFO_K];
+  if (c->info_host[INFO_K] != 0) {
+    set_error("gpfit_potrf_append_block: the extended matrix is not positive definite");
+    return c->info_host[INFO_K];
+  }
+  if (logdet_inout_host) *logdet_inout_host += c->scal_host[S_APPEND_LOGDET];
+  return 0;
+}
+
 int gpfit_potrf(gpfit_ctx* c, void* stream, const double* A, int64_t lda, int64_t n, double* L, int64_t ldl,
                 double* Linv, int64_t ldi, double* logdet_host, int* info_host) {
   if (!c || !A || n <= 0) {

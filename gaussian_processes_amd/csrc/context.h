@@ -88,6 +88,7 @@ enum ScalSlot {
   S_FPARAM = 32,                        // 32-38, scal_host only: launch_fparam writes them directly (gpfit_fparam_eval)
   S_LOGDET_V = 40,                      // log|V| (launch_logdet / launch_logdet_pair); kept while lv_valid
   S_APPEND = 48, S_APPEND_LAMBDA = 49,  // gpfit_potrf_append: l . l, the new diagonal entry
+  S_APPEND_LOGDET = 50,                 // gpfit_potrf_append_block: 2 sum log diag L22
   S_LBFGS = 52,                         // 52-60, scal_host only: launch_fparam_lbfgs writes them directly
 };
 // gpfit_ctx::info / info_host (4 ints)

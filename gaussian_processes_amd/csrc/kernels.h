@@ -53,6 +53,45 @@ struct LeafBatchT {
 };
 template <typename R> int launch_chol_leaf_batch(const LeafBatchT<R>& bt, hipStream_t s);
 
+// ---- skinny.hip: products with at most 128 columns on one side and a long reduction, cut into fixed slabs of the
+// reduction across workgroups (gpfit_potrf_append_block).  Stage 1 writes per-slab partials, stage 2 adds them in slab
+// order: no atomics, the same bits on every run.
+constexpr int SKINNY_SLAB = 256;   // rows of the reduction per slab
+constexpr int SKINNY_MT = 64;      // output rows per workgroup
+constexpr int SKINNY_LD = 128;     // widest skinny side = leading dimension of the partials and of the n x k work matrices
+struct SkinnyArgs {
+  const double* A; int64_t sam, sar;   // op(A)(m, r) at A[m sam + r sar]
+  const double* B; int64_t sbr, sbc;   // B(r, c) at B[r sbr + c sbc]
+  double* O; int64_t soz, som, soc;    // out(z)(m, c) at O[z soz + m som + c soc]
+  double alpha;
+  int M, K, kc;                        // rows of the output, length of the reduction, columns (1 .. 128)
+  int tri;                             // 0 dense; op(A)(m, r) is taken as zero for 1: r > m, 2: r < m
+};
+inline int skinny_slabs(int K) { return (K + SKINNY_SLAB - 1) / SKINNY_SLAB; }
+// does slab z hold anything of the row panel that starts at row mt0 (a multiple of SKINNY_MT)?
+__host__ __device__ inline bool skinny_slab_live(int tri, int z, int mt0) {
+  if (tri == 1) return z * SKINNY_SLAB < mt0 + SKINNY_MT;
+  if (tri == 2) return (z + 1) * SKINNY_SLAB > mt0;
+  return true;
+}
+int launch_skinny_slabs(const SkinnyArgs& a, hipStream_t s);
+enum SkinnySumMode {
+  SKINNY_SUM_PLAIN = 0,   // dst[m][c] = sum
+  SKINNY_SUM_ROWS = 1,    // and L[n + c][m] = sum, L[m][n + c] = Li[m][n + c] = 0   (Y = L^-1 K12: L21 = Y^T)
+  SKINNY_SUM_SCHUR = 2,   // dst = the 128 x 128 tile of S = K22 - sum (K22 = rows n .. of Kc, lower triangle), unit diagonal behind k
+};
+struct SkinnySumArgs {
+  const double* P; int64_t pz;   // partial (z)(m, c) at P[z pz + m SKINNY_LD + c]
+  int M, kc, nslab, tri, mode;
+  double* dst;                   // [.][SKINNY_LD]
+  double* L; int64_t ldl; double* Li; int64_t ldi; int n;   // SKINNY_SUM_ROWS
+  const double* Kc; int64_t ldk;                             // SKINNY_SUM_SCHUR (and n)
+};
+int launch_skinny_sum(const SkinnySumArgs& a, hipStream_t s);
+// rows n .. n + k - 1, columns n .. of both factors from the leaf's 128-tiles (zero above the diagonal); logdet[0] = 2 sum log diag
+int launch_append_block_finish(const double* Lt, const double* Lit, double* L, int64_t ldl, double* Li, int64_t ldi, int n,
+                               int k, double* logdet, hipStream_t s);
+
 // ---- elementwise.hip  (templated on the scalar type R = double | float; reductions are always
 //      accumulated and returned in fp64)
 // Spatial metric C (utils.py:861-914) over the masked pixels pix[d] of an n_rows x n_cols

@@ -332,6 +332,48 @@ def cholesky_append(L, Linv, kcol, logdet=0.0):
     return float(ld.value), int(info.value)
 
 
+APPEND_BLOCK_MAX = 128   # columns of one gpfit_potrf_append_block call
+
+
+def cholesky_append_block(L, Linv, Kcols, logdet=0.0):
+    """Factor of ``[[K, K12], [K12^T, K22]]`` from the factor of K, k rows at once (``gpfit_potrf_append_block``):
+    ``L``, ``Linv`` are (n+k) x (n+k) device tensors whose leading n x n blocks hold the factor of K and its
+    inverse, ``Kcols`` the (n+k) x k block of the new last k columns (of its bottom k x k block only the lower
+    triangle is read).  Rows n .. n+k-1 of both are written in place; returns ``(logdet_new, info)``.  Any k >= 1:
+    the columns go to the library at most 128 at a time, each chunk growing the factor the next one starts from;
+    a chunk that fails stops the sweep and its ``info`` (the 1-based index of the pivot in the grown matrix) is
+    returned with the log-det of the chunks before it.  A closed-loop round that shows b images costs O(n^2 b) in
+    two passes over ``L^-1`` and one host wait per chunk, where b ``cholesky_append`` calls wait b times."""
+    if not (isinstance(L, torch.Tensor) and isinstance(Linv, torch.Tensor) and isinstance(Kcols, torch.Tensor)):
+        raise ValueError("cholesky_append_block: L, Linv and Kcols must be tensors")
+    if Kcols.dim() != 2 or Kcols.shape[1] < 1:
+        raise ValueError("cholesky_append_block: Kcols must be (n+k) x k with k >= 1")
+    nk, k = Kcols.shape
+    n = nk - k
+    if n < 1 or L.shape != (nk, nk) or Linv.shape != (nk, nk):
+        raise ValueError("cholesky_append_block: L and Linv must be (n+k) x (n+k) and Kcols (n+k) x k, n >= 1")
+    if not (L.is_cuda and Linv.is_cuda and Kcols.is_cuda):
+        raise ValueError("cholesky_append_block: L, Linv and Kcols must be device tensors")
+    if L.dtype != TORCH_DTYPE or Linv.dtype != TORCH_DTYPE or L.stride(1) != 1 or Linv.stride(1) != 1:
+        raise ValueError("cholesky_append_block: L and Linv must be row-major float64")
+    if Kcols.dtype != TORCH_DTYPE or Kcols.stride(1) != 1:
+        raise ValueError("cholesky_append_block: Kcols must be row-major float64")
+    lib = _lib.load()
+    eng = get_engine(nk, 1)
+    ld = ctypes.c_double(float(logdet))
+    info = ctypes.c_int(0)
+    for c0 in range(0, k, APPEND_BLOCK_MAX):
+        kc = min(APPEND_BLOCK_MAX, k - c0)
+        cols = Kcols[:, c0:]                  # rows 0 .. n + c0 + kc - 1, columns c0 .. c0 + kc - 1 of the grown matrix
+        rc = lib.gpfit_potrf_append_block(eng._ctx, _stream(), L.data_ptr(), L.stride(0), Linv.data_ptr(), Linv.stride(0),
+                                          n + c0, kc, cols.data_ptr(), Kcols.stride(0), ctypes.byref(ld), ctypes.byref(info))
+        if rc < 0:
+            _lib.check(rc, "gpfit_potrf_append_block")
+        if info.value != 0:
+            break
+    return float(ld.value), int(info.value)
+
+
 def spd_inverse(M):
     """M^-1 = L^-T L^-1 for a symmetric positive definite matrix (replaces the LU
     ``torch.linalg.solve(M, I)`` of utils.py:2067)."""
@@ -1948,16 +1990,21 @@ def extend_inducing_set(fit_model, x_new, route=None):
     the grown matrix goes through ``_stabilised_basis`` like any other.
 
     Returns ``dict(xtilde=, m=, V=, init_kernel=)``; ``x_new`` is one image (any shape with the model's pixel
-    count).  The caller updates ``fit_parameters['ntilde']``.  PRECONDITION (the closed loop of the notebook, where
+    count) or the several images of a round (anything that reshapes to ``[-1, n_pixels]``): those are prepared in one
+    go, the factor grown by one block step (``_extend_inducing_block``), while one image takes the rank-1 step below
+    with the bits it always had.  The caller updates ``fit_parameters['ntilde']``.  PRECONDITION (the closed loop of the notebook, where
     ``in_use_idx == xtilde_idx``): the refit's training set is the grown inducing set, ``x == xtilde`` -- the
     ``init_kernel`` returned here carries ``K = K~`` and ``KKtilde_inv_b = B``, which is only the kernel of THAT
     training set; ``varGP`` refuses it for any other (``init_kernel['square']``).
     ``route='eigh'`` forces the notebook's own step (eigendecomposition of the grown matrix), for A/B timing."""
     xt = _cu(fit_model['xtilde'])
     n, npx = xt.shape
-    row = _cu(x_new).reshape(1, -1)
-    if row.shape[1] != npx:
-        raise ValueError(f"extend_inducing_set: the new image has {row.shape[1]} pixels, the model {npx}")
+    x_new = _cu(x_new)
+    if x_new.numel() == 0 or x_new.numel() % npx != 0:
+        raise ValueError(f"extend_inducing_set: the new image has {x_new.numel()} pixels, the model {npx}")
+    if x_new.numel() > npx:
+        return _extend_inducing_block(fit_model, x_new.reshape(-1, npx), route)
+    row = x_new.reshape(1, -1)
     theta = fit_model['hyperparams_tuple'][0]
     fk = fit_model['final_kernel']
     C, mask = _cu(fit_model['C']), fit_model['mask'].to(xt.device)
@@ -1992,6 +2039,66 @@ def extend_inducing_set(fit_model, x_new, route=None):
         if info == 0 and _all_kept_given_factor(K_new, Li):
             route, chol = 'identity', {'L': L, 'Linv': Li}
             B = _mark_identity(torch.eye(n + 1, dtype=TORCH_DTYPE, device=xt.device))
+            Kinv = matmul(Li, Li, transA=True)
+            K_b_, K_inv_b = K_new, (Kinv + Kinv.T) * 0.5
+    if route is None:
+        _BASIS.factor = None
+        _, B, K_b_, K_inv_b = _stabilised_basis(K_new, route=forced)
+        route = _BASIS.route
+        if route == 'identity' and _BASIS.factor is not None:
+            chol = {'L': _BASIS.factor[0], 'Linv': _BASIS.factor[1]}
+        _BASIS.factor = None
+    KB = K_new if route == 'identity' else matmul(K_new, B)
+    init_kernel = {'C': C, 'mask': mask, 'K_tilde': K_new, 'K': K_new, 'Kvec': Kvec_new, 'B': B, 'K_tilde_b': K_b_, 'K_b': KB,
+                   'K_tilde_inv_b': K_inv_b, 'KKtilde_inv_b': B, 'basis_route': route, 'chol': chol, 'square': True}
+    return {'xtilde': xt_new, 'm': m_new, 'V': V_new, 'init_kernel': init_kernel}
+
+
+def _extend_inducing_block(fit_model, rows, route=None):
+    """``extend_inducing_set`` for k > 1 images (a closed-loop round that shows a batch): what k successive calls
+    prepare, in one go -- the k new columns of K~ from one ``acosker`` call, the grown tensors copied once, every new
+    point with the mean of the old ``m`` (appending its own mean does not move the mean of ``m``) and a unit variance,
+    the factor grown by ONE block step (``cholesky_append_block``), the all-kept proof and ``K~^-1 = L^-T L^-1``
+    evaluated once, on the grown factor.  The single-image step above is kept as it was, line for line, so that its
+    results keep their bits; this is the same sequence with k columns."""
+    xt = _cu(fit_model['xtilde'])
+    n = xt.shape[0]
+    k = rows.shape[0]
+    theta = fit_model['hyperparams_tuple'][0]
+    fk = fit_model['final_kernel']
+    C, mask = _cu(fit_model['C']), fit_model['mask'].to(xt.device)
+    K_old, Kvec_old = _cu(fk['K_tilde']), _cu(fk['Kvec'])
+    xt_new = torch.cat((xt, rows), 0)
+    xm = xt_new[:, mask].contiguous()
+    xm_new = xm[n:].contiguous()
+    cols = acosker(theta, xm, xm_new, C=C, dC=None, diag=False).reshape(n + k, k)                # latest k columns
+    K_new = torch.empty((n + k, n + k), dtype=TORCH_DTYPE, device=xt.device)
+    K_new[:n, :n] = K_old
+    K_new[:n, n:] = cols[:n]
+    K_new[n:, :n] = cols[:n].T
+    corner = torch.tril(cols[n:])                                                                 # the new diagonal block from its lower triangle
+    K_new[n:, n:] = corner + torch.tril(corner, -1).T
+    Kvec_new = torch.cat((Kvec_old, acosker(theta, xm_new, x2=None, C=C, dC=None, diag=True).reshape(-1)))
+    B_old = fit_model['B']
+    if _is_identity(B_old) or fit_model.get('basis_route') == 'identity':
+        m_img, V_img = _cu(fit_model['m_b']), _cu(fit_model['V_b'])
+    else:
+        B_old = _cu(B_old)
+        m_img = matmul(B_old, _cu(fit_model['m_b']))
+        V_img = matmul(B_old, matmul(_cu(fit_model['V_b']), B_old, transB=True))
+    V_new = torch.eye(n + k, dtype=TORCH_DTYPE, device=xt.device)
+    V_new[:n, :n] = (V_img + V_img.T) * 0.5
+    m_new = torch.cat((m_img, m_img.mean().reshape(1).expand(k)))
+    forced, route, chol = route, None, None
+    if forced is None and fit_model.get('basis_route') == 'identity' and fk.get('chol') is not None:
+        L = torch.zeros((n + k, n + k), dtype=TORCH_DTYPE, device=xt.device)
+        Li = torch.zeros_like(L)
+        L[:n, :n] = _cu(fk['chol']['L'])
+        Li[:n, :n] = _cu(fk['chol']['Linv'])
+        _, info = cholesky_append_block(L, Li, K_new[:, n:].contiguous())
+        if info == 0 and _all_kept_given_factor(K_new, Li):
+            route, chol = 'identity', {'L': L, 'Linv': Li}
+            B = _mark_identity(torch.eye(n + k, dtype=TORCH_DTYPE, device=xt.device))
             Kinv = matmul(Li, Li, transA=True)
             K_b_, K_inv_b = K_new, (Kinv + Kinv.T) * 0.5
     if route is None:

@@ -290,6 +290,21 @@ int gpfit_potrf(gpfit_ctx* ctx, void* stream, const double* A, int64_t lda, int6
 int gpfit_potrf_append(gpfit_ctx* ctx, void* stream, double* L, int64_t ldl, double* Linv, int64_t ldi, int64_t n,
                        const double* kcol, double* logdet_inout_host, int* info_host);
 
+/* Block append: k rows at once (1 <= k <= 128).  L and L^-1 of the n x n matrix K sit in the leading blocks of
+ * (n + k)-sized arrays (device, row-major, ldl, ldi >= n + k) as for the rank-1 call; Kcols[n + k][ldk >= k] holds the
+ * new last k columns of K' = [K K12; K12^T K22] (device, row-major; of its bottom k x k block only the lower
+ * triangle is read, and of L^-1 only its lower triangle).  Writes rows n .. n + k - 1 of both factors in place,
+ *   Y = L^-1 K12,  L21 = Y^T,  L22 = chol(K22 - Y^T Y),  [L'^-1]22 = L22^-1,  [L'^-1]21 = -L22^-1 Y^T L^-1,
+ * zeroes columns n .. n + k - 1 of the rows above and the strict upper triangles of the new diagonal blocks, and
+ * adds 2 sum log diag L22 to *logdet_inout_host.  O(n^2 k) in two passes over L^-1, a fixed number of launches
+ * whatever n and k, no floating-point atomics (the same inputs give the same bits), one synchronisation.
+ * Returns 0, or the LAPACK info n + j + 1 (1-based, in K') of the first non-positive pivot: rows n .. are then
+ * meaningless, the leading n x n blocks and the log-det are untouched.  -3: a null pointer, n < 1, k outside
+ * 1 .. 128, ldl or ldi < n + k, ldk < k, n + k above the context capacity, a pending asynchronous evaluation
+ * (the argument checks come before the context or the device is touched). */
+int gpfit_potrf_append_block(gpfit_ctx* ctx, void* stream, double* L, int64_t ldl, double* Linv, int64_t ldi, int64_t n,
+                             int64_t k, const double* Kcols, int64_t ldk, double* logdet_inout_host, int* info_host);
+
 /* E-step Newton update of q(lambda~) = N(m, V) (Estep, alpha = 1 branch, utils.py:1420-1439) in
  * the original basis (a = I): with s = A sqrt(f), M = I + S K~ S = L_M L_M^T, T = L_M^-1 S K~:
  *   V_new = K~ - T^T T,  m_new = V_new (A^2 f o m + A (r - f)).
