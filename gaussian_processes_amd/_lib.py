@@ -60,6 +60,9 @@ _SIGS = {
                                       i32, i32, i32, f64, f64, f64, pd]),
     "gpfit_estep_chain_full_batch": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, pd, i32, pd, i32, i32, i32,
                                            f64, f64, f64, pd]),
+    "gpfit_subspace_sweeps": (i32, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, i32, pd, i32, ctypes.POINTER(i32)]),
+    "gpfit_subspace_sweeps_batch": (i32, [vp, i32, vp, vp, i64, i64, i64, vp, vp, vp, vp, ctypes.POINTER(i32), vp, i32,
+                                          ctypes.POINTER(i32)]),
     "gpfit_fparam_lbfgs_host": (i32, [vp, vp, vp, i64, f64, i32, f64, i32, i32, f64, f64, f64, vp, pd]),
     "gpfit_set_profile": (i32, [vp, i32]),
     "gpfit_get_profile": (i32, [vp, pd]),

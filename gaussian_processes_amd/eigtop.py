@@ -316,7 +316,7 @@ def _filter_gain(applied, a, tau):
 
 
 def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_sweeps=60, angle_tol=1e-7, seed=20240229,
-                   log=None, accelerate=True, basis="eigenvectors", gemm_into=None, start=None):
+                   log=None, accelerate=True, basis="eigenvectors", gemm_into=None, start=None, sweep_chain=None):
     """Eigenpairs of the symmetric positive definite ``K`` with ``lambda > max(lambda_max * tol, tol)``.
 
     Returns ``(eigenvalues ascending [n], eigenvectors [N, n], info)`` or ``None`` when the caller should fall
@@ -342,7 +342,16 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
     kernel matrices has no gap at the threshold -- with a block of twice the kept count the first dropped-out
     eigenvalue is still tau / 4 -- so plain sweeps contract by 0.25 each (16 of them for the 1e-7 certificate);
     the shifted ones by 0.08 (9).  The orthonormalisation after EVERY sweep stays: one factor spreads the
-    block over lambda_max / tau = 1e4, two would exceed what a Gram matrix in fp64 resolves."""
+    block over lambda_max / tau = 1e4, two would exceed what a Gram matrix in fp64 resolves.
+
+    ``sweep_chain``: a callable ``(K, Q, Y_or_None, shifts, want_rr) -> (Q, Y, S)`` that runs the rest of a pass in one go
+    (``utils._basis_sweeps``: one device call): for every shift of the list ``Y = K Q`` (not for the first when ``Y`` is
+    given: it is that product already), ``Y -= shift Q`` where the shift is not zero, one round of ``_cholqr`` (two on the
+    last), ``Q <- Y``; then, with ``want_rr``, ``Y = K Q`` and the symmetrised ``S = Q^T Y``.  It returns ``None`` when a
+    Gram matrix was not positive definite, and so does this function then.  A pass is handed over as soon as its shifts
+    are known -- behind the unshifted sweep and the plan of a cold or warm start, before the first product of a re-swept
+    block and of the plain iteration -- and only for blocks whose width is a multiple of 16.  The plan stays here, and
+    ``info`` counts the products and sweeps the loop below would have run.  ``None``: that loop."""
     import math
     N_true = K.shape[0]
     if N_true % 16:
@@ -353,7 +362,8 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
         Kp = torch.zeros((Np, Np), device=K.device, dtype=K.dtype)
         Kp[:N_true, :N_true] = K
         out = top_eigenpairs(Kp, tol, matmul, cholesky, k0=k0, first_sweeps=first_sweeps, max_sweeps=max_sweeps, angle_tol=angle_tol,
-                             seed=seed, log=log, accelerate=accelerate, basis=basis, gemm_into=gemm_into, start=start)
+                             seed=seed, log=log, accelerate=accelerate, basis=basis, gemm_into=gemm_into, start=start,
+                             sweep_chain=sweep_chain)
         if out is None:
             return None
         vals, vecs, info = out
@@ -397,6 +407,19 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
             return None                      # not a truncation problem any more: a full eigh is the right tool
         shifts, applied = [], []
         i = 0
+        chain = sweep_chain if (sweep_chain is not None and not (k & 15)) else None
+        handed = None           # (Q, Y, S) of a pass that went to the chain
+        if chain is not None and (not accelerate or a_block is not None):
+            # the shifts of this pass do not depend on any product of it: the whole pass goes
+            if accelerate and a_block > 0:
+                applied = _chebyshev_shifts(a_block, sweeps)
+            else:
+                applied = [0.0] * sweeps
+            handed = chain(K, Q, None, list(applied), True)
+            if handed is None:
+                return None
+            info["products"] += sweeps
+            i = sweeps
         while i < sweeps:
             Y = matmul(K, Q)
             info["products"] += 1
@@ -437,6 +460,14 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
                     else:
                         a = a_block
                     shifts = _chebyshev_shifts(a, sweeps - i) if a > 0 else [0.0] * (sweeps - i)
+                    if chain is not None:
+                        # planned: the rest of the pass goes, with the product the plan was made from
+                        handed = chain(K, Q, Y, list(shifts), True)
+                        if handed is None:
+                            return None
+                        applied.extend(shifts)
+                        info["products"] += sweeps - i - 1
+                        break
                 sigma = shifts.pop(0)
                 if sigma != 0.0:
                     Y.sub_(Q, alpha=sigma)
@@ -448,10 +479,14 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
                 return None
             i += 1
         done += sweeps
-        Y = matmul(K, Q)
-        info["products"] += 1
-        S = matmul(Q, Y, transA=True)
-        S = (S + S.T) * 0.5
+        if handed is not None:
+            Q, Y, S = handed
+            info["products"] += 1
+        else:
+            Y = matmul(K, Q)
+            info["products"] += 1
+            S = matmul(Q, Y, transA=True)
+            S = (S + S.T) * 0.5
         if basis == "subspace" and a_plan is not None:
             sub = _kept_subspace(Q, Y, S, tol, a_plan, matmul, cholesky, angle_tol, log=log, gemm_into=gemm_into)
             if sub is not None and 4 * sub["n"] > 3 * k and k < kmax:

@@ -924,6 +924,103 @@ def _estep_chain_full_group(units, n_steps, n_fparam_steps):
                         lambda **u: _chain_full_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, **u))
 
 
+# ------------------------------------------------------------------ the sweeps of a basis rebuild as one device call
+_SWEEPS_Y_READY, _SWEEPS_WANT_RR = 1, 2   # GPFIT_SWEEPS_Y_READY, GPFIT_SWEEPS_WANT_RR of the C header
+
+
+def _sweeps_prepare(K, Q, Y=None, shifts=(), want_rr=True, engine=None):
+    """The arguments of ``_basis_sweeps`` as one request: ``K`` as it is, the block as a copy of its own (the call updates
+    it in place, the caller's ``Q`` is left alone), ``Y`` itself when given (it is the product ``K Q`` the plan formed, and
+    the call's work block from then on), the second work block and ``S``, and the workspace and stream the call runs on,
+    this thread's unless an engine is given.  float64 tensors on one device."""
+    N, k = (int(v) for v in Q.shape)
+    for t, shape in ((K, (N, N)), (Q, (N, k))) + (() if Y is None else ((Y, (N, k)),)):
+        if t.dtype is not TORCH_DTYPE or tuple(t.shape) != shape or t.device != K.device:
+            raise ValueError("_basis_sweeps: K [N, N], Q and Y [N, k] are float64 tensors on one device")
+    K, Y = K.contiguous(), None if Y is None else Y.contiguous()
+
+    def block(*shape):
+        return torch.empty(shape, dtype=TORCH_DTYPE, device=K.device)
+    q = {"kind": "sweeps", "K": K, "Q": Q.contiguous().clone(), "Y": block(N, k) if Y is None else Y, "W": block(N, k),
+         "S": block(k, k) if want_rr else None, "N": N, "k": k, "shifts": [float(v) for v in shifts],
+         "flags": (0 if Y is None else _SWEEPS_Y_READY) | (_SWEEPS_WANT_RR if want_rr else 0)}
+    q["engine"] = engine if engine is not None else get_engine(k, 1)
+    q["stream"] = _stream()
+    return q
+
+
+def _sweeps_bucket_key(q):
+    """Requests with equal keys may share one ``gpfit_subspace_sweeps_batch`` call: what that call shares between its
+    units, and the capacity of their workspaces."""
+    return (q["K"].device.index, q["stream"].value, q["N"], q["k"], q["flags"], -(-q["engine"].n_max // 128))
+
+
+def _sweeps_batch_raw(ctxs, qs, rec=None):
+    """``gpfit_subspace_sweeps_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return
+    code and the ``(step, info)`` pairs, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor
+    given as None goes in as a null pointer; ``rec``: the caller's array instead of a new one."""
+    q0 = qs[0]
+    rec = (ctypes.c_int * (2 * len(qs)))() if rec is None else rec
+    shifts = [_lib.darr(q["shifts"]) if q["shifts"] else None for q in qs]       # (kept alive until the call returns)
+    sigma = (ctypes.c_void_p * len(qs))(*[None if a is None else ctypes.addressof(a) for a in shifts])
+    rc = _lib.load().gpfit_subspace_sweeps_batch(
+        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "K"), q0["K"].stride(0) if q0["K"] is not None else q0["N"],
+        q0["N"], q0["k"], _ptr_table(qs, "Q"), _ptr_table(qs, "Y"), _ptr_table(qs, "W"), _ptr_table(qs, "S"),
+        (ctypes.c_int * len(qs))(*[len(q["shifts"]) for q in qs]), sigma, q0["flags"], rec)
+    return rc, rec
+
+
+def _sweeps_result(q, u, rec):
+    """What a sweeps call returns for its unit ``u``: ``(Q, Y, S)`` of the request, or None when one of its Gram matrices
+    was not positive definite (``rec``: the ``(step, info)`` pairs of the call)."""
+    return None if rec[2 * u + 1] != 0 else (q["Q"], q["Y"], q["S"])
+
+
+def _sweeps_run_single(q):
+    """``gpfit_subspace_sweeps`` on one request."""
+    rec = (ctypes.c_int * 2)()
+    sigma = _lib.darr(q["shifts"]) if q["shifts"] else None
+    K, S = q["K"], q["S"]
+    _lib.check(_lib.load().gpfit_subspace_sweeps(q["engine"]._ctx, q["stream"], K.data_ptr(), K.stride(0), q["N"], q["k"],
+                                                 q["Q"].data_ptr(), q["Y"].data_ptr(), q["W"].data_ptr(),
+                                                 None if S is None else S.data_ptr(), len(q["shifts"]), sigma, q["flags"], rec),
+               "gpfit_subspace_sweeps")
+    return _sweeps_result(q, 0, rec)
+
+
+def _sweeps_run_group(qs):
+    """One ``gpfit_subspace_sweeps_batch`` call on requests of one bucket (``_sweeps_bucket_key``), each on its own
+    workspace; per request what ``_sweeps_run_single`` returns, with the same bits."""
+    if len({_sweeps_bucket_key(q) for q in qs}) != 1:
+        raise ValueError("gpfit_subspace_sweeps_batch: the requests of one call share the device, the stream, N, the block "
+                         "width, the flags and the capacity of their workspaces")
+    rc, rec = _sweeps_batch_raw([q["engine"]._ctx for q in qs], qs)
+    _lib.check(rc, "gpfit_subspace_sweeps_batch")
+    return [_sweeps_result(q, u, rec) for u, q in enumerate(qs)]
+
+
+def _basis_sweeps(K, Q, Y, shifts, want_rr):
+    """The ``sweep_chain`` of ``eigtop.top_eigenpairs`` on the library: the rest of a pass of the subspace iteration --
+    per shift ``Y = K Q`` (not for the first when ``Y`` is given), ``Y -= shift Q``, CholeskyQR (twice on the last) -- and
+    the inputs of its Rayleigh-Ritz step as ONE device call and one wait (``gpfit_subspace_sweeps``) on the calling
+    thread's workspace, with the bits of the loop through ``matmul`` and ``cholesky``.  Returns ``(Q, Y, S)`` as new
+    tensors (``Y`` given is overwritten), or None when a Gram matrix was not positive definite."""
+    return _sweeps_run_single(_sweeps_prepare(K, Q, Y, shifts, want_rr))
+
+
+def _basis_sweeps_group(units):
+    """``_basis_sweeps`` for several independent units (cells: their kernel matrices and blocks) as ONE device call
+    (``gpfit_subspace_sweeps_batch``).  ``units``: one dict per unit with the arguments of ``_basis_sweeps`` by name
+    (``K``, ``Q``, ``shifts`` and optionally ``Y``, ``want_rr``); 1 .. 16 units of one ``(device, stream, N, k, flags,
+    workspace capacity)`` -- all with or all without ``Y``, the same ``want_rr``; the numbers of shifts may differ --
+    otherwise a ValueError before any call.  Returns, per unit, what ``_basis_sweeps`` returns for it, bit for bit: a
+    unit whose factorisation fails has None in its place and stops alone."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"_basis_sweeps_group: 1 .. {MAX_CHAIN_UNITS} units per call")
+    engines = _group_engines(len(units), max(int(u["Q"].shape[1]) for u in units), exact=True)
+    return _sweeps_run_group([_sweeps_prepare(engine=e, **u) for u, e in zip(units, engines)])
+
+
 _BOOKS = ("", "closure_", "full_", "full_closure_")   # the prefixes of the counters a call of the rendezvous is counted in
 
 
@@ -1430,7 +1527,8 @@ def _stabilised_basis(K_tilde, route=None, start=None):
             return None
         top = eigtop.top_eigenpairs(K_tilde, EIGVAL_TOL, matmul, cholesky,
                                     basis="subspace" if want == "subspace" else "eigenvectors", gemm_into=gemm_into,
-                                    start=start if want == "subspace" else None)
+                                    start=start if want == "subspace" else None,
+                                    sweep_chain=_basis_sweeps if SWEEP_CHAIN else None)
         if top is None:
             return None
         vals, vecs, info = top
@@ -1523,6 +1621,10 @@ EIGTOP_BASIS = _os_mod.environ.get("GPFIT_EIGTOP_BASIS", "subspace")
 # _estep_chain_full in the full-rank regime with the identity basis) instead of two calls and two waits per update (module global read at call time; GPFIT_ESTEP_CHAIN=0 turns it off).  A = exp(logA)
 # is then the device's exp, not the host's: a fit may differ from the loop's by rounding.
 ESTEP_CHAIN = _os_mod.environ.get("GPFIT_ESTEP_CHAIN", "1") != "0"
+# The sweeps of a pass of the subspace iteration as one device call (_basis_sweeps) instead of one wait per sweep (module
+# global read at call time; GPFIT_SWEEP_CHAIN=0 turns it off).  The call has the bits of the loop, so the switch changes
+# no number of a fit.
+SWEEP_CHAIN = _os_mod.environ.get("GPFIT_SWEEP_CHAIN", "1") != "0"
 # Under varGP_cells the chains (_estep_chain_full) and the M-step closures of fits in the full-rank regime meet at the
 # wave's rendezvous and go out as group calls (module global read at call time; GPFIT_FULL_RANK_GROUPS=0 turns it off: such
 # a fit then issues its own calls and keeps its turn until it ends).

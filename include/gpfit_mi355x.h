@@ -457,6 +457,40 @@ int gpfit_estep_chain_full_batch(gpfit_ctx* const* ctxs, int n_units, void* stre
                                  const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                                  double tol_grad, double tol_change, double* rec_host);
 
+/* The sweeps of a basis rebuild (eigtop.top_eigenpairs: the inner loop of a pass and the inputs of its Rayleigh-Ritz
+ * step) as ONE call, for 1 .. GPFIT_ESTEP_CHAIN_MAX_UNITS independent units: unit u runs on its own context ctxs[u]
+ * (pairwise distinct, one device) with its own K[u], Q[u], Y[u], W[u], S[u], step count m[u] and shifts sigma[u]; N, k,
+ * ldk and the flags are shared.  Everything is enqueued on `stream`, one synchronisation at the end.
+ * Device: K[u][N][ldk] symmetric (full); Q[u][N][k] in / out (the block, contiguous); Y[u], W[u] [N][k] caller-owned
+ * work blocks (contiguous, distinct from Q[u] and from each other); S[u][k][k] out (read only with WANT_RR; S may be
+ * NULL without it).  Host: m[u] >= 0 and sigma[u][0 .. m[u]) (sigma[u] may be NULL when m[u] is 0).
+ * N and k multiples of 16, 16 <= k <= N, round_up(k, 128) within every context's capacity.
+ * Step j of unit u (j < m[u]):
+ *   Y = K Q                       skipped when j == 0 and GPFIT_SWEEPS_Y_READY is set: Y[u] already holds K Q
+ *   Y -= sigma[u][j] Q            when sigma[u][j] != 0
+ *   G = Y^T Y, G = (G + G^T) / 2, G = L L^T with L^-1 (the factorisation of gpfit_potrf), Y <- Y L^-T: once, and a
+ *   second time on the unit's last step; then Q <- Y.
+ * Tail (GPFIT_SWEEPS_WANT_RR): Y = K Q, S = Q^T Y, S = (S + S^T) / 2, left in Y[u] and S[u].  Without the flag the
+ * contents of Y[u] are unspecified on return; W[u] always is.
+ * Every product is the launch gpfit_dgemm makes of it and the factorisation is gpfit_potrf's, so Q, Y and S have the bits
+ * of that host loop, and a unit has the same bits alone and in any group.  The factorisations of a round run in lock
+ * step, every product of a step is one call on the list of the units that still have that step.
+ * rec_host[n_units][2]: {step, info}.  info = 0: every step ran, step = m[u].  Otherwise info is the LAPACK info of the
+ * first Gram matrix that was not positive definite and step the step it belongs to, counted from 1 (step - 1 steps were
+ * completed); nothing of the failed step or of a later one is written to Q[u], which then holds the block it came with or
+ * the block its completed steps left, and Y[u], S[u] are unspecified.  A unit that fails fails alone: the others finish
+ * with the bits they have without it.
+ * gpfit_subspace_sweeps is the batch call with one unit.
+ * Returns 0 when the sweeps ran, whatever rec_host says; -3, with nothing enqueued, on a bad argument. */
+#define GPFIT_SWEEPS_Y_READY 1
+#define GPFIT_SWEEPS_WANT_RR 2
+#define GPFIT_SUBSPACE_SWEEPS_MAX_STEPS 1024
+int gpfit_subspace_sweeps(gpfit_ctx* ctx, void* stream, const double* K, int64_t ldk, int64_t N, int64_t k, double* Q,
+                          double* Y, double* W, double* S, int m, const double* sigma, int flags, int* rec_host);
+int gpfit_subspace_sweeps_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* K, int64_t ldk,
+                                int64_t N, int64_t k, double* const* Q, double* const* Y, double* const* W,
+                                double* const* S, const int* m, const double* const* sigma, int flags, int* rec_host);
+
 /* Active-learning utility of nstar candidate stimuli, U = H(r|x,D) - <H(r|f,x)>
  * (nd_utility with nd_p_r_given_xD, nd_lambda_r_mean, nd_mean_noise_entropy, utils.py:413-525;
  * call site one_cell_active_training.ipynb: u2d = nd_utility(logf_var, logf_mean, arange(100))).
