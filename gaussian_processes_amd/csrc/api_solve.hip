@@ -1,7 +1,7 @@
 // C-ABI entry points built on the recursive MFMA Cholesky: a standalone factorisation
 // (log_det, general solves of the drop-in module), the fused E-step Newton update and the
 // one-pass firing-rate-parameter evaluation.
-#include "product.h"
+#include "units.h"
 #include "gpfit_mi355x.h"
 
 #include <algorithm>
@@ -15,8 +15,7 @@ using namespace gpfit;
 // look-ahead side stream)
 static CholBatchT<double> one_chain(gpfit_ctx* c, int64_t ld) {
   CholBatchT<double> b;
-  b.nb = 1;
-  b.A[0] = c->Kbuf; b.L[0] = c->Lbuf; b.Li[0] = c->Libuf; b.Tmp[0] = c->Tmp; b.info[0] = c->info + INFO_K;
+  add_k_chain(b, c);
   b.ld = ld;
   return b;
 }
@@ -33,35 +32,27 @@ static int full_update_split(int np) {
   const int n1 = ((kt + 1) / 2) * TILE;
   return n1;
 }
-static int full_update_factor(gpfit_ctx* const* ctxs, int nu, int np, Lane lane) {
+static int full_update_factor(const Units& U, int np, Lane lane) {
   CholBatchT<double> b;
-  for (int u = 0; u < nu; ++u) {
-    gpfit_ctx* c = ctxs[u];
-    const int i = b.nb++;
-    b.A[i] = c->Kbuf; b.L[i] = c->Lbuf; b.Li[i] = c->Libuf; b.Tmp[i] = c->Tmp; b.info[i] = c->info + INFO_K;
-  }
+  for (int i = 0; i < U.cnt; ++i) add_k_chain(b, U.ctx[i]);
   b.ld = np;
-  const uint32_t all = (uint32_t)((1ull << nu) - 1ull);
-  if (full_update_split(np)) return potrf_lockstep(b, 0, np, 0u, lane, all);   // [L^-1]11 and [L^-1]22 only
-  return potrf_lockstep(b, 0, np, all, lane);
+  if (full_update_split(np)) return potrf_lockstep(b, 0, np, 0u, lane, U.chains());   // [L^-1]11 and [L^-1]22 only
+  return potrf_lockstep(b, 0, np, U.chains(), lane);
 }
-static int full_update_products(gpfit_ctx* const* ctxs, int nu, int np, Lane lane) {
+static int full_update_products(const Units& U, int np, Lane lane) {
   const int64_t ld = np;
-  auto at = [&](double* gpfit_ctx::*X, int r, int col) {
-    return mats(nu, ld, [&](int i) { return ctxs[i]->*X + (int64_t)r * ld + col; });
-  };
   const auto Li = &gpfit_ctx::Libuf, L = &gpfit_ctx::Lbuf, SK = &gpfit_ctx::Zbuf, T = &gpfit_ctx::Abuf, Kl = &gpfit_ctx::Wbuf;
   // T = L_M^-1 (S K)          lower x dense                         N^3
   if (const int n1 = full_update_split(np)) {
     const int n2 = np - n1;
-    GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(at(Li, 0, 0))), plain(at(SK, 0, 0)), into(at(T, 0, 0)), 1));
-    GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(at(L, n1, 0)), plain(at(T, 0, 0)), into(at(SK, n1, 0), 1.0)));
-    GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(at(Li, n1, n1))), plain(at(SK, n1, 0)), into(at(T, n1, 0)), 1));
+    GP_TRY(product(lane, {n1, np, n1}, 1.0, plain(tril(U.mats(Li, ld))), plain(U.mats(SK, ld)), into(U.mats(T, ld)), 1));
+    GP_TRY(product(lane, {n2, np, n1}, -1.0, plain(U.mats(L, ld, n1)), plain(U.mats(T, ld)), into(U.mats(SK, ld, n1), 1.0)));
+    GP_TRY(product(lane, {n2, np, n2}, 1.0, plain(tril(U.mats(Li, ld, n1, n1))), plain(U.mats(SK, ld, n1)), into(U.mats(T, ld, n1)), 1));
   } else {
-    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(at(Li, 0, 0))), plain(at(SK, 0, 0)), into(at(T, 0, 0)), 1));
+    GP_TRY(product(lane, {np, np, np}, 1.0, plain(tril(U.mats(Li, ld))), plain(U.mats(SK, ld)), into(U.mats(T, ld)), 1));
   }
   // V = K - T^T T             lower tiles only                      N^3
-  return product(lane, {np, np, np}, -1.0, trans(at(T, 0, 0)), plain(at(T, 0, 0)), into_lower(at(Kl, 0, 0), 1.0));
+  return product(lane, {np, np, np}, -1.0, trans(U.mats(T, ld)), plain(U.mats(T, ld)), into_lower(U.mats(Kl, ld), 1.0));
 }
 
 namespace {
@@ -175,6 +166,89 @@ static int fparam_lbfgs_config(const char* name, int max_iter, int history_size,
   cfg->history_size = history_size;
   return 0;
 }
+
+static_assert(GPFIT_ESTEP_CHAIN_MAX_STEPS == CHAIN_MAX_STEPS, "the header states the cap of the chain block");
+static_assert(GPFIT_ESTEP_CHAIN_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+static_assert(GPFIT_ESTEP_CHAIN_FULL_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+
+// The skeleton of the chained E-steps: what the projected chain (estep_chain_group_impl) and the full-rank chain
+// (estep_chain_full_group_impl) have in common -- n_steps x (a Newton update, its moments, the rate-parameter optimiser)
+// for every unit on its own context, all on the caller's stream with one synchronisation at the end.  A kind of chain
+// hands over its own operands' checks (admit), adds its work matrices to the group (group) and supplies the three
+// stretches of a step that differ (run); everything else -- the shared arguments and their refusals, the bookkeeping
+// fields of the ChainGroupT, the init, the info word, the gated commits of m and V, the optimiser, the collect and the
+// records -- is here once.
+struct ChainCall {
+  // (in the order of the entry points' argument lists)
+  const char* name; gpfit_ctx* const* ctxs; int n_units; void* stream; int64_t N;
+  const double *const *r, *const *kv0;
+  double *const *m, *const *f, *const *V; const int64_t* ldv; double *const *lam_m, *const *lam_var;
+  const double* logA0; int lambda0_mode; const double* lambda0_fixed;
+  int n_steps, max_iter, history_size; double lr, tol_grad, tol_change; double* rec_host;
+  Lbfgs1dConfig cfg;   // (admit fills it)
+
+  // Every refusal of the call, before anything is enqueued.  tables: the kind's own argument tables are there;
+  // operands(u): so are unit u's entries of them; sizes(u): the unit's sizes and leading dimensions are in order;
+  // fits(u): what the kind asks of the unit's context beyond the shared checks -- the sentence of a refusal, or empty.
+  template <typename Operands, typename Sizes, typename Fits>
+  int admit(bool tables, Operands&& operands, Sizes&& sizes, Fits&& fits) {
+    const Refuse refuse{name};
+    if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+    if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS)
+      return refuse("n_steps " + std::to_string(n_steps) + " is not within 1 .. " + std::to_string(CHAIN_MAX_STEPS));
+    if (!tables || !ctxs || !r || !kv0 || !m || !f || !V || !ldv || !lam_m || !lam_var || !logA0 ||
+        (lambda0_mode && !lambda0_fixed) || !rec_host || N <= 0 || N > INT32_MAX)
+      return refuse("bad argument");
+    GP_TRY(fparam_lbfgs_config(name, max_iter, history_size, lr, tol_grad, tol_change, &cfg));
+    for (int u = 0; u < n_units; ++u) {
+      const std::string unit = unit_prefix(n_units, u);
+      if (!ctxs[u] || !r[u] || !kv0[u] || !m[u] || !f[u] || !V[u] || !lam_m[u] || !lam_var[u] || !operands(u))
+        return refuse(unit + "bad argument: null context or operand");
+      if (!sizes(u)) return refuse(unit + "bad argument: bad size or leading dimension");
+      if (const char* why = unit_context_refusal(ctxs, u)) return refuse(why);
+      const std::string why = fits(u);
+      if (!why.empty()) return refuse(unit + why);
+    }
+    return 0;
+  }
+  // The group with what both kinds fill the same way: n training points padded to nrows, the padded basis size npc =
+  // the leading dimension of the work matrices, the caller's arrays, each context's chain block, info words and records.
+  ChainGroupT group(int nrows, int npc) const {
+    const Units U = Units::all(ctxs, n_units);
+    ChainGroupT g{};
+    g.n_units = n_units; g.n = (int)N; g.nrows = nrows; g.npc = npc; g.ld = npc;
+    g.r = U.from(r); g.kv0 = U.from(kv0); g.ldv = U.from(ldv);
+    g.m = U.from(m); g.f = U.from(f); g.V = U.from(V); g.lam_m = U.from(lam_m); g.lam_var = U.from(lam_var);
+    g.logA0 = U.from(logA0);
+    g.lambda0 = U.table<double>([&](int u) { return lambda0_mode ? lambda0_fixed[u] : 0.0; });
+    g.blk = U.of(&gpfit_ctx::chain); g.info = U.of(&gpfit_ctx::info); g.rec_host = U.of(&gpfit_ctx::chain_host);
+    return g;
+  }
+  // THE chain loop.  Of a step the kind supplies: before_factor(step), from the first kernel of the step (the only
+  // reader of m and f in it, ahead of all of the step's writers) up to and including the factorisation; after_info(),
+  // the inputs of the commits (mo and Vw); moments(), the moments of lambda behind the update.
+  template <typename Before, typename After, typename Moments>
+  int run(const ChainGroupT& g, Before&& before_factor, After&& after_info, Moments&& moments) const {
+    DeviceGuard device_guard(ctxs[0]->device);
+    hipStream_t s = (hipStream_t)stream;
+    GP_TRY(launch_chain_init_group(g, n_steps, s));
+    for (int step = 0; step < n_steps; ++step) {
+      GP_TRY(before_factor(step));
+      GP_TRY(launch_chain_info_group(g, step, s));
+      // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
+      GP_TRY(after_info());
+      GP_TRY(launch_chain_copy_group(g, s));
+      GP_TRY(launch_unpack_sym_chain_group(g, s));
+      GP_TRY(moments());
+      GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
+    }
+    GP_TRY(launch_chain_collect_group(g, n_steps, s));
+    GP_HIP(hipStreamSynchronize(s));
+    for (int u = 0; u < n_units; ++u)
+      for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[(size_t)u * n_steps * CHAIN_REC + i] = ctxs[u]->chain_host[i];
+    return 0;
+  }
+};
 
 extern "C" {
 
@@ -343,8 +417,9 @@ int gpfit_estep(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_
   // M = I + S K S (lower), SK = S K (dense), Kl = K (lower)
   GP_TRY(launch_estep_build(K, ldk, n, np, sv, c->Kbuf, c->Zbuf, c->Wbuf, ld, s));
   const Lane lane = main_lane(c, s);
-  GP_TRY(full_update_factor(&c, 1, np, lane));
-  GP_TRY(full_update_products(&c, 1, np, lane));
+  const Units one = Units::all(&c, 1);
+  GP_TRY(full_update_factor(one, np, lane));
+  GP_TRY(full_update_products(one, np, lane));
   // m_new = V (A^2 f o m + A (r - f))                                utils.py:1431
   GP_TRY(launch_symv_lower(c->Wbuf, ld, n, rhs, c->tvec, s));
   GP_HIP(hipMemcpyAsync(m_new, c->tvec, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -453,117 +528,120 @@ int gpfit_fparam_lbfgs(gpfit_ctx* c, void* stream, const double* lam_m, const do
   return 0;
 }
 
-static_assert(GPFIT_ESTEP_CHAIN_MAX_STEPS == CHAIN_MAX_STEPS, "the header states the cap of the chain block");
-static_assert(GPFIT_ESTEP_CHAIN_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
-
-// ONE body for gpfit_estep_chain (the group of one) and gpfit_estep_chain_batch: n_steps x (the update of
-// gpfit_estep_projected, product for product on the same work vectors and matrices, its moments, the rate-parameter
-// optimiser) for every unit on its own context, all on the caller's stream with one synchronisation at the end.  The
-// factorisations of all units are one lock-step recursion, every product goes through product on the list of units,
-// every small kernel is its unit-batched form: a unit runs the same products in the same order with the same reduction
-// order whatever else is in the group, so its outputs have the same bits alone and in any group.
-static int estep_chain_group_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a,
-                                  const int64_t* lda, const double* const* aL, const int64_t* ldal, const double* const* L,
-                                  const int64_t* ldl, int64_t N, const int64_t* nb, const double* const* r,
-                                  const double* const* kv0, double* const* m, double* const* f, double* const* V,
-                                  const int64_t* ldv, double* const* lam_m, double* const* lam_var, const double* logA0,
-                                  int lambda0_mode, const double* lambda0_fixed, int n_steps, int max_iter, int history_size,
-                                  double lr, double tol_grad, double tol_change, double* rec_host) {
-  auto refuse = [&](const std::string& why) {
-    set_error(std::string(name) + ": " + why);
-    return -3;
-  };
-  if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
-  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS)
-    return refuse("n_steps " + std::to_string(n_steps) + " is not within 1 .. " + std::to_string(CHAIN_MAX_STEPS));
-  if (!ctxs || !a || !lda || !aL || !ldal || !L || !ldl || !nb || !r || !kv0 || !m || !f || !V || !ldv || !lam_m || !lam_var ||
-      !logA0 || (lambda0_mode && !lambda0_fixed) || !rec_host || N <= 0 || N > INT32_MAX)
-    return refuse("bad argument");
-  Lbfgs1dConfig cfg;
-  GP_TRY(fparam_lbfgs_config(name, max_iter, history_size, lr, tol_grad, tol_change, &cfg));
-  const int nrows = (int)round_up(N, TILE);
-  for (int u = 0; u < n_units; ++u) {
-    const std::string unit = n_units > 1 ? "unit " + std::to_string(u) + ": " : std::string();
-    if (!ctxs[u] || !a[u] || !aL[u] || !L[u] || !r[u] || !kv0[u] || !m[u] || !f[u] || !V[u] || !lam_m[u] || !lam_var[u])
-      return refuse(unit + "bad argument: null context or operand");
-    if (nb[u] <= 0 || lda[u] < nb[u] || ldal[u] < nb[u] || ldl[u] < nb[u] || ldv[u] < nb[u])
-      return refuse(unit + "bad argument: bad size or leading dimension");
-    if (ctxs[u]->device != ctxs[0]->device) return refuse("the contexts of one call must live on one device");
-    for (int v = 0; v < u; ++v)
-      if (ctxs[v] == ctxs[u]) return refuse("every unit needs a context of its own");
-    if (ctxs[u]->pend.active)
-      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
-    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
-    if (round_up(nb[u], TILE) != round_up(nb[0], TILE))
-      return refuse(unit + "round_up(nb, 128) = " + std::to_string(round_up(nb[u], TILE)) + " differs from unit 0's " +
-                    std::to_string(round_up(nb[0], TILE)) + " (group the units by padded size)");
-    if (nrows > ctxs[u]->np_cap || round_up(nb[u], TILE) > ctxs[u]->np_cap)
-      return refuse(unit + "problem larger than the context capacity");
-  }
-  DeviceGuard device_guard(ctxs[0]->device);
-  hipStream_t s = (hipStream_t)stream;
-  const int nu = n_units, npc = (int)round_up(nb[0], TILE);
+// ONE body for gpfit_estep_chain (the group of one) and gpfit_estep_chain_batch: every step runs the update of
+// gpfit_estep_projected, product for product on the same work vectors and matrices, and its moments, inside the
+// skeleton of ChainCall.  The factorisations of all units are one lock-step recursion, every product goes through
+// product on the list of units, every small kernel is its unit-batched form: a unit runs the same products in the same
+// order with the same reduction order whatever else is in the group, so its outputs have the same bits alone and in any
+// group.
+static int estep_chain_group_impl(ChainCall call, const double* const* a, const int64_t* lda, const double* const* aL,
+                                  const int64_t* ldal, const double* const* L, const int64_t* ldl, const int64_t* nb) {
+  gpfit_ctx* const* ctxs = call.ctxs;
+  const int nrows = (int)round_up(call.N, TILE);
+  GP_TRY(call.admit(
+      a && lda && aL && ldal && L && ldl && nb, [&](int u) { return a[u] && aL[u] && L[u]; },
+      [&](int u) { return nb[u] > 0 && lda[u] >= nb[u] && ldal[u] >= nb[u] && ldl[u] >= nb[u] && call.ldv[u] >= nb[u]; },
+      [&](int u) -> std::string {
+        // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+        if (round_up(nb[u], TILE) != round_up(nb[0], TILE))
+          return "round_up(nb, 128) = " + std::to_string(round_up(nb[u], TILE)) + " differs from unit 0's " +
+                 std::to_string(round_up(nb[0], TILE)) + " (group the units by padded size)";
+        if (nrows > ctxs[u]->np_cap || round_up(nb[u], TILE) > ctxs[u]->np_cap) return "problem larger than the context capacity";
+        return std::string();
+      }));
+  hipStream_t s = (hipStream_t)call.stream;
+  const Units U = Units::all(ctxs, call.n_units);
+  const int nu = U.cnt, npc = (int)round_up(nb[0], TILE);
   const int64_t ld = npc;
-  ChainGroupT g{};
-  g.n_units = nu; g.n = (int)N; g.nrows = nrows; g.npc = npc; g.ld = ld;
-  CholBatchT<double> cb;
+  ChainGroupT g = call.group(nrows, npc);
+  g.nb = U.table<int>([&](int u) { return (int)nb[u]; });
   for (int u = 0; u < nu; ++u) {
-    gpfit_ctx* c = ctxs[u];
-    c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
-    g.nb.v[u] = (int)nb[u]; g.kmax = std::max(g.kmax, (int)nb[u]);
-    g.a.v[u] = a[u]; g.aL.v[u] = aL[u]; g.L.v[u] = L[u]; g.r.v[u] = r[u]; g.kv0.v[u] = kv0[u];
-    g.lda.v[u] = lda[u]; g.ldal.v[u] = ldal[u]; g.ldl.v[u] = ldl[u]; g.ldv.v[u] = ldv[u];
-    g.m.v[u] = m[u]; g.f.v[u] = f[u]; g.V.v[u] = V[u]; g.lam_m.v[u] = lam_m[u]; g.lam_var.v[u] = lam_var[u];
-    g.logA0.v[u] = logA0[u]; g.lambda0.v[u] = lambda0_mode ? lambda0_fixed[u] : 0.0;
-    g.blk.v[u] = c->chain; g.info.v[u] = c->info; g.rec_host.v[u] = c->chain_host;
-    // the work vectors and matrices of gpfit_estep_projected
-    g.sv.v[u] = c->yv; g.u.v[u] = c->bv; g.t2.v[u] = c->tvec; g.z1.v[u] = c->mpad; g.z.v[u] = c->rpad; g.mo.v[u] = c->hvec;
-    g.Y.v[u] = c->Tbuf; g.Lp.v[u] = c->Wbuf; g.Vw.v[u] = c->Zbuf; g.part.v[u] = c->TmpV; g.aLp.v[u] = c->LiVbuf;
-    g.Zm.v[u] = c->Cos; g.W.v[u] = c->Kbuf; g.Li.v[u] = c->Libuf; g.trmv_part.v[u] = c->trmv_part;
-    const int b = cb.nb++;
-    cb.A[b] = c->Kbuf; cb.L[b] = c->Lbuf; cb.Li[b] = c->Libuf; cb.Tmp[b] = c->Tmp; cb.info[b] = c->info + INFO_K;
+    g.kmax = std::max(g.kmax, g.nb[u]);
+    ctxs[u]->lv_valid = false; ctxs[u]->lv32_valid = false;   // the V work matrices are reused
   }
+  g.a = U.from(a); g.aL = U.from(aL); g.L = U.from(L); g.lda = U.from(lda); g.ldal = U.from(ldal); g.ldl = U.from(ldl);
+  // the work vectors and matrices of gpfit_estep_projected
+  g.sv = U.of(&gpfit_ctx::yv); g.u = U.of(&gpfit_ctx::bv); g.t2 = U.of(&gpfit_ctx::tvec); g.z1 = U.of(&gpfit_ctx::mpad);
+  g.z = U.of(&gpfit_ctx::rpad); g.mo = U.of(&gpfit_ctx::hvec); g.Y = U.of(&gpfit_ctx::Tbuf); g.Lp = U.of(&gpfit_ctx::Wbuf);
+  g.Vw = U.of(&gpfit_ctx::Zbuf); g.part = U.of(&gpfit_ctx::TmpV); g.aLp = U.of(&gpfit_ctx::LiVbuf); g.Zm = U.of(&gpfit_ctx::Cos);
+  g.W = U.of(&gpfit_ctx::Kbuf); g.Li = U.of(&gpfit_ctx::Libuf); g.trmv_part = U.of(&gpfit_ctx::trmv_part);
+  CholBatchT<double> cb;
+  for (int u = 0; u < nu; ++u) add_k_chain(cb, ctxs[u]);
   cb.ld = ld;
-  const uint32_t all = (1u << nu) - 1u;
   const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
-  auto all_of = [&](double* gpfit_ctx::*X) { return mats(nu, ld, [&](int i) { return ctxs[i]->*X; }); };
-  const Mat<double> Y = all_of(&gpfit_ctx::Tbuf), W = all_of(&gpfit_ctx::Kbuf), Lp = all_of(&gpfit_ctx::Wbuf),
-                    Li = all_of(&gpfit_ctx::Libuf), P = all_of(&gpfit_ctx::Abuf), Vw = all_of(&gpfit_ctx::Zbuf),
-                    aLp = all_of(&gpfit_ctx::LiVbuf), Zm = all_of(&gpfit_ctx::Cos);
-  GP_TRY(launch_chain_init_group(g, n_steps, s));
-  // L does not change over the chain: packed once
-  GP_TRY(launch_pack_lower_group(nu, g.L, g.ldl, g.nb, g.Lp, ld, npc, s));
-  for (int step = 0; step < n_steps; ++step) {
-    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
-    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
-    GP_TRY(launch_estep_proj_rows_chain_group(g, step, s));
-    GP_TRY(launch_estep_proj_scale_group(g, s));
-    GP_TRY(launch_reduce_slices_group(nu, g.part, npc, nrows / 32, g.t2, npc, s));   // t2 = (a L)^T u
-    // W = I + Y^T Y  (= I + L^T G L, G = A^2 a^T diag(f) a), lower tiles, identity on the padding
-    GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(Y), plain(Y), into_lower(W)));
-    GP_TRY(launch_add_diag_group(nu, g.W, ld, npc, 1.0, s));
-    GP_TRY(potrf_lockstep(cb, 0, npc, all, lane));
-    GP_TRY(launch_chain_info_group(g, step, s));
-    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
-    // m_new = L W^-1 (a L)^T u
-    GP_TRY(launch_trmv_lower_group(nu, g.Li, ld, npc, g.t2, g.z1, s));
-    GP_TRY(launch_trmv_lower_t_group(nu, g.Li, ld, npc, g.z1, g.z, g.trmv_part, s));
-    GP_TRY(launch_trmv_lower_group(nu, g.Lp, ld, npc, g.z, g.mo, s));
-    // V_new = P P^T, P = L L_W^-T
-    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(Lp)), trans(tril(Li)), into(P)));
-    GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(P), trans(P), into_lower(Vw)));
-    GP_TRY(launch_chain_copy_group(g, s));
-    GP_TRY(launch_unpack_sym_chain_group(g, s));
-    // the moments of lambda behind the update, from Z = aL L_W^-T
-    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(aLp), trans(tril(Li)), into(Zm)));
-    GP_TRY(launch_estep_proj_moments_chain_group(g, s));
-    GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
-  }
-  GP_TRY(launch_chain_collect_group(g, n_steps, s));
-  GP_HIP(hipStreamSynchronize(s));
-  for (int u = 0; u < nu; ++u)
-    for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[(size_t)u * n_steps * CHAIN_REC + i] = ctxs[u]->chain_host[i];
-  return 0;
+  const Mat<double> Y = U.mats(&gpfit_ctx::Tbuf, ld), W = U.mats(&gpfit_ctx::Kbuf, ld), Lp = U.mats(&gpfit_ctx::Wbuf, ld),
+                    Li = U.mats(&gpfit_ctx::Libuf, ld), P = U.mats(&gpfit_ctx::Abuf, ld), Vw = U.mats(&gpfit_ctx::Zbuf, ld),
+                    aLp = U.mats(&gpfit_ctx::LiVbuf, ld), Zm = U.mats(&gpfit_ctx::Cos, ld);
+  return call.run(
+      g,
+      [&](int step) -> int {
+        // L does not change over the chain: packed once
+        if (step == 0) GP_TRY(launch_pack_lower_group(nu, g.L, g.ldl, g.nb, g.Lp, ld, npc, s));
+        // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
+        // step's writers (the gated copy into m, the optimiser's rate), all on one stream
+        GP_TRY(launch_estep_proj_rows_chain_group(g, step, s));
+        GP_TRY(launch_estep_proj_scale_group(g, s));
+        GP_TRY(launch_reduce_slices_group(nu, g.part, npc, nrows / 32, g.t2, npc, s));   // t2 = (a L)^T u
+        // W = I + Y^T Y  (= I + L^T G L, G = A^2 a^T diag(f) a), lower tiles, identity on the padding
+        GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(Y), plain(Y), into_lower(W)));
+        GP_TRY(launch_add_diag_group(nu, g.W, ld, npc, 1.0, s));
+        return potrf_lockstep(cb, 0, npc, U.chains(), lane);
+      },
+      [&]() -> int {
+        // m_new = L W^-1 (a L)^T u
+        GP_TRY(launch_trmv_lower_group(nu, g.Li, ld, npc, g.t2, g.z1, s));
+        GP_TRY(launch_trmv_lower_t_group(nu, g.Li, ld, npc, g.z1, g.z, g.trmv_part, s));
+        GP_TRY(launch_trmv_lower_group(nu, g.Lp, ld, npc, g.z, g.mo, s));
+        // V_new = P P^T, P = L L_W^-T
+        GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(Lp)), trans(tril(Li)), into(P)));
+        return product(lane, {npc, npc, npc}, 1.0, plain(P), trans(P), into_lower(Vw));
+      },
+      [&]() -> int {
+        // from Z = aL L_W^-T
+        GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(aLp), trans(tril(Li)), into(Zm)));
+        return launch_estep_proj_moments_chain_group(g, s);
+      });
+}
+
+// ONE body for gpfit_estep_chain_full (the group of one) and gpfit_estep_chain_full_batch.  The full-rank chain: the
+// update of gpfit_estep (full_update_factor / full_update_products) in place of the projected one, on the bookkeeping of
+// the projected chain -- a ChainGroupT with nb = n, so that the init, the info word, the gated commits of m and V, the
+// optimiser and the collect are the launches of ChainCall::run.  One lock-step recursion, every product on the list of
+// units, every small kernel in its unit-batched form: the same bits alone and in any group.
+static int estep_chain_full_group_impl(ChainCall call, const double* const* K, const int64_t* ldk) {
+  gpfit_ctx* const* ctxs = call.ctxs;
+  const int64_t N = call.N;
+  const int n = (int)N, np = (int)round_up(N, TILE);
+  GP_TRY(call.admit(
+      K && ldk, [&](int u) { return K[u] != nullptr; }, [&](int u) { return ldk[u] >= N && call.ldv[u] >= N; },
+      [&](int u) { return np > ctxs[u]->np_cap ? std::string("problem larger than the context capacity") : std::string(); }));
+  hipStream_t s = (hipStream_t)call.stream;
+  const Units U = Units::all(ctxs, call.n_units);
+  const int nu = U.cnt;
+  const int64_t ld = np;
+  ChainGroupT g = call.group(np, np);
+  g.kmax = n;
+  g.nb = U.same(n);
+  g.K = U.from(K); g.ldk = U.from(ldk);
+  // the work vectors and matrices of gpfit_estep
+  g.sv = U.of(&gpfit_ctx::yv); g.u = U.of(&gpfit_ctx::bv); g.mo = U.of(&gpfit_ctx::tvec);
+  g.W = U.of(&gpfit_ctx::Kbuf); g.SK = U.of(&gpfit_ctx::Zbuf); g.Vw = U.of(&gpfit_ctx::Wbuf);
+  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
+  return call.run(
+      g,
+      [&](int step) -> int {
+        // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
+        // step's writers (the gated copy into m, the optimiser's rate), all on one stream
+        GP_TRY(launch_estep_prep_chain_group(g, step, s));
+        // M = I + S K S (lower), SK = S K (dense), Kl = K (lower): Kl is overwritten by V, so it is rebuilt every step
+        GP_TRY(launch_estep_build_group(g, s));
+        return full_update_factor(U, np, lane);
+      },
+      [&]() -> int {
+        GP_TRY(full_update_products(U, np, lane));
+        return launch_symv_lower_group(nu, g.Vw, ld, n, g.u, g.mo, s);
+      },
+      [&]() -> int { return launch_estep_full_moments_chain_group(g, s); });
 }
 
 int gpfit_estep_chain(gpfit_ctx* c, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
@@ -572,9 +650,9 @@ int gpfit_estep_chain(gpfit_ctx* c, void* stream, const double* a, int64_t lda, 
                       int lambda0_mode, double lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                       double tol_grad, double tol_change, double* rec_host) {
   // the group of one (estep_chain_group_impl): a unit's numbers are the same alone and in any group
-  return estep_chain_group_impl("gpfit_estep_chain", &c, 1, stream, &a, &lda, &aL, &ldal, &L, &ldl, N, &nb, &r, &kv0, &m, &f,
-                                &V_out, &ldv, &lam_m, &lam_var, &logA0, lambda0_mode, &lambda0_fixed, n_steps, max_iter,
-                                history_size, lr, tol_grad, tol_change, rec_host);
+  return estep_chain_group_impl({"gpfit_estep_chain", &c, 1, stream, N, &r, &kv0, &m, &f, &V_out, &ldv, &lam_m, &lam_var, &logA0,
+                                 lambda0_mode, &lambda0_fixed, n_steps, max_iter, history_size, lr, tol_grad, tol_change, rec_host},
+                                &a, &lda, &aL, &ldal, &L, &ldl, &nb);
 }
 
 int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a, const int64_t* lda,
@@ -584,90 +662,9 @@ int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, c
                             double* const* lam_m, double* const* lam_var, const double* logA0, int lambda0_mode,
                             const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                             double tol_grad, double tol_change, double* rec_host) {
-  return estep_chain_group_impl("gpfit_estep_chain_batch", ctxs, n_units, stream, a, lda, aL, ldal, L, ldl, N, nb, r, kv0, m, f,
-                                V, ldv, lam_m, lam_var, logA0, lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr,
-                                tol_grad, tol_change, rec_host);
-}
-
-static_assert(GPFIT_ESTEP_CHAIN_FULL_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
-
-// ONE body for gpfit_estep_chain_full (the group of one) and gpfit_estep_chain_full_batch.  The full-rank chain: the
-// update of gpfit_estep (full_update_factor / full_update_products) in place of the projected one, on the bookkeeping of
-// the projected chain -- a ChainGroupT with nb = n, so that the init, the info word, the gated commits of m and V, the
-// optimiser and the collect are the launches of estep_chain_group_impl.  Every unit on its own context, all on the
-// caller's stream with one synchronisation at the end; one lock-step recursion, every product on the list of units,
-// every small kernel in its unit-batched form: the same bits alone and in any group.
-static int estep_chain_full_group_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* stream,
-                                       const double* const* K, const int64_t* ldk, int64_t N, const double* const* r,
-                                       const double* const* kv0, double* const* m, double* const* f, double* const* V,
-                                       const int64_t* ldv, double* const* lam_m, double* const* lam_var, const double* logA0,
-                                       int lambda0_mode, const double* lambda0_fixed, int n_steps, int max_iter,
-                                       int history_size, double lr, double tol_grad, double tol_change, double* rec_host) {
-  auto refuse = [&](const std::string& why) {
-    set_error(std::string(name) + ": " + why);
-    return -3;
-  };
-  if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
-  if (n_steps < 1 || n_steps > CHAIN_MAX_STEPS)
-    return refuse("n_steps " + std::to_string(n_steps) + " is not within 1 .. " + std::to_string(CHAIN_MAX_STEPS));
-  if (!ctxs || !K || !ldk || !r || !kv0 || !m || !f || !V || !ldv || !lam_m || !lam_var || !logA0 ||
-      (lambda0_mode && !lambda0_fixed) || !rec_host || N <= 0 || N > INT32_MAX)
-    return refuse("bad argument");
-  Lbfgs1dConfig cfg;
-  GP_TRY(fparam_lbfgs_config(name, max_iter, history_size, lr, tol_grad, tol_change, &cfg));
-  const int n = (int)N, np = (int)round_up(N, TILE);
-  for (int u = 0; u < n_units; ++u) {
-    const std::string unit = n_units > 1 ? "unit " + std::to_string(u) + ": " : std::string();
-    if (!ctxs[u] || !K[u] || !r[u] || !kv0[u] || !m[u] || !f[u] || !V[u] || !lam_m[u] || !lam_var[u])
-      return refuse(unit + "bad argument: null context or operand");
-    if (ldk[u] < N || ldv[u] < N) return refuse(unit + "bad argument: bad size or leading dimension");
-    if (ctxs[u]->device != ctxs[0]->device) return refuse("the contexts of one call must live on one device");
-    for (int v = 0; v < u; ++v)
-      if (ctxs[v] == ctxs[u]) return refuse("every unit needs a context of its own");
-    if (ctxs[u]->pend.active)
-      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
-    if (np > ctxs[u]->np_cap) return refuse(unit + "problem larger than the context capacity");
-  }
-  DeviceGuard device_guard(ctxs[0]->device);
-  hipStream_t s = (hipStream_t)stream;
-  const int nu = n_units;
-  const int64_t ld = np;
-  ChainGroupT g{};
-  g.n_units = nu; g.n = n; g.nrows = np; g.npc = np; g.ld = ld; g.kmax = n;
-  for (int u = 0; u < nu; ++u) {
-    gpfit_ctx* c = ctxs[u];
-    g.nb.v[u] = n;
-    g.K.v[u] = K[u]; g.ldk.v[u] = ldk[u]; g.r.v[u] = r[u]; g.kv0.v[u] = kv0[u]; g.ldv.v[u] = ldv[u];
-    g.m.v[u] = m[u]; g.f.v[u] = f[u]; g.V.v[u] = V[u]; g.lam_m.v[u] = lam_m[u]; g.lam_var.v[u] = lam_var[u];
-    g.logA0.v[u] = logA0[u]; g.lambda0.v[u] = lambda0_mode ? lambda0_fixed[u] : 0.0;
-    g.blk.v[u] = c->chain; g.info.v[u] = c->info; g.rec_host.v[u] = c->chain_host;
-    // the work vectors and matrices of gpfit_estep
-    g.sv.v[u] = c->yv; g.u.v[u] = c->bv; g.mo.v[u] = c->tvec;
-    g.W.v[u] = c->Kbuf; g.SK.v[u] = c->Zbuf; g.Vw.v[u] = c->Wbuf;
-  }
-  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
-  GP_TRY(launch_chain_init_group(g, n_steps, s));
-  for (int step = 0; step < n_steps; ++step) {
-    // m and f are updated in place: this kernel is the only reader of both in a step and runs before any of the
-    // step's writers (the gated copy into m, the optimiser's rate), all on one stream
-    GP_TRY(launch_estep_prep_chain_group(g, step, s));
-    // M = I + S K S (lower), SK = S K (dense), Kl = K (lower): Kl is overwritten by V, so it is rebuilt every step
-    GP_TRY(launch_estep_build_group(g, s));
-    GP_TRY(full_update_factor(ctxs, nu, np, lane));
-    GP_TRY(launch_chain_info_group(g, step, s));
-    // from here on a failed or skipped step only writes workspace: every write to the caller's arrays is gated
-    GP_TRY(full_update_products(ctxs, nu, np, lane));
-    GP_TRY(launch_symv_lower_group(nu, g.Vw, ld, n, g.u, g.mo, s));
-    GP_TRY(launch_chain_copy_group(g, s));
-    GP_TRY(launch_unpack_sym_chain_group(g, s));
-    GP_TRY(launch_estep_full_moments_chain_group(g, s));
-    GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
-  }
-  GP_TRY(launch_chain_collect_group(g, n_steps, s));
-  GP_HIP(hipStreamSynchronize(s));
-  for (int u = 0; u < nu; ++u)
-    for (int i = 0; i < n_steps * CHAIN_REC; ++i) rec_host[(size_t)u * n_steps * CHAIN_REC + i] = ctxs[u]->chain_host[i];
-  return 0;
+  return estep_chain_group_impl({"gpfit_estep_chain_batch", ctxs, n_units, stream, N, r, kv0, m, f, V, ldv, lam_m, lam_var, logA0,
+                                 lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr, tol_grad, tol_change, rec_host},
+                                a, lda, aL, ldal, L, ldl, nb);
 }
 
 int gpfit_estep_chain_full(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_t N, const double* r,
@@ -676,9 +673,10 @@ int gpfit_estep_chain_full(gpfit_ctx* c, void* stream, const double* K, int64_t 
                            int max_iter, int history_size, double lr, double tol_grad, double tol_change,
                            double* rec_host) {
   // the group of one (estep_chain_full_group_impl): a unit's numbers are the same alone and in any group
-  return estep_chain_full_group_impl("gpfit_estep_chain_full", &c, 1, stream, &K, &ldk, N, &r, &kv0, &m, &f, &V_out, &ldv,
-                                     &lam_m, &lam_var, &logA0, lambda0_mode, &lambda0_fixed, n_steps, max_iter, history_size,
-                                     lr, tol_grad, tol_change, rec_host);
+  return estep_chain_full_group_impl({"gpfit_estep_chain_full", &c, 1, stream, N, &r, &kv0, &m, &f, &V_out, &ldv, &lam_m, &lam_var,
+                                      &logA0, lambda0_mode, &lambda0_fixed, n_steps, max_iter, history_size, lr, tol_grad, tol_change,
+                                      rec_host},
+                                     &K, &ldk);
 }
 
 int gpfit_estep_chain_full_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* K,
@@ -687,9 +685,10 @@ int gpfit_estep_chain_full_batch(gpfit_ctx* const* ctxs, int n_units, void* stre
                                  double* const* lam_m, double* const* lam_var, const double* logA0, int lambda0_mode,
                                  const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                                  double tol_grad, double tol_change, double* rec_host) {
-  return estep_chain_full_group_impl("gpfit_estep_chain_full_batch", ctxs, n_units, stream, K, ldk, N, r, kv0, m, f, V, ldv,
-                                     lam_m, lam_var, logA0, lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr,
-                                     tol_grad, tol_change, rec_host);
+  return estep_chain_full_group_impl({"gpfit_estep_chain_full_batch", ctxs, n_units, stream, N, r, kv0, m, f, V, ldv, lam_m, lam_var,
+                                      logA0, lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr, tol_grad, tol_change,
+                                      rec_host},
+                                     K, ldk);
 }
 
 int gpfit_fparam_lbfgs_host(const double* lam_m, const double* lam_var, const double* r, int64_t N, double logA0,

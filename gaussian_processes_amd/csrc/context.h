@@ -119,12 +119,13 @@ struct DeviceGuard {
 };
 // First statements of a context entry point (after its argument check): refuse to touch the
 // workspace of an evaluation that is still in flight, then pin the device.
-#define GP_CTX_ENTER(c, name)                                                                        \
-  if ((c)->pend.active) {                                                                            \
-    gpfit::set_error(name ": an asynchronous evaluation is pending on this context (collect it with " \
-                          "gpfit_fit_eval_finish first)");                                           \
-    return -3;                                                                                       \
-  }                                                                                                  \
+#define GP_PENDING_REFUSAL \
+  "an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)"
+#define GP_CTX_ENTER(c, name)                         \
+  if ((c)->pend.active) {                             \
+    gpfit::set_error(name ": " GP_PENDING_REFUSAL);   \
+    return -3;                                        \
+  }                                                   \
   gpfit::DeviceGuard _device_guard((c)->device)
 
 // profiling scope: when a context with profile=1 is evaluating, launches are bracketed by events

@@ -8,7 +8,7 @@
 // the vectors behind the factor, the mixed-precision hand-over, the pull-back to the metric, the
 // n_kept x n_kept algebra of the truncated-rank closures, the host assembly of the 16 outputs); what
 // differs between the entry points is which stages they call and what they launch in between.
-#include "product.h"
+#include "units.h"
 #include "gemm_core.h"
 #include "gpfit_mi355x.h"
 
@@ -770,12 +770,7 @@ static int pullback_to_metric(gpfit_ctx* c, Lane lane, const double* W, const do
 // ---- the n_kept x n_kept algebra of the truncated-rank closures (nb = n_kept padded; leading dimension nb), in the
 // scratch matrices S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV of each unit's context -- for a list of cnt units (the
 // closures of a group; one unit: the single closures), every small kernel one launch for the list (kernels.h).
-template <typename T, typename F>
-static PerUnit<T> per_unit(int cnt, F&& at) {
-  PerUnit<T> t{};
-  for (int i = 0; i < cnt && i < CHAIN_MAXU; ++i) t.v[i] = at(i);
-  return t;
-}
+// What is kept per unit beside the contexts (V_b, ldvb, nk, vc, m_b, d) is indexed like the caller's tables (units.h).
 // the work matrices of a unit's V_b chain (the caller's: which of the context's are idle differs between the closures).
 // The recursion writes a chain's L, L^-1 and Tmp on and below the diagonal only and reads them as triangles (k ranges
 // that end with the diagonal tile, which the leaf writes whole) or as blocks below the diagonal: what the tiles above
@@ -786,48 +781,39 @@ struct ProjChain { double *Va, *Vl, *Vli, *Vt; };
 // K~_b (packed into S1) = L L^T with L^-1 (utils.py:2067) and V_b (packed into Va) = L_V L_V^T (log|V_b|, :1326): the
 // 2 cnt chains in lock step, the inverse for the K~_b chains only; then K~_b^-1 = L^-T L^-1 in S1 and V_b in S2, both
 // stored in full with the identity on the padding.  nk[i]: the unit's own n_kept; nb is shared (the recursion's split).
-static int projected_factor(Lane lane, int cnt, gpfit_ctx* const* cs, const double* const* V_b, const int64_t* ldvb, const int* nk,
-                            int nb, const ProjChain* vc) {
-  if (cnt <= 0 || cnt > CHAIN_MAXU) return cnt == 0 ? 0 : -3;
+static int projected_factor(Lane lane, const Units& U, const double* const* V_b, const int64_t* ldvb, const int* nk, int nb,
+                            const ProjChain* vc) {
+  if (U.cnt == 0) return 0;
+  const int cnt = U.cnt;
   const int64_t lb = nb;
   const hipStream_t s = lane.s;
-  auto of = [&](double* gpfit_ctx::*X) { return per_unit<double*>(cnt, [&](int i) { return cs[i]->*X; }); };
-  auto all = [&](double* gpfit_ctx::*X) { return mats(cnt, lb, [&](int i) { return cs[i]->*X; }); };
   CholBatchT<double> cb;
   uint32_t kchains = 0;
   for (int i = 0; i < cnt; ++i) {
-    gpfit_ctx* c = cs[i];
-    int b = cb.nb++;
-    cb.A[b] = c->Vbuf; cb.L[b] = c->LVbuf; cb.Li[b] = c->LiVbuf; cb.Tmp[b] = c->TmpV; cb.info[b] = c->info + INFO_K;
-    kchains |= 1u << b;
-    b = cb.nb++;
-    cb.A[b] = vc[i].Va; cb.L[b] = vc[i].Vl; cb.Li[b] = vc[i].Vli; cb.Tmp[b] = vc[i].Vt; cb.info[b] = c->info + INFO_V;
+    const ProjChain& v = vc[U.at[i]];
+    kchains |= 1u << add_v_chain(cb, U.ctx[i], INFO_K);   // K~_b's chain, in S1..S4
+    add_chain(cb, v.Va, v.Vl, v.Vli, v.Vt, U.ctx[i]->info + INFO_V);
   }
   cb.ld = lb; cb.ctx = nullptr; cb.side_min = 0;
   GP_TRY(potrf_lockstep<double>(cb, 0, nb, kchains, lane));
-  const PerUnit<int> nks = per_unit<int>(cnt, [&](int i) { return nk[i]; });
-  GP_TRY(launch_logdet_pair_group(cnt, per_unit<const double*>(cnt, [&](int i) { return vc[i].Vl; }),
-                                  per_unit<double*>(cnt, [&](int i) { return cs[i]->scal + S_LOGDET_V; }),
-                                  per_unit<const double*>(cnt, [&](int i) { return cs[i]->LVbuf; }),
-                                  per_unit<double*>(cnt, [&](int i) { return cs[i]->scal + S_LOGDET_K; }), lb, nks, s));
-  GP_TRY(product(lane, {nb, nb, nb}, 1.0, trans(tril(all(&gpfit_ctx::LiVbuf))), plain(tril(all(&gpfit_ctx::LiVbuf))),
-                 into_lower(all(&gpfit_ctx::Vbuf))));   // L^-T L^-1
-  GP_TRY(launch_symmetrize_group(cnt, of(&gpfit_ctx::Vbuf), lb, nb, s));
-  GP_TRY(launch_pack_lower_group(cnt, per_unit<const double*>(cnt, [&](int i) { return V_b[i]; }),
-                                 per_unit<int64_t>(cnt, [&](int i) { return ldvb[i]; }), nks, of(&gpfit_ctx::LVbuf), lb, nb, s));
-  return launch_symmetrize_group(cnt, of(&gpfit_ctx::LVbuf), lb, nb, s);
+  const PerUnit<int> nks = U.from(nk);
+  GP_TRY(launch_logdet_pair_group(cnt, U.table<const double*>([&](int u) { return vc[u].Vl; }), U.scal(S_LOGDET_V),
+                                  U.cof(&gpfit_ctx::LVbuf), U.scal(S_LOGDET_K), lb, nks, s));
+  GP_TRY(product(lane, {nb, nb, nb}, 1.0, trans(tril(U.mats(&gpfit_ctx::LiVbuf, lb))), plain(tril(U.mats(&gpfit_ctx::LiVbuf, lb))),
+                 into_lower(U.mats(&gpfit_ctx::Vbuf, lb))));   // L^-T L^-1
+  GP_TRY(launch_symmetrize_group(cnt, U.of(&gpfit_ctx::Vbuf), lb, nb, s));
+  GP_TRY(launch_pack_lower_group(cnt, U.from(V_b), U.from(ldvb), nks, U.of(&gpfit_ctx::LVbuf), lb, nb, s));
+  return launch_symmetrize_group(cnt, U.of(&gpfit_ctx::LVbuf), lb, nb, s);
 }
 // K~_b^-1 V_b in S3, its trace tr(K~_b^-1 V_b) in scal[S_TRACE], P1 = K~_b^-1 V_b K~_b^-1 in S4.  (The two closures form
 // a V_b on different sides of this stage, and b = K~_b^-1 m_b behind it.)
-static int projected_kl_products(Lane lane, int cnt, gpfit_ctx* const* cs, const int* nk, int nb) {
-  if (cnt <= 0 || cnt > CHAIN_MAXU) return cnt == 0 ? 0 : -3;
+static int projected_kl_products(Lane lane, const Units& U, const int* nk, int nb) {
+  if (U.cnt == 0) return 0;
   const int64_t lb = nb;
-  auto all = [&](double* gpfit_ctx::*X) { return mats(cnt, lb, [&](int i) { return cs[i]->*X; }); };
-  const Mat<double> Ki = all(&gpfit_ctx::Vbuf), S2 = all(&gpfit_ctx::LVbuf), S3 = all(&gpfit_ctx::LiVbuf), S4 = all(&gpfit_ctx::TmpV);
+  const Mat<double> Ki = U.mats(&gpfit_ctx::Vbuf, lb), S2 = U.mats(&gpfit_ctx::LVbuf, lb), S3 = U.mats(&gpfit_ctx::LiVbuf, lb),
+                    S4 = U.mats(&gpfit_ctx::TmpV, lb);
   GP_TRY(product(lane, {nb, nb, nb}, 1.0, plain(Ki), plain(S2), into(S3)));
-  GP_TRY(launch_proj_trace_group(cnt, per_unit<double*>(cnt, [&](int i) { return cs[i]->LiVbuf; }), lb,
-                                 per_unit<int>(cnt, [&](int i) { return nk[i]; }),
-                                 per_unit<double*>(cnt, [&](int i) { return cs[i]->scal + S_TRACE; }), lane.s));
+  GP_TRY(launch_proj_trace_group(U.cnt, U.of(&gpfit_ctx::LiVbuf), lb, U.from(nk), U.scal(S_TRACE), lane.s));
   return product(lane, {nb, nb, nb}, 1.0, plain(S3), plain(Ki), into(S4));
 }
 // What both closures run behind a V_b, for the units of pg (a = pg.am is B, or K_b K~_b^-1): b = K~_b^-1 m_b and m_b . b;
@@ -846,22 +832,21 @@ static int projected_adjoints(Lane lane, const ProjGroupT& pg, double* const* pa
 }
 // The housekeeping of the closures of cnt units, one launch each (kernels.h).  Begin: pixel lists, info words, m_b padded
 // to nb, bv / wl cleared.  End: the 64 scalars and the info words of every unit straight into its pinned host buffers.
-static int closure_prepare(int cnt, gpfit_ctx* const* cs, const int* d, const int* nk, const double* const* m_b, int nb, hipStream_t s) {
+static int closure_prepare(const Units& U, const int* d, const int* nk, const double* const* m_b, int nb, hipStream_t s) {
   ClosurePrepT gp{};
-  gp.n_units = cnt; gp.nb = nb;
-  for (int i = 0; i < cnt; ++i) {
-    gpfit_ctx* c = cs[i];
-    gp.pix_host.v[i] = c->pix_host; gp.pix.v[i] = c->pix; gp.info.v[i] = c->info; gp.d.v[i] = d[i]; gp.nk.v[i] = nk[i];
-    gp.cap.v[i] = c->np_cap; gp.cap_max = std::max(gp.cap_max, c->np_cap);
-    gp.m_b.v[i] = m_b[i]; gp.mpad.v[i] = c->mpad; gp.bv.v[i] = c->bv; gp.wl.v[i] = c->wl;
+  gp.n_units = U.cnt; gp.nb = nb;
+  for (int i = 0; i < U.cnt; ++i) {
+    gp.pix_host.v[i] = U.ctx[i]->pix_host; gp.cap.v[i] = U.ctx[i]->np_cap; gp.cap_max = std::max(gp.cap_max, U.ctx[i]->np_cap);
   }
+  gp.pix = U.of(&gpfit_ctx::pix); gp.info = U.of(&gpfit_ctx::info); gp.d = U.from(d); gp.nk = U.from(nk);
+  gp.m_b = U.from(m_b); gp.mpad = U.of(&gpfit_ctx::mpad); gp.bv = U.of(&gpfit_ctx::bv); gp.wl = U.of(&gpfit_ctx::wl);
   return launch_closure_prepare(gp, s);
 }
-static int closure_collect(int cnt, gpfit_ctx* const* cs, hipStream_t s) {
+static int closure_collect(const Units& U, hipStream_t s) {
   GroupCollectT gc{};
-  gc.n_units = cnt;
-  for (int i = 0; i < cnt; ++i) {
-    gpfit_ctx* c = cs[i];
+  gc.n_units = U.cnt;
+  for (int i = 0; i < U.cnt; ++i) {
+    gpfit_ctx* c = U.ctx[i];
     gc.scal[i] = c->scal; gc.info[i] = c->info; gc.scal_host[i] = c->scal_host; gc.info_host[i] = c->info_host;
   }
   return launch_group_collect(gc, s);
@@ -1219,9 +1204,8 @@ static int fit_eval_impl(gpfit_ctx* c, void* stream, const double* theta, const 
   {
     // K~ (with its inverse) and V in lock step; K~ alone when V's factor is reused
     CholBatchT<R> cb;
-    cb.nb = reuse_V ? 1 : 2;
-    cb.A[0] = RP(c->Kbuf); cb.L[0] = RP(c->Lbuf); cb.Li[0] = RP(c->Libuf); cb.Tmp[0] = RP(c->Tmp); cb.info[0] = c->info + INFO_K;
-    cb.A[1] = RP(c->Vbuf); cb.L[1] = RP(c->LVbuf); cb.Li[1] = RP(c->LiVbuf); cb.Tmp[1] = RP(c->TmpV); cb.info[1] = c->info + INFO_V;
+    add_k_chain(cb, c);
+    if (!reuse_V) add_v_chain(cb, c);
     cb.ld = ld; cb.ctx = c; cb.side_min = side_min;
     if (!reuse_V) GP_HIP(hipStreamWaitEvent(s, c->ev_join, 0));   // V is packed
     // (K~'s chain in block form: the inverses of the two diagonal halves only -- everything behind substitutes with
@@ -1274,29 +1258,14 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
                                const R* const* r, const R* const* m, const R* const* V, int64_t ldv, const double* logA,
                                const double* lambda0, int want_grad, double* out_host, int* rc_out) {
   auto RP = ws_as<R>;
+  const Refuse refuse{"gpfit_fit_eval_batch"};
   if (!cs || nu <= 0 || 2 * nu > GEMM_MAXB || !theta6 || !X || !r || !m || !V || !logA || !lambda0 || !out_host || !rc_out ||
-      N <= 0) {
-    set_error("gpfit_fit_eval_batch: bad argument (1 .. 16 units per call)");
-    return -3;
-  }
+      N <= 0)
+    return refuse("bad argument (1 .. 16 units per call)");
   for (int u = 0; u < nu; ++u) {
-    if (!cs[u] || !X[u] || !r[u] || !m[u] || !V[u]) {
-      set_error("gpfit_fit_eval_batch: null context or operand");
-      return -3;
-    }
-    if (cs[u]->device != cs[0]->device) {
-      set_error("gpfit_fit_eval_batch: the contexts of one call must live on one device");
-      return -3;
-    }
-    for (int v = 0; v < u; ++v)
-      if (cs[v] == cs[u]) {
-        set_error("gpfit_fit_eval_batch: every unit needs a context of its own");
-        return -3;
-      }
-    if (cs[u]->pend.active) {
-      set_error("gpfit_fit_eval_batch: an asynchronous evaluation is pending on one of the contexts");
-      return -3;
-    }
+    if (!cs[u] || !X[u] || !r[u] || !m[u] || !V[u]) return refuse("null context or operand");
+    if (const char* why = unit_context_refusal(cs, u, "an asynchronous evaluation is pending on one of the contexts"))
+      return refuse(why);
   }
   DeviceGuard device_guard(cs[0]->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1366,13 +1335,8 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
     CholBatchT<R> cb;
     uint32_t kchains = 0;   // the K~ chains: their inverse factors -- in block form the two diagonal halves only
     for (int i = 0; i < na; ++i) {
-      gpfit_ctx* c = un[i].c;
-      int b = cb.nb++;
-      cb.A[b] = RP(c->Kbuf); cb.L[b] = RP(c->Lbuf); cb.Li[b] = RP(c->Libuf); cb.Tmp[b] = RP(c->Tmp); cb.info[b] = c->info + INFO_K;
-      kchains |= 1u << b;
-      if (un[i].reuse_V) continue;
-      b = cb.nb++;
-      cb.A[b] = RP(c->Vbuf); cb.L[b] = RP(c->LVbuf); cb.Li[b] = RP(c->LiVbuf); cb.Tmp[b] = RP(c->TmpV); cb.info[b] = c->info + INFO_V;
+      kchains |= 1u << add_k_chain(cb, un[i].c);
+      if (!un[i].reuse_V) add_v_chain(cb, un[i].c);
     }
     cb.ld = ld; cb.ctx = nullptr; cb.side_min = 0;
     if (blocks) GP_TRY(potrf_lockstep<R>(cb, 0, np, 0u, lane, kchains));
@@ -1398,15 +1362,7 @@ static int fit_eval_batch_impl(gpfit_ctx* const* cs, int nu, void* stream, const
   }
   if (mixed_grad) GP_TRY(post_join_list<float>(lane, na, cl, pfl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, no_phase));
   else GP_TRY(post_join_list<R>(lane, na, cl, pjl, thl, n, np, dl, dpl, n_rows, n_cols, want_grad, blocks, no_phase));
-  {
-    GroupCollectT gc{};
-    gc.n_units = na;
-    for (int i = 0; i < na; ++i) {
-      gpfit_ctx* c = un[i].c;
-      gc.scal[i] = c->scal; gc.info[i] = c->info; gc.scal_host[i] = c->scal_host; gc.info_host[i] = c->info_host;
-    }
-    GP_TRY(launch_group_collect(gc, s));
-  }
+  GP_TRY(closure_collect(Units::all(cl, na), s));
   // one completion event for the group, recorded on the leader's context and waited on by every unit's finish
   if (!c0->pend.done) GP_HIP(hipEventCreateWithFlags(&c0->pend.done, hipEventDisableTiming));
   GP_HIP(hipEventRecord(c0->pend.done, s));
@@ -1473,6 +1429,98 @@ static int grad_pullback_impl(gpfit_ctx* c, void* stream, const double* theta, i
   return 0;
 }
 
+// The admission of the units of a truncated closure call (gpfit_fit_eval_projected / _sparse and their _batch forms),
+// all of it before anything is enqueued or written: every unit's arguments and context, then every unit's admit();
+// then rc_out[u] = 0 or -2 with the infinite loss / gradients in the unit's outputs.  U: the units to run (none: the
+// call is done); what was found out about them, indexed like the caller's tables.
+struct ClosureUnits {
+  Units U;
+  int nb;   // n_kept padded, shared: the recursion's split depends on it
+  int d[CHAIN_MAXU], dp[CHAIN_MAXU], nk[CHAIN_MAXU];
+  Theta th[CHAIN_MAXU];
+  double A[CHAIN_MAXU];
+};
+// nk_max / nk_max_name: the bound on n_kept and what the refusal calls it; np: the padded stimuli a context must hold;
+// operands(u): the body's own operands of unit u are there; fits(u): what the body asks of the unit's context beyond
+// the shared checks -- the sentence of a refusal, or empty.
+template <typename Operands, typename Fits>
+static int admit_closure_units(const char* name, gpfit_ctx* const* cs, int nu, const double* theta6, const double* lower6,
+                               const double* upper6, int n_rows, int n_cols, int np, const int64_t* n_kept, int64_t nk_max,
+                               const char* nk_max_name, const int64_t* ldb, const int64_t* ldvb, const double* logA,
+                               Operands&& operands, Fits&& fits, double* out_host, int* rc_out, ClosureUnits* a) {
+  const Refuse refuse{name};
+  a->nb = (int)round_up(n_kept[0], TILE);
+  for (int u = 0; u < nu; ++u) {
+    const std::string unit = unit_prefix(nu, u);
+    if (!cs[u] || !operands(u)) return refuse(unit + "null context or operand");
+    if (n_kept[u] <= 0 || n_kept[u] > nk_max)
+      return refuse(unit + "bad argument: n_kept " + std::to_string(n_kept[u]) + " is not within 1 .. " + nk_max_name + " = " +
+                    std::to_string(nk_max));
+    if (ldb[u] < n_kept[u] || ldvb[u] < n_kept[u]) return refuse(unit + "bad leading dimension");
+    if (const char* why = unit_context_refusal(cs, u)) return refuse(why);
+    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+    if (round_up(n_kept[u], TILE) != a->nb)
+      return refuse(unit + "round_up(n_kept, 128) = " + std::to_string(round_up(n_kept[u], TILE)) + " differs from unit 0's " +
+                    std::to_string(a->nb) + " (group the units by padded size)");
+    const std::string why = fits(u);
+    if (!why.empty()) return refuse(unit + why);
+  }
+  bool outside[CHAIN_MAXU];
+  for (int u = 0; u < nu; ++u) {
+    double scratch_out[OUT_COUNT];
+    Admitted ad;
+    const int rc = admit(cs[u], name, nu > 1 ? "a context's" : "the context", theta6 + 6 * u, lower6 ? lower6 + 6 * u : nullptr,
+                         upper6 ? upper6 + 6 * u : nullptr, n_rows, n_cols, np, scratch_out, &ad);
+    outside[u] = rc == -2;
+    if (rc == -2) continue;
+    if (rc != 0) return rc;
+    a->U.add(cs[u], u);
+    a->d[u] = ad.d; a->dp[u] = ad.dp; a->nk[u] = (int)n_kept[u]; a->th[u] = ad.th; a->A[u] = std::exp(logA[u]);
+  }
+  for (int u = 0; u < nu; ++u) {
+    rc_out[u] = outside[u] ? -2 : 0;
+    if (outside[u]) fill_out_of_box(out_host + OUT_COUNT * u);
+  }
+  for (int i = 0; i < a->U.cnt; ++i) {
+    gpfit_ctx* c = a->U.ctx[i];
+    c->lv_valid = false; c->lv32_valid = false;
+    c->side_ev_next = 0;
+  }
+  return 0;
+}
+
+// The operands of the element-wise passes (ProjGroupT) that both closures keep in the same members of a context: n
+// training points padded to np; each closure adds the matrices it places differently (am, Kb, aV, Ga, GaKi, P2).
+static ProjGroupT closure_group(const ClosureUnits& a, int n, int np, const double* const* r, const double* lambda0) {
+  const Units& U = a.U;
+  ProjGroupT pg{};
+  pg.n_units = U.cnt; pg.n = n; pg.np = np; pg.nb = a.nb; pg.ld = a.nb;
+  pg.r = U.from(r); pg.A = U.from(a.A); pg.lambda0 = U.from(lambda0);
+  pg.mb = U.of(&gpfit_ctx::mpad); pg.Kvec = U.of(&gpfit_ctx::Kvec); pg.lam_m = U.of(&gpfit_ctx::lam_m);
+  pg.lam_var = U.of(&gpfit_ctx::lam_var); pg.f = U.of(&gpfit_ctx::fvec); pg.gm = U.of(&gpfit_ctx::dq1); pg.gv = U.of(&gpfit_ctx::dq2);
+  pg.part = U.of(&gpfit_ctx::upart); pg.out3 = U.scal(S_RLAM);
+  pg.Ki = U.of(&gpfit_ctx::Vbuf); pg.P1 = U.of(&gpfit_ctx::TmpV); pg.bvec = U.of(&gpfit_ctx::yv);
+  pg.mkm = U.scal(S_MKM); pg.G = U.of(&gpfit_ctx::LiVbuf);
+  return pg;
+}
+// Behind a closure's last launch: every unit's scalars and info words to the host, the call's one synchronisation, and
+// each unit's 16 outputs and return code.  sigma0_row(scal_host, A, sigma0): the closure's own row of sigma_0.
+template <typename Row>
+static int closure_finish(const char* name, const ClosureUnits& a, hipStream_t s, const double* lambda0, double* out_host,
+                          int* rc_out, Row&& sigma0_row) {
+  GP_TRY(closure_collect(a.U, s));
+  GP_HIP(hipStreamSynchronize(s));
+  const std::string err_K = std::string(name) + ": Cholesky of the projected K_tilde failed (non-positive pivot)";
+  const std::string err_V = std::string(name) + ": Cholesky of V_b failed (non-positive pivot)";
+  for (int i = 0; i < a.U.cnt; ++i) {
+    gpfit_ctx* c = a.U.ctx[i];
+    const int u = a.U.at[i];
+    rc_out[u] = assemble_out(c, a.A[u], lambda0[u], sigma0_row(c->scal_host, a.A[u], a.th[u].sigma0), 0, a.d[u], 1, err_K.c_str(),
+                             err_V.c_str(), out_host + OUT_COUNT * u);
+  }
+  return 0;
+}
+
 // Truncated-rank (B-projected) M-step closure with the inducing set = the training set
 // (utils.py:2030-2099 with n < n_tilde = n_t), fused: kernel build, projection on the kept
 // eigen-directions B, Cholesky of the n x n matrices, moments / likelihood / KL, the n x n and N x n
@@ -1501,69 +1549,31 @@ static int fit_eval_projected_group_impl(const char* name, gpfit_ctx* const* cs,
                                          const double* const* m_b, const double* const* V_b, const int64_t* ldvb,
                                          const double* logA, const double* lambda0, double* out_host, int* rc_out) {
   using R = double;
-  auto refuse = [&](const std::string& why) {
-    set_error(std::string(name) + ": " + why);
-    return -3;
-  };
+  const Refuse refuse{name};
   if (nu < 1 || nu > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
   if (!cs || !theta6 || !X || !r || !B || !ldb || !n_kept || !m_b || !V_b || !ldvb || !logA || !lambda0 || !out_host || !rc_out ||
       N <= 0 || (lower6 == nullptr) != (upper6 == nullptr))
     return refuse("bad argument");
-  const int n = (int)N, np = (int)round_up(N, TILE), nb = (int)round_up(n_kept[0], TILE);
-  // ---- admission of every unit before anything is enqueued or written
-  struct Unit { gpfit_ctx* c; int u, d, dp, nk; Theta th; double A; };
-  Unit un[CHAIN_MAXU];
-  bool outside[CHAIN_MAXU];
-  int na = 0;
-  for (int u = 0; u < nu; ++u) {
-    const std::string unit = nu > 1 ? "unit " + std::to_string(u) + ": " : std::string();
-    if (!cs[u] || !X[u] || !r[u] || !B[u] || !m_b[u] || !V_b[u]) return refuse(unit + "null context or operand");
-    if (n_kept[u] <= 0 || n_kept[u] > N)
-      return refuse(unit + "bad argument: n_kept " + std::to_string(n_kept[u]) + " is not within 1 .. N = " + std::to_string(N));
-    if (ldb[u] < n_kept[u] || ldvb[u] < n_kept[u]) return refuse(unit + "bad leading dimension");
-    if (cs[u]->device != cs[0]->device) return refuse("the contexts of one call must live on one device");
-    for (int v = 0; v < u; ++v)
-      if (cs[v] == cs[u]) return refuse("every unit needs a context of its own");
-    if (cs[u]->pend.active)
-      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
-    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
-    if (round_up(n_kept[u], TILE) != nb)
-      return refuse(unit + "round_up(n_kept, 128) = " + std::to_string(round_up(n_kept[u], TILE)) + " differs from unit 0's " +
-                    std::to_string(nb) + " (group the units by padded size)");
-    // the slabs of the projections and the route of the lift depend on the capacity: one capacity, one route per call
-    if (cs[u]->np_cap != cs[0]->np_cap)
-      return refuse(unit + "the context's capacity of " + std::to_string(cs[u]->np_cap) + " stimuli differs from unit 0's " +
-                    std::to_string(cs[0]->np_cap) + " (group the units by the capacity of their contexts)");
-  }
-  for (int u = 0; u < nu; ++u) {
-    double scratch_out[OUT_COUNT];
-    Admitted ad;
-    const int rc = admit(cs[u], name, nu > 1 ? "a context's" : "the context", theta6 + 6 * u, lower6 ? lower6 + 6 * u : nullptr,
-                         upper6 ? upper6 + 6 * u : nullptr, n_rows, n_cols, np, scratch_out, &ad);
-    outside[u] = rc == -2;
-    if (rc == -2) continue;
-    if (rc != 0) return rc;
-    Unit& q = un[na++];
-    q.c = cs[u]; q.u = u; q.d = ad.d; q.dp = ad.dp; q.nk = (int)n_kept[u]; q.th = ad.th; q.A = std::exp(logA[u]);
-  }
-  for (int u = 0; u < nu; ++u) {
-    rc_out[u] = outside[u] ? -2 : 0;
-    if (outside[u]) fill_out_of_box(out_host + OUT_COUNT * u);
-  }
+  const int n = (int)N, np = (int)round_up(N, TILE);
+  ClosureUnits ad;
+  GP_TRY(admit_closure_units(
+      name, cs, nu, theta6, lower6, upper6, n_rows, n_cols, np, n_kept, N, "N", ldb, ldvb, logA,
+      [&](int u) { return X[u] && r[u] && B[u] && m_b[u] && V_b[u]; },
+      [&](int u) -> std::string {
+        // the slabs of the projections and the route of the lift depend on the capacity: one capacity, one route per call
+        if (cs[u]->np_cap != cs[0]->np_cap)
+          return "the context's capacity of " + std::to_string(cs[u]->np_cap) + " stimuli differs from unit 0's " +
+                 std::to_string(cs[0]->np_cap) + " (group the units by the capacity of their contexts)";
+        return std::string();
+      },
+      out_host, rc_out, &ad));
+  const Units& U = ad.U;
+  const int na = U.cnt, nb = ad.nb;
   if (na == 0) return 0;
   DeviceGuard device_guard(cs[0]->device);
   hipStream_t s = (hipStream_t)stream;
   const int64_t ld = np, lb = nb;
-  gpfit_ctx* cl[CHAIN_MAXU];
-  int nkl[CHAIN_MAXU], dl[CHAIN_MAXU];
-  const double* mbl[CHAIN_MAXU];
-  for (int i = 0; i < na; ++i) {
-    gpfit_ctx* c = un[i].c;
-    cl[i] = c; nkl[i] = un[i].nk; dl[i] = un[i].d; mbl[i] = m_b[un[i].u];
-    c->lv_valid = false; c->lv32_valid = false;
-    c->side_ev_next = 0;
-  }
-  gpfit_ctx* c0 = cl[0];
+  gpfit_ctx* c0 = U.ctx[0];
   const Lane lane = main_lane(c0, s);   // every launch on the caller's stream with the leader's workspace
   ++g_eval_count;
   prof_begin(c0);
@@ -1571,62 +1581,47 @@ static int fit_eval_projected_group_impl(const char* name, gpfit_ctx* const* cs,
   // The work matrices, per context (as ever): Kt = Kbuf, Bp = Lbuf, Kb = Libuf, aV = Tbuf, Ga = Zbuf, GaKi = Tmp, W = Wbuf;
   // the V_b chain in Abuf, Wbuf, Zbuf, Tmp; P2 = Abuf; S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV (n x n, leading dimension nb);
   // mbp = mpad, bvec = yv, gm = dq1, gv = dq2.
-  auto of = [&](double* gpfit_ctx::*X_) { return per_unit<double*>(na, [&](int i) { return cl[i]->*X_; }); };
-  auto cof = [&](double* gpfit_ctx::*X_) { return per_unit<const double*>(na, [&](int i) { return cl[i]->*X_; }); };
-  auto scal_of = [&](int slot) { return per_unit<double*>(na, [&](int i) { return cl[i]->scal + slot; }); };
-  auto all = [&](double* gpfit_ctx::*X_, int64_t ld_) { return mats(na, ld_, [&](int i) { return cl[i]->*X_; }); };
-  auto same = [&](auto v) { return per_unit<decltype(v)>(na, [&](int) { return v; }); };
-  const PerUnit<int> nks = per_unit<int>(na, [&](int i) { return nkl[i]; });
-  GP_TRY(closure_prepare(na, cl, dl, nkl, mbl, nb, s));   // pixel lists, info words, the padded m_b, bv / wl cleared
+  const PerUnit<int> nks = U.from(ad.nk);
+  GP_TRY(closure_prepare(U, ad.d, ad.nk, m_b, nb, s));   // pixel lists, info words, the padded m_b, bv / wl cleared
   // ---- unit by unit, the kernel build (as the full-rank unit): C, X masked, cos, Kvec, q, and K~ stored in full by the
   // tiles themselves (mirror): it is multiplied from the left below.  (The masked pixel count differs per unit.)
-  for (int i = 0; i < na; ++i)
-    GP_TRY(build_kernel<R>(cl[i], lane, un[i].th, un[i].d, un[i].dp, n_rows, n_cols, X[un[i].u], ldx, n, np, 1));
+  for (int i = 0; i < na; ++i) {
+    const int u = U.at[i];
+    GP_TRY(build_kernel<R>(U.ctx[i], lane, ad.th[u], ad.d[u], ad.dp[u], n_rows, n_cols, X[u], ldx, n, np, 1));
+  }
   // ---- projection (utils.py:2047-2049): K_b = K~ B, K~_b = sym(B^T K_b)
-  const Mat<R> Kt = all(&gpfit_ctx::Kbuf, ld), Bp = all(&gpfit_ctx::Lbuf, lb), Kb = all(&gpfit_ctx::Libuf, lb),
-               aV = all(&gpfit_ctx::Tbuf, lb), GaKi = all(&gpfit_ctx::Tmp, lb);
-  const Mat<R> S2 = all(&gpfit_ctx::LVbuf, lb), S3 = all(&gpfit_ctx::LiVbuf, lb), S4 = all(&gpfit_ctx::TmpV, lb);
-  GP_TRY(launch_pad_copy_group(na, per_unit<const double*>(na, [&](int i) { return B[un[i].u]; }),
-                               per_unit<int64_t>(na, [&](int i) { return ldb[un[i].u]; }), n, nks, of(&gpfit_ctx::Lbuf), lb, np, nb, s));
+  const Mat<R> Kt = U.mats(&gpfit_ctx::Kbuf, ld), Bp = U.mats(&gpfit_ctx::Lbuf, lb), Kb = U.mats(&gpfit_ctx::Libuf, lb),
+               aV = U.mats(&gpfit_ctx::Tbuf, lb), GaKi = U.mats(&gpfit_ctx::Tmp, lb);
+  const Mat<R> S2 = U.mats(&gpfit_ctx::LVbuf, lb), S3 = U.mats(&gpfit_ctx::LiVbuf, lb), S4 = U.mats(&gpfit_ctx::TmpV, lb);
+  GP_TRY(launch_pad_copy_group(na, U.from(B), U.from(ldb), n, nks, U.of(&gpfit_ctx::Lbuf), lb, np, nb, s));
   // (skinny products with a long k are cut into k slabs, gemm_splitk_list, each unit's in its own scratch; Wbuf is free
   // until the adjoints)
   R* part[CHAIN_MAXU];
   int64_t part_elems[CHAIN_MAXU];
-  for (int i = 0; i < na; ++i) { part[i] = cl[i]->Wbuf; part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap; }
+  for (int i = 0; i < na; ++i) { part[i] = U.ctx[i]->Wbuf; part_elems[i] = (int64_t)U.ctx[i]->np_cap * U.ctx[i]->np_cap; }
   GP_TRY(gemm_splitk_list(lane, {np, nb, np}, 1.0, plain(Kt), plain(Bp), Kb, part, part_elems));
   GP_TRY(gemm_splitk_list(lane, {nb, nb, np}, 1.0, trans(Bp), plain(Kb), S4, part, part_elems));
-  GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::TmpV), lb, nks, s));                                 // :2048
-  GP_TRY(launch_pack_lower_group(na, cof(&gpfit_ctx::TmpV), same(lb), nks, of(&gpfit_ctx::Vbuf), lb, nb, s));
+  GP_TRY(launch_symmetrize_avg_group(na, U.of(&gpfit_ctx::TmpV), lb, nks, s));                                 // :2048
+  GP_TRY(launch_pack_lower_group(na, U.cof(&gpfit_ctx::TmpV), U.same(lb), nks, U.of(&gpfit_ctx::Vbuf), lb, nb, s));
   {
     // (log|V_b| of :1326: V_b is factored together with K~_b -- the 2 na chains as one lock-step recursion on this stream,
     // each unit's V_b chain in four work matrices of its context nothing else needs before the adjoints: Abuf, Wbuf, Zbuf,
     // Tmp, handed over as the last evaluation left them -- the note at ProjChain)
     ProjChain vc[CHAIN_MAXU];
-    const double* Vb[CHAIN_MAXU];
-    int64_t ldv[CHAIN_MAXU];
     for (int i = 0; i < na; ++i) {
-      vc[i] = ProjChain{cl[i]->Abuf, cl[i]->Wbuf, cl[i]->Zbuf, cl[i]->Tmp};
-      Vb[i] = V_b[un[i].u]; ldv[i] = ldvb[un[i].u];
+      gpfit_ctx* c = U.ctx[i];
+      vc[U.at[i]] = ProjChain{c->Abuf, c->Wbuf, c->Zbuf, c->Tmp};
     }
-    GP_TRY(launch_pack_lower_group(na, per_unit<const double*>(na, [&](int i) { return Vb[i]; }),
-                                   per_unit<int64_t>(na, [&](int i) { return ldv[i]; }), nks, of(&gpfit_ctx::Abuf), lb, nb, s));
-    GP_TRY(projected_factor(lane, na, cl, Vb, ldv, nkl, nb, vc));
+    GP_TRY(launch_pack_lower_group(na, U.from(V_b), U.from(ldvb), nks, U.of(&gpfit_ctx::Abuf), lb, nb, s));
+    GP_TRY(projected_factor(lane, U, V_b, ldvb, ad.nk, nb, vc));
   }
   // K~_b^-1 is in S1 now.  a V = B V_b, then K~_b^-1 V_b with its trace and K~_b^-1 V_b K~_b^-1 (P1, in S4)
   GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(Bp), plain(S2), into(aV)));
-  GP_TRY(projected_kl_products(lane, na, cl, nkl, nb));
+  GP_TRY(projected_kl_products(lane, U, ad.nk, nb));
   // ---- moments / likelihood pieces with a = B and the adjoints G_a, G_Kb, G_K~b (P2 = B^T G_a K~_b^-1 in Abuf)
-  ProjGroupT pg{};
-  pg.n_units = na; pg.n = n; pg.np = np; pg.nb = nb; pg.ld = lb;
-  pg.r = per_unit<const double*>(na, [&](int i) { return r[un[i].u]; });
-  pg.A = per_unit<double>(na, [&](int i) { return un[i].A; });
-  pg.lambda0 = per_unit<double>(na, [&](int i) { return lambda0[un[i].u]; });
-  pg.am = of(&gpfit_ctx::Lbuf); pg.Kb = of(&gpfit_ctx::Libuf); pg.aV = of(&gpfit_ctx::Tbuf); pg.mb = of(&gpfit_ctx::mpad);
-  pg.Kvec = of(&gpfit_ctx::Kvec); pg.lam_m = of(&gpfit_ctx::lam_m); pg.lam_var = of(&gpfit_ctx::lam_var); pg.f = of(&gpfit_ctx::fvec);
-  pg.gm = of(&gpfit_ctx::dq1); pg.gv = of(&gpfit_ctx::dq2); pg.part = of(&gpfit_ctx::upart); pg.out3 = scal_of(S_RLAM);
-  pg.Ga = of(&gpfit_ctx::Zbuf); pg.GaKi = of(&gpfit_ctx::Tmp);
-  pg.Ki = of(&gpfit_ctx::Vbuf); pg.P1 = of(&gpfit_ctx::TmpV); pg.P2 = of(&gpfit_ctx::Abuf); pg.bvec = of(&gpfit_ctx::yv);
-  pg.mkm = scal_of(S_MKM); pg.G = of(&gpfit_ctx::LiVbuf);
+  ProjGroupT pg = closure_group(ad, n, np, r, lambda0);
+  pg.am = U.of(&gpfit_ctx::Lbuf); pg.Kb = U.of(&gpfit_ctx::Libuf); pg.aV = U.of(&gpfit_ctx::Tbuf);
+  pg.Ga = U.of(&gpfit_ctx::Zbuf); pg.GaKi = U.of(&gpfit_ctx::Tmp); pg.P2 = U.of(&gpfit_ctx::Abuf);
   GP_TRY(projected_adjoints(lane, pg, part, part_elems));
   GP_TRY(product(lane, {np, nb, nb}, 1.0, plain(Bp), plain(S3), into(GaKi, 1.0)));          // + B G_K~b
   // W = sym((.) B^T).  With P = B G_K~b + G_Kb:  1/2 (P B^T + B P^T) = 1/2 [P | B] [B | P]^T -- ONE product with
@@ -1634,44 +1629,36 @@ static int fit_eval_projected_group_impl(const char* name, gpfit_ctx* const* cs,
   // neither its upper half nor the averaging pass over N x N exist.  (Falls back to the two steps when 2 nb
   // columns do not fit the N x N scratch matrices, i.e. when hardly anything was truncated.)  One route for the call:
   // nb, np and the capacity are shared.
-  const Mat<R> W = all(&gpfit_ctx::Wbuf, ld);
+  const Mat<R> W = U.mats(&gpfit_ctx::Wbuf, ld);
   if (2 * (int64_t)nb * np <= (int64_t)c0->np_cap * c0->np_cap) {
     const int64_t l2b = 2 * lb;   // Cat1 = Zbuf, Cat2 = Tbuf: G_a and a V_b are dead
-    const PerUnit<const double*> P = cof(&gpfit_ctx::Tmp), Bc = cof(&gpfit_ctx::Lbuf);
-    const PerUnit<double*> Cat1 = of(&gpfit_ctx::Zbuf), Cat2 = of(&gpfit_ctx::Tbuf);
-    const PerUnit<double*> Cat1b = per_unit<double*>(na, [&](int i) { return cl[i]->Zbuf + nb; }),
-                           Cat2b = per_unit<double*>(na, [&](int i) { return cl[i]->Tbuf + nb; });
-    GP_TRY(launch_pad_copy_group(na, P, same(lb), np, same(nb), Cat1, l2b, np, nb, s));
-    GP_TRY(launch_pad_copy_group(na, Bc, same(lb), np, same(nb), Cat1b, l2b, np, nb, s));
-    GP_TRY(launch_pad_copy_group(na, Bc, same(lb), np, same(nb), Cat2, l2b, np, nb, s));
-    GP_TRY(launch_pad_copy_group(na, P, same(lb), np, same(nb), Cat2b, l2b, np, nb, s));
-    GP_TRY(product(lane, {np, np, 2 * nb}, 0.5, plain(all(&gpfit_ctx::Zbuf, l2b)), trans(all(&gpfit_ctx::Tbuf, l2b)), into_lower(W)));
+    const PerUnit<const double*> P = U.cof(&gpfit_ctx::Tmp), Bc = U.cof(&gpfit_ctx::Lbuf);
+    const PerUnit<double*> Cat1 = U.of(&gpfit_ctx::Zbuf), Cat2 = U.of(&gpfit_ctx::Tbuf);
+    const PerUnit<double*> Cat1b = U.of(&gpfit_ctx::Zbuf, nb), Cat2b = U.of(&gpfit_ctx::Tbuf, nb);
+    const PerUnit<int64_t> lbs = U.same(lb);
+    const PerUnit<int> nbs = U.same(nb);
+    GP_TRY(launch_pad_copy_group(na, P, lbs, np, nbs, Cat1, l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(na, Bc, lbs, np, nbs, Cat1b, l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(na, Bc, lbs, np, nbs, Cat2, l2b, np, nb, s));
+    GP_TRY(launch_pad_copy_group(na, P, lbs, np, nbs, Cat2b, l2b, np, nb, s));
+    GP_TRY(product(lane, {np, np, 2 * nb}, 0.5, plain(U.mats(&gpfit_ctx::Zbuf, l2b)), trans(U.mats(&gpfit_ctx::Tbuf, l2b)),
+                   into_lower(W)));
   } else {
     GP_TRY(product(lane, {np, np, nb}, 1.0, plain(GaKi), trans(Bp), into(W)));
-    GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::Wbuf), ld, same(np), s));
+    GP_TRY(launch_symmetrize_avg_group(na, U.of(&gpfit_ctx::Wbuf), ld, U.same(np), s));
   }
   // ---- unit by unit (the masked pixel count again), the pull-back of <W, dK~_p> + <gvec, dKvec_p> to the metric (as
   // gpfit_grad_pullback; gvec = -g_v; bv and wl were cleared at the start)
   for (int i = 0; i < na; ++i) {
-    gpfit_ctx* c = cl[i];
-    const Unit& q = un[i];
+    gpfit_ctx* c = U.ctx[i];
+    const int u = U.at[i], d = ad.d[u], dp = ad.dp[u];
     GP_TRY(launch_scale_copy<R>(c->wl, c->dq2, n, 1.0, s));
-    GP_TRY(pullback_to_metric(c, lane, c->Wbuf, c->Cos, c->q, n, np, q.dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
-    GP_TRY(launch_metric_contract(q.th, c->pix, q.d, n_rows, n_cols, c->Cmat, q.dp, c->Mmat, q.dp, c->scal + S_METRIC, c->upart,
+    GP_TRY(pullback_to_metric(c, lane, c->Wbuf, c->Cos, c->q, n, np, dp, c->Abuf, c->Xm, c->Zbuf));   // G_a's Zbuf is dead
+    GP_TRY(launch_metric_contract(ad.th[u], c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
                                   c->info + INFO_METRIC, s));
   }
-  GP_TRY(closure_collect(na, cl, s));
-  GP_HIP(hipStreamSynchronize(s));
-  const std::string err_K = std::string(name) + ": Cholesky of the projected K_tilde failed (non-positive pivot)";
-  const std::string err_V = std::string(name) + ": Cholesky of V_b failed (non-positive pivot)";
-  for (int i = 0; i < na; ++i) {
-    gpfit_ctx* c = cl[i];
-    const Unit& q = un[i];
-    const double* sc = c->scal_host;
-    rc_out[q.u] = assemble_out(c, q.A, lambda0[q.u], sigma0_row_metric(sc, q.th.sigma0) - 2.0 * q.th.sigma0 * sc[S_ADJ_WL], 0,
-                               q.d, 1, err_K.c_str(), err_V.c_str(), out_host + OUT_COUNT * q.u);
-  }
-  return 0;
+  return closure_finish(name, ad, s, lambda0, out_host, rc_out,
+                        [](const double* sc, double, double sigma0) { return sigma0_row_metric(sc, sigma0) - 2.0 * sigma0 * sc[S_ADJ_WL]; });
 }
 
 // Sparse M-step closure (n_tilde < n_t: K[n_t][n_tilde] != K~, a = K_b K~_b^-1 with non-zero da_p;
@@ -1699,66 +1686,25 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
                                       const int64_t* ldvb, const double* logA, const double* lambda0, double* out_host,
                                       int* rc_out) {
   using R = double;
-  auto refuse = [&](const std::string& why) {
-    set_error(std::string(name) + ": " + why);
-    return -3;
-  };
+  const Refuse refuse{name};
   if (nu < 1 || nu > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
   if (!cs || !theta6 || !X || !Xtilde || !r || !B || !ldb || !n_kept || !m_b || !V_b || !ldvb || !logA || !lambda0 || !out_host ||
       !rc_out || N <= 0 || Ntilde <= 0 || (lower6 == nullptr) != (upper6 == nullptr))
     return refuse("bad argument");
   const int n1 = (int)N, n2 = (int)Ntilde;
-  const int np1 = (int)round_up(N, TILE), np2 = (int)round_up(Ntilde, TILE), nb = (int)round_up(n_kept[0], TILE);
-  // ---- admission of every unit before anything is enqueued or written
-  struct Unit { gpfit_ctx* c; int u, d, dp, nk; Theta th; double A; };
-  Unit un[CHAIN_MAXU];
-  bool outside[CHAIN_MAXU];
-  int na = 0;
-  for (int u = 0; u < nu; ++u) {
-    const std::string unit = nu > 1 ? "unit " + std::to_string(u) + ": " : std::string();
-    if (!cs[u] || !X[u] || !Xtilde[u] || !r[u] || !B[u] || !m_b[u] || !V_b[u]) return refuse(unit + "null context or operand");
-    if (n_kept[u] <= 0 || n_kept[u] > Ntilde)
-      return refuse(unit + "bad argument: n_kept " + std::to_string(n_kept[u]) + " is not within 1 .. Ntilde = " + std::to_string(Ntilde));
-    if (ldb[u] < n_kept[u] || ldvb[u] < n_kept[u]) return refuse(unit + "bad leading dimension");
-    if (cs[u]->device != cs[0]->device) return refuse("the contexts of one call must live on one device");
-    for (int v = 0; v < u; ++v)
-      if (cs[v] == cs[u]) return refuse("every unit needs a context of its own");
-    if (cs[u]->pend.active)
-      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
-    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
-    if (round_up(n_kept[u], TILE) != nb)
-      return refuse(unit + "round_up(n_kept, 128) = " + std::to_string(round_up(n_kept[u], TILE)) + " differs from unit 0's " +
-                    std::to_string(nb) + " (group the units by padded size)");
-  }
-  for (int u = 0; u < nu; ++u) {
-    double scratch_out[OUT_COUNT];
-    Admitted ad;
-    const int rc = admit(cs[u], name, nu > 1 ? "a context's" : "the context", theta6 + 6 * u, lower6 ? lower6 + 6 * u : nullptr,
-                         upper6 ? upper6 + 6 * u : nullptr, n_rows, n_cols, std::max(np1, np2), scratch_out, &ad);
-    outside[u] = rc == -2;
-    if (rc == -2) continue;
-    if (rc != 0) return rc;
-    Unit& q = un[na++];
-    q.c = cs[u]; q.u = u; q.d = ad.d; q.dp = ad.dp; q.nk = (int)n_kept[u]; q.th = ad.th; q.A = std::exp(logA[u]);
-  }
-  for (int u = 0; u < nu; ++u) {
-    rc_out[u] = outside[u] ? -2 : 0;
-    if (outside[u]) fill_out_of_box(out_host + OUT_COUNT * u);
-  }
+  const int np1 = (int)round_up(N, TILE), np2 = (int)round_up(Ntilde, TILE);
+  ClosureUnits ad;
+  GP_TRY(admit_closure_units(
+      name, cs, nu, theta6, lower6, upper6, n_rows, n_cols, std::max(np1, np2), n_kept, Ntilde, "Ntilde", ldb, ldvb, logA,
+      [&](int u) { return X[u] && Xtilde[u] && r[u] && B[u] && m_b[u] && V_b[u]; }, [](int) { return std::string(); }, out_host,
+      rc_out, &ad));
+  const Units& U = ad.U;
+  const int na = U.cnt, nb = ad.nb;
   if (na == 0) return 0;
   DeviceGuard device_guard(cs[0]->device);
   hipStream_t s = (hipStream_t)stream;
   const int64_t l2 = np2, lb = nb;
-  gpfit_ctx* cl[CHAIN_MAXU];
-  int nkl[CHAIN_MAXU], dl[CHAIN_MAXU];
-  const double* mbl[CHAIN_MAXU];
-  for (int i = 0; i < na; ++i) {
-    gpfit_ctx* c = un[i].c;
-    cl[i] = c; nkl[i] = un[i].nk; dl[i] = un[i].d; mbl[i] = m_b[un[i].u];
-    c->lv_valid = false; c->lv32_valid = false;
-    c->side_ev_next = 0;
-  }
-  gpfit_ctx* c0 = cl[0];
+  gpfit_ctx* c0 = U.ctx[0];
   const Lane lane = main_lane(c0, s);   // every launch on the caller's stream with the leader's workspace
   ++g_eval_count;
   prof_begin(c0);
@@ -1766,47 +1712,42 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
   // The work matrices, per context (as ever): X1m = Xm, X2m = XDt, Zm = XDt2; Kt = Kbuf, CosT = Cos, Kr = Lbuf,
   // CosR = Libuf, Bp = Tbuf, Kb = Zbuf, am = Tmp, aV = Abuf; S1..S4 = Vbuf, LVbuf, LiVbuf, TmpV; mbp = mpad, bvec = yv,
   // gm = dq1, gv = dq2, gvec = hvec.
-  auto of = [&](double* gpfit_ctx::*X_) { return per_unit<double*>(na, [&](int i) { return cl[i]->*X_; }); };
-  auto cof = [&](double* gpfit_ctx::*X_) { return per_unit<const double*>(na, [&](int i) { return cl[i]->*X_; }); };
-  auto scal_of = [&](int slot) { return per_unit<double*>(na, [&](int i) { return cl[i]->scal + slot; }); };
-  auto all = [&](double* gpfit_ctx::*X_, int64_t ld) { return mats(na, ld, [&](int i) { return cl[i]->*X_; }); };
-  const PerUnit<int> nks = per_unit<int>(na, [&](int i) { return nkl[i]; });
-  GP_TRY(closure_prepare(na, cl, dl, nkl, mbl, nb, s));   // pixel lists, info words, the padded m_b, bv / wl cleared
+  const PerUnit<int> nks = U.from(ad.nk);
+  GP_TRY(closure_prepare(U, ad.d, ad.nk, m_b, nb, s));   // pixel lists, info words, the padded m_b, bv / wl cleared
   // ---- unit by unit, the kernel objects: C; training side (x: Xt, XCt, q, Kvec), inducing side (xtilde: Xt2, XCt2, q2);
   // K~ = acosker(xtilde, xtilde), lower tiles mirrored by the tiles themselves; K = acosker(x, xtilde)
   for (int i = 0; i < na; ++i) {
-    gpfit_ctx* c = cl[i];
-    const Unit& q = un[i];
-    const double s0sq = q.th.sigma0 * q.th.sigma0;
-    GP_TRY(build_metric<R>(c, s, q.th, q.d, q.dp, n_rows, n_cols));
-    GP_TRY(kernel_side<R>(c, lane, X[q.u], ldx, n1, np1, q.d, q.dp, s0sq, c->Xt, c->XCt, c->Xm, c->Kvec, c->q));
-    GP_TRY(kernel_side<R>(c, lane, Xtilde[q.u], ldxt, n2, np2, q.d, q.dp, s0sq, c->Xt2, c->XCt2, c->XDt, c->hvec, c->q2));
-    GP_TRY(gram_square<R>(s, c->XCt2, c->Xt2, c->q2, c->Kbuf, c->Cos, n2, np2, q.dp, s0sq, 1));
+    gpfit_ctx* c = U.ctx[i];
+    const int u = U.at[i], d = ad.d[u], dp = ad.dp[u];
+    const Theta& th = ad.th[u];
+    const double s0sq = th.sigma0 * th.sigma0;
+    GP_TRY(build_metric<R>(c, s, th, d, dp, n_rows, n_cols));
+    GP_TRY(kernel_side<R>(c, lane, X[u], ldx, n1, np1, d, dp, s0sq, c->Xt, c->XCt, c->Xm, c->Kvec, c->q));
+    GP_TRY(kernel_side<R>(c, lane, Xtilde[u], ldxt, n2, np2, d, dp, s0sq, c->Xt2, c->XCt2, c->XDt, c->hvec, c->q2));
+    GP_TRY(gram_square<R>(s, c->XCt2, c->Xt2, c->q2, c->Kbuf, c->Cos, n2, np2, dp, s0sq, 1));
     GramArgsT<R> g{};  // K = acosker(x, xtilde): rectangular, with its cosine matrix
     g.XCt = c->XCt; g.Xt = c->Xt2; g.q1 = c->q; g.q2 = c->q2; g.Kout = c->Lbuf; g.Cos = c->Libuf;
-    g.ld1 = np1; g.ld2 = l2; g.ldk = l2; g.np1 = np1; g.np2 = np2; g.nv1 = n1; g.nv2 = n2; g.Kd = q.dp;
+    g.ld1 = np1; g.ld2 = l2; g.ldk = l2; g.np1 = np1; g.np2 = np2; g.nv1 = n1; g.nv2 = n2; g.Kd = dp;
     g.s0sq = s0sq; g.lower = 0; g.pad_identity = 0;
     g.ldcos = l2;
-    ProfScope ps(s, 2.0 * np1 * np2 * q.dp, 2);
+    ProfScope ps(s, 2.0 * np1 * np2 * dp, 2);
     GP_TRY(launch_gram(g, s));
   }
   // ---- projection (:2047-2049, 2067-2068): K_b = K B, K~_b = sym(B^T K~ B), a = K_b K~_b^-1
-  const Mat<R> Kt = all(&gpfit_ctx::Kbuf, l2), Kr = all(&gpfit_ctx::Lbuf, l2), Bp = all(&gpfit_ctx::Tbuf, lb),
-               Kb = all(&gpfit_ctx::Zbuf, lb), am = all(&gpfit_ctx::Tmp, lb), aV = all(&gpfit_ctx::Abuf, lb);
-  const Mat<R> Ki = all(&gpfit_ctx::Vbuf, lb), S2 = all(&gpfit_ctx::LVbuf, lb), S3 = all(&gpfit_ctx::LiVbuf, lb),
-               S4 = all(&gpfit_ctx::TmpV, lb);
-  GP_TRY(launch_pad_copy_group(na, per_unit<const double*>(na, [&](int i) { return B[un[i].u]; }),
-                               per_unit<int64_t>(na, [&](int i) { return ldb[un[i].u]; }), n2, nks, of(&gpfit_ctx::Tbuf), lb, np2, nb, s));
+  const Mat<R> Kt = U.mats(&gpfit_ctx::Kbuf, l2), Kr = U.mats(&gpfit_ctx::Lbuf, l2), Bp = U.mats(&gpfit_ctx::Tbuf, lb),
+               Kb = U.mats(&gpfit_ctx::Zbuf, lb), am = U.mats(&gpfit_ctx::Tmp, lb), aV = U.mats(&gpfit_ctx::Abuf, lb);
+  const Mat<R> Ki = U.mats(&gpfit_ctx::Vbuf, lb), S2 = U.mats(&gpfit_ctx::LVbuf, lb), S3 = U.mats(&gpfit_ctx::LiVbuf, lb),
+               S4 = U.mats(&gpfit_ctx::TmpV, lb);
+  GP_TRY(launch_pad_copy_group(na, U.from(B), U.from(ldb), n2, nks, U.of(&gpfit_ctx::Tbuf), lb, np2, nb, s));
   // (skinny products with a long k are cut into k slabs, gemm_splitk_list; Wbuf is free until the adjoints)
   R* part[CHAIN_MAXU];
   int64_t part_elems[CHAIN_MAXU];
-  for (int i = 0; i < na; ++i) { part[i] = cl[i]->Wbuf; part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap; }
+  for (int i = 0; i < na; ++i) { part[i] = U.ctx[i]->Wbuf; part_elems[i] = (int64_t)U.ctx[i]->np_cap * U.ctx[i]->np_cap; }
   GP_TRY(gemm_splitk_list(lane, {np1, nb, np2}, 1.0, plain(Kr), plain(Bp), Kb, part, part_elems));
   GP_TRY(gemm_splitk_list(lane, {np2, nb, np2}, 1.0, plain(Kt), plain(Bp), am, part, part_elems));   // K~ B (temporary)
   GP_TRY(gemm_splitk_list(lane, {nb, nb, np2}, 1.0, trans(Bp), plain(am), S4, part, part_elems));
-  GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::TmpV), lb, nks, s));
-  const PerUnit<int64_t> lbs = per_unit<int64_t>(na, [&](int) { return lb; });
-  GP_TRY(launch_pack_lower_group(na, cof(&gpfit_ctx::TmpV), lbs, nks, of(&gpfit_ctx::Vbuf), lb, nb, s));
+  GP_TRY(launch_symmetrize_avg_group(na, U.of(&gpfit_ctx::TmpV), lb, nks, s));
+  GP_TRY(launch_pack_lower_group(na, U.cof(&gpfit_ctx::TmpV), U.same(lb), nks, U.of(&gpfit_ctx::Vbuf), lb, nb, s));
   {
     // The V_b chain of the lock-step factorisation takes four work matrices that are dead between the projections
     // above and the adjoints below, each of the context's full np_cap^2 size (nb <= np2 <= np_cap: an nb x nb chain
@@ -1814,48 +1755,36 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
     // rewritten as G_a and G_a K~_b^-1 further down) and Abuf (a V_b is formed behind the chain).  The cosine
     // matrices in Cos / Libuf stay untouched.
     ProjChain vc[CHAIN_MAXU];
-    const double* Vb[CHAIN_MAXU];
-    int64_t ldv[CHAIN_MAXU];
     for (int i = 0; i < na; ++i) {
-      vc[i] = ProjChain{cl[i]->Wbuf, cl[i]->Kbuf, cl[i]->Lbuf, cl[i]->Abuf};
-      Vb[i] = V_b[un[i].u]; ldv[i] = ldvb[un[i].u];
+      gpfit_ctx* c = U.ctx[i];
+      vc[U.at[i]] = ProjChain{c->Wbuf, c->Kbuf, c->Lbuf, c->Abuf};
     }
-    GP_TRY(launch_pack_lower_group(na, per_unit<const double*>(na, [&](int i) { return Vb[i]; }),
-                                   per_unit<int64_t>(na, [&](int i) { return ldv[i]; }), nks, of(&gpfit_ctx::Wbuf), lb, nb, s));
+    GP_TRY(launch_pack_lower_group(na, U.from(V_b), U.from(ldvb), nks, U.of(&gpfit_ctx::Wbuf), lb, nb, s));
     // tiles above the diagonal read as zero
-    GP_TRY(launch_zero3_group(na, of(&gpfit_ctx::Kbuf), of(&gpfit_ctx::Lbuf), of(&gpfit_ctx::Abuf), (int64_t)nb * nb, s));
-    GP_TRY(projected_factor(lane, na, cl, Vb, ldv, nkl, nb, vc));
+    GP_TRY(launch_zero3_group(na, U.of(&gpfit_ctx::Kbuf), U.of(&gpfit_ctx::Lbuf), U.of(&gpfit_ctx::Abuf), (int64_t)nb * nb, s));
+    GP_TRY(projected_factor(lane, U, V_b, ldvb, ad.nk, nb, vc));
   }
-  GP_TRY(projected_kl_products(lane, na, cl, nkl, nb));
+  GP_TRY(projected_kl_products(lane, U, ad.nk, nb));
   GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(Kb), plain(Ki), into(am)));           // a
   GP_TRY(product(lane, {np1, nb, nb}, 1.0, plain(am), plain(S2), into(aV)));           // a V_b
   // ---- moments / likelihood pieces with a = K_b K~_b^-1, per-point adjoints; G_a = Kbuf, G_a K~_b^-1 = Lbuf [np1][nb]
-  ProjGroupT pg{};
-  pg.n_units = na; pg.n = n1; pg.np = np1; pg.nb = nb; pg.ld = lb;
-  pg.r = per_unit<const double*>(na, [&](int i) { return r[un[i].u]; });
-  pg.A = per_unit<double>(na, [&](int i) { return un[i].A; });
-  pg.lambda0 = per_unit<double>(na, [&](int i) { return lambda0[un[i].u]; });
-  pg.am = of(&gpfit_ctx::Tmp); pg.Kb = of(&gpfit_ctx::Zbuf); pg.aV = of(&gpfit_ctx::Abuf); pg.mb = of(&gpfit_ctx::mpad);
-  pg.Kvec = of(&gpfit_ctx::Kvec); pg.lam_m = of(&gpfit_ctx::lam_m); pg.lam_var = of(&gpfit_ctx::lam_var); pg.f = of(&gpfit_ctx::fvec);
-  pg.gm = of(&gpfit_ctx::dq1); pg.gv = of(&gpfit_ctx::dq2); pg.part = of(&gpfit_ctx::upart); pg.out3 = scal_of(S_RLAM);
-  pg.Ga = of(&gpfit_ctx::Kbuf); pg.GaKi = of(&gpfit_ctx::Lbuf);
-  pg.Ki = of(&gpfit_ctx::Vbuf); pg.P1 = of(&gpfit_ctx::TmpV); pg.P2 = of(&gpfit_ctx::Wbuf); pg.bvec = of(&gpfit_ctx::yv);
-  pg.mkm = scal_of(S_MKM); pg.G = of(&gpfit_ctx::LiVbuf);
+  ProjGroupT pg = closure_group(ad, n1, np1, r, lambda0);
+  pg.am = U.of(&gpfit_ctx::Tmp); pg.Kb = U.of(&gpfit_ctx::Zbuf); pg.aV = U.of(&gpfit_ctx::Abuf);
+  pg.Ga = U.of(&gpfit_ctx::Kbuf); pg.GaKi = U.of(&gpfit_ctx::Lbuf); pg.P2 = U.of(&gpfit_ctx::Wbuf);
   for (int i = 0; i < na; ++i) {   // P2's slabs behind P1 in TmpV
-    part[i] = cl[i]->TmpV + (int64_t)nb * nb;
-    part_elems[i] = (int64_t)cl[i]->np_cap * cl[i]->np_cap - (int64_t)nb * nb;
+    part[i] = U.ctx[i]->TmpV + (int64_t)nb * nb;
+    part_elems[i] = (int64_t)U.ctx[i]->np_cap * U.ctx[i]->np_cap - (int64_t)nb * nb;
   }
   GP_TRY(projected_adjoints(lane, pg, part, part_elems));
   // ---- the two adjoints:  W~ = sym(B G_K~b B^T) [np2 x np2],  W_K = G_Kb B^T [np1 x np2]
-  GP_TRY(product(lane, {np2, nb, nb}, 1.0, plain(Bp), plain(S3), into(all(&gpfit_ctx::Kbuf, lb))));   // B G_K~b  (G_a is dead)
-  GP_TRY(product(lane, {np2, np2, nb}, 1.0, plain(all(&gpfit_ctx::Kbuf, lb)), trans(Bp), into(all(&gpfit_ctx::Wbuf, l2))));
-  GP_TRY(launch_symmetrize_avg_group(na, of(&gpfit_ctx::Wbuf), l2, per_unit<int>(na, [&](int) { return np2; }), s));
-  GP_TRY(product(lane, {np1, np2, nb}, 1.0, plain(all(&gpfit_ctx::Lbuf, lb)), trans(Bp), into(all(&gpfit_ctx::Abuf, l2))));   // W_K  (a V_b is dead)
+  GP_TRY(product(lane, {np2, nb, nb}, 1.0, plain(Bp), plain(S3), into(U.mats(&gpfit_ctx::Kbuf, lb))));   // B G_K~b  (G_a is dead)
+  GP_TRY(product(lane, {np2, np2, nb}, 1.0, plain(U.mats(&gpfit_ctx::Kbuf, lb)), trans(Bp), into(U.mats(&gpfit_ctx::Wbuf, l2))));
+  GP_TRY(launch_symmetrize_avg_group(na, U.of(&gpfit_ctx::Wbuf), l2, U.same(np2), s));
+  GP_TRY(product(lane, {np1, np2, nb}, 1.0, plain(U.mats(&gpfit_ctx::Lbuf, lb)), trans(Bp), into(U.mats(&gpfit_ctx::Abuf, l2))));   // W_K  (a V_b is dead)
   // ---- unit by unit, the two pull-backs
   for (int i = 0; i < na; ++i) {
-    gpfit_ctx* c = cl[i];
-    const Unit& q = un[i];
-    const int d = q.d, dp = q.dp;
+    gpfit_ctx* c = U.ctx[i];
+    const int u = U.at[i], d = ad.d[u], dp = ad.dp[u];
     double *X1m = c->Xm, *X2m = c->XDt, *Zm = c->XDt2, *KtU = c->Kbuf, *WK = c->Abuf, *gv = c->dq2, *gvec = c->hvec;
     // square pull-back on the inducing stimuli (no b b^T term, no dKvec term: bv / wl were cleared at the start; A_w
     // into K_b, which is dead; a (Tmp) is dead)
@@ -1875,24 +1804,13 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
     GP_TRY(xty<R>(c, s, X2m, Zm, np2, dp, c->dCpad, false));
     GP_TRY(launch_axpby_block<double>(c->Mmat, dp, c->dCpad, dp, dp, dp, 1.0, 1.0, s));
     GP_TRY(launch_symmetrize_avg(c->Mmat, dp, dp, s));
-    GP_TRY(launch_metric_contract(q.th, c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
+    GP_TRY(launch_metric_contract(ad.th[u], c->pix, d, n_rows, n_cols, c->Cmat, dp, c->Mmat, dp, c->scal + S_METRIC, c->upart,
                                   c->info + INFO_METRIC, s));
   }
-  GP_TRY(closure_collect(na, cl, s));
-  GP_HIP(hipStreamSynchronize(s));
-  const std::string err_K = std::string(name) + ": Cholesky of the projected K_tilde failed (non-positive pivot)";
-  const std::string err_V = std::string(name) + ": Cholesky of V_b failed (non-positive pivot)";
-  for (int i = 0; i < na; ++i) {
-    gpfit_ctx* c = cl[i];
-    const Unit& q = un[i];
-    const double* sc = c->scal_host;
-    const double sum_gvec = 0.5 * q.A * q.A * sc[S_SUMF];                                               // -sum g_v
-    rc_out[q.u] = assemble_out(c, q.A, lambda0[q.u],
-                               sigma0_row_metric(sc, q.th.sigma0) +
-                                   q.th.sigma0 * (2.0 * sc[S_RECT] + sc[S_RECT_U1] + sc[S_RECT_U2]) + 2.0 * q.th.sigma0 * sum_gvec,
-                               0, q.d, 1, err_K.c_str(), err_V.c_str(), out_host + OUT_COUNT * q.u);
-  }
-  return 0;
+  return closure_finish(name, ad, s, lambda0, out_host, rc_out, [](const double* sc, double A, double sigma0) {
+    const double sum_gvec = 0.5 * A * A * sc[S_SUMF];                                               // -sum g_v
+    return sigma0_row_metric(sc, sigma0) + sigma0 * (2.0 * sc[S_RECT] + sc[S_RECT_U1] + sc[S_RECT_U2]) + 2.0 * sigma0 * sum_gvec;
+  });
 }
 
 // Wait for the evaluation enqueued on this context and assemble its 16 host scalars.

@@ -11,7 +11,7 @@
 // so it keeps the first failure) and a stop word next to it (INFO_V's slot, which nothing else uses during this call)
 // that records the step.  No kernel waits on another: a unit that has failed still takes part in the later launches,
 // which only touch its own work matrices and its own Y / W, and the copy that makes steps visible in Q tests the gate.
-#include "product.h"
+#include "units.h"
 #include "gpfit_mi355x.h"
 
 #include <algorithm>
@@ -93,27 +93,10 @@ __global__ void sweep_collect_kernel(PerUnit<int*> info, PerUnit<int*> info_host
   __threadfence_system();
 }
 
-// the units of one launch: indices into the call's tables, in ascending order
-struct UnitList {
-  int cnt = 0;
-  int at[CHAIN_MAXU];
-  void add(int u) { at[cnt++] = u; }
-};
-
-template <typename T, typename F>
-PerUnit<T> table(const UnitList& l, F&& of) {
-  PerUnit<T> t{};
-  for (int i = 0; i < l.cnt; ++i) t.v[i] = of(l.at[i]);
-  return t;
-}
-
 int sweeps_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* K, int64_t ldk,
                 int64_t N, int64_t k, double* const* Q, double* const* Y, double* const* W, double* const* S, const int* m,
                 const double* const* sigma, int flags, int* rec_host) {
-  auto refuse = [&](const std::string& why) {
-    set_error(std::string(name) + ": " + why);
-    return -3;
-  };
+  const Refuse refuse{name};
   if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
   if (!ctxs || !K || !Q || !Y || !W || !m || !sigma || !rec_host) return refuse("bad argument");
   if (flags & ~(GPFIT_SWEEPS_Y_READY | GPFIT_SWEEPS_WANT_RR)) return refuse("bad argument: unknown flag");
@@ -124,16 +107,12 @@ int sweeps_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* str
   const int np = (int)round_up(k, TILE);
   int mmax = 0;
   for (int u = 0; u < n_units; ++u) {
-    const std::string unit = n_units > 1 ? "unit " + std::to_string(u) + ": " : std::string();
+    const std::string unit = unit_prefix(n_units, u);
     if (!ctxs[u] || !K[u] || !Q[u] || !Y[u] || !W[u] || (want_rr && !S[u])) return refuse(unit + "bad argument: null context or operand");
     if (m[u] < 0 || m[u] > GPFIT_SUBSPACE_SWEEPS_MAX_STEPS)
       return refuse(unit + "m = " + std::to_string(m[u]) + " is not within 0 .. " + std::to_string(GPFIT_SUBSPACE_SWEEPS_MAX_STEPS));
     if (m[u] > 0 && !sigma[u]) return refuse(unit + "bad argument: no shifts");
-    if (ctxs[u]->device != ctxs[0]->device) return refuse("the contexts of one call must live on one device");
-    for (int v = 0; v < u; ++v)
-      if (ctxs[v] == ctxs[u]) return refuse("every unit needs a context of its own");
-    if (ctxs[u]->pend.active)
-      return refuse("an asynchronous evaluation is pending on this context (collect it with gpfit_fit_eval_finish first)");
+    if (const char* why = unit_context_refusal(ctxs, u)) return refuse(why);
     if (np > ctxs[u]->np_cap) return refuse(unit + "block larger than the context capacity");
     mmax = std::max(mmax, m[u]);
   }
@@ -143,8 +122,7 @@ int sweeps_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* str
   const int64_t ld = np, count = N * k;
   const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
   const dim3 flat((unsigned)((count + 255) / 256));
-  UnitList everyone;
-  for (int u = 0; u < n_units; ++u) everyone.add(u);
+  const Units everyone = Units::all(ctxs, n_units);
   // Where a unit's block and its product stand is known to the host at every launch.  blk: the block the step starts
   // from, the caller's Q at first; y: K blk, shifted, then the input of a round; the round's output becomes the next y
   // or the next blk.  The caller's Q is only ever written by the gated copy.  With a third work block beside Y and W
@@ -165,69 +143,57 @@ int sweeps_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* str
       if (w && w != a && w != b) return w;
     return nullptr;
   };
-  auto info_of = [&](const UnitList& l) { return table<int*>(l, [&](int u) { return ctxs[u]->info; }); };
-  auto list_of = [&](const UnitList& l, int64_t ldm, auto&& at) { return mats(l.cnt, ldm, [&](int i) { return at(l.at[i]); }); };
   // y = K blk                                                           matmul(K, Q)
-  auto apply_K = [&](const UnitList& l) -> int {
+  auto apply_K = [&](const Units& l) -> int {
     for (int i = 0; i < l.cnt; ++i) y[l.at[i]] = pick(l.at[i], blk[l.at[i]], nullptr);
-    return product(lane, {n, kb, n}, 1.0, plain(list_of(l, ldk, [&](int u) { return K[u]; })),
-                   plain(list_of(l, k, [&](int u) { return blk[u]; })), into(list_of(l, k, [&](int u) { return y[u]; })));
+    return product(lane, {n, kb, n}, 1.0, plain(l.mats(K, ldk)), plain(l.mats(blk, k)), into(l.mats(y, k)));
   };
   // Q <- blk behind the gate, and the block is the caller's Q again
-  auto commit = [&](const UnitList& l) -> int {
+  auto commit = [&](const Units& l) -> int {
     if (!l.cnt) return 0;
-    hipLaunchKernelGGL(sweep_commit_kernel, dim3(flat.x, l.cnt), dim3(256), 0, s, info_of(l),
-                       table<const double*>(l, [&](int u) { return blk[u]; }), table<double*>(l, [&](int u) { return Q[u]; }), count);
+    hipLaunchKernelGGL(sweep_commit_kernel, dim3(flat.x, l.cnt), dim3(256), 0, s, l.of(&gpfit_ctx::info), l.from(blk), l.from(Q),
+                       count);
     GP_HIP(hipGetLastError());
     for (int i = 0; i < l.cnt; ++i) blk[l.at[i]] = Q[l.at[i]];
     return 0;
   };
   // one round of _cholqr on the units of the list: G = Y^T Y, (G + G^T) / 2, gpfit_potrf's factorisation with the
   // inverse, Y L^-T.  G in Abuf and the dense L^-1 in TmpV, both k x k with leading dimension k as the host loop has them
-  auto round = [&](const UnitList& l, int step) -> int {
-    const auto G = [&](int u) { return ctxs[u]->Abuf; };
-    const auto Lid = [&](int u) { return ctxs[u]->TmpV; };
-    GP_TRY(product(lane, {kb, kb, n}, 1.0, trans(list_of(l, k, [&](int u) { return y[u]; })),
-                   plain(list_of(l, k, [&](int u) { return y[u]; })), into(list_of(l, k, G))));
-    hipLaunchKernelGGL(sweep_sym_pack_kernel, dim3(np / TILE, np / TILE, l.cnt * (TILE / 16)), dim3(256), 0, s,
-                       table<const double*>(l, G), kb, table<double*>(l, [&](int u) { return ctxs[u]->Kbuf; }), ld);
+  auto round = [&](const Units& l, int step) -> int {
+    const auto G = &gpfit_ctx::Abuf, Lid = &gpfit_ctx::TmpV;
+    GP_TRY(product(lane, {kb, kb, n}, 1.0, trans(l.mats(y, k)), plain(l.mats(y, k)), into(l.mats(G, k))));
+    hipLaunchKernelGGL(sweep_sym_pack_kernel, dim3(np / TILE, np / TILE, l.cnt * (TILE / 16)), dim3(256), 0, s, l.cof(G), kb,
+                       l.of(&gpfit_ctx::Kbuf), ld);
     GP_HIP(hipGetLastError());
     CholBatchT<double> cb;
-    for (int i = 0; i < l.cnt; ++i) {
-      gpfit_ctx* c = ctxs[l.at[i]];
-      const int b = cb.nb++;
-      cb.A[b] = c->Kbuf; cb.L[b] = c->Lbuf; cb.Li[b] = c->Libuf; cb.Tmp[b] = c->Tmp; cb.info[b] = c->info + INFO_K;
-    }
+    for (int i = 0; i < l.cnt; ++i) add_k_chain(cb, l.ctx[i]);
     cb.ld = ld;
-    GP_TRY(potrf_lockstep(cb, 0, np, (uint32_t)((1ull << l.cnt) - 1ull), lane));
-    hipLaunchKernelGGL(sweep_unpack_tri_kernel, dim3((kb + 255) / 256, kb, l.cnt), dim3(256), 0, s, info_of(l), step,
-                       table<const double*>(l, [&](int u) { return ctxs[u]->Libuf; }), ld, kb, table<double*>(l, Lid), k);
+    GP_TRY(potrf_lockstep(cb, 0, np, l.chains(), lane));
+    hipLaunchKernelGGL(sweep_unpack_tri_kernel, dim3((kb + 255) / 256, kb, l.cnt), dim3(256), 0, s, l.of(&gpfit_ctx::info), step,
+                       l.cof(&gpfit_ctx::Libuf), ld, kb, l.of(Lid), k);
     GP_HIP(hipGetLastError());
     double* out[CHAIN_MAXU];
     for (int i = 0; i < l.cnt; ++i) out[l.at[i]] = pick(l.at[i], blk[l.at[i]], y[l.at[i]]);
-    GP_TRY(product(lane, {n, kb, kb}, 1.0, plain(list_of(l, k, [&](int u) { return y[u]; })),
-                   trans(list_of(l, k, [&](int u) { return Lid(u); })), into(list_of(l, k, [&](int u) { return out[u]; }))));
+    GP_TRY(product(lane, {n, kb, kb}, 1.0, plain(l.mats(y, k)), trans(l.mats(Lid, k)), into(l.mats(out, k))));
     for (int i = 0; i < l.cnt; ++i) y[l.at[i]] = out[l.at[i]];
     return 0;
   };
-  hipLaunchKernelGGL(sweep_init_kernel, dim3(n_units), dim3(64), 0, s, info_of(everyone));
+  hipLaunchKernelGGL(sweep_init_kernel, dim3(n_units), dim3(64), 0, s, everyone.of(&gpfit_ctx::info));
   GP_HIP(hipGetLastError());
   for (int j = 0; j < mmax; ++j) {
     // the units that have step j; those with a shift in it; those for which it is the last; those whose Q is due
-    UnitList act, shifted, last, due;
+    Units act, shifted, last, due;
     for (int u = 0; u < n_units; ++u) {
       if (m[u] <= j) continue;
-      act.add(u);
-      if (sigma[u][j] != 0.0) shifted.add(u);
-      if (m[u] == j + 1) last.add(u);
-      if (m[u] == j + 1 || !third[u]) due.add(u);
+      act.add(ctxs[u], u);
+      if (sigma[u][j] != 0.0) shifted.add(ctxs[u], u);
+      if (m[u] == j + 1) last.add(ctxs[u], u);
+      if (m[u] == j + 1 || !third[u]) due.add(ctxs[u], u);
     }
     if (!(j == 0 && y_ready)) GP_TRY(apply_K(act));   // (ready: y is the caller's Y, as set above)
     if (shifted.cnt) {
-      hipLaunchKernelGGL(sweep_shift_kernel, dim3(flat.x, shifted.cnt), dim3(256), 0, s, info_of(shifted),
-                         table<double*>(shifted, [&](int u) { return y[u]; }),
-                         table<const double*>(shifted, [&](int u) { return blk[u]; }),
-                         table<double>(shifted, [&](int u) { return sigma[u][j]; }), count);
+      hipLaunchKernelGGL(sweep_shift_kernel, dim3(flat.x, shifted.cnt), dim3(256), 0, s, shifted.of(&gpfit_ctx::info),
+                         shifted.from(y), shifted.from(blk), shifted.table<double>([&](int u) { return sigma[u][j]; }), count);
       GP_HIP(hipGetLastError());
     }
     GP_TRY(round(act, j));
@@ -237,16 +203,12 @@ int sweeps_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* str
   }
   if (want_rr) {
     // Y = K Q, S = Q^T Y, S = (S + S^T) / 2: what the Rayleigh-Ritz step and the certificate read
-    GP_TRY(product(lane, {n, kb, n}, 1.0, plain(list_of(everyone, ldk, [&](int u) { return K[u]; })),
-                   plain(list_of(everyone, k, [&](int u) { return Q[u]; })), into(list_of(everyone, k, [&](int u) { return Y[u]; }))));
-    GP_TRY(product(lane, {kb, kb, n}, 1.0, trans(list_of(everyone, k, [&](int u) { return Q[u]; })),
-                   plain(list_of(everyone, k, [&](int u) { return Y[u]; })),
-                   into(list_of(everyone, k, [&](int u) { return S[u]; }))));
-    GP_TRY(launch_symmetrize_avg_group(n_units, table<double*>(everyone, [&](int u) { return S[u]; }), k,
-                                       table<int>(everyone, [&](int) { return kb; }), s));
+    GP_TRY(product(lane, {n, kb, n}, 1.0, plain(everyone.mats(K, ldk)), plain(everyone.mats(Q, k)), into(everyone.mats(Y, k))));
+    GP_TRY(product(lane, {kb, kb, n}, 1.0, trans(everyone.mats(Q, k)), plain(everyone.mats(Y, k)), into(everyone.mats(S, k))));
+    GP_TRY(launch_symmetrize_avg_group(n_units, everyone.from(S), k, everyone.same(kb), s));
   }
-  hipLaunchKernelGGL(sweep_collect_kernel, dim3(n_units), dim3(64), 0, s, info_of(everyone),
-                     table<int*>(everyone, [&](int u) { return ctxs[u]->info_host; }));
+  hipLaunchKernelGGL(sweep_collect_kernel, dim3(n_units), dim3(64), 0, s, everyone.of(&gpfit_ctx::info),
+                     everyone.of(&gpfit_ctx::info_host));
   GP_HIP(hipGetLastError());
   GP_HIP(hipStreamSynchronize(s));
   for (int u = 0; u < n_units; ++u) {

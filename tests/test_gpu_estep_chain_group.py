@@ -187,8 +187,8 @@ def test_a_unit_whose_optimiser_fails_stops_alone(gp):
 
 
 def test_refusals_enqueue_nothing(gp):
-    """17 units, a repeated context, mixed padded sizes and a null unit pointer: -3 with a message, and no output of any
-    unit changes."""
+    """17 units, a repeated context, mixed padded sizes, a null unit pointer, and two faults of which the earlier unit's is
+    named: -3 with a message, and no output of any unit changes."""
     engines = gp._group_engines(3, 200)
     cs = [case(200, 128, 500 + i) for i in range(3)]
     odd = case(200, 130, 503)                                # round_up(130, 128) = 256
@@ -220,6 +220,10 @@ def test_refusals_enqueue_nothing(gp):
     qs = requests(cs)
     qs[1]["m"] = None
     refused(ctxs, qs, "null")
+    # two faults in one call -- unit 1's V narrower than nb, unit 2 on unit 0's context: the units are checked in order
+    qs = requests(cs)
+    qs[1]["V"] = torch.empty(128, 64, dtype=torch.float64, device="cuda")
+    refused([ctxs[0], ctxs[1], ctxs[0]], qs, "unit 1: bad argument: bad size or leading dimension")
     # and the same three units are accepted as they are
     qs = requests(cs)
     rc, _ = gp._chain_batch_raw(ctxs, qs)

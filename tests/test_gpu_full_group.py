@@ -222,8 +222,8 @@ def test_a_unit_whose_optimiser_fails_stops_alone(gp):
 
 
 def test_refusals_enqueue_nothing(gp):
-    """A repeated context, a context whose capacity is too small and a leading dimension of K below N: -3 with a message,
-    and no output or record of any unit changes."""
+    """A repeated context, a context whose capacity is too small, a leading dimension of K below N, and two faults of which
+    the earlier unit's is named: -3 with a message, and no output or record of any unit changes."""
     from gaussian_processes_amd.engine import GPFitEngine
     N = 300
     engines = gp._group_engines(3, N)
@@ -258,6 +258,10 @@ def test_refusals_enqueue_nothing(gp):
     qs = requests()
     qs[0]["ldv"] = N - 1
     refused(ctxs, qs, "unit 0: bad argument: bad size or leading dimension")
+    # two faults in one call -- unit 1's leading dimension, unit 2 on unit 0's context: the units are checked in order
+    qs = requests()
+    qs[1]["ldk"] = N - 1
+    refused([ctxs[0], ctxs[1], ctxs[0]], qs, "unit 1: bad argument: bad size or leading dimension")
     # and the same three units are accepted as they are
     qs = requests()
     rc, _ = gp._chain_full_batch_raw(ctxs, qs)

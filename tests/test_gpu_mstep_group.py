@@ -272,6 +272,10 @@ def test_refusals_enqueue_nothing(gp):
     qs = requests(gp, good, engines)
     qs[2]["n_kept"] = Nt + 1
     refused(ctxs, qs, "n_kept")
+    # two faults in one call -- unit 1's V_b narrower than n_kept, unit 2 on unit 0's context: the units are checked in order
+    qs = requests(gp, good, engines)
+    qs[1]["V_b"] = qs[1]["V_b"][:, :-1].contiguous()
+    refused([ctxs[0], ctxs[1], ctxs[0]], qs, "gpfit_fit_eval_sparse_batch: unit 1: bad leading dimension")
     small = gp.GPFitEngine(128, N_PX * N_PX, N_PX * N_PX, device=engines[0].device)
     refused([ctxs[0], ctxs[1], small._ctx], requests(gp, good, engines), "capacity")
     # and the same three units are accepted as they are

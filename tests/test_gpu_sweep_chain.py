@@ -184,6 +184,12 @@ def test_the_refusals_of_the_entry_point(gp):
         q2 = dict(q, **over)
         rc, _ = gp._sweeps_batch_raw([eng._ctx, eng._ctx] if not over else [eng._ctx], [q2, q2] if not over else [q2], rec)
         assert rc == -3 and "gpfit_subspace_sweeps_batch: " in _lib.last_error() and word in _lib.last_error(), (what, _lib.last_error())
+    # two faults in one call -- unit 1 has more steps than a call takes (the one size a unit has of its own), unit 2 is on
+    # unit 0's context: the units are checked in order
+    other = gp._group_engines(2, k)[1]
+    rec6 = (ctypes.c_int * 6)()
+    rc, _ = gp._sweeps_batch_raw([eng._ctx, other._ctx, eng._ctx], [q, dict(q, shifts=[0.0] * 1025), q], rec6)
+    assert rc == -3 and "gpfit_subspace_sweeps_batch: unit 1: m = 1025 is not within 0 .. 1024" in _lib.last_error(), _lib.last_error()
     small = gp.GPFitEngine(128, 1, 1, device=eng.device)
     N2, k2 = SHAPES[2]
     K2, Q2, s2 = problem(N2, k2)

@@ -352,6 +352,8 @@ def test_refusals_enqueue_nothing(gp):
     qs = requests(gp, good, engines)
     qs[1]["B"] = Narrow(qs[1]["B"], qs[1]["n_kept"] - 1)
     refused(ctxs, qs, "leading dimension")
+    # two faults in one call -- that leading dimension of unit 1, unit 2 on unit 0's context: the units are checked in order
+    refused([ctxs[0], ctxs[1], ctxs[0]], qs, "gpfit_fit_eval_projected_batch: unit 1: bad leading dimension")
     refused(ctxs, requests(gp, [good[0], unit(N, 100, 1), good[2]], engines), "round_up(n_kept, 128)")
     large = engines_for(gp, 1, 1024)[0]
     refused([ctxs[0], ctxs[1], large._ctx], requests(gp, good, engines), "capacity")
