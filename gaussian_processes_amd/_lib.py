@@ -50,6 +50,8 @@ _SIGS = {
     "gpfit_estep": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, f64, vp, vp, i64]),
     "gpfit_estep_projected": (i32, [vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, f64, vp, vp, i64, vp, vp,
                                     vp]),
+    "gpfit_estep_projected_damped": (i32, [vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, f64, f64,
+                                           vp, vp, i64, ctypes.POINTER(i32)]),
     "gpfit_fparam_eval": (i32, [vp, vp, vp, vp, vp, i64, f64, i32, f64, vp, pd]),
     "gpfit_fparam_lbfgs": (i32, [vp, vp, vp, vp, vp, i64, f64, i32, f64, i32, i32, f64, f64, f64, vp, pd]),
     "gpfit_estep_chain": (i32, [vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, f64, i32, f64,

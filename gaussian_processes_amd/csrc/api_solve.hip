@@ -250,6 +250,51 @@ struct ChainCall {
   }
 };
 
+// The stages gpfit_estep_projected and gpfit_estep_projected_damped share, on the work vectors and matrices of one
+// context (ld = npc): the same launches in the same order for both callers.
+struct ProjStep {
+  gpfit_ctx* c;
+  hipStream_t s;
+  Lane lane;
+  int n, k, nrows, npc;
+  int64_t ld;
+  double *sv, *u, *t2, *z1, *z, *mo, *Y, *Lp, *P, *V, *part, *aLp, *Zm;
+  Mat<double> M(double* X) const { return mat(X, ld); }
+};
+static ProjStep proj_step(gpfit_ctx* c, hipStream_t s, int64_t N, int64_t nb) {
+  ProjStep w{};
+  w.c = c; w.s = s; w.lane = main_lane(c, s);
+  w.n = (int)N; w.k = (int)nb; w.nrows = (int)round_up(N, TILE); w.npc = (int)round_up(nb, TILE);
+  w.ld = w.npc;
+  w.sv = c->yv; w.u = c->bv; w.t2 = c->tvec; w.z1 = c->mpad; w.z = c->rpad; w.mo = c->hvec;
+  w.Y = c->Tbuf; w.Lp = c->Wbuf; w.P = c->Abuf; w.V = c->Zbuf; w.part = c->TmpV; w.aLp = c->LiVbuf; w.Zm = c->Cos;
+  return w;
+}
+// t2 = (a L)^T u and W = I + Y^T Y in Kbuf (lower tiles, identity on the padding); with_aLp: the padded copy of aL too
+static int proj_step_w(const ProjStep& w, const double* a, int64_t lda, const double* aL, int64_t ldal, const double* r,
+                       const double* m, const double* f, double A, bool with_aLp) {
+  gpfit_ctx* c = w.c;
+  GP_TRY(launch_estep_proj_rows(a, lda, w.k, m, f, r, w.n, w.nrows, A, w.sv, w.u, w.s));
+  GP_TRY(launch_estep_proj_scale(aL, ldal, w.k, w.n, w.nrows, w.sv, w.u, w.Y, with_aLp ? w.aLp : nullptr, w.ld, w.npc, w.part, w.s));
+  GP_TRY((launch_reduce_slices<double, double>(w.part, w.npc, w.nrows / 32, w.t2, w.npc, w.s)));   // t2 = (a L)^T u
+  // W = I + Y^T Y  (= I + L^T G L, G = A^2 a^T diag(f) a), lower tiles, identity on the padding
+  GP_TRY(product(w.lane, {w.npc, w.npc, w.nrows}, 1.0, trans(w.M(w.Y)), plain(w.M(w.Y)), into_lower(w.M(c->Kbuf))));
+  return launch_add_diag(c->Kbuf, w.ld, w.npc, 1.0, w.s);
+}
+// mo = L W^-1 (a L)^T u from W's inverse factor in Libuf; leaves L packed in Lp
+static int proj_step_mean(const ProjStep& w, const double* L, int64_t ldl) {
+  gpfit_ctx* c = w.c;
+  GP_TRY(launch_trmv_lower(c->Libuf, w.ld, w.npc, w.t2, w.z1, w.s));
+  GP_TRY(launch_trmv_lower_t(c->Libuf, w.ld, w.npc, w.z1, w.z, c->trmv_part, w.s));
+  GP_TRY(launch_pack_lower(L, ldl, w.k, w.Lp, w.ld, w.npc, w.s));
+  return launch_trmv_lower(w.Lp, w.ld, w.npc, w.z, w.mo, w.s);
+}
+// V (lower tiles) = P P^T, P = L Li^T with Li the inverse factor of the matrix whose inverse V is in L's coordinates
+static int proj_step_cov(const ProjStep& w, double* Li) {
+  GP_TRY(product(w.lane, {w.npc, w.npc, w.npc}, 1.0, plain(tril(w.M(w.Lp))), trans(tril(w.M(Li))), into(w.M(w.P))));
+  return product(w.lane, {w.npc, w.npc, w.npc}, 1.0, plain(w.M(w.P)), trans(w.M(w.P)), into_lower(w.M(w.V)));
+}
+
 extern "C" {
 
 int gpfit_potrf_append(gpfit_ctx* c, void* stream, double* L, int64_t ldl, double* Linv, int64_t ldi, int64_t n,
@@ -445,46 +490,102 @@ int gpfit_estep_projected(gpfit_ctx* c, void* stream, const double* a, int64_t l
   }
   GP_CTX_ENTER(c, "gpfit_estep_projected");
   hipStream_t s = (hipStream_t)stream;
-  const int n = (int)N, k = (int)nb;
-  const int nrows = (int)round_up(N, TILE), npc = (int)round_up(nb, TILE);
-  if (nrows > c->np_cap || npc > c->np_cap) {
+  const ProjStep w = proj_step(c, s, N, nb);
+  if (w.nrows > c->np_cap || w.npc > c->np_cap) {
     set_error("gpfit_estep_projected: problem larger than the context capacity");
     return -3;
   }
-  const int64_t ld = npc;
-  const double A = std::exp(logA);
-  double *sv = c->yv, *u = c->bv, *t2 = c->tvec, *z1 = c->mpad, *z = c->rpad, *mo = c->hvec;
-  double *Y = c->Tbuf, *Lp = c->Wbuf, *P = c->Abuf, *V = c->Zbuf, *part = c->TmpV, *aLp = c->LiVbuf, *Zm = c->Cos;
   c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
-  const Lane lane = main_lane(c, s);
-  auto M = [&](double* X) { return mat(X, ld); };
   GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
-  GP_TRY(launch_estep_proj_rows(a, lda, k, m, f, r, n, nrows, A, sv, u, s));
-  GP_TRY(launch_estep_proj_scale(aL, ldal, k, n, nrows, sv, u, Y, want_moments ? aLp : nullptr, ld, npc, part, s));
-  GP_TRY((launch_reduce_slices<double, double>(part, npc, nrows / 32, t2, npc, s)));   // t2 = (a L)^T u
-  // W = I + Y^T Y  (= I + L^T G L, G = A^2 a^T diag(f) a), lower tiles, identity on the padding
-  GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(M(Y)), plain(M(Y)), into_lower(M(c->Kbuf))));
-  GP_TRY(launch_add_diag(c->Kbuf, ld, npc, 1.0, s));
-  GP_TRY(potrf_lockstep(one_chain(c, ld), 0, npc, 1u, lane));
+  GP_TRY(proj_step_w(w, a, lda, aL, ldal, r, m, f, std::exp(logA), want_moments));
+  GP_TRY(potrf_lockstep(one_chain(c, w.ld), 0, w.npc, 1u, w.lane));
   // m_new = L W^-1 (a L)^T u
-  GP_TRY(launch_trmv_lower(c->Libuf, ld, npc, t2, z1, s));
-  GP_TRY(launch_trmv_lower_t(c->Libuf, ld, npc, z1, z, c->trmv_part, s));
-  GP_TRY(launch_pack_lower(L, ldl, k, Lp, ld, npc, s));
-  GP_TRY(launch_trmv_lower(Lp, ld, npc, z, mo, s));
+  GP_TRY(proj_step_mean(w, L, ldl));
   // V_new = P P^T, P = L L_W^-T  (= (K~^-1 + G)^-1 = solve(I + K~ G, K~), utils.py:1430)
-  GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(M(Lp))), trans(tril(M(c->Libuf))), into(M(P))));
-  GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(M(P)), trans(M(P)), into_lower(M(V))));
-  GP_HIP(hipMemcpyAsync(m_new, mo, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s));
-  GP_TRY(launch_unpack_sym(V, ld, k, V_new, ldv, s));   // symmetric by construction (utils.py:1438)
+  GP_TRY(proj_step_cov(w, c->Libuf));
+  GP_HIP(hipMemcpyAsync(m_new, w.mo, (size_t)w.k * sizeof(double), hipMemcpyDeviceToDevice, s));
+  GP_TRY(launch_unpack_sym(w.V, w.ld, w.k, V_new, ldv, s));   // symmetric by construction (utils.py:1438)
   if (want_moments) {
     // the moments of lambda the caller evaluates next (utils.py:1090, 1101), from Z = aL L_W^-T: a V_new a^T = Z Z^T
-    GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(M(aLp)), trans(tril(M(c->Libuf))), into(M(Zm))));
-    GP_TRY(launch_estep_proj_moments(Zm, ld, k, z1, kv0, n, lam_m_out, lam_var_out, s));
+    GP_TRY(product(w.lane, {w.nrows, w.npc, w.npc}, 1.0, plain(w.M(w.aLp)), trans(tril(w.M(c->Libuf))), into(w.M(w.Zm))));
+    GP_TRY(launch_estep_proj_moments(w.Zm, w.ld, w.k, w.z1, kv0, w.n, lam_m_out, lam_var_out, s));
   }
   GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   GP_HIP(hipStreamSynchronize(s));
   if (c->info_host[INFO_K] != 0) {
     set_error("gpfit_estep_projected: I + L^T G L is not positive definite (NaN or negative firing rates?)");
+    return c->info_host[INFO_K];
+  }
+  return 0;
+}
+
+// The damped update (header: gpfit_estep_projected_damped).  Work matrices beyond those of the full step, all ld = npc:
+//   Zbuf  L^-1 packed (lower, identity padding)     Abuf  V symmetric, identity padding     Wbuf  L^-1 V
+//   Vbuf  P = L^-1 V L^-T (lower tiles): the V chain's matrix, factored beside W1 (the K chain) in one lock-step call
+//   Cos   the copy of W1 taken before its factorisation, then W_a = (1 - a) P^-1 + a W1 in place (the product's beta)
+// Zbuf, Abuf and Wbuf are free again once P is formed: the full step's stages use them as they always do (Lp, P, V).
+// W_a is factored on the K chain's L / L^-1 / scratch matrices, after the mean has read W1's inverse factor there.
+int gpfit_estep_projected_damped(gpfit_ctx* c, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
+                                 const double* L, int64_t ldl, const double* Linv, int64_t ldli, const double* V,
+                                 int64_t ldv_in, int64_t N, int64_t nb, const double* r, const double* m, const double* f,
+                                 double logA, double alpha, double* m_new, double* V_new, int64_t ldv, int* info_v_host) {
+  const Refuse refuse{"gpfit_estep_projected_damped"};
+  if (!c || !a || !aL || !L || !Linv || !V || !r || !m || !f || !m_new || !V_new)
+    return refuse("bad argument: null context or operand");
+  if (N <= 0 || nb <= 0) return refuse("bad argument: N and nb must be positive");
+  if (lda < nb || ldal < nb || ldl < nb || ldli < nb || ldv_in < nb || ldv < nb)
+    return refuse("bad argument: a leading dimension is smaller than nb");
+  if (!std::isfinite(alpha) || !(alpha > 0.0) || alpha > 1.0)
+    return refuse("bad argument: the step size alpha must lie in (0, 1]");
+  GP_CTX_ENTER(c, "gpfit_estep_projected_damped");
+  hipStream_t s = (hipStream_t)stream;
+  const ProjStep w = proj_step(c, s, N, nb);
+  if (w.nrows > c->np_cap || w.npc > c->np_cap) return refuse("problem larger than the context capacity");
+  const int npc = w.npc;
+  const int64_t ld = w.ld;
+  double *Lip = c->Zbuf, *Vs = c->Abuf, *LiV = c->Wbuf, *Wa = c->Cos, *mpad = c->dq1;
+  c->lv_valid = false; c->lv32_valid = false;   // the V work matrices are reused
+  GP_HIP(hipMemsetAsync(c->info, 0, 4 * sizeof(int), s));
+  GP_TRY(proj_step_w(w, a, lda, aL, ldal, r, m, f, std::exp(logA), false));
+  GP_HIP(hipMemcpyAsync(Wa, c->Kbuf, (size_t)npc * npc * sizeof(double), hipMemcpyDeviceToDevice, s));   // W1, kept
+  // P = L^-1 V L^-T, lower tiles, identity on the padding (positive definite iff V is)
+  GP_TRY(launch_pack_tri(Linv, ldli, w.k, Lip, ld, npc, s));
+  GP_TRY(launch_pack_tri(V, ldv_in, w.k, Vs, ld, npc, s));
+  GP_TRY(launch_symmetrize(Vs, ld, npc, s));
+  GP_TRY(product(w.lane, {npc, npc, npc}, 1.0, plain(tril(w.M(Lip))), plain(w.M(Vs)), into(w.M(LiV))));
+  GP_TRY(product(w.lane, {npc, npc, npc}, 1.0, plain(w.M(LiV)), trans(tril(w.M(Lip))), into_lower(w.M(c->Vbuf))));
+  // W1 and P in lock step, both with their full inverse factors
+  CholBatchT<double> two;
+  add_k_chain(two, c);
+  add_v_chain(two, c);
+  two.ld = ld;
+  GP_TRY(potrf_lockstep(two, 0, npc, 3u, w.lane));
+  // m_new = (1 - a) m + a L W1^-1 (a L)^T u: the full step's mean, damped.  The same vector as utils.py:1436, since
+  // m - (I + K~ G)^-1 (m - K~ g) = (I + K~ G)^-1 K~ (G m + g)
+  GP_TRY(proj_step_mean(w, L, ldl));
+  GP_HIP(hipMemsetAsync(mpad, 0, (size_t)npc * sizeof(double), s));
+  GP_HIP(hipMemcpyAsync(mpad, m, (size_t)w.k * sizeof(double), hipMemcpyDeviceToDevice, s));
+  GP_TRY(launch_axpby_block<double>(w.mo, ld, mpad, ld, 1, npc, alpha, 1.0 - alpha, s));
+  // W_a = (1 - a) P^-1 + a W1 (lower tiles), P^-1 = L_P^-T L_P^-1; then its factor with the full inverse
+  GP_TRY(product(w.lane, {npc, npc, npc}, 1.0 - alpha, trans(tril(w.M(c->LiVbuf))), plain(tril(w.M(c->LiVbuf))),
+                 into_lower(w.M(Wa), alpha)));
+  CholBatchT<double> one;
+  add_chain(one, Wa, c->Lbuf, c->Libuf, c->Tmp, c->info + INFO_K);
+  one.ld = ld;
+  GP_TRY(potrf_lockstep(one, 0, npc, 1u, w.lane));
+  // V_new = P P^T, P = L L_Wa^-T  (V_new^-1 = (1 - a) V^-1 + a (K~^-1 + G) = L^-T W_a L^-1)
+  GP_TRY(proj_step_cov(w, c->Libuf));
+  GP_HIP(hipMemcpyAsync(m_new, w.mo, (size_t)w.k * sizeof(double), hipMemcpyDeviceToDevice, s));
+  GP_TRY(launch_unpack_sym(w.V, ld, w.k, V_new, ldv, s));   // symmetric by construction
+  GP_HIP(hipMemcpyAsync(c->info_host, c->info, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  GP_HIP(hipStreamSynchronize(s));
+  if (info_v_host) *info_v_host = c->info_host[INFO_V];
+  if (c->info_host[INFO_V] != 0) {
+    set_error("gpfit_estep_projected_damped: V is not positive definite (the damped update needs a positive definite V)");
+    return c->info_host[INFO_V];
+  }
+  if (c->info_host[INFO_K] != 0) {
+    set_error("gpfit_estep_projected_damped: I + L^T G L is not positive definite (NaN or negative firing rates?)");
     return c->info_host[INFO_K];
   }
   return 0;

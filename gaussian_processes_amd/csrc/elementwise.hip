@@ -1416,6 +1416,23 @@ int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_
   return 0;
 }
 
+// dst[np][ldd] <- the lower triangle of src[n][lds]: zero above the diagonal (whatever src holds there), identity on the
+// padding; every element of the np x np block is written
+__global__ void pack_tri_kernel(const double* __restrict__ src, int64_t lds, int n, double* __restrict__ dst, int64_t ldd,
+                                int np) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+  if (i >= np || j >= np) return;
+  double v = (i == j) ? 1.0 : 0.0;
+  if (i < n && j < n) v = (j <= i) ? src[(int64_t)i * lds + j] : 0.0;
+  dst[(int64_t)i * ldd + j] = v;
+}
+
+int launch_pack_tri(const double* src, int64_t lds, int n, double* dst, int64_t ldd, int np, hipStream_t s) {
+  hipLaunchKernelGGL(pack_tri_kernel, dim3((np + 255) / 256, np), dim3(256), 0, s, src, lds, n, dst, ldd, np);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- the small kernels of a chained E-step (kernels.h: ChainBlock, ChainGate, ChainGroupT)
 // the full-rank moments behind a committed update (gpfit_estep_chain_full / _batch; a = B = I; unit u = blockIdx.y behind
 // its own gate): lam_m = m_new and lam_var = (Kvec - diag K~) + diag V, the diagonal read from the lower-tile work

@@ -233,6 +233,9 @@ int launch_estep_build(const double* K, int64_t ldk, int n, int np, const double
 int launch_symv_lower(const double* A, int64_t lda, int n, const double* x, double* y, hipStream_t s);
 int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
 int launch_unpack_tri(const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
+// dst [np][ldd] <- the lower triangle of src (n x n; what src holds above its diagonal is not read), zero above the
+// diagonal, identity padding up to np: a triangular operand of product, or (launch_symmetrize behind it) a symmetric one
+int launch_pack_tri(const double* src, int64_t lds, int n, double* dst, int64_t ldd, int np, hipStream_t s);
 int launch_fparam(const double* lam_m, const double* lam_var, const double* r, int n, double A, int closed_form,
                   double lambda0_in, double* f, double* out, hipStream_t s);
 // The rate-parameter L-BFGS of an E-step in one launch (one workgroup): out[9] as documented at the kernel.

@@ -597,15 +597,33 @@ def compute_KL_div(m, V, K_tilde, K_tilde_inv, dK_tilde=None, ignore_warning=Fal
 
 
 def Estep(r, KKtilde_inv, m, f_params, f_mean, K_tilde=None, K_tilde_inv=None, V=None, update_V_inv=False, alpha=1):
-    """Newton update of (m, V) -- the supported branch of the reference (alpha = 1,
-    update_V_inv=False; utils.py:1420-1439).  ``V = (I + K~ G)^-1 K~`` is evaluated in its
-    symmetric form ``L (I + L^T G L)^-1 L^T`` (K~ = L L^T) with two MFMA Cholesky factorisations
-    instead of the reference's LU solve.  The alpha != 1 / update_V_inv branches are documented
-    as not to be used (reference docs.md:5-7) and are not provided."""
-    if update_V_inv or K_tilde is None or alpha != 1:
-        warnings.warn('Estep: only the alpha = 1, update_V_inv = False update on V is implemented')
+    """Newton update of (m, V) -- the update on V of the reference (update_V_inv=False; utils.py:1420-1439), with the
+    full step (alpha = 1) or a damped one (0 < alpha < 1, which needs the current ``V``).
+
+    alpha = 1: ``V = (I + K~ G)^-1 K~`` is evaluated in its symmetric form ``L (I + L^T G L)^-1 L^T`` (K~ = L L^T) with
+    two MFMA Cholesky factorisations instead of the reference's LU solve.
+
+    alpha != 1 (the remedy the reference's docs.md:18 names first when the E-step misbehaves, :1432-1436): the
+    reference's ``V solve((1-a) K~ + a V + a K~ G V, K~)`` is ``V_new^-1 = (1-a) V^-1 + a (K~^-1 + G)``, a convex
+    combination of positive definite precisions, and is evaluated as such from Cholesky factors only, as one device
+    call (``gpfit_estep_projected_damped``): V_new is exactly symmetric and positive definite whenever V and K~ are.  A V
+    that is not raises ``torch.linalg.LinAlgError`` ("Estep: V is not positive definite").  alpha outside (0, 1] is a
+    ``ValueError``.
+
+    ``update_V_inv=True`` is documented as not to be used (reference docs.md:5-7) and is not provided; neither is a
+    call without ``K_tilde``, nor alpha != 1 without ``V``."""
+    if not 0 < alpha <= 1:     # (also refuses NaN)
+        raise ValueError(f'Estep: the step size alpha must lie in (0, 1], got {alpha}')
+    if update_V_inv or K_tilde is None or (alpha != 1 and V is None):
+        warnings.warn('Estep: only the update_V_inv = False update on V is implemented (alpha != 1 needs V)')
         raise NotImplementedError
     K_tilde = _cu(K_tilde)
+    if alpha != 1:
+        L, Linv, _, info = cholesky(K_tilde, want_inverse=True)
+        if info != 0:
+            raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info})")
+        a = _cu(KKtilde_inv)
+        return _estep_projected_damped(r, a, matmul(a, L), L, Linv, V, m, f_params, f_mean, alpha)
     L, _, _, info = cholesky(K_tilde)
     if info != 0:
         raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info})")
@@ -663,6 +681,38 @@ def _estep_projected(r, KKtilde_inv, aL, L, m, f_params, f_mean, kv0=None):
         raise _lib.GpfitError(f"gpfit_estep_projected: {_lib.last_error()} (rc={rc})")
     if kv0 is not None:
         return m_new, V_new, lam_m, lam_var
+    return m_new, V_new
+
+
+_V_NOT_POSDEF = "Estep: V is not positive definite"
+
+
+def _estep_projected_damped(r, KKtilde_inv, aL, L, Linv, V, m, f_params, f_mean, alpha):
+    """The damped Newton update (``Estep`` with 0 < alpha <= 1, utils.py:1432-1436) as ONE device call
+    (``gpfit_estep_projected_damped``): ``V_new^-1 = (1-a) V^-1 + a (K~^-1 + G)`` and ``m_new = (1-a) m + a m_full`` from
+    Cholesky factors only, with ``L``, ``Linv = L^-1`` and ``aL = a L`` supplied by the caller (fixed between two kernel
+    rebuilds) and the current ``V`` (symmetric; positive definite, or ``torch.linalg.LinAlgError`` beginning
+    "Estep: V is not positive definite").  Returns ``(m_new, V_new)``, V_new exactly symmetric."""
+    r, a, aL, L, Linv, V, m, f_mean = (_cu(r), _cu(KKtilde_inv), _cu(aL), _cu(L), _cu(Linv), _cu(V), _cu(m),
+                                       _cu(f_mean))
+    a, aL, L, Linv, V = a.contiguous(), aL.contiguous(), L.contiguous(), Linv.contiguous(), V.contiguous()
+    N, nb = a.shape
+    m_new = torch.empty(nb, dtype=TORCH_DTYPE, device=a.device)
+    V_new = torch.empty((nb, nb), dtype=TORCH_DTYPE, device=a.device)
+    eng = get_engine(max(N, nb), 1)
+    info_v = ctypes.c_int(0)
+    rc = _lib.load().gpfit_estep_projected_damped(
+        eng._ctx, _stream(), a.data_ptr(), a.stride(0), aL.data_ptr(), aL.stride(0), L.data_ptr(), L.stride(0),
+        Linv.data_ptr(), Linv.stride(0), V.data_ptr(), V.stride(0), N, nb, r.contiguous().data_ptr(),
+        m.contiguous().data_ptr(), f_mean.contiguous().data_ptr(), _scalar(f_params['logA']), float(alpha),
+        m_new.data_ptr(), V_new.data_ptr(), V_new.stride(0), ctypes.byref(info_v))
+    if rc > 0 and info_v.value != 0:
+        raise torch.linalg.LinAlgError(f"{_V_NOT_POSDEF}: the damped update needs a positive definite V "
+                                       f"(info={info_v.value})")
+    if rc > 0:
+        raise torch.linalg.LinAlgError(f"Estep: I + L^T G L is not positive definite (info={rc})")
+    if rc != 0:
+        raise _lib.GpfitError(f"gpfit_estep_projected_damped: {_lib.last_error()} (rc={rc})")
     return m_new, V_new
 
 
@@ -1154,7 +1204,7 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     of equal key (``_REQUEST_KINDS``, ``_request_bucket_key``); two kinds never share a call.  Each cell's numbers are
     those of ``varGP`` on its own, bit for bit.  Between two calls the fits of a wave take turns, one running at a
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
-    Fits that never chain (f_params carrying ``loglambda0``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
+    Fits that never chain (f_params carrying ``loglambda0``, ``estep_alpha != 1``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
     being waited for.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is the
     error of every fit in that call.  Out of the groups stay the basis rebuilds, the loss evaluation between chain and
     M-step and the fp32 instance.
@@ -2229,7 +2279,7 @@ def varGP(x, r, **kwargs):
     (``gpfit_estep_chain_full``: the update of ``gpfit_estep``, the moments and the rate-parameter optimiser,
     ``nEstep`` times, with one wait); otherwise the same steps run in the reference's projected formulation on
     the GPU primitives, the E-steps again as one call (``gpfit_estep_chain``).  The host loop around single
-    updates stays where a chain does not apply: ``f_params`` carrying ``loglambda0``, more than 1024 E-steps,
+    updates stays where a chain does not apply: ``f_params`` carrying ``loglambda0``, ``estep_alpha != 1``, more than 1024 E-steps,
     ``GPFIT_ESTEP_CHAIN=0``, and the full-rank regime with a square basis that is not the identity (the ``eigh``
     route keeping every eigenvalue), which rotates by ``B`` around every update.
 
@@ -2240,7 +2290,11 @@ def varGP(x, r, **kwargs):
       True`` asks for the reference's full matrix (one ``torch.linalg.eigh`` of the final K~ at the end of the fit).
     * extra keys: ``fit_model['basis_route']`` and ``values_track['variation_par_track']['basis_route']``
       (``'identity'`` / ``'eigtop'`` / ``'eigh'`` per tracked iteration): the route that built the basis ``(m_b,
-      V_b)`` are expressed in, which ``test(at_iteration=...)`` reproduces or refuses."""
+      V_b)`` are expressed in, which ``test(at_iteration=...)`` reproduces or refuses.
+    * ``fit_parameters['estep_alpha']`` (default 1: nothing changes) in (0, 1): every E-step takes the damped Newton
+      update (``Estep``'s alpha, ``gpfit_estep_projected_damped``) in the host loop, in every regime.  An update whose
+      reprojected ``V_b`` is not positive definite takes the full step instead, with a warning;
+      ``fit_model['estep_full_steps']`` (present only then) counts them."""
     import time
     start_time_before_init = time.time()
     err_dict = {'is_error': False, 'error_message': None}
@@ -2281,7 +2335,14 @@ def varGP(x, r, **kwargs):
 
     same_points = (ntilde == nt) and (x_given_as_xtilde or torch.equal(xtilde, x))
     eigvecs = None
-    if not ESTEP_CHAIN or 'loglambda0' in f_params or not 0 < nEstep <= CHAIN_MAX_STEPS or maxiter <= 1:
+    # step size of the E-step's Newton update (Estep's alpha); != 1: the damped update, one device call per E-step
+    estep_alpha = fit_parameters.get('estep_alpha', 1)
+    if not 0 < estep_alpha <= 1:
+        raise ValueError(f"varGP: fit_parameters['estep_alpha'] must lie in (0, 1], got {estep_alpha}")
+    damped = estep_alpha != 1
+    estep_full_steps = [0]   # damped E-steps that took the full step because the reprojected V_b was not positive definite
+    if (not ESTEP_CHAIN or 'loglambda0' in f_params or not 0 < nEstep <= CHAIN_MAX_STEPS or maxiter <= 1
+            or damped):
         _cells_withdraw()     # under varGP_cells: this fit keeps the host loop, nobody waits for its chains
 
     def build_kernels(th):
@@ -2429,7 +2490,7 @@ def varGP(x, r, **kwargs):
 
             t0 = time.time()
             if nEstep > 0:
-                if (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params
+                if (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params and not damped
                         and not full_rank()):
                     # the nEstep updates of this iteration as one device call (the loop below, enqueued in one go).
                     # The host loop stays (silently: the "E-steps" time is then the loop's) for more updates than the
@@ -2453,7 +2514,7 @@ def varGP(x, r, **kwargs):
                     last_rec = _estep_chain_commit(chain_rec, f_params)     # raises for the first failing step
                     rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), last_rec[1], f_fp)
                     # (the rate-parameter share of the call is not separable: times['fparams'] stays as it is)
-                elif (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params
+                elif (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params and not damped
                         and full_rank() and _is_identity(B)):
                     # the full-rank regime in the original basis (a = B = I): the loop below around gpfit_estep as one
                     # device call.  A square B that is not the identity (the eigh route keeping everything) keeps the
@@ -2475,7 +2536,7 @@ def varGP(x, r, **kwargs):
                             f_params['lambda0'] = lambda0_and_rate()                              # :1874
                         f_mean = rate_now()                                                         # :1877
                         fused_moments = False
-                        if full_rank():
+                        if full_rank() and not damped:
                             # fused Newton update in the original basis, then back to the eigenbasis
                             m_orig = m_b if _is_identity(B) else matmul(B, m_b)
                             m_new = torch.empty(nt, dtype=TORCH_DTYPE, device=dev)
@@ -2501,17 +2562,37 @@ def varGP(x, r, **kwargs):
                                 V_b = (V_b + V_b.T) / 2
                         else:
                             # :1880, with the factor of K~_b shared by the E-steps of this iteration
+                            # (a damped fit comes here in the full-rank regime too, with a = KKtilde_inv_b = B, and
+                            # keeps L^-1 beside the factor)
                             if estep_factor[0] is None or estep_factor[0][0] is not K_tilde_b:
-                                L_kb, _, _, info_kb = cholesky(K_tilde_b)
+                                L_kb, Li_kb, _, info_kb = cholesky(K_tilde_b, want_inverse=damped)
                                 if info_kb != 0:
                                     raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info_kb})")
                                 estep_factor[0] = (K_tilde_b, L_kb, matmul(KKtilde_inv_b, L_kb),
-                                                   Kvec - torch.sum(K_b * KKtilde_inv_b, 1))
-                            # the update and the moments behind it (:1884) in one device call
-                            m_b, V_b, lambda_m, lambda_var = _estep_projected(r, KKtilde_inv_b, estep_factor[0][2],
-                                                                              estep_factor[0][1], m_b, f_params, f_mean,
-                                                                              kv0=estep_factor[0][3])
-                            fused_moments = True
+                                                   Kvec - torch.sum(K_b * KKtilde_inv_b, 1), Li_kb)
+                            if damped:
+                                # :1432-1436 as one device call; the moments follow separately (moments_now below)
+                                try:
+                                    m_b, V_b = _estep_projected_damped(r, KKtilde_inv_b, estep_factor[0][2],
+                                                                       estep_factor[0][1], estep_factor[0][4], V_b, m_b,
+                                                                       f_params, f_mean, estep_alpha)
+                                except torch.linalg.LinAlgError as e:
+                                    if not str(e).startswith(_V_NOT_POSDEF):
+                                        raise
+                                    # the V_b reprojected onto a new basis need not be positive definite (reference
+                                    # docs.md:26-30, utils.py:1829): this one update takes the full step, which does
+                                    # not read V
+                                    warnings.warn(f'varGP: V_b is not positive definite in E-step {i_estep} of iteration '
+                                                  f'{iteration}; this update takes the full Newton step (alpha = 1)')
+                                    estep_full_steps[0] += 1
+                                    m_b, V_b = _estep_projected(r, KKtilde_inv_b, estep_factor[0][2],
+                                                                estep_factor[0][1], m_b, f_params, f_mean)
+                            else:
+                                # the update and the moments behind it (:1884) in one device call
+                                m_b, V_b, lambda_m, lambda_var = _estep_projected(r, KKtilde_inv_b, estep_factor[0][2],
+                                                                                  estep_factor[0][1], m_b, f_params,
+                                                                                  f_mean, kv0=estep_factor[0][3])
+                                fused_moments = True
                         if not fused_moments:
                             lambda_m, lambda_var = moments_now()                                    # :1884
                         # (the reference evaluates the rate here, :1885; nothing reads it before the closure below overwrites it)
@@ -2650,6 +2731,8 @@ def varGP(x, r, **kwargs):
         'V_b': V_b, 'C': C, 'mask': mask, 'K_tilde_b': K_tilde_b, 'K_tilde_inv_b': K_tilde_inv_b, 'K_b': K_b,
         'Kvec': Kvec, 'B': B, 'values_track': values_track, 'basis_route': basis_route[0],
     }
+    if damped:
+        fit_model['estep_full_steps'] = int(estep_full_steps[0])
     return fit_model, err_dict
 
 

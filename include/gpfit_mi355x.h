@@ -330,6 +330,34 @@ int gpfit_estep_projected(gpfit_ctx* ctx, void* stream, const double* a, int64_t
                           const double* f, double logA, double* m_new, double* V_new, int64_t ldv, const double* kv0,
                           double* lam_m_out, double* lam_var_out);
 
+/* The damped Newton update of the same basis (Estep with a step size alpha != 1, utils.py:1432-1436), in a form that
+ * keeps V positive definite by construction.  The reference's
+ *   V_new = V solve((1 - a) K~ + a V + a K~ G V, K~)      is      V_new^-1 = (1 - a) V^-1 + a (K~^-1 + G),
+ * a convex combination of positive definite precisions for 0 < a <= 1.  With K~ = L L^T, Y = diag(A sqrt f) aL:
+ *   W1  = I + Y^T Y = L_W1 L_W1^T                    (the matrix gpfit_estep_projected factors)
+ *   P   = L^-1 V L^-T = L_P L_P^T                    (positive definite iff V is; factored beside W1 in lock step)
+ *   W_a = (1 - a) L_P^-T L_P^-1 + a W1 = L_Wa L_Wa^T
+ *   V_new = (L L_Wa^-T)(L L_Wa^-T)^T
+ *   m_new = (1 - a) m + a L W1^-1 aL^T u              (u as in gpfit_estep_projected; equal to :1436, because
+ *                                                     m - (I + K~ G)^-1 (m - K~ g) = (I + K~ G)^-1 K~ (G m + g))
+ * Cholesky factorisations only: V_new is exactly symmetric and positive definite.  alpha = 1 gives the update of
+ * gpfit_estep_projected (W_a = W1 then; V is still factored and must be positive definite).
+ * Arguments as gpfit_estep_projected, without the moments, plus Linv[nb][ldli] = L^-1 and V[nb][ldv_in] = the current
+ * V (symmetric); of both only the lower triangle is read.  V_new may be V itself (V is read before V_new is written).
+ * Runs on the caller's stream, allocates nothing, synchronises once.
+ * Returns 0, or a positive LAPACK info when a factorisation fails; *info_v_host (may be NULL) tells which one:
+ *   *info_v_host != 0 (= the return value): V is not positive definite;
+ *   *info_v_host == 0: I + L^T G L (or, behind it, W_a) is not positive definite -- NaN or negative rates.
+ * gpfit_last_error() names the matrix as well.  The outputs are meaningless after a failure.
+ * -3 (before the context or any operand is read): a null pointer, N or nb <= 0, a leading dimension < nb, alpha not
+ * finite or outside (0, 1]; then: a problem above the context capacity, a pending asynchronous evaluation.
+ * *info_v_host is written only when the call ran. */
+int gpfit_estep_projected_damped(gpfit_ctx* ctx, void* stream, const double* a, int64_t lda, const double* aL,
+                                 int64_t ldal, const double* L, int64_t ldl, const double* Linv, int64_t ldli,
+                                 const double* V, int64_t ldv_in, int64_t N, int64_t nb, const double* r, const double* m,
+                                 const double* f, double logA, double alpha, double* m_new, double* V_new, int64_t ldv,
+                                 int* info_v_host);
+
 /* One pass over the training points for the firing-rate parameters (mean_f_given_lambda_moments
  * utils.py:1126-1141, lambda0_given_logA :1215-1229, compute_loglikelihood with
  * compute_grad_for_f_params :1243-1255).  out_host[7]: lambda0 used (closed form if requested,
