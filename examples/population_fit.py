@@ -18,7 +18,10 @@ cell is printed as (that time - the time between handing a chain in and getting 
 the phase, plus the cell's share of the group calls; the M-step time per cell by the same accounting with the closure
 calls.  The chain and closure calls of fits in the full-rank regime are counted apart (``last_full_group_sizes``,
 ``last_full_closure_group_sizes``) and enter the same two figures; ``GPFIT_FULL_RANK_GROUPS=0`` makes such fits issue their
-own calls, one fit after the other."""
+own calls, one fit after the other.  The loss evaluations of the wave (``last_loss_group_sizes``) are printed by units
+carried as well, with the cell's share of those calls: under ``varGP_cells`` a fit's "computing Loss" contains its wait
+for the wave, and ``--loop`` shows what one fit's evaluations cost (``GPFIT_FUSED_LOSS=0``: the composite, every fit on its
+own)."""
 import argparse
 import contextlib
 import io
@@ -117,6 +120,12 @@ for rep in range(max(1, args.repeat)):
         line += (f" | closure calls by units carried {chist}, full-rank closure calls {fchist}, {sum(csecs):.3f} s in all; in "
                  f"the rendezvous {in_closure:.3f}s per cell -> M-step time per cell {mstep:.3f}s (own part {ph['M-steps'] - in_closure:.3f} + share of the calls "
                  f"{sum(csecs) / args.cells:.3f})")
+        # (a fit's "computing Loss" contains its wait for the wave; the time in the rendezvous also covers the loss
+        # before the first iteration, which varGP does not count in that phase: only the calls' share is a cost)
+        lsizes, lsecs = v.last_loss_group_sizes, v.last_loss_call_seconds
+        lhist = {n: lsizes.count(n) for n in sorted(set(lsizes))}
+        line += (f" | loss calls by units carried {lhist}, {sum(lsecs):.4f} s in all -> share of the loss calls per cell "
+                 f"{sum(lsecs) / args.cells:.4f}s (in the rendezvous {v.last_seconds_in_loss_call / args.cells:.4f}s per cell)")
     print(line + (f" | FAILED cells {failed}" if failed else ""), flush=True)
 kept = [int(fit["B"].shape[1]) for fit, _ in fits]
 regime = "sparse" if args.ntilde < args.n else ("truncated rank" if max(kept) < args.ntilde else "full rank")

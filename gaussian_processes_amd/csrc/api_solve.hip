@@ -295,7 +295,133 @@ static int proj_step_cov(const ProjStep& w, double* Li) {
   return product(w.lane, {w.npc, w.npc, w.npc}, 1.0, plain(w.M(w.P)), trans(w.M(w.P)), into_lower(w.M(w.V)));
 }
 
+static_assert(GPFIT_ELBO_MAX_UNITS == CHAIN_MAXU, "the header states the units of a group call");
+static_assert(2 * CHAIN_MAXU <= GEMM_MAXB, "two chains per unit in one lock-step batch");
+
+// ONE body for gpfit_elbo (the group of one) and gpfit_elbo_batch (header: gpfit_elbo).  Per unit: V packed into the V
+// chain's work matrix and, unless log|K~| is given, K~ into the K chain's; all chains of all units are one lock-step
+// recursion that forms no full inverse; the two passes over the caller's arrays (elbo_rows_group, elbo_quad_group) read
+// them where they are.  Partials: upart (the quadratic forms, 2 ceil(nb / 8) <= np / 4 doubles) and vpart (the three
+// likelihood sums, 96 doubles); both hold at least 2 np doubles at any capacity.  Everything on the caller's stream, one
+// synchronisation; a unit's launches, partials and sums do not depend on the other units: the same bits alone and in
+// any group.
+struct ElboCall {
+  // (in the order of the entry points' argument lists)
+  const char* name; gpfit_ctx* const* ctxs; int n_units; void* stream;
+  const double *const *m, *const *V; const int64_t* ldv; const double* const* K; const int64_t* ldk;
+  const double* const* Kinv; const int64_t *ldki, *nb; const int* known; const double* logdet_K;
+  const double *const *r, *const *f, *const *lam_m; int64_t N; const double *logA, *lambda0;
+  double* out_host; int* info_host;
+};
+static int elbo_group_impl(const ElboCall& a) {
+  const Refuse refuse{a.name};
+  gpfit_ctx* const* ctxs = a.ctxs;
+  const int nu = a.n_units;
+  // every refusal of the call, before anything is enqueued; those of the arguments before any context is read
+  if (nu < 1 || nu > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+  if (!ctxs || !a.m || !a.V || !a.ldv || !a.Kinv || !a.ldki || !a.nb || !a.known || !a.logdet_K || !a.r || !a.f || !a.lam_m ||
+      !a.logA || !a.lambda0 || !a.out_host || !a.info_host)
+    return refuse("bad argument: null table or output");
+  if (a.N <= 0 || a.N > INT32_MAX) return refuse("bad argument: N must be positive");
+  auto K_of = [&](int u) { return a.K ? a.K[u] : nullptr; };
+  for (int u = 0; u < nu; ++u) {
+    const std::string unit = unit_prefix(nu, u);
+    if (!ctxs[u] || !a.m[u] || !a.V[u] || !a.Kinv[u] || !a.r[u] || !a.f[u] || !a.lam_m[u])
+      return refuse(unit + "bad argument: null context or operand");
+    if (a.nb[u] <= 0) return refuse(unit + "bad argument: nb must be positive");
+    if (!a.known[u] && !K_of(u)) return refuse(unit + "bad argument: K is needed unless logdet_K_known is set");
+    if (a.ldv[u] < a.nb[u] || a.ldki[u] < a.nb[u] || (!a.known[u] && (!a.ldk || a.ldk[u] < a.nb[u])))
+      return refuse(unit + "bad argument: a leading dimension is smaller than nb");
+    // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+    if (round_up(a.nb[u], TILE) != round_up(a.nb[0], TILE))
+      return refuse(unit + "round_up(nb, 128) = " + std::to_string(round_up(a.nb[u], TILE)) + " differs from unit 0's " +
+                    std::to_string(round_up(a.nb[0], TILE)) + " (group the units by padded size)");
+  }
+  for (int u = 0; u < nu; ++u) {
+    const std::string unit = unit_prefix(nu, u);
+    if (const char* why = unit_context_refusal(ctxs, u)) return refuse(unit + why);
+    if (round_up(a.nb[u], TILE) > ctxs[u]->np_cap) return refuse(unit + "round_up(nb, 128) is larger than the context capacity");
+  }
+  DeviceGuard device_guard(ctxs[0]->device);
+  hipStream_t s = (hipStream_t)a.stream;
+  const Units U = Units::all(ctxs, nu);
+  Units UK;   // the units whose K~ is factored here
+  for (int u = 0; u < nu; ++u) {
+    if (!a.known[u]) UK.add(ctxs[u], u);
+    ctxs[u]->lv_valid = false; ctxs[u]->lv32_valid = false;   // the V work matrices are reused
+  }
+  const int n = (int)a.N, npc = (int)round_up(a.nb[0], TILE);
+  const int64_t ld = npc;
+  const auto nb_of = [&](int u) { return (int)a.nb[u]; };
+  const PerUnit<int> nbt = U.table<int>(nb_of);
+  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
+  // the likelihood sums first: its kernel also zeroes the info words
+  GP_TRY(launch_elbo_rows_group(nu, U.from(a.r), U.from(a.f), U.from(a.lam_m), n, U.of(&gpfit_ctx::vpart), U.of(&gpfit_ctx::info), s));
+  GP_TRY(launch_elbo_quad_group(nu, U.from(a.Kinv), U.from(a.ldki), U.from(a.V), U.from(a.ldv), U.from(a.m), nbt,
+                                U.of(&gpfit_ctx::upart), s));
+  GP_TRY(launch_pack_lower_group(nu, U.from(a.V), U.from(a.ldv), nbt, U.of(&gpfit_ctx::Vbuf), ld, npc, s));
+  if (UK.cnt)
+    GP_TRY(launch_pack_lower_group(UK.cnt, UK.from(a.K), UK.from(a.ldk), UK.table<int>(nb_of), UK.of(&gpfit_ctx::Kbuf), ld, npc, s));
+  CholBatchT<double> cb;
+  for (int i = 0; i < U.cnt; ++i) add_v_chain(cb, U.ctx[i]);
+  for (int i = 0; i < UK.cnt; ++i) add_k_chain(cb, UK.ctx[i]);
+  cb.ld = ld;
+  GP_TRY(potrf_lockstep(cb, 0, npc, 0u, lane));   // the factors only: no full inverse of either
+  // log|V| and log|K~| (a unit whose log|K~| is given reads its V factor twice; the finishing launch takes the given one)
+  GP_TRY(launch_logdet_pair_group(nu, U.cof(&gpfit_ctx::LVbuf), U.scal(S_LOGDET_V),
+                                  U.table<const double*>([&](int u) { return a.known[u] ? ctxs[u]->LVbuf : ctxs[u]->Lbuf; }),
+                                  U.scal(S_LOGDET_K), ld, nbt, s));
+  ElboFinishT fin{};
+  fin.n_units = nu; fin.nb = nbt;
+  fin.known = U.table<int>([&](int u) { return a.known[u] ? 1 : 0; });
+  fin.quad_part = U.cof(&gpfit_ctx::upart); fin.rows_part = U.cof(&gpfit_ctx::vpart);
+  fin.logdet_V = U.table<const double*>([&](int u) { return ctxs[u]->scal + S_LOGDET_V; });
+  fin.logdet_K = U.table<const double*>([&](int u) { return ctxs[u]->scal + S_LOGDET_K; });
+  fin.info_V = U.table<const int*>([&](int u) { return ctxs[u]->info + INFO_V; });
+  fin.info_K = U.table<const int*>([&](int u) { return ctxs[u]->info + INFO_K; });
+  fin.given = U.from(a.logdet_K);
+  fin.A = U.table<double>([&](int u) { return std::exp(a.logA[u]); });
+  fin.lambda0 = U.from(a.lambda0);
+  fin.out_host = U.of(&gpfit_ctx::scal_host, S_ELBO);
+  fin.info_V_host = U.of(&gpfit_ctx::info_host, INFO_V); fin.info_K_host = U.of(&gpfit_ctx::info_host, INFO_K);
+  GP_TRY(launch_elbo_finish_group(fin, s));
+  GP_HIP(hipStreamSynchronize(s));
+  for (int u = 0; u < nu; ++u) {
+    for (int i = 0; i < ELBO_OUT; ++i) a.out_host[(size_t)u * ELBO_OUT + i] = ctxs[u]->scal_host[S_ELBO + i];
+    a.info_host[2 * u] = ctxs[u]->info_host[INFO_V];
+    a.info_host[2 * u + 1] = ctxs[u]->info_host[INFO_K];
+  }
+  return 0;
+}
+
 extern "C" {
+
+int gpfit_elbo(gpfit_ctx* c, void* stream, const double* m, const double* V, int64_t ldv, const double* K, int64_t ldk,
+               const double* Kinv, int64_t ldki, int64_t nb, int logdet_K_known, double logdet_K, const double* r,
+               const double* f, const double* lam_m, int64_t N, double logA, double lambda0, double* out_host,
+               int* info_host) {
+  // the group of one (elbo_group_impl): a unit's numbers are the same alone and in any group
+  GP_TRY(elbo_group_impl({"gpfit_elbo", &c, 1, stream, &m, &V, &ldv, &K, &ldk, &Kinv, &ldki, &nb, &logdet_K_known, &logdet_K,
+                          &r, &f, &lam_m, N, &logA, &lambda0, out_host, info_host}));
+  if (info_host[0] != 0) {
+    set_error("gpfit_elbo: V is not positive definite");
+    return info_host[0];
+  }
+  if (info_host[1] != 0) {
+    set_error("gpfit_elbo: K_tilde is not positive definite");
+    return info_host[1];
+  }
+  return 0;
+}
+
+int gpfit_elbo_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* m, const double* const* V,
+                     const int64_t* ldv, const double* const* K, const int64_t* ldk, const double* const* Kinv,
+                     const int64_t* ldki, const int64_t* nb, const int* logdet_K_known, const double* logdet_K,
+                     const double* const* r, const double* const* f, const double* const* lam_m, int64_t N,
+                     const double* logA, const double* lambda0, double* out_host, int* info_host) {
+  return elbo_group_impl({"gpfit_elbo_batch", ctxs, n_units, stream, m, V, ldv, K, ldk, Kinv, ldki, nb, logdet_K_known, logdet_K,
+                          r, f, lam_m, N, logA, lambda0, out_host, info_host});
+}
 
 int gpfit_potrf_append(gpfit_ctx* c, void* stream, double* L, int64_t ldl, double* Linv, int64_t ldi, int64_t n,
                        const double* kcol, double* logdet_inout_host, int* info_host) {

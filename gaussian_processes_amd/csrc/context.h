@@ -29,7 +29,7 @@ struct gpfit_ctx {
   std::vector<hipEvent_t> side_ev;
   int side_ev_next = 0;
   double* scal = nullptr;       // device scalars [64]
-  double* scal_host = nullptr;  // pinned [64]
+  double* scal_host = nullptr;  // pinned [SCAL_HOST_COUNT]: the copy of scal, then slots only the device writes
   int* pix = nullptr;           // device [dfull_cap]
   int* pix_host = nullptr;      // pinned
   int* info = nullptr;          // device [4]
@@ -75,7 +75,7 @@ inline Lane main_lane(const gpfit_ctx* c, hipStream_t s) { return {s, c->sk_ws[0
 inline Lane side_lane(const gpfit_ctx* c) { return {c->side, c->sk_ws[1]}; }
 
 // ---- names of the numbered slots
-// gpfit_ctx::scal / scal_host (64 doubles), with who writes each
+// gpfit_ctx::scal (64 doubles) / scal_host (its copy, then the slots from 64 on), with who writes each
 enum ScalSlot {
   S_RLAM = 0, S_SUMR = 1, S_SUMF = 2,   // likelihood sums r . lam_m, sum r, sum f (launch_moments / launch_proj_moments_group)
   S_LOGDET_K = 3,                       // log|K~| (launch_logdet / launch_logdet_pair)
@@ -90,6 +90,8 @@ enum ScalSlot {
   S_APPEND = 48, S_APPEND_LAMBDA = 49,  // gpfit_potrf_append: l . l, the new diagonal entry
   S_APPEND_LOGDET = 50,                 // gpfit_potrf_append_block: 2 sum log diag L22
   S_LBFGS = 52,                         // 52-60, scal_host only: launch_fparam_lbfgs writes them directly
+  S_ELBO = 64,                          // 64-73, scal_host only (behind the copy of scal): launch_elbo_finish_group writes them directly
+  SCAL_HOST_COUNT = 80,
 };
 // gpfit_ctx::info / info_host (4 ints)
 enum InfoWord {

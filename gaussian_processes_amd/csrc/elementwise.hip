@@ -1529,6 +1529,135 @@ int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s)
   return 0;
 }
 
+// ------------------------------------------------------------------ tracked loss (gpfit_elbo, gpfit_elbo_batch)
+// unit = blockIdx.y; workgroup w owns rows w ELBO_QUAD_ROWS .. of Kinv, wave v rows 2 v and 2 v + 1 of those.  A lane
+// takes the column pairs (2 lane, 2 lane + 1) + 128 k: explicit fmas in one fixed order, so that the 16-byte loads of
+// an aligned row and the 8-byte loads of any other row feed the same arithmetic.
+__global__ __launch_bounds__(256) void elbo_quad_group_kernel(PerUnit<const double*> Kinv, PerUnit<int64_t> ldki,
+                                                              PerUnit<const double*> V, PerUnit<int64_t> ldv,
+                                                              PerUnit<const double*> m, PerUnit<int> nb, PerUnit<double*> part) {
+  __shared__ double sh[2][4];
+  const int u = blockIdx.y, n = nb[u];
+  const int r0 = blockIdx.x * ELBO_QUAD_ROWS;
+  if (r0 >= n) return;   // (the whole workgroup: the grid covers the largest unit)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double* __restrict__ mu = m[u];
+  double tr = 0.0, quad = 0.0;
+  for (int k = 0; k < ELBO_QUAD_ROWS / 4; ++k) {
+    const int i = r0 + (ELBO_QUAD_ROWS / 4) * wave + k;   // wave-uniform
+    if (i >= n) break;
+    const double* __restrict__ kr = Kinv[u] + (int64_t)i * ldki[u];
+    const double* __restrict__ vr = V[u] + (int64_t)i * ldv[u];
+    const bool aligned = (((uintptr_t)kr | (uintptr_t)vr) & 15) == 0;
+    double a = 0.0, b = 0.0;
+#pragma unroll 4
+    for (int j = 2 * lane; j < n; j += 128) {
+      double k0, k1 = 0.0, v0, v1 = 0.0, m1 = 0.0;
+      if (j + 1 < n) {
+        if (aligned) {
+          const double2 kk = *reinterpret_cast<const double2*>(kr + j), vv = *reinterpret_cast<const double2*>(vr + j);
+          k0 = kk.x; k1 = kk.y; v0 = vv.x; v1 = vv.y;
+        } else {
+          k0 = kr[j]; k1 = kr[j + 1]; v0 = vr[j]; v1 = vr[j + 1];
+        }
+        m1 = mu[j + 1];
+      } else {
+        k0 = kr[j]; v0 = vr[j];
+      }
+      a = fma(k0, v0, a); a = fma(k1, v1, a);
+      b = fma(k0, mu[j], b); b = fma(k1, m1, b);
+    }
+    a = wave_sum(a);
+    b = wave_sum(b);
+    tr += a;
+    quad = fma(mu[i], b, quad);
+  }
+  if (lane == 0) { sh[0][wave] = tr; sh[1][wave] = quad; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const double* p = sh[threadIdx.x];
+    part[u][2 * blockIdx.x + threadIdx.x] = ((p[0] + p[1]) + p[2]) + p[3];
+  }
+}
+int launch_elbo_quad_group(int n_units, PerUnit<const double*> Kinv, PerUnit<int64_t> ldki, PerUnit<const double*> V,
+                           PerUnit<int64_t> ldv, PerUnit<const double*> m, PerUnit<int> nb, PerUnit<double*> part,
+                           hipStream_t s) {
+  int nmax = 0;
+  for (int u = 0; u < n_units; ++u) nmax = std::max(nmax, nb[u]);
+  hipLaunchKernelGGL(elbo_quad_group_kernel, dim3((nmax + ELBO_QUAD_ROWS - 1) / ELBO_QUAD_ROWS, n_units), dim3(256), 0, s, Kinv,
+                     ldki, V, ldv, m, nb, part);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+// unit = blockIdx.y; workgroup b sums the b-th stretch of ceil(n / ELBO_ROWS_WG) training points
+__global__ __launch_bounds__(256) void elbo_rows_group_kernel(PerUnit<const double*> r, PerUnit<const double*> f,
+                                                              PerUnit<const double*> lam_m, int n, PerUnit<double*> part,
+                                                              PerUnit<int*> info) {
+  __shared__ double sh[17];
+  const int u = blockIdx.y, b = blockIdx.x;
+  if (b == 0 && threadIdx.x < 4) info[u][threadIdx.x] = 0;
+  const int chunk = (n + ELBO_ROWS_WG - 1) / ELBO_ROWS_WG;
+  const int64_t lo = (int64_t)b * chunk, hi = lo + chunk < n ? lo + chunk : n;
+  const double* __restrict__ ru = r[u];
+  const double* __restrict__ fu = f[u];
+  const double* __restrict__ lu = lam_m[u];
+  double rl = 0.0, sr = 0.0, sf = 0.0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+    const double ri = ru[i];
+    rl = fma(ri, lu[i], rl);
+    sr += ri;
+    sf += fu[i];
+  }
+  rl = block_sum(rl, sh);
+  sr = block_sum(sr, sh);
+  sf = block_sum(sf, sh);
+  if (threadIdx.x == 0) { part[u][3 * b] = rl; part[u][3 * b + 1] = sr; part[u][3 * b + 2] = sf; }
+}
+int launch_elbo_rows_group(int n_units, PerUnit<const double*> r, PerUnit<const double*> f, PerUnit<const double*> lam_m, int n,
+                           PerUnit<double*> part, PerUnit<int*> info, hipStream_t s) {
+  hipLaunchKernelGGL(elbo_rows_group_kernel, dim3(ELBO_ROWS_WG, n_units), dim3(256), 0, s, r, f, lam_m, n, part, info);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+// unit = blockIdx.x; threads 0 .. 4 add one list of partials each in index order, thread 0 forms the results
+__global__ __launch_bounds__(64) void elbo_finish_group_kernel(ElboFinishT g) {
+  __shared__ double sums[5];
+  const int u = blockIdx.x, t = threadIdx.x;
+  if (t < 2) {
+    const int nwg = (g.nb[u] + ELBO_QUAD_ROWS - 1) / ELBO_QUAD_ROWS;
+    const double* p = g.quad_part[u];
+    double acc = 0.0;
+    for (int w = 0; w < nwg; ++w) acc += p[2 * w + t];
+    sums[t] = acc;
+  } else if (t < 5) {
+    const double* p = g.rows_part[u];
+    double acc = 0.0;
+    for (int b = 0; b < ELBO_ROWS_WG; ++b) acc += p[3 * b + (t - 2)];
+    sums[t] = acc;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  const int info_V = *g.info_V[u], info_K = g.known[u] ? 0 : *g.info_K[u];
+  const double tr = sums[0], mkm = sums[1], rlam = sums[2], sum_r = sums[3], sum_f = sums[4];
+  const double logdet_V = *g.logdet_V[u], logdet_K = g.known[u] ? g.given[u] : *g.logdet_K[u];
+  const double loglik = g.A[u] * rlam + g.lambda0[u] * sum_r - sum_f;                     // utils.py:1243
+  const double KL = -0.5 * logdet_V + 0.5 * logdet_K + 0.5 * mkm + 0.5 * tr;               // utils.py:1326
+  double o[ELBO_OUT] = {loglik, KL, loglik - KL, logdet_V, logdet_K, mkm, tr, rlam, sum_r, sum_f};
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (info_V != 0) o[1] = o[2] = o[3] = o[4] = nan;
+  if (info_K != 0) o[1] = o[2] = o[4] = nan;
+  double* out = g.out_host[u];
+  for (int i = 0; i < ELBO_OUT; ++i) out[i] = o[i];
+  *g.info_V_host[u] = info_V;
+  *g.info_K_host[u] = info_K;
+  __threadfence_system();
+}
+int launch_elbo_finish_group(const ElboFinishT& g, hipStream_t s) {
+  hipLaunchKernelGGL(elbo_finish_group_kernel, dim3(g.n_units), dim3(64), 0, s, g);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 // dst[n][ldd] <- lower triangle of src, strict upper zeroed (triangular factor for the caller)
 __global__ void unpack_tri_kernel(const double* __restrict__ src, int64_t lds, int n, double* __restrict__ dst,
                                   int64_t ldd) {

@@ -1978,7 +1978,7 @@ int gpfit_ctx_create(int device, int64_t n_max, int64_t d_max, int64_t d_full_ma
   // pinned AND mapped into the device's address space: the group kernels read pix_host and write scal_host / info_host
   // directly (elementwise.hip: group_prepare_kernel, group_collect_kernel)
   constexpr unsigned HOST_FLAGS = hipHostMallocMapped | hipHostMallocPortable;
-  GP_HIP(hipHostMalloc((void**)&c->scal_host, 64 * sizeof(double), HOST_FLAGS));
+  GP_HIP(hipHostMalloc((void**)&c->scal_host, SCAL_HOST_COUNT * sizeof(double), HOST_FLAGS));
   GP_HIP(hipHostMalloc((void**)&c->pix_host, (size_t)c->dfull_cap * sizeof(int), HOST_FLAGS));
   GP_HIP(hipHostMalloc((void**)&c->info_host, 4 * sizeof(int), HOST_FLAGS));
   GP_HIP(hipHostMalloc((void**)&c->chain_host, (size_t)CHAIN_MAX_STEPS * CHAIN_REC * sizeof(double), HOST_FLAGS));

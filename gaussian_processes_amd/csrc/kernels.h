@@ -385,4 +385,37 @@ int launch_proj_ga_group(const ProjGroupT& g, hipStream_t s);
 int launch_proj_gkb_group(const ProjGroupT& g, hipStream_t s);
 int launch_proj_gktb_group(const ProjGroupT& g, hipStream_t s);
 
+// ---- the tracked loss of an EM iteration (gpfit_elbo; gpfit_elbo_batch: the single call is the group of one): the
+// same rule -- the unit on a free grid dimension, tables by value.  Every sum is formed from per-workgroup partials that
+// a finishing launch adds in index order: no floating-point atomics, no hand-off between workgroups, and a unit's
+// partials depend on its own sizes only, hence the same bits alone and in any group.
+constexpr int ELBO_QUAD_ROWS = 8;   // rows of K~^-1 per workgroup of elbo_quad_group (two per wave)
+constexpr int ELBO_ROWS_WG = 32;    // workgroups of elbo_rows_group per unit: a fixed partition of [0, N)
+constexpr int ELBO_OUT = 10;        // doubles of a unit's result (include/gpfit_mi355x.h: gpfit_elbo)
+// One pass over the rows of Kinv[nb][ldki] beside V[nb][ldv] and m[nb], read where the caller has them:
+//   part[2 w] = sum over the rows i of workgroup w of sum_j Kinv_ij V_ij,  part[2 w + 1] = ... of m_i sum_j Kinv_ij m_j
+// (w < ceil(nb / ELBO_QUAD_ROWS)).  A row is read in pairs of columns, as one 16-byte load where the row starts on a
+// 16-byte boundary and as two 8-byte loads elsewhere, and summed in the same order either way.
+int launch_elbo_quad_group(int n_units, PerUnit<const double*> Kinv, PerUnit<int64_t> ldki, PerUnit<const double*> V,
+                           PerUnit<int64_t> ldv, PerUnit<const double*> m, PerUnit<int> nb, PerUnit<double*> part,
+                           hipStream_t s);
+// part[3 b + {0, 1, 2}] = r . lam_m, sum r, sum f over the b-th of ELBO_ROWS_WG equal stretches of [0, n); the unit's
+// four info words zeroed (the first kernel of the call)
+int launch_elbo_rows_group(int n_units, PerUnit<const double*> r, PerUnit<const double*> f, PerUnit<const double*> lam_m, int n,
+                           PerUnit<double*> part, PerUnit<int*> info, hipStream_t s);
+// The partials added in index order, the ten results formed and written with the two info words straight into pinned
+// host memory.  logdet_V / logdet_K: where launch_logdet_pair_group left them; info_V / info_K: the info words of the two
+// chains; known: log|K~| is `given` and no K~ chain ran (its info counts as 0).  NaN into slots 1-4 when V's
+// factorisation failed, into 1, 2 and 4 when K~'s did.
+struct ElboFinishT {
+  int n_units;
+  PerUnit<int> nb, known;
+  PerUnit<const double*> quad_part, rows_part, logdet_V, logdet_K;
+  PerUnit<const int*> info_V, info_K;
+  PerUnit<double> given, A, lambda0;
+  PerUnit<double*> out_host;              // [ELBO_OUT]
+  PerUnit<int*> info_V_host, info_K_host;
+};
+int launch_elbo_finish_group(const ElboFinishT& g, hipStream_t s);
+
 }  // namespace gpfit

@@ -1072,6 +1072,8 @@ def _basis_sweeps_group(units):
 
 
 _BOOKS = ("", "closure_", "full_", "full_closure_")   # the prefixes of the counters a call of the rendezvous is counted in
+_LOSS_BOOK = "loss_"                                  # ... and the book of the loss evaluations (_LOSS_KIND), kept beside them
+_ALL_BOOKS = _BOOKS + (_LOSS_BOOK,)
 
 
 class _ChainRendezvous:
@@ -1087,10 +1089,11 @@ class _ChainRendezvous:
     line searches differ from cell to cell -- so at any moment some fits wait with a closure and others with a chain.
     The rendezvous does not tell them apart: ``single``, ``group`` and ``key`` dispatch on the request's kind
     (``_REQUEST_KINDS``), and ``key`` carries the kind, so two kinds never share a call.  Only the bookkeeping looks at
-    it: per book of ``_BOOKS`` there are three counters, ``<book>group_sizes`` / ``<book>call_seconds`` /
+    it: per book of ``_ALL_BOOKS`` there are three counters, ``<book>group_sizes`` / ``<book>call_seconds`` /
     ``seconds_in_<book>call``, and a call is counted in the book of its kind -- the projected chains in ``""`` (a request
     without a kind included), the sparse and truncated closures in ``"closure_"``, and the full-rank regime in two
-    books of its own, its chains in ``"full_"`` and its closures in ``"full_closure_"``."""
+    books of its own, its chains in ``"full_"`` and its closures in ``"full_closure_"``; the loss evaluations of every
+    regime in ``"loss_"`` (``_LOSS_BOOK``)."""
 
     def __init__(self, parties, single, group, key, max_units=MAX_CHAIN_UNITS):
         self.cond = threading.Condition()
@@ -1102,7 +1105,7 @@ class _ChainRendezvous:
         self.single, self.group, self.key, self.max_units = single, group, key, int(max_units)
         self.waiting = {}      # ticket -> request
         self.results = {}      # ticket -> result or exception
-        for book in _BOOKS:
+        for book in _ALL_BOOKS:
             setattr(self, book + "group_sizes", [])        # the units of every call issued, in order
             setattr(self, book + "call_seconds", [])       # host wall time of each of them (enqueue to results)
             # summed over the fits: time between handing a request in and getting its result
@@ -1189,7 +1192,7 @@ def release_cell_workspaces():
         _IDLE_ENGINES.clear()
 
 
-_CELLS_COUNTERS = tuple(name for book in _BOOKS for name in (book + "group_sizes", book + "call_seconds",
+_CELLS_COUNTERS = tuple(name for book in _ALL_BOOKS for name in (book + "group_sizes", book + "call_seconds",
                                                               "seconds_in_" + book + "call"))
 
 
@@ -1206,8 +1209,7 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
     Fits that never chain (f_params carrying ``loglambda0``, ``estep_alpha != 1``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
     being waited for.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is the
-    error of every fit in that call.  Out of the groups stay the basis rebuilds, the loss evaluation between chain and
-    M-step and the fp32 instance.
+    error of every fit in that call.  Out of the groups stay the basis rebuilds and the fp32 instance.
 
     Projected chains (``_estep_chain``: the E-steps of an EM iteration as one device call, truncated and sparse
     regimes): ONE ``gpfit_estep_chain_batch`` call per group of equal ``(N, round_up(nb, 128), nEstep, nFparamstep,
@@ -1232,6 +1234,10 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     ``FULL_RANK_GROUPS`` off (``GPFIT_FULL_RANK_GROUPS=0``) a full-rank fit issues its chains and closures directly on
     its own workspace and keeps its turn until it ends.
 
+    Loss evaluations (``elbo_terms``: the tracked loss before the first iteration, behind every chain and after a
+    roll-back, in every regime): ONE ``gpfit_elbo_batch`` call per group of equal ``(N, round_up(nb, 128))``.  A fit
+    that has withdrawn from the wave, and any fit with ``FUSED_LOSS`` off, evaluates its loss on its own.
+
     The counters.  ``varGP_cells.last_group_sizes``: the units of every projected chain call of the last invocation, in
     order (1: the single call); ``last_call_seconds``: the host wall time of each of those calls;
     ``last_seconds_in_call``: summed over the fits, the time between handing a request in and getting its result
@@ -1239,7 +1245,8 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     for the sparse and truncated closure calls.  The calls of the full-rank regime are counted apart, in
     ``last_full_group_sizes`` / ``last_full_call_seconds`` / ``last_seconds_in_full_call`` (chains) and
     ``last_full_closure_group_sizes`` / ``last_full_closure_call_seconds`` / ``last_seconds_in_full_closure_call``
-    (closures).  The workspaces of the fits (one per concurrent fit, each of the size of a ``varGP`` workspace) are
+    (closures); the loss calls in ``last_loss_group_sizes`` / ``last_loss_call_seconds`` / ``last_seconds_in_loss_call``.
+    The workspaces of the fits (one per concurrent fit, each of the size of a ``varGP`` workspace) are
     kept for the next call; ``release_cell_workspaces()`` frees them."""
     n_fits = len(r_list)
     if len(kwargs_list) != n_fits:
@@ -1511,9 +1518,10 @@ def _all_eigenvalues_kept(K_tilde):
     Both bounds are rigorous, so ``True`` is a proof that nothing would be truncated; when they are
     inconclusive (or K~ is not numerically positive definite) the caller falls back to
     ``torch.linalg.eigh``.  Returns ``(decided_all_kept, L, Linv)``."""
-    L, Li, _, info = cholesky(K_tilde, want_inverse=True)
+    L, Li, logdet, info = cholesky(K_tilde, want_inverse=True)
     if info != 0:
         return False, None, None
+    _BASIS.factor_logdet = logdet      # log|K~| of the factor returned here (per host thread; varGP hands it to the loss)
     return _all_kept_given_factor(K_tilde, Li), L, Li
 
 
@@ -1679,6 +1687,12 @@ SWEEP_CHAIN = _os_mod.environ.get("GPFIT_SWEEP_CHAIN", "1") != "0"
 # wave's rendezvous and go out as group calls (module global read at call time; GPFIT_FULL_RANK_GROUPS=0 turns it off: such
 # a fit then issues its own calls and keeps its turn until it ends).
 FULL_RANK_GROUPS = _os_mod.environ.get("GPFIT_FULL_RANK_GROUPS", "1") != "0"
+# The tracked loss of an EM iteration (compute_loglikelihood + compute_KL_div) as one device call (elbo_terms:
+# gpfit_elbo, under varGP_cells one gpfit_elbo_batch call per wave) instead of two factorisations, the product
+# V K~^-1 and half a dozen read-backs (module global read at call time; GPFIT_FUSED_LOSS=0 turns it off).  The loss is
+# reported and never fed back: the switch changes no m_b, V_b, theta or rate parameter of a fit, only the last digits
+# of the tracked loss.
+FUSED_LOSS = _os_mod.environ.get("GPFIT_FUSED_LOSS", "1") != "0"
 # per host thread (the reference's active-learning notebook fits and scores on two threads): the route the last
 # call of _stabilised_basis took, and (N, EIGVAL_TOL) -> "full" | "truncated", which of the two rank checks to try
 # first -- a hint only, so one thread's history never changes what another thread's fit costs
@@ -2005,8 +2019,86 @@ def _closure_full_unit(q, u, out, rcs):
         return err
 
 
-# What the rendezvous of varGP_cells is given: five kinds of request, one record each.  ``book``: the counters its calls
-# are counted in (_BOOKS); ``gated``: FULL_RANK_GROUPS off keeps it out of the rendezvous; ``run_single(q)``: the single
+def _loss_prepare(r, f_mean, lambda_m, f_params, m, V, K_tilde, K_tilde_inv, logdet_K=None, engine=None):
+    """The arguments of ``elbo_terms`` as one request (kind ``"loss"``): the operands contiguous on the device, read
+    only; ``K`` is left out when ``logdet_K`` is given.  The workspace and stream are this thread's unless an engine is
+    given."""
+    r, f, lam_m, m, V, Kinv = (_cu(t) for t in (r, f_mean, lambda_m, m, V, K_tilde_inv))
+    nb = int(m.shape[0])
+    q = {"kind": "loss", "r": r, "f": f, "lam_m": lam_m, "m": m, "V": V, "Kinv": Kinv,
+         "K": None if logdet_K is not None else _cu(K_tilde), "N": int(r.shape[0]), "nb": nb,
+         "logdet_K": None if logdet_K is None else float(logdet_K), "logA": _scalar(f_params['logA']),
+         "lambda0": _scalar(_lambda0_of(f_params))}
+    q["engine"] = engine if engine is not None else get_engine(nb, 1)
+    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
+    return q
+
+
+def _loss_result(q, u, out, info):
+    """What a loss call returns for its unit ``u``: the ten numbers of ``gpfit_elbo`` and the two info words (V's,
+    K~'s)."""
+    return list(out[10 * u:10 * u + 10]), (int(info[2 * u]), int(info[2 * u + 1]))
+
+
+def _loss_run_single(q):
+    """``gpfit_elbo`` on one request.  A positive return code (a failed factorisation) is in the info words."""
+    out, info = (ctypes.c_double * 10)(), (ctypes.c_int * 2)()
+    known, K = q["logdet_K"] is not None, q["K"]
+    _lib.check(_lib.load().gpfit_elbo(q["engine"]._ctx, q["stream"], q["m"].data_ptr(), q["V"].data_ptr(), q["V"].stride(0),
+                                      None if K is None else K.data_ptr(), q["nb"] if K is None else K.stride(0),
+                                      q["Kinv"].data_ptr(), q["Kinv"].stride(0), q["nb"], 1 if known else 0,
+                                      q["logdet_K"] if known else 0.0, q["r"].data_ptr(), q["f"].data_ptr(),
+                                      q["lam_m"].data_ptr(), q["N"], q["logA"], q["lambda0"], out, info),
+               "gpfit_elbo")
+    return _loss_result(q, 0, out, info)
+
+
+def _loss_bucket_key(q):
+    """Requests with equal keys may share one ``gpfit_elbo_batch`` call: the device and stream, then what that call
+    shares between its units -- N and the padded basis size (the recursion's split, hence the bits, depend on it)."""
+    return (q["m"].device.index, q["stream"].value, q["N"], -(-q["nb"] // 128) * 128)
+
+
+def _loss_batch_raw(ctxs, qs, out=None, info=None):
+    """``gpfit_elbo_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return code and the
+    two output arrays, nothing checked here -- N is that of ``qs[0]``.  A tensor given as None goes in as a null
+    pointer, a leading dimension given as ``q["ldv"]`` / ``q["ldk"]`` / ``q["ldki"]`` replaces the tensor's."""
+    nu, q0 = len(qs), qs[0]
+    out = (ctypes.c_double * (10 * nu))() if out is None else out
+    info = (ctypes.c_int * (2 * nu))() if info is None else info
+    rc = _lib.load().gpfit_elbo_batch(
+        _ctx_table(ctxs), nu, q0["stream"], _ptr_table(qs, "m"), _ptr_table(qs, "V"), _ld_table(qs, "V", "nb", "ldv"),
+        _ptr_table(qs, "K"), _ld_table(qs, "K", "nb", "ldk"), _ptr_table(qs, "Kinv"), _ld_table(qs, "Kinv", "nb", "ldki"),
+        (ctypes.c_int64 * nu)(*[q["nb"] for q in qs]), (ctypes.c_int * nu)(*[0 if q["logdet_K"] is None else 1 for q in qs]),
+        _lib.darr([0.0 if q["logdet_K"] is None else q["logdet_K"] for q in qs]), _ptr_table(qs, "r"), _ptr_table(qs, "f"),
+        _ptr_table(qs, "lam_m"), q0["N"], _lib.darr([q["logA"] for q in qs]), _lib.darr([q["lambda0"] for q in qs]), out, info)
+    return rc, out, info
+
+
+def elbo_terms(r, f_mean, lambda_m, f_params, m, V, K_tilde, K_tilde_inv, logdet_K=None, ignore_warning=True, grouped=True):
+    """``(loglikelihood, KL_div)`` of the tracked loss -- ``compute_loglikelihood(r, f_mean, lambda_m, ., f_params)[0]``
+    and ``compute_KL_div(m, V, K_tilde, K_tilde_inv, ignore_warning=True)`` -- as ONE device call and one wait
+    (``gpfit_elbo``): V is factored for its log-determinant, ``tr(V K~^-1)`` and ``m^T K~^-1 m`` are one pass over the
+    two matrices in place of the nb^3 product, the three likelihood sums ride along.  ``logdet_K``: log|K~| where the
+    caller holds it (from ``cholesky(K_tilde)``); without it the call factors K~ beside V.  In a fit of ``varGP_cells``
+    the call is the wave's (``_submit``: one ``gpfit_elbo_batch`` call, the same bits) unless ``grouped`` is off (a
+    fit that keeps its turn: the full-rank regime with ``FULL_RANK_GROUPS`` off).  Both results are 0-d fp64
+    tensors on the device, as the two functions return them.
+
+    The composite calls are made exactly as ever, with their warnings (``ignore_warning`` is ``compute_KL_div``'s) and
+    the eigen fall-back of ``log_det``, when ``FUSED_LOSS`` is off and when a factorisation of the fused call fails."""
+    if FUSED_LOSS:
+        q = _loss_prepare(r, f_mean, lambda_m, f_params, m, V, K_tilde, K_tilde_inv, logdet_K)
+        out, info = _submit(q) if grouped else _loss_run_single(q)
+        if info == (0, 0):
+            dev = _device()
+            return (torch.tensor(out[0], dtype=TORCH_DTYPE, device=dev), torch.tensor(out[1], dtype=TORCH_DTYPE, device=dev))
+    loglikelihood = compute_loglikelihood(r, f_mean, lambda_m, lambda_m, f_params)[0]   # (lambda_var: gradients only)
+    return loglikelihood, compute_KL_div(m, V, K_tilde, K_tilde_inv, dK_tilde=None, ignore_warning=ignore_warning)
+
+
+# What the rendezvous of varGP_cells is given: five kinds of chain and closure request here and the loss below them
+# (_LOSS_KIND), one record each.  ``book``: the counters its calls are counted in (_ALL_BOOKS); ``gated``: FULL_RANK_GROUPS off keeps it out of the rendezvous; ``run_single(q)``: the single
 # entry point; ``batch(ctxs, qs)``: the batch entry point ``entry``, unchecked -- its return code, then its output
 # arrays; ``unit(q, u, *arrays)``: the result of unit u cut out of them, what run_single returns for q alone;
 # ``key(q)``: requests of one kind with equal keys may share a call; ``share``: what that means, for the error.
@@ -2035,9 +2127,16 @@ _REQUEST_KINDS = {(k.kind, k.regime): k for k in (
                  key=_closure_full_bucket_key,
                  share="the full-rank requests of one call share the stimuli's size and leading dimension, the pixel grid, "
                  "the capacity of their workspaces and the reuse_V flag"))}
+# The sixth kind, the loss evaluation of elbo_terms: every regime, a book of its own (_LOSS_BOOK).  Its record stands
+# beside the table of the chains and closures, and _request_kind finds it like theirs.
+_LOSS_KIND = _RequestKind(kind="loss", regime=None, book=_LOSS_BOOK, gated=False, run_single=_loss_run_single,
+                          entry="gpfit_elbo_batch", batch=_loss_batch_raw, unit=_loss_result, key=_loss_bucket_key,
+                          share="the requests of one call share N and the padded basis size")
 
 
 def _request_kind(q):
+    if q["kind"] == _LOSS_KIND.kind:
+        return _LOSS_KIND
     return _REQUEST_KINDS[q["kind"], q.get("regime")]
 
 
@@ -2360,14 +2459,18 @@ def varGP(x, r, **kwargs):
     chol_factor = [None]   # (L, L^-1) of the K~ in force when its basis is the identity, else None
     estep_factor = [None]  # (K~_b, its Cholesky factor): shared by the E-steps between two kernel rebuilds
     solver_state = [None]  # the subspace solver's converged block of the previous kernel matrix (warm start)
+    ktb_logdet = [None]    # (K~_b, log|K~_b|) where a factor of the K~_b in force came with its log-determinant
 
     def project(Kt, K_):
         _BASIS.factor = None
+        _BASIS.factor_logdet = None
         eigvecs_, B_, Ktb, Ktib = _stabilised_basis(Kt, start=solver_state[0])
         solver_state[0] = getattr(_BASIS, "state", None)     # the subspace solver's block, for the next EM iteration
         _BASIS.state = None
         basis_route[0] = _BASIS.route
         chol_factor[0] = _BASIS.factor if _BASIS.route == "identity" else None
+        if chol_factor[0] is not None and _BASIS.factor_logdet is not None:
+            ktb_logdet[0] = (Ktb, _BASIS.factor_logdet)      # the identity basis: K~_b is K~, factored by the all-kept proof
         _BASIS.factor = None
         if _is_identity(B_):
             Kb = K_
@@ -2387,6 +2490,15 @@ def varGP(x, r, **kwargs):
         return Mb
 
     rate_cache = [None]
+
+    def loss_now(ignore_warning=True):
+        """The tracked loss of the state in force (``elbo_terms``), with log|K~_b| where the factor of this K~_b has
+        been computed already -- by the all-kept proof behind ``project`` or for the E-steps -- so that the call factors
+        V_b only."""
+        known = ktb_logdet[0] is not None and ktb_logdet[0][0] is K_tilde_b
+        return elbo_terms(r, f_mean, lambda_m, f_params, m_b, V_b, K_tilde_b, K_tilde_inv_b,
+                          logdet_K=ktb_logdet[0][1] if known else None, ignore_warning=ignore_warning,
+                          grouped=FULL_RANK_GROUPS or not full_rank())
 
     def lambda0_and_rate():
         """``lambda0_given_logA`` (:1874, :1934) and, from the same pass over the training points, the rate at that
@@ -2443,8 +2555,7 @@ def varGP(x, r, **kwargs):
 
     lambda_m, lambda_var = moments_now()
     f_mean = mean_f_given_lambda_moments(f_params, lambda_m, lambda_var)
-    loglikelihood, _, __ = compute_loglikelihood(r, f_mean, lambda_m, lambda_var, f_params)
-    KL_div = compute_KL_div(m_b, V_b, K_tilde_b, K_tilde_inv_b, dK_tilde=None, ignore_warning=True)
+    loglikelihood, KL_div = loss_now()
     logmarginal = loglikelihood - KL_div
 
     loss_track = {k: torch.zeros(maxiter) for k in ('logmarginal', 'loglikelihood', 'KL')}
@@ -2502,11 +2613,12 @@ def varGP(x, r, **kwargs):
                         f_params['lambda0'] = lambda0_and_rate()                              # :1874
                     f_mean = rate_now()                                                         # :1877
                     if estep_factor[0] is None or estep_factor[0][0] is not K_tilde_b:
-                        L_kb, _, _, info_kb = cholesky(K_tilde_b)
+                        L_kb, _, logdet_kb, info_kb = cholesky(K_tilde_b)
                         if info_kb != 0:
                             raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info_kb})")
                         estep_factor[0] = (K_tilde_b, L_kb, matmul(KKtilde_inv_b, L_kb),
                                            Kvec - torch.sum(K_b * KKtilde_inv_b, 1))
+                        ktb_logdet[0] = (K_tilde_b, logdet_kb)
                     m_b, V_b, lambda_m, lambda_var, f_fp, chain_rec = _estep_chain(
                         r, KKtilde_inv_b, estep_factor[0][2], estep_factor[0][1], estep_factor[0][3], m_b, f_mean,
                         _scalar(f_params['logA']), nEstep, nFparamstep, V=V_b, lambda_m=lambda_m,
@@ -2565,11 +2677,12 @@ def varGP(x, r, **kwargs):
                             # (a damped fit comes here in the full-rank regime too, with a = KKtilde_inv_b = B, and
                             # keeps L^-1 beside the factor)
                             if estep_factor[0] is None or estep_factor[0][0] is not K_tilde_b:
-                                L_kb, Li_kb, _, info_kb = cholesky(K_tilde_b, want_inverse=damped)
+                                L_kb, Li_kb, logdet_kb, info_kb = cholesky(K_tilde_b, want_inverse=damped)
                                 if info_kb != 0:
                                     raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info_kb})")
                                 estep_factor[0] = (K_tilde_b, L_kb, matmul(KKtilde_inv_b, L_kb),
                                                    Kvec - torch.sum(K_b * KKtilde_inv_b, 1), Li_kb)
+                                ktb_logdet[0] = (K_tilde_b, logdet_kb)
                             if damped:
                                 # :1432-1436 as one device call; the moments follow separately (moments_now below)
                                 try:
@@ -2608,8 +2721,7 @@ def varGP(x, r, **kwargs):
 
             t0 = time.time()
             f_mean = rate_now()                                                                             # :1958
-            loglikelihood, _, __ = compute_loglikelihood(r, f_mean, lambda_m, lambda_var, f_params)
-            KL_div = compute_KL_div(m_b, V_b, K_tilde_b, K_tilde_inv_b, dK_tilde=None, ignore_warning=True)
+            loglikelihood, KL_div = loss_now()
             logmarginal = loglikelihood - KL_div
             times['loss'] += time.time() - t0
             record(iteration)
@@ -2687,8 +2799,7 @@ def varGP(x, r, **kwargs):
         eigvecs, B, K_tilde_b, K_tilde_inv_b, K_b, KKtilde_inv_b = project(K_tilde, K)
         lambda_m, lambda_var = moments_now()
         f_mean = mean_f_given_lambda_moments(f_params, lambda_m, lambda_var)
-        loglikelihood = compute_loglikelihood(r, f_mean, lambda_m, lambda_var, f_params)[0]
-        KL_div = compute_KL_div(m_b, V_b, K_tilde_b, K_tilde_inv_b, dK_tilde=None)
+        loglikelihood, KL_div = loss_now(ignore_warning=False)
         logmarginal = loglikelihood - KL_div
         last = fit_parameters['maxiter'] - 1
         loss_track['loglikelihood'][last] = _scalar(loglikelihood)

@@ -485,6 +485,49 @@ int gpfit_estep_chain_full_batch(gpfit_ctx* const* ctxs, int n_units, void* stre
                                  const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
                                  double tol_grad, double tol_change, double* rec_host);
 
+/* The tracked loss of an EM iteration (varGP utils.py:1958-1962): compute_loglikelihood (utils.py:1243) and
+ * compute_KL_div (utils.py:1318-1326) of a posterior (m, V) under K~ as ONE call with one synchronisation.
+ *   loglik = A r.lam_m + lambda0 sum r - sum f                                              A = exp(logA)
+ *   KL     = -1/2 log|V| + 1/2 log|K~| + 1/2 m^T (K~^-1 m) + 1/2 sum_ij V_ij K~^-1_ij        (no -n/2 term, :1326)
+ * tr(V K~^-1) is that elementwise sum because both matrices are symmetric: one pass over the nb^2 elements in place of
+ * the nb^3 product of :1318, with m^T K~^-1 m in the same pass.  V is factored for its log-determinant; so is K~,
+ * beside it in the same lock-step recursion, unless the caller knows log|K~| (logdet_K_known != 0: logdet_K is taken
+ * as it is and K may be NULL).  No inverse factor is formed.
+ * Device: m [nb]; V [nb][ldv], K [nb][ldk] (lower triangles read), Kinv [nb][ldki] = the caller's K~^-1, symmetric (the
+ * call does not derive it from a factor) -- V and Kinv are read where they are, no padded copy is made; r, f (the
+ * caller's rate vector), lam_m [N].  N is not bounded by the context's capacity; round_up(nb, 128) is.
+ * out_host[10]: loglik, KL, loglik - KL, log|V|, log|K~|, m^T K~^-1 m, tr(V K~^-1), r.lam_m, sum r, sum f.
+ * info_host[2]: LAPACK info of V, of K~ (0 when logdet_K_known).  A V that is not positive definite leaves NaN in
+ * slots 1-4, a K~ that is not in slots 1, 2 and 4; loglik and slots 5-9 stay valid.
+ * Every sum is formed from per-workgroup partials added in index order (no atomics): the same bits on every run.
+ * Runs on the caller's stream, allocates nothing, uses the V work matrices (a cached V factor is dropped).
+ * Returns 0, or the positive info of the failed factorisation (V's first; gpfit_last_error() names the matrix).
+ * -3, with nothing enqueued and nothing written (before any context is read): a null pointer, N or nb <= 0, a leading
+ * dimension < nb, K NULL while logdet_K_known is 0; then: a pending asynchronous evaluation, round_up(nb, 128) above
+ * the context's capacity. */
+int gpfit_elbo(gpfit_ctx* ctx, void* stream, const double* m, const double* V, int64_t ldv, const double* K, int64_t ldk,
+               const double* Kinv, int64_t ldki, int64_t nb, int logdet_K_known, double logdet_K, const double* r,
+               const double* f, const double* lam_m, int64_t N, double logA, double lambda0, double* out_host,
+               int* info_host);
+/* gpfit_elbo for 1 .. GPFIT_ELBO_MAX_UNITS independent units (cells, restarts of one cell) as ONE call: unit u runs on
+ * its own context ctxs[u] (pairwise distinct, one device) with its own m[u], V[u], K[u], Kinv[u], r[u], f[u], lam_m[u],
+ * leading dimensions, size nb[u], logdet_K_known[u] / logdet_K[u], logA[u] and lambda0[u]; N is shared.  The tables K
+ * and ldk may be NULL when every unit knows its log|K~|.  Two chains per unit at most, all in one lock-step recursion;
+ * every other stage is one launch for the group.  All units must have the same round_up(nb[u], 128) (nb[u] itself may
+ * differ): the recursion's split depends on the padded size.
+ * out_host[n_units][10], info_host[n_units][2]: as gpfit_elbo, unit by unit.  Every output of unit u has the bits it has
+ * when that unit is called alone (gpfit_elbo is this call with one unit), whatever the other units, their number and
+ * their nb; a unit whose factorisation fails stops alone.
+ * Returns 0 when the call ran, whatever the info words say; -3, with nothing enqueued and nothing written: n_units
+ * outside 1 .. 16, what gpfit_elbo refuses, different padded sizes, contexts on different devices, the same context
+ * twice. */
+#define GPFIT_ELBO_MAX_UNITS 16
+int gpfit_elbo_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* m, const double* const* V,
+                     const int64_t* ldv, const double* const* K, const int64_t* ldk, const double* const* Kinv,
+                     const int64_t* ldki, const int64_t* nb, const int* logdet_K_known, const double* logdet_K,
+                     const double* const* r, const double* const* f, const double* const* lam_m, int64_t N,
+                     const double* logA, const double* lambda0, double* out_host, int* info_host);
+
 /* The sweeps of a basis rebuild (eigtop.top_eigenpairs: the inner loop of a pass and the inputs of its Rayleigh-Ritz
  * step) as ONE call, for 1 .. GPFIT_ESTEP_CHAIN_MAX_UNITS independent units: unit u runs on its own context ctxs[u]
  * (pairwise distinct, one device) with its own K[u], Q[u], Y[u], W[u], S[u], step count m[u] and shifts sigma[u]; N, k,

@@ -1,0 +1,442 @@
+"""The fused loss on the GPU: gpfit_elbo and gpfit_elbo_batch against the numpy restatement of compute_loglikelihood and
+compute_KL_div (elbo_cases.elbo_reference, itself within 1.3e-11 of extended precision on these inputs:
+test_elbo_cpu.py) and against this module's own composite on the device; the exactness of a unit alone, strided and in
+any group; failures that stop alone; refusals that enqueue nothing; and varGP / varGP_cells with the switch on and off.
+
+Shapes (N, nb): (64, 64) below a tile, one leaf per chain; (130, 130) a ragged pad to 256, both chains recurse;
+(200, 130) N != nb; (1000, 300) padded to 384, several tiles with unequal halves and 38 workgroups of the quadratic
+pass.  The bound 1e-9 relative is the project's written bar for loss, loglik and KL."""
+import contextlib
+import copy
+import ctypes
+import functools
+import io
+import math
+import threading
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import elbo_cases as cases
+from conftest import load_golden
+from gaussian_processes_amd import synthetic as syn
+
+pytestmark = pytest.mark.gpu
+KEYS = syn.THETA_KEYS
+LOWER, UPPER = syn.limits()
+TOL = 1e-9
+SENTINEL = -12345.0
+JOIN_S = 300            # a fit thread still alive after this is a deadlock: the test fails instead of hanging
+OPERANDS = ("m", "V", "K", "Kinv", "r", "f", "lam_m")
+
+
+def T(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+
+
+@pytest.fixture(scope="module")
+def gp():
+    from gaussian_processes_amd import utils
+    return utils
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from gaussian_processes_amd import _lib
+    return _lib.load()
+
+
+@pytest.fixture(scope="module")
+def engines():
+    """Sixteen workspaces of capacity 384, shared by the tests of this file."""
+    from gaussian_processes_amd.engine import GPFitEngine
+    engs = [GPFitEngine(384, 1) for _ in range(16)]
+    yield engs
+    for e in engs:
+        e.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _case(N, nb, cond, v_kind):
+    return cases.make_elbo_case(N, nb, cond, v_kind)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(N, nb, cond, v_kind):
+    return cases.elbo_reference(_case(N, nb, cond, v_kind))
+
+
+@functools.lru_cache(maxsize=None)
+def _unit(N, nb, cond, v_kind):
+    """The case on the device, contiguous (shared between the tests, never written)."""
+    c = _case(N, nb, cond, v_kind)
+    return {**{k: T(c[k]) for k in OPERANDS}, "N": N, "nb": nb, "logA": c["logA"], "lambda0": c["lambda0"], "logdet_K": None}
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def single(lib, eng, u, ctx=None):
+    """gpfit_elbo on a unit: (rc, the ten outputs, the two info words); the outputs start as the sentinel."""
+    out, info = (ctypes.c_double * 10)(*[SENTINEL] * 10), (ctypes.c_int * 2)(-7, -7)
+    known, K = u["logdet_K"] is not None, u["K"]
+    rc = lib.gpfit_elbo(ctx if ctx is not None else eng._ctx, _stream(), u["m"].data_ptr(), u["V"].data_ptr(), u["V"].stride(0),
+                        None if K is None else K.data_ptr(), u["nb"] if K is None else K.stride(0), u["Kinv"].data_ptr(),
+                        u["Kinv"].stride(0), u["nb"], 1 if known else 0, u["logdet_K"] if known else 0.0, u["r"].data_ptr(),
+                        u["f"].data_ptr(), u["lam_m"].data_ptr(), u["N"], u["logA"], u["lambda0"], out, info)
+    return rc, list(out), list(info)
+
+
+def batch(gp, engs, units):
+    """gpfit_elbo_batch on the units, one workspace each: (rc, [ten outputs per unit], [two info words per unit])."""
+    nu = len(units)
+    out, info = (ctypes.c_double * (10 * nu))(*[SENTINEL] * (10 * nu)), (ctypes.c_int * (2 * nu))(*[-7] * (2 * nu))
+    qs = [{**u, "stream": _stream()} for u in units]
+    rc, out, info = gp._loss_batch_raw([e._ctx for e in engs[:nu]], qs, out, info)
+    return rc, [list(out[10 * i:10 * i + 10]) for i in range(nu)], [list(info[2 * i:2 * i + 2]) for i in range(nu)]
+
+
+def bits(values):
+    return [float(v).hex() for v in values]
+
+
+def rel(got, want):
+    return np.abs((np.asarray(got) - want) / want)
+
+
+@pytest.mark.parametrize("N,nb", cases.SHAPES)
+def test_every_output_matches_the_restatement(lib, engines, N, nb):
+    worst = np.zeros(10)
+    for cond in cases.CONDS:
+        for v_kind in cases.V_KINDS:
+            rc, out, info = single(lib, engines[0], _unit(N, nb, cond, v_kind))
+            err = rel(out, _reference(N, nb, cond, v_kind))
+            print(f"N {N} nb {nb} cond {cond:g} V {v_kind}: " + ", ".join(f"{s} {e:.1e}" for s, e in zip(cases.SLOTS, err)))
+            worst = np.maximum(worst, err)
+            assert rc == 0 and info == [0, 0]
+            assert err.max() < TOL, dict(zip(cases.SLOTS, err))
+    print(f"N {N} nb {nb}: worst deviation per term " + ", ".join(f"{s} {e:.1e}" for s, e in zip(cases.SLOTS, worst)))
+
+
+@pytest.mark.parametrize("N,nb", cases.SHAPES)
+def test_the_call_matches_the_composite_of_this_module(gp, lib, engines, N, nb):
+    for cond in cases.CONDS:
+        for v_kind in cases.V_KINDS:
+            u = _unit(N, nb, cond, v_kind)
+            fp = {"logA": torch.tensor(u["logA"], dtype=torch.float64), "lambda0": torch.tensor(u["lambda0"], dtype=torch.float64)}
+            loglik = gp.compute_loglikelihood(u["r"], u["f"], u["lam_m"], u["lam_m"], fp)[0]
+            KL = gp.compute_KL_div(u["m"], u["V"], u["K"], u["Kinv"])
+            rc, out, info = single(lib, engines[0], u)
+            e = rel(out[:2], np.array([float(loglik), float(KL)]))
+            print(f"N {N} nb {nb} cond {cond:g} V {v_kind}: against the composite, loglik {e[0]:.1e} KL {e[1]:.1e}")
+            assert rc == 0 and e.max() < TOL
+            # and through the public function: the fused numbers with the types of the composite
+            ll, kl = gp.elbo_terms(u["r"], u["f"], u["lam_m"], fp, u["m"], u["V"], u["K"], u["Kinv"])
+            for got, want in ((ll, loglik), (kl, KL)):
+                assert got.dtype == want.dtype and got.device == want.device and got.shape == want.shape == ()
+            assert rel([float(ll), float(kl)], np.array([float(loglik), float(KL)])).max() < TOL
+
+
+@pytest.mark.parametrize("N,nb", cases.SHAPES)
+def test_a_given_logdet_replaces_the_factorisation_of_k(lib, engines, N, nb):
+    u = _unit(N, nb, 1e4, "newton")
+    rc, factored, _ = single(lib, engines[0], u)
+    assert rc == 0
+    # the factored value handed back in, K left out: every slot has the same bits
+    rc, given, info = single(lib, engines[0], {**u, "K": None, "logdet_K": factored[4]})
+    assert rc == 0 and info == [0, 0] and bits(given) == bits(factored)
+    # any other value: slot 4 is the given one, KL follows it, nothing else moves
+    other = factored[4] + 1.0
+    rc, moved, info = single(lib, engines[0], {**u, "logdet_K": other})     # (K given as well: not read)
+    assert rc == 0 and info == [0, 0] and moved[4] == other
+    assert bits(moved[:1] + moved[3:4] + moved[5:]) == bits(factored[:1] + factored[3:4] + factored[5:])
+    assert moved[1] == -0.5 * factored[3] + 0.5 * other + 0.5 * factored[5] + 0.5 * factored[6] and moved[2] == moved[0] - moved[1]
+
+
+def _strided(u):
+    """The same numbers as views: V, K and Kinv with ld = nb + 5 inside larger matrices, m at an odd element offset."""
+    nb = u["nb"]
+    v = dict(u)
+    for k in ("V", "K", "Kinv"):
+        big = torch.full((nb + 3, nb + 5), float("nan"), dtype=torch.float64, device="cuda")
+        big[:nb, :nb] = u[k]
+        v[k] = big[:nb, :nb]
+        assert v[k].stride(0) == nb + 5
+    buf = torch.full((nb + 1,), float("nan"), dtype=torch.float64, device="cuda")
+    buf[1:] = u["m"]
+    v["m"] = buf[1:]
+    assert v["m"].data_ptr() % 16 == 8 and u["V"].data_ptr() % 16 == 0
+    return v
+
+
+@pytest.mark.parametrize("N,nb", cases.SHAPES)
+def test_strided_operands_give_the_same_bits(lib, engines, N, nb):
+    u = _unit(N, nb, 1e4, "newton")
+    rc0, contiguous, _ = single(lib, engines[0], u)
+    rc1, strided, info = single(lib, engines[0], _strided(u))
+    assert rc0 == 0 and rc1 == 0 and info == [0, 0]
+    assert bits(strided) == bits(contiguous)
+
+
+def _group_is_its_single_calls(gp, lib, engines, units):
+    alone = [single(lib, engines[-1], u) for u in units]
+    rc, outs, infos = batch(gp, engines, units)
+    assert rc == 0
+    for i, (rc1, out1, info1) in enumerate(alone):
+        assert rc1 == 0 and infos[i] == info1 == [0, 0]
+        assert bits(outs[i]) == bits(out1), (i, dict(zip(cases.SLOTS, zip(outs[i], out1))))
+
+
+def test_three_units_of_one_padded_size(gp, lib, engines):
+    """nb = 257, 300 and 384 share the padded size 384: leading blocks of the (1000, 300) cases and a 384 case of its own."""
+    big = cases.make_elbo_case(1000, 384, 1e4, "newton")
+
+    def leading(c, nb):
+        u = {k: T(c[k][:nb, :nb]) for k in ("V", "K", "Kinv")}
+        u.update(m=T(c["m"][:nb]), r=T(c["r"]), f=T(c["f"]), lam_m=T(c["lam_m"]))
+        return {**u, "N": 1000, "nb": nb, "logA": c["logA"], "lambda0": c["lambda0"], "logdet_K": None}
+    units = [leading(big, 257), leading(_case(1000, 300, 1e2, "prior"), 300), leading(big, 384)]
+    units[1]["logdet_K"] = 12.5       # one unit knows its log|K~|: two chains for the others, one for it
+    _group_is_its_single_calls(gp, lib, engines, units)
+    _group_is_its_single_calls(gp, lib, engines, units[::-1])
+
+
+def test_sixteen_units_and_a_group_of_one(gp, lib, engines):
+    kinds = [(cond, v_kind) for cond in cases.CONDS for v_kind in cases.V_KINDS]
+    units = [dict(_unit(200, 130, *kinds[i % len(kinds)])) for i in range(16)]
+    for i, u in enumerate(units):
+        u["lambda0"] = -0.3 - 0.01 * i
+        u["logA"] = 0.1 + 0.01 * i
+    _group_is_its_single_calls(gp, lib, engines, units)
+    _group_is_its_single_calls(gp, lib, engines, units[:1])
+    _group_is_its_single_calls(gp, lib, engines, units[5:7])
+
+
+def _indefinite(nb, seed):
+    """A symmetric matrix with one negative eigenvalue whose eigenvector lives in rows 256 .. only (the last tile)."""
+    rng = np.random.default_rng(seed)
+    Q1, _ = np.linalg.qr(rng.standard_normal((256, 256)))
+    Q2, _ = np.linalg.qr(rng.standard_normal((nb - 256, nb - 256)))
+    Q = np.zeros((nb, nb))
+    Q[:256, :256], Q[256:, 256:] = Q1, Q2
+    d = np.linspace(1.0, 3.0, nb)
+    d[270] = -0.5
+    M = (Q * d) @ Q.T
+    return (M + M.T) / 2
+
+
+@pytest.mark.parametrize("which", ["V", "K"])
+def test_a_failing_unit_stops_alone(gp, lib, engines, which):
+    from gaussian_processes_amd import _lib
+    good = [_unit(1000, 300, 1e2, "prior"), _unit(1000, 300, 1e4, "newton"), _unit(1000, 300, 1e8, "newton")]
+    bad = {**good[1], which: T(_indefinite(300, 3))}
+    ref = _reference(1000, 300, 1e4, "newton")
+    alone = [single(lib, engines[-1], u) for u in (good[0], good[2])]
+    rc, outs, infos = batch(gp, engines, [good[0], bad, good[2]])
+    assert rc == 0                                                 # the call ran, whatever the info words say
+    assert bits(outs[0]) == bits(alone[0][1]) and bits(outs[2]) == bits(alone[1][1]) and infos[0] == infos[2] == [0, 0]
+    nan_slots = (1, 2, 3, 4) if which == "V" else (1, 2, 4)
+    iv, ik = infos[1]
+    assert (iv > 0 and ik == 0) if which == "V" else (iv == 0 and ik > 0), infos[1]
+    assert 257 <= max(iv, ik) <= 300                               # LAPACK's info: the first pivot that is not positive
+    for s in range(10):
+        if s in nan_slots:
+            assert math.isnan(outs[1][s]), (s, outs[1])
+        elif not (which == "V" and s == 6):                        # (tr(V K~^-1) reads the replaced V)
+            assert abs(outs[1][s] - ref[s]) <= TOL * abs(ref[s]), (s, outs[1][s], ref[s])
+    assert math.isfinite(outs[1][0]) and all(math.isfinite(outs[1][s]) for s in range(5, 10))
+    # the single call: the same numbers, the positive info as its return value, the matrix named
+    rc1, out1, info1 = single(lib, engines[-1], bad)
+    assert rc1 == max(iv, ik) and info1 == infos[1] and bits(o for o in out1 if not math.isnan(o)) == bits(
+        o for o in outs[1] if not math.isnan(o))
+    assert ("V is not" if which == "V" else "K_tilde is not") in _lib.last_error() and "gpfit_elbo" in _lib.last_error()
+    # elbo_terms on the failing inputs: what the composite returns, its warnings included
+    fp = {"logA": torch.tensor(bad["logA"], dtype=torch.float64), "lambda0": torch.tensor(bad["lambda0"], dtype=torch.float64)}
+
+    def terms():
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            ll, kl = gp.elbo_terms(bad["r"], bad["f"], bad["lam_m"], fp, bad["m"], bad["V"], bad["K"], bad["Kinv"],
+                                   ignore_warning=False)
+        return float(ll), float(kl), sorted(str(w.message) for w in caught)
+    fused = terms()
+    old = gp.FUSED_LOSS
+    gp.FUSED_LOSS = False
+    try:
+        composite = terms()
+    finally:
+        gp.FUSED_LOSS = old
+    assert fused == composite and any("not posdef" in w for w in fused[2]), (fused, composite)
+
+
+def test_refusals_enqueue_nothing(gp, lib, engines):
+    from gaussian_processes_amd import _lib
+    from gaussian_processes_amd.engine import GPFitEngine
+    a, b = _unit(200, 130, 1e4, "newton"), _unit(1000, 300, 1e4, "newton")
+
+    def refused(rc, outs, what):
+        assert rc == -3 and what in _lib.last_error(), (rc, _lib.last_error())
+        assert all(o == SENTINEL for out in outs for o in out), "a refused call wrote its outputs"
+    # mixed padded sizes (256 and 384; N differs too, but the sizes are looked at first)
+    rc, outs, infos = batch(gp, engines, [{**a, "N": 1000, "r": b["r"], "f": b["f"], "lam_m": b["lam_m"]}, b])
+    refused(rc, outs, "round_up(nb, 128)")
+    assert infos == [[-7, -7], [-7, -7]] and "gpfit_elbo_batch" in _lib.last_error()
+    # the same context twice
+    rc, outs, _ = batch(gp, [engines[0], engines[0]], [a, a])
+    refused(rc, outs, "context of its own")
+    # nb above the capacity, single and in a group
+    small = GPFitEngine(128, 1)
+    try:
+        rc, out, info = single(lib, small, a)
+        refused(rc, [out], "capacity")
+        assert info == [-7, -7] and _lib.last_error().startswith("gpfit_elbo: ")
+        rc, outs, _ = batch(gp, [engines[0], small], [a, a])
+        refused(rc, outs, "capacity")
+        assert "unit 1" in _lib.last_error()
+    finally:
+        small.close()
+    # a context with a pending asynchronous evaluation
+    N, d = 128, 64
+    eng = GPFitEngine(256, d)
+    try:
+        X = T(syn.stimuli(N, d))
+        r_np, m_np = syn.cell_inputs(N)
+        V = torch.eye(N, dtype=torch.float64, device="cuda") * 0.5
+        ticket = eng.fit_eval_async(syn.theta_eval(), LOWER, UPPER, syn.grid_for(d), X, T(r_np), T(m_np), V, syn.F_PARAMS["logA"],
+                                    syn.F_PARAMS["lambda0"])
+        try:
+            rc, out, _ = single(lib, eng, a)
+            refused(rc, [out], "pending")
+            rc, outs, _ = batch(gp, [engines[0], eng], [a, a])
+            refused(rc, outs, "pending")
+        finally:
+            eng.fit_eval_finish(ticket)
+        rc, out, info = single(lib, eng, a)                        # collected: the context serves again
+        assert rc == 0 and info == [0, 0] and rel(out, _reference(200, 130, 1e4, "newton")).max() < TOL
+    finally:
+        eng.close()
+
+
+def test_n_is_not_bounded_by_the_capacity(lib, engines):
+    from gaussian_processes_amd.engine import GPFitEngine
+    fresh = GPFitEngine(384, 1)                                    # capacity exactly round_up(300, 128), N = 1000
+    try:
+        u = _unit(1000, 300, 1e4, "newton")
+        rc, out, info = single(lib, fresh, u)
+        assert rc == 0 and info == [0, 0]
+        assert rel(out, _reference(1000, 300, 1e4, "newton")).max() < TOL
+    finally:
+        fresh.close()
+
+
+# ---- varGP and varGP_cells with the switch on and off
+def vargp_args(g, X, ntilde):
+    fit_parameters = {"ntilde": ntilde, "maxiter": int(g["maxiter"]), "nEstep": int(g["nEstep"]), "nMstep": int(g["nMstep"]),
+                      "nFparamstep": int(g["nFparamstep"]), "kernfun": "acosker", "cellid": 0, "n_px_side": 8,
+                      "display_hyper": False}
+    theta = {k: torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for k, v in zip(KEYS, g["theta0"])}
+    return {"fit_parameters": fit_parameters, "xtilde": X if ntilde == X.shape[0] else X[:ntilde].clone(),
+            "hyperparams_tuple": (theta, LOWER, UPPER),
+            "f_params": {"logA": torch.tensor(syn.F_PARAMS["logA"], dtype=torch.float64),
+                         "lambda0": torch.tensor(syn.F_PARAMS["lambda0"], dtype=torch.float64)}}
+
+
+def in_a_thread(fn):
+    """fn() in a fresh host thread, joined with a bound: its result, or its exception re-raised here."""
+    box = {}
+
+    def body():
+        try:
+            with contextlib.redirect_stdout(io.StringIO()), warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                box["out"] = fn()
+        except BaseException as err:
+            box["err"] = err
+    t = threading.Thread(target=body, daemon=True)
+    t.start()
+    t.join(JOIN_S)
+    assert not t.is_alive(), "the fit thread is still running: a fit waits for one that will never arrive"
+    if "err" in box:
+        raise box["err"]
+    return box["out"]
+
+
+def _spy(monkeypatch, gp, name, calls):
+    inner = getattr(gp, name)
+
+    def wrapper(*a, **kw):
+        calls.append(name)
+        return inner(*a, **kw)
+    monkeypatch.setattr(gp, name, wrapper)
+
+
+def assert_same_state(fit, fit1, what):
+    """m_b, V_b, the theta track and the f-parameter track: the loss is never fed back."""
+    for k in ("m_b", "V_b"):
+        assert torch.equal(fit[k], fit1[k]), (what, k)
+    for group in ("theta_track", "f_par_track"):
+        for k, v in fit["values_track"][group].items():
+            assert torch.equal(v, fit1["values_track"][group][k]), (what, group, k)
+
+
+@pytest.mark.parametrize("name", ["g6_vargp_full_N128.npz", "g6_vargp_sparse_N128_nt64.npz"])
+def test_vargp_with_the_switch_on_and_off(gp, monkeypatch, name):
+    g = load_golden(name)
+    X, r = T(g["X"]), T(g["r"])
+    ntilde = int(g["ntilde"]) if "ntilde" in g else int(g["N"])
+    monkeypatch.setattr(gp, "EIGVAL_TOL", float(g["tol"]))
+    calls = []
+    for fn in ("compute_KL_div", "compute_loglikelihood", "_loss_prepare"):
+        _spy(monkeypatch, gp, fn, calls)
+    fits = {}
+    for on in (True, False):
+        monkeypatch.setattr(gp, "FUSED_LOSS", on)
+        del calls[:]
+        fit, err = in_a_thread(lambda: gp.varGP(X, r, **vargp_args(g, X, ntilde)))
+        assert not err["is_error"], err
+        recorded = len(fit["values_track"]["loss_track"]["KL"])
+        assert recorded == int(g["maxiter"])
+        if on:        # one fused call per recorded loss, no composite
+            assert calls.count("_loss_prepare") == recorded and "compute_KL_div" not in calls, calls
+            assert "compute_loglikelihood" not in calls, calls
+        else:         # the reverse
+            assert calls.count("compute_KL_div") == recorded and "_loss_prepare" not in calls, calls
+        fits[on] = fit
+    assert_same_state(fits[True], fits[False], name)
+    for k in ("logmarginal", "loglikelihood", "KL"):
+        a, b = fits[True]["values_track"]["loss_track"][k], fits[False]["values_track"]["loss_track"][k]
+        assert float(((a - b).abs() / b.abs()).max()) < 1e-6, (k, a, b)
+
+
+def test_vargp_cells_loss_calls_meet(gp, monkeypatch):
+    """Three cells on the sparse fixture's stimuli (cell 0 is the fixture's, the others have Poisson counts at its mean
+    rate): every loss call carried the three units, every fit is varGP on that cell alone, and the chains and closures
+    met as they do with the switch off."""
+    g = load_golden("g6_vargp_sparse_N128_nt64.npz")
+    X, ntilde = T(g["X"]), int(g["ntilde"])
+    rng = np.random.default_rng(17)
+    rs = [T(g["r"])] + [T(rng.poisson(np.maximum(g["r"].mean(), 0.2), g["r"].shape).astype(np.float64)) for _ in range(2)]
+    monkeypatch.setattr(gp, "EIGVAL_TOL", float(g["tol"]))
+    kwargs = [vargp_args(g, X, ntilde) for _ in rs]
+    counters = {}
+    for on in (False, True):
+        monkeypatch.setattr(gp, "FUSED_LOSS", on)
+        cells = in_a_thread(lambda: gp.varGP_cells(X, rs, copy.deepcopy(kwargs)))
+        counters[on] = {book: list(getattr(gp.varGP_cells, "last_" + book + "group_sizes")) for book in gp._ALL_BOOKS}
+    assert counters[False]["loss_"] == []
+    sizes = counters[True]["loss_"]
+    print(f"loss calls by units carried: {sizes}")
+    assert sizes and all(n == 3 for n in sizes), sizes
+    assert len(sizes) == int(g["maxiter"]) and len(gp.varGP_cells.last_loss_call_seconds) == len(sizes)
+    assert gp.varGP_cells.last_seconds_in_loss_call > 0.0
+    for book in gp._BOOKS:
+        assert counters[True][book] == counters[False][book], (book, counters)
+    for i, r in enumerate(rs):
+        alone = in_a_thread(lambda: gp.varGP(X, r, **copy.deepcopy(kwargs[i])))
+        assert not alone[1]["is_error"] and not cells[i][1]["is_error"], (alone[1], cells[i][1])
+        assert_same_state(cells[i][0], alone[0], i)
+        for k, v in cells[i][0]["values_track"]["loss_track"].items():
+            assert torch.equal(v, alone[0]["values_track"]["loss_track"][k]), (i, k)
