@@ -10,6 +10,7 @@ numbers per cell, bit for bit.
         --nfstep 4 --repeat 3                                        # the lab's shape (scripts/lab_fit_times.py's settings)
     python examples/population_fit.py --n 1024 --ntilde 1024 --d 256 --cells 16   # inducing set = training set: truncated rank
     python examples/population_fit.py --n 512 --ntilde 512 --d 64 --cells 16 --eigval-tol 1e-14   # every eigenvalue kept: full rank
+    python examples/population_fit.py --cells 4 --estep-alpha 0.5 --damped-chain   # damped E-steps, chained and grouped
 
 Per repetition it prints the wall time of all fits and, averaged over the cells, the phase times ``varGP`` reports;
 for ``varGP_cells`` also how many units each chain call and each closure call carried and how long those calls took.
@@ -21,7 +22,9 @@ calls.  The chain and closure calls of fits in the full-rank regime are counted 
 own calls, one fit after the other.  The loss evaluations of the wave (``last_loss_group_sizes``) are printed by units
 carried as well, with the cell's share of those calls: under ``varGP_cells`` a fit's "computing Loss" contains its wait
 for the wave, and ``--loop`` shows what one fit's evaluations cost (``GPFIT_FUSED_LOSS=0``: the composite, every fit on its
-own)."""
+own).  ``--estep-alpha A`` (A < 1) makes every E-step the damped update; such fits keep the host loop and run beside the
+others unless ``--damped-chain`` is given, with which their E-steps are chains again (counted with the projected chain
+calls) and meet in one group call per wave."""
 import argparse
 import contextlib
 import io
@@ -45,6 +48,11 @@ ap.add_argument("--nfstep", type=int, default=4)
 ap.add_argument("--max-units", type=int, default=16, help="fits per wave of varGP_cells")
 ap.add_argument("--repeat", type=int, default=2, help="the first repetition carries the one-time costs of the process")
 ap.add_argument("--loop", action="store_true", help="varGP cell after cell instead of varGP_cells")
+ap.add_argument("--estep-alpha", type=float, default=1.0,
+                help="fit_parameters['estep_alpha']: step size of the E-step's Newton update; below 1 the damped update")
+ap.add_argument("--damped-chain", action="store_true",
+                help="fit_parameters['estep_damped_chain']: the damped E-steps of an iteration as one device call "
+                "(utils._estep_chain_damped; under varGP_cells one group call per step size) instead of the host loop")
 ap.add_argument("--eigval-tol", type=float, default=None,
                 help="utils.EIGVAL_TOL: eigenvalues of K~ below it (relative) are dropped; 1e-14 keeps them all (full rank)")
 args = ap.parse_args()
@@ -66,6 +74,9 @@ def start(cell):
     theta = {k: torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for k, v in syn.theta0().items()}
     fp = {"ntilde": args.ntilde, "maxiter": args.maxiter, "nEstep": args.nestep, "nMstep": args.nmstep,
           "nFparamstep": args.nfstep, "kernfun": "acosker", "cellid": cell, "n_px_side": n_px, "display_hyper": False}
+    if args.estep_alpha != 1.0:
+        fp["estep_alpha"] = args.estep_alpha
+        fp["estep_damped_chain"] = args.damped_chain
     return {"fit_parameters": fp, "xtilde": X[:args.ntilde].clone(), "hyperparams_tuple": (theta, lower, upper),
             "f_params": {"logA": torch.tensor(syn.F_PARAMS["logA"], dtype=torch.float64, requires_grad=True),
                          "lambda0": torch.tensor(syn.F_PARAMS["lambda0"], dtype=torch.float64)}}

@@ -62,6 +62,10 @@ _SIGS = {
                                       i32, i32, i32, f64, f64, f64, pd]),
     "gpfit_estep_chain_full_batch": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, pd, i32, pd, i32, i32, i32,
                                            f64, f64, f64, pd]),
+    "gpfit_estep_chain_damped": (i32, [vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp,
+                                       f64, f64, i32, f64, i32, i32, i32, f64, f64, f64, pd]),
+    "gpfit_estep_chain_damped_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, pd, f64, i32, pd, i32, i32, i32, f64, f64, f64, pd]),
     "gpfit_elbo": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i32, f64, vp, vp, vp, i64, f64, f64, pd,
                          ctypes.POINTER(i32)]),
     "gpfit_elbo_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(i32), pd, vp, vp, vp, i64, pd, pd, pd,

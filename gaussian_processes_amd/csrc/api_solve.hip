@@ -186,6 +186,7 @@ struct ChainCall {
   const double* logA0; int lambda0_mode; const double* lambda0_fixed;
   int n_steps, max_iter, history_size; double lr, tol_grad, tol_change; double* rec_host;
   Lbfgs1dConfig cfg;   // (admit fills it)
+  PerUnit<const int*> full_step{};   // (the damped chain fills it: the words that turn a record's slot 10 into 2)
 
   // Every refusal of the call, before anything is enqueued.  tables: the kind's own argument tables are there;
   // operands(u): so are unit u's entries of them; sizes(u): the unit's sizes and leading dimensions are in order;
@@ -225,8 +226,9 @@ struct ChainCall {
     return g;
   }
   // THE chain loop.  Of a step the kind supplies: before_factor(step), from the first kernel of the step (the only
-  // reader of m and f in it, ahead of all of the step's writers) up to and including the factorisation; after_info(),
-  // the inputs of the commits (mo and Vw); moments(), the moments of lambda behind the update.
+  // reader of m and f in it, ahead of all of the step's writers; the damped step reads m once more there, for its
+  // blend) up to and including the factorisation -- the last one, where a step has two; after_info(), the inputs of the
+  // commits (mo and Vw); moments(), the moments of lambda behind the update.
   template <typename Before, typename After, typename Moments>
   int run(const ChainGroupT& g, Before&& before_factor, After&& after_info, Moments&& moments) const {
     DeviceGuard device_guard(ctxs[0]->device);
@@ -240,7 +242,7 @@ struct ChainCall {
       GP_TRY(launch_chain_copy_group(g, s));
       GP_TRY(launch_unpack_sym_chain_group(g, s));
       GP_TRY(moments());
-      GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s));
+      GP_TRY(launch_fparam_lbfgs_chain_group(g, step, lambda0_mode ? 1 : 0, cfg, s, full_step));
     }
     GP_TRY(launch_chain_collect_group(g, n_steps, s));
     GP_HIP(hipStreamSynchronize(s));
@@ -830,6 +832,130 @@ static int estep_chain_group_impl(ChainCall call, const double* const* a, const 
       });
 }
 
+// ONE body for gpfit_estep_chain_damped (the group of one) and gpfit_estep_chain_damped_batch: every step runs the update
+// of gpfit_estep_projected_damped, stage for stage and product for product, then the moments of the committed state,
+// inside the skeleton of ChainCall.  Per unit and step, on the 13 work matrices (all ld = npc; nothing is kept from one
+// step to the next, L^-1, L and aL are packed again from the caller's arrays):
+//   Tbuf   Y = diag(s) aL                      -> the second copy of W1 (Y is dead once W1 is formed)
+//   TmpV   the slice sums of aL^T u            -> scratch of the V chain
+//   Kbuf   W1 = I + Y^T Y, the K chain's matrix (destroyed by it)          -> aL zero-padded, for the moments
+//   Cos    the first copy of W1                -> W_a = (1 - a) P^-1 + a W1 in place, factored by the second recursion
+//   Zbuf   L^-1 packed                         -> V_new (lower tiles), the source of the gated commit
+//   Abuf   V symmetric, identity padding       -> L L_Wa^-T
+//   Wbuf   L^-1 V                              -> L packed (behind the first recursion)
+//   Vbuf   P = L^-1 V L^-T, the V chain's matrix (destroyed by it)         -> Z = aL L_Wa^-T, for the moments
+//   Lbuf / Libuf / Tmp    the K chain: W1's factor and inverse factor (read by the mean), then W_a's
+//   LVbuf / LiVbuf        the V chain: P's factor and inverse factor
+// The first recursion factors W1 and P of all units in lock step (2 x units chains).  Its info word of the K chain is
+// latched into the record, and stops the unit when non-zero, before the second recursion reports into the same word.
+// The fallback is decided on the device, per unit, by the info word of the V chain (zeroed by the step's first kernel,
+// written by the first recursion only): non-zero = V is not positive definite = this update is the full step.  Such a
+// unit keeps the full step's mean (the blend skips it), and behind the blend of W_a -- which ran for it like for the
+// others, on whatever the failed chain left -- the whole of W_a is overwritten with the second copy of W1, so that its
+// second factorisation is W1's and the group stays in lock step; its record's slot 10 reads 2.  No launch, grid or
+// operand of the other units depends on it.
+static int estep_chain_damped_group_impl(ChainCall call, const double* const* a, const int64_t* lda, const double* const* aL,
+                                         const int64_t* ldal, const double* const* L, const int64_t* ldl,
+                                         const double* const* Linv, const int64_t* ldli, const int64_t* nb, double alpha) {
+  gpfit_ctx* const* ctxs = call.ctxs;
+  const int nrows = (int)round_up(call.N, TILE);
+  if (!std::isfinite(alpha) || !(alpha > 0.0) || alpha > 1.0)
+    return Refuse{call.name}("bad argument: the step size alpha must lie in (0, 1]");
+  GP_TRY(call.admit(
+      a && lda && aL && ldal && L && ldl && Linv && ldli && nb, [&](int u) { return a[u] && aL[u] && L[u] && Linv[u]; },
+      [&](int u) {
+        return nb[u] > 0 && lda[u] >= nb[u] && ldal[u] >= nb[u] && ldl[u] >= nb[u] && ldli[u] >= nb[u] && call.ldv[u] >= nb[u];
+      },
+      [&](int u) -> std::string {
+        // the recursion's split depends on the padded size: only equal padded sizes give the bits of the single call
+        if (round_up(nb[u], TILE) != round_up(nb[0], TILE))
+          return "round_up(nb, 128) = " + std::to_string(round_up(nb[u], TILE)) + " differs from unit 0's " +
+                 std::to_string(round_up(nb[0], TILE)) + " (group the units by padded size)";
+        if (nrows > ctxs[u]->np_cap || round_up(nb[u], TILE) > ctxs[u]->np_cap) return "problem larger than the context capacity";
+        return std::string();
+      }));
+  hipStream_t s = (hipStream_t)call.stream;
+  const Units U = Units::all(ctxs, call.n_units);
+  const int nu = U.cnt, npc = (int)round_up(nb[0], TILE);
+  const int64_t ld = npc, count = (int64_t)npc * npc;
+  ChainGroupT g = call.group(nrows, npc);
+  g.nb = U.table<int>([&](int u) { return (int)nb[u]; });
+  for (int u = 0; u < nu; ++u) {
+    g.kmax = std::max(g.kmax, g.nb[u]);
+    ctxs[u]->lv_valid = false; ctxs[u]->lv32_valid = false;   // the V work matrices are reused
+  }
+  g.a = U.from(a); g.aL = U.from(aL); g.L = U.from(L); g.lda = U.from(lda); g.ldal = U.from(ldal); g.ldl = U.from(ldl);
+  // the work vectors of gpfit_estep_projected; the work matrices as laid out above (aLp stays null: no copy of aL here)
+  g.sv = U.of(&gpfit_ctx::yv); g.u = U.of(&gpfit_ctx::bv); g.t2 = U.of(&gpfit_ctx::tvec); g.z1 = U.of(&gpfit_ctx::mpad);
+  g.z = U.of(&gpfit_ctx::rpad); g.mo = U.of(&gpfit_ctx::hvec); g.Y = U.of(&gpfit_ctx::Tbuf); g.Lp = U.of(&gpfit_ctx::Wbuf);
+  g.Vw = U.of(&gpfit_ctx::Zbuf); g.part = U.of(&gpfit_ctx::TmpV); g.Zm = U.of(&gpfit_ctx::Vbuf);
+  g.W = U.of(&gpfit_ctx::Kbuf); g.Li = U.of(&gpfit_ctx::Libuf); g.trmv_part = U.of(&gpfit_ctx::trmv_part);
+  const PerUnit<const int*> info_v = U.table<const int*>([&](int u) { return ctxs[u]->info + INFO_V; });
+  call.full_step = info_v;
+  const PerUnit<double*> W1c = U.of(&gpfit_ctx::Tbuf), Wa_t = U.of(&gpfit_ctx::Cos), Lip_t = U.of(&gpfit_ctx::Zbuf),
+                         Vs_t = U.of(&gpfit_ctx::Abuf), aLp_t = U.of(&gpfit_ctx::Kbuf);
+  const PerUnit<const double*> Linv_t = U.from(Linv), Vin_t = U.table<const double*>([&](int u) { return call.V[u]; });
+  const PerUnit<int64_t> ldli_t = U.from(ldli);
+  CholBatchT<double> two, one;   // W1 and P of every unit; then W_a of every unit on the K chain's matrices
+  for (int u = 0; u < nu; ++u) {
+    add_k_chain(two, ctxs[u]);
+    add_v_chain(two, ctxs[u]);
+    add_chain(one, ctxs[u]->Cos, ctxs[u]->Lbuf, ctxs[u]->Libuf, ctxs[u]->Tmp, ctxs[u]->info + INFO_K);
+  }
+  two.ld = one.ld = ld;
+  const uint32_t all_two = (uint32_t)((1ull << (2 * nu)) - 1ull);
+  const Lane lane = main_lane(ctxs[0], s);   // every launch on the caller's stream with the leader's workspace
+  const Mat<double> Y = U.mats(&gpfit_ctx::Tbuf, ld), W = U.mats(&gpfit_ctx::Kbuf, ld), Lp = U.mats(&gpfit_ctx::Wbuf, ld),
+                    Li = U.mats(&gpfit_ctx::Libuf, ld), P = U.mats(&gpfit_ctx::Abuf, ld), Vw = U.mats(&gpfit_ctx::Zbuf, ld),
+                    Lip = U.mats(&gpfit_ctx::Zbuf, ld), Vs = U.mats(&gpfit_ctx::Abuf, ld), LiV = U.mats(&gpfit_ctx::Wbuf, ld),
+                    Pv = U.mats(&gpfit_ctx::Vbuf, ld), LiP = U.mats(&gpfit_ctx::LiVbuf, ld), Wa = U.mats(&gpfit_ctx::Cos, ld),
+                    aLp = U.mats(&gpfit_ctx::Kbuf, ld), Zm = U.mats(&gpfit_ctx::Vbuf, ld);
+  return call.run(
+      g,
+      [&](int step) -> int {
+        // m and f are updated in place: of f this kernel is the only reader in a step, of m it and the blend below, and
+        // both run before any of the step's writers (the gated copy into m, the optimiser's rate), all on one stream
+        GP_TRY(launch_estep_proj_rows_chain_group(g, step, s));
+        GP_TRY(launch_estep_proj_scale_group(g, s));
+        GP_TRY(launch_reduce_slices_group(nu, g.part, npc, nrows / 32, g.t2, npc, s));   // t2 = (a L)^T u
+        GP_TRY(product(lane, {npc, npc, nrows}, 1.0, trans(Y), plain(Y), into_lower(W)));
+        GP_TRY(launch_add_diag_group(nu, g.W, ld, npc, 1.0, s));
+        GP_TRY(launch_chain_keep2_group(nu, g.W, Wa_t, W1c, count, s));   // W1, kept twice
+        // P = L^-1 V L^-T, lower tiles, identity on the padding (positive definite iff V is); V: what the caller gave
+        // (step 0) or what the last committed step left there
+        GP_TRY(launch_pack_tri_group(nu, Linv_t, ldli_t, g.nb, Lip_t, ld, npc, s));
+        GP_TRY(launch_pack_tri_group(nu, Vin_t, g.ldv, g.nb, Vs_t, ld, npc, s));
+        GP_TRY(launch_symmetrize_group(nu, Vs_t, ld, npc, s));
+        GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(Lip)), plain(Vs), into(LiV)));
+        GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(LiV), trans(tril(Lip)), into_lower(Pv)));
+        // W1 and P in lock step, both with their full inverse factors
+        GP_TRY(potrf_lockstep(two, 0, npc, all_two, lane));
+        // W1's info word into the record (and the stop word) before the second recursion reports into the same word
+        GP_TRY(launch_chain_info_group(g, step, s));
+        // the full step's mean L W1^-1 (a L)^T u, then its blend with m (not for a unit that falls back)
+        GP_TRY(launch_trmv_lower_group(nu, g.Li, ld, npc, g.t2, g.z1, s));
+        GP_TRY(launch_trmv_lower_t_group(nu, g.Li, ld, npc, g.z1, g.z, g.trmv_part, s));
+        GP_TRY(launch_pack_lower_group(nu, g.L, g.ldl, g.nb, g.Lp, ld, npc, s));
+        GP_TRY(launch_trmv_lower_group(nu, g.Lp, ld, npc, g.z, g.mo, s));
+        GP_TRY(launch_chain_damped_mean_group(g, info_v, alpha, s));
+        // W_a = (1 - a) P^-1 + a W1 (lower tiles), P^-1 = L_P^-T L_P^-1; W1 itself where V was not positive definite
+        GP_TRY(product(lane, {npc, npc, npc}, 1.0 - alpha, trans(tril(LiP)), plain(tril(LiP)), into_lower(Wa, alpha)));
+        GP_TRY(launch_chain_damped_restore_group(nu, info_v, W1c, Wa_t, count, s));
+        return potrf_lockstep(one, 0, npc, U.chains(), lane);
+      },
+      [&]() -> int {
+        // V_new = P P^T, P = L L_Wa^-T
+        GP_TRY(product(lane, {npc, npc, npc}, 1.0, plain(tril(Lp)), trans(tril(Li)), into(P)));
+        return product(lane, {npc, npc, npc}, 1.0, plain(P), trans(P), into_lower(Vw));
+      },
+      [&]() -> int {
+        // from Z = aL L_Wa^-T and the committed mean
+        GP_TRY(launch_pad_copy_group(nu, g.aL, g.ldal, g.n, g.nb, aLp_t, ld, nrows, npc, s));
+        GP_TRY(product(lane, {nrows, npc, npc}, 1.0, plain(aLp), trans(tril(Li)), into(Zm)));
+        return launch_estep_damped_moments_chain_group(g, s);
+      });
+}
+
 // ONE body for gpfit_estep_chain_full (the group of one) and gpfit_estep_chain_full_batch.  The full-rank chain: the
 // update of gpfit_estep (full_update_factor / full_update_products) in place of the projected one, on the bookkeeping of
 // the projected chain -- a ChainGroupT with nb = n, so that the init, the info word, the gated commits of m and V, the
@@ -892,6 +1018,32 @@ int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, c
   return estep_chain_group_impl({"gpfit_estep_chain_batch", ctxs, n_units, stream, N, r, kv0, m, f, V, ldv, lam_m, lam_var, logA0,
                                  lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr, tol_grad, tol_change, rec_host},
                                 a, lda, aL, ldal, L, ldl, nb);
+}
+
+int gpfit_estep_chain_damped(gpfit_ctx* c, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
+                             const double* L, int64_t ldl, const double* Linv, int64_t ldli, int64_t N, int64_t nb,
+                             const double* r, const double* kv0, double* m, double* f, double* V, int64_t ldv, double* lam_m,
+                             double* lam_var, double logA0, double alpha, int lambda0_mode, double lambda0_fixed, int n_steps,
+                             int max_iter, int history_size, double lr, double tol_grad, double tol_change, double* rec_host) {
+  // the group of one (estep_chain_damped_group_impl): a unit's numbers are the same alone and in any group
+  return estep_chain_damped_group_impl({"gpfit_estep_chain_damped", &c, 1, stream, N, &r, &kv0, &m, &f, &V, &ldv, &lam_m, &lam_var,
+                                        &logA0, lambda0_mode, &lambda0_fixed, n_steps, max_iter, history_size, lr, tol_grad,
+                                        tol_change, rec_host},
+                                       &a, &lda, &aL, &ldal, &L, &ldl, &Linv, &ldli, &nb, alpha);
+}
+
+int gpfit_estep_chain_damped_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a,
+                                   const int64_t* lda, const double* const* aL, const int64_t* ldal, const double* const* L,
+                                   const int64_t* ldl, const double* const* Linv, const int64_t* ldli, int64_t N,
+                                   const int64_t* nb, const double* const* r, const double* const* kv0, double* const* m,
+                                   double* const* f, double* const* V, const int64_t* ldv, double* const* lam_m,
+                                   double* const* lam_var, const double* logA0, double alpha, int lambda0_mode,
+                                   const double* lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                                   double tol_grad, double tol_change, double* rec_host) {
+  return estep_chain_damped_group_impl({"gpfit_estep_chain_damped_batch", ctxs, n_units, stream, N, r, kv0, m, f, V, ldv, lam_m,
+                                        lam_var, logA0, lambda0_mode, lambda0_fixed, n_steps, max_iter, history_size, lr, tol_grad,
+                                        tol_change, rec_host},
+                                       a, lda, aL, ldal, L, ldl, Linv, ldli, nb, alpha);
 }
 
 int gpfit_estep_chain_full(gpfit_ctx* c, void* stream, const double* K, int64_t ldk, int64_t N, const double* r,

@@ -1418,17 +1418,33 @@ int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_
 
 // dst[np][ldd] <- the lower triangle of src[n][lds]: zero above the diagonal (whatever src holds there), identity on the
 // padding; every element of the np x np block is written
-__global__ void pack_tri_kernel(const double* __restrict__ src, int64_t lds, int n, double* __restrict__ dst, int64_t ldd,
-                                int np) {
+__device__ __forceinline__ void pack_tri_body(const double* __restrict__ src, int64_t lds, int n, double* __restrict__ dst,
+                                              int64_t ldd, int np) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
   if (i >= np || j >= np) return;
   double v = (i == j) ? 1.0 : 0.0;
   if (i < n && j < n) v = (j <= i) ? src[(int64_t)i * lds + j] : 0.0;
   dst[(int64_t)i * ldd + j] = v;
 }
+__global__ void pack_tri_kernel(const double* __restrict__ src, int64_t lds, int n, double* __restrict__ dst, int64_t ldd,
+                                int np) {
+  pack_tri_body(src, lds, n, dst, ldd, np);
+}
+// the same for every unit of a group: unit = blockIdx.z
+__global__ void pack_tri_group_kernel(PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
+                                      int64_t ldd, int np) {
+  const int u = blockIdx.z;
+  pack_tri_body(src[u], lds[u], n[u], dst[u], ldd, np);
+}
 
 int launch_pack_tri(const double* src, int64_t lds, int n, double* dst, int64_t ldd, int np, hipStream_t s) {
   hipLaunchKernelGGL(pack_tri_kernel, dim3((np + 255) / 256, np), dim3(256), 0, s, src, lds, n, dst, ldd, np);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+int launch_pack_tri_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
+                          int64_t ldd, int np, hipStream_t s) {
+  hipLaunchKernelGGL(pack_tri_group_kernel, dim3((np + 255) / 256, np, n_units), dim3(256), 0, s, src, lds, n, dst, ldd, np);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -1525,6 +1541,55 @@ __global__ __launch_bounds__(256) void chain_collect_group_kernel(PerUnit<ChainB
 }
 int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s) {
   hipLaunchKernelGGL(chain_collect_group_kernel, dim3(g.n_units), dim3(256), 0, s, g.blk, g.rec_host, n_steps * CHAIN_REC);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the damped step of a chain (gpfit_estep_chain_damped / _batch; kernels.h): unit = blockIdx.y.  The fallback test
+// is block-uniform: every thread reads the unit's one word of the V chain
+__global__ __launch_bounds__(256) void chain_keep2_group_kernel(PerUnit<double*> src, PerUnit<double*> d0, PerUnit<double*> d1,
+                                                                int64_t count) {
+  const int u = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const double v = src[u][i];
+  d0[u][i] = v;
+  d1[u][i] = v;
+}
+int launch_chain_keep2_group(int n_units, PerUnit<double*> src, PerUnit<double*> d0, PerUnit<double*> d1, int64_t count,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(chain_keep2_group_kernel, dim3((unsigned)((count + 255) / 256), n_units), dim3(256), 0, s, src, d0, d1, count);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+// (the expression of axpby_block_kernel: the damped mean of gpfit_estep_projected_damped, bit for bit)
+__global__ __launch_bounds__(256) void chain_damped_mean_group_kernel(PerUnit<const int*> info_v, PerUnit<double*> mo,
+                                                                      PerUnit<double*> m, PerUnit<int> nb, double a, double b) {
+  const int u = blockIdx.y;
+  if (*info_v[u] != 0) return;   // V is not positive definite: the full step's mean stays
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= nb[u]) return;
+  double* d = mo[u] + j;
+  const double* q = m[u] + j;
+  d[0] = a * d[0] + b * q[0];
+}
+int launch_chain_damped_mean_group(const ChainGroupT& g, PerUnit<const int*> info_v, double alpha, hipStream_t s) {
+  hipLaunchKernelGGL(chain_damped_mean_group_kernel, dim3((g.kmax + 255) / 256, g.n_units), dim3(256), 0, s, info_v, g.mo, g.m,
+                     g.nb, alpha, 1.0 - alpha);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+__global__ __launch_bounds__(256) void chain_damped_restore_group_kernel(PerUnit<const int*> info_v, PerUnit<double*> W1c,
+                                                                         PerUnit<double*> Wa, int64_t count) {
+  const int u = blockIdx.y;
+  if (*info_v[u] == 0) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < count) Wa[u][i] = W1c[u][i];
+}
+int launch_chain_damped_restore_group(int n_units, PerUnit<const int*> info_v, PerUnit<double*> W1c, PerUnit<double*> Wa,
+                                      int64_t count, hipStream_t s) {
+  hipLaunchKernelGGL(chain_damped_restore_group_kernel, dim3((unsigned)((count + 255) / 256), n_units), dim3(256), 0, s, info_v,
+                     W1c, Wa, count);
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -1862,14 +1927,15 @@ __device__ __forceinline__ void fparam_lbfgs_chain_body(ChainGate g, const doubl
                                                         const double* __restrict__ lam_var, const double* __restrict__ r,
                                                         int n, int lambda0_mode, double lambda0_fixed,
                                                         const Lbfgs1dConfig& cfg, double* __restrict__ f, ChainBlock* blk,
-                                                        double* __restrict__ rec, double* sh, double* hist) {
+                                                        double* __restrict__ rec, double* sh, double* hist,
+                                                        const int* full_step = nullptr) {
   if (!g.open()) return;   // the same two words in every thread: uniform
   const double logA0 = blk->logA;
   const FparamLbfgsRun o = fparam_lbfgs_run(lam_m, lam_var, r, n, logA0, lambda0_mode, lambda0_fixed, cfg, f, sh, hist);
   __syncthreads();         // every thread has read the gate and the block before thread 0 writes them
   if (threadIdx.x == 0) {
     fparam_lbfgs_store(o, rec + CR_LBFGS);
-    rec[CR_RAN] = 1.0;
+    rec[CR_RAN] = (full_step && *full_step != 0) ? 2.0 : 1.0;   // 2: the damped chain committed the full step
     if (o.res.status == 0) {
       blk->logA = o.res.x;
       blk->lambda0 = o.lambda0;
@@ -1883,13 +1949,14 @@ __global__ __launch_bounds__(1024) void fparam_lbfgs_chain_group_kernel(PerUnit<
                                                                         PerUnit<double*> lam_m, PerUnit<double*> lam_var,
                                                                         PerUnit<const double*> r, int n, int lambda0_mode,
                                                                         PerUnit<double> lambda0_fixed, Lbfgs1dConfig cfg,
-                                                                        PerUnit<double*> f, int step) {
+                                                                        PerUnit<double*> f, int step,
+                                                                        PerUnit<const int*> full_step) {
   __shared__ double sh[17];
   extern __shared__ double hist[];
   const int u = blockIdx.x;
   ChainBlock* blk = blks[u];
   fparam_lbfgs_chain_body(ChainGate{&blk->stop, info[u]}, lam_m[u], lam_var[u], r[u], n, lambda0_mode, lambda0_fixed[u], cfg,
-                          f[u], blk, &blk->rec[step][0], sh, hist);
+                          f[u], blk, &blk->rec[step][0], sh, hist, full_step[u]);
 }
 
 int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double* r, int n, double logA0,
@@ -1901,10 +1968,11 @@ int launch_fparam_lbfgs(const double* lam_m, const double* lam_var, const double
   GP_HIP(hipGetLastError());
   return 0;
 }
-int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s) {
+int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s,
+                                    PerUnit<const int*> full_step) {
   const size_t lds = 4 * (size_t)cfg.history_size * sizeof(double);
   hipLaunchKernelGGL(fparam_lbfgs_chain_group_kernel, dim3(g.n_units), dim3(1024), lds, s, g.blk, g.info, g.lam_m, g.lam_var,
-                     g.r, g.n, lambda0_mode, g.lambda0, cfg, g.f, step);
+                     g.r, g.n, lambda0_mode, g.lambda0, cfg, g.f, step, full_step);
   GP_HIP(hipGetLastError());
   return 0;
 }

@@ -314,7 +314,10 @@ int launch_unpack_sym_chain_group(const ChainGroupT& g, hipStream_t s);
 int launch_estep_proj_moments_chain_group(const ChainGroupT& g, hipStream_t s);
 // launch_fparam_lbfgs behind the gate, started at blk->logA: rec[step][0..8] <- its results and rec[step][CR_RAN] <- 1;
 // with status 0 it leaves (logA, lambda0) in the block and the rate in f, otherwise it sets the stop word
-int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s);
+// full_step (the damped chain only; null tables elsewhere): a unit whose word *full_step[u] is non-zero -- the info word of
+// its V chain: this step was committed as the full step -- gets rec[step][CR_RAN] <- 2 instead
+int launch_fparam_lbfgs_chain_group(const ChainGroupT& g, int step, int lambda0_mode, const Lbfgs1dConfig& cfg, hipStream_t s,
+                                    PerUnit<const int*> full_step = PerUnit<const int*>{});
 // the first n_steps records of every unit into its rec_host (one launch instead of a copy command per unit)
 int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s);
 // the three kernels of the full-rank step only (gpfit_estep_chain_full, gpfit_estep_chain_full_batch), unit-batched like
@@ -326,6 +329,23 @@ int launch_chain_collect_group(const ChainGroupT& g, int n_steps, hipStream_t s)
 int launch_estep_prep_chain_group(const ChainGroupT& g, int step, hipStream_t s);
 int launch_estep_build_group(const ChainGroupT& g, hipStream_t s);
 int launch_estep_full_moments_chain_group(const ChainGroupT& g, hipStream_t s);
+// the kernels of the damped step only (gpfit_estep_chain_damped, gpfit_estep_chain_damped_batch), unit-batched like the
+// rest.  info_v: each unit's info word of the V chain (P = L^-1 V L^-T), zeroed by the step's first kernel; non-zero
+// behind the first factorisation = V is not positive definite = the unit takes the full step in this update.
+//   keep2    d0, d1 <- src (count doubles each): W1 before its factorisation, for the blend and for the fallback
+//   mean     mo <- alpha mo + (1 - alpha) m over the unit's nb entries (the arithmetic of launch_axpby_block); a unit
+//            with *info_v != 0 keeps mo, the full step's mean
+//   restore  Wa <- W1c (count doubles) for a unit with *info_v != 0: nothing of the failed P chain stays in W_a
+//   moments  behind the gate: lam_m = a m (m: the committed mean), lam_var = kv0 + row norms^2 of Z = aL L_Wa^-T
+int launch_chain_keep2_group(int n_units, PerUnit<double*> src, PerUnit<double*> d0, PerUnit<double*> d1, int64_t count,
+                             hipStream_t s);
+int launch_chain_damped_mean_group(const ChainGroupT& g, PerUnit<const int*> info_v, double alpha, hipStream_t s);
+int launch_chain_damped_restore_group(int n_units, PerUnit<const int*> info_v, PerUnit<double*> W1c, PerUnit<double*> Wa,
+                                      int64_t count, hipStream_t s);
+int launch_estep_damped_moments_chain_group(const ChainGroupT& g, hipStream_t s);
+// launch_pack_tri for every unit of a group (the unit's own source, leading dimension and n)
+int launch_pack_tri_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
+                          int64_t ldd, int np, hipStream_t s);
 // the unit-batched forms of the general kernels a step uses (common sizes and leading dimensions unless per unit)
 int launch_pack_lower_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> n, PerUnit<double*> dst,
                             int64_t ldd, int np, hipStream_t s);

@@ -353,5 +353,46 @@ int launch_estep_proj_moments_chain_group(const ChainGroupT& g, hipStream_t s) {
   GP_HIP(hipGetLastError());
   return 0;
 }
+// The moments behind a damped update (gpfit_estep_chain_damped / _batch), behind each unit's gate, one wave per training
+// point: lam_m_i = a_i . m with the committed mean -- a blend, so the full step's Z_i . z1 does not give it -- and
+// lam_var_i = kv0_i + |Z_i|^2 with Z = aL L_Wa^-T.  Lane l adds columns l, l + 64, .. and the wave folds in a fixed
+// order: the same bits alone and in any group.
+__global__ __launch_bounds__(256) void estep_damped_moments_chain_group_kernel(PerUnit<ChainBlock*> blk, PerUnit<int*> info,
+                                                                                PerUnit<double*> Z, int64_t ld, PerUnit<int> nb,
+                                                                                PerUnit<const double*> a, PerUnit<int64_t> lda,
+                                                                                PerUnit<double*> m, PerUnit<const double*> kv0,
+                                                                                int n, PerUnit<double*> lam_m,
+                                                                                PerUnit<double*> lam_var) {
+  const int u = blockIdx.y;
+  const ChainGate g{&blk[u]->stop, info[u]};
+  if (!g.open()) return;
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const double* __restrict__ zrow = Z[u] + (int64_t)i * ld;
+  const double* __restrict__ arow = a[u] + (int64_t)i * lda[u];
+  const double* __restrict__ mu = m[u];
+  const int k = nb[u];
+  double s0 = 0.0, s1 = 0.0;
+  for (int j = lane; j < k; j += 64) {
+    const double v = zrow[j];
+    s0 += arow[j] * mu[j];
+    s1 += v * v;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    s0 += __shfl_down(s0, o);
+    s1 += __shfl_down(s1, o);
+  }
+  if (lane == 0) {
+    lam_m[u][i] = s0;
+    lam_var[u][i] = kv0[u][i] + s1;
+  }
+}
+int launch_estep_damped_moments_chain_group(const ChainGroupT& g, hipStream_t s) {
+  hipLaunchKernelGGL(estep_damped_moments_chain_group_kernel, dim3((g.n + 3) / 4, g.n_units), dim3(256), 0, s, g.blk, g.info,
+                     g.Zm, g.ld, g.nb, g.a, g.lda, g.m, g.kv0, g.n, g.lam_m, g.lam_var);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
 
 }  // namespace gpfit

@@ -780,6 +780,21 @@ def _estep_chain_full(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_steps
                                        lambda_m, lambda_var))
 
 
+def _estep_chain_damped(r, KKtilde_inv, aL, L, Linv, kv0, V, m, f_mean, logA0, alpha, n_steps, n_fparam_steps,
+                        lambda0_fixed=None, lambda_m=None, lambda_var=None):
+    """``n_steps`` damped E-steps between two kernel rebuilds (``_estep_projected_damped`` with step size ``alpha``, the
+    moments of lambda at the committed ``(m, V)``, then ``_fparam_lbfgs``) as ONE device call and one wait
+    (``gpfit_estep_chain_damped``).  ``V`` is the current covariance: step 0 reads it, step k what step k - 1 left.  A
+    step whose ``V`` is not positive definite takes the full Newton step on the device, as the host loop of ``varGP``
+    does, and says so in its record (slot 10 == 2).  Returns what ``_estep_chain`` returns: copies ``(m, V, lambda_m,
+    lambda_var, f, records)``, the arguments left alone; ``lambda0_fixed`` as there.  In a fit of ``varGP_cells`` the
+    device call is the wave's (``_submit``): the damped chains of equal key meet in one
+    ``gpfit_estep_chain_damped_batch``.  ``_estep_chain_damped_commit`` turns the records into f_params, the warnings of
+    the full steps and the error of the first failing step."""
+    return _submit(_chain_damped_prepare(r, KKtilde_inv, aL, L, Linv, kv0, V, m, f_mean, logA0, alpha, n_steps,
+                                         n_fparam_steps, lambda0_fixed, lambda_m, lambda_var))
+
+
 def _chain_request(kind, operands, N, nv, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m, lambda_var,
                    engine):
     """What the requests of the two chain kinds share: the fixed ``operands`` (name -> tensor, contiguous on the device),
@@ -817,6 +832,19 @@ def _chain_full_prepare(r, K_tilde, kv0, m, f_mean, logA0, n_steps, n_fparam_ste
     N = int(K.shape[0])
     return _chain_request("chain_full", {"r": r, "K": K, "kv0": kv0}, N, N, m, f_mean, logA0, n_steps, n_fparam_steps,
                           lambda0_fixed, V, lambda_m, lambda_var, engine)
+
+
+def _chain_damped_prepare(r, KKtilde_inv, aL, L, Linv, kv0, V, m, f_mean, logA0, alpha, n_steps, n_fparam_steps,
+                          lambda0_fixed=None, lambda_m=None, lambda_var=None, engine=None):
+    """The arguments of ``_estep_chain_damped`` as one request (kind ``"chain_damped"``, ``_chain_request``)."""
+    if not 0 < alpha <= 1:     # (also refuses NaN)
+        raise ValueError(f'_estep_chain_damped: the step size alpha must lie in (0, 1], got {alpha}')
+    r, a, aL, L, Linv, kv0 = (_cu(t).contiguous() for t in (r, KKtilde_inv, aL, L, Linv, kv0))
+    N, nb = a.shape
+    q = _chain_request("chain_damped", {"r": r, "a": a, "aL": aL, "L": L, "Linv": Linv, "kv0": kv0}, N, nb, m, f_mean, logA0,
+                       n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m, lambda_var, engine)
+    q["nb"], q["alpha"] = int(nb), float(alpha)
+    return q
 
 
 def _chain_rec_array(q, n_units=1):
@@ -860,6 +888,46 @@ def _chain_full_run_single(q):
                                                   *_FPARAM_LBFGS, rec),
                "gpfit_estep_chain_full")
     return _chain_result(q, 0, rec)
+
+
+def _chain_damped_run_single(q):
+    """``gpfit_estep_chain_damped`` on one request."""
+    rec = _chain_rec_array(q)
+    fixed = q["lambda0_fixed"] is not None
+    a, aL, L, Linv, V = q["a"], q["aL"], q["L"], q["Linv"], q["V"]
+    _lib.check(_lib.load().gpfit_estep_chain_damped(
+        q["engine"]._ctx, q["stream"], a.data_ptr(), a.stride(0), aL.data_ptr(), aL.stride(0), L.data_ptr(), L.stride(0),
+        Linv.data_ptr(), Linv.stride(0), q["N"], q["nb"], q["r"].data_ptr(), q["kv0"].data_ptr(), q["m"].data_ptr(),
+        q["f"].data_ptr(), V.data_ptr(), V.stride(0), q["lam_m"].data_ptr(), q["lam_var"].data_ptr(), q["logA0"], q["alpha"],
+        1 if fixed else 0, q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"], q["nfp"], *_FPARAM_LBFGS, rec),
+               "gpfit_estep_chain_damped")
+    return _chain_result(q, 0, rec)
+
+
+def _chain_damped_bucket_key(q):
+    """Requests with equal keys may share one ``gpfit_estep_chain_damped_batch`` call: the key of ``"chain"`` and the
+    step size, which that call has one of."""
+    return _chain_bucket_key(q) + (q["alpha"],)
+
+
+def _chain_damped_batch_raw(ctxs, qs, rec=None):
+    """``gpfit_estep_chain_damped_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return
+    code and the records, nothing checked here -- the shared arguments are those of ``qs[0]``, except that requests
+    which disagree on the step size have none (NaN, which the entry point refuses).  A tensor given as None goes in as a
+    null pointer; ``rec``: the caller's array instead of a new one."""
+    q0 = qs[0]
+    fixed = q0["lambda0_fixed"] is not None
+    rec = _chain_rec_array(q0, len(qs)) if rec is None else rec
+    alpha = q0["alpha"] if all(q["alpha"] == q0["alpha"] for q in qs) else float("nan")
+    rc = _lib.load().gpfit_estep_chain_damped_batch(
+        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "a"), _ld_table(qs, "a", "nb"), _ptr_table(qs, "aL"),
+        _ld_table(qs, "aL", "nb"), _ptr_table(qs, "L"), _ld_table(qs, "L", "nb"), _ptr_table(qs, "Linv"),
+        _ld_table(qs, "Linv", "nb"), q0["N"], (ctypes.c_int64 * len(qs))(*[q["nb"] for q in qs]), _ptr_table(qs, "r"),
+        _ptr_table(qs, "kv0"), _ptr_table(qs, "m"), _ptr_table(qs, "f"), _ptr_table(qs, "V"), _ld_table(qs, "V", "nb"),
+        _ptr_table(qs, "lam_m"), _ptr_table(qs, "lam_var"), _lib.darr([q["logA0"] for q in qs]), alpha, 1 if fixed else 0,
+        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], *_FPARAM_LBFGS,
+        rec)
+    return rc, rec
 
 
 def _chain_bucket_key(q):
@@ -962,6 +1030,17 @@ def _estep_chain_group(units, n_steps, n_fparam_steps):
     for it, bit for bit: a unit that fails stops alone."""
     return _units_group("_estep_chain_group", units, lambda us: (max(max(u["KKtilde_inv"].shape) for u in us),),
                         lambda **u: _chain_prepare(n_steps=n_steps, n_fparam_steps=n_fparam_steps, **u))
+
+
+def _estep_chain_damped_group(units, alpha, n_steps, n_fparam_steps):
+    """``_estep_chain_damped`` for several independent units as ONE device call (``gpfit_estep_chain_damped_batch``).
+    ``units``: one dict per unit with the arguments of ``_estep_chain_damped`` by name (``r``, ``KKtilde_inv``, ``aL``,
+    ``L``, ``Linv``, ``kv0``, ``V``, ``m``, ``f_mean``, ``logA0`` and optionally ``lambda0_fixed``, ``lambda_m``,
+    ``lambda_var``); the step size ``alpha`` is the call's.  1 .. 16 units with the same number of training points and the
+    same ``round_up(nb, 128)``, all with or all without ``lambda0_fixed``.  Returns, per unit, what ``_estep_chain_damped``
+    returns for it, bit for bit: a unit that fails stops alone, a unit that takes the full step takes it alone."""
+    return _units_group("_estep_chain_damped_group", units, lambda us: (max(max(u["KKtilde_inv"].shape) for u in us),),
+                        lambda **u: _chain_damped_prepare(alpha=alpha, n_steps=n_steps, n_fparam_steps=n_fparam_steps, **u))
 
 
 def _estep_chain_full_group(units, n_steps, n_fparam_steps):
@@ -1207,14 +1286,18 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     of equal key (``_REQUEST_KINDS``, ``_request_bucket_key``); two kinds never share a call.  Each cell's numbers are
     those of ``varGP`` on its own, bit for bit.  Between two calls the fits of a wave take turns, one running at a
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
-    Fits that never chain (f_params carrying ``loglambda0``, ``estep_alpha != 1``, ``GPFIT_ESTEP_CHAIN=0``) run beside the others without
-    being waited for.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is the
+    Fits that never chain (f_params carrying ``loglambda0``, ``estep_alpha != 1`` without the damped chain,
+    ``GPFIT_ESTEP_CHAIN=0``) run beside the others without being waited for.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is the
     error of every fit in that call.  Out of the groups stay the basis rebuilds and the fp32 instance.
 
     Projected chains (``_estep_chain``: the E-steps of an EM iteration as one device call, truncated and sparse
     regimes): ONE ``gpfit_estep_chain_batch`` call per group of equal ``(N, round_up(nb, 128), nEstep, nFparamstep,
     lambda0 mode)`` -- the small kernels and the bottom of the Cholesky recursions cost one launch for the group
     instead of one per cell.
+
+    Damped chains (``_estep_chain_damped``: ``estep_alpha != 1`` with ``DAMPED_CHAIN`` or the fit's
+    ``estep_damped_chain`` on, every regime): ONE ``gpfit_estep_chain_damped_batch`` call per group of equal key of the
+    projected chains and equal ``alpha``; counted with the projected chains.
 
     Full-rank chains (``_estep_chain_full``: inducing set = training set, every eigenvalue kept, identity basis): ONE
     ``gpfit_estep_chain_full_batch`` call per group of equal ``(N, nEstep, nFparamstep, lambda0 mode)``; they never
@@ -1323,6 +1406,25 @@ def _estep_chain_commit(records, f_params):
             raise ValueError(f'Nan in f_mean during f param update in Estep, closure has been called {status} times in '
                              f'estep {k} iteration.')                                                        # :1923
     return records[-1]
+
+
+_FULL_STEP_WARNING = ('varGP: V_b is not positive definite in E-step {} of iteration {}; this update takes the full Newton '
+                      'step (alpha = 1)')
+
+
+def _estep_chain_damped_commit(records, f_params, iteration, full_steps):
+    """``_estep_chain_commit`` for the records of ``_estep_chain_damped`` in EM iteration ``iteration``: a record whose
+    slot 10 reads 2 was committed as the full Newton step because V_b was not positive definite -- it raises the warning
+    the host loop raises for that update and counts in ``full_steps[0]``; the warnings go in step order and precede the
+    error of a later step (behind a failing step every record is zero).  Returns the last record."""
+    committed = []
+    for k, rec in enumerate(records):
+        if rec[10] == 2:
+            warnings.warn(_FULL_STEP_WARNING.format(k, iteration))
+            full_steps[0] += 1
+            rec = list(rec[:10]) + [1.0] + list(rec[11:])
+        committed.append(rec)
+    return _estep_chain_commit(committed, f_params)
 
 
 def _estep_chain_full_commit(records, f_params, f_mean):
@@ -1679,6 +1781,12 @@ EIGTOP_BASIS = _os_mod.environ.get("GPFIT_EIGTOP_BASIS", "subspace")
 # _estep_chain_full in the full-rank regime with the identity basis) instead of two calls and two waits per update (module global read at call time; GPFIT_ESTEP_CHAIN=0 turns it off).  A = exp(logA)
 # is then the device's exp, not the host's: a fit may differ from the loop's by rounding.
 ESTEP_CHAIN = _os_mod.environ.get("GPFIT_ESTEP_CHAIN", "1") != "0"
+# The nEstep DAMPED updates of an EM iteration (fit_parameters['estep_alpha'] != 1) as one device call
+# (_estep_chain_damped) instead of the host loop around _estep_projected_damped.  Opt-in (module global read at call
+# time; GPFIT_DAMPED_CHAIN=1 turns it on, fit_parameters['estep_damped_chain'] overrides it for one fit): off, nothing in a
+# fit changes.  On, A = exp(logA) is the device's exp and the moments come from the chain's own kernels, so a fit may
+# differ from the loop's by rounding.
+DAMPED_CHAIN = _os_mod.environ.get("GPFIT_DAMPED_CHAIN", "0") not in ("", "0")
 # The sweeps of a pass of the subspace iteration as one device call (_basis_sweeps) instead of one wait per sweep (module
 # global read at call time; GPFIT_SWEEP_CHAIN=0 turns it off).  The call has the bits of the loop, so the switch changes
 # no number of a fit.
@@ -2134,9 +2242,20 @@ _LOSS_KIND = _RequestKind(kind="loss", regime=None, book=_LOSS_BOOK, gated=False
                           share="the requests of one call share N and the padded basis size")
 
 
+# The seventh kind, the damped chain (_estep_chain_damped).  Its record stands beside the table as well: the table's own
+# five are pinned by name and number.  Its calls are counted in book "" beside the other projected chains.
+_DAMPED_CHAIN_KIND = _RequestKind(kind="chain_damped", regime=None, book="", gated=False, run_single=_chain_damped_run_single,
+                                  entry="gpfit_estep_chain_damped_batch", batch=_chain_damped_batch_raw, unit=_chain_result,
+                                  key=_chain_damped_bucket_key,
+                                  share="the requests of one call share N, the padded basis size, the step size alpha, the "
+                                  "number of steps and the optimiser's settings")
+
+
 def _request_kind(q):
     if q["kind"] == _LOSS_KIND.kind:
         return _LOSS_KIND
+    if q["kind"] == _DAMPED_CHAIN_KIND.kind:
+        return _DAMPED_CHAIN_KIND
     return _REQUEST_KINDS[q["kind"], q.get("regime")]
 
 
@@ -2378,7 +2497,8 @@ def varGP(x, r, **kwargs):
     (``gpfit_estep_chain_full``: the update of ``gpfit_estep``, the moments and the rate-parameter optimiser,
     ``nEstep`` times, with one wait); otherwise the same steps run in the reference's projected formulation on
     the GPU primitives, the E-steps again as one call (``gpfit_estep_chain``).  The host loop around single
-    updates stays where a chain does not apply: ``f_params`` carrying ``loglambda0``, ``estep_alpha != 1``, more than 1024 E-steps,
+    updates stays where a chain does not apply: ``f_params`` carrying ``loglambda0``, ``estep_alpha != 1`` (unless the
+    damped chain is switched on, below), more than 1024 E-steps,
     ``GPFIT_ESTEP_CHAIN=0``, and the full-rank regime with a square basis that is not the identity (the ``eigh``
     route keeping every eigenvalue), which rotates by ``B`` around every update.
 
@@ -2393,7 +2513,12 @@ def varGP(x, r, **kwargs):
     * ``fit_parameters['estep_alpha']`` (default 1: nothing changes) in (0, 1): every E-step takes the damped Newton
       update (``Estep``'s alpha, ``gpfit_estep_projected_damped``) in the host loop, in every regime.  An update whose
       reprojected ``V_b`` is not positive definite takes the full step instead, with a warning;
-      ``fit_model['estep_full_steps']`` (present only then) counts them."""
+      ``fit_model['estep_full_steps']`` (present only then) counts them.
+    * ``fit_parameters['estep_damped_chain']`` (default: the module's ``DAMPED_CHAIN``, off unless
+      ``GPFIT_DAMPED_CHAIN=1``): with ``estep_alpha != 1``, ``f_params`` carrying ``lambda0``, at most 1024 E-steps and
+      ``ESTEP_CHAIN`` on, the damped E-steps of an EM iteration are one device call (``_estep_chain_damped``,
+      ``gpfit_estep_chain_damped``) in every regime; the full step for a ``V_b`` that is not positive definite is taken
+      on the device, with the same warning and count.  Off, nothing in a fit changes."""
     import time
     start_time_before_init = time.time()
     err_dict = {'is_error': False, 'error_message': None}
@@ -2440,8 +2565,11 @@ def varGP(x, r, **kwargs):
         raise ValueError(f"varGP: fit_parameters['estep_alpha'] must lie in (0, 1], got {estep_alpha}")
     damped = estep_alpha != 1
     estep_full_steps = [0]   # damped E-steps that took the full step because the reprojected V_b was not positive definite
+    # the damped updates of an iteration as one device call (opt-in: DAMPED_CHAIN, or this fit's own switch), every regime
+    damped_chain = bool(damped and fit_parameters.get('estep_damped_chain', DAMPED_CHAIN) and ESTEP_CHAIN
+                        and 'lambda0' in f_params and 'loglambda0' not in f_params and nEstep <= CHAIN_MAX_STEPS)
     if (not ESTEP_CHAIN or 'loglambda0' in f_params or not 0 < nEstep <= CHAIN_MAX_STEPS or maxiter <= 1
-            or damped):
+            or (damped and not damped_chain)):
         _cells_withdraw()     # under varGP_cells: this fit keeps the host loop, nobody waits for its chains
 
     def build_kernels(th):
@@ -2601,7 +2729,28 @@ def varGP(x, r, **kwargs):
 
             t0 = time.time()
             if nEstep > 0:
-                if (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params and not damped
+                if damped_chain:
+                    # the nEstep damped updates of this iteration as one device call, in every regime (the full-rank
+                    # one with a = KKtilde_inv_b = B, as in the loop below); the preamble and the factor as there
+                    if nMstep > 0:
+                        lambda_m, lambda_var = moments_now()                                  # :1871
+                        f_params['lambda0'] = lambda0_and_rate()                              # :1874
+                    f_mean = rate_now()                                                         # :1877
+                    if estep_factor[0] is None or estep_factor[0][0] is not K_tilde_b:
+                        L_kb, Li_kb, logdet_kb, info_kb = cholesky(K_tilde_b, want_inverse=True)
+                        if info_kb != 0:
+                            raise torch.linalg.LinAlgError(f"Estep: K_tilde is not positive definite (info={info_kb})")
+                        estep_factor[0] = (K_tilde_b, L_kb, matmul(KKtilde_inv_b, L_kb),
+                                           Kvec - torch.sum(K_b * KKtilde_inv_b, 1), Li_kb)
+                        ktb_logdet[0] = (K_tilde_b, logdet_kb)
+                    m_b, V_b, lambda_m, lambda_var, f_fp, chain_rec = _estep_chain_damped(
+                        r, KKtilde_inv_b, estep_factor[0][2], estep_factor[0][1], estep_factor[0][4], estep_factor[0][3],
+                        V_b, m_b, f_mean, _scalar(f_params['logA']), estep_alpha, nEstep, nFparamstep,
+                        lambda_m=lambda_m, lambda_var=lambda_var)
+                    # (the full steps' warnings in step order, then what the first failing step raises)
+                    last_rec = _estep_chain_damped_commit(chain_rec, f_params, iteration, estep_full_steps)
+                    rate_cache[0] = (lambda_m, lambda_var, _scalar(f_params['logA']), last_rec[1], f_fp)
+                elif (ESTEP_CHAIN and nEstep <= CHAIN_MAX_STEPS and 'loglambda0' not in f_params and not damped
                         and not full_rank()):
                     # the nEstep updates of this iteration as one device call (the loop below, enqueued in one go).
                     # The host loop stays (silently: the "E-steps" time is then the loop's) for more updates than the
@@ -2695,8 +2844,7 @@ def varGP(x, r, **kwargs):
                                     # the V_b reprojected onto a new basis need not be positive definite (reference
                                     # docs.md:26-30, utils.py:1829): this one update takes the full step, which does
                                     # not read V
-                                    warnings.warn(f'varGP: V_b is not positive definite in E-step {i_estep} of iteration '
-                                                  f'{iteration}; this update takes the full Newton step (alpha = 1)')
+                                    warnings.warn(_FULL_STEP_WARNING.format(i_estep, iteration))
                                     estep_full_steps[0] += 1
                                     m_b, V_b = _estep_projected(r, KKtilde_inv_b, estep_factor[0][2],
                                                                 estep_factor[0][1], m_b, f_params, f_mean)

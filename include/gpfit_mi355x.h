@@ -464,6 +464,48 @@ int gpfit_estep_chain_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, c
                             int lambda0_mode, const double* lambda0_fixed, int n_steps, int max_iter, int history_size,
                             double lr, double tol_grad, double tol_change, double* rec_host);
 
+/* The damped E-steps between two kernel rebuilds as ONE call (varGP with fit_parameters['estep_alpha'] != 1), for one
+ * unit and for 1 .. GPFIT_ESTEP_CHAIN_MAX_UNITS units in lock step: n_steps x (the update of
+ * gpfit_estep_projected_damped, the moments of lambda at the committed (m, V), then gpfit_fparam_lbfgs started at the
+ * logA in force), everything enqueued on `stream`, one synchronisation at the end.
+ * Operands per unit: those of gpfit_estep_chain (gpfit_estep_chain_batch) plus Linv[nb][ldli] = L^-1 (its lower triangle
+ * is read).  alpha in (0, 1] is shared by the call (the blend of W_a rides on a product's scalars).  V[nb][ldv] is
+ * in/out here: step 0 reads the caller's V (symmetric; its lower triangle is read), step k what step k - 1 committed.
+ * A = exp(logA) of a step is formed on the device, as in the other chains.  All units of a call share N,
+ * round_up(nb, 128), n_steps, alpha, lambda0_mode and the optimiser's settings.
+ * A step: W1 = I + Y^T Y and P = L^-1 V L^-T are factored in one lock-step recursion (two chains per unit);
+ * m_new = (1 - alpha) m + alpha L W1^-1 aL^T u; W_a = (1 - alpha) P^-1 + alpha W1 and its factorisation;
+ * V_new = (L L_Wa^-T)(L L_Wa^-T)^T.  Behind the commit: lam_var = kv0 + rowsum((aL L_Wa^-T)^2), lam_m = a m_new.
+ * V not positive definite (P's factorisation fails while W1's does not) is answered on the device, as varGP's host loop
+ * answers it: that one update is the full Newton step -- the mean is not blended, W_a is W1 -- and the step commits the
+ * full step's m and V.  Nothing of the failed factorisation reaches them, and nothing in the other units of a group
+ * depends on it.
+ * rec_host[n_units][n_steps][12]: the records of gpfit_estep_chain, slot for slot, except that [10] reads 2 for a step
+ * committed as the full step because V was not positive definite (1: committed as the damped step; 0: skipped, or its
+ * factorisation failed).  [9] is the LAPACK info of W1, or of W_a when W1's was 0.  A step with [9] != 0 commits
+ * nothing and stops its unit exactly as in gpfit_estep_chain; so does a failing optimiser, behind the commit of m, V
+ * and the moments.  Every output and record of a unit has the same bits alone and in any group; at equal A a step's
+ * (m, V) have the bits of gpfit_estep_projected_damped, its slots 0-8 and rate those of gpfit_fparam_lbfgs on its moments.
+ * No work matrix is added to the context; a cached factor of V in it is invalidated.
+ * Returns 0 when the chains ran, whatever the records say; -3, with nothing enqueued and nothing written, for every
+ * refusal of gpfit_estep_chain / _batch, a null Linv, ldli < nb, alpha not finite or outside (0, 1], or units of
+ * different round_up(nb, 128). */
+int gpfit_estep_chain_damped(gpfit_ctx* ctx, void* stream, const double* a, int64_t lda, const double* aL, int64_t ldal,
+                             const double* L, int64_t ldl, const double* Linv, int64_t ldli, int64_t N, int64_t nb,
+                             const double* r, const double* kv0, double* m, double* f, double* V, int64_t ldv,
+                             double* lam_m, double* lam_var, double logA0, double alpha, int lambda0_mode,
+                             double lambda0_fixed, int n_steps, int max_iter, int history_size, double lr,
+                             double tol_grad, double tol_change, double* rec_host);
+int gpfit_estep_chain_damped_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* a,
+                                   const int64_t* lda, const double* const* aL, const int64_t* ldal,
+                                   const double* const* L, const int64_t* ldl, const double* const* Linv,
+                                   const int64_t* ldli, int64_t N, const int64_t* nb, const double* const* r,
+                                   const double* const* kv0, double* const* m, double* const* f, double* const* V,
+                                   const int64_t* ldv, double* const* lam_m, double* const* lam_var,
+                                   const double* logA0, double alpha, int lambda0_mode, const double* lambda0_fixed,
+                                   int n_steps, int max_iter, int history_size, double lr, double tol_grad,
+                                   double tol_change, double* rec_host);
+
 /* gpfit_estep_chain_full for 1 .. GPFIT_ESTEP_CHAIN_FULL_MAX_UNITS independent units (cells, restarts of one cell) as ONE
  * call: unit u runs on its own context ctxs[u] (pairwise distinct, one device) with its own K[u], r[u], kv0[u], m[u],
  * f[u], V[u], lam_m[u], lam_var[u], leading dimensions ldk[u], ldv[u] and start logA0[u] / lambda0_fixed[u] (read when
