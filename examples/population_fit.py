@@ -11,6 +11,7 @@ numbers per cell, bit for bit.
     python examples/population_fit.py --n 1024 --ntilde 1024 --d 256 --cells 16   # inducing set = training set: truncated rank
     python examples/population_fit.py --n 512 --ntilde 512 --d 64 --cells 16 --eigval-tol 1e-14   # every eigenvalue kept: full rank
     python examples/population_fit.py --cells 4 --estep-alpha 0.5 --damped-chain   # damped E-steps, chained and grouped
+    python examples/population_fit.py --n 3160 --ntilde 2100 --d 256 --cells 16 --basis-groups   # the basis rebuilds in group calls
 
 Per repetition it prints the wall time of all fits and, averaged over the cells, the phase times ``varGP`` reports;
 for ``varGP_cells`` also how many units each chain call and each closure call carried and how long those calls took.
@@ -24,7 +25,10 @@ carried as well, with the cell's share of those calls: under ``varGP_cells`` a f
 for the wave, and ``--loop`` shows what one fit's evaluations cost (``GPFIT_FUSED_LOSS=0``: the composite, every fit on its
 own).  ``--estep-alpha A`` (A < 1) makes every E-step the damped update; such fits keep the host loop and run beside the
 others unless ``--damped-chain`` is given, with which their E-steps are chains again (counted with the projected chain
-calls) and meet in one group call per wave."""
+calls) and meet in one group call per wave.  ``--basis-groups`` (``utils.BASIS_GROUPS``) sends the two halves of every
+basis rebuild -- the sweeps and the stretches of the sign iteration -- to the wave's rendezvous as well; the units each of
+those calls carried are printed (``last_basis_group_sizes``), and a fit's "computing Kernels" then contains its wait for
+the wave, so the kernel-phase time per cell is printed by the accounting of the E-steps."""
 import argparse
 import contextlib
 import io
@@ -53,6 +57,9 @@ ap.add_argument("--estep-alpha", type=float, default=1.0,
 ap.add_argument("--damped-chain", action="store_true",
                 help="fit_parameters['estep_damped_chain']: the damped E-steps of an iteration as one device call "
                 "(utils._estep_chain_damped; under varGP_cells one group call per step size) instead of the host loop")
+ap.add_argument("--basis-groups", action="store_true",
+                help="utils.BASIS_GROUPS: under varGP_cells the sweeps and the sign stretches of the basis rebuilds meet at "
+                "the wave's rendezvous and go out as group calls")
 ap.add_argument("--eigval-tol", type=float, default=None,
                 help="utils.EIGVAL_TOL: eigenvalues of K~ below it (relative) are dropped; 1e-14 keeps them all (full rank)")
 args = ap.parse_args()
@@ -62,6 +69,7 @@ from gaussian_processes_amd import synthetic as syn, utils as gp  # noqa: E402
 
 if args.eigval_tol is not None:
     gp.EIGVAL_TOL = args.eigval_tol      # a module global read at call time
+gp.BASIS_GROUPS = bool(args.basis_groups)   # (a module global read at call time, too)
 n_px = int(round(args.d ** 0.5))
 assert n_px * n_px == args.d, "--d must be a square number of pixels"
 dev = torch.device("cuda")
@@ -137,6 +145,15 @@ for rep in range(max(1, args.repeat)):
         lhist = {n: lsizes.count(n) for n in sorted(set(lsizes))}
         line += (f" | loss calls by units carried {lhist}, {sum(lsecs):.4f} s in all -> share of the loss calls per cell "
                  f"{sum(lsecs) / args.cells:.4f}s (in the rendezvous {v.last_seconds_in_loss_call / args.cells:.4f}s per cell)")
+        if args.basis_groups:
+            # (as with the loss: the time in the rendezvous also covers the rebuild before the first iteration, which varGP
+            # does not count in "computing Kernels", so the own part can come out below zero in a process's first fits)
+            bsizes, bsecs = v.last_basis_group_sizes, v.last_basis_call_seconds
+            in_basis = v.last_seconds_in_basis_call / args.cells
+            bhist = {n: bsizes.count(n) for n in sorted(set(bsizes))}
+            line += (f" | basis calls by units carried {bhist}, {sum(bsecs):.3f} s in all; in the rendezvous {in_basis:.3f}s per "
+                     f"cell -> kernel-phase time per cell {ph['computing Kernels'] - in_basis + sum(bsecs) / args.cells:.3f}s "
+                     f"(own part {ph['computing Kernels'] - in_basis:.3f} + share of the calls {sum(bsecs) / args.cells:.3f})")
     print(line + (f" | FAILED cells {failed}" if failed else ""), flush=True)
 kept = [int(fit["B"].shape[1]) for fit, _ in fits]
 regime = "sparse" if args.ntilde < args.n else ("truncated rank" if max(kept) < args.ntilde else "full rank")

@@ -73,6 +73,8 @@ _SIGS = {
     "gpfit_subspace_sweeps": (i32, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, i32, pd, i32, ctypes.POINTER(i32)]),
     "gpfit_subspace_sweeps_batch": (i32, [vp, i32, vp, vp, i64, i64, i64, vp, vp, vp, vp, ctypes.POINTER(i32), vp, i32,
                                           ctypes.POINTER(i32)]),
+    "gpfit_sign_steps": (i32, [vp, vp, vp, i64, f64, vp, vp, vp, i32, pd, i32, i32, ctypes.POINTER(i32)]),
+    "gpfit_sign_steps_batch": (i32, [vp, i32, vp, vp, i64, pd, vp, vp, vp, i32, pd, i32, i32, ctypes.POINTER(i32)]),
     "gpfit_fparam_lbfgs_host": (i32, [vp, vp, vp, i64, f64, i32, f64, i32, i32, f64, f64, f64, vp, pd]),
     "gpfit_set_profile": (i32, [vp, i32]),
     "gpfit_get_profile": (i32, [vp, pd]),

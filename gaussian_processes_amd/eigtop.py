@@ -111,8 +111,25 @@ def _hash_matrix_build(rows, cols, device, dtype):
 _SIGN_L0 = 1e-3
 
 
+def _sign_schedule(lo, its, cap):
+    """The scalings of the scaled sign iteration from the assumed bound ``lo`` up to its next convergence test: the
+    recurrence of the loop in ``_kept_subspace`` -- ``c = sqrt(3 / (1 + lo + lo^2))`` (1 once ``lo`` has reached 1),
+    ``lo <- min(1, c lo (3 - c^2 lo^2) / 2)`` -- step by step until ``lo > 1 - 1e-9``, where that loop tests, or until
+    ``its`` reaches ``cap``.  A stretch has at least one step (the loop steps once behind a failed test whatever the
+    test's figure gives for ``lo``).  Returns ``(cs, lo_after)``."""
+    cs = []
+    while its < cap:
+        c = math.sqrt(3.0 / (1.0 + lo + lo * lo)) if lo < 1.0 else 1.0
+        cs.append(c)
+        lo = min(1.0, 0.5 * c * lo * (3.0 - c * c * lo * lo))
+        its += 1
+        if lo > 1.0 - 1e-9:
+            break
+    return cs, lo
+
+
 def _kept_subspace(Q, Y, S, tol, a_out, matmul, cholesky, angle_tol, max_sign_iterations=40, log=None, gemm_into=None,
-                   scaled=True, k_true=None):
+                   scaled=True, k_true=None, sign_chain=None):
     """The kept invariant subspace WITHOUT the k x k eigendecomposition (24 ms of rocSOLVER at k = 1024: a third of a
     basis build at N = 8192, more than half at N = 4096), from GEMMs and Cholesky factorisations only.
 
@@ -130,7 +147,16 @@ def _kept_subspace(Q, Y, S, tol, a_out, matmul, cholesky, angle_tol, max_sign_it
     Certificate: the part of K B that leaves the block, ||(I - Q Q^T) K B||_F / (tau - a_out), a_out >= everything the
     block left outside -- the quantity the eigenpair route bounds vector by vector.  Returns None when the sign
     iteration does not settle (a Ritz value within ~1e-7 tau of the threshold: the count is ambiguous, as in the
-    eigenpair route) or a factorisation fails; the caller then takes the eigenpair route."""
+    eigenpair route) or a factorisation fails; the caller then takes the eigenpair route.
+
+    ``sign_chain``: a callable ``(S, tau, X_or_None, X2_or_None, cs, its0) -> (X, X2) or None`` that runs a stretch of the
+    sign iteration in one go (``utils._sign_steps``: one device call): the Cayley transform when ``X`` is None, then for
+    every scaling of ``cs`` one step of the in-place branch below (``X2 = X X`` first, except for the first step when
+    ``X2`` is given: it is that product already; the symmetrisation where ``its0`` + the step's index is 7 mod 8), then
+    ``X2 = X X``, the product the convergence test reads.  It returns None when ``S + tau I`` was not positive definite,
+    and so does this function then.  The loop below becomes "plan the scalings up to the next test (``_sign_schedule``),
+    hand the stretch over, test, repeat": the test, the cap and the resume from the test's own figure stay here.  Only
+    for the scaled iteration on its in-place branch (``gemm_into`` given, k a multiple of 16); ``None``: that loop."""
     k = S.shape[0]
     k_true = k if k_true is None else k_true      # rows of the matrix proper when S carries zero padding (Q is None)
     dev, dt = S.device, S.dtype
@@ -179,12 +205,15 @@ def _kept_subspace(Q, Y, S, tol, a_out, matmul, cholesky, angle_tol, max_sign_it
     tau = max(lam_max * tol, tol)
     if not (a_out < 0.55 * tau):
         return None                                 # the block does not reach well below the threshold: eigenpair route
-    L, Li, _, info = cholesky(S + tau * eye, want_inverse=True)
-    if info != 0:
-        return None
-    Sinv = matmul(Li, Li, transA=True)
-    X = matmul(S - tau * eye, Sinv)
-    X = (X + X.T) * 0.5
+    inplace = gemm_into is not None and not (k & 15)
+    hooked = sign_chain is not None and scaled and inplace
+    if not hooked:
+        L, Li, _, info = cholesky(S + tau * eye, want_inverse=True)
+        if info != 0:
+            return None
+        Sinv = matmul(Li, Li, transA=True)
+        X = matmul(S - tau * eye, Sinv)
+        X = (X + X.T) * 0.5
     # Newton-Schulz, X <- X (3 I - X^2) / 2: every eigenvalue x of X grows by 3/2 per step while small and then converges
     # cubically to +-1; the smallest |x_0| is half the relative distance of the nearest Ritz value from tau (1e-2 to
     # 1e-5 on these spectra: 21-28 plain steps).  Scaled (Chen & Chow 2014): with every |x| in [l, 1], the step applied to
@@ -195,9 +224,25 @@ def _kept_subspace(Q, Y, S, tol, a_out, matmul, cholesky, angle_tol, max_sign_it
     # synchronisation) runs once the recurrence says l' = 1; if it fails, its own figure bounds the straggler from below
     # (1 - x_min^2 <= ||X^2 - I||_F) and the scaled steps resume from there.
     its, settled = 0, False
-    inplace = gemm_into is not None and not (k & 15)
     lo = _SIGN_L0 if scaled else 1.0
-    while its < max_sign_iterations:
+    X2 = None
+    while hooked:
+        # the loop below by stretches: the steps up to the next test are one call, the test and what follows from it
+        # are the loop's own
+        cs, lo = _sign_schedule(lo, its, max_sign_iterations)
+        out = sign_chain(S, tau, None if X2 is None else X, X2, cs, its)
+        if out is None:
+            return None
+        X, X2 = out
+        its += len(cs)
+        if its >= max_sign_iterations:
+            break
+        dev2 = float(torch.linalg.matrix_norm(X2 - eye))
+        if dev2 < 1e-13 * k:
+            settled = True
+            break
+        lo = math.sqrt(1.0 - dev2) if dev2 < 0.99 else 0.1
+    while not hooked and its < max_sign_iterations:
         X2 = matmul(X, X)
         if lo > 1.0 - 1e-9 and (scaled or its >= 12):
             dev2 = float(torch.linalg.matrix_norm(X2 - eye))      # Frobenius: sqrt(sum (x_i^2 - 1)^2)
@@ -264,7 +309,7 @@ def _kept_subspace(Q, Y, S, tol, a_out, matmul, cholesky, angle_tol, max_sign_it
             "angle": angle, "sign_iterations": its}
 
 
-def kept_eigenspace_dense(K, tol, matmul, cholesky, gemm_into=None, log=None):
+def kept_eigenspace_dense(K, tol, matmul, cholesky, gemm_into=None, log=None, sign_chain=None):
     """The kept eigenspace of a SMALL symmetric positive definite ``K`` (n up to ~1800) with no sweeps at all:
     ``_kept_subspace`` with the whole space as its block (Q = I, S = K) -- the spectral projector of K itself by the
     Cayley transform and the scaled sign iteration (two n^3 products per step, 12-15 steps), its trace the kept count,
@@ -274,7 +319,8 @@ def kept_eigenspace_dense(K, tol, matmul, cholesky, gemm_into=None, log=None):
     this.  Returns ``(None, B, info)`` like ``top_eigenpairs(basis="subspace")`` (no ``state``: nothing to warm-start);
     ``(None, None, info)`` with ``info["all_kept"]`` when the projector is the identity, i.e. EVERY eigenvalue lies above
     the threshold -- the exact form of the all-kept proof the caller first attempts with norm bounds; or ``None`` when
-    the count is ambiguous or a factorisation fails (the caller takes the eigh)."""
+    the count is ambiguous or a factorisation fails (the caller takes the eigh).  ``sign_chain``: handed on to
+    ``_kept_subspace``."""
     n_true = K.shape[0]
     if n_true % 16:
         npad = (n_true + 15) // 16 * 16        # zero rows / columns: zero eigenvalues, far below any threshold
@@ -282,7 +328,8 @@ def kept_eigenspace_dense(K, tol, matmul, cholesky, gemm_into=None, log=None):
         Kp[:n_true, :n_true] = K
         K = Kp
     S = (K + K.T) * 0.5
-    sub = _kept_subspace(None, None, S, tol, 0.0, matmul, cholesky, 1e-7, log=log, gemm_into=gemm_into, k_true=n_true)
+    sub = _kept_subspace(None, None, S, tol, 0.0, matmul, cholesky, 1e-7, log=log, gemm_into=gemm_into, k_true=n_true,
+                         sign_chain=sign_chain)
     if sub is None:
         return None
     if sub.get("all_kept"):
@@ -316,7 +363,8 @@ def _filter_gain(applied, a, tau):
 
 
 def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_sweeps=60, angle_tol=1e-7, seed=20240229,
-                   log=None, accelerate=True, basis="eigenvectors", gemm_into=None, start=None, sweep_chain=None):
+                   log=None, accelerate=True, basis="eigenvectors", gemm_into=None, start=None, sweep_chain=None,
+                   sign_chain=None):
     """Eigenpairs of the symmetric positive definite ``K`` with ``lambda > max(lambda_max * tol, tol)``.
 
     Returns ``(eigenvalues ascending [n], eigenvectors [N, n], info)`` or ``None`` when the caller should fall
@@ -351,7 +399,10 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
     Gram matrix was not positive definite, and so does this function then.  A pass is handed over as soon as its shifts
     are known -- behind the unshifted sweep and the plan of a cold or warm start, before the first product of a re-swept
     block and of the plain iteration -- and only for blocks whose width is a multiple of 16.  The plan stays here, and
-    ``info`` counts the products and sweeps the loop below would have run.  ``None``: that loop."""
+    ``info`` counts the products and sweeps the loop below would have run.  ``None``: that loop.
+
+    ``sign_chain``: handed on to ``_kept_subspace`` (``utils._sign_steps``: a stretch of its sign iteration as one device
+    call)."""
     import math
     N_true = K.shape[0]
     if N_true % 16:
@@ -363,7 +414,7 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
         Kp[:N_true, :N_true] = K
         out = top_eigenpairs(Kp, tol, matmul, cholesky, k0=k0, first_sweeps=first_sweeps, max_sweeps=max_sweeps, angle_tol=angle_tol,
                              seed=seed, log=log, accelerate=accelerate, basis=basis, gemm_into=gemm_into, start=start,
-                             sweep_chain=sweep_chain)
+                             sweep_chain=sweep_chain, sign_chain=sign_chain)
         if out is None:
             return None
         vals, vecs, info = out
@@ -488,7 +539,8 @@ def top_eigenpairs(K, tol, matmul, cholesky, k0=None, first_sweeps=None, max_swe
             S = matmul(Q, Y, transA=True)
             S = (S + S.T) * 0.5
         if basis == "subspace" and a_plan is not None:
-            sub = _kept_subspace(Q, Y, S, tol, a_plan, matmul, cholesky, angle_tol, log=log, gemm_into=gemm_into)
+            sub = _kept_subspace(Q, Y, S, tol, a_plan, matmul, cholesky, angle_tol, log=log, gemm_into=gemm_into,
+                                 sign_chain=sign_chain)
             if sub is not None and 4 * sub["n"] > 3 * k and k < kmax:
                 # nearly every direction of the block is kept: it does not reach below the threshold, grow it
                 grow = min(max(256, (k // 4 + 127) // 128 * 128), kmax - k, N - k)

@@ -1133,8 +1133,10 @@ def _basis_sweeps(K, Q, Y, shifts, want_rr):
     per shift ``Y = K Q`` (not for the first when ``Y`` is given), ``Y -= shift Q``, CholeskyQR (twice on the last) -- and
     the inputs of its Rayleigh-Ritz step as ONE device call and one wait (``gpfit_subspace_sweeps``) on the calling
     thread's workspace, with the bits of the loop through ``matmul`` and ``cholesky``.  Returns ``(Q, Y, S)`` as new
-    tensors (``Y`` given is overwritten), or None when a Gram matrix was not positive definite."""
-    return _sweeps_run_single(_sweeps_prepare(K, Q, Y, shifts, want_rr))
+    tensors (``Y`` given is overwritten), or None when a Gram matrix was not positive definite.  With ``BASIS_GROUPS`` on,
+    in a fit of ``varGP_cells`` the device call is the wave's (``_submit``)."""
+    q = _sweeps_prepare(K, Q, Y, shifts, want_rr)
+    return _submit(q) if BASIS_GROUPS else _sweeps_run_single(q)
 
 
 def _basis_sweeps_group(units):
@@ -1150,9 +1152,117 @@ def _basis_sweeps_group(units):
     return _sweeps_run_group([_sweeps_prepare(engine=e, **u) for u, e in zip(units, engines)])
 
 
+# ------------------------------------------------------------------ the projector step of a basis rebuild as device calls
+_SIGN_CAYLEY, _SIGN_X2_READY = 1, 2   # GPFIT_SIGN_CAYLEY, GPFIT_SIGN_X2_READY of the C header
+
+
+def _sign_prepare(S, tau, X=None, X2=None, cs=(), its0=0, engine=None):
+    """The arguments of ``_sign_steps`` as one request: ``S`` as it is (read only), ``X`` and ``X2`` themselves when given
+    (the call's work blocks from then on: both are overwritten) or new blocks, the spare block, the schedule, and the
+    workspace and stream the call runs on, this thread's unless an engine is given.  Without ``X`` the call forms it (the
+    Cayley head); ``X2`` given is the product ``X X`` already.  float64 tensors on one device."""
+    k = int(S.shape[0])
+    if X is None and X2 is not None:
+        raise ValueError("_sign_steps: X2 without X")
+    for t in (S, X, X2):
+        if t is not None and (t.dtype is not TORCH_DTYPE or tuple(t.shape) != (k, k) or t.device != S.device):
+            raise ValueError("_sign_steps: S, X and X2 [k, k] are float64 tensors on one device")
+    if (X is not None and not X.is_contiguous()) or (X2 is not None and not X2.is_contiguous()):
+        raise ValueError("_sign_steps: X and X2 are contiguous (the call works in them)")
+
+    def block():
+        return torch.empty((k, k), dtype=TORCH_DTYPE, device=S.device)
+    q = {"kind": "sign", "S": S.contiguous(), "tau": float(tau), "X": block() if X is None else X,
+         "X2": block() if X2 is None else X2, "W": block(), "k": k, "c": [float(v) for v in cs], "its0": int(its0),
+         "flags": (_SIGN_CAYLEY if X is None else 0) | (0 if X2 is None else _SIGN_X2_READY)}
+    q["engine"] = engine if engine is not None else get_engine(k, 1)
+    q["stream"] = _stream()
+    return q
+
+
+def _sign_bucket_key(q):
+    """Requests with equal keys may share one ``gpfit_sign_steps_batch`` call: what that call shares between its units
+    -- the schedule among it -- and the capacity of their workspaces."""
+    return (q["S"].device.index, q["stream"].value, q["k"], q["flags"], q["its0"], tuple(q["c"]),
+            -(-q["engine"].n_max // 128))
+
+
+def _sign_batch_raw(ctxs, qs, rec=None):
+    """``gpfit_sign_steps_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return code and
+    the ``(steps, info)`` pairs, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as
+    None goes in as a null pointer; ``rec``: the caller's array instead of a new one."""
+    q0 = qs[0]
+    rec = (ctypes.c_int * (2 * len(qs)))() if rec is None else rec
+    rc = _lib.load().gpfit_sign_steps_batch(
+        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "S"), q0["k"], _lib.darr([q["tau"] for q in qs]),
+        _ptr_table(qs, "X"), _ptr_table(qs, "X2"), _ptr_table(qs, "W"), len(q0["c"]), _lib.darr(q0["c"]) if q0["c"] else None,
+        q0["its0"], q0["flags"], rec)
+    return rc, rec
+
+
+def _sign_result(q, u, rec):
+    """What a sign call returns for its unit ``u``: ``(X, X2)``, or None when ``S + tau I`` was not positive definite
+    (``rec``: the ``(steps, info)`` pairs of the call).  X and the spare block change places with every step."""
+    if rec[2 * u + 1] != 0:
+        return None
+    return (q["W"] if len(q["c"]) & 1 else q["X"]), q["X2"]
+
+
+def _sign_run_single(q):
+    """``gpfit_sign_steps`` on one request."""
+    rec = (ctypes.c_int * 2)()
+    _lib.check(_lib.load().gpfit_sign_steps(q["engine"]._ctx, q["stream"], q["S"].data_ptr(), q["k"], q["tau"],
+                                            q["X"].data_ptr(), q["X2"].data_ptr(), q["W"].data_ptr(), len(q["c"]),
+                                            _lib.darr(q["c"]) if q["c"] else None, q["its0"], q["flags"], rec),
+               "gpfit_sign_steps")
+    return _sign_result(q, 0, rec)
+
+
+def _sign_run_group(qs):
+    """One ``gpfit_sign_steps_batch`` call on requests of one bucket (``_sign_bucket_key``), each on its own workspace;
+    per request what ``_sign_run_single`` returns, with the same bits."""
+    if len({_sign_bucket_key(q) for q in qs}) != 1:
+        raise ValueError("gpfit_sign_steps_batch: the requests of one call share the device, the stream, k, the flags, the "
+                         "schedule and the capacity of their workspaces")
+    rc, rec = _sign_batch_raw([q["engine"]._ctx for q in qs], qs)
+    _lib.check(rc, "gpfit_sign_steps_batch")
+    return [_sign_result(q, u, rec) for u, q in enumerate(qs)]
+
+
+def _sign_steps(S, tau, X, X2, cs, its0):
+    """The ``sign_chain`` of ``eigtop._kept_subspace`` on the library: a stretch of the projector step -- the Cayley
+    transform of ``S`` when ``X`` is None, one step of the scaled sign iteration per scaling of ``cs`` (``X2`` given is the
+    first step's ``X X``), the symmetrisation where ``its0`` + the step's index is 7 mod 8, and the product ``X X`` behind
+    the last step -- as ONE device call and one wait (``gpfit_sign_steps``) on the calling thread's workspace, with the
+    bits of the loop through ``cholesky``, ``matmul`` and ``gemm_into``.  Returns ``(X, X2)`` (``X`` and ``X2`` given are
+    overwritten; ``S`` is left alone), or None when ``S + tau I`` was not positive definite.  With ``BASIS_GROUPS`` on, in
+    a fit of ``varGP_cells`` the device call is the wave's (``_submit``)."""
+    q = _sign_prepare(S, tau, X, X2, cs, its0)
+    return _submit(q) if BASIS_GROUPS else _sign_run_single(q)
+
+
+def _sign_steps_group(units):
+    """``_sign_steps`` for several independent units (cells: their Rayleigh quotient matrices) as ONE device call
+    (``gpfit_sign_steps_batch``).  ``units``: one dict per unit with the arguments of ``_sign_steps`` by name (``S``,
+    ``tau``, ``cs`` and optionally ``X``, ``X2``, ``its0``); 1 .. 16 units of one ``(device, stream, k, flags, its0, cs,
+    workspace capacity)`` -- all with or all without ``X``, all with or all without ``X2``, the same schedule -- otherwise a
+    ValueError before any call.  Returns, per unit, what ``_sign_steps`` returns for it, bit for bit: a unit whose
+    factorisation fails has None in its place and fails alone."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"_sign_steps_group: 1 .. {MAX_CHAIN_UNITS} units per call")
+    shared = {(int(u["S"].shape[0]), u.get("X") is None, u.get("X2") is None, int(u.get("its0", 0)),
+               tuple(float(v) for v in u["cs"])) for u in units}
+    if len(shared) != 1:
+        raise ValueError("_sign_steps_group: the units of one call share k, the flags (all with or all without X and X2) and "
+                         "the schedule (its0 and cs)")
+    engines = _group_engines(len(units), int(units[0]["S"].shape[0]), exact=True)
+    return _sign_run_group([_sign_prepare(engine=e, **u) for u, e in zip(units, engines)])
+
+
 _BOOKS = ("", "closure_", "full_", "full_closure_")   # the prefixes of the counters a call of the rendezvous is counted in
 _LOSS_BOOK = "loss_"                                  # ... and the book of the loss evaluations (_LOSS_KIND), kept beside them
-_ALL_BOOKS = _BOOKS + (_LOSS_BOOK,)
+_BASIS_BOOK = "basis_"                                # ... and the book of the basis rebuilds (_SWEEPS_KIND, _SIGN_KIND)
+_ALL_BOOKS = _BOOKS + (_LOSS_BOOK, _BASIS_BOOK)
 
 
 class _ChainRendezvous:
@@ -1172,7 +1282,8 @@ class _ChainRendezvous:
     ``seconds_in_<book>call``, and a call is counted in the book of its kind -- the projected chains in ``""`` (a request
     without a kind included), the sparse and truncated closures in ``"closure_"``, and the full-rank regime in two
     books of its own, its chains in ``"full_"`` and its closures in ``"full_closure_"``; the loss evaluations of every
-    regime in ``"loss_"`` (``_LOSS_BOOK``)."""
+    regime in ``"loss_"`` (``_LOSS_BOOK``); the sweeps and the sign stretches of the basis rebuilds, when they come here
+    (``BASIS_GROUPS``), in ``"basis_"`` (``_BASIS_BOOK``)."""
 
     def __init__(self, parties, single, group, key, max_units=MAX_CHAIN_UNITS):
         self.cond = threading.Condition()
@@ -1288,7 +1399,8 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     time, so the phase times a fit prints are its own -- except that its E-step time contains the wait for the others.
     Fits that never chain (f_params carrying ``loglambda0``, ``estep_alpha != 1`` without the damped chain,
     ``GPFIT_ESTEP_CHAIN=0``) run beside the others without being waited for.  A fit that fails returns its ``err_dict`` as ``varGP`` does, and an error of a group call is the
-    error of every fit in that call.  Out of the groups stay the basis rebuilds and the fp32 instance.
+    error of every fit in that call.  Out of the groups stay the fp32 instance and, unless ``BASIS_GROUPS`` is on, the basis
+    rebuilds.
 
     Projected chains (``_estep_chain``: the E-steps of an EM iteration as one device call, truncated and sparse
     regimes): ONE ``gpfit_estep_chain_batch`` call per group of equal ``(N, round_up(nb, 128), nEstep, nFparamstep,
@@ -1321,6 +1433,12 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     roll-back, in every regime): ONE ``gpfit_elbo_batch`` call per group of equal ``(N, round_up(nb, 128))``.  A fit
     that has withdrawn from the wave, and any fit with ``FUSED_LOSS`` off, evaluates its loss on its own.
 
+    Basis rebuilds (``_basis_sweeps``, ``_sign_steps``; only with ``BASIS_GROUPS`` on, ``GPFIT_BASIS_GROUPS=1``): ONE
+    ``gpfit_subspace_sweeps_batch`` call per group of equal ``_sweeps_bucket_key`` for the sweeps of a pass, and ONE
+    ``gpfit_sign_steps_batch`` call per group of equal ``_sign_bucket_key`` -- the schedule of scalings is part of it, so
+    the first stretches of the fits' sign iterations share a call and a straggler's second stretch usually runs alone.
+    Off (the default), a wave issues exactly the calls it issues without the switch.
+
     The counters.  ``varGP_cells.last_group_sizes``: the units of every projected chain call of the last invocation, in
     order (1: the single call); ``last_call_seconds``: the host wall time of each of those calls;
     ``last_seconds_in_call``: summed over the fits, the time between handing a request in and getting its result
@@ -1328,7 +1446,9 @@ def varGP_cells(x, r_list, kwargs_list, max_units=MAX_CHAIN_UNITS):
     for the sparse and truncated closure calls.  The calls of the full-rank regime are counted apart, in
     ``last_full_group_sizes`` / ``last_full_call_seconds`` / ``last_seconds_in_full_call`` (chains) and
     ``last_full_closure_group_sizes`` / ``last_full_closure_call_seconds`` / ``last_seconds_in_full_closure_call``
-    (closures); the loss calls in ``last_loss_group_sizes`` / ``last_loss_call_seconds`` / ``last_seconds_in_loss_call``.
+    (closures); the loss calls in ``last_loss_group_sizes`` / ``last_loss_call_seconds`` / ``last_seconds_in_loss_call``; the sweeps
+    and sign calls of the basis rebuilds in ``last_basis_group_sizes`` / ``last_basis_call_seconds`` /
+    ``last_seconds_in_basis_call``.
     The workspaces of the fits (one per concurrent fit, each of the size of a ``varGP`` workspace) are
     kept for the next call; ``release_cell_workspaces()`` frees them."""
     n_fits = len(r_list)
@@ -1677,7 +1797,8 @@ def _stabilised_basis(K_tilde, route=None, start=None):
             # small matrices: the spectral projector of K~ itself (Cayley transform + scaled sign iteration on the
             # n x n matrix, no sweeps): 2.6 / 3.8 / 5.6 / 7.7 ms at n = 512 / 1024 / 1280 / 1536 against 12 / 22 / 29 /
             # 35 ms for rocSOLVER's eigh; the same canonical basis as the sweeps route gives for that space
-            top = eigtop.kept_eigenspace_dense(K_tilde, EIGVAL_TOL, matmul, cholesky, gemm_into=gemm_into)
+            top = eigtop.kept_eigenspace_dense(K_tilde, EIGVAL_TOL, matmul, cholesky, gemm_into=gemm_into,
+                                               sign_chain=_sign_steps if (SIGN_CHAIN or BASIS_GROUPS) else None)
             if top is None:
                 return None
             if top[1] is None:
@@ -1688,7 +1809,8 @@ def _stabilised_basis(K_tilde, route=None, start=None):
         top = eigtop.top_eigenpairs(K_tilde, EIGVAL_TOL, matmul, cholesky,
                                     basis="subspace" if want == "subspace" else "eigenvectors", gemm_into=gemm_into,
                                     start=start if want == "subspace" else None,
-                                    sweep_chain=_basis_sweeps if SWEEP_CHAIN else None)
+                                    sweep_chain=_basis_sweeps if SWEEP_CHAIN else None,
+                                    sign_chain=_sign_steps if (SIGN_CHAIN or BASIS_GROUPS) else None)
         if top is None:
             return None
         vals, vecs, info = top
@@ -1791,6 +1913,18 @@ DAMPED_CHAIN = _os_mod.environ.get("GPFIT_DAMPED_CHAIN", "0") not in ("", "0")
 # global read at call time; GPFIT_SWEEP_CHAIN=0 turns it off).  The call has the bits of the loop, so the switch changes
 # no number of a fit.
 SWEEP_CHAIN = _os_mod.environ.get("GPFIT_SWEEP_CHAIN", "1") != "0"
+# The projector step of a basis rebuild (eigtop._kept_subspace: the Cayley transform and the sign iteration up to each of
+# its convergence tests) as one device call per stretch (_sign_steps) instead of two launches and a clone per step from
+# the host (module global read at call time; GPFIT_SIGN_CHAIN=1 turns it on).  The call has the bits of the loop, so the
+# switch changes no number of a fit.  Off by default: the loop's launches already keep the device busy, and alone the call
+# measures level with it, a few hundredths of a millisecond above at some sizes (profiles/r24_sign_chain.txt); what pays
+# is the group call (BASIS_GROUPS), which takes this route whatever the switch says.
+SIGN_CHAIN = _os_mod.environ.get("GPFIT_SIGN_CHAIN", "0") not in ("", "0")
+# Under varGP_cells the two halves of a basis rebuild -- the sweeps (_basis_sweeps) and the sign stretches (_sign_steps)
+# -- meet at the wave's rendezvous and go out as group calls, one per kind and bucket.  Opt-in (module global read at
+# call time; GPFIT_BASIS_GROUPS=1 turns it on): off, a wave issues exactly the calls it issues without it.  On or off,
+# each cell's numbers are those of varGP on its own.
+BASIS_GROUPS = _os_mod.environ.get("GPFIT_BASIS_GROUPS", "0") not in ("", "0")
 # Under varGP_cells the chains (_estep_chain_full) and the M-step closures of fits in the full-rank regime meet at the
 # wave's rendezvous and go out as group calls (module global read at call time; GPFIT_FULL_RANK_GROUPS=0 turns it off: such
 # a fit then issues its own calls and keeps its turn until it ends).
@@ -2251,9 +2385,27 @@ _DAMPED_CHAIN_KIND = _RequestKind(kind="chain_damped", regime=None, book="", gat
                                   "number of steps and the optimiser's settings")
 
 
+# The eighth and ninth kind, the two halves of a basis rebuild: the sweeps of a pass (_basis_sweeps) and a stretch of the
+# projector step (_sign_steps).  They come to the rendezvous only with BASIS_GROUPS on; their calls are counted in a book
+# of their own (_BASIS_BOOK).
+_SWEEPS_KIND = _RequestKind(kind="sweeps", regime=None, book=_BASIS_BOOK, gated=False, run_single=_sweeps_run_single,
+                            entry="gpfit_subspace_sweeps_batch", batch=_sweeps_batch_raw, unit=_sweeps_result,
+                            key=_sweeps_bucket_key,
+                            share="the requests of one call share the device, the stream, N, the block width, the flags and "
+                            "the capacity of their workspaces")
+_SIGN_KIND = _RequestKind(kind="sign", regime=None, book=_BASIS_BOOK, gated=False, run_single=_sign_run_single,
+                          entry="gpfit_sign_steps_batch", batch=_sign_batch_raw, unit=_sign_result, key=_sign_bucket_key,
+                          share="the requests of one call share the device, the stream, k, the flags, the schedule and the "
+                          "capacity of their workspaces")
+
+
 def _request_kind(q):
     if q["kind"] == _LOSS_KIND.kind:
         return _LOSS_KIND
+    if q["kind"] == _SWEEPS_KIND.kind:
+        return _SWEEPS_KIND
+    if q["kind"] == _SIGN_KIND.kind:
+        return _SIGN_KIND
     if q["kind"] == _DAMPED_CHAIN_KIND.kind:
         return _DAMPED_CHAIN_KIND
     return _REQUEST_KINDS[q["kind"], q.get("regime")]

@@ -604,6 +604,41 @@ int gpfit_subspace_sweeps_batch(gpfit_ctx* const* ctxs, int n_units, void* strea
                                 int64_t N, int64_t k, double* const* Q, double* const* Y, double* const* W,
                                 double* const* S, const int* m, const double* const* sigma, int flags, int* rec_host);
 
+/* The projector step of a basis rebuild (eigtop._kept_subspace: the Cayley transform of the k x k Rayleigh quotient
+ * matrix and a stretch of the scaled Newton-Schulz sign iteration) as ONE call, for 1 .. GPFIT_ESTEP_CHAIN_MAX_UNITS
+ * independent units: unit u runs on its own context ctxs[u] (pairwise distinct, one device) with its own S[u], tau[u],
+ * X[u], X2[u], W[u]; k, the flags and the schedule -- n_steps, c[0 .. n_steps), its0 -- are shared.  Everything is
+ * enqueued on `stream`, one synchronisation at the end.
+ * Device: S[u][k][k] symmetric, read only (only read with GPFIT_SIGN_CAYLEY; S and tau may be NULL without it);
+ * X[u], X2[u], W[u] [k][k] caller-owned blocks (contiguous, pairwise distinct).  Host: tau[u], c.
+ * k a multiple of 16, 16 <= k, round_up(k, 128) within every context's capacity; 0 <= n_steps <= GPFIT_SIGN_MAX_STEPS.
+ * Head (GPFIT_SIGN_CAYLEY): S + tau I = L L^T with L^-1 (the factorisation of gpfit_potrf: the lower triangle of S, the
+ *   diagonal with one rounded add), Sinv = L^-T L^-1, X = (S - tau I) Sinv, X = (X + X^T) / 2, left in X[u].  Without
+ *   the flag X[u] is the caller's.
+ * Step j (j < n_steps):
+ *   X2 = X X                      skipped when j == 0 and GPFIT_SIGN_X2_READY is set: X2[u] already holds X X
+ *   Xn <- X; Xn = -0.5 c[j]^3 X X2 + 1.5 c[j] Xn (one product with a beta); X <- Xn
+ *   X = (X + X^T) / 2             when ((its0 + j) & 7) == 7
+ * Tail: X2 = X X, the product a convergence test reads and the first product of a next step.
+ * X[u] and W[u] change places with every step and nothing is copied back: on return X stands in X[u] when n_steps is
+ * even and in W[u] when it is odd; the other of the two is unspecified.  X2 stands in X2[u].
+ * Every product is the launch gpfit_dgemm makes of it and the factorisation is gpfit_potrf's, so X and X2 have the bits
+ * of that host loop, and a unit has the same bits alone and in any group.
+ * rec_host[n_units][2]: {steps, info}.  info = 0: steps = n_steps.  Otherwise info is the LAPACK info of S + tau I, which
+ * was not positive definite, steps = 0, and X[u], X2[u], W[u] are unspecified.  A unit that fails fails alone: the others
+ * finish with the bits they have without it.
+ * gpfit_sign_steps is the batch call with one unit.
+ * Returns 0 when the call ran, whatever rec_host says; -3, with nothing enqueued, on a bad argument (GPFIT_SIGN_X2_READY
+ * together with GPFIT_SIGN_CAYLEY is one). */
+#define GPFIT_SIGN_CAYLEY 1
+#define GPFIT_SIGN_X2_READY 2
+#define GPFIT_SIGN_MAX_STEPS 64
+int gpfit_sign_steps(gpfit_ctx* ctx, void* stream, const double* S, int64_t k, double tau, double* X, double* X2, double* W,
+                     int n_steps, const double* c, int its0, int flags, int* rec_host);
+int gpfit_sign_steps_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* const* S, int64_t k,
+                           const double* tau, double* const* X, double* const* X2, double* const* W, int n_steps,
+                           const double* c, int its0, int flags, int* rec_host);
+
 /* Active-learning utility of nstar candidate stimuli, U = H(r|x,D) - <H(r|f,x)>
  * (nd_utility with nd_p_r_given_xD, nd_lambda_r_mean, nd_mean_noise_entropy, utils.py:413-525;
  * call site one_cell_active_training.ipynb: u2d = nd_utility(logf_var, logf_mean, arange(100))).
