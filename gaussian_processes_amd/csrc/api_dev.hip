@@ -1,7 +1,8 @@
 // C-ABI test hooks of the GEMM launcher: which route a launch takes, the plans of the balanced schedules, and an
 // entry point that reaches every field of GemmArgsT (both element types, pointer batches, strided batches,
-// split-K, fused epilogues, the pair launch).  No arithmetic happens here: the hooks fill the launcher's own
-// argument struct and read the launcher's own decision (gemm_route, common.h) and its planners.
+// split-K, fused epilogues, the pair launch) -- and of the Cholesky recursion: potrf_lockstep on the caller's own
+// buffers with every argument exposed.  No arithmetic happens here: the hooks fill the launcher's own argument
+// struct and read the launcher's own decision (gemm_route, common.h) and its planners.
 #include "gemm_core.h"
 #include "context.h"
 #include "gpfit_mi355x.h"
@@ -150,6 +151,25 @@ CtxBuf ctx_buffer(gpfit_ctx* c, const char* name) {
   return {nullptr, 0};
 }
 
+// potrf_lockstep on the caller's buffers: nothing but the batch struct is filled here
+template <typename R>
+int potrf(gpfit_ctx* c, hipStream_t s, int nb, void* const* A, void* const* L, void* const* Li, void* const* Tmp,
+          int* const* info, int64_t ld, int n, uint32_t need, uint32_t halves, int side_min) {
+  CholBatchT<R> B;
+  B.nb = nb;
+  for (int b = 0; b < nb; ++b) {
+    B.A[b] = (R*)A[b]; B.L[b] = (R*)L[b]; B.Li[b] = (R*)Li[b]; B.Tmp[b] = (R*)Tmp[b];
+    B.info[b] = info[b];
+  }
+  B.ld = ld;
+  if (side_min > 0) {
+    GP_TRY(ensure_side_stream(c));
+    B.ctx = c; B.side_min = side_min;
+    c->side_ev_next = 0;   // as the closures do at the head of a call: the events of the look-ahead are reused
+  }
+  return potrf_lockstep<R>(B, 0, n, need, main_lane(c, s), halves);
+}
+
 }  // namespace
 }  // namespace gpfit
 
@@ -170,6 +190,25 @@ int gpfit_dev_gemm(void* stream, int is_f32, const gpfit_dev_gemm_args* args, co
   if (!args) return -3;
   return is_f32 ? gpfit::run<float>((hipStream_t)stream, *args, pair_args)
                 : gpfit::run<double>((hipStream_t)stream, *args, pair_args);
+}
+
+int gpfit_dev_potrf(gpfit_ctx* ctx, void* stream, int is_f32, int nb, void* const* A, void* const* L, void* const* Li,
+                    void* const* Tmp, int* const* info, int64_t ld, int n, uint32_t need, uint32_t halves, int side_min) {
+  const int64_t elem = is_f32 ? 4 : 8;
+  bool ok = ctx && A && L && Li && Tmp && info && nb >= 1 && nb <= gpfit::GEMM_MAXB && n > 0 && n % gpfit::TILE == 0 &&
+            ld >= n && (ld * elem) % 16 == 0 && side_min >= 0;
+  if (ok) {
+    const uint32_t all = nb >= 32 ? 0xffffffffu : ((1u << nb) - 1u);
+    ok = ((need | halves) & ~all) == 0;
+    for (int b = 0; b < nb && ok; ++b) ok = A[b] && L[b] && Li[b] && Tmp[b] && info[b];
+  }
+  if (!ok) {
+    gpfit::set_error("gpfit_dev_potrf: bad argument");
+    return -3;
+  }
+  GP_CTX_ENTER(ctx, "gpfit_dev_potrf");
+  return is_f32 ? gpfit::potrf<float>(ctx, (hipStream_t)stream, nb, A, L, Li, Tmp, info, ld, n, need, halves, side_min)
+                : gpfit::potrf<double>(ctx, (hipStream_t)stream, nb, A, L, Li, Tmp, info, ld, n, need, halves, side_min);
 }
 
 int gpfit_dev_ctx_copy(gpfit_ctx* ctx, const char* name, int64_t offset, void* dev, int64_t bytes, int to_ctx) {

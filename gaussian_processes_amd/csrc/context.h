@@ -73,6 +73,7 @@ namespace gpfit {
 struct Lane { hipStream_t s; void* sk_ws; };
 inline Lane main_lane(const gpfit_ctx* c, hipStream_t s) { return {s, c->sk_ws[0]}; }
 inline Lane side_lane(const gpfit_ctx* c) { return {c->side, c->sk_ws[1]}; }
+int ensure_side_stream(gpfit_ctx* c);   // fit.hip: the side stream is created on first use
 
 // ---- names of the numbered slots
 // gpfit_ctx::scal (64 doubles) / scal_host (its copy, then the slots from 64 on), with who writes each

@@ -556,7 +556,7 @@ static int check_limits(const double* theta, const double* lower, const double* 
 // Side stream of the factorisation's look-ahead products: off the critical path, lowest priority.  Created when a
 // synchronous evaluation first wants it -- contexts that only ever serve grouped / asynchronous evaluations never
 // do, and every stream a process creates is one more claimant of the few hardware queues.
-static int ensure_side_stream(gpfit_ctx* c) {
+int ensure_side_stream(gpfit_ctx* c) {
   if (c->side) return 0;
   int least = 0, greatest = 0;
   GP_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));

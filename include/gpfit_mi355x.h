@@ -683,9 +683,9 @@ int gpfit_probe_mfma_f64(void* stream, double* scratch, int blocks, int iters);
 int gpfit_probe_stream_copy(void* stream, const double* in, double* out, int64_t n_doubles);
 
 /* ---- test hooks ----------------------------------------------------------------------
- * For the test-suite (tests/test_gemm_plans_cpu.py, tests/test_gpu_gemm_schedules.py), not for
- * applications: the GEMM launcher with every field of its argument struct exposed, and host-only
- * queries of what it would do with a launch.  They add no arithmetic of their own. */
+ * For the test-suite (tests/test_gemm_plans_cpu.py, tests/test_gpu_gemm_schedules.py, tests/test_gpu_potrf.py), not
+ * for applications: the GEMM launcher with every field of its argument struct exposed, host-only queries of what it
+ * would do with a launch, and the Cholesky recursion on the caller's buffers.  They add no arithmetic of their own. */
 typedef struct gpfit_dev_gemm_args {
   const void* A;            /* device operands of element type double (is_f32 = 0) or float (1) */
   const void* B;
@@ -753,6 +753,19 @@ int gpfit_dev_gemm(void* stream, int is_f32, const gpfit_dev_gemm_args* args, co
  * from (1) the device pointer `dev`, or fill the whole buffer with one byte value.  Synchronous.  0, or -3. */
 int gpfit_dev_ctx_copy(gpfit_ctx* ctx, const char* name, int64_t offset, void* dev, int64_t bytes, int to_ctx);
 int gpfit_dev_ctx_fill(gpfit_ctx* ctx, const char* name, int byte);
+/* The Cholesky recursion behind gpfit_potrf and every closure (tests/test_gpu_potrf.py), on the caller's own device
+ * buffers: nb chains (1 .. 32) of n x n matrices, n a multiple of 128, element type double (is_f32 = 0) or float (1), all
+ * with leading dimension ld (elements; >= n, a multiple of 16 bytes).  A, L, Li, Tmp, info: HOST arrays of nb DEVICE
+ * pointers each (matrices of n x ld elements; info: one int per chain, zeroed by the caller).  Chain b factors the lower
+ * triangle of A[b] (destroyed) into L[b]; Li[b] receives the inverse of the factor for the chains in the bit mask `need`,
+ * the inverses of the two diagonal half blocks (without [L^-1]21) for the chains in `halves`, and for every other chain
+ * the inverse of the top block (the first ceil(n / 256) * 128 rows; below it only the diagonal blocks the recursion
+ * inverts for its own solves); Tmp[b] is scratch; info[b] receives the
+ * LAPACK info (the first failing pivot wins; stays as it was on success).  side_min > 0: blocks of at least that size put
+ * the first product of their inverse merge on the context's side stream (the caller's stream waits for it), 0: one
+ * stream.  The call only enqueues.  0, or -3 for a refused argument (nothing has touched the device then). */
+int gpfit_dev_potrf(gpfit_ctx* ctx, void* stream, int is_f32, int nb, void* const* A, void* const* L, void* const* Li,
+                    void* const* Tmp, int* const* info, int64_t ld, int n, uint32_t need, uint32_t halves, int side_min);
 
 #ifdef __cplusplus
 }
