@@ -96,6 +96,8 @@ _SIGS = {
                                           vp, vp, pd, pd, pd, ctypes.POINTER(i32)]),
     "gpfit_grad_pullback": (i32, [vp, vp, pd, i32, i32, vp, i64, i64, vp, i64, vp, pd]),
     "gpfit_nd_utility": (i32, [vp, vp, vp, i64, vp, i32, vp]),
+    "gpfit_score_pool": (i32, [vp, vp, f64, vp, i64, i64, vp, i64, vp, i64, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp,
+                               f64, f64, vp, i32, i64, vp, vp, vp, vp]),
     "gpfit_probe_mfma_f64": (i32, [vp, vp, i32, i32]),
     "gpfit_probe_stream_copy": (i32, [vp, vp, vp, i64]),
     # test hooks

@@ -1584,6 +1584,109 @@ def lambda_moments_star(xstar, xtilde, C, theta, K_tilde, K_tilde_inv, m, V, B, 
     return mu_star, torch.reshape(sigma_star2, (_cu(xstar).reshape(-1, _cu(xstar).shape[-1]).shape[0],))
 
 
+# Rows of a pool that the workspace of pool_moments / score_pool is sized for (when the model itself is smaller): a
+# chunk of the pool is at most as long as the workspace, and short chunks leave the quadratic-form launch too few
+# tiles to fill the chip (profiles/r25_score_pool.txt).  ``reserve`` more rows beforehand for longer chunks.
+POOL_ROWS = 4096
+
+
+def fold_posterior(K_tilde, K_tilde_inv, m, V, B):
+    """What a prediction needs of the posterior, formed once per model for ``pool_moments`` / ``score_pool``:
+    ``w = K~_b^-1 m_b`` and the symmetric ``S = K~_b^-1 (V_b - K~_b) K~_b^-1`` (utils.py:1489-1498 with the products
+    re-associated).  ``K_tilde``, ``K_tilde_inv``, ``m`` and ``V`` are in the basis ``B`` (any orthonormal one), exactly
+    as ``lambda_moments_star`` takes them.  Returns a dict with ``S``, ``w``, ``B`` (None for the identity) and ``k``;
+    ``pool_moments`` / ``score_pool`` keep the pixel list of their ``mask`` (and the masked copy of unmasked inducing
+    images) in it under private keys, formed on the first call with that mask and reused while the same tensors are
+    passed (a mask changed in place needs a new fold)."""
+    Ki = _cu(K_tilde_inv)
+    w = matmul(Ki, _cu(m).reshape(-1))
+    S = matmul(matmul(Ki, _cu(V) - _cu(K_tilde)), Ki, transB=True)
+    S = (0.5 * (S + S.T)).contiguous()
+    return {"S": S, "w": w.reshape(-1).contiguous(), "B": None if _is_identity(B) else _cu(B), "k": int(S.shape[0])}
+
+
+def _score_pool_call(xstar, xtilde, C, theta, folded, A, lambda0, r_masked, mask, chunk_rows, want_rate):
+    """One ``gpfit_score_pool`` call on this thread's workspace; returns (mu, sigma2, rate or None, utility or None)."""
+    lib = _lib.load()
+    dev = _device()
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 0 or chunk_rows % 128:
+        raise ValueError("chunk_rows must be 0 (the workspace's capacity) or a multiple of 128")
+    C = _cu(C)
+    d = C.shape[0]
+    xtilde_given = xtilde
+    xstar, xtilde = _cu(xstar), _cu(xtilde)
+    xstar = xstar.reshape(-1, xstar.shape[-1])
+    if xtilde.dim() == 1:
+        xtilde = xtilde[None, :]
+    pix, d_full = None, d
+    if mask is not None:
+        # the pixel list and the masked inducing images belong to the model: formed on the first call (the one host
+        # synchronisation of the mask path, in torch.nonzero) and kept with the folded posterior, keyed on the caller's
+        # tensors themselves, so that later calls on the same model enqueue the device call and nothing else
+        kept = folded.get("_pixels")
+        if kept is None or kept[0] is not mask:
+            mk = torch.as_tensor(mask).to(dev).reshape(-1).to(torch.bool)
+            kept = folded["_pixels"] = (mask, mk, torch.nonzero(mk).reshape(-1).to(torch.int32).contiguous())
+        _, mk, pix = kept
+        d_full = mk.numel()
+        if pix.numel() != d or xstar.shape[1] != d_full:
+            raise RuntimeError(f"score_pool: the mask keeps {pix.numel()} of {d_full} pixels but C is {tuple(C.shape)} and "
+                               f"xstar has {xstar.shape[1]} columns")
+        if xtilde.shape[1] == d_full and d_full != d:     # inducing images given unmasked as well
+            kept = folded.get("_xtilde")
+            if kept is None or kept[0] is not xtilde_given or kept[1] is not mask:
+                kept = folded["_xtilde"] = (xtilde_given, mask, xtilde[:, mk].contiguous())
+            xtilde = kept[2]
+    if xstar.shape[1] != d_full or xtilde.shape[1] != d or C.shape != (d, d):
+        raise RuntimeError("score_pool: xstar, xtilde and C disagree on the number of pixels")
+    S, w, B, k = folded["S"], folded["w"], folded["B"], int(folded["k"])
+    nt, P = xtilde.shape[0], xstar.shape[0]
+    if tuple(S.shape) != (k, k) or w.numel() != k or (B is None and k != nt) or (B is not None and tuple(B.shape) != (nt, k)):
+        raise RuntimeError("score_pool: the folded posterior does not fit the inducing set")
+    mu = torch.empty(P, dtype=TORCH_DTYPE, device=dev)
+    sigma2 = torch.empty(P, dtype=TORCH_DTYPE, device=dev)
+    rate = torch.empty(P, dtype=TORCH_DTYPE, device=dev) if want_rate else None
+    r = _cu(r_masked).reshape(-1).contiguous() if r_masked is not None else None
+    U = torch.empty(P, dtype=TORCH_DTYPE, device=dev) if r is not None else None
+    if P == 0:
+        return mu, sigma2, rate, U
+    eng = get_engine(max(nt, k, min(P, POOL_ROWS)), d, d_full)
+    _lib.check(lib.gpfit_score_pool(eng._ctx, _stream(), _scalar(theta["sigma_0"]), xstar.data_ptr(), xstar.stride(0), P,
+                                    pix.data_ptr() if pix is not None else None, d_full, xtilde.data_ptr(),
+                                    xtilde.stride(0), nt, d, C.data_ptr(), C.stride(0),
+                                    B.data_ptr() if B is not None else None, B.stride(0) if B is not None else 0, k,
+                                    S.data_ptr(), S.stride(0), w.data_ptr(), float(A), float(lambda0),
+                                    r.data_ptr() if r is not None else None, r.numel() if r is not None else 0, chunk_rows,
+                                    mu.data_ptr(), sigma2.data_ptr(), rate.data_ptr() if rate is not None else None,
+                                    U.data_ptr() if U is not None else None), "gpfit_score_pool")
+    return mu, sigma2, rate, U
+
+
+@torch.no_grad()
+def pool_moments(xstar, xtilde, C, theta, folded, mask=None, chunk_rows=0):
+    """Predictive mean and variance of lambda for every row of ``xstar`` in one device call (``gpfit_score_pool``):
+    what ``lambda_moments_star`` returns, from the posterior folded by ``fold_posterior``.  ``xstar`` is already masked,
+    or holds whole images together with ``mask`` (``xtilde`` may then be unmasked too); the pool is walked in chunks of
+    ``chunk_rows`` rows (0: as many as the workspace holds) without any pool-sized temporary.  Beside the device call the
+    wrapper allocates the outputs; the first call with a given ``mask`` also forms the pixel list (``torch.nonzero``: one
+    host synchronisation) and keeps it in ``folded``.  The bits of a row do not depend on ``chunk_rows``, on the
+    workspace's size or on the row's position.  ``sigma2`` is not clamped."""
+    mu, sigma2, _, _ = _score_pool_call(xstar, xtilde, C, theta, folded, 1.0, 0.0, None, mask, chunk_rows, False)
+    return mu, sigma2
+
+
+@torch.no_grad()
+def score_pool(xstar, xtilde, C, theta, folded, f_params, r_masked=None, mask=None, chunk_rows=0):
+    """Moments, firing rate (utils.py:395) and, with the response counts ``r_masked``, the active-learning utility
+    (``nd_utility`` at ``A^2 sigma2``, ``A mu + lambda0``: the same kernel, the same bits) of every row of ``xstar`` in
+    one device call.  Returns a dict with ``mu``, ``sigma2``, ``rate`` and ``utility`` (None without ``r_masked``)."""
+    A = _scalar(torch.exp(torch.as_tensor(f_params['logA'])))
+    lambda0 = _scalar(_lambda0_of(f_params))
+    mu, sigma2, rate, U = _score_pool_call(xstar, xtilde, C, theta, folded, A, lambda0, r_masked, mask, chunk_rows, True)
+    return {"mu": mu, "sigma2": sigma2, "rate": rate, "utility": U}
+
+
 # ------------------------------------------------------------------ initialisation (utils.py:705-857)
 def generate_xtilde(ntilde, x):
     """Jittered random subset of the first ``ntilde`` stimuli (utils.py:705-711)."""

@@ -648,6 +648,34 @@ int gpfit_sign_steps_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, co
 int gpfit_nd_utility(void* stream, const double* sigma2, const double* mu, int64_t nstar, const double* r,
                      int nr, double* U);
 
+/* Score a stimulus pool in one call: predictive moments of lambda (lambda_moments_star, utils.py:1476-1500), the
+ * firing rate (utils.py:395) and the active-learning utility of P candidate images.  The posterior enters through
+ * one vector and one symmetric matrix that the caller forms once per model (utils.fold_posterior):
+ *     w   = K~_b^-1 m_b                               [k]
+ *     S_b = K~_b^-1 (V_b - K~_b) K~_b^-1, symmetric   [k][k]   (only its lower triangle is read)
+ * and per pool row i, with z_i = k*_i B (k*_i when B is NULL: the identity basis, k == nt),
+ *     mu_i     = z_i . w
+ *     sigma2_i = k**_i + z_i S_b z_i^T            (not clamped; the reference does not clamp it either)
+ *     rate_i   = exp(A mu_i + A^2 sigma2_i / 2 + lambda0)
+ *     U_i      = the utility of gpfit_nd_utility at (A^2 sigma2_i, A mu_i + lambda0)   (the same kernel, the same bits)
+ * which is the reference's formula with the products re-associated: one triangular P x k x k product instead of two
+ * dense ones, and no P x k result ever written.
+ *   xstar   device [P][ldxs]: already masked (pixels == NULL, d columns) or whole images of d_full pixels of which
+ *           the d columns listed in `pixels` (device int [d], ascending as a mask gives them) are gathered
+ *   xtilde  device [nt][ldxt], masked inducing images;  C device [d][ldc];  B device [nt][ldb] or NULL
+ *   S, w    device, as above;  r device [nr] response counts, or NULL: no utility, U is not touched
+ *   mu, sigma2, rate, U   device [P]; rate and U may be NULL
+ * The pool is walked in row chunks of min(chunk_rows, capacity) rows (chunk_rows 0: the context's capacity, else a
+ * multiple of 128) inside the context's workspace: nothing is allocated, nt, k and d must fit the context (-3
+ * otherwise).  Every sum of a row runs over the same terms in the same order wherever the row sits (the dense products
+ * of a chunk are launched so that none is cut along k, at any size): results do not depend on the chunking, on the
+ * context's capacity, on a row's position in the pool or on the run.  Asynchronous on `stream`; P == 0 returns at once. */
+int gpfit_score_pool(gpfit_ctx* ctx, void* stream, double sigma0, const double* xstar, int64_t ldxs, int64_t P,
+                     const int* pixels, int64_t d_full, const double* xtilde, int64_t ldxt, int64_t nt, int64_t d,
+                     const double* C, int64_t ldc, const double* B, int64_t ldb, int64_t k, const double* S,
+                     int64_t lds, const double* w, double A, double lambda0, const double* r, int nr,
+                     int64_t chunk_rows, double* mu, double* sigma2, double* rate, double* U);
+
 /* Per-launch HIP-event timing of the dominant kernels during gpfit_fit_eval (bench.py's
  * roofline leg; adds two event records per launch, so leave it off when timing throughput).
  * out16: 0 sum of the 128-tile GEMM launch durations [ms] (the dominant kernel family, stream-K
