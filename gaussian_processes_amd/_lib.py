@@ -98,6 +98,9 @@ _SIGS = {
     "gpfit_nd_utility": (i32, [vp, vp, vp, i64, vp, i32, vp]),
     "gpfit_score_pool": (i32, [vp, vp, f64, vp, i64, i64, vp, i64, vp, i64, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp,
                                f64, f64, vp, i32, i64, vp, vp, vp, vp]),
+    "gpfit_score_pool_batch": (i32, [vp, i32, vp, pd, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, pd, pd,
+                                     vp, i32, i64, vp, vp, vp, vp]),
+    "gpfit_utility_sum": (i32, [vp, vp, i64, i32, vp, i64, vp]),
     "gpfit_probe_mfma_f64": (i32, [vp, vp, i32, i32]),
     "gpfit_probe_stream_copy": (i32, [vp, vp, vp, i64]),
     # test hooks

@@ -85,8 +85,8 @@ int launch_localker(const Theta& th, const int* pix, int d, int dp, int n_rows, 
 
 // ------------------------------------------------------------------ gather / transpose
 template <typename R>
-__global__ void gather_kernel(const R* __restrict__ X, int64_t ldx, int n, const int* __restrict__ pix, int d,
-                              R* __restrict__ Xt, int64_t ldt, R* __restrict__ Xm, int64_t ldm) {
+__device__ __forceinline__ void gather_body(const R* __restrict__ X, int64_t ldx, int n, const int* __restrict__ pix, int d,
+                                            R* __restrict__ Xt, int64_t ldt, R* __restrict__ Xm, int64_t ldm) {
   __shared__ R tile[32][33];
   const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
   const int tx = threadIdx.x, ty = threadIdx.y;  // 32 x 8
@@ -104,6 +104,27 @@ __global__ void gather_kernel(const R* __restrict__ X, int64_t ldx, int n, const
     const int k = k0 + ty + 8 * r, nn = n0 + tx;
     Xt[(int64_t)k * ldt + nn] = tile[tx][ty + 8 * r];
   }
+}
+template <typename R>
+__global__ void gather_kernel(const R* __restrict__ X, int64_t ldx, int n, const int* __restrict__ pix, int d,
+                              R* __restrict__ Xt, int64_t ldt, R* __restrict__ Xm, int64_t ldm) {
+  gather_body(X, ldx, n, pix, d, Xt, ldt, Xm, ldm);
+}
+// unit u = blockIdx.z of a group: its own images, pixel list and extents, the k-major copy only
+__global__ void gather_group_kernel(PerUnit<const double*> X, PerUnit<int64_t> ldx, PerUnit<int> n, PerUnit<const int*> pix,
+                                    PerUnit<int> d, PerUnit<double*> Xt, int64_t ldt) {
+  const int u = blockIdx.z;
+  gather_body<double>(X[u], ldx[u], n[u], pix[u], d[u], Xt[u], ldt, nullptr, 0);
+}
+int launch_gather_group(int n_units, PerUnit<const double*> X, PerUnit<int64_t> ldx, PerUnit<int> n, PerUnit<const int*> pix,
+                        PerUnit<int> d, int dp, int np, PerUnit<double*> Xt, int64_t ldt, hipStream_t s) {
+  if (dp % 32 || np % 32) {
+    set_error("launch_gather: padded extents must be multiples of 32");
+    return -3;
+  }
+  hipLaunchKernelGGL(gather_group_kernel, dim3(dp / 32, np / 32, n_units), dim3(32, 8), 0, s, X, ldx, n, pix, d, Xt, ldt);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 template <typename R>
@@ -124,8 +145,8 @@ int launch_gather(const R* X, int64_t ldx, int n, const int* pix, int d, int dp,
 // the samples), the eight partial sums meet in LDS in a fixed order.  (One thread per sample walked all dp pixels
 // with one load in flight: 37 us at N = 4096, 67 us at N = 8192 -- latency, not bandwidth.)
 template <typename R>
-__global__ __launch_bounds__(256) void qvec_kernel(const R* __restrict__ Xt, const R* __restrict__ XCt, int64_t ld, int dp,
-                                                   int n, int np, double s0sq, R* __restrict__ Kvec, R* __restrict__ q) {
+__device__ __forceinline__ void qvec_body(const R* __restrict__ Xt, const R* __restrict__ XCt, int64_t ld, int dp, int n,
+                                          int np, double s0sq, R* __restrict__ Kvec, R* __restrict__ q) {
   __shared__ double part[8][33];
   const int li = threadIdx.x & 31, sl = threadIdx.x >> 5;
   const int i = blockIdx.x * 32 + li;
@@ -148,6 +169,24 @@ __global__ __launch_bounds__(256) void qvec_kernel(const R* __restrict__ Xt, con
   const double kv = t + s0sq;  // utils.py:1029
   Kvec[i] = (R)kv;
   q[i] = (R)sqrt(kv);          // utils.py:978
+}
+template <typename R>
+__global__ __launch_bounds__(256) void qvec_kernel(const R* __restrict__ Xt, const R* __restrict__ XCt, int64_t ld, int dp,
+                                                   int n, int np, double s0sq, R* __restrict__ Kvec, R* __restrict__ q) {
+  qvec_body(Xt, XCt, ld, dp, n, np, s0sq, Kvec, q);
+}
+// unit u = blockIdx.y of a group: its own operands, sample count and sigma_0^2
+__global__ __launch_bounds__(256) void qvec_group_kernel(PerUnit<const double*> Xt, PerUnit<const double*> XCt, int64_t ld,
+                                                         int dp, PerUnit<int> n, int np, PerUnit<double> s0sq,
+                                                         PerUnit<double*> Kvec, PerUnit<double*> q) {
+  const int u = blockIdx.y;
+  qvec_body<double>(Xt[u], XCt[u], ld, dp, n[u], np, s0sq[u], Kvec[u], q[u]);
+}
+int launch_qvec_group(int n_units, PerUnit<const double*> Xt, PerUnit<const double*> XCt, int64_t ld, int dp, PerUnit<int> n,
+                      int np, PerUnit<double> s0sq, PerUnit<double*> Kvec, PerUnit<double*> q, hipStream_t s) {
+  hipLaunchKernelGGL(qvec_group_kernel, dim3((np + 31) / 32, n_units), dim3(256), 0, s, Xt, XCt, ld, dp, n, np, s0sq, Kvec, q);
+  GP_HIP(hipGetLastError());
+  return 0;
 }
 
 template <typename R>
@@ -1088,17 +1127,23 @@ __global__ void pad_copy_kernel(const double* __restrict__ src, int64_t lds, int
                                 double* __restrict__ dst, int64_t ldd, int prow, int pcol) {
   pad_copy_body(src, lds, rows, cols, dst, ldd, prow, pcol);
 }
-__global__ void pad_copy_group_kernel(PerUnit<const double*> src, PerUnit<int64_t> lds, int rows, PerUnit<int> cols,
+__global__ void pad_copy_group_kernel(PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> rows, PerUnit<int> cols,
                                       PerUnit<double*> dst, int64_t ldd, int prow, int pcol) {
   const int u = blockIdx.z;
-  pad_copy_body(src[u], lds[u], rows, cols[u], dst[u], ldd, prow, pcol);
+  pad_copy_body(src[u], lds[u], rows[u], cols[u], dst[u], ldd, prow, pcol);
 }
-int launch_pad_copy_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, int rows, PerUnit<int> cols,
+int launch_pad_copy_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> rows, PerUnit<int> cols,
                           PerUnit<double*> dst, int64_t ldd, int prow, int pcol, hipStream_t s) {
   hipLaunchKernelGGL(pad_copy_group_kernel, dim3((pcol + 255) / 256, prow, n_units), dim3(256), 0, s, src, lds, rows, cols,
                      dst, ldd, prow, pcol);
   GP_HIP(hipGetLastError());
   return 0;
+}
+int launch_pad_copy_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, int rows, PerUnit<int> cols,
+                          PerUnit<double*> dst, int64_t ldd, int prow, int pcol, hipStream_t s) {
+  PerUnit<int> r{};
+  for (int u = 0; u < n_units; ++u) r.v[u] = rows;
+  return launch_pad_copy_group(n_units, src, lds, r, cols, dst, ldd, prow, pcol, s);
 }
 
 int launch_pad_copy(const double* src, int64_t lds, int rows, int cols, double* dst, int64_t ldd, int prow,

@@ -374,6 +374,18 @@ int launch_closure_prepare(const ClosurePrepT& g, hipStream_t s);
 int launch_zero3_group(int n_units, PerUnit<double*> a, PerUnit<double*> b, PerUnit<double*> c, int64_t count, hipStream_t s);
 int launch_pad_copy_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, int rows, PerUnit<int> cols,
                           PerUnit<double*> dst, int64_t ldd, int prow, int pcol, hipStream_t s);
+// the same with the row count per unit (gpfit_score_pool_batch: C and B of cells whose true sizes differ)
+int launch_pad_copy_group(int n_units, PerUnit<const double*> src, PerUnit<int64_t> lds, PerUnit<int> rows, PerUnit<int> cols,
+                          PerUnit<double*> dst, int64_t ldd, int prow, int pcol, hipStream_t s);
+// launch_gather (the k-major copy only) and launch_qvec for unit u of a group: its own images, pixel list (or nullptr),
+// true extents n[u], d[u] and sigma_0^2; the padded extents are the group's
+int launch_gather_group(int n_units, PerUnit<const double*> X, PerUnit<int64_t> ldx, PerUnit<int> n, PerUnit<const int*> pix,
+                        PerUnit<int> d, int dp, int np, PerUnit<double*> Xt, int64_t ldt, hipStream_t s);
+int launch_qvec_group(int n_units, PerUnit<const double*> Xt, PerUnit<const double*> XCt, int64_t ld, int dp, PerUnit<int> n,
+                      int np, PerUnit<double> s0sq, PerUnit<double*> Kvec, PerUnit<double*> q, hipStream_t s);
+// launch_nd_utility for unit u of a group (its own moments and output; the response counts are the call's)
+int launch_nd_utility_group(int n_units, PerUnit<const double*> sigma2, PerUnit<const double*> mu, int64_t nstar,
+                            const double* r, int nr, PerUnit<double*> U, hipStream_t s);
 int launch_symmetrize_group(int n_units, PerUnit<double*> A, int64_t lda, int n, hipStream_t s);
 int launch_symmetrize_avg_group(int n_units, PerUnit<double*> A, int64_t lda, PerUnit<int> n, hipStream_t s);
 // out0[u] = log|L0[u] L0[u]^T|, out1[u] likewise (launch_logdet_pair per unit, the unit's own n)

@@ -1,4 +1,5 @@
-// Scoring a stimulus pool in one call (gpfit_score_pool): predictive moments of lambda, firing rate and
+// Scoring a stimulus pool in one call (gpfit_score_pool; gpfit_score_pool_batch for up to 16 cells on one pool: the
+// single call is the group of one, every kernel below carries a unit index): predictive moments of lambda, firing rate and
 // active-learning utility of P candidate images from a posterior folded once per model into
 //   w = K~_b^-1 m_b   and   S_b = K~_b^-1 (V_b - K~_b) K~_b^-1   (symmetric),
 // so that per pool row (reference utils.py:1486-1498 with the products re-associated)
@@ -8,10 +9,12 @@
 // Its epilogue multiplies the accumulators by Z, adds each row's 128 columns in a fixed order and writes one partial
 // per (row, column tile); the partial of z . w rides along on the same Z elements.  No P x k result exists, nothing
 // is allocated, nothing is added atomically.  Every sum of a row runs over the same terms in the same order wherever
-// the row sits -- the two dense products of a chunk (x* C and K* B) go out as pointer batches of one, which the GEMM
-// launcher never cuts along k -- so the bits do not depend on the chunking, the row offset or the run.
+// the row sits -- the dense products (C xtilde once, x* C and K* B per chunk) go out as pointer batches of one problem per
+// unit, which the GEMM launcher never cuts along k -- so the bits do not depend on the chunking, the row offset, the run,
+// or on which other units share the call.  Each unit works in its own context's matrices.
 #include "gemm_core.h"
 #include "product.h"
+#include "units.h"
 #include "gpfit_mi355x.h"
 
 #include <algorithm>
@@ -19,20 +22,22 @@
 namespace gpfit {
 namespace {
 
-// ---- the Gram panel K*[np1][np2] of a row chunk against the inducing images, padding written as zeros
+// ---- the Gram panel K*[np1][np2] of a row chunk against the inducing images, padding written as zeros; unit blockIdx.y
 struct PoolGramArgs {
-  const double* XCt;   // [Kd][ld1]  (x* C)^T of the chunk
-  const double* Xt;    // [Kd][ld2]  inducing images, k-major
-  const double* q1;    // [np1]
-  const double* q2;    // [np2]
-  double* Kout;        // [np1][ldk]
+  PerUnit<const double*> XCt;   // [Kd][ld1]  (x* C)^T of the chunk
+  PerUnit<const double*> Xt;    // [Kd][ld2]  inducing images, k-major
+  PerUnit<const double*> q1;    // [np1]
+  PerUnit<const double*> q2;    // [np2]
+  PerUnit<double*> Kout;        // [np1][ldk]
+  PerUnit<int> nv2;             // the unit's inducing images
+  PerUnit<double> s0sq;
   int64_t ld1, ld2, ldk;
-  int np1, np2, nv1, nv2, Kd;
-  double s0sq;
+  int np1, np2, nv1, Kd;
 };
 
 __global__ __launch_bounds__(GEMM_THREADS, 2) void pool_gram_kernel(PoolGramArgs p, int tiles_n) {
   __shared__ __attribute__((aligned(16))) double smem[4 * Real<double>::KT * TILE];
+  const int u = blockIdx.y;
   const int ti = blockIdx.x / tiles_n, tj = blockIdx.x % tiles_n;
   const int row0 = ti * TILE, col0 = tj * TILE;
   Real<double>::acc_t acc[4][4];
@@ -42,15 +47,15 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pool_gram_kernel(PoolGramArgs
     for (int j = 0; j < 4; ++j) acc[i][j] = acc_zero<double>();
 
   // operands are zero-padded to whole tiles: no edge predication on the loads
-  gemm_mainloop<double, true, true, false, TILE>(p.XCt, p.ld1, p.Xt, p.ld2, p.np1, p.np2, row0, col0, 0, p.Kd, smem, acc);
+  gemm_mainloop<double, true, true, false, TILE>(p.XCt[u], p.ld1, p.Xt[u], p.ld2, p.np1, p.np2, row0, col0, 0, p.Kd, smem, acc);
 
-  const int nv1 = p.nv1, nv2 = p.nv2;
+  const int nv1 = p.nv1, nv2 = p.nv2[u];
   const int64_t ldk = p.ldk;
-  const double s0sq = p.s0sq;
+  const double s0sq = p.s0sq[u];
   const double pi32 = PI32;
-  const double* __restrict__ q1 = p.q1;
-  const double* __restrict__ q2 = p.q2;
-  double* __restrict__ Ko = p.Kout;
+  const double* __restrict__ q1 = p.q1[u];
+  const double* __restrict__ q2 = p.q2[u];
+  double* __restrict__ Ko = p.Kout[u];
 
   for_each_acc<double, TILE>(acc, row0, col0, [&](int row, int col, double g) {
     const int64_t o = (int64_t)row * ldk + col;
@@ -67,12 +72,19 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pool_gram_kernel(PoolGramArgs
   });
 }
 
-// ---- S' and w, zero-padded (once per call).  One 32 x 32 tile per workgroup, transposed through LDS: S is read
-// along its rows (only elements on or below its diagonal are ever loaded) and S' written along its rows.
-__global__ __launch_bounds__(256) void pool_weights_kernel(const double* __restrict__ S, int64_t lds, int k, int kp,
-                                                           double* __restrict__ Sw, const double* __restrict__ w,
-                                                           double* __restrict__ wpad) {
+// ---- S' and w, zero-padded (once per call).  One 32 x 32 tile per workgroup (unit blockIdx.z), transposed through
+// LDS: S is read along its rows (only elements on or below its diagonal are ever loaded) and S' written along its rows.
+__global__ __launch_bounds__(256) void pool_weights_kernel(PerUnit<const double*> S_u, PerUnit<int64_t> lds_u, PerUnit<int> k_u,
+                                                           int kp, PerUnit<double*> Sw_u, PerUnit<const double*> w_u,
+                                                           PerUnit<double*> wpad_u) {
   __shared__ double tile[32][33];
+  const int u = blockIdx.z;
+  const double* __restrict__ S = S_u[u];
+  const double* __restrict__ w = w_u[u];
+  double* __restrict__ Sw = Sw_u[u];
+  double* __restrict__ wpad = wpad_u[u];
+  const int64_t lds = lds_u[u];
+  const int k = k_u[u];
   const int c0 = blockIdx.x * 32, l0 = blockIdx.y * 32;
   const int tx = threadIdx.x, ty = threadIdx.y;   // 32 x 8
 #pragma unroll
@@ -92,18 +104,20 @@ __global__ __launch_bounds__(256) void pool_weights_kernel(const double* __restr
 
 // ---- the quadratic form: tile (ti, tj) of Z S', reduced against Z along its columns
 struct PoolQuadArgs {
-  const double* Z;     // [np1][ldz], zero padded
-  const double* Sw;    // [kp][kp]
-  const double* w;     // [kp]
-  double* part;        // [tiles_n][2][np1]: (row, tj) partials of z S z^T and of z . w
+  PerUnit<const double*> Z;     // [np1][ldz], zero padded
+  PerUnit<const double*> Sw;    // [kp][kp]
+  PerUnit<const double*> w;     // [kp]
+  PerUnit<double*> part;        // [tiles_n][2][np1]: (row, tj) partials of z S z^T and of z . w
   int64_t ldz;
-  int np1, kp, tiles_m, tiles_n;
+  int np1, kp, tiles_m, tiles_n, n_units;
 };
 
 __global__ __launch_bounds__(GEMM_THREADS, 2) void pool_quad_kernel(PoolQuadArgs p) {
   __shared__ __attribute__((aligned(16))) double smem[4 * Real<double>::KT * TILE];   // 8192 doubles
-  // long tiles first (the k range grows with the column tile); the tiles of a column share their S' panel
-  const int tj = p.tiles_n - 1 - (int)blockIdx.x / p.tiles_m, ti = (int)blockIdx.x % p.tiles_m;
+  // long tiles first (the k range grows with the column tile), those of all units before any shorter one; the tiles
+  // of a unit's column share their S' panel
+  const int per_col = p.tiles_m * p.n_units, in_col = (int)blockIdx.x % per_col;
+  const int tj = p.tiles_n - 1 - (int)blockIdx.x / per_col, u = in_col / p.tiles_m, ti = in_col % p.tiles_m;
   const int row0 = ti * TILE, col0 = tj * TILE;
   Real<double>::acc_t acc[4][4];
 #pragma unroll
@@ -111,15 +125,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pool_quad_kernel(PoolQuadArgs
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = acc_zero<double>();
 
-  gemm_mainloop<double, false, true, false, TILE>(p.Z, p.ldz, p.Sw, p.kp, p.np1, p.kp, row0, col0, 0, col0 + TILE, smem, acc);
+  const double* __restrict__ Z = p.Z[u];
+  gemm_mainloop<double, false, true, false, TILE>(Z, p.ldz, p.Sw[u], p.kp, p.np1, p.kp, row0, col0, 0, col0 + TILE, smem, acc);
   __syncthreads();   // every wave is done with the operand stages: the reduction reuses them
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, fr = lane & 15;
-  const double* __restrict__ Z = p.Z;
+  const double* __restrict__ wp = p.w[u];
   double wv[4];
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) wv[ni] = p.w[col0 + wn * 64 + ni * 16 + fr];
+  for (int ni = 0; ni < 4; ++ni) wv[ni] = wp[col0 + wn * 64 + ni * 16 + fr];
   // smem as [2][128 rows][32 slots]: slot = 16 wn + fr holds the row's sum over the lane's four columns; the slot index
   // is XORed with the row so that neither the writes nor the row-wise reads below pile up on one bank
   const int slot = wn * 16 + fr;
@@ -146,25 +161,34 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pool_quad_kernel(PoolQuadArgs
   double t = 0.0;
 #pragma unroll
   for (int sl = 0; sl < 32; ++sl) t += sr[sl ^ (row & 31)];
-  p.part[((int64_t)tj * 2 + which) * p.np1 + row0 + row] = t;
+  p.part[u][((int64_t)tj * 2 + which) * p.np1 + row0 + row] = t;
 }
 
 // ---- per row: the partials in ascending column-tile order, then the moments, the rate and the utility's arguments
-__global__ __launch_bounds__(256) void pool_finish_kernel(const double* __restrict__ part, int np1, int tiles_n,
-                                                          const double* __restrict__ Kvec, int rows, double A, double A2,
-                                                          double lambda0, double* __restrict__ mu,
-                                                          double* __restrict__ sigma2, double* __restrict__ rate,
-                                                          double* __restrict__ s2_scaled, double* __restrict__ mu_scaled) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows) return;
+struct PoolFinishArgs {
+  PerUnit<const double*> part, Kvec;
+  PerUnit<double> A, A2, lambda0;
+  PerUnit<double*> mu, sigma2, rate;         // the unit's outputs at the chunk's first row; rate may be nullptr
+  PerUnit<double*> s2_scaled, mu_scaled;     // nullptr without response counts
+  int np1, tiles_n, rows;
+};
+
+__global__ __launch_bounds__(256) void pool_finish_kernel(PoolFinishArgs p) {
+  const int i = blockIdx.x * 256 + threadIdx.x, u = blockIdx.y;
+  if (i >= p.rows) return;
+  const double* __restrict__ part = p.part[u];
+  const int np1 = p.np1;
+  const double A = p.A[u], A2 = p.A2[u], lambda0 = p.lambda0[u];
+  double* __restrict__ rate = p.rate[u];
+  double* __restrict__ s2_scaled = p.s2_scaled[u];
   double qf = 0.0, m = 0.0;
-  for (int j = 0; j < tiles_n; ++j) {
+  for (int j = 0; j < p.tiles_n; ++j) {
     qf += part[((int64_t)j * 2) * np1 + i];
     m += part[((int64_t)j * 2 + 1) * np1 + i];
   }
-  const double s2 = Kvec[i] + qf;
-  mu[i] = m;
-  sigma2[i] = s2;
+  const double s2 = p.Kvec[u][i] + qf;
+  p.mu[u][i] = m;
+  p.sigma2[u][i] = s2;
   if (rate) rate[i] = exp(A * m + 0.5 * A * A * s2 + lambda0);   // utils.py:395
   if (s2_scaled) {
     // one rounding per operation (no fused multiply-add), as the element-wise host expressions A^2 sigma2 and
@@ -172,16 +196,130 @@ __global__ __launch_bounds__(256) void pool_finish_kernel(const double* __restri
 #pragma clang fp contract(off)
     const double am = A * m;
     s2_scaled[i] = A2 * s2;
-    mu_scaled[i] = am + lambda0;
+    p.mu_scaled[u][i] = am + lambda0;
   }
 }
 
-// ---- a dense product whose bits do not depend on how many rows the chunk has.  The launcher's balanced schedules cut
-// the k range of the tail tiles of a large launch (stream-K, gemm.hip: streamk_first_tile), and which rows sit in tail
-// tiles depends on the tile count, hence on the chunk.  A pointer batch never takes such a schedule: as a batch of one
-// the product runs data-parallel, every tile over its whole k range in ascending order, whatever the tile size.
+// ---- a dense product whose bits do not depend on how many rows the chunk has, nor on the units beside it.  The
+// launcher's balanced schedules cut the k range of the tail tiles of a large launch (stream-K, gemm.hip:
+// streamk_first_tile), and which rows sit in tail tiles depends on the tile count, hence on the chunk.  A pointer batch
+// never takes such a schedule: one problem per unit, the product runs data-parallel, every tile over its whole k range
+// in ascending order, whatever the tile size.
 int product_whole_k(Lane lane, Dims d, const Operand<double>& a, const Operand<double>& b, const Output<double>& c) {
   return run_gemm(lane.s, batch_args(lane, d, 1.0, a, b, c));
+}
+
+// The call for 1 .. CHAIN_MAXU units; tables indexed by unit (pixels, B, rate: the table itself may be null).
+int score_pool_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void* stream, const double* sigma0,
+                    const double* const* xstar, const int64_t* ldxs, int64_t P, const int* const* pixels,
+                    const int64_t* d_full, const double* const* xtilde, const int64_t* ldxt, const int64_t* nt, const int64_t* d,
+                    const double* const* C, const int64_t* ldc, const double* const* B, const int64_t* ldb, const int64_t* k,
+                    const double* const* S, const int64_t* lds, const double* const* w, const double* A, const double* lambda0,
+                    const double* r, int nr, int64_t chunk_rows, double* const* mu, double* const* sigma2,
+                    double* const* rate, double* const* U) {
+  const Refuse refuse{name};
+  if (n_units < 1 || n_units > CHAIN_MAXU) return refuse("1 .. " + std::to_string(CHAIN_MAXU) + " units per call");
+  if (!ctxs || !sigma0 || !xstar || !ldxs || !d_full || !xtilde || !ldxt || !nt || !d || !C || !ldc || !k || !S || !lds || !w ||
+      !A || !lambda0 || !mu || !sigma2 || P < 0 || (B && !ldb) || (r && (!U || nr <= 0)))
+    return refuse("bad argument");
+  auto basis = [&](int u) { return B ? B[u] : nullptr; };
+  auto pix = [&](int u) { return pixels ? pixels[u] : nullptr; };
+  for (int u = 0; u < n_units; ++u)
+    if (!ctxs[u] || !xtilde[u] || !C[u] || !S[u] || !w[u] || nt[u] <= 0 || d[u] <= 0 || k[u] <= 0 || ldxt[u] < d[u] ||
+        ldc[u] < d[u] || lds[u] < k[u] || (P > 0 && (!xstar[u] || !mu[u] || !sigma2[u])) ||
+        (basis(u) ? ldb[u] < k[u] : k[u] != nt[u]) || (r && !U[u]) ||
+        (pix(u) ? (d_full[u] < d[u] || ldxs[u] < d_full[u]) : ldxs[u] < d[u]))
+      return refuse(unit_prefix(n_units, u) + "bad argument");
+  if (chunk_rows < 0 || chunk_rows % TILE) return refuse("chunk_rows must be 0 or a multiple of 128");
+  const int64_t dp64 = round_up(d[0], 32), ntp64 = round_up(nt[0], TILE), kp64 = round_up(k[0], TILE);
+  int64_t cap = 0;
+  for (int u = 0; u < n_units; ++u) {
+    const std::string unit = unit_prefix(n_units, u);
+    if (const char* why = unit_context_refusal(ctxs, u)) return refuse(unit + why);
+    if (round_up(d[u], 32) > ctxs[u]->dp_cap || round_up(nt[u], TILE) > ctxs[u]->np_cap || round_up(k[u], TILE) > ctxs[u]->np_cap)
+      return refuse(unit + "problem larger than the context capacity");
+    if (round_up(d[u], 32) != dp64 || round_up(nt[u], TILE) != ntp64 || round_up(k[u], TILE) != kp64 || !basis(u) != !basis(0))
+      return refuse(unit + "the units of one call share round_up(d, 32), round_up(nt, 128) and round_up(k, 128), and all "
+                           "have a basis B or none has");
+    cap = u == 0 ? ctxs[u]->np_cap : std::min<int64_t>(cap, ctxs[u]->np_cap);
+  }
+  DeviceGuard device_guard(ctxs[0]->device);
+  if (P == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const Lane lane{s, nullptr};   // the process-wide stream-K workspace, as the other kernel entry points
+  const int dp = (int)dp64, ntp = (int)ntp64, kp = (int)kp64, nu = n_units;
+  const bool with_B = basis(0) != nullptr;
+  const int64_t chunk = chunk_rows ? std::min<int64_t>(chunk_rows, cap) : cap;
+  const Units all = Units::all(ctxs, nu);
+  const PerUnit<double> s0sq = all.table<double>([&](int u) { return sigma0[u] * sigma0[u]; });
+  const PerUnit<int> d_u = all.table<int>([&](int u) { return (int)d[u]; }), nt_u = all.table<int>([&](int u) { return (int)nt[u]; }),
+                     k_u = all.table<int>([&](int u) { return (int)k[u]; });
+  const PerUnit<const int*> no_pix = all.same<const int*>(nullptr);
+  // work matrices (np_cap^2 doubles each): none of them caches the factor of V, so lv_valid / lv32_valid stand
+  const auto panel = &gpfit_ctx::Cos;    // K* of a chunk [np1][ntp]
+  const auto Zb = &gpfit_ctx::Zbuf;      // K* B of a chunk [np1][kp]
+  const auto Sw = &gpfit_ctx::Wbuf;      // S' [kp][kp]
+  const auto Bpad = &gpfit_ctx::Tbuf;    // B zero padded [ntp][kp]
+  const auto part = &gpfit_ctx::Abuf;    // [kp / 128][2][np1]
+  const auto wpad = &gpfit_ctx::bv;
+
+  // once per call: the inducing side of the kernel, S' and w
+  GP_TRY(launch_pad_copy_group(nu, all.from(C), all.from(ldc), d_u, d_u, all.of(&gpfit_ctx::Cmat), dp, dp, dp, s));
+  GP_TRY(launch_gather_group(nu, all.from(xtilde), all.from(ldxt), nt_u, no_pix, d_u, dp, ntp, all.of(&gpfit_ctx::Xt2), ntp, s));
+  GP_TRY(product_whole_k(lane, {dp, ntp, dp}, trans(all.mats(&gpfit_ctx::Cmat, dp)), plain(all.mats(&gpfit_ctx::Xt2, ntp)),
+                         into(all.mats(&gpfit_ctx::XCt2, ntp))));
+  GP_TRY(launch_qvec_group(nu, all.cof(&gpfit_ctx::Xt2), all.cof(&gpfit_ctx::XCt2), ntp, dp, nt_u, ntp, s0sq,
+                           all.of(&gpfit_ctx::hvec), all.of(&gpfit_ctx::q2), s));
+  hipLaunchKernelGGL(pool_weights_kernel, dim3(kp / 32, kp / 32, nu), dim3(32, 8), 0, s, all.from(S), all.from(lds), k_u, kp,
+                     all.of(Sw), all.from(w), all.of(wpad));
+  GP_HIP(hipGetLastError());
+  if (with_B) GP_TRY(launch_pad_copy_group(nu, all.from(B), all.from(ldb), nt_u, k_u, all.of(Bpad), kp, ntp, kp, s));
+
+  PoolFinishArgs f{};
+  f.part = all.cof(part); f.Kvec = all.cof(&gpfit_ctx::Kvec); f.tiles_n = kp / TILE;
+  f.A = all.from(A); f.A2 = all.table<double>([&](int u) { return A[u] * A[u]; }); f.lambda0 = all.from(lambda0);
+  if (r) {
+    f.s2_scaled = all.of(&gpfit_ctx::lam_var);
+    f.mu_scaled = all.of(&gpfit_ctx::lam_m);
+  }
+  for (int64_t off = 0; off < P; off += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, P - off);
+    const int np1 = (int)round_up(rows, TILE);
+    GP_TRY(launch_gather_group(nu, all.table<const double*>([&](int u) { return xstar[u] + off * ldxs[u]; }), all.from(ldxs),
+                               all.same(rows), all.table<const int*>(pix), d_u, dp, np1, all.of(&gpfit_ctx::Xt), np1, s));
+    GP_TRY(product_whole_k(lane, {dp, np1, dp}, trans(all.mats(&gpfit_ctx::Cmat, dp)), plain(all.mats(&gpfit_ctx::Xt, np1)),
+                           into(all.mats(&gpfit_ctx::XCt, np1))));
+    GP_TRY(launch_qvec_group(nu, all.cof(&gpfit_ctx::Xt), all.cof(&gpfit_ctx::XCt), np1, dp, all.same(rows), np1, s0sq,
+                             all.of(&gpfit_ctx::Kvec), all.of(&gpfit_ctx::q), s));
+    {
+      PoolGramArgs g{};
+      g.XCt = all.cof(&gpfit_ctx::XCt); g.Xt = all.cof(&gpfit_ctx::Xt2); g.q1 = all.cof(&gpfit_ctx::q);
+      g.q2 = all.cof(&gpfit_ctx::q2); g.Kout = all.of(panel); g.nv2 = nt_u; g.s0sq = s0sq;
+      g.ld1 = np1; g.ld2 = ntp; g.ldk = ntp; g.np1 = np1; g.np2 = ntp; g.nv1 = rows; g.Kd = dp;
+      hipLaunchKernelGGL(pool_gram_kernel, dim3((np1 / TILE) * (ntp / TILE), nu), dim3(GEMM_THREADS), 0, s, g, ntp / TILE);
+      GP_HIP(hipGetLastError());
+    }
+    if (with_B)
+      GP_TRY(product_whole_k(lane, {np1, kp, ntp}, plain(all.mats(panel, ntp)), plain(all.mats(Bpad, kp)), into(all.mats(Zb, kp))));
+    {
+      PoolQuadArgs q{};
+      q.Z = all.cof(with_B ? Zb : panel); q.Sw = all.cof(Sw); q.w = all.cof(wpad); q.part = all.of(part);
+      q.ldz = with_B ? kp : ntp;
+      q.np1 = np1; q.kp = kp; q.tiles_m = np1 / TILE; q.tiles_n = kp / TILE; q.n_units = nu;
+      hipLaunchKernelGGL(pool_quad_kernel, dim3(q.tiles_m * q.tiles_n * nu), dim3(GEMM_THREADS), 0, s, q);
+      GP_HIP(hipGetLastError());
+    }
+    f.np1 = np1; f.rows = rows;
+    f.mu = all.table<double*>([&](int u) { return mu[u] + off; });
+    f.sigma2 = all.table<double*>([&](int u) { return sigma2[u] + off; });
+    f.rate = all.table<double*>([&](int u) { return rate && rate[u] ? rate[u] + off : nullptr; });
+    hipLaunchKernelGGL(pool_finish_kernel, dim3((rows + 255) / 256, nu), dim3(256), 0, s, f);
+    GP_HIP(hipGetLastError());
+    if (r)
+      GP_TRY(launch_nd_utility_group(nu, all.cof(&gpfit_ctx::lam_var), all.cof(&gpfit_ctx::lam_m), rows, r, nr,
+                                     all.table<double*>([&](int u) { return U[u] + off; }), s));
+  }
+  return 0;
 }
 
 }  // namespace
@@ -195,78 +333,18 @@ extern "C" int gpfit_score_pool(gpfit_ctx* c, void* stream, double sigma0, const
                                 const double* S, int64_t lds, const double* w, double A, double lambda0,
                                 const double* r, int nr, int64_t chunk_rows, double* mu, double* sigma2, double* rate,
                                 double* U) {
-  if (!c || P < 0 || !xtilde || !C || !S || !w || nt <= 0 || d <= 0 || k <= 0 || ldxt < d || ldc < d || lds < k ||
-      (P > 0 && (!xstar || !mu || !sigma2)) || (B ? ldb < k : k != nt) || (r && (!U || nr <= 0)) ||
-      (pixels ? (d_full < d || ldxs < d_full) : ldxs < d)) {
-    set_error("gpfit_score_pool: bad argument");
-    return -3;
-  }
-  if (chunk_rows < 0 || chunk_rows % TILE) {
-    set_error("gpfit_score_pool: chunk_rows must be 0 or a multiple of 128");
-    return -3;
-  }
-  GP_CTX_ENTER(c, "gpfit_score_pool");
-  hipStream_t s = (hipStream_t)stream;
-  const Lane lane{s, nullptr};   // the process-wide stream-K workspace, as the other kernel entry points
-  const int dp = (int)round_up(d, 32), ntp = (int)round_up(nt, TILE), kp = (int)round_up(k, TILE);
-  if (dp > c->dp_cap || ntp > c->np_cap || kp > c->np_cap) {
-    set_error("gpfit_score_pool: problem larger than the context capacity");
-    return -3;
-  }
-  if (P == 0) return 0;
-  const int64_t chunk = chunk_rows ? std::min<int64_t>(chunk_rows, c->np_cap) : c->np_cap;
-  const double s0sq = sigma0 * sigma0;
-  // work matrices (np_cap^2 doubles each): none of them caches the factor of V, so lv_valid / lv32_valid stand
-  double* panel = c->Cos;    // K* of a chunk [np1][ntp]
-  double* Zb = c->Zbuf;      // K* B of a chunk [np1][kp]
-  double* Sw = c->Wbuf;      // S' [kp][kp]
-  double* Bpad = c->Tbuf;    // B zero padded [ntp][kp]
-  double* part = c->Abuf;    // [kp / 128][2][np1]
-  double* wpad = c->bv;
+  return score_pool_impl("gpfit_score_pool", &c, 1, stream, &sigma0, &xstar, &ldxs, P, &pixels, &d_full, &xtilde, &ldxt, &nt, &d,
+                         &C, &ldc, &B, &ldb, &k, &S, &lds, &w, &A, &lambda0, r, nr, chunk_rows, &mu, &sigma2, &rate, &U);
+}
 
-  // once per call: the inducing side of the kernel, S' and w
-  GP_TRY(launch_pad_copy(C, ldc, (int)d, (int)d, c->Cmat, dp, dp, dp, s));
-  GP_TRY(launch_gather<double>(xtilde, ldxt, (int)nt, nullptr, (int)d, dp, ntp, c->Xt2, ntp, nullptr, 0, s));
-  GP_TRY(product(lane, {dp, ntp, dp}, 1.0, trans(mat(c->Cmat, dp)), plain(mat(c->Xt2, ntp)), into(mat(c->XCt2, ntp))));
-  GP_TRY(launch_qvec(c->Xt2, c->XCt2, ntp, dp, (int)nt, ntp, s0sq, c->hvec, c->q2, s));
-  hipLaunchKernelGGL(pool_weights_kernel, dim3(kp / 32, kp / 32), dim3(32, 8), 0, s, S, lds, (int)k, kp, Sw, w, wpad);
-  GP_HIP(hipGetLastError());
-  if (B) GP_TRY(launch_pad_copy(B, ldb, (int)nt, (int)k, Bpad, kp, ntp, kp, s));
-
-  for (int64_t off = 0; off < P; off += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, P - off);
-    const int np1 = (int)round_up(rows, TILE);
-    const double* xs = xstar + off * ldxs;
-    GP_TRY(launch_gather<double>(xs, ldxs, rows, pixels, (int)d, dp, np1, c->Xt, np1, nullptr, 0, s));
-    GP_TRY(product_whole_k(lane, {dp, np1, dp}, trans(mat(c->Cmat, dp)), plain(mat(c->Xt, np1)), into(mat(c->XCt, np1))));
-    GP_TRY(launch_qvec(c->Xt, c->XCt, np1, dp, rows, np1, s0sq, c->Kvec, c->q, s));
-    {
-      PoolGramArgs g{};
-      g.XCt = c->XCt; g.Xt = c->Xt2; g.q1 = c->q; g.q2 = c->q2; g.Kout = panel;
-      g.ld1 = np1; g.ld2 = ntp; g.ldk = ntp; g.np1 = np1; g.np2 = ntp; g.nv1 = rows; g.nv2 = (int)nt; g.Kd = dp;
-      g.s0sq = s0sq;
-      hipLaunchKernelGGL(pool_gram_kernel, dim3((np1 / TILE) * (ntp / TILE)), dim3(GEMM_THREADS), 0, s, g, ntp / TILE);
-      GP_HIP(hipGetLastError());
-    }
-    const double* Z = panel;
-    int64_t ldz = ntp;
-    if (B) {
-      GP_TRY(product_whole_k(lane, {np1, kp, ntp}, plain(mat(panel, ntp)), plain(mat(Bpad, kp)), into(mat(Zb, kp))));
-      Z = Zb;
-      ldz = kp;
-    }
-    {
-      PoolQuadArgs q{};
-      q.Z = Z; q.Sw = Sw; q.w = wpad; q.part = part; q.ldz = ldz;
-      q.np1 = np1; q.kp = kp; q.tiles_m = np1 / TILE; q.tiles_n = kp / TILE;
-      hipLaunchKernelGGL(pool_quad_kernel, dim3(q.tiles_m * q.tiles_n), dim3(GEMM_THREADS), 0, s, q);
-      GP_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(pool_finish_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, part, np1, kp / TILE, c->Kvec, rows,
-                       A, A * A, lambda0, mu + off, sigma2 + off, rate ? rate + off : nullptr,
-                       r ? c->lam_var : nullptr, r ? c->lam_m : nullptr);
-    GP_HIP(hipGetLastError());
-    if (r) GP_TRY(launch_nd_utility(c->lam_var, c->lam_m, rows, r, nr, U + off, s));
-  }
-  return 0;
+extern "C" int gpfit_score_pool_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* sigma0,
+                                      const double* const* xstar, const int64_t* ldxs, int64_t P, const int* const* pixels,
+                                      const int64_t* d_full, const double* const* xtilde, const int64_t* ldxt,
+                                      const int64_t* nt, const int64_t* d, const double* const* C, const int64_t* ldc,
+                                      const double* const* B, const int64_t* ldb, const int64_t* k, const double* const* S,
+                                      const int64_t* lds, const double* const* w, const double* A, const double* lambda0,
+                                      const double* r, int nr, int64_t chunk_rows, double* const* mu, double* const* sigma2,
+                                      double* const* rate, double* const* U) {
+  return score_pool_impl("gpfit_score_pool_batch", ctxs, n_units, stream, sigma0, xstar, ldxs, P, pixels, d_full, xtilde, ldxt,
+                         nt, d, C, ldc, B, ldb, k, S, lds, w, A, lambda0, r, nr, chunk_rows, mu, sigma2, rate, U);
 }

@@ -1605,13 +1605,10 @@ def fold_posterior(K_tilde, K_tilde_inv, m, V, B):
     return {"S": S, "w": w.reshape(-1).contiguous(), "B": None if _is_identity(B) else _cu(B), "k": int(S.shape[0])}
 
 
-def _score_pool_call(xstar, xtilde, C, theta, folded, A, lambda0, r_masked, mask, chunk_rows, want_rate):
-    """One ``gpfit_score_pool`` call on this thread's workspace; returns (mu, sigma2, rate or None, utility or None)."""
-    lib = _lib.load()
+def _score_pool_prepare(xstar, xtilde, C, theta, folded, mask):
+    """The operands of one ``gpfit_score_pool`` unit, checked, as a request: the tensors on the device (``pix`` None for
+    a pool that is already masked), the sizes and ``sigma0``."""
     dev = _device()
-    chunk_rows = int(chunk_rows)
-    if chunk_rows < 0 or chunk_rows % 128:
-        raise ValueError("chunk_rows must be 0 (the workspace's capacity) or a multiple of 128")
     C = _cu(C)
     d = C.shape[0]
     xtilde_given = xtilde
@@ -1644,15 +1641,44 @@ def _score_pool_call(xstar, xtilde, C, theta, folded, A, lambda0, r_masked, mask
     nt, P = xtilde.shape[0], xstar.shape[0]
     if tuple(S.shape) != (k, k) or w.numel() != k or (B is None and k != nt) or (B is not None and tuple(B.shape) != (nt, k)):
         raise RuntimeError("score_pool: the folded posterior does not fit the inducing set")
-    mu = torch.empty(P, dtype=TORCH_DTYPE, device=dev)
-    sigma2 = torch.empty(P, dtype=TORCH_DTYPE, device=dev)
-    rate = torch.empty(P, dtype=TORCH_DTYPE, device=dev) if want_rate else None
+    return {"xstar": xstar, "xtilde": xtilde, "C": C, "pix": pix, "d": d, "d_full": d_full, "nt": nt, "P": P, "S": S, "w": w,
+            "B": B, "k": k, "sigma0": _scalar(theta["sigma_0"])}
+
+
+def _pool_chunk_rows(chunk_rows):
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 0 or chunk_rows % 128:
+        raise ValueError("chunk_rows must be 0 (the workspace's capacity) or a multiple of 128")
+    return chunk_rows
+
+
+def _pool_workspace_rows(q):
+    """Stimuli the workspace of a pool call is sized for (``POOL_ROWS``)."""
+    return max(q["nt"], q["k"], min(q["P"], POOL_ROWS))
+
+
+def _score_pool_call(xstar, xtilde, C, theta, folded, A, lambda0, r_masked, mask, chunk_rows, want_rate, out=None):
+    """One ``gpfit_score_pool`` call on this thread's workspace; returns (mu, sigma2, rate or None, utility or None).
+    ``out``: the caller's four float64 device vectors of P elements in place of new ones (``score_pool_cells``: rows of
+    its tables; the last is ignored without ``r_masked``)."""
+    lib = _lib.load()
+    dev = _device()
+    chunk_rows = _pool_chunk_rows(chunk_rows)
+    q = _score_pool_prepare(xstar, xtilde, C, theta, folded, mask)
+    xstar, xtilde, C, pix, S, w, B = (q[key] for key in ("xstar", "xtilde", "C", "pix", "S", "w", "B"))
+    d, d_full, nt, P, k = (q[key] for key in ("d", "d_full", "nt", "P", "k"))
     r = _cu(r_masked).reshape(-1).contiguous() if r_masked is not None else None
-    U = torch.empty(P, dtype=TORCH_DTYPE, device=dev) if r is not None else None
+    if out is None:
+        mu = torch.empty(P, dtype=TORCH_DTYPE, device=dev)
+        sigma2 = torch.empty(P, dtype=TORCH_DTYPE, device=dev)
+        rate = torch.empty(P, dtype=TORCH_DTYPE, device=dev) if want_rate else None
+        U = torch.empty(P, dtype=TORCH_DTYPE, device=dev) if r is not None else None
+    else:
+        mu, sigma2, rate, U = out[0], out[1], out[2], out[3] if r is not None else None
     if P == 0:
         return mu, sigma2, rate, U
-    eng = get_engine(max(nt, k, min(P, POOL_ROWS)), d, d_full)
-    _lib.check(lib.gpfit_score_pool(eng._ctx, _stream(), _scalar(theta["sigma_0"]), xstar.data_ptr(), xstar.stride(0), P,
+    eng = get_engine(_pool_workspace_rows(q), d, d_full)
+    _lib.check(lib.gpfit_score_pool(eng._ctx, _stream(), q["sigma0"], xstar.data_ptr(), xstar.stride(0), P,
                                     pix.data_ptr() if pix is not None else None, d_full, xtilde.data_ptr(),
                                     xtilde.stride(0), nt, d, C.data_ptr(), C.stride(0),
                                     B.data_ptr() if B is not None else None, B.stride(0) if B is not None else 0, k,
@@ -1685,6 +1711,164 @@ def score_pool(xstar, xtilde, C, theta, folded, f_params, r_masked=None, mask=No
     lambda0 = _scalar(_lambda0_of(f_params))
     mu, sigma2, rate, U = _score_pool_call(xstar, xtilde, C, theta, folded, A, lambda0, r_masked, mask, chunk_rows, True)
     return {"mu": mu, "sigma2": sigma2, "rate": rate, "utility": U}
+
+
+# ------------------------------------------------------------------ a pool scored for several cells at once
+last_pool_group_sizes = []   # units per device call of the last score_pool_cells, in the order the calls were made
+
+
+def _link_scalars(f_params):
+    return _scalar(torch.exp(torch.as_tensor(f_params['logA']))), _scalar(_lambda0_of(f_params))
+
+
+def _pool_bucket_key(d, nt, k, with_B):
+    """Units with equal keys may share one ``gpfit_score_pool_batch`` call: the three padded sizes and the presence of a
+    basis (the true sizes may differ)."""
+    return (-(-int(d) // 32) * 32, -(-int(nt) // 128) * 128, -(-int(k) // 128) * 128, bool(with_B))
+
+
+def _pool_cell_key(cell):
+    """``_pool_bucket_key`` of a cell as ``score_pool_cells`` is given it (shapes only, nothing is moved)."""
+    folded, xtilde = cell["folded"], cell["xtilde"]
+    return _pool_bucket_key(cell["C"].shape[0], 1 if xtilde.dim() == 1 else xtilde.shape[0], folded["k"], folded["B"] is not None)
+
+
+def _score_pool_batch_raw(ctxs, qs, r, chunk_rows, mu, sigma2, rate, U):
+    """``gpfit_score_pool_batch`` on the requests ``qs`` (``_score_pool_prepare`` plus ``A``, ``lambda0``) with the contexts
+    ``ctxs`` (one per request) and one output vector per request in each of ``mu``, ``sigma2``, ``rate``, ``U`` (``U``
+    None without ``r``): the return code, nothing checked here -- ``P`` is that of ``qs[0]``."""
+    n = len(qs)
+    i64s = lambda vals: (ctypes.c_int64 * n)(*[int(v) for v in vals])      # noqa: E731
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])   # noqa: E731
+    Bs = [q["B"] for q in qs]
+    return _lib.load().gpfit_score_pool_batch(
+        _ctx_table(ctxs), n, _stream(), _lib.darr([q["sigma0"] for q in qs]), _ptr_table(qs, "xstar"),
+        i64s(q["xstar"].stride(0) for q in qs), qs[0]["P"], _ptr_table(qs, "pix"), i64s(q["d_full"] for q in qs),
+        _ptr_table(qs, "xtilde"), i64s(q["xtilde"].stride(0) for q in qs), i64s(q["nt"] for q in qs), i64s(q["d"] for q in qs),
+        _ptr_table(qs, "C"), i64s(q["C"].stride(0) for q in qs), ptrs(Bs), i64s(0 if B is None else B.stride(0) for B in Bs),
+        i64s(q["k"] for q in qs), _ptr_table(qs, "S"), i64s(q["S"].stride(0) for q in qs), _ptr_table(qs, "w"),
+        _lib.darr([q["A"] for q in qs]), _lib.darr([q["lambda0"] for q in qs]), None if r is None else r.data_ptr(),
+        0 if r is None else r.numel(), chunk_rows, ptrs(mu), ptrs(sigma2), ptrs(rate), None if U is None else ptrs(U))
+
+
+@torch.no_grad()
+def _score_pool_group(units, r_masked, chunk_rows, out=None):
+    """``score_pool`` for several independent units (the cells of a population on one pool) as ONE device call
+    (``gpfit_score_pool_batch``).  ``units``: one dict per unit with the arguments of ``score_pool`` by name (``xstar``,
+    ``xtilde``, ``C``, ``theta``, ``folded``, ``f_params`` and optionally ``mask``; the mask's pixel list is kept in
+    ``folded`` as the single call keeps it); 1 .. 16 units with pools of one length and one ``_pool_bucket_key`` --
+    otherwise a ValueError before any call.  ``out``: per unit the four float64 device vectors the call writes (``mu``,
+    ``sigma2``, ``rate``, ``utility``) in place of new ones.  Returns, per unit, what ``score_pool`` returns for it, bit
+    for bit."""
+    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"_score_pool_group: 1 .. {MAX_CHAIN_UNITS} units per call")
+    chunk_rows = _pool_chunk_rows(chunk_rows)
+    qs = []
+    for u in units:
+        q = _score_pool_prepare(u["xstar"], u["xtilde"], u["C"], u["theta"], u["folded"], u.get("mask"))
+        q["A"], q["lambda0"] = _link_scalars(u["f_params"])
+        qs.append(q)
+    if len({q["P"] for q in qs}) != 1 or len({_pool_bucket_key(q["d"], q["nt"], q["k"], q["B"] is not None) for q in qs}) != 1:
+        raise ValueError("gpfit_score_pool_batch: the units of one call share the pool's length, round_up(d, 32), "
+                         "round_up(nt, 128), round_up(k, 128) and the presence of a basis")
+    dev, P = _device(), qs[0]["P"]
+    r = _cu(r_masked).reshape(-1).contiguous() if r_masked is not None else None
+    if out is None:
+        block = torch.empty((len(qs), 4 if r is not None else 3, P), dtype=TORCH_DTYPE, device=dev)
+        out = [tuple(block[i]) + (() if r is not None else (None,)) for i in range(len(qs))]
+    res = [{"mu": o[0], "sigma2": o[1], "rate": o[2], "utility": o[3] if r is not None else None} for o in out]
+    if P == 0:
+        return res
+    engines = _group_engines(len(qs), max(_pool_workspace_rows(q) for q in qs), max(q["d"] for q in qs),
+                             max(q["d_full"] for q in qs))
+    _lib.check(_score_pool_batch_raw([e._ctx for e in engines], qs, r, chunk_rows, [o["mu"] for o in res],
+                                     [o["sigma2"] for o in res], [o["rate"] for o in res],
+                                     None if r is None else [o["utility"] for o in res]), "gpfit_score_pool_batch")
+    return res
+
+
+def _score_pool_single(unit, r_masked, chunk_rows, out):
+    """One unit of ``score_pool_cells`` through the single call (``gpfit_score_pool``) into the rows ``out``."""
+    A, lambda0 = _link_scalars(unit["f_params"])
+    _score_pool_call(unit["xstar"], unit["xtilde"], unit["C"], unit["theta"], unit["folded"], A, lambda0, r_masked,
+                     unit.get("mask"), chunk_rows, True, out=out)
+
+
+def _utility_sum(U, weights=None):
+    """``gpfit_utility_sum``: the weighted sum of the rows of ``U`` [n_rows][P] (``weights`` None: ones), rows in ascending
+    order."""
+    U = _cu(U)
+    n_rows, P = U.shape
+    w = None if weights is None else _cu(weights).reshape(-1).contiguous()
+    if w is not None and w.numel() != n_rows:
+        raise ValueError("one weight per row")
+    out = torch.empty(P, dtype=TORCH_DTYPE, device=U.device)
+    _lib.check(_lib.load().gpfit_utility_sum(_stream(), U.data_ptr(), U.stride(0), n_rows, None if w is None else w.data_ptr(),
+                                             P, out.data_ptr()), "gpfit_utility_sum")
+    return out
+
+
+@torch.no_grad()
+def score_pool_cells(xstar, cells, r_masked=None, weights=None, chunk_rows=0, max_units=MAX_CHAIN_UNITS):
+    """``score_pool`` of one pool for any number of cells, and the utility of the population.  ``cells``: one dict per cell
+    with ``xtilde``, ``C``, ``theta``, ``folded`` (``fold_posterior``), ``f_params`` and optionally ``mask`` -- the
+    arguments of ``score_pool`` by name; ``xstar`` is the pool all of them are scored on (whole images where the cells
+    have masks).  The cells are sorted into buckets by ``_pool_bucket_key`` and every bucket goes out in device calls of at
+    most ``max_units`` cells (``gpfit_score_pool_batch``); with ``POOL_GROUPS`` off every cell goes through the single
+    call.  Either way each cell has the bits of ``score_pool`` on it alone.
+
+    Returns a dict: ``mu``, ``sigma2``, ``rate``, ``utility`` as tensors [n_cells][P] in the caller's order (``utility``
+    None without ``r_masked``), ``population_utility`` [P] = sum over the cells of ``weights[c] * utility[c]`` in the
+    caller's order (``gpfit_utility_sum``; ``weights`` None: ones; None without ``r_masked``), and ``errors``: per cell None,
+    or the exception its call raised -- that cell's rows are NaN (and so is the sum), the other cells are scored.  The units
+    per device call are left in ``last_pool_group_sizes``."""
+    global last_pool_group_sizes
+    if not 1 <= int(max_units) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"score_pool_cells: max_units is 1 .. {MAX_CHAIN_UNITS}")
+    chunk_rows = _pool_chunk_rows(chunk_rows)
+    dev = _device()
+    xstar = _cu(xstar)
+    xstar = xstar.reshape(-1, xstar.shape[-1])
+    n, P = len(cells), xstar.shape[0]
+    keys = ("mu", "sigma2", "rate") + (("utility",) if r_masked is not None else ())
+    block = torch.empty((len(keys), n, P), dtype=TORCH_DTYPE, device=dev)
+    res = {key: block[i] for i, key in enumerate(keys)}
+    rows = [tuple(res[key][c] for key in keys) + (() if r_masked is not None else (None,)) for c in range(n)]
+    errors, sizes, buckets = [None] * n, [], collections.OrderedDict()
+    for c, cell in enumerate(cells):
+        try:
+            buckets.setdefault(_pool_cell_key(cell), []).append(c)
+        except Exception as err:          # a cell that cannot even be sorted: its own error
+            errors[c] = err
+    step = int(max_units) if POOL_GROUPS else 1
+    for members in buckets.values():
+        for a in range(0, len(members), step):
+            part = members[a:a + step]
+            try:
+                if POOL_GROUPS:
+                    _score_pool_group([dict(cells[c], xstar=xstar) for c in part], r_masked, chunk_rows,
+                                      out=[rows[c] for c in part])
+                else:
+                    _score_pool_single(dict(cells[part[0]], xstar=xstar), r_masked, chunk_rows, rows[part[0]])
+                sizes.append(len(part))
+            except Exception as err:
+                if len(part) == 1:
+                    errors[part[0]] = err
+                    continue
+                for c in part:            # the group was refused for one of its cells: each on its own, to find which
+                    try:
+                        _score_pool_single(dict(cells[c], xstar=xstar), r_masked, chunk_rows, rows[c])
+                        sizes.append(1)
+                    except Exception as own:
+                        errors[c] = own
+    for c, err in enumerate(errors):
+        if err is not None:
+            block[:, c] = float("nan")
+    last_pool_group_sizes = sizes
+    res["utility"] = res.get("utility")
+    res["population_utility"] = _utility_sum(res["utility"], weights) if r_masked is not None and n > 0 else None
+    res["errors"] = errors
+    return res
 
 
 # ------------------------------------------------------------------ initialisation (utils.py:705-857)
@@ -2038,6 +2222,9 @@ FULL_RANK_GROUPS = _os_mod.environ.get("GPFIT_FULL_RANK_GROUPS", "1") != "0"
 # reported and never fed back: the switch changes no m_b, V_b, theta or rate parameter of a fit, only the last digits
 # of the tracked loss.
 FUSED_LOSS = _os_mod.environ.get("GPFIT_FUSED_LOSS", "1") != "0"
+# score_pool_cells scores the cells of a bucket in group calls (gpfit_score_pool_batch); GPFIT_POOL_GROUPS=0: every cell
+# through the single call, with the same bits.
+POOL_GROUPS = _os_mod.environ.get("GPFIT_POOL_GROUPS", "1") != "0"
 # per host thread (the reference's active-learning notebook fits and scores on two threads): the route the last
 # call of _stabilised_basis took, and (N, EIGVAL_TOL) -> "full" | "truncated", which of the two rank checks to try
 # first -- a hint only, so one thread's history never changes what another thread's fit costs

@@ -676,6 +676,41 @@ int gpfit_score_pool(gpfit_ctx* ctx, void* stream, double sigma0, const double* 
                      int64_t lds, const double* w, double A, double lambda0, const double* r, int nr,
                      int64_t chunk_rows, double* mu, double* sigma2, double* rate, double* U);
 
+/* gpfit_score_pool for 1 .. GPFIT_ESTEP_CHAIN_MAX_UNITS independent units (the cells of a population, which all see
+ * the same candidate images) as ONE call: unit u runs on its own context ctxs[u] (pairwise distinct, one device) in that
+ * context's workspace, and every launch of the call -- the three dense products as pointer batches of n_units problems,
+ * the Gram, weights, quadratic-form, finish and utility kernels with a unit index -- carries all units, so the number of
+ * launches does not grow with n_units (gpfit_score_pool is this call with one unit).  Per unit, tables indexed by u:
+ *   sigma0[u]; xstar[u] with ldxs[u], pixels[u] (the table or an entry may be NULL: that unit's xstar is already masked)
+ *   and d_full[u] -- in a population every xstar[u] is the same pool of whole images and only the pixel lists differ;
+ *   xtilde[u], ldxt[u], nt[u], d[u];  C[u], ldc[u];  B[u], ldb[u] (B may be NULL: no unit has a basis);  k[u];
+ *   S[u], lds[u];  w[u];  A[u], lambda0[u];  the outputs mu[u], sigma2[u], rate[u] (table or entry may be NULL), U[u],
+ *   device [P] each.
+ * Shared by the call: P, the response counts r / nr (NULL: no utility, no U[u] is touched) and chunk_rows; the chunk is
+ * min(chunk_rows or capacity, the smallest capacity among the units' contexts) rows.
+ * What lets the units share launches: round_up(d, 32), round_up(nt, 128) and round_up(k, 128) agree, and all units have
+ * a basis B or none has; the true d, nt and k may differ.  A disagreement is refused (-3, "unit u: ...", nothing
+ * written), as is a unit whose context is too small, repeated, on another device, or has an evaluation pending.
+ * For every unit mu, sigma2, rate and U are bit-identical to gpfit_score_pool on that unit's arguments alone, whatever
+ * the other units, their number and order, chunk_rows and the contexts' capacities.  No atomics, nothing allocated.
+ * Asynchronous on `stream`; P == 0 returns at once. */
+int gpfit_score_pool_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* sigma0,
+                           const double* const* xstar, const int64_t* ldxs, int64_t P, const int* const* pixels,
+                           const int64_t* d_full, const double* const* xtilde, const int64_t* ldxt, const int64_t* nt,
+                           const int64_t* d, const double* const* C, const int64_t* ldc, const double* const* B,
+                           const int64_t* ldb, const int64_t* k, const double* const* S, const int64_t* lds,
+                           const double* const* w, const double* A, const double* lambda0, const double* r, int nr,
+                           int64_t chunk_rows, double* const* mu, double* const* sigma2, double* const* rate,
+                           double* const* U);
+
+/* The utility of a population: out[i] = sum over rows u of weight[u] * U[u][i], i < P, for U device [n_rows][ldu]
+ * (ldu >= P; the rows of utilities that gpfit_score_pool / gpfit_score_pool_batch wrote), weight device [n_rows] or NULL
+ * (every weight one), out device [P].  The rows are added in ascending order starting from the first product, with one
+ * rounding per multiply and per add (no fused multiply-add): the bits of the loop acc = weight[0] U[0];
+ * acc = acc + weight[u] U[u], whatever calls produced the rows.  NaN propagates, nothing is masked; n_rows >= 1 is not
+ * limited by GPFIT_ESTEP_CHAIN_MAX_UNITS.  Asynchronous on `stream`; P == 0 returns at once. */
+int gpfit_utility_sum(void* stream, const double* U, int64_t ldu, int n_rows, const double* weight, int64_t P, double* out);
+
 /* Per-launch HIP-event timing of the dominant kernels during gpfit_fit_eval (bench.py's
  * roofline leg; adds two event records per launch, so leave it off when timing throughput).
  * out16: 0 sum of the 128-tile GEMM launch durations [ms] (the dominant kernel family, stream-K
