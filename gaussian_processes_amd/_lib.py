@@ -20,7 +20,7 @@ class DevGemmArgs(ctypes.Structure):
                 [("alpha", f64), ("beta", f64)] +
                 [(n, vp) for n in ("sk_ws", "aux", "sumsq", "Ap", "Bp", "Cp", "auxp", "sumsqp")] +
                 [(n, ctypes.c_int32) for n in ("M", "N", "K", "a_kmajor", "b_kmajor", "out_lower", "a_tri", "b_tri", "batch",
-                                               "split_k", "tile", "walk", "epi", "nptr", "k_slabs")])
+                                               "split_k", "tile", "walk", "epi", "nptr", "k_slabs", "b_split")])
 
 
 class DevGemmRoute(ctypes.Structure):

@@ -32,6 +32,7 @@ int fill(const gpfit_dev_gemm_args& d, GemmArgsT<R>& g) {
   g.epi = d.epi;
   g.aux = (R*)d.aux;
   g.sumsq = d.sumsq;
+  g.b_split = d.b_split;
   g.nptr = d.nptr;
   if (d.nptr < 0 || d.nptr > GEMM_MAXB) return d.nptr < 0 ? -3 : 0;  // too many: the launcher's own error, no copy
   for (int b = 0; b < d.nptr; ++b) {
@@ -87,6 +88,22 @@ int64_t plan(const gpfit_dev_gemm_args& d, int kind, int32_t* out, int64_t cap) 
     if (need > cap || !out) return need;
     out[0] = (int32_t)table.size();
     std::memcpy(out + 1, table.data(), table.size() * sizeof(int));
+    return need;
+  }
+  if (kind == 4) {
+    // the same table, every entry with the k range the kernel gives its tile
+    if (r.sched != GEMM_XCD) return -1;
+    std::vector<int> table;
+    if (xcd_plan_host(a, table) != 0) return -1;
+    const int64_t need = 1 + 3 * (int64_t)table.size();
+    if (need > cap || !out) return need;
+    out[0] = (int32_t)table.size();
+    for (size_t e = 0; e < table.size(); ++e) {
+      const int t = table[e];
+      KRange kr{0, 0};
+      if (t >= 0) kr = gemm_tile_k_range(a.a_tri, a.b_tri, a.K, (t >> 16) * TILE, (t & 0xffff) * TILE, TILE, a.b_split);
+      out[1 + 3 * e] = t; out[2 + 3 * e] = kr.beg; out[3 + 3 * e] = kr.end;
+    }
     return need;
   }
   if (kind == 3) {

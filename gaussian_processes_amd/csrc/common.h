@@ -78,7 +78,12 @@ struct GemmArgsT {
                              // of LDS, 320 VGPRs) to the latency-bound kernels of the critical chain instead
                              // of holding every workgroup slot of the chip for its whole duration
   void* sk_ws;               // caller-owned stream-K workspace (>= SK_WS_BYTES); nullptr: process-wide one
-  int reserved;              // unused, always 0: keeps the fields a kernel reads behind it at their offsets
+  int b_split;               // > 0 (a multiple of 128, b_tri == 1): op(B) is dense left of column b_split and lower
+                             // triangular from it on, the triangle's origin at that column: [T21 | T22] = C [S | LV22]
+                             // as one launch.  The columns from b_split on are read from B2 (indexed like B: element
+                             // (k, n) of op(B) at the same offset) where B2 is set.  One problem on the XCD-aware table
+                             // only, which leaves out the tiles whose k range is empty: they stay unwritten
+                             // (gemm_route refuses every other launch of this kind)
   const int* sched;          // device tile table of an XCD-aware schedule (gemm_sched.hip), or nullptr: set by
                              // launch_gemm_xcd, callers leave it null (the table's length is the route's grid)
   // Fused epilogues of the data-parallel launches (gemm.hip; a launch that takes the stream-K schedule cannot
@@ -91,6 +96,7 @@ struct GemmArgsT {
   //      tiles leave theirs per fix-up band behind the per-tile table: GemmRoute::sumsq_entries)
   //   4  dual update: with D = aux (same leading dimension as C), C = alpha op(A) op(B) + D and then
   //      aux = C + D (beta is ignored; replaces a copy and an axpby pass)
+  //   8  added matrix: C = alpha op(A) op(B) + aux, aux only read (beta is ignored; replaces a copy of aux into C)
   int epi;
   R* aux;
   double* sumsq;
@@ -106,6 +112,7 @@ struct GemmArgsT {
   R* Cp[GEMM_MAXB];
   R* auxp[GEMM_MAXB];        // epi 4: problem b's aux
   double* sumsqp[GEMM_MAXB]; // epi 2: problem b's tile-norm table
+  const R* B2;               // b_split: the matrix the columns from b_split on are read from (nullptr: B)
 };
 using GemmArgs = GemmArgsT<double>;
 

@@ -160,6 +160,8 @@ struct CholBatchT {
 // its block (L^-1 costs n^3/3 more); the diagonal sub-block inverses every chain's solves need are always formed
 // (n^3/12).  halves: bit b = chain b needs the inverses of the two diagonal half blocks but not the off-diagonal
 // block [L^-1]21 (for callers that apply L^-1 block-wise, n^3/8 less than need); read at this node only.
+// A chain in neither mask gets its factor and, of the inverse, the top block -- from first halves of VSOLVE_MIN on
+// (fit.hip) only the two diagonal halves of that block: its row solve substitutes block-wise.
 template <typename R>
 int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, Lane lane, uint32_t halves = 0);
 

@@ -104,7 +104,7 @@ double gemm_flops(const GemmArgsT<R>& g, int T) {
   for (int ti = 0; ti < tm; ++ti)
     for (int tj = 0; tj < tn; ++tj) {
       if (g.out_lower && tj / r > ti / r) continue;
-      const KRange kr = gemm_tile_k_range(g.a_tri, g.b_tri, g.K, ti * T, tj * T, T);
+      const KRange kr = gemm_tile_k_range(g.a_tri, g.b_tri, g.K, ti * T, tj * T, T, g.b_split);
       if (kr.end > kr.beg) steps += (kr.end - kr.beg);
     }
   return 2.0 * T * T * steps * (g.nptr > 0 ? g.nptr : (g.batch > 0 ? g.batch : 1));
@@ -134,7 +134,9 @@ int run_gemm(hipStream_t s, const GemmArgsT<R>& g, const GemmRoute& r) {
   if (gemm_logging()) {
     fprintf(stderr, "[gpfit gemm] M %d N %d K %d atri %d btri %d lower %d nb %d tile %d ak %d bk %d epi %d flops %.6e", g.M, g.N, g.K,
             g.a_tri, g.b_tri, g.out_lower, g.nptr > 0 ? g.nptr : 1, r.tile, g.a_kmajor, g.b_kmajor, g.epi, gemm_flops(g, r.tile));
-    gemm_log_tail("", g, "\n");
+    gemm_log_tail("", g, "");
+    if (g.b_split > 0) fprintf(stderr, " bsplit %d", g.b_split);
+    fprintf(stderr, "\n");
   }
   // profile kind 0: the 128-tile kernel family (the dominant kernel), 3: the small-tile instances
   ProfScope ps(s, g_prof ? gemm_flops(g, r.tile) : 0.0, (g_prof && r.tile != TILE) ? 3 : 0);
@@ -188,10 +190,10 @@ static int gemm_splitk_list(Lane lane, Dims d, double alpha, const Operand<R>& a
   return 0;
 }
 
-// tuning knob (bit mask, default all): fused GEMM epilogues -- 1 Q's symmetrisation, 2 T's norm, 4 the H / Z21 update
-// of the two-sided product
+// tuning knob (bit mask, default all): fused GEMM epilogues -- 1 Q's symmetrisation, 2 T's norm (without it T21 and
+// T22 stay two launches), 4 the H / Z21 update of the two-sided product, 8 LV21 added in S's launch
 static int fused_epilogues() {
-  static const int v = getenv("GPFIT_FUSED_EPI") ? atoi(getenv("GPFIT_FUSED_EPI")) : 7;
+  static const int v = getenv("GPFIT_FUSED_EPI") ? atoi(getenv("GPFIT_FUSED_EPI")) : 15;
   return v;
 }
 
@@ -211,7 +213,7 @@ int product(Lane lane, Dims d, double alpha, const Operand<R>& a, const Operand<
   static const bool no_batch = getenv("GPFIT_NO_BATCH") != nullptr;   // tuning knob: every product on its own
   if (cnt == 1 || gemm_pick_tile(g) == TILE || no_batch) {
     auto problem = [&](int i, bool fused) {
-      g.A = a.m.p[i]; g.B = b.m.p[i]; g.C = c.m.p[i];
+      g.A = a.m.p[i]; g.B = b.m.p[i]; g.C = c.m.p[i]; g.B2 = b.split > 0 ? b.p2[i] : nullptr;
       g.epi = fused ? epi : 0; g.aux = fused ? e->aux[i] : nullptr; g.sumsq = fused ? e->sumsq[i] : nullptr;
     };
     GemmRoute routes[GEMM_MAXB];
@@ -255,6 +257,20 @@ template int product<float>(Lane, Dims, double, const Operand<float>&, const Ope
 // the batch: its launches are the same products in the same order, stream-K only ever applies to 128-tile launches of
 // a single problem, and every data-parallel instance sums k in ascending order per element whatever block tile the
 // launcher picks.
+//
+// A chain in neither `need` nor `halves` (V's chain of the closures: the factor only) reads the inverse of a node's first
+// half in one place, the row solve L21 = A21 L11^-T.  From first halves of VSOLVE_MIN on that solve is a block
+// substitution with the inverses of the first half's own two halves (three products, the same flops), and the first
+// half's recursion skips the chain's merge [L11^-1]21: 2 h1^2 h2 flops and two launches off the critical path.
+// Smaller first halves keep the single product: there the merge rides in launches the other chains need anyway and
+// two more dependent launches cost more than it (one size down, first halves of 2048: profiles/r27_top_node.txt).
+// Tuning knob GPFIT_VSOLVE_MIN (0: never).
+constexpr int VSOLVE_MIN = 4096;
+static int vsolve_min() {
+  static const int v = getenv("GPFIT_VSOLVE_MIN") ? atoi(getenv("GPFIT_VSOLVE_MIN")) : VSOLVE_MIN;
+  return v;
+}
+
 template <typename R>
 int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, Lane lane, uint32_t halves) {
   const int64_t ld = B.ld;
@@ -284,10 +300,34 @@ int potrf_lockstep(const CholBatchT<R>& B, int r0, int n, uint32_t need, Lane la
   const int k = n / TILE;
   const int n1 = ((k + 1) / 2) * TILE, n2 = n - n1;
   const int r1 = r0 + n1;
-  GP_TRY(potrf_lockstep<R>(B, r0, n1, all, lane));
+  // the chains whose first half is read by this node's row solve alone (neither `need` nor `halves`): from
+  // VSOLVE_MIN on they substitute with the first half's own blocks and that half skips their merge
+  const uint32_t sub = (vsolve_min() > 0 && n1 >= vsolve_min() && n1 >= 2 * TILE) ? (all & ~(need | halves)) : 0u;
+  const uint32_t full = all & ~sub;
+  GP_TRY(potrf_lockstep<R>(B, r0, n1, full, lane, sub));
   // L21 = A21 L11^-T       (trsm as a GEMM against the explicit inverse)
-  GP_TRY(product(lane, {n2, n1, n1}, 1.0, plain(blk(all, B.A, r1, r0)), trans(tril(blk(all, B.Li, r0, r0))),
-                 into(blk(all, B.L, r1, r0)), walk(W_TRSM)));
+  if (full)
+    GP_TRY(product(lane, {n2, n1, n1}, 1.0, plain(blk(full, B.A, r1, r0)), trans(tril(blk(full, B.Li, r0, r0))),
+                   into(blk(full, B.L, r1, r0)), walk(W_TRSM)));
+  if (sub) {
+    // the same solve against L11 = [P 0; R S] with P^-1 and S^-1 only (the first half's split h1 + h2):
+    //   Z1 = Y1 P^-T ;  Y2 -= Z1 R^T (in A, which the factorisation destroys anyway) ;  Z2 = Y2 S^-T
+    const int h1 = ((n1 / TILE + 1) / 2) * TILE, h2 = n1 - h1;
+    // A half-width solve that is a 128-tile launch of less than two rounds of the chip (4096 x 2048: 512 tiles for 512
+    // workgroup slots) takes as long as its longest tile, the whole k range -- the time of the dense product, which has
+    // twice its flops (profiles/r27_top_node.txt).  On 64-tiles it is four rounds, heavy tiles first.  The one shape
+    // this rests on is the headline's; the bits do not depend on the tile.
+    auto half_solve = [&](Dims d, const Operand<R>& y, const Operand<R>& li, const Output<R>& z) -> int {
+      const bool one_round = gemm_pick_tile(product_args(lane, d, 1.0, y, li, z, walk(W_TRSM))) == TILE &&
+                             (long)(d.M / TILE) * (d.N / TILE) < 2 * SK_SLOTS;
+      return product(lane, d, 1.0, y, li, one_round ? on_tiles(z, 64) : z, walk(W_TRSM));
+    };
+    GP_TRY(half_solve({n2, h1, h1}, plain(blk(sub, B.A, r1, r0)), trans(tril(blk(sub, B.Li, r0, r0))), into(blk(sub, B.L, r1, r0))));
+    GP_TRY(product(lane, {n2, h2, h1}, -1.0, plain(blk(sub, B.L, r1, r0)), trans(blk(sub, B.L, r0 + h1, r0)),
+                   into(blk(sub, B.A, r1, r0 + h1), 1.0)));
+    GP_TRY(half_solve({n2, h2, h2}, plain(blk(sub, B.A, r1, r0 + h1)), trans(tril(blk(sub, B.Li, r0 + h1, r0 + h1))),
+                      into(blk(sub, B.L, r1, r0 + h1))));
+  }
   // the two products that only need L21 and L11^-1:  A22 -= L21 L21^T (syrk, lower tiles only) for every chain, and
   // tmp = L21 Li11, the first product of the inverse merge, for the chains in `need`
   const Operand<R> L21 = plain(blk(all, B.L, r1, r0)), L21t = trans(blk(all, B.L, r1, r0));
@@ -950,6 +990,7 @@ static int demote_for_mixed(gpfit_ctx* c, bool reuse_V, int np, int dp, bool blo
 //   T11 = A LV11 ,  T22 = C LV22                 lower x lower -> lower (one list when the halves are equal)
 //   S = LV21 - L21 T11 ,  T21 = C S              dense x lower, lower x dense; S in Z's 21 block (idle until W):
 //                                                L_V stays intact (its factor may be reused)
+//   from the size where the launch takes the XCD-aware table: T11 alone, then [T21 | T22] = C [S | LV22] as one launch
 // The tiles leave their sums of squares behind (no separate pass over T) where a launch can carry the epilogue;
 // whether it is asked to depends on the single unit's launch only, so a group sums the norm in the unit's order.
 template <typename R>
@@ -971,7 +1012,22 @@ static int t_in_blocks(Lane lane, int cnt, gpfit_ctx* const* cs, const PostJoin<
   };
   auto asks_diag = [&](int nblk) { return asks({nblk, nblk, nblk}, plain(tril(LV0)), into_lower(T0), walk(W_T)); };
   auto asks_21 = [&]() { return asks({n2, n1, n2}, plain(LV0), into(T0), walk(W_MERGE)); };
-  const bool any_fused = asks_diag(n1) > 0 || asks_diag(n2) > 0 || asks_21() > 0;
+  auto blk = [&](auto X, int64_t o) { return mats(cnt, ld, [&](int i) { return a[i].*X + o; }); };
+  // [T21 | T22] = C [S | LV22] as ONE launch of n2 x np x n2 where the single unit's launch qualifies for the XCD-aware
+  // table and carries the tile norms: T21 and T22 share their left operand, and together they are a launch the
+  // table balances (1552 tiles with a k range at N = 8192) where T22 alone went to stream-K and T21 alone to a plain
+  // walk.  op(B) is dense left of column n1 (S, in Z's 21 block) and LV22's lower triangle from it on, read in place
+  // (dense_then_lower); T's strict upper tiles of the 22 block have no k range and stay unwritten, as before.
+  const Dims joint{n2, np, n2};
+  int e_joint = 0;
+  if (fused_epilogues() & 2) {
+    GemmArgsT<R> g1 = product_args(lane, joint, 1.0, plain(tril(mat(a[0].Li + o21 + n1, ld))),
+                                   dense_then_lower(mat(a[0].Z + o21, ld), mat(a[0].LV + o21, ld), n1), into(mat(a[0].T + o21, ld)), walk(W_T));
+    g1.epi = 2; g1.sumsq = cs[0]->frob_part;
+    const GemmRoute r1 = gemm_route(g1);
+    if (r1.rc == 0 && r1.epi) e_joint = r1.sumsq_entries;
+  }
+  const bool any_fused = e_joint > 0 || asks_diag(n1) > 0 || asks_diag(n2) > 0 || asks_21() > 0;
   // the product into T's blocks `out` with the tile norms asked for (e entries per problem, from sums[q] on) or passed
   // over afterwards
   auto normed_product = [&](Dims d, const Operand<R>& A, const Operand<R>& B, const Output<R>& out, int wk, bool ask, Epilogue<R>& e,
@@ -1001,19 +1057,53 @@ static int t_in_blocks(Lane lane, int cnt, gpfit_ctx* const* cs, const PostJoin<
     return 0;
   };
   const int r_both[2] = {0, n1};
-  if (n2 == n1 && 2 * cnt <= GEMM_MAXB) GP_TRY(diag_blocks(2, r_both, n1));
+  if (e_joint > 0) GP_TRY(diag_blocks(1, r_both, n1));
+  else if (n2 == n1 && 2 * cnt <= GEMM_MAXB) GP_TRY(diag_blocks(2, r_both, n1));
   else {
     GP_TRY(diag_blocks(1, r_both, n1));
     GP_TRY(diag_blocks(1, r_both + 1, n2));
   }
   {
-    auto blk = [&](auto X, int64_t o) { return mats(cnt, ld, [&](int i) { return a[i].*X + o; }); };
-    for (int i = 0; i < cnt; ++i)
-      GP_HIP(hipMemcpy2DAsync(a[i].Z + o21, (size_t)ld * sizeof(R), a[i].LV + o21, (size_t)ld * sizeof(R), (size_t)n1 * sizeof(R),
-                              (size_t)n2, hipMemcpyDeviceToDevice, s));
-    // S = LV21 - L21 T11 (in Z's 21 block) ;  T21 = C S
-    GP_TRY(product(lane, {n2, n1, n1}, -1.0, plain(blk(&PJ::L, o21)), plain(tril(blk(&PJ::T, 0))), into(blk(&PJ::Z, o21), 1.0),
-                   walk(W_TMP)));
+    // S = LV21 - L21 T11 (in Z's 21 block): LV21 comes in through the added-matrix epilogue where the launch carries it
+    // (L_V stays intact), else from a copy with beta = 1 -- the same arithmetic
+    const Dims dS{n2, n1, n1};
+    const Operand<R> L21 = plain(blk(&PJ::L, o21)), T11 = plain(tril(blk(&PJ::T, 0)));
+    const Mat<R> S = blk(&PJ::Z, o21);
+    Epilogue<R> add{8};
+    for (int i = 0; i < cnt; ++i) add.aux[i] = const_cast<R*>(a[i].LV) + o21;   // (read only: epilogue 8)
+    bool fused_s = false;
+    if (fused_epilogues() & 8) {
+      GemmArgsT<R> g = product_args(lane, dS, -1.0, L21, T11, into(S), walk(W_TMP));
+      g.epi = 8; g.aux = add.aux[0];
+      fused_s = gemm_route(g).epi != 0;   // (128-tiles only, which are issued unit by unit: the single unit's route decides)
+    }
+    if (fused_s) {
+      GP_TRY(product(lane, dS, -1.0, L21, T11, into(S), walk(W_TMP), &add));
+      if (!add.carried) {
+        set_error("post_join: the added-matrix epilogue of S was announced but not carried");
+        return -100;
+      }
+    } else {
+      if (gemm_logging()) fprintf(stderr, "[gpfit copy] rows %d cols %d problems %d (LV21 into Z21)\n", n2, n1, cnt);
+      for (int i = 0; i < cnt; ++i)
+        GP_HIP(hipMemcpy2DAsync(a[i].Z + o21, (size_t)ld * sizeof(R), a[i].LV + o21, (size_t)ld * sizeof(R), (size_t)n1 * sizeof(R),
+                                (size_t)n2, hipMemcpyDeviceToDevice, s));
+      GP_TRY(product(lane, dS, -1.0, L21, T11, into(S, 1.0), walk(W_TMP)));
+    }
+  }
+  if (e_joint > 0) {
+    // unit by unit (a 128-tile launch each).  The table's tiles leave their norms at ti * tiles_n + tj; the entries of
+    // the tiles that are not in it are zeroed here
+    Epilogue<R> ep{};
+    for (int i = 0; i < cnt; ++i) {
+      ep.sumsq[i] = cs[i]->frob_part + ent;
+      GP_HIP(hipMemsetAsync(ep.sumsq[i], 0, (size_t)e_joint * sizeof(double), s));
+    }
+    GP_TRY(normed_product(joint, plain(tril(blk(&PJ::Li, o21 + n1))), dense_then_lower(blk(&PJ::Z, o21), blk(&PJ::LV, o21), n1),
+                          into(blk(&PJ::T, o21)), walk(W_T), true, ep, "[T21 | T22]"));
+    ent += e_joint;
+  } else {
+    // T21 = C S
     int e = asks_21();
     const bool ask = e > 0;
     if (!ask) e = (n2 / TILE) * (n1 / TILE);

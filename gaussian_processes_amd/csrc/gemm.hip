@@ -56,7 +56,8 @@ __device__ __forceinline__ bool gemm_tile_compute(const GemmArgsT<R>& p, int til
     C = p.C + (int64_t)b * p.sC;
   }
 
-  const KRange kr = gemm_tile_k_range(p.a_tri, p.b_tri, p.K, row0, col0, T);
+  if (p.b_split > 0 && col0 >= p.b_split && p.B2 != nullptr) B = p.B2;   // the triangular part of a split op(B)
+  const KRange kr = gemm_tile_k_range(p.a_tri, p.b_tri, p.K, row0, col0, T, p.b_split);
   int kbeg = kr.beg, kend = kr.end;
   // tri bounds are multiples of T >= 32 = the largest K step, so they stay K-step aligned
   if (slabbed) {
@@ -95,7 +96,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgsT<R>& p, int tiles_
   const int64_t ldc = p.ldc;
   const int M = p.M, N = p.N;
   if constexpr (EPI != 0) {
-    // fused epilogues (common.h: 1 mirror, 2 tile norms, 4 dual update); the launcher has checked that the
+    // fused epilogues (common.h: 1 mirror, 2 tile norms, 4 dual update, 8 added matrix); the launcher has checked that the
     // launch is data-parallel on full tiles
     constexpr int epi = EPI;
     R* __restrict__ D = p.nptr > 0 ? p.auxp[blockIdx.y] : p.aux;
@@ -110,6 +111,8 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgsT<R>& p, int tiles_
         const R d0 = *dd;
         o += d0;
         *dd = o + d0;
+      } else if (epi & 8) {
+        o += D[(int64_t)row * ldc + col];
       } else if (beta != (R)0) {
         o += beta * (*c);
       }
@@ -295,10 +298,21 @@ GemmRoute gemm_route(const GemmArgsT<R>& a) {
   if (T == TILE && !r.edge && a.nptr <= 0 && a.batch <= 1 && a.split_k <= 1 && !a.half_occ &&
       (a.tile == 0 || a.tile == TILE)) {
     static const long xcd_min = getenv("GPFIT_XCD_MIN_TILES") ? atol(getenv("GPFIT_XCD_MIN_TILES")) : 1536;
-    const long tm = a.M / TILE, tn = a.N / TILE, ntiles = a.out_lower ? tm * (tm + 1) / 2 : tm * tn;
+    const long tm = a.M / TILE, tn = a.N / TILE;
+    long ntiles = a.out_lower ? tm * (tm + 1) / 2 : tm * tn;
+    if (a.b_split > 0) {   // the table of a split op(B) holds the tiles with a k range only
+      ntiles = 0;
+      for (long ti = 0; ti < tm; ++ti)
+        for (long tj = 0; tj < tn; ++tj) {
+          const KRange kr = gemm_tile_k_range(a.a_tri, a.b_tri, a.K, (int)ti * TILE, (int)tj * TILE, TILE, a.b_split);
+          ntiles += kr.end > kr.beg;
+        }
+    }
     if ((a.reverse & 8) && !(a.out_lower && a.M != a.N) && tm < 32768 && tn < 32768 && ntiles >= xcd_min) r.sched = GEMM_XCD;
-    else if ((r.sk_first = streamk_first_tile(a, ntiles)) >= 0) r.sched = GEMM_STREAMK;
+    else if (a.b_split <= 0 && (r.sk_first = streamk_first_tile(a, ntiles)) >= 0) r.sched = GEMM_STREAMK;
   }
+  if (a.b_split != 0 && (r.sched != GEMM_XCD || a.b_split < 0 || a.b_split >= a.N || (a.b_split % TILE) || a.b_tri != 1 || a.out_lower))
+    return refuse("launch_gemm: a split op(B) needs a lower triangle from a 128-column on and the XCD-aware table (gemm_route says so beforehand)");
 
   // Fused epilogues: full tiles of one problem or a pointer batch, and the instances that exist (launch_T): 128-tile,
   // row-major A, and per mode the operand layout the fit uses -- the blocks of T = L^-1 L_V with tile norms (lower or
@@ -311,8 +325,8 @@ GemmRoute gemm_route(const GemmArgsT<R>& a) {
   if (a.epi) {
     bool ok = a.split_k <= 1 && a.k_slabs <= 0 && !strided && T == TILE && !(a.M % T) && !(a.N % T) && !a.a_kmajor && !a.half_occ;
     if ((a.epi & 1) && (!a.out_lower || a.M != a.N)) ok = false;
-    if ((a.epi & 4) && a.nptr <= 0 && a.aux == nullptr) ok = false;
-    if (!((a.epi == 2 && a.b_kmajor) || (a.epi == 1 && !a.b_kmajor) || (a.epi == 4 && a.b_kmajor))) ok = false;
+    if ((a.epi & 12) && a.nptr <= 0 && a.aux == nullptr) ok = false;
+    if (!((a.epi == 2 && a.b_kmajor) || (a.epi == 1 && !a.b_kmajor) || ((a.epi == 4 || a.epi == 8) && a.b_kmajor))) ok = false;
     if (r.sched == GEMM_STREAMK && !(r.sk_first == 0 && a.out_lower && a.M == a.N && a.epi == 2 && a.sumsq != nullptr)) ok = false;
     if (!ok) return refuse("launch_gemm: this launch cannot carry a fused epilogue (gemm_route says so beforehand)");
   }
@@ -370,6 +384,7 @@ static void launch_T(const GemmArgsT<R>& p, const GemmRoute& r, hipStream_t s) {
       if (key == 2 * 4 + 1) hipLaunchKernelGGL((gemm_epi_kernel<R, false, true, 2>), grid, block, 0, s, p, tn, tiles);
       else if (key == 1 * 4 + 0) hipLaunchKernelGGL((gemm_epi_kernel<R, false, false, 1>), grid, block, 0, s, p, tn, tiles);
       else if (key == 4 * 4 + 1) hipLaunchKernelGGL((gemm_epi_kernel<R, false, true, 4>), grid, block, 0, s, p, tn, tiles);
+      else if (key == 8 * 4 + 1) hipLaunchKernelGGL((gemm_epi_kernel<R, false, true, 8>), grid, block, 0, s, p, tn, tiles);
     }
     return;
   }

@@ -439,13 +439,16 @@ __host__ __device__ __forceinline__ void gemm_walk_tile(int b, int walk, bool lo
 // THE k range of a tile: op(A) op(B) of the T x T tile at (row0, col0) sums k over [beg, end) -- all of [0, K) for
 // dense operands; a lower triangular op(A) (a_tri 1) has nothing right of the tile's last row, an upper triangular
 // one (2) nothing left of its first; op(B) likewise by the tile's columns (b_tri 1 lower: from the first column on,
-// 2 upper: up to the last).  end <= beg: the tile is zero.  Kernels, planners and the flop count all ask here.
+// 2 upper: up to the last).  b_split > 0 (GemmArgsT::b_split, b_tri 1): op(B) is dense left of that column and lower
+// triangular from it on, with the triangle's origin there.  end <= beg: the tile is zero.  Kernels, planners and the
+// flop count all ask here.
 struct KRange { int beg, end; };
-__host__ __device__ __forceinline__ KRange gemm_tile_k_range(int a_tri, int b_tri, int K, int row0, int col0, int T) {
+__host__ __device__ __forceinline__ KRange gemm_tile_k_range(int a_tri, int b_tri, int K, int row0, int col0, int T,
+                                                             int b_split = 0) {
   int kbeg = 0, kend = K;
   if (a_tri == 1) kend = kend < row0 + T ? kend : row0 + T;
   if (a_tri == 2) kbeg = kbeg > row0 ? kbeg : row0;
-  if (b_tri == 1) kbeg = kbeg > col0 ? kbeg : col0;
+  if (b_tri == 1 && col0 >= b_split) kbeg = kbeg > col0 - b_split ? kbeg : col0 - b_split;
   if (b_tri == 2) kend = kend < col0 + T ? kend : col0 + T;
   return {kbeg, kend};
 }

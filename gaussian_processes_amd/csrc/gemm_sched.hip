@@ -28,7 +28,7 @@ struct Plan {
   int* table = nullptr;  // device
   int blocks = 0;
 };
-using Key = std::tuple<int, int, int, int, int, int, int, int>;  // device, M, N, K, lower, a_tri, b_tri, K step
+using Key = std::tuple<int, int, int, int, int, int, int, int, int>;  // device, M, N, K, lower, a_tri, b_tri, K step, b_split
 std::map<Key, Plan> g_plans;
 std::mutex g_mutex;
 
@@ -43,10 +43,12 @@ int xcd_plan_host(const GemmArgsT<R>& a, std::vector<int>& table) {
   constexpr int KT = 128 / (int)sizeof(R);
   const int tm = a.M / TILE, tn = a.N / TILE;
   auto ksteps = [&](int ti, int tj) {
-    const KRange kr = gemm_tile_k_range(a.a_tri, a.b_tri, a.K, ti * TILE, tj * TILE, TILE);
+    const KRange kr = gemm_tile_k_range(a.a_tri, a.b_tri, a.K, ti * TILE, tj * TILE, TILE, a.b_split);
     const int kb = kr.beg, ke = kr.end;
     return std::max(0, ke - kb) / KT;
   };
+  // a split op(B) (GemmArgsT::b_split): the tiles without a k range are not in the table and stay unwritten
+  const bool skip_empty = a.b_split > 0;
   // tuning knobs: macro-tile rows x columns, and the weight (as a fraction 1/cutdiv of a queue's
   // average load) below which a macro-tile is split into quarters
   static const int gr_env = getenv("GPFIT_XCD_GR") ? atoi(getenv("GPFIT_XCD_GR")) : 2;
@@ -60,6 +62,7 @@ int xcd_plan_host(const GemmArgsT<R>& a, std::vector<int>& table) {
     for (int ti = I0; ti < std::min(I1, tm); ++ti)
       for (int tj = J0; tj < std::min(J1, tn); ++tj) {
         if (a.out_lower && tj > ti) continue;
+        if (skip_empty && ksteps(ti, tj) == 0) continue;
         it.tiles.push_back((ti << 16) | tj);
         it.weight += ksteps(ti, tj) + 2;
       }
@@ -124,7 +127,7 @@ int launch_gemm_xcd(const GemmArgsT<R>& a, GemmRoute r, hipStream_t s) {
   Plan plan;
   {
     std::lock_guard<std::mutex> lock(g_mutex);
-    const Key key{device, a.M, a.N, a.K, a.out_lower, a.a_tri, a.b_tri, (int)sizeof(R)};
+    const Key key{device, a.M, a.N, a.K, a.out_lower, a.a_tri, a.b_tri, (int)sizeof(R), a.b_split};
     auto it = g_plans.find(key);
     if (it == g_plans.end()) {
       Plan np;

@@ -1,6 +1,7 @@
 // How the host code writes one GEMM launch down: C = alpha op(A) op(B) + beta C as the algebra states it, for one
 // problem or for a list of problems of one shape.  Internal header.
 //   product(lane, {M, N, K}, alpha, plain(a) | trans(a), plain(b) | trans(b), into(c, beta) | into_lower(c, beta), walk, &epilogue)
+// (on_tiles(into(c), 64): the same product on the block tile named)
 // a, b, c are Mats: mat(p, ld) names one matrix block, mats(cnt, ld, i -> pointer) the same block of every problem of
 // a list; tril(m) / triu(m) state the triangle of the block AS STORED (what op() makes of it is derived).  A block
 // named through a pointer to const is a Mat<const R>: an operand, never an output (into() of it does not compile).
@@ -35,7 +36,9 @@ template <typename R> Mat<R> tril(Mat<R> m) { m.tri = Lower; return m; }
 template <typename R> Mat<R> triu(Mat<R> m) { m.tri = Upper; return m; }
 
 // op(X): X as stored, or transposed; an operand is read only, whatever it was named through
-template <typename R> struct Operand { Mat<const R> m; bool t; };
+// split > 0: op(B) only -- dense left of column `split`, lower triangular from it on (m.tri says Lower), those columns
+// read from p2 (GemmArgsT::b_split, B2)
+template <typename R> struct Operand { Mat<const R> m; bool t; int split = 0; const R* p2[GEMM_MAXB] = {}; };
 template <typename R> Operand<R> plain(const Mat<const R>& m) { return {m, false}; }
 template <typename R> Operand<R> trans(const Mat<const R>& m) { return {m, true}; }
 template <typename R> Operand<R> plain(const Mat<R>& m) {
@@ -44,10 +47,20 @@ template <typename R> Operand<R> plain(const Mat<R>& m) {
   return o;
 }
 template <typename R> Operand<R> trans(const Mat<R>& m) { Operand<R> o = plain(m); o.t = true; return o; }
+// [dense | lower]: the columns left of `col` from `dense`, the lower triangle from column `col` on from `lower`, both
+// named by the block's origin (column 0) and of one leading dimension
+template <typename R> Operand<R> dense_then_lower(const Mat<R>& dense, const Mat<const R>& lower, int col) {
+  Operand<R> o = plain(tril(dense));
+  o.split = col;
+  for (int i = 0; i < lower.cnt && i < GEMM_MAXB; ++i) o.p2[i] = lower.p[i];
+  return o;
+}
 
-template <typename R> struct Output { Mat<R> m; bool lower; double beta; };   // lower: the tiles on / below the diagonal only
+// lower: the tiles on / below the diagonal only; tile: 0 the launcher's choice, else the block tile asked for
+template <typename R> struct Output { Mat<R> m; bool lower; double beta; int tile = 0; };
 template <typename R> Output<R> into(const Mat<R>& m, double beta = 0.0) { return {m, false, beta}; }
 template <typename R> Output<R> into_lower(const Mat<R>& m, double beta = 0.0) { return {m, true, beta}; }
+template <typename R> Output<R> on_tiles(Output<R> o, int tile) { o.tile = tile; return o; }
 
 // A fused epilogue (GemmArgsT::epi): the request -- which one (0: none) and its per-problem operands -- and the
 // launcher's answer: carried by all launches of the product or by none, and the sumsq entries each left per problem.
@@ -68,6 +81,8 @@ GemmArgsT<R> product_args(Lane lane, Dims d, double alpha, const Operand<R>& a, 
   g.a_kmajor = a.t ? 1 : 0; g.b_kmajor = b.t ? 0 : 1;
   g.out_lower = c.lower ? 1 : 0; g.a_tri = tri(a); g.b_tri = tri(b);
   g.batch = 1; g.split_k = 1; g.reverse = walk; g.sk_ws = lane.sk_ws;
+  g.b_split = b.split; g.B2 = b.split > 0 ? b.p2[0] : nullptr;
+  g.tile = c.tile;
   return g;
 }
 // the same as ONE pointer-batched launch over all problems of the list, with the epilogue's request (if any)

@@ -770,12 +770,15 @@ typedef struct gpfit_dev_gemm_args {
   int32_t split_k;          /* > 1: k slabs, slab z written to C + z sC, beta ignored */
   int32_t tile;             /* 0 automatic, or 128 / 64 / 32 */
   int32_t walk;             /* as gpfit_dgemm_ex */
-  int32_t epi;              /* fused epilogue: 0 none, 1 mirror, 2 tile norms, 4 dual update */
+  int32_t epi;              /* fused epilogue: 0 none, 1 mirror, 2 tile norms, 4 dual update, 8 added matrix (aux read only) */
   int32_t nptr;             /* > 0: pointer batch of nptr problems (at most 32) */
   int32_t k_slabs;          /* > 0: the triangular-operand route (a_tri 2, M == K a multiple of 64): 64-tiles, k in
                              * at most k_slabs fixed slabs, one workgroup per (tile, slab) with a non-empty k range;
                              * slab z of a row panel written to C + z sC, beta ignored; the slabs below a panel's own
                              * k range are not written */
+  int32_t b_split;          /* > 0 (a multiple of 128, b_tri 1): op(B) is dense left of this column and lower triangular
+                             * from it on, the triangle's origin there; XCD-aware table only, whose tiles are those with
+                             * a non-empty k range (the others stay unwritten) */
 } gpfit_dev_gemm_args;
 
 typedef struct gpfit_dev_gemm_route_t {
@@ -804,6 +807,7 @@ int gpfit_dev_gemm_route(int is_f32, const gpfit_dev_gemm_args* args, const gpfi
  *   then ntiles records (row0, col0, kbeg, ksteps, prefix) in walk order, fix_tile[nfix] (indices into the
  *   records), fix_ptr[nfix + 1], fix_slot[nslot].
  * kind 1, XCD-aware table: out[0] = length, then the table (ti << 16 | tj, -1 padding).
+ * kind 4, the same table with each tile's k range: out[0] = length, then per entry (ti << 16 | tj or -1, kbeg, kend).
  * kind 3, slab plan of the k_slabs route: out[0..3] = items, live slabs, k per slab, tile; then per item in launch
  *   order (row panel, slab, kbeg, kend); every tile column of a panel runs the same items.
  * Returns the number of int32 the plan takes (nothing is written when that exceeds cap), -1 when the launch does
