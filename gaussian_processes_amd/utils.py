@@ -725,8 +725,8 @@ _CELLS = threading.local()   # .rendezvous: the _ChainRendezvous of the varGP_ce
 # ------------------------------------------------------------------ requests: what a device call of a fit is made of
 # A call that the fits of a varGP_cells wave can share is prepared as a request: a dict with its ``kind`` (and, for a
 # closure, its ``regime``), the operands on the device, the scalars, and the workspace (``engine``) and stream it runs
-# on.  _REQUEST_KINDS (below the closures) describes each kind; the four helpers here marshal a list of requests into
-# the per-unit tables of a batch entry point.
+# on.  _REQUEST_KINDS (below the closures) describes each kind; the first four helpers here marshal a list of requests
+# into the per-unit tables of a batch entry point, the fifth gives a request its workspace and stream.
 def _ctx_table(ctxs):
     """The contexts of a batch call, given as engines' ``_ctx`` values or as raw integers."""
     return (ctypes.c_void_p * len(ctxs))(*[c.value if isinstance(c, ctypes.c_void_p) else c for c in ctxs])
@@ -747,6 +747,15 @@ def _ld_table(qs, key, default, override=None):
 def _flat(qs, key):
     """The per-request lists of floats ``q[key]``, one behind the other."""
     return _lib.darr([v for q in qs for v in q[key]])
+
+
+def _request_place(q, engine, *size):
+    """Where the request ``q`` runs: on the workspace ``engine``, or without one on this thread's for ``size`` (``n, d,
+    d_full`` of ``get_engine``), and on the requesting thread's stream -- under ``varGP_cells`` another thread may issue
+    the call.  Returns ``q``."""
+    q["engine"] = engine if engine is not None else get_engine(*size)
+    q["stream"] = _stream()
+    return q
 
 
 def _estep_chain(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
@@ -797,7 +806,7 @@ def _estep_chain_damped(r, KKtilde_inv, aL, L, Linv, kv0, V, m, f_mean, logA0, a
 
 def _chain_request(kind, operands, N, nv, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed, V, lambda_m, lambda_var,
                    engine):
-    """What the requests of the two chain kinds share: the fixed ``operands`` (name -> tensor, contiguous on the device),
+    """What the requests of the three chain kinds share: the fixed ``operands`` (name -> tensor, contiguous on the device),
     the scalars, the state ``(m, f, V, lam_m, lam_var)`` as copies of its own -- the call updates them in place, the
     arguments are left alone; ``V`` (nv x nv) and the moments (N) not given start uninitialised -- and the workspace and
     stream the call runs on, this thread's unless an engine is given."""
@@ -809,9 +818,7 @@ def _chain_request(kind, operands, N, nv, m, f_mean, logA0, n_steps, n_fparam_st
          "lambda0_fixed": None if lambda0_fixed is None else float(lambda0_fixed)}
     q["m"], q["f"] = _cu(m).clone().contiguous(), _cu(f_mean).clone().contiguous()
     q["V"], q["lam_m"], q["lam_var"] = own(V, nv, nv), own(lambda_m, N), own(lambda_var, N)
-    q["engine"] = engine if engine is not None else get_engine(max(N, nv), 1)
-    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
-    return q
+    return _request_place(q, engine, max(N, nv), 1)
 
 
 def _chain_prepare(r, KKtilde_inv, aL, L, kv0, m, f_mean, logA0, n_steps, n_fparam_steps, lambda0_fixed=None, V=None,
@@ -860,48 +867,69 @@ def _chain_result(q, u, rec):
     return q["m"], q["V"], q["lam_m"], q["lam_var"], q["f"], [list(rec[first + 12 * k:first + 12 * k + 12]) for k in range(n)]
 
 
+# The argument lists of the three chain kinds (include/gpfit_mi355x.h) differ in three things: the matrices in front of
+# N, a pointer and a leading dimension each; whether nb follows N -- the projected kinds, where it is also the leading
+# dimension that goes with a null pointer (the full-rank kind has N for that, and takes a leading dimension given as
+# q["ldk"] / q["ldv"] in place of the tensor's); and whether the step size alpha precedes lambda0_mode.
+_CHAIN_HEADS = {"chain": (("a", "aL", "L"), True, False), "chain_full": (("K",), False, False),
+                "chain_damped": (("a", "aL", "L", "Linv"), True, True)}
+
+
+def _chain_call(kind, ctxs, qs, rec=None):
+    """An entry point of the chain kind ``kind`` on the requests ``qs``: the batch one, ``gpfit_estep_<kind>_batch``, with
+    the contexts ``ctxs`` (one per request), or with ``ctxs`` None the single one, ``gpfit_estep_<kind>``, on ``qs[0]``
+    and its own workspace.  One list serves both: where the batch call takes a table with an entry per unit, the single
+    call takes the entry of its one unit.  Returns the return code and the records, nothing checked here -- the shared
+    arguments are those of ``qs[0]``, except that damped requests which disagree on the step size have none (NaN, which
+    the entry point refuses).  A tensor given as None goes in as a null pointer; ``rec``: the caller's array instead of a
+    new one."""
+    heads, has_nb, has_alpha = _CHAIN_HEADS[kind]
+    batch, q0, fixed = ctxs is not None, qs[0], qs[0]["lambda0_fixed"] is not None
+    rec = _chain_rec_array(q0, len(qs)) if rec is None else rec
+    ld_default, ld_given = ("nb", {}) if has_nb else ("N", {"K": "ldk", "V": "ldv"})
+
+    def per_unit(table):
+        return table if batch else table[0]
+
+    def ptr(key):
+        return per_unit(_ptr_table(qs, key))
+
+    def ld(key):
+        return per_unit(_ld_table(qs, key, ld_default, ld_given.get(key)))
+    args = [v for key in heads for v in (ptr(key), ld(key))] + [q0["N"]]
+    if has_nb:
+        args.append(per_unit((ctypes.c_int64 * len(qs))(*[q["nb"] for q in qs])))
+    args += [ptr("r"), ptr("kv0"), ptr("m"), ptr("f"), ptr("V"), ld("V"), ptr("lam_m"), ptr("lam_var"),
+             per_unit(_lib.darr([q["logA0"] for q in qs]))]
+    if has_alpha:
+        args.append(q0["alpha"] if all(q["alpha"] == q0["alpha"] for q in qs) else float("nan"))
+    args += [1 if fixed else 0, per_unit(_lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs])), q0["n_steps"],
+             q0["nfp"], q0["nfp"], *_FPARAM_LBFGS, rec]
+    where = (_ctx_table(ctxs), len(qs)) if batch else (q0["engine"]._ctx,)
+    entry = getattr(_lib.load(), "gpfit_estep_" + kind + ("_batch" if batch else ""))
+    return entry(*where, q0["stream"], *args), rec
+
+
+def _chain_single(kind, q):
+    """``gpfit_estep_<kind>`` on one request, checked: the request's state and its records (``_chain_result``)."""
+    rc, rec = _chain_call(kind, None, [q])
+    _lib.check(rc, "gpfit_estep_" + kind)
+    return _chain_result(q, 0, rec)
+
+
 def _chain_run_single(q):
     """``gpfit_estep_chain`` on one request."""
-    rec = _chain_rec_array(q)
-    fixed = q["lambda0_fixed"] is not None
-    a, aL, L, V = q["a"], q["aL"], q["L"], q["V"]
-    _lib.check(_lib.load().gpfit_estep_chain(q["engine"]._ctx, q["stream"], a.data_ptr(), a.stride(0), aL.data_ptr(),
-                                             aL.stride(0), L.data_ptr(), L.stride(0), q["N"], q["nb"], q["r"].data_ptr(),
-                                             q["kv0"].data_ptr(), q["m"].data_ptr(), q["f"].data_ptr(), V.data_ptr(),
-                                             V.stride(0), q["lam_m"].data_ptr(), q["lam_var"].data_ptr(), q["logA0"],
-                                             1 if fixed else 0, q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"],
-                                             q["nfp"], *_FPARAM_LBFGS, rec),
-               "gpfit_estep_chain")
-    return _chain_result(q, 0, rec)
+    return _chain_single("chain", q)
 
 
 def _chain_full_run_single(q):
     """``gpfit_estep_chain_full`` on one request."""
-    rec = _chain_rec_array(q)
-    fixed = q["lambda0_fixed"] is not None
-    K, V = q["K"], q["V"]
-    _lib.check(_lib.load().gpfit_estep_chain_full(q["engine"]._ctx, q["stream"], K.data_ptr(), K.stride(0), q["N"],
-                                                  q["r"].data_ptr(), q["kv0"].data_ptr(), q["m"].data_ptr(),
-                                                  q["f"].data_ptr(), V.data_ptr(), V.stride(0), q["lam_m"].data_ptr(),
-                                                  q["lam_var"].data_ptr(), q["logA0"], 1 if fixed else 0,
-                                                  q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"], q["nfp"],
-                                                  *_FPARAM_LBFGS, rec),
-               "gpfit_estep_chain_full")
-    return _chain_result(q, 0, rec)
+    return _chain_single("chain_full", q)
 
 
 def _chain_damped_run_single(q):
     """``gpfit_estep_chain_damped`` on one request."""
-    rec = _chain_rec_array(q)
-    fixed = q["lambda0_fixed"] is not None
-    a, aL, L, Linv, V = q["a"], q["aL"], q["L"], q["Linv"], q["V"]
-    _lib.check(_lib.load().gpfit_estep_chain_damped(
-        q["engine"]._ctx, q["stream"], a.data_ptr(), a.stride(0), aL.data_ptr(), aL.stride(0), L.data_ptr(), L.stride(0),
-        Linv.data_ptr(), Linv.stride(0), q["N"], q["nb"], q["r"].data_ptr(), q["kv0"].data_ptr(), q["m"].data_ptr(),
-        q["f"].data_ptr(), V.data_ptr(), V.stride(0), q["lam_m"].data_ptr(), q["lam_var"].data_ptr(), q["logA0"], q["alpha"],
-        1 if fixed else 0, q["lambda0_fixed"] if fixed else 0.0, q["n_steps"], q["nfp"], q["nfp"], *_FPARAM_LBFGS, rec),
-               "gpfit_estep_chain_damped")
-    return _chain_result(q, 0, rec)
+    return _chain_single("chain_damped", q)
 
 
 def _chain_damped_bucket_key(q):
@@ -912,22 +940,8 @@ def _chain_damped_bucket_key(q):
 
 def _chain_damped_batch_raw(ctxs, qs, rec=None):
     """``gpfit_estep_chain_damped_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return
-    code and the records, nothing checked here -- the shared arguments are those of ``qs[0]``, except that requests
-    which disagree on the step size have none (NaN, which the entry point refuses).  A tensor given as None goes in as a
-    null pointer; ``rec``: the caller's array instead of a new one."""
-    q0 = qs[0]
-    fixed = q0["lambda0_fixed"] is not None
-    rec = _chain_rec_array(q0, len(qs)) if rec is None else rec
-    alpha = q0["alpha"] if all(q["alpha"] == q0["alpha"] for q in qs) else float("nan")
-    rc = _lib.load().gpfit_estep_chain_damped_batch(
-        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "a"), _ld_table(qs, "a", "nb"), _ptr_table(qs, "aL"),
-        _ld_table(qs, "aL", "nb"), _ptr_table(qs, "L"), _ld_table(qs, "L", "nb"), _ptr_table(qs, "Linv"),
-        _ld_table(qs, "Linv", "nb"), q0["N"], (ctypes.c_int64 * len(qs))(*[q["nb"] for q in qs]), _ptr_table(qs, "r"),
-        _ptr_table(qs, "kv0"), _ptr_table(qs, "m"), _ptr_table(qs, "f"), _ptr_table(qs, "V"), _ld_table(qs, "V", "nb"),
-        _ptr_table(qs, "lam_m"), _ptr_table(qs, "lam_var"), _lib.darr([q["logA0"] for q in qs]), alpha, 1 if fixed else 0,
-        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], *_FPARAM_LBFGS,
-        rec)
-    return rc, rec
+    code and the records, unchecked (``_chain_call``); requests which disagree on the step size go in with NaN."""
+    return _chain_call("chain_damped", ctxs, qs, rec)
 
 
 def _chain_bucket_key(q):
@@ -945,38 +959,15 @@ def _chain_full_bucket_key(q):
 
 def _chain_batch_raw(ctxs, qs, rec=None):
     """``gpfit_estep_chain_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return code
-    and the records, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as None goes
-    in as a null pointer; ``rec``: the caller's array instead of a new one."""
-    q0 = qs[0]
-    fixed = q0["lambda0_fixed"] is not None
-    rec = _chain_rec_array(q0, len(qs)) if rec is None else rec
-    rc = _lib.load().gpfit_estep_chain_batch(
-        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "a"), _ld_table(qs, "a", "nb"), _ptr_table(qs, "aL"),
-        _ld_table(qs, "aL", "nb"), _ptr_table(qs, "L"), _ld_table(qs, "L", "nb"), q0["N"],
-        (ctypes.c_int64 * len(qs))(*[q["nb"] for q in qs]), _ptr_table(qs, "r"), _ptr_table(qs, "kv0"), _ptr_table(qs, "m"),
-        _ptr_table(qs, "f"), _ptr_table(qs, "V"), _ld_table(qs, "V", "nb"), _ptr_table(qs, "lam_m"), _ptr_table(qs, "lam_var"),
-        _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
-        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], *_FPARAM_LBFGS,
-        rec)
-    return rc, rec
+    and the records, unchecked (``_chain_call``)."""
+    return _chain_call("chain", ctxs, qs, rec)
 
 
 def _chain_full_batch_raw(ctxs, qs, rec=None):
     """``gpfit_estep_chain_full_batch`` on the requests ``qs`` with the contexts ``ctxs`` (one per request): the return
-    code and the records, nothing checked here -- the shared arguments are those of ``qs[0]``.  A tensor given as None
-    goes in as a null pointer, a leading dimension given as ``q["ldk"]`` / ``q["ldv"]`` replaces the tensor's; ``rec``: the
-    caller's array instead of a new one."""
-    q0 = qs[0]
-    fixed = q0["lambda0_fixed"] is not None
-    rec = _chain_rec_array(q0, len(qs)) if rec is None else rec
-    rc = _lib.load().gpfit_estep_chain_full_batch(
-        _ctx_table(ctxs), len(qs), q0["stream"], _ptr_table(qs, "K"), _ld_table(qs, "K", "N", "ldk"), q0["N"],
-        _ptr_table(qs, "r"), _ptr_table(qs, "kv0"), _ptr_table(qs, "m"), _ptr_table(qs, "f"), _ptr_table(qs, "V"),
-        _ld_table(qs, "V", "N", "ldv"), _ptr_table(qs, "lam_m"), _ptr_table(qs, "lam_var"),
-        _lib.darr([q["logA0"] for q in qs]), 1 if fixed else 0,
-        _lib.darr([q["lambda0_fixed"] if fixed else 0.0 for q in qs]), q0["n_steps"], q0["nfp"], q0["nfp"], *_FPARAM_LBFGS,
-        rec)
-    return rc, rec
+    code and the records, unchecked (``_chain_call``); a leading dimension given as ``q["ldk"]`` / ``q["ldv"]`` replaces
+    the tensor's."""
+    return _chain_call("chain_full", ctxs, qs, rec)
 
 
 def _group_engines(count, n, d=1, d_full=1, exact=False):
@@ -1000,14 +991,17 @@ def _group_engines(count, n, d=1, d_full=1, exact=False):
     return (mine + fitting + new)[:count]
 
 
-def _units_group(name, units, size, prepare, steps=None, exact=False):
-    """What the four ``*_group(units)`` functions share: 1 .. 16 units, one workspace each (``size(units)``: ``n, d,
-    d_full`` of ``_group_engines``), one request each (``prepare(engine=..., **unit)``) and one device call.  Chains
-    (``steps`` None) go to the batch entry point whatever their number: what ``_request_run_group`` returns.  A closure
-    alone goes to the single entry point, and every closure is finished (``_closure_finish`` with ``steps``): a unit
-    whose call would raise has the exception in its place."""
+def _units_group(name, units, size, prepare, steps=None, exact=False, check=None):
+    """What the ``*_group(units)`` functions of the request kinds share: 1 .. 16 units (then ``check(units)``, which raises
+    for a list the wrapper refuses before any workspace is taken), one workspace each (``size(units)``: ``n, d, d_full``
+    of ``_group_engines``, ``exact`` handed on), one request each (``prepare(engine=..., **unit)``) and one device call.
+    Chains and the halves of a basis rebuild (``steps`` None) go to the batch entry point whatever their number: what
+    ``_request_run_group`` returns.  A closure alone goes to the single entry point, and every closure is finished
+    (``_closure_finish`` with ``steps``): a unit whose call would raise has the exception in its place."""
     if not 1 <= len(units) <= MAX_CHAIN_UNITS:
         raise ValueError(f"{name}: 1 .. {MAX_CHAIN_UNITS} units per call")
+    if check is not None:
+        check(units)
     engines = _group_engines(len(units), *size(units), exact=exact)
     qs = [prepare(engine=e, **u) for u, e in zip(units, engines)]
     if steps is None:
@@ -1073,9 +1067,7 @@ def _sweeps_prepare(K, Q, Y=None, shifts=(), want_rr=True, engine=None):
     q = {"kind": "sweeps", "K": K, "Q": Q.contiguous().clone(), "Y": block(N, k) if Y is None else Y, "W": block(N, k),
          "S": block(k, k) if want_rr else None, "N": N, "k": k, "shifts": [float(v) for v in shifts],
          "flags": (0 if Y is None else _SWEEPS_Y_READY) | (_SWEEPS_WANT_RR if want_rr else 0)}
-    q["engine"] = engine if engine is not None else get_engine(k, 1)
-    q["stream"] = _stream()
-    return q
+    return _request_place(q, engine, k, 1)
 
 
 def _sweeps_bucket_key(q):
@@ -1117,17 +1109,6 @@ def _sweeps_run_single(q):
     return _sweeps_result(q, 0, rec)
 
 
-def _sweeps_run_group(qs):
-    """One ``gpfit_subspace_sweeps_batch`` call on requests of one bucket (``_sweeps_bucket_key``), each on its own
-    workspace; per request what ``_sweeps_run_single`` returns, with the same bits."""
-    if len({_sweeps_bucket_key(q) for q in qs}) != 1:
-        raise ValueError("gpfit_subspace_sweeps_batch: the requests of one call share the device, the stream, N, the block "
-                         "width, the flags and the capacity of their workspaces")
-    rc, rec = _sweeps_batch_raw([q["engine"]._ctx for q in qs], qs)
-    _lib.check(rc, "gpfit_subspace_sweeps_batch")
-    return [_sweeps_result(q, u, rec) for u, q in enumerate(qs)]
-
-
 def _basis_sweeps(K, Q, Y, shifts, want_rr):
     """The ``sweep_chain`` of ``eigtop.top_eigenpairs`` on the library: the rest of a pass of the subspace iteration --
     per shift ``Y = K Q`` (not for the first when ``Y`` is given), ``Y -= shift Q``, CholeskyQR (twice on the last) -- and
@@ -1135,8 +1116,7 @@ def _basis_sweeps(K, Q, Y, shifts, want_rr):
     thread's workspace, with the bits of the loop through ``matmul`` and ``cholesky``.  Returns ``(Q, Y, S)`` as new
     tensors (``Y`` given is overwritten), or None when a Gram matrix was not positive definite.  With ``BASIS_GROUPS`` on,
     in a fit of ``varGP_cells`` the device call is the wave's (``_submit``)."""
-    q = _sweeps_prepare(K, Q, Y, shifts, want_rr)
-    return _submit(q) if BASIS_GROUPS else _sweeps_run_single(q)
+    return _submit(_sweeps_prepare(K, Q, Y, shifts, want_rr))
 
 
 def _basis_sweeps_group(units):
@@ -1146,10 +1126,8 @@ def _basis_sweeps_group(units):
     workspace capacity)`` -- all with or all without ``Y``, the same ``want_rr``; the numbers of shifts may differ --
     otherwise a ValueError before any call.  Returns, per unit, what ``_basis_sweeps`` returns for it, bit for bit: a
     unit whose factorisation fails has None in its place and stops alone."""
-    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
-        raise ValueError(f"_basis_sweeps_group: 1 .. {MAX_CHAIN_UNITS} units per call")
-    engines = _group_engines(len(units), max(int(u["Q"].shape[1]) for u in units), exact=True)
-    return _sweeps_run_group([_sweeps_prepare(engine=e, **u) for u, e in zip(units, engines)])
+    return _units_group("_basis_sweeps_group", units, lambda us: (max(int(u["Q"].shape[1]) for u in us),), _sweeps_prepare,
+                        exact=True)
 
 
 # ------------------------------------------------------------------ the projector step of a basis rebuild as device calls
@@ -1175,9 +1153,7 @@ def _sign_prepare(S, tau, X=None, X2=None, cs=(), its0=0, engine=None):
     q = {"kind": "sign", "S": S.contiguous(), "tau": float(tau), "X": block() if X is None else X,
          "X2": block() if X2 is None else X2, "W": block(), "k": k, "c": [float(v) for v in cs], "its0": int(its0),
          "flags": (_SIGN_CAYLEY if X is None else 0) | (0 if X2 is None else _SIGN_X2_READY)}
-    q["engine"] = engine if engine is not None else get_engine(k, 1)
-    q["stream"] = _stream()
-    return q
+    return _request_place(q, engine, k, 1)
 
 
 def _sign_bucket_key(q):
@@ -1218,17 +1194,6 @@ def _sign_run_single(q):
     return _sign_result(q, 0, rec)
 
 
-def _sign_run_group(qs):
-    """One ``gpfit_sign_steps_batch`` call on requests of one bucket (``_sign_bucket_key``), each on its own workspace;
-    per request what ``_sign_run_single`` returns, with the same bits."""
-    if len({_sign_bucket_key(q) for q in qs}) != 1:
-        raise ValueError("gpfit_sign_steps_batch: the requests of one call share the device, the stream, k, the flags, the "
-                         "schedule and the capacity of their workspaces")
-    rc, rec = _sign_batch_raw([q["engine"]._ctx for q in qs], qs)
-    _lib.check(rc, "gpfit_sign_steps_batch")
-    return [_sign_result(q, u, rec) for u, q in enumerate(qs)]
-
-
 def _sign_steps(S, tau, X, X2, cs, its0):
     """The ``sign_chain`` of ``eigtop._kept_subspace`` on the library: a stretch of the projector step -- the Cayley
     transform of ``S`` when ``X`` is None, one step of the scaled sign iteration per scaling of ``cs`` (``X2`` given is the
@@ -1237,8 +1202,7 @@ def _sign_steps(S, tau, X, X2, cs, its0):
     bits of the loop through ``cholesky``, ``matmul`` and ``gemm_into``.  Returns ``(X, X2)`` (``X`` and ``X2`` given are
     overwritten; ``S`` is left alone), or None when ``S + tau I`` was not positive definite.  With ``BASIS_GROUPS`` on, in
     a fit of ``varGP_cells`` the device call is the wave's (``_submit``)."""
-    q = _sign_prepare(S, tau, X, X2, cs, its0)
-    return _submit(q) if BASIS_GROUPS else _sign_run_single(q)
+    return _submit(_sign_prepare(S, tau, X, X2, cs, its0))
 
 
 def _sign_steps_group(units):
@@ -1248,42 +1212,39 @@ def _sign_steps_group(units):
     workspace capacity)`` -- all with or all without ``X``, all with or all without ``X2``, the same schedule -- otherwise a
     ValueError before any call.  Returns, per unit, what ``_sign_steps`` returns for it, bit for bit: a unit whose
     factorisation fails has None in its place and fails alone."""
-    if not 1 <= len(units) <= MAX_CHAIN_UNITS:
-        raise ValueError(f"_sign_steps_group: 1 .. {MAX_CHAIN_UNITS} units per call")
-    shared = {(int(u["S"].shape[0]), u.get("X") is None, u.get("X2") is None, int(u.get("its0", 0)),
-               tuple(float(v) for v in u["cs"])) for u in units}
-    if len(shared) != 1:
-        raise ValueError("_sign_steps_group: the units of one call share k, the flags (all with or all without X and X2) and "
-                         "the schedule (its0 and cs)")
-    engines = _group_engines(len(units), int(units[0]["S"].shape[0]), exact=True)
-    return _sign_run_group([_sign_prepare(engine=e, **u) for u, e in zip(units, engines)])
+    def check(us):
+        if len({(int(u["S"].shape[0]), u.get("X") is None, u.get("X2") is None, int(u.get("its0", 0)),
+                 tuple(float(v) for v in u["cs"])) for u in us}) != 1:
+            raise ValueError("_sign_steps_group: the units of one call share k, the flags (all with or all without X and X2) "
+                             "and the schedule (its0 and cs)")
+    return _units_group("_sign_steps_group", units, lambda us: (int(us[0]["S"].shape[0]),), _sign_prepare, exact=True,
+                        check=check)
 
 
-_BOOKS = ("", "closure_", "full_", "full_closure_")   # the prefixes of the counters a call of the rendezvous is counted in
-_LOSS_BOOK = "loss_"                                  # ... and the book of the loss evaluations (_LOSS_KIND), kept beside them
-_BASIS_BOOK = "basis_"                                # ... and the book of the basis rebuilds (_SWEEPS_KIND, _SIGN_KIND)
-_ALL_BOOKS = _BOOKS + (_LOSS_BOOK, _BASIS_BOOK)
+# The books: the prefixes of the counters a call of the rendezvous is counted in, each named by the records of
+# _REQUEST_KINDS whose calls it counts.
+_ALL_BOOKS = ("", "closure_", "full_", "full_closure_", "loss_", "basis_")
 
 
 class _ChainRendezvous:
     """Where the fits of one ``varGP_cells`` wave meet.  Each of ``parties`` host threads runs one fit; a fit that
-    reaches its E-steps hands its chain request to ``call`` and waits.  When every fit still alive has arrived, the
-    last one to arrive sorts the requests into buckets by ``key`` and issues ``group`` once per bucket (``single`` for a
+    reaches a device call that the wave shares hands its request to ``call`` and waits.  When every fit still alive has
+    arrived, the last one to arrive sorts the requests into buckets by ``key`` and issues ``group`` once per bucket (``single`` for a
     bucket of one, ``group`` in slices of ``max_units`` for a larger one), then hands every fit its result.  A fit's
     thread starts with ``enter``; a fit that ends, fails or will never ask (``leave``) is no longer waited for.  An
     exception of a call is raised in every fit whose request was part of that call.  ``group_sizes``: the units of
     every call issued, in order.
 
-    A wave's fits hand in several kinds of request -- the E-step chains and the M-step closures of their L-BFGS, whose
-    line searches differ from cell to cell -- so at any moment some fits wait with a closure and others with a chain.
-    The rendezvous does not tell them apart: ``single``, ``group`` and ``key`` dispatch on the request's kind
-    (``_REQUEST_KINDS``), and ``key`` carries the kind, so two kinds never share a call.  Only the bookkeeping looks at
-    it: per book of ``_ALL_BOOKS`` there are three counters, ``<book>group_sizes`` / ``<book>call_seconds`` /
-    ``seconds_in_<book>call``, and a call is counted in the book of its kind -- the projected chains in ``""`` (a request
-    without a kind included), the sparse and truncated closures in ``"closure_"``, and the full-rank regime in two
-    books of its own, its chains in ``"full_"`` and its closures in ``"full_closure_"``; the loss evaluations of every
-    regime in ``"loss_"`` (``_LOSS_BOOK``); the sweeps and the sign stretches of the basis rebuilds, when they come here
-    (``BASIS_GROUPS``), in ``"basis_"`` (``_BASIS_BOOK``)."""
+    A wave's fits hand in the nine kinds of request of ``_REQUEST_KINDS`` -- the E-step chains, the M-step closures of
+    their L-BFGS, whose line searches differ from cell to cell, the loss evaluations, the halves of the basis rebuilds
+    -- so at any moment some fits wait with a closure and others with a chain.  The rendezvous does not tell them
+    apart: ``single``, ``group`` and ``key`` dispatch on the request's kind, and ``key`` carries the kind, so two kinds
+    never share a call.  Only the bookkeeping looks at it: per book of ``_ALL_BOOKS`` there are three counters,
+    ``<book>group_sizes`` / ``<book>call_seconds`` / ``seconds_in_<book>call``, and a call is counted in the book of its
+    kind -- the projected chains, damped ones among them, in ``""`` (a request without a kind included), the sparse and
+    truncated closures in ``"closure_"``, and the full-rank regime in two books of its own, its chains in ``"full_"``
+    and its closures in ``"full_closure_"``; the loss evaluations of every regime in ``"loss_"``; the sweeps and the sign
+    stretches of the basis rebuilds, when they come here (``BASIS_GROUPS``), in ``"basis_"``."""
 
     def __init__(self, parties, single, group, key, max_units=MAX_CHAIN_UNITS):
         self.cond = threading.Condition()
@@ -2296,10 +2257,9 @@ def _closure_prepare(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params, xtilde
     else:
         q.update(regime="truncated", N=int(Bc.shape[0]), args=(theta, lims, n_px_side, x, r, B, m_b, V_b, f_params))
         n_max = q["N"]
-    q["engine"] = engine if engine is not None else get_engine(n_max, xc.shape[1], rows * cols)
+    _request_place(q, engine, n_max, xc.shape[1], rows * cols)
     if not sparse:
         q["cap"] = -(-q["engine"].n_max // 128) * 128
-    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
     return q
 
 
@@ -2505,9 +2465,8 @@ def _closure_full(theta, lims, n_px_side, x, r, m, V, f_params, reuse_V):
          "n_px_side": n_px_side, "rows": rows, "cols": cols, "x": xc, "r": _cu(r), "m": _cu(m), "V": _cu(V),
          "N": int(xc.shape[0]), "logA": _scalar(f_params['logA']), "lambda0": _scalar(_lambda0_of(f_params)),
          "reuse_V": bool(reuse_V)}
-    q["engine"] = get_engine(q["N"], xc.shape[1], rows * cols)
+    _request_place(q, None, q["N"], xc.shape[1], rows * cols)
     q["cap"] = -(-q["engine"].n_max // 128) * 128
-    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
     return _submit(q)
 
 
@@ -2561,9 +2520,7 @@ def _loss_prepare(r, f_mean, lambda_m, f_params, m, V, K_tilde, K_tilde_inv, log
          "K": None if logdet_K is not None else _cu(K_tilde), "N": int(r.shape[0]), "nb": nb,
          "logdet_K": None if logdet_K is None else float(logdet_K), "logA": _scalar(f_params['logA']),
          "lambda0": _scalar(_lambda0_of(f_params))}
-    q["engine"] = engine if engine is not None else get_engine(nb, 1)
-    q["stream"] = _stream()      # the requesting thread's: under varGP_cells another thread may issue the call
-    return q
+    return _request_place(q, engine, nb, 1)
 
 
 def _loss_result(q, u, out, info):
@@ -2629,75 +2586,58 @@ def elbo_terms(r, f_mean, lambda_m, f_params, m, V, K_tilde, K_tilde_inv, logdet
     return loglikelihood, compute_KL_div(m, V, K_tilde, K_tilde_inv, dK_tilde=None, ignore_warning=ignore_warning)
 
 
-# What the rendezvous of varGP_cells is given: five kinds of chain and closure request here and the loss below them
-# (_LOSS_KIND), one record each.  ``book``: the counters its calls are counted in (_ALL_BOOKS); ``gated``: FULL_RANK_GROUPS off keeps it out of the rendezvous; ``run_single(q)``: the single
-# entry point; ``batch(ctxs, qs)``: the batch entry point ``entry``, unchecked -- its return code, then its output
-# arrays; ``unit(q, u, *arrays)``: the result of unit u cut out of them, what run_single returns for q alone;
-# ``key(q)``: requests of one kind with equal keys may share a call; ``share``: what that means, for the error.
-_RequestKind = collections.namedtuple("_RequestKind", "kind regime book gated run_single entry batch unit key share")
+# What the rendezvous of varGP_cells is given: the kinds of request, one record each, keyed by (kind, regime) -- only a
+# closure request has a regime.  ``book``: the counters its calls are counted in (one of _ALL_BOOKS); ``switch``: the
+# name of the module switch that, off, keeps the kind out of the rendezvous (None: the kind always goes there);
+# ``run_single(q)``: the single entry point; ``batch(ctxs, qs)``: the batch entry point ``entry``, unchecked -- its return
+# code, then its output arrays; ``unit(q, u, *arrays)``: the result of unit u cut out of them, what run_single returns
+# for q alone; ``key(q)``: requests of one kind with equal keys may share a call; ``share``: what that means, for the
+# error.
+_RequestKind = collections.namedtuple("_RequestKind", "kind regime book switch run_single entry batch unit key share")
 _REQUEST_KINDS = {(k.kind, k.regime): k for k in (
-    _RequestKind(kind="chain", regime=None, book="", gated=False, run_single=_chain_run_single,
+    _RequestKind(kind="chain", regime=None, book="", switch=None, run_single=_chain_run_single,
                  entry="gpfit_estep_chain_batch", batch=_chain_batch_raw, unit=_chain_result, key=_chain_bucket_key,
                  share="the requests of one call share N, the padded basis size, the number of steps and the optimiser's "
                  "settings"),
-    _RequestKind(kind="chain_full", regime=None, book="full_", gated=True, run_single=_chain_full_run_single,
+    _RequestKind(kind="chain_damped", regime=None, book="", switch=None, run_single=_chain_damped_run_single,
+                 entry="gpfit_estep_chain_damped_batch", batch=_chain_damped_batch_raw, unit=_chain_result,
+                 key=_chain_damped_bucket_key,
+                 share="the requests of one call share N, the padded basis size, the step size alpha, the number of steps "
+                 "and the optimiser's settings"),
+    _RequestKind(kind="chain_full", regime=None, book="full_", switch="FULL_RANK_GROUPS", run_single=_chain_full_run_single,
                  entry="gpfit_estep_chain_full_batch", batch=_chain_full_batch_raw, unit=_chain_result,
                  key=_chain_full_bucket_key,
                  share="the requests of one call share N, the number of steps and the optimiser's settings"),
-    _RequestKind(kind="closure", regime=None, book="closure_", gated=False, run_single=_closure_run_single,
+    _RequestKind(kind="closure", regime=None, book="closure_", switch=None, run_single=_closure_run_single,
                  entry="gpfit_fit_eval_sparse_batch", batch=_closure_batch_raw, unit=_closure_unit,
                  key=_closure_sparse_bucket_key,
                  share="the requests of one call share the stimuli's sizes and leading dimensions, the pixel grid and the "
                  "padded basis size"),
-    _RequestKind(kind="closure", regime="truncated", book="closure_", gated=False, run_single=_closure_run_single,
+    _RequestKind(kind="closure", regime="truncated", book="closure_", switch=None, run_single=_closure_run_single,
                  entry="gpfit_fit_eval_projected_batch", batch=_closure_batch_raw, unit=_closure_unit,
                  key=_closure_projected_bucket_key,
                  share="the truncated requests of one call share the stimuli's size and leading dimension, the pixel grid, "
                  "the padded basis size and the capacity of their workspaces"),
-    _RequestKind(kind="closure", regime="full", book="full_closure_", gated=True, run_single=_closure_full_run_single,
-                 entry="gpfit_fit_eval_batch", batch=_closure_full_batch_raw, unit=_closure_full_unit,
-                 key=_closure_full_bucket_key,
+    _RequestKind(kind="closure", regime="full", book="full_closure_", switch="FULL_RANK_GROUPS",
+                 run_single=_closure_full_run_single, entry="gpfit_fit_eval_batch", batch=_closure_full_batch_raw,
+                 unit=_closure_full_unit, key=_closure_full_bucket_key,
                  share="the full-rank requests of one call share the stimuli's size and leading dimension, the pixel grid, "
-                 "the capacity of their workspaces and the reuse_V flag"))}
-# The sixth kind, the loss evaluation of elbo_terms: every regime, a book of its own (_LOSS_BOOK).  Its record stands
-# beside the table of the chains and closures, and _request_kind finds it like theirs.
-_LOSS_KIND = _RequestKind(kind="loss", regime=None, book=_LOSS_BOOK, gated=False, run_single=_loss_run_single,
-                          entry="gpfit_elbo_batch", batch=_loss_batch_raw, unit=_loss_result, key=_loss_bucket_key,
-                          share="the requests of one call share N and the padded basis size")
-
-
-# The seventh kind, the damped chain (_estep_chain_damped).  Its record stands beside the table as well: the table's own
-# five are pinned by name and number.  Its calls are counted in book "" beside the other projected chains.
-_DAMPED_CHAIN_KIND = _RequestKind(kind="chain_damped", regime=None, book="", gated=False, run_single=_chain_damped_run_single,
-                                  entry="gpfit_estep_chain_damped_batch", batch=_chain_damped_batch_raw, unit=_chain_result,
-                                  key=_chain_damped_bucket_key,
-                                  share="the requests of one call share N, the padded basis size, the step size alpha, the "
-                                  "number of steps and the optimiser's settings")
-
-
-# The eighth and ninth kind, the two halves of a basis rebuild: the sweeps of a pass (_basis_sweeps) and a stretch of the
-# projector step (_sign_steps).  They come to the rendezvous only with BASIS_GROUPS on; their calls are counted in a book
-# of their own (_BASIS_BOOK).
-_SWEEPS_KIND = _RequestKind(kind="sweeps", regime=None, book=_BASIS_BOOK, gated=False, run_single=_sweeps_run_single,
-                            entry="gpfit_subspace_sweeps_batch", batch=_sweeps_batch_raw, unit=_sweeps_result,
-                            key=_sweeps_bucket_key,
-                            share="the requests of one call share the device, the stream, N, the block width, the flags and "
-                            "the capacity of their workspaces")
-_SIGN_KIND = _RequestKind(kind="sign", regime=None, book=_BASIS_BOOK, gated=False, run_single=_sign_run_single,
-                          entry="gpfit_sign_steps_batch", batch=_sign_batch_raw, unit=_sign_result, key=_sign_bucket_key,
-                          share="the requests of one call share the device, the stream, k, the flags, the schedule and the "
-                          "capacity of their workspaces")
+                 "the capacity of their workspaces and the reuse_V flag"),
+    _RequestKind(kind="loss", regime=None, book="loss_", switch=None, run_single=_loss_run_single,
+                 entry="gpfit_elbo_batch", batch=_loss_batch_raw, unit=_loss_result, key=_loss_bucket_key,
+                 share="the requests of one call share N and the padded basis size"),
+    _RequestKind(kind="sweeps", regime=None, book="basis_", switch="BASIS_GROUPS", run_single=_sweeps_run_single,
+                 entry="gpfit_subspace_sweeps_batch", batch=_sweeps_batch_raw, unit=_sweeps_result, key=_sweeps_bucket_key,
+                 share="the requests of one call share the device, the stream, N, the block width, the flags and the "
+                 "capacity of their workspaces"),
+    _RequestKind(kind="sign", regime=None, book="basis_", switch="BASIS_GROUPS", run_single=_sign_run_single,
+                 entry="gpfit_sign_steps_batch", batch=_sign_batch_raw, unit=_sign_result, key=_sign_bucket_key,
+                 share="the requests of one call share the device, the stream, k, the flags, the schedule and the "
+                 "capacity of their workspaces"))}
 
 
 def _request_kind(q):
-    if q["kind"] == _LOSS_KIND.kind:
-        return _LOSS_KIND
-    if q["kind"] == _SWEEPS_KIND.kind:
-        return _SWEEPS_KIND
-    if q["kind"] == _SIGN_KIND.kind:
-        return _SIGN_KIND
-    if q["kind"] == _DAMPED_CHAIN_KIND.kind:
-        return _DAMPED_CHAIN_KIND
+    """The record of the request's kind."""
     return _REQUEST_KINDS[q["kind"], q.get("regime")]
 
 
@@ -2722,11 +2662,12 @@ def _request_run_group(qs):
 
 def _submit(q):
     """The result of the request's device call: in a fit of ``varGP_cells`` the call is the wave's -- the request goes to
-    the rendezvous and comes back as one unit of a group call -- unless the kind is a full-rank one and
-    ``FULL_RANK_GROUPS`` is off; anywhere else it is the kind's single call."""
+    the rendezvous and comes back as one unit of a group call -- unless the kind names a module switch
+    (``FULL_RANK_GROUPS``, ``BASIS_GROUPS``; read here, at call time) and that switch is off; anywhere else it is the kind's
+    single call."""
     kind = _request_kind(q)
     rendezvous = getattr(_CELLS, "rendezvous", None)
-    if rendezvous is not None and (FULL_RANK_GROUPS or not kind.gated):
+    if rendezvous is not None and (kind.switch is None or globals()[kind.switch]):
         return rendezvous.call(q)
     return kind.run_single(q)
 

@@ -141,9 +141,10 @@ def test_the_loss_is_a_request_kind_with_its_own_book_and_key():
     def request(N, nb):
         return {"kind": "loss", "stream": Stream(), "N": N, "nb": nb, "m": M()}
     kind = gp._request_kind(request(1000, 300))
-    assert kind.kind == "loss" and kind.entry == "gpfit_elbo_batch" and kind.book == "loss_" and not kind.gated
+    assert kind.kind == "loss" and kind.entry == "gpfit_elbo_batch" and kind.book == "loss_" and kind.switch is None
     assert all(callable(f) for f in (kind.run_single, kind.batch, kind.unit, kind.key)) and "share" in kind.share
-    assert kind.book not in {k.book for k in gp._REQUEST_KINDS.values()}, "the loss has a book of its own"
+    assert kind is gp._REQUEST_KINDS["loss", None]
+    assert [k for k in gp._REQUEST_KINDS.values() if k.book == "loss_"] == [kind], "no other record's book is loss_"
     assert gp._ChainRendezvous._book(request(1000, 300)) == "loss_"
     rv = gp._ChainRendezvous(1, None, None, None)
     assert rv.loss_group_sizes == [] and rv.loss_call_seconds == [] and rv.seconds_in_loss_call == 0.0

@@ -85,13 +85,13 @@ def request(nb=200, alpha=0.5, kind="chain_damped"):
 
 
 def test_the_request_kind_and_its_bucket_key():
-    """The record stands beside the table of five, which tests/test_request_kinds_cpu.py pins by name and number, and is
-    found by the same lookup (_request_kind), as the loss kind is."""
+    """The record is one of the table (tests/test_request_kinds_cpu.py pins the table as a whole) and is found by the
+    lookup of every kind (_request_kind)."""
     kind = gp._request_kind(request())
-    assert kind is gp._DAMPED_CHAIN_KIND and kind.kind == "chain_damped" and kind.regime is None
+    assert kind is gp._REQUEST_KINDS["chain_damped", None] and kind.kind == "chain_damped" and kind.regime is None
     assert kind.run_single is gp._chain_damped_run_single and kind.batch is gp._chain_damped_batch_raw
     assert kind.unit is gp._chain_result and kind.entry == "gpfit_estep_chain_damped_batch"
-    assert kind.book == "" == gp._ChainRendezvous._book(request()) and kind.gated is False and "share" in kind.share
+    assert kind.book == "" == gp._ChainRendezvous._book(request()) and kind.switch is None and "share" in kind.share
     key = gp._request_bucket_key
     assert key(request())[0] == "chain_damped"
     assert key(request())[1:] == gp._chain_bucket_key(request()) + (0.5,)        # the key of "chain" plus alpha

@@ -1,6 +1,6 @@
-"""The table of request kinds behind varGP_cells, without a GPU: its five records, the bucket keys and books of hand-built
+"""The table of request kinds behind varGP_cells, without a GPU: its nine records, the bucket keys and books of hand-built
 requests of every kind, the refusal of mixed lists before any call goes out (stub batch calls), and the unit bounds of the
-four *_group wrappers."""
+*_group wrappers."""
 import itertools
 
 import pytest
@@ -28,18 +28,21 @@ class M:
 
 class Engine:
     _ctx = 0
+    n_max = 256
 
 
 N = 200
-BOOKS = {("chain", None): "", ("chain_full", None): "full_", ("closure", None): "closure_",
-         ("closure", "truncated"): "closure_", ("closure", "full"): "full_closure_"}
+BOOKS = {("chain", None): "", ("chain_full", None): "full_", ("chain_damped", None): "", ("closure", None): "closure_",
+         ("closure", "truncated"): "closure_", ("closure", "full"): "full_closure_", ("loss", None): "loss_",
+         ("sweeps", None): "basis_", ("sign", None): "basis_"}
+ALL_BOOKS = ("", "closure_", "full_", "full_closure_", "loss_", "basis_")
 
 
 def request(kind, regime):
     """A request of the kind with the fields its key reads: every field that two kinds share has one value."""
     q = {"kind": kind, "stream": Stream(), "engine": Engine(), "N": N, "n_steps": 10, "nfp": 10, "lambda0_fixed": None,
          "nb": N, "a": M(N), "K": M(N), "x": M(64), "xt": M(64), "V": M(N), "Nt": N, "n_kept": N, "rows": 8, "cols": 8,
-         "cap": 256, "reuse_V": False}
+         "cap": 256, "reuse_V": False, "alpha": 0.5, "k": 32, "flags": 2, "its0": 0, "c": [1.5, 1.2], "S": M(32), "m": M(N)}
     if regime is not None:
         q["regime"] = regime
     return q
@@ -48,15 +51,21 @@ def request(kind, regime):
 REQUESTS = {key: request(*key) for key in BOOKS}
 
 
-def test_the_table_has_exactly_the_five_kinds_and_every_record_is_complete():
-    assert set(gp._REQUEST_KINDS) == set(BOOKS) and len(gp._REQUEST_KINDS) == 5
+def test_the_table_has_exactly_the_nine_kinds_and_every_record_is_complete():
+    assert set(gp._REQUEST_KINDS) == set(BOOKS) and len(gp._REQUEST_KINDS) == 9
     for key, kind in gp._REQUEST_KINDS.items():
-        assert (kind.kind, kind.regime) == key
-        assert kind.book in gp._BOOKS and isinstance(kind.gated, bool)
+        assert (kind.kind, kind.regime) == key and len(kind) == 10 and gp._request_kind(REQUESTS[key]) is kind
+        assert kind.book in gp._ALL_BOOKS and kind.switch in (None, "FULL_RANK_GROUPS", "BASIS_GROUPS")
+        assert kind.switch is None or isinstance(getattr(gp, kind.switch), bool)
         assert all(callable(f) for f in (kind.run_single, kind.batch, kind.unit, kind.key)), key
         assert kind.entry.startswith("gpfit_") and kind.entry.endswith("_batch") and "share" in kind.share, key
-    assert len({kind.entry for kind in gp._REQUEST_KINDS.values()}) == 5
-    assert {key for key, kind in gp._REQUEST_KINDS.items() if kind.gated} == {("chain_full", None), ("closure", "full")}
+    assert len({kind.entry for kind in gp._REQUEST_KINDS.values()}) == 9
+    switched = {name: {key for key, kind in gp._REQUEST_KINDS.items() if kind.switch == name}
+                for name in ("FULL_RANK_GROUPS", "BASIS_GROUPS")}
+    assert switched["FULL_RANK_GROUPS"] == {("chain_full", None), ("closure", "full")}
+    assert switched["BASIS_GROUPS"] == {("sweeps", None), ("sign", None)}
+    # a request with nothing but its kind is found too
+    assert gp._request_kind({"kind": "sweeps"}) is gp._REQUEST_KINDS["sweeps", None]
 
 
 def test_a_key_begins_with_the_kind_and_keys_of_different_kinds_differ():
@@ -66,16 +75,17 @@ def test_a_key_begins_with_the_kind_and_keys_of_different_kinds_differ():
         if kind == "closure":
             assert k[1:] == gp._closure_bucket_key(REQUESTS[kind, regime])
             assert (k[1] == regime) if regime else (k[1] not in ("truncated", "full"))
-    assert len(set(keys.values())) == 5
+    assert len(set(keys.values())) == 9
 
 
 def test_the_book_of_each_kind_and_of_a_request_without_one():
-    assert gp._BOOKS == ("", "closure_", "full_", "full_closure_")
+    assert gp._ALL_BOOKS == ALL_BOOKS
+    assert {kind.book for kind in gp._REQUEST_KINDS.values()} == set(gp._ALL_BOOKS)
     for key, q in REQUESTS.items():
         assert gp._REQUEST_KINDS[key].book == BOOKS[key] == gp._ChainRendezvous._book(q)
     assert gp._ChainRendezvous._book({"name": "x"}) == "" and gp._ChainRendezvous._book("not a dict") == ""
     rv = gp._ChainRendezvous(1, None, None, None)
-    for book in gp._BOOKS:
+    for book in ALL_BOOKS:
         assert getattr(rv, book + "group_sizes") == [] and getattr(rv, book + "call_seconds") == []
         assert getattr(rv, "seconds_in_" + book + "call") == 0.0
         assert isinstance(getattr(gp.varGP_cells, "last_" + book + "group_sizes"), list)

@@ -158,7 +158,9 @@ def test_sign_schedule_is_the_recurrence_of_the_loop():
 
 def test_group_refuses_bad_lists_before_any_call(monkeypatch):
     called = []
-    monkeypatch.setattr(gp, "_sign_batch_raw", lambda *a, **k: called.append("batch"))
+    monkeypatch.setitem(gp._REQUEST_KINDS, ("sign", None), gp._REQUEST_KINDS["sign", None]._replace(
+        batch=lambda *a, **k: called.append("batch")))
+    monkeypatch.setattr(gp, "_sign_prepare", lambda *a, **k: called.append("prepare"))
     monkeypatch.setattr(gp, "_group_engines", lambda *a, **k: called.append("engines"))
 
     def unit(k=32, cs=(1.5, 1.2), its0=0, with_x=False, with_x2=False):
@@ -182,10 +184,10 @@ def test_group_refuses_bad_lists_before_any_call(monkeypatch):
 def test_basis_requests_are_kinds_of_their_own():
     for kind, entry in (("sweeps", "gpfit_subspace_sweeps_batch"), ("sign", "gpfit_sign_steps_batch")):
         rec = gp._request_kind({"kind": kind})
-        assert rec.kind == kind and rec.book == "basis_" and rec.entry == entry and not rec.gated
-        assert gp._ChainRendezvous._book({"kind": kind}) == "basis_"
-    assert gp._ALL_BOOKS[-1] == "basis_"
-    assert len(gp._REQUEST_KINDS) == 5 and gp._BOOKS == ("", "closure_", "full_", "full_closure_")
+        assert rec.kind == kind and rec.book == "basis_" and rec.entry == entry and rec.switch == "BASIS_GROUPS"
+        assert rec is gp._REQUEST_KINDS[kind, None] and gp._ChainRendezvous._book({"kind": kind}) == "basis_"
+    assert gp._ALL_BOOKS == ("", "closure_", "full_", "full_closure_", "loss_", "basis_")
+    assert {key for key, rec in gp._REQUEST_KINDS.items() if rec.book == "basis_"} == {("sweeps", None), ("sign", None)}
     for name in ("last_basis_group_sizes", "last_basis_call_seconds", "last_seconds_in_basis_call"):
         assert hasattr(gp.varGP_cells, name)
     assert gp.BASIS_GROUPS in (False, True) and gp.SIGN_CHAIN in (False, True)

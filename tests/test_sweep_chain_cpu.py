@@ -187,6 +187,12 @@ def unit(N=64, k=32, with_y=False, want_rr=True, shifts=(0.0, 0.5)):
     return u
 
 
+def set_batch(monkeypatch, batch):
+    """The batch entry of the kind "sweeps" replaced (the group wrapper calls what the kind's record names)."""
+    key = ("sweeps", None)
+    monkeypatch.setitem(gp._REQUEST_KINDS, key, gp._REQUEST_KINDS[key]._replace(batch=batch))
+
+
 @pytest.fixture
 def stubbed(monkeypatch):
     """_basis_sweeps_group with workspaces, stream and batch entry replaced: what it would have sent is recorded."""
@@ -200,7 +206,7 @@ def stubbed(monkeypatch):
     def batch(ctxs, qs, rec=None):
         sent.append(qs)
         return 0, [len(q["shifts"]) if i % 2 == 0 else 0 for q in qs for i in range(2)]
-    monkeypatch.setattr(gp, "_sweeps_batch_raw", batch)
+    set_batch(monkeypatch, batch)
     return sent
 
 
@@ -231,7 +237,7 @@ def test_the_group_wrapper_sends_one_call_and_cuts_the_results_per_unit(stubbed,
         assert r[0] is q["Q"] and r[1] is q["Y"] and r[2] is q["S"]
         assert q["Q"] is not units[u]["Q"] and r[2].shape == (32, 32)
     # a unit whose factorisation failed has None in its place, the others their results
-    monkeypatch.setattr(gp, "_sweeps_batch_raw", lambda ctxs, qs, rec=None: (0, [1, 0, 1, 4, 0, 0]))
+    set_batch(monkeypatch, lambda ctxs, qs, rec=None: (0, [1, 0, 1, 4, 0, 0]))
     res = gp._basis_sweeps_group(units)
     assert res[1] is None and res[0] is not None and res[2] is not None
 
