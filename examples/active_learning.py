@@ -3,6 +3,7 @@ then repeatedly score every remaining image with the information-gain utility, a
 and inducing sets and refit from the previous posterior.
 
     python examples/active_learning.py --pool 1200 --start 300 --iterations 5 [--per-round 8] [--notebook-step] [--score-call]
+                                          [--batch-aware]
 
 The step between two fits is ``utils.extend_inducing_set``: K~ grown by its latest column and, while every
 eigenvalue is kept, the Cholesky factor of the previous fit extended by one row (gpfit_potrf_append) -- no
@@ -12,7 +13,10 @@ against the real reference in the GPU suite (fixture g9).  ``--per-round B`` run
 in batches: a round takes the B images of largest utility, grows the model by all of them in ONE
 ``extend_inducing_set`` (the factor by a block of B rows, gpfit_potrf_append_block) and refits once.
 ``--score-call`` scores the remaining images with ``utils.fold_posterior`` and ``utils.score_pool`` (one device call,
-gpfit_score_pool) instead of the composition of kernel, GEMM and element-wise calls the loop uses by default."""
+gpfit_score_pool) instead of the composition of kernel, GEMM and element-wise calls the loop uses by default.
+``--batch-aware`` picks the B images of a round one by one, each conditioned on those already chosen
+(``utils.select_round``: gpfit_pool_covariance and gpfit_select_batch), so that a round does not spend two slots on an
+image and its near-copy; the default stays the B images of largest utility."""
 import argparse
 import contextlib
 import copy
@@ -33,6 +37,8 @@ ap.add_argument("--px", type=int, default=8, help="pixels per side")
 ap.add_argument("--per-round", type=int, default=1, help="images added per round (one preparation and one refit per round)")
 ap.add_argument("--notebook-step", action="store_true", help="eigh of the grown K~ for every added image, as the notebook does")
 ap.add_argument("--score-call", action="store_true", help="score the remaining images in one device call (utils.score_pool)")
+ap.add_argument("--batch-aware", action="store_true",
+                help="pick a round's images one by one, each conditioned on those already chosen (utils.select_round)")
 args = ap.parse_args()
 if args.per_round < 1:
     ap.error("--per-round must be at least 1")
@@ -82,7 +88,13 @@ for it in range(args.iterations):
         th, fp = model["hyperparams_tuple"][0], model["f_params"]
         A, lambda0 = torch.exp(fp["logA"]), fp["lambda0"]
         # utility of every remaining image (notebook cell 'Calculate the utility of each remaining image')
-        if args.score_call:
+        take = min(args.per_round, remaining.shape[0])
+        if args.batch_aware:
+            folded = U.fold_posterior(model["K_tilde_b"], model["K_tilde_inv_b"], model["m_b"], model["V_b"], B)
+            cell = {"xtilde": xtilde, "C": C, "theta": th, "folded": folded, "f_params": fp, "mask": mask}
+            chosen = U.select_round(xstar, [cell], take, r_counts)
+            u = chosen["scores"]["population_utility"]
+        elif args.score_call:
             folded = U.fold_posterior(model["K_tilde_b"], model["K_tilde_inv_b"], model["m_b"], model["V_b"], B)
             u = U.score_pool(xstar, xtilde, C, th, folded, fp, r_masked=r_counts, mask=mask)["utility"]
         else:
@@ -91,8 +103,12 @@ for it in range(args.iterations):
             lam_m, lam_var = U.lambda_moments(xstar[:, mask], model["K_tilde_b"], K_star_b @ model["K_tilde_inv_b"], Kvec_star,
                                               K_star_b, C, model["m_b"], model["V_b"], th)
             u = U.nd_utility(A ** 2 * lam_var, A * lam_m + lambda0, r_counts)
-        take = min(args.per_round, remaining.shape[0])
-        best = remaining[torch.topk(u.reshape(-1), take).indices.cpu()] if take > 1 else remaining[int(u.argmax())][None]
+        if args.batch_aware:
+            picks = chosen["picked"].cpu()
+            best = remaining[picks[picks >= 0]]
+            take = best.shape[0]
+        else:
+            best = remaining[torch.topk(u.reshape(-1), take).indices.cpu()] if take > 1 else remaining[int(u.argmax())][None]
         sync()
         t_score = time.time() - t0
         # add it and prepare the refit from the previous posterior

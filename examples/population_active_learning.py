@@ -11,9 +11,13 @@ shown on the rig is shown to all of them.  A round fits nothing twice:
 
     python examples/population_active_learning.py --cells 16 --pool 1200 --start 300 --rounds 3 --per-round 8
     python examples/population_active_learning.py --cells 16 --loop      # step 3 cell after cell (utils.score_pool), for the A/B
+    python examples/population_active_learning.py --cells 16 --batch-aware
 
 It prints the time of every phase of a round and the units each scoring call carried (``utils.last_pool_group_sizes``).
-Both ways pick the same images: a cell's utilities have the same bits either way, and so has their sum."""
+Both ways pick the same images: a cell's utilities have the same bits either way, and so has their sum.
+``--batch-aware`` replaces steps 3 and 4 by ``utils.select_round`` (at most 16 cells): the same scoring, then the round's
+images picked one by one from the shortlist of largest population utility, each conditioned on those already chosen
+(gpfit_pool_covariance per cell, one gpfit_select_batch for all of them)."""
 import argparse
 import contextlib
 import io
@@ -33,9 +37,13 @@ ap.add_argument("--px", type=int, default=8, help="pixels per side")
 ap.add_argument("--per-round", type=int, default=8, help="images added per round")
 ap.add_argument("--max-units", type=int, default=16, help="cells per device call of the fits and of the scoring")
 ap.add_argument("--loop", action="store_true", help="score cell after cell with utils.score_pool and sum on the host side")
+ap.add_argument("--batch-aware", action="store_true",
+                help="pick a round's images one by one, each conditioned on those already chosen (utils.select_round)")
 args = ap.parse_args()
 if args.per_round < 1 or args.cells < 1:
     ap.error("--per-round and --cells must be at least 1")
+if args.batch_aware and (args.loop or args.cells > 16 or args.per_round > 128):
+    ap.error("--batch-aware takes at most 16 cells and 128 images per round, and not --loop")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -91,7 +99,14 @@ for rnd in range(args.rounds):
         torch.cuda.synchronize()
         t_fold = time.time() - t0
         t0 = time.time()
-        if args.loop:
+        take = min(args.per_round, remaining.shape[0])
+        if args.batch_aware:
+            chosen = U.select_round(xstar, cells, take, r_counts)
+            total, sizes = chosen["scores"]["population_utility"], list(U.last_pool_group_sizes)
+            picks = chosen["picked"].cpu()
+            best = remaining[picks[picks >= 0]]
+            take = best.shape[0]
+        elif args.loop:
             total, sizes = None, []
             for c in cells:
                 u = U.score_pool(xstar, c["xtilde"], c["C"], c["theta"], c["folded"], c["f_params"], r_masked=r_counts,
@@ -103,8 +118,8 @@ for rnd in range(args.rounds):
             failed = [cell for cell, err in enumerate(scored["errors"]) if err is not None]
             assert not failed, f"cells {failed} could not be scored: {scored['errors'][failed[0]]}"
             total, sizes = scored["population_utility"], list(U.last_pool_group_sizes)
-        take = min(args.per_round, remaining.shape[0])
-        best = remaining[torch.topk(total, take).indices.cpu()]
+        if not args.batch_aware:
+            best = remaining[torch.topk(total, take).indices.cpu()]
         torch.cuda.synchronize()
         t_score = time.time() - t0
         t0 = time.time()
@@ -120,7 +135,7 @@ for rnd in range(args.rounds):
         t_prep = time.time() - t0
     models, t_fit = fit_cells(nxt)
     print(f"round {rnd + 1}: folded {args.cells} posteriors in {t_fold * 1e3:.1f} ms; scored {remaining.shape[0]} images for "
-          f"{args.cells} cells in {t_score * 1e3:.1f} ms ({'score_pool per cell' if args.loop else 'score_pool_cells'}, units per "
+          f"{args.cells} cells in {t_score * 1e3:.1f} ms ({'select_round' if args.batch_aware else 'score_pool per cell' if args.loop else 'score_pool_cells'}, units per "
           f"call {sizes}; max population utility {float(total.max()):.4f}, images {[int(i) for i in best]}); refits prepared in "
           f"{t_prep * 1e3:.1f} ms, {args.cells} refits on {in_use.shape[0]} images in {t_fit:.2f} s, "
           f"mean log marginal {logmarginal(models):.3f}")

@@ -101,6 +101,9 @@ _SIGS = {
     "gpfit_score_pool_batch": (i32, [vp, i32, vp, pd, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, pd, pd,
                                      vp, i32, i64, vp, vp, vp, vp]),
     "gpfit_utility_sum": (i32, [vp, vp, i64, i32, vp, i64, vp]),
+    "gpfit_pool_covariance": (i32, [vp, vp, f64, vp, i64, i64, vp, i64, vp, i64, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp,
+                                    i64]),
+    "gpfit_select_batch": (i32, [vp, i32, vp, vp, i64, vp, pd, pd, pd, vp, i32, i32, vp, vp, vp, vp]),
     "gpfit_probe_mfma_f64": (i32, [vp, vp, i32, i32]),
     "gpfit_probe_stream_copy": (i32, [vp, vp, vp, i64]),
     # test hooks

@@ -160,7 +160,7 @@ CtxBuf ctx_buffer(gpfit_ctx* c, const char* name) {
   const int64_t np = c->np_cap, dp = c->dp_cap, nn = np * np * 8;
   const struct { const char* n; double* p; int64_t bytes; } tab[] = {
       {"Abuf", c->Abuf, nn}, {"Tbuf", c->Tbuf, nn}, {"Wbuf", c->Wbuf, nn}, {"Zbuf", c->Zbuf, nn}, {"Cos", c->Cos, nn},
-      {"TmpV", c->TmpV, nn}, {"Xm", c->Xm, np * dp * 8}, {"Xt2", c->Xt2, np * dp * 8}, {"Ybuf", c->Ybuf, np * dp * 8},
+      {"TmpV", c->TmpV, nn}, {"Tmp", c->Tmp, nn}, {"Kbuf", c->Kbuf, nn}, {"Xm", c->Xm, np * dp * 8}, {"Xt2", c->Xt2, np * dp * 8}, {"Ybuf", c->Ybuf, np * dp * 8},
       {"Mmat", c->Mmat, dp * dp * 8}, {"Cmat", c->Cmat, dp * dp * 8}, {"tvec", c->tvec, 2 * np * 8}, {"bv", c->bv, np * 8},
       {"q", c->q, np * 8}, {"wl", c->wl, np * 8}, {"q2", c->q2, np * 8}, {"dq1", c->dq1, np * 8}, {"dq2", c->dq2, np * 8}};
   for (const auto& t : tab)

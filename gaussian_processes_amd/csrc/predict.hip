@@ -12,6 +12,8 @@
 // the row sits -- the dense products (C xtilde once, x* C and K* B per chunk) go out as pointer batches of one problem per
 // unit, which the GEMM launcher never cuts along k -- so the bits do not depend on the chunking, the row offset, the run,
 // or on which other units share the call.  Each unit works in its own context's matrices.
+// gpfit_pool_covariance (below the pool call) forms the full posterior covariance of a shortlist's latents from the same
+// stages: Sigma = K(x, x) + (Z S_b) Z^T on one triangle of tiles, mirrored, the diagonal from the pool call's own kernels.
 #include "gemm_core.h"
 #include "product.h"
 #include "units.h"
@@ -33,12 +35,14 @@ struct PoolGramArgs {
   PerUnit<double> s0sq;
   int64_t ld1, ld2, ldk;
   int np1, np2, nv1, Kd;
+  int lower;                    // the tiles on or below the block diagonal only (a chunk against itself)
 };
 
 __global__ __launch_bounds__(GEMM_THREADS, 2) void pool_gram_kernel(PoolGramArgs p, int tiles_n) {
   __shared__ __attribute__((aligned(16))) double smem[4 * Real<double>::KT * TILE];
   const int u = blockIdx.y;
   const int ti = blockIdx.x / tiles_n, tj = blockIdx.x % tiles_n;
+  if (p.lower && tj > ti) return;   // the whole workgroup, before any barrier
   const int row0 = ti * TILE, col0 = tj * TILE;
   Real<double>::acc_t acc[4][4];
 #pragma unroll
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void pool_weights_kernel(PerUnit<const double*
     const double v = tile[tx][ty + 8 * r];
     Sw[(int64_t)l * kp + c] = l < c ? 2.0 * v : (l == c ? v : 0.0);
   }
-  if (blockIdx.y == 0 && ty == 0) wpad[c0 + tx] = c0 + tx < k ? w[c0 + tx] : 0.0;
+  if (blockIdx.y == 0 && ty == 0) wpad[c0 + tx] = (w && c0 + tx < k) ? w[c0 + tx] : 0.0;   // no w: the covariance call
 }
 
 // ---- the quadratic form: tile (ti, tj) of Z S', reduced against Z along its columns
@@ -322,6 +326,144 @@ int score_pool_impl(const char* name, gpfit_ctx* const* ctxs, int n_units, void*
   return 0;
 }
 
+// ---- the posterior covariance of a shortlist (gpfit_pool_covariance): the stages above on ONE chunk that holds every
+// row, then  Sigma = K(x, x) + (Z S) Z^T  on the tiles on or below the block diagonal, mirrored on the way out.
+
+// S as the full symmetric matrix, zero padded to [kp][kp]; only elements on or below S's diagonal are read
+__global__ __launch_bounds__(256) void pool_symmetric_kernel(const double* __restrict__ S, int64_t lds, int k, int kp,
+                                                             double* __restrict__ Sf) {
+  const int c = blockIdx.x * 32 + (threadIdx.x & 31), l = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (l >= kp || c >= kp) return;
+  const int hi = l > c ? l : c, lo = l > c ? c : l;
+  Sf[(int64_t)l * kp + c] = hi < k ? S[(int64_t)hi * lds + lo] : 0.0;
+}
+
+// Sigma[i][j] = G[max(i, j)][min(i, j)] off the diagonal (both halves from ONE computed element: the same bits), the
+// pool call's sigma2 on it.  A 32 x 32 block per workgroup; blocks above the diagonal read G's block transposed through LDS.
+__global__ __launch_bounds__(256) void pool_cov_store_kernel(const double* __restrict__ G, int64_t ldg,
+                                                             const double* __restrict__ sigma2, int M,
+                                                             double* __restrict__ Sigma, int64_t ldsig) {
+  __shared__ double tile[32][33];
+  const int bi = blockIdx.y, bj = blockIdx.x;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+  const bool upper = bj > bi;
+  const int g0r = (upper ? bj : bi) * 32, g0c = (upper ? bi : bj) * 32;   // the block of G at or below the diagonal
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int gr = g0r + ty + 8 * r, gc = g0c + tx;
+    // inside a diagonal block the element above the diagonal comes from its mirror image
+    double v = 0.0;
+    if (gr < M && gc < M) v = gc <= gr ? G[(int64_t)gr * ldg + gc] : G[(int64_t)gc * ldg + gr];
+    tile[ty + 8 * r][tx] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = bi * 32 + ty + 8 * r, j = bj * 32 + tx;
+    if (i >= M || j >= M) continue;
+    const double v = upper ? tile[tx][ty + 8 * r] : tile[ty + 8 * r][tx];
+    Sigma[(int64_t)i * ldsig + j] = i == j ? sigma2[i] : v;
+  }
+}
+
+int pool_covariance_impl(gpfit_ctx* ctx, void* stream, double sigma0, const double* xstar, int64_t ldxs, int64_t M,
+                         const int* pixels, int64_t d_full, const double* xtilde, int64_t ldxt, int64_t nt, int64_t d,
+                         const double* C, int64_t ldc, const double* B, int64_t ldb, int64_t k, const double* S, int64_t lds,
+                         double* Sigma, int64_t ldsig) {
+  const Refuse refuse{"gpfit_pool_covariance"};
+  if (!ctx || !xtilde || !C || !S || M < 0 || nt <= 0 || d <= 0 || k <= 0 || ldxt < d || ldc < d || lds < k ||
+      (M > 0 && (!xstar || !Sigma || ldsig < M)) || (B ? ldb < k : k != nt) ||
+      (pixels ? (d_full < d || ldxs < d_full) : ldxs < d))
+    return refuse("bad argument");
+  if (ctx->pend.active) return refuse(GP_PENDING_REFUSAL);
+  if (round_up(d, 32) > ctx->dp_cap || round_up(nt, TILE) > ctx->np_cap || round_up(k, TILE) > ctx->np_cap ||
+      round_up(M, TILE) > ctx->np_cap)
+    return refuse("problem larger than the context capacity");
+  DeviceGuard device_guard(ctx->device);
+  if (M == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const Lane lane{s, nullptr};
+  const int dp = (int)round_up(d, 32), ntp = (int)round_up(nt, TILE), kp = (int)round_up(k, TILE);
+  const int rows = (int)M, np1 = (int)round_up(M, TILE);
+  const bool with_B = B != nullptr;
+  gpfit_ctx* const ctxs[1] = {ctx};
+  const Units one = Units::all(ctxs, 1);
+  const PerUnit<double> s0sq = one.same(sigma0 * sigma0);
+  const PerUnit<int> d_u = one.same((int)d), nt_u = one.same((int)nt), k_u = one.same((int)k);
+  const PerUnit<const int*> no_pix = one.same<const int*>(nullptr);
+  // the pool call's work matrices in the pool call's roles, and three more: none caches the factor of V
+  const auto panel = &gpfit_ctx::Cos;    // K* [np1][ntp]
+  const auto Zb = &gpfit_ctx::Zbuf;      // K* B [np1][kp]
+  const auto Sw = &gpfit_ctx::Wbuf;      // S' [kp][kp] (the diagonal's quadratic form)
+  const auto Bpad = &gpfit_ctx::Tbuf;    // B zero padded [ntp][kp]
+  const auto part = &gpfit_ctx::Abuf;    // [kp / 128][2][np1]
+  const auto wpad = &gpfit_ctx::bv;      // zeros: no mean is asked for
+  const auto Sf = &gpfit_ctx::Tmp;       // S, full and symmetric [kp][kp]
+  const auto Wm = &gpfit_ctx::TmpV;      // W = Z S [np1][kp]
+  const auto Gm = &gpfit_ctx::Kbuf;      // K(x, x) + W Z^T, the tiles on or below the block diagonal [np1][np1]
+
+  // the inducing side, S' and B exactly as the pool call forms them
+  GP_TRY(launch_pad_copy_group(1, one.same(C), one.same(ldc), d_u, d_u, one.of(&gpfit_ctx::Cmat), dp, dp, dp, s));
+  GP_TRY(launch_gather_group(1, one.same(xtilde), one.same(ldxt), nt_u, no_pix, d_u, dp, ntp, one.of(&gpfit_ctx::Xt2), ntp, s));
+  GP_TRY(product_whole_k(lane, {dp, ntp, dp}, trans(one.mats(&gpfit_ctx::Cmat, dp)), plain(one.mats(&gpfit_ctx::Xt2, ntp)),
+                         into(one.mats(&gpfit_ctx::XCt2, ntp))));
+  GP_TRY(launch_qvec_group(1, one.cof(&gpfit_ctx::Xt2), one.cof(&gpfit_ctx::XCt2), ntp, dp, nt_u, ntp, s0sq,
+                           one.of(&gpfit_ctx::hvec), one.of(&gpfit_ctx::q2), s));
+  hipLaunchKernelGGL(pool_weights_kernel, dim3(kp / 32, kp / 32, 1), dim3(32, 8), 0, s, one.same(S), one.same(lds), k_u, kp,
+                     one.of(Sw), one.same<const double*>(nullptr), one.of(wpad));
+  GP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pool_symmetric_kernel, dim3(kp / 32, kp / 8), dim3(256), 0, s, S, lds, (int)k, kp, ctx->*Sf);
+  GP_HIP(hipGetLastError());
+  if (with_B) GP_TRY(launch_pad_copy_group(1, one.same(B), one.same(ldb), nt_u, k_u, one.of(Bpad), kp, ntp, kp, s));
+
+  // the shortlist: one chunk
+  GP_TRY(launch_gather_group(1, one.same(xstar), one.same(ldxs), one.same(rows), one.same(pixels), d_u, dp, np1,
+                             one.of(&gpfit_ctx::Xt), np1, s));
+  GP_TRY(product_whole_k(lane, {dp, np1, dp}, trans(one.mats(&gpfit_ctx::Cmat, dp)), plain(one.mats(&gpfit_ctx::Xt, np1)),
+                         into(one.mats(&gpfit_ctx::XCt, np1))));
+  GP_TRY(launch_qvec_group(1, one.cof(&gpfit_ctx::Xt), one.cof(&gpfit_ctx::XCt), np1, dp, one.same(rows), np1, s0sq,
+                           one.of(&gpfit_ctx::Kvec), one.of(&gpfit_ctx::q), s));
+  PoolGramArgs g{};
+  g.XCt = one.cof(&gpfit_ctx::XCt); g.Xt = one.cof(&gpfit_ctx::Xt2); g.q1 = one.cof(&gpfit_ctx::q);
+  g.q2 = one.cof(&gpfit_ctx::q2); g.Kout = one.of(panel); g.nv2 = nt_u; g.s0sq = s0sq;
+  g.ld1 = np1; g.ld2 = ntp; g.ldk = ntp; g.np1 = np1; g.np2 = ntp; g.nv1 = rows; g.Kd = dp;
+  hipLaunchKernelGGL(pool_gram_kernel, dim3((np1 / TILE) * (ntp / TILE), 1), dim3(GEMM_THREADS), 0, s, g, ntp / TILE);
+  GP_HIP(hipGetLastError());
+  // the chunk against itself: x_i C x_j for i >= j
+  g.Xt = one.cof(&gpfit_ctx::Xt); g.q2 = one.cof(&gpfit_ctx::q); g.Kout = one.of(Gm); g.nv2 = one.same(rows);
+  g.ld2 = np1; g.ldk = np1; g.np2 = np1; g.lower = 1;
+  hipLaunchKernelGGL(pool_gram_kernel, dim3((np1 / TILE) * (np1 / TILE), 1), dim3(GEMM_THREADS), 0, s, g, np1 / TILE);
+  GP_HIP(hipGetLastError());
+  if (with_B)
+    GP_TRY(product_whole_k(lane, {np1, kp, ntp}, plain(one.mats(panel, ntp)), plain(one.mats(Bpad, kp)), into(one.mats(Zb, kp))));
+  const auto Zm = with_B ? Zb : panel;
+  const int64_t ldz = with_B ? kp : ntp;
+
+  // the diagonal: the pool call's quadratic form and finish, so that it holds the bits of its sigma2
+  PoolQuadArgs q{};
+  q.Z = one.cof(Zm); q.Sw = one.cof(Sw); q.w = one.cof(wpad); q.part = one.of(part);
+  q.ldz = ldz; q.np1 = np1; q.kp = kp; q.tiles_m = np1 / TILE; q.tiles_n = kp / TILE; q.n_units = 1;
+  hipLaunchKernelGGL(pool_quad_kernel, dim3(q.tiles_m * q.tiles_n), dim3(GEMM_THREADS), 0, s, q);
+  GP_HIP(hipGetLastError());
+  PoolFinishArgs f{};
+  f.part = one.cof(part); f.Kvec = one.cof(&gpfit_ctx::Kvec); f.tiles_n = kp / TILE;
+  f.A = one.same(0.0); f.A2 = one.same(0.0); f.lambda0 = one.same(0.0);
+  f.mu = one.of(&gpfit_ctx::lam_m); f.sigma2 = one.of(&gpfit_ctx::lam_var);
+  f.np1 = np1; f.rows = rows;
+  hipLaunchKernelGGL(pool_finish_kernel, dim3((rows + 255) / 256, 1), dim3(256), 0, s, f);
+  GP_HIP(hipGetLastError());
+
+  // off the diagonal: W = Z S, then G += W Z^T on the tiles on or below the block diagonal
+  GP_TRY(product_whole_k(lane, {np1, kp, kp}, plain(one.mats(Zm, ldz)), plain(one.mats(Sf, kp)), into(one.mats(Wm, kp))));
+  GP_TRY(product_whole_k(lane, {np1, np1, kp}, plain(one.mats(Wm, kp)), trans(one.mats(Zm, ldz)),
+                         into_lower(one.mats(Gm, np1), 1.0)));
+  const int nb = (rows + 31) / 32;
+  hipLaunchKernelGGL(pool_cov_store_kernel, dim3(nb, nb), dim3(256), 0, s, ctx->*Gm, (int64_t)np1, ctx->lam_var, rows, Sigma,
+                     ldsig);
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 }  // namespace gpfit
 
@@ -335,6 +477,14 @@ extern "C" int gpfit_score_pool(gpfit_ctx* c, void* stream, double sigma0, const
                                 double* U) {
   return score_pool_impl("gpfit_score_pool", &c, 1, stream, &sigma0, &xstar, &ldxs, P, &pixels, &d_full, &xtilde, &ldxt, &nt, &d,
                          &C, &ldc, &B, &ldb, &k, &S, &lds, &w, &A, &lambda0, r, nr, chunk_rows, &mu, &sigma2, &rate, &U);
+}
+
+extern "C" int gpfit_pool_covariance(gpfit_ctx* ctx, void* stream, double sigma0, const double* xstar, int64_t ldxs, int64_t M,
+                                     const int* pixels, int64_t d_full, const double* xtilde, int64_t ldxt, int64_t nt,
+                                     int64_t d, const double* C, int64_t ldc, const double* B, int64_t ldb, int64_t k,
+                                     const double* S, int64_t lds, double* Sigma, int64_t ldsig) {
+  return pool_covariance_impl(ctx, stream, sigma0, xstar, ldxs, M, pixels, d_full, xtilde, ldxt, nt, d, C, ldc, B, ldb, k, S, lds,
+                              Sigma, ldsig);
 }
 
 extern "C" int gpfit_score_pool_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, const double* sigma0,

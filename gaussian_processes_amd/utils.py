@@ -1832,6 +1832,117 @@ def score_pool_cells(xstar, cells, r_masked=None, weights=None, chunk_rows=0, ma
     return res
 
 
+# ------------------------------------------------------------------ a round picked one by one (batch-aware selection)
+SELECT_MAX = 128         # GPFIT_SELECT_MAX of the C header
+SHORTLIST = 1024         # select_round's default: 8 MiB of covariance per cell, 16 cells in flight
+
+
+@torch.no_grad()
+def pool_covariance(xstar, xtilde, C, theta, folded, mask=None):
+    """Posterior covariance of the latents of a shortlist in one device call (``gpfit_pool_covariance``):
+    ``Sigma[i][j] = k(x_i, x_j) + z_i S z_j^T`` as a tensor [M, M], symmetric bit for bit, its diagonal the bits of
+    ``pool_moments``' ``sigma2`` on the same rows.  The arguments, their checks and the mask handling are those of
+    ``pool_moments``; the whole shortlist must fit this thread's workspace as one chunk (it is sized for it: M^2 doubles
+    per work matrix)."""
+    q = _score_pool_prepare(xstar, xtilde, C, theta, folded, mask)
+    xstar, xtilde, C, pix, S, B = (q[key] for key in ("xstar", "xtilde", "C", "pix", "S", "B"))
+    M = q["P"]
+    Sigma = torch.empty((M, M), dtype=TORCH_DTYPE, device=_device())
+    if M == 0:
+        return Sigma
+    eng = get_engine(max(q["nt"], q["k"], M), q["d"], q["d_full"])
+    _lib.check(_lib.load().gpfit_pool_covariance(
+        eng._ctx, _stream(), q["sigma0"], xstar.data_ptr(), xstar.stride(0), M, pix.data_ptr() if pix is not None else None,
+        q["d_full"], xtilde.data_ptr(), xtilde.stride(0), q["nt"], q["d"], C.data_ptr(), C.stride(0),
+        B.data_ptr() if B is not None else None, B.stride(0) if B is not None else 0, q["k"], S.data_ptr(), S.stride(0),
+        Sigma.data_ptr(), Sigma.stride(0)), "gpfit_pool_covariance")
+    return Sigma
+
+
+@torch.no_grad()
+def select_batch(Sigmas, mus, f_params_list, r_masked, n_select, weights=None):
+    """Pick ``n_select`` rows one by one, each conditioned on those already chosen (``gpfit_select_batch``; DESIGN.md
+    section 5): per unit (cell) the covariance ``Sigmas[u]`` [M, M] of ``pool_covariance``, the means ``mus[u]`` [M] and
+    the link parameters ``f_params_list[u]``; ``weights`` as in ``score_pool_cells`` (None: ones).  1 .. 16 units,
+    ``n_select`` in 1 .. 128.  Everything stays on the device and nothing is synchronised: returns a dict with ``picked``
+    (int64 [n_select], row indices in pick order, -1 from the step on at which no row with a finite utility is left),
+    ``utility`` ([n_select], the population utility of each pick when it was picked, NaN beside a -1) and ``sigma2`` (per
+    unit the conditional variances [M] given all picks)."""
+    n, n_select = len(Sigmas), int(n_select)
+    if not 1 <= n <= MAX_CHAIN_UNITS or len(mus) != n or len(f_params_list) != n:
+        raise ValueError(f"select_batch: 1 .. {MAX_CHAIN_UNITS} units, with one mean vector and one link each")
+    if not 1 <= n_select <= SELECT_MAX:
+        raise ValueError(f"select_batch: n_select is 1 .. {SELECT_MAX}")
+    dev = _device()
+    Sigmas = [_cu(S) for S in Sigmas]
+    mus = [_cu(m).reshape(-1).contiguous() for m in mus]
+    M = mus[0].numel()
+    if M < 1 or any(tuple(S.shape) != (M, M) or S.stride(1) != 1 for S in Sigmas) or any(m.numel() != M for m in mus):
+        raise ValueError("select_batch: every unit needs a covariance [M, M] and a mean [M] of one M >= 1")
+    r = _cu(r_masked).reshape(-1).contiguous()
+    w = None if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
+    if w is not None and len(w) != n:
+        raise ValueError("one weight per unit")
+    links = [_link_scalars(fp) for fp in f_params_list]
+    work = torch.empty((n, n_select, M), dtype=TORCH_DTYPE, device=dev)
+    s2 = torch.empty((n, M), dtype=TORCH_DTYPE, device=dev)
+    picked = torch.empty(n_select, dtype=torch.int32, device=dev)
+    utility = torch.empty(n_select, dtype=TORCH_DTYPE, device=dev)
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])   # noqa: E731
+    _lib.check(_lib.load().gpfit_select_batch(
+        _stream(), n, ptrs(Sigmas), (ctypes.c_int64 * n)(*[S.stride(0) for S in Sigmas]), M, ptrs(mus),
+        _lib.darr([a for a, _ in links]), _lib.darr([l0 for _, l0 in links]), None if w is None else _lib.darr(w), r.data_ptr(),
+        r.numel(), n_select, ptrs(list(work)), ptrs(list(s2)), picked.data_ptr(), utility.data_ptr()), "gpfit_select_batch")
+    return {"picked": picked.to(torch.int64), "utility": utility, "sigma2": list(s2)}
+
+
+@torch.no_grad()
+def select_round(xstar, cells, n_select, r_masked, weights=None, shortlist=SHORTLIST, chunk_rows=0):
+    """The images of one round of the closed loop, picked one by one, each conditioned on those already chosen.
+    ``xstar``, ``cells``, ``weights`` and ``chunk_rows`` are those of ``score_pool_cells`` (``cells`` may hold one cell):
+      1. the whole pool is scored with ``score_pool_cells``, unchanged;
+      2. the ``min(P, shortlist)`` rows of largest population utility are kept, sorted by pool index, so that among equal
+         utilities the image that comes first in the pool wins;
+      3. ``pool_covariance`` of the shortlist, cell after cell, then one ``select_batch`` for all cells.
+    An image outside the shortlist can never be picked: only the shortlist's covariance is formed, M^2 doubles per cell,
+    and that is what the shortlist is for.  The default of 1024 keeps it at 8 MiB per cell, 128 MiB with the 16 cells of
+    one call in flight, and is eight times the longest round; a shortlist above the workspace's ``POOL_ROWS`` is
+    refused.  ``shortlist >= P`` means the whole pool.
+
+    Returns a dict: ``picked`` (int64 device [n_select], POOL indices in pick order, -1 once nothing is left), ``utility``
+    ([n_select]), ``shortlist`` (the pool indices kept) and ``scores`` (what ``score_pool_cells`` returned).  The one
+    host synchronisation is the sort of the shortlist's indices inside torch."""
+    shortlist, n_select = int(shortlist), int(n_select)
+    if not 1 <= shortlist <= POOL_ROWS:
+        raise ValueError(f"select_round: shortlist is 1 .. {POOL_ROWS} (the rows the pool workspace is sized for)")
+    if not 1 <= len(cells) <= MAX_CHAIN_UNITS:
+        raise ValueError(f"select_round: 1 .. {MAX_CHAIN_UNITS} cells")
+    if not 1 <= n_select <= SELECT_MAX:
+        raise ValueError(f"select_round: n_select is 1 .. {SELECT_MAX}")
+    xstar = _cu(xstar)
+    xstar = xstar.reshape(-1, xstar.shape[-1])
+    scores = score_pool_cells(xstar, cells, r_masked=r_masked, weights=weights, chunk_rows=chunk_rows)
+    for err in scores["errors"]:
+        if err is not None:
+            raise err
+    P = xstar.shape[0]
+    if P == 0:
+        raise ValueError("select_round: the pool is empty")
+    total = scores["population_utility"]
+    if shortlist >= P:
+        keep = torch.arange(P, device=total.device)
+    else:
+        # NaN sorts as the largest value in torch.topk: such rows would only waste the shortlist
+        keep = torch.sort(torch.topk(torch.nan_to_num(total, nan=-float("inf")), shortlist).indices).values
+    rows = xstar[keep].contiguous()
+    Sigmas = [pool_covariance(rows, c["xtilde"], c["C"], c["theta"], c["folded"], c.get("mask")) for c in cells]
+    out = select_batch(Sigmas, [scores["mu"][u][keep] for u in range(len(cells))], [c["f_params"] for c in cells], r_masked,
+                       n_select, weights)
+    local = out["picked"]
+    picked = torch.where(local >= 0, keep[local.clamp_min(0)], local)
+    return {"picked": picked, "utility": out["utility"], "shortlist": keep, "scores": scores}
+
+
 # ------------------------------------------------------------------ initialisation (utils.py:705-857)
 def generate_xtilde(ntilde, x):
     """Jittered random subset of the first ``ntilde`` stimuli (utils.py:705-711)."""

@@ -711,6 +711,53 @@ int gpfit_score_pool_batch(gpfit_ctx* const* ctxs, int n_units, void* stream, co
  * limited by GPFIT_ESTEP_CHAIN_MAX_UNITS.  Asynchronous on `stream`; P == 0 returns at once. */
 int gpfit_utility_sum(void* stream, const double* U, int64_t ldu, int n_rows, const double* weight, int64_t P, double* out);
 
+/* Posterior covariance of the latents of a shortlist of M candidate images: with the operands of gpfit_score_pool (same
+ * meaning: masked rows or whole images with `pixels`, B == NULL for the identity basis, only the lower triangle of S read)
+ *     Sigma[i][j] = k(x_i, x_j) + z_i S_b z_j^T   (i != j),   z_i = k*_i B,  k the arc-cosine kernel of gpfit_acosker
+ *     Sigma[i][i] = the sigma2_i that gpfit_score_pool writes for the same row, bit for bit (its k**_i + z_i S_b z_i^T
+ *                   form, not the "- 1e-7" diagonal of the off-diagonal formula)
+ * into Sigma, device [M][ldsig] (ldsig >= M) owned by the caller.  One triangle of tiles is computed and mirrored on the
+ * way out: Sigma[i][j] and Sigma[j][i] have the same bits.  The dense products (x* C, K* B, W = Z S_b, W Z^T) go out as
+ * pointer batches as in the pool call, so none is cut along k: the bits of an element depend on its two rows and on
+ * which of them comes first, not on the context's capacity, on M or on where the rows sit in the shortlist.
+ * M, nt, k (rounded up to 128) and d must fit the context (-3 otherwise, "problem larger than the context capacity",
+ * nothing written); the whole shortlist is one chunk of the workspace.  Nothing is allocated, no atomics.  Asynchronous on
+ * `stream`; M == 0 returns at once. */
+int gpfit_pool_covariance(gpfit_ctx* ctx, void* stream, double sigma0, const double* xstar, int64_t ldxs, int64_t M,
+                          const int* pixels, int64_t d_full, const double* xtilde, int64_t ldxt, int64_t nt, int64_t d,
+                          const double* C, int64_t ldc, const double* B, int64_t ldb, int64_t k, const double* S,
+                          int64_t lds, double* Sigma, int64_t ldsig);
+
+/* Pick the n_select images of a round one by one, each conditioned on those already chosen, for 1 .. 16 units (cells)
+ * that see the same M candidates.  One more presentation of image i adds A^2 f_i a_i a_i^T to the posterior precision
+ * (the E-step's Newton term) and, at the expected response r_i = f_i, leaves the mean where it is: a rank-1 Gaussian
+ * conditioning of the latents with pseudo-noise tau_i = 1 / (A^2 f_i).  Step t = 0 .. n_select - 1:
+ *   1. U_u[j] = the utility of gpfit_nd_utility at (A_u^2 s_u[j], A_u mu_u[j] + lambda0_u) with s_u the current
+ *      conditional variances (the same device code, the arguments rounded as gpfit_score_pool rounds them), and
+ *      T[j] = sum_u weight[u] U_u[j] in the order and rounding of gpfit_utility_sum (one unit, no weights: T = U).
+ *   2. i = the lowest index among the rows not yet chosen whose T[j] is finite and maximal; picked[t] = i,
+ *      utility[t] = T[i].  If no row qualifies, this and every later step write -1 and NaN and do nothing else.
+ *   3. per unit: tau = 1 / (A^2 exp(A mu_i + A^2 s_i / 2 + lambda0)), v = s_i + tau,
+ *      c_j = Sigma[j][i] - sum_{q<t} G[q][j] G[q][i],  G[t][j] = c_j / sqrt(v),  s_j -= G[t][j]^2  (chosen rows too).
+ * With n_select == 1 the call is the argmax of gpfit_score_pool's utility.  The conditional variances are those of exact
+ * Gaussian conditioning on the chosen rows with noise diag(tau).
+ *   Sigma[u]  device [M][ldsig[u]], symmetric (gpfit_pool_covariance);  mu[u] device [M]
+ *   A, lambda0, weight   HOST [n_units]; weight may be NULL (every weight one)
+ *   r   device [nr] response counts
+ *   work[u]         device [n_select][M]: the factor rows G on return; its prior content is irrelevant
+ *   sigma2_cond[u]  device [M]: written by the call -- it starts as the diagonal of Sigma[u] and ends as the
+ *                   conditional variances given all picks
+ *   picked (int), utility   device [n_select]
+ * 2 n_select + 1 small launches ordered by the stream alone: no cooperative launch, no grid-wide barrier, no spin-wait,
+ * no atomic, no host synchronisation, nothing allocated; every sum is reduced in a fixed order (bit-reproducible).
+ * Refused (-3, nothing written): n_units outside 1 .. 16, n_select outside 1 .. GPFIT_SELECT_MAX, M < 1, null
+ * pointers, ldsig[u] < M.  Takes no context.  Asynchronous on `stream`. */
+#define GPFIT_SELECT_MAX 128      /* = the block of one gpfit_potrf_append_block step */
+int gpfit_select_batch(void* stream, int n_units, const double* const* Sigma, const int64_t* ldsig, int64_t M,
+                       const double* const* mu, const double* A, const double* lambda0, const double* weight,
+                       const double* r, int nr, int n_select, double* const* work, double* const* sigma2_cond,
+                       int* picked, double* utility);
+
 /* Per-launch HIP-event timing of the dominant kernels during gpfit_fit_eval (bench.py's
  * roofline leg; adds two event records per launch, so leave it off when timing throughput).
  * out16: 0 sum of the 128-tile GEMM launch durations [ms] (the dominant kernel family, stream-K
