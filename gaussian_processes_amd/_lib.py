@@ -29,6 +29,23 @@ class DevGemmRoute(ctypes.Structure):
                                               "sumsq_entries", "blocks", "pair", "slabs")]
 
 
+class DevEwArgs(ctypes.Structure):
+    """gpfit_dev_ew_args (test hooks of include/gpfit_mi355x.h): the slots of gpfit_dev_elementwise."""
+    _fields_ = [("p", vp * 16), ("ld", i64 * 4), ("n", ctypes.c_int32 * 4), ("s", f64 * 2), ("theta", f64 * 8),
+                ("n_units", ctypes.c_int32), ("up", ctypes.POINTER(vp) * 8), ("uld", ctypes.POINTER(i64) * 4),
+                ("un", ctypes.POINTER(ctypes.c_int32) * 4), ("us", pd * 2)]
+
+
+# the op numbers of gpfit_dev_elementwise, in the order of the header's enum; a group form is op + EW_GROUP
+EW_OPS = ("trmv_lower", "trmv_lower_t", "symv_lower", "gemv_sub", "gemv_t_sub", "dot", "logdet", "logdet_pair", "frob_lower",
+          "frob_tiles", "reduce_slices", "reduce_slabs", "reduce_slices_sym", "pack_lower", "pack_tri", "unpack_sym",
+          "unpack_tri", "symmetrize", "symmetrize_avg", "pad_copy", "gather", "estep_build", "add_diag", "axpby_block",
+          "demote_block", "qvec", "moments", "adjoint", "adjoint_reduce", "adjoint_rect", "metric_contract", "dk_sigma0", "dq",
+          "dk_metric", "estep_prep", "rowscale_add")
+EW_OP = {name: k for k, name in enumerate(EW_OPS)}
+EW_GROUP = 256
+
+
 _SIGS = {
     "gpfit_version": (i32, []),
     "gpfit_last_error": (ctypes.c_char_p, []),
@@ -113,6 +130,7 @@ _SIGS = {
     "gpfit_dev_ctx_copy": (i32, [vp, ctypes.c_char_p, i64, vp, i64, i32]),
     "gpfit_dev_ctx_fill": (i32, [vp, ctypes.c_char_p, i32]),
     "gpfit_dev_potrf": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, i32, ctypes.c_uint32, ctypes.c_uint32, i32]),
+    "gpfit_dev_elementwise": (i32, [vp, vp, i32, i32, ctypes.POINTER(DevEwArgs)]),
 }
 
 _lib = None

@@ -1,7 +1,8 @@
 // C-ABI test hooks of the GEMM launcher: which route a launch takes, the plans of the balanced schedules, and an
 // entry point that reaches every field of GemmArgsT (both element types, pointer batches, strided batches,
 // split-K, fused epilogues, the pair launch) -- and of the Cholesky recursion: potrf_lockstep on the caller's own
-// buffers with every argument exposed.  No arithmetic happens here: the hooks fill the launcher's own argument
+// buffers with every argument exposed -- and of the element-wise and reduction launchers of elementwise.hip, one table
+// from an op number to the launcher.  No arithmetic happens here: the hooks fill the launcher's own argument
 // struct and read the launcher's own decision (gemm_route, common.h) and its planners.
 #include "gemm_core.h"
 #include "context.h"
@@ -187,10 +188,212 @@ int potrf(gpfit_ctx* c, hipStream_t s, int nb, void* const* A, void* const* L, v
   return potrf_lockstep<R>(B, 0, n, need, main_lane(c, s), halves);
 }
 
+// ---- the element-wise launchers by number (gpfit_dev_elementwise): a table from the op to its launch_* function
+// what an op requires: the pointers p[0 .. nptr), the extents n[0 .. nsize) >= 1; f32: the launcher has a float instance
+struct EwSpec { int nptr, nsize; bool f32; };
+constexpr EwSpec EW_SPEC[GPFIT_EW_NOPS] = {
+    /* TRMV_LOWER */ {3, 1, true},   /* TRMV_LOWER_T */ {4, 1, true},    /* SYMV_LOWER */ {3, 1, false},
+    /* GEMV_SUB */ {4, 2, true},     /* GEMV_T_SUB */ {5, 2, true},      /* DOT */ {3, 1, true},
+    /* LOGDET */ {2, 1, true},       /* LOGDET_PAIR */ {4, 1, true},     /* FROB_LOWER */ {3, 1, true},
+    /* FROB_TILES */ {2, 2, true},   /* REDUCE_SLICES */ {2, 1, true},   /* REDUCE_SLABS */ {2, 4, true},
+    /* REDUCE_SLICES_SYM */ {2, 2, true}, /* PACK_LOWER */ {2, 2, true}, /* PACK_TRI */ {2, 2, false},
+    /* UNPACK_SYM */ {2, 1, false},  /* UNPACK_TRI */ {2, 1, false},     /* SYMMETRIZE */ {1, 1, true},
+    /* SYMMETRIZE_AVG */ {1, 1, false}, /* PAD_COPY */ {2, 4, false},    /* GATHER */ {2, 4, true},
+    /* ESTEP_BUILD */ {5, 2, false}, /* ADD_DIAG */ {1, 1, true},        /* AXPBY_BLOCK */ {2, 2, true},
+    /* DEMOTE_BLOCK */ {2, 2, false}, /* QVEC */ {4, 3, true},           /* MOMENTS */ {13, 1, true},
+    /* ADJOINT */ {8, 2, true},      /* ADJOINT_REDUCE */ {8, 4, true},  /* ADJOINT_RECT */ {13, 4, false},
+    /* METRIC_CONTRACT */ {6, 3, true}, /* DK_SIGMA0 */ {4, 2, false},   /* DQ */ {3, 2, false},
+    /* DK_METRIC */ {6, 2, false},   /* ESTEP_PREP */ {5, 2, false},     /* ROWSCALE_ADD */ {3, 2, true},
+};
+
+// the multiples the launchers state for their extents (kernels.h); launch_gather and launch_gemv_t_sub refuse their own
+bool ew_multiples(int op, const int32_t* n) {
+  switch (op) {
+    case GPFIT_EW_TRMV_LOWER_T: return n[0] % 64 == 0;
+    case GPFIT_EW_FROB_LOWER: return n[0] % TILE == 0;
+    case GPFIT_EW_FROB_TILES: return n[0] % TILE == 0 && n[1] % TILE == 0;
+    case GPFIT_EW_PACK_LOWER: case GPFIT_EW_ESTEP_BUILD: return n[1] % TILE == 0;
+    case GPFIT_EW_ADJOINT: return n[1] % 64 == 0;
+    case GPFIT_EW_ADJOINT_RECT: return n[2] % 64 == 0 && n[3] % 64 == 0;
+    case GPFIT_EW_AXPBY_BLOCK: return n[1] % 2 == 0;
+    default: return true;
+  }
+}
+
+template <typename R>
+int ew_single(hipStream_t s, int op, const gpfit_dev_ew_args& a) {
+  void* const* p = a.p;
+  const int64_t* ld = a.ld;
+  const int32_t* n = a.n;
+  auto in = [&](int k) { return (const R*)p[k]; };
+  auto out = [&](int k) { return (R*)p[k]; };
+  auto din = [&](int k) { return (const double*)p[k]; };
+  auto dout = [&](int k) { return (double*)p[k]; };
+  switch (op) {
+    case GPFIT_EW_TRMV_LOWER: return launch_trmv_lower<R>(in(0), ld[0], n[0], in(1), out(2), s);
+    case GPFIT_EW_TRMV_LOWER_T: return launch_trmv_lower_t<R>(in(0), ld[0], n[0], in(1), out(2), dout(3), s);
+    case GPFIT_EW_GEMV_SUB: return launch_gemv_sub<R>(in(0), ld[0], n[0], n[1], in(1), in(2), out(3), s);
+    case GPFIT_EW_GEMV_T_SUB: return launch_gemv_t_sub<R>(in(0), ld[0], n[0], n[1], in(1), in(2), out(3), dout(4), s);
+    case GPFIT_EW_DOT: return launch_dot<R>(in(0), in(1), n[0], dout(2), s);
+    case GPFIT_EW_LOGDET: return launch_logdet<R>(in(0), ld[0], n[0], dout(1), s);
+    case GPFIT_EW_LOGDET_PAIR: return launch_logdet_pair<R>(in(0), dout(1), in(2), dout(3), ld[0], n[0], s);
+    case GPFIT_EW_FROB_LOWER: return launch_frob_lower<R>(in(0), ld[0], n[0], dout(1), dout(2), s);
+    case GPFIT_EW_FROB_TILES: return launch_frob_tiles<R>(in(0), ld[0], n[0], n[1], n[2], dout(1), s);
+    case GPFIT_EW_REDUCE_SLICES: return launch_reduce_slices<R, R>(in(0), ld[0], n[0], out(1), ld[1], s);
+    case GPFIT_EW_REDUCE_SLABS: return launch_reduce_slabs<R>(in(0), ld[0], n[0], n[1], out(1), n[2], n[3], s);
+    case GPFIT_EW_REDUCE_SLICES_SYM: return launch_reduce_slices_sym<R>(in(0), ld[0], n[0], out(1), n[1], s);
+    case GPFIT_EW_PACK_LOWER: return launch_pack_lower<R>(in(0), ld[0], n[0], out(1), ld[1], n[1], s);
+    case GPFIT_EW_SYMMETRIZE: return launch_symmetrize<R>(out(0), ld[0], n[0], s);
+    case GPFIT_EW_GATHER:
+      return launch_gather<R>(in(0), ld[0], n[0], (const int*)p[2], n[1], n[2], n[3], out(1), ld[1], out(3), ld[2], s);
+    case GPFIT_EW_ADD_DIAG: return launch_add_diag<R>(out(0), ld[0], n[0], a.s[0], s);
+    case GPFIT_EW_AXPBY_BLOCK: return launch_axpby_block<R>(out(0), ld[0], in(1), ld[1], n[0], n[1], a.s[0], a.s[1], s);
+    case GPFIT_EW_QVEC: return launch_qvec<R>(in(0), in(1), ld[0], n[2], n[0], n[1], a.s[0], out(2), out(3), s);
+    case GPFIT_EW_MOMENTS:
+      return launch_moments<R>(in(0), in(1), in(2), ld[0], in(3), ld[1], in(4), in(5), n[0], a.s[0], a.s[1], out(6), out(7),
+                               out(8), out(9), dout(10), dout(11), (int*)p[12], s);
+    case GPFIT_EW_ADJOINT:
+      return launch_adjoint<R>(in(0), in(1), ld[0], in(2), in(3), n[0], n[1], out(4), dout(5), dout(6), dout(7), s);
+    case GPFIT_EW_ADJOINT_REDUCE:
+      return launch_adjoint_reduce<R>(din(0), din(1), din(2), n[2], n[3], in(3), in(4), n[0], n[1], out(5), dout(6), dout(7),
+                                      s);
+    case GPFIT_EW_METRIC_CONTRACT: {
+      Theta th;
+      static_assert(sizeof(Theta) == sizeof(a.theta), "gpfit_dev_ew_args::theta is Theta as its doubles");
+      std::memcpy(&th, a.theta, sizeof(th));
+      return launch_metric_contract<R>(th, (const int*)p[0], n[0], n[1], n[2], in(1), ld[0], in(2), ld[1], dout(3), dout(4),
+                                       (int*)p[5], s);
+    }
+    case GPFIT_EW_ROWSCALE_ADD: return launch_rowscale_add<R>(out(0), ld[0], in(1), ld[1], in(2), n[0], n[1], s, a.s[0]);
+    default: break;
+  }
+  return -3;
+}
+
+// the launchers that exist for double only
+int ew_single_f64(hipStream_t s, int op, const gpfit_dev_ew_args& a) {
+  void* const* p = a.p;
+  const int64_t* ld = a.ld;
+  const int32_t* n = a.n;
+  auto in = [&](int k) { return (const double*)p[k]; };
+  auto out = [&](int k) { return (double*)p[k]; };
+  switch (op) {
+    case GPFIT_EW_SYMV_LOWER: return launch_symv_lower(in(0), ld[0], n[0], in(1), out(2), s);
+    case GPFIT_EW_PACK_TRI: return launch_pack_tri(in(0), ld[0], n[0], out(1), ld[1], n[1], s);
+    case GPFIT_EW_UNPACK_SYM: return launch_unpack_sym(in(0), ld[0], n[0], out(1), ld[1], s);
+    case GPFIT_EW_UNPACK_TRI: return launch_unpack_tri(in(0), ld[0], n[0], out(1), ld[1], s);
+    case GPFIT_EW_SYMMETRIZE_AVG: return launch_symmetrize_avg(out(0), ld[0], n[0], s);
+    case GPFIT_EW_PAD_COPY: return launch_pad_copy(in(0), ld[0], n[0], n[1], out(1), ld[1], n[2], n[3], s);
+    case GPFIT_EW_ESTEP_BUILD: return launch_estep_build(in(0), ld[0], n[0], n[1], in(1), out(2), out(3), out(4), ld[1], s);
+    case GPFIT_EW_DEMOTE_BLOCK: return launch_demote_block(in(0), ld[0], (float*)p[1], ld[1], n[0], n[1], s);
+    case GPFIT_EW_ADJOINT_RECT:
+      return launch_adjoint_rect(in(0), ld[0], in(1), ld[1], in(2), in(3), n[0], n[1], n[2], n[3], out(4), ld[2], out(5), out(6),
+                                 out(7), in(13), out(8), out(9), out(10), out(11), out(12), s);
+    case GPFIT_EW_DK_SIGMA0: return launch_dk_sigma0(in(0), ld[0], in(1), in(2), n[0], n[1], a.s[0], out(3), ld[1], s);
+    case GPFIT_EW_DQ: return launch_dq(in(0), in(1), ld[0], n[1], n[0], in(2), out(3), out(4), s);
+    case GPFIT_EW_DK_METRIC: return launch_dk_metric(out(0), ld[0], in(1), ld[1], in(2), in(3), in(4), in(5), n[0], n[1], s);
+    case GPFIT_EW_ESTEP_PREP: return launch_estep_prep(in(0), in(1), in(2), n[0], n[1], a.s[0], out(3), out(4), s);
+    default: break;
+  }
+  return ew_single<double>(s, op, a);
+}
+
+// the unit-batched launchers: the host tables copied into PerUnit<>, a common value where no table is given
+template <typename T>
+PerUnit<T> ew_ptrs(const gpfit_dev_ew_args& a, int k) {
+  PerUnit<T> r{};
+  for (int u = 0; u < a.n_units; ++u) r.v[u] = a.up[k] ? (T)a.up[k][u] : nullptr;
+  return r;
+}
+PerUnit<int> ew_sizes(const gpfit_dev_ew_args& a, int k) {
+  PerUnit<int> r{};
+  for (int u = 0; u < a.n_units; ++u) r.v[u] = a.un[k] ? a.un[k][u] : a.n[k];
+  return r;
+}
+PerUnit<int64_t> ew_lds(const gpfit_dev_ew_args& a, int k) {
+  PerUnit<int64_t> r{};
+  for (int u = 0; u < a.n_units; ++u) r.v[u] = a.uld[k] ? a.uld[k][u] : a.ld[k];
+  return r;
+}
+PerUnit<double> ew_scalars(const gpfit_dev_ew_args& a, int k) {
+  PerUnit<double> r{};
+  for (int u = 0; u < a.n_units; ++u) r.v[u] = a.us[k] ? a.us[k][u] : a.s[k];
+  return r;
+}
+
+int ew_group(hipStream_t s, int op, const gpfit_dev_ew_args& a) {
+  const int nu = a.n_units;
+  const int64_t* ld = a.ld;
+  const int32_t* n = a.n;
+  auto in = [&](int k) { return ew_ptrs<const double*>(a, k); };
+  auto out = [&](int k) { return ew_ptrs<double*>(a, k); };
+  switch (op) {
+    case GPFIT_EW_TRMV_LOWER: return launch_trmv_lower_group(nu, out(0), ld[0], n[0], out(1), out(2), s);
+    case GPFIT_EW_TRMV_LOWER_T: return launch_trmv_lower_t_group(nu, out(0), ld[0], n[0], out(1), out(2), out(3), s);
+    case GPFIT_EW_SYMV_LOWER: return launch_symv_lower_group(nu, out(0), ld[0], n[0], out(1), out(2), s);
+    case GPFIT_EW_DOT: return launch_dot_group(nu, out(0), out(1), n[0], out(2), s);
+    case GPFIT_EW_LOGDET_PAIR: return launch_logdet_pair_group(nu, in(0), out(1), in(2), out(3), ld[0], ew_sizes(a, 0), s);
+    case GPFIT_EW_REDUCE_SLICES: return launch_reduce_slices_group(nu, out(0), ld[0], n[0], out(1), ld[1], s);
+    case GPFIT_EW_PACK_LOWER:
+      return launch_pack_lower_group(nu, in(0), ew_lds(a, 0), ew_sizes(a, 0), out(1), ld[1], n[1], s);
+    case GPFIT_EW_PACK_TRI: return launch_pack_tri_group(nu, in(0), ew_lds(a, 0), ew_sizes(a, 0), out(1), ld[1], n[1], s);
+    case GPFIT_EW_SYMMETRIZE: return launch_symmetrize_group(nu, out(0), ld[0], n[0], s);
+    case GPFIT_EW_SYMMETRIZE_AVG: return launch_symmetrize_avg_group(nu, out(0), ld[0], ew_sizes(a, 0), s);
+    case GPFIT_EW_PAD_COPY:
+      return launch_pad_copy_group(nu, in(0), ew_lds(a, 0), ew_sizes(a, 0), ew_sizes(a, 1), out(1), ld[1], n[2], n[3], s);
+    case GPFIT_EW_GATHER:
+      return launch_gather_group(nu, in(0), ew_lds(a, 0), ew_sizes(a, 0), ew_ptrs<const int*>(a, 2), ew_sizes(a, 1), n[2], n[3],
+                                 out(1), ld[1], s);
+    case GPFIT_EW_ADD_DIAG: return launch_add_diag_group(nu, out(0), ld[0], n[0], a.s[0], s);
+    case GPFIT_EW_QVEC:
+      return launch_qvec_group(nu, in(0), in(1), ld[0], n[2], ew_sizes(a, 0), n[1], ew_scalars(a, 0), out(2), out(3), s);
+    default: break;
+  }
+  return -3;
+}
+
+// what a wrong test could turn into a wild access, refused before any launch
+bool ew_valid(int op, int is_f32, const gpfit_dev_ew_args& a) {
+  const bool group = (op & GPFIT_EW_GROUP) != 0;
+  const int base = op & ~GPFIT_EW_GROUP;
+  if (base < 0 || base >= GPFIT_EW_NOPS) return false;
+  const EwSpec sp = EW_SPEC[base];
+  if (is_f32 && (group || !sp.f32)) return false;
+  if (!group) {
+    for (int k = 0; k < sp.nptr; ++k) if (!a.p[k]) return false;
+    for (int k = 0; k < sp.nsize; ++k) if (a.n[k] < 1) return false;
+    if (base == GPFIT_EW_REDUCE_SLICES && a.ld[1] < 1) return false;
+    return ew_multiples(base, a.n);
+  }
+  if (a.n_units < 1 || a.n_units > CHAIN_MAXU) return false;
+  for (int k = 0; k < sp.nptr; ++k) {
+    if (!a.up[k]) return false;
+    for (int u = 0; u < a.n_units; ++u) if (!a.up[k][u]) return false;
+  }
+  for (int k = 0; k < sp.nsize; ++k)
+    for (int u = 0; u < a.n_units; ++u) if ((a.un[k] ? a.un[k][u] : a.n[k]) < 1) return false;
+  if (base == GPFIT_EW_REDUCE_SLICES && a.ld[1] < 1) return false;
+  return ew_multiples(base, a.n);   // the extents with a stated multiple are common to the units
+}
+
 }  // namespace
 }  // namespace gpfit
 
 extern "C" {
+
+int gpfit_dev_elementwise(gpfit_ctx* ctx, void* stream, int op, int is_f32, const gpfit_dev_ew_args* args) {
+  if (!ctx || !args || !gpfit::ew_valid(op, is_f32, *args)) {
+    gpfit::set_error("gpfit_dev_elementwise: bad argument");
+    return -3;
+  }
+  GP_CTX_ENTER(ctx, "gpfit_dev_elementwise");
+  hipStream_t s = (hipStream_t)stream;
+  if (op & GPFIT_EW_GROUP) return gpfit::ew_group(s, op & ~GPFIT_EW_GROUP, *args);
+  if (op == GPFIT_EW_REDUCE_SLICES && !is_f32 && args->n[1] == 1)   // double slices into a float destination
+    return gpfit::launch_reduce_slices<double, float>((const double*)args->p[0], args->ld[0], args->n[0], (float*)args->p[1],
+                                                      args->ld[1], s);
+  return is_f32 ? gpfit::ew_single<float>(s, op, *args) : gpfit::ew_single_f64(s, op, *args);
+}
 
 int gpfit_dev_gemm_route(int is_f32, const gpfit_dev_gemm_args* args, const gpfit_dev_gemm_args* pair_args,
                          gpfit_dev_gemm_route_t* out) {

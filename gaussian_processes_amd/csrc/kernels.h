@@ -101,15 +101,19 @@ template <typename R>
 int launch_localker(const Theta& th, const int* pix, int d, int dp, int n_rows, int n_cols, R* C, int64_t ldc,
                     R* dC, hipStream_t s);
 // Xt[k][n] = X[n][pix[k]] (k-major, zero padded to [dp][ldt]) and optionally the row-major
-// masked copy Xm[n][k] ([np][ldm], zero padded).
+// masked copy Xm[n][k] ([np][ldm], zero padded).  dp, np: multiples of 32.  Of X only the rows below n and the columns
+// the pixel list names are read (pix == nullptr: the first d columns).
 template <typename R>
 int launch_gather(const R* X, int64_t ldx, int n, const int* pix, int d, int dp, int np, R* Xt, int64_t ldt, R* Xm,
                   int64_t ldm, hipStream_t s);
-// h[n] = sum_k Xt[k][n]*XCt[k][n];  Kvec = h + s0^2;  q = sqrt(Kvec)  (q = 1 on padding)
+// h[n] = sum_k Xt[k][n]*XCt[k][n];  Kvec = h + s0^2;  q = sqrt(Kvec)  (Kvec = q = 1 on the padding n .. np: the
+// adjoint pass multiplies q's padding by zero, so it has to be finite).  All dp rows, the columns below n only, are read.
 template <typename R>
 int launch_qvec(const R* Xt, const R* XCt, int64_t ld, int dp, int n, int np, double s0sq, R* Kvec, R* q,
                 hipStream_t s);
-// dst lower tiles <- src (n x n, ld lds) with identity padding up to np.
+// dst lower tiles <- src (n x n, ld lds) with identity padding up to np (a multiple of 128).  Whole 128-tiles on and
+// below the diagonal are written -- inside a diagonal tile what src holds above its diagonal is copied as it is -- and
+// the tiles above the diagonal are left alone.
 template <typename R>
 int launch_pack_lower(const R* src, int64_t lds, int n, R* dst, int64_t ldd, int np, hipStream_t s);
 // mirror the lower triangle of an n x n matrix into its upper triangle (in place)
@@ -117,10 +121,13 @@ template <typename R> int launch_symmetrize(R* A, int64_t lda, int n, hipStream_
 // out[0] = 2*sum_i log(L_ii), i < n
 template <typename R> int launch_logdet(const R* L, int64_t ldl, int n, double* out, hipStream_t s);
 template <typename R> int launch_logdet_pair(const R* L0, double* out0, const R* L1, double* out1, int64_t ldl, int n, hipStream_t s);
-// out[0] = sum over the lower-triangular tiles of T^2 (T has exact zeros above its diagonal)
+// out[0] = sum over the lower-triangular tiles of T^2 (T has exact zeros above its diagonal inside the diagonal tiles;
+// the tiles above the diagonal are not read).  np: a multiple of 128; partial: np/128 (np/128 + 1) / 2 doubles.
 template <typename R>
 int launch_frob_lower(const R* T, int64_t ldt, int np, double* out, double* partial, hipStream_t s);
-// y = L x (L lower, row-major) ; and z = L^T x
+// y = L x (L lower, row-major) ; and z = L^T x.  Only L[i][j], j <= i, is read: what lies above the diagonal may hold
+// anything.  All np entries of x are read and of y / z written (a padded factor has the identity there).  The transposed
+// form needs np a multiple of 64 and partial: ceil(np / TRMV_ROWS) * np doubles.
 template <typename R> int launch_trmv_lower(const R* L, int64_t ldl, int np, const R* x, R* y, hipStream_t s);
 template <typename R>
 int launch_trmv_lower_t(const R* L, int64_t ldl, int np, const R* x, R* z, double* partial, hipStream_t s);
@@ -140,7 +147,8 @@ int launch_demote_block(const double* src, int64_t lds, float* dst, int64_t ldd,
 // out[0] = x . y
 template <typename R> int launch_dot(const R* x, const R* y, int n, double* out, hipStream_t s);
 
-// Latent moments / rate / likelihood pieces in the full-rank original basis:
+// Latent moments / rate / likelihood pieces in the full-rank original basis; of Cos and V the diagonals
+// alone are read, every vector below n only:
 //   lam_m = m ; lam_var = Kvec - K~_ii + V_ii ; f = exp(A lam_m + A^2/2 lam_var + lambda0)
 //   scal[0] = r.lam_m  scal[1] = sum r  scal[2] = sum f
 //   wl_i = -1/2 A^2 f_i g_i  with g_i = 1 - J_ii - (pi - delta_ii)(1 - c_ii)/pi
@@ -155,23 +163,29 @@ int launch_moments(const R* Kvec, const R* q, const R* Cos, int64_t ldc, const R
 //   diagonal inside the diagonal tiles, zero on padding); the tiles above the diagonal are not written;
 //   upart[tj][i] = sum_{j in tile tj} Bm_ij q_j  (+ mirrored contribution -> vpart[ti][j])
 //   sumA_part[tile] = sum of Aw over the tile (off-diagonal tiles counted twice)
+// np: a multiple of 64.  The canonical lower triangle of W and Cos alone is read, below row and column n (a diagonal
+// tile takes (j, i) for i < j).  b is read below n only; q up to np, its padding multiplied by zero: it has to be finite
+// (launch_qvec writes 1).  upart, vpart: np/64 * np doubles each, sumA_part: one per lower tile; upart[t][i] is written for
+// t <= i / 64 and vpart[t][i] for t > i / 64, and that is all launch_adjoint_reduce reads.
 template <typename R>
 int launch_adjoint(const R* W, const R* Cos, int64_t ld, const R* b, const R* q, int n, int np, R* Aout,
                    double* upart, double* vpart, double* sumA_part, hipStream_t s);
 // u_i = sum_t upart[t][i] + vpart[t][i];  tvec_i = u_i/q_i - wl_i (uq: fp64 scratch [np]);
 // scal_out[0] = sum_i u_i/q_i, scal_out[1] = sum_i wl_i, scal_out[2] = sum of sumA_part
+// (ntile = np / 64, ntile_tri = the number of lower tiles; q and wl are read below n only; tvec and uq are zero on n .. np)
 template <typename R>
 int launch_adjoint_reduce(const double* upart, const double* vpart, const double* sumA_part, int ntile,
                           int ntile_tri, const R* q, const R* wl, int n, int np, R* tvec, double* uq,
                           double* scal_out, hipStream_t s);
-// Y[n][k] += scale * t[n] * Xm[n][k]
+// Y[n][k] += scale * t[n] * Xm[n][k]  over all np rows and dp columns: the padding of t and Xm is read (zero there)
 template <typename R>
 int launch_rowscale_add(R* Y, int64_t ldy, const R* Xm, int64_t ldm, const R* t, int np, int dp, hipStream_t s,
                         double scale = 1.0);
-// dst = sum_z src[z] (split-K reduction), count elements each
+// dst = sum_z src[z] (split-K reduction), count elements each; what lies between count and slice_stride is not read
 template <typename RI, typename RO>
 int launch_reduce_slices(const RI* src, int64_t slice_stride, int nslice, RO* dst, int64_t count, hipStream_t s);
-// dst [rows][cols] = sum over the live k slabs of a row, z >= row / slab_rows, of src[z] (GemmArgsT::k_slabs)
+// dst [rows][cols] = sum over the live k slabs of a row, z >= row / slab_rows, of src[z] (GemmArgsT::k_slabs); the
+// slabs below a row's own never were written and are not read (rows past the last slab's start take the last slab)
 template <typename R>
 int launch_reduce_slabs(const R* src, int64_t slab_stride, int nslab, int slab_rows, R* dst, int rows, int cols, hipStream_t s);
 // dst = G + G^T, G = sum_z src[z] (n x n)
@@ -192,6 +206,8 @@ int launch_axpby_block(R* dst, int64_t ldd, const R* src, int64_t lds, int rows,
 
 // rectangular adjoint pass (W[n1][n2] against the analytic dK of acosker(x1, x2)): A_w, the two
 // u vectors as t = u/(2q) (+ extra1) and u/q, scal3 = {sum A_w, sum u1/q1, sum u2/q2}
+// np1, np2: multiples of 64.  W, Cos, q1, q2 and extra1 are read inside n1 x n2 only; Aout is written over np1 x np2 and
+// t1, uq1 / t2, uq2 over np1 / np2, zero on the padding.  upart: np2/64 * np1, vpart: np1/64 * np2, tile_sum: one per tile.
 int launch_adjoint_rect(const double* W, int64_t ldw, const double* Cos, int64_t ldc, const double* q1,
                         const double* q2, int n1, int n2, int np1, int np2, double* Aout, int64_t lda, double* upart,
                         double* vpart, double* tile_sum, const double* extra1, double* t1, double* t2, double* uq1,
@@ -226,11 +242,18 @@ int launch_estep_proj_moments(const double* Z, int64_t ld, int nb, const double*
                               double* lam_m, double* lam_var, hipStream_t s);
 
 // ---- E-step / factorisation / firing-rate helpers
+// estep_prep: s = A sqrt(f), rhs = A^2 f m + A (r - f) below n, both zero on n .. np.  estep_build: M = I + diag(s) K diag(s)
+// and Kl = K on the lower 128-tiles of np x np (identity / zero padding; the tiles above the diagonal are left alone),
+// SK = diag(s) K in full (zero padded).  K is read inside n x n only; sv over all of [0, np): its padding has to be the zero
+// estep_prep writes.  np: a multiple of 128.
 int launch_estep_prep(const double* f, const double* r, const double* m, int n, int np, double A, double* sv,
                       double* rhs, hipStream_t s);
 int launch_estep_build(const double* K, int64_t ldk, int n, int np, const double* sv, double* Mb, double* SK,
                        double* Kl, int64_t ld, hipStream_t s);
+// y = A x for a symmetric A stored in its lower triangle: what lies above the diagonal is not read
 int launch_symv_lower(const double* A, int64_t lda, int n, const double* x, double* y, hipStream_t s);
+// dst (n x n) <- the lower triangle of src, mirrored (unpack_sym) or with zeros above the diagonal (unpack_tri); what src
+// holds above its diagonal is not read
 int launch_unpack_sym(const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
 int launch_unpack_tri(const double* src, int64_t lds, int n, double* dst, int64_t ldd, hipStream_t s);
 // dst [np][ldd] <- the lower triangle of src (n x n; what src holds above its diagonal is not read), zero above the

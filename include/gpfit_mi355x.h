@@ -793,9 +793,10 @@ int gpfit_probe_mfma_f64(void* stream, double* scratch, int blocks, int iters);
 int gpfit_probe_stream_copy(void* stream, const double* in, double* out, int64_t n_doubles);
 
 /* ---- test hooks ----------------------------------------------------------------------
- * For the test-suite (tests/test_gemm_plans_cpu.py, tests/test_gpu_gemm_schedules.py, tests/test_gpu_potrf.py), not
- * for applications: the GEMM launcher with every field of its argument struct exposed, host-only queries of what it
- * would do with a launch, and the Cholesky recursion on the caller's buffers.  They add no arithmetic of their own. */
+ * For the test-suite (tests/test_gemm_plans_cpu.py, tests/test_gpu_gemm_schedules.py, tests/test_gpu_potrf.py,
+ * tests/test_gpu_elementwise.py), not for applications: the GEMM launcher with every field of its argument struct
+ * exposed, host-only queries of what it would do with a launch, the Cholesky recursion and the element-wise launchers
+ * on the caller's buffers.  They add no arithmetic of their own. */
 typedef struct gpfit_dev_gemm_args {
   const void* A;            /* device operands of element type double (is_f32 = 0) or float (1) */
   const void* B;
@@ -880,6 +881,92 @@ int gpfit_dev_ctx_fill(gpfit_ctx* ctx, const char* name, int byte);
  * stream.  The call only enqueues.  0, or -3 for a refused argument (nothing has touched the device then). */
 int gpfit_dev_potrf(gpfit_ctx* ctx, void* stream, int is_f32, int nb, void* const* A, void* const* L, void* const* Li,
                     void* const* Tmp, int* const* info, int64_t ld, int n, uint32_t need, uint32_t halves, int side_min);
+
+/* The launchers of the element-wise and reduction kernels (elementwise.hip; tests/test_gpu_elementwise.py), each on the
+ * caller's own device buffers.  One flat argument struct for all of them; the list below names, per op, what the slots
+ * p[], ld[], n[] and s[] hold, in the order of the launcher's own arguments.  "(opt)" marks a pointer that may be NULL.
+ * Element type: double, or float with is_f32 = 1 where the launcher is instantiated for it (marked f32); scratch and
+ * reduction outputs named double below are double in both.
+ *
+ *   TRMV_LOWER    f32  p: L x y                      ld: ldl        n: np
+ *   TRMV_LOWER_T  f32  p: L x z partial(double)      ld: ldl        n: np (a multiple of 64)
+ *   SYMV_LOWER         p: A x y                      ld: lda        n: n
+ *   GEMV_SUB      f32  p: M x y out                  ld: ldm        n: rows cols
+ *   GEMV_T_SUB    f32  p: M x y out partial(double)  ld: ldm        n: rows cols
+ *   DOT           f32  p: x y out(double)                           n: n
+ *   LOGDET        f32  p: L out(double)              ld: ldl        n: n
+ *   LOGDET_PAIR   f32  p: L0 out0 L1 out1            ld: ldl        n: n
+ *   FROB_LOWER    f32  p: T out(double) partial      ld: ldt        n: np (a multiple of 128)
+ *   FROB_TILES    f32  p: T partial(double)          ld: ldt        n: rows cols (multiples of 128) lower
+ *   REDUCE_SLICES f32  p: src dst                    ld: stride count   n: nslice dst_f32 (1, with is_f32 = 0: double
+ *                                                                       slices into a float dst)
+ *   REDUCE_SLABS  f32  p: src dst                    ld: stride     n: nslab slab_rows rows cols
+ *   REDUCE_SLICES_SYM f32  p: src dst                ld: stride     n: nslice n
+ *   PACK_LOWER    f32  p: src dst                    ld: lds ldd    n: n np (a multiple of 128)
+ *   PACK_TRI           p: src dst                    ld: lds ldd    n: n np
+ *   UNPACK_SYM         p: src dst                    ld: lds ldd    n: n
+ *   UNPACK_TRI         p: src dst                    ld: lds ldd    n: n
+ *   SYMMETRIZE    f32  p: A                          ld: lda        n: n
+ *   SYMMETRIZE_AVG     p: A                          ld: lda        n: n
+ *   PAD_COPY           p: src dst                    ld: lds ldd    n: rows cols prow pcol
+ *   GATHER        f32  p: X Xt pix(opt, int) Xm(opt) ld: ldx ldt ldm   n: n d dp np (dp, np multiples of 32)
+ *   ESTEP_BUILD        p: K sv Mb SK Kl              ld: ldk ld     n: n np (a multiple of 128)
+ *   ADD_DIAG      f32  p: A                          ld: lda        n: n            s: v
+ *   AXPBY_BLOCK   f32  p: dst src                    ld: ldd lds    n: rows cols (even)   s: a b
+ *   DEMOTE_BLOCK       p: src(double) dst(float)     ld: lds ldd    n: rows cols
+ *   QVEC          f32  p: Xt XCt Kvec q              ld: ld         n: n np dp      s: s0sq
+ *   MOMENTS       f32  p: Kvec q Cos V m r lam_m lam_var f wl scal(double) part(double) ticket(int)
+ *                                                    ld: ldc ldv    n: n            s: A lambda0
+ *   ADJOINT       f32  p: W Cos b q Aout upart vpart sumA_part (the last three double)
+ *                                                    ld: ld         n: n np (a multiple of 64)
+ *   ADJOINT_REDUCE f32 p: upart vpart sumA_part q wl tvec uq(double) scal_out(double)
+ *                                                                   n: n np ntile ntile_tri
+ *   ADJOINT_RECT       p: W Cos q1 q2 Aout upart vpart tile_sum t1 t2 uq1 uq2 scal3 extra1(opt)
+ *                                                    ld: ldw ldc lda   n: n1 n2 np1 np2 (multiples of 64)
+ *   METRIC_CONTRACT f32  p: pix(int) C M grad5(double) part(double) ticket(int)
+ *                                                    ld: ldc ldm    n: d n_rows n_cols     theta
+ *   DK_SIGMA0          p: Cos q1 q2 dK               ld: ldc ldk    n: n1 n2        s: s0
+ *   DQ                 p: Xt XDt q dq(opt) h(opt)    ld: ld         n: n dp
+ *   DK_METRIC          p: H Cos q1 q2 dq1 dq2        ld: ldh ldc    n: n1 n2
+ *   ESTEP_PREP         p: f r m sv rhs                              n: n np         s: A
+ *   ROWSCALE_ADD  f32  p: Y Xm t                     ld: ldy ldm    n: np dp        s: scale
+ *
+ * op + GPFIT_EW_GROUP is the unit-batched launcher of the same name (double only; TRMV_LOWER, TRMV_LOWER_T, SYMV_LOWER,
+ * DOT, LOGDET_PAIR, REDUCE_SLICES, PACK_LOWER, PACK_TRI, SYMMETRIZE, SYMMETRIZE_AVG, PAD_COPY, GATHER, ADD_DIAG, QVEC) for
+ * n_units units (1 .. 16).  The slots keep their meaning: up[k] is a HOST array of n_units DEVICE pointers in place of
+ * p[k]; where the launcher takes an extent, a leading dimension or a scalar per unit, un[k] / uld[k] / us[k] is a HOST
+ * array of n_units values in place of n[k] / ld[k] / s[k] (PACK_LOWER, PACK_TRI: n, lds; PAD_COPY: rows, cols, lds;
+ * GATHER: n, d, ldx, and Xm is not written; QVEC: n, s0sq; SYMMETRIZE_AVG, LOGDET_PAIR: n); everything else is common
+ * and comes from n[], ld[], s[].
+ *
+ * The hook fills the launcher's arguments and returns its return code; it adds no arithmetic.  theta: the launcher's
+ * Theta as its eight doubles (sigma_0, eps_0x, eps_0y, -2log2beta, -log2rho2, Amp, exp(-2log2beta), exp(-log2rho2)).
+ * -3 before any launch: an unknown op, an op without a float instance asked for one, a NULL among the pointers an op
+ * requires, an extent below 1, n_units outside 1 .. 16, or an extent that breaks the multiple stated above.  The call
+ * only enqueues. */
+enum {
+  GPFIT_EW_TRMV_LOWER = 0, GPFIT_EW_TRMV_LOWER_T, GPFIT_EW_SYMV_LOWER, GPFIT_EW_GEMV_SUB, GPFIT_EW_GEMV_T_SUB, GPFIT_EW_DOT,
+  GPFIT_EW_LOGDET, GPFIT_EW_LOGDET_PAIR, GPFIT_EW_FROB_LOWER, GPFIT_EW_FROB_TILES, GPFIT_EW_REDUCE_SLICES,
+  GPFIT_EW_REDUCE_SLABS, GPFIT_EW_REDUCE_SLICES_SYM, GPFIT_EW_PACK_LOWER, GPFIT_EW_PACK_TRI, GPFIT_EW_UNPACK_SYM,
+  GPFIT_EW_UNPACK_TRI, GPFIT_EW_SYMMETRIZE, GPFIT_EW_SYMMETRIZE_AVG, GPFIT_EW_PAD_COPY, GPFIT_EW_GATHER,
+  GPFIT_EW_ESTEP_BUILD, GPFIT_EW_ADD_DIAG, GPFIT_EW_AXPBY_BLOCK, GPFIT_EW_DEMOTE_BLOCK, GPFIT_EW_QVEC, GPFIT_EW_MOMENTS,
+  GPFIT_EW_ADJOINT, GPFIT_EW_ADJOINT_REDUCE, GPFIT_EW_ADJOINT_RECT, GPFIT_EW_METRIC_CONTRACT, GPFIT_EW_DK_SIGMA0,
+  GPFIT_EW_DQ, GPFIT_EW_DK_METRIC, GPFIT_EW_ESTEP_PREP, GPFIT_EW_ROWSCALE_ADD, GPFIT_EW_NOPS,
+  GPFIT_EW_GROUP = 256
+};
+typedef struct gpfit_dev_ew_args {
+  void* p[16];                /* device pointers */
+  int64_t ld[4];              /* leading dimensions, strides, 64-bit counts (elements) */
+  int32_t n[4];               /* sizes */
+  double s[2];                /* scalars */
+  double theta[8];
+  int32_t n_units;            /* group forms */
+  void* const* up[8];         /* HOST arrays of n_units device pointers */
+  const int64_t* uld[4];      /* HOST arrays of n_units values */
+  const int32_t* un[4];
+  const double* us[2];
+} gpfit_dev_ew_args;
+int gpfit_dev_elementwise(gpfit_ctx* ctx, void* stream, int op, int is_f32, const gpfit_dev_ew_args* args);
 
 #ifdef __cplusplus
 }
