@@ -46,6 +46,28 @@ EW_OP = {name: k for k, name in enumerate(EW_OPS)}
 EW_GROUP = 256
 
 
+class DevSkinnyArgs(ctypes.Structure):
+    """gpfit_dev_skinny_args: the fields of SkinnyArgs and SkinnySumArgs and the arguments of the finish launcher."""
+    _fields_ = [("A", vp), ("sam", i64), ("sar", i64), ("B", vp), ("sbr", i64), ("sbc", i64), ("O", vp), ("soz", i64),
+                ("som", i64), ("soc", i64), ("alpha", f64), ("M", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("kc", ctypes.c_int32), ("tri", ctypes.c_int32), ("P", vp), ("pz", i64), ("nslab", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("dst", vp), ("L", vp), ("ldl", i64), ("Li", vp), ("ldi", i64), ("Kc", vp),
+                ("ldk", i64), ("n", ctypes.c_int32), ("Lt", vp), ("Lit", vp), ("logdet", vp)]
+
+
+class DevProjArgs(ctypes.Structure):
+    """gpfit_dev_proj_args: the slots of gpfit_dev_projected."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_units", "n", "np", "nb", "nrows", "npc")] + [
+        ("ld", i64), ("lda", i64), ("A", f64), ("up", ctypes.POINTER(vp) * 13), ("uA", pd), ("ulambda0", pd),
+        ("un", ctypes.POINTER(ctypes.c_int32)), ("p", vp * 6)]
+
+
+# the op numbers of gpfit_dev_skinny and gpfit_dev_projected, in the order of the header's enums
+SKINNY_OP = {name: k for k, name in enumerate(("slabs", "sum", "finish"))}
+PROJ_OP = {name: k for k, name in enumerate(("moments", "ga", "gkb", "gktb", "trace", "estep_rows", "estep_scale",
+                                             "estep_moments"))}
+
+
 _SIGS = {
     "gpfit_version": (i32, []),
     "gpfit_last_error": (ctypes.c_char_p, []),
@@ -131,6 +153,8 @@ _SIGS = {
     "gpfit_dev_ctx_fill": (i32, [vp, ctypes.c_char_p, i32]),
     "gpfit_dev_potrf": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, i32, ctypes.c_uint32, ctypes.c_uint32, i32]),
     "gpfit_dev_elementwise": (i32, [vp, vp, i32, i32, ctypes.POINTER(DevEwArgs)]),
+    "gpfit_dev_skinny": (i32, [vp, vp, i32, ctypes.POINTER(DevSkinnyArgs)]),
+    "gpfit_dev_projected": (i32, [vp, vp, i32, ctypes.POINTER(DevProjArgs)]),
 }
 
 _lib = None

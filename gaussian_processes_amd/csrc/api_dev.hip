@@ -2,8 +2,9 @@
 // entry point that reaches every field of GemmArgsT (both element types, pointer batches, strided batches,
 // split-K, fused epilogues, the pair launch) -- and of the Cholesky recursion: potrf_lockstep on the caller's own
 // buffers with every argument exposed -- and of the element-wise and reduction launchers of elementwise.hip, one table
-// from an op number to the launcher.  No arithmetic happens here: the hooks fill the launcher's own argument
-// struct and read the launcher's own decision (gemm_route, common.h) and its planners.
+// from an op number to the launcher -- and of the launchers of skinny.hip and the ungated ones of projected.hip.  No
+// arithmetic happens here: the hooks fill the launcher's own argument struct and read the launcher's own decision
+// (gemm_route, common.h) and its planners.
 #include "gemm_core.h"
 #include "context.h"
 #include "gpfit_mi355x.h"
@@ -376,10 +377,141 @@ bool ew_valid(int op, int is_f32, const gpfit_dev_ew_args& a) {
   return ew_multiples(base, a.n);   // the extents with a stated multiple are common to the units
 }
 
+// ---- the launchers of skinny.hip (gpfit_dev_skinny): the hook's struct into SkinnyArgs / SkinnySumArgs, field by field
+bool skinny_valid(int op, const gpfit_dev_skinny_args& d) {
+  if (d.kc < 1 || d.kc > SKINNY_LD) return false;
+  switch (op) {
+    case GPFIT_SKINNY_SLABS: return d.A && d.B && d.O && d.M >= 1 && d.K >= 1 && d.tri >= 0 && d.tri <= 2;
+    case GPFIT_SKINNY_SUM:
+      if (!d.P || !d.dst || d.M < 1 || d.nslab < 1 || d.tri < 0 || d.tri > 2) return false;
+      if (d.mode == SKINNY_SUM_PLAIN) return true;
+      if (d.mode == SKINNY_SUM_ROWS) return d.L && d.Li && d.n >= 1;
+      if (d.mode == SKINNY_SUM_SCHUR) return d.Kc && d.n >= 1;
+      return false;
+    case GPFIT_SKINNY_FINISH: return d.Lt && d.Lit && d.L && d.Li && d.logdet && d.n >= 1;
+    default: return false;
+  }
+}
+
+int skinny_run(hipStream_t s, int op, const gpfit_dev_skinny_args& d) {
+  if (op == GPFIT_SKINNY_SLABS) {
+    SkinnyArgs g{};
+    g.A = d.A; g.sam = d.sam; g.sar = d.sar;
+    g.B = d.B; g.sbr = d.sbr; g.sbc = d.sbc;
+    g.O = d.O; g.soz = d.soz; g.som = d.som; g.soc = d.soc;
+    g.alpha = d.alpha;
+    g.M = d.M; g.K = d.K; g.kc = d.kc; g.tri = d.tri;
+    return launch_skinny_slabs(g, s);
+  }
+  if (op == GPFIT_SKINNY_SUM) {
+    SkinnySumArgs r{};
+    r.P = d.P; r.pz = d.pz;
+    r.M = d.M; r.kc = d.kc; r.nslab = d.nslab; r.tri = d.tri; r.mode = d.mode;
+    r.dst = d.dst;
+    r.L = d.L; r.ldl = d.ldl; r.Li = d.Li; r.ldi = d.ldi; r.n = d.n;
+    r.Kc = d.Kc; r.ldk = d.ldk;
+    return launch_skinny_sum(r, s);
+  }
+  return launch_append_block_finish(d.Lt, d.Lit, d.L, d.ldl, d.Li, d.ldi, d.n, d.kc, d.logdet, s);
+}
+
+// ---- the ungated launchers of projected.hip (gpfit_dev_projected): the host tables copied into ProjGroupT / PerUnit<>
+// how many of up[] (group ops) or p[] (single launchers) an op requires; p[4] of ESTEP_SCALE (aLp) may be NULL
+constexpr int PROJ_NPTR[GPFIT_PROJ_NOPS] = {13, 6, 3, 5, 2, 6, 6, 5};
+
+bool proj_valid(int op, const gpfit_dev_proj_args& d) {
+  if (op < 0 || op >= GPFIT_PROJ_NOPS) return false;
+  if (op >= GPFIT_PROJ_ESTEP_ROWS) {
+    for (int k = 0; k < PROJ_NPTR[op]; ++k)
+      if (!d.p[k] && !(op == GPFIT_PROJ_ESTEP_SCALE && k == 4)) return false;
+    if (d.n < 1 || d.nb < 1) return false;
+    if (op == GPFIT_PROJ_ESTEP_MOMENTS) return d.ld >= d.nb;
+    if (d.nrows < d.n || d.nrows % 32 != 0 || d.lda < d.nb) return false;
+    return op == GPFIT_PROJ_ESTEP_ROWS || (d.npc >= 1 && d.ld >= d.npc);
+  }
+  if (d.n_units < 1 || d.n_units > CHAIN_MAXU) return false;
+  for (int k = 0; k < PROJ_NPTR[op]; ++k) {
+    if (!d.up[k]) return false;
+    for (int u = 0; u < d.n_units; ++u) if (!d.up[k][u]) return false;
+  }
+  if (op == GPFIT_PROJ_TRACE) {
+    if (!d.un || d.ld < 1) return false;
+    for (int u = 0; u < d.n_units; ++u) if (d.un[u] < 1) return false;
+    return true;
+  }
+  if (d.nb < 1 || d.ld < d.nb) return false;
+  if (op == GPFIT_PROJ_GKTB) return true;
+  if (d.n < 1) return false;
+  if (op == GPFIT_PROJ_MOMENTS) return d.uA && d.ulambda0;
+  return d.np >= d.n;
+}
+
+template <typename T>
+PerUnit<T> proj_ptrs(const gpfit_dev_proj_args& d, int k) {
+  PerUnit<T> r{};
+  for (int u = 0; u < d.n_units; ++u) r.v[u] = (T)d.up[k][u];
+  return r;
+}
+
+int proj_run(hipStream_t s, int op, const gpfit_dev_proj_args& d) {
+  auto in = [&](int k) { return (const double*)d.p[k]; };
+  auto out = [&](int k) { return (double*)d.p[k]; };
+  auto up = [&](int k) { return proj_ptrs<double*>(d, k); };
+  switch (op) {
+    case GPFIT_PROJ_ESTEP_ROWS:
+      return launch_estep_proj_rows(in(0), d.lda, d.nb, in(1), in(2), in(3), d.n, d.nrows, d.A, out(4), out(5), s);
+    case GPFIT_PROJ_ESTEP_SCALE:
+      return launch_estep_proj_scale(in(0), d.lda, d.nb, d.n, d.nrows, in(1), in(2), out(3), out(4), d.ld, d.npc, out(5), s);
+    case GPFIT_PROJ_ESTEP_MOMENTS: return launch_estep_proj_moments(in(0), d.ld, d.nb, in(1), in(2), d.n, out(3), out(4), s);
+    case GPFIT_PROJ_TRACE: {
+      PerUnit<int> n{};
+      for (int u = 0; u < d.n_units; ++u) n.v[u] = d.un[u];
+      return launch_proj_trace_group(d.n_units, up(0), d.ld, n, up(1), s);
+    }
+    default: break;
+  }
+  ProjGroupT g{};
+  g.n_units = d.n_units; g.n = d.n; g.np = d.np; g.nb = d.nb; g.ld = d.ld;
+  switch (op) {
+    case GPFIT_PROJ_MOMENTS:
+      g.am = up(0); g.Kb = up(1); g.aV = up(2); g.mb = up(3); g.Kvec = up(4); g.r = proj_ptrs<const double*>(d, 5);
+      g.lam_m = up(6); g.lam_var = up(7); g.f = up(8); g.gm = up(9); g.gv = up(10); g.part = up(11); g.out3 = up(12);
+      for (int u = 0; u < d.n_units; ++u) { g.A.v[u] = d.uA[u]; g.lambda0.v[u] = d.ulambda0[u]; }
+      return launch_proj_moments_group(g, s);
+    case GPFIT_PROJ_GA:
+      g.Kb = up(0); g.aV = up(1); g.gm = up(2); g.gv = up(3); g.mb = up(4); g.Ga = up(5);
+      return launch_proj_ga_group(g, s);
+    case GPFIT_PROJ_GKB:
+      g.am = up(0); g.gv = up(1); g.GaKi = up(2);
+      return launch_proj_gkb_group(g, s);
+    default:
+      g.Ki = up(0); g.P1 = up(1); g.P2 = up(2); g.bvec = up(3); g.G = up(4);
+      return launch_proj_gktb_group(g, s);
+  }
+}
+
 }  // namespace
 }  // namespace gpfit
 
 extern "C" {
+
+int gpfit_dev_skinny(gpfit_ctx* ctx, void* stream, int op, const gpfit_dev_skinny_args* args) {
+  if (!ctx || !args || !gpfit::skinny_valid(op, *args)) {
+    gpfit::set_error("gpfit_dev_skinny: bad argument");
+    return -3;
+  }
+  GP_CTX_ENTER(ctx, "gpfit_dev_skinny");
+  return gpfit::skinny_run((hipStream_t)stream, op, *args);
+}
+
+int gpfit_dev_projected(gpfit_ctx* ctx, void* stream, int op, const gpfit_dev_proj_args* args) {
+  if (!ctx || !args || !gpfit::proj_valid(op, *args)) {
+    gpfit::set_error("gpfit_dev_projected: bad argument");
+    return -3;
+  }
+  GP_CTX_ENTER(ctx, "gpfit_dev_projected");
+  return gpfit::proj_run((hipStream_t)stream, op, *args);
+}
 
 int gpfit_dev_elementwise(gpfit_ctx* ctx, void* stream, int op, int is_f32, const gpfit_dev_ew_args* args) {
   if (!ctx || !args || !gpfit::ew_valid(op, is_f32, *args)) {

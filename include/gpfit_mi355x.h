@@ -968,6 +968,71 @@ typedef struct gpfit_dev_ew_args {
 } gpfit_dev_ew_args;
 int gpfit_dev_elementwise(gpfit_ctx* ctx, void* stream, int op, int is_f32, const gpfit_dev_ew_args* args);
 
+/* The three launchers of skinny.hip (the slab products, their sums and the finish pass of gpfit_potrf_append_block;
+ * tests/test_gpu_skinny.py), each on the caller's own device buffers.  The struct carries the fields of the launchers'
+ * own argument structs under their own names (kernels.h: SkinnyArgs, SkinnySumArgs; M, kc and tri are common to the
+ * two) and the arguments of the finish launcher (Lt, Lit, logdet, with L, ldl, Li, ldi, n of the sum and k = kc):
+ *
+ *   SLABS   A sam sar  B sbr sbc  O soz som soc  alpha  M K kc tri
+ *   SUM     P pz  M kc nslab tri mode  dst;  mode ROWS (1): L ldl Li ldi n;  mode SCHUR (2): Kc ldk n
+ *   FINISH  Lt Lit  L ldl Li ldi  n kc  logdet
+ *
+ * The hook fills the launcher's arguments and returns its return code; it adds no arithmetic.  -3 before any launch: an
+ * unknown op, a NULL among the pointers the op (and its mode) reads or writes, M, K, nslab or n below 1, kc outside
+ * 1 .. 128, tri outside 0 .. 2, a mode outside 0 .. 2.  The call only enqueues. */
+enum { GPFIT_SKINNY_SLABS = 0, GPFIT_SKINNY_SUM, GPFIT_SKINNY_FINISH, GPFIT_SKINNY_NOPS };
+typedef struct gpfit_dev_skinny_args {
+  const double* A; int64_t sam, sar;
+  const double* B; int64_t sbr, sbc;
+  double* O; int64_t soz, som, soc;
+  double alpha;
+  int32_t M, K, kc, tri;
+  const double* P; int64_t pz;
+  int32_t nslab, mode;
+  double* dst;
+  double* L; int64_t ldl;
+  double* Li; int64_t ldi;
+  const double* Kc; int64_t ldk;
+  int32_t n;
+  const double* Lt; const double* Lit;
+  double* logdet;
+} gpfit_dev_skinny_args;
+int gpfit_dev_skinny(gpfit_ctx* ctx, void* stream, int op, const gpfit_dev_skinny_args* args);
+
+/* The launchers of projected.hip that run behind no chain gate (tests/test_gpu_projected.py), each on the caller's own
+ * device buffers.  The five passes of the projected closures are unit-batched: up[k] is a HOST array of n_units
+ * (1 .. 16) DEVICE pointers, uA / ulambda0 / un HOST arrays of n_units values, copied into ProjGroupT / PerUnit<>; the
+ * three passes of the projected E-step are the single launchers on p[].  Slots, in the order below:
+ *
+ *   MOMENTS        up: am Kb aV mb Kvec r lam_m lam_var f gm gv part out3     n nb ld   uA ulambda0   (with its sum3)
+ *   GA             up: Kb aV gm gv mb Ga                                      n np nb ld
+ *   GKB            up: am gv GaKi                                             n np nb ld
+ *   GKTB           up: Ki P1 P2 bvec G                                        nb ld
+ *   TRACE          up: A out                                                  ld (of A)   un (n per unit)
+ *   ESTEP_ROWS     p: a mb f r sv u                                           lda nb n nrows   A
+ *   ESTEP_SCALE    p: aL sv u Y aLp(opt) part                                 lda (of aL) ld nb n nrows npc
+ *   ESTEP_MOMENTS  p: Z z1 kv0 lam_m lam_var                                  ld nb n
+ *
+ * The hook fills the launcher's arguments and returns its return code; it adds no arithmetic.  -3 before any launch: an
+ * unknown op, n_units outside 1 .. 16, a NULL among the tables or pointers the op requires (aLp may be NULL), an extent
+ * below 1, np or nrows below n, nrows no multiple of 32, a leading dimension below its width.  The call only
+ * enqueues. */
+enum {
+  GPFIT_PROJ_MOMENTS = 0, GPFIT_PROJ_GA, GPFIT_PROJ_GKB, GPFIT_PROJ_GKTB, GPFIT_PROJ_TRACE, GPFIT_PROJ_ESTEP_ROWS,
+  GPFIT_PROJ_ESTEP_SCALE, GPFIT_PROJ_ESTEP_MOMENTS, GPFIT_PROJ_NOPS
+};
+typedef struct gpfit_dev_proj_args {
+  int32_t n_units, n, np, nb, nrows, npc;
+  int64_t ld, lda;
+  double A;
+  void* const* up[13];        /* HOST arrays of n_units device pointers */
+  const double* uA;           /* HOST arrays of n_units values */
+  const double* ulambda0;
+  const int32_t* un;
+  void* p[6];                 /* device pointers of the single launchers */
+} gpfit_dev_proj_args;
+int gpfit_dev_projected(gpfit_ctx* ctx, void* stream, int op, const gpfit_dev_proj_args* args);
+
 #ifdef __cplusplus
 }
 #endif

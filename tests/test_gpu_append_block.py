@@ -160,6 +160,38 @@ def test_block_append_reports_the_pivot_in_the_grown_matrix(gp):
     check_against_reference(c, L, Li, logdet, rows=n0 + 128)
 
 
+def test_nothing_above_the_diagonal_of_the_factors_is_read(gp):
+    """(g) (257, 17): with NaN in the strict upper triangle of the leading n0 x n0 blocks of both factors, the block call
+    and the rank-1 call return, on and below the diagonal, the bits they return with zeros there -- the claim of
+    skinny.hip's header ("what lies beyond the diagonal is never used") and what the rank-1 path's two triangular
+    matrix-vector kernels index."""
+    c = randn_case(257, 17)
+    n0, k, S = c["n0"], c["k"], c["S"]
+    above = torch.triu(torch.ones((n0, n0), dtype=torch.bool, device="cuda"), 1)
+    bits = lambda X: torch.tril(X).view(torch.int64)
+
+    def start(rows, fill):
+        L, Li = embedded(c)
+        L[:n0, :n0][above] = fill
+        Li[:n0, :n0][above] = fill
+        return L[:rows, :rows].contiguous(), Li[:rows, :rows].contiguous()
+
+    out = {}
+    for fill in (0.0, float("nan")):
+        L, Li = start(n0 + k, fill)
+        logdet, info = gp.cholesky_append_block(L, Li, S[:, n0:].contiguous(), c["logdet0"])
+        assert info == 0
+        L1, Li1 = start(n0 + 1, fill)
+        logdet1, info = gp.cholesky_append(L1, Li1, S[:n0 + 1, n0].contiguous(), c["logdet0"])
+        assert info == 0
+        out[fill == 0.0] = (bits(L), bits(Li), logdet, bits(L1), bits(Li1), logdet1)
+    zeros, nans = out[True], out[False]
+    for a, b in zip(zeros, nans):
+        assert torch.equal(a, b) if isinstance(a, torch.Tensor) else a == b
+    assert not bool(torch.isnan(torch.tril(L)).any()) and not bool(torch.isnan(torch.tril(Li)).any())
+    check_against_reference(c, torch.tril(L), torch.tril(Li), logdet)
+
+
 # ---------------------------------------------------------------- (f) extend_inducing_set on fixture g9
 def quiet():
     stack = contextlib.ExitStack()
