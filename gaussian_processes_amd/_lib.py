@@ -151,6 +151,7 @@ _SIGS = {
     "gpfit_dev_gemm": (i32, [vp, i32, ctypes.POINTER(DevGemmArgs), ctypes.POINTER(DevGemmArgs)]),
     "gpfit_dev_ctx_copy": (i32, [vp, ctypes.c_char_p, i64, vp, i64, i32]),
     "gpfit_dev_ctx_fill": (i32, [vp, ctypes.c_char_p, i32]),
+    "gpfit_dev_ctx_buffer_name": (i32, [i32, ctypes.c_char_p, i32]),
     "gpfit_dev_potrf": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, i32, ctypes.c_uint32, ctypes.c_uint32, i32]),
     "gpfit_dev_elementwise": (i32, [vp, vp, i32, i32, ctypes.POINTER(DevEwArgs)]),
     "gpfit_dev_skinny": (i32, [vp, vp, i32, ctypes.POINTER(DevSkinnyArgs)]),

@@ -156,18 +156,43 @@ int run(hipStream_t s, const gpfit_dev_gemm_args& d, const gpfit_dev_gemm_args* 
   return d2 ? launch_gemm_pair(a, b, gemm_pair_shape(a, b), s) : launch_gemm(a, s);
 }
 
-// a work buffer of the context by name, with its size in bytes
-struct CtxBuf { void* p; int64_t bytes; };
+// The one table of the floating-point device work buffers of a context: every one gpfit_ctx_create allocates, by the
+// member's name (the stream-K workspaces as sk_ws[0] and sk_ws[1]), with the byte size of that allocation.  A test fills
+// them (gpfit_dev_ctx_fill) to show that no entry point reads what an earlier call left behind.  Deliberately absent:
+//   pix          -- pixel indices: a stale one is an address, and a test that filled it could cause a wild read; the
+//                   tests built on this table must not be able to provoke a fault
+//   info         -- words 2 and 3 are tickets whose contract is "0 between calls" (INFO_MOMENTS, INFO_METRIC)
+//   chain        -- the ChainBlock holds step counters and flags beside its numbers
+//   scal_host, pix_host, info_host, chain_host -- pinned host memory, written by the host as well
+// (tests/test_context_cases_cpu.py holds this table against the members of gpfit_ctx.)
+struct CtxBuf { const char* name; void* p; int64_t bytes; };
+std::vector<CtxBuf> ctx_buffers(gpfit_ctx* c) {
+  const int64_t np = c->np_cap, dp = c->dp_cap, nn = np * np * 8, nd = np * dp * 8, dd = dp * dp * 8, v = np * 8;
+  const int64_t t64 = np / 64, t128 = np / TILE;
+  return {
+      // N x N work matrices
+      {"Kbuf", c->Kbuf, nn}, {"Cos", c->Cos, nn}, {"Lbuf", c->Lbuf, nn}, {"Libuf", c->Libuf, nn}, {"Vbuf", c->Vbuf, nn},
+      {"LVbuf", c->LVbuf, nn}, {"LiVbuf", c->LiVbuf, nn}, {"Tbuf", c->Tbuf, nn}, {"Zbuf", c->Zbuf, nn}, {"Wbuf", c->Wbuf, nn},
+      {"Abuf", c->Abuf, nn}, {"Tmp", c->Tmp, nn}, {"TmpV", c->TmpV, nn},
+      // N x d / d x d
+      {"Xt", c->Xt, nd}, {"Xm", c->Xm, nd}, {"XCt", c->XCt, nd}, {"Cmat", c->Cmat, dd}, {"Ybuf", c->Ybuf, nd},
+      {"Mpart", c->Mpart, (int64_t)c->split_k_M * dd}, {"Mmat", c->Mmat, dd}, {"Xt2", c->Xt2, nd}, {"XCt2", c->XCt2, nd},
+      {"XDt", c->XDt, nd}, {"XDt2", c->XDt2, nd}, {"dCpad", c->dCpad, dd},
+      // vectors
+      {"Kvec", c->Kvec, v}, {"q", c->q, v}, {"lam_m", c->lam_m, v}, {"lam_var", c->lam_var, v}, {"fvec", c->fvec, v},
+      {"wl", c->wl, v}, {"yv", c->yv, v}, {"bv", c->bv, v}, {"tvec", c->tvec, 2 * v}, {"mpad", c->mpad, v}, {"rpad", c->rpad, v},
+      {"q2", c->q2, v}, {"dq1", c->dq1, v}, {"dq2", c->dq2, v}, {"hvec", c->hvec, v},
+      // partial sums
+      {"upart", c->upart, t64 * v}, {"vpart", c->vpart, t64 * v}, {"sumA_part", c->sumA_part, t64 * (t64 + 1) / 2 * 8},
+      {"frob_part", c->frob_part, 33 * t128 * (t128 + 1) / 2 * 8}, {"trmv_part", c->trmv_part, (np / TRMV_ROWS + 1) * v},
+      {"rect_part", c->rect_part, t64 * t64 * 8},
+      // device scalars and the stream-K workspaces
+      {"scal", c->scal, 64 * 8}, {"sk_ws[0]", c->sk_ws[0], (int64_t)SK_WS_BYTES}, {"sk_ws[1]", c->sk_ws[1], (int64_t)SK_WS_BYTES}};
+}
 CtxBuf ctx_buffer(gpfit_ctx* c, const char* name) {
-  const int64_t np = c->np_cap, dp = c->dp_cap, nn = np * np * 8;
-  const struct { const char* n; double* p; int64_t bytes; } tab[] = {
-      {"Abuf", c->Abuf, nn}, {"Tbuf", c->Tbuf, nn}, {"Wbuf", c->Wbuf, nn}, {"Zbuf", c->Zbuf, nn}, {"Cos", c->Cos, nn},
-      {"TmpV", c->TmpV, nn}, {"Tmp", c->Tmp, nn}, {"Kbuf", c->Kbuf, nn}, {"Xm", c->Xm, np * dp * 8}, {"Xt2", c->Xt2, np * dp * 8}, {"Ybuf", c->Ybuf, np * dp * 8},
-      {"Mmat", c->Mmat, dp * dp * 8}, {"Cmat", c->Cmat, dp * dp * 8}, {"tvec", c->tvec, 2 * np * 8}, {"bv", c->bv, np * 8},
-      {"q", c->q, np * 8}, {"wl", c->wl, np * 8}, {"q2", c->q2, np * 8}, {"dq1", c->dq1, np * 8}, {"dq2", c->dq2, np * 8}};
-  for (const auto& t : tab)
-    if (std::strcmp(t.n, name) == 0) return {t.p, t.bytes};
-  return {nullptr, 0};
+  for (const CtxBuf& t : ctx_buffers(c))
+    if (std::strcmp(t.name, name) == 0) return t;
+  return {nullptr, nullptr, 0};
 }
 
 // potrf_lockstep on the caller's buffers: nothing but the batch struct is filled here
@@ -572,6 +597,15 @@ int gpfit_dev_ctx_copy(gpfit_ctx* ctx, const char* name, int64_t offset, void* d
   char* w = (char*)b.p + offset;
   GP_HIP(hipMemcpy(to_ctx ? (void*)w : dev, to_ctx ? dev : (void*)w, (size_t)bytes, hipMemcpyDeviceToDevice));
   GP_HIP(hipDeviceSynchronize());
+  return 0;
+}
+
+int gpfit_dev_ctx_buffer_name(int index, char* out, int cap) {
+  // the names do not depend on the context: the table of an empty one has them all
+  gpfit_ctx none;
+  const std::vector<gpfit::CtxBuf> tab = gpfit::ctx_buffers(&none);
+  if (index < 0 || index >= (int)tab.size() || !out || cap <= (int)std::strlen(tab[index].name)) return -3;
+  std::strcpy(out, tab[index].name);
   return 0;
 }
 

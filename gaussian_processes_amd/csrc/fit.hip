@@ -1820,6 +1820,11 @@ static int fit_eval_sparse_group_impl(const char* name, gpfit_ctx* const* cs, in
     g.ld1 = np1; g.ld2 = l2; g.ldk = l2; g.np1 = np1; g.np2 = np2; g.nv1 = n1; g.nv2 = n2; g.Kd = dp;
     g.s0sq = s0sq; g.lower = 0; g.pad_identity = 0;
     g.ldcos = l2;
+    // The Gram kernel leaves K's padding alone, and the projection K B below runs over all np2 columns (against the zero
+    // rows of the padded B) and all np1 rows: what an earlier call left there must not reach it -- a stale NaN times
+    // zero is NaN.  (On a fresh context the padding already reads zero: the same bits.)
+    if (np2 > n2) GP_HIP(hipMemset2DAsync(c->Lbuf + n2, (size_t)l2 * sizeof(R), 0, (size_t)(np2 - n2) * sizeof(R), (size_t)n1, s));
+    if (np1 > n1) GP_HIP(hipMemsetAsync(c->Lbuf + (int64_t)n1 * l2, 0, (size_t)(np1 - n1) * l2 * sizeof(R), s));
     ProfScope ps(s, 2.0 * np1 * np2 * dp, 2);
     GP_TRY(launch_gram(g, s));
   }

@@ -863,11 +863,16 @@ int gpfit_dev_gemm_route(int is_f32, const gpfit_dev_gemm_args* args, const gpfi
 int64_t gpfit_dev_gemm_plan(int is_f32, const gpfit_dev_gemm_args* args, int kind, int32_t* out, int64_t cap);
 /* launch_gemm on these arguments, or launch_gemm_pair when pair_args is given.  Return value as gpfit_dgemm. */
 int gpfit_dev_gemm(void* stream, int is_f32, const gpfit_dev_gemm_args* args, const gpfit_dev_gemm_args* pair_args);
-/* A context's work buffer by its name in the sources ("Abuf", "Tbuf", "Wbuf", "Zbuf", "Cos", "TmpV", "Xm", "Xt2", "Ybuf",
- * "Mmat", "Cmat", "tvec", "bv", "q", "wl", "q2", "dq1", "dq2"): copy `bytes` bytes at byte `offset` to (to_ctx = 0) or
- * from (1) the device pointer `dev`, or fill the whole buffer with one byte value.  Synchronous.  0, or -3. */
+/* A context's work buffer by its name in the sources -- every floating-point device work buffer of the context: the
+ * matrices ("Abuf", "LVbuf", ...), the N x d and d x d blocks, the vectors, the partial arrays, "scal", and the two
+ * stream-K workspaces "sk_ws[0]" and "sk_ws[1]"; not the integer buffers, the chain block or pinned host memory: copy
+ * `bytes` bytes at byte `offset` to (to_ctx = 0) or from (1) the device pointer `dev`, or fill the whole buffer (the
+ * size of its allocation) with one byte value.  Synchronous.  0, or -3 (also while an evaluation is pending). */
 int gpfit_dev_ctx_copy(gpfit_ctx* ctx, const char* name, int64_t offset, void* dev, int64_t bytes, int to_ctx);
 int gpfit_dev_ctx_fill(gpfit_ctx* ctx, const char* name, int byte);
+/* The names those two calls know, by index from 0: writes the NUL-terminated name into out[cap] and returns 0; -3 past
+ * the end of the table (or when the name does not fit).  Needs no context and no GPU. */
+int gpfit_dev_ctx_buffer_name(int index, char* out, int cap);
 /* The Cholesky recursion behind gpfit_potrf and every closure (tests/test_gpu_potrf.py), on the caller's own device
  * buffers: nb chains (1 .. 32) of n x n matrices, n a multiple of 128, element type double (is_f32 = 0) or float (1), all
  * with leading dimension ld (elements; >= n, a multiple of 16 bytes).  A, L, Li, Tmp, info: HOST arrays of nb DEVICE
