@@ -2129,10 +2129,14 @@ def _stabilised_basis(K_tilde, route=None, start=None):
     N >= 256, the kept eigenspace comes from ``eigtop`` (block subspace iteration from N = 1792, the spectral projector of K~
     itself below) and the
     first return value holds only those columns; otherwise, and whenever that solver declines, the
-    reference's own eigendecomposition + truncation.  Every route is a deterministic function of K~, so
-    ``test(at_iteration=...)`` rebuilds the basis the tracked ``(m_b, V_b)`` were expressed in.
+    reference's own eigendecomposition + truncation.  A COLD call (no ``start``) is a deterministic function of K~
+    alone on every route, so ``test(at_iteration=...)`` rebuilds a basis of the space the tracked ``(m_b, V_b)`` were
+    expressed in; a WARM call (``start`` given) agrees with the cold one to the certificate, not to the bit: the same
+    count (lambda_max, so the threshold, is certified to 1e-8 relative on both, or the route declines) and the same
+    stopping criterion of the sweeps (angle bound 1e-7), so nearly the same kept space and canonical basis -- the
+    warm-start tests hold the two bases within 1e-5 of each other, entry by entry.
 
-    The route taken (``'identity'``, ``'eigtop'`` or ``'eigh'``) is left in ``_BASIS.route`` (per host thread);
+    The route taken (``'identity'``, ``'subspace'``, ``'eigtop'`` or ``'eigh'``) is left in ``_BASIS.route`` (per host thread);
     ``varGP`` records it with every tracked iteration.  ``route=...`` asks for exactly that route -- what
     ``test(at_iteration=...)`` does with the recorded one, so that a model fitted under one setting
     (``GPFIT_FORCE_EIGH``, another library version) is never evaluated in a different basis: a route that
